@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mrays/s of the render hot path at 2400x1800 on the ~1M-tet synthetic grid.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, roofline).
+--full adds every figure that takes runs of its own: the CPU baselines, frames delivered to host memory, the C++ host
+(`course --bench`) and, for N > 1, the one-GPU time of the same frame and BASELINE configs 4 and 5.
+--dump-outputs DIR writes the frame of the last timed step (rank 0's whole image) as DIR/image.npy, float32.
 
 A step = one frame through the whole hot path on data already resident in HBM: view transform ->
 per-cell records -> boundary entry raster -> walk_composite -> fp32 image in device memory
@@ -20,7 +25,7 @@ roofline    of the dominant kernel walk_composite, every fraction <= 1 by constr
               contract                 SURVEY.md section 8(d)'s algorithmic figure (S * 144 B + P * 8 B) / duration —
                                        NOT a fraction of anything: the 128 MB of per-view records are re-read
                                        from L2 / Infinity Cache ~130 times per ray, so it exceeds the HBM peak.
-cpu_baseline  the CPU oracle (own restatement of the reference algorithm, OpenMP) timed on this box's
+cpu_baseline  (--full) the CPU oracle (own restatement of the reference algorithm, OpenMP) timed on this box's
             host cores on the SAME workload at the SAME image size (rank 0, N = 1 only).  It is the checker
             being timed as a baseline, never the product path.
 """
@@ -49,6 +54,7 @@ B_SEG_RECORD = 128           # what walk_composite actually reads per step: one 
 B_PIX = 8                    # 2 x fp32 store per pixel
 TILE_ROWS = 16
 ROOFLINE_FILE = os.path.join(ROOT, "profiles", "roofline.json")  # written by scripts/summarize_profile.py
+DUMP_BUDGET = 64 * 10**6     # bytes --dump-outputs may write in all
 
 
 def parse():
@@ -56,6 +62,12 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=1000)
     p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what lies beyond the headline (CPU baselines, frames delivered to host memory, the C++ host; "
+                        "N > 1: the one-GPU time of the same frame, BASELINE configs 4 and 5); the --no-* options skip single ones")
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="write what the last timed step computed (the image rank 0 receives, float32) to DIR/image.npy; a frame "
+                        f"larger than {DUMP_BUDGET // 10**6} MB is written as a fixed, seeded sample of its pixels")
     p.add_argument("--workload", default="c3", help="c3 (998 250 tets, default), c2, kuhnN")
     p.add_argument("--res", default="2400x1800", help="image size of the N = 1 workload")
     p.add_argument("--scaling", choices=["weak", "strong"], default="strong",
@@ -93,7 +105,10 @@ def parse():
     p.add_argument("--row-base-cost", type=float, default=3.0,
                    help="blocks: fixed cost per pixel in segment units added when balancing (measured: an empty "
                         "pixel costs about six segments)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def usable_cpus() -> int:
@@ -106,6 +121,22 @@ def usable_cpus() -> int:
     except (OSError, ValueError):
         pass
     return n
+
+
+def dump_outputs(directory, image):
+    """--dump-outputs: the frame of the last timed step as a caller of the render path receives it ([rows][columns][2]
+    float32: optical depth, intensity) -> DIR/image.npy.  A frame over the budget is sampled at fixed pixels (seed 0):
+    their values -> image_sample.npy [n][2], their row-major pixel indices -> image_sample_pixels.npy (float64)."""
+    os.makedirs(directory, exist_ok=True)
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    if image.nbytes <= DUMP_BUDGET:
+        np.save(os.path.join(directory, "image.npy"), image)
+        return
+    flat = image.reshape(-1, image.shape[-1])
+    n = (DUMP_BUDGET - 2 * 4096) // (flat.shape[1] * 4 + 8)  # (4096: room for the two .npy headers)
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=n, replace=False))
+    np.save(os.path.join(directory, "image_sample.npy"), flat[idx])
+    np.save(os.path.join(directory, "image_sample_pixels.npy"), idx.astype(np.float64))
 
 
 def cpu_baseline(xyz, cells, alpha, q, rots, res):
@@ -391,9 +422,10 @@ def main():
         ctx.set_option("stage_timing", 0)
         return blocks
 
-    def measure(rx, ry, steps, warmup, split, steadying):
+    def measure(rx, ry, steps, warmup, split, steadying, keep_frame=False):
         """W warm-up frames (+ clock-steadying batches), then exactly `steps` frames between barriers +
-        torch.cuda.synchronize() on both sides; a C5_RETRY inside the region re-times it."""
+        torch.cuda.synchronize() on both sides; a C5_RETRY inside the region re-times it.  keep_frame: also return
+        the frame of the last timed step in host memory (rank 0: the whole image)."""
         with torch.cuda.stream(stream):
             blocks = lay_out_rows(rx, ry, split)
             n_local = ctx.local_rows
@@ -477,6 +509,7 @@ def main():
                 raise SystemExit("frames kept being re-rendered inside the timed region")
             ctx.set_option("walk_timing", 1)
             retries += pipe.retries
+            frame = pipe.frame.cpu().numpy() if keep_frame and pipe.frame is not None else None
         el = torch.tensor([elapsed], dtype=torch.float64, device=rdev)
         seg = torch.tensor([stats["segments"], n_local * rx, retries], dtype=torch.int64, device=rdev)
         if world > 1:
@@ -485,7 +518,7 @@ def main():
         S_total, P_total, retries_total = (int(v) for v in seg.tolist())
         return {"elapsed": float(el.item()), "steps": steps, "blocks": blocks, "n_local": n_local, "stats": stats,
                 "walk_ms": walk_ms, "walk_launches": walk_launches, "steady": steady, "S_total": S_total, "P_total": P_total,
-                "retries": retries_total}
+                "retries": retries_total, "frame": frame}
 
     def one_gpu_reference(rx, ry, frames):
         """Rank 0 renders the WHOLE rx x ry frame alone, the other ranks wait on the host: the N = 1 time of the very
@@ -516,15 +549,17 @@ def main():
         return ms
 
     sharded = world > 1 and not frame_parallel
-    head = measure(res_x, res_y, args.steps, args.warmup, sharded, not args.no_steady)
+    head = measure(res_x, res_y, args.steps, args.warmup, sharded, not args.no_steady, keep_frame=bool(args.dump_outputs) and rank == 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head.pop("frame"))
     elapsed, stats, blocks, n_local = head["elapsed"], head["stats"], head["blocks"], head["n_local"]
     walk_ms, walk_launches, steady, retries_total = head["walk_ms"], head["walk_launches"], head["steady"], head["retries"]
     S_total, P_total = head["S_total"], head["P_total"]
     k_ref = max(10, min(args.steps, 200))
-    head_one_gpu_ms = one_gpu_reference(res_x, res_y, k_ref) if sharded else None
+    head_one_gpu_ms = one_gpu_reference(res_x, res_y, k_ref) if sharded and args.full else None
 
     host_image = None
-    if world == 1 and not args.no_host_image and hasattr(ctx, "render_host_async"):
+    if args.full and world == 1 and not args.no_host_image and hasattr(ctx, "render_host_async"):
         host_image = ctx.bench_host_frames(max(100, min(args.steps, 400)))
 
     # N > 1: BASELINE's other multi-GPU configurations, each beside the one-GPU time of the same work measured by rank 0
@@ -532,7 +567,7 @@ def main():
     # the Roche lobe and the accretor sphere resident, whole frames dealt to the GPUs (frame k on rank k mod N, no
     # exchange: utility/rotate_traces.py runs one process per frame).
     config4 = config5 = None
-    if sharded and not args.no_configs and args.sweep == "none" and not args.solids:
+    if args.full and sharded and not args.no_configs and args.sweep == "none" and not args.solids:
         c4x, c4y = (int(v) for v in args.config4_res.lower().split("x"))
         k4 = max(10, min(args.steps, 100))
         m4 = measure(c4x, c4y, k4, min(args.warmup, 10), True, False)
@@ -615,7 +650,7 @@ def main():
     # The C++ host on the same workload: rank 0 runs it as a child process on all N GPUs while the other ranks
     # idle at the barrier below (their GPUs are free: nothing of this job is running on them).
     native = None
-    if not args.no_native and not args.solids and args.sweep == "none" and args.workload == "c3":
+    if args.full and not args.no_native and not args.solids and args.sweep == "none" and args.workload == "c3":
         torch.cuda.synchronize()
         host_barrier()
         if rank == 0:
@@ -769,7 +804,7 @@ def main():
                                           "view and image; frames delivered to pinned host memory (sweep_files: written as zlib "
                                           ".vti files, end to end); Mrays/s in mrays_per_s",
                                   **native}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             sres = tuple(int(v) for v in args.cpu_sample_res.lower().split("x")) if args.cpu_sample_res else (res_x, res_y)
             out["cpu_baseline"], _ = cpu_baseline(xyz, cells, alpha, q, rots, sres)
             if not args.no_cpu_reference:

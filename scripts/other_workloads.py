@@ -15,7 +15,7 @@ rows = [("C3 998 250-cell grid, 2400x1800 (the bench line)", os.path.join(ROOT, 
         ("C2 ball (107k cells, non-convex), 1200x900", "c2_1200x900"),
         ("config 5 on one GPU: 360 frames, lobe + sphere, -D sweep", "c5_D"),
         ("config 5 on one GPU: 360 frames, lobe + sphere, -Y sweep", "c5_Y")]
-out = [f"# {tag}: other workloads on one MI355X (scripts/other_workloads.sh: python bench.py --no-cpu-baseline --no-native --steps 200 ...; "
+out = [f"# {tag}: other workloads on one MI355X (scripts/other_workloads.sh: python bench.py --full --no-cpu-baseline --no-native --steps 200 ...; "
        f"same build as {tag}_bench.json)", "",
        "| workload | Mrays/s | ms per frame | walk kernel ms | delivered to host: Mrays/s | segments per frame |",
        "|---|---|---|---|---|---|"]

@@ -4,7 +4,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 OUT=gpurun_out/other
 mkdir -p "$OUT"
-B="python3 bench.py --no-cpu-baseline --no-native --steps 200"
+B="python3 bench.py --full --no-cpu-baseline --no-native --steps 200"
 $B --lds-stage 1 --no-host-image > $OUT/stage1.json 2> $OUT/err.log || exit 1
 $B --lds-stage 0 --no-host-image > $OUT/stage0.json 2>> $OUT/err.log || exit 1
 $B --res 1200x900 --no-host-image > $OUT/c3_1200x900.json 2>> $OUT/err.log || exit 1

@@ -8,7 +8,8 @@
 //   host_san vti    <out.vti> <w> <h> <raw> write a synthetic frame (zero blocks, NaNs, ragged last block) + PNG
 //   host_san cli    <args...>               the option parser on the given command line
 //   host_san solids                         init_polar: Roche lobe + sphere, unique faces -> counts
-//   host_san oracle <scene.bin> <out.f32>   the CPU oracle on a dumped scene (see the pytest for the layout)
+//   host_san oracle <scene.bin> <out.f32> [threads]   the CPU oracle on a dumped scene (see the pytest for the layout;
+//                                                      OpenMP threads, default 2)
 //   host_san blocks <world> <base> <c0> <c1> ...  cost-balanced row blocks of the native multi-GPU host
 //   host_san wblocks <world> <base> <t0> .. <c0> <c1> ...  the same blocks cut again by the times t_k their devices took
 #include <chrono>
@@ -259,6 +260,7 @@ int main(int argc, char** argv) try {
     }
     if (mode == "oracle") {
         if (argc < 4) throw std::runtime_error("oracle: scene out?");
+        const int threads = argc > 4 ? std::atoi(argv[4]) : 2;
         std::ifstream f(argv[2], std::ios::binary);
         if (!f) throw std::runtime_error("cannot open scene");
         const std::vector<int64_t> hd = take<int64_t>(f, 6);  // n_pts, n_cells, n_rot, res_x, res_y, n_solid
@@ -274,7 +276,7 @@ int main(int argc, char** argv) try {
         char err[512] = {0};
         const int rc = c5o_render(xyz.data(), hd[0], cells.data(), hd[1], alpha.data(), q.data(), rots.data(), static_cast<int>(hd[2]),
                                   hd[5] ? solids.data() : nullptr, hd[5] ? colour.data() : nullptr, hd[5], static_cast<int>(hd[3]),
-                                  static_cast<int>(hd[4]), bounds.data(), limit[0], 2, out.data(), stats, timing, nullptr, 0, 0, nullptr,
+                                  static_cast<int>(hd[4]), bounds.data(), limit[0], threads, out.data(), stats, timing, nullptr, 0, 0, nullptr,
                                   nullptr, err, sizeof err);
         if (rc != 0) throw std::runtime_error(std::string("oracle: ") + err);
         std::ofstream o(argv[3], std::ios::binary);

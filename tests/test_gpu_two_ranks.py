@@ -36,7 +36,7 @@ def test_two_ranks_reassemble_every_frame(layout, extra):
 
 
 def test_bench_two_ranks_reports_the_baseline_configs():
-    """`python bench.py --gpus 2` started by ONE plain command (bench.py spawns its ranks itself, as
+    """`python bench.py --gpus 2 --full` started by ONE plain command (bench.py spawns its ranks itself, as
     a child `torch.distributed.run` job, before it has touched the GPU; here: gloo, both ranks on the one GPU, a small
     grid and small images): the headline is the N = 1 frame split by rows (strong scaling) beside its own one-GPU time, followed by
     BASELINE config 4 (a larger frame split by rows) and config 5 (a -D sweep with the solids, whole frames dealt to
@@ -46,7 +46,7 @@ def test_bench_two_ranks_reports_the_baseline_configs():
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(v, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "6", "--warmup", "2", "--backend", "gloo", "--workload", "kuhn12",
+                        "--gpus", "2", "--full", "--steps", "6", "--warmup", "2", "--backend", "gloo", "--workload", "kuhn12",
                         "--res", "400x300", "--config4-res", "800x600", "--config5-frames", "8", "--no-native", "--no-steady"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])

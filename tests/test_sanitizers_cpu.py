@@ -164,12 +164,23 @@ def test_oracle_under_the_sanitizers(san, tmp_path, oracle_port):
                 f.write(np.ascontiguousarray(arr, dtype=t).tobytes())
 
     dump(tmp_path / "scene.bin", 160, 120, rots)
-    p = san("oracle", tmp_path / "scene.bin", tmp_path / "out.f32")
+    ref = oracle_port.render(xyz, cells, a, q, rots, 160, 120, mg.REFERENCE_BOUNDS, solid_tets=solid, solid_colour=float("nan"), threads=1)
+    # One thread bins the solid after every cell (it has the last id), so every segment of a pixel it marks is counted:
+    # the counts must equal the optimised build's exactly.
+    p = san("oracle", tmp_path / "scene.bin", tmp_path / "out.f32", 1)
     assert p.returncode == 0, p.stderr
     got = np.fromfile(tmp_path / "out.f32", dtype=np.float32).reshape(120, 160, 2)
-    ref = oracle_port.render(xyz, cells, a, q, rots, 160, 120, mg.REFERENCE_BOUNDS, solid_tets=solid, solid_colour=float("nan"), threads=2)
     assert np.array_equal(got.view(np.uint32), ref["image"].view(np.uint32))
     assert f"segments {ref['segments']} covered {ref['covered']} marked {ref['marked']}" in p.stdout
+    # Two threads (the dynamic schedule of plane.cpp:184-192): a pixel the solid has marked takes no more segments, so
+    # which cells are binned after the solid, and with them the segment and covered counts, depend on timing. The image
+    # does not (a marked pixel shows its mark) and neither does the number of marked pixels.
+    p = san("oracle", tmp_path / "scene.bin", tmp_path / "out2.f32", 2)
+    assert p.returncode == 0, p.stderr
+    got = np.fromfile(tmp_path / "out2.f32", dtype=np.float32).reshape(120, 160, 2)
+    assert np.array_equal(got.view(np.uint32), ref["image"].view(np.uint32))
+    seg, cov, mark = (int(v) for v in p.stdout.split()[1::2])
+    assert seg <= ref["segments"] and cov <= ref["covered"] and mark == ref["marked"], p.stdout
     # an unrotated lattice-aligned grid: pixel centres on projected edges -> the reference aborts (plane.cpp:39-41),
     # the oracle reports; either way no sanitizer report
     san("oracle", tmp_path / "scene.bin", tmp_path / "out.f32")
