@@ -28,6 +28,7 @@ EXPORTS = [
     "c5_download_view_points", "c5_face_adjacency", "c5_set_stream",
     "c5_set_row_range", "c5_get_row_costs", "c5_weld_points",
     "c5_render_host_async", "c5_render_host_wait", "c5_host_alloc", "c5_host_free", "c5_render_frame_rows_async",
+    "c5_render_adjoint", "c5_render_adjoint_device",
 ]
 
 
@@ -99,6 +100,8 @@ def load_library() -> C.CDLL:
     lib.c5_render_frame_rows_async.argtypes = [vp, C.POINTER(C.c_float)]
     lib.c5_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.c5_host_free.argtypes = [vp, vp]
+    lib.c5_render_adjoint.argtypes = [vp, C.POINTER(C.c_float), dp, dp]
+    lib.c5_render_adjoint_device.argtypes = [vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("c5_destroy", "c5_last_error"):
             getattr(lib, name).restype = C.c_int
@@ -129,7 +132,15 @@ class Context:
         rc = self.lib.c5_create(device, C.byref(self.handle))
         if rc != C5_OK:
             raise C5Error(rc, self.lib.c5_last_error(None).decode())
+        self.device = device
         self.res_x = self.res_y = 0
+        self.n_cells = 0
+        # bumped by everything that changes which frame a render produces apart from the cells' scalars (grid, view, image,
+        # rows, solids, alpha limit): course5_amd.autograd refuses to differentiate a frame other than the one it rendered
+        self.frame_state = 0
+        # which set of scalars the context holds (course5_amd.autograd; None: the caller's own)
+        self.scalars_owner = None
+        self.stream_ptr = 0
         # the library's instruments are off by default (they cost 5 % of a frame); tests and scripts read stats()["ms_*"] and
         # walk_kernel_ms() everywhere, so this wrapper switches them on - bench.py switches the stage events off again
         self.set_option("stage_timing", 1)
@@ -159,7 +170,9 @@ class Context:
 
     def set_stream(self, stream_ptr: int):
         """Run on a caller-owned HIP stream (e.g. torch.cuda.current_stream().cuda_stream); 0 = own."""
-        return self._check(self.lib.c5_set_stream(self.handle, C.c_void_p(stream_ptr)), allow=(C5_RETRY,))
+        rc = self._check(self.lib.c5_set_stream(self.handle, C.c_void_p(stream_ptr)), allow=(C5_RETRY,))
+        self.stream_ptr = stream_ptr
+        return rc
 
     # -- scene ---------------------------------------------------------------------------------
     def upload_grid(self, xyz, cells, alpha, q):
@@ -172,27 +185,35 @@ class Context:
         self._check(self.lib.c5_upload_grid(self.handle, _dp(xyz), xyz.shape[0],
                                             cells.ctypes.data_as(C.POINTER(C.c_int32)), cells.shape[0],
                                             _dp(alpha), _dp(q)))
+        self.n_cells = cells.shape[0]
+        self.frame_state += 1
+        self.scalars_owner = None
 
     def update_scalars(self, alpha, q):
         alpha = np.ascontiguousarray(alpha, dtype=np.float64)
         q = np.ascontiguousarray(q, dtype=np.float64)
         self._check(self.lib.c5_update_scalars(self.handle, _dp(alpha), _dp(q), alpha.shape[0]))
+        self.scalars_owner = None
 
     def set_solid(self, slot: int, tets, colour: float = float("nan")):
         tets = np.ascontiguousarray(tets, dtype=np.float64).reshape(-1, 12)
         self._check(self.lib.c5_set_solid(self.handle, slot, _dp(tets), tets.shape[0], colour))
+        self.frame_state += 1
 
     # -- per frame -----------------------------------------------------------------------------
     def set_image(self, res_x: int, res_y: int, bounds):
         b = np.ascontiguousarray(bounds, dtype=np.float64)
         self._check(self.lib.c5_set_image(self.handle, res_x, res_y, _dp(b)))
         self.res_x, self.res_y = res_x, res_y
+        self.frame_state += 1
 
     def set_row_tiles(self, tile_rows: int, rank: int, world: int):
         self._check(self.lib.c5_set_row_tiles(self.handle, tile_rows, rank, world))
+        self.frame_state += 1
 
     def set_row_range(self, row_begin: int, row_count: int = -1):
         self._check(self.lib.c5_set_row_range(self.handle, row_begin, row_count))
+        self.frame_state += 1
 
     def row_costs(self) -> np.ndarray:
         """Segments per local row of the last frame (option "row_costs" must be on)."""
@@ -209,13 +230,16 @@ class Context:
     def set_view(self, rots):
         arr, n = _rot_array(rots)
         self._check(self.lib.c5_set_view(self.handle, arr, n))
+        self.frame_state += 1
 
     def set_solid_view(self, slot: int, rots):
         arr, n = _rot_array(rots)
         self._check(self.lib.c5_set_solid_view(self.handle, slot, arr, n))
+        self.frame_state += 1
 
     def set_alpha_limit(self, v: float):
         self._check(self.lib.c5_set_alpha_limit(self.handle, v))
+        self.frame_state += 1
 
     def set_option(self, name: str, value: float):
         self._check(self.lib.c5_set_option(self.handle, name.encode(), float(value)))
@@ -230,6 +254,35 @@ class Context:
     def render_device(self, device_ptr: int):
         """Asynchronous render into device memory (e.g. a torch tensor's data_ptr())."""
         self._check(self.lib.c5_render_device(self.handle, C.c_void_p(device_ptr)))
+
+    # -- adjoint render ----------------------------------------------------------------------------
+    def render_adjoint(self, grad_out) -> tuple:
+        """Gradients of the frame render() would produce now, weighted by grad_out ([local_rows, res_x, 2]: the weights
+        of tau and of I per pixel): (grad_alpha, grad_q), float64 [n_cells] each in the order of upload_grid.
+        Synchronous; retries by itself."""
+        g = np.ascontiguousarray(grad_out, dtype=np.float32)
+        if g.shape != (self.local_rows, self.res_x, 2):
+            raise ValueError(f"grad_out must be [{self.local_rows}, {self.res_x}, 2], not {list(g.shape)}")
+        ga = np.zeros(self.n_cells, dtype=np.float64)
+        gq = np.zeros(self.n_cells, dtype=np.float64)
+        self._check(self.lib.c5_render_adjoint(self.handle, g.ctypes.data_as(C.POINTER(C.c_float)), _dp(ga), _dp(gq)))
+        return ga, gq
+
+    def render_adjoint_device(self, grad_out, grad_alpha, grad_q):
+        """Asynchronous form on the context's stream, into device memory: torch tensors on this context's GPU (grad_out
+        float32 [local_rows, res_x, 2] contiguous, grad_alpha / grad_q float64 [n_cells] contiguous) or raw device
+        pointers.  The status comes with the next synchronize() (C5_RETRY: run it again)."""
+        def ptr(t, dtype, shape):
+            if isinstance(t, int):
+                return t
+            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"expected a contiguous {dtype} tensor of shape {shape} on the GPU")
+            return t.data_ptr()
+
+        import torch
+        self._check(self.lib.c5_render_adjoint_device(
+            self.handle, C.c_void_p(ptr(grad_out, torch.float32, (self.local_rows, self.res_x, 2))),
+            C.c_void_p(ptr(grad_alpha, torch.float64, (self.n_cells,))), C.c_void_p(ptr(grad_q, torch.float64, (self.n_cells,)))))
 
     # -- frames delivered to host memory, pipelined -------------------------------------------------
     def host_image(self, full: bool = False) -> np.ndarray:

@@ -1,0 +1,379 @@
+// gfx950 kernels of the adjoint render: d(image)/d(alpha) and d(image)/d(Q) per cell, weighted by an upstream image.
+//
+// For one pixel, number its segments k = 1..n in the order line::integrate_ray_value_by_i processes them (line.cpp:206:
+// from the deepest, z ascending; segment n is the one nearest the viewer), a_k = min(alpha_k, limit), active_k =
+// !(a_k < DBL_EPSILON), E_k = exp(-a_k dz_k), I_k = E_k I_{k-1} + Q_k (1 - E_k) / a_k (inactive: I_k = I_{k-1}), and
+// T_k = prod_{j > k} E_j = exp(-(Lambda - Lambda_k)), Lambda_k = sum_{j <= k} a_j dz_j over the active segments.  Then
+//     d tau / d alpha_k = dz_k                                                 (raw alpha, every segment)
+//     d I / d Q_k       = T_k (1 - E_k) / a_k                                  (active)
+//     d I / d alpha_k   = T_k [Q_k (dz_k E_k / a_k - (1 - E_k) / a_k^2) - dz_k E_k I_{k-1}]   (active, alpha_k <= limit)
+// and grad_alpha[c] = sum over the segments of c of g_tau dz + g_I dI/dalpha, grad_q[c] = sum of g_I dI/dQ, with the
+// upstream weights (g_tau, g_I) of the segment's pixel.  Solid-marked pixels contribute nothing.
+//
+//   adjoint_walk<1>   the forward walk (walk_kernels.hip: walk_composite, "integration" 0: -z -> +z, the reference's
+//                     order) once: Lambda per pixel.  Leaves the entry lists in place for ...
+//   adjoint_walk<2>   ... the same walk again over exactly the same segments: I_{k-1} runs along, T_k from Lambda - Lambda_k,
+//                     and the per-segment terms go to per-cell fp64 arrays (device order).  Lanes of a wavefront in the
+//                     same cell at the same step are summed first: one pair of atomics per distinct cell and step.
+//   adjoint_resolve   the same for the per-pixel sorted segment lists of bin_sort_resolve ("algorithm" 1).
+//   adjoint_permute   device order -> the caller's (c5_upload_grid, "cell_order").
+//
+// The sums are fp64 atomics, added in arrival order: the gradients are NOT bit-reproducible from run to run (the last bits
+// move).  This file is compiled with -munsafe-fp-atomics (build.py): the adds are global_atomic_add_f64, no
+// compare-and-swap loop.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+
+#include "adjoint.hpp"
+#include "device_types.hpp"
+#include "kernels.hpp"
+#include "walk_common.hpp"
+
+namespace c5 {
+namespace adj {
+
+// The walk's per-step helpers, as walk_kernels.hip has them (CellRegs, load_cell, step_geometry): that file stays as it is.
+struct CellRegs {
+    D2 r0, r1, r2, r3, r4, r5, r6, r7;  // ExitRecord: r0-r4 planes (+ nbr[0..1] in r4.b), r5.a = nbr[2] | flags, r6 / r7 optics
+};
+
+__device__ __forceinline__ void load_cell(CellRegs& c, const ExitRecord* rec, int cell) {
+    const D2* rp = reinterpret_cast<const D2*>(rec + cell);
+    c.r0 = rp[0];
+    c.r1 = rp[1];
+    c.r2 = rp[2];
+    c.r3 = rp[3];
+    c.r4 = rp[4];
+    c.r5 = rp[5];
+    c.r6 = rp[6];
+    c.r7 = rp[7];
+}
+
+struct StepGeometry {
+    double w_exit;   // +inf: the ray cannot leave (flat cell, edge-on faces): it ends here
+    uint32_t w_out;  // neighbour word of the exit face
+};
+
+__device__ __forceinline__ StepGeometry step_geometry(const CellRegs& cur, double x, double y) {
+    const double w0 = fma(cur.r0.b, x, fma(cur.r1.a, y, cur.r0.a));
+    const double w1 = fma(cur.r2.a, x, fma(cur.r2.b, y, cur.r1.b));
+    const double w2 = fma(cur.r3.b, x, fma(cur.r4.a, y, cur.r3.a));
+    const unsigned long long n01 = __double_as_longlong(cur.r4.b);
+    const uint32_t n0 = static_cast<uint32_t>(n01), n1 = static_cast<uint32_t>(n01 >> 32);
+    const uint32_t n2 = static_cast<uint32_t>(__double_as_longlong(cur.r5.a));
+    StepGeometry g;
+    g.w_exit = fmin(w0, fmin(w1, w2));  // (never NaN: a candidate is a finite depth or +inf)
+    g.w_out = (w0 == g.w_exit) ? n0 : (w1 == g.w_exit) ? n1 : n2;
+    return g;
+}
+
+// (1 - e^-x) / x = sum_m (-x)^m / (m + 1)!  for 0 <= x < 1/8 (truncation below 1e-19)
+__device__ __forceinline__ double one_minus_exp_over_x(double x) {
+    double p = 1.0 / 39916800.0;
+    p = fma(p, -x, 1.0 / 3628800.0);
+    p = fma(p, -x, 1.0 / 362880.0);
+    p = fma(p, -x, 1.0 / 40320.0);
+    p = fma(p, -x, 1.0 / 5040.0);
+    p = fma(p, -x, 1.0 / 720.0);
+    p = fma(p, -x, 1.0 / 120.0);
+    p = fma(p, -x, 1.0 / 24.0);
+    p = fma(p, -x, 1.0 / 6.0);
+    p = fma(p, -x, 0.5);
+    return fma(p, -x, 1.0);
+}
+
+// (x e^-x - (1 - e^-x)) / x^2 = sum_m (-1)^(m+1) (m + 1) / (m + 2)! x^m = -1/2 + x/3 - x^2/8 + ...  for 0 <= x < 1/8: the
+// bracket of d I / d alpha divided by Q dz^2, which cancels to nothing when evaluated as written for small a dz
+__device__ __forceinline__ double dalpha_bracket_series(double x) {
+    double p = -1.0 / 43545600.0;
+    p = fma(p, x, 1.0 / 3991680.0);
+    p = fma(p, x, -1.0 / 403200.0);
+    p = fma(p, x, 1.0 / 45360.0);
+    p = fma(p, x, -1.0 / 5760.0);
+    p = fma(p, x, 1.0 / 840.0);
+    p = fma(p, x, -1.0 / 144.0);
+    p = fma(p, x, 1.0 / 30.0);
+    p = fma(p, x, -1.0 / 8.0);
+    p = fma(p, x, 1.0 / 3.0);
+    return fma(p, x, -0.5);
+}
+
+// The terms of one active segment: d I / d Q and (unclamped) d I / d alpha, and I_k from I_{k-1}.  T: transmittance to the
+// viewer; E: exp(-a dz).
+struct SegmentTerms {
+    double dI_dq, dI_da, I_next;
+};
+__device__ __forceinline__ SegmentTerms segment_terms(double a, double q, double dz, double E, double T, double I_prev) {
+    const double x = a * dz;
+    double s_over_q, bracket;  // (1 - E) / a;  Q (dz E / a - (1 - E) / a^2)
+    if (x < -kSmallExpArg) {
+        s_over_q = dz * one_minus_exp_over_x(x);
+        bracket = q * dz * dz * dalpha_bracket_series(x);
+    } else {
+        s_over_q = (1.0 - E) / a;
+        bracket = q * (dz * E - s_over_q) / a;
+    }
+    SegmentTerms t;
+    t.dI_dq = T * s_over_q;
+    t.dI_da = T * (bracket - dz * E * I_prev);
+    t.I_next = fma(E, I_prev, q * s_over_q);
+    return t;
+}
+
+// Adds (ga, gq) of every lane with `pending` set to grad_a / grad_q [its cell]: the lanes in one cell are summed across
+// the wavefront first, and one lane adds the sums (one pair of atomics per distinct cell).  Every lane of the wavefront
+// must be active.
+__device__ __forceinline__ void scatter_wave(bool pending, int cell, double ga, double gq, double* __restrict__ grad_a,
+                                             double* __restrict__ grad_q) {
+    const int lane = static_cast<int>(threadIdx.x & 63);
+    unsigned long long m = __builtin_amdgcn_ballot_w64(pending);
+    while (m != 0ull) {
+        const int leader = __builtin_ctzll(m);
+        const int lc = __builtin_amdgcn_readlane(cell, leader);
+        const bool mine = pending && cell == lc;
+        double sa = mine ? ga : 0.0, sq = mine ? gq : 0.0;
+        const unsigned long long mine_mask = __builtin_amdgcn_ballot_w64(mine);
+        if (mine_mask != (1ull << leader)) {  // (wave-uniform) more than one lane in this cell
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                sa += __shfl_xor(sa, d);
+                sq += __shfl_xor(sq, d);
+            }
+        }
+        if (lane == leader) {
+            atomicAdd(grad_a + lc, sa);
+            atomicAdd(grad_q + lc, sq);
+        }
+        pending = pending && !mine;
+        m &= ~mine_mask;
+    }
+}
+
+}  // namespace adj
+
+// One wavefront per 8x8 pixel tile, one lane per pixel (the walk's default tiling: neighbouring rays share cells, which is
+// what the per-wave sum before the atomics lives on).
+template <int PASS>
+__global__ __launch_bounds__(64) void adjoint_walk(AdjointParams A) {
+    using namespace adj;
+    const WalkParams& P = A.w;
+    const ImageParams& im = P.im;
+    const int tiles_x = (im.res_x + 7) / 8;
+    const int ty = static_cast<int>(blockIdx.x) / tiles_x, tx = static_cast<int>(blockIdx.x) - ty * tiles_x;
+    const int lane = static_cast<int>(threadIdx.x);
+    const int col = tx * 8 + (lane & 7), lrow = ty * 8 + (lane >> 3);
+    const bool in_image = (col < im.res_x) && (lrow < im.n_local_rows);
+
+    unsigned n_step = 0, overflow = 0;
+    bool skipped = false;
+    double key_taken = -DBL_MAX;
+    double x = 0.0, y = 0.0, w_cur = -DBL_MAX, carry = 0.0;
+    EntryHead ent{0, 0};
+    int cell = -1;
+    size_t lp = 0;
+    double lam = 0.0;                                  // Lambda_k so far
+    double lam_total = 0.0, I = 0.0, g_tau = 0.0, g_I = 0.0;  // pass 2
+
+    if (in_image) {
+        lp = static_cast<size_t>(lrow) * im.res_x + col;
+        const uint32_t mv = P.mask ? P.mask[lp] : 0u;
+        if (!mv) {  // (a solid-marked pixel shows the solid: line.cpp:177-179, nothing of the grid)
+            x = P.Xtab[col];
+            y = P.Ytab[global_row_of(im, lrow)];
+            ent = load_entry_head(P.entry_head + lp);
+            if (PASS == 2) {
+                const float2 g = A.grad_out[lp];
+                g_tau = g.x;
+                g_I = g.y;
+                lam_total = A.lambda[lp];
+            }
+            if (ent.count > 0 && (PASS == 1 || g_tau != 0.0 || g_I != 0.0))
+                cell = next_entry<true>(P, lp, ent, w_cur, carry, -DBL_MAX, -DBL_MAX, skipped);
+            key_taken = w_cur;
+        }
+    }
+
+    CellRegs cur;
+    if (cell >= 0) load_cell(cur, P.xrec, cell);
+
+    // wave-uniform loop (the scatter wants every lane): a lane whose ray has ended takes part with nothing to add
+    for (;;) {
+        const bool live = cell >= 0;
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        bool emit = false;
+        double ga = 0.0, gq = 0.0;
+        const int here = cell;
+        if (live) {
+            // the step of walk_composite<*, 0> (walk_kernels.hip), operation for operation: the same segments
+            const StepGeometry sg = step_geometry(cur, x, y);
+            ++n_step;
+            const bool has_exit = sg.w_exit < INFINITY;
+            const double dz = sg.w_exit - carry;
+            const bool contributes = dz > 0.0 && dz < INFINITY;
+            int nb = -1;
+            double carry_next = carry;
+            if (has_exit) {
+                carry_next = sg.w_exit;
+                w_cur = fmax(w_cur, sg.w_exit);
+                const uint32_t id = sg.w_out & kIdMask;
+                if (id != kNoCell) nb = static_cast<int>(id);
+            }
+            if (nb >= 0 && n_step >= P.max_steps) {
+                overflow = 1;
+                nb = -1;
+            } else if (nb < 0 && !overflow) {
+                nb = next_entry<true>(P, lp, ent, w_cur, carry_next, key_taken, has_exit ? sg.w_exit : -DBL_MAX, skipped);
+                key_taken = w_cur;
+            }
+            CellRegs nxt;
+            if (nb >= 0) load_cell(nxt, P.xrec, nb);
+
+            if (contributes) {
+                const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+                if (PASS == 1) {
+                    if (a != 0.0) lam = fma(a, dz, lam);
+                } else {
+                    emit = true;
+                    ga = g_tau * dz;  // d tau / d alpha (line.cpp:189: raw alpha)
+                    if (a != 0.0) {
+                        lam = fma(a, dz, lam);  // (as in pass 1: Lambda_n == Lambda bit for bit, Lambda - Lambda_k >= 0)
+                        const double T = exp_nonpositive(fmin(lam - lam_total, 0.0));
+                        const double E = exp_nonpositive(-a * dz);
+                        const SegmentTerms t = segment_terms(a, q, dz, E, T, I);
+                        gq = g_I * t.dI_dq;
+                        if (a == a_raw) ga = fma(g_I, t.dI_da, ga);  // (a clamped alpha does not move: line.cpp:216)
+                        I = t.I_next;
+                    }
+                }
+            }
+            cell = nb;
+            carry = carry_next;
+            cur = nxt;
+        }
+        if (PASS == 2) scatter_wave(emit, here, ga, gq, A.grad_a, A.grad_q);
+    }
+
+    if (in_image) {
+        if (PASS == 1) A.lambda[lp] = lam;
+        else __builtin_nontemporal_store(0ll, reinterpret_cast<long long*>(P.entry_head + lp));  // cleared, as the walk leaves them
+    }
+    if (PASS == 1) {
+        const unsigned s_ovf = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(overflow != 0u)));
+        const unsigned s_skip = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(skipped)));
+        if (lane == 0) {
+            if (s_ovf) atomicAdd(&P.counters->walk_overflow, s_ovf);
+            if (s_skip) atomicAdd(&P.counters->overlap_rays, s_skip);
+        }
+    }
+}
+
+// bin_sort_resolve's segments (exact_kernels.hip: Segment; c_api.hip checks the size)
+struct alignas(8) AdjSegment {
+    double z_hi;
+    double dz;
+    long long cell;
+};
+static_assert(sizeof(AdjSegment) == 24, "AdjSegment mirrors exact_kernels.hip's Segment");
+size_t adjoint_segment_bytes() { return sizeof(AdjSegment); }
+
+// resolve_pixels (exact_kernels.hip) differentiated: its list sorted by descending z_hi (line.cpp:138, the same Shell sort),
+// the recurrence run from the back (i = n - 1 ... 0: k = n - i).
+__global__ __launch_bounds__(256) void adjoint_resolve(GridView g, ImageParams im, const int64_t* __restrict__ offs,
+                                                       AdjSegment* __restrict__ segs, const uint32_t* __restrict__ mask,
+                                                       double alpha_limit, const float2* __restrict__ grad_out,
+                                                       double* __restrict__ grad_a, double* __restrict__ grad_q) {
+    using namespace adj;
+    const int64_t lp = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    int n = 0;
+    AdjSegment* list = segs;
+    double g_tau = 0.0, g_I = 0.0, lam_total = 0.0;
+    if (lp < n_px && !(mask && mask[lp])) {
+        list = segs + offs[lp];
+        n = static_cast<int>(offs[lp + 1] - offs[lp]);
+        const float2 gw = grad_out[lp];
+        g_tau = gw.x;
+        g_I = gw.y;
+        if (g_tau == 0.0 && g_I == 0.0) n = 0;
+        for (int gap = n / 2; gap > 0; gap = (gap == 2) ? 1 : static_cast<int>(gap / 2.2)) {
+            for (int i = gap; i < n; ++i) {
+                const AdjSegment t = list[i];
+                int j = i;
+                while (j >= gap && list[j - gap].z_hi < t.z_hi) {
+                    list[j] = list[j - gap];
+                    j -= gap;
+                }
+                list[j] = t;
+            }
+        }
+        for (int i = n - 1; i >= 0; --i) {  // Lambda, in the order pass 2 runs
+            double a = g.alpha[list[i].cell];
+            if (a > alpha_limit) a = alpha_limit;
+            if (!(a < DBL_EPSILON)) lam_total = fma(a, list[i].dz, lam_total);
+        }
+    }
+    double lam = 0.0, I = 0.0;
+    // wave-uniform loop over the steps (the scatter wants every lane)
+    for (int i = n - 1;; --i) {
+        const bool live = i >= 0;
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        int c = -1;
+        double ga = 0.0, gq = 0.0;
+        if (live) {
+            c = static_cast<int>(list[i].cell);
+            const double dz = list[i].dz, q = g.q[c], a_raw = g.alpha[c];
+            double a = a_raw;
+            if (a > alpha_limit) a = alpha_limit;
+            ga = g_tau * dz;
+            if (!(a < DBL_EPSILON)) {
+                lam = fma(a, dz, lam);
+                const double T = exp(fmin(lam - lam_total, 0.0));
+                const double E = exp(-a * dz);
+                const SegmentTerms t = segment_terms(a, q, dz, E, T, I);
+                gq = g_I * t.dI_dq;
+                if (!(a_raw > alpha_limit)) ga = fma(g_I, t.dI_da, ga);
+                I = t.I_next;
+            }
+        }
+        scatter_wave(live, c, ga, gq, grad_a, grad_q);
+    }
+}
+
+__global__ __launch_bounds__(256) void adjoint_permute(const double* __restrict__ ga_dev, const double* __restrict__ gq_dev,
+                                                       const int32_t* __restrict__ perm, int64_t n, double* __restrict__ ga_out,
+                                                       double* __restrict__ gq_out) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n) return;
+    const int64_t d = perm ? static_cast<int64_t>(perm[i]) : i;
+    ga_out[d] = ga_dev[i];
+    gq_out[d] = gq_dev[i];
+}
+
+void launch_adjoint_walk(hipStream_t s, const AdjointParams& a, int pass) {
+    const ImageParams& im = a.w.im;
+    if (im.res_x <= 0 || im.n_local_rows <= 0) return;
+    const unsigned blocks = static_cast<unsigned>(((im.res_x + 7) / 8) * ((im.n_local_rows + 7) / 8));
+    if (pass == 1)
+        hipLaunchKernelGGL(adjoint_walk<1>, dim3(blocks), dim3(64), 0, s, a);
+    else
+        hipLaunchKernelGGL(adjoint_walk<2>, dim3(blocks), dim3(64), 0, s, a);
+}
+
+void launch_adjoint_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const int64_t* offs, void* segs,
+                            const uint32_t* mask, double alpha_limit, const float2* grad_out, double* grad_a, double* grad_q) {
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    if (n_px <= 0) return;
+    const unsigned blocks = static_cast<unsigned>((n_px + 255) / 256);
+    hipLaunchKernelGGL(adjoint_resolve, dim3(blocks), dim3(256), 0, s, g, im, offs, static_cast<AdjSegment*>(segs), mask, alpha_limit,
+                       grad_out, grad_a, grad_q);
+}
+
+void launch_adjoint_permute(hipStream_t s, const double* ga_dev, const double* gq_dev, const int32_t* perm, int64_t n,
+                            double* ga_out, double* gq_out) {
+    if (n <= 0) return;
+    const unsigned blocks = static_cast<unsigned>((n + 255) / 256);
+    hipLaunchKernelGGL(adjoint_permute, dim3(blocks), dim3(256), 0, s, ga_dev, gq_dev, perm, n, ga_out, gq_out);
+}
+
+}  // namespace c5

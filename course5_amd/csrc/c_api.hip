@@ -17,6 +17,7 @@
 
 #include "../../include/course5_hip.h"
 #include "adjacency.hpp"
+#include "adjoint.hpp"
 #include "device_types.hpp"
 #include "kernels.hpp"
 
@@ -261,6 +262,17 @@ struct c5_context {
     bool counters_on_host = true;  // the last frame's counters / sticky words have been copied to the host
     bool frame_timed = false;
     c5_stats last{};
+
+    // adjoint render (c5_render_adjoint*): nothing of it is allocated before the first adjoint call
+    DeviceBuffer adj_lambda;    // [n_local_px] fp64: pass 1 -> pass 2 (adjoint_kernels.hip)
+    DeviceBuffer adj_counters;  // the adjoint's own FrameCounters: a frame's statistics and failure words stay the frame's
+    DeviceBuffer adj_sticky;    // the entry raster's failure words for the adjoint (never the frames' sticky words)
+    DeviceBuffer adj_grad;      // [2][n_cells] fp64, device order
+    DeviceBuffer adj_perm;      // cell_perm on the device, for the grid of upload adj_perm_serial
+    DeviceBuffer adj_io;        // c5_render_adjoint: the weights' image and the caller-order gradients
+    uint64_t grid_serial = 0, adj_perm_serial = ~uint64_t{0};
+    unsigned* adj_status = nullptr;  // pinned: walk_overflow, entry_overflow, overlap_rays of the last adjoint
+    bool adjoint_pending = false;    // its status has not been looked at yet
 };
 
 namespace {
@@ -945,6 +957,7 @@ int enqueue_frame(c5_context* ctx, float2* out_dev, c5::FrameCounters* own_count
 }
 
 int finish_frame(c5_context* ctx);
+int finish_adjoint(c5_context* ctx);
 
 // Wait for the context's stream and collect the last frame's outcome.
 int wait_and_collect(c5_context* ctx) {
@@ -957,7 +970,9 @@ int wait_and_collect(c5_context* ctx) {
         ctx->counters_on_host = true;
     }
     C5_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return finish_frame(ctx);
+    const int rc = finish_frame(ctx);
+    const int rc_adj = finish_adjoint(ctx);
+    return rc ? rc : rc_adj;
 }
 
 // After the stream drained: collect counters/timings; grow the entry buffer if it overflowed.
@@ -1174,6 +1189,184 @@ int finish_frame(c5_context* ctx) {
     return C5_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Adjoint render (c5_render_adjoint*, adjoint_kernels.hip): the frame c5_render would produce now, differentiated with
+// respect to the cells' alpha and Q.  Its own per-view setup on the context's stream into slot 0's buffers - records of
+// "integration" 0 (the reference's order, whatever the option says), whole rays (no "depth_split"), the entry lists, the
+// solid mask - then the two passes of the walk (or bin_sort_resolve's lists) and the permutation into the caller's order.
+// It leaves the options alone and the frames' statistics and failure words too (counters and sticky words of its own);
+// the slot's per-view data are marked stale, so the next frame builds its own ("view_cache").
+// ------------------------------------------------------------------------------------------
+int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, double* gq_out) {
+    if (ctx->n_cells <= 0 && [&] {
+            for (const Solid& s : ctx->solids)
+                if (s.n_tets > 0) return false;
+            return true;
+        }())
+        return fail(ctx, C5_ERR_STATE, "plane initializer. empty set of objects to render");  // plane.cpp:269-271
+    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    if (ctx->n_cells <= 0) return C5_OK;  // (solids only: no cell to differentiate)
+    if (c5::segment_bytes() != c5::adjoint_segment_bytes())
+        return fail(ctx, C5_ERR_STATE, "bin_sort_resolve's segment layout differs from the adjoint's");
+    // everything below runs on the context's stream: frames set up on the others ("pipeline", "overlap_setup") must be done
+    if (ctx->pipeline || ctx->overlap_setup) {
+        rc = drain(ctx);
+        if (rc) return rc;
+    }
+    FrameSlot& fs = ctx->slots[0];
+    hipStream_t s = ctx->stream;
+    const c5::ImageParams& im = ctx->im;
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    const int64_t padded = ((n_px + 1023) / 1024) * 1024;
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
+
+    C5_HIP(ctx, ctx->adj_counters.ensure(kCountersBytes));
+    C5_HIP(ctx, ctx->adj_sticky.ensure(kStickyWords * sizeof(unsigned)));
+    C5_HIP(ctx, ctx->adj_grad.ensure(2 * n_cells * sizeof(double)));
+    if (!ctx->adj_status) C5_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->adj_status), 4 * sizeof(unsigned), hipHostMallocDefault));
+    if (!ctx->cell_perm.empty() && ctx->adj_perm_serial != ctx->grid_serial) {
+        C5_HIP(ctx, ctx->adj_perm.ensure(n_cells * sizeof(int32_t)));
+        C5_HIP(ctx, hipMemcpy(ctx->adj_perm.ptr, ctx->cell_perm.data(), n_cells * sizeof(int32_t), hipMemcpyHostToDevice));
+        ctx->adj_perm_serial = ctx->grid_serial;
+    }
+    double* const ga_dev = ctx->adj_grad.as<double>();
+    double* const gq_dev = ga_dev + n_cells;
+    c5::FrameCounters* const counters = ctx->adj_counters.as<c5::FrameCounters>();
+    C5_HIP(ctx, hipMemsetAsync(ctx->adj_sticky.ptr, 0, kStickyWords * sizeof(unsigned), s));
+    C5_HIP(ctx, hipMemsetAsync(ga_dev, 0, 2 * n_cells * sizeof(double), s));
+
+    c5::GridView g;
+    g.n_pts = ctx->n_pts;
+    g.n_cells = ctx->n_cells;
+    g.n_bfaces = ctx->n_bfaces;
+    g.px = ctx->px.as<double>();
+    g.py = ctx->py.as<double>();
+    g.pz = ctx->pz.as<double>();
+    g.vx = fs.vx.as<double>();
+    g.vy = fs.vy.as<double>();
+    g.vz = fs.vz.as<double>();
+    g.cell_vert = ctx->cell_vert.as<int4>();
+    g.cell_adj = ctx->cell_adj.as<int4>();
+    g.alpha = ctx->alpha.as<double>();
+    g.q = ctx->q.as<double>();
+    g.bface = ctx->bface.as<uint32_t>();
+    g.xrec = fs.rec.as<c5::ExitRecord>();
+    g.rot = ctx->view;
+    g.block_sphere = (ctx->block_cull && im.n_local_rows > 0 && im.n_local_rows < im.res_y && ctx->block_sphere.ptr) ? ctx->block_sphere.as<double4>() : nullptr;
+    if (im.n_local_rows > 0) {  // (as enqueue_frame)
+        const int first = c5::global_row_of(im, 0), last = c5::global_row_of(im, im.n_local_rows - 1);
+        const double pad = std::fabs(im.step_y);
+        const double ya = ctx->host_ytab[static_cast<size_t>(first)], yb = ctx->host_ytab[static_cast<size_t>(last)];
+        g.cull_y_lo = std::fmin(ya, yb) - pad;
+        g.cull_y_hi = std::fmax(ya, yb) + pad;
+    } else {
+        g.cull_y_lo = 1.0;
+        g.cull_y_hi = -1.0;
+    }
+    // the slot's per-view data are about to hold the adjoint's: no frame may take them for its own
+    fs.setup_epoch = 0;
+    fs.setup_kept = false;
+    fs.flags_valid = false;
+
+    c5::launch_transform_soa(s, g.px, g.py, g.pz, g.vx, g.vy, g.vz, g.n_pts, ctx->view, counters);
+    c5::SolidTable table{};
+    bool any_solid = false;
+    const bool bin_sort = ctx->algorithm == 1 || !ctx->grid_conforming || ctx->overlap_seen;
+    if (bin_sort) {
+        C5_HIP(ctx, ctx->offs64.ensure(static_cast<size_t>(padded + 1024) * sizeof(int64_t)));
+        C5_HIP(ctx, ctx->scratch64.ensure(static_cast<size_t>(padded / 1024 + 1024) * sizeof(int64_t)));
+        C5_HIP(ctx, hipMemsetAsync(fs.count.ptr, 0, static_cast<size_t>(padded + 1) * sizeof(int32_t), s));
+        c5::launch_bin_count(s, g, ctx->xtab.as<double>(), ctx->ytab.as<double>(), im, fs.count.as<int32_t>(), &counters->odd_pixels);
+        c5::launch_scan64(s, fs.count.as<int32_t>(), ctx->offs64.as<int64_t>(), n_px, ctx->scratch64.as<int64_t>());
+        int64_t total = 0;
+        C5_HIP(ctx, hipMemcpyAsync(&total, ctx->offs64.as<int64_t>() + n_px, sizeof total, hipMemcpyDeviceToHost, s));
+        C5_HIP(ctx, hipStreamSynchronize(s));
+        C5_HIP(ctx, ctx->segs.ensure(static_cast<size_t>(total + 16) * c5::segment_bytes()));
+        c5::launch_bin_fill(s, g, ctx->xtab.as<double>(), ctx->ytab.as<double>(), im, fs.count.as<int32_t>(),
+                            ctx->offs64.as<int64_t>(), ctx->segs.ptr);
+        rc = enqueue_solids(ctx, fs, 0, s, table, any_solid);
+        if (rc) return rc;
+        c5::launch_adjoint_resolve(s, g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, any_solid ? fs.mask.as<uint32_t>() : nullptr,
+                                   ctx->alpha_limit, grad_out, ga_dev, gq_dev);
+    } else {
+        C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(padded) * sizeof(double)));
+        const double key_slack = !ctx->entry_key ? -1.0 : c5::kEntryKeySlack * ctx->grid_diagonal + 0x1p-40 * ctx->coord_max;
+        c5::launch_build_records(s, g, ctx->alpha_limit, 0);
+        if (!fs.head_clean) C5_HIP(ctx, hipMemsetAsync(fs.head.ptr, 0, static_cast<size_t>(padded) * sizeof(c5::EntryHead), s));
+        fs.head_clean = false;
+        c5::launch_entry_lists(s, g, ctx->xtab.as<double>(), ctx->ytab.as<double>(), im, fs.head.as<c5::EntryHead>(),
+                               fs.first.as<c5::Entry>(), fs.pool.as<c5::Entry>(), fs.entry_capacity, counters,
+                               ctx->adj_sticky.as<unsigned>(), 0, key_slack);
+        rc = enqueue_solids(ctx, fs, 0, s, table, any_solid);
+        if (rc) return rc;
+        c5::AdjointParams ap{};
+        c5::WalkParams& wp = ap.w;
+        wp.xrec = g.xrec;
+        wp.entry_head = fs.head.as<c5::EntryHead>();
+        wp.entry_first = fs.first.as<c5::Entry>();
+        wp.entry_pool = fs.pool.as<c5::Entry>();
+        wp.pool_capacity = fs.entry_capacity;
+        wp.key_slack = key_slack > 0.0 ? key_slack : 0.0;
+        wp.mask = any_solid ? fs.mask.as<uint32_t>() : nullptr;
+        wp.solids = table;
+        wp.Xtab = ctx->xtab.as<double>();
+        wp.Ytab = ctx->ytab.as<double>();
+        wp.im = im;
+        wp.max_steps = static_cast<uint32_t>(ctx->n_cells + 64);
+        wp.counters = counters;
+        wp.sticky = ctx->adj_sticky.as<unsigned>();
+        ap.grad_out = grad_out;
+        ap.lambda = ctx->adj_lambda.as<double>();
+        ap.grad_a = ga_dev;
+        ap.grad_q = gq_dev;
+        c5::launch_adjoint_walk(s, ap, 1);
+        c5::launch_adjoint_walk(s, ap, 2);
+        fs.head_clean = true;  // (pass 2 hands every head back cleared)
+    }
+    c5::launch_adjoint_permute(s, ga_dev, gq_dev, ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>(), ctx->n_cells,
+                               ga_out, gq_out);
+    C5_HIP(ctx, hipGetLastError());
+    C5_HIP(ctx, hipMemcpyAsync(ctx->adj_status, &counters->walk_overflow, kStatusWords * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    if (ctx->pipeline) {  // (the next frame's setup on the auxiliary stream waits for slot 0's buffers)
+        C5_HIP(ctx, hipEventRecord(fs.walk_done, s));
+        fs.walk_recorded = true;
+    }
+    ctx->adjoint_pending = true;
+    return C5_OK;
+}
+
+// After the stream drained: the adjoint's failure words (as finish_frame treats a frame's).
+int finish_adjoint(c5_context* ctx) {
+    if (!ctx->adjoint_pending) return C5_OK;
+    ctx->adjoint_pending = false;
+    const unsigned lost_rays = ctx->adj_status[0], refused = ctx->adj_status[1], overlap_rays = ctx->adj_status[2];
+    if (refused) {
+        int rc = drain(ctx);
+        if (rc) return rc;
+        const int64_t want = std::min<int64_t>(2 * (ctx->slots[0].entry_capacity + refused) + 8192, static_cast<int64_t>(16777214) * 64);
+        for (int k = 0; k < (ctx->pipeline ? kFrameSlots : 1); ++k) {
+            FrameSlot& o = ctx->slots[k];
+            if (o.entry_capacity >= want) continue;
+            o.entry_capacity = want;
+            C5_HIP(ctx, o.pool.ensure(static_cast<size_t>(want) * sizeof(c5::Entry)));
+            ++ctx->setup_epoch;
+        }
+        return fail(ctx, C5_RETRY, "adjoint: %u boundary entries found no room in the overflow pool (now %lld records): run it again",
+                    refused, static_cast<long long>(ctx->slots[0].entry_capacity));
+    }
+    if (lost_rays) return fail(ctx, C5_ERR_WALK, "adjoint: %u rays exceeded the walk step bound (malformed grid?)", lost_rays);
+    if (overlap_rays) {
+        ctx->overlap_seen = true;  // (what the next frame would find out for itself: bin_sort_resolve from now on)
+        ++ctx->setup_epoch;
+        return fail(ctx, C5_RETRY,
+                    "adjoint: %u rays met a boundary entry inside a stretch of cells they had walked: components of the grid "
+                    "interpenetrate; run it again (bin_sort_resolve from now on)", overlap_rays);
+    }
+    return C5_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1281,8 +1474,10 @@ void c5_destroy(c5_context* ctx) {
     if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
     DeviceBuffer* bufs[] = {&ctx->px, &ctx->py, &ctx->pz, &ctx->cell_vert, &ctx->cell_adj, &ctx->alpha,
                             &ctx->q, &ctx->bface, &ctx->xtab, &ctx->ytab, &ctx->out, &ctx->sticky,
-                            &ctx->offs64, &ctx->scratch64, &ctx->segs};
+                            &ctx->offs64, &ctx->scratch64, &ctx->segs, &ctx->adj_lambda, &ctx->adj_counters,
+                            &ctx->adj_sticky, &ctx->adj_grad, &ctx->adj_perm, &ctx->adj_io};
     if (ctx->host_sticky) (void)hipHostFree(ctx->host_sticky);
+    if (ctx->adj_status) (void)hipHostFree(ctx->adj_status);
     if (ctx->host_sb) (void)hipHostFree(ctx->host_sb);
     for (DeviceBuffer* b : bufs) b->release();
     for (FrameSlot& fs : ctx->slots) {
@@ -1487,6 +1682,7 @@ int c5_upload_grid(c5_context* ctx, const double* xyz, int64_t n_pts, const int3
         C5_HIP(ctx, hipMemcpy(ctx->q.ptr, q_src, cb * 8, hipMemcpyHostToDevice));
     }
     ctx->cell_perm = std::move(perm);
+    ++ctx->grid_serial;
     if (!bfaces.empty())
         C5_HIP(ctx, hipMemcpy(ctx->bface.ptr, bfaces.data(), bfaces.size() * 4, hipMemcpyHostToDevice));
     {
@@ -1952,6 +2148,44 @@ int c5_render(c5_context* ctx, float* out_host) {
         return copy_image_to_host(ctx, ctx->out.ptr, out_host, bytes);
     }
     return fail(ctx, C5_ERR_STATE, "entry buffer kept overflowing");
+}
+
+int c5_render_adjoint_device(c5_context* ctx, const void* grad_out_device, void* grad_alpha_device, void* grad_q_device) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (!grad_out_device || (ctx->n_cells > 0 && (!grad_alpha_device || !grad_q_device)))
+        return fail(ctx, C5_ERR_INVALID, "null adjoint pointer");
+    return enqueue_adjoint(ctx, static_cast<const float2*>(grad_out_device), static_cast<double*>(grad_alpha_device),
+                           static_cast<double*>(grad_q_device));
+}
+
+int c5_render_adjoint(c5_context* ctx, const float* grad_out_host, double* grad_alpha_host, double* grad_q_host) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (!grad_out_host || (ctx->n_cells > 0 && (!grad_alpha_host || !grad_q_host)))
+        return fail(ctx, C5_ERR_INVALID, "null adjoint pointer");
+    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_adjoint while c5_render_host_async frames are outstanding");
+    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    const size_t img_bytes = static_cast<size_t>(ctx->im.n_local_rows) * ctx->im.res_x * 2 * sizeof(float);
+    const size_t img_room = (img_bytes + 255) / 256 * 256;
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
+    C5_HIP(ctx, ctx->adj_io.ensure(img_room + 2 * n_cells * sizeof(double) + 16));
+    char* const io = ctx->adj_io.as<char>();
+    double* const ga = reinterpret_cast<double*>(io + img_room);
+    C5_HIP(ctx, hipMemcpyAsync(io, grad_out_host, img_bytes, hipMemcpyHostToDevice, ctx->stream));
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        rc = enqueue_adjoint(ctx, reinterpret_cast<const float2*>(io), ga, ga + n_cells);
+        if (rc) return rc;
+        rc = c5_synchronize(ctx);
+        if (rc == C5_RETRY) continue;
+        if (rc) return rc;
+        if (n_cells > 0) {
+            C5_HIP(ctx, hipMemcpy(grad_alpha_host, ga, n_cells * sizeof(double), hipMemcpyDeviceToHost));
+            C5_HIP(ctx, hipMemcpy(grad_q_host, ga + n_cells, n_cells * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        return C5_OK;
+    }
+    return fail(ctx, C5_ERR_STATE, "adjoint: entry buffer kept overflowing");
 }
 
 namespace {

@@ -57,6 +57,7 @@ const option_spec kOptions[] = {
     {"frames", 0, true, "number of frames of a sweep (grid stays on the GPU)", "1"},
     {"sweep", 0, true, "angle advanced per frame: X, Y, D or I", "Y"},
     {"sweep_step", 0, true, "sweep increment per frame, units of pi", "0.00555556"},
+    {"contribution", 0, true, "after the frame, write the grid with Contribution = Q dSum(I)/dQ and dI_dAbsorpCoef = dSum(I)/dAbsorpCoef per cell to this legacy .vtk (one frame, one GPU)", nullptr},
 };
 
 const option_spec* find_long(const std::string& name) {
@@ -83,6 +84,14 @@ long long to_integer(const std::string& opt, const std::string& v) {
     if (v.empty() || *end != '\0')
         throw std::runtime_error("the argument ('" + v + "') for option '--" + opt + "' is invalid");
     return r;
+}
+
+// "0", "0-7", "0,2,4": more than one device named?  (plane.cpp: parse_device_list reads the list itself, and says what is
+// wrong with a malformed one)
+bool more_than_one_device(const std::string& list) {
+    if (list.find(',') != std::string::npos) return true;
+    const auto dash = list.find('-');
+    return dash != std::string::npos && list.substr(0, dash) != list.substr(dash + 1);
 }
 
 }  // namespace
@@ -162,6 +171,7 @@ bool program_options(int argc, char** argv, std::ostream& out) {
         else if (n == "frames") cfg.frames = static_cast<std::size_t>(std::max(1ll, to_integer(n, v)));
         else if (n == "sweep") cfg.sweep = v;
         else if (n == "sweep_step") cfg.sweep_step = to_double(n, v);
+        else if (n == "contribution") cfg.contribution = v;
     };
 
     for (int i = 1; i < argc; ++i) {
@@ -210,6 +220,12 @@ bool program_options(int argc, char** argv, std::ostream& out) {
         throw std::runtime_error("the argument ('" + cfg.split + "') for option '--split' is invalid");
     if (cfg.row_layout != "auto" && cfg.row_layout != "blocks" && cfg.row_layout != "tiles")
         throw std::runtime_error("the argument ('" + cfg.row_layout + "') for option '--row_layout' is invalid");
+    if (!cfg.contribution.empty()) {  // the adjoint of ONE frame on ONE GPU
+        if (cfg.frames > 1) throw std::runtime_error("option '--contribution' cannot be used with '--frames' above 1");
+        if (cfg.bench > 0) throw std::runtime_error("option '--contribution' cannot be used with '--bench'");
+        if (more_than_one_device(cfg.devices))
+            throw std::runtime_error("option '--contribution' cannot be used with more than one of '--devices'");
+    }
     if (!(have_file && have_dest)) {  // main.cpp:43-51
         out << "Error! Source filename and destination filename must be specified" << std::endl;
         print_usage(out);

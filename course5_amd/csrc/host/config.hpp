@@ -48,6 +48,7 @@ struct render_config {
     std::size_t frames = 1;       // > 1: sweep, grid stays resident on the GPU
     std::string sweep = "Y";      // which angle advances per frame: X, Y, D or I
     double sweep_step = 1.0 / 180.0;
+    std::string contribution;     // after the frame: the grid with each cell's share of the image's intensity (adjoint render)
 };
 
 // Process-wide configuration, as in the reference (config.hpp:7-32).

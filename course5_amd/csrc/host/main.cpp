@@ -22,6 +22,7 @@
 #include "config.hpp"
 #include "plane.hpp"
 #include "scene.hpp"
+#include "vtk_io.hpp"
 
 namespace {
 const auto& timestamp = std::chrono::high_resolution_clock::now;
@@ -354,6 +355,18 @@ int main(int argc, char** argv) try {
     std::cout << "Ray-tracing completed in " << ms_between(t1, t2) << " ms. " << std::endl;  // main.cpp:131-135
 
     if (config.bench == 0) write_frame(result, frame_name(config.destination, 0, config.frames));
+    if (!config.contribution.empty()) {
+        // adjoint render of this frame with the weights (g_tau, g_I) = (0, 1): each cell's share of the image's intensity,
+        // Q dSum(I)/dQ (sums to Sum(I): I is linear in Q), and dSum(I)/dAbsorpCoef, beside the grid and its scalars as read
+        std::vector<double> d_alpha, d_q;
+        base_plane.intensity_gradients(d_alpha, d_q);
+        const object3d_data& d = *acc_disk.get_pointer();
+        std::vector<double> share(d_q.size());
+        for (std::size_t c = 0; c < share.size(); ++c) share[c] = d.value1[c] * d_q[c];
+        write_legacy_vtk(config.contribution, d.points, d.cells,
+                         {{"AbsorpCoef", &d.value0}, {"radEnLooseRate", &d.value1}, {"Contribution", &share}, {"dI_dAbsorpCoef", &d_alpha}});
+        std::cout << "Cell contributions written to " << config.contribution << std::endl;
+    }
     if (config.print_stats) {
         const c5_stats st = base_plane.stats();
         std::cout << "GPU frame: " << st.ms_total << " ms (transform " << st.ms_transform << ", records " << st.ms_records

@@ -348,6 +348,7 @@ plane::plane(std::size_t res_x, std::size_t res_y, std::vector<object3d_base> ob
         }
     }
     _views.solids.resize(static_cast<std::size_t>(next_slot));
+    _n_cells = cells.size() / 4;
 
     // blocks layout: equal blocks to start with; the first frame counts its segments per row, and the blocks are
     // balanced by that before the second (read_row_costs / apply_blocks)
@@ -782,3 +783,15 @@ c5_stats plane::stats() {
 }
 
 std::size_t plane::count_all_intersections() { return static_cast<std::size_t>(stats().segments); }
+
+void plane::intensity_gradients(std::vector<double>& d_alpha, std::vector<double>& d_q) {
+    if (_ctx.size() != 1) throw std::runtime_error("the adjoint render runs on one device");
+    if (!_flight.empty() || !_parked.empty()) throw std::runtime_error("the adjoint render wants no frame in flight");
+    int rows = 0;
+    check(c5_local_rows(_ctx[0], &rows), "c5_local_rows");
+    std::vector<float> weights(static_cast<std::size_t>(rows) * _x * 2, 0.0f);
+    for (std::size_t p = 1; p < weights.size(); p += 2) weights[p] = 1.0f;  // (g_tau, g_I) = (0, 1)
+    d_alpha.assign(_n_cells, 0.0);
+    d_q.assign(_n_cells, 0.0);
+    check(c5_render_adjoint(_ctx[0], weights.data(), d_alpha.data(), d_q.data()), "c5_render_adjoint");
+}

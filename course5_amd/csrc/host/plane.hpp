@@ -97,6 +97,9 @@ public:
     // select the cell values for ch0/ch1 as in the reference; only (alpha, Q) is meaningful there and here.
     object2d trace_rays(tetra_value value_alpha, tetra_value value_Q);
     std::size_t count_all_intersections();  // plane.cpp:3-12 (segments of the last frame, all devices)
+    // Adjoint render (c5_render_adjoint) of the current view with the weights g_tau = 0, g_I = 1 on every pixel: d sum(I) /
+    // d alpha and d sum(I) / d Q of every cell of the merged volume grid, in its order.  One device, no frame in flight.
+    void intensity_gradients(std::vector<double>& d_alpha, std::vector<double>& d_q);
 
     std::size_t get_x() const { return _x; }
     std::size_t get_y() const { return _y; }
@@ -139,6 +142,7 @@ private:
     bool retry_seen();                      // any device's stats() ran into C5_RETRY since the last look (cleared)
     std::vector<c5_context*> _ctx;
     std::vector<int> _devices;
+    std::size_t _n_cells = 0;  // of the merged volume grid
     exchange_mode _exchange = exchange_mode::host;
     std::size_t _x = 0, _y = 0;
     std::vector<int> _slot_of_object;  // -1: part of the volume grid, >= 0: solid slot

@@ -688,3 +688,41 @@ void write_png(const std::string& path, const float* image, int res_x, int res_y
     png_chunk(f, "IEND", nullptr, 0);
     if (!f) throw std::runtime_error("error while writing '" + path + "'");
 }
+
+namespace {
+template <class T>
+void put_big_endian(std::vector<unsigned char>& out, T v) {
+    unsigned char b[sizeof(T)];
+    std::memcpy(b, &v, sizeof(T));
+    for (size_t k = 0; k < sizeof(T); ++k) out.push_back(b[sizeof(T) - 1 - k]);
+}
+}  // namespace
+
+void write_legacy_vtk(const std::string& path, const std::vector<double>& points, const std::vector<int32_t>& tets,
+                      const std::vector<std::pair<std::string, const std::vector<double>*>>& cell_scalars) {
+    const size_t n_pts = points.size() / 3, n_cells = tets.size() / 4;
+    for (const auto& a : cell_scalars)
+        if (a.second->size() != n_cells) throw std::runtime_error("write_legacy_vtk: array '" + a.first + "' has the wrong length");
+    std::vector<unsigned char> buf;
+    auto text = [&](const std::string& s) { buf.insert(buf.end(), s.begin(), s.end()); };
+    text("# vtk DataFile Version 3.0\ncourse: cell contributions to the image\nBINARY\nDATASET UNSTRUCTURED_GRID\n");
+    text("POINTS " + std::to_string(n_pts) + " double\n");
+    for (size_t i = 0; i < 3 * n_pts; ++i) put_big_endian(buf, points[i]);
+    text("\nCELLS " + std::to_string(n_cells) + " " + std::to_string(5 * n_cells) + "\n");
+    for (size_t c = 0; c < n_cells; ++c) {
+        put_big_endian(buf, int32_t{4});
+        for (int v = 0; v < 4; ++v) put_big_endian(buf, tets[4 * c + v]);
+    }
+    text("\nCELL_TYPES " + std::to_string(n_cells) + "\n");
+    for (size_t c = 0; c < n_cells; ++c) put_big_endian(buf, int32_t{10});  // VTK_TETRA
+    text("\nCELL_DATA " + std::to_string(n_cells) + "\n");
+    for (const auto& a : cell_scalars) {
+        text("SCALARS " + a.first + " double 1\nLOOKUP_TABLE default\n");
+        for (double v : *a.second) put_big_endian(buf, v);
+        text("\n");
+    }
+    std::ofstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("cannot write '" + path + "'");
+    f.write(reinterpret_cast<const char*>(buf.data()), static_cast<std::streamsize>(buf.size()));
+    if (!f) throw std::runtime_error("cannot write '" + path + "'");
+}

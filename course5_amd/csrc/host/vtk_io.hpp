@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 struct vtk_grid {
@@ -22,6 +23,11 @@ struct vtk_grid {
 
 // Throws std::runtime_error with a readable message on malformed input.
 vtk_grid read_legacy_vtk(const std::string& path);
+
+// Legacy-VTK UNSTRUCTURED_GRID, BINARY (big-endian): the points (double), the tetrahedra (CELLS / CELL_TYPES 10) and one
+// double CELL_DATA SCALARS array per entry, in order — what read_legacy_vtk reads back.
+void write_legacy_vtk(const std::string& path, const std::vector<double>& points, const std::vector<int32_t>& tets,
+                      const std::vector<std::pair<std::string, const std::vector<double>*>>& cell_scalars);
 
 // image[row][col][2] fp32 (col fastest) -> .vti with dims (res_x, res_y, 1), origin 0, spacing 1,
 // Float64 x 2 "ImageScalars" (object2d.cpp:12-13).

@@ -254,6 +254,29 @@ int c5_render(c5_context* ctx, float* out_host);
 int c5_render_device(c5_context* ctx, void* out_device);
 int c5_synchronize(c5_context* ctx);
 
+/* --- adjoint render ----------------------------------------------------------------------------
+ * Gradients of the frame c5_render would produce NOW (same grid, scalars, solids, image, rows, view and alpha limit; no
+ * render needs to come first) with respect to every cell's AbsorpCoef (alpha) and radEnLooseRate (Q), weighted by an
+ * upstream image grad_out[local_rows][res_x][2] fp32 in the output's own layout (channel 0: the weight of tau, channel 1:
+ * the weight of I):
+ *     grad_alpha[c] = sum over the pixels p and the segments of cell c on p's ray of g_tau(p) dtau/dalpha_c + g_I(p) dI/dalpha_c
+ *     grad_q[c]     = sum of g_I(p) dI/dQ_c
+ * The derivative of the reference's integral as written (line.cpp:176-227): the alpha limit clamps (a clamped alpha has
+ * dI/dalpha = 0; tau takes the raw alpha), a cell with clamped alpha < DBL_EPSILON neither absorbs nor emits (dI/d. = 0),
+ * solid-marked pixels contribute nothing, whatever "integration", "depth_split", "lds_stage" or "tile" say.
+ * grad_alpha / grad_q: n_cells fp64 each, in the caller's cell order (c5_upload_grid's), overwritten.
+ * The sums are fp64 atomics added in arrival order: the results are NOT bit-reproducible from run to run (relative
+ * differences of ~1e-15).
+ * Side effects: none on the options, the statistics or the images — a c5_render after an adjoint returns bit for bit
+ * what it would have returned without it (the per-view data it reused are rebuilt: "view_cache").  The first call
+ * allocates what the adjoint needs (8 bytes per local pixel, 16 per cell, the status words); a context that never
+ * calls it uses no more memory than before.
+ * c5_render_adjoint: synchronous, host arrays; retries by itself on C5_RETRY, like c5_render.
+ * c5_render_adjoint_device: asynchronous on the context's stream, device arrays; its status (C5_RETRY included: run it
+ * again) is reported by the next call that waits for the stream, like c5_render_device's. */
+int c5_render_adjoint(c5_context* ctx, const float* grad_out_host, double* grad_alpha_host, double* grad_q_host);
+int c5_render_adjoint_device(c5_context* ctx, const void* grad_out_device, void* grad_alpha_device, void* grad_q_device);
+
 /* --- frames delivered to host memory, pipelined ----------------------------------------------------
  * plane::trace_rays hands back HOST pixels (plane.cpp:144-172); over PCIe Gen5 a 2400x1800 image is
  * 0.65 ms of transfer beside 0.7 ms of rendering, so the two are overlapped: c5_render_host_async renders

@@ -1,0 +1,204 @@
+"""numpy restatement of the adjoint render (include/course5_hip.h: c5_render_adjoint) from per-pixel segment lists.
+
+A pixel's segments come as rows {tet, z_hi, dz} in the reference's order: sorted by descending z_hi (line.cpp:138, what
+the port oracle's probes return), the recurrence run from the last row to the first (line.cpp:206), so the first row is
+the segment nearest the viewer.  Number them k = 1..n in processing order (row n - k):
+    a_k = min(alpha_k, limit), active_k = !(a_k < DBL_EPSILON), E_k = exp(-a_k dz_k),
+    I_k = E_k I_{k-1} + Q_k (1 - E_k) / a_k (active), tau = sum dz_k alpha_k, T_k = prod_{j > k} E_j
+    dtau/dalpha_k = dz_k, dI/dQ_k = T_k (1 - E_k) / a_k, dI/dalpha_k = T_k [Q_k (dz_k E_k / a_k - (1 - E_k) / a_k^2) - dz_k E_k I_{k-1}]
+(dI/d. = 0 for an inactive segment, dI/dalpha = 0 for a clamped one).
+
+Whole images take their segment lists from segment_lists, the reference's binning and pairing restated in numpy: the port
+oracle's probes give the same lists (tests/test_adjoint_cpu.py checks them pixel by pixel) but re-bin the grid once per
+probed pixel, too slow for every pixel of an image.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+EPS = np.finfo(np.float64).eps
+
+
+def _bracket_over_q_dz2(x: float) -> float:
+    """(x e^-x - (1 - e^-x)) / x^2 by its series (-1/2 + x/3 - x^2/8 + ...) for small x, as written otherwise."""
+    if x < 0.125:
+        return sum((-1.0) ** (m + 1) * (m + 1) / math.factorial(m + 2) * x ** m for m in range(14))
+    return (x * math.exp(-x) + math.expm1(-x)) / (x * x)
+
+
+def forward(segs, alpha, q, limit: float = 2.5) -> tuple[float, float]:
+    """(tau, I) of one pixel in fp64 (the rearranged recurrence, for finite differences)."""
+    tau, I = 0.0, 0.0
+    for tet, _z, dz in segs:
+        tau += dz * alpha[int(tet)]
+    for tet, _z, dz in segs[::-1]:
+        c = int(tet)
+        a = min(alpha[c], limit)
+        if a < EPS:
+            continue
+        I = math.exp(-a * dz) * I + q[c] * (-math.expm1(-a * dz)) / a
+    return tau, I
+
+
+def pixel_terms(segs, alpha, q, limit: float = 2.5):
+    """Per segment (in the rows' order): (cell, dtau/dalpha, dI/dalpha, dI/dQ)."""
+    n = len(segs)
+    out = [None] * n
+    a_eff = [min(alpha[int(s[0])], limit) for s in segs]
+    active = [not (a < EPS) for a in a_eff]
+    # T of row i = prod over the rows before it (nearer the viewer) of E
+    T = np.ones(n)
+    for i in range(1, n):
+        T[i] = T[i - 1] * (math.exp(-a_eff[i - 1] * segs[i - 1][2]) if active[i - 1] else 1.0)
+    I = 0.0
+    for i in range(n - 1, -1, -1):
+        c, dz = int(segs[i][0]), float(segs[i][2])
+        a, Q = a_eff[i], q[c]
+        dI_da = dI_dq = 0.0
+        if active[i]:
+            E = math.exp(-a * dz)
+            s = -math.expm1(-a * dz) / a
+            dI_dq = T[i] * s
+            if not alpha[c] > limit:
+                dI_da = T[i] * (Q * dz * dz * _bracket_over_q_dz2(a * dz) - dz * E * I)
+            I = E * I + Q * s
+        out[i] = (c, dz, dI_da, dI_dq)
+    return out
+
+
+def gradients(probes, weights, alpha, q, n_cells: int, limit: float = 2.5):
+    """grad_alpha, grad_q [n_cells] from segment lists `probes` (one per pixel) and the pixels' weights (g_tau, g_I)."""
+    ga = np.zeros(n_cells)
+    gq = np.zeros(n_cells)
+    for segs, (g_tau, g_I) in zip(probes, weights):
+        if len(segs) == 0 or (g_tau == 0.0 and g_I == 0.0):
+            continue
+        for c, dtau, dI_da, dI_dq in pixel_terms(segs, alpha, q, limit):
+            ga[c] += g_tau * dtau + g_I * dI_da
+            gq[c] += g_I * dI_dq
+    return ga, gq
+
+
+def rotate(xyz, rots):
+    """The view transform (tetra.cpp:44-62, applied in order; angles in radians as c5_set_view takes them)."""
+    p = np.array(xyz, dtype=np.float64).reshape(-1, 3)
+    for axis, angle, x0 in np.asarray(rots, dtype=np.float64).reshape(-1, 3):
+        co, si = math.cos(angle), math.sin(angle)
+        if int(axis) == 0:
+            y, z = p[:, 1].copy(), p[:, 2].copy()
+            p[:, 1], p[:, 2] = y * co - z * si, y * si + z * co
+        else:
+            x, z = p[:, 0] - x0, p[:, 2].copy()
+            p[:, 0], p[:, 2] = x * co - z * si + x0, x * si + z * co
+    return p
+
+
+_FACES = ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3))  # plane.cpp:30-37
+
+
+def segment_lists(xyz, cells, rots, res_x, res_y, bounds):
+    """Every pixel's segments, as the reference bins and pairs them (plane.cpp:184-192, line.cpp:99-138): a cell whose
+    projection holds the pixel centre (two covering faces; four: two pairs in face order) gives {cell, z_hi, dz}.
+    Returns (pixel, cell, z_hi, dz) arrays sorted by pixel and then by ASCENDING z_hi - the order the recurrence runs
+    in (line.cpp:206); pixel = row * res_x + col over the full image."""
+    P = rotate(xyz, rots)[np.asarray(cells).reshape(-1, 4)]  # [C, 4, 3]
+    b = np.asarray(bounds, dtype=np.float64)
+    sx, sy = (b[0] - b[1]) / (res_x - 1.0), (b[2] - b[3]) / (res_y - 1.0)
+    X = b[1] + sx * np.arange(res_x)
+    Y = b[3] + sy * np.arange(res_y)
+    lo, hi = P[:, :, :2].min(1), P[:, :, :2].max(1)
+    c0 = np.clip(np.floor((lo[:, 0] - b[1]) / sx) - 1, 0, res_x - 1).astype(np.int64)
+    c1 = np.clip(np.ceil((hi[:, 0] - b[1]) / sx) + 1, 0, res_x - 1).astype(np.int64)
+    r0 = np.clip(np.floor((lo[:, 1] - b[3]) / sy) - 1, 0, res_y - 1).astype(np.int64)
+    r1 = np.clip(np.ceil((hi[:, 1] - b[3]) / sy) + 1, 0, res_y - 1).astype(np.int64)
+    nx, ny = c1 - c0 + 1, r1 - r0 + 1
+    cnt = nx * ny
+    cid = np.repeat(np.arange(len(P)), cnt)
+    local = np.arange(cnt.sum()) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    ii = c0[cid] + local % nx[cid]
+    jj = r0[cid] + local // nx[cid]
+    x, y = X[ii], Y[jj]
+    cover = np.zeros((len(cid), 4), dtype=bool)
+    zf = np.zeros((len(cid), 4))
+    for f, (ia, ib, ic) in enumerate(_FACES):
+        A, B, Cc = P[cid, ia], P[cid, ib], P[cid, ic]
+        e0 = (B[:, 0] - A[:, 0]) * (y - A[:, 1]) - (B[:, 1] - A[:, 1]) * (x - A[:, 0])
+        e1 = (Cc[:, 0] - B[:, 0]) * (y - B[:, 1]) - (Cc[:, 1] - B[:, 1]) * (x - B[:, 0])
+        e2 = (A[:, 0] - Cc[:, 0]) * (y - Cc[:, 1]) - (A[:, 1] - Cc[:, 1]) * (x - Cc[:, 0])
+        cover[:, f] = ((e0 >= 0) & (e1 >= 0) & (e2 >= 0)) | ((e0 <= 0) & (e1 <= 0) & (e2 <= 0))
+        # line.cpp:158-171
+        Aa = (B[:, 0] - A[:, 0]) * (Cc[:, 2] - A[:, 2]) - (Cc[:, 0] - A[:, 0]) * (B[:, 2] - A[:, 2])
+        Bb = (B[:, 1] - A[:, 1]) * (Cc[:, 2] - A[:, 2]) - (Cc[:, 1] - A[:, 1]) * (B[:, 2] - A[:, 2])
+        m = (B[:, 0] - A[:, 0]) * (Cc[:, 1] - A[:, 1]) - (Cc[:, 0] - A[:, 0]) * (B[:, 1] - A[:, 1])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            zf[:, f] = ((y - A[:, 1]) * Aa - (x - A[:, 0]) * Bb) / m + A[:, 2]
+    n_cov = cover.sum(1)
+    out = []
+    for want in (2, 4):
+        sel = n_cov == want
+        order = np.argsort(~cover[sel], axis=1, kind="stable")  # covering faces first, in face order
+        z = np.take_along_axis(zf[sel], order, axis=1)
+        for k in range(want // 2):
+            za, zb = z[:, 2 * k], z[:, 2 * k + 1]
+            zh = np.maximum(za, zb)
+            out.append((jj[sel] * res_x + ii[sel], cid[sel], zh, zh - np.minimum(za, zb)))
+    pix, cell, zh, dz = (np.concatenate([o[k] for o in out]) for k in range(4))
+    keep = dz > 0
+    pix, cell, zh, dz = pix[keep], cell[keep], zh[keep], dz[keep]
+    o = np.lexsort((zh, pix))
+    return pix[o], cell[o], zh[o], dz[o]
+
+
+def image_gradients(xyz, cells, alpha, q, rots, res_x, res_y, bounds, weights, limit: float = 2.5, rows=None, skip=None):
+    """The helper over whole images, vectorised over the pixels.  weights: [len(rows), res_x, 2] (g_tau, g_I) of the
+    global rows `rows` (default: all); skip: optional bool [len(rows), res_x], True = the pixel contributes nothing
+    (solid).  Returns (grad_alpha, grad_q, tau, I) with tau / I the fp64 images of those rows."""
+    rows = np.arange(res_y) if rows is None else np.asarray(rows)
+    alpha, q = np.asarray(alpha, np.float64), np.asarray(q, np.float64)
+    pix, cell, _zh, dz = segment_lists(xyz, cells, rots, res_x, res_y, bounds)
+    row_slot = np.full(res_y, -1)
+    row_slot[rows] = np.arange(len(rows))
+    lp = row_slot[pix // res_x] * res_x + pix % res_x
+    sel = row_slot[pix // res_x] >= 0
+    lp, cell, dz = lp[sel], cell[sel], dz[sel]
+    n_px = len(rows) * res_x
+    w = np.asarray(weights, np.float64).reshape(n_px, 2).copy()
+    if skip is not None:
+        w[np.asarray(skip).reshape(-1)] = 0.0
+    # [pixel, k] matrices, k = processing order (deepest first)
+    starts = np.searchsorted(lp, np.arange(n_px))
+    k = np.arange(len(lp)) - starts[lp]
+    M = int(k.max()) + 1 if len(k) else 1
+    C = np.full((n_px, M), -1)
+    D = np.zeros((n_px, M))
+    C[lp, k], D[lp, k] = cell, dz
+    valid = C >= 0
+    a_raw = np.where(valid, alpha[np.maximum(C, 0)], 0.0)
+    Q = np.where(valid, q[np.maximum(C, 0)], 0.0)
+    a = np.minimum(a_raw, limit)
+    active = valid & ~(a < EPS)
+    x = np.where(active, a * D, 0.0)
+    E = np.exp(-x)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        S_over_q = np.where(active, -np.expm1(-x) / np.where(active, a, 1.0), 0.0)
+        ser = sum((-1.0) ** (m + 1) * (m + 1) / math.factorial(m + 2) * x ** m for m in range(14))
+        direct = (x * E + np.expm1(-x)) / np.where(x > 0, x * x, 1.0)
+    br = Q * D * D * np.where(x < 0.125, ser, direct)
+    lam = np.cumsum(x, axis=1)
+    T = np.exp(-(lam[:, -1:] - lam))
+    I_prev = np.zeros_like(D)
+    I = np.zeros(n_px)
+    for j in range(M):
+        I_prev[:, j] = I
+        I = np.where(active[:, j], E[:, j] * I + Q[:, j] * S_over_q[:, j], I)
+    tau = (np.where(valid, D * a_raw, 0.0)).sum(1)
+    dI_dq = np.where(active, T * S_over_q, 0.0)
+    dI_da = np.where(active & ~(a_raw > limit), T * (br - D * E * I_prev), 0.0)
+    g_tau, g_I = w[:, :1], w[:, 1:]
+    ga = np.zeros(len(alpha))
+    gq = np.zeros(len(alpha))
+    np.add.at(ga, C[valid], (g_tau * D + g_I * dI_da)[valid])
+    np.add.at(gq, C[valid], (np.broadcast_to(g_I, D.shape) * dI_dq)[valid])
+    return ga, gq, tau.reshape(len(rows), res_x), I.reshape(len(rows), res_x)
