@@ -28,7 +28,7 @@ EXPORTS = [
     "c5_download_view_points", "c5_face_adjacency", "c5_set_stream",
     "c5_set_row_range", "c5_get_row_costs", "c5_weld_points",
     "c5_render_host_async", "c5_render_host_wait", "c5_host_alloc", "c5_host_free", "c5_render_frame_rows_async",
-    "c5_render_adjoint", "c5_render_adjoint_device",
+    "c5_render_adjoint", "c5_render_adjoint_device", "c5_render_tangent", "c5_render_tangent_device",
 ]
 
 
@@ -102,6 +102,8 @@ def load_library() -> C.CDLL:
     lib.c5_host_free.argtypes = [vp, vp]
     lib.c5_render_adjoint.argtypes = [vp, C.POINTER(C.c_float), dp, dp]
     lib.c5_render_adjoint_device.argtypes = [vp, vp, vp, vp]
+    lib.c5_render_tangent.argtypes = [vp, dp, dp, C.POINTER(C.c_float)]
+    lib.c5_render_tangent_device.argtypes = [vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("c5_destroy", "c5_last_error"):
             getattr(lib, name).restype = C.c_int
@@ -283,6 +285,42 @@ class Context:
         self._check(self.lib.c5_render_adjoint_device(
             self.handle, C.c_void_p(ptr(grad_out, torch.float32, (self.local_rows, self.res_x, 2))),
             C.c_void_p(ptr(grad_alpha, torch.float64, (self.n_cells,))), C.c_void_p(ptr(grad_q, torch.float64, (self.n_cells,)))))
+
+    # -- tangent render ----------------------------------------------------------------------------
+    def render_tangent(self, d_alpha=None, d_q=None) -> np.ndarray:
+        """The change of the frame render() would produce now for a change (d_alpha, d_q) of the cells' scalars ([n_cells]
+        each in the order of upload_grid; None: zero): float32 [local_rows, res_x, 2] (tau_dot, I_dot).  Synchronous;
+        retries by itself.  Bit-reproducible."""
+        def direction(d):
+            if d is None:
+                return None
+            d = np.ascontiguousarray(d, dtype=np.float64)
+            if d.shape != (self.n_cells,):
+                raise ValueError(f"a direction must hold one value per cell ({self.n_cells}), not {list(d.shape)}")
+            return d
+
+        da, dq = direction(d_alpha), direction(d_q)
+        out = np.zeros((self.local_rows, self.res_x, 2), dtype=np.float32)
+        self._check(self.lib.c5_render_tangent(self.handle, None if da is None else _dp(da), None if dq is None else _dp(dq),
+                                               out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def render_tangent_device(self, d_alpha, d_q, out):
+        """Asynchronous form on the context's stream, in device memory: torch tensors on this context's GPU (d_alpha / d_q
+        float64 [n_cells] contiguous or None for zero, out float32 [local_rows, res_x, 2] contiguous) or raw device
+        pointers (0: zero).  The status comes with the next synchronize() (C5_RETRY: run it again)."""
+        def ptr(t, dtype, shape):
+            if t is None or isinstance(t, int):
+                return t or 0
+            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"expected a contiguous {dtype} tensor of shape {shape} on the GPU")
+            return t.data_ptr()
+
+        import torch
+        self._check(self.lib.c5_render_tangent_device(
+            self.handle, C.c_void_p(ptr(d_alpha, torch.float64, (self.n_cells,)) or None),
+            C.c_void_p(ptr(d_q, torch.float64, (self.n_cells,)) or None),
+            C.c_void_p(ptr(out, torch.float32, (self.local_rows, self.res_x, 2)))))
 
     # -- frames delivered to host memory, pipelined -------------------------------------------------
     def host_image(self, full: bool = False) -> np.ndarray:

@@ -18,6 +18,18 @@
 //   adjoint_resolve   the same for the per-pixel sorted segment lists of bin_sort_resolve ("algorithm" 1).
 //   adjoint_permute   device order -> the caller's (c5_upload_grid, "cell_order").
 //
+// The tangent (forward mode, c5_render_tangent*): the change (tau_dot, I_dot) of every pixel for a change (dalpha, dQ) of
+// the cells' scalars, the same terms carried forward along the ray instead of scattered back:
+//     tau_dot = sum_k dz_k dalpha_k                                              (raw alpha, every segment)
+//     I_dot_k = E_k I_dot_{k-1} + dQ_k (1 - E_k) / a_k + dalpha'_k [Q_k (dz_k E_k / a_k - (1 - E_k) / a_k^2) - dz_k E_k I_{k-1}]
+// (active segments; inactive: I_dot_k = I_dot_{k-1}; dalpha'_k = 0 where alpha_k is clamped), i.e. segment_terms with
+// T = 1.  It is exactly the transpose of the adjoint: <g, J v> = <J^T g, v>.
+//   tangent_gather    the caller's (dalpha, dQ) -> one 16-byte {dalpha, dQ} per cell in device order.
+//   tangent_walk      the step of adjoint_walk<1> once, I, I_dot and tau_dot in registers: (tau_dot, I_dot) per pixel.
+//   tangent_resolve   the same over the per-pixel sorted segment lists of bin_sort_resolve ("algorithm" 1).
+// No atomics and no pre-pass: every pixel's sum runs in the reference's order on one lane, so the tangent IS
+// bit-reproducible from run to run.
+//
 // The sums are fp64 atomics, added in arrival order: the gradients are NOT bit-reproducible from run to run (the last bits
 // move).  This file is compiled with -munsafe-fp-atomics (build.py): the adds are global_atomic_add_f64, no
 // compare-and-swap loop.
@@ -350,6 +362,158 @@ __global__ __launch_bounds__(256) void adjoint_permute(const double* __restrict_
     gq_out[d] = gq_dev[i];
 }
 
+// The tangent of one active segment's I: dQ (1 - E) / a + dalpha' (dI/dalpha at T = 1) + E I_dot_{k-1}; I_k from I_{k-1}.
+__device__ __forceinline__ void tangent_step(double a, bool clamped, double q, double dz, double E, double da, double dq,
+                                             double& I, double& I_dot) {
+    const adj::SegmentTerms t = adj::segment_terms(a, q, dz, E, 1.0, I);
+    double src = dq * t.dI_dq;
+    if (!clamped) src = fma(da, t.dI_da, src);  // (a clamped alpha does not move: line.cpp:216)
+    I_dot = fma(E, I_dot, src);
+    I = t.I_next;
+}
+
+// One wavefront per 8x8 pixel tile, one lane per pixel, as adjoint_walk; nothing is shared between the lanes, so a lane
+// leaves the loop when its ray ends.
+__global__ __launch_bounds__(64) void tangent_walk(TangentParams A) {
+    using namespace adj;
+    const WalkParams& P = A.w;
+    const ImageParams& im = P.im;
+    const D2* __restrict__ dir = reinterpret_cast<const D2*>(A.dir);
+    const int tiles_x = (im.res_x + 7) / 8;
+    const int ty = static_cast<int>(blockIdx.x) / tiles_x, tx = static_cast<int>(blockIdx.x) - ty * tiles_x;
+    const int lane = static_cast<int>(threadIdx.x);
+    const int col = tx * 8 + (lane & 7), lrow = ty * 8 + (lane >> 3);
+    const bool in_image = (col < im.res_x) && (lrow < im.n_local_rows);
+
+    unsigned n_step = 0, overflow = 0;
+    bool skipped = false;
+    double key_taken = -DBL_MAX;
+    double x = 0.0, y = 0.0, w_cur = -DBL_MAX, carry = 0.0;
+    EntryHead ent{0, 0};
+    int cell = -1;
+    size_t lp = 0;
+    double I = 0.0, I_dot = 0.0, tau_dot = 0.0;
+
+    if (in_image) {
+        lp = static_cast<size_t>(lrow) * im.res_x + col;
+        const uint32_t mv = P.mask ? P.mask[lp] : 0u;
+        if (!mv) {  // (a solid-marked pixel shows the solid: line.cpp:177-179, nothing of the grid)
+            x = P.Xtab[col];
+            y = P.Ytab[global_row_of(im, lrow)];
+            ent = load_entry_head(P.entry_head + lp);
+            if (ent.count > 0) cell = next_entry<true>(P, lp, ent, w_cur, carry, -DBL_MAX, -DBL_MAX, skipped);
+            key_taken = w_cur;
+        }
+    }
+
+    CellRegs cur;
+    D2 d_cur{0.0, 0.0};
+    if (cell >= 0) {
+        load_cell(cur, P.xrec, cell);
+        d_cur = dir[cell];
+    }
+
+    while (cell >= 0) {
+        // the step of walk_composite<*, 0> (walk_kernels.hip) as adjoint_walk has it: the same segments
+        const StepGeometry sg = step_geometry(cur, x, y);
+        ++n_step;
+        const bool has_exit = sg.w_exit < INFINITY;
+        const double dz = sg.w_exit - carry;
+        const bool contributes = dz > 0.0 && dz < INFINITY;
+        int nb = -1;
+        double carry_next = carry;
+        if (has_exit) {
+            carry_next = sg.w_exit;
+            w_cur = fmax(w_cur, sg.w_exit);
+            const uint32_t id = sg.w_out & kIdMask;
+            if (id != kNoCell) nb = static_cast<int>(id);
+        }
+        if (nb >= 0 && n_step >= P.max_steps) {
+            overflow = 1;
+            nb = -1;
+        } else if (nb < 0 && !overflow) {
+            nb = next_entry<true>(P, lp, ent, w_cur, carry_next, key_taken, has_exit ? sg.w_exit : -DBL_MAX, skipped);
+            key_taken = w_cur;
+        }
+        CellRegs nxt;
+        D2 d_nxt{0.0, 0.0};
+        if (nb >= 0) {
+            load_cell(nxt, P.xrec, nb);
+            d_nxt = dir[nb];
+        }
+
+        if (contributes) {
+            const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+            tau_dot = fma(dz, d_cur.a, tau_dot);  // d tau / d alpha (line.cpp:189: raw alpha)
+            if (a != 0.0) tangent_step(a, a != a_raw, q, dz, exp_nonpositive(-a * dz), d_cur.a, d_cur.b, I, I_dot);
+        }
+        cell = nb;
+        carry = carry_next;
+        cur = nxt;
+        d_cur = d_nxt;
+    }
+
+    if (in_image) {
+        A.out[lp] = make_float2(static_cast<float>(tau_dot), static_cast<float>(I_dot));
+        __builtin_nontemporal_store(0ll, reinterpret_cast<long long*>(P.entry_head + lp));  // cleared, as the walk leaves them
+    }
+    const unsigned s_ovf = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(overflow != 0u)));
+    const unsigned s_skip = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(skipped)));
+    if (lane == 0) {
+        if (s_ovf) atomicAdd(&P.counters->walk_overflow, s_ovf);
+        if (s_skip) atomicAdd(&P.counters->overlap_rays, s_skip);
+    }
+}
+
+// adjoint_resolve's twin: the same sort, the same back-to-front order, the tangent carried along.
+__global__ __launch_bounds__(256) void tangent_resolve(GridView g, ImageParams im, const int64_t* __restrict__ offs,
+                                                       AdjSegment* __restrict__ segs, const uint32_t* __restrict__ mask,
+                                                       double alpha_limit, const double2* __restrict__ dir_v,
+                                                       float2* __restrict__ out) {
+    const int64_t lp = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    if (lp >= n_px) return;
+    const D2* __restrict__ dir = reinterpret_cast<const D2*>(dir_v);
+    double I = 0.0, I_dot = 0.0, tau_dot = 0.0;
+    if (!(mask && mask[lp])) {
+        AdjSegment* const list = segs + offs[lp];
+        const int n = static_cast<int>(offs[lp + 1] - offs[lp]);
+        for (int gap = n / 2; gap > 0; gap = (gap == 2) ? 1 : static_cast<int>(gap / 2.2)) {
+            for (int i = gap; i < n; ++i) {
+                const AdjSegment t = list[i];
+                int j = i;
+                while (j >= gap && list[j - gap].z_hi < t.z_hi) {
+                    list[j] = list[j - gap];
+                    j -= gap;
+                }
+                list[j] = t;
+            }
+        }
+        for (int i = n - 1; i >= 0; --i) {
+            const int c = static_cast<int>(list[i].cell);
+            const double dz = list[i].dz, q = g.q[c], a_raw = g.alpha[c];
+            const D2 d = dir[c];
+            double a = a_raw;
+            if (a > alpha_limit) a = alpha_limit;
+            tau_dot = fma(dz, d.a, tau_dot);
+            if (!(a < DBL_EPSILON)) tangent_step(a, a_raw > alpha_limit, q, dz, exp(-a * dz), d.a, d.b, I, I_dot);
+        }
+    }
+    out[lp] = make_float2(static_cast<float>(tau_dot), static_cast<float>(I_dot));
+}
+
+// dir[i] = {d_alpha[perm[i]], d_q[perm[i]]} (perm nullptr: the identity; a null direction: 0)
+__global__ __launch_bounds__(256) void tangent_gather(const double* __restrict__ d_alpha, const double* __restrict__ d_q,
+                                                      const int32_t* __restrict__ perm, int64_t n, double2* __restrict__ dir) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n) return;
+    const int64_t c = perm ? static_cast<int64_t>(perm[i]) : i;
+    D2 d;
+    d.a = d_alpha ? d_alpha[c] : 0.0;
+    d.b = d_q ? d_q[c] : 0.0;
+    reinterpret_cast<D2*>(dir)[i] = d;
+}
+
 void launch_adjoint_walk(hipStream_t s, const AdjointParams& a, int pass) {
     const ImageParams& im = a.w.im;
     if (im.res_x <= 0 || im.n_local_rows <= 0) return;
@@ -374,6 +538,29 @@ void launch_adjoint_permute(hipStream_t s, const double* ga_dev, const double* g
     if (n <= 0) return;
     const unsigned blocks = static_cast<unsigned>((n + 255) / 256);
     hipLaunchKernelGGL(adjoint_permute, dim3(blocks), dim3(256), 0, s, ga_dev, gq_dev, perm, n, ga_out, gq_out);
+}
+
+void launch_tangent_gather(hipStream_t s, const double* d_alpha, const double* d_q, const int32_t* perm, int64_t n,
+                           double2* dir) {
+    if (n <= 0) return;
+    const unsigned blocks = static_cast<unsigned>((n + 255) / 256);
+    hipLaunchKernelGGL(tangent_gather, dim3(blocks), dim3(256), 0, s, d_alpha, d_q, perm, n, dir);
+}
+
+void launch_tangent_walk(hipStream_t s, const TangentParams& t) {
+    const ImageParams& im = t.w.im;
+    if (im.res_x <= 0 || im.n_local_rows <= 0) return;
+    const unsigned blocks = static_cast<unsigned>(((im.res_x + 7) / 8) * ((im.n_local_rows + 7) / 8));
+    hipLaunchKernelGGL(tangent_walk, dim3(blocks), dim3(64), 0, s, t);
+}
+
+void launch_tangent_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const int64_t* offs, void* segs,
+                            const uint32_t* mask, double alpha_limit, const double2* dir, float2* out) {
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    if (n_px <= 0) return;
+    const unsigned blocks = static_cast<unsigned>((n_px + 255) / 256);
+    hipLaunchKernelGGL(tangent_resolve, dim3(blocks), dim3(256), 0, s, g, im, offs, static_cast<AdjSegment*>(segs), mask, alpha_limit,
+                       dir, out);
 }
 
 }  // namespace c5

@@ -271,8 +271,14 @@ struct c5_context {
     DeviceBuffer adj_perm;      // cell_perm on the device, for the grid of upload adj_perm_serial
     DeviceBuffer adj_io;        // c5_render_adjoint: the weights' image and the caller-order gradients
     uint64_t grid_serial = 0, adj_perm_serial = ~uint64_t{0};
-    unsigned* adj_status = nullptr;  // pinned: walk_overflow, entry_overflow, overlap_rays of the last adjoint
+    unsigned* adj_status = nullptr;  // pinned: walk_overflow, entry_overflow, overlap_rays of the last adjoint or tangent
     bool adjoint_pending = false;    // its status has not been looked at yet
+    const char* adj_what = "adjoint";  // which of the two it was (finish_adjoint's messages)
+
+    // tangent render (c5_render_tangent*): shares the adjoint's counters, sticky and status words and adj_perm; nothing of
+    // it is allocated before the first tangent call
+    DeviceBuffer tan_dir;  // [n_cells] {dalpha, dQ} fp64, device order (adjoint_kernels.hip: tangent_gather)
+    DeviceBuffer tan_io;   // c5_render_tangent: the caller's directions and the image
 };
 
 namespace {
@@ -1190,14 +1196,22 @@ int finish_frame(c5_context* ctx) {
 }
 
 // ------------------------------------------------------------------------------------------
-// Adjoint render (c5_render_adjoint*, adjoint_kernels.hip): the frame c5_render would produce now, differentiated with
-// respect to the cells' alpha and Q.  Its own per-view setup on the context's stream into slot 0's buffers - records of
-// "integration" 0 (the reference's order, whatever the option says), whole rays (no "depth_split"), the entry lists, the
-// solid mask - then the two passes of the walk (or bin_sort_resolve's lists) and the permutation into the caller's order.
-// It leaves the options alone and the frames' statistics and failure words too (counters and sticky words of its own);
-// the slot's per-view data are marked stale, so the next frame builds its own ("view_cache").
+// Derivative renders (c5_render_adjoint*, c5_render_tangent*; adjoint_kernels.hip): the frame c5_render would produce now,
+// differentiated with respect to the cells' alpha and Q.  Both share one per-view setup on the context's stream into slot
+// 0's buffers - records of "integration" 0 (the reference's order, whatever the option says), whole rays (no
+// "depth_split"), the entry lists, the solid mask; or bin_sort_resolve's lists - then run their own kernels.  They leave
+// the options alone and the frames' statistics and failure words too (counters and sticky words of their own); the slot's
+// per-view data are marked stale, so the next frame builds its own ("view_cache").
 // ------------------------------------------------------------------------------------------
-int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, double* gq_out) {
+struct DerivativeView {
+    bool no_cells = false;  // a scene of solids only: nothing was set up (there is no cell to differentiate)
+    bool bin_sort = false;  // "algorithm" 1: bin_sort_resolve's lists in ctx->offs64 / ctx->segs; else the walk's in w
+    c5::GridView g{};
+    const uint32_t* mask = nullptr;  // solid-marked pixels, or nullptr
+    c5::WalkParams w{};
+};
+
+int setup_derivative(c5_context* ctx, DerivativeView& v) {
     if (ctx->n_cells <= 0 && [&] {
             for (const Solid& s : ctx->solids)
                 if (s.n_tets > 0) return false;
@@ -1207,7 +1221,10 @@ int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, dou
     if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
     int rc = bind_device(ctx);
     if (rc) return rc;
-    if (ctx->n_cells <= 0) return C5_OK;  // (solids only: no cell to differentiate)
+    if (ctx->n_cells <= 0) {  // (solids only: no cell to differentiate)
+        v.no_cells = true;
+        return C5_OK;
+    }
     if (c5::segment_bytes() != c5::adjoint_segment_bytes())
         return fail(ctx, C5_ERR_STATE, "bin_sort_resolve's segment layout differs from the adjoint's");
     // everything below runs on the context's stream: frames set up on the others ("pipeline", "overlap_setup") must be done
@@ -1224,20 +1241,16 @@ int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, dou
 
     C5_HIP(ctx, ctx->adj_counters.ensure(kCountersBytes));
     C5_HIP(ctx, ctx->adj_sticky.ensure(kStickyWords * sizeof(unsigned)));
-    C5_HIP(ctx, ctx->adj_grad.ensure(2 * n_cells * sizeof(double)));
     if (!ctx->adj_status) C5_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->adj_status), 4 * sizeof(unsigned), hipHostMallocDefault));
     if (!ctx->cell_perm.empty() && ctx->adj_perm_serial != ctx->grid_serial) {
         C5_HIP(ctx, ctx->adj_perm.ensure(n_cells * sizeof(int32_t)));
         C5_HIP(ctx, hipMemcpy(ctx->adj_perm.ptr, ctx->cell_perm.data(), n_cells * sizeof(int32_t), hipMemcpyHostToDevice));
         ctx->adj_perm_serial = ctx->grid_serial;
     }
-    double* const ga_dev = ctx->adj_grad.as<double>();
-    double* const gq_dev = ga_dev + n_cells;
     c5::FrameCounters* const counters = ctx->adj_counters.as<c5::FrameCounters>();
     C5_HIP(ctx, hipMemsetAsync(ctx->adj_sticky.ptr, 0, kStickyWords * sizeof(unsigned), s));
-    C5_HIP(ctx, hipMemsetAsync(ga_dev, 0, 2 * n_cells * sizeof(double), s));
 
-    c5::GridView g;
+    c5::GridView& g = v.g;
     g.n_pts = ctx->n_pts;
     g.n_cells = ctx->n_cells;
     g.n_bfaces = ctx->n_bfaces;
@@ -1265,7 +1278,7 @@ int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, dou
         g.cull_y_lo = 1.0;
         g.cull_y_hi = -1.0;
     }
-    // the slot's per-view data are about to hold the adjoint's: no frame may take them for its own
+    // the slot's per-view data are about to hold the derivative's: no frame may take them for its own
     fs.setup_epoch = 0;
     fs.setup_kept = false;
     fs.flags_valid = false;
@@ -1273,8 +1286,8 @@ int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, dou
     c5::launch_transform_soa(s, g.px, g.py, g.pz, g.vx, g.vy, g.vz, g.n_pts, ctx->view, counters);
     c5::SolidTable table{};
     bool any_solid = false;
-    const bool bin_sort = ctx->algorithm == 1 || !ctx->grid_conforming || ctx->overlap_seen;
-    if (bin_sort) {
+    v.bin_sort = ctx->algorithm == 1 || !ctx->grid_conforming || ctx->overlap_seen;
+    if (v.bin_sort) {
         C5_HIP(ctx, ctx->offs64.ensure(static_cast<size_t>(padded + 1024) * sizeof(int64_t)));
         C5_HIP(ctx, ctx->scratch64.ensure(static_cast<size_t>(padded / 1024 + 1024) * sizeof(int64_t)));
         C5_HIP(ctx, hipMemsetAsync(fs.count.ptr, 0, static_cast<size_t>(padded + 1) * sizeof(int32_t), s));
@@ -1288,10 +1301,8 @@ int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, dou
                             ctx->offs64.as<int64_t>(), ctx->segs.ptr);
         rc = enqueue_solids(ctx, fs, 0, s, table, any_solid);
         if (rc) return rc;
-        c5::launch_adjoint_resolve(s, g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, any_solid ? fs.mask.as<uint32_t>() : nullptr,
-                                   ctx->alpha_limit, grad_out, ga_dev, gq_dev);
+        v.mask = any_solid ? fs.mask.as<uint32_t>() : nullptr;
     } else {
-        C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(padded) * sizeof(double)));
         const double key_slack = !ctx->entry_key ? -1.0 : c5::kEntryKeySlack * ctx->grid_diagonal + 0x1p-40 * ctx->coord_max;
         c5::launch_build_records(s, g, ctx->alpha_limit, 0);
         if (!fs.head_clean) C5_HIP(ctx, hipMemsetAsync(fs.head.ptr, 0, static_cast<size_t>(padded) * sizeof(c5::EntryHead), s));
@@ -1301,15 +1312,15 @@ int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, dou
                                ctx->adj_sticky.as<unsigned>(), 0, key_slack);
         rc = enqueue_solids(ctx, fs, 0, s, table, any_solid);
         if (rc) return rc;
-        c5::AdjointParams ap{};
-        c5::WalkParams& wp = ap.w;
+        v.mask = any_solid ? fs.mask.as<uint32_t>() : nullptr;
+        c5::WalkParams& wp = v.w;
         wp.xrec = g.xrec;
         wp.entry_head = fs.head.as<c5::EntryHead>();
         wp.entry_first = fs.first.as<c5::Entry>();
         wp.entry_pool = fs.pool.as<c5::Entry>();
         wp.pool_capacity = fs.entry_capacity;
         wp.key_slack = key_slack > 0.0 ? key_slack : 0.0;
-        wp.mask = any_solid ? fs.mask.as<uint32_t>() : nullptr;
+        wp.mask = v.mask;
         wp.solids = table;
         wp.Xtab = ctx->xtab.as<double>();
         wp.Ytab = ctx->ytab.as<double>();
@@ -1317,6 +1328,48 @@ int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, dou
         wp.max_steps = static_cast<uint32_t>(ctx->n_cells + 64);
         wp.counters = counters;
         wp.sticky = ctx->adj_sticky.as<unsigned>();
+    }
+    return C5_OK;
+}
+
+// After a derivative's kernels: its status words to the host for finish_adjoint, at the next wait.
+int commit_derivative(c5_context* ctx, const char* what) {
+    FrameSlot& fs = ctx->slots[0];
+    hipStream_t s = ctx->stream;
+    C5_HIP(ctx, hipGetLastError());
+    C5_HIP(ctx, hipMemcpyAsync(ctx->adj_status, &ctx->adj_counters.as<c5::FrameCounters>()->walk_overflow,
+                               kStatusWords * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    if (ctx->pipeline) {  // (the next frame's setup on the auxiliary stream waits for slot 0's buffers)
+        C5_HIP(ctx, hipEventRecord(fs.walk_done, s));
+        fs.walk_recorded = true;
+    }
+    ctx->adjoint_pending = true;
+    ctx->adj_what = what;
+    return C5_OK;
+}
+
+// The adjoint: two passes of the walk (or adjoint_resolve over bin_sort_resolve's lists), then the permutation into the
+// caller's order.
+int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, double* gq_out) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc || v.no_cells) return rc;
+    FrameSlot& fs = ctx->slots[0];
+    hipStream_t s = ctx->stream;
+    const c5::ImageParams& im = ctx->im;
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
+    C5_HIP(ctx, ctx->adj_grad.ensure(2 * n_cells * sizeof(double)));
+    double* const ga_dev = ctx->adj_grad.as<double>();
+    double* const gq_dev = ga_dev + n_cells;
+    C5_HIP(ctx, hipMemsetAsync(ga_dev, 0, 2 * n_cells * sizeof(double), s));
+    if (v.bin_sort) {
+        c5::launch_adjoint_resolve(s, v.g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, grad_out,
+                                   ga_dev, gq_dev);
+    } else {
+        const int64_t padded = ((static_cast<int64_t>(im.n_local_rows) * im.res_x + 1023) / 1024) * 1024;
+        C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(padded) * sizeof(double)));
+        c5::AdjointParams ap{};
+        ap.w = v.w;
         ap.grad_out = grad_out;
         ap.lambda = ctx->adj_lambda.as<double>();
         ap.grad_a = ga_dev;
@@ -1327,17 +1380,41 @@ int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, dou
     }
     c5::launch_adjoint_permute(s, ga_dev, gq_dev, ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>(), ctx->n_cells,
                                ga_out, gq_out);
-    C5_HIP(ctx, hipGetLastError());
-    C5_HIP(ctx, hipMemcpyAsync(ctx->adj_status, &counters->walk_overflow, kStatusWords * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    if (ctx->pipeline) {  // (the next frame's setup on the auxiliary stream waits for slot 0's buffers)
-        C5_HIP(ctx, hipEventRecord(fs.walk_done, s));
-        fs.walk_recorded = true;
-    }
-    ctx->adjoint_pending = true;
-    return C5_OK;
+    return commit_derivative(ctx, "adjoint");
 }
 
-// After the stream drained: the adjoint's failure words (as finish_frame treats a frame's).
+// The tangent: the caller's directions into device order, then one walk (or tangent_resolve over bin_sort_resolve's
+// lists) that writes (tau_dot, I_dot) per pixel.
+int enqueue_tangent(c5_context* ctx, const double* d_alpha, const double* d_q, float2* out) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const c5::ImageParams& im = ctx->im;
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    if (v.no_cells) {  // (nothing but solids: the image does not depend on any cell)
+        if (n_px > 0) C5_HIP(ctx, hipMemsetAsync(out, 0, static_cast<size_t>(n_px) * sizeof(float2), s));
+        return C5_OK;
+    }
+    FrameSlot& fs = ctx->slots[0];
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
+    C5_HIP(ctx, ctx->tan_dir.ensure(n_cells * sizeof(double2)));
+    double2* const dir = ctx->tan_dir.as<double2>();
+    c5::launch_tangent_gather(s, d_alpha, d_q, ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>(), ctx->n_cells, dir);
+    if (v.bin_sort) {
+        c5::launch_tangent_resolve(s, v.g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, dir, out);
+    } else {
+        c5::TangentParams tp{};
+        tp.w = v.w;
+        tp.dir = dir;
+        tp.out = out;
+        c5::launch_tangent_walk(s, tp);
+        fs.head_clean = true;  // (the walk hands every head back cleared)
+    }
+    return commit_derivative(ctx, "tangent");
+}
+
+// After the stream drained: the failure words of the last adjoint or tangent (as finish_frame treats a frame's).
 int finish_adjoint(c5_context* ctx) {
     if (!ctx->adjoint_pending) return C5_OK;
     ctx->adjoint_pending = false;
@@ -1353,16 +1430,16 @@ int finish_adjoint(c5_context* ctx) {
             C5_HIP(ctx, o.pool.ensure(static_cast<size_t>(want) * sizeof(c5::Entry)));
             ++ctx->setup_epoch;
         }
-        return fail(ctx, C5_RETRY, "adjoint: %u boundary entries found no room in the overflow pool (now %lld records): run it again",
-                    refused, static_cast<long long>(ctx->slots[0].entry_capacity));
+        return fail(ctx, C5_RETRY, "%s: %u boundary entries found no room in the overflow pool (now %lld records): run it again",
+                    ctx->adj_what, refused, static_cast<long long>(ctx->slots[0].entry_capacity));
     }
-    if (lost_rays) return fail(ctx, C5_ERR_WALK, "adjoint: %u rays exceeded the walk step bound (malformed grid?)", lost_rays);
+    if (lost_rays) return fail(ctx, C5_ERR_WALK, "%s: %u rays exceeded the walk step bound (malformed grid?)", ctx->adj_what, lost_rays);
     if (overlap_rays) {
         ctx->overlap_seen = true;  // (what the next frame would find out for itself: bin_sort_resolve from now on)
         ++ctx->setup_epoch;
         return fail(ctx, C5_RETRY,
-                    "adjoint: %u rays met a boundary entry inside a stretch of cells they had walked: components of the grid "
-                    "interpenetrate; run it again (bin_sort_resolve from now on)", overlap_rays);
+                    "%s: %u rays met a boundary entry inside a stretch of cells they had walked: components of the grid "
+                    "interpenetrate; run it again (bin_sort_resolve from now on)", ctx->adj_what, overlap_rays);
     }
     return C5_OK;
 }
@@ -1475,7 +1552,7 @@ void c5_destroy(c5_context* ctx) {
     DeviceBuffer* bufs[] = {&ctx->px, &ctx->py, &ctx->pz, &ctx->cell_vert, &ctx->cell_adj, &ctx->alpha,
                             &ctx->q, &ctx->bface, &ctx->xtab, &ctx->ytab, &ctx->out, &ctx->sticky,
                             &ctx->offs64, &ctx->scratch64, &ctx->segs, &ctx->adj_lambda, &ctx->adj_counters,
-                            &ctx->adj_sticky, &ctx->adj_grad, &ctx->adj_perm, &ctx->adj_io};
+                            &ctx->adj_sticky, &ctx->adj_grad, &ctx->adj_perm, &ctx->adj_io, &ctx->tan_dir, &ctx->tan_io};
     if (ctx->host_sticky) (void)hipHostFree(ctx->host_sticky);
     if (ctx->adj_status) (void)hipHostFree(ctx->adj_status);
     if (ctx->host_sb) (void)hipHostFree(ctx->host_sb);
@@ -2186,6 +2263,42 @@ int c5_render_adjoint(c5_context* ctx, const float* grad_out_host, double* grad_
         return C5_OK;
     }
     return fail(ctx, C5_ERR_STATE, "adjoint: entry buffer kept overflowing");
+}
+
+int c5_render_tangent_device(c5_context* ctx, const void* d_alpha_dev, const void* d_q_dev, void* out_device) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (!out_device) return fail(ctx, C5_ERR_INVALID, "null output pointer");
+    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_tangent while c5_render_host_async frames are outstanding");
+    return enqueue_tangent(ctx, static_cast<const double*>(d_alpha_dev), static_cast<const double*>(d_q_dev),
+                           static_cast<float2*>(out_device));
+}
+
+int c5_render_tangent(c5_context* ctx, const double* d_alpha_host, const double* d_q_host, float* out_host) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (!out_host) return fail(ctx, C5_ERR_INVALID, "null output pointer");
+    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_tangent while c5_render_host_async frames are outstanding");
+    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    const size_t img_bytes = static_cast<size_t>(ctx->im.n_local_rows) * ctx->im.res_x * 2 * sizeof(float);
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
+    const size_t dir_bytes = n_cells * sizeof(double);
+    C5_HIP(ctx, ctx->tan_io.ensure(2 * dir_bytes + img_bytes + 16));
+    double* const da = ctx->tan_io.as<double>();
+    double* const dq = da + n_cells;
+    float2* const img = reinterpret_cast<float2*>(dq + n_cells);
+    if (d_alpha_host && n_cells > 0) C5_HIP(ctx, hipMemcpyAsync(da, d_alpha_host, dir_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (d_q_host && n_cells > 0) C5_HIP(ctx, hipMemcpyAsync(dq, d_q_host, dir_bytes, hipMemcpyHostToDevice, ctx->stream));
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        rc = enqueue_tangent(ctx, d_alpha_host ? da : nullptr, d_q_host ? dq : nullptr, img);
+        if (rc) return rc;
+        rc = c5_synchronize(ctx);
+        if (rc == C5_RETRY) continue;
+        if (rc) return rc;
+        if (img_bytes > 0) C5_HIP(ctx, hipMemcpy(out_host, img, img_bytes, hipMemcpyDeviceToHost));
+        return C5_OK;
+    }
+    return fail(ctx, C5_ERR_STATE, "tangent: entry buffer kept overflowing");
 }
 
 namespace {

@@ -277,6 +277,28 @@ int c5_synchronize(c5_context* ctx);
 int c5_render_adjoint(c5_context* ctx, const float* grad_out_host, double* grad_alpha_host, double* grad_q_host);
 int c5_render_adjoint_device(c5_context* ctx, const void* grad_out_device, void* grad_alpha_device, void* grad_q_device);
 
+/* --- tangent render ----------------------------------------------------------------------------
+ * The forward-mode twin of the adjoint: the change of the same frame (the one c5_render would produce NOW; no render needs
+ * to come first) for a change (d_alpha, d_q) of the cells' AbsorpCoef and radEnLooseRate, i.e. J v where the adjoint
+ * gives J^T g:
+ *     out[p] = (sum over the cells c on p's ray of dtau/dalpha_c d_alpha[c],  sum of dI/dalpha_c d_alpha[c] + dI/dQ_c d_q[c])
+ * with the adjoint's conventions: the alpha limit clamps (a clamped alpha does not move I), a cell with clamped alpha <
+ * DBL_EPSILON neither absorbs nor emits, solid-marked and uncovered pixels are 0 in both channels, whole rays in the
+ * reference's order whatever "integration", "depth_split", "lds_stage" or "tile" say.
+ * d_alpha / d_q: n_cells fp64 each in the caller's cell order (c5_upload_grid's); either may be NULL (a zero direction).
+ * out: [local_rows][res_x][2] fp32, the output's own layout (row range and row tiles as for a frame).
+ * One walk per ray, no atomics: the result IS bit-reproducible from run to run, and <g, J v> = <J^T g, v> holds with
+ * c5_render_adjoint to rounding.
+ * Side effects: as the adjoint's (it shares the adjoint's counters and status words, never a frame's); the first call
+ * allocates 16 bytes per cell (c5_render_tangent: 16 more, and one image); a context that never calls it uses no more
+ * memory than before.
+ * c5_render_tangent: synchronous, host arrays; retries by itself on C5_RETRY, like c5_render.
+ * c5_render_tangent_device: asynchronous on the context's stream, device arrays; its status (C5_RETRY included: run it
+ * again) is reported by the next call that waits for the stream.  Both refuse while c5_render_host_async frames are
+ * outstanding. */
+int c5_render_tangent(c5_context* ctx, const double* d_alpha_host, const double* d_q_host, float* out_host);
+int c5_render_tangent_device(c5_context* ctx, const void* d_alpha_dev, const void* d_q_dev, void* out_device);
+
 /* --- frames delivered to host memory, pipelined ----------------------------------------------------
  * plane::trace_rays hands back HOST pixels (plane.cpp:144-172); over PCIe Gen5 a 2400x1800 image is
  * 0.65 ms of transfer beside 0.7 ms of rendering, so the two are overlapped: c5_render_host_async renders
