@@ -8,22 +8,29 @@
         img_dot = fwAD.unpack_dual(img).tangent          # [local_rows, res_x, 2] float32 (tau_dot, I_dot)
     img, img_dot = torch.func.jvp(lambda a, b: render(ctx, a, b), (alpha, q), (d_alpha, d_q))   # the same
 
+    J = torch.func.jacfwd(lambda th: render(ctx, f(th), q))(theta)      # [local_rows, res_x, 2, P]: one batched tangent
+    J = torch.func.jacrev(lambda a: losses(render(ctx, a, q)))(alpha)   # [L, n_cells]: one batched adjoint
+
 `ctx` is a capi.Context with grid, image, rows, view (and solids) set; alpha and q hold one value per cell in the order of
 its upload_grid.  The backward pass is the library's adjoint render (c5_render_adjoint_device), the forward-mode
 derivative (jvp) its tangent render (c5_render_tangent_device): the derivative of the reference's integral as written,
-alpha limit and all (include/course5_hip.h).
+alpha limit and all (include/course5_hip.h).  Under torch.func.vmap - jacfwd, jacrev, vmap over jvp or over vjp's function -
+a batch of tangents or cotangents goes to the batched renders (c5_render_tangent_batch_device,
+c5_render_adjoint_batch_device) in one call: every ray is walked once for several directions.  A batch of scalar fields
+(vmap over alpha or q themselves) and second derivatives (hessian, jacrev of jacrev, double backward, ...) raise.
 
-Forward: the scalars go to the context through c5_update_scalars, i.e. through host memory (16 bytes per cell each way:
-~16 MB and a few ms for the 1M-cell C3 grid; the library has no device-pointer upload), then the frame is rendered on
-torch's current stream and waited for (a C5_RETRY renders it again).  Backward: the adjoint on torch's current stream,
-waited for likewise; gradients come back in the dtype and on the device of alpha and q.  jvp: the tangents of alpha and
-q (None: zero) go to the context's GPU as float64, the tangent render runs on torch's current stream and is waited for;
-the image's tangent is float32 on the context's GPU, like the image.
+Forward: alpha and q on the context's GPU go to it through c5_update_scalars_device (gathered on the device; the call waits
+for the stream), others through c5_update_scalars, i.e. through host memory; then the frame is rendered on torch's current
+stream and waited for (a C5_RETRY renders it again).  The image is the same bits either way.  Backward: the adjoint on
+torch's current stream, waited for likewise; gradients come back in the dtype and on the device of alpha and q.  jvp: the
+tangents of alpha and q (None: zero) go to the context's GPU as float64, the tangent render runs on torch's current stream
+and is waited for; the image's tangent is float32 on the context's GPU, like the image.
 
 The context holds ONE set of scalars: a backward or jvp whose forward's scalars have since been replaced (another forward,
-an update_scalars) uploads its own again.  A backward or jvp after the view, image, rows, solids, alpha limit or grid
-changed raises instead of differentiating a frame other than the one rendered.  The gradients are fp64 sums added by
-atomics in arrival order: not bit-reproducible from run to run; the tangent is.
+an update_scalars) uploads its own again, from the copy the forward kept (on the GPU when they came from there).  A
+backward or jvp after the view, image, rows, solids, alpha limit or grid changed raises instead of differentiating a frame
+other than the one rendered.  The gradients are fp64 sums added by atomics in arrival order: not bit-reproducible from run
+to run; the tangent is, batched or not.
 """
 from __future__ import annotations
 
@@ -58,11 +65,23 @@ def _plain(t: torch.Tensor) -> torch.Tensor:
 
 
 class _Scalars:
-    """The scalars one forward uploaded; the context's scalars_owner while they are the ones it holds."""
+    """The scalars one forward uploaded (float64: numpy arrays on the host, or torch tensors on the context's GPU); the
+    context's scalars_owner while they are the ones it holds."""
     __slots__ = ("alpha", "q")
 
     def __init__(self, alpha, q):
         self.alpha, self.q = alpha, q
+
+
+def _upload(ctx: capi.Context, owner: _Scalars) -> None:
+    if isinstance(owner.alpha, torch.Tensor):
+        device = torch.device("cuda", ctx.device)
+        with torch.cuda.device(device):
+            _use_torch_stream(ctx, device)
+            ctx.update_scalars_device(owner.alpha, owner.q)
+    else:
+        ctx.update_scalars(owner.alpha, owner.q)
+    ctx.scalars_owner = owner
 
 
 def _current(fctx, what: str) -> capi.Context:
@@ -72,9 +91,133 @@ def _current(fctx, what: str) -> capi.Context:
         raise RuntimeError("course5_amd.autograd.render: the context's view, image, rows, solids, alpha limit or grid "
                            f"changed since the forward pass; render again before calling {what}")
     if ctx.scalars_owner is not fctx.owner:
-        ctx.update_scalars(fctx.owner.alpha, fctx.owner.q)
-        ctx.scalars_owner = fctx.owner
+        _upload(ctx, fctx.owner)
     return ctx
+
+
+def _differentiating_levels() -> int:
+    """torch.func transforms that differentiate (grad / vjp, jvp) around the current call."""
+    from torch._C._functorch import TransformType
+    from torch._functorch.pyfunctorch import retrieve_all_functorch_interpreters
+    return sum(i.key() in (TransformType.Grad, TransformType.Jvp) for i in retrieve_all_functorch_interpreters())
+
+
+def _first_order(fctx, what: str) -> None:
+    # a forward recorded under two differentiating transforms (hessian, jacrev of jacrev, jvp of grad, ...) is being
+    # differentiated twice: the derivative renders have no derivatives of their own
+    if getattr(fctx, "levels", 0) > 1:
+        raise RuntimeError(f"course5_amd.autograd.render: second derivatives are not supported ({what} of a render that is "
+                           "itself being differentiated)")
+
+
+def _no_second(what: str):
+    raise RuntimeError(f"course5_amd.autograd.render: second derivatives are not supported (the {what} render has no "
+                       "derivative of its own)")
+
+
+def _unbatched_primals(in_dims) -> None:
+    if any(d is not None for d in in_dims):
+        raise RuntimeError("course5_amd.autograd.render: vmap over alpha or q themselves (a batch of scalar fields) is not "
+                           "supported; batches of tangents or cotangents (jacfwd, jacrev, vmap over jvp / vjp) are")
+
+
+def _tangent_arg(t, device: torch.device):
+    return None if t is None else _plain(t).detach().to(device=device, dtype=torch.float64).contiguous()
+
+
+class _Tangent(torch.autograd.Function):
+    """J v: the tangent render of the frame of `fr` (the forward's autograd context); alpha and q only mark what the
+    result depends on.  Batched under vmap."""
+
+    @staticmethod
+    def forward(fr, alpha, q, alpha_t, q_t):
+        ctx = _current(fr, "jvp")
+        device = torch.device("cuda", ctx.device)
+        # under torch.func.jvp the tangents arrive wrapped (no storage of their own): the library reads plain tensors
+        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
+            da, dq = _tangent_arg(alpha_t, device), _tangent_arg(q_t, device)
+            out = torch.empty((ctx.local_rows, ctx.res_x, 2), dtype=torch.float32, device=device)
+            _use_torch_stream(ctx, device)
+            _run(ctx, lambda: ctx.render_tangent_device(da, dq, out))
+        return out
+
+    @staticmethod
+    def setup_context(fctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(fctx, *grads):
+        _no_second("tangent")
+
+    @staticmethod
+    def jvp(fctx, *tangents):
+        _no_second("tangent")
+
+    @staticmethod
+    def vmap(info, in_dims, fr, alpha, q, alpha_t, q_t):
+        _unbatched_primals(in_dims[1:3])
+        ctx = _current(fr, "jvp")
+        device = torch.device("cuda", ctx.device)
+        k = info.batch_size
+
+        def lift(t, d):  # the batch dimension first; an unbatched tangent is the same for every direction
+            if t is None:
+                return None
+            t = _plain(t).detach()
+            t = t.movedim(d, 0) if d is not None else t.expand(k, *t.shape)
+            return t.to(device=device, dtype=torch.float64).contiguous()
+
+        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
+            da, dq = lift(alpha_t, in_dims[3]), lift(q_t, in_dims[4])
+            out = torch.empty((k, ctx.local_rows, ctx.res_x, 2), dtype=torch.float32, device=device)
+            _use_torch_stream(ctx, device)
+            _run(ctx, lambda: ctx.render_tangent_batch_device(da, dq, out, n=k))
+        return out, 0
+
+
+class _Adjoint(torch.autograd.Function):
+    """J^T g: the adjoint render of the frame of `fr`; (grad_alpha, grad_q) float64 on the context's GPU.  Batched under
+    vmap."""
+
+    @staticmethod
+    def forward(fr, alpha, q, grad_img):
+        ctx = _current(fr, "backward")
+        device = torch.device("cuda", ctx.device)
+        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
+            g = _plain(grad_img).detach().to(device=device, dtype=torch.float32).contiguous()
+            ga = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
+            gq = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
+            _use_torch_stream(ctx, device)
+            _run(ctx, lambda: ctx.render_adjoint_device(g, ga, gq))
+        return ga, gq
+
+    @staticmethod
+    def setup_context(fctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(fctx, *grads):
+        _no_second("adjoint")
+
+    @staticmethod
+    def jvp(fctx, *tangents):
+        _no_second("adjoint")
+
+    @staticmethod
+    def vmap(info, in_dims, fr, alpha, q, grad_img):
+        _unbatched_primals(in_dims[1:3])
+        ctx = _current(fr, "backward")
+        device = torch.device("cuda", ctx.device)
+        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
+            g = _plain(grad_img).detach()
+            g = g.movedim(in_dims[3], 0) if in_dims[3] is not None else g.expand(info.batch_size, *g.shape)
+            g = g.to(device=device, dtype=torch.float32).contiguous()
+            k = g.shape[0]
+            ga = torch.empty((k, ctx.n_cells), dtype=torch.float64, device=device)
+            gq = torch.empty((k, ctx.n_cells), dtype=torch.float64, device=device)
+            _use_torch_stream(ctx, device)
+            _run(ctx, lambda: ctx.render_adjoint_batch_device(g, ga, gq, n=k))
+        return (ga, gq), (0, 0)
 
 
 class _Render(torch.autograd.Function):
@@ -82,14 +225,19 @@ class _Render(torch.autograd.Function):
     def forward(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor):
         if alpha.shape != (ctx.n_cells,) or q.shape != (ctx.n_cells,):
             raise ValueError(f"alpha and q must hold one value per cell ({ctx.n_cells})")
-        a_host = alpha.detach().to("cpu", torch.float64).contiguous().numpy().copy()
-        q_host = q.detach().to("cpu", torch.float64).contiguous().numpy().copy()
-        ctx.update_scalars(a_host, q_host)
-        ctx.scalars_owner = _Scalars(a_host, q_host)  # (setup_context takes it from here)
         device = torch.device("cuda", ctx.device)
+        on_gpu = all(t.is_cuda and t.device.index == ctx.device for t in (alpha, q))
+        if not on_gpu:
+            a_host = alpha.detach().to("cpu", torch.float64).contiguous().numpy().copy()
+            q_host = q.detach().to("cpu", torch.float64).contiguous().numpy().copy()
+            ctx.update_scalars(a_host, q_host)
+            ctx.scalars_owner = _Scalars(a_host, q_host)  # (setup_context takes it from here)
         out = torch.empty((ctx.local_rows, ctx.res_x, 2), dtype=torch.float32, device=device)
         with torch.cuda.device(device):
             _use_torch_stream(ctx, device)
+            if on_gpu:  # (a copy of their own: the caller may change alpha and q in place before a backward)
+                _upload(ctx, _Scalars(alpha.detach().to(dtype=torch.float64, copy=True).contiguous(),
+                                      q.detach().to(dtype=torch.float64, copy=True).contiguous()))
             _run(ctx, lambda: ctx.render_device(out.data_ptr()))
         return out
 
@@ -100,17 +248,14 @@ class _Render(torch.autograd.Function):
         fctx.state = ctx.frame_state
         fctx.owner = ctx.scalars_owner  # (forward has just set it)
         fctx.meta = ((alpha.dtype, alpha.device), (q.dtype, q.device))
+        fctx.primals = (alpha, q)
+        fctx.levels = _differentiating_levels()
 
     @staticmethod
     def backward(fctx, grad_img: torch.Tensor):
-        ctx = _current(fctx, "backward")
-        device = torch.device("cuda", ctx.device)
-        g = grad_img.to(device=device, dtype=torch.float32).contiguous()
-        ga = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
-        gq = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
-        with torch.cuda.device(device):
-            _use_torch_stream(ctx, device)
-            _run(ctx, lambda: ctx.render_adjoint_device(g, ga, gq))
+        _first_order(fctx, "backward")
+        alpha, q = fctx.primals
+        ga, gq = _Adjoint.apply(fctx, alpha, q, grad_img)
         (a_dtype, a_dev), (q_dtype, q_dev) = fctx.meta
         ga_out = ga.to(device=a_dev, dtype=a_dtype) if fctx.needs_input_grad[1] else None
         gq_out = gq.to(device=q_dev, dtype=q_dtype) if fctx.needs_input_grad[2] else None
@@ -118,16 +263,16 @@ class _Render(torch.autograd.Function):
 
     @staticmethod
     def jvp(fctx, _ctx_tangent, alpha_t, q_t):
-        ctx = _current(fctx, "jvp")
-        device = torch.device("cuda", ctx.device)
-        # under torch.func.jvp the tangents arrive wrapped (no storage of their own): the library reads plain tensors
-        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
-            da = None if alpha_t is None else _plain(alpha_t).detach().to(device=device, dtype=torch.float64).contiguous()
-            dq = None if q_t is None else _plain(q_t).detach().to(device=device, dtype=torch.float64).contiguous()
-            out = torch.empty((ctx.local_rows, ctx.res_x, 2), dtype=torch.float32, device=device)
-            _use_torch_stream(ctx, device)
-            _run(ctx, lambda: ctx.render_tangent_device(da, dq, out))
-        return out
+        _current(fctx, "jvp")
+        _first_order(fctx, "jvp")
+        alpha, q = getattr(fctx, "primals", (None, None))
+        return _Tangent.apply(fctx, alpha, q, alpha_t, q_t)
+
+    @staticmethod
+    def vmap(info, in_dims, ctx, alpha, q):
+        # jacfwd and vmap over jvp batch the tangents only: the frame itself is rendered once
+        _unbatched_primals(in_dims[1:])
+        return _Render.apply(ctx, alpha, q), None
 
 
 def render(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor) -> torch.Tensor:

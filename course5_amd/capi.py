@@ -29,6 +29,8 @@ EXPORTS = [
     "c5_set_row_range", "c5_get_row_costs", "c5_weld_points",
     "c5_render_host_async", "c5_render_host_wait", "c5_host_alloc", "c5_host_free", "c5_render_frame_rows_async",
     "c5_render_adjoint", "c5_render_adjoint_device", "c5_render_tangent", "c5_render_tangent_device",
+    "c5_render_tangent_batch", "c5_render_tangent_batch_device", "c5_render_adjoint_batch", "c5_render_adjoint_batch_device",
+    "c5_update_scalars_device",
 ]
 
 
@@ -104,6 +106,11 @@ def load_library() -> C.CDLL:
     lib.c5_render_adjoint_device.argtypes = [vp, vp, vp, vp]
     lib.c5_render_tangent.argtypes = [vp, dp, dp, C.POINTER(C.c_float)]
     lib.c5_render_tangent_device.argtypes = [vp, vp, vp, vp]
+    lib.c5_render_tangent_batch.argtypes = [vp, C.c_int, dp, dp, C.POINTER(C.c_float)]
+    lib.c5_render_tangent_batch_device.argtypes = [vp, C.c_int, vp, vp, vp]
+    lib.c5_render_adjoint_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_float), dp, dp]
+    lib.c5_render_adjoint_batch_device.argtypes = [vp, C.c_int, vp, vp, vp]
+    lib.c5_update_scalars_device.argtypes = [vp, vp, vp, C.c_int64]
     for name in EXPORTS:
         if name not in ("c5_destroy", "c5_last_error"):
             getattr(lib, name).restype = C.c_int
@@ -123,6 +130,16 @@ def _rot_array(rots) -> tuple:
 
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _device_ptr(t, dtype, shape) -> int:
+    """A raw device pointer as it is (None: 0), or the data pointer of a contiguous torch tensor of that dtype and shape
+    on the GPU."""
+    if t is None or isinstance(t, int):
+        return t or 0
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or not t.is_cuda:
+        raise ValueError(f"expected a contiguous {dtype} tensor of shape {tuple(shape)} on the GPU")
+    return t.data_ptr()
 
 
 class Context:
@@ -195,6 +212,16 @@ class Context:
         alpha = np.ascontiguousarray(alpha, dtype=np.float64)
         q = np.ascontiguousarray(q, dtype=np.float64)
         self._check(self.lib.c5_update_scalars(self.handle, _dp(alpha), _dp(q), alpha.shape[0]))
+        self.scalars_owner = None
+
+    def update_scalars_device(self, alpha, q):
+        """update_scalars from device memory: torch tensors on this context's GPU (float64 [n_cells] contiguous) or raw
+        device pointers, read on the context's stream.  Waits for the stream (the host needs the largest and smallest
+        alpha back)."""
+        import torch
+        n = self.n_cells
+        self._check(self.lib.c5_update_scalars_device(
+            self.handle, C.c_void_p(_device_ptr(alpha, torch.float64, (n,))), C.c_void_p(_device_ptr(q, torch.float64, (n,))), n))
         self.scalars_owner = None
 
     def set_solid(self, slot: int, tets, colour: float = float("nan")):
@@ -321,6 +348,65 @@ class Context:
             self.handle, C.c_void_p(ptr(d_alpha, torch.float64, (self.n_cells,)) or None),
             C.c_void_p(ptr(d_q, torch.float64, (self.n_cells,)) or None),
             C.c_void_p(ptr(out, torch.float32, (self.local_rows, self.res_x, 2)))))
+
+    # -- batched derivative renders ---------------------------------------------------------------
+    def _batch_directions(self, d_alpha, d_q) -> tuple:
+        def direction(d):
+            if d is None:
+                return None
+            d = np.ascontiguousarray(d, dtype=np.float64)
+            if d.ndim != 2 or d.shape[1] != self.n_cells:
+                raise ValueError(f"directions must be [K, {self.n_cells}], not {list(d.shape)}")
+            return d
+
+        da, dq = direction(d_alpha), direction(d_q)
+        ks = {d.shape[0] for d in (da, dq) if d is not None}
+        if len(ks) != 1:
+            raise ValueError("give d_alpha and / or d_q, with the same number of directions")
+        return da, dq, ks.pop()
+
+    def render_tangent_batch(self, d_alpha=None, d_q=None) -> np.ndarray:
+        """render_tangent for K directions at once (d_alpha / d_q: [K, n_cells], either may be None: zero): float32
+        [K, local_rows, res_x, 2], every slice bit for bit render_tangent's for that direction alone."""
+        da, dq, k = self._batch_directions(d_alpha, d_q)
+        out = np.zeros((k, self.local_rows, self.res_x, 2), dtype=np.float32)
+        self._check(self.lib.c5_render_tangent_batch(self.handle, k, None if da is None else _dp(da), None if dq is None else _dp(dq),
+                                                     out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def render_tangent_batch_device(self, d_alpha, d_q, out, n: int | None = None):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (d_alpha / d_q float64 [K,
+        n_cells] contiguous or None, out float32 [K, local_rows, res_x, 2] contiguous) or raw device pointers (then give
+        n = K).  The status comes with the next synchronize() (C5_RETRY: run it again)."""
+        import torch
+        k = n if n is not None else out.shape[0]
+        self._check(self.lib.c5_render_tangent_batch_device(
+            self.handle, k, C.c_void_p(_device_ptr(d_alpha, torch.float64, (k, self.n_cells)) or None),
+            C.c_void_p(_device_ptr(d_q, torch.float64, (k, self.n_cells)) or None),
+            C.c_void_p(_device_ptr(out, torch.float32, (k, self.local_rows, self.res_x, 2)))))
+
+    def render_adjoint_batch(self, grad_out) -> tuple:
+        """render_adjoint for K upstream images at once (grad_out [K, local_rows, res_x, 2]): (grad_alpha, grad_q), float64
+        [K, n_cells] each; every slice render_adjoint's for that image to rounding.  Synchronous; retries by itself."""
+        g = np.ascontiguousarray(grad_out, dtype=np.float32)
+        if g.ndim != 4 or g.shape[1:] != (self.local_rows, self.res_x, 2):
+            raise ValueError(f"grad_out must be [K, {self.local_rows}, {self.res_x}, 2], not {list(g.shape)}")
+        k = g.shape[0]
+        ga = np.zeros((k, self.n_cells), dtype=np.float64)
+        gq = np.zeros((k, self.n_cells), dtype=np.float64)
+        self._check(self.lib.c5_render_adjoint_batch(self.handle, k, g.ctypes.data_as(C.POINTER(C.c_float)), _dp(ga), _dp(gq)))
+        return ga, gq
+
+    def render_adjoint_batch_device(self, grad_out, grad_alpha, grad_q, n: int | None = None):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (grad_out float32 [K, local_rows,
+        res_x, 2], grad_alpha / grad_q float64 [K, n_cells], contiguous) or raw device pointers (then give n = K).  The
+        status comes with the next synchronize() (C5_RETRY: run it again)."""
+        import torch
+        k = n if n is not None else grad_out.shape[0]
+        self._check(self.lib.c5_render_adjoint_batch_device(
+            self.handle, k, C.c_void_p(_device_ptr(grad_out, torch.float32, (k, self.local_rows, self.res_x, 2))),
+            C.c_void_p(_device_ptr(grad_alpha, torch.float64, (k, self.n_cells))),
+            C.c_void_p(_device_ptr(grad_q, torch.float64, (k, self.n_cells)))))
 
     # -- frames delivered to host memory, pipelined -------------------------------------------------
     def host_image(self, full: bool = False) -> np.ndarray:

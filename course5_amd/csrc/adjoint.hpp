@@ -56,4 +56,48 @@ void launch_tangent_resolve(hipStream_t s, const GridView& g, const ImageParams&
 // bytes of one segment of the bin-sort lists as this file reads them (c_api.hip checks it against segment_bytes())
 size_t adjoint_segment_bytes();
 
+// ---- batches (c5_render_tangent_batch*, c5_render_adjoint_batch*): one walk per ray for up to kc directions or upstream
+// images (kc: the chunk width, 4 or 8); a call with more runs several chunks over the same per-view setup.
+
+// dirs[i][j] = {d_alpha[k0 + j][perm[i]], d_q[k0 + j][perm[i]]} for j < n_used, zero for n_used <= j < kc: the caller's
+// [K][n] directions -> kc interleaved pairs per cell in device order (a null d_alpha or d_q stands for zeros)
+void launch_tangent_gather_batch(hipStream_t s, int kc, const double* d_alpha, const double* d_q, const int32_t* perm, int64_t n,
+                                 int k0, int n_used, double2* dirs);
+
+struct TangentBatchParams {
+    WalkParams w;          // as TangentParams
+    const double2* dirs;   // [n_cells][kc] device order (launch_tangent_gather_batch)
+    float2* out;           // [n_used][n_local_rows][res_x] (tau_dot, I_dot): the chunk's first image
+    int64_t image_px;      // pixels per image (n_local_rows * res_x)
+    int32_t n_used;        // directions of the chunk (<= kc)
+    int32_t keep_entries;  // 1: leave the entry heads in place for a later chunk; 0: hand them back cleared
+};
+
+// tangent_walk's step once per ray for kc directions: every image bit for bit what launch_tangent_walk gives for its
+// direction alone; counts as tangent_walk does
+void launch_tangent_walk_batch(hipStream_t s, int kc, const TangentBatchParams& t);
+
+struct AdjointBatchParams {
+    WalkParams w;              // as AdjointParams (the heads left in place by pass 1)
+    const float2* grad_out;    // [n_used][n_local_rows][res_x] upstream weights: the chunk's first image
+    int64_t image_px;          // pixels per image
+    const double* lambda;      // pass 1's Lambda per pixel (launch_adjoint_walk(.., 1), once for every chunk)
+    double* grad;              // [n_cells][2 kc] device order, accumulated: {ga_0 .. ga_kc-1, gq_0 .. gq_kc-1} per cell
+    int32_t n_used;            // images of the chunk (<= kc)
+    int32_t keep_entries;      // as TangentBatchParams
+};
+
+// adjoint_walk<2> for kc upstream images at once (needs pass 1 first)
+void launch_adjoint_walk_batch(hipStream_t s, int kc, const AdjointBatchParams& a);
+
+// ga_out[(k0 + j) n + perm[i]] = grad[i][j], gq_out[...] = grad[i][kc + j] for j < n_used (perm nullptr: the identity)
+void launch_adjoint_permute_batch(hipStream_t s, int kc, const double* grad, const int32_t* perm, int64_t n, int k0, int n_used,
+                                  double* ga_out, double* gq_out);
+
+// c5_update_scalars_device: alpha[i] = alpha_src[perm[i]], q[i] = q_src[perm[i]] (perm nullptr: the identity), and into
+// stats[3] (zeroed by the caller): the bits of the largest alpha > 0, the complemented bits of the smallest alpha >=
+// DBL_EPSILON, and 1 if some alpha is NaN (the host loop of c5_update_scalars, as an order-free max / min / or)
+void launch_scalars_gather(hipStream_t s, const double* alpha_src, const double* q_src, const int32_t* perm, int64_t n, double* alpha,
+                           double* q, unsigned long long* stats);
+
 }  // namespace c5

@@ -35,6 +35,7 @@
 // compare-and-swap loop.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
 
 #include "adjoint.hpp"
@@ -514,6 +515,338 @@ __global__ __launch_bounds__(256) void tangent_gather(const double* __restrict__
     reinterpret_cast<D2*>(dir)[i] = d;
 }
 
+// ---- batches: KC directions (tangent) or upstream images (adjoint) per walk -------------------------------------------
+// The ray's walk - geometry, entries, record loads, E and the segment terms - is shared; only the per-direction sums are
+// KC-fold.  A tangent step runs tangent_step's operations on every direction's own registers, so each image is bit for
+// bit tangent_walk's for that direction alone.
+
+// dirs[i][j] = {d_alpha[k0 + j][perm[i]], d_q[k0 + j][perm[i]]}, zero beyond n_used (a null direction array: 0); one
+// thread per (cell, direction): the 16-byte stores of a wavefront are contiguous
+template <int KC>
+__global__ __launch_bounds__(256) void tangent_gather_batch(const double* __restrict__ d_alpha, const double* __restrict__ d_q,
+                                                            const int32_t* __restrict__ perm, int64_t n, int k0, int n_used,
+                                                            double2* __restrict__ dirs) {
+    const int64_t t = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (t >= n * KC) return;
+    const int64_t i = t / KC;
+    const int j = static_cast<int>(t - i * KC);
+    const int64_t c = perm ? static_cast<int64_t>(perm[i]) : i;
+    D2 d{0.0, 0.0};
+    if (j < n_used) {
+        const int64_t at = static_cast<int64_t>(k0 + j) * n + c;
+        if (d_alpha) d.a = d_alpha[at];
+        if (d_q) d.b = d_q[at];
+    }
+    reinterpret_cast<D2*>(dirs)[t] = d;
+}
+
+// tangent_walk for KC directions: one wavefront per 8x8 pixel tile, one lane per pixel.  The cell's KC direction pairs are
+// loaded at the top of its step (one 16 * KC-byte stretch) and consumed at its end, behind the geometry and the next
+// record's loads.
+template <int KC>
+__global__ __launch_bounds__(64) void tangent_walk_batch(TangentBatchParams A) {
+    using namespace adj;
+    const WalkParams& P = A.w;
+    const ImageParams& im = P.im;
+    const D2* __restrict__ dirs = reinterpret_cast<const D2*>(A.dirs);
+    const int tiles_x = (im.res_x + 7) / 8;
+    const int ty = static_cast<int>(blockIdx.x) / tiles_x, tx = static_cast<int>(blockIdx.x) - ty * tiles_x;
+    const int lane = static_cast<int>(threadIdx.x);
+    const int col = tx * 8 + (lane & 7), lrow = ty * 8 + (lane >> 3);
+    const bool in_image = (col < im.res_x) && (lrow < im.n_local_rows);
+
+    unsigned n_step = 0, overflow = 0;
+    bool skipped = false;
+    double key_taken = -DBL_MAX;
+    double x = 0.0, y = 0.0, w_cur = -DBL_MAX, carry = 0.0;
+    EntryHead ent{0, 0};
+    int cell = -1;
+    size_t lp = 0;
+    double I = 0.0, I_dot[KC], tau_dot[KC];
+#pragma unroll
+    for (int j = 0; j < KC; ++j) I_dot[j] = tau_dot[j] = 0.0;
+
+    if (in_image) {
+        lp = static_cast<size_t>(lrow) * im.res_x + col;
+        const uint32_t mv = P.mask ? P.mask[lp] : 0u;
+        if (!mv) {  // (a solid-marked pixel shows the solid: line.cpp:177-179, nothing of the grid)
+            x = P.Xtab[col];
+            y = P.Ytab[global_row_of(im, lrow)];
+            ent = load_entry_head(P.entry_head + lp);
+            if (ent.count > 0) cell = next_entry<true>(P, lp, ent, w_cur, carry, -DBL_MAX, -DBL_MAX, skipped);
+            key_taken = w_cur;
+        }
+    }
+
+    CellRegs cur;
+    if (cell >= 0) load_cell(cur, P.xrec, cell);
+
+    while (cell >= 0) {
+        D2 d[KC];
+#pragma unroll
+        for (int j = 0; j < KC; ++j) d[j] = dirs[static_cast<size_t>(cell) * KC + j];
+        // the step of tangent_walk, operation for operation
+        const StepGeometry sg = step_geometry(cur, x, y);
+        ++n_step;
+        const bool has_exit = sg.w_exit < INFINITY;
+        const double dz = sg.w_exit - carry;
+        const bool contributes = dz > 0.0 && dz < INFINITY;
+        int nb = -1;
+        double carry_next = carry;
+        if (has_exit) {
+            carry_next = sg.w_exit;
+            w_cur = fmax(w_cur, sg.w_exit);
+            const uint32_t id = sg.w_out & kIdMask;
+            if (id != kNoCell) nb = static_cast<int>(id);
+        }
+        if (nb >= 0 && n_step >= P.max_steps) {
+            overflow = 1;
+            nb = -1;
+        } else if (nb < 0 && !overflow) {
+            nb = next_entry<true>(P, lp, ent, w_cur, carry_next, key_taken, has_exit ? sg.w_exit : -DBL_MAX, skipped);
+            key_taken = w_cur;
+        }
+        CellRegs nxt;
+        if (nb >= 0) load_cell(nxt, P.xrec, nb);
+
+        if (contributes) {
+            const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+#pragma unroll
+            for (int j = 0; j < KC; ++j) tau_dot[j] = fma(dz, d[j].a, tau_dot[j]);  // d tau / d alpha (raw alpha)
+            if (a != 0.0) {
+                // tangent_step, its direction-free part once: segment_terms at T = 1, E
+                const double E = exp_nonpositive(-a * dz);
+                const SegmentTerms t = segment_terms(a, q, dz, E, 1.0, I);
+                const bool clamped = a != a_raw;
+#pragma unroll
+                for (int j = 0; j < KC; ++j) {
+                    double src = d[j].b * t.dI_dq;
+                    if (!clamped) src = fma(d[j].a, t.dI_da, src);  // (a clamped alpha does not move: line.cpp:216)
+                    I_dot[j] = fma(E, I_dot[j], src);
+                }
+                I = t.I_next;
+            }
+        }
+        cell = nb;
+        carry = carry_next;
+        cur = nxt;
+    }
+
+    if (in_image) {
+#pragma unroll
+        for (int j = 0; j < KC; ++j)
+            if (j < A.n_used)
+                A.out[static_cast<size_t>(j) * A.image_px + lp] = make_float2(static_cast<float>(tau_dot[j]), static_cast<float>(I_dot[j]));
+        if (!A.keep_entries) __builtin_nontemporal_store(0ll, reinterpret_cast<long long*>(P.entry_head + lp));
+    }
+    const unsigned s_ovf = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(overflow != 0u)));
+    const unsigned s_skip = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(skipped)));
+    if (lane == 0) {
+        if (s_ovf) atomicAdd(&P.counters->walk_overflow, s_ovf);
+        if (s_skip) atomicAdd(&P.counters->overlap_rays, s_skip);
+    }
+}
+
+// adjoint_walk<2> for KC upstream images.  Per step every lane has 2 KC values (ga_j, gq_j) for its cell.  They are staged
+// in LDS, one row per lane; then, per distinct cell of the step, lanes v < 2 KC each sum column v over the cell's member
+// rows (four rows per round, an all-zero row 64 filling up) and add it with one atomic: 2 KC atomics in one instruction,
+// to one 16 KC-byte stretch of grad.  A 64-lane butterfly per value, as scatter_wave does for two, would cost 2 KC times
+// its twelve cross-lane moves per shared cell.
+template <int KC>
+__global__ __launch_bounds__(64) void adjoint_walk_batch(AdjointBatchParams A) {
+    using namespace adj;
+    constexpr int kV = 2 * KC, kRow = kV + 1;  // (row pitch: an odd number of doubles)
+    __shared__ double stage[65 * kRow];
+    const WalkParams& P = A.w;
+    const ImageParams& im = P.im;
+    const int tiles_x = (im.res_x + 7) / 8;
+    const int ty = static_cast<int>(blockIdx.x) / tiles_x, tx = static_cast<int>(blockIdx.x) - ty * tiles_x;
+    const int lane = static_cast<int>(threadIdx.x);
+    const int col = tx * 8 + (lane & 7), lrow = ty * 8 + (lane >> 3);
+    const bool in_image = (col < im.res_x) && (lrow < im.n_local_rows);
+    if (lane < kRow) stage[64 * kRow + lane] = 0.0;
+
+    unsigned n_step = 0, overflow = 0;
+    bool skipped = false;
+    double key_taken = -DBL_MAX;
+    double x = 0.0, y = 0.0, w_cur = -DBL_MAX, carry = 0.0;
+    EntryHead ent{0, 0};
+    int cell = -1;
+    size_t lp = 0;
+    double lam = 0.0, lam_total = 0.0, I = 0.0;
+    float2 g[KC];
+#pragma unroll
+    for (int j = 0; j < KC; ++j) g[j] = make_float2(0.0f, 0.0f);
+
+    if (in_image) {
+        lp = static_cast<size_t>(lrow) * im.res_x + col;
+        const uint32_t mv = P.mask ? P.mask[lp] : 0u;
+        if (!mv) {  // (a solid-marked pixel shows the solid: line.cpp:177-179, nothing of the grid)
+            x = P.Xtab[col];
+            y = P.Ytab[global_row_of(im, lrow)];
+            ent = load_entry_head(P.entry_head + lp);
+            bool any = false;
+#pragma unroll
+            for (int j = 0; j < KC; ++j)
+                if (j < A.n_used) {
+                    g[j] = A.grad_out[static_cast<size_t>(j) * A.image_px + lp];
+                    any = any || g[j].x != 0.0f || g[j].y != 0.0f;
+                }
+            lam_total = A.lambda[lp];
+            if (ent.count > 0 && any) cell = next_entry<true>(P, lp, ent, w_cur, carry, -DBL_MAX, -DBL_MAX, skipped);
+            key_taken = w_cur;
+        }
+    }
+
+    CellRegs cur;
+    if (cell >= 0) load_cell(cur, P.xrec, cell);
+
+    // wave-uniform loop (the reduction wants every lane): a lane whose ray has ended takes part with nothing to add
+    for (;;) {
+        const bool live = cell >= 0;
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        bool emit = false;
+        const int here = cell;
+        if (live) {
+            // the step of adjoint_walk<2>, operation for operation
+            const StepGeometry sg = step_geometry(cur, x, y);
+            ++n_step;
+            const bool has_exit = sg.w_exit < INFINITY;
+            const double dz = sg.w_exit - carry;
+            const bool contributes = dz > 0.0 && dz < INFINITY;
+            int nb = -1;
+            double carry_next = carry;
+            if (has_exit) {
+                carry_next = sg.w_exit;
+                w_cur = fmax(w_cur, sg.w_exit);
+                const uint32_t id = sg.w_out & kIdMask;
+                if (id != kNoCell) nb = static_cast<int>(id);
+            }
+            if (nb >= 0 && n_step >= P.max_steps) {
+                overflow = 1;
+                nb = -1;
+            } else if (nb < 0 && !overflow) {
+                nb = next_entry<true>(P, lp, ent, w_cur, carry_next, key_taken, has_exit ? sg.w_exit : -DBL_MAX, skipped);
+                key_taken = w_cur;
+            }
+            CellRegs nxt;
+            if (nb >= 0) load_cell(nxt, P.xrec, nb);
+
+            if (contributes) {
+                const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+                double ga[KC], gq[KC];
+#pragma unroll
+                for (int j = 0; j < KC; ++j) {
+                    ga[j] = static_cast<double>(g[j].x) * dz;  // d tau / d alpha (line.cpp:189: raw alpha)
+                    gq[j] = 0.0;
+                }
+                emit = true;
+                if (a != 0.0) {
+                    lam = fma(a, dz, lam);
+                    const double T = exp_nonpositive(fmin(lam - lam_total, 0.0));
+                    const double E = exp_nonpositive(-a * dz);
+                    const SegmentTerms t = segment_terms(a, q, dz, E, T, I);
+                    const bool moves = a == a_raw;  // (a clamped alpha does not move: line.cpp:216)
+#pragma unroll
+                    for (int j = 0; j < KC; ++j) {
+                        gq[j] = static_cast<double>(g[j].y) * t.dI_dq;
+                        if (moves) ga[j] = fma(static_cast<double>(g[j].y), t.dI_da, ga[j]);
+                    }
+                    I = t.I_next;
+                }
+#pragma unroll
+                for (int j = 0; j < KC; ++j) {
+                    stage[lane * kRow + j] = ga[j];
+                    stage[lane * kRow + KC + j] = gq[j];
+                }
+            }
+            cell = nb;
+            carry = carry_next;
+            cur = nxt;
+        }
+        __syncthreads();  // (one wavefront: the rows are visible to every lane)
+        unsigned long long m = __builtin_amdgcn_ballot_w64(emit);
+        while (m != 0ull) {
+            const int leader = __builtin_ctzll(m);
+            const int lc = __builtin_amdgcn_readlane(here, leader);
+            const unsigned long long members = __builtin_amdgcn_ballot_w64(emit && here == lc);
+            if (lane < kV) {
+                double s = 0.0;
+                for (unsigned long long r = members; r != 0ull;) {
+                    const int b0 = __builtin_ctzll(r);
+                    r &= r - 1;
+                    const int b1 = r ? __builtin_ctzll(r) : 64;
+                    r &= r - 1;
+                    const int b2 = r ? __builtin_ctzll(r) : 64;
+                    r &= r - 1;
+                    const int b3 = r ? __builtin_ctzll(r) : 64;
+                    r &= r - 1;
+                    s += (stage[b0 * kRow + lane] + stage[b1 * kRow + lane]) + (stage[b2 * kRow + lane] + stage[b3 * kRow + lane]);
+                }
+                if (s != 0.0) atomicAdd(A.grad + static_cast<size_t>(lc) * kV + lane, s);
+            }
+            m &= ~members;
+        }
+        __syncthreads();  // (the rows are read before the next step writes them)
+    }
+
+    if (in_image && !A.keep_entries) __builtin_nontemporal_store(0ll, reinterpret_cast<long long*>(P.entry_head + lp));
+}
+
+// one thread per (cell, image)
+template <int KC>
+__global__ __launch_bounds__(256) void adjoint_permute_batch(const double* __restrict__ grad, const int32_t* __restrict__ perm, int64_t n,
+                                                             int k0, int n_used, double* __restrict__ ga_out, double* __restrict__ gq_out) {
+    const int64_t t = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (t >= n * KC) return;
+    const int64_t i = t / KC;
+    const int j = static_cast<int>(t - i * KC);
+    if (j >= n_used) return;
+    const int64_t d = perm ? static_cast<int64_t>(perm[i]) : i;
+    ga_out[static_cast<int64_t>(k0 + j) * n + d] = grad[i * (2 * KC) + j];
+    gq_out[static_cast<int64_t>(k0 + j) * n + d] = grad[i * (2 * KC) + KC + j];
+}
+
+// c5_update_scalars_device: the gather into device order, and c5_update_scalars' three statistics as bit-pattern maxima
+// (non-negative doubles order as their bits do; the smallest one is the largest complement).  A grid-stride loop over a
+// few hundred workgroups, reduced per workgroup: one atomic per statistic and workgroup (atomics on one address are
+// serialised at its L2 channel: one per wavefront cost 0.36 ms on a million cells).
+constexpr int kScalarBlocks = 512;
+__global__ __launch_bounds__(256) void scalars_gather(const double* __restrict__ alpha_src, const double* __restrict__ q_src,
+                                                      const int32_t* __restrict__ perm, int64_t n, double* __restrict__ alpha,
+                                                      double* __restrict__ q, unsigned long long* __restrict__ stats) {
+    __shared__ unsigned long long part[3][4];
+    unsigned long long top = 0ull, floor_c = 0ull, nan = 0ull;
+    for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n;
+         i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const int64_t c = perm ? static_cast<int64_t>(perm[i]) : i;
+        const double a = alpha_src[c];
+        alpha[i] = a;
+        q[i] = q_src[c];
+        if (a > 0.0) top = max(top, static_cast<unsigned long long>(__double_as_longlong(a)));
+        if (a >= DBL_EPSILON) floor_c = max(floor_c, ~static_cast<unsigned long long>(__double_as_longlong(a)));
+        if (a != a) nan = 1ull;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        top = max(top, static_cast<unsigned long long>(__shfl_xor(top, d)));
+        floor_c = max(floor_c, static_cast<unsigned long long>(__shfl_xor(floor_c, d)));
+        nan = max(nan, static_cast<unsigned long long>(__shfl_xor(nan, d)));
+    }
+    const int wave = static_cast<int>(threadIdx.x >> 6);
+    if ((threadIdx.x & 63) == 0) {
+        part[0][wave] = top;
+        part[1][wave] = floor_c;
+        part[2][wave] = nan;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const unsigned long long* p = part[threadIdx.x];
+        const unsigned long long v = max(max(p[0], p[1]), max(p[2], p[3]));
+        if (v) atomicMax(stats + threadIdx.x, v);
+    }
+}
+
 void launch_adjoint_walk(hipStream_t s, const AdjointParams& a, int pass) {
     const ImageParams& im = a.w.im;
     if (im.res_x <= 0 || im.n_local_rows <= 0) return;
@@ -561,6 +894,53 @@ void launch_tangent_resolve(hipStream_t s, const GridView& g, const ImageParams&
     const unsigned blocks = static_cast<unsigned>((n_px + 255) / 256);
     hipLaunchKernelGGL(tangent_resolve, dim3(blocks), dim3(256), 0, s, g, im, offs, static_cast<AdjSegment*>(segs), mask, alpha_limit,
                        dir, out);
+}
+
+void launch_tangent_gather_batch(hipStream_t s, int kc, const double* d_alpha, const double* d_q, const int32_t* perm, int64_t n,
+                                 int k0, int n_used, double2* dirs) {
+    if (n <= 0) return;
+    const unsigned blocks = static_cast<unsigned>((n * kc + 255) / 256);
+    if (kc == 4)
+        hipLaunchKernelGGL(tangent_gather_batch<4>, dim3(blocks), dim3(256), 0, s, d_alpha, d_q, perm, n, k0, n_used, dirs);
+    else
+        hipLaunchKernelGGL(tangent_gather_batch<8>, dim3(blocks), dim3(256), 0, s, d_alpha, d_q, perm, n, k0, n_used, dirs);
+}
+
+void launch_tangent_walk_batch(hipStream_t s, int kc, const TangentBatchParams& t) {
+    const ImageParams& im = t.w.im;
+    if (im.res_x <= 0 || im.n_local_rows <= 0) return;
+    const unsigned blocks = static_cast<unsigned>(((im.res_x + 7) / 8) * ((im.n_local_rows + 7) / 8));
+    if (kc == 4)
+        hipLaunchKernelGGL(tangent_walk_batch<4>, dim3(blocks), dim3(64), 0, s, t);
+    else
+        hipLaunchKernelGGL(tangent_walk_batch<8>, dim3(blocks), dim3(64), 0, s, t);
+}
+
+void launch_adjoint_walk_batch(hipStream_t s, int kc, const AdjointBatchParams& a) {
+    const ImageParams& im = a.w.im;
+    if (im.res_x <= 0 || im.n_local_rows <= 0) return;
+    const unsigned blocks = static_cast<unsigned>(((im.res_x + 7) / 8) * ((im.n_local_rows + 7) / 8));
+    if (kc == 4)
+        hipLaunchKernelGGL(adjoint_walk_batch<4>, dim3(blocks), dim3(64), 0, s, a);
+    else
+        hipLaunchKernelGGL(adjoint_walk_batch<8>, dim3(blocks), dim3(64), 0, s, a);
+}
+
+void launch_adjoint_permute_batch(hipStream_t s, int kc, const double* grad, const int32_t* perm, int64_t n, int k0, int n_used,
+                                  double* ga_out, double* gq_out) {
+    if (n <= 0) return;
+    const unsigned blocks = static_cast<unsigned>((n * kc + 255) / 256);
+    if (kc == 4)
+        hipLaunchKernelGGL(adjoint_permute_batch<4>, dim3(blocks), dim3(256), 0, s, grad, perm, n, k0, n_used, ga_out, gq_out);
+    else
+        hipLaunchKernelGGL(adjoint_permute_batch<8>, dim3(blocks), dim3(256), 0, s, grad, perm, n, k0, n_used, ga_out, gq_out);
+}
+
+void launch_scalars_gather(hipStream_t s, const double* alpha_src, const double* q_src, const int32_t* perm, int64_t n, double* alpha,
+                           double* q, unsigned long long* stats) {
+    if (n <= 0) return;
+    const unsigned blocks = static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, kScalarBlocks));
+    hipLaunchKernelGGL(scalars_gather, dim3(blocks), dim3(256), 0, s, alpha_src, q_src, perm, n, alpha, q, stats);
 }
 
 }  // namespace c5

@@ -279,6 +279,15 @@ struct c5_context {
     // it is allocated before the first tangent call
     DeviceBuffer tan_dir;  // [n_cells] {dalpha, dQ} fp64, device order (adjoint_kernels.hip: tangent_gather)
     DeviceBuffer tan_io;   // c5_render_tangent: the caller's directions and the image
+
+    // batches (c5_render_tangent_batch*, c5_render_adjoint_batch*): nothing of it is allocated before the first batch call
+    int batch_width = 0;    // "batch_width": directions or upstream images per walk (0: 4 for batches of up to 4, else 8)
+    DeviceBuffer bat_dirs;  // [n_cells][width] {dalpha, dQ} fp64, device order (adjoint_kernels.hip: tangent_gather_batch)
+    DeviceBuffer bat_grad;  // [n_cells][2 width] fp64, device order (adjoint_walk_batch)
+    DeviceBuffer bat_io;    // the synchronous forms: the caller's directions or weights, and what goes back
+    // c5_update_scalars_device: the three statistics of the scalars on the device, and their pinned copy
+    DeviceBuffer scal_stats;
+    unsigned long long* scal_host = nullptr;
 };
 
 namespace {
@@ -1211,6 +1220,17 @@ struct DerivativeView {
     c5::WalkParams w{};
 };
 
+// cell_perm on the device (adj_perm), for the derivatives' and c5_update_scalars_device's gathers and permutations
+int ensure_device_perm(c5_context* ctx) {
+    if (!ctx->cell_perm.empty() && ctx->adj_perm_serial != ctx->grid_serial) {
+        const size_t n_cells = static_cast<size_t>(ctx->n_cells);
+        C5_HIP(ctx, ctx->adj_perm.ensure(n_cells * sizeof(int32_t)));
+        C5_HIP(ctx, hipMemcpy(ctx->adj_perm.ptr, ctx->cell_perm.data(), n_cells * sizeof(int32_t), hipMemcpyHostToDevice));
+        ctx->adj_perm_serial = ctx->grid_serial;
+    }
+    return C5_OK;
+}
+
 int setup_derivative(c5_context* ctx, DerivativeView& v) {
     if (ctx->n_cells <= 0 && [&] {
             for (const Solid& s : ctx->solids)
@@ -1237,16 +1257,12 @@ int setup_derivative(c5_context* ctx, DerivativeView& v) {
     const c5::ImageParams& im = ctx->im;
     const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
     const int64_t padded = ((n_px + 1023) / 1024) * 1024;
-    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
 
     C5_HIP(ctx, ctx->adj_counters.ensure(kCountersBytes));
     C5_HIP(ctx, ctx->adj_sticky.ensure(kStickyWords * sizeof(unsigned)));
     if (!ctx->adj_status) C5_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->adj_status), 4 * sizeof(unsigned), hipHostMallocDefault));
-    if (!ctx->cell_perm.empty() && ctx->adj_perm_serial != ctx->grid_serial) {
-        C5_HIP(ctx, ctx->adj_perm.ensure(n_cells * sizeof(int32_t)));
-        C5_HIP(ctx, hipMemcpy(ctx->adj_perm.ptr, ctx->cell_perm.data(), n_cells * sizeof(int32_t), hipMemcpyHostToDevice));
-        ctx->adj_perm_serial = ctx->grid_serial;
-    }
+    rc = ensure_device_perm(ctx);
+    if (rc) return rc;
     c5::FrameCounters* const counters = ctx->adj_counters.as<c5::FrameCounters>();
     C5_HIP(ctx, hipMemsetAsync(ctx->adj_sticky.ptr, 0, kStickyWords * sizeof(unsigned), s));
 
@@ -1414,6 +1430,111 @@ int enqueue_tangent(c5_context* ctx, const double* d_alpha, const double* d_q, f
     return commit_derivative(ctx, "tangent");
 }
 
+// Batches: the chunk width (4 or 8 directions / upstream images per walk; "batch_width").
+int batch_width(const c5_context* ctx, int n) {
+    if (ctx->batch_width) return ctx->batch_width;
+    return n <= 4 ? 4 : 8;
+}
+
+// n directions ([n][n_cells] fp64 each, the caller's order; null: zero) -> out[n][local_rows][res_x]: one per-view setup,
+// then per chunk of up to `width` directions a gather into device order and one walk; the entry heads stay in place
+// between the chunks and the last walk hands them back cleared.  On bin_sort_resolve's lists: tangent_resolve once per
+// direction (the first sorts the lists, the others find them sorted).  A batch of one is the single tangent.
+int enqueue_tangent_batch(c5_context* ctx, int n, const double* d_alpha, const double* d_q, float2* out) {
+    if (n == 1) return enqueue_tangent(ctx, d_alpha, d_q, out);
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const c5::ImageParams& im = ctx->im;
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    if (v.no_cells) {  // (nothing but solids: the images do not depend on any cell)
+        if (n_px > 0) C5_HIP(ctx, hipMemsetAsync(out, 0, static_cast<size_t>(n) * n_px * sizeof(float2), s));
+        return C5_OK;
+    }
+    FrameSlot& fs = ctx->slots[0];
+    const int64_t n_cells = ctx->n_cells;
+    const int32_t* const perm = ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>();
+    if (v.bin_sort) {
+        C5_HIP(ctx, ctx->tan_dir.ensure(static_cast<size_t>(n_cells) * sizeof(double2)));
+        double2* const dir = ctx->tan_dir.as<double2>();
+        for (int j = 0; j < n; ++j) {
+            c5::launch_tangent_gather(s, d_alpha ? d_alpha + j * n_cells : nullptr, d_q ? d_q + j * n_cells : nullptr, perm, n_cells, dir);
+            c5::launch_tangent_resolve(s, v.g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, dir,
+                                       out + j * n_px);
+        }
+        return commit_derivative(ctx, "tangent batch");
+    }
+    const int width = batch_width(ctx, n);
+    C5_HIP(ctx, ctx->bat_dirs.ensure(static_cast<size_t>(n_cells) * width * sizeof(double2)));
+    c5::TangentBatchParams tb{};
+    tb.w = v.w;
+    tb.dirs = ctx->bat_dirs.as<double2>();
+    tb.image_px = n_px;
+    for (int k0 = 0; k0 < n; k0 += width) {
+        tb.n_used = std::min(width, n - k0);
+        tb.out = out + k0 * n_px;
+        tb.keep_entries = k0 + width < n;
+        c5::launch_tangent_gather_batch(s, width, d_alpha, d_q, perm, n_cells, k0, tb.n_used, ctx->bat_dirs.as<double2>());
+        c5::launch_tangent_walk_batch(s, width, tb);
+    }
+    fs.head_clean = true;  // (the last chunk's walk hands every head back cleared)
+    return commit_derivative(ctx, "tangent batch");
+}
+
+// n upstream images ([n][local_rows][res_x] float2) -> ga_out / gq_out [n][n_cells] in the caller's order: one per-view
+// setup and ONE pass 1 (Lambda does not depend on the weights), then per chunk of up to `width` images the batched pass 2
+// into [n_cells][2 width] and its permutation.  On bin_sort_resolve's lists: adjoint_resolve once per image.  A batch of
+// one is the single adjoint.
+int enqueue_adjoint_batch(c5_context* ctx, int n, const float2* grad_out, double* ga_out, double* gq_out) {
+    if (n == 1) return enqueue_adjoint(ctx, grad_out, ga_out, gq_out);
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc || v.no_cells) return rc;
+    FrameSlot& fs = ctx->slots[0];
+    hipStream_t s = ctx->stream;
+    const c5::ImageParams& im = ctx->im;
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    const int64_t n_cells = ctx->n_cells;
+    const int32_t* const perm = ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>();
+    if (v.bin_sort) {
+        C5_HIP(ctx, ctx->adj_grad.ensure(2 * static_cast<size_t>(n_cells) * sizeof(double)));
+        double* const ga_dev = ctx->adj_grad.as<double>();
+        double* const gq_dev = ga_dev + n_cells;
+        for (int j = 0; j < n; ++j) {
+            C5_HIP(ctx, hipMemsetAsync(ga_dev, 0, 2 * static_cast<size_t>(n_cells) * sizeof(double), s));
+            c5::launch_adjoint_resolve(s, v.g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit,
+                                       grad_out + j * n_px, ga_dev, gq_dev);
+            c5::launch_adjoint_permute(s, ga_dev, gq_dev, perm, n_cells, ga_out + j * n_cells, gq_out + j * n_cells);
+        }
+        return commit_derivative(ctx, "adjoint batch");
+    }
+    const int width = batch_width(ctx, n);
+    const size_t grad_bytes = static_cast<size_t>(n_cells) * 2 * width * sizeof(double);
+    const int64_t padded = ((n_px + 1023) / 1024) * 1024;
+    C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(padded) * sizeof(double)));
+    C5_HIP(ctx, ctx->bat_grad.ensure(grad_bytes));
+    c5::AdjointParams ap{};
+    ap.w = v.w;
+    ap.lambda = ctx->adj_lambda.as<double>();
+    c5::launch_adjoint_walk(s, ap, 1);
+    c5::AdjointBatchParams ab{};
+    ab.w = v.w;
+    ab.image_px = n_px;
+    ab.lambda = ctx->adj_lambda.as<double>();
+    ab.grad = ctx->bat_grad.as<double>();
+    for (int k0 = 0; k0 < n; k0 += width) {
+        ab.n_used = std::min(width, n - k0);
+        ab.grad_out = grad_out + k0 * n_px;
+        ab.keep_entries = k0 + width < n;
+        C5_HIP(ctx, hipMemsetAsync(ab.grad, 0, grad_bytes, s));
+        c5::launch_adjoint_walk_batch(s, width, ab);
+        c5::launch_adjoint_permute_batch(s, width, ab.grad, perm, n_cells, k0, ab.n_used, ga_out, gq_out);
+    }
+    fs.head_clean = true;  // (the last chunk's pass 2 hands every head back cleared)
+    return commit_derivative(ctx, "adjoint batch");
+}
+
 // After the stream drained: the failure words of the last adjoint or tangent (as finish_frame treats a frame's).
 int finish_adjoint(c5_context* ctx) {
     if (!ctx->adjoint_pending) return C5_OK;
@@ -1552,9 +1673,11 @@ void c5_destroy(c5_context* ctx) {
     DeviceBuffer* bufs[] = {&ctx->px, &ctx->py, &ctx->pz, &ctx->cell_vert, &ctx->cell_adj, &ctx->alpha,
                             &ctx->q, &ctx->bface, &ctx->xtab, &ctx->ytab, &ctx->out, &ctx->sticky,
                             &ctx->offs64, &ctx->scratch64, &ctx->segs, &ctx->adj_lambda, &ctx->adj_counters,
-                            &ctx->adj_sticky, &ctx->adj_grad, &ctx->adj_perm, &ctx->adj_io, &ctx->tan_dir, &ctx->tan_io};
+                            &ctx->adj_sticky, &ctx->adj_grad, &ctx->adj_perm, &ctx->adj_io, &ctx->tan_dir, &ctx->tan_io,
+                            &ctx->bat_dirs, &ctx->bat_grad, &ctx->bat_io, &ctx->scal_stats};
     if (ctx->host_sticky) (void)hipHostFree(ctx->host_sticky);
     if (ctx->adj_status) (void)hipHostFree(ctx->adj_status);
+    if (ctx->scal_host) (void)hipHostFree(ctx->scal_host);
     if (ctx->host_sb) (void)hipHostFree(ctx->host_sb);
     for (DeviceBuffer* b : bufs) b->release();
     for (FrameSlot& fs : ctx->slots) {
@@ -1855,6 +1978,47 @@ int c5_update_scalars(c5_context* ctx, const double* alpha, const double* q, int
     return C5_OK;
 }
 
+int c5_update_scalars_device(c5_context* ctx, const void* alpha_dev, const void* q_dev, int64_t n_cells) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    ++ctx->setup_epoch;  // whatever was built per view is stale ("view_cache")
+    if (n_cells != ctx->n_cells) return fail(ctx, C5_ERR_INVALID, "scalar count differs from the uploaded grid");
+    if (n_cells > 0 && (!alpha_dev || !q_dev)) return fail(ctx, C5_ERR_INVALID, "null scalar array");
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    if (ctx->pipeline || ctx->overlap_setup) {  // (frames set up on the other streams read the scalars)
+        rc = drain(ctx);
+        if (rc) return rc;
+    }
+    double top = 0.0, floor = INFINITY;
+    if (n_cells > 0) {
+        rc = ensure_device_perm(ctx);
+        if (rc) return rc;
+        C5_HIP(ctx, ctx->scal_stats.ensure(4 * sizeof(unsigned long long)));
+        if (!ctx->scal_host)
+            C5_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->scal_host), 4 * sizeof(unsigned long long), hipHostMallocDefault));
+        unsigned long long* const stats = ctx->scal_stats.as<unsigned long long>();
+        hipStream_t s = ctx->stream;
+        C5_HIP(ctx, hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), s));
+        c5::launch_scalars_gather(s, static_cast<const double*>(alpha_dev), static_cast<const double*>(q_dev),
+                                  ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>(), n_cells, ctx->alpha.as<double>(),
+                                  ctx->q.as<double>(), stats);
+        C5_HIP(ctx, hipGetLastError());
+        C5_HIP(ctx, hipMemcpyAsync(ctx->scal_host, stats, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        C5_HIP(ctx, hipStreamSynchronize(s));
+        unsigned long long bits = ctx->scal_host[0];
+        std::memcpy(&top, &bits, sizeof top);
+        if (ctx->scal_host[2]) {
+            floor = 0.0;  // (a NaN alpha)
+        } else if (ctx->scal_host[1]) {
+            bits = ~ctx->scal_host[1];
+            std::memcpy(&floor, &bits, sizeof floor);
+        }
+    }
+    ctx->alpha_top = top;
+    ctx->alpha_floor = floor;
+    return C5_OK;
+}
+
 int c5_set_solid(c5_context* ctx, int slot, const double* tets, int64_t n_tets, double colour) {
     if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
     if (slot < 0 || slot >= C5_MAX_SOLIDS) return fail(ctx, C5_ERR_INVALID, "solid slot %d out of range", slot);
@@ -2110,6 +2274,9 @@ int c5_set_option(c5_context* ctx, const char* name, double value) {
         for (Solid& so : ctx->solids) so.own_mask_ready = false, so.unchanged_frames = 0, so.seen_generation = ~uint64_t{0};
     } else if (n == "view_cache") {
         ctx->view_cache = static_cast<int>(value) != 0;
+    } else if (n == "batch_width") {
+        if (value != 0 && value != 4 && value != 8) return fail(ctx, C5_ERR_INVALID, "batch_width must be 0 (by the batch), 4 or 8");
+        ctx->batch_width = static_cast<int>(value);
     } else if (n == "split_tilt_x" || n == "split_tilt_y") {  // testing: tilt of a forced split's planes
         if (!(std::fabs(value) < 64.0)) return fail(ctx, C5_ERR_INVALID, "split tilt out of range");
         (n == "split_tilt_x" ? ctx->split_tilt_x : ctx->split_tilt_y) = value;
@@ -2299,6 +2466,85 @@ int c5_render_tangent(c5_context* ctx, const double* d_alpha_host, const double*
         return C5_OK;
     }
     return fail(ctx, C5_ERR_STATE, "tangent: entry buffer kept overflowing");
+}
+
+int c5_render_tangent_batch_device(c5_context* ctx, int n_dirs, const void* d_alpha_dev, const void* d_q_dev, void* out_dev) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (n_dirs < 1) return fail(ctx, C5_ERR_INVALID, "a batch needs at least one direction (%d)", n_dirs);
+    if (!out_dev) return fail(ctx, C5_ERR_INVALID, "null output pointer");
+    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_tangent_batch while c5_render_host_async frames are outstanding");
+    return enqueue_tangent_batch(ctx, n_dirs, static_cast<const double*>(d_alpha_dev), static_cast<const double*>(d_q_dev),
+                                 static_cast<float2*>(out_dev));
+}
+
+int c5_render_tangent_batch(c5_context* ctx, int n_dirs, const double* d_alpha_host, const double* d_q_host, float* out_host) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (n_dirs < 1) return fail(ctx, C5_ERR_INVALID, "a batch needs at least one direction (%d)", n_dirs);
+    if (!out_host) return fail(ctx, C5_ERR_INVALID, "null output pointer");
+    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_tangent_batch while c5_render_host_async frames are outstanding");
+    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    const size_t img_bytes = static_cast<size_t>(n_dirs) * ctx->im.n_local_rows * ctx->im.res_x * 2 * sizeof(float);
+    const size_t dir_bytes = static_cast<size_t>(n_dirs) * static_cast<size_t>(ctx->n_cells) * sizeof(double);
+    C5_HIP(ctx, ctx->bat_io.ensure(2 * dir_bytes + img_bytes + 16));
+    double* const da = ctx->bat_io.as<double>();
+    double* const dq = reinterpret_cast<double*>(reinterpret_cast<char*>(da) + dir_bytes);
+    float2* const img = reinterpret_cast<float2*>(reinterpret_cast<char*>(dq) + dir_bytes);
+    if (d_alpha_host && dir_bytes > 0) C5_HIP(ctx, hipMemcpyAsync(da, d_alpha_host, dir_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (d_q_host && dir_bytes > 0) C5_HIP(ctx, hipMemcpyAsync(dq, d_q_host, dir_bytes, hipMemcpyHostToDevice, ctx->stream));
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        rc = enqueue_tangent_batch(ctx, n_dirs, d_alpha_host ? da : nullptr, d_q_host ? dq : nullptr, img);
+        if (rc) return rc;
+        rc = c5_synchronize(ctx);
+        if (rc == C5_RETRY) continue;
+        if (rc) return rc;
+        if (img_bytes > 0) C5_HIP(ctx, hipMemcpy(out_host, img, img_bytes, hipMemcpyDeviceToHost));
+        return C5_OK;
+    }
+    return fail(ctx, C5_ERR_STATE, "tangent batch: entry buffer kept overflowing");
+}
+
+int c5_render_adjoint_batch_device(c5_context* ctx, int n_imgs, const void* grad_out_dev, void* grad_alpha_dev, void* grad_q_dev) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (n_imgs < 1) return fail(ctx, C5_ERR_INVALID, "a batch needs at least one upstream image (%d)", n_imgs);
+    if (!grad_out_dev || (ctx->n_cells > 0 && (!grad_alpha_dev || !grad_q_dev)))
+        return fail(ctx, C5_ERR_INVALID, "null adjoint pointer");
+    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_adjoint_batch while c5_render_host_async frames are outstanding");
+    return enqueue_adjoint_batch(ctx, n_imgs, static_cast<const float2*>(grad_out_dev), static_cast<double*>(grad_alpha_dev),
+                                 static_cast<double*>(grad_q_dev));
+}
+
+int c5_render_adjoint_batch(c5_context* ctx, int n_imgs, const float* grad_out_host, double* grad_alpha_host, double* grad_q_host) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (n_imgs < 1) return fail(ctx, C5_ERR_INVALID, "a batch needs at least one upstream image (%d)", n_imgs);
+    if (!grad_out_host || (ctx->n_cells > 0 && (!grad_alpha_host || !grad_q_host)))
+        return fail(ctx, C5_ERR_INVALID, "null adjoint pointer");
+    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_adjoint_batch while c5_render_host_async frames are outstanding");
+    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    const size_t img_bytes = static_cast<size_t>(n_imgs) * ctx->im.n_local_rows * ctx->im.res_x * 2 * sizeof(float);
+    const size_t img_room = (img_bytes + 255) / 256 * 256;
+    const size_t grad_bytes = static_cast<size_t>(n_imgs) * static_cast<size_t>(ctx->n_cells) * sizeof(double);
+    C5_HIP(ctx, ctx->bat_io.ensure(img_room + 2 * grad_bytes + 16));
+    char* const io = ctx->bat_io.as<char>();
+    double* const ga = reinterpret_cast<double*>(io + img_room);
+    double* const gq = reinterpret_cast<double*>(io + img_room + grad_bytes);
+    C5_HIP(ctx, hipMemcpyAsync(io, grad_out_host, img_bytes, hipMemcpyHostToDevice, ctx->stream));
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        rc = enqueue_adjoint_batch(ctx, n_imgs, reinterpret_cast<const float2*>(io), ga, gq);
+        if (rc) return rc;
+        rc = c5_synchronize(ctx);
+        if (rc == C5_RETRY) continue;
+        if (rc) return rc;
+        if (grad_bytes > 0) {
+            C5_HIP(ctx, hipMemcpy(grad_alpha_host, ga, grad_bytes, hipMemcpyDeviceToHost));
+            C5_HIP(ctx, hipMemcpy(grad_q_host, gq, grad_bytes, hipMemcpyDeviceToHost));
+        }
+        return C5_OK;
+    }
+    return fail(ctx, C5_ERR_STATE, "adjoint batch: entry buffer kept overflowing");
 }
 
 namespace {

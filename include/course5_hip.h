@@ -120,6 +120,11 @@ int c5_upload_grid(c5_context* ctx, const double* xyz, int64_t n_pts, const int3
                    int64_t n_cells, const double* alpha, const double* q);
 /* Replace only the cell scalars of the uploaded grid. */
 int c5_update_scalars(c5_context* ctx, const double* alpha, const double* q, int64_t n_cells);
+/* The same from device memory (hipMalloc'ed by anyone in this process, the caller's cell order): gathered into the
+ * library's order on the context's stream, which sees the caller's work before it when it is the caller's own stream
+ * (c5_set_stream).  The host needs the largest and the smallest alpha (the walk's choices, "depth_split"): the call reads
+ * them back and WAITS for the stream.  A render after it returns the same bits as after c5_update_scalars. */
+int c5_update_scalars_device(c5_context* ctx, const void* alpha_dev, const void* q_dev, int64_t n_cells);
 /* Solid object `slot` (0..C5_MAX_SOLIDS-1): tets[n][4][3] raw vertex copies, one colour.
  * Replaces the solid part of the tetra vector (main.cpp:110-116,127; plane.cpp:130-131).
  * n == 0 removes the object.  Higher slots / higher tet index win ties, like serial -j1. */
@@ -220,6 +225,8 @@ int c5_set_alpha_limit(c5_context* ctx, double alpha_limit);
  *                  Anything the data depend on makes them stale: c5_upload_grid, c5_update_scalars, c5_set_image, the row
  *                  setters, c5_set_stream, any option but "row_costs" / "stage_timing" / "walk_timing", a grown entry pool.
  *                  A sweep whose view changes every frame never pays for it.  0: every frame builds its own.  Same results.
+ *   "batch_width"  tuning: directions or upstream images one walk of c5_render_tangent_batch* / c5_render_adjoint_batch*
+ *                  carries: 4 or 8; 0 (default): 4 for batches of up to 4, else 8.  Same results (the adjoint's to rounding).
  *   "overlap_setup" 1: entry lists and solid mask are built on a side stream while build_records
  *                  runs (only when "stage_timing" is 0).  Default 0: measured no faster.
  *   "pipeline"     1: two frame slots; the per-view setup of frame k + 1 runs on a second stream while
@@ -298,6 +305,29 @@ int c5_render_adjoint_device(c5_context* ctx, const void* grad_out_device, void*
  * outstanding. */
 int c5_render_tangent(c5_context* ctx, const double* d_alpha_host, const double* d_q_host, float* out_host);
 int c5_render_tangent_device(c5_context* ctx, const void* d_alpha_dev, const void* d_q_dev, void* out_device);
+
+/* --- batched derivative renders -----------------------------------------------------------------
+ * n tangents or n adjoints of the same frame in one call: what a Jacobian against a few parameters, several losses at
+ * once or a block of Gauss-Newton / CG directions asks for.  The per-view setup is built once and every ray is walked
+ * once for up to "batch_width" directions or upstream images at a time; the adjoint's first pass (the ray's optical
+ * depths) runs once for all n.
+ * c5_render_tangent_batch: d_alpha / d_q [n_dirs][n_cells] fp64 in the caller's cell order, either may be NULL (zero);
+ * out [n_dirs][local_rows][res_x][2] fp32.  Every slice is bit for bit what c5_render_tangent returns for that direction
+ * alone, whatever the batch size or "batch_width" (on "algorithm" 1, a pixel whose list holds segments of equal depth
+ * takes them in the order the lists were filled in, which may change from call to call: for the single call too).
+ * c5_render_adjoint_batch: grad_out [n_imgs][local_rows][res_x][2] fp32; grad_alpha / grad_q [n_imgs][n_cells] fp64 in
+ * the caller's order, overwritten.  Every slice is c5_render_adjoint's for that image alone to rounding: fp64 atomics
+ * added in arrival order, NOT bit-reproducible from run to run (as the single adjoint).
+ * n < 1 or a null output: C5_ERR_INVALID.  Side effects, status and retries: as the single calls' (their counters and
+ * status words, never a frame's; a c5_render after them returns what it would have without them); the first call
+ * allocates 16 x "batch_width" bytes per cell (the adjoint twice that); the synchronous forms, room for the caller's
+ * arrays besides.  The _device forms are asynchronous on the context's stream with device arrays; their status
+ * (C5_RETRY included: run them again) is reported by the next call that waits for the stream.  All four refuse while
+ * c5_render_host_async frames are outstanding. */
+int c5_render_tangent_batch(c5_context* ctx, int n_dirs, const double* d_alpha_host, const double* d_q_host, float* out_host);
+int c5_render_tangent_batch_device(c5_context* ctx, int n_dirs, const void* d_alpha_dev, const void* d_q_dev, void* out_dev);
+int c5_render_adjoint_batch(c5_context* ctx, int n_imgs, const float* grad_out_host, double* grad_alpha_host, double* grad_q_host);
+int c5_render_adjoint_batch_device(c5_context* ctx, int n_imgs, const void* grad_out_dev, void* grad_alpha_dev, void* grad_q_dev);
 
 /* --- frames delivered to host memory, pipelined ----------------------------------------------------
  * plane::trace_rays hands back HOST pixels (plane.cpp:144-172); over PCIe Gen5 a 2400x1800 image is
