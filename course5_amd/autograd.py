@@ -31,6 +31,11 @@ an update_scalars) uploads its own again, from the copy the forward kept (on the
 backward or jvp after the view, image, rows, solids, alpha limit or grid changed raises instead of differentiating a frame
 other than the one rendered.  The gradients are fp64 sums added by atomics in arrival order: not bit-reproducible from run
 to run; the tangent is, batched or not.
+
+Beside render, two operators for Gauss-Newton fits (course5_amd.fit): gn_product(ctx, alpha, q, v_alpha, v_q, weight) =
+J^T W J v and gn_diagonal(ctx, alpha, q, weight) = diag(J^T W J), one library call each (c5_render_gn_product_device,
+c5_render_gn_diagonal_device).  They upload the scalars as the forward does, return float64 tensors on the context's GPU
+without a graph, and raise under a differentiating torch.func transform.
 """
 from __future__ import annotations
 
@@ -280,4 +285,67 @@ def render(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor) -> torch.Ten
     return _Render.apply(ctx, alpha, q)
 
 
-__all__ = ["render"]
+# ---- Gauss-Newton operators ------------------------------------------------------------------------------------------
+# H v = J^T W J v and diag(J^T W J) of the frame with the scalars (alpha, q): what a Gauss-Newton / CG fit calls in its
+# inner loop (course5_amd.fit).  Operators, not differentiable functions: the results carry no graph.
+
+def _gn_enter(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, what: str) -> torch.device:
+    if _differentiating_levels():
+        raise RuntimeError(f"course5_amd.autograd.{what}: it is an operator with no derivative of its own (second derivatives "
+                           "are not supported); call it outside torch.func.grad / vjp / jvp")
+    alpha, q = _plain(alpha).detach(), _plain(q).detach()
+    if alpha.shape != (ctx.n_cells,) or q.shape != (ctx.n_cells,):
+        raise ValueError(f"alpha and q must hold one value per cell ({ctx.n_cells})")
+    device = torch.device("cuda", ctx.device)
+    if all(t.is_cuda and t.device.index == ctx.device for t in (alpha, q)):
+        _upload(ctx, _Scalars(alpha.to(dtype=torch.float64, copy=True).contiguous(), q.to(dtype=torch.float64, copy=True).contiguous()))
+    else:
+        _upload(ctx, _Scalars(alpha.to("cpu", torch.float64).contiguous().numpy().copy(),
+                              q.to("cpu", torch.float64).contiguous().numpy().copy()))
+    return device
+
+
+def _gn_weight(ctx: capi.Context, weight, device: torch.device):
+    if weight is None:
+        return None
+    w = _plain(weight).detach().to(device=device, dtype=torch.float32).contiguous()
+    if tuple(w.shape) != (ctx.local_rows, ctx.res_x, 2):
+        raise ValueError(f"weight must be [{ctx.local_rows}, {ctx.res_x}, 2], not {list(w.shape)}")
+    return w
+
+
+def gn_product(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, v_alpha, v_q, weight=None) -> tuple:
+    """(h_alpha, h_q) = J^T W J (v_alpha, v_q) for the frame of `ctx` with the scalars alpha and q: v_alpha / v_q [n_cells]
+    or [K, n_cells] (either may be None: zero), weight [local_rows, res_x, 2] (None: ones).  float64 on the context's GPU,
+    shaped like the directions.  One library call (c5_render_gn_product_device) on torch's current stream."""
+    device = _gn_enter(ctx, alpha, q, "gn_product")
+    given = [v for v in (v_alpha, v_q) if v is not None]
+    if not given or any(v.shape != given[0].shape for v in given) or given[0].ndim not in (1, 2) or given[0].shape[-1] != ctx.n_cells:
+        raise ValueError(f"v_alpha and / or v_q must be [{ctx.n_cells}] or [K, {ctx.n_cells}], of one shape")
+    single = given[0].ndim == 1
+    with torch.cuda.device(device):
+        va, vq = (None if v is None else _plain(v).detach().to(device=device, dtype=torch.float64).reshape(-1, ctx.n_cells).contiguous()
+                  for v in (v_alpha, v_q))
+        w = _gn_weight(ctx, weight, device)
+        k = (va if va is not None else vq).shape[0]
+        ha = torch.empty((k, ctx.n_cells), dtype=torch.float64, device=device)
+        hq = torch.empty((k, ctx.n_cells), dtype=torch.float64, device=device)
+        _use_torch_stream(ctx, device)
+        _run(ctx, lambda: ctx.render_gn_product_device(va, vq, w, ha, hq, None, n=k))
+    return (ha[0], hq[0]) if single else (ha, hq)
+
+
+def gn_diagonal(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, weight=None) -> tuple:
+    """(d_alpha, d_q) = diag(J^T W J), float64 [n_cells] each on the context's GPU (c5_render_gn_diagonal_device on
+    torch's current stream)."""
+    device = _gn_enter(ctx, alpha, q, "gn_diagonal")
+    with torch.cuda.device(device):
+        w = _gn_weight(ctx, weight, device)
+        da = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
+        dq = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
+        _use_torch_stream(ctx, device)
+        _run(ctx, lambda: ctx.render_gn_diagonal_device(w, da, dq))
+    return da, dq
+
+
+__all__ = ["render", "gn_product", "gn_diagonal"]

@@ -31,6 +31,7 @@ EXPORTS = [
     "c5_render_adjoint", "c5_render_adjoint_device", "c5_render_tangent", "c5_render_tangent_device",
     "c5_render_tangent_batch", "c5_render_tangent_batch_device", "c5_render_adjoint_batch", "c5_render_adjoint_batch_device",
     "c5_update_scalars_device",
+    "c5_render_gn_product", "c5_render_gn_product_device", "c5_render_gn_diagonal", "c5_render_gn_diagonal_device",
 ]
 
 
@@ -111,6 +112,10 @@ def load_library() -> C.CDLL:
     lib.c5_render_adjoint_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_float), dp, dp]
     lib.c5_render_adjoint_batch_device.argtypes = [vp, C.c_int, vp, vp, vp]
     lib.c5_update_scalars_device.argtypes = [vp, vp, vp, C.c_int64]
+    lib.c5_render_gn_product.argtypes = [vp, C.c_int, dp, dp, C.POINTER(C.c_float), dp, dp, C.POINTER(C.c_float)]
+    lib.c5_render_gn_product_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.c5_render_gn_diagonal.argtypes = [vp, C.POINTER(C.c_float), dp, dp]
+    lib.c5_render_gn_diagonal_device.argtypes = [vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("c5_destroy", "c5_last_error"):
             getattr(lib, name).restype = C.c_int
@@ -407,6 +412,79 @@ class Context:
             self.handle, k, C.c_void_p(_device_ptr(grad_out, torch.float32, (k, self.local_rows, self.res_x, 2))),
             C.c_void_p(_device_ptr(grad_alpha, torch.float64, (k, self.n_cells))),
             C.c_void_p(_device_ptr(grad_q, torch.float64, (k, self.n_cells)))))
+
+    # -- Gauss-Newton renders -----------------------------------------------------------------------
+    def _weight_image(self, weight):
+        if weight is None:
+            return None
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        if w.shape != (self.local_rows, self.res_x, 2):
+            raise ValueError(f"weight must be [{self.local_rows}, {self.res_x}, 2], not {list(w.shape)}")
+        return w
+
+    def render_gn_product(self, d_alpha=None, d_q=None, weight=None, want_jv: bool = False, fit=("alpha", "q")):
+        """H v = J^T W J v for K directions (d_alpha / d_q: [K, n_cells], either may be None: zero), J the Jacobian of the
+        frame render() would produce now, W = diag(weight) ([local_rows, res_x, 2] float32 >= 0; None: ones):
+        (h_alpha, h_q), float64 [K, n_cells] each; with want_jv also J v, float32 [K, local_rows, res_x, 2], bit for bit
+        render_tangent_batch's.  fit names the blocks wanted (the other comes back as None).  One call for
+        render_adjoint_batch(weight * render_tangent_batch(v)); synchronous, retries by itself."""
+        da, dq, k = self._batch_directions(d_alpha, d_q)
+        w = self._weight_image(weight)
+        fit = tuple(fit)
+        if not fit or any(f not in ("alpha", "q") for f in fit):
+            raise ValueError(f"fit must name 'alpha', 'q' or both, not {fit!r}")
+        ha = np.zeros((k, self.n_cells), dtype=np.float64) if "alpha" in fit else None
+        hq = np.zeros((k, self.n_cells), dtype=np.float64) if "q" in fit else None
+        jv = np.zeros((k, self.local_rows, self.res_x, 2), dtype=np.float32) if want_jv else None
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.c5_render_gn_product(
+            self.handle, k, None if da is None else _dp(da), None if dq is None else _dp(dq),
+            None if w is None else w.ctypes.data_as(fp), None if ha is None else _dp(ha), None if hq is None else _dp(hq),
+            None if jv is None else jv.ctypes.data_as(fp)))
+        return (ha, hq, jv) if want_jv else (ha, hq)
+
+    def render_gn_product_device(self, d_alpha, d_q, weight, h_alpha, h_q, jv_out=None, n: int | None = None):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (d_alpha / d_q float64 [K,
+        n_cells] or None, weight float32 [local_rows, res_x, 2] or None, h_alpha / h_q float64 [K, n_cells], one of them
+        may be None, jv_out float32 [K, local_rows, res_x, 2] or None; contiguous) or raw device pointers (then give
+        n = K).  The status comes with the next synchronize() (C5_RETRY: run it again)."""
+        import torch
+        if n is None:
+            shaped = [t for t in (h_alpha, h_q, d_alpha, d_q) if t is not None and not isinstance(t, int)]
+            if not shaped:
+                raise ValueError("give n with raw device pointers")
+            n = shaped[0].shape[0]
+        if d_alpha is None and d_q is None:
+            raise ValueError("give d_alpha and / or d_q")
+        if h_alpha is None and h_q is None:
+            raise ValueError("give h_alpha and / or h_q")
+        self._check(self.lib.c5_render_gn_product_device(
+            self.handle, n, C.c_void_p(_device_ptr(d_alpha, torch.float64, (n, self.n_cells)) or None),
+            C.c_void_p(_device_ptr(d_q, torch.float64, (n, self.n_cells)) or None),
+            C.c_void_p(_device_ptr(weight, torch.float32, (self.local_rows, self.res_x, 2)) or None),
+            C.c_void_p(_device_ptr(h_alpha, torch.float64, (n, self.n_cells)) or None),
+            C.c_void_p(_device_ptr(h_q, torch.float64, (n, self.n_cells)) or None),
+            C.c_void_p(_device_ptr(jv_out, torch.float32, (n, self.local_rows, self.res_x, 2)) or None)))
+
+    def render_gn_diagonal(self, weight=None) -> tuple:
+        """diag(J^T W J) as (diag_alpha, diag_q), float64 [n_cells] each in the order of upload_grid (weight: as
+        render_gn_product).  Synchronous; retries by itself."""
+        w = self._weight_image(weight)
+        da = np.zeros(self.n_cells, dtype=np.float64)
+        dq = np.zeros(self.n_cells, dtype=np.float64)
+        self._check(self.lib.c5_render_gn_diagonal(self.handle, None if w is None else w.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   _dp(da), _dp(dq)))
+        return da, dq
+
+    def render_gn_diagonal_device(self, weight, diag_alpha, diag_q):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (weight float32 [local_rows,
+        res_x, 2] or None, diag_alpha / diag_q float64 [n_cells]; contiguous) or raw device pointers.  The status comes
+        with the next synchronize() (C5_RETRY: run it again)."""
+        import torch
+        self._check(self.lib.c5_render_gn_diagonal_device(
+            self.handle, C.c_void_p(_device_ptr(weight, torch.float32, (self.local_rows, self.res_x, 2)) or None),
+            C.c_void_p(_device_ptr(diag_alpha, torch.float64, (self.n_cells,))),
+            C.c_void_p(_device_ptr(diag_q, torch.float64, (self.n_cells,)))))
 
     # -- frames delivered to host memory, pipelined -------------------------------------------------
     def host_image(self, full: bool = False) -> np.ndarray:

@@ -94,6 +94,33 @@ void launch_adjoint_walk_batch(hipStream_t s, int kc, const AdjointBatchParams& 
 void launch_adjoint_permute_batch(hipStream_t s, int kc, const double* grad, const int32_t* perm, int64_t n, int k0, int n_used,
                                   double* ga_out, double* gq_out);
 
+// ---- Gauss-Newton renders (c5_render_gn_product*, c5_render_gn_diagonal*)
+
+struct GnWalkParams {
+    WalkParams w;          // as TangentParams
+    const double2* dirs;   // [n_cells][kc] device order (launch_tangent_gather_batch)
+    const float2* weight;  // [n_local_rows][res_x] (w_tau, w_I), or nullptr: ones
+    double* lambda;        // [n_local_px] out: pass 1's Lambda
+    float2* g;             // [n_used][n_local_rows][res_x] out: w * (float)(tau_dot, I_dot), one fp32 multiply per channel
+    float2* jv_out;        // the same shape, out: (tau_dot, I_dot) as launch_tangent_walk_batch stores them; or nullptr
+    int64_t image_px;      // pixels per image
+    int32_t n_used;        // directions of the chunk (<= kc)
+};
+
+// tangent_walk_batch's walk that is also pass 1 of the adjoint: leaves the entry heads in place and counts as pass 1 does
+void launch_gn_walk_a(hipStream_t s, int kc, const GnWalkParams& a);
+
+// adjoint_walk<2> with the segment terms squared (needs pass 1 first): a.grad_out holds the weights (nullptr: ones),
+// a.grad_a / a.grad_q accumulate diag(J^T W J); hands the heads back cleared
+void launch_gn_diag_walk(hipStream_t s, const AdjointParams& a);
+
+// g[j][p] = w[p] * t[j][p] per channel in fp32 (w nullptr: ones), n_imgs images of n_px pixels
+void launch_gn_weight(hipStream_t s, const float2* t, const float2* w, int64_t n_px, int n_imgs, float2* g);
+
+// launch_adjoint_resolve's twin for the diagonal
+void launch_gn_diag_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const int64_t* offs, void* segs,
+                            const uint32_t* mask, double alpha_limit, const float2* weight, double* diag_a, double* diag_q);
+
 // c5_update_scalars_device: alpha[i] = alpha_src[perm[i]], q[i] = q_src[perm[i]] (perm nullptr: the identity), and into
 // stats[3] (zeroed by the caller): the bits of the largest alpha > 0, the complemented bits of the smallest alpha >=
 // DBL_EPSILON, and 1 if some alpha is NaN (the host loop of c5_update_scalars, as an order-free max / min / or)

@@ -807,6 +807,298 @@ __global__ __launch_bounds__(256) void adjoint_permute_batch(const double* __res
     gq_out[static_cast<int64_t>(k0 + j) * n + d] = grad[i * (2 * KC) + KC + j];
 }
 
+// ---- Gauss-Newton renders (c5_render_gn_product*, c5_render_gn_diagonal*) ------------------------------------------------
+// H v = J^T W J v and diag(J^T W J), J the Jacobian of the image with respect to (alpha, Q), W a per-pixel, per-channel
+// weight image.
+//   gn_walk_a<KC>     tangent_walk_batch<KC>'s walk that is also adjoint_walk<1>: per pixel Lambda, and per direction
+//                     g = w * (float)(tau_dot, I_dot), ONE fp32 multiply per channel - the bits a caller would get who
+//                     multiplied render_tangent_batch's image by the weights in fp32 and handed it to
+//                     render_adjoint_batch.  The fp32 intermediate is deliberate: with it the fused product IS that
+//                     composition up to the order of pass B's atomics, which is what it is tested against.
+//   pass B            adjoint_walk_batch<KC> as it is, on g and Lambda.
+//   gn_diag_walk      adjoint_walk<2> with the segment's terms squared: d_alpha += w_tau dz^2 + w_I (dI/dalpha_k)^2,
+//                     d_q += w_I (dI/dQ_k)^2 (a ray crosses a convex cell in at most one segment, so the Jacobian's entry
+//                     of (pixel, cell) is that segment's term).
+//   gn_weight / gn_diag_resolve   the same over bin_sort_resolve's lists ("algorithm" 1).
+
+template <int KC>
+__global__ __launch_bounds__(64) void gn_walk_a(GnWalkParams A) {
+    using namespace adj;
+    const WalkParams& P = A.w;
+    const ImageParams& im = P.im;
+    const D2* __restrict__ dirs = reinterpret_cast<const D2*>(A.dirs);
+    const int tiles_x = (im.res_x + 7) / 8;
+    const int ty = static_cast<int>(blockIdx.x) / tiles_x, tx = static_cast<int>(blockIdx.x) - ty * tiles_x;
+    const int lane = static_cast<int>(threadIdx.x);
+    const int col = tx * 8 + (lane & 7), lrow = ty * 8 + (lane >> 3);
+    const bool in_image = (col < im.res_x) && (lrow < im.n_local_rows);
+
+    unsigned n_step = 0, overflow = 0;
+    bool skipped = false;
+    double key_taken = -DBL_MAX;
+    double x = 0.0, y = 0.0, w_cur = -DBL_MAX, carry = 0.0;
+    EntryHead ent{0, 0};
+    int cell = -1;
+    size_t lp = 0;
+    double lam = 0.0;  // Lambda, summed as adjoint_walk<1> sums it
+    double I = 0.0, I_dot[KC], tau_dot[KC];
+#pragma unroll
+    for (int j = 0; j < KC; ++j) I_dot[j] = tau_dot[j] = 0.0;
+
+    if (in_image) {
+        lp = static_cast<size_t>(lrow) * im.res_x + col;
+        const uint32_t mv = P.mask ? P.mask[lp] : 0u;
+        if (!mv) {  // (a solid-marked pixel shows the solid: line.cpp:177-179, nothing of the grid)
+            x = P.Xtab[col];
+            y = P.Ytab[global_row_of(im, lrow)];
+            ent = load_entry_head(P.entry_head + lp);
+            if (ent.count > 0) cell = next_entry<true>(P, lp, ent, w_cur, carry, -DBL_MAX, -DBL_MAX, skipped);
+            key_taken = w_cur;
+        }
+    }
+
+    CellRegs cur;
+    if (cell >= 0) load_cell(cur, P.xrec, cell);
+
+    while (cell >= 0) {
+        D2 d[KC];
+#pragma unroll
+        for (int j = 0; j < KC; ++j) d[j] = dirs[static_cast<size_t>(cell) * KC + j];
+        // the step of tangent_walk_batch, operation for operation
+        const StepGeometry sg = step_geometry(cur, x, y);
+        ++n_step;
+        const bool has_exit = sg.w_exit < INFINITY;
+        const double dz = sg.w_exit - carry;
+        const bool contributes = dz > 0.0 && dz < INFINITY;
+        int nb = -1;
+        double carry_next = carry;
+        if (has_exit) {
+            carry_next = sg.w_exit;
+            w_cur = fmax(w_cur, sg.w_exit);
+            const uint32_t id = sg.w_out & kIdMask;
+            if (id != kNoCell) nb = static_cast<int>(id);
+        }
+        if (nb >= 0 && n_step >= P.max_steps) {
+            overflow = 1;
+            nb = -1;
+        } else if (nb < 0 && !overflow) {
+            nb = next_entry<true>(P, lp, ent, w_cur, carry_next, key_taken, has_exit ? sg.w_exit : -DBL_MAX, skipped);
+            key_taken = w_cur;
+        }
+        CellRegs nxt;
+        if (nb >= 0) load_cell(nxt, P.xrec, nb);
+
+        if (contributes) {
+            const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+#pragma unroll
+            for (int j = 0; j < KC; ++j) tau_dot[j] = fma(dz, d[j].a, tau_dot[j]);  // d tau / d alpha (raw alpha)
+            if (a != 0.0) {
+                lam = fma(a, dz, lam);  // (adjoint_walk<1>: pass B's running Lambda_k ends on this to the bit)
+                const double E = exp_nonpositive(-a * dz);
+                const SegmentTerms t = segment_terms(a, q, dz, E, 1.0, I);
+                const bool clamped = a != a_raw;
+#pragma unroll
+                for (int j = 0; j < KC; ++j) {
+                    double src = d[j].b * t.dI_dq;
+                    if (!clamped) src = fma(d[j].a, t.dI_da, src);  // (a clamped alpha does not move: line.cpp:216)
+                    I_dot[j] = fma(E, I_dot[j], src);
+                }
+                I = t.I_next;
+            }
+        }
+        cell = nb;
+        carry = carry_next;
+        cur = nxt;
+    }
+
+    if (in_image) {
+        A.lambda[lp] = lam;
+        const float2 w = A.weight ? A.weight[lp] : make_float2(1.0f, 1.0f);  // (loaded here, not held across the loop)
+#pragma unroll
+        for (int j = 0; j < KC; ++j)
+            if (j < A.n_used) {
+                const float2 t = make_float2(static_cast<float>(tau_dot[j]), static_cast<float>(I_dot[j]));
+                if (A.jv_out) A.jv_out[static_cast<size_t>(j) * A.image_px + lp] = t;
+                A.g[static_cast<size_t>(j) * A.image_px + lp] = make_float2(__fmul_rn(w.x, t.x), __fmul_rn(w.y, t.y));
+            }
+        // (the entry heads stay in place for pass B)
+    }
+    const unsigned s_ovf = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(overflow != 0u)));
+    const unsigned s_skip = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(skipped)));
+    if (lane == 0) {
+        if (s_ovf) atomicAdd(&P.counters->walk_overflow, s_ovf);
+        if (s_skip) atomicAdd(&P.counters->overlap_rays, s_skip);
+    }
+}
+
+// adjoint_walk<2> with squares (after adjoint_walk<1>: A.lambda).  A.grad_out holds the weights, or nullptr for ones.
+__global__ __launch_bounds__(64) void gn_diag_walk(AdjointParams A) {
+    using namespace adj;
+    const WalkParams& P = A.w;
+    const ImageParams& im = P.im;
+    const int tiles_x = (im.res_x + 7) / 8;
+    const int ty = static_cast<int>(blockIdx.x) / tiles_x, tx = static_cast<int>(blockIdx.x) - ty * tiles_x;
+    const int lane = static_cast<int>(threadIdx.x);
+    const int col = tx * 8 + (lane & 7), lrow = ty * 8 + (lane >> 3);
+    const bool in_image = (col < im.res_x) && (lrow < im.n_local_rows);
+
+    unsigned n_step = 0, overflow = 0;
+    bool skipped = false;
+    double key_taken = -DBL_MAX;
+    double x = 0.0, y = 0.0, w_cur = -DBL_MAX, carry = 0.0;
+    EntryHead ent{0, 0};
+    int cell = -1;
+    size_t lp = 0;
+    double lam = 0.0, lam_total = 0.0, I = 0.0, w_tau = 0.0, w_I = 0.0;
+
+    if (in_image) {
+        lp = static_cast<size_t>(lrow) * im.res_x + col;
+        const uint32_t mv = P.mask ? P.mask[lp] : 0u;
+        if (!mv) {  // (a solid-marked pixel shows the solid: line.cpp:177-179, nothing of the grid)
+            x = P.Xtab[col];
+            y = P.Ytab[global_row_of(im, lrow)];
+            ent = load_entry_head(P.entry_head + lp);
+            const float2 w = A.grad_out ? A.grad_out[lp] : make_float2(1.0f, 1.0f);
+            w_tau = w.x;
+            w_I = w.y;
+            lam_total = A.lambda[lp];
+            if (ent.count > 0 && (w_tau != 0.0 || w_I != 0.0))
+                cell = next_entry<true>(P, lp, ent, w_cur, carry, -DBL_MAX, -DBL_MAX, skipped);
+            key_taken = w_cur;
+        }
+    }
+
+    CellRegs cur;
+    if (cell >= 0) load_cell(cur, P.xrec, cell);
+
+    // wave-uniform loop (the scatter wants every lane): a lane whose ray has ended takes part with nothing to add
+    for (;;) {
+        const bool live = cell >= 0;
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        bool emit = false;
+        double da = 0.0, dq = 0.0;
+        const int here = cell;
+        if (live) {
+            // the step of adjoint_walk<2>, operation for operation: the same segments, the same T_k
+            const StepGeometry sg = step_geometry(cur, x, y);
+            ++n_step;
+            const bool has_exit = sg.w_exit < INFINITY;
+            const double dz = sg.w_exit - carry;
+            const bool contributes = dz > 0.0 && dz < INFINITY;
+            int nb = -1;
+            double carry_next = carry;
+            if (has_exit) {
+                carry_next = sg.w_exit;
+                w_cur = fmax(w_cur, sg.w_exit);
+                const uint32_t id = sg.w_out & kIdMask;
+                if (id != kNoCell) nb = static_cast<int>(id);
+            }
+            if (nb >= 0 && n_step >= P.max_steps) {
+                overflow = 1;
+                nb = -1;
+            } else if (nb < 0 && !overflow) {
+                nb = next_entry<true>(P, lp, ent, w_cur, carry_next, key_taken, has_exit ? sg.w_exit : -DBL_MAX, skipped);
+                key_taken = w_cur;
+            }
+            CellRegs nxt;
+            if (nb >= 0) load_cell(nxt, P.xrec, nb);
+
+            if (contributes) {
+                const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+                emit = true;
+                da = w_tau * (dz * dz);  // (d tau / d alpha)^2 (raw alpha, every segment)
+                if (a != 0.0) {
+                    lam = fma(a, dz, lam);
+                    const double T = exp_nonpositive(fmin(lam - lam_total, 0.0));
+                    const double E = exp_nonpositive(-a * dz);
+                    const SegmentTerms t = segment_terms(a, q, dz, E, T, I);
+                    dq = w_I * (t.dI_dq * t.dI_dq);
+                    if (a == a_raw) da = fma(w_I, t.dI_da * t.dI_da, da);  // (a clamped alpha does not move)
+                    I = t.I_next;
+                }
+            }
+            cell = nb;
+            carry = carry_next;
+            cur = nxt;
+        }
+        scatter_wave(emit, here, da, dq, A.grad_a, A.grad_q);
+    }
+
+    if (in_image) __builtin_nontemporal_store(0ll, reinterpret_cast<long long*>(P.entry_head + lp));  // cleared, as the walk leaves them
+}
+
+// g = w * t per channel, one fp32 multiply (gn_walk_a's store, for tangent_resolve's images); w nullptr: ones
+__global__ __launch_bounds__(256) void gn_weight(const float2* __restrict__ t, const float2* __restrict__ w, int64_t n_px, int n_imgs,
+                                                 float2* __restrict__ g) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n_px * n_imgs) return;
+    const float2 v = t[i];
+    const float2 wp = w ? w[i % n_px] : make_float2(1.0f, 1.0f);
+    g[i] = make_float2(__fmul_rn(wp.x, v.x), __fmul_rn(wp.y, v.y));
+}
+
+// adjoint_resolve's twin with squares (weights nullptr: ones)
+__global__ __launch_bounds__(256) void gn_diag_resolve(GridView g, ImageParams im, const int64_t* __restrict__ offs,
+                                                       AdjSegment* __restrict__ segs, const uint32_t* __restrict__ mask,
+                                                       double alpha_limit, const float2* __restrict__ weight,
+                                                       double* __restrict__ diag_a, double* __restrict__ diag_q) {
+    using namespace adj;
+    const int64_t lp = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    int n = 0;
+    AdjSegment* list = segs;
+    double w_tau = 0.0, w_I = 0.0, lam_total = 0.0;
+    if (lp < n_px && !(mask && mask[lp])) {
+        list = segs + offs[lp];
+        n = static_cast<int>(offs[lp + 1] - offs[lp]);
+        const float2 w = weight ? weight[lp] : make_float2(1.0f, 1.0f);
+        w_tau = w.x;
+        w_I = w.y;
+        if (w_tau == 0.0 && w_I == 0.0) n = 0;
+        for (int gap = n / 2; gap > 0; gap = (gap == 2) ? 1 : static_cast<int>(gap / 2.2)) {
+            for (int i = gap; i < n; ++i) {
+                const AdjSegment t = list[i];
+                int j = i;
+                while (j >= gap && list[j - gap].z_hi < t.z_hi) {
+                    list[j] = list[j - gap];
+                    j -= gap;
+                }
+                list[j] = t;
+            }
+        }
+        for (int i = n - 1; i >= 0; --i) {  // Lambda, in the order the loop below runs
+            double a = g.alpha[list[i].cell];
+            if (a > alpha_limit) a = alpha_limit;
+            if (!(a < DBL_EPSILON)) lam_total = fma(a, list[i].dz, lam_total);
+        }
+    }
+    double lam = 0.0, I = 0.0;
+    // wave-uniform loop over the steps (the scatter wants every lane)
+    for (int i = n - 1;; --i) {
+        const bool live = i >= 0;
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        int c = -1;
+        double da = 0.0, dq = 0.0;
+        if (live) {
+            c = static_cast<int>(list[i].cell);
+            const double dz = list[i].dz, q = g.q[c], a_raw = g.alpha[c];
+            double a = a_raw;
+            if (a > alpha_limit) a = alpha_limit;
+            da = w_tau * (dz * dz);
+            if (!(a < DBL_EPSILON)) {
+                lam = fma(a, dz, lam);
+                const double T = exp(fmin(lam - lam_total, 0.0));
+                const double E = exp(-a * dz);
+                const SegmentTerms t = segment_terms(a, q, dz, E, T, I);
+                dq = w_I * (t.dI_dq * t.dI_dq);
+                if (!(a_raw > alpha_limit)) da = fma(w_I, t.dI_da * t.dI_da, da);
+                I = t.I_next;
+            }
+        }
+        scatter_wave(live, c, da, dq, diag_a, diag_q);
+    }
+}
+
 // c5_update_scalars_device: the gather into device order, and c5_update_scalars' three statistics as bit-pattern maxima
 // (non-negative doubles order as their bits do; the smallest one is the largest complement).  A grid-stride loop over a
 // few hundred workgroups, reduced per workgroup: one atomic per statistic and workgroup (atomics on one address are
@@ -934,6 +1226,38 @@ void launch_adjoint_permute_batch(hipStream_t s, int kc, const double* grad, con
         hipLaunchKernelGGL(adjoint_permute_batch<4>, dim3(blocks), dim3(256), 0, s, grad, perm, n, k0, n_used, ga_out, gq_out);
     else
         hipLaunchKernelGGL(adjoint_permute_batch<8>, dim3(blocks), dim3(256), 0, s, grad, perm, n, k0, n_used, ga_out, gq_out);
+}
+
+void launch_gn_walk_a(hipStream_t s, int kc, const GnWalkParams& a) {
+    const ImageParams& im = a.w.im;
+    if (im.res_x <= 0 || im.n_local_rows <= 0) return;
+    const unsigned blocks = static_cast<unsigned>(((im.res_x + 7) / 8) * ((im.n_local_rows + 7) / 8));
+    if (kc == 4)
+        hipLaunchKernelGGL(gn_walk_a<4>, dim3(blocks), dim3(64), 0, s, a);
+    else
+        hipLaunchKernelGGL(gn_walk_a<8>, dim3(blocks), dim3(64), 0, s, a);
+}
+
+void launch_gn_diag_walk(hipStream_t s, const AdjointParams& a) {
+    const ImageParams& im = a.w.im;
+    if (im.res_x <= 0 || im.n_local_rows <= 0) return;
+    const unsigned blocks = static_cast<unsigned>(((im.res_x + 7) / 8) * ((im.n_local_rows + 7) / 8));
+    hipLaunchKernelGGL(gn_diag_walk, dim3(blocks), dim3(64), 0, s, a);
+}
+
+void launch_gn_weight(hipStream_t s, const float2* t, const float2* w, int64_t n_px, int n_imgs, float2* g) {
+    if (n_px <= 0 || n_imgs <= 0) return;
+    const unsigned blocks = static_cast<unsigned>((n_px * n_imgs + 255) / 256);
+    hipLaunchKernelGGL(gn_weight, dim3(blocks), dim3(256), 0, s, t, w, n_px, n_imgs, g);
+}
+
+void launch_gn_diag_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const int64_t* offs, void* segs,
+                            const uint32_t* mask, double alpha_limit, const float2* weight, double* diag_a, double* diag_q) {
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    if (n_px <= 0) return;
+    const unsigned blocks = static_cast<unsigned>((n_px + 255) / 256);
+    hipLaunchKernelGGL(gn_diag_resolve, dim3(blocks), dim3(256), 0, s, g, im, offs, static_cast<AdjSegment*>(segs), mask, alpha_limit,
+                       weight, diag_a, diag_q);
 }
 
 void launch_scalars_gather(hipStream_t s, const double* alpha_src, const double* q_src, const int32_t* perm, int64_t n, double* alpha,

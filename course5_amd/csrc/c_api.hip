@@ -285,6 +285,10 @@ struct c5_context {
     DeviceBuffer bat_dirs;  // [n_cells][width] {dalpha, dQ} fp64, device order (adjoint_kernels.hip: tangent_gather_batch)
     DeviceBuffer bat_grad;  // [n_cells][2 width] fp64, device order (adjoint_walk_batch)
     DeviceBuffer bat_io;    // the synchronous forms: the caller's directions or weights, and what goes back
+    // Gauss-Newton renders (c5_render_gn_product*, c5_render_gn_diagonal*): nothing of it is allocated before the first call
+    DeviceBuffer gn_g;      // [width][n_local_px] float2: pass A's w * J v, pass B's upstream images (a chunk's)
+    DeviceBuffer gn_spare;  // [width][n_cells] fp64: where the block of H v goes that the caller did not ask for
+    DeviceBuffer gn_io;     // the synchronous forms: directions, weights, and what goes back
     // c5_update_scalars_device: the three statistics of the scalars on the device, and their pinned copy
     DeviceBuffer scal_stats;
     unsigned long long* scal_host = nullptr;
@@ -1535,6 +1539,119 @@ int enqueue_adjoint_batch(c5_context* ctx, int n, const float2* grad_out, double
     return commit_derivative(ctx, "adjoint batch");
 }
 
+// The Gauss-Newton product H v = J^T W J v for n directions: one per-view setup, then per chunk of up to `width` directions
+// the gather, pass A (gn_walk_a: the tangent walk that is also the adjoint's pass 1; g = w * J v in fp32 and Lambda), the
+// batched pass 2 on g, and its permutation.  The heads stay in place from pass A to pass B and between the chunks; the
+// last pass B hands them back cleared.  On bin_sort_resolve's lists: tangent_resolve -> gn_weight -> adjoint_resolve per
+// direction.  ha_out / hq_out: either may be null (then that block goes to a spare buffer); jv_out may be null.
+int enqueue_gn_product(c5_context* ctx, int n, const double* d_alpha, const double* d_q, const float2* weight, double* ha_out,
+                       double* hq_out, float2* jv_out) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const c5::ImageParams& im = ctx->im;
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    if (v.no_cells) {  // (nothing but solids: no cell, and the images do not depend on any)
+        if (jv_out && n_px > 0) C5_HIP(ctx, hipMemsetAsync(jv_out, 0, static_cast<size_t>(n) * n_px * sizeof(float2), s));
+        return C5_OK;
+    }
+    FrameSlot& fs = ctx->slots[0];
+    const int64_t n_cells = ctx->n_cells;
+    const int32_t* const perm = ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>();
+    if (v.bin_sort) {
+        C5_HIP(ctx, ctx->tan_dir.ensure(static_cast<size_t>(n_cells) * sizeof(double2)));
+        C5_HIP(ctx, ctx->adj_grad.ensure(2 * static_cast<size_t>(n_cells) * sizeof(double)));
+        C5_HIP(ctx, ctx->gn_g.ensure(2 * static_cast<size_t>(n_px) * sizeof(float2) + 16));
+        if (!ha_out || !hq_out) C5_HIP(ctx, ctx->gn_spare.ensure(static_cast<size_t>(n_cells) * sizeof(double)));
+        double2* const dir = ctx->tan_dir.as<double2>();
+        double* const ga_dev = ctx->adj_grad.as<double>();
+        double* const gq_dev = ga_dev + n_cells;
+        float2* const g = ctx->gn_g.as<float2>();
+        for (int j = 0; j < n; ++j) {
+            float2* const t = jv_out ? jv_out + j * n_px : g + n_px;
+            c5::launch_tangent_gather(s, d_alpha ? d_alpha + j * n_cells : nullptr, d_q ? d_q + j * n_cells : nullptr, perm, n_cells, dir);
+            c5::launch_tangent_resolve(s, v.g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, dir, t);
+            c5::launch_gn_weight(s, t, weight, n_px, 1, g);
+            C5_HIP(ctx, hipMemsetAsync(ga_dev, 0, 2 * static_cast<size_t>(n_cells) * sizeof(double), s));
+            c5::launch_adjoint_resolve(s, v.g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, g, ga_dev, gq_dev);
+            c5::launch_adjoint_permute(s, ga_dev, gq_dev, perm, n_cells, ha_out ? ha_out + j * n_cells : ctx->gn_spare.as<double>(),
+                                       hq_out ? hq_out + j * n_cells : ctx->gn_spare.as<double>());
+        }
+        return commit_derivative(ctx, "gn product");
+    }
+    const int width = batch_width(ctx, n);
+    const size_t grad_bytes = static_cast<size_t>(n_cells) * 2 * width * sizeof(double);
+    const int64_t padded = ((n_px + 1023) / 1024) * 1024;
+    C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(padded) * sizeof(double)));
+    C5_HIP(ctx, ctx->bat_dirs.ensure(static_cast<size_t>(n_cells) * width * sizeof(double2)));
+    C5_HIP(ctx, ctx->bat_grad.ensure(grad_bytes));
+    C5_HIP(ctx, ctx->gn_g.ensure(static_cast<size_t>(width) * n_px * sizeof(float2) + 16));
+    if (!ha_out || !hq_out) C5_HIP(ctx, ctx->gn_spare.ensure(static_cast<size_t>(n_cells) * width * sizeof(double)));
+    c5::GnWalkParams ga{};
+    ga.w = v.w;
+    ga.dirs = ctx->bat_dirs.as<double2>();
+    ga.weight = weight;
+    ga.lambda = ctx->adj_lambda.as<double>();
+    ga.g = ctx->gn_g.as<float2>();
+    ga.image_px = n_px;
+    c5::AdjointBatchParams ab{};
+    ab.w = v.w;
+    ab.grad_out = ctx->gn_g.as<float2>();
+    ab.image_px = n_px;
+    ab.lambda = ctx->adj_lambda.as<double>();
+    ab.grad = ctx->bat_grad.as<double>();
+    for (int k0 = 0; k0 < n; k0 += width) {
+        ga.n_used = ab.n_used = std::min(width, n - k0);
+        ga.jv_out = jv_out ? jv_out + k0 * n_px : nullptr;
+        ab.keep_entries = k0 + width < n;
+        c5::launch_tangent_gather_batch(s, width, d_alpha, d_q, perm, n_cells, k0, ga.n_used, ctx->bat_dirs.as<double2>());
+        c5::launch_gn_walk_a(s, width, ga);
+        C5_HIP(ctx, hipMemsetAsync(ab.grad, 0, grad_bytes, s));
+        c5::launch_adjoint_walk_batch(s, width, ab);
+        c5::launch_adjoint_permute_batch(s, width, ab.grad, perm, n_cells, 0, ab.n_used,
+                                         ha_out ? ha_out + k0 * n_cells : ctx->gn_spare.as<double>(),
+                                         hq_out ? hq_out + k0 * n_cells : ctx->gn_spare.as<double>());
+    }
+    fs.head_clean = true;  // (the last chunk's pass B hands every head back cleared)
+    return commit_derivative(ctx, "gn product");
+}
+
+// diag(J^T W J): the adjoint's two passes with gn_diag_walk as the second (or gn_diag_resolve over bin_sort_resolve's
+// lists), then the permutation into the caller's order.  weight null: ones.
+int enqueue_gn_diagonal(c5_context* ctx, const float2* weight, double* da_out, double* dq_out) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc || v.no_cells) return rc;
+    FrameSlot& fs = ctx->slots[0];
+    hipStream_t s = ctx->stream;
+    const c5::ImageParams& im = ctx->im;
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
+    C5_HIP(ctx, ctx->adj_grad.ensure(2 * n_cells * sizeof(double)));
+    double* const da_dev = ctx->adj_grad.as<double>();
+    double* const dq_dev = da_dev + n_cells;
+    C5_HIP(ctx, hipMemsetAsync(da_dev, 0, 2 * n_cells * sizeof(double), s));
+    if (v.bin_sort) {
+        c5::launch_gn_diag_resolve(s, v.g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, weight, da_dev,
+                                   dq_dev);
+    } else {
+        const int64_t padded = ((static_cast<int64_t>(im.n_local_rows) * im.res_x + 1023) / 1024) * 1024;
+        C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(padded) * sizeof(double)));
+        c5::AdjointParams ap{};
+        ap.w = v.w;
+        ap.grad_out = weight;
+        ap.lambda = ctx->adj_lambda.as<double>();
+        ap.grad_a = da_dev;
+        ap.grad_q = dq_dev;
+        c5::launch_adjoint_walk(s, ap, 1);
+        c5::launch_gn_diag_walk(s, ap);
+        fs.head_clean = true;  // (gn_diag_walk hands every head back cleared)
+    }
+    c5::launch_adjoint_permute(s, da_dev, dq_dev, ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>(), ctx->n_cells,
+                               da_out, dq_out);
+    return commit_derivative(ctx, "gn diagonal");
+}
+
 // After the stream drained: the failure words of the last adjoint or tangent (as finish_frame treats a frame's).
 int finish_adjoint(c5_context* ctx) {
     if (!ctx->adjoint_pending) return C5_OK;
@@ -1674,7 +1791,8 @@ void c5_destroy(c5_context* ctx) {
                             &ctx->q, &ctx->bface, &ctx->xtab, &ctx->ytab, &ctx->out, &ctx->sticky,
                             &ctx->offs64, &ctx->scratch64, &ctx->segs, &ctx->adj_lambda, &ctx->adj_counters,
                             &ctx->adj_sticky, &ctx->adj_grad, &ctx->adj_perm, &ctx->adj_io, &ctx->tan_dir, &ctx->tan_io,
-                            &ctx->bat_dirs, &ctx->bat_grad, &ctx->bat_io, &ctx->scal_stats};
+                            &ctx->bat_dirs, &ctx->bat_grad, &ctx->bat_io, &ctx->gn_g, &ctx->gn_spare, &ctx->gn_io,
+                            &ctx->scal_stats};
     if (ctx->host_sticky) (void)hipHostFree(ctx->host_sticky);
     if (ctx->adj_status) (void)hipHostFree(ctx->adj_status);
     if (ctx->scal_host) (void)hipHostFree(ctx->scal_host);
@@ -2545,6 +2663,93 @@ int c5_render_adjoint_batch(c5_context* ctx, int n_imgs, const float* grad_out_h
         return C5_OK;
     }
     return fail(ctx, C5_ERR_STATE, "adjoint batch: entry buffer kept overflowing");
+}
+
+int c5_render_gn_product_device(c5_context* ctx, int n_dirs, const void* d_alpha_dev, const void* d_q_dev, const void* weight_dev,
+                                void* h_alpha_dev, void* h_q_dev, void* jv_out_dev) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (n_dirs < 1) return fail(ctx, C5_ERR_INVALID, "a batch needs at least one direction (%d)", n_dirs);
+    if (!h_alpha_dev && !h_q_dev) return fail(ctx, C5_ERR_INVALID, "null output pointers: give h_alpha, h_q or both");
+    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_gn_product while c5_render_host_async frames are outstanding");
+    return enqueue_gn_product(ctx, n_dirs, static_cast<const double*>(d_alpha_dev), static_cast<const double*>(d_q_dev),
+                              static_cast<const float2*>(weight_dev), static_cast<double*>(h_alpha_dev), static_cast<double*>(h_q_dev),
+                              static_cast<float2*>(jv_out_dev));
+}
+
+int c5_render_gn_product(c5_context* ctx, int n_dirs, const double* d_alpha_host, const double* d_q_host, const float* weight_host,
+                         double* h_alpha_host, double* h_q_host, float* jv_out_host) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (n_dirs < 1) return fail(ctx, C5_ERR_INVALID, "a batch needs at least one direction (%d)", n_dirs);
+    if (!h_alpha_host && !h_q_host) return fail(ctx, C5_ERR_INVALID, "null output pointers: give h_alpha, h_q or both");
+    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_gn_product while c5_render_host_async frames are outstanding");
+    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    const size_t w_bytes = static_cast<size_t>(ctx->im.n_local_rows) * ctx->im.res_x * 2 * sizeof(float);
+    const size_t w_room = (w_bytes + 255) / 256 * 256;
+    const size_t jv_room = (static_cast<size_t>(n_dirs) * w_bytes + 255) / 256 * 256;
+    const size_t dir_bytes = static_cast<size_t>(n_dirs) * static_cast<size_t>(ctx->n_cells) * sizeof(double);
+    C5_HIP(ctx, ctx->gn_io.ensure(w_room + jv_room + 4 * dir_bytes + 16));
+    char* const io = ctx->gn_io.as<char>();
+    float2* const w = reinterpret_cast<float2*>(io);
+    float2* const jv = reinterpret_cast<float2*>(io + w_room);
+    double* const da = reinterpret_cast<double*>(io + w_room + jv_room);
+    double* const dq = reinterpret_cast<double*>(io + w_room + jv_room + dir_bytes);
+    double* const ha = reinterpret_cast<double*>(io + w_room + jv_room + 2 * dir_bytes);
+    double* const hq = reinterpret_cast<double*>(io + w_room + jv_room + 3 * dir_bytes);
+    if (weight_host && w_bytes > 0) C5_HIP(ctx, hipMemcpyAsync(w, weight_host, w_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (d_alpha_host && dir_bytes > 0) C5_HIP(ctx, hipMemcpyAsync(da, d_alpha_host, dir_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (d_q_host && dir_bytes > 0) C5_HIP(ctx, hipMemcpyAsync(dq, d_q_host, dir_bytes, hipMemcpyHostToDevice, ctx->stream));
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        rc = enqueue_gn_product(ctx, n_dirs, d_alpha_host ? da : nullptr, d_q_host ? dq : nullptr, weight_host ? w : nullptr,
+                                h_alpha_host ? ha : nullptr, h_q_host ? hq : nullptr, jv_out_host ? jv : nullptr);
+        if (rc) return rc;
+        rc = c5_synchronize(ctx);
+        if (rc == C5_RETRY) continue;
+        if (rc) return rc;
+        if (h_alpha_host && dir_bytes > 0) C5_HIP(ctx, hipMemcpy(h_alpha_host, ha, dir_bytes, hipMemcpyDeviceToHost));
+        if (h_q_host && dir_bytes > 0) C5_HIP(ctx, hipMemcpy(h_q_host, hq, dir_bytes, hipMemcpyDeviceToHost));
+        if (jv_out_host && w_bytes > 0) C5_HIP(ctx, hipMemcpy(jv_out_host, jv, static_cast<size_t>(n_dirs) * w_bytes, hipMemcpyDeviceToHost));
+        return C5_OK;
+    }
+    return fail(ctx, C5_ERR_STATE, "gn product: entry buffer kept overflowing");
+}
+
+int c5_render_gn_diagonal_device(c5_context* ctx, const void* weight_dev, void* diag_alpha_dev, void* diag_q_dev) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (ctx->n_cells > 0 && (!diag_alpha_dev || !diag_q_dev)) return fail(ctx, C5_ERR_INVALID, "null diagonal pointer");
+    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_gn_diagonal while c5_render_host_async frames are outstanding");
+    return enqueue_gn_diagonal(ctx, static_cast<const float2*>(weight_dev), static_cast<double*>(diag_alpha_dev),
+                               static_cast<double*>(diag_q_dev));
+}
+
+int c5_render_gn_diagonal(c5_context* ctx, const float* weight_host, double* diag_alpha_host, double* diag_q_host) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (ctx->n_cells > 0 && (!diag_alpha_host || !diag_q_host)) return fail(ctx, C5_ERR_INVALID, "null diagonal pointer");
+    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_gn_diagonal while c5_render_host_async frames are outstanding");
+    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    const size_t w_bytes = static_cast<size_t>(ctx->im.n_local_rows) * ctx->im.res_x * 2 * sizeof(float);
+    const size_t w_room = (w_bytes + 255) / 256 * 256;
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
+    C5_HIP(ctx, ctx->gn_io.ensure(w_room + 2 * n_cells * sizeof(double) + 16));
+    char* const io = ctx->gn_io.as<char>();
+    double* const da = reinterpret_cast<double*>(io + w_room);
+    if (weight_host && w_bytes > 0) C5_HIP(ctx, hipMemcpyAsync(io, weight_host, w_bytes, hipMemcpyHostToDevice, ctx->stream));
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        rc = enqueue_gn_diagonal(ctx, weight_host ? reinterpret_cast<const float2*>(io) : nullptr, da, da + n_cells);
+        if (rc) return rc;
+        rc = c5_synchronize(ctx);
+        if (rc == C5_RETRY) continue;
+        if (rc) return rc;
+        if (n_cells > 0) {
+            C5_HIP(ctx, hipMemcpy(diag_alpha_host, da, n_cells * sizeof(double), hipMemcpyDeviceToHost));
+            C5_HIP(ctx, hipMemcpy(diag_q_host, da + n_cells, n_cells * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        return C5_OK;
+    }
+    return fail(ctx, C5_ERR_STATE, "gn diagonal: entry buffer kept overflowing");
 }
 
 namespace {

@@ -367,6 +367,16 @@ int main(int argc, char** argv) try {
                          {{"AbsorpCoef", &d.value0}, {"radEnLooseRate", &d.value1}, {"Contribution", &share}, {"dI_dAbsorpCoef", &d_alpha}});
         std::cout << "Cell contributions written to " << config.contribution << std::endl;
     }
+    if (!config.sensitivity.empty()) {
+        // Gauss-Newton diagonal of this frame at unit weights: how strongly the image constrains each cell's two scalars
+        // (sum over the pixels of the squared derivative; 0: the image does not see the cell)
+        std::vector<double> s_alpha, s_q;
+        base_plane.sensitivities(s_alpha, s_q);
+        const object3d_data& d = *acc_disk.get_pointer();
+        write_legacy_vtk(config.sensitivity, d.points, d.cells,
+                         {{"AbsorpCoef", &d.value0}, {"radEnLooseRate", &d.value1}, {"SensAbsorpCoef", &s_alpha}, {"SensRadEnLooseRate", &s_q}});
+        std::cout << "Cell sensitivities written to " << config.sensitivity << std::endl;
+    }
     if (config.print_stats) {
         const c5_stats st = base_plane.stats();
         std::cout << "GPU frame: " << st.ms_total << " ms (transform " << st.ms_transform << ", records " << st.ms_records

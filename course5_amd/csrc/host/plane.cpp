@@ -795,3 +795,11 @@ void plane::intensity_gradients(std::vector<double>& d_alpha, std::vector<double
     d_q.assign(_n_cells, 0.0);
     check(c5_render_adjoint(_ctx[0], weights.data(), d_alpha.data(), d_q.data()), "c5_render_adjoint");
 }
+
+void plane::sensitivities(std::vector<double>& diag_alpha, std::vector<double>& diag_q) {
+    if (_ctx.size() != 1) throw std::runtime_error("the Gauss-Newton diagonal render runs on one device");
+    if (!_flight.empty() || !_parked.empty()) throw std::runtime_error("the Gauss-Newton diagonal render wants no frame in flight");
+    diag_alpha.assign(_n_cells, 0.0);
+    diag_q.assign(_n_cells, 0.0);
+    check(c5_render_gn_diagonal(_ctx[0], nullptr, diag_alpha.data(), diag_q.data()), "c5_render_gn_diagonal");
+}

@@ -100,6 +100,9 @@ public:
     // Adjoint render (c5_render_adjoint) of the current view with the weights g_tau = 0, g_I = 1 on every pixel: d sum(I) /
     // d alpha and d sum(I) / d Q of every cell of the merged volume grid, in its order.  One device, no frame in flight.
     void intensity_gradients(std::vector<double>& d_alpha, std::vector<double>& d_q);
+    // Gauss-Newton diagonal render (c5_render_gn_diagonal) of the current view at unit weights: diag(J^T J) for alpha and
+    // for Q of every cell of the merged volume grid, in its order.  One device, no frame in flight.
+    void sensitivities(std::vector<double>& diag_alpha, std::vector<double>& diag_q);
 
     std::size_t get_x() const { return _x; }
     std::size_t get_y() const { return _y; }

@@ -1,0 +1,108 @@
+"""One Gauss-Newton step of a fit of the cell field (alpha, Q) to observed images.
+
+    delta, models = course5_amd.fit.gn_step(ctx, alpha, q, residual, fit=("q",))
+
+With J the Jacobian of the frame of `ctx` at (alpha, q), r = render(alpha, q) - target the residual image and W the
+per-pixel weights, the step minimises the quadratic model  m(d) = 1/2 d^T H d + d^T J^T W r,  H = J^T W J, by
+preconditioned conjugate gradients on
+
+    (H + damping * diag(H)) d = -J^T W r
+
+with one adjoint render for the right-hand side, one gn_diagonal (the Jacobi preconditioner and Levenberg-Marquardt's
+scaling) and one gn_product per iteration (course5_amd.autograd).  No line search and no outer loop: the caller owns
+both.  Everything is float64 on the context's GPU.
+
+A context may bring its own operators: if it has a method gn_operators(alpha, q, weight) returning an object with
+rhs(residual) -> (J^T W r)_alpha, (..)_q, diagonal() -> (diag_alpha, diag_q) and product(v_alpha, v_q) -> (h_alpha, h_q)
+(torch float64 tensors; v_alpha / v_q None: zero), gn_step uses those - a set of row shards that sums its parts, a dense
+model.
+"""
+from __future__ import annotations
+
+import torch
+
+
+class _LibraryOperators:
+    """The three operators of a capi.Context."""
+
+    def __init__(self, ctx, alpha, q, weight):
+        self.ctx, self.alpha, self.q, self.weight = ctx, alpha, q, weight
+
+    def rhs(self, residual):
+        from . import autograd
+        ctx = self.ctx
+        device = autograd._gn_enter(ctx, self.alpha, self.q, "gn_step")
+        with torch.cuda.device(device):
+            g = residual.detach().to(device=device, dtype=torch.float32)
+            if self.weight is not None:
+                g = g * autograd._gn_weight(ctx, self.weight, device)
+            g = g.contiguous()
+            ga = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
+            gq = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
+            autograd._use_torch_stream(ctx, device)
+            autograd._run(ctx, lambda: ctx.render_adjoint_device(g, ga, gq))
+        return ga, gq
+
+    def diagonal(self):
+        from . import autograd
+        return autograd.gn_diagonal(self.ctx, self.alpha, self.q, self.weight)
+
+    def product(self, v_alpha, v_q):
+        from . import autograd
+        return autograd.gn_product(self.ctx, self.alpha, self.q, v_alpha, v_q, self.weight)
+
+
+def gn_step(ctx, alpha, q, residual, weight=None, fit=("q",), damping: float = 0.0, iters: int = 10, precondition: bool = True):
+    """Up to `iters` iterations of (Jacobi-preconditioned) CG from d = 0 on (H + damping diag(H)) d = -J^T W r over the
+    fields named in `fit` ("alpha", "q" or both; the other is held fixed).  Returns ((d_alpha, d_q), models): the step
+    (None for a field not fitted) and the model value m(d_i) after every iteration done, as floats.  It stops early when
+    the residual of the linear system vanishes or a direction has no curvature."""
+    fit = tuple(fit)
+    if not fit or any(f not in ("alpha", "q") for f in fit) or len(set(fit)) != len(fit):
+        raise ValueError(f"fit must name 'alpha', 'q' or both, not {fit!r}")
+    if damping < 0.0 or iters < 1:
+        raise ValueError("damping must be >= 0 and iters >= 1")
+    ops = ctx.gn_operators(alpha, q, weight) if hasattr(ctx, "gn_operators") else _LibraryOperators(ctx, alpha, q, weight)
+    n = alpha.shape[0]
+
+    def pick(a, b):
+        return torch.cat([t for name, t in (("alpha", a), ("q", b)) if name in fit])
+
+    def split(x):
+        if len(fit) == 2:
+            return x[:n], x[n:]
+        return (x, None) if fit[0] == "alpha" else (None, x)
+
+    def H(x):
+        return pick(*ops.product(*split(x)))
+
+    g = pick(*ops.rhs(residual)).to(torch.float64)  # J^T W r
+    d = pick(*ops.diagonal()).to(torch.float64)
+    # (a cell no ray crosses: a zero row and column of H and a zero of the right-hand side; its unknown stays 0)
+    m_inv = torch.where(d > 0, 1.0 / torch.where(d > 0, d, torch.ones_like(d)), torch.zeros_like(d)) if precondition else None
+
+    x = torch.zeros_like(g)
+    hx = torch.zeros_like(g)
+    r = -g
+    z = r * m_inv if precondition else r
+    p = z.clone()
+    rz = float(r @ z)
+    models = []
+    for _ in range(iters):
+        if not rz > 0.0:
+            break
+        hp = H(p)
+        ap = hp + damping * d * p
+        curvature = float(p @ ap)
+        if not curvature > 0.0:
+            break
+        step = rz / curvature
+        x += step * p
+        hx += step * hp
+        r -= step * ap
+        models.append(float(0.5 * (x @ hx) + x @ g))
+        z = r * m_inv if precondition else r
+        rz_next = float(r @ z)
+        p = z + (rz_next / rz) * p
+        rz = rz_next
+    return split(x), models

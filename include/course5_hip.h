@@ -329,6 +329,39 @@ int c5_render_tangent_batch_device(c5_context* ctx, int n_dirs, const void* d_al
 int c5_render_adjoint_batch(c5_context* ctx, int n_imgs, const float* grad_out_host, double* grad_alpha_host, double* grad_q_host);
 int c5_render_adjoint_batch_device(c5_context* ctx, int n_imgs, const void* grad_out_dev, void* grad_alpha_dev, void* grad_q_dev);
 
+/* --- Gauss-Newton renders ---------------------------------------------------------------------------
+ * With J the Jacobian of the frame c5_render would produce now with respect to the cells' (alpha, Q) - the map of
+ * c5_render_tangent, its transpose the map of c5_render_adjoint - and W a diagonal matrix of per-pixel, per-channel
+ * weights:
+ * c5_render_gn_product: H v = J^T W J v for n_dirs directions v = (d_alpha, d_q), the normal-equation product of a
+ * Gauss-Newton / CG fit of the cell field to observed images.  d_alpha / d_q [n_dirs][n_cells] fp64 in the caller's cell
+ * order, either may be NULL (a zero direction; the matching output block is still written: the off-diagonal block's
+ * action).  weight [local_rows][res_x][2] fp32 (channel 0 weighs tau, 1 weighs I), NULL = all ones; one weight image for
+ * all directions.  h_alpha / h_q [n_dirs][n_cells] fp64, overwritten; either may be NULL when only the other field is
+ * fitted, not both.  jv_out [n_dirs][local_rows][res_x][2] fp32 or NULL: J v, bit for bit c5_render_tangent_batch's image.
+ * It is ONE call for what otherwise takes c5_render_tangent_batch, a multiply and c5_render_adjoint_batch: one per-view
+ * setup, and the tangent walk leaves the adjoint's first pass behind.  The intermediate image is fp32 on purpose: the
+ * result is that of c5_render_adjoint_batch on grad_out = weight * (fp32 image of c5_render_tangent_batch), one fp32
+ * multiply per channel, up to the order of the adjoint's atomics.  So H is symmetric positive semidefinite for weights
+ * >= 0 up to that fp32 rounding (6e-8 relative per pixel), and the results are NOT bit-reproducible from run to run, as
+ * the adjoint's.
+ * c5_render_gn_diagonal: diag(J^T W J), split as diag_alpha / diag_q [n_cells] fp64 in the caller's order, overwritten:
+ * the Jacobi preconditioner of that CG, the scaling of Levenberg-Marquardt, and a measure of how strongly the frame
+ * constrains each cell (0: no walked ray crosses it).  A ray crosses a cell in at most one segment, so it is the per-cell
+ * sum of weight * (the adjoint's per-segment term)^2, in fp64 throughout; not bit-reproducible either.
+ * n_dirs < 1 or no output: C5_ERR_INVALID.  Row ranges and row tiles, side effects, status and retries: as the batch
+ * calls' (the adjoint's counters and status words, never a frame's; a c5_render afterwards returns the bits it would
+ * have returned without them; the synchronous forms retry by themselves on C5_RETRY, the _device forms are asynchronous
+ * on the context's stream and report through the next call that waits for it).  Memory is allocated at the first call
+ * only: the batch calls' buffers, "batch_width" images, and for a NULL h_alpha or h_q 8 x "batch_width" bytes per cell.
+ * All four refuse while c5_render_host_async frames are outstanding. */
+int c5_render_gn_product(c5_context* ctx, int n_dirs, const double* d_alpha_host, const double* d_q_host,
+                         const float* weight_host, double* h_alpha_host, double* h_q_host, float* jv_out_host);
+int c5_render_gn_product_device(c5_context* ctx, int n_dirs, const void* d_alpha_dev, const void* d_q_dev,
+                                const void* weight_dev, void* h_alpha_dev, void* h_q_dev, void* jv_out_dev);
+int c5_render_gn_diagonal(c5_context* ctx, const float* weight_host, double* diag_alpha_host, double* diag_q_host);
+int c5_render_gn_diagonal_device(c5_context* ctx, const void* weight_dev, void* diag_alpha_dev, void* diag_q_dev);
+
 /* --- frames delivered to host memory, pipelined ----------------------------------------------------
  * plane::trace_rays hands back HOST pixels (plane.cpp:144-172); over PCIe Gen5 a 2400x1800 image is
  * 0.65 ms of transfer beside 0.7 ms of rendering, so the two are overlapped: c5_render_host_async renders
