@@ -30,6 +30,12 @@
 // No atomics and no pre-pass: every pixel's sum runs in the reference's order on one lane, so the tangent IS
 // bit-reproducible from run to run.
 //
+// Every walk kernel here (the batched and Gauss-Newton ones further down included) takes its rays through adj::Ray: ONE
+// definition of the walk's step, of how a ray begins and of what it leaves behind.  The kernels differ in what they
+// accumulate along the ray, and those that differ in nothing else share a body with a compile-time parameter
+// (adjoint_walk_body: gn_diag_walk is pass 2 with squares; tangent_batch_body: gn_walk_a is tangent_walk_batch plus
+// Lambda and the weighted store).  The *_resolve kernels share the reference's sort and its clamp of alpha.
+//
 // The sums are fp64 atomics, added in arrival order: the gradients are NOT bit-reproducible from run to run (the last bits
 // move).  This file is compiled with -munsafe-fp-atomics (build.py): the adds are global_atomic_add_f64, no
 // compare-and-swap loop.
@@ -37,6 +43,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <type_traits>
 
 #include "adjoint.hpp"
 #include "device_types.hpp"
@@ -163,122 +170,176 @@ __device__ __forceinline__ void scatter_wave(bool pending, int cell, double ga, 
     }
 }
 
-}  // namespace adj
+// One ray of a walk kernel: one wavefront per 8x8 pixel tile, one lane per pixel (the walk's default tiling: neighbouring
+// rays share cells, which is what the per-wave sums before the atomics live on).  Every walk kernel of this file takes its
+// steps through this struct, and the step is that of walk_composite<*, 0> (walk_kernels.hip) operation for operation: the
+// same segments, to the bit.  What a kernel accumulates along the ray stays in its own body.
+//
+// Three things a step needs are deliberately NOT members but locals of the kernel: the cell's record `cur`, the next
+// one's `nxt` with the step's results (nb, dz, carry_next), and the pixel's EntryHead, handed over by value.  As members
+// they end up on the stack, and next_entry's chain hop then reads through a pointer that is the stack or global memory
+// (walk_common.hpp: next_entry).  The compiler's register count is sensitive to the shape of these helpers: check
+// -Rpass-analysis=kernel-resource-usage after touching them (gn_walk_a<8> sits on its occupancy step, 168 VGPRs).
+struct Ray {
+    int lane = static_cast<int>(threadIdx.x);
+    bool in_image = false;
+    size_t lp = 0;  // the pixel among the context's rows
+    double x = 0.0, y = 0.0;
+    int cell = -1;  // the cell the ray is in; < 0: it has ended (or never began)
+    double w_cur = -DBL_MAX, carry = 0.0, key_taken = -DBL_MAX;
+    unsigned n_step = 0, overflow = 0;
+    bool skipped = false;
+};
 
-// One wavefront per 8x8 pixel tile, one lane per pixel (the walk's default tiling: neighbouring rays share cells, which is
-// what the per-wave sum before the atomics lives on).
-template <int PASS>
-__global__ __launch_bounds__(64) void adjoint_walk(AdjointParams A) {
-    using namespace adj;
-    const WalkParams& P = A.w;
+// The lane's pixel, its entry head and the ray's first cell.  Where there is a ray - the pixel is in the image and not
+// solid-marked (such a pixel shows the solid: line.cpp:177-179, nothing of the grid) - the kernel's `wanted` loads what
+// else it needs of the pixel (r.lp) and says whether the ray is to be walked at all.
+template <class Wanted>
+__device__ __forceinline__ EntryHead ray_begin(Ray& r, const WalkParams& P, Wanted wanted) {
     const ImageParams& im = P.im;
     const int tiles_x = (im.res_x + 7) / 8;
     const int ty = static_cast<int>(blockIdx.x) / tiles_x, tx = static_cast<int>(blockIdx.x) - ty * tiles_x;
-    const int lane = static_cast<int>(threadIdx.x);
-    const int col = tx * 8 + (lane & 7), lrow = ty * 8 + (lane >> 3);
-    const bool in_image = (col < im.res_x) && (lrow < im.n_local_rows);
-
-    unsigned n_step = 0, overflow = 0;
-    bool skipped = false;
-    double key_taken = -DBL_MAX;
-    double x = 0.0, y = 0.0, w_cur = -DBL_MAX, carry = 0.0;
+    const int col = tx * 8 + (r.lane & 7), lrow = ty * 8 + (r.lane >> 3);
+    r.in_image = (col < im.res_x) && (lrow < im.n_local_rows);
     EntryHead ent{0, 0};
-    int cell = -1;
-    size_t lp = 0;
-    double lam = 0.0;                                  // Lambda_k so far
-    double lam_total = 0.0, I = 0.0, g_tau = 0.0, g_I = 0.0;  // pass 2
-
-    if (in_image) {
-        lp = static_cast<size_t>(lrow) * im.res_x + col;
-        const uint32_t mv = P.mask ? P.mask[lp] : 0u;
-        if (!mv) {  // (a solid-marked pixel shows the solid: line.cpp:177-179, nothing of the grid)
-            x = P.Xtab[col];
-            y = P.Ytab[global_row_of(im, lrow)];
-            ent = load_entry_head(P.entry_head + lp);
-            if (PASS == 2) {
-                const float2 g = A.grad_out[lp];
-                g_tau = g.x;
-                g_I = g.y;
-                lam_total = A.lambda[lp];
-            }
-            if (ent.count > 0 && (PASS == 1 || g_tau != 0.0 || g_I != 0.0))
-                cell = next_entry<true>(P, lp, ent, w_cur, carry, -DBL_MAX, -DBL_MAX, skipped);
-            key_taken = w_cur;
+    if (r.in_image) {
+        r.lp = static_cast<size_t>(lrow) * im.res_x + col;
+        const uint32_t mv = P.mask ? P.mask[r.lp] : 0u;
+        if (!mv) {
+            r.x = P.Xtab[col];
+            r.y = P.Ytab[global_row_of(im, lrow)];
+            ent = load_entry_head(P.entry_head + r.lp);
+            if (wanted() && ent.count > 0) r.cell = next_entry<true>(P, r.lp, ent, r.w_cur, r.carry, -DBL_MAX, -DBL_MAX, r.skipped);
+            r.key_taken = r.w_cur;
         }
     }
+    return ent;
+}
+__device__ __forceinline__ EntryHead ray_begin(Ray& r, const WalkParams& P) {
+    return ray_begin(r, P, [] { return true; });
+}
+
+// One step up to the next cell's id (or -1): the exit, the step bound, the re-entry.  dz: the chord through the cell the
+// ray is in.  The kernel then issues the next record's load (load_cell(nxt, P.xrec, nb)) BEFORE the segment's arithmetic
+// and ends the step with ray_advance and cur = nxt.
+__device__ __forceinline__ int ray_step(Ray& r, const WalkParams& P, EntryHead ent, const CellRegs& cur, double& dz, double& carry_next) {
+    const StepGeometry sg = step_geometry(cur, r.x, r.y);
+    ++r.n_step;
+    const bool has_exit = sg.w_exit < INFINITY;
+    dz = sg.w_exit - r.carry;
+    int nb = -1;
+    carry_next = r.carry;
+    if (has_exit) {
+        carry_next = sg.w_exit;
+        r.w_cur = fmax(r.w_cur, sg.w_exit);
+        const uint32_t id = sg.w_out & kIdMask;
+        if (id != kNoCell) nb = static_cast<int>(id);
+    }
+    if (nb >= 0 && r.n_step >= P.max_steps) {
+        r.overflow = 1;
+        nb = -1;
+    } else if (nb < 0 && !r.overflow) {
+        nb = next_entry<true>(P, r.lp, ent, r.w_cur, carry_next, r.key_taken, has_exit ? sg.w_exit : -DBL_MAX, r.skipped);
+        r.key_taken = r.w_cur;
+    }
+    return nb;
+}
+
+// a chord that is a segment of the pixel's sum
+__device__ __forceinline__ bool is_segment(double dz) { return dz > 0.0 && dz < INFINITY; }
+
+__device__ __forceinline__ void ray_advance(Ray& r, int nb, double carry_next) {
+    r.cell = nb;
+    r.carry = carry_next;
+}
+
+// the pixel's entry head cleared, as the walk leaves them (the last kernel over a view's entry lists)
+__device__ __forceinline__ void ray_clear_head(const Ray& r, const WalkParams& P) {
+    if (r.in_image) __builtin_nontemporal_store(0ll, reinterpret_cast<long long*>(P.entry_head + r.lp));
+}
+
+// rays over the step bound and rays that skipped an entry, counted once per view (the first kernel over its entry lists)
+__device__ __forceinline__ void ray_count(const Ray& r, const WalkParams& P) {
+    const unsigned s_ovf = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(r.overflow != 0u)));
+    const unsigned s_skip = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(r.skipped)));
+    if (r.lane == 0) {
+        if (s_ovf) atomicAdd(&P.counters->walk_overflow, s_ovf);
+        if (s_skip) atomicAdd(&P.counters->overlap_rays, s_skip);
+    }
+}
+
+// Pass 1 (Lambda per pixel) and pass 2 (the scatter) of the adjoint; SQUARED: pass 2 with the segment's terms squared
+// and A.grad_out the weights or nullptr for ones (gn_diag_walk).
+template <int PASS, bool SQUARED>
+__device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A) {
+    const WalkParams& P = A.w;
+    Ray r;
+    double lam = 0.0;                                         // Lambda_k so far
+    double lam_total = 0.0, I = 0.0, g_tau = 0.0, g_I = 0.0;  // pass 2
+
+    const EntryHead ent = ray_begin(r, P, [&] {
+        if (PASS == 1) return true;
+        const float2 g = (SQUARED && !A.grad_out) ? make_float2(1.0f, 1.0f) : A.grad_out[r.lp];
+        g_tau = g.x;
+        g_I = g.y;
+        lam_total = A.lambda[r.lp];
+        return g_tau != 0.0 || g_I != 0.0;
+    });
 
     CellRegs cur;
-    if (cell >= 0) load_cell(cur, P.xrec, cell);
+    if (r.cell >= 0) load_cell(cur, P.xrec, r.cell);
 
     // wave-uniform loop (the scatter wants every lane): a lane whose ray has ended takes part with nothing to add
     for (;;) {
-        const bool live = cell >= 0;
+        const bool live = r.cell >= 0;
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         bool emit = false;
         double ga = 0.0, gq = 0.0;
-        const int here = cell;
+        const int here = r.cell;
         if (live) {
-            // the step of walk_composite<*, 0> (walk_kernels.hip), operation for operation: the same segments
-            const StepGeometry sg = step_geometry(cur, x, y);
-            ++n_step;
-            const bool has_exit = sg.w_exit < INFINITY;
-            const double dz = sg.w_exit - carry;
-            const bool contributes = dz > 0.0 && dz < INFINITY;
-            int nb = -1;
-            double carry_next = carry;
-            if (has_exit) {
-                carry_next = sg.w_exit;
-                w_cur = fmax(w_cur, sg.w_exit);
-                const uint32_t id = sg.w_out & kIdMask;
-                if (id != kNoCell) nb = static_cast<int>(id);
-            }
-            if (nb >= 0 && n_step >= P.max_steps) {
-                overflow = 1;
-                nb = -1;
-            } else if (nb < 0 && !overflow) {
-                nb = next_entry<true>(P, lp, ent, w_cur, carry_next, key_taken, has_exit ? sg.w_exit : -DBL_MAX, skipped);
-                key_taken = w_cur;
-            }
+            double dz, carry_next;
+            const int nb = ray_step(r, P, ent, cur, dz, carry_next);
             CellRegs nxt;
             if (nb >= 0) load_cell(nxt, P.xrec, nb);
 
-            if (contributes) {
+            if (is_segment(dz)) {
                 const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
                 if (PASS == 1) {
                     if (a != 0.0) lam = fma(a, dz, lam);
                 } else {
                     emit = true;
-                    ga = g_tau * dz;  // d tau / d alpha (line.cpp:189: raw alpha)
+                    ga = g_tau * (SQUARED ? dz * dz : dz);  // d tau / d alpha (line.cpp:189: raw alpha, every segment)
                     if (a != 0.0) {
                         lam = fma(a, dz, lam);  // (as in pass 1: Lambda_n == Lambda bit for bit, Lambda - Lambda_k >= 0)
                         const double T = exp_nonpositive(fmin(lam - lam_total, 0.0));
                         const double E = exp_nonpositive(-a * dz);
                         const SegmentTerms t = segment_terms(a, q, dz, E, T, I);
-                        gq = g_I * t.dI_dq;
-                        if (a == a_raw) ga = fma(g_I, t.dI_da, ga);  // (a clamped alpha does not move: line.cpp:216)
+                        gq = g_I * (SQUARED ? t.dI_dq * t.dI_dq : t.dI_dq);
+                        // (a clamped alpha does not move: line.cpp:216)
+                        if (a == a_raw) ga = fma(g_I, SQUARED ? t.dI_da * t.dI_da : t.dI_da, ga);
                         I = t.I_next;
                     }
                 }
             }
-            cell = nb;
-            carry = carry_next;
+            ray_advance(r, nb, carry_next);
             cur = nxt;
         }
         if (PASS == 2) scatter_wave(emit, here, ga, gq, A.grad_a, A.grad_q);
     }
 
-    if (in_image) {
-        if (PASS == 1) A.lambda[lp] = lam;
-        else __builtin_nontemporal_store(0ll, reinterpret_cast<long long*>(P.entry_head + lp));  // cleared, as the walk leaves them
-    }
     if (PASS == 1) {
-        const unsigned s_ovf = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(overflow != 0u)));
-        const unsigned s_skip = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(skipped)));
-        if (lane == 0) {
-            if (s_ovf) atomicAdd(&P.counters->walk_overflow, s_ovf);
-            if (s_skip) atomicAdd(&P.counters->overlap_rays, s_skip);
-        }
+        if (r.in_image) A.lambda[r.lp] = lam;
+        ray_count(r, P);
+    } else {
+        ray_clear_head(r, P);
     }
+}
+
+}  // namespace adj
+
+template <int PASS>
+__global__ __launch_bounds__(64) void adjoint_walk(AdjointParams A) {
+    adj::adjoint_walk_body<PASS, false>(A);
 }
 
 // bin_sort_resolve's segments (exact_kernels.hip: Segment; c_api.hip checks the size)
@@ -290,13 +351,44 @@ struct alignas(8) AdjSegment {
 static_assert(sizeof(AdjSegment) == 24, "AdjSegment mirrors exact_kernels.hip's Segment");
 size_t adjoint_segment_bytes() { return sizeof(AdjSegment); }
 
-// resolve_pixels (exact_kernels.hip) differentiated: its list sorted by descending z_hi (line.cpp:138, the same Shell sort),
-// the recurrence run from the back (i = n - 1 ... 0: k = n - i).
-__global__ __launch_bounds__(256) void adjoint_resolve(GridView g, ImageParams im, const int64_t* __restrict__ offs,
-                                                       AdjSegment* __restrict__ segs, const uint32_t* __restrict__ mask,
-                                                       double alpha_limit, const float2* __restrict__ grad_out,
-                                                       double* __restrict__ grad_a, double* __restrict__ grad_q) {
-    using namespace adj;
+namespace adj {
+
+// The reference's Shell sort of a pixel's list by descending z_hi (line.cpp:138), as resolve_pixels (exact_kernels.hip)
+// runs it.
+__device__ __forceinline__ void sort_segments(AdjSegment* list, int n) {
+    for (int gap = n / 2; gap > 0; gap = (gap == 2) ? 1 : static_cast<int>(gap / 2.2)) {
+        for (int i = gap; i < n; ++i) {
+            const AdjSegment t = list[i];
+            int j = i;
+            while (j >= gap && list[j - gap].z_hi < t.z_hi) {
+                list[j] = list[j - gap];
+                j -= gap;
+            }
+            list[j] = t;
+        }
+    }
+}
+
+// a = min(alpha, limit), and whether a segment of such a cell takes part in I (line.cpp:204-224)
+struct ClampedAlpha {
+    double a;
+    bool active, clamped;
+};
+__device__ __forceinline__ ClampedAlpha clamp_alpha(double a_raw, double alpha_limit) {
+    ClampedAlpha c;
+    c.clamped = a_raw > alpha_limit;
+    c.a = c.clamped ? alpha_limit : a_raw;
+    c.active = !(c.a < DBL_EPSILON);
+    return c;
+}
+
+// resolve_pixels (exact_kernels.hip) differentiated: its list sorted, the recurrence run from the back (i = n - 1 ... 0:
+// k = n - i).  SQUARED: the segment's terms squared, `weights` nullptr for ones (gn_diag_resolve).
+template <bool SQUARED>
+__device__ __forceinline__ void adjoint_resolve_body(const GridView& g, const ImageParams& im, const int64_t* __restrict__ offs,
+                                                     AdjSegment* __restrict__ segs, const uint32_t* __restrict__ mask,
+                                                     double alpha_limit, const float2* __restrict__ weights,
+                                                     double* __restrict__ grad_a, double* __restrict__ grad_q) {
     const int64_t lp = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
     const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
     int n = 0;
@@ -305,25 +397,14 @@ __global__ __launch_bounds__(256) void adjoint_resolve(GridView g, ImageParams i
     if (lp < n_px && !(mask && mask[lp])) {
         list = segs + offs[lp];
         n = static_cast<int>(offs[lp + 1] - offs[lp]);
-        const float2 gw = grad_out[lp];
+        const float2 gw = (SQUARED && !weights) ? make_float2(1.0f, 1.0f) : weights[lp];
         g_tau = gw.x;
         g_I = gw.y;
         if (g_tau == 0.0 && g_I == 0.0) n = 0;
-        for (int gap = n / 2; gap > 0; gap = (gap == 2) ? 1 : static_cast<int>(gap / 2.2)) {
-            for (int i = gap; i < n; ++i) {
-                const AdjSegment t = list[i];
-                int j = i;
-                while (j >= gap && list[j - gap].z_hi < t.z_hi) {
-                    list[j] = list[j - gap];
-                    j -= gap;
-                }
-                list[j] = t;
-            }
-        }
-        for (int i = n - 1; i >= 0; --i) {  // Lambda, in the order pass 2 runs
-            double a = g.alpha[list[i].cell];
-            if (a > alpha_limit) a = alpha_limit;
-            if (!(a < DBL_EPSILON)) lam_total = fma(a, list[i].dz, lam_total);
+        sort_segments(list, n);
+        for (int i = n - 1; i >= 0; --i) {  // Lambda, in the order the loop below runs
+            const ClampedAlpha c = clamp_alpha(g.alpha[list[i].cell], alpha_limit);
+            if (c.active) lam_total = fma(c.a, list[i].dz, lam_total);
         }
     }
     double lam = 0.0, I = 0.0;
@@ -335,22 +416,31 @@ __global__ __launch_bounds__(256) void adjoint_resolve(GridView g, ImageParams i
         double ga = 0.0, gq = 0.0;
         if (live) {
             c = static_cast<int>(list[i].cell);
-            const double dz = list[i].dz, q = g.q[c], a_raw = g.alpha[c];
-            double a = a_raw;
-            if (a > alpha_limit) a = alpha_limit;
-            ga = g_tau * dz;
-            if (!(a < DBL_EPSILON)) {
+            const double dz = list[i].dz, q = g.q[c];
+            const ClampedAlpha ca = clamp_alpha(g.alpha[c], alpha_limit);
+            const double a = ca.a;
+            ga = g_tau * (SQUARED ? dz * dz : dz);
+            if (ca.active) {
                 lam = fma(a, dz, lam);
                 const double T = exp(fmin(lam - lam_total, 0.0));
                 const double E = exp(-a * dz);
                 const SegmentTerms t = segment_terms(a, q, dz, E, T, I);
-                gq = g_I * t.dI_dq;
-                if (!(a_raw > alpha_limit)) ga = fma(g_I, t.dI_da, ga);
+                gq = g_I * (SQUARED ? t.dI_dq * t.dI_dq : t.dI_dq);
+                if (!ca.clamped) ga = fma(g_I, SQUARED ? t.dI_da * t.dI_da : t.dI_da, ga);
                 I = t.I_next;
             }
         }
         scatter_wave(live, c, ga, gq, grad_a, grad_q);
     }
+}
+
+}  // namespace adj
+
+__global__ __launch_bounds__(256) void adjoint_resolve(GridView g, ImageParams im, const int64_t* __restrict__ offs,
+                                                       AdjSegment* __restrict__ segs, const uint32_t* __restrict__ mask,
+                                                       double alpha_limit, const float2* __restrict__ grad_out,
+                                                       double* __restrict__ grad_a, double* __restrict__ grad_q) {
+    adj::adjoint_resolve_body<false>(g, im, offs, segs, mask, alpha_limit, grad_out, grad_a, grad_q);
 }
 
 __global__ __launch_bounds__(256) void adjoint_permute(const double* __restrict__ ga_dev, const double* __restrict__ gq_dev,
@@ -373,69 +463,27 @@ __device__ __forceinline__ void tangent_step(double a, bool clamped, double q, d
     I = t.I_next;
 }
 
-// One wavefront per 8x8 pixel tile, one lane per pixel, as adjoint_walk; nothing is shared between the lanes, so a lane
-// leaves the loop when its ray ends.
+// Nothing is shared between the lanes, so a lane leaves the loop when its ray ends.  The cell's direction is loaded
+// beside the next record.
 __global__ __launch_bounds__(64) void tangent_walk(TangentParams A) {
     using namespace adj;
     const WalkParams& P = A.w;
-    const ImageParams& im = P.im;
     const D2* __restrict__ dir = reinterpret_cast<const D2*>(A.dir);
-    const int tiles_x = (im.res_x + 7) / 8;
-    const int ty = static_cast<int>(blockIdx.x) / tiles_x, tx = static_cast<int>(blockIdx.x) - ty * tiles_x;
-    const int lane = static_cast<int>(threadIdx.x);
-    const int col = tx * 8 + (lane & 7), lrow = ty * 8 + (lane >> 3);
-    const bool in_image = (col < im.res_x) && (lrow < im.n_local_rows);
-
-    unsigned n_step = 0, overflow = 0;
-    bool skipped = false;
-    double key_taken = -DBL_MAX;
-    double x = 0.0, y = 0.0, w_cur = -DBL_MAX, carry = 0.0;
-    EntryHead ent{0, 0};
-    int cell = -1;
-    size_t lp = 0;
+    Ray r;
     double I = 0.0, I_dot = 0.0, tau_dot = 0.0;
 
-    if (in_image) {
-        lp = static_cast<size_t>(lrow) * im.res_x + col;
-        const uint32_t mv = P.mask ? P.mask[lp] : 0u;
-        if (!mv) {  // (a solid-marked pixel shows the solid: line.cpp:177-179, nothing of the grid)
-            x = P.Xtab[col];
-            y = P.Ytab[global_row_of(im, lrow)];
-            ent = load_entry_head(P.entry_head + lp);
-            if (ent.count > 0) cell = next_entry<true>(P, lp, ent, w_cur, carry, -DBL_MAX, -DBL_MAX, skipped);
-            key_taken = w_cur;
-        }
-    }
+    const EntryHead ent = ray_begin(r, P);
 
     CellRegs cur;
     D2 d_cur{0.0, 0.0};
-    if (cell >= 0) {
-        load_cell(cur, P.xrec, cell);
-        d_cur = dir[cell];
+    if (r.cell >= 0) {
+        load_cell(cur, P.xrec, r.cell);
+        d_cur = dir[r.cell];
     }
 
-    while (cell >= 0) {
-        // the step of walk_composite<*, 0> (walk_kernels.hip) as adjoint_walk has it: the same segments
-        const StepGeometry sg = step_geometry(cur, x, y);
-        ++n_step;
-        const bool has_exit = sg.w_exit < INFINITY;
-        const double dz = sg.w_exit - carry;
-        const bool contributes = dz > 0.0 && dz < INFINITY;
-        int nb = -1;
-        double carry_next = carry;
-        if (has_exit) {
-            carry_next = sg.w_exit;
-            w_cur = fmax(w_cur, sg.w_exit);
-            const uint32_t id = sg.w_out & kIdMask;
-            if (id != kNoCell) nb = static_cast<int>(id);
-        }
-        if (nb >= 0 && n_step >= P.max_steps) {
-            overflow = 1;
-            nb = -1;
-        } else if (nb < 0 && !overflow) {
-            nb = next_entry<true>(P, lp, ent, w_cur, carry_next, key_taken, has_exit ? sg.w_exit : -DBL_MAX, skipped);
-            key_taken = w_cur;
-        }
+    while (r.cell >= 0) {
+        double dz, carry_next;
+        const int nb = ray_step(r, P, ent, cur, dz, carry_next);
         CellRegs nxt;
         D2 d_nxt{0.0, 0.0};
         if (nb >= 0) {
@@ -443,27 +491,19 @@ __global__ __launch_bounds__(64) void tangent_walk(TangentParams A) {
             d_nxt = dir[nb];
         }
 
-        if (contributes) {
+        if (is_segment(dz)) {
             const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
             tau_dot = fma(dz, d_cur.a, tau_dot);  // d tau / d alpha (line.cpp:189: raw alpha)
             if (a != 0.0) tangent_step(a, a != a_raw, q, dz, exp_nonpositive(-a * dz), d_cur.a, d_cur.b, I, I_dot);
         }
-        cell = nb;
-        carry = carry_next;
+        ray_advance(r, nb, carry_next);
         cur = nxt;
         d_cur = d_nxt;
     }
 
-    if (in_image) {
-        A.out[lp] = make_float2(static_cast<float>(tau_dot), static_cast<float>(I_dot));
-        __builtin_nontemporal_store(0ll, reinterpret_cast<long long*>(P.entry_head + lp));  // cleared, as the walk leaves them
-    }
-    const unsigned s_ovf = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(overflow != 0u)));
-    const unsigned s_skip = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(skipped)));
-    if (lane == 0) {
-        if (s_ovf) atomicAdd(&P.counters->walk_overflow, s_ovf);
-        if (s_skip) atomicAdd(&P.counters->overlap_rays, s_skip);
-    }
+    if (r.in_image) A.out[r.lp] = make_float2(static_cast<float>(tau_dot), static_cast<float>(I_dot));
+    ray_clear_head(r, P);
+    ray_count(r, P);
 }
 
 // adjoint_resolve's twin: the same sort, the same back-to-front order, the tangent carried along.
@@ -471,6 +511,7 @@ __global__ __launch_bounds__(256) void tangent_resolve(GridView g, ImageParams i
                                                        AdjSegment* __restrict__ segs, const uint32_t* __restrict__ mask,
                                                        double alpha_limit, const double2* __restrict__ dir_v,
                                                        float2* __restrict__ out) {
+    using namespace adj;
     const int64_t lp = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
     const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
     if (lp >= n_px) return;
@@ -479,25 +520,14 @@ __global__ __launch_bounds__(256) void tangent_resolve(GridView g, ImageParams i
     if (!(mask && mask[lp])) {
         AdjSegment* const list = segs + offs[lp];
         const int n = static_cast<int>(offs[lp + 1] - offs[lp]);
-        for (int gap = n / 2; gap > 0; gap = (gap == 2) ? 1 : static_cast<int>(gap / 2.2)) {
-            for (int i = gap; i < n; ++i) {
-                const AdjSegment t = list[i];
-                int j = i;
-                while (j >= gap && list[j - gap].z_hi < t.z_hi) {
-                    list[j] = list[j - gap];
-                    j -= gap;
-                }
-                list[j] = t;
-            }
-        }
+        sort_segments(list, n);
         for (int i = n - 1; i >= 0; --i) {
             const int c = static_cast<int>(list[i].cell);
-            const double dz = list[i].dz, q = g.q[c], a_raw = g.alpha[c];
+            const double dz = list[i].dz, q = g.q[c];
+            const ClampedAlpha ca = clamp_alpha(g.alpha[c], alpha_limit);
             const D2 d = dir[c];
-            double a = a_raw;
-            if (a > alpha_limit) a = alpha_limit;
             tau_dot = fma(dz, d.a, tau_dot);
-            if (!(a < DBL_EPSILON)) tangent_step(a, a_raw > alpha_limit, q, dz, exp(-a * dz), d.a, d.b, I, I_dot);
+            if (ca.active) tangent_step(ca.a, ca.clamped, q, dz, exp(-ca.a * dz), d.a, d.b, I, I_dot);
         }
     }
     out[lp] = make_float2(static_cast<float>(tau_dot), static_cast<float>(I_dot));
@@ -540,80 +570,41 @@ __global__ __launch_bounds__(256) void tangent_gather_batch(const double* __rest
     reinterpret_cast<D2*>(dirs)[t] = d;
 }
 
-// tangent_walk for KC directions: one wavefront per 8x8 pixel tile, one lane per pixel.  The cell's KC direction pairs are
-// loaded at the top of its step (one 16 * KC-byte stretch) and consumed at its end, behind the geometry and the next
-// record's loads.
-template <int KC>
-__global__ __launch_bounds__(64) void tangent_walk_batch(TangentBatchParams A) {
+// tangent_walk for KC directions.  The cell's KC direction pairs are loaded at the top of its step (one 16 * KC-byte
+// stretch) and consumed at its end, behind the geometry and the next record's loads.  Params: TangentBatchParams, or
+// GnWalkParams for the walk that is also adjoint_walk<1> (gn_walk_a below).
+template <int KC, class Params>
+__device__ __forceinline__ void tangent_batch_body(const Params& A) {
     using namespace adj;
+    constexpr bool kGn = std::is_same<Params, GnWalkParams>::value;
     const WalkParams& P = A.w;
-    const ImageParams& im = P.im;
     const D2* __restrict__ dirs = reinterpret_cast<const D2*>(A.dirs);
-    const int tiles_x = (im.res_x + 7) / 8;
-    const int ty = static_cast<int>(blockIdx.x) / tiles_x, tx = static_cast<int>(blockIdx.x) - ty * tiles_x;
-    const int lane = static_cast<int>(threadIdx.x);
-    const int col = tx * 8 + (lane & 7), lrow = ty * 8 + (lane >> 3);
-    const bool in_image = (col < im.res_x) && (lrow < im.n_local_rows);
-
-    unsigned n_step = 0, overflow = 0;
-    bool skipped = false;
-    double key_taken = -DBL_MAX;
-    double x = 0.0, y = 0.0, w_cur = -DBL_MAX, carry = 0.0;
-    EntryHead ent{0, 0};
-    int cell = -1;
-    size_t lp = 0;
+    Ray r;
+    double lam = 0.0;  // (kGn) Lambda, summed as adjoint_walk<1> sums it
     double I = 0.0, I_dot[KC], tau_dot[KC];
 #pragma unroll
     for (int j = 0; j < KC; ++j) I_dot[j] = tau_dot[j] = 0.0;
 
-    if (in_image) {
-        lp = static_cast<size_t>(lrow) * im.res_x + col;
-        const uint32_t mv = P.mask ? P.mask[lp] : 0u;
-        if (!mv) {  // (a solid-marked pixel shows the solid: line.cpp:177-179, nothing of the grid)
-            x = P.Xtab[col];
-            y = P.Ytab[global_row_of(im, lrow)];
-            ent = load_entry_head(P.entry_head + lp);
-            if (ent.count > 0) cell = next_entry<true>(P, lp, ent, w_cur, carry, -DBL_MAX, -DBL_MAX, skipped);
-            key_taken = w_cur;
-        }
-    }
+    const EntryHead ent = ray_begin(r, P);
 
     CellRegs cur;
-    if (cell >= 0) load_cell(cur, P.xrec, cell);
+    if (r.cell >= 0) load_cell(cur, P.xrec, r.cell);
 
-    while (cell >= 0) {
+    while (r.cell >= 0) {
         D2 d[KC];
 #pragma unroll
-        for (int j = 0; j < KC; ++j) d[j] = dirs[static_cast<size_t>(cell) * KC + j];
-        // the step of tangent_walk, operation for operation
-        const StepGeometry sg = step_geometry(cur, x, y);
-        ++n_step;
-        const bool has_exit = sg.w_exit < INFINITY;
-        const double dz = sg.w_exit - carry;
-        const bool contributes = dz > 0.0 && dz < INFINITY;
-        int nb = -1;
-        double carry_next = carry;
-        if (has_exit) {
-            carry_next = sg.w_exit;
-            w_cur = fmax(w_cur, sg.w_exit);
-            const uint32_t id = sg.w_out & kIdMask;
-            if (id != kNoCell) nb = static_cast<int>(id);
-        }
-        if (nb >= 0 && n_step >= P.max_steps) {
-            overflow = 1;
-            nb = -1;
-        } else if (nb < 0 && !overflow) {
-            nb = next_entry<true>(P, lp, ent, w_cur, carry_next, key_taken, has_exit ? sg.w_exit : -DBL_MAX, skipped);
-            key_taken = w_cur;
-        }
+        for (int j = 0; j < KC; ++j) d[j] = dirs[static_cast<size_t>(r.cell) * KC + j];
+        double dz, carry_next;
+        const int nb = ray_step(r, P, ent, cur, dz, carry_next);
         CellRegs nxt;
         if (nb >= 0) load_cell(nxt, P.xrec, nb);
 
-        if (contributes) {
+        if (is_segment(dz)) {
             const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
 #pragma unroll
             for (int j = 0; j < KC; ++j) tau_dot[j] = fma(dz, d[j].a, tau_dot[j]);  // d tau / d alpha (raw alpha)
             if (a != 0.0) {
+                if (kGn) lam = fma(a, dz, lam);  // (adjoint_walk<1>: pass B's running Lambda_k ends on this to the bit)
                 // tangent_step, its direction-free part once: segment_terms at T = 1, E
                 const double E = exp_nonpositive(-a * dz);
                 const SegmentTerms t = segment_terms(a, q, dz, E, 1.0, I);
@@ -627,24 +618,38 @@ __global__ __launch_bounds__(64) void tangent_walk_batch(TangentBatchParams A) {
                 I = t.I_next;
             }
         }
-        cell = nb;
-        carry = carry_next;
+        ray_advance(r, nb, carry_next);
         cur = nxt;
     }
 
-    if (in_image) {
+    if constexpr (kGn) {
+        if (r.in_image) {
+            A.lambda[r.lp] = lam;
+            const float2 w = A.weight ? A.weight[r.lp] : make_float2(1.0f, 1.0f);  // (loaded here, not held across the loop)
 #pragma unroll
-        for (int j = 0; j < KC; ++j)
-            if (j < A.n_used)
-                A.out[static_cast<size_t>(j) * A.image_px + lp] = make_float2(static_cast<float>(tau_dot[j]), static_cast<float>(I_dot[j]));
-        if (!A.keep_entries) __builtin_nontemporal_store(0ll, reinterpret_cast<long long*>(P.entry_head + lp));
+            for (int j = 0; j < KC; ++j)
+                if (j < A.n_used) {
+                    const float2 t = make_float2(static_cast<float>(tau_dot[j]), static_cast<float>(I_dot[j]));
+                    if (A.jv_out) A.jv_out[static_cast<size_t>(j) * A.image_px + r.lp] = t;
+                    A.g[static_cast<size_t>(j) * A.image_px + r.lp] = make_float2(__fmul_rn(w.x, t.x), __fmul_rn(w.y, t.y));
+                }
+            // (the entry heads stay in place for pass B)
+        }
+    } else {
+        if (r.in_image) {
+#pragma unroll
+            for (int j = 0; j < KC; ++j)
+                if (j < A.n_used)
+                    A.out[static_cast<size_t>(j) * A.image_px + r.lp] = make_float2(static_cast<float>(tau_dot[j]), static_cast<float>(I_dot[j]));
+        }
+        if (!A.keep_entries) ray_clear_head(r, P);
     }
-    const unsigned s_ovf = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(overflow != 0u)));
-    const unsigned s_skip = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(skipped)));
-    if (lane == 0) {
-        if (s_ovf) atomicAdd(&P.counters->walk_overflow, s_ovf);
-        if (s_skip) atomicAdd(&P.counters->overlap_rays, s_skip);
-    }
+    ray_count(r, P);
+}
+
+template <int KC>
+__global__ __launch_bounds__(64) void tangent_walk_batch(TangentBatchParams A) {
+    tangent_batch_body<KC>(A);
 }
 
 // adjoint_walk<2> for KC upstream images.  Per step every lane has 2 KC values (ga_j, gq_j) for its cell.  They are staged
@@ -658,81 +663,43 @@ __global__ __launch_bounds__(64) void adjoint_walk_batch(AdjointBatchParams A) {
     constexpr int kV = 2 * KC, kRow = kV + 1;  // (row pitch: an odd number of doubles)
     __shared__ double stage[65 * kRow];
     const WalkParams& P = A.w;
-    const ImageParams& im = P.im;
-    const int tiles_x = (im.res_x + 7) / 8;
-    const int ty = static_cast<int>(blockIdx.x) / tiles_x, tx = static_cast<int>(blockIdx.x) - ty * tiles_x;
-    const int lane = static_cast<int>(threadIdx.x);
-    const int col = tx * 8 + (lane & 7), lrow = ty * 8 + (lane >> 3);
-    const bool in_image = (col < im.res_x) && (lrow < im.n_local_rows);
+    Ray r;
+    const int lane = r.lane;
     if (lane < kRow) stage[64 * kRow + lane] = 0.0;
 
-    unsigned n_step = 0, overflow = 0;
-    bool skipped = false;
-    double key_taken = -DBL_MAX;
-    double x = 0.0, y = 0.0, w_cur = -DBL_MAX, carry = 0.0;
-    EntryHead ent{0, 0};
-    int cell = -1;
-    size_t lp = 0;
     double lam = 0.0, lam_total = 0.0, I = 0.0;
     float2 g[KC];
 #pragma unroll
     for (int j = 0; j < KC; ++j) g[j] = make_float2(0.0f, 0.0f);
 
-    if (in_image) {
-        lp = static_cast<size_t>(lrow) * im.res_x + col;
-        const uint32_t mv = P.mask ? P.mask[lp] : 0u;
-        if (!mv) {  // (a solid-marked pixel shows the solid: line.cpp:177-179, nothing of the grid)
-            x = P.Xtab[col];
-            y = P.Ytab[global_row_of(im, lrow)];
-            ent = load_entry_head(P.entry_head + lp);
-            bool any = false;
+    const EntryHead ent = ray_begin(r, P, [&] {
+        bool any = false;
 #pragma unroll
-            for (int j = 0; j < KC; ++j)
-                if (j < A.n_used) {
-                    g[j] = A.grad_out[static_cast<size_t>(j) * A.image_px + lp];
-                    any = any || g[j].x != 0.0f || g[j].y != 0.0f;
-                }
-            lam_total = A.lambda[lp];
-            if (ent.count > 0 && any) cell = next_entry<true>(P, lp, ent, w_cur, carry, -DBL_MAX, -DBL_MAX, skipped);
-            key_taken = w_cur;
-        }
-    }
+        for (int j = 0; j < KC; ++j)
+            if (j < A.n_used) {
+                g[j] = A.grad_out[static_cast<size_t>(j) * A.image_px + r.lp];
+                any = any || g[j].x != 0.0f || g[j].y != 0.0f;
+            }
+        lam_total = A.lambda[r.lp];
+        return any;
+    });
 
     CellRegs cur;
-    if (cell >= 0) load_cell(cur, P.xrec, cell);
+    if (r.cell >= 0) load_cell(cur, P.xrec, r.cell);
 
     // wave-uniform loop (the reduction wants every lane): a lane whose ray has ended takes part with nothing to add
     for (;;) {
-        const bool live = cell >= 0;
+        const bool live = r.cell >= 0;
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         bool emit = false;
-        const int here = cell;
+        const int here = r.cell;
         if (live) {
-            // the step of adjoint_walk<2>, operation for operation
-            const StepGeometry sg = step_geometry(cur, x, y);
-            ++n_step;
-            const bool has_exit = sg.w_exit < INFINITY;
-            const double dz = sg.w_exit - carry;
-            const bool contributes = dz > 0.0 && dz < INFINITY;
-            int nb = -1;
-            double carry_next = carry;
-            if (has_exit) {
-                carry_next = sg.w_exit;
-                w_cur = fmax(w_cur, sg.w_exit);
-                const uint32_t id = sg.w_out & kIdMask;
-                if (id != kNoCell) nb = static_cast<int>(id);
-            }
-            if (nb >= 0 && n_step >= P.max_steps) {
-                overflow = 1;
-                nb = -1;
-            } else if (nb < 0 && !overflow) {
-                nb = next_entry<true>(P, lp, ent, w_cur, carry_next, key_taken, has_exit ? sg.w_exit : -DBL_MAX, skipped);
-                key_taken = w_cur;
-            }
+            double dz, carry_next;
+            const int nb = ray_step(r, P, ent, cur, dz, carry_next);
             CellRegs nxt;
             if (nb >= 0) load_cell(nxt, P.xrec, nb);
 
-            if (contributes) {
+            if (is_segment(dz)) {
                 const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
                 double ga[KC], gq[KC];
 #pragma unroll
@@ -760,8 +727,7 @@ __global__ __launch_bounds__(64) void adjoint_walk_batch(AdjointBatchParams A) {
                     stage[lane * kRow + KC + j] = gq[j];
                 }
             }
-            cell = nb;
-            carry = carry_next;
+            ray_advance(r, nb, carry_next);
             cur = nxt;
         }
         __syncthreads();  // (one wavefront: the rows are visible to every lane)
@@ -772,15 +738,15 @@ __global__ __launch_bounds__(64) void adjoint_walk_batch(AdjointBatchParams A) {
             const unsigned long long members = __builtin_amdgcn_ballot_w64(emit && here == lc);
             if (lane < kV) {
                 double s = 0.0;
-                for (unsigned long long r = members; r != 0ull;) {
-                    const int b0 = __builtin_ctzll(r);
-                    r &= r - 1;
-                    const int b1 = r ? __builtin_ctzll(r) : 64;
-                    r &= r - 1;
-                    const int b2 = r ? __builtin_ctzll(r) : 64;
-                    r &= r - 1;
-                    const int b3 = r ? __builtin_ctzll(r) : 64;
-                    r &= r - 1;
+                for (unsigned long long rows = members; rows != 0ull;) {
+                    const int b0 = __builtin_ctzll(rows);
+                    rows &= rows - 1;
+                    const int b1 = rows ? __builtin_ctzll(rows) : 64;
+                    rows &= rows - 1;
+                    const int b2 = rows ? __builtin_ctzll(rows) : 64;
+                    rows &= rows - 1;
+                    const int b3 = rows ? __builtin_ctzll(rows) : 64;
+                    rows &= rows - 1;
                     s += (stage[b0 * kRow + lane] + stage[b1 * kRow + lane]) + (stage[b2 * kRow + lane] + stage[b3 * kRow + lane]);
                 }
                 if (s != 0.0) atomicAdd(A.grad + static_cast<size_t>(lc) * kV + lane, s);
@@ -790,7 +756,7 @@ __global__ __launch_bounds__(64) void adjoint_walk_batch(AdjointBatchParams A) {
         __syncthreads();  // (the rows are read before the next step writes them)
     }
 
-    if (in_image && !A.keep_entries) __builtin_nontemporal_store(0ll, reinterpret_cast<long long*>(P.entry_head + lp));
+    if (!A.keep_entries) ray_clear_head(r, P);
 }
 
 // one thread per (cell, image)
@@ -823,208 +789,12 @@ __global__ __launch_bounds__(256) void adjoint_permute_batch(const double* __res
 
 template <int KC>
 __global__ __launch_bounds__(64) void gn_walk_a(GnWalkParams A) {
-    using namespace adj;
-    const WalkParams& P = A.w;
-    const ImageParams& im = P.im;
-    const D2* __restrict__ dirs = reinterpret_cast<const D2*>(A.dirs);
-    const int tiles_x = (im.res_x + 7) / 8;
-    const int ty = static_cast<int>(blockIdx.x) / tiles_x, tx = static_cast<int>(blockIdx.x) - ty * tiles_x;
-    const int lane = static_cast<int>(threadIdx.x);
-    const int col = tx * 8 + (lane & 7), lrow = ty * 8 + (lane >> 3);
-    const bool in_image = (col < im.res_x) && (lrow < im.n_local_rows);
-
-    unsigned n_step = 0, overflow = 0;
-    bool skipped = false;
-    double key_taken = -DBL_MAX;
-    double x = 0.0, y = 0.0, w_cur = -DBL_MAX, carry = 0.0;
-    EntryHead ent{0, 0};
-    int cell = -1;
-    size_t lp = 0;
-    double lam = 0.0;  // Lambda, summed as adjoint_walk<1> sums it
-    double I = 0.0, I_dot[KC], tau_dot[KC];
-#pragma unroll
-    for (int j = 0; j < KC; ++j) I_dot[j] = tau_dot[j] = 0.0;
-
-    if (in_image) {
-        lp = static_cast<size_t>(lrow) * im.res_x + col;
-        const uint32_t mv = P.mask ? P.mask[lp] : 0u;
-        if (!mv) {  // (a solid-marked pixel shows the solid: line.cpp:177-179, nothing of the grid)
-            x = P.Xtab[col];
-            y = P.Ytab[global_row_of(im, lrow)];
-            ent = load_entry_head(P.entry_head + lp);
-            if (ent.count > 0) cell = next_entry<true>(P, lp, ent, w_cur, carry, -DBL_MAX, -DBL_MAX, skipped);
-            key_taken = w_cur;
-        }
-    }
-
-    CellRegs cur;
-    if (cell >= 0) load_cell(cur, P.xrec, cell);
-
-    while (cell >= 0) {
-        D2 d[KC];
-#pragma unroll
-        for (int j = 0; j < KC; ++j) d[j] = dirs[static_cast<size_t>(cell) * KC + j];
-        // the step of tangent_walk_batch, operation for operation
-        const StepGeometry sg = step_geometry(cur, x, y);
-        ++n_step;
-        const bool has_exit = sg.w_exit < INFINITY;
-        const double dz = sg.w_exit - carry;
-        const bool contributes = dz > 0.0 && dz < INFINITY;
-        int nb = -1;
-        double carry_next = carry;
-        if (has_exit) {
-            carry_next = sg.w_exit;
-            w_cur = fmax(w_cur, sg.w_exit);
-            const uint32_t id = sg.w_out & kIdMask;
-            if (id != kNoCell) nb = static_cast<int>(id);
-        }
-        if (nb >= 0 && n_step >= P.max_steps) {
-            overflow = 1;
-            nb = -1;
-        } else if (nb < 0 && !overflow) {
-            nb = next_entry<true>(P, lp, ent, w_cur, carry_next, key_taken, has_exit ? sg.w_exit : -DBL_MAX, skipped);
-            key_taken = w_cur;
-        }
-        CellRegs nxt;
-        if (nb >= 0) load_cell(nxt, P.xrec, nb);
-
-        if (contributes) {
-            const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
-#pragma unroll
-            for (int j = 0; j < KC; ++j) tau_dot[j] = fma(dz, d[j].a, tau_dot[j]);  // d tau / d alpha (raw alpha)
-            if (a != 0.0) {
-                lam = fma(a, dz, lam);  // (adjoint_walk<1>: pass B's running Lambda_k ends on this to the bit)
-                const double E = exp_nonpositive(-a * dz);
-                const SegmentTerms t = segment_terms(a, q, dz, E, 1.0, I);
-                const bool clamped = a != a_raw;
-#pragma unroll
-                for (int j = 0; j < KC; ++j) {
-                    double src = d[j].b * t.dI_dq;
-                    if (!clamped) src = fma(d[j].a, t.dI_da, src);  // (a clamped alpha does not move: line.cpp:216)
-                    I_dot[j] = fma(E, I_dot[j], src);
-                }
-                I = t.I_next;
-            }
-        }
-        cell = nb;
-        carry = carry_next;
-        cur = nxt;
-    }
-
-    if (in_image) {
-        A.lambda[lp] = lam;
-        const float2 w = A.weight ? A.weight[lp] : make_float2(1.0f, 1.0f);  // (loaded here, not held across the loop)
-#pragma unroll
-        for (int j = 0; j < KC; ++j)
-            if (j < A.n_used) {
-                const float2 t = make_float2(static_cast<float>(tau_dot[j]), static_cast<float>(I_dot[j]));
-                if (A.jv_out) A.jv_out[static_cast<size_t>(j) * A.image_px + lp] = t;
-                A.g[static_cast<size_t>(j) * A.image_px + lp] = make_float2(__fmul_rn(w.x, t.x), __fmul_rn(w.y, t.y));
-            }
-        // (the entry heads stay in place for pass B)
-    }
-    const unsigned s_ovf = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(overflow != 0u)));
-    const unsigned s_skip = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(skipped)));
-    if (lane == 0) {
-        if (s_ovf) atomicAdd(&P.counters->walk_overflow, s_ovf);
-        if (s_skip) atomicAdd(&P.counters->overlap_rays, s_skip);
-    }
+    tangent_batch_body<KC>(A);
 }
 
 // adjoint_walk<2> with squares (after adjoint_walk<1>: A.lambda).  A.grad_out holds the weights, or nullptr for ones.
 __global__ __launch_bounds__(64) void gn_diag_walk(AdjointParams A) {
-    using namespace adj;
-    const WalkParams& P = A.w;
-    const ImageParams& im = P.im;
-    const int tiles_x = (im.res_x + 7) / 8;
-    const int ty = static_cast<int>(blockIdx.x) / tiles_x, tx = static_cast<int>(blockIdx.x) - ty * tiles_x;
-    const int lane = static_cast<int>(threadIdx.x);
-    const int col = tx * 8 + (lane & 7), lrow = ty * 8 + (lane >> 3);
-    const bool in_image = (col < im.res_x) && (lrow < im.n_local_rows);
-
-    unsigned n_step = 0, overflow = 0;
-    bool skipped = false;
-    double key_taken = -DBL_MAX;
-    double x = 0.0, y = 0.0, w_cur = -DBL_MAX, carry = 0.0;
-    EntryHead ent{0, 0};
-    int cell = -1;
-    size_t lp = 0;
-    double lam = 0.0, lam_total = 0.0, I = 0.0, w_tau = 0.0, w_I = 0.0;
-
-    if (in_image) {
-        lp = static_cast<size_t>(lrow) * im.res_x + col;
-        const uint32_t mv = P.mask ? P.mask[lp] : 0u;
-        if (!mv) {  // (a solid-marked pixel shows the solid: line.cpp:177-179, nothing of the grid)
-            x = P.Xtab[col];
-            y = P.Ytab[global_row_of(im, lrow)];
-            ent = load_entry_head(P.entry_head + lp);
-            const float2 w = A.grad_out ? A.grad_out[lp] : make_float2(1.0f, 1.0f);
-            w_tau = w.x;
-            w_I = w.y;
-            lam_total = A.lambda[lp];
-            if (ent.count > 0 && (w_tau != 0.0 || w_I != 0.0))
-                cell = next_entry<true>(P, lp, ent, w_cur, carry, -DBL_MAX, -DBL_MAX, skipped);
-            key_taken = w_cur;
-        }
-    }
-
-    CellRegs cur;
-    if (cell >= 0) load_cell(cur, P.xrec, cell);
-
-    // wave-uniform loop (the scatter wants every lane): a lane whose ray has ended takes part with nothing to add
-    for (;;) {
-        const bool live = cell >= 0;
-        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
-        bool emit = false;
-        double da = 0.0, dq = 0.0;
-        const int here = cell;
-        if (live) {
-            // the step of adjoint_walk<2>, operation for operation: the same segments, the same T_k
-            const StepGeometry sg = step_geometry(cur, x, y);
-            ++n_step;
-            const bool has_exit = sg.w_exit < INFINITY;
-            const double dz = sg.w_exit - carry;
-            const bool contributes = dz > 0.0 && dz < INFINITY;
-            int nb = -1;
-            double carry_next = carry;
-            if (has_exit) {
-                carry_next = sg.w_exit;
-                w_cur = fmax(w_cur, sg.w_exit);
-                const uint32_t id = sg.w_out & kIdMask;
-                if (id != kNoCell) nb = static_cast<int>(id);
-            }
-            if (nb >= 0 && n_step >= P.max_steps) {
-                overflow = 1;
-                nb = -1;
-            } else if (nb < 0 && !overflow) {
-                nb = next_entry<true>(P, lp, ent, w_cur, carry_next, key_taken, has_exit ? sg.w_exit : -DBL_MAX, skipped);
-                key_taken = w_cur;
-            }
-            CellRegs nxt;
-            if (nb >= 0) load_cell(nxt, P.xrec, nb);
-
-            if (contributes) {
-                const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
-                emit = true;
-                da = w_tau * (dz * dz);  // (d tau / d alpha)^2 (raw alpha, every segment)
-                if (a != 0.0) {
-                    lam = fma(a, dz, lam);
-                    const double T = exp_nonpositive(fmin(lam - lam_total, 0.0));
-                    const double E = exp_nonpositive(-a * dz);
-                    const SegmentTerms t = segment_terms(a, q, dz, E, T, I);
-                    dq = w_I * (t.dI_dq * t.dI_dq);
-                    if (a == a_raw) da = fma(w_I, t.dI_da * t.dI_da, da);  // (a clamped alpha does not move)
-                    I = t.I_next;
-                }
-            }
-            cell = nb;
-            carry = carry_next;
-            cur = nxt;
-        }
-        scatter_wave(emit, here, da, dq, A.grad_a, A.grad_q);
-    }
-
-    if (in_image) __builtin_nontemporal_store(0ll, reinterpret_cast<long long*>(P.entry_head + lp));  // cleared, as the walk leaves them
+    adj::adjoint_walk_body<2, true>(A);
 }
 
 // g = w * t per channel, one fp32 multiply (gn_walk_a's store, for tangent_resolve's images); w nullptr: ones
@@ -1042,61 +812,7 @@ __global__ __launch_bounds__(256) void gn_diag_resolve(GridView g, ImageParams i
                                                        AdjSegment* __restrict__ segs, const uint32_t* __restrict__ mask,
                                                        double alpha_limit, const float2* __restrict__ weight,
                                                        double* __restrict__ diag_a, double* __restrict__ diag_q) {
-    using namespace adj;
-    const int64_t lp = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
-    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
-    int n = 0;
-    AdjSegment* list = segs;
-    double w_tau = 0.0, w_I = 0.0, lam_total = 0.0;
-    if (lp < n_px && !(mask && mask[lp])) {
-        list = segs + offs[lp];
-        n = static_cast<int>(offs[lp + 1] - offs[lp]);
-        const float2 w = weight ? weight[lp] : make_float2(1.0f, 1.0f);
-        w_tau = w.x;
-        w_I = w.y;
-        if (w_tau == 0.0 && w_I == 0.0) n = 0;
-        for (int gap = n / 2; gap > 0; gap = (gap == 2) ? 1 : static_cast<int>(gap / 2.2)) {
-            for (int i = gap; i < n; ++i) {
-                const AdjSegment t = list[i];
-                int j = i;
-                while (j >= gap && list[j - gap].z_hi < t.z_hi) {
-                    list[j] = list[j - gap];
-                    j -= gap;
-                }
-                list[j] = t;
-            }
-        }
-        for (int i = n - 1; i >= 0; --i) {  // Lambda, in the order the loop below runs
-            double a = g.alpha[list[i].cell];
-            if (a > alpha_limit) a = alpha_limit;
-            if (!(a < DBL_EPSILON)) lam_total = fma(a, list[i].dz, lam_total);
-        }
-    }
-    double lam = 0.0, I = 0.0;
-    // wave-uniform loop over the steps (the scatter wants every lane)
-    for (int i = n - 1;; --i) {
-        const bool live = i >= 0;
-        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
-        int c = -1;
-        double da = 0.0, dq = 0.0;
-        if (live) {
-            c = static_cast<int>(list[i].cell);
-            const double dz = list[i].dz, q = g.q[c], a_raw = g.alpha[c];
-            double a = a_raw;
-            if (a > alpha_limit) a = alpha_limit;
-            da = w_tau * (dz * dz);
-            if (!(a < DBL_EPSILON)) {
-                lam = fma(a, dz, lam);
-                const double T = exp(fmin(lam - lam_total, 0.0));
-                const double E = exp(-a * dz);
-                const SegmentTerms t = segment_terms(a, q, dz, E, T, I);
-                dq = w_I * (t.dI_dq * t.dI_dq);
-                if (!(a_raw > alpha_limit)) da = fma(w_I, t.dI_da * t.dI_da, da);
-                I = t.I_next;
-            }
-        }
-        scatter_wave(live, c, da, dq, diag_a, diag_q);
-    }
+    adj::adjoint_resolve_body<true>(g, im, offs, segs, mask, alpha_limit, weight, diag_a, diag_q);
 }
 
 // c5_update_scalars_device: the gather into device order, and c5_update_scalars' three statistics as bit-pattern maxima
@@ -1139,10 +855,27 @@ __global__ __launch_bounds__(256) void scalars_gather(const double* __restrict__
     }
 }
 
+namespace {
+// workgroups of a walk kernel: one wavefront per 8x8 pixel tile (0: no pixel)
+unsigned tile_blocks(const ImageParams& im) {
+    if (im.res_x <= 0 || im.n_local_rows <= 0) return 0u;
+    return static_cast<unsigned>(((im.res_x + 7) / 8) * ((im.n_local_rows + 7) / 8));
+}
+// workgroups of 256 threads for n items (0: none)
+unsigned item_blocks(int64_t n) { return n > 0 ? static_cast<unsigned>((n + 255) / 256) : 0u; }
+unsigned pixel_blocks(const ImageParams& im) { return item_blocks(static_cast<int64_t>(im.n_local_rows) * im.res_x); }
+}  // namespace
+
+// kernel<4> or kernel<8> by the chunk width kc
+#define C5_LAUNCH_KC(kernel, kc, blocks, threads, s, ...)                                      \
+    do {                                                                                       \
+        if ((kc) == 4) hipLaunchKernelGGL(kernel<4>, dim3(blocks), dim3(threads), 0, s, __VA_ARGS__); \
+        else hipLaunchKernelGGL(kernel<8>, dim3(blocks), dim3(threads), 0, s, __VA_ARGS__);    \
+    } while (0)
+
 void launch_adjoint_walk(hipStream_t s, const AdjointParams& a, int pass) {
-    const ImageParams& im = a.w.im;
-    if (im.res_x <= 0 || im.n_local_rows <= 0) return;
-    const unsigned blocks = static_cast<unsigned>(((im.res_x + 7) / 8) * ((im.n_local_rows + 7) / 8));
+    const unsigned blocks = tile_blocks(a.w.im);
+    if (!blocks) return;
     if (pass == 1)
         hipLaunchKernelGGL(adjoint_walk<1>, dim3(blocks), dim3(64), 0, s, a);
     else
@@ -1151,9 +884,8 @@ void launch_adjoint_walk(hipStream_t s, const AdjointParams& a, int pass) {
 
 void launch_adjoint_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const int64_t* offs, void* segs,
                             const uint32_t* mask, double alpha_limit, const float2* grad_out, double* grad_a, double* grad_q) {
-    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
-    if (n_px <= 0) return;
-    const unsigned blocks = static_cast<unsigned>((n_px + 255) / 256);
+    const unsigned blocks = pixel_blocks(im);
+    if (!blocks) return;
     hipLaunchKernelGGL(adjoint_resolve, dim3(blocks), dim3(256), 0, s, g, im, offs, static_cast<AdjSegment*>(segs), mask, alpha_limit,
                        grad_out, grad_a, grad_q);
 }
@@ -1161,29 +893,24 @@ void launch_adjoint_resolve(hipStream_t s, const GridView& g, const ImageParams&
 void launch_adjoint_permute(hipStream_t s, const double* ga_dev, const double* gq_dev, const int32_t* perm, int64_t n,
                             double* ga_out, double* gq_out) {
     if (n <= 0) return;
-    const unsigned blocks = static_cast<unsigned>((n + 255) / 256);
-    hipLaunchKernelGGL(adjoint_permute, dim3(blocks), dim3(256), 0, s, ga_dev, gq_dev, perm, n, ga_out, gq_out);
+    hipLaunchKernelGGL(adjoint_permute, dim3(item_blocks(n)), dim3(256), 0, s, ga_dev, gq_dev, perm, n, ga_out, gq_out);
 }
 
 void launch_tangent_gather(hipStream_t s, const double* d_alpha, const double* d_q, const int32_t* perm, int64_t n,
                            double2* dir) {
     if (n <= 0) return;
-    const unsigned blocks = static_cast<unsigned>((n + 255) / 256);
-    hipLaunchKernelGGL(tangent_gather, dim3(blocks), dim3(256), 0, s, d_alpha, d_q, perm, n, dir);
+    hipLaunchKernelGGL(tangent_gather, dim3(item_blocks(n)), dim3(256), 0, s, d_alpha, d_q, perm, n, dir);
 }
 
 void launch_tangent_walk(hipStream_t s, const TangentParams& t) {
-    const ImageParams& im = t.w.im;
-    if (im.res_x <= 0 || im.n_local_rows <= 0) return;
-    const unsigned blocks = static_cast<unsigned>(((im.res_x + 7) / 8) * ((im.n_local_rows + 7) / 8));
-    hipLaunchKernelGGL(tangent_walk, dim3(blocks), dim3(64), 0, s, t);
+    const unsigned blocks = tile_blocks(t.w.im);
+    if (blocks) hipLaunchKernelGGL(tangent_walk, dim3(blocks), dim3(64), 0, s, t);
 }
 
 void launch_tangent_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const int64_t* offs, void* segs,
                             const uint32_t* mask, double alpha_limit, const double2* dir, float2* out) {
-    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
-    if (n_px <= 0) return;
-    const unsigned blocks = static_cast<unsigned>((n_px + 255) / 256);
+    const unsigned blocks = pixel_blocks(im);
+    if (!blocks) return;
     hipLaunchKernelGGL(tangent_resolve, dim3(blocks), dim3(256), 0, s, g, im, offs, static_cast<AdjSegment*>(segs), mask, alpha_limit,
                        dir, out);
 }
@@ -1191,71 +918,44 @@ void launch_tangent_resolve(hipStream_t s, const GridView& g, const ImageParams&
 void launch_tangent_gather_batch(hipStream_t s, int kc, const double* d_alpha, const double* d_q, const int32_t* perm, int64_t n,
                                  int k0, int n_used, double2* dirs) {
     if (n <= 0) return;
-    const unsigned blocks = static_cast<unsigned>((n * kc + 255) / 256);
-    if (kc == 4)
-        hipLaunchKernelGGL(tangent_gather_batch<4>, dim3(blocks), dim3(256), 0, s, d_alpha, d_q, perm, n, k0, n_used, dirs);
-    else
-        hipLaunchKernelGGL(tangent_gather_batch<8>, dim3(blocks), dim3(256), 0, s, d_alpha, d_q, perm, n, k0, n_used, dirs);
+    C5_LAUNCH_KC(tangent_gather_batch, kc, item_blocks(n * kc), 256, s, d_alpha, d_q, perm, n, k0, n_used, dirs);
 }
 
 void launch_tangent_walk_batch(hipStream_t s, int kc, const TangentBatchParams& t) {
-    const ImageParams& im = t.w.im;
-    if (im.res_x <= 0 || im.n_local_rows <= 0) return;
-    const unsigned blocks = static_cast<unsigned>(((im.res_x + 7) / 8) * ((im.n_local_rows + 7) / 8));
-    if (kc == 4)
-        hipLaunchKernelGGL(tangent_walk_batch<4>, dim3(blocks), dim3(64), 0, s, t);
-    else
-        hipLaunchKernelGGL(tangent_walk_batch<8>, dim3(blocks), dim3(64), 0, s, t);
+    const unsigned blocks = tile_blocks(t.w.im);
+    if (blocks) C5_LAUNCH_KC(tangent_walk_batch, kc, blocks, 64, s, t);
 }
 
 void launch_adjoint_walk_batch(hipStream_t s, int kc, const AdjointBatchParams& a) {
-    const ImageParams& im = a.w.im;
-    if (im.res_x <= 0 || im.n_local_rows <= 0) return;
-    const unsigned blocks = static_cast<unsigned>(((im.res_x + 7) / 8) * ((im.n_local_rows + 7) / 8));
-    if (kc == 4)
-        hipLaunchKernelGGL(adjoint_walk_batch<4>, dim3(blocks), dim3(64), 0, s, a);
-    else
-        hipLaunchKernelGGL(adjoint_walk_batch<8>, dim3(blocks), dim3(64), 0, s, a);
+    const unsigned blocks = tile_blocks(a.w.im);
+    if (blocks) C5_LAUNCH_KC(adjoint_walk_batch, kc, blocks, 64, s, a);
 }
 
 void launch_adjoint_permute_batch(hipStream_t s, int kc, const double* grad, const int32_t* perm, int64_t n, int k0, int n_used,
                                   double* ga_out, double* gq_out) {
     if (n <= 0) return;
-    const unsigned blocks = static_cast<unsigned>((n * kc + 255) / 256);
-    if (kc == 4)
-        hipLaunchKernelGGL(adjoint_permute_batch<4>, dim3(blocks), dim3(256), 0, s, grad, perm, n, k0, n_used, ga_out, gq_out);
-    else
-        hipLaunchKernelGGL(adjoint_permute_batch<8>, dim3(blocks), dim3(256), 0, s, grad, perm, n, k0, n_used, ga_out, gq_out);
+    C5_LAUNCH_KC(adjoint_permute_batch, kc, item_blocks(n * kc), 256, s, grad, perm, n, k0, n_used, ga_out, gq_out);
 }
 
 void launch_gn_walk_a(hipStream_t s, int kc, const GnWalkParams& a) {
-    const ImageParams& im = a.w.im;
-    if (im.res_x <= 0 || im.n_local_rows <= 0) return;
-    const unsigned blocks = static_cast<unsigned>(((im.res_x + 7) / 8) * ((im.n_local_rows + 7) / 8));
-    if (kc == 4)
-        hipLaunchKernelGGL(gn_walk_a<4>, dim3(blocks), dim3(64), 0, s, a);
-    else
-        hipLaunchKernelGGL(gn_walk_a<8>, dim3(blocks), dim3(64), 0, s, a);
+    const unsigned blocks = tile_blocks(a.w.im);
+    if (blocks) C5_LAUNCH_KC(gn_walk_a, kc, blocks, 64, s, a);
 }
 
 void launch_gn_diag_walk(hipStream_t s, const AdjointParams& a) {
-    const ImageParams& im = a.w.im;
-    if (im.res_x <= 0 || im.n_local_rows <= 0) return;
-    const unsigned blocks = static_cast<unsigned>(((im.res_x + 7) / 8) * ((im.n_local_rows + 7) / 8));
-    hipLaunchKernelGGL(gn_diag_walk, dim3(blocks), dim3(64), 0, s, a);
+    const unsigned blocks = tile_blocks(a.w.im);
+    if (blocks) hipLaunchKernelGGL(gn_diag_walk, dim3(blocks), dim3(64), 0, s, a);
 }
 
 void launch_gn_weight(hipStream_t s, const float2* t, const float2* w, int64_t n_px, int n_imgs, float2* g) {
     if (n_px <= 0 || n_imgs <= 0) return;
-    const unsigned blocks = static_cast<unsigned>((n_px * n_imgs + 255) / 256);
-    hipLaunchKernelGGL(gn_weight, dim3(blocks), dim3(256), 0, s, t, w, n_px, n_imgs, g);
+    hipLaunchKernelGGL(gn_weight, dim3(item_blocks(n_px * n_imgs)), dim3(256), 0, s, t, w, n_px, n_imgs, g);
 }
 
 void launch_gn_diag_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const int64_t* offs, void* segs,
                             const uint32_t* mask, double alpha_limit, const float2* weight, double* diag_a, double* diag_q) {
-    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
-    if (n_px <= 0) return;
-    const unsigned blocks = static_cast<unsigned>((n_px + 255) / 256);
+    const unsigned blocks = pixel_blocks(im);
+    if (!blocks) return;
     hipLaunchKernelGGL(gn_diag_resolve, dim3(blocks), dim3(256), 0, s, g, im, offs, static_cast<AdjSegment*>(segs), mask, alpha_limit,
                        weight, diag_a, diag_q);
 }

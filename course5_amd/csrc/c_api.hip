@@ -269,7 +269,6 @@ struct c5_context {
     DeviceBuffer adj_sticky;    // the entry raster's failure words for the adjoint (never the frames' sticky words)
     DeviceBuffer adj_grad;      // [2][n_cells] fp64, device order
     DeviceBuffer adj_perm;      // cell_perm on the device, for the grid of upload adj_perm_serial
-    DeviceBuffer adj_io;        // c5_render_adjoint: the weights' image and the caller-order gradients
     uint64_t grid_serial = 0, adj_perm_serial = ~uint64_t{0};
     unsigned* adj_status = nullptr;  // pinned: walk_overflow, entry_overflow, overlap_rays of the last adjoint or tangent
     bool adjoint_pending = false;    // its status has not been looked at yet
@@ -278,17 +277,16 @@ struct c5_context {
     // tangent render (c5_render_tangent*): shares the adjoint's counters, sticky and status words and adj_perm; nothing of
     // it is allocated before the first tangent call
     DeviceBuffer tan_dir;  // [n_cells] {dalpha, dQ} fp64, device order (adjoint_kernels.hip: tangent_gather)
-    DeviceBuffer tan_io;   // c5_render_tangent: the caller's directions and the image
 
     // batches (c5_render_tangent_batch*, c5_render_adjoint_batch*): nothing of it is allocated before the first batch call
     int batch_width = 0;    // "batch_width": directions or upstream images per walk (0: 4 for batches of up to 4, else 8)
     DeviceBuffer bat_dirs;  // [n_cells][width] {dalpha, dQ} fp64, device order (adjoint_kernels.hip: tangent_gather_batch)
     DeviceBuffer bat_grad;  // [n_cells][2 width] fp64, device order (adjoint_walk_batch)
-    DeviceBuffer bat_io;    // the synchronous forms: the caller's directions or weights, and what goes back
     // Gauss-Newton renders (c5_render_gn_product*, c5_render_gn_diagonal*): nothing of it is allocated before the first call
     DeviceBuffer gn_g;      // [width][n_local_px] float2: pass A's w * J v, pass B's upstream images (a chunk's)
     DeviceBuffer gn_spare;  // [width][n_cells] fp64: where the block of H v goes that the caller did not ask for
-    DeviceBuffer gn_io;     // the synchronous forms: directions, weights, and what goes back
+    // the host-pointer forms of all derivative renders: what the caller hands in and what goes back (run_staged)
+    DeviceBuffer deriv_io;
     // c5_update_scalars_device: the three statistics of the scalars on the device, and their pinned copy
     DeviceBuffer scal_stats;
     unsigned long long* scal_host = nullptr;
@@ -565,38 +563,17 @@ int enqueue_bin_sort(c5_context* ctx, FrameSlot& fs, const c5::GridView& g, int 
     return C5_OK;
 }
 
-// Enqueue one frame; the image goes to out_dev.  The per-view setup runs on the auxiliary stream
-// into frame slot (frame_index & 1), the walk on the main stream once that setup is done, so the
-// setup of the next frame overlaps this frame's walk.
-// own_counters: the frame's statistics go to these FrameCounters[kCounterShards] instead of the slot's (frames delivered to
-// host memory: each frame of the ring keeps its own, c5_render_host_async).
-int enqueue_frame(c5_context* ctx, float2* out_dev, c5::FrameCounters* own_counters = nullptr) {
-    if (ctx->n_cells <= 0 && [&] {
-            for (const Solid& s : ctx->solids)
-                if (s.n_tets > 0) return false;
-            return true;
-        }())
-        return fail(ctx, C5_ERR_STATE, "plane initializer. empty set of objects to render");  // plane.cpp:269-271
-    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
-    int rc = bind_device(ctx);
-    if (rc) return rc;
+// no cell and no solid with a tetrahedron (plane.cpp:269-271)
+bool nothing_to_render(const c5_context* ctx) {
+    if (ctx->n_cells > 0) return false;
+    for (const Solid& s : ctx->solids)
+        if (s.n_tets > 0) return false;
+    return true;
+}
 
-    const int slot_id = ctx->pipeline ? static_cast<int>(ctx->frame_index & 1) : 0;
-    FrameSlot& fs = ctx->slots[slot_id];
-    hipStream_t main_s = ctx->stream;
-    hipStream_t s = ctx->pipeline ? ctx->aux_stream : ctx->stream;  // setup stream
+// The grid as the kernels see it, with the per-view buffers of frame slot fs.
+c5::GridView grid_view(const c5_context* ctx, const FrameSlot& fs) {
     const c5::ImageParams& im = ctx->im;
-    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
-    const int64_t padded = ((n_px + 1023) / 1024) * 1024;
-    const bool timed = ctx->stage_timing != 0;
-    auto mark = [&](int k, hipStream_t st) -> hipError_t { return timed ? hipEventRecord(fs.ev[k], st) : hipSuccess; };
-    c5::FrameCounters* const counters = own_counters ? own_counters : fs.counters.as<c5::FrameCounters>();
-
-    // the slot's buffers are free once the walk that last read them has finished
-    if (ctx->pipeline && fs.walk_recorded) C5_HIP(ctx, hipStreamWaitEvent(s, fs.walk_done, 0));
-
-    C5_HIP(ctx, mark(0, s));
-
     c5::GridView g;
     g.n_pts = ctx->n_pts;
     g.n_cells = ctx->n_cells;
@@ -627,6 +604,37 @@ int enqueue_frame(c5_context* ctx, float2* out_dev, c5::FrameCounters* own_count
         g.cull_y_lo = 1.0;
         g.cull_y_hi = -1.0;
     }
+    return g;
+}
+
+// Enqueue one frame; the image goes to out_dev.  The per-view setup runs on the auxiliary stream
+// into frame slot (frame_index & 1), the walk on the main stream once that setup is done, so the
+// setup of the next frame overlaps this frame's walk.
+// own_counters: the frame's statistics go to these FrameCounters[kCounterShards] instead of the slot's (frames delivered to
+// host memory: each frame of the ring keeps its own, c5_render_host_async).
+int enqueue_frame(c5_context* ctx, float2* out_dev, c5::FrameCounters* own_counters = nullptr) {
+    if (nothing_to_render(ctx)) return fail(ctx, C5_ERR_STATE, "plane initializer. empty set of objects to render");  // plane.cpp:269-271
+    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+
+    const int slot_id = ctx->pipeline ? static_cast<int>(ctx->frame_index & 1) : 0;
+    FrameSlot& fs = ctx->slots[slot_id];
+    hipStream_t main_s = ctx->stream;
+    hipStream_t s = ctx->pipeline ? ctx->aux_stream : ctx->stream;  // setup stream
+    const c5::ImageParams& im = ctx->im;
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    const int64_t padded = ((n_px + 1023) / 1024) * 1024;
+    const bool timed = ctx->stage_timing != 0;
+    auto mark = [&](int k, hipStream_t st) -> hipError_t { return timed ? hipEventRecord(fs.ev[k], st) : hipSuccess; };
+    c5::FrameCounters* const counters = own_counters ? own_counters : fs.counters.as<c5::FrameCounters>();
+
+    // the slot's buffers are free once the walk that last read them has finished
+    if (ctx->pipeline && fs.walk_recorded) C5_HIP(ctx, hipStreamWaitEvent(s, fs.walk_done, 0));
+
+    C5_HIP(ctx, mark(0, s));
+
+    c5::GridView g = grid_view(ctx, fs);
 
     // (a2) view transform
     // (a2) + the frame's statistics cleared by the same launch
@@ -1219,6 +1227,9 @@ int finish_frame(c5_context* ctx) {
 struct DerivativeView {
     bool no_cells = false;  // a scene of solids only: nothing was set up (there is no cell to differentiate)
     bool bin_sort = false;  // "algorithm" 1: bin_sort_resolve's lists in ctx->offs64 / ctx->segs; else the walk's in w
+    hipStream_t s = nullptr;        // the context's stream: everything of a derivative runs on it
+    int64_t n_px = 0, padded = 0;   // pixels of the context's rows; rounded up to the scan's 1024
+    const int32_t* perm = nullptr;  // cell_perm on the device (device order -> the caller's), or nullptr: the identity
     c5::GridView g{};
     const uint32_t* mask = nullptr;  // solid-marked pixels, or nullptr
     c5::WalkParams w{};
@@ -1236,15 +1247,15 @@ int ensure_device_perm(c5_context* ctx) {
 }
 
 int setup_derivative(c5_context* ctx, DerivativeView& v) {
-    if (ctx->n_cells <= 0 && [&] {
-            for (const Solid& s : ctx->solids)
-                if (s.n_tets > 0) return false;
-            return true;
-        }())
-        return fail(ctx, C5_ERR_STATE, "plane initializer. empty set of objects to render");  // plane.cpp:269-271
+    if (nothing_to_render(ctx)) return fail(ctx, C5_ERR_STATE, "plane initializer. empty set of objects to render");  // plane.cpp:269-271
     if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
     int rc = bind_device(ctx);
     if (rc) return rc;
+    FrameSlot& fs = ctx->slots[0];
+    hipStream_t s = v.s = ctx->stream;
+    const c5::ImageParams& im = ctx->im;
+    const int64_t n_px = v.n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    const int64_t padded = v.padded = ((n_px + 1023) / 1024) * 1024;
     if (ctx->n_cells <= 0) {  // (solids only: no cell to differentiate)
         v.no_cells = true;
         return C5_OK;
@@ -1256,48 +1267,17 @@ int setup_derivative(c5_context* ctx, DerivativeView& v) {
         rc = drain(ctx);
         if (rc) return rc;
     }
-    FrameSlot& fs = ctx->slots[0];
-    hipStream_t s = ctx->stream;
-    const c5::ImageParams& im = ctx->im;
-    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
-    const int64_t padded = ((n_px + 1023) / 1024) * 1024;
 
     C5_HIP(ctx, ctx->adj_counters.ensure(kCountersBytes));
     C5_HIP(ctx, ctx->adj_sticky.ensure(kStickyWords * sizeof(unsigned)));
     if (!ctx->adj_status) C5_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->adj_status), 4 * sizeof(unsigned), hipHostMallocDefault));
     rc = ensure_device_perm(ctx);
     if (rc) return rc;
+    v.perm = ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>();
     c5::FrameCounters* const counters = ctx->adj_counters.as<c5::FrameCounters>();
     C5_HIP(ctx, hipMemsetAsync(ctx->adj_sticky.ptr, 0, kStickyWords * sizeof(unsigned), s));
 
-    c5::GridView& g = v.g;
-    g.n_pts = ctx->n_pts;
-    g.n_cells = ctx->n_cells;
-    g.n_bfaces = ctx->n_bfaces;
-    g.px = ctx->px.as<double>();
-    g.py = ctx->py.as<double>();
-    g.pz = ctx->pz.as<double>();
-    g.vx = fs.vx.as<double>();
-    g.vy = fs.vy.as<double>();
-    g.vz = fs.vz.as<double>();
-    g.cell_vert = ctx->cell_vert.as<int4>();
-    g.cell_adj = ctx->cell_adj.as<int4>();
-    g.alpha = ctx->alpha.as<double>();
-    g.q = ctx->q.as<double>();
-    g.bface = ctx->bface.as<uint32_t>();
-    g.xrec = fs.rec.as<c5::ExitRecord>();
-    g.rot = ctx->view;
-    g.block_sphere = (ctx->block_cull && im.n_local_rows > 0 && im.n_local_rows < im.res_y && ctx->block_sphere.ptr) ? ctx->block_sphere.as<double4>() : nullptr;
-    if (im.n_local_rows > 0) {  // (as enqueue_frame)
-        const int first = c5::global_row_of(im, 0), last = c5::global_row_of(im, im.n_local_rows - 1);
-        const double pad = std::fabs(im.step_y);
-        const double ya = ctx->host_ytab[static_cast<size_t>(first)], yb = ctx->host_ytab[static_cast<size_t>(last)];
-        g.cull_y_lo = std::fmin(ya, yb) - pad;
-        g.cull_y_hi = std::fmax(ya, yb) + pad;
-    } else {
-        g.cull_y_lo = 1.0;
-        g.cull_y_hi = -1.0;
-    }
+    c5::GridView& g = v.g = grid_view(ctx, fs);
     // the slot's per-view data are about to hold the derivative's: no frame may take them for its own
     fs.setup_epoch = 0;
     fs.setup_kept = false;
@@ -1368,70 +1348,86 @@ int commit_derivative(c5_context* ctx, const char* what) {
     return C5_OK;
 }
 
-// The adjoint: two passes of the walk (or adjoint_resolve over bin_sort_resolve's lists), then the permutation into the
-// caller's order.
-int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, double* gq_out) {
-    DerivativeView v;
-    int rc = setup_derivative(ctx, v);
-    if (rc || v.no_cells) return rc;
-    FrameSlot& fs = ctx->slots[0];
-    hipStream_t s = ctx->stream;
-    const c5::ImageParams& im = ctx->im;
+// The adjoint's parameters over the view's walk, with Lambda's buffer (pass 1 -> pass 2); the weights and where the sums
+// go are the caller's to fill in.
+int adjoint_params(c5_context* ctx, const DerivativeView& v, c5::AdjointParams& ap) {
+    C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
+    ap = c5::AdjointParams{};
+    ap.w = v.w;
+    ap.lambda = ctx->adj_lambda.as<double>();
+    return C5_OK;
+}
+
+// One adjoint over the view: the per-cell sums zeroed, two passes of the walk (or the resolve over bin_sort_resolve's
+// lists), and the permutation into the caller's order.  squared: the Gauss-Newton diagonal's kernels, `weights` may
+// then be null (ones).
+int adjoint_one(c5_context* ctx, const DerivativeView& v, bool squared, const float2* weights, double* ga_out, double* gq_out) {
     const size_t n_cells = static_cast<size_t>(ctx->n_cells);
     C5_HIP(ctx, ctx->adj_grad.ensure(2 * n_cells * sizeof(double)));
     double* const ga_dev = ctx->adj_grad.as<double>();
     double* const gq_dev = ga_dev + n_cells;
-    C5_HIP(ctx, hipMemsetAsync(ga_dev, 0, 2 * n_cells * sizeof(double), s));
+    C5_HIP(ctx, hipMemsetAsync(ga_dev, 0, 2 * n_cells * sizeof(double), v.s));
     if (v.bin_sort) {
-        c5::launch_adjoint_resolve(s, v.g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, grad_out,
-                                   ga_dev, gq_dev);
+        const auto resolve = squared ? c5::launch_gn_diag_resolve : c5::launch_adjoint_resolve;
+        resolve(v.s, v.g, ctx->im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, weights, ga_dev, gq_dev);
     } else {
-        const int64_t padded = ((static_cast<int64_t>(im.n_local_rows) * im.res_x + 1023) / 1024) * 1024;
-        C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(padded) * sizeof(double)));
-        c5::AdjointParams ap{};
-        ap.w = v.w;
-        ap.grad_out = grad_out;
-        ap.lambda = ctx->adj_lambda.as<double>();
+        c5::AdjointParams ap;
+        int rc = adjoint_params(ctx, v, ap);
+        if (rc) return rc;
+        ap.grad_out = weights;
         ap.grad_a = ga_dev;
         ap.grad_q = gq_dev;
-        c5::launch_adjoint_walk(s, ap, 1);
-        c5::launch_adjoint_walk(s, ap, 2);
-        fs.head_clean = true;  // (pass 2 hands every head back cleared)
+        c5::launch_adjoint_walk(v.s, ap, 1);
+        if (squared) c5::launch_gn_diag_walk(v.s, ap);
+        else c5::launch_adjoint_walk(v.s, ap, 2);
+        ctx->slots[0].head_clean = true;  // (the second pass hands every head back cleared)
     }
-    c5::launch_adjoint_permute(s, ga_dev, gq_dev, ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>(), ctx->n_cells,
-                               ga_out, gq_out);
-    return commit_derivative(ctx, "adjoint");
+    c5::launch_adjoint_permute(v.s, ga_dev, gq_dev, v.perm, ctx->n_cells, ga_out, gq_out);
+    return C5_OK;
 }
 
-// The tangent: the caller's directions into device order, then one walk (or tangent_resolve over bin_sort_resolve's
-// lists) that writes (tau_dot, I_dot) per pixel.
-int enqueue_tangent(c5_context* ctx, const double* d_alpha, const double* d_q, float2* out) {
+// The adjoint: adjoint_one on the upstream image.
+int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, double* gq_out) {
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
-    if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    const c5::ImageParams& im = ctx->im;
-    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
-    if (v.no_cells) {  // (nothing but solids: the image does not depend on any cell)
-        if (n_px > 0) C5_HIP(ctx, hipMemsetAsync(out, 0, static_cast<size_t>(n_px) * sizeof(float2), s));
-        return C5_OK;
-    }
-    FrameSlot& fs = ctx->slots[0];
-    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
-    C5_HIP(ctx, ctx->tan_dir.ensure(n_cells * sizeof(double2)));
+    if (rc || v.no_cells) return rc;
+    rc = adjoint_one(ctx, v, false, grad_out, ga_out, gq_out);
+    return rc ? rc : commit_derivative(ctx, "adjoint");
+}
+
+// One tangent over the view: the caller's direction into device order, then one walk (or tangent_resolve over
+// bin_sort_resolve's lists) that writes (tau_dot, I_dot) per pixel.
+int tangent_one(c5_context* ctx, const DerivativeView& v, const double* d_alpha, const double* d_q, float2* out) {
+    C5_HIP(ctx, ctx->tan_dir.ensure(static_cast<size_t>(ctx->n_cells) * sizeof(double2)));
     double2* const dir = ctx->tan_dir.as<double2>();
-    c5::launch_tangent_gather(s, d_alpha, d_q, ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>(), ctx->n_cells, dir);
+    c5::launch_tangent_gather(v.s, d_alpha, d_q, v.perm, ctx->n_cells, dir);
     if (v.bin_sort) {
-        c5::launch_tangent_resolve(s, v.g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, dir, out);
+        c5::launch_tangent_resolve(v.s, v.g, ctx->im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, dir, out);
     } else {
         c5::TangentParams tp{};
         tp.w = v.w;
         tp.dir = dir;
         tp.out = out;
-        c5::launch_tangent_walk(s, tp);
-        fs.head_clean = true;  // (the walk hands every head back cleared)
+        c5::launch_tangent_walk(v.s, tp);
+        ctx->slots[0].head_clean = true;  // (the walk hands every head back cleared)
     }
-    return commit_derivative(ctx, "tangent");
+    return C5_OK;
+}
+
+// nothing but solids: n tangent images do not depend on any cell
+int zero_tangents(c5_context* ctx, const DerivativeView& v, int n, float2* out) {
+    if (out && v.n_px > 0) C5_HIP(ctx, hipMemsetAsync(out, 0, static_cast<size_t>(n) * v.n_px * sizeof(float2), v.s));
+    return C5_OK;
+}
+
+// The tangent: tangent_one on the direction.
+int enqueue_tangent(c5_context* ctx, const double* d_alpha, const double* d_q, float2* out) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    if (v.no_cells) return zero_tangents(ctx, v, 1, out);
+    rc = tangent_one(ctx, v, d_alpha, d_q, out);
+    return rc ? rc : commit_derivative(ctx, "tangent");
 }
 
 // Batches: the chunk width (4 or 8 directions / upstream images per walk; "batch_width").
@@ -1440,154 +1436,134 @@ int batch_width(const c5_context* ctx, int n) {
     return n <= 4 ? 4 : 8;
 }
 
+// directions k0 .. k0 + n_used - 1 of the caller's [n][n_cells] arrays into bat_dirs (ensured by the caller): `width`
+// interleaved pairs per cell in device order
+void gather_chunk(c5_context* ctx, const DerivativeView& v, int width, const double* d_alpha, const double* d_q, int k0, int n_used) {
+    c5::launch_tangent_gather_batch(v.s, width, d_alpha, d_q, v.perm, ctx->n_cells, k0, n_used, ctx->bat_dirs.as<double2>());
+}
+
+// The batched pass 2 over the view's walk: its buffers (Lambda's, and [n_cells][2 width] sums in device order) and its
+// parameters but for the chunk's (grad_out, n_used, keep_entries).
+int adjoint_batch_params(c5_context* ctx, const DerivativeView& v, int width, c5::AdjointBatchParams& ab) {
+    C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
+    C5_HIP(ctx, ctx->bat_grad.ensure(static_cast<size_t>(ctx->n_cells) * 2 * width * sizeof(double)));
+    ab = c5::AdjointBatchParams{};
+    ab.w = v.w;
+    ab.image_px = v.n_px;
+    ab.lambda = ctx->adj_lambda.as<double>();
+    ab.grad = ctx->bat_grad.as<double>();
+    return C5_OK;
+}
+
+// ... and one chunk of it: the sums zeroed, the walk, the permutation into rows k0_out .. of the caller's arrays
+int adjoint_chunk(c5_context* ctx, const DerivativeView& v, int width, const c5::AdjointBatchParams& ab, int k0_out, double* ga_out,
+                  double* gq_out) {
+    C5_HIP(ctx, hipMemsetAsync(ab.grad, 0, static_cast<size_t>(ctx->n_cells) * 2 * width * sizeof(double), v.s));
+    c5::launch_adjoint_walk_batch(v.s, width, ab);
+    c5::launch_adjoint_permute_batch(v.s, width, ab.grad, v.perm, ctx->n_cells, k0_out, ab.n_used, ga_out, gq_out);
+    return C5_OK;
+}
+
 // n directions ([n][n_cells] fp64 each, the caller's order; null: zero) -> out[n][local_rows][res_x]: one per-view setup,
 // then per chunk of up to `width` directions a gather into device order and one walk; the entry heads stay in place
-// between the chunks and the last walk hands them back cleared.  On bin_sort_resolve's lists: tangent_resolve once per
-// direction (the first sorts the lists, the others find them sorted).  A batch of one is the single tangent.
+// between the chunks and the last walk hands them back cleared.  On bin_sort_resolve's lists: tangent_one per direction
+// (the first sorts the lists, the others find them sorted).  A batch of one is the single tangent.
 int enqueue_tangent_batch(c5_context* ctx, int n, const double* d_alpha, const double* d_q, float2* out) {
     if (n == 1) return enqueue_tangent(ctx, d_alpha, d_q, out);
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    const c5::ImageParams& im = ctx->im;
-    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
-    if (v.no_cells) {  // (nothing but solids: the images do not depend on any cell)
-        if (n_px > 0) C5_HIP(ctx, hipMemsetAsync(out, 0, static_cast<size_t>(n) * n_px * sizeof(float2), s));
-        return C5_OK;
-    }
-    FrameSlot& fs = ctx->slots[0];
+    if (v.no_cells) return zero_tangents(ctx, v, n, out);
     const int64_t n_cells = ctx->n_cells;
-    const int32_t* const perm = ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>();
     if (v.bin_sort) {
-        C5_HIP(ctx, ctx->tan_dir.ensure(static_cast<size_t>(n_cells) * sizeof(double2)));
-        double2* const dir = ctx->tan_dir.as<double2>();
-        for (int j = 0; j < n; ++j) {
-            c5::launch_tangent_gather(s, d_alpha ? d_alpha + j * n_cells : nullptr, d_q ? d_q + j * n_cells : nullptr, perm, n_cells, dir);
-            c5::launch_tangent_resolve(s, v.g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, dir,
-                                       out + j * n_px);
-        }
-        return commit_derivative(ctx, "tangent batch");
+        for (int j = 0; j < n && !rc; ++j)
+            rc = tangent_one(ctx, v, d_alpha ? d_alpha + j * n_cells : nullptr, d_q ? d_q + j * n_cells : nullptr,
+                             out + j * v.n_px);
+        return rc ? rc : commit_derivative(ctx, "tangent batch");
     }
     const int width = batch_width(ctx, n);
     C5_HIP(ctx, ctx->bat_dirs.ensure(static_cast<size_t>(n_cells) * width * sizeof(double2)));
     c5::TangentBatchParams tb{};
     tb.w = v.w;
     tb.dirs = ctx->bat_dirs.as<double2>();
-    tb.image_px = n_px;
+    tb.image_px = v.n_px;
     for (int k0 = 0; k0 < n; k0 += width) {
         tb.n_used = std::min(width, n - k0);
-        tb.out = out + k0 * n_px;
+        tb.out = out + k0 * v.n_px;
         tb.keep_entries = k0 + width < n;
-        c5::launch_tangent_gather_batch(s, width, d_alpha, d_q, perm, n_cells, k0, tb.n_used, ctx->bat_dirs.as<double2>());
-        c5::launch_tangent_walk_batch(s, width, tb);
+        gather_chunk(ctx, v, width, d_alpha, d_q, k0, tb.n_used);
+        c5::launch_tangent_walk_batch(v.s, width, tb);
     }
-    fs.head_clean = true;  // (the last chunk's walk hands every head back cleared)
+    ctx->slots[0].head_clean = true;  // (the last chunk's walk hands every head back cleared)
     return commit_derivative(ctx, "tangent batch");
 }
 
 // n upstream images ([n][local_rows][res_x] float2) -> ga_out / gq_out [n][n_cells] in the caller's order: one per-view
 // setup and ONE pass 1 (Lambda does not depend on the weights), then per chunk of up to `width` images the batched pass 2
-// into [n_cells][2 width] and its permutation.  On bin_sort_resolve's lists: adjoint_resolve once per image.  A batch of
-// one is the single adjoint.
+// into [n_cells][2 width] and its permutation.  On bin_sort_resolve's lists: adjoint_one per image.  A batch of one is the
+// single adjoint.
 int enqueue_adjoint_batch(c5_context* ctx, int n, const float2* grad_out, double* ga_out, double* gq_out) {
     if (n == 1) return enqueue_adjoint(ctx, grad_out, ga_out, gq_out);
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc || v.no_cells) return rc;
-    FrameSlot& fs = ctx->slots[0];
-    hipStream_t s = ctx->stream;
-    const c5::ImageParams& im = ctx->im;
-    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
     const int64_t n_cells = ctx->n_cells;
-    const int32_t* const perm = ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>();
     if (v.bin_sort) {
-        C5_HIP(ctx, ctx->adj_grad.ensure(2 * static_cast<size_t>(n_cells) * sizeof(double)));
-        double* const ga_dev = ctx->adj_grad.as<double>();
-        double* const gq_dev = ga_dev + n_cells;
-        for (int j = 0; j < n; ++j) {
-            C5_HIP(ctx, hipMemsetAsync(ga_dev, 0, 2 * static_cast<size_t>(n_cells) * sizeof(double), s));
-            c5::launch_adjoint_resolve(s, v.g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit,
-                                       grad_out + j * n_px, ga_dev, gq_dev);
-            c5::launch_adjoint_permute(s, ga_dev, gq_dev, perm, n_cells, ga_out + j * n_cells, gq_out + j * n_cells);
-        }
-        return commit_derivative(ctx, "adjoint batch");
+        for (int j = 0; j < n && !rc; ++j)
+            rc = adjoint_one(ctx, v, false, grad_out + j * v.n_px, ga_out + j * n_cells, gq_out + j * n_cells);
+        return rc ? rc : commit_derivative(ctx, "adjoint batch");
     }
     const int width = batch_width(ctx, n);
-    const size_t grad_bytes = static_cast<size_t>(n_cells) * 2 * width * sizeof(double);
-    const int64_t padded = ((n_px + 1023) / 1024) * 1024;
-    C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(padded) * sizeof(double)));
-    C5_HIP(ctx, ctx->bat_grad.ensure(grad_bytes));
-    c5::AdjointParams ap{};
-    ap.w = v.w;
-    ap.lambda = ctx->adj_lambda.as<double>();
-    c5::launch_adjoint_walk(s, ap, 1);
-    c5::AdjointBatchParams ab{};
-    ab.w = v.w;
-    ab.image_px = n_px;
-    ab.lambda = ctx->adj_lambda.as<double>();
-    ab.grad = ctx->bat_grad.as<double>();
+    c5::AdjointParams ap;
+    c5::AdjointBatchParams ab;
+    rc = adjoint_params(ctx, v, ap);
+    if (!rc) rc = adjoint_batch_params(ctx, v, width, ab);
+    if (rc) return rc;
+    c5::launch_adjoint_walk(v.s, ap, 1);
     for (int k0 = 0; k0 < n; k0 += width) {
         ab.n_used = std::min(width, n - k0);
-        ab.grad_out = grad_out + k0 * n_px;
+        ab.grad_out = grad_out + k0 * v.n_px;
         ab.keep_entries = k0 + width < n;
-        C5_HIP(ctx, hipMemsetAsync(ab.grad, 0, grad_bytes, s));
-        c5::launch_adjoint_walk_batch(s, width, ab);
-        c5::launch_adjoint_permute_batch(s, width, ab.grad, perm, n_cells, k0, ab.n_used, ga_out, gq_out);
+        rc = adjoint_chunk(ctx, v, width, ab, k0, ga_out, gq_out);
+        if (rc) return rc;
     }
-    fs.head_clean = true;  // (the last chunk's pass 2 hands every head back cleared)
+    ctx->slots[0].head_clean = true;  // (the last chunk's pass 2 hands every head back cleared)
     return commit_derivative(ctx, "adjoint batch");
 }
 
 // The Gauss-Newton product H v = J^T W J v for n directions: one per-view setup, then per chunk of up to `width` directions
 // the gather, pass A (gn_walk_a: the tangent walk that is also the adjoint's pass 1; g = w * J v in fp32 and Lambda), the
 // batched pass 2 on g, and its permutation.  The heads stay in place from pass A to pass B and between the chunks; the
-// last pass B hands them back cleared.  On bin_sort_resolve's lists: tangent_resolve -> gn_weight -> adjoint_resolve per
+// last pass B hands them back cleared.  On bin_sort_resolve's lists: tangent_one -> gn_weight -> adjoint_one per
 // direction.  ha_out / hq_out: either may be null (then that block goes to a spare buffer); jv_out may be null.
 int enqueue_gn_product(c5_context* ctx, int n, const double* d_alpha, const double* d_q, const float2* weight, double* ha_out,
                        double* hq_out, float2* jv_out) {
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    const c5::ImageParams& im = ctx->im;
-    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
-    if (v.no_cells) {  // (nothing but solids: no cell, and the images do not depend on any)
-        if (jv_out && n_px > 0) C5_HIP(ctx, hipMemsetAsync(jv_out, 0, static_cast<size_t>(n) * n_px * sizeof(float2), s));
-        return C5_OK;
-    }
-    FrameSlot& fs = ctx->slots[0];
-    const int64_t n_cells = ctx->n_cells;
-    const int32_t* const perm = ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>();
+    if (v.no_cells) return zero_tangents(ctx, v, n, jv_out);
+    const int64_t n_cells = ctx->n_cells, n_px = v.n_px;
+    const int width = v.bin_sort ? 1 : batch_width(ctx, n);
+    if (!ha_out || !hq_out) C5_HIP(ctx, ctx->gn_spare.ensure(static_cast<size_t>(n_cells) * width * sizeof(double)));
+    double* const spare = ctx->gn_spare.as<double>();
     if (v.bin_sort) {
-        C5_HIP(ctx, ctx->tan_dir.ensure(static_cast<size_t>(n_cells) * sizeof(double2)));
-        C5_HIP(ctx, ctx->adj_grad.ensure(2 * static_cast<size_t>(n_cells) * sizeof(double)));
         C5_HIP(ctx, ctx->gn_g.ensure(2 * static_cast<size_t>(n_px) * sizeof(float2) + 16));
-        if (!ha_out || !hq_out) C5_HIP(ctx, ctx->gn_spare.ensure(static_cast<size_t>(n_cells) * sizeof(double)));
-        double2* const dir = ctx->tan_dir.as<double2>();
-        double* const ga_dev = ctx->adj_grad.as<double>();
-        double* const gq_dev = ga_dev + n_cells;
         float2* const g = ctx->gn_g.as<float2>();
         for (int j = 0; j < n; ++j) {
             float2* const t = jv_out ? jv_out + j * n_px : g + n_px;
-            c5::launch_tangent_gather(s, d_alpha ? d_alpha + j * n_cells : nullptr, d_q ? d_q + j * n_cells : nullptr, perm, n_cells, dir);
-            c5::launch_tangent_resolve(s, v.g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, dir, t);
-            c5::launch_gn_weight(s, t, weight, n_px, 1, g);
-            C5_HIP(ctx, hipMemsetAsync(ga_dev, 0, 2 * static_cast<size_t>(n_cells) * sizeof(double), s));
-            c5::launch_adjoint_resolve(s, v.g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, g, ga_dev, gq_dev);
-            c5::launch_adjoint_permute(s, ga_dev, gq_dev, perm, n_cells, ha_out ? ha_out + j * n_cells : ctx->gn_spare.as<double>(),
-                                       hq_out ? hq_out + j * n_cells : ctx->gn_spare.as<double>());
+            rc = tangent_one(ctx, v, d_alpha ? d_alpha + j * n_cells : nullptr, d_q ? d_q + j * n_cells : nullptr, t);
+            if (rc) return rc;
+            c5::launch_gn_weight(v.s, t, weight, n_px, 1, g);
+            rc = adjoint_one(ctx, v, false, g, ha_out ? ha_out + j * n_cells : spare, hq_out ? hq_out + j * n_cells : spare);
+            if (rc) return rc;
         }
         return commit_derivative(ctx, "gn product");
     }
-    const int width = batch_width(ctx, n);
-    const size_t grad_bytes = static_cast<size_t>(n_cells) * 2 * width * sizeof(double);
-    const int64_t padded = ((n_px + 1023) / 1024) * 1024;
-    C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(padded) * sizeof(double)));
+    c5::AdjointBatchParams ab;
+    rc = adjoint_batch_params(ctx, v, width, ab);
+    if (rc) return rc;
     C5_HIP(ctx, ctx->bat_dirs.ensure(static_cast<size_t>(n_cells) * width * sizeof(double2)));
-    C5_HIP(ctx, ctx->bat_grad.ensure(grad_bytes));
     C5_HIP(ctx, ctx->gn_g.ensure(static_cast<size_t>(width) * n_px * sizeof(float2) + 16));
-    if (!ha_out || !hq_out) C5_HIP(ctx, ctx->gn_spare.ensure(static_cast<size_t>(n_cells) * width * sizeof(double)));
     c5::GnWalkParams ga{};
     ga.w = v.w;
     ga.dirs = ctx->bat_dirs.as<double2>();
@@ -1595,61 +1571,27 @@ int enqueue_gn_product(c5_context* ctx, int n, const double* d_alpha, const doub
     ga.lambda = ctx->adj_lambda.as<double>();
     ga.g = ctx->gn_g.as<float2>();
     ga.image_px = n_px;
-    c5::AdjointBatchParams ab{};
-    ab.w = v.w;
-    ab.grad_out = ctx->gn_g.as<float2>();
-    ab.image_px = n_px;
-    ab.lambda = ctx->adj_lambda.as<double>();
-    ab.grad = ctx->bat_grad.as<double>();
+    ab.grad_out = ga.g;
     for (int k0 = 0; k0 < n; k0 += width) {
         ga.n_used = ab.n_used = std::min(width, n - k0);
         ga.jv_out = jv_out ? jv_out + k0 * n_px : nullptr;
         ab.keep_entries = k0 + width < n;
-        c5::launch_tangent_gather_batch(s, width, d_alpha, d_q, perm, n_cells, k0, ga.n_used, ctx->bat_dirs.as<double2>());
-        c5::launch_gn_walk_a(s, width, ga);
-        C5_HIP(ctx, hipMemsetAsync(ab.grad, 0, grad_bytes, s));
-        c5::launch_adjoint_walk_batch(s, width, ab);
-        c5::launch_adjoint_permute_batch(s, width, ab.grad, perm, n_cells, 0, ab.n_used,
-                                         ha_out ? ha_out + k0 * n_cells : ctx->gn_spare.as<double>(),
-                                         hq_out ? hq_out + k0 * n_cells : ctx->gn_spare.as<double>());
+        gather_chunk(ctx, v, width, d_alpha, d_q, k0, ga.n_used);
+        c5::launch_gn_walk_a(v.s, width, ga);
+        rc = adjoint_chunk(ctx, v, width, ab, 0, ha_out ? ha_out + k0 * n_cells : spare, hq_out ? hq_out + k0 * n_cells : spare);
+        if (rc) return rc;
     }
-    fs.head_clean = true;  // (the last chunk's pass B hands every head back cleared)
+    ctx->slots[0].head_clean = true;  // (the last chunk's pass B hands every head back cleared)
     return commit_derivative(ctx, "gn product");
 }
 
-// diag(J^T W J): the adjoint's two passes with gn_diag_walk as the second (or gn_diag_resolve over bin_sort_resolve's
-// lists), then the permutation into the caller's order.  weight null: ones.
+// diag(J^T W J): adjoint_one with the squared kernels.  weight null: ones.
 int enqueue_gn_diagonal(c5_context* ctx, const float2* weight, double* da_out, double* dq_out) {
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc || v.no_cells) return rc;
-    FrameSlot& fs = ctx->slots[0];
-    hipStream_t s = ctx->stream;
-    const c5::ImageParams& im = ctx->im;
-    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
-    C5_HIP(ctx, ctx->adj_grad.ensure(2 * n_cells * sizeof(double)));
-    double* const da_dev = ctx->adj_grad.as<double>();
-    double* const dq_dev = da_dev + n_cells;
-    C5_HIP(ctx, hipMemsetAsync(da_dev, 0, 2 * n_cells * sizeof(double), s));
-    if (v.bin_sort) {
-        c5::launch_gn_diag_resolve(s, v.g, im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, weight, da_dev,
-                                   dq_dev);
-    } else {
-        const int64_t padded = ((static_cast<int64_t>(im.n_local_rows) * im.res_x + 1023) / 1024) * 1024;
-        C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(padded) * sizeof(double)));
-        c5::AdjointParams ap{};
-        ap.w = v.w;
-        ap.grad_out = weight;
-        ap.lambda = ctx->adj_lambda.as<double>();
-        ap.grad_a = da_dev;
-        ap.grad_q = dq_dev;
-        c5::launch_adjoint_walk(s, ap, 1);
-        c5::launch_gn_diag_walk(s, ap);
-        fs.head_clean = true;  // (gn_diag_walk hands every head back cleared)
-    }
-    c5::launch_adjoint_permute(s, da_dev, dq_dev, ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>(), ctx->n_cells,
-                               da_out, dq_out);
-    return commit_derivative(ctx, "gn diagonal");
+    rc = adjoint_one(ctx, v, true, weight, da_out, dq_out);
+    return rc ? rc : commit_derivative(ctx, "gn diagonal");
 }
 
 // After the stream drained: the failure words of the last adjoint or tangent (as finish_frame treats a frame's).
@@ -1682,6 +1624,70 @@ int finish_adjoint(c5_context* ctx) {
     return C5_OK;
 }
 
+// What the twelve derivative entry points check before anything else, in this order: the context; a batch's size; the
+// call's own pointers (`required_ok`, and `per_cell_ok` where the grid has cells); no c5_render_host_async frame
+// outstanding; and for the host-pointer forms the image, after which the device is bound.
+struct DerivativeCall {
+    const char* name;         // as the messages spell it: "c5_render_tangent_batch" also for its _device form
+    bool host;                // a host-pointer form
+    int n;                    // a batch's size (1: not a batch)
+    const char* batch_of;     // "direction" / "upstream image"
+    bool required_ok, per_cell_ok;
+    const char* pointer_msg;
+    bool refuse_async = true;
+};
+
+int check_derivative(c5_context* ctx, const DerivativeCall& c) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (c.n < 1) return fail(ctx, C5_ERR_INVALID, "a batch needs at least one %s (%d)", c.batch_of, c.n);
+    if (!c.required_ok || (ctx->n_cells > 0 && !c.per_cell_ok)) return fail(ctx, C5_ERR_INVALID, "%s", c.pointer_msg);
+    if (c.refuse_async && ctx->hr_count) return fail(ctx, C5_ERR_STATE, "%s while c5_render_host_async frames are outstanding", c.name);
+    if (!c.host) return C5_OK;
+    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
+    return bind_device(ctx);
+}
+
+// One block of a host-pointer derivative call's staging buffer: uploaded from `src` before the work, downloaded to `dst`
+// after it (either may be null).  dev: its place on the device, or nullptr where the caller gave neither - the enqueue
+// then sees the null pointer the caller passed.
+struct Staged {
+    const void* src;
+    void* dst;
+    size_t bytes;
+    char* dev = nullptr;
+    template <class T>
+    T* as() const { return reinterpret_cast<T*>(dev); }
+};
+
+// The host-pointer form of a derivative: the blocks laid out in deriv_io (256-byte aligned), the uploads on the context's
+// stream, `enqueue` and c5_synchronize - again while the entry pool had to grow (C5_RETRY) - and the downloads.
+template <size_t N, class Enqueue>
+int run_staged(c5_context* ctx, const char* what, Staged (&blocks)[N], Enqueue enqueue) {
+    auto room = [](const Staged& b) { return (b.bytes + 255) / 256 * 256; };
+    size_t total = 0;
+    for (const Staged& b : blocks) total += room(b);
+    C5_HIP(ctx, ctx->deriv_io.ensure(total + 256));
+    char* at = ctx->deriv_io.as<char>();
+    for (Staged& b : blocks) {
+        if (b.src || b.dst) b.dev = at;
+        at += room(b);
+        if (b.src && b.bytes > 0) C5_HIP(ctx, hipMemcpyAsync(b.dev, b.src, b.bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        int rc = enqueue();
+        if (rc) return rc;
+        rc = c5_synchronize(ctx);
+        if (rc == C5_RETRY) continue;
+        if (rc) return rc;
+        for (const Staged& b : blocks)
+            if (b.dst && b.bytes > 0) C5_HIP(ctx, hipMemcpy(b.dst, b.dev, b.bytes, hipMemcpyDeviceToHost));
+        return C5_OK;
+    }
+    return fail(ctx, C5_ERR_STATE, "%s: entry buffer kept overflowing", what);
+}
+
+size_t image_bytes(const c5_context* ctx) { return static_cast<size_t>(ctx->im.n_local_rows) * ctx->im.res_x * 2 * sizeof(float); }
+size_t cells_bytes(const c5_context* ctx) { return static_cast<size_t>(ctx->n_cells) * sizeof(double); }
 }  // namespace
 
 extern "C" {
@@ -1790,8 +1796,8 @@ void c5_destroy(c5_context* ctx) {
     DeviceBuffer* bufs[] = {&ctx->px, &ctx->py, &ctx->pz, &ctx->cell_vert, &ctx->cell_adj, &ctx->alpha,
                             &ctx->q, &ctx->bface, &ctx->xtab, &ctx->ytab, &ctx->out, &ctx->sticky,
                             &ctx->offs64, &ctx->scratch64, &ctx->segs, &ctx->adj_lambda, &ctx->adj_counters,
-                            &ctx->adj_sticky, &ctx->adj_grad, &ctx->adj_perm, &ctx->adj_io, &ctx->tan_dir, &ctx->tan_io,
-                            &ctx->bat_dirs, &ctx->bat_grad, &ctx->bat_io, &ctx->gn_g, &ctx->gn_spare, &ctx->gn_io,
+                            &ctx->adj_sticky, &ctx->adj_grad, &ctx->adj_perm, &ctx->tan_dir,
+                            &ctx->bat_dirs, &ctx->bat_grad, &ctx->gn_g, &ctx->gn_spare, &ctx->deriv_io,
                             &ctx->scal_stats};
     if (ctx->host_sticky) (void)hipHostFree(ctx->host_sticky);
     if (ctx->adj_status) (void)hipHostFree(ctx->adj_status);
@@ -2512,165 +2518,92 @@ int c5_render(c5_context* ctx, float* out_host) {
     return fail(ctx, C5_ERR_STATE, "entry buffer kept overflowing");
 }
 
+// The only derivative entry point that does not refuse while c5_render_host_async frames are outstanding (it never has).
 int c5_render_adjoint_device(c5_context* ctx, const void* grad_out_device, void* grad_alpha_device, void* grad_q_device) {
-    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
-    if (!grad_out_device || (ctx->n_cells > 0 && (!grad_alpha_device || !grad_q_device)))
-        return fail(ctx, C5_ERR_INVALID, "null adjoint pointer");
+    int rc = check_derivative(ctx, {"c5_render_adjoint", false, 1, nullptr, grad_out_device != nullptr,
+                                    grad_alpha_device && grad_q_device, "null adjoint pointer", false});
+    if (rc) return rc;
     return enqueue_adjoint(ctx, static_cast<const float2*>(grad_out_device), static_cast<double*>(grad_alpha_device),
                            static_cast<double*>(grad_q_device));
 }
 
 int c5_render_adjoint(c5_context* ctx, const float* grad_out_host, double* grad_alpha_host, double* grad_q_host) {
-    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
-    if (!grad_out_host || (ctx->n_cells > 0 && (!grad_alpha_host || !grad_q_host)))
-        return fail(ctx, C5_ERR_INVALID, "null adjoint pointer");
-    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_adjoint while c5_render_host_async frames are outstanding");
-    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
-    int rc = bind_device(ctx);
+    int rc = check_derivative(ctx, {"c5_render_adjoint", true, 1, nullptr, grad_out_host != nullptr, grad_alpha_host && grad_q_host,
+                                    "null adjoint pointer"});
     if (rc) return rc;
-    const size_t img_bytes = static_cast<size_t>(ctx->im.n_local_rows) * ctx->im.res_x * 2 * sizeof(float);
-    const size_t img_room = (img_bytes + 255) / 256 * 256;
-    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
-    C5_HIP(ctx, ctx->adj_io.ensure(img_room + 2 * n_cells * sizeof(double) + 16));
-    char* const io = ctx->adj_io.as<char>();
-    double* const ga = reinterpret_cast<double*>(io + img_room);
-    C5_HIP(ctx, hipMemcpyAsync(io, grad_out_host, img_bytes, hipMemcpyHostToDevice, ctx->stream));
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        rc = enqueue_adjoint(ctx, reinterpret_cast<const float2*>(io), ga, ga + n_cells);
-        if (rc) return rc;
-        rc = c5_synchronize(ctx);
-        if (rc == C5_RETRY) continue;
-        if (rc) return rc;
-        if (n_cells > 0) {
-            C5_HIP(ctx, hipMemcpy(grad_alpha_host, ga, n_cells * sizeof(double), hipMemcpyDeviceToHost));
-            C5_HIP(ctx, hipMemcpy(grad_q_host, ga + n_cells, n_cells * sizeof(double), hipMemcpyDeviceToHost));
-        }
-        return C5_OK;
-    }
-    return fail(ctx, C5_ERR_STATE, "adjoint: entry buffer kept overflowing");
+    Staged b[] = {{grad_out_host, nullptr, image_bytes(ctx)},
+                  {nullptr, grad_alpha_host, cells_bytes(ctx)},
+                  {nullptr, grad_q_host, cells_bytes(ctx)}};
+    return run_staged(ctx, "adjoint", b, [&] {
+        return enqueue_adjoint(ctx, b[0].as<const float2>(), b[1].as<double>(), b[2].as<double>());
+    });
 }
 
 int c5_render_tangent_device(c5_context* ctx, const void* d_alpha_dev, const void* d_q_dev, void* out_device) {
-    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
-    if (!out_device) return fail(ctx, C5_ERR_INVALID, "null output pointer");
-    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_tangent while c5_render_host_async frames are outstanding");
+    int rc = check_derivative(ctx, {"c5_render_tangent", false, 1, nullptr, out_device != nullptr, true, "null output pointer"});
+    if (rc) return rc;
     return enqueue_tangent(ctx, static_cast<const double*>(d_alpha_dev), static_cast<const double*>(d_q_dev),
                            static_cast<float2*>(out_device));
 }
 
 int c5_render_tangent(c5_context* ctx, const double* d_alpha_host, const double* d_q_host, float* out_host) {
-    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
-    if (!out_host) return fail(ctx, C5_ERR_INVALID, "null output pointer");
-    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_tangent while c5_render_host_async frames are outstanding");
-    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
-    int rc = bind_device(ctx);
+    int rc = check_derivative(ctx, {"c5_render_tangent", true, 1, nullptr, out_host != nullptr, true, "null output pointer"});
     if (rc) return rc;
-    const size_t img_bytes = static_cast<size_t>(ctx->im.n_local_rows) * ctx->im.res_x * 2 * sizeof(float);
-    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
-    const size_t dir_bytes = n_cells * sizeof(double);
-    C5_HIP(ctx, ctx->tan_io.ensure(2 * dir_bytes + img_bytes + 16));
-    double* const da = ctx->tan_io.as<double>();
-    double* const dq = da + n_cells;
-    float2* const img = reinterpret_cast<float2*>(dq + n_cells);
-    if (d_alpha_host && n_cells > 0) C5_HIP(ctx, hipMemcpyAsync(da, d_alpha_host, dir_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (d_q_host && n_cells > 0) C5_HIP(ctx, hipMemcpyAsync(dq, d_q_host, dir_bytes, hipMemcpyHostToDevice, ctx->stream));
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        rc = enqueue_tangent(ctx, d_alpha_host ? da : nullptr, d_q_host ? dq : nullptr, img);
-        if (rc) return rc;
-        rc = c5_synchronize(ctx);
-        if (rc == C5_RETRY) continue;
-        if (rc) return rc;
-        if (img_bytes > 0) C5_HIP(ctx, hipMemcpy(out_host, img, img_bytes, hipMemcpyDeviceToHost));
-        return C5_OK;
-    }
-    return fail(ctx, C5_ERR_STATE, "tangent: entry buffer kept overflowing");
+    Staged b[] = {{d_alpha_host, nullptr, cells_bytes(ctx)},
+                  {d_q_host, nullptr, cells_bytes(ctx)},
+                  {nullptr, out_host, image_bytes(ctx)}};
+    return run_staged(ctx, "tangent", b, [&] {
+        return enqueue_tangent(ctx, b[0].as<const double>(), b[1].as<const double>(), b[2].as<float2>());
+    });
 }
 
 int c5_render_tangent_batch_device(c5_context* ctx, int n_dirs, const void* d_alpha_dev, const void* d_q_dev, void* out_dev) {
-    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
-    if (n_dirs < 1) return fail(ctx, C5_ERR_INVALID, "a batch needs at least one direction (%d)", n_dirs);
-    if (!out_dev) return fail(ctx, C5_ERR_INVALID, "null output pointer");
-    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_tangent_batch while c5_render_host_async frames are outstanding");
+    int rc = check_derivative(ctx, {"c5_render_tangent_batch", false, n_dirs, "direction", out_dev != nullptr, true,
+                                    "null output pointer"});
+    if (rc) return rc;
     return enqueue_tangent_batch(ctx, n_dirs, static_cast<const double*>(d_alpha_dev), static_cast<const double*>(d_q_dev),
                                  static_cast<float2*>(out_dev));
 }
 
 int c5_render_tangent_batch(c5_context* ctx, int n_dirs, const double* d_alpha_host, const double* d_q_host, float* out_host) {
-    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
-    if (n_dirs < 1) return fail(ctx, C5_ERR_INVALID, "a batch needs at least one direction (%d)", n_dirs);
-    if (!out_host) return fail(ctx, C5_ERR_INVALID, "null output pointer");
-    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_tangent_batch while c5_render_host_async frames are outstanding");
-    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
-    int rc = bind_device(ctx);
+    int rc = check_derivative(ctx, {"c5_render_tangent_batch", true, n_dirs, "direction", out_host != nullptr, true,
+                                    "null output pointer"});
     if (rc) return rc;
-    const size_t img_bytes = static_cast<size_t>(n_dirs) * ctx->im.n_local_rows * ctx->im.res_x * 2 * sizeof(float);
-    const size_t dir_bytes = static_cast<size_t>(n_dirs) * static_cast<size_t>(ctx->n_cells) * sizeof(double);
-    C5_HIP(ctx, ctx->bat_io.ensure(2 * dir_bytes + img_bytes + 16));
-    double* const da = ctx->bat_io.as<double>();
-    double* const dq = reinterpret_cast<double*>(reinterpret_cast<char*>(da) + dir_bytes);
-    float2* const img = reinterpret_cast<float2*>(reinterpret_cast<char*>(dq) + dir_bytes);
-    if (d_alpha_host && dir_bytes > 0) C5_HIP(ctx, hipMemcpyAsync(da, d_alpha_host, dir_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (d_q_host && dir_bytes > 0) C5_HIP(ctx, hipMemcpyAsync(dq, d_q_host, dir_bytes, hipMemcpyHostToDevice, ctx->stream));
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        rc = enqueue_tangent_batch(ctx, n_dirs, d_alpha_host ? da : nullptr, d_q_host ? dq : nullptr, img);
-        if (rc) return rc;
-        rc = c5_synchronize(ctx);
-        if (rc == C5_RETRY) continue;
-        if (rc) return rc;
-        if (img_bytes > 0) C5_HIP(ctx, hipMemcpy(out_host, img, img_bytes, hipMemcpyDeviceToHost));
-        return C5_OK;
-    }
-    return fail(ctx, C5_ERR_STATE, "tangent batch: entry buffer kept overflowing");
+    const size_t dir_bytes = n_dirs * cells_bytes(ctx);
+    Staged b[] = {{d_alpha_host, nullptr, dir_bytes},
+                  {d_q_host, nullptr, dir_bytes},
+                  {nullptr, out_host, n_dirs * image_bytes(ctx)}};
+    return run_staged(ctx, "tangent batch", b, [&] {
+        return enqueue_tangent_batch(ctx, n_dirs, b[0].as<const double>(), b[1].as<const double>(), b[2].as<float2>());
+    });
 }
 
 int c5_render_adjoint_batch_device(c5_context* ctx, int n_imgs, const void* grad_out_dev, void* grad_alpha_dev, void* grad_q_dev) {
-    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
-    if (n_imgs < 1) return fail(ctx, C5_ERR_INVALID, "a batch needs at least one upstream image (%d)", n_imgs);
-    if (!grad_out_dev || (ctx->n_cells > 0 && (!grad_alpha_dev || !grad_q_dev)))
-        return fail(ctx, C5_ERR_INVALID, "null adjoint pointer");
-    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_adjoint_batch while c5_render_host_async frames are outstanding");
+    int rc = check_derivative(ctx, {"c5_render_adjoint_batch", false, n_imgs, "upstream image", grad_out_dev != nullptr,
+                                    grad_alpha_dev && grad_q_dev, "null adjoint pointer"});
+    if (rc) return rc;
     return enqueue_adjoint_batch(ctx, n_imgs, static_cast<const float2*>(grad_out_dev), static_cast<double*>(grad_alpha_dev),
                                  static_cast<double*>(grad_q_dev));
 }
 
 int c5_render_adjoint_batch(c5_context* ctx, int n_imgs, const float* grad_out_host, double* grad_alpha_host, double* grad_q_host) {
-    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
-    if (n_imgs < 1) return fail(ctx, C5_ERR_INVALID, "a batch needs at least one upstream image (%d)", n_imgs);
-    if (!grad_out_host || (ctx->n_cells > 0 && (!grad_alpha_host || !grad_q_host)))
-        return fail(ctx, C5_ERR_INVALID, "null adjoint pointer");
-    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_adjoint_batch while c5_render_host_async frames are outstanding");
-    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
-    int rc = bind_device(ctx);
+    int rc = check_derivative(ctx, {"c5_render_adjoint_batch", true, n_imgs, "upstream image", grad_out_host != nullptr,
+                                    grad_alpha_host && grad_q_host, "null adjoint pointer"});
     if (rc) return rc;
-    const size_t img_bytes = static_cast<size_t>(n_imgs) * ctx->im.n_local_rows * ctx->im.res_x * 2 * sizeof(float);
-    const size_t img_room = (img_bytes + 255) / 256 * 256;
-    const size_t grad_bytes = static_cast<size_t>(n_imgs) * static_cast<size_t>(ctx->n_cells) * sizeof(double);
-    C5_HIP(ctx, ctx->bat_io.ensure(img_room + 2 * grad_bytes + 16));
-    char* const io = ctx->bat_io.as<char>();
-    double* const ga = reinterpret_cast<double*>(io + img_room);
-    double* const gq = reinterpret_cast<double*>(io + img_room + grad_bytes);
-    C5_HIP(ctx, hipMemcpyAsync(io, grad_out_host, img_bytes, hipMemcpyHostToDevice, ctx->stream));
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        rc = enqueue_adjoint_batch(ctx, n_imgs, reinterpret_cast<const float2*>(io), ga, gq);
-        if (rc) return rc;
-        rc = c5_synchronize(ctx);
-        if (rc == C5_RETRY) continue;
-        if (rc) return rc;
-        if (grad_bytes > 0) {
-            C5_HIP(ctx, hipMemcpy(grad_alpha_host, ga, grad_bytes, hipMemcpyDeviceToHost));
-            C5_HIP(ctx, hipMemcpy(grad_q_host, gq, grad_bytes, hipMemcpyDeviceToHost));
-        }
-        return C5_OK;
-    }
-    return fail(ctx, C5_ERR_STATE, "adjoint batch: entry buffer kept overflowing");
+    const size_t grad_bytes = n_imgs * cells_bytes(ctx);
+    Staged b[] = {{grad_out_host, nullptr, n_imgs * image_bytes(ctx)},
+                  {nullptr, grad_alpha_host, grad_bytes},
+                  {nullptr, grad_q_host, grad_bytes}};
+    return run_staged(ctx, "adjoint batch", b, [&] {
+        return enqueue_adjoint_batch(ctx, n_imgs, b[0].as<const float2>(), b[1].as<double>(), b[2].as<double>());
+    });
 }
 
 int c5_render_gn_product_device(c5_context* ctx, int n_dirs, const void* d_alpha_dev, const void* d_q_dev, const void* weight_dev,
                                 void* h_alpha_dev, void* h_q_dev, void* jv_out_dev) {
-    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
-    if (n_dirs < 1) return fail(ctx, C5_ERR_INVALID, "a batch needs at least one direction (%d)", n_dirs);
-    if (!h_alpha_dev && !h_q_dev) return fail(ctx, C5_ERR_INVALID, "null output pointers: give h_alpha, h_q or both");
-    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_gn_product while c5_render_host_async frames are outstanding");
+    int rc = check_derivative(ctx, {"c5_render_gn_product", false, n_dirs, "direction", h_alpha_dev || h_q_dev, true,
+                                    "null output pointers: give h_alpha, h_q or both"});
+    if (rc) return rc;
     return enqueue_gn_product(ctx, n_dirs, static_cast<const double*>(d_alpha_dev), static_cast<const double*>(d_q_dev),
                               static_cast<const float2*>(weight_dev), static_cast<double*>(h_alpha_dev), static_cast<double*>(h_q_dev),
                               static_cast<float2*>(jv_out_dev));
@@ -2678,78 +2611,40 @@ int c5_render_gn_product_device(c5_context* ctx, int n_dirs, const void* d_alpha
 
 int c5_render_gn_product(c5_context* ctx, int n_dirs, const double* d_alpha_host, const double* d_q_host, const float* weight_host,
                          double* h_alpha_host, double* h_q_host, float* jv_out_host) {
-    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
-    if (n_dirs < 1) return fail(ctx, C5_ERR_INVALID, "a batch needs at least one direction (%d)", n_dirs);
-    if (!h_alpha_host && !h_q_host) return fail(ctx, C5_ERR_INVALID, "null output pointers: give h_alpha, h_q or both");
-    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_gn_product while c5_render_host_async frames are outstanding");
-    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
-    int rc = bind_device(ctx);
+    int rc = check_derivative(ctx, {"c5_render_gn_product", true, n_dirs, "direction", h_alpha_host || h_q_host, true,
+                                    "null output pointers: give h_alpha, h_q or both"});
     if (rc) return rc;
-    const size_t w_bytes = static_cast<size_t>(ctx->im.n_local_rows) * ctx->im.res_x * 2 * sizeof(float);
-    const size_t w_room = (w_bytes + 255) / 256 * 256;
-    const size_t jv_room = (static_cast<size_t>(n_dirs) * w_bytes + 255) / 256 * 256;
-    const size_t dir_bytes = static_cast<size_t>(n_dirs) * static_cast<size_t>(ctx->n_cells) * sizeof(double);
-    C5_HIP(ctx, ctx->gn_io.ensure(w_room + jv_room + 4 * dir_bytes + 16));
-    char* const io = ctx->gn_io.as<char>();
-    float2* const w = reinterpret_cast<float2*>(io);
-    float2* const jv = reinterpret_cast<float2*>(io + w_room);
-    double* const da = reinterpret_cast<double*>(io + w_room + jv_room);
-    double* const dq = reinterpret_cast<double*>(io + w_room + jv_room + dir_bytes);
-    double* const ha = reinterpret_cast<double*>(io + w_room + jv_room + 2 * dir_bytes);
-    double* const hq = reinterpret_cast<double*>(io + w_room + jv_room + 3 * dir_bytes);
-    if (weight_host && w_bytes > 0) C5_HIP(ctx, hipMemcpyAsync(w, weight_host, w_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (d_alpha_host && dir_bytes > 0) C5_HIP(ctx, hipMemcpyAsync(da, d_alpha_host, dir_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (d_q_host && dir_bytes > 0) C5_HIP(ctx, hipMemcpyAsync(dq, d_q_host, dir_bytes, hipMemcpyHostToDevice, ctx->stream));
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        rc = enqueue_gn_product(ctx, n_dirs, d_alpha_host ? da : nullptr, d_q_host ? dq : nullptr, weight_host ? w : nullptr,
-                                h_alpha_host ? ha : nullptr, h_q_host ? hq : nullptr, jv_out_host ? jv : nullptr);
-        if (rc) return rc;
-        rc = c5_synchronize(ctx);
-        if (rc == C5_RETRY) continue;
-        if (rc) return rc;
-        if (h_alpha_host && dir_bytes > 0) C5_HIP(ctx, hipMemcpy(h_alpha_host, ha, dir_bytes, hipMemcpyDeviceToHost));
-        if (h_q_host && dir_bytes > 0) C5_HIP(ctx, hipMemcpy(h_q_host, hq, dir_bytes, hipMemcpyDeviceToHost));
-        if (jv_out_host && w_bytes > 0) C5_HIP(ctx, hipMemcpy(jv_out_host, jv, static_cast<size_t>(n_dirs) * w_bytes, hipMemcpyDeviceToHost));
-        return C5_OK;
-    }
-    return fail(ctx, C5_ERR_STATE, "gn product: entry buffer kept overflowing");
+    const size_t dir_bytes = n_dirs * cells_bytes(ctx);
+    Staged b[] = {{weight_host, nullptr, image_bytes(ctx)},
+                  {d_alpha_host, nullptr, dir_bytes},
+                  {d_q_host, nullptr, dir_bytes},
+                  {nullptr, h_alpha_host, dir_bytes},
+                  {nullptr, h_q_host, dir_bytes},
+                  {nullptr, jv_out_host, n_dirs * image_bytes(ctx)}};
+    return run_staged(ctx, "gn product", b, [&] {
+        return enqueue_gn_product(ctx, n_dirs, b[1].as<const double>(), b[2].as<const double>(), b[0].as<const float2>(),
+                                  b[3].as<double>(), b[4].as<double>(), b[5].as<float2>());
+    });
 }
 
 int c5_render_gn_diagonal_device(c5_context* ctx, const void* weight_dev, void* diag_alpha_dev, void* diag_q_dev) {
-    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
-    if (ctx->n_cells > 0 && (!diag_alpha_dev || !diag_q_dev)) return fail(ctx, C5_ERR_INVALID, "null diagonal pointer");
-    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_gn_diagonal while c5_render_host_async frames are outstanding");
+    int rc = check_derivative(ctx, {"c5_render_gn_diagonal", false, 1, nullptr, true, diag_alpha_dev && diag_q_dev,
+                                    "null diagonal pointer"});
+    if (rc) return rc;
     return enqueue_gn_diagonal(ctx, static_cast<const float2*>(weight_dev), static_cast<double*>(diag_alpha_dev),
                                static_cast<double*>(diag_q_dev));
 }
 
 int c5_render_gn_diagonal(c5_context* ctx, const float* weight_host, double* diag_alpha_host, double* diag_q_host) {
-    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
-    if (ctx->n_cells > 0 && (!diag_alpha_host || !diag_q_host)) return fail(ctx, C5_ERR_INVALID, "null diagonal pointer");
-    if (ctx->hr_count) return fail(ctx, C5_ERR_STATE, "c5_render_gn_diagonal while c5_render_host_async frames are outstanding");
-    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
-    int rc = bind_device(ctx);
+    int rc = check_derivative(ctx, {"c5_render_gn_diagonal", true, 1, nullptr, true, diag_alpha_host && diag_q_host,
+                                    "null diagonal pointer"});
     if (rc) return rc;
-    const size_t w_bytes = static_cast<size_t>(ctx->im.n_local_rows) * ctx->im.res_x * 2 * sizeof(float);
-    const size_t w_room = (w_bytes + 255) / 256 * 256;
-    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
-    C5_HIP(ctx, ctx->gn_io.ensure(w_room + 2 * n_cells * sizeof(double) + 16));
-    char* const io = ctx->gn_io.as<char>();
-    double* const da = reinterpret_cast<double*>(io + w_room);
-    if (weight_host && w_bytes > 0) C5_HIP(ctx, hipMemcpyAsync(io, weight_host, w_bytes, hipMemcpyHostToDevice, ctx->stream));
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        rc = enqueue_gn_diagonal(ctx, weight_host ? reinterpret_cast<const float2*>(io) : nullptr, da, da + n_cells);
-        if (rc) return rc;
-        rc = c5_synchronize(ctx);
-        if (rc == C5_RETRY) continue;
-        if (rc) return rc;
-        if (n_cells > 0) {
-            C5_HIP(ctx, hipMemcpy(diag_alpha_host, da, n_cells * sizeof(double), hipMemcpyDeviceToHost));
-            C5_HIP(ctx, hipMemcpy(diag_q_host, da + n_cells, n_cells * sizeof(double), hipMemcpyDeviceToHost));
-        }
-        return C5_OK;
-    }
-    return fail(ctx, C5_ERR_STATE, "gn diagonal: entry buffer kept overflowing");
+    Staged b[] = {{weight_host, nullptr, image_bytes(ctx)},
+                  {nullptr, diag_alpha_host, cells_bytes(ctx)},
+                  {nullptr, diag_q_host, cells_bytes(ctx)}};
+    return run_staged(ctx, "gn diagonal", b, [&] {
+        return enqueue_gn_diagonal(ctx, b[0].as<const float2>(), b[1].as<double>(), b[2].as<double>());
+    });
 }
 
 namespace {
