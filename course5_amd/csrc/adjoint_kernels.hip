@@ -119,6 +119,18 @@ __device__ __forceinline__ double dalpha_bracket_series(double x) {
     return fma(p, x, -0.5);
 }
 
+// Lambda's running sum, the same in every kernel that sums or re-sums it (pass 1 and pass 2 must agree to the bit).  A
+// segment of optical depth beyond kLambdaCap counts as kLambdaCap: T = exp(-(Lambda - Lambda_k)) is 0 behind such a
+// segment either way (exp_nonpositive is 0 below -746), and Lambda keeps the size of what can still be seen.  With
+// alpha = 1e9 a single chord is worth 1e7, and Lambda - Lambda_k carried Lambda's rounding - 1e7 x 2^-53 per term, 2e-8
+// of T and of every gradient seen through it - into the segments in front of that cell (tests/derivative_fuzz.py).
+constexpr double kLambdaCap = 1024.0;
+__device__ __forceinline__ double lambda_add(double lam, double a, double dz) {
+    // (rounding is monotone: below the cap this is the fused sum to the bit; a NaN alpha stays a NaN)
+    const double sum = fma(a, dz, lam), capped = lam + kLambdaCap;
+    return capped < sum ? capped : sum;
+}
+
 // The terms of one active segment: d I / d Q and (unclamped) d I / d alpha, and I_k from I_{k-1}.  T: transmittance to the
 // viewer; E: exp(-a dz).
 struct SegmentTerms {
@@ -305,12 +317,12 @@ __device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A) {
             if (is_segment(dz)) {
                 const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
                 if (PASS == 1) {
-                    if (a != 0.0) lam = fma(a, dz, lam);
+                    if (a != 0.0) lam = lambda_add(lam, a, dz);
                 } else {
                     emit = true;
                     ga = g_tau * (SQUARED ? dz * dz : dz);  // d tau / d alpha (line.cpp:189: raw alpha, every segment)
                     if (a != 0.0) {
-                        lam = fma(a, dz, lam);  // (as in pass 1: Lambda_n == Lambda bit for bit, Lambda - Lambda_k >= 0)
+                        lam = lambda_add(lam, a, dz);  // (as in pass 1: Lambda_n == Lambda bit for bit, Lambda - Lambda_k >= 0)
                         const double T = exp_nonpositive(fmin(lam - lam_total, 0.0));
                         const double E = exp_nonpositive(-a * dz);
                         const SegmentTerms t = segment_terms(a, q, dz, E, T, I);
@@ -354,13 +366,14 @@ size_t adjoint_segment_bytes() { return sizeof(AdjSegment); }
 namespace adj {
 
 // The reference's Shell sort of a pixel's list by descending z_hi (line.cpp:138), as resolve_pixels (exact_kernels.hip)
-// runs it.
+// runs it - with one addition: segments of EQUAL depth (interpenetrating components) are ordered by cell, so that a pixel's
+// list, which bin_fill's atomics leave in another order every call, is the same list for every derivative call.
 __device__ __forceinline__ void sort_segments(AdjSegment* list, int n) {
     for (int gap = n / 2; gap > 0; gap = (gap == 2) ? 1 : static_cast<int>(gap / 2.2)) {
         for (int i = gap; i < n; ++i) {
             const AdjSegment t = list[i];
             int j = i;
-            while (j >= gap && list[j - gap].z_hi < t.z_hi) {
+            while (j >= gap && (list[j - gap].z_hi < t.z_hi || (list[j - gap].z_hi == t.z_hi && list[j - gap].cell < t.cell))) {
                 list[j] = list[j - gap];
                 j -= gap;
             }
@@ -404,7 +417,7 @@ __device__ __forceinline__ void adjoint_resolve_body(const GridView& g, const Im
         sort_segments(list, n);
         for (int i = n - 1; i >= 0; --i) {  // Lambda, in the order the loop below runs
             const ClampedAlpha c = clamp_alpha(g.alpha[list[i].cell], alpha_limit);
-            if (c.active) lam_total = fma(c.a, list[i].dz, lam_total);
+            if (c.active) lam_total = lambda_add(lam_total, c.a, list[i].dz);
         }
     }
     double lam = 0.0, I = 0.0;
@@ -421,7 +434,7 @@ __device__ __forceinline__ void adjoint_resolve_body(const GridView& g, const Im
             const double a = ca.a;
             ga = g_tau * (SQUARED ? dz * dz : dz);
             if (ca.active) {
-                lam = fma(a, dz, lam);
+                lam = lambda_add(lam, a, dz);
                 const double T = exp(fmin(lam - lam_total, 0.0));
                 const double E = exp(-a * dz);
                 const SegmentTerms t = segment_terms(a, q, dz, E, T, I);
@@ -604,7 +617,7 @@ __device__ __forceinline__ void tangent_batch_body(const Params& A) {
 #pragma unroll
             for (int j = 0; j < KC; ++j) tau_dot[j] = fma(dz, d[j].a, tau_dot[j]);  // d tau / d alpha (raw alpha)
             if (a != 0.0) {
-                if (kGn) lam = fma(a, dz, lam);  // (adjoint_walk<1>: pass B's running Lambda_k ends on this to the bit)
+                if (kGn) lam = lambda_add(lam, a, dz);  // (adjoint_walk<1>: pass B's running Lambda_k ends on this to the bit)
                 // tangent_step, its direction-free part once: segment_terms at T = 1, E
                 const double E = exp_nonpositive(-a * dz);
                 const SegmentTerms t = segment_terms(a, q, dz, E, 1.0, I);
@@ -709,7 +722,7 @@ __global__ __launch_bounds__(64) void adjoint_walk_batch(AdjointBatchParams A) {
                 }
                 emit = true;
                 if (a != 0.0) {
-                    lam = fma(a, dz, lam);
+                    lam = lambda_add(lam, a, dz);
                     const double T = exp_nonpositive(fmin(lam - lam_total, 0.0));
                     const double E = exp_nonpositive(-a * dz);
                     const SegmentTerms t = segment_terms(a, q, dz, E, T, I);

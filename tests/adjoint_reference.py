@@ -8,6 +8,13 @@ the segment nearest the viewer.  Number them k = 1..n in processing order (row n
     dtau/dalpha_k = dz_k, dI/dQ_k = T_k (1 - E_k) / a_k, dI/dalpha_k = T_k [Q_k (dz_k E_k / a_k - (1 - E_k) / a_k^2) - dz_k E_k I_{k-1}]
 (dI/d. = 0 for an inactive segment, dI/dalpha = 0 for a clamped one).
 
+SCALE and CHORD SENSITIVITY.  Beside a result the restatements can return two bounds per element (with_scale).  Its scale:
+the same sum with every contribution replaced by its absolute value (|g_tau| dz, |g_I| T s, |g_I| T (|B| + dz E I_{k-1})):
+what rounding can do to it.  Its chord sensitivity, sum_k F_k |contribution_k| / dz_k: what an error of the chords can do
+(a contribution is close to proportional to its chord).  F_k = max(1, |gx| + |gy|) over the two faces the chord runs
+between, z = c + gx x + gy y: the depth of a face almost parallel to the rays is known that much worse than its
+coordinates, to whoever evaluates it (segment_lists(with_slope=True)).
+
 Whole images take their segment lists from segment_lists, the reference's binning and pairing restated in numpy: the port
 oracle's probes give the same lists (tests/test_adjoint_cpu.py checks them pixel by pixel) but re-bin the grid once per
 probed pixel, too slow for every pixel of an image.
@@ -98,11 +105,12 @@ def rotate(xyz, rots):
 _FACES = ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3))  # plane.cpp:30-37
 
 
-def segment_lists(xyz, cells, rots, res_x, res_y, bounds):
+def segment_lists(xyz, cells, rots, res_x, res_y, bounds, with_slope: bool = False):
     """Every pixel's segments, as the reference bins and pairs them (plane.cpp:184-192, line.cpp:99-138): a cell whose
     projection holds the pixel centre (two covering faces; four: two pairs in face order) gives {cell, z_hi, dz}.
     Returns (pixel, cell, z_hi, dz) arrays sorted by pixel and then by ASCENDING z_hi - the order the recurrence runs
-    in (line.cpp:206); pixel = row * res_x + col over the full image."""
+    in (line.cpp:206); pixel = row * res_x + col over the full image.  with_slope: a fifth array, the larger |dz/dx| + |dz/dy|
+    of the segment's two faces."""
     P = rotate(xyz, rots)[np.asarray(cells).reshape(-1, 4)]  # [C, 4, 3]
     b = np.asarray(bounds, dtype=np.float64)
     sx, sy = (b[0] - b[1]) / (res_x - 1.0), (b[2] - b[3]) / (res_y - 1.0)
@@ -122,6 +130,7 @@ def segment_lists(xyz, cells, rots, res_x, res_y, bounds):
     x, y = X[ii], Y[jj]
     cover = np.zeros((len(cid), 4), dtype=bool)
     zf = np.zeros((len(cid), 4))
+    sf = np.zeros((len(cid), 4))
     for f, (ia, ib, ic) in enumerate(_FACES):
         A, B, Cc = P[cid, ia], P[cid, ib], P[cid, ic]
         e0 = (B[:, 0] - A[:, 0]) * (y - A[:, 1]) - (B[:, 1] - A[:, 1]) * (x - A[:, 0])
@@ -134,46 +143,75 @@ def segment_lists(xyz, cells, rots, res_x, res_y, bounds):
         m = (B[:, 0] - A[:, 0]) * (Cc[:, 1] - A[:, 1]) - (Cc[:, 0] - A[:, 0]) * (B[:, 1] - A[:, 1])
         with np.errstate(divide="ignore", invalid="ignore"):
             zf[:, f] = ((y - A[:, 1]) * Aa - (x - A[:, 0]) * Bb) / m + A[:, 2]
+            sf[:, f] = (np.abs(Aa) + np.abs(Bb)) / np.abs(m)
     n_cov = cover.sum(1)
     out = []
     for want in (2, 4):
         sel = n_cov == want
         order = np.argsort(~cover[sel], axis=1, kind="stable")  # covering faces first, in face order
         z = np.take_along_axis(zf[sel], order, axis=1)
+        sl = np.take_along_axis(sf[sel], order, axis=1)
         for k in range(want // 2):
             za, zb = z[:, 2 * k], z[:, 2 * k + 1]
             zh = np.maximum(za, zb)
-            out.append((jj[sel] * res_x + ii[sel], cid[sel], zh, zh - np.minimum(za, zb)))
-    pix, cell, zh, dz = (np.concatenate([o[k] for o in out]) for k in range(4))
+            out.append((jj[sel] * res_x + ii[sel], cid[sel], zh, zh - np.minimum(za, zb), np.maximum(sl[:, 2 * k], sl[:, 2 * k + 1])))
+    pix, cell, zh, dz, slope = (np.concatenate([o[k] for o in out]) for k in range(5))
     keep = dz > 0
-    pix, cell, zh, dz = pix[keep], cell[keep], zh[keep], dz[keep]
+    pix, cell, zh, dz, slope = pix[keep], cell[keep], zh[keep], dz[keep], slope[keep]
     o = np.lexsort((zh, pix))
-    return pix[o], cell[o], zh[o], dz[o]
+    return (pix[o], cell[o], zh[o], dz[o], slope[o]) if with_slope else (pix[o], cell[o], zh[o], dz[o])
 
 
-def image_gradients(xyz, cells, alpha, q, rots, res_x, res_y, bounds, weights, limit: float = 2.5, rows=None, skip=None):
-    """The helper over whole images, vectorised over the pixels.  weights: [len(rows), res_x, 2] (g_tau, g_I) of the
-    global rows `rows` (default: all); skip: optional bool [len(rows), res_x], True = the pixel contributes nothing
-    (solid).  Returns (grad_alpha, grad_q, tau, I) with tau / I the fp64 images of those rows."""
+def _transmittance(a, D):
+    """T_k = exp(-sum_{j > k} a_j dz_j) over [pixel, k] matrices, the sum taken from the viewer's end (k = M - 1) in
+    double-double: exp turns an error of its argument u into a relative error of that size, and u is not small where it
+    matters (a cell seen through an optical depth of 500 has all its terms at e^-500: 2^-53 u from the rounding of the
+    products a dz alone would be 500 x 2^-53 of that cell's gradient).  As Lambda - Lambda_k it would carry Lambda's
+    rounding into the segments near the viewer as well."""
+    def split(v):
+        c = 134217729.0 * v
+        hi = c - (c - v)
+        return hi, v - hi
+
+    p = a * D
+    ah, al = split(a)
+    dh, dl = split(D)
+    e = ((ah * dh - p) + ah * dl + al * dh) + al * dl  # a dz = p + e exactly (Dekker)
+    hi = np.zeros(len(a))
+    lo = np.zeros(len(a))
+    T = np.ones_like(D)
+    for k in range(D.shape[1] - 1, -1, -1):
+        T[:, k] = np.exp(-hi) * np.exp(-lo)
+        s = hi + p[:, k]
+        b = s - hi
+        lo = lo + ((hi - (s - b)) + (p[:, k] - b)) + e[:, k]
+        hi = s + lo
+        lo = lo - (hi - s)
+    return T
+
+
+def ray_matrices(xyz, cells, alpha, q, rots, res_x, res_y, bounds, limit: float = 2.5, rows=None):
+    """The per-segment quantities of the rays of the global rows `rows` (default: all) as [pixel, k] matrices, k the
+    processing order (deepest first), pixel = local row * res_x + col.  A dict: C cell (-1: no segment), D dz, valid,
+    a_raw, Q, active, clamped, E, S = (1 - E) / a, B = Q (dz E / a - (1 - E) / a^2) (by its series below a dz = 1/8),
+    T, I_prev, F (module docstring), abs_da, sens_a, sens_q, and per pixel I and tau.  What image_gradients, tangent_reference.image_tangent and
+    gn_reference.segment_terms are built from."""
     rows = np.arange(res_y) if rows is None else np.asarray(rows)
     alpha, q = np.asarray(alpha, np.float64), np.asarray(q, np.float64)
-    pix, cell, _zh, dz = segment_lists(xyz, cells, rots, res_x, res_y, bounds)
+    pix, cell, _zh, dz, slope = segment_lists(xyz, cells, rots, res_x, res_y, bounds, with_slope=True)
     row_slot = np.full(res_y, -1)
     row_slot[rows] = np.arange(len(rows))
     lp = row_slot[pix // res_x] * res_x + pix % res_x
     sel = row_slot[pix // res_x] >= 0
-    lp, cell, dz = lp[sel], cell[sel], dz[sel]
+    lp, cell, dz, slope = lp[sel], cell[sel], dz[sel], slope[sel]
     n_px = len(rows) * res_x
-    w = np.asarray(weights, np.float64).reshape(n_px, 2).copy()
-    if skip is not None:
-        w[np.asarray(skip).reshape(-1)] = 0.0
-    # [pixel, k] matrices, k = processing order (deepest first)
     starts = np.searchsorted(lp, np.arange(n_px))
     k = np.arange(len(lp)) - starts[lp]
     M = int(k.max()) + 1 if len(k) else 1
     C = np.full((n_px, M), -1)
     D = np.zeros((n_px, M))
-    C[lp, k], D[lp, k] = cell, dz
+    F = np.ones((n_px, M))
+    C[lp, k], D[lp, k], F[lp, k] = cell, dz, np.maximum(1.0, slope)
     valid = C >= 0
     a_raw = np.where(valid, alpha[np.maximum(C, 0)], 0.0)
     Q = np.where(valid, q[np.maximum(C, 0)], 0.0)
@@ -181,24 +219,62 @@ def image_gradients(xyz, cells, alpha, q, rots, res_x, res_y, bounds, weights, l
     active = valid & ~(a < EPS)
     x = np.where(active, a * D, 0.0)
     E = np.exp(-x)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        S_over_q = np.where(active, -np.expm1(-x) / np.where(active, a, 1.0), 0.0)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        S = np.where(active, -np.expm1(-x) / np.where(active, a, 1.0), 0.0)
         ser = sum((-1.0) ** (m + 1) * (m + 1) / math.factorial(m + 2) * x ** m for m in range(14))
         direct = (x * E + np.expm1(-x)) / np.where(x > 0, x * x, 1.0)
-    br = Q * D * D * np.where(x < 0.125, ser, direct)
-    lam = np.cumsum(x, axis=1)
-    T = np.exp(-(lam[:, -1:] - lam))
+    B = Q * D * D * np.where(x < 0.125, ser, direct)
+    T = _transmittance(np.where(active, a, 0.0), D)
+    a_eff = np.where(active, a, 0.0)
     I_prev = np.zeros_like(D)
     I = np.zeros(n_px)
     for j in range(M):
         I_prev[:, j] = I
-        I = np.where(active[:, j], E[:, j] * I + Q[:, j] * S_over_q[:, j], I)
+        I = np.where(active[:, j], E[:, j] * I + Q[:, j] * S[:, j], I)
     tau = (np.where(valid, D * a_raw, 0.0)).sum(1)
-    dI_dq = np.where(active, T * S_over_q, 0.0)
-    dI_da = np.where(active & ~(a_raw > limit), T * (br - D * E * I_prev), 0.0)
+    moves = active & ~(a_raw > limit)
+    abs_da = np.where(moves, T * (np.abs(B) + D * E * np.abs(I_prev)), 0.0)
+    # chord sensitivities of a segment's dI/dQ and dI/dalpha (module docstring): F |term| / dz
+    F_dz = np.where(valid, F / np.where(valid, D, 1.0), 0.0)
+    sens_q = np.where(active, T * S, 0.0) * F_dz
+    sens_a = np.where(moves, np.abs(T * (B - D * E * I_prev)), 0.0) * F_dz
+    return dict(C=C, D=D, F=F, F_dz=F_dz, valid=valid, a_raw=a_raw, a=a_eff, Q=Q, active=active, clamped=a_raw > limit, E=E, S=S,
+                B=B, T=T, I_prev=I_prev, I=I, tau=tau, abs_da=abs_da, sens_a=sens_a, sens_q=sens_q, n_px=n_px,
+                shape=(len(rows), res_x))
+
+
+def image_gradients(xyz, cells, alpha, q, rots, res_x, res_y, bounds, weights, limit: float = 2.5, rows=None, skip=None,
+                    with_scale: bool = False):
+    """The helper over whole images, vectorised over the pixels.  weights: [len(rows), res_x, 2] (g_tau, g_I) of the
+    global rows `rows` (default: all); skip: optional bool [len(rows), res_x], True = the pixel contributes nothing
+    (solid).  Returns (grad_alpha, grad_q, tau, I) with tau / I the fp64 images of those rows; with_scale: and
+    gradients_of's dict."""
+    m = ray_matrices(xyz, cells, alpha, q, rots, res_x, res_y, bounds, limit, rows)
+    return gradients_of(m, len(np.asarray(alpha)), weights, skip, with_scale)
+
+
+def gradients_of(m, n_cells: int, weights, skip=None, with_scale: bool = False):
+    """image_gradients from ray_matrices' dict (one set of matrices serves many upstream images).
+
+    with_scale: also a dict of per-cell bounds on what rounding can do to each gradient: scale_alpha / scale_q, the same
+    sums with every contribution replaced by its absolute value (|g_tau| dz, |g_I| T s, |g_I| T (|B| + dz E I_{k-1})),
+    and sens_alpha / sens_q, the chord sensitivity (module docstring)."""
+    C, D, valid, active, E, T = m["C"], m["D"], m["valid"], m["active"], m["E"], m["T"]
+    w = np.asarray(weights, np.float64).reshape(m["n_px"], 2).copy()
+    if skip is not None:
+        w[np.asarray(skip).reshape(-1)] = 0.0
+    moves = active & ~m["clamped"]
+    dI_dq = np.where(active, T * m["S"], 0.0)
+    dI_da = np.where(moves, T * (m["B"] - D * E * m["I_prev"]), 0.0)
     g_tau, g_I = w[:, :1], w[:, 1:]
-    ga = np.zeros(len(alpha))
-    gq = np.zeros(len(alpha))
+    ga = np.zeros(n_cells)
+    gq = np.zeros(n_cells)
     np.add.at(ga, C[valid], (g_tau * D + g_I * dI_da)[valid])
     np.add.at(gq, C[valid], (np.broadcast_to(g_I, D.shape) * dI_dq)[valid])
-    return ga, gq, tau.reshape(len(rows), res_x), I.reshape(len(rows), res_x)
+    out = ga, gq, m["tau"].reshape(m["shape"]), m["I"].reshape(m["shape"])
+    if not with_scale:
+        return out
+    terms = {"scale_alpha": np.abs(g_tau) * D + np.abs(g_I) * m["abs_da"], "scale_q": np.abs(g_I) * dI_dq,
+             "sens_alpha": np.abs(g_tau) * m["F"] + np.abs(g_I) * m["sens_a"], "sens_q": np.abs(g_I) * m["sens_q"]}
+    extra = {name: np.bincount(C[valid], weights=np.broadcast_to(t, D.shape)[valid], minlength=n_cells) for name, t in terms.items()}
+    return out + (extra,)

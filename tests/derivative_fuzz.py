@@ -1,0 +1,515 @@
+"""Randomised sweep of the derivative renders (tangent, adjoint, their batches, the Gauss-Newton product and diagonal)
+against the numpy restatements, element by element.
+
+    python tests/derivative_fuzz.py [n_scenes] [seed0]
+    python tests/derivative_fuzz.py chords SEED PIXEL      (the GPU's chords along one ray against the reference's)
+
+reports every mismatch and the worst error / tolerance per call kind; exit status 1 on any mismatch or when more than
+10 % of the seeds had to be skipped.  tests/test_gpu_derivative_fuzz.py runs 40 seeds of it under pytest;
+tests/test_derivative_references_cpu.py holds the restatements to an 80-digit reference on the same scenes.
+
+derivative_scene(seed) takes grid, view, image size and alpha limit from fuzz_scenes.scene(seed) (images of 20-500
+pixels a side, almost never a multiple of the 8x8 tile; limits U[0.5, 6); views about three axes) and adds
+  * alpha by class, every class in every scene with >= 10 cells (ALPHA_CLASSES): 0; (0, DBL_EPSILON); [DBL_EPSILON, 1e-6)
+    log-uniform; == limit; the two doubles next to the limit; (limit, 2 limit]; the rest U[0, limit).  "threshold" scenes
+    (one in four) scale the rest so that the median a dz of the segments sits at 1/8, the switch between series and closed
+    form in segment_terms (the limit is raised to the scaled maximum where it would clamp them), and give up to six
+    cells alpha = 0.125 / dz of one of their own chords or one of its two neighbouring doubles.  "underflow" scenes (one
+    in eight) have limit 1e9 and alpha up to 200 / (mean chord): T and E run through the subnormals to 0.
+    Q = U[0, 2) with 10 % zeros;
+  * K in 2..11 normal directions, d_alpha or d_q NULL in a third of the scenes; K normal upstream images with a patch
+    of exact zeros; Gauss-Newton weights U[0, 2) with a patch and a tenth of exact zeros (NULL in a fifth of the scenes);
+  * the frame layout: whole image, a random row range, or cyclic row tiles over every rank of a world of 2..5 (adjoints
+    summed, tangents put back in their rows), a third each;
+  * one in five as a soup on "algorithm" 1; one in five with a solid over part of the grid (its mask from the NaNs of a
+    forward render); one in four through the _device calls; in half of them the alpha limit is set only AFTER a first
+    forward render.
+
+A scene is used iff the port oracle renders it, adjoint_reference.segment_lists gives the oracle's segment and
+covered-pixel counts and the grid stays a pixel inside the image border (qualify).  No element of a used scene is left
+out of a comparison; GPU stats that disagree with those counts are a mismatch, not a skip.
+
+The bar, per element (a pixel's channel, a cell's gradient), with scale and sens from the reference:
+    tol = r_out |ref| + r64 scale + dz_err sens + 2^-970                                                   (tolerance)
+  r_out  2^-23 for fp32 outputs (one rounding to fp32 is 2^-24, doubled), 0 for fp64 ones.  The product's h carries its
+         fp32 intermediate as 2^-22 scale_h instead: one fp32 rounding of J v and one of its product with the weight,
+         2 x 2^-24, doubled; scale_h the absolute sums of the adjoint with the upstream image |w| |J v|.
+  r64    1e-9: the project's bar between two fp64 derivative results, on the element's own absolute-sum
+         scale instead of the array's maximum.
+  dz_err 16 x 2^-52 x max(1, max |coordinate in view space|), per segment times F = max(1, |gx| + |gy|) of the steeper of
+         its two faces z = c + gx x + gy y: the GPU's chord is a difference of two plane evaluations at absolute pixel
+         coordinates, three products and three sums each, whose terms have the size of (|gx| + |gy|) x the coordinates
+         (csrc/walk_common.hpp says the same of its entry keys: "rounding eps * kappa * |x|"); the reference gets the
+         chord from differences about a vertex.  sens = sum_k F_k |contribution_k| / dz_k, twice that for the
+         diagonal, whose terms go with dz^2 (tests/adjoint_reference.py, gn_reference.py).  Matters for sliver chords
+         only.  F and the 2 were missing at first: over 300 scenes three cells that a single weighted ray crosses in a
+         sliver ending on a steep face showed it - seed 10166 diag_q[108] (dz 9.6e-6, |gx| + |gy| = 18.7) at 5.5 x that
+         bar, 10114 grad[13922] (9.7e-7, 21.1) at 1.08 x, 10269 diag_q[13851] (3.5e-7, 23.2) at 1.03 x.  The GPU's chords
+         there, read back with `chords` (gpu_chords), are off by -11.05, -1.26 and +1.08 of the unscaled dz_err, 0.59,
+         0.06 and 0.05 of F x dz_err; the other 108 segments of those rays by at most 0.96 of F x dz_err, following their
+         faces' slopes (profiles/derivative_fuzz.md has the table).
+  2^-970 DBL_MIN / DBL_EPSILON: below it (underflow scenes) a double keeps no relative accuracy.  For an fp32 output the
+         same with fp32's numbers, FLT_MIN / 2^-23 = 2^-103: seed 3033's I_dot = 3.6e-86 is 0 in the image.
+None of these is fitted to what the GPU returns.
+"""
+import os
+import sys
+import time
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+import numpy as np
+
+from course5_amd import meshgen as mg, sharding
+from tests import adjoint_reference as ar, gn_reference as gr, tangent_reference as tr
+from tests.fuzz_scenes import scene
+
+B = mg.REFERENCE_BOUNDS
+EPS = float(np.finfo(np.float64).eps)
+R_OUT = 2.0 ** -23
+R_H = 2.0 ** -22
+R64 = 1e-9
+ABS_FLOOR = 2.0 ** -970
+ABS_FLOOR_32 = 2.0 ** -103
+ALPHA_CLASSES = ("zero", "below_eps", "eps_to_1e-6", "at_limit", "ulp_above_limit", "ulp_below_limit", "above_limit", "rest")
+_CLASS_P = (0.05, 0.04, 0.08, 0.05, 0.03, 0.03, 0.10, 0.62)
+KINDS = ("tangent", "tangent_batch", "adjoint", "adjoint_batch", "gn_product", "gn_diagonal")
+
+
+def alpha_class(alpha, limit):
+    """The class index (ALPHA_CLASSES) of every alpha."""
+    a = np.asarray(alpha)
+    c = np.full(a.shape, 7)
+    c[a == 0] = 0
+    c[(a > 0) & (a < EPS)] = 1
+    c[(a >= EPS) & (a < 1e-6)] = 2
+    c[a > limit] = 6
+    c[a == limit] = 3
+    c[a == np.nextafter(limit, np.inf)] = 4
+    c[a == np.nextafter(limit, -np.inf)] = 5
+    return c
+
+
+def derivative_scene(seed):
+    xyz, cells, _alpha, _q, rots, res, limit = scene(seed)
+    rng = np.random.default_rng([seed, 0xD5])
+    s = types.SimpleNamespace(seed=seed, rots=rots, res=res)
+    s.soup = bool(rng.integers(5) == 0)
+    if s.soup:
+        xyz, cells = mg.per_cell_point_copies(xyz, cells)
+    s.xyz, s.cells = xyz, cells
+    n = len(cells)
+    rx, ry = res
+    s.segments = pix, cell, _zh, dz, _slope = ar.segment_lists(xyz, cells, rots, rx, ry, B, with_slope=True)
+    s.mode = ("threshold", "threshold", "underflow", "plain", "plain", "plain", "plain", "plain")[int(rng.integers(8))]
+    # -- alpha
+    u = rng.uniform(0.0, 1.0, n)
+    amp = limit
+    if s.mode == "threshold" and len(dz):
+        amp = 0.125 / max(float(np.median(u[cell] * dz)), 1e-300)
+        limit = max(limit, amp)
+    elif s.mode == "underflow":
+        limit = 1e9
+        amp = 200.0 / float(dz.mean()) if len(dz) else 1e4
+    s.limit = limit
+    alpha = u * amp
+    cls = rng.choice(8, n, p=_CLASS_P)
+    first = rng.permutation(n)
+    if n >= 10:
+        cls[first[:8]] = np.arange(8)
+    k = [int((cls == c).sum()) for c in range(8)]
+    alpha[cls == 0] = 0.0
+    alpha[cls == 1] = np.minimum(10.0 ** rng.uniform(-300.0, np.log10(EPS), k[1]), np.nextafter(EPS, 0.0))
+    alpha[cls == 2] = np.clip(10.0 ** rng.uniform(np.log10(EPS), -6.0, k[2]), EPS, np.nextafter(1e-6, 0.0))
+    alpha[cls == 3] = limit
+    alpha[cls == 4] = np.nextafter(limit, np.inf)
+    alpha[cls == 5] = np.nextafter(limit, -np.inf)
+    alpha[cls == 6] = limit * (2.0 - rng.uniform(0.0, 1.0, k[6]))
+    s.threshold_cells = []
+    if s.mode == "threshold" and len(dz):
+        free = np.setdiff1d(np.flatnonzero(cls == 7), first[:8])
+        for j, c in enumerate(rng.permutation(free)):
+            chords = dz[cell == c]
+            if len(chords) == 0:
+                continue
+            a0 = 0.125 / float(rng.choice(chords))
+            if not a0 < limit:
+                continue
+            alpha[c] = (a0, np.nextafter(a0, np.inf), np.nextafter(a0, 0.0))[len(s.threshold_cells) % 3]
+            s.threshold_cells.append(int(c))
+            if len(s.threshold_cells) == 6:
+                break
+    s.alpha = alpha
+    s.q = rng.uniform(0.0, 2.0, n)
+    s.q[rng.uniform(size=n) < 0.1] = 0.0
+    # -- directions, upstream images, weights
+    s.k = int(rng.integers(2, 12))
+    null = int(rng.integers(6))
+    s.d_alpha = None if null == 0 else rng.normal(size=(s.k, n))
+    s.d_q = None if null == 1 else rng.normal(size=(s.k, n))
+
+    def patch():
+        r = np.sort(rng.integers(0, ry + 1, 2))
+        c = np.sort(rng.integers(0, rx + 1, 2))
+        return slice(r[0], max(r[1], r[0] + 1)), slice(c[0], max(c[1], c[0] + 1))
+
+    s.g = rng.normal(size=(s.k, ry, rx, 2)).astype(np.float32)
+    r, c = patch()
+    s.g[:, r, c] = 0.0
+    s.w = rng.uniform(0.0, 2.0, (ry, rx, 2)).astype(np.float32)
+    r, c = patch()
+    s.w[r, c] = 0.0
+    s.w[rng.uniform(size=s.w.shape) < 0.1] = 0.0
+    if rng.integers(5) == 0:
+        s.w = None
+    # -- frame layout
+    s.layout = ("whole", "range", "cyclic")[int(rng.integers(3))]
+    begin = int(rng.integers(0, ry))
+    s.row_range = (begin, int(rng.integers(1, ry - begin + 1)))
+    s.tile_rows, s.world = int(rng.choice([1, 3, 8, 16])), int(rng.integers(2, 6))
+    s.solid = bool(rng.integers(5) == 0)
+    s.solid_at = rng.uniform(0.3, 0.7, 3), float(rng.uniform(0.2, 0.5))
+    s.device = bool(rng.integers(4) == 0)
+    s.late_limit = bool(rng.integers(2) == 0)
+    return s
+
+
+def qualify(s, oracle):
+    """None if the scene is used, else why it is not (docstring: which scenes count)."""
+    rx, ry = s.res
+    v = oracle.rotate_points(s.xyz, s.rots)
+    px, py = (B[0] - B[1]) / (rx - 1), (B[2] - B[3]) / (ry - 1)
+    if v[:, 0].min() < B[1] + px or v[:, 0].max() > B[0] - px or v[:, 1].min() < B[3] + py or v[:, 1].max() > B[2] - py:
+        return "the grid reaches the image's border"
+    try:
+        ref = oracle.render(s.xyz, s.cells, s.alpha, s.q, s.rots, rx, ry, B, alpha_limit=s.limit, threads=8)
+    except RuntimeError as e:
+        return f"the oracle rejects the scene ({e})"
+    pix = s.segments[0]
+    s.n_segments, s.n_covered = len(pix), len(np.unique(pix))
+    if (s.n_segments, s.n_covered) != (ref["segments"], ref["covered"]):
+        return (f"segment_lists gives {s.n_segments} segments on {s.n_covered} pixels, the oracle "
+                f"{ref['segments']} on {ref['covered']}")
+    return None
+
+
+def dz_err(s):
+    return 16.0 * 2.0 ** -52 * max(1.0, float(np.abs(ar.rotate(s.xyz, s.rots)).max()))
+
+
+def ratio(got, ref, scale, sens, dz_e, r_out=0.0, r_scale=R64):
+    """error / tolerance per element (docstring: the bar); a value that is not finite counts as infinitely wrong."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    tol = r_out * np.abs(ref) + r_scale * scale + dz_e * sens + (ABS_FLOOR_32 if r_out else ABS_FLOOR)
+    r = np.abs(got - ref) / tol
+    return np.where(np.isfinite(got), r, np.inf)
+
+
+class Worst:
+    """The worst error / tolerance per call kind, with the seed and element that showed it, and the elements compared."""
+
+    def __init__(self):
+        self.by_kind = {k: (0.0, None) for k in KINDS}
+        self.elements = 0
+
+    def add(self, kind, r, seed, what=""):
+        r = np.asarray(r)
+        self.elements += r.size
+        if r.size and r.max() > self.by_kind[kind][0]:
+            i = np.unravel_index(int(np.argmax(r)), r.shape)
+            self.by_kind[kind] = (float(r.max()), f"seed {seed} {what} element {tuple(int(v) for v in i)}")
+        return float(r.max()) if r.size else 0.0
+
+    def lines(self):
+        return [f"worst error / tol, {k}: {v:.3g} ({w})" for k, (v, w) in self.by_kind.items()]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+class _Calls:
+    """The derivative calls of one context in their host forms (numpy in, numpy out)."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def tangent(self, da, dq):
+        return self.ctx.render_tangent(da, dq)
+
+    def tangent_batch(self, da, dq):
+        return self.ctx.render_tangent_batch(da, dq)
+
+    def adjoint(self, g):
+        return self.ctx.render_adjoint(g)
+
+    def adjoint_batch(self, g):
+        return self.ctx.render_adjoint_batch(g)
+
+    def gn_product(self, da, dq, w):
+        return self.ctx.render_gn_product(da, dq, w, want_jv=True)
+
+    def gn_diagonal(self, w):
+        return self.ctx.render_gn_diagonal(w)
+
+
+class _DeviceCalls(_Calls):
+    """The same through the _device forms: torch tensors on the GPU, the status from synchronize() (C5_RETRY: again)."""
+
+    def _run(self, call):
+        from course5_amd import capi
+        for _ in range(3):
+            call()
+            if self.ctx.synchronize() == capi.C5_OK:
+                return
+        raise RuntimeError("C5_RETRY three times in a row")
+
+    def _t(self, a, dtype=None):
+        import torch
+        return None if a is None else torch.tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
+
+    def _empty(self, shape, dtype):
+        import torch
+        return torch.full(shape, float("nan"), dtype=dtype, device="cuda")
+
+    def _image_shape(self):
+        return (self.ctx.local_rows, self.ctx.res_x, 2)
+
+    def tangent(self, da, dq):
+        import torch
+        out = self._empty(self._image_shape(), torch.float32)
+        a, q = self._t(da), self._t(dq)
+        self._run(lambda: self.ctx.render_tangent_device(a, q, out))
+        return out.cpu().numpy()
+
+    def tangent_batch(self, da, dq):
+        import torch
+        k = len(da if da is not None else dq)
+        out = self._empty((k,) + self._image_shape(), torch.float32)
+        a, q = self._t(da), self._t(dq)
+        self._run(lambda: self.ctx.render_tangent_batch_device(a, q, out))
+        return out.cpu().numpy()
+
+    def adjoint(self, g):
+        import torch
+        n = self.ctx.n_cells
+        ga, gq, gt = self._empty((n,), torch.float64), self._empty((n,), torch.float64), self._t(g, torch.float32)
+        self._run(lambda: self.ctx.render_adjoint_device(gt, ga, gq))
+        return ga.cpu().numpy(), gq.cpu().numpy()
+
+    def adjoint_batch(self, g):
+        import torch
+        n, k = self.ctx.n_cells, len(g)
+        ga, gq, gt = self._empty((k, n), torch.float64), self._empty((k, n), torch.float64), self._t(g, torch.float32)
+        self._run(lambda: self.ctx.render_adjoint_batch_device(gt, ga, gq))
+        return ga.cpu().numpy(), gq.cpu().numpy()
+
+    def gn_product(self, da, dq, w):
+        import torch
+        n, k = self.ctx.n_cells, len(da if da is not None else dq)
+        ha, hq = self._empty((k, n), torch.float64), self._empty((k, n), torch.float64)
+        jv = self._empty((k,) + self._image_shape(), torch.float32)
+        a, q, wt = self._t(da), self._t(dq), self._t(w, torch.float32)
+        self._run(lambda: self.ctx.render_gn_product_device(a, q, wt, ha, hq, jv))
+        return ha.cpu().numpy(), hq.cpu().numpy(), jv.cpu().numpy()
+
+    def gn_diagonal(self, w):
+        import torch
+        n = self.ctx.n_cells
+        da, dq, wt = self._empty((n,), torch.float64), self._empty((n,), torch.float64), self._t(w, torch.float32)
+        self._run(lambda: self.ctx.render_gn_diagonal_device(wt, da, dq))
+        return da.cpu().numpy(), dq.cpu().numpy()
+
+
+def check_scene(s, worst):
+    """Every derivative call on one used scene (qualify first) in a context of its own.  Returns the mismatches, strings."""
+    from course5_amd import capi
+    bad = []
+    rx, ry = s.res
+    n = len(s.cells)
+    K = s.k
+    with capi.Context(0) as ctx:
+        if s.soup:
+            ctx.set_option("algorithm", 1)
+        ctx.upload_grid(s.xyz, s.cells, s.alpha, s.q)
+        ctx.set_image(rx, ry, B)
+        ctx.set_view(s.rots)
+        if not s.late_limit:
+            ctx.set_alpha_limit(s.limit)
+        ctx.render()
+        st = ctx.stats()
+        if (st["segments"], st["covered_pixels"]) != (s.n_segments, s.n_covered):
+            bad.append(f"stats: {st['segments']} segments on {st['covered_pixels']} pixels, the reference has "
+                       f"{s.n_segments} on {s.n_covered}")
+        if s.late_limit:
+            ctx.set_alpha_limit(s.limit)  # (after a frame: the cell records carry the clamp and must be rebuilt)
+        skip = None
+        if s.solid:
+            v = ar.rotate(s.xyz, s.rots)
+            frac, size = s.solid_at
+            ext = v.max(0) - v.min(0)
+            sx, sc = mg.kuhn_box(2, lo=tuple(v.min(0) + frac * ext - 0.5 * size * ext.max()), size=size * float(ext.max()))
+            ctx.set_solid(0, sx[sc].reshape(-1, 12))
+            skip = np.isnan(ctx.render()[..., 0])
+        if s.layout == "range":
+            b, c = s.row_range
+            rows_ref = np.arange(b, b + c)
+            parts = [(lambda: ctx.set_row_range(b, c), np.arange(c))]
+        elif s.layout == "cyclic":
+            rows_ref = np.arange(ry)
+            parts = [((lambda r=r: ctx.set_row_tiles(s.tile_rows, r, s.world)), sharding.local_rows(ry, s.tile_rows, r, s.world))
+                     for r in range(s.world)]
+        else:
+            rows_ref = np.arange(ry)
+            parts = [(lambda: None, np.arange(ry))]
+        nr = len(rows_ref)
+        g_ref = s.g[:, rows_ref]
+        w_ref = None if s.w is None else s.w[rows_ref]
+        calls = _DeviceCalls(ctx) if s.device else _Calls(ctx)
+        tan = np.full((K, nr, rx, 2), np.nan, np.float32)
+        sums = {name: 0.0 for name in ("ga1", "gq1", "ga", "gq", "ha", "hq", "diag_a", "diag_q")}
+        for place, where in parts:
+            if len(where) == 0:  # (a rank without rows: small images in tall tiles)
+                continue
+            place()
+            before = ctx.render()
+            da, dq = s.d_alpha, s.d_q
+            singles = np.stack([calls.tangent(None if da is None else da[j], None if dq is None else dq[j]) for j in range(K)])
+            for width in (4, 8):
+                ctx.set_option("batch_width", width)
+                batch = calls.tangent_batch(da, dq)
+                if not np.array_equal(_bits(batch), _bits(singles)):
+                    bad.append(f"tangent batch (width {width}) differs from the single calls in "
+                               f"{int((_bits(batch) != _bits(singles)).sum())} values")
+            tan[:, where] = singles
+            g_part = np.ascontiguousarray(g_ref[:, where])
+            w_part = None if w_ref is None else np.ascontiguousarray(w_ref[where])
+            out = dict(zip(("ga1", "gq1"), calls.adjoint(g_part[0])))
+            out.update(zip(("ga", "gq"), calls.adjoint_batch(g_part)))
+            ha, hq, jv = calls.gn_product(da, dq, w_part)
+            if not np.array_equal(_bits(jv), _bits(singles)):
+                bad.append(f"the product's J v differs from the tangent batch in {int((_bits(jv) != _bits(singles)).sum())} values")
+            out.update(ha=ha, hq=hq)
+            out.update(zip(("diag_a", "diag_q"), calls.gn_diagonal(w_part)))
+            for name, v in out.items():
+                sums[name] = sums[name] + v
+            if not np.array_equal(_bits(ctx.render()), _bits(before)):
+                bad.append("a plain render after the derivative calls differs from the one before them")
+    # -- against the restatement, element by element
+    e = dz_err(s)
+    m = ar.ray_matrices(s.xyz, s.cells, s.alpha, s.q, s.rots, rx, ry, B, s.limit, rows_ref)
+    skip_ref = None if skip is None else skip[rows_ref]
+    found = []
+    for j in range(K):
+        td, Id, _tau, _I, x = tr.tangent_of(m, n, None if s.d_alpha is None else s.d_alpha[j],
+                                            None if s.d_q is None else s.d_q[j], skip_ref, with_scale=True)
+        r = np.stack([ratio(tan[j, ..., 0], td, x["scale_tau"], x["sens_tau"], e, R_OUT),
+                      ratio(tan[j, ..., 1], Id, x["scale_I"], x["sens_I"], e, R_OUT)], axis=-1)
+        found.append(("tangent" if j == 0 else "tangent_batch", f"direction {j}", r))
+        ga, gq, _tau, _I, x = ar.gradients_of(m, n, g_ref[j], skip_ref, with_scale=True)
+        r = np.stack([ratio(sums["ga"][j], ga, x["scale_alpha"], x["sens_alpha"], e),
+                      ratio(sums["gq"][j], gq, x["scale_q"], x["sens_q"], e)])
+        found.append(("adjoint_batch", f"image {j} (alpha, q)", r))
+        if j == 0:
+            r = np.stack([ratio(sums["ga1"], ga, x["scale_alpha"], x["sens_alpha"], e),
+                          ratio(sums["gq1"], gq, x["scale_q"], x["sens_q"], e)])
+            found.append(("adjoint", "(alpha, q)", r))
+    terms = gr.terms_of(m, skip_ref, with_scale=True)
+    for j in range(K):
+        ha, hq, _jv, x = gr.product_header(terms, nr * rx, n, None if s.d_alpha is None else s.d_alpha[j],
+                                           None if s.d_q is None else s.d_q[j], w_ref)
+        r = np.stack([ratio(sums["ha"][j], ha, x["scale_alpha"], x["sens_alpha"], e, r_scale=R64 + R_H),
+                      ratio(sums["hq"][j], hq, x["scale_q"], x["sens_q"], e, r_scale=R64 + R_H)])
+        found.append(("gn_product", f"direction {j} (alpha, q)", r))
+    da, dq = gr.diagonal(terms, nr * rx, n, w_ref)
+    x = gr.diagonal_scale(terms, nr * rx, n, w_ref)
+    r = np.stack([ratio(sums["diag_a"], da, x["scale_alpha"], x["sens_alpha"], e),
+                  ratio(sums["diag_q"], dq, x["scale_q"], x["sens_q"], e)])
+    found.append(("gn_diagonal", "(alpha, q)", r))
+    for kind, what, r in found:
+        top = worst.add(kind, r, s.seed, what)
+        if not top <= 1.0:
+            i = np.unravel_index(int(np.argmax(r)), r.shape)
+            bad.append(f"{kind} {what}: {int((~(r <= 1.0)).sum())} elements beyond the bar, worst error / tol {top:.3g} at {tuple(int(v) for v in i)}")
+    return bad
+
+
+def gpu_chords(s, pixel):
+    """The GPU's own chords along the ray of one pixel (row * res_x + col) of the whole frame: grad_alpha for an upstream
+    image that is (g_tau, g_I) = (1, 0) there is dz per cell.  Returns (cells, the reference's dz, the GPU's, F) in
+    processing order - how the chord errors in the bar's derivation were read (`derivative_fuzz.py chords SEED PIXEL`)."""
+    from course5_amd import capi
+    rx, ry = s.res
+    pix, cell, _zh, dz, slope = s.segments
+    sel = pix == pixel
+    with capi.Context(0) as ctx:
+        if s.soup:
+            ctx.set_option("algorithm", 1)
+        ctx.upload_grid(s.xyz, s.cells, s.alpha, s.q)
+        ctx.set_image(rx, ry, B)
+        ctx.set_view(s.rots)
+        ctx.set_alpha_limit(s.limit)
+        g = np.zeros((ry, rx, 2), np.float32)
+        g[pixel // rx, pixel % rx, 0] = 1.0
+        ga, _gq = ctx.render_adjoint(g)
+    return cell[sel], dz[sel], ga[cell[sel]], np.maximum(1.0, slope[sel])
+
+
+def describe(s):
+    return (f"{len(s.cells)} cells, {s.res[0]}x{s.res[1]}, limit {s.limit:.4g}, {s.mode}, {s.layout}, K {s.k}"
+            + (", soup" if s.soup else "") + (", solid" if s.solid else "") + (", device" if s.device else "")
+            + (", late limit" if s.late_limit else "") + (", no d_alpha" if s.d_alpha is None else "")
+            + (", no d_q" if s.d_q is None else "") + (", no weight" if s.w is None else ""))
+
+
+def run(seeds, oracle, worst, log=print):
+    """check_scene over seeds.  Returns (used, skipped, mismatches [(seed, text)])."""
+    used = skipped = 0
+    mismatches = []
+    for seed in seeds:
+        s = derivative_scene(seed)
+        why = qualify(s, oracle)
+        if why is not None:
+            skipped += 1
+            log(f"seed {seed}: {why} - skipped")
+            continue
+        used += 1
+        for text in check_scene(s, worst):
+            mismatches.append((seed, text))
+            log(f"seed {seed} ({describe(s)}): {text}")
+    return used, skipped, mismatches
+
+
+def main():
+    import torch  # noqa: F401  (HIP runtime load order)
+    from oracle.pyoracle import Oracle
+    if len(sys.argv) > 3 and sys.argv[1] == "chords":
+        s = derivative_scene(int(sys.argv[2]))
+        for c, d, got, f in zip(*gpu_chords(s, int(sys.argv[3]))):
+            print(f"cell {c}: dz {d:.6g}, GPU - reference {got - d:+.3g} = {(got - d) / dz_err(s):+.2f} dz_err, F {f:.1f}")
+        return 0
+    n_scenes = int(sys.argv[1]) if len(sys.argv) > 1 else 100
+    seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    worst = Worst()
+    t0 = time.time()
+    used = skipped = 0
+    mismatches = []
+    oracle = Oracle("port")
+    for k in range(0, n_scenes, 25):
+        u, sk, mm = run(range(seed0 + k, seed0 + min(k + 25, n_scenes)), oracle, worst, log=lambda t: print(t, flush=True))
+        used, skipped, mismatches = used + u, skipped + sk, mismatches + mm
+        print(f"... {min(k + 25, n_scenes)} of {n_scenes} seeds, {len(mismatches)} mismatches so far", flush=True)
+    print(f"{n_scenes} seeds from {seed0}: {used} used, {skipped} skipped, {len(mismatches)} mismatches, "
+          f"{worst.elements} elements compared, {time.time() - t0:.0f} s")
+    for line in worst.lines():
+        print(line)
+    too_many = skipped > 0.1 * n_scenes
+    if too_many:
+        print("more than 10 % of the seeds were skipped")
+    return 1 if mismatches or too_many else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,140 @@
+"""80-digit reference of the derivative renders (include/course5_hip.h: c5_render_tangent, c5_render_adjoint,
+c5_render_gn_product, c5_render_gn_diagonal) from per-pixel segment lists, in mpmath.
+
+The per-segment terms are evaluated AS THE HEADER AND line.cpp:176-227 STATE THEM - no series, no threshold at
+a dz = 1/8, no expm1: at 80 digits the cancellation of (1 - E) / a and of the bracket does not matter down to
+alpha = DBL_EPSILON.  For the segments k = 1..n of a pixel in processing order (deepest first):
+    a_k = min(alpha_k, limit), active_k = !(a_k < DBL_EPSILON), clamped_k = alpha_k > limit,
+    E_k = exp(-a_k dz_k), s_k = (1 - E_k) / a_k, B_k = Q_k (dz_k E_k / a_k - (1 - E_k) / a_k^2),
+    I_k = E_k I_{k-1} + Q_k s_k (active; else I_{k-1}), T_k = prod_{j > k, active} E_j, tau = sum dz_k alpha_k (raw alpha),
+    dI/dQ_k = T_k s_k (active), dI/dalpha_k = T_k (B_k - dz_k E_k I_{k-1}) (active and not clamped), dtau/dalpha_k = dz_k.
+The inputs (dz, alpha, Q, directions, weights) are the doubles the numpy restatements see, taken exactly.
+
+Every result comes with its SCALE, the same sum with every contribution replaced by its absolute value
+(|g_tau| dz, |g_I| T s, |g_I| T (|B| + dz E I_{k-1}); for the tangent |d_q| T s + |d_alpha| T (|B| + dz E I_{k-1})), and
+its CHORD SENSITIVITY sum_k F_k |contribution_k| / dz_k (F: tests/adjoint_reference.py): what a rounding error and an
+error of the chords can do to it.
+Results are returned rounded to fp64 (one rounding of the exact sum).
+"""
+from __future__ import annotations
+
+import numpy as np
+from mpmath import mp, mpf
+
+DPS = 80
+EPS = float(np.finfo(np.float64).eps)
+
+
+class Segments:
+    """The terms of every segment of the chosen pixels.  pix / cell / dz: adjoint_reference.segment_lists' arrays
+    (sorted by pixel, then in processing order); pixels: the pixels wanted (default: every pixel with a segment); slope:
+    segment_lists(with_slope=True)'s fifth array (default: flat faces, F = 1)."""
+
+    def __init__(self, pix, cell, dz, alpha, q, limit: float, pixels=None, slope=None):
+        mp.dps = DPS
+        pix, cell, dz = np.asarray(pix), np.asarray(cell), np.asarray(dz, np.float64)
+        self.pixels = np.unique(pix) if pixels is None else np.asarray(pixels)
+        # per pixel, per segment in processing order: dicts of mpf (c cell, d dz, F, a, Q, E, s, B, I_prev, T, moves; and the
+        # derived dI_dq, dI_da, abs_da)
+        self.rays = []
+        lo = np.searchsorted(pix, self.pixels, side="left")
+        hi = np.searchsorted(pix, self.pixels, side="right")
+        zero, one = mpf(0), mpf(1)
+        self.n_segments = int((hi - lo).sum())
+        for b, e in zip(lo, hi):
+            ray = []
+            I = zero
+            for k in range(b, e):
+                c = int(cell[k])
+                a_raw = float(alpha[c])
+                a = min(a_raw, limit)
+                t = dict(c=c, d=mpf(float(dz[k])), Q=mpf(float(q[c])), active=not a < EPS, moves=False, a=zero, E=one, s=zero,
+                         B=zero, I_prev=I, F=mpf(1.0 if slope is None else max(1.0, float(slope[k]))))
+                if t["active"]:
+                    d, Q, am = t["d"], t["Q"], mpf(a)
+                    E = mp.exp(-am * d)
+                    s = (one - E) / am
+                    t.update(a=am, E=E, s=s, B=Q * (d * E / am - (one - E) / (am * am)), moves=not a_raw > limit)
+                    I = E * I + Q * s
+                ray.append(t)
+            T = one
+            for t in reversed(ray):
+                d, E, I_prev = t["d"], t["E"], t["I_prev"]
+                t.update(T=T, dI_dq=T * t["s"], dI_da=zero, abs_da=zero)
+                if t["moves"]:
+                    t["dI_da"] = T * (t["B"] - d * E * I_prev)
+                    t["abs_da"] = T * (abs(t["B"]) + d * E * abs(I_prev))
+                T = T * E
+            self.rays.append(ray)
+
+
+def tangent(seg: Segments, d_alpha, d_q):
+    """Per pixel of seg.pixels: (tau_dot, I_dot, scale_tau, scale_I, sens_tau, sens_I), fp64 arrays.  None: zero."""
+    out = np.zeros((6, len(seg.pixels)))
+    for i, ray in enumerate(seg.rays):
+        tau_dot = I_dot = scale_tau = scale_I = sens_tau = sens_I = mpf(0)
+        for t in ray:
+            c, d = t["c"], t["d"]
+            da = mpf(0) if d_alpha is None else mpf(float(d_alpha[c]))
+            dq = mpf(0) if d_q is None else mpf(float(d_q[c]))
+            tau_dot += d * da
+            scale_tau += d * abs(da)
+            sens_tau += t["F"] * abs(da)
+            if not t["active"]:
+                continue
+            if not t["moves"]:
+                da = mpf(0)
+            E, I_prev = t["E"], t["I_prev"]
+            src = dq * t["s"] + da * (t["B"] - d * E * I_prev)
+            sens_I += t["F"] * abs(t["T"] * src) / d
+            I_dot = E * I_dot + src
+            scale_I = E * scale_I + abs(dq) * t["s"] + abs(da) * (abs(t["B"]) + d * E * abs(I_prev))
+        out[:, i] = [float(v) for v in (tau_dot, I_dot, scale_tau, scale_I, sens_tau, sens_I)]
+    return out
+
+
+def _per_cell(seg: Segments, n_cells: int, weights, contributions):
+    """Sums contributions(g_tau, g_I, t) -> 6 mpf (alpha, q, their scales, their sensitivities) per cell over the segments
+    t of seg's pixels; weights [len(pixels), 2] doubles."""
+    acc = {}
+    for ray, (g_tau, g_I) in zip(seg.rays, weights):
+        g_tau, g_I = mpf(float(g_tau)), mpf(float(g_I))
+        for t in ray:
+            v = contributions(g_tau, g_I, t)
+            a = acc.get(t["c"])
+            if a is None:
+                acc[t["c"]] = list(v)
+            else:
+                for j in range(6):
+                    a[j] += v[j]
+    out = np.zeros((6, n_cells))
+    for c, a in acc.items():
+        out[:, c] = [float(v) for v in a]
+    return dict(zip(("alpha", "q", "scale_alpha", "scale_q", "sens_alpha", "sens_q"), out))
+
+
+def adjoint(seg: Segments, n_cells: int, weights):
+    """grad_alpha / grad_q per cell with scales and sensitivities, for the upstream weights (g_tau, g_I) of seg.pixels."""
+    def terms(g_tau, g_I, t):
+        return (g_tau * t["d"] + g_I * t["dI_da"], g_I * t["dI_dq"], abs(g_tau) * t["d"] + abs(g_I) * t["abs_da"],
+                abs(g_I) * t["dI_dq"], t["F"] * (abs(g_tau * t["d"]) + abs(g_I * t["dI_da"])) / t["d"],
+                t["F"] * abs(g_I * t["dI_dq"]) / t["d"])
+    return _per_cell(seg, n_cells, weights, terms)
+
+
+def gn_diagonal(seg: Segments, n_cells: int, weights):
+    """diag(J^T W J) per cell with scales and sensitivities; weights (w_tau, w_I) >= 0 of seg.pixels."""
+    def terms(w_tau, w_I, t):
+        d = t["d"]
+        ca, cq = w_tau * d * d + w_I * t["dI_da"] ** 2, w_I * t["dI_dq"] ** 2
+        return (ca, cq, abs(w_tau) * d * d + abs(w_I) * t["abs_da"] ** 2, abs(cq), 2 * t["F"] * abs(ca) / d, 2 * t["F"] * abs(cq) / d)
+    return _per_cell(seg, n_cells, weights, terms)
+
+
+def gn_product(seg: Segments, n_cells: int, d_alpha, d_q, weights=None):
+    """J^T W (J v) with the header's fp32 intermediate: J v rounded to fp32, one fp32 multiply by the fp32 weight (None:
+    none), J^T of that exactly.  Returns (adjoint()'s dict for that upstream image, jv fp32 [len(pixels), 2])."""
+    t = tangent(seg, d_alpha, d_q)
+    jv32 = np.stack([t[0], t[1]], axis=1).astype(np.float32)
+    g32 = jv32 if weights is None else (np.asarray(weights, np.float32) * jv32).astype(np.float32)
+    return adjoint(seg, n_cells, g32.astype(np.float64)), jv32

@@ -12,13 +12,10 @@ image_gradients(weights = w * image_tangent(v)).
 """
 from __future__ import annotations
 
-import math
-
 import numpy as np
 
 from tests import adjoint_reference as ar
 
-EPS = ar.EPS
 
 
 def pixel_lists(xyz, cells, rots, res_x, res_y, bounds):
@@ -43,50 +40,29 @@ def dense_jacobian(lists, alpha, q, n_cells: int, limit: float = 2.5) -> np.ndar
     return J
 
 
-def segment_terms(xyz, cells, alpha, q, rots, res_x, res_y, bounds, limit: float = 2.5, rows=None, skip=None):
+def segment_terms(xyz, cells, alpha, q, rots, res_x, res_y, bounds, limit: float = 2.5, rows=None, skip=None,
+                  with_scale: bool = False):
     """Flat arrays over every segment of the pixels of the global rows `rows` (default: all; skip: bool [len(rows),
     res_x], True = solid-marked, nothing): (pixel, cell, dtau/dalpha, dI/dalpha, dI/dQ), pixel = local row * res_x + col.
-    The [pixel, k] evaluation of adjoint_reference.image_gradients, the terms kept instead of summed."""
-    rows = np.arange(res_y) if rows is None else np.asarray(rows)
-    alpha, q = np.asarray(alpha, np.float64), np.asarray(q, np.float64)
-    pix, cell, _zh, dz = ar.segment_lists(xyz, cells, rots, res_x, res_y, bounds)
-    row_slot = np.full(res_y, -1)
-    row_slot[rows] = np.arange(len(rows))
-    sel = row_slot[pix // res_x] >= 0
-    lp = (row_slot[pix // res_x] * res_x + pix % res_x)[sel]
-    cell, dz = cell[sel], dz[sel]
-    n_px = len(rows) * res_x
-    starts = np.searchsorted(lp, np.arange(n_px))
-    k = np.arange(len(lp)) - starts[lp]
-    M = int(k.max()) + 1 if len(k) else 1
-    C = np.full((n_px, M), -1)
-    D = np.zeros((n_px, M))
-    C[lp, k], D[lp, k] = cell, dz
-    valid = C >= 0
-    a_raw = np.where(valid, alpha[np.maximum(C, 0)], 0.0)
-    Q = np.where(valid, q[np.maximum(C, 0)], 0.0)
-    a = np.minimum(a_raw, limit)
-    active = valid & ~(a < EPS)
-    x = np.where(active, a * D, 0.0)
-    E = np.exp(-x)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        S = np.where(active, -np.expm1(-x) / np.where(active, a, 1.0), 0.0)
-        ser = sum((-1.0) ** (m + 1) * (m + 1) / math.factorial(m + 2) * x ** m for m in range(14))
-        direct = (x * E + np.expm1(-x)) / np.where(x > 0, x * x, 1.0)
-    br = Q * D * D * np.where(x < 0.125, ser, direct)
-    lam = np.cumsum(x, axis=1)
-    T = np.exp(-(lam[:, -1:] - lam))
-    I_prev = np.zeros_like(D)
-    I = np.zeros(n_px)
-    for j in range(M):
-        I_prev[:, j] = I
-        I = np.where(active[:, j], E[:, j] * I + Q[:, j] * S[:, j], I)
-    dI_dq = np.where(active, T * S, 0.0)
-    dI_da = np.where(active & ~(a_raw > limit), T * (br - D * E * I_prev), 0.0)
+    The [pixel, k] evaluation of adjoint_reference.image_gradients, the terms kept instead of summed.
+    with_scale: two more arrays, |dI/dalpha| with its two parts added in absolute value, T (|B| + dz E I_{k-1}), and the
+    segment's factor F of the chord sensitivity (adjoint_reference's docstring)."""
+    return terms_of(ar.ray_matrices(xyz, cells, alpha, q, rots, res_x, res_y, bounds, limit, rows), skip, with_scale)
+
+
+def terms_of(m, skip=None, with_scale: bool = False):
+    """segment_terms from adjoint_reference.ray_matrices' dict."""
+    C, D, valid, active, E, T = m["C"], m["D"], m["valid"], m["active"], m["E"], m["T"]
+    moves = active & ~m["clamped"]
+    dI_dq = np.where(active, T * m["S"], 0.0)
+    dI_da = np.where(moves, T * (m["B"] - D * E * m["I_prev"]), 0.0)
     if skip is not None:
         valid = valid & ~np.asarray(skip).reshape(-1)[:, None]
-    P = np.broadcast_to(np.arange(n_px)[:, None], C.shape)
-    return P[valid], C[valid], D[valid], dI_da[valid], dI_dq[valid]
+    P = np.broadcast_to(np.arange(m["n_px"])[:, None], C.shape)
+    out = P[valid], C[valid], D[valid], dI_da[valid], dI_dq[valid]
+    if with_scale:
+        out += (m["abs_da"][valid], m["F"][valid])
+    return out
 
 
 def _weights(weight, n_px):
@@ -95,7 +71,7 @@ def _weights(weight, n_px):
 
 def product(terms, n_px: int, n_cells: int, v_alpha, v_q, weight=None):
     """(h_alpha, h_q, jv) for one direction (None: zero): jv [n_px, 2] fp64 = J v, h = J^T (weight * jv)."""
-    P, C, dtau, dI_da, dI_dq = terms
+    P, C, dtau, dI_da, dI_dq = terms[:5]
     va = np.zeros(n_cells) if v_alpha is None else np.asarray(v_alpha, np.float64)
     vq = np.zeros(n_cells) if v_q is None else np.asarray(v_q, np.float64)
     jv = np.zeros((n_px, 2))
@@ -110,9 +86,39 @@ def product(terms, n_px: int, n_cells: int, v_alpha, v_q, weight=None):
 
 def diagonal(terms, n_px: int, n_cells: int, weight=None):
     """(diag_alpha, diag_q) of J^T W J."""
-    P, C, dtau, dI_da, dI_dq = terms
+    P, C, dtau, dI_da, dI_dq = terms[:5]
     w = _weights(weight, n_px)
     da, dq = np.zeros(n_cells), np.zeros(n_cells)
     np.add.at(da, C, w[P, 0] * dtau ** 2 + w[P, 1] * dI_da ** 2)
     np.add.at(dq, C, w[P, 1] * dI_dq ** 2)
     return da, dq
+
+
+def diagonal_scale(terms, n_px: int, n_cells: int, weight=None):
+    """Per-cell bounds for diagonal(): a dict scale_alpha / scale_q (the sums with dI/dalpha's two parts added in absolute
+    value before squaring) and sens_alpha / sens_q (sum of 2 F contribution / dz: a squared term goes with dz^2).
+    terms: segment_terms(with_scale=True)."""
+    P, C, dtau, dI_da, dI_dq, abs_da, F = terms
+    w = np.abs(_weights(weight, n_px))
+    parts = {"scale_alpha": w[P, 0] * dtau ** 2 + w[P, 1] * abs_da ** 2, "scale_q": w[P, 1] * dI_dq ** 2,
+             "sens_alpha": 2.0 * F * (w[P, 0] * dtau ** 2 + w[P, 1] * dI_da ** 2) / dtau, "sens_q": 2.0 * F * w[P, 1] * dI_dq ** 2 / dtau}
+    return {name: np.bincount(C, weights=t, minlength=n_cells) for name, t in parts.items()}
+
+
+def product_header(terms, n_px: int, n_cells: int, v_alpha, v_q, weight=None):
+    """product() with the fp32 intermediate of include/course5_hip.h: J v rounded to fp32, one fp32 multiply by the
+    weight (None: no multiply), J^T of that in fp64.  Returns (h_alpha, h_q, jv fp32 [n_px, 2], extra); extra: a dict
+    scale_alpha / scale_q / sens_alpha / sens_q of the adjoint with the upstream image |w| |J v| (its absolute sums and
+    chord sensitivity, as image_gradients(with_scale=True) defines them).  terms: segment_terms(with_scale=True)."""
+    P, C, dtau, dI_da, dI_dq, abs_da, F = terms
+    _, _, jv = product(terms, n_px, n_cells, v_alpha, v_q, None)
+    jv32 = jv.astype(np.float32)
+    g32 = jv32 if weight is None else (np.asarray(weight, np.float32).reshape(n_px, 2) * jv32).astype(np.float32)
+    g = g32.astype(np.float64)
+    ha, hq = np.zeros(n_cells), np.zeros(n_cells)
+    np.add.at(ha, C, g[P, 0] * dtau + g[P, 1] * dI_da)
+    np.add.at(hq, C, g[P, 1] * dI_dq)
+    ag = np.abs(g)
+    parts = {"scale_alpha": ag[P, 0] * dtau + ag[P, 1] * abs_da, "scale_q": ag[P, 1] * np.abs(dI_dq),
+             "sens_alpha": F * (ag[P, 0] * dtau + np.abs(g[P, 1] * dI_da)) / dtau, "sens_q": F * np.abs(g[P, 1] * dI_dq) / dtau}
+    return ha, hq, jv32, {name: np.bincount(C, weights=t, minlength=n_cells) for name, t in parts.items()}

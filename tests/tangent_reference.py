@@ -18,7 +18,6 @@ import numpy as np
 from tests import adjoint_reference as ar
 
 EPS = ar.EPS
-_SERIES = [(-1.0) ** (m + 1) * (m + 1) / math.factorial(m + 2) for m in range(14)]
 
 
 def pixel_tangent(segs, alpha, q, d_alpha, d_q, limit: float = 2.5) -> tuple[float, float]:
@@ -42,55 +41,49 @@ def pixel_tangent(segs, alpha, q, d_alpha, d_q, limit: float = 2.5) -> tuple[flo
     return tau_dot, I_dot
 
 
-def image_tangent(xyz, cells, alpha, q, rots, res_x, res_y, bounds, d_alpha, d_q, limit: float = 2.5, rows=None, skip=None):
+def image_tangent(xyz, cells, alpha, q, rots, res_x, res_y, bounds, d_alpha, d_q, limit: float = 2.5, rows=None, skip=None,
+                  with_scale: bool = False):
     """pixel_tangent over whole images, vectorised over the pixels.  d_alpha / d_q: [n_cells] (None: zero); rows: the
     global rows of the output (default: all); skip: optional bool [len(rows), res_x], True = a solid-marked pixel (0).
-    Returns (tau_dot, I_dot, tau, I), each fp64 [len(rows), res_x]."""
-    rows = np.arange(res_y) if rows is None else np.asarray(rows)
-    alpha, q = np.asarray(alpha, np.float64), np.asarray(q, np.float64)
-    d_alpha = np.zeros_like(alpha) if d_alpha is None else np.asarray(d_alpha, np.float64)
-    d_q = np.zeros_like(q) if d_q is None else np.asarray(d_q, np.float64)
-    pix, cell, _zh, dz = ar.segment_lists(xyz, cells, rots, res_x, res_y, bounds)
-    row_slot = np.full(res_y, -1)
-    row_slot[rows] = np.arange(len(rows))
-    sel = row_slot[pix // res_x] >= 0
-    lp = (row_slot[pix // res_x] * res_x + pix % res_x)[sel]
-    cell, dz = cell[sel], dz[sel]
-    n_px = len(rows) * res_x
-    # [pixel, k] matrices, k = processing order (deepest first)
-    starts = np.searchsorted(lp, np.arange(n_px))
-    k = np.arange(len(lp)) - starts[lp]
-    M = int(k.max()) + 1 if len(k) else 1
-    C = np.full((n_px, M), -1)
-    D = np.zeros((n_px, M))
-    C[lp, k], D[lp, k] = cell, dz
-    valid = C >= 0
+    Returns (tau_dot, I_dot, tau, I), each fp64 [len(rows), res_x]; with_scale: and tangent_of's dict."""
+    m = ar.ray_matrices(xyz, cells, alpha, q, rots, res_x, res_y, bounds, limit, rows)
+    return tangent_of(m, len(np.asarray(alpha)), d_alpha, d_q, skip, with_scale)
+
+
+def tangent_of(m, n_cells: int, d_alpha, d_q, skip=None, with_scale: bool = False):
+    """image_tangent from adjoint_reference.ray_matrices' dict (one set of matrices serves many directions).
+
+    with_scale: also a dict of per-pixel bounds (adjoint_reference's docstring): scale_tau = sum dz |d_alpha|, scale_I = the
+    recurrence run on |d_q| s + |d_alpha'| (|B| + dz E I_{k-1}), and the chord sensitivities sens_tau = sum F |d_alpha|,
+    sens_I = sum_k F_k |T_k (d_q s + d_alpha' (B - dz E I_{k-1}))| / dz_k."""
+    d_alpha = np.zeros(n_cells) if d_alpha is None else np.asarray(d_alpha, np.float64)
+    d_q = np.zeros(n_cells) if d_q is None else np.asarray(d_q, np.float64)
+    C, D, valid, active, E, S, Bk = m["C"], m["D"], m["valid"], m["active"], m["E"], m["S"], m["B"]
     Cc = np.maximum(C, 0)
-    a_raw = np.where(valid, alpha[Cc], 0.0)
-    Q = np.where(valid, q[Cc], 0.0)
     dA = np.where(valid, d_alpha[Cc], 0.0)
     dQ = np.where(valid, d_q[Cc], 0.0)
-    a = np.minimum(a_raw, limit)
-    active = valid & ~(a < EPS)
-    x = np.where(active, a * D, 0.0)
-    E = np.exp(-x)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        S = np.where(active, -np.expm1(-x) / np.where(active, a, 1.0), 0.0)
-        direct = (x * E + np.expm1(-x)) / np.where(x > 0, x * x, 1.0)
-    ser = sum(c * x ** m for m, c in enumerate(_SERIES))
-    Bk = Q * D * D * np.where(x < 0.125, ser, direct)
-    dA_eff = np.where(a_raw > limit, 0.0, dA)
-    I = np.zeros(n_px)
-    I_dot = np.zeros(n_px)
-    for j in range(M):
-        act = active[:, j]
-        src = dQ[:, j] * S[:, j] + dA_eff[:, j] * (Bk[:, j] - D[:, j] * E[:, j] * I)
-        I_dot = np.where(act, E[:, j] * I_dot + src, I_dot)
-        I = np.where(act, E[:, j] * I + Q[:, j] * S[:, j], I)
+    dA_eff = np.where(m["clamped"], 0.0, dA)
+    I_prev = m["I_prev"]
+    src = dQ * S + dA_eff * (Bk - D * E * I_prev)
+    I_dot = np.zeros(m["n_px"])
+    for j in range(D.shape[1]):
+        I_dot = np.where(active[:, j], E[:, j] * I_dot + src[:, j], I_dot)
     tau_dot = (D * dA).sum(1)
-    tau = (D * a_raw).sum(1)
+    tau, I = m["tau"].copy(), m["I"].copy()
+    shape = m["shape"]
+    extra = None
+    if with_scale:
+        abs_src = np.abs(dQ) * S + np.abs(dA_eff) * (np.abs(Bk) + D * E * np.abs(I_prev))
+        scale_I = np.zeros(m["n_px"])
+        for j in range(D.shape[1]):
+            scale_I = np.where(active[:, j], E[:, j] * scale_I + abs_src[:, j], scale_I)
+        extra = {"scale_tau": (D * np.abs(dA)).sum(1), "scale_I": scale_I, "sens_tau": (m["F"] * np.abs(dA)).sum(1),
+                 "sens_I": (np.where(active, np.abs(m["T"] * src), 0.0) * m["F_dz"]).sum(1)}
     if skip is not None:
-        s = np.asarray(skip).reshape(-1)
-        tau_dot[s] = I_dot[s] = tau[s] = I[s] = 0.0
-    shape = (len(rows), res_x)
-    return tau_dot.reshape(shape), I_dot.reshape(shape), tau.reshape(shape), I.reshape(shape)
+        sk = np.asarray(skip).reshape(-1)
+        tau_dot[sk] = I_dot[sk] = tau[sk] = I[sk] = 0.0
+        if extra:
+            for v in extra.values():
+                v[sk] = 0.0
+    out = tau_dot.reshape(shape), I_dot.reshape(shape), tau.reshape(shape), I.reshape(shape)
+    return out + ({k: v.reshape(shape) for k, v in extra.items()},) if with_scale else out
