@@ -27,7 +27,12 @@ LIB_SOURCES = [
     ("exact_kernels.hip", ["-ffp-contract=off"]),   # must round like the reference's host build
     ("walk_kernels.hip", []),
     ("adjoint_kernels.hip", ["-munsafe-fp-atomics"]),  # fp64 atomicAdd as global_atomic_add_f64, no compare-and-swap loop
-    ("c_api.hip", []),
+    # the C ABI, host code only (context.hpp)
+    ("context.hip", []),
+    ("grid.hip", []),
+    ("frame.hip", []),
+    ("derivatives.hip", []),
+    ("host_ring.hip", []),
     ("adjacency.cpp", ["-x", "c++", "-fopenmp"]),
 ]
 

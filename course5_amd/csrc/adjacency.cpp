@@ -307,7 +307,7 @@ void unique_solid_faces(const double* tets, int64_t n_tets, std::vector<double>&
     // union over all faces (plane.cpp:130-131 -> line.cpp:246-249), so such a face is pure overdraw: on the centre-fan
     // solids of the reference the three fan faces of every cell (long slivers from the centre to the surface: 460 times
     // the pixels of the surface triangles together).  Marked in the face's fourth word and sorted to the front, so that
-    // the raster can start behind them (c_api.hip, option "solid_interior_faces").  Sides by the sign of the cell's fourth
+    // the raster can start behind them (frame.hip: enqueue_solids, option "solid_interior_faces").  Sides by the sign of the cell's fourth
     // vertex against the face through its three (sorted, hence shared) point ids; a cell too flat to have a side
     // (|det| <= 1e-9 of the product of its edge lengths: the duplicated points at the poles of init_polar) counts for
     // neither, and a face with cells on one side only is a boundary face whatever its multiplicity.

@@ -1,0 +1,592 @@
+// ------------------------------------------------------------------------------------------
+// Derivative renders (c5_render_adjoint*, c5_render_tangent*; adjoint_kernels.hip): the frame c5_render would produce now,
+// differentiated with respect to the cells' alpha and Q.  Both share one per-view setup on the context's stream into slot
+// 0's buffers - records of "integration" 0 (the reference's order, whatever the option says), whole rays (no
+// "depth_split"), the entry lists, the solid mask; or bin_sort_resolve's lists - then run their own kernels.  They leave
+// the options alone and the frames' statistics and failure words too (counters and sticky words of their own); the slot's
+// per-view data are marked stale, so the next frame builds its own ("view_cache").
+// ------------------------------------------------------------------------------------------
+#include "context.hpp"
+
+using namespace c5api;
+
+namespace {
+
+struct DerivativeView {
+    bool no_cells = false;  // a scene of solids only: nothing was set up (there is no cell to differentiate)
+    bool bin_sort = false;  // "algorithm" 1: bin_sort_resolve's lists in ctx->offs64 / ctx->segs; else the walk's in w
+    hipStream_t s = nullptr;        // the context's stream: everything of a derivative runs on it
+    int64_t n_px = 0, padded = 0;   // pixels of the context's rows; rounded up to the scan's 1024
+    const int32_t* perm = nullptr;  // cell_perm on the device (device order -> the caller's), or nullptr: the identity
+    c5::GridView g{};
+    const uint32_t* mask = nullptr;  // solid-marked pixels, or nullptr
+    c5::WalkParams w{};
+};
+
+int setup_derivative(c5_context* ctx, DerivativeView& v) {
+    if (nothing_to_render(ctx)) return fail(ctx, C5_ERR_STATE, "plane initializer. empty set of objects to render");  // plane.cpp:269-271
+    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    FrameSlot& fs = ctx->slots[0];
+    hipStream_t s = v.s = ctx->stream;
+    const c5::ImageParams& im = ctx->im;
+    v.n_px = local_pixels(im);
+    const int64_t padded = v.padded = padded_pixels(im);
+    if (ctx->n_cells <= 0) {  // (solids only: no cell to differentiate)
+        v.no_cells = true;
+        return C5_OK;
+    }
+    if (c5::segment_bytes() != c5::adjoint_segment_bytes())
+        return fail(ctx, C5_ERR_STATE, "bin_sort_resolve's segment layout differs from the adjoint's");
+    // everything below runs on the context's stream: frames set up on the others ("pipeline", "overlap_setup") must be done
+    if (ctx->pipeline || ctx->overlap_setup) {
+        rc = drain(ctx);
+        if (rc) return rc;
+    }
+
+    C5_HIP(ctx, ctx->adj_counters.ensure(kCountersBytes));
+    C5_HIP(ctx, ctx->adj_sticky.ensure(kStickyWords * sizeof(unsigned)));
+    if (!ctx->adj_status) C5_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->adj_status), 4 * sizeof(unsigned), hipHostMallocDefault));
+    rc = ensure_device_perm(ctx);
+    if (rc) return rc;
+    v.perm = ctx->cell_perm.empty() ? nullptr : ctx->adj_perm.as<int32_t>();
+    c5::FrameCounters* const counters = ctx->adj_counters.as<c5::FrameCounters>();
+    C5_HIP(ctx, hipMemsetAsync(ctx->adj_sticky.ptr, 0, kStickyWords * sizeof(unsigned), s));
+
+    c5::GridView& g = v.g = grid_view(ctx, fs);
+    // the slot's per-view data are about to hold the derivative's: no frame may take them for its own
+    fs.setup_epoch = 0;
+    fs.setup_kept = false;
+    fs.flags_valid = false;
+
+    c5::launch_transform_soa(s, g.px, g.py, g.pz, g.vx, g.vy, g.vz, g.n_pts, ctx->view, counters);
+    c5::SolidTable table{};
+    bool any_solid = false;
+    v.bin_sort = uses_bin_sort(ctx);
+    if (v.bin_sort) {
+        int64_t total = 0;
+        rc = enqueue_bin_lists(ctx, fs, g, s, counters, total);
+        if (rc) return rc;
+        rc = enqueue_solids(ctx, fs, 0, s, table, any_solid);
+        if (rc) return rc;
+        v.mask = any_solid ? fs.mask.as<uint32_t>() : nullptr;
+    } else {
+        const double key_slack = entry_key_slack(ctx);
+        c5::launch_build_records(s, g, ctx->alpha_limit, 0);
+        if (!fs.head_clean) C5_HIP(ctx, hipMemsetAsync(fs.head.ptr, 0, static_cast<size_t>(padded) * sizeof(c5::EntryHead), s));
+        fs.head_clean = false;
+        c5::launch_entry_lists(s, g, ctx->xtab.as<double>(), ctx->ytab.as<double>(), im, fs.head.as<c5::EntryHead>(),
+                               fs.first.as<c5::Entry>(), fs.pool.as<c5::Entry>(), fs.entry_capacity, counters,
+                               ctx->adj_sticky.as<unsigned>(), 0, key_slack);
+        rc = enqueue_solids(ctx, fs, 0, s, table, any_solid);
+        if (rc) return rc;
+        v.mask = any_solid ? fs.mask.as<uint32_t>() : nullptr;
+        c5::WalkParams& wp = v.w;
+        wp.xrec = g.xrec;
+        wp.entry_head = fs.head.as<c5::EntryHead>();
+        wp.entry_first = fs.first.as<c5::Entry>();
+        wp.entry_pool = fs.pool.as<c5::Entry>();
+        wp.pool_capacity = fs.entry_capacity;
+        wp.key_slack = key_slack > 0.0 ? key_slack : 0.0;
+        wp.mask = v.mask;
+        wp.solids = table;
+        wp.Xtab = ctx->xtab.as<double>();
+        wp.Ytab = ctx->ytab.as<double>();
+        wp.im = im;
+        wp.max_steps = static_cast<uint32_t>(ctx->n_cells + 64);
+        wp.counters = counters;
+        wp.sticky = ctx->adj_sticky.as<unsigned>();
+    }
+    return C5_OK;
+}
+
+// After a derivative's kernels: its status words to the host for finish_adjoint, at the next wait.
+int commit_derivative(c5_context* ctx, const char* what) {
+    FrameSlot& fs = ctx->slots[0];
+    hipStream_t s = ctx->stream;
+    C5_HIP(ctx, hipGetLastError());
+    C5_HIP(ctx, hipMemcpyAsync(ctx->adj_status, &ctx->adj_counters.as<c5::FrameCounters>()->walk_overflow,
+                               kStatusWords * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    if (ctx->pipeline) {  // (the next frame's setup on the auxiliary stream waits for slot 0's buffers)
+        C5_HIP(ctx, hipEventRecord(fs.walk_done, s));
+        fs.walk_recorded = true;
+    }
+    ctx->adjoint_pending = true;
+    ctx->adj_what = what;
+    return C5_OK;
+}
+
+// The adjoint's parameters over the view's walk, with Lambda's buffer (pass 1 -> pass 2); the weights and where the sums
+// go are the caller's to fill in.
+int adjoint_params(c5_context* ctx, const DerivativeView& v, c5::AdjointParams& ap) {
+    C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
+    ap = c5::AdjointParams{};
+    ap.w = v.w;
+    ap.lambda = ctx->adj_lambda.as<double>();
+    return C5_OK;
+}
+
+// One adjoint over the view: the per-cell sums zeroed, two passes of the walk (or the resolve over bin_sort_resolve's
+// lists), and the permutation into the caller's order.  squared: the Gauss-Newton diagonal's kernels, `weights` may
+// then be null (ones).
+int adjoint_one(c5_context* ctx, const DerivativeView& v, bool squared, const float2* weights, double* ga_out, double* gq_out) {
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
+    C5_HIP(ctx, ctx->adj_grad.ensure(2 * n_cells * sizeof(double)));
+    double* const ga_dev = ctx->adj_grad.as<double>();
+    double* const gq_dev = ga_dev + n_cells;
+    C5_HIP(ctx, hipMemsetAsync(ga_dev, 0, 2 * n_cells * sizeof(double), v.s));
+    if (v.bin_sort) {
+        const auto resolve = squared ? c5::launch_gn_diag_resolve : c5::launch_adjoint_resolve;
+        resolve(v.s, v.g, ctx->im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, weights, ga_dev, gq_dev);
+    } else {
+        c5::AdjointParams ap;
+        int rc = adjoint_params(ctx, v, ap);
+        if (rc) return rc;
+        ap.grad_out = weights;
+        ap.grad_a = ga_dev;
+        ap.grad_q = gq_dev;
+        c5::launch_adjoint_walk(v.s, ap, 1);
+        if (squared) c5::launch_gn_diag_walk(v.s, ap);
+        else c5::launch_adjoint_walk(v.s, ap, 2);
+        ctx->slots[0].head_clean = true;  // (the second pass hands every head back cleared)
+    }
+    c5::launch_adjoint_permute(v.s, ga_dev, gq_dev, v.perm, ctx->n_cells, ga_out, gq_out);
+    return C5_OK;
+}
+
+// The adjoint: adjoint_one on the upstream image.
+int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, double* gq_out) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc || v.no_cells) return rc;
+    rc = adjoint_one(ctx, v, false, grad_out, ga_out, gq_out);
+    return rc ? rc : commit_derivative(ctx, "adjoint");
+}
+
+// One tangent over the view: the caller's direction into device order, then one walk (or tangent_resolve over
+// bin_sort_resolve's lists) that writes (tau_dot, I_dot) per pixel.
+int tangent_one(c5_context* ctx, const DerivativeView& v, const double* d_alpha, const double* d_q, float2* out) {
+    C5_HIP(ctx, ctx->tan_dir.ensure(static_cast<size_t>(ctx->n_cells) * sizeof(double2)));
+    double2* const dir = ctx->tan_dir.as<double2>();
+    c5::launch_tangent_gather(v.s, d_alpha, d_q, v.perm, ctx->n_cells, dir);
+    if (v.bin_sort) {
+        c5::launch_tangent_resolve(v.s, v.g, ctx->im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, dir, out);
+    } else {
+        c5::TangentParams tp{};
+        tp.w = v.w;
+        tp.dir = dir;
+        tp.out = out;
+        c5::launch_tangent_walk(v.s, tp);
+        ctx->slots[0].head_clean = true;  // (the walk hands every head back cleared)
+    }
+    return C5_OK;
+}
+
+// nothing but solids: n tangent images do not depend on any cell
+int zero_tangents(c5_context* ctx, const DerivativeView& v, int n, float2* out) {
+    if (out && v.n_px > 0) C5_HIP(ctx, hipMemsetAsync(out, 0, static_cast<size_t>(n) * v.n_px * sizeof(float2), v.s));
+    return C5_OK;
+}
+
+// The tangent: tangent_one on the direction.
+int enqueue_tangent(c5_context* ctx, const double* d_alpha, const double* d_q, float2* out) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    if (v.no_cells) return zero_tangents(ctx, v, 1, out);
+    rc = tangent_one(ctx, v, d_alpha, d_q, out);
+    return rc ? rc : commit_derivative(ctx, "tangent");
+}
+
+// Batches: the chunk width (4 or 8 directions / upstream images per walk; "batch_width").
+int batch_width(const c5_context* ctx, int n) {
+    if (ctx->batch_width) return ctx->batch_width;
+    return n <= 4 ? 4 : 8;
+}
+
+// directions k0 .. k0 + n_used - 1 of the caller's [n][n_cells] arrays into bat_dirs (ensured by the caller): `width`
+// interleaved pairs per cell in device order
+void gather_chunk(c5_context* ctx, const DerivativeView& v, int width, const double* d_alpha, const double* d_q, int k0, int n_used) {
+    c5::launch_tangent_gather_batch(v.s, width, d_alpha, d_q, v.perm, ctx->n_cells, k0, n_used, ctx->bat_dirs.as<double2>());
+}
+
+// The batched pass 2 over the view's walk: its buffers (Lambda's, and [n_cells][2 width] sums in device order) and its
+// parameters but for the chunk's (grad_out, n_used, keep_entries).
+int adjoint_batch_params(c5_context* ctx, const DerivativeView& v, int width, c5::AdjointBatchParams& ab) {
+    C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
+    C5_HIP(ctx, ctx->bat_grad.ensure(static_cast<size_t>(ctx->n_cells) * 2 * width * sizeof(double)));
+    ab = c5::AdjointBatchParams{};
+    ab.w = v.w;
+    ab.image_px = v.n_px;
+    ab.lambda = ctx->adj_lambda.as<double>();
+    ab.grad = ctx->bat_grad.as<double>();
+    return C5_OK;
+}
+
+// ... and one chunk of it: the sums zeroed, the walk, the permutation into rows k0_out .. of the caller's arrays
+int adjoint_chunk(c5_context* ctx, const DerivativeView& v, int width, const c5::AdjointBatchParams& ab, int k0_out, double* ga_out,
+                  double* gq_out) {
+    C5_HIP(ctx, hipMemsetAsync(ab.grad, 0, static_cast<size_t>(ctx->n_cells) * 2 * width * sizeof(double), v.s));
+    c5::launch_adjoint_walk_batch(v.s, width, ab);
+    c5::launch_adjoint_permute_batch(v.s, width, ab.grad, v.perm, ctx->n_cells, k0_out, ab.n_used, ga_out, gq_out);
+    return C5_OK;
+}
+
+// n directions ([n][n_cells] fp64 each, the caller's order; null: zero) -> out[n][local_rows][res_x]: one per-view setup,
+// then per chunk of up to `width` directions a gather into device order and one walk; the entry heads stay in place
+// between the chunks and the last walk hands them back cleared.  On bin_sort_resolve's lists: tangent_one per direction
+// (the first sorts the lists, the others find them sorted).  A batch of one is the single tangent.
+int enqueue_tangent_batch(c5_context* ctx, int n, const double* d_alpha, const double* d_q, float2* out) {
+    if (n == 1) return enqueue_tangent(ctx, d_alpha, d_q, out);
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    if (v.no_cells) return zero_tangents(ctx, v, n, out);
+    const int64_t n_cells = ctx->n_cells;
+    if (v.bin_sort) {
+        for (int j = 0; j < n && !rc; ++j)
+            rc = tangent_one(ctx, v, d_alpha ? d_alpha + j * n_cells : nullptr, d_q ? d_q + j * n_cells : nullptr,
+                             out + j * v.n_px);
+        return rc ? rc : commit_derivative(ctx, "tangent batch");
+    }
+    const int width = batch_width(ctx, n);
+    C5_HIP(ctx, ctx->bat_dirs.ensure(static_cast<size_t>(n_cells) * width * sizeof(double2)));
+    c5::TangentBatchParams tb{};
+    tb.w = v.w;
+    tb.dirs = ctx->bat_dirs.as<double2>();
+    tb.image_px = v.n_px;
+    for (int k0 = 0; k0 < n; k0 += width) {
+        tb.n_used = std::min(width, n - k0);
+        tb.out = out + k0 * v.n_px;
+        tb.keep_entries = k0 + width < n;
+        gather_chunk(ctx, v, width, d_alpha, d_q, k0, tb.n_used);
+        c5::launch_tangent_walk_batch(v.s, width, tb);
+    }
+    ctx->slots[0].head_clean = true;  // (the last chunk's walk hands every head back cleared)
+    return commit_derivative(ctx, "tangent batch");
+}
+
+// n upstream images ([n][local_rows][res_x] float2) -> ga_out / gq_out [n][n_cells] in the caller's order: one per-view
+// setup and ONE pass 1 (Lambda does not depend on the weights), then per chunk of up to `width` images the batched pass 2
+// into [n_cells][2 width] and its permutation.  On bin_sort_resolve's lists: adjoint_one per image.  A batch of one is the
+// single adjoint.
+int enqueue_adjoint_batch(c5_context* ctx, int n, const float2* grad_out, double* ga_out, double* gq_out) {
+    if (n == 1) return enqueue_adjoint(ctx, grad_out, ga_out, gq_out);
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc || v.no_cells) return rc;
+    const int64_t n_cells = ctx->n_cells;
+    if (v.bin_sort) {
+        for (int j = 0; j < n && !rc; ++j)
+            rc = adjoint_one(ctx, v, false, grad_out + j * v.n_px, ga_out + j * n_cells, gq_out + j * n_cells);
+        return rc ? rc : commit_derivative(ctx, "adjoint batch");
+    }
+    const int width = batch_width(ctx, n);
+    c5::AdjointParams ap;
+    c5::AdjointBatchParams ab;
+    rc = adjoint_params(ctx, v, ap);
+    if (!rc) rc = adjoint_batch_params(ctx, v, width, ab);
+    if (rc) return rc;
+    c5::launch_adjoint_walk(v.s, ap, 1);
+    for (int k0 = 0; k0 < n; k0 += width) {
+        ab.n_used = std::min(width, n - k0);
+        ab.grad_out = grad_out + k0 * v.n_px;
+        ab.keep_entries = k0 + width < n;
+        rc = adjoint_chunk(ctx, v, width, ab, k0, ga_out, gq_out);
+        if (rc) return rc;
+    }
+    ctx->slots[0].head_clean = true;  // (the last chunk's pass 2 hands every head back cleared)
+    return commit_derivative(ctx, "adjoint batch");
+}
+
+// The Gauss-Newton product H v = J^T W J v for n directions: one per-view setup, then per chunk of up to `width` directions
+// the gather, pass A (gn_walk_a: the tangent walk that is also the adjoint's pass 1; g = w * J v in fp32 and Lambda), the
+// batched pass 2 on g, and its permutation.  The heads stay in place from pass A to pass B and between the chunks; the
+// last pass B hands them back cleared.  On bin_sort_resolve's lists: tangent_one -> gn_weight -> adjoint_one per
+// direction.  ha_out / hq_out: either may be null (then that block goes to a spare buffer); jv_out may be null.
+int enqueue_gn_product(c5_context* ctx, int n, const double* d_alpha, const double* d_q, const float2* weight, double* ha_out,
+                       double* hq_out, float2* jv_out) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    if (v.no_cells) return zero_tangents(ctx, v, n, jv_out);
+    const int64_t n_cells = ctx->n_cells, n_px = v.n_px;
+    const int width = v.bin_sort ? 1 : batch_width(ctx, n);
+    if (!ha_out || !hq_out) C5_HIP(ctx, ctx->gn_spare.ensure(static_cast<size_t>(n_cells) * width * sizeof(double)));
+    double* const spare = ctx->gn_spare.as<double>();
+    if (v.bin_sort) {
+        C5_HIP(ctx, ctx->gn_g.ensure(2 * static_cast<size_t>(n_px) * sizeof(float2) + 16));
+        float2* const g = ctx->gn_g.as<float2>();
+        for (int j = 0; j < n; ++j) {
+            float2* const t = jv_out ? jv_out + j * n_px : g + n_px;
+            rc = tangent_one(ctx, v, d_alpha ? d_alpha + j * n_cells : nullptr, d_q ? d_q + j * n_cells : nullptr, t);
+            if (rc) return rc;
+            c5::launch_gn_weight(v.s, t, weight, n_px, 1, g);
+            rc = adjoint_one(ctx, v, false, g, ha_out ? ha_out + j * n_cells : spare, hq_out ? hq_out + j * n_cells : spare);
+            if (rc) return rc;
+        }
+        return commit_derivative(ctx, "gn product");
+    }
+    c5::AdjointBatchParams ab;
+    rc = adjoint_batch_params(ctx, v, width, ab);
+    if (rc) return rc;
+    C5_HIP(ctx, ctx->bat_dirs.ensure(static_cast<size_t>(n_cells) * width * sizeof(double2)));
+    C5_HIP(ctx, ctx->gn_g.ensure(static_cast<size_t>(width) * n_px * sizeof(float2) + 16));
+    c5::GnWalkParams ga{};
+    ga.w = v.w;
+    ga.dirs = ctx->bat_dirs.as<double2>();
+    ga.weight = weight;
+    ga.lambda = ctx->adj_lambda.as<double>();
+    ga.g = ctx->gn_g.as<float2>();
+    ga.image_px = n_px;
+    ab.grad_out = ga.g;
+    for (int k0 = 0; k0 < n; k0 += width) {
+        ga.n_used = ab.n_used = std::min(width, n - k0);
+        ga.jv_out = jv_out ? jv_out + k0 * n_px : nullptr;
+        ab.keep_entries = k0 + width < n;
+        gather_chunk(ctx, v, width, d_alpha, d_q, k0, ga.n_used);
+        c5::launch_gn_walk_a(v.s, width, ga);
+        rc = adjoint_chunk(ctx, v, width, ab, 0, ha_out ? ha_out + k0 * n_cells : spare, hq_out ? hq_out + k0 * n_cells : spare);
+        if (rc) return rc;
+    }
+    ctx->slots[0].head_clean = true;  // (the last chunk's pass B hands every head back cleared)
+    return commit_derivative(ctx, "gn product");
+}
+
+// diag(J^T W J): adjoint_one with the squared kernels.  weight null: ones.
+int enqueue_gn_diagonal(c5_context* ctx, const float2* weight, double* da_out, double* dq_out) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc || v.no_cells) return rc;
+    rc = adjoint_one(ctx, v, true, weight, da_out, dq_out);
+    return rc ? rc : commit_derivative(ctx, "gn diagonal");
+}
+
+}  // namespace
+
+namespace c5api __attribute__((visibility("hidden"))) {
+// After the stream drained: the failure words of the last adjoint or tangent (as finish_frame treats a frame's).
+int finish_adjoint(c5_context* ctx) {
+    if (!ctx->adjoint_pending) return C5_OK;
+    ctx->adjoint_pending = false;
+    const unsigned lost_rays = ctx->adj_status[0], refused = ctx->adj_status[1], overlap_rays = ctx->adj_status[2];
+    if (refused) {
+        int rc = drain(ctx);
+        if (rc) return rc;
+        rc = grow_entry_pools(ctx, std::min<int64_t>(2 * (ctx->slots[0].entry_capacity + refused) + 8192, kMaxEntryPool));
+        if (rc) return rc;
+        return fail(ctx, C5_RETRY, "%s: %u boundary entries found no room in the overflow pool (now %lld records): run it again",
+                    ctx->adj_what, refused, static_cast<long long>(ctx->slots[0].entry_capacity));
+    }
+    if (lost_rays) return fail(ctx, C5_ERR_WALK, "%s: %u rays exceeded the walk step bound (malformed grid?)", ctx->adj_what, lost_rays);
+    if (overlap_rays) {
+        ctx->overlap_seen = true;  // (what the next frame would find out for itself: bin_sort_resolve from now on)
+        ++ctx->setup_epoch;
+        return fail(ctx, C5_RETRY,
+                    "%s: %u rays met a boundary entry inside a stretch of cells they had walked: components of the grid "
+                    "interpenetrate; run it again (bin_sort_resolve from now on)", ctx->adj_what, overlap_rays);
+    }
+    return C5_OK;
+}
+}  // namespace c5api
+
+namespace {
+
+// What the twelve derivative entry points check before anything else, in this order: the context; a batch's size; the
+// call's own pointers (`required_ok`, and `per_cell_ok` where the grid has cells); no c5_render_host_async frame
+// outstanding; and for the host-pointer forms the image, after which the device is bound.
+struct DerivativeCall {
+    const char* name;         // as the messages spell it: "c5_render_tangent_batch" also for its _device form
+    bool host;                // a host-pointer form
+    int n;                    // a batch's size (1: not a batch)
+    const char* batch_of;     // "direction" / "upstream image"
+    bool required_ok, per_cell_ok;
+    const char* pointer_msg;
+    bool refuse_async = true;
+};
+
+int check_derivative(c5_context* ctx, const DerivativeCall& c) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (c.n < 1) return fail(ctx, C5_ERR_INVALID, "a batch needs at least one %s (%d)", c.batch_of, c.n);
+    if (!c.required_ok || (ctx->n_cells > 0 && !c.per_cell_ok)) return fail(ctx, C5_ERR_INVALID, "%s", c.pointer_msg);
+    if (c.refuse_async && ctx->hr_count) return fail(ctx, C5_ERR_STATE, "%s while c5_render_host_async frames are outstanding", c.name);
+    if (!c.host) return C5_OK;
+    if (!ctx->have_image) return fail(ctx, C5_ERR_STATE, "critical error. empty plane");  // plane.cpp:151-153
+    return bind_device(ctx);
+}
+
+// One block of a host-pointer derivative call's staging buffer: uploaded from `src` before the work, downloaded to `dst`
+// after it (either may be null).  dev: its place on the device, or nullptr where the caller gave neither - the enqueue
+// then sees the null pointer the caller passed.
+struct Staged {
+    const void* src;
+    void* dst;
+    size_t bytes;
+    char* dev = nullptr;
+    template <class T>
+    T* as() const { return reinterpret_cast<T*>(dev); }
+};
+
+// The host-pointer form of a derivative: the blocks laid out in deriv_io (256-byte aligned), the uploads on the context's
+// stream, `enqueue` and c5_synchronize - again while the entry pool had to grow (C5_RETRY) - and the downloads.
+template <size_t N, class Enqueue>
+int run_staged(c5_context* ctx, const char* what, Staged (&blocks)[N], Enqueue enqueue) {
+    auto room = [](const Staged& b) { return (b.bytes + 255) / 256 * 256; };
+    size_t total = 0;
+    for (const Staged& b : blocks) total += room(b);
+    C5_HIP(ctx, ctx->deriv_io.ensure(total + 256));
+    char* at = ctx->deriv_io.as<char>();
+    for (Staged& b : blocks) {
+        if (b.src || b.dst) b.dev = at;
+        at += room(b);
+        if (b.src && b.bytes > 0) C5_HIP(ctx, hipMemcpyAsync(b.dev, b.src, b.bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        int rc = enqueue();
+        if (rc) return rc;
+        rc = c5_synchronize(ctx);
+        if (rc == C5_RETRY) continue;
+        if (rc) return rc;
+        for (const Staged& b : blocks)
+            if (b.dst && b.bytes > 0) C5_HIP(ctx, hipMemcpy(b.dst, b.dev, b.bytes, hipMemcpyDeviceToHost));
+        return C5_OK;
+    }
+    return fail(ctx, C5_ERR_STATE, "%s: entry buffer kept overflowing", what);
+}
+
+size_t cells_bytes(const c5_context* ctx) { return static_cast<size_t>(ctx->n_cells) * sizeof(double); }
+}  // namespace
+
+extern "C" {
+
+// The only derivative entry point that does not refuse while c5_render_host_async frames are outstanding (it never has).
+int c5_render_adjoint_device(c5_context* ctx, const void* grad_out_device, void* grad_alpha_device, void* grad_q_device) {
+    int rc = check_derivative(ctx, {"c5_render_adjoint", false, 1, nullptr, grad_out_device != nullptr,
+                                    grad_alpha_device && grad_q_device, "null adjoint pointer", false});
+    if (rc) return rc;
+    return enqueue_adjoint(ctx, static_cast<const float2*>(grad_out_device), static_cast<double*>(grad_alpha_device),
+                           static_cast<double*>(grad_q_device));
+}
+
+int c5_render_adjoint(c5_context* ctx, const float* grad_out_host, double* grad_alpha_host, double* grad_q_host) {
+    int rc = check_derivative(ctx, {"c5_render_adjoint", true, 1, nullptr, grad_out_host != nullptr, grad_alpha_host && grad_q_host,
+                                    "null adjoint pointer"});
+    if (rc) return rc;
+    Staged b[] = {{grad_out_host, nullptr, image_bytes(ctx)},
+                  {nullptr, grad_alpha_host, cells_bytes(ctx)},
+                  {nullptr, grad_q_host, cells_bytes(ctx)}};
+    return run_staged(ctx, "adjoint", b, [&] {
+        return enqueue_adjoint(ctx, b[0].as<const float2>(), b[1].as<double>(), b[2].as<double>());
+    });
+}
+
+int c5_render_tangent_device(c5_context* ctx, const void* d_alpha_dev, const void* d_q_dev, void* out_device) {
+    int rc = check_derivative(ctx, {"c5_render_tangent", false, 1, nullptr, out_device != nullptr, true, "null output pointer"});
+    if (rc) return rc;
+    return enqueue_tangent(ctx, static_cast<const double*>(d_alpha_dev), static_cast<const double*>(d_q_dev),
+                           static_cast<float2*>(out_device));
+}
+
+int c5_render_tangent(c5_context* ctx, const double* d_alpha_host, const double* d_q_host, float* out_host) {
+    int rc = check_derivative(ctx, {"c5_render_tangent", true, 1, nullptr, out_host != nullptr, true, "null output pointer"});
+    if (rc) return rc;
+    Staged b[] = {{d_alpha_host, nullptr, cells_bytes(ctx)},
+                  {d_q_host, nullptr, cells_bytes(ctx)},
+                  {nullptr, out_host, image_bytes(ctx)}};
+    return run_staged(ctx, "tangent", b, [&] {
+        return enqueue_tangent(ctx, b[0].as<const double>(), b[1].as<const double>(), b[2].as<float2>());
+    });
+}
+
+int c5_render_tangent_batch_device(c5_context* ctx, int n_dirs, const void* d_alpha_dev, const void* d_q_dev, void* out_dev) {
+    int rc = check_derivative(ctx, {"c5_render_tangent_batch", false, n_dirs, "direction", out_dev != nullptr, true,
+                                    "null output pointer"});
+    if (rc) return rc;
+    return enqueue_tangent_batch(ctx, n_dirs, static_cast<const double*>(d_alpha_dev), static_cast<const double*>(d_q_dev),
+                                 static_cast<float2*>(out_dev));
+}
+
+int c5_render_tangent_batch(c5_context* ctx, int n_dirs, const double* d_alpha_host, const double* d_q_host, float* out_host) {
+    int rc = check_derivative(ctx, {"c5_render_tangent_batch", true, n_dirs, "direction", out_host != nullptr, true,
+                                    "null output pointer"});
+    if (rc) return rc;
+    const size_t dir_bytes = n_dirs * cells_bytes(ctx);
+    Staged b[] = {{d_alpha_host, nullptr, dir_bytes},
+                  {d_q_host, nullptr, dir_bytes},
+                  {nullptr, out_host, n_dirs * image_bytes(ctx)}};
+    return run_staged(ctx, "tangent batch", b, [&] {
+        return enqueue_tangent_batch(ctx, n_dirs, b[0].as<const double>(), b[1].as<const double>(), b[2].as<float2>());
+    });
+}
+
+int c5_render_adjoint_batch_device(c5_context* ctx, int n_imgs, const void* grad_out_dev, void* grad_alpha_dev, void* grad_q_dev) {
+    int rc = check_derivative(ctx, {"c5_render_adjoint_batch", false, n_imgs, "upstream image", grad_out_dev != nullptr,
+                                    grad_alpha_dev && grad_q_dev, "null adjoint pointer"});
+    if (rc) return rc;
+    return enqueue_adjoint_batch(ctx, n_imgs, static_cast<const float2*>(grad_out_dev), static_cast<double*>(grad_alpha_dev),
+                                 static_cast<double*>(grad_q_dev));
+}
+
+int c5_render_adjoint_batch(c5_context* ctx, int n_imgs, const float* grad_out_host, double* grad_alpha_host, double* grad_q_host) {
+    int rc = check_derivative(ctx, {"c5_render_adjoint_batch", true, n_imgs, "upstream image", grad_out_host != nullptr,
+                                    grad_alpha_host && grad_q_host, "null adjoint pointer"});
+    if (rc) return rc;
+    const size_t grad_bytes = n_imgs * cells_bytes(ctx);
+    Staged b[] = {{grad_out_host, nullptr, n_imgs * image_bytes(ctx)},
+                  {nullptr, grad_alpha_host, grad_bytes},
+                  {nullptr, grad_q_host, grad_bytes}};
+    return run_staged(ctx, "adjoint batch", b, [&] {
+        return enqueue_adjoint_batch(ctx, n_imgs, b[0].as<const float2>(), b[1].as<double>(), b[2].as<double>());
+    });
+}
+
+int c5_render_gn_product_device(c5_context* ctx, int n_dirs, const void* d_alpha_dev, const void* d_q_dev, const void* weight_dev,
+                                void* h_alpha_dev, void* h_q_dev, void* jv_out_dev) {
+    int rc = check_derivative(ctx, {"c5_render_gn_product", false, n_dirs, "direction", h_alpha_dev || h_q_dev, true,
+                                    "null output pointers: give h_alpha, h_q or both"});
+    if (rc) return rc;
+    return enqueue_gn_product(ctx, n_dirs, static_cast<const double*>(d_alpha_dev), static_cast<const double*>(d_q_dev),
+                              static_cast<const float2*>(weight_dev), static_cast<double*>(h_alpha_dev), static_cast<double*>(h_q_dev),
+                              static_cast<float2*>(jv_out_dev));
+}
+
+int c5_render_gn_product(c5_context* ctx, int n_dirs, const double* d_alpha_host, const double* d_q_host, const float* weight_host,
+                         double* h_alpha_host, double* h_q_host, float* jv_out_host) {
+    int rc = check_derivative(ctx, {"c5_render_gn_product", true, n_dirs, "direction", h_alpha_host || h_q_host, true,
+                                    "null output pointers: give h_alpha, h_q or both"});
+    if (rc) return rc;
+    const size_t dir_bytes = n_dirs * cells_bytes(ctx);
+    Staged b[] = {{weight_host, nullptr, image_bytes(ctx)},
+                  {d_alpha_host, nullptr, dir_bytes},
+                  {d_q_host, nullptr, dir_bytes},
+                  {nullptr, h_alpha_host, dir_bytes},
+                  {nullptr, h_q_host, dir_bytes},
+                  {nullptr, jv_out_host, n_dirs * image_bytes(ctx)}};
+    return run_staged(ctx, "gn product", b, [&] {
+        return enqueue_gn_product(ctx, n_dirs, b[1].as<const double>(), b[2].as<const double>(), b[0].as<const float2>(),
+                                  b[3].as<double>(), b[4].as<double>(), b[5].as<float2>());
+    });
+}
+
+int c5_render_gn_diagonal_device(c5_context* ctx, const void* weight_dev, void* diag_alpha_dev, void* diag_q_dev) {
+    int rc = check_derivative(ctx, {"c5_render_gn_diagonal", false, 1, nullptr, true, diag_alpha_dev && diag_q_dev,
+                                    "null diagonal pointer"});
+    if (rc) return rc;
+    return enqueue_gn_diagonal(ctx, static_cast<const float2*>(weight_dev), static_cast<double*>(diag_alpha_dev),
+                               static_cast<double*>(diag_q_dev));
+}
+
+int c5_render_gn_diagonal(c5_context* ctx, const float* weight_host, double* diag_alpha_host, double* diag_q_host) {
+    int rc = check_derivative(ctx, {"c5_render_gn_diagonal", true, 1, nullptr, true, diag_alpha_host && diag_q_host,
+                                    "null diagonal pointer"});
+    if (rc) return rc;
+    Staged b[] = {{weight_host, nullptr, image_bytes(ctx)},
+                  {nullptr, diag_alpha_host, cells_bytes(ctx)},
+                  {nullptr, diag_q_host, cells_bytes(ctx)}};
+    return run_staged(ctx, "gn diagonal", b, [&] {
+        return enqueue_gn_diagonal(ctx, b[0].as<const float2>(), b[1].as<double>(), b[2].as<double>());
+    });
+}
+
+}  // extern "C"
