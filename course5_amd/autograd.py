@@ -32,6 +32,14 @@ backward or jvp after the view, image, rows, solids, alpha limit or grid changed
 other than the one rendered.  The gradients are fp64 sums added by atomics in arrival order: not bit-reproducible from run
 to run; the tangent is, batched or not.
 
+render_view(ctx, alpha, q, angles) is render with the view's angles as a third differentiable input: angles [n_rots]
+(radians) are written into the context's current rotation list (axes and x0 kept) before the frame is rendered.  Its
+derivative in the angles is the library's motion tangent render (c5_render_motion_tangent_device): backward is ONE such
+call for all the angles and grad_angles[i] = sum g * d img / d angle_i in fp64; jvp is one call for the one affine field
+sum_i t_i field_i; under vmap, batches of angle tangents go to one batched call and batches of cotangents share one.
+Pixels that gain or lose coverage when the view turns are not differentiated (include/course5_hip.h): the derivative is
+that of the smooth piece every pixel is on.  alpha and q are differentiated as by render.
+
 Beside render, two operators for Gauss-Newton fits (course5_amd.fit): gn_product(ctx, alpha, q, v_alpha, v_q, weight) =
 J^T W J v and gn_diagonal(ctx, alpha, q, weight) = diag(J^T W J), one library call each (c5_render_gn_product_device,
 c5_render_gn_diagonal_device).  They upload the scalars as the forward does, return float64 tensors on the context's GPU
@@ -285,6 +293,148 @@ def render(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor) -> torch.Ten
     return _Render.apply(ctx, alpha, q)
 
 
+# ---- the view's angles as an input ------------------------------------------------------------------------------------
+
+def _set_angles(ctx: capi.Context, angles: torch.Tensor) -> None:
+    a = _plain(angles).detach().to("cpu", torch.float64).reshape(-1).numpy()
+    if a.shape != (len(ctx.rots),):
+        raise ValueError(f"angles must hold one value per rotation of the context's view ({len(ctx.rots)})")
+    rots = ctx.rots.copy()
+    rots[:, 1] = a
+    ctx.set_view(rots)
+
+
+def _motion(ctx: capi.Context, fields, device: torch.device) -> torch.Tensor:
+    """[K, local_rows, res_x, 2] float32 on the context's GPU: the motion tangent render for fields [K, 12] (numpy)."""
+    with torch._C._DisableFuncTorch(), torch.cuda.device(device):
+        out = torch.empty((len(fields), ctx.local_rows, ctx.res_x, 2), dtype=torch.float32, device=device)
+        _use_torch_stream(ctx, device)
+        _run(ctx, lambda: ctx.render_motion_tangent_device(fields, out))
+    return out
+
+
+class _ViewTangent(torch.autograd.Function):
+    """d img / d angles . t: one motion tangent render for the field sum_i t_i field_i.  Batched under vmap."""
+
+    @staticmethod
+    def forward(fr, alpha, q, angles, angles_t):
+        ctx = _current(fr, "jvp")
+        t = _plain(angles_t).detach().to("cpu", torch.float64).reshape(1, -1).numpy()
+        return _motion(ctx, t @ ctx.view_fields(), torch.device("cuda", ctx.device))[0]
+
+    @staticmethod
+    def setup_context(fctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(fctx, *grads):
+        _no_second("motion tangent")
+
+    @staticmethod
+    def jvp(fctx, *tangents):
+        _no_second("motion tangent")
+
+    @staticmethod
+    def vmap(info, in_dims, fr, alpha, q, angles, angles_t):
+        _unbatched_primals(in_dims[1:4])
+        ctx = _current(fr, "jvp")
+        t = _plain(angles_t).detach()
+        t = t.movedim(in_dims[4], 0) if in_dims[4] is not None else t.expand(info.batch_size, *t.shape)
+        t = t.to("cpu", torch.float64).reshape(info.batch_size, -1).numpy()
+        return _motion(ctx, t @ ctx.view_fields(), torch.device("cuda", ctx.device)), 0
+
+
+class _ViewAdjoint(torch.autograd.Function):
+    """grad_angles[i] = sum g * d img / d angle_i, summed in fp64: one motion tangent render for all the angles.  A batch
+    of upstream images (vmap) shares it."""
+
+    @staticmethod
+    def forward(fr, alpha, q, angles, grad_img):
+        ctx = _current(fr, "backward")
+        device = torch.device("cuda", ctx.device)
+        imgs = _motion(ctx, ctx.view_fields(), device)
+        with torch._C._DisableFuncTorch():
+            g = _plain(grad_img).detach().to(device=device, dtype=torch.float64)
+            return (imgs.to(torch.float64) * g).sum(dim=(1, 2, 3))
+
+    @staticmethod
+    def setup_context(fctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(fctx, *grads):
+        _no_second("motion tangent")
+
+    @staticmethod
+    def jvp(fctx, *tangents):
+        _no_second("motion tangent")
+
+    @staticmethod
+    def vmap(info, in_dims, fr, alpha, q, angles, grad_img):
+        _unbatched_primals(in_dims[1:4])
+        ctx = _current(fr, "backward")
+        device = torch.device("cuda", ctx.device)
+        imgs = _motion(ctx, ctx.view_fields(), device)
+        with torch._C._DisableFuncTorch():
+            g = _plain(grad_img).detach()
+            g = g.movedim(in_dims[4], 0) if in_dims[4] is not None else g.expand(info.batch_size, *g.shape)
+            g = g.to(device=device, dtype=torch.float64)
+            return torch.einsum("kyxc,nyxc->kn", g, imgs.to(torch.float64)), 0
+
+
+class _RenderView(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, angles: torch.Tensor):
+        _set_angles(ctx, angles)
+        return _Render.forward(ctx, alpha, q)
+
+    @staticmethod
+    def setup_context(fctx, inputs, output):
+        ctx, alpha, q, angles = inputs
+        _Render.setup_context(fctx, (ctx, alpha, q), output)
+        fctx.primals = (alpha, q, angles)
+        fctx.angles_meta = (angles.dtype, angles.device)
+
+    @staticmethod
+    def backward(fctx, grad_img: torch.Tensor):
+        _first_order(fctx, "backward")
+        alpha, q, angles = fctx.primals
+        ga_out = gq_out = gv_out = None
+        if fctx.needs_input_grad[1] or fctx.needs_input_grad[2]:
+            ga, gq = _Adjoint.apply(fctx, alpha, q, grad_img)
+            (a_dtype, a_dev), (q_dtype, q_dev) = fctx.meta
+            ga_out = ga.to(device=a_dev, dtype=a_dtype) if fctx.needs_input_grad[1] else None
+            gq_out = gq.to(device=q_dev, dtype=q_dtype) if fctx.needs_input_grad[2] else None
+        if fctx.needs_input_grad[3]:
+            dtype, dev = fctx.angles_meta
+            gv_out = _ViewAdjoint.apply(fctx, alpha, q, angles, grad_img).to(device=dev, dtype=dtype)
+        return None, ga_out, gq_out, gv_out
+
+    @staticmethod
+    def jvp(fctx, _ctx_tangent, alpha_t, q_t, angles_t):
+        _current(fctx, "jvp")
+        _first_order(fctx, "jvp")
+        alpha, q, angles = getattr(fctx, "primals", (None, None, None))
+        out = None
+        if alpha_t is not None or q_t is not None:
+            out = _Tangent.apply(fctx, alpha, q, alpha_t, q_t)
+        if angles_t is not None:
+            t = _ViewTangent.apply(fctx, alpha, q, angles, angles_t)
+            out = t if out is None else out + t
+        return out
+
+    @staticmethod
+    def vmap(info, in_dims, ctx, alpha, q, angles):
+        _unbatched_primals(in_dims[1:])
+        return _RenderView.apply(ctx, alpha, q, angles), None
+
+
+def render_view(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, angles: torch.Tensor) -> torch.Tensor:
+    """The frame of `ctx` with the scalars alpha and q and the view's angles `angles` ([n_rots] radians, written into the
+    context's current rotation list; axes and x0 are kept), differentiable in all three."""
+    return _RenderView.apply(ctx, alpha, q, angles)
+
+
 # ---- Gauss-Newton operators ------------------------------------------------------------------------------------------
 # H v = J^T W J v and diag(J^T W J) of the frame with the scalars (alpha, q): what a Gauss-Newton / CG fit calls in its
 # inner loop (course5_amd.fit).  Operators, not differentiable functions: the results carry no graph.
@@ -348,4 +498,4 @@ def gn_diagonal(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, weight=
     return da, dq
 
 
-__all__ = ["render", "gn_product", "gn_diagonal"]
+__all__ = ["render", "render_view", "gn_product", "gn_diagonal"]

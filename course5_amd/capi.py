@@ -32,6 +32,7 @@ EXPORTS = [
     "c5_render_tangent_batch", "c5_render_tangent_batch_device", "c5_render_adjoint_batch", "c5_render_adjoint_batch_device",
     "c5_update_scalars_device",
     "c5_render_gn_product", "c5_render_gn_product_device", "c5_render_gn_diagonal", "c5_render_gn_diagonal_device",
+    "c5_render_motion_tangent", "c5_render_motion_tangent_device", "c5_rotation_motion",
 ]
 
 
@@ -116,6 +117,9 @@ def load_library() -> C.CDLL:
     lib.c5_render_gn_product_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.c5_render_gn_diagonal.argtypes = [vp, C.POINTER(C.c_float), dp, dp]
     lib.c5_render_gn_diagonal_device.argtypes = [vp, vp, vp, vp]
+    lib.c5_render_motion_tangent.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_float)]
+    lib.c5_render_motion_tangent_device.argtypes = [vp, C.c_int, dp, vp]
+    lib.c5_rotation_motion.argtypes = [C.POINTER(Rotation), C.c_int, C.c_int, C.c_int, dp]
     for name in EXPORTS:
         if name not in ("c5_destroy", "c5_last_error"):
             getattr(lib, name).restype = C.c_int
@@ -165,6 +169,7 @@ class Context:
         # which set of scalars the context holds (course5_amd.autograd; None: the caller's own)
         self.scalars_owner = None
         self.stream_ptr = 0
+        self.rots = np.zeros((0, 3))  # the view as set_view last had it: rows (axis, angle, x0)
         # the library's instruments are off by default (they cost 5 % of a frame); tests and scripts read stats()["ms_*"] and
         # walk_kernel_ms() everywhere, so this wrapper switches them on - bench.py switches the stage events off again
         self.set_option("stage_timing", 1)
@@ -264,6 +269,7 @@ class Context:
     def set_view(self, rots):
         arr, n = _rot_array(rots)
         self._check(self.lib.c5_set_view(self.handle, arr, n))
+        self.rots = np.array(rots, dtype=np.float64).reshape(-1, 3)
         self.frame_state += 1
 
     def set_solid_view(self, slot: int, rots):
@@ -412,6 +418,46 @@ class Context:
             self.handle, k, C.c_void_p(_device_ptr(grad_out, torch.float32, (k, self.local_rows, self.res_x, 2))),
             C.c_void_p(_device_ptr(grad_alpha, torch.float64, (k, self.n_cells))),
             C.c_void_p(_device_ptr(grad_q, torch.float64, (k, self.n_cells)))))
+
+    # -- motion tangent render -----------------------------------------------------------------------
+    @staticmethod
+    def _motion_fields(fields) -> np.ndarray:
+        f = np.ascontiguousarray(fields, dtype=np.float64)
+        if f.ndim not in (1, 2) or f.shape[-1] != 12 or f.size == 0:
+            raise ValueError(f"fields must be [12] or [K, 12] (A row-major, then b), not {list(f.shape)}")
+        return f
+
+    def render_motion_tangent(self, fields) -> np.ndarray:
+        """The change of the frame render() would produce now when the grid moves in view space with the velocity field
+        u(p) = A p + b (fields [K, 12]: A row-major then b; rotation_motion gives a view angle's): float32 [K, local_rows,
+        res_x, 2] (tau_dot, I_dot); a single [12] field gives [local_rows, res_x, 2].  Synchronous; retries by itself.
+        Bit-reproducible, and every slice is bit for bit the call for that field alone."""
+        f = self._motion_fields(fields)
+        k = f.size // 12
+        out = np.zeros((k, self.local_rows, self.res_x, 2), dtype=np.float32)
+        self._check(self.lib.c5_render_motion_tangent(self.handle, k, _dp(f), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out[0] if f.ndim == 1 else out
+
+    def render_motion_tangent_device(self, fields, out):
+        """Asynchronous form on the context's stream: fields as above (host memory: they travel as kernel arguments), out a
+        float32 [K, local_rows, res_x, 2] contiguous torch tensor on this context's GPU or a raw device pointer.  The
+        status comes with the next synchronize() (C5_RETRY: run it again)."""
+        import torch
+        f = self._motion_fields(fields)
+        k = f.size // 12
+        self._check(self.lib.c5_render_motion_tangent_device(
+            self.handle, k, _dp(f), C.c_void_p(_device_ptr(out, torch.float32, (k, self.local_rows, self.res_x, 2)))))
+
+    def view_fields(self) -> np.ndarray:
+        """[n_rots, 12]: the velocity field of every angle of the current view (rotation_motion)."""
+        return np.array([rotation_motion(self.rots, i) for i in range(len(self.rots))]).reshape(-1, 12)
+
+    def render_view_tangent(self) -> np.ndarray:
+        """d image / d angle for every rotation of the current view (set_view): float32 [n_rots, local_rows, res_x, 2], per
+        radian."""
+        if len(self.rots) == 0:
+            return np.zeros((0, self.local_rows, self.res_x, 2), dtype=np.float32)
+        return self.render_motion_tangent(self.view_fields())
 
     # -- Gauss-Newton renders -----------------------------------------------------------------------
     def _weight_image(self, weight):
@@ -594,6 +640,18 @@ def face_adjacency(cells, n_pts: int):
     if rc != C5_OK:
         raise C5Error(rc, lib.c5_last_error(None).decode())
     return adj, nb.value
+
+
+def rotation_motion(rots, index: int, what: int = 0) -> np.ndarray:
+    """Host-only: the view-space velocity field [12] (A row-major, then b) of d / d(angle) (what 0) or d / d(x0) (what 1)
+    of rotation `index` of the view `rots` (rows (axis, angle, x0)), via c5_rotation_motion."""
+    lib = load_library()
+    arr, n = _rot_array(rots)
+    field = np.zeros(12, dtype=np.float64)
+    rc = lib.c5_rotation_motion(arr, n, index, what, _dp(field))
+    if rc != C5_OK:
+        raise C5Error(rc, lib.c5_last_error(None).decode())
+    return field
 
 
 def weld_points(xyz):

@@ -121,6 +121,37 @@ void launch_gn_weight(hipStream_t s, const float2* t, const float2* w, int64_t n
 void launch_gn_diag_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const int64_t* offs, void* segs,
                             const uint32_t* mask, double alpha_limit, const float2* weight, double* diag_a, double* diag_q);
 
+// ---- motion tangent (c5_render_motion_tangent*): the frame differentiated with respect to an affine motion of the grid in
+// view space, u(p) = A p + b
+
+constexpr int kMotionWidth = 8;  // fields one walk carries at most (the widest "batch_width")
+struct MotionField {
+    double f[12];  // A row-major, then b, in the walk coordinate (records of "integration" 0: w = view z)
+};
+// what finds a cell's faces where the walk has no plane for them: the cell's vertices in view space (device order)
+struct MotionGeometry {
+    const int4* cell_vert;
+    const double *vx, *vy, *vz;
+};
+struct MotionParams {
+    WalkParams w;          // as TangentParams
+    MotionGeometry geo;
+    float2* out;           // [n_used][n_local_rows][res_x] (tau_dot, I_dot): the chunk's first image
+    int64_t image_px;      // pixels per image
+    int32_t n_used;        // fields of the chunk (<= kc)
+    int32_t keep_entries;  // as TangentBatchParams
+    double field[kMotionWidth][12];  // the chunk's fields (zero beyond n_used): read by uniform loads
+};
+
+// tangent_walk's walk for kc (4 or 8) velocity fields; every image bit for bit that of its field alone at either width;
+// counts as tangent_walk does
+void launch_motion_walk(hipStream_t s, int kc, const MotionParams& m);
+
+// the same over bin_sort_resolve's lists, one field (sorts them in place, as launch_tangent_resolve)
+void launch_motion_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const double* Xtab, const double* Ytab,
+                           const int64_t* offs, void* segs, const uint32_t* mask, double alpha_limit, const MotionField& field,
+                           float2* out);
+
 // c5_update_scalars_device: alpha[i] = alpha_src[perm[i]], q[i] = q_src[perm[i]] (perm nullptr: the identity), and into
 // stats[3] (zeroed by the caller): the bits of the largest alpha > 0, the complemented bits of the smallest alpha >=
 // DBL_EPSILON, and 1 if some alpha is NaN (the host loop of c5_update_scalars, as an order-free max / min / or)

@@ -30,6 +30,24 @@
 // No atomics and no pre-pass: every pixel's sum runs in the reference's order on one lane, so the tangent IS
 // bit-reproducible from run to run.
 //
+// The motion tangent (c5_render_motion_tangent*): the change of every pixel when the grid moves rigidly or affinely in
+// view space with the velocity field u(p) = A p + b (a change of a view angle is one such field, c5_rotation_motion),
+// the cells' scalars held.  The rays are parallel to z, and a face is a plane w = c + gx x + gy y: its depth at the
+// pixel (x, y) changes by dw = u_z(P) - gx u_x(P) - gy u_y(P), P = (x, y, w) the point hit.  With ddz_k = dw_exit,k -
+// dw_entry,k the change of the k-th chord,
+//     tau_dot = sum_k alpha_k ddz_k                                              (raw alpha, every segment)
+//     I_dot_k = E_k I_dot_{k-1} + E_k (Q_k - a_k I_{k-1}) ddz_k                  (active segments; dI_k / ddz_k)
+// (a clamped alpha still moves with its chord: the clamp is on alpha).  Pixels that gain or lose coverage - silhouettes,
+// a ray that crosses an edge into another list of cells - are not differentiated: the result is the derivative of the
+// smooth piece the pixel is on.
+//   motion_walk<KC>   tangent_walk's frame for KC fields: I, and per field I_dot, tau_dot and the dw of the face the ray
+//                     entered its cell through.  An interior step hands the exit face's dw on; a boundary entry (the
+//                     ray's start, a re-entry, a pick-up across a hanging-node interface) has no plane in the record of
+//                     the cell entered and finds the face from the cell's four vertices (cell_faces).  The fields are
+//                     kernel arguments: uniform loads.
+//   motion_resolve    the same over bin_sort_resolve's lists: both faces of every segment from the cell's vertices.
+// No atomics, no pre-pass: bit-reproducible, like the tangent.
+//
 // Every walk kernel here (the batched and Gauss-Newton ones further down included) takes its rays through adj::Ray: ONE
 // definition of the walk's step, of how a ray begins and of what it leaves behind.  The kernels differ in what they
 // accumulate along the ray, and those that differ in nothing else share a body with a compile-time parameter
@@ -86,6 +104,24 @@ __device__ __forceinline__ StepGeometry step_geometry(const CellRegs& cur, doubl
     g.w_exit = fmin(w0, fmin(w1, w2));  // (never NaN: a candidate is a finite depth or +inf)
     g.w_out = (w0 == g.w_exit) ? n0 : (w1 == g.w_exit) ? n1 : n2;
     return g;
+}
+
+// step_geometry, and the exit face's slopes beside it (the motion tangent: how the face's depth moves)
+struct SlopedExit {
+    double w_exit;
+    uint32_t w_out;
+    double gx, gy;
+};
+__device__ __forceinline__ SlopedExit step_geometry_sloped(const CellRegs& cur, double x, double y) {
+    const StepGeometry g = step_geometry(cur, x, y);
+    const double w0 = fma(cur.r0.b, x, fma(cur.r1.a, y, cur.r0.a));
+    const double w1 = fma(cur.r2.a, x, fma(cur.r2.b, y, cur.r1.b));
+    SlopedExit s;
+    s.w_exit = g.w_exit;
+    s.w_out = g.w_out;
+    s.gx = (w0 == g.w_exit) ? cur.r0.b : (w1 == g.w_exit) ? cur.r2.a : cur.r3.b;
+    s.gy = (w0 == g.w_exit) ? cur.r1.a : (w1 == g.w_exit) ? cur.r2.b : cur.r4.a;
+    return s;
 }
 
 // (1 - e^-x) / x = sum_m (-x)^m / (m + 1)!  for 0 <= x < 1/8 (truncation below 1e-19)
@@ -868,6 +904,170 @@ __global__ __launch_bounds__(256) void scalars_gather(const double* __restrict__
     }
 }
 
+// ---- motion tangent (c5_render_motion_tangent*) ---------------------------------------------------------------------------
+
+namespace adj {
+
+// dw = u_z(P) - gx u_x(P) - gy u_y(P) at P = (x, y, w) for the field f = {A row-major, b}: how the depth of a face of
+// slopes (gx, gy) moves at the pixel.  w is the innermost term: nothing of this is invariant along the ray, so the
+// compiler keeps no per-field registers for it.
+__device__ __forceinline__ double face_dw(const double* f, double gx, double gy, double x, double y, double w) {
+    const double ux = fma(f[0], x, fma(f[1], y, fma(f[2], w, f[9])));
+    const double uy = fma(f[3], x, fma(f[4], y, fma(f[5], w, f[10])));
+    const double uz = fma(f[6], x, fma(f[7], y, fma(f[8], w, f[11])));
+    return fma(-gy, uy, fma(-gx, ux, uz));
+}
+
+// The two faces of `cell` the ray of pixel (x, y) runs between, from the cell's view-space vertices: a tetrahedron is
+// convex, so among the faces it lies ABOVE (face_plane: kind < 0; a ray along +z enters through one of them) the one
+// met is the deepest at (x, y), and among those it lies below the shallowest.  Faces edge-on to rounding (kind 0) are
+// never candidates.  found: both exist.
+struct FaceAt {
+    double w, gx, gy;
+};
+struct CellFaces {
+    FaceAt in, out;
+    bool found;
+};
+__device__ __forceinline__ CellFaces cell_faces(const MotionGeometry& G, int cell, double x, double y) {
+    const int4 cv = G.cell_vert[cell];
+    const int vid[4] = {cv.x, cv.y, cv.z, cv.w};
+    double p[4][3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        p[k][0] = G.vx[vid[k]];
+        p[k][1] = G.vy[vid[k]];
+        p[k][2] = G.vz[vid[k]];
+    }
+    CellFaces r;
+    r.in = FaceAt{-INFINITY, 0.0, 0.0};
+    r.out = FaceAt{INFINITY, 0.0, 0.0};
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+        const FacePlane fp = face_plane(p, f);
+        const double w = fma(fp.gx, x - p[0][0], fma(fp.gy, y - p[0][1], fp.c));
+        if (fp.kind < 0 && w > r.in.w) r.in = FaceAt{w, fp.gx, fp.gy};
+        if (fp.kind > 0 && w < r.out.w) r.out = FaceAt{w, fp.gx, fp.gy};
+    }
+    r.found = r.in.w > -INFINITY && r.out.w < INFINITY;
+    return r;
+}
+
+}  // namespace adj
+
+// tangent_walk's frame for KC velocity fields.  Nothing is shared between the lanes: a lane leaves when its ray ends.
+template <int KC>
+__global__ __launch_bounds__(64) void motion_walk(MotionParams A) {
+    using namespace adj;
+    const WalkParams& P = A.w;
+    Ray r;
+    double I = 0.0, I_dot[KC], tau_dot[KC], dw_carry[KC];  // dw_carry: of the face the ray entered its cell through
+#pragma unroll
+    for (int j = 0; j < KC; ++j) I_dot[j] = tau_dot[j] = dw_carry[j] = 0.0;
+
+    const EntryHead ent = ray_begin(r, P);
+
+    // a boundary entry into `cell`: the entry face from the cell's vertices (rare: a few times per ray)
+    auto enter = [&](int cell) {
+        const CellFaces cf = cell_faces(A.geo, cell, r.x, r.y);
+#pragma unroll
+        for (int j = 0; j < KC; ++j) dw_carry[j] = cf.found ? face_dw(A.field[j], cf.in.gx, cf.in.gy, r.x, r.y, cf.in.w) : 0.0;
+    };
+
+    CellRegs cur;
+    if (r.cell >= 0) {
+        load_cell(cur, P.xrec, r.cell);
+        enter(r.cell);
+    }
+
+    while (r.cell >= 0) {
+        const SlopedExit se = step_geometry_sloped(cur, r.x, r.y);  // (ray_step's own geometry: the same operations, once)
+        double dz, carry_next;
+        const int nb = ray_step(r, P, ent, cur, dz, carry_next);
+        CellRegs nxt;
+        if (nb >= 0) load_cell(nxt, P.xrec, nb);
+
+        const bool has_exit = se.w_exit < INFINITY;
+        // nb, if any, lies behind the exit face (else it is a boundary entry)
+        const bool through_face = has_exit && (se.w_out & kIdMask) != kNoCell;
+        double dw_exit[KC];
+#pragma unroll
+        for (int j = 0; j < KC; ++j) dw_exit[j] = has_exit ? face_dw(A.field[j], se.gx, se.gy, r.x, r.y, se.w_exit) : 0.0;
+
+        if (is_segment(dz)) {
+            const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+            double ddz[KC];
+#pragma unroll
+            for (int j = 0; j < KC; ++j) {
+                ddz[j] = dw_exit[j] - dw_carry[j];
+                tau_dot[j] = fma(a_raw, ddz[j], tau_dot[j]);  // d tau / d dz (raw alpha)
+            }
+            if (a != 0.0) {
+                const double E = exp_nonpositive(-a * dz);
+                const double dI_ddz = E * fma(-a, I, q);  // d I_k / d dz_k (the clamp is on alpha, not on the chord)
+#pragma unroll
+                for (int j = 0; j < KC; ++j) I_dot[j] = fma(E, I_dot[j], dI_ddz * ddz[j]);
+                I = segment_terms(a, q, dz, E, 1.0, I).I_next;
+            }
+        }
+        if (nb >= 0) {
+            if (through_face) {
+#pragma unroll
+                for (int j = 0; j < KC; ++j) dw_carry[j] = dw_exit[j];
+            } else {
+                enter(nb);
+            }
+        }
+        ray_advance(r, nb, carry_next);
+        cur = nxt;
+    }
+
+    if (r.in_image) {
+#pragma unroll
+        for (int j = 0; j < KC; ++j)
+            if (j < A.n_used)
+                A.out[static_cast<size_t>(j) * A.image_px + r.lp] = make_float2(static_cast<float>(tau_dot[j]), static_cast<float>(I_dot[j]));
+    }
+    if (!A.keep_entries) ray_clear_head(r, P);
+    ray_count(r, P);
+}
+
+// tangent_resolve's twin: the same sort, the same back-to-front order; both faces of a segment from its cell's vertices.
+__global__ __launch_bounds__(256) void motion_resolve(GridView g, ImageParams im, const double* __restrict__ Xtab,
+                                                      const double* __restrict__ Ytab, const int64_t* __restrict__ offs,
+                                                      AdjSegment* __restrict__ segs, const uint32_t* __restrict__ mask,
+                                                      double alpha_limit, MotionField field, float2* __restrict__ out) {
+    using namespace adj;
+    const int64_t lp = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    if (lp >= n_px) return;
+    double I = 0.0, I_dot = 0.0, tau_dot = 0.0;
+    if (!(mask && mask[lp])) {
+        const int lrow = static_cast<int>(lp / im.res_x);
+        const double x = Xtab[lp - static_cast<int64_t>(lrow) * im.res_x], y = Ytab[global_row_of(im, lrow)];
+        const MotionGeometry geo{g.cell_vert, g.vx, g.vy, g.vz};
+        AdjSegment* const list = segs + offs[lp];
+        const int n = static_cast<int>(offs[lp + 1] - offs[lp]);
+        sort_segments(list, n);
+        for (int i = n - 1; i >= 0; --i) {
+            const int c = static_cast<int>(list[i].cell);
+            const double dz = list[i].dz, q = g.q[c], a_raw = g.alpha[c];
+            const ClampedAlpha ca = clamp_alpha(a_raw, alpha_limit);
+            const CellFaces cf = cell_faces(geo, c, x, y);
+            const double ddz = cf.found ? face_dw(field.f, cf.out.gx, cf.out.gy, x, y, cf.out.w) -
+                                              face_dw(field.f, cf.in.gx, cf.in.gy, x, y, cf.in.w)
+                                        : 0.0;
+            tau_dot = fma(a_raw, ddz, tau_dot);
+            if (ca.active) {
+                const double E = exp(-ca.a * dz);
+                I_dot = fma(E, I_dot, E * fma(-ca.a, I, q) * ddz);
+                I = segment_terms(ca.a, q, dz, E, 1.0, I).I_next;
+            }
+        }
+    }
+    out[lp] = make_float2(static_cast<float>(tau_dot), static_cast<float>(I_dot));
+}
+
 namespace {
 // workgroups of a walk kernel: one wavefront per 8x8 pixel tile (0: no pixel)
 unsigned tile_blocks(const ImageParams& im) {
@@ -971,6 +1171,20 @@ void launch_gn_diag_resolve(hipStream_t s, const GridView& g, const ImageParams&
     if (!blocks) return;
     hipLaunchKernelGGL(gn_diag_resolve, dim3(blocks), dim3(256), 0, s, g, im, offs, static_cast<AdjSegment*>(segs), mask, alpha_limit,
                        weight, diag_a, diag_q);
+}
+
+void launch_motion_walk(hipStream_t s, int kc, const MotionParams& m) {
+    const unsigned blocks = tile_blocks(m.w.im);
+    if (blocks) C5_LAUNCH_KC(motion_walk, kc, blocks, 64, s, m);
+}
+
+void launch_motion_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const double* Xtab, const double* Ytab,
+                           const int64_t* offs, void* segs, const uint32_t* mask, double alpha_limit, const MotionField& field,
+                           float2* out) {
+    const unsigned blocks = pixel_blocks(im);
+    if (!blocks) return;
+    hipLaunchKernelGGL(motion_resolve, dim3(blocks), dim3(256), 0, s, g, im, Xtab, Ytab, offs, static_cast<AdjSegment*>(segs), mask,
+                       alpha_limit, field, out);
 }
 
 void launch_scalars_gather(hipStream_t s, const double* alpha_src, const double* q_src, const int32_t* perm, int64_t n, double* alpha,

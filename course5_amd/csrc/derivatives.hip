@@ -354,6 +354,42 @@ int enqueue_gn_product(c5_context* ctx, int n, const double* d_alpha, const doub
     return commit_derivative(ctx, "gn product");
 }
 
+// The motion tangent: n velocity fields (host memory, [n][12]: A row-major then b, view space) -> out[n][local_rows][res_x]:
+// one per-view setup, then per chunk of up to `width` fields one walk; the heads stay in place between the chunks and the
+// last walk hands them back cleared.  The derivative's records are those of "integration" 0, whose walk coordinate IS
+// view z (walk_common.hpp: to_exit_record, sign +1): the fields go to the kernels as they are.  On bin_sort_resolve's
+// lists: motion_resolve per field (the first sorts the lists, the others find them sorted).
+int enqueue_motion(c5_context* ctx, int n, const double* fields, float2* out) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    if (v.no_cells) return zero_tangents(ctx, v, n, out);
+    if (v.bin_sort) {
+        for (int j = 0; j < n; ++j) {
+            c5::MotionField f;
+            std::copy(fields + 12 * j, fields + 12 * j + 12, f.f);
+            c5::launch_motion_resolve(v.s, v.g, ctx->im, ctx->xtab.as<double>(), ctx->ytab.as<double>(), ctx->offs64.as<int64_t>(),
+                                      ctx->segs.ptr, v.mask, ctx->alpha_limit, f, out + j * v.n_px);
+        }
+        return commit_derivative(ctx, "motion tangent");
+    }
+    const int width = batch_width(ctx, n);
+    c5::MotionParams mp{};
+    mp.w = v.w;
+    mp.geo = c5::MotionGeometry{v.g.cell_vert, v.g.vx, v.g.vy, v.g.vz};
+    mp.image_px = v.n_px;
+    for (int k0 = 0; k0 < n; k0 += width) {
+        mp.n_used = std::min(width, n - k0);
+        mp.out = out + k0 * v.n_px;
+        mp.keep_entries = k0 + width < n;
+        for (int j = 0; j < c5::kMotionWidth; ++j)
+            for (int i = 0; i < 12; ++i) mp.field[j][i] = j < mp.n_used ? fields[12 * (k0 + j) + i] : 0.0;
+        c5::launch_motion_walk(v.s, width, mp);
+    }
+    ctx->slots[0].head_clean = true;  // (the last chunk's walk hands every head back cleared)
+    return commit_derivative(ctx, "motion tangent");
+}
+
 // diag(J^T W J): adjoint_one with the squared kernels.  weight null: ones.
 int enqueue_gn_diagonal(c5_context* ctx, const float2* weight, double* da_out, double* dq_out) {
     DerivativeView v;
@@ -393,7 +429,7 @@ int finish_adjoint(c5_context* ctx) {
 
 namespace {
 
-// What the twelve derivative entry points check before anything else, in this order: the context; a batch's size; the
+// What the fourteen derivative entry points check before anything else, in this order: the context; a batch's size; the
 // call's own pointers (`required_ok`, and `per_cell_ok` where the grid has cells); no c5_render_host_async frame
 // outstanding; and for the host-pointer forms the image, after which the device is bound.
 struct DerivativeCall {
@@ -587,6 +623,70 @@ int c5_render_gn_diagonal(c5_context* ctx, const float* weight_host, double* dia
     return run_staged(ctx, "gn diagonal", b, [&] {
         return enqueue_gn_diagonal(ctx, b[0].as<const float2>(), b[1].as<double>(), b[2].as<double>());
     });
+}
+
+// The fields are host memory in both forms: they travel as kernel arguments.
+int c5_render_motion_tangent_device(c5_context* ctx, int n_dirs, const double* fields_host, void* out_dev) {
+    int rc = check_derivative(ctx, {"c5_render_motion_tangent", false, n_dirs, "field", fields_host && out_dev, true,
+                                    "null field or output pointer"});
+    if (rc) return rc;
+    return enqueue_motion(ctx, n_dirs, fields_host, static_cast<float2*>(out_dev));
+}
+
+int c5_render_motion_tangent(c5_context* ctx, int n_dirs, const double* fields_host, float* out_host) {
+    int rc = check_derivative(ctx, {"c5_render_motion_tangent", true, n_dirs, "field", fields_host && out_host, true,
+                                    "null field or output pointer"});
+    if (rc) return rc;
+    Staged b[] = {{nullptr, out_host, n_dirs * image_bytes(ctx)}};
+    return run_staged(ctx, "motion tangent", b, [&] { return enqueue_motion(ctx, n_dirs, fields_host, b[0].as<float2>()); });
+}
+
+// Host only.  The view is p -> R_n(... R_1(p)), R_k(p) = M_k (p - o_k) + o_k (axis 0: about the x axis, o = 0; axis 1: about
+// the line x = x0, z = 0).  With s the point after rotation `index` and L = R_n ... R_{index+1} = (M_L, t_L) the rest:
+//   d s / d angle = G (s - o), G = M' M^T the generator (axis 0: (0, -z, y); axis 1: (-z, 0, x - x0));
+//   d s / d x0    = (I - M) e_x = (1 - cos, 0, -sin)  (axis 1; axis 0 has no x0: the zero field);
+// and in view space, s = M_L^T (p - t_L): u(p) = M_L G M_L^T (p - t_L) - M_L G o, or the constant M_L d.
+int c5_rotation_motion(const c5_rotation* rots, int n_rots, int index, int what, double field[12]) {
+    if (!rots || !field || n_rots < 1 || n_rots > c5::kMaxRotations || index < 0 || index >= n_rots || (what != 0 && what != 1))
+        return fail(nullptr, C5_ERR_INVALID, "c5_rotation_motion: bad rotation list, index or what");
+    for (int k = 0; k < n_rots; ++k)
+        if (rots[k].axis != 0 && rots[k].axis != 1) return fail(nullptr, C5_ERR_INVALID, "rotation axis must be 0 (x) or 1 (y)");
+    double M[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, t[3] = {0, 0, 0};  // L so far: p -> M p + t
+    for (int k = index + 1; k < n_rots; ++k) {
+        const double c = std::cos(rots[k].angle), s = std::sin(rots[k].angle), x0 = rots[k].axis == 1 ? rots[k].x0 : 0.0;
+        const int i = rots[k].axis == 0 ? 1 : 0;  // the rotation mixes rows i and 2: (r_i, r_2) <- (c r_i - s r_2, s r_i + c r_2)
+        t[0] -= x0;
+        for (int j = 0; j < 3; ++j) {
+            const double a = M[i][j], b = M[2][j];
+            M[i][j] = c * a - s * b;
+            M[2][j] = s * a + c * b;
+        }
+        const double a = t[i], b = t[2];
+        t[i] = c * a - s * b;
+        t[2] = s * a + c * b;
+        t[0] += x0;
+    }
+    const c5_rotation& r = rots[index];
+    double A[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, bb[3] = {0, 0, 0};
+    if (what == 0) {
+        const int i = r.axis == 0 ? 1 : 0;  // G: u_i = -s_2, u_2 = s_i - o_i
+        const double o[3] = {r.axis == 1 ? r.x0 : 0.0, 0.0, 0.0};
+        double MG[3][3];  // M G: column 2 = -M[:, i], column i = M[:, 2]
+        for (int a = 0; a < 3; ++a)
+            for (int j = 0; j < 3; ++j) MG[a][j] = j == 2 ? -M[a][i] : (j == i ? M[a][2] : 0.0);
+        for (int a = 0; a < 3; ++a)
+            for (int j = 0; j < 3; ++j) A[a][j] = MG[a][0] * M[j][0] + MG[a][1] * M[j][1] + MG[a][2] * M[j][2];
+        for (int a = 0; a < 3; ++a)
+            bb[a] = -(A[a][0] * t[0] + A[a][1] * t[1] + A[a][2] * t[2]) - (MG[a][0] * o[0] + MG[a][1] * o[1] + MG[a][2] * o[2]);
+    } else if (r.axis == 1) {
+        const double d[3] = {1.0 - std::cos(r.angle), 0.0, -std::sin(r.angle)};
+        for (int a = 0; a < 3; ++a) bb[a] = M[a][0] * d[0] + M[a][1] * d[1] + M[a][2] * d[2];
+    }
+    for (int a = 0; a < 3; ++a) {
+        for (int j = 0; j < 3; ++j) field[3 * a + j] = A[a][j];
+        field[9 + a] = bb[a];
+    }
+    return C5_OK;
 }
 
 }  // extern "C"

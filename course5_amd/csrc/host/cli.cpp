@@ -58,6 +58,7 @@ const option_spec kOptions[] = {
     {"sweep", 0, true, "angle advanced per frame: X, Y, D or I", "Y"},
     {"sweep_step", 0, true, "sweep increment per frame, units of pi", "0.00555556"},
     {"contribution", 0, true, "after the frame, write the grid with Contribution = Q dSum(I)/dQ and dI_dAbsorpCoef = dSum(I)/dAbsorpCoef per cell to this legacy .vtk (one frame, one GPU)", nullptr},
+    {"view_tangent", 0, true, "after the frame, write d image / d angle (per radian, two channels like the frame) for every rotation of the grid's view to <arg>_X.vti (the last, about x: -X), <arg>_Y.vti (about y: -Y) and <arg>_I.vti (the first, about x: -I) (one frame, one GPU)", nullptr},
     {"sensitivity", 0, true, "after the frame, write the grid with SensAbsorpCoef and SensRadEnLooseRate = the diagonal of J^T J per cell (J: the image's Jacobian; 0: the image does not see the cell) to this legacy .vtk (one frame, one GPU)", nullptr},
 };
 
@@ -174,6 +175,7 @@ bool program_options(int argc, char** argv, std::ostream& out) {
         else if (n == "sweep_step") cfg.sweep_step = to_double(n, v);
         else if (n == "contribution") cfg.contribution = v;
         else if (n == "sensitivity") cfg.sensitivity = v;
+        else if (n == "view_tangent") cfg.view_tangent = v;
     };
 
     for (int i = 1; i < argc; ++i) {
@@ -227,6 +229,12 @@ bool program_options(int argc, char** argv, std::ostream& out) {
         if (cfg.bench > 0) throw std::runtime_error("option '--contribution' cannot be used with '--bench'");
         if (more_than_one_device(cfg.devices))
             throw std::runtime_error("option '--contribution' cannot be used with more than one of '--devices'");
+    }
+    if (!cfg.view_tangent.empty()) {  // the motion tangent of ONE frame on ONE GPU
+        if (cfg.frames > 1) throw std::runtime_error("option '--view_tangent' cannot be used with '--frames' above 1");
+        if (cfg.bench > 0) throw std::runtime_error("option '--view_tangent' cannot be used with '--bench'");
+        if (more_than_one_device(cfg.devices))
+            throw std::runtime_error("option '--view_tangent' cannot be used with more than one of '--devices'");
     }
     if (!cfg.sensitivity.empty()) {  // the Gauss-Newton diagonal of ONE frame on ONE GPU
         if (cfg.frames > 1) throw std::runtime_error("option '--sensitivity' cannot be used with '--frames' above 1");

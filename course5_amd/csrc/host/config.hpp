@@ -49,6 +49,7 @@ struct render_config {
     std::string sweep = "Y";      // which angle advances per frame: X, Y, D or I
     double sweep_step = 1.0 / 180.0;
     std::string contribution;     // after the frame: the grid with each cell's share of the image's intensity (adjoint render)
+    std::string view_tangent;     // after the frame: PREFIX of one two-channel .vti per grid rotation, d image / d angle (motion tangent render)
     std::string sensitivity;      // after the frame: the grid with diag(J^T J) per cell for both scalars (Gauss-Newton diagonal render)
 };
 

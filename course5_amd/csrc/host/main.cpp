@@ -377,6 +377,14 @@ int main(int argc, char** argv) try {
                          {{"AbsorpCoef", &d.value0}, {"radEnLooseRate", &d.value1}, {"SensAbsorpCoef", &s_alpha}, {"SensRadEnLooseRate", &s_q}});
         std::cout << "Cell sensitivities written to " << config.sensitivity << std::endl;
     }
+    if (!config.view_tangent.empty()) {
+        // motion tangent render of this frame: d image / d angle for the grid's rotations (apply_view: the first turns the
+        // system about x by -I, then -Y about y, the last about x carries -X), per radian
+        const std::vector<object2d> tangents = base_plane.view_tangents();
+        const char* const names[] = {"_I", "_Y", "_X"};
+        for (std::size_t i = 0; i < tangents.size() && i < 3; ++i) write_frame(tangents[i], config.view_tangent + names[i] + ".vti");
+        std::cout << "View tangents written to " << config.view_tangent << "_{X,Y,I}.vti" << std::endl;
+    }
     if (config.print_stats) {
         const c5_stats st = base_plane.stats();
         std::cout << "GPU frame: " << st.ms_total << " ms (transform " << st.ms_transform << ", records " << st.ms_records

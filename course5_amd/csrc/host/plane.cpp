@@ -803,3 +803,21 @@ void plane::sensitivities(std::vector<double>& diag_alpha, std::vector<double>& 
     diag_q.assign(_n_cells, 0.0);
     check(c5_render_gn_diagonal(_ctx[0], nullptr, diag_alpha.data(), diag_q.data()), "c5_render_gn_diagonal");
 }
+
+std::vector<object2d> plane::view_tangents() {
+    if (_ctx.size() != 1) throw std::runtime_error("the motion tangent render runs on one device");
+    if (!_flight.empty() || !_parked.empty()) throw std::runtime_error("the motion tangent render wants no frame in flight");
+    const int n = static_cast<int>(_views.grid.size());
+    std::vector<object2d> out;
+    if (n == 0) return out;
+    int rows = 0;
+    check(c5_local_rows(_ctx[0], &rows), "c5_local_rows");
+    std::vector<double> fields(12 * static_cast<std::size_t>(n));
+    for (int i = 0; i < n; ++i) check(c5_rotation_motion(_views.grid.data(), n, i, 0, &fields[12 * i]), "c5_rotation_motion");
+    const std::size_t per_image = static_cast<std::size_t>(rows) * _x * 2;
+    std::vector<float> images(per_image * n);
+    check(c5_render_motion_tangent(_ctx[0], n, fields.data(), images.data()), "c5_render_motion_tangent");
+    for (int i = 0; i < n; ++i)
+        out.emplace_back(std::vector<float>(images.begin() + i * per_image, images.begin() + (i + 1) * per_image), _x, static_cast<std::size_t>(rows));
+    return out;
+}

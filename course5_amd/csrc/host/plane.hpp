@@ -103,6 +103,9 @@ public:
     // Gauss-Newton diagonal render (c5_render_gn_diagonal) of the current view at unit weights: diag(J^T J) for alpha and
     // for Q of every cell of the merged volume grid, in its order.  One device, no frame in flight.
     void sensitivities(std::vector<double>& diag_alpha, std::vector<double>& diag_q);
+    // Motion tangent render (c5_render_motion_tangent) of the current view: d image / d angle, per radian, for every rotation
+    // of the volume grid's list (c5_rotation_motion), in the list's order.  One device, no frame in flight.
+    std::vector<object2d> view_tangents();
 
     std::size_t get_x() const { return _x; }
     std::size_t get_y() const { return _y; }

@@ -106,3 +106,27 @@ def gn_step(ctx, alpha, q, residual, weight=None, fit=("q",), damping: float = 0
         p = z + (rz_next / rz) * p
         rz = rz_next
     return split(x), models
+
+
+def view_step(ctx, alpha, q, angles, residual, weight=None, damping: float = 0.0):
+    """One Gauss-Newton step for the angles of the view (the pose: what a fit to observations has to find first).  The
+    angles ([n_rots] radians) are written into the context's rotation list as autograd.render_view writes them; with
+    J = d img / d angles from ONE motion tangent render (n_rots images), r = render_view(alpha, q, angles) - target and W
+    the per-pixel weights ([local_rows, res_x, 2]; None: ones) it solves the dense n_rots x n_rots system
+        (J^T W J + damping diag(J^T W J)) d = -J^T W r
+    in float64.  Returns (d, model): the step, float64 [n_rots] on the context's GPU, and the quadratic model's value
+    1/2 d^T J^T W J d + d^T J^T W r there.  No line search and no outer loop: the caller owns both.  An angle the image
+    does not depend on (a singular system) needs damping > 0."""
+    from . import autograd
+    autograd._set_angles(ctx, angles)
+    device = autograd._gn_enter(ctx, alpha, q, "view_step")
+    J = autograd._motion(ctx, ctx.view_fields(), device).to(torch.float64).reshape(len(ctx.rots), -1)
+    r = residual.detach().to(device=device, dtype=torch.float64).reshape(-1)
+    if r.shape[0] != J.shape[1]:
+        raise ValueError(f"residual must be [{ctx.local_rows}, {ctx.res_x}, 2]")
+    w = autograd._gn_weight(ctx, weight, device)
+    JW = J if w is None else J * w.to(torch.float64).reshape(1, -1)
+    H = JW @ J.T
+    g = JW @ r
+    d = torch.linalg.solve(H + damping * torch.diag(torch.diagonal(H)), -g)
+    return d, float(0.5 * d @ H @ d + d @ g)

@@ -362,6 +362,35 @@ int c5_render_gn_product_device(c5_context* ctx, int n_dirs, const void* d_alpha
 int c5_render_gn_diagonal(c5_context* ctx, const float* weight_host, double* diag_alpha_host, double* diag_q_host);
 int c5_render_gn_diagonal_device(c5_context* ctx, const void* weight_dev, void* diag_alpha_dev, void* diag_q_dev);
 
+/* --- motion tangent render ---------------------------------------------------------------------------
+ * The frame c5_render would produce NOW differentiated with respect to the GEOMETRY, the cells' scalars held: the grid
+ * moves in view space with an affine velocity field u(p) = A p + b, and out is the change of every pixel per unit of that
+ * motion.  A change of a view angle is one such field (c5_rotation_motion), so is a shift or a stretch of the grid.
+ * The rays are parallel to z and a face is a plane w = c + gx x + gy y: its depth at the pixel (x, y) changes by
+ *     dw = u_z(P) - gx u_x(P) - gy u_y(P),   P = (x, y, w) the point the ray hits,
+ * a segment's chord by ddz_k = dw_exit,k - dw_entry,k, and with the adjoint's numbering and conventions
+ *     tau_dot = sum_k alpha_k ddz_k                                   (raw alpha, every segment)
+ *     I_dot_k = E_k I_dot_{k-1} + E_k (Q_k - a_k I_{k-1}) ddz_k       (active segments)
+ * A clamped alpha still moves with its chord (the clamp is on alpha); a cell with clamped alpha < DBL_EPSILON adds nothing
+ * to I_dot; solid-marked and uncovered pixels are 0 in both channels (a solid's own motion is not differentiated); whole
+ * rays in the reference's order whatever "integration", "depth_split", "lds_stage" or "tile" say.
+ * Pixels that GAIN OR LOSE coverage under the motion - silhouettes, a ray that crosses an edge into another list of
+ * cells - are not differentiated: the result is the derivative of the smooth piece the pixel is on (the image is
+ * piecewise smooth in the pose; the jumps are of the size of one chord).
+ * fields: [n_dirs][12] fp64 in HOST memory in both forms (they travel as kernel arguments): A row-major, then b, in view
+ * space (x, y the image's axes, z towards the viewer's depth).  out: [n_dirs][local_rows][res_x][2] fp32, the output's own
+ * layout (row range and row tiles as for a frame).  More than "batch_width" fields run as chunks over one per-view setup;
+ * every slice is bit for bit what the call returns for that field alone.  One walk per ray, no atomics: bit-reproducible.
+ * Status, retries, side effects and the refusal while c5_render_host_async frames are outstanding: as
+ * c5_render_tangent_batch's (the adjoint's counters and status words, never a frame's; a c5_render afterwards returns the
+ * bits it would have returned without it).  c5_render_motion_tangent is synchronous into host memory and retries by
+ * itself; the _device form is asynchronous on the context's stream into device memory.
+ * c5_rotation_motion: host only, no context, no GPU.  field[12] = the view-space velocity field of d / d(rots[index].angle)
+ * (what 0) or d / d(rots[index].x0) (what 1; zero for axis 0) of the view c5_set_view(rots, n_rots) sets. */
+int c5_render_motion_tangent(c5_context* ctx, int n_dirs, const double* fields_host, float* out_host);
+int c5_render_motion_tangent_device(c5_context* ctx, int n_dirs, const double* fields_host, void* out_dev);
+int c5_rotation_motion(const c5_rotation* rots, int n_rots, int index, int what, double field[12]);
+
 /* --- frames delivered to host memory, pipelined ----------------------------------------------------
  * plane::trace_rays hands back HOST pixels (plane.cpp:144-172); over PCIe Gen5 a 2400x1800 image is
  * 0.65 ms of transfer beside 0.7 ms of rendering, so the two are overlapped: c5_render_host_async renders
