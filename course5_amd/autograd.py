@@ -40,6 +40,15 @@ sum_i t_i field_i; under vmap, batches of angle tangents go to one batched call 
 Pixels that gain or lose coverage when the view turns are not differentiated (include/course5_hip.h): the derivative is
 that of the smooth piece every pixel is on.  alpha and q are differentiated as by render.
 
+render_mesh(ctx, xyz, alpha, q) is render with the grid's points as a differentiable input: xyz [n_pts, 3] in the order
+and the coordinates of upload_grid go to the context through c5_update_points when they differ from the ones it holds
+(connectivity, weld groups and cell order stay; through host memory, the call waits for the stream).  Backward is ONE
+vertex adjoint render (c5_render_vertex_adjoint_device) for xyz and the adjoint render for alpha and q, whichever
+needs_input_grad asks for; a point welded to another at upload gets a zero gradient, its representative the group's sum.
+There is no per-vertex forward mode: a tangent on xyz (jvp, jacfwd) raises, as second derivatives do; tangents on alpha and
+q go through the tangent render as in render.  Under vmap a batch of cotangents (jacrev) loops the single vertex adjoint
+call: there is no batched form.
+
 Beside render, two operators for Gauss-Newton fits (course5_amd.fit): gn_product(ctx, alpha, q, v_alpha, v_q, weight) =
 J^T W J v and gn_diagonal(ctx, alpha, q, weight) = diag(J^T W J), one library call each (c5_render_gn_product_device,
 c5_render_gn_diagonal_device).  They upload the scalars as the forward does, return float64 tensors on the context's GPU
@@ -47,6 +56,7 @@ without a graph, and raise under a differentiating torch.func transform.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import capi
@@ -435,6 +445,115 @@ def render_view(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, angles:
     return _RenderView.apply(ctx, alpha, q, angles)
 
 
+# ---- the grid's points as an input -------------------------------------------------------------------------------------
+
+def _set_points(ctx: capi.Context, xyz: torch.Tensor) -> None:
+    p = _plain(xyz).detach().to("cpu", torch.float64).contiguous().numpy()
+    if p.shape != (ctx.n_pts, 3):
+        raise ValueError(f"xyz must hold the grid's points, [{ctx.n_pts}, 3]")
+    if not np.array_equal(p, ctx.points):
+        ctx.update_points(p)
+
+
+def _vertex_adjoint(ctx: capi.Context, g: torch.Tensor, device: torch.device) -> torch.Tensor:
+    """[n_pts, 3] float64 on the context's GPU: the vertex adjoint render for the upstream image g (float32, there)."""
+    out = torch.empty((ctx.n_pts, 3), dtype=torch.float64, device=device)
+    _use_torch_stream(ctx, device)
+    _run(ctx, lambda: ctx.render_vertex_adjoint_device(g, out))
+    return out
+
+
+class _VertexAdjoint(torch.autograd.Function):
+    """d loss / d xyz: the vertex adjoint render of the frame of `fr`, float64 [n_pts, 3] on the context's GPU.  A batch of
+    upstream images (vmap) loops the single call."""
+
+    @staticmethod
+    def forward(fr, xyz, grad_img):
+        ctx = _current(fr, "backward")
+        device = torch.device("cuda", ctx.device)
+        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
+            g = _plain(grad_img).detach().to(device=device, dtype=torch.float32).contiguous()
+            return _vertex_adjoint(ctx, g, device)
+
+    @staticmethod
+    def setup_context(fctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(fctx, *grads):
+        _no_second("vertex adjoint")
+
+    @staticmethod
+    def jvp(fctx, *tangents):
+        _no_second("vertex adjoint")
+
+    @staticmethod
+    def vmap(info, in_dims, fr, xyz, grad_img):
+        _unbatched_primals(in_dims[1:2])
+        ctx = _current(fr, "backward")
+        device = torch.device("cuda", ctx.device)
+        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
+            g = _plain(grad_img).detach()
+            g = g.movedim(in_dims[2], 0) if in_dims[2] is not None else g.expand(info.batch_size, *g.shape)
+            g = g.to(device=device, dtype=torch.float32).contiguous()
+            return torch.stack([_vertex_adjoint(ctx, gk, device) for gk in g]), 0
+
+
+class _RenderMesh(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx: capi.Context, xyz: torch.Tensor, alpha: torch.Tensor, q: torch.Tensor):
+        _set_points(ctx, xyz)
+        return _Render.forward(ctx, alpha, q)
+
+    @staticmethod
+    def setup_context(fctx, inputs, output):
+        ctx, xyz, alpha, q = inputs
+        _Render.setup_context(fctx, (ctx, alpha, q), output)
+        fctx.primals = (xyz, alpha, q)
+        fctx.xyz_meta = (xyz.dtype, xyz.device)
+
+    @staticmethod
+    def backward(fctx, grad_img: torch.Tensor):
+        _first_order(fctx, "backward")
+        xyz, alpha, q = fctx.primals
+        gx_out = ga_out = gq_out = None
+        if fctx.needs_input_grad[1]:
+            dtype, dev = fctx.xyz_meta
+            gx_out = _VertexAdjoint.apply(fctx, xyz, grad_img).to(device=dev, dtype=dtype)
+        if fctx.needs_input_grad[2] or fctx.needs_input_grad[3]:
+            ga, gq = _Adjoint.apply(fctx, alpha, q, grad_img)
+            (a_dtype, a_dev), (q_dtype, q_dev) = fctx.meta
+            ga_out = ga.to(device=a_dev, dtype=a_dtype) if fctx.needs_input_grad[2] else None
+            gq_out = gq.to(device=q_dev, dtype=q_dtype) if fctx.needs_input_grad[3] else None
+        return None, gx_out, ga_out, gq_out
+
+    @staticmethod
+    def jvp(fctx, _ctx_tangent, xyz_t, alpha_t, q_t):
+        _current(fctx, "jvp")
+        _first_order(fctx, "jvp")
+        # (torch.func hands every input a tangent, zeros for the ones it does not differentiate: J 0 = 0 needs no render)
+        if xyz_t is not None and bool((_plain(xyz_t) != 0).any()):
+            raise RuntimeError("course5_amd.autograd.render_mesh: forward mode in the points is not supported (there is no "
+                               "per-vertex tangent render); use backward / vjp for xyz, or render_view for a rigid motion")
+        xyz, alpha, q = getattr(fctx, "primals", (None, None, None))
+        if alpha_t is None and q_t is None:
+            return None
+        return _Tangent.apply(fctx, alpha, q, alpha_t, q_t)
+
+    @staticmethod
+    def vmap(info, in_dims, ctx, xyz, alpha, q):
+        _unbatched_primals(in_dims[1:])
+        return _RenderMesh.apply(ctx, xyz, alpha, q), None
+
+
+def render_mesh(ctx: capi.Context, xyz: torch.Tensor, alpha: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
+    """The frame of `ctx` with the grid's points xyz ([n_pts, 3], the order and coordinates of upload_grid; sent to the
+    context when they differ from the ones it holds) and the scalars alpha and q, differentiable in all three.  xyz has
+    reverse mode only (one vertex adjoint render per backward; under vmap, one per cotangent): forward mode in xyz and
+    second derivatives raise."""
+    return _RenderMesh.apply(ctx, xyz, alpha, q)
+
+
 # ---- Gauss-Newton operators ------------------------------------------------------------------------------------------
 # H v = J^T W J v and diag(J^T W J) of the frame with the scalars (alpha, q): what a Gauss-Newton / CG fit calls in its
 # inner loop (course5_amd.fit).  Operators, not differentiable functions: the results carry no graph.
@@ -498,4 +617,4 @@ def gn_diagonal(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, weight=
     return da, dq
 
 
-__all__ = ["render", "render_view", "gn_product", "gn_diagonal"]
+__all__ = ["render", "render_view", "render_mesh", "gn_product", "gn_diagonal"]

@@ -33,6 +33,7 @@ EXPORTS = [
     "c5_update_scalars_device",
     "c5_render_gn_product", "c5_render_gn_product_device", "c5_render_gn_diagonal", "c5_render_gn_diagonal_device",
     "c5_render_motion_tangent", "c5_render_motion_tangent_device", "c5_rotation_motion",
+    "c5_render_vertex_adjoint", "c5_render_vertex_adjoint_device", "c5_update_points",
 ]
 
 
@@ -120,6 +121,9 @@ def load_library() -> C.CDLL:
     lib.c5_render_motion_tangent.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_float)]
     lib.c5_render_motion_tangent_device.argtypes = [vp, C.c_int, dp, vp]
     lib.c5_rotation_motion.argtypes = [C.POINTER(Rotation), C.c_int, C.c_int, C.c_int, dp]
+    lib.c5_render_vertex_adjoint.argtypes = [vp, C.POINTER(C.c_float), dp]
+    lib.c5_render_vertex_adjoint_device.argtypes = [vp, vp, vp]
+    lib.c5_update_points.argtypes = [vp, dp, C.c_int64]
     for name in EXPORTS:
         if name not in ("c5_destroy", "c5_last_error"):
             getattr(lib, name).restype = C.c_int
@@ -163,6 +167,8 @@ class Context:
         self.device = device
         self.res_x = self.res_y = 0
         self.n_cells = 0
+        self.n_pts = 0
+        self.points = np.zeros((0, 3))  # the points as upload_grid / update_points last had them (course5_amd.autograd.render_mesh)
         # bumped by everything that changes which frame a render produces apart from the cells' scalars (grid, view, image,
         # rows, solids, alpha limit): course5_amd.autograd refuses to differentiate a frame other than the one it rendered
         self.frame_state = 0
@@ -215,8 +221,21 @@ class Context:
                                             cells.ctypes.data_as(C.POINTER(C.c_int32)), cells.shape[0],
                                             _dp(alpha), _dp(q)))
         self.n_cells = cells.shape[0]
+        self.n_pts = xyz.shape[0]
         self.frame_state += 1
         self.scalars_owner = None
+        self.points = xyz.copy()
+
+    def update_points(self, xyz):
+        """Replace the coordinates of the uploaded grid's points (float64 [n_pts, 3], the order of upload_grid);
+        connectivity, weld groups, cell order and scalars stay.  A render after it is bit for bit that of a fresh context
+        uploaded with these coordinates, as long as they create no new coincident points.  Waits for the stream."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        if xyz.ndim != 2 or xyz.shape[1] != 3:
+            raise ValueError(f"xyz must be [n_pts, 3], not {list(xyz.shape)}")
+        self._check(self.lib.c5_update_points(self.handle, _dp(xyz), xyz.shape[0]))
+        self.frame_state += 1
+        self.points = xyz.copy()
 
     def update_scalars(self, alpha, q):
         alpha = np.ascontiguousarray(alpha, dtype=np.float64)
@@ -323,6 +342,28 @@ class Context:
         self._check(self.lib.c5_render_adjoint_device(
             self.handle, C.c_void_p(ptr(grad_out, torch.float32, (self.local_rows, self.res_x, 2))),
             C.c_void_p(ptr(grad_alpha, torch.float64, (self.n_cells,))), C.c_void_p(ptr(grad_q, torch.float64, (self.n_cells,)))))
+
+    # -- vertex adjoint render ---------------------------------------------------------------------
+    def render_vertex_adjoint(self, grad_out) -> np.ndarray:
+        """The gradient of the frame render() would produce now with respect to the grid's points, weighted by grad_out
+        ([local_rows, res_x, 2]: the weights of tau and of I per pixel): float64 [n_pts, 3] in the order and the coordinates
+        of upload_grid.  A point welded to another at upload gets 0, its representative the group's sum.  Synchronous;
+        retries by itself.  Not bit-reproducible from run to run (fp64 atomics), like render_adjoint."""
+        g = np.ascontiguousarray(grad_out, dtype=np.float32)
+        if g.shape != (self.local_rows, self.res_x, 2):
+            raise ValueError(f"grad_out must be [{self.local_rows}, {self.res_x}, 2], not {list(g.shape)}")
+        out = np.zeros((self.n_pts, 3), dtype=np.float64)
+        self._check(self.lib.c5_render_vertex_adjoint(self.handle, g.ctypes.data_as(C.POINTER(C.c_float)), _dp(out)))
+        return out
+
+    def render_vertex_adjoint_device(self, grad_out, grad_xyz):
+        """Asynchronous form on the context's stream, in device memory: torch tensors on this context's GPU (grad_out
+        float32 [local_rows, res_x, 2], grad_xyz float64 [n_pts, 3]; contiguous) or raw device pointers.  The status comes
+        with the next synchronize() (C5_RETRY: run it again)."""
+        import torch
+        self._check(self.lib.c5_render_vertex_adjoint_device(
+            self.handle, C.c_void_p(_device_ptr(grad_out, torch.float32, (self.local_rows, self.res_x, 2)) or None),
+            C.c_void_p(_device_ptr(grad_xyz, torch.float64, (self.n_pts, 3)) or None)))
 
     # -- tangent render ----------------------------------------------------------------------------
     def render_tangent(self, d_alpha=None, d_q=None) -> np.ndarray:

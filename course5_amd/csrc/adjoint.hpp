@@ -152,6 +152,33 @@ void launch_motion_resolve(hipStream_t s, const GridView& g, const ImageParams& 
                            const int64_t* offs, void* segs, const uint32_t* mask, double alpha_limit, const MotionField& field,
                            float2* out);
 
+// ---- vertex adjoint (c5_render_vertex_adjoint*): the gradient of the frame with respect to the grid's points.  With
+// G_k = d loss / d dz_k of a segment and lambda the barycentric coordinates of the pixel in the two faces the chord runs
+// between, the face's three vertices receive +-G_k lambda (exit +, entry -); a face's slopes then turn that weight into
+// the view-space gradient (-gx, -gy, 1) per vertex, and the view's linear part M into the caller's coordinates.
+
+struct VertexParams {
+    WalkParams w;            // as AdjointParams (the heads left in place by pass 1)
+    MotionGeometry geo;
+    const float2* grad_out;  // [n_local_rows][res_x] upstream weights (g_tau, g_I)
+    const double* lambda;    // pass 1's Lambda per pixel (launch_adjoint_walk(.., 1))
+    double* face_w;          // [n_cells][4][3] device order, accumulated: face f, its three vertices in face_plane's order
+};
+
+// adjoint_walk<2>'s walk with the chords' weights scattered to face_w (needs pass 1 first); hands the heads back cleared.
+// merge: the lanes of a wavefront in one cell are summed in LDS first ("vertex_merge"); else every lane adds its own
+void launch_vertex_walk(hipStream_t s, const VertexParams& v, bool merge);
+
+// the same over bin_sort_resolve's lists (sorts them in place, as launch_adjoint_resolve)
+void launch_vertex_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const double* Xtab, const double* Ytab,
+                           const int64_t* offs, void* segs, const uint32_t* mask, double alpha_limit, const float2* grad_out,
+                           double* face_w);
+
+// face_w -> grad_view[n_pts][3] (zeroed by the caller; accumulated per cell and face, edge-on faces skipped), then
+// grad_xyz[v] = M^T grad_view[v] for every point, M the linear part of the view R
+void launch_vertex_finish(hipStream_t s, const MotionGeometry& geo, int64_t n_cells, const double* face_w, double* grad_view,
+                          int64_t n_pts, const RotationList& R, double* grad_xyz);
+
 // c5_update_scalars_device: alpha[i] = alpha_src[perm[i]], q[i] = q_src[perm[i]] (perm nullptr: the identity), and into
 // stats[3] (zeroed by the caller): the bits of the largest alpha > 0, the complemented bits of the smallest alpha >=
 // DBL_EPSILON, and 1 if some alpha is NaN (the host loop of c5_update_scalars, as an order-free max / min / or)

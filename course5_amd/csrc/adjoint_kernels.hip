@@ -48,6 +48,9 @@
 //   motion_resolve    the same over bin_sort_resolve's lists: both faces of every segment from the cell's vertices.
 // No atomics, no pre-pass: bit-reproducible, like the tangent.
 //
+// The vertex adjoint (c5_render_vertex_adjoint*): the motion tangent's reverse mode, per grid point instead of per affine
+// field - adjoint_walk<1>, then vertex_walk / vertex_resolve and vertex_finish (their block further down).
+//
 // Every walk kernel here (the batched and Gauss-Newton ones further down included) takes its rays through adj::Ray: ONE
 // definition of the walk's step, of how a ray begins and of what it leaves behind.  The kernels differ in what they
 // accumulate along the ray, and those that differ in nothing else share a body with a compile-time parameter
@@ -1068,6 +1071,315 @@ __global__ __launch_bounds__(256) void motion_resolve(GridView g, ImageParams im
     out[lp] = make_float2(static_cast<float>(tau_dot), static_cast<float>(I_dot));
 }
 
+// ---- vertex adjoint (c5_render_vertex_adjoint*) ---------------------------------------------------------------------------
+// The gradient of the frame with respect to the grid's points, the reverse mode of the motion tangent.  A segment's chord is
+// dz_k = w_exit - w_entry and d loss / d dz_k = G_k = g_tau alpha_k + g_I T_k E_k (Q_k - a_k I_{k-1}) (the second term for
+// active segments; T_k as the adjoint's pass 2 forms it).  A face's depth at the pixel is w = sum_i lambda_i z_i, lambda the
+// barycentric coordinates of (x, y) in the projected triangle, and dw / d(x_i, y_i, z_i) = lambda_i (-gx, -gy, 1).
+//   adjoint_walk<1>   Lambda per pixel, as for the adjoint.
+//   vertex_walk       adjoint_walk<2>'s walk; per segment the two faces from the cell's vertices (cell_faces_bary) and
+//                     +-G_k lambda added to face_w[cell][face][vertex of the face]: six atomics per segment, no slopes.
+//   vertex_resolve    the same over bin_sort_resolve's lists.
+//   vertex_finish     per cell: the four faces' slopes again, face_w times (-gx, -gy, 1) added to grad_view[point]; per
+//                     point: M^T grad_view, M the linear part of the view, into the caller's array.
+// Cells name the representatives of welded points, so a group's sum lands on its representative and the others stay 0.
+
+namespace adj {
+
+__device__ __forceinline__ void load_vertices(const MotionGeometry& G, int4 cv, double (&p)[4][3]) {
+    const int vid[4] = {cv.x, cv.y, cv.z, cv.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        p[k][0] = G.vx[vid[k]];
+        p[k][1] = G.vy[vid[k]];
+        p[k][2] = G.vz[vid[k]];
+    }
+}
+
+// cell_faces' sibling: the same two faces by the same rule, as the face's index and the pixel's barycentric coordinates in
+// its projected triangle (l0, l1, l2: the face's vertices in face_plane's order).  p: the cell's view-space vertices.
+struct FaceBary {
+    int f;
+    double l0, l1, l2;
+};
+struct CellFacesBary {
+    FaceBary in, out;
+    bool found;
+};
+__device__ __forceinline__ CellFacesBary cell_faces_bary(const double (&p)[4][3], double x, double y) {
+    constexpr int FV[4][3] = {{0, 1, 2}, {0, 1, 3}, {0, 2, 3}, {1, 2, 3}};
+    double w_in = -INFINITY, w_out = INFINITY;
+    // of the face chosen so far: the numerators of l1 and l2 and their denominator (divided once, behind the loop)
+    double in_n1 = 0.0, in_n2 = 0.0, in_m = 1.0, out_n1 = 0.0, out_n2 = 0.0, out_m = 1.0;
+    int f_in = 0, f_out = 0;
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+        const FacePlane fp = face_plane(p, f);
+        const double w = fma(fp.gx, x - p[0][0], fma(fp.gy, y - p[0][1], fp.c));
+        const double* a = p[FV[f][0]];
+        const double* b = p[FV[f][1]];
+        const double* c = p[FV[f][2]];
+        const double m = (b[0] - a[0]) * (c[1] - a[1]) - (c[0] - a[0]) * (b[1] - a[1]);
+        const double n1 = (x - a[0]) * (c[1] - a[1]) - (c[0] - a[0]) * (y - a[1]);
+        const double n2 = (b[0] - a[0]) * (y - a[1]) - (x - a[0]) * (b[1] - a[1]);
+        if (fp.kind < 0 && w > w_in) {
+            w_in = w;
+            f_in = f;
+            in_n1 = n1, in_n2 = n2, in_m = m;
+        }
+        if (fp.kind > 0 && w < w_out) {
+            w_out = w;
+            f_out = f;
+            out_n1 = n1, out_n2 = n2, out_m = m;
+        }
+    }
+    CellFacesBary r;
+    r.found = w_in > -INFINITY && w_out < INFINITY;
+    r.in.f = f_in;
+    r.in.l1 = in_n1 / in_m;
+    r.in.l2 = in_n2 / in_m;
+    r.in.l0 = 1.0 - r.in.l1 - r.in.l2;
+    r.out.f = f_out;
+    r.out.l1 = out_n1 / out_m;
+    r.out.l2 = out_n2 / out_m;
+    r.out.l0 = 1.0 - r.out.l1 - r.out.l2;
+    return r;
+}
+
+// +G lambda to the exit face's three vertices, -G lambda to the entry face's: six atomics
+__device__ __forceinline__ void scatter_faces(double* __restrict__ face_w, int cell, double G, const CellFacesBary& cf) {
+    double* const fw = face_w + static_cast<size_t>(cell) * 12;
+    double* const o = fw + 3 * cf.out.f;
+    double* const i = fw + 3 * cf.in.f;
+    atomicAdd(o, G * cf.out.l0);
+    atomicAdd(o + 1, G * cf.out.l1);
+    atomicAdd(o + 2, G * cf.out.l2);
+    atomicAdd(i, -G * cf.in.l0);
+    atomicAdd(i + 1, -G * cf.in.l1);
+    atomicAdd(i + 2, -G * cf.in.l2);
+}
+
+}  // namespace adj
+
+// adjoint_walk<2>'s frame.  The cell's vertex ids are loaded beside its record, the vertices at the top of its step.
+// MERGE false ("vertex_merge" 0): nothing is shared between the lanes, a lane leaves when its ray ends and adds its six
+// values by itself - ten times slower on the C3 frame (neighbouring rays are in the same cells: the atomics of a step
+// queue up on a few addresses).  MERGE true (the default): adjoint_walk_batch's reduction - the loop is wave-uniform, every lane stages its cell's
+// twelve values (six of them zero) in a row of LDS, and per distinct cell of the step lanes v < 12 each sum column v over
+// the cell's member rows and add it with one atomic.
+template <bool MERGE>
+__global__ __launch_bounds__(64) void vertex_walk(VertexParams A) {
+    using namespace adj;
+    constexpr int kV = 12, kRow = kV + 1;  // (row pitch: an odd number of doubles)
+    __shared__ double stage[MERGE ? 65 * kRow : 1];
+    const WalkParams& P = A.w;
+    Ray r;
+    const int lane = r.lane;
+    if (MERGE && lane < kRow) stage[64 * kRow + lane] = 0.0;  // (an all-zero row 64 fills the rounds of four up)
+    double lam = 0.0, lam_total = 0.0, I = 0.0, g_tau = 0.0, g_I = 0.0;
+
+    const EntryHead ent = ray_begin(r, P, [&] {
+        const float2 g = A.grad_out[r.lp];
+        g_tau = g.x;
+        g_I = g.y;
+        lam_total = A.lambda[r.lp];
+        return g_tau != 0.0 || g_I != 0.0;
+    });
+
+    CellRegs cur;
+    int4 cv = make_int4(0, 0, 0, 0);
+    if (r.cell >= 0) {
+        load_cell(cur, P.xrec, r.cell);
+        cv = A.geo.cell_vert[r.cell];
+    }
+
+    for (;;) {
+        const bool live = r.cell >= 0;
+        if (MERGE ? __builtin_amdgcn_ballot_w64(live) == 0ull : !live) break;
+        const int here = r.cell;
+        bool emit = false;
+        if (live) {
+            double p[4][3];
+            load_vertices(A.geo, cv, p);
+            double dz, carry_next;
+            const int nb = ray_step(r, P, ent, cur, dz, carry_next);
+            CellRegs nxt;
+            int4 cv_nxt = cv;
+            if (nb >= 0) {
+                load_cell(nxt, P.xrec, nb);
+                cv_nxt = A.geo.cell_vert[nb];
+            }
+
+            if (is_segment(dz)) {
+                const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+                double G = g_tau * a_raw;                                  // d tau / d dz (raw alpha, every segment)
+                if (a != 0.0) {
+                    lam = lambda_add(lam, a, dz);  // (as in pass 1: Lambda_n == Lambda bit for bit, Lambda - Lambda_k >= 0)
+                    const double T = exp_nonpositive(fmin(lam - lam_total, 0.0));
+                    const double E = exp_nonpositive(-a * dz);
+                    G = fma(g_I * T, E * fma(-a, I, q), G);  // d I / d dz_k (the clamp is on alpha, not on the chord)
+                    I = segment_terms(a, q, dz, E, 1.0, I).I_next;
+                }
+                if (G != 0.0) {
+                    const CellFacesBary cf = cell_faces_bary(p, r.x, r.y);
+                    if (cf.found) {
+                        if (!MERGE) {
+                            scatter_faces(A.face_w, here, G, cf);
+                        } else {
+                            emit = true;
+                            double* const row = stage + lane * kRow;
+#pragma unroll
+                            for (int v = 0; v < kV; ++v) row[v] = 0.0;
+                            row[3 * cf.out.f] = G * cf.out.l0;
+                            row[3 * cf.out.f + 1] = G * cf.out.l1;
+                            row[3 * cf.out.f + 2] = G * cf.out.l2;
+                            row[3 * cf.in.f] = -G * cf.in.l0;
+                            row[3 * cf.in.f + 1] = -G * cf.in.l1;
+                            row[3 * cf.in.f + 2] = -G * cf.in.l2;
+                        }
+                    }
+                }
+            }
+            ray_advance(r, nb, carry_next);
+            cur = nxt;
+            cv = cv_nxt;
+        }
+        if (MERGE) {
+            __syncthreads();  // (one wavefront: the rows are visible to every lane)
+            unsigned long long m = __builtin_amdgcn_ballot_w64(emit);
+            while (m != 0ull) {
+                const int leader = __builtin_ctzll(m);
+                const int lc = __builtin_amdgcn_readlane(here, leader);
+                const unsigned long long members = __builtin_amdgcn_ballot_w64(emit && here == lc);
+                if (lane < kV) {
+                    double s = 0.0;
+                    for (unsigned long long rows = members; rows != 0ull;) {
+                        const int b0 = __builtin_ctzll(rows);
+                        rows &= rows - 1;
+                        const int b1 = rows ? __builtin_ctzll(rows) : 64;
+                        rows &= rows - 1;
+                        const int b2 = rows ? __builtin_ctzll(rows) : 64;
+                        rows &= rows - 1;
+                        const int b3 = rows ? __builtin_ctzll(rows) : 64;
+                        rows &= rows - 1;
+                        s += (stage[b0 * kRow + lane] + stage[b1 * kRow + lane]) + (stage[b2 * kRow + lane] + stage[b3 * kRow + lane]);
+                    }
+                    if (s != 0.0) atomicAdd(A.face_w + static_cast<size_t>(lc) * kV + lane, s);
+                }
+                m &= ~members;
+            }
+            __syncthreads();  // (the rows are read before the next step writes them)
+        }
+    }
+
+    ray_clear_head(r, P);
+}
+
+// adjoint_resolve's twin: the same sort, the same back-to-front order; both faces of a segment from its cell's vertices.
+__global__ __launch_bounds__(256) void vertex_resolve(GridView g, ImageParams im, const double* __restrict__ Xtab,
+                                                      const double* __restrict__ Ytab, const int64_t* __restrict__ offs,
+                                                      AdjSegment* __restrict__ segs, const uint32_t* __restrict__ mask,
+                                                      double alpha_limit, const float2* __restrict__ grad_out,
+                                                      double* __restrict__ face_w) {
+    using namespace adj;
+    const int64_t lp = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    if (lp >= n_px || (mask && mask[lp])) return;
+    const float2 gw = grad_out[lp];
+    const double g_tau = gw.x, g_I = gw.y;
+    if (g_tau == 0.0 && g_I == 0.0) return;
+    const int lrow = static_cast<int>(lp / im.res_x);
+    const double x = Xtab[lp - static_cast<int64_t>(lrow) * im.res_x], y = Ytab[global_row_of(im, lrow)];
+    const MotionGeometry geo{g.cell_vert, g.vx, g.vy, g.vz};
+    AdjSegment* const list = segs + offs[lp];
+    const int n = static_cast<int>(offs[lp + 1] - offs[lp]);
+    sort_segments(list, n);
+    double lam_total = 0.0;
+    for (int i = n - 1; i >= 0; --i) {  // Lambda, in the order the loop below runs
+        const ClampedAlpha c = clamp_alpha(g.alpha[list[i].cell], alpha_limit);
+        if (c.active) lam_total = lambda_add(lam_total, c.a, list[i].dz);
+    }
+    double lam = 0.0, I = 0.0;
+    for (int i = n - 1; i >= 0; --i) {
+        const int c = static_cast<int>(list[i].cell);
+        const double dz = list[i].dz, q = g.q[c], a_raw = g.alpha[c];
+        const ClampedAlpha ca = clamp_alpha(a_raw, alpha_limit);
+        double G = g_tau * a_raw;
+        if (ca.active) {
+            lam = lambda_add(lam, ca.a, dz);
+            const double T = exp(fmin(lam - lam_total, 0.0));
+            const double E = exp(-ca.a * dz);
+            G = fma(g_I * T, E * fma(-ca.a, I, q), G);
+            I = segment_terms(ca.a, q, dz, E, 1.0, I).I_next;
+        }
+        if (G != 0.0) {
+            double p[4][3];
+            load_vertices(geo, g.cell_vert[c], p);
+            const CellFacesBary cf = cell_faces_bary(p, x, y);
+            if (cf.found) scatter_faces(face_w, c, G, cf);
+        }
+    }
+}
+
+// vertex_finish, per cell: the weights of its faces' vertices times (-gx, -gy, 1) to the points
+__global__ __launch_bounds__(256) void vertex_finish_cells(MotionGeometry G, int64_t n_cells, const double* __restrict__ face_w,
+                                                           double* __restrict__ grad_view) {
+    constexpr int FV[4][3] = {{0, 1, 2}, {0, 1, 3}, {0, 2, 3}, {1, 2, 3}};
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n_cells) return;
+    double w[12];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        w[k] = face_w[i * 12 + k];
+        any = any || w[k] != 0.0;
+    }
+    if (!any) return;
+    const int4 cv = G.cell_vert[i];
+    const int vid[4] = {cv.x, cv.y, cv.z, cv.w};
+    double p[4][3];
+    adj::load_vertices(G, cv, p);
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+        const FacePlane fp = face_plane(p, f);
+        if (fp.kind == 0) continue;  // (edge-on: no ray crosses it, and it has no slopes)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double wk = w[3 * f + k];
+            if (wk != 0.0) {
+                double* const gv = grad_view + 3 * static_cast<int64_t>(vid[FV[f][k]]);
+                atomicAdd(gv, -fp.gx * wk);
+                atomicAdd(gv + 1, -fp.gy * wk);
+                atomicAdd(gv + 2, wk);
+            }
+        }
+    }
+}
+
+// vertex_finish, per point: grad_xyz = M^T grad_view, the view's rotations transposed in reverse order (their centres
+// drop out of the linear part)
+__global__ __launch_bounds__(256) void vertex_finish_points(const double* __restrict__ grad_view, int64_t n_pts, RotationList R,
+                                                            double* __restrict__ grad_xyz) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n_pts) return;
+    double gx = grad_view[3 * i], gy = grad_view[3 * i + 1], gz = grad_view[3 * i + 2];
+    for (int r = R.n - 1; r >= 0; --r) {
+        const double c = R.cosv[r], s = R.sinv[r];
+        if (R.axis[r] == 0) {  // y' = c y - s z, z' = s y + c z
+            const double t = gy;
+            gy = c * t + s * gz;
+            gz = c * gz - s * t;
+        } else {  // x' = c (x - x0) - s z + x0, z' = s (x - x0) + c z
+            const double t = gx;
+            gx = c * t + s * gz;
+            gz = c * gz - s * t;
+        }
+    }
+    grad_xyz[3 * i] = gx;
+    grad_xyz[3 * i + 1] = gy;
+    grad_xyz[3 * i + 2] = gz;
+}
+
 namespace {
 // workgroups of a walk kernel: one wavefront per 8x8 pixel tile (0: no pixel)
 unsigned tile_blocks(const ImageParams& im) {
@@ -1185,6 +1497,28 @@ void launch_motion_resolve(hipStream_t s, const GridView& g, const ImageParams& 
     if (!blocks) return;
     hipLaunchKernelGGL(motion_resolve, dim3(blocks), dim3(256), 0, s, g, im, Xtab, Ytab, offs, static_cast<AdjSegment*>(segs), mask,
                        alpha_limit, field, out);
+}
+
+void launch_vertex_walk(hipStream_t s, const VertexParams& v, bool merge) {
+    const unsigned blocks = tile_blocks(v.w.im);
+    if (!blocks) return;
+    if (merge) hipLaunchKernelGGL(vertex_walk<true>, dim3(blocks), dim3(64), 0, s, v);
+    else hipLaunchKernelGGL(vertex_walk<false>, dim3(blocks), dim3(64), 0, s, v);
+}
+
+void launch_vertex_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const double* Xtab, const double* Ytab,
+                           const int64_t* offs, void* segs, const uint32_t* mask, double alpha_limit, const float2* grad_out,
+                           double* face_w) {
+    const unsigned blocks = pixel_blocks(im);
+    if (!blocks) return;
+    hipLaunchKernelGGL(vertex_resolve, dim3(blocks), dim3(256), 0, s, g, im, Xtab, Ytab, offs, static_cast<AdjSegment*>(segs), mask,
+                       alpha_limit, grad_out, face_w);
+}
+
+void launch_vertex_finish(hipStream_t s, const MotionGeometry& geo, int64_t n_cells, const double* face_w, double* grad_view,
+                          int64_t n_pts, const RotationList& R, double* grad_xyz) {
+    if (n_cells > 0) hipLaunchKernelGGL(vertex_finish_cells, dim3(item_blocks(n_cells)), dim3(256), 0, s, geo, n_cells, face_w, grad_view);
+    if (n_pts > 0) hipLaunchKernelGGL(vertex_finish_points, dim3(item_blocks(n_pts)), dim3(256), 0, s, grad_view, n_pts, R, grad_xyz);
 }
 
 void launch_scalars_gather(hipStream_t s, const double* alpha_src, const double* q_src, const int32_t* perm, int64_t n, double* alpha,

@@ -285,6 +285,14 @@ struct c5_context {
     // Gauss-Newton renders (c5_render_gn_product*, c5_render_gn_diagonal*): nothing of it is allocated before the first call
     c5api::DeviceBuffer gn_g;      // [width][n_local_px] float2: pass A's w * J v, pass B's upstream images (a chunk's)
     c5api::DeviceBuffer gn_spare;  // [width][n_cells] fp64: where the block of H v goes that the caller did not ask for
+    // vertex adjoint (c5_render_vertex_adjoint*): nothing of it is allocated before the first call (it shares adj_lambda)
+    c5api::DeviceBuffer vtx_face;  // [n_cells][4][3] fp64, device order: the chords' weights per face and vertex of the face
+    c5api::DeviceBuffer vtx_grad;  // [n_pts][3] fp64: the gradient in view space
+    int vertex_merge = 1;          // "vertex_merge": vertex_walk sums the lanes of a wavefront in one cell before its atomics
+                                   // (measured on the C3 frame: 5.7 ms against 58 ms for the walk; profiles/vertex_adjoint_probe.md)
+    // c5_update_points: the cells as the device has them (welded, in its order) and, where c5_upload_grid welded points,
+    // every point's representative (empty: none welded) - what measure_grid and upload_block_spheres are run again with
+    std::vector<int32_t> host_cell_vert, point_rep;
     // the host-pointer forms of all derivative renders: what the caller hands in and what goes back (run_staged)
     c5api::DeviceBuffer deriv_io;
     // c5_update_scalars_device: the three statistics of the scalars on the device, and their pinned copy

@@ -390,6 +390,46 @@ int enqueue_motion(c5_context* ctx, int n, const double* fields, float2* out) {
     return commit_derivative(ctx, "motion tangent");
 }
 
+// The vertex adjoint: the per-face weights and the view-space gradient zeroed, the adjoint's pass 1 and vertex_walk (or
+// vertex_resolve over bin_sort_resolve's lists), then vertex_finish into the caller's [n_pts][3] (the caller's point
+// order is the device's: only the cells are reordered).
+int enqueue_vertex_adjoint(c5_context* ctx, const float2* grad_out, double* grad_xyz) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells), n_pts = static_cast<size_t>(ctx->n_pts);
+    if (v.no_cells) {  // (solids only: no point the frame depends on)
+        if (n_pts > 0) C5_HIP(ctx, hipMemsetAsync(grad_xyz, 0, 3 * n_pts * sizeof(double), v.s));
+        return C5_OK;
+    }
+    C5_HIP(ctx, ctx->vtx_face.ensure(12 * n_cells * sizeof(double)));
+    C5_HIP(ctx, ctx->vtx_grad.ensure(3 * n_pts * sizeof(double)));
+    double* const face_w = ctx->vtx_face.as<double>();
+    double* const grad_view = ctx->vtx_grad.as<double>();
+    C5_HIP(ctx, hipMemsetAsync(face_w, 0, 12 * n_cells * sizeof(double), v.s));
+    C5_HIP(ctx, hipMemsetAsync(grad_view, 0, 3 * n_pts * sizeof(double), v.s));
+    const c5::MotionGeometry geo{v.g.cell_vert, v.g.vx, v.g.vy, v.g.vz};
+    if (v.bin_sort) {
+        c5::launch_vertex_resolve(v.s, v.g, ctx->im, ctx->xtab.as<double>(), ctx->ytab.as<double>(), ctx->offs64.as<int64_t>(),
+                                  ctx->segs.ptr, v.mask, ctx->alpha_limit, grad_out, face_w);
+    } else {
+        c5::AdjointParams ap;
+        rc = adjoint_params(ctx, v, ap);
+        if (rc) return rc;
+        c5::launch_adjoint_walk(v.s, ap, 1);
+        c5::VertexParams vp{};
+        vp.w = v.w;
+        vp.geo = geo;
+        vp.grad_out = grad_out;
+        vp.lambda = ap.lambda;
+        vp.face_w = face_w;
+        c5::launch_vertex_walk(v.s, vp, ctx->vertex_merge != 0);
+        ctx->slots[0].head_clean = true;  // (vertex_walk hands every head back cleared)
+    }
+    c5::launch_vertex_finish(v.s, geo, ctx->n_cells, face_w, grad_view, ctx->n_pts, ctx->view, grad_xyz);
+    return commit_derivative(ctx, "vertex adjoint");
+}
+
 // diag(J^T W J): adjoint_one with the squared kernels.  weight null: ones.
 int enqueue_gn_diagonal(c5_context* ctx, const float2* weight, double* da_out, double* dq_out) {
     DerivativeView v;
@@ -429,7 +469,7 @@ int finish_adjoint(c5_context* ctx) {
 
 namespace {
 
-// What the fourteen derivative entry points check before anything else, in this order: the context; a batch's size; the
+// What the sixteen derivative entry points check before anything else, in this order: the context; a batch's size; the
 // call's own pointers (`required_ok`, and `per_cell_ok` where the grid has cells); no c5_render_host_async frame
 // outstanding; and for the host-pointer forms the image, after which the device is bound.
 struct DerivativeCall {
@@ -639,6 +679,22 @@ int c5_render_motion_tangent(c5_context* ctx, int n_dirs, const double* fields_h
     if (rc) return rc;
     Staged b[] = {{nullptr, out_host, n_dirs * image_bytes(ctx)}};
     return run_staged(ctx, "motion tangent", b, [&] { return enqueue_motion(ctx, n_dirs, fields_host, b[0].as<float2>()); });
+}
+
+int c5_render_vertex_adjoint_device(c5_context* ctx, const void* grad_out_dev, void* grad_xyz_dev) {
+    int rc = check_derivative(ctx, {"c5_render_vertex_adjoint", false, 1, nullptr, grad_out_dev && grad_xyz_dev, true,
+                                    "null vertex adjoint pointer"});
+    if (rc) return rc;
+    return enqueue_vertex_adjoint(ctx, static_cast<const float2*>(grad_out_dev), static_cast<double*>(grad_xyz_dev));
+}
+
+int c5_render_vertex_adjoint(c5_context* ctx, const float* grad_out_host, double* grad_xyz_host) {
+    int rc = check_derivative(ctx, {"c5_render_vertex_adjoint", true, 1, nullptr, grad_out_host && grad_xyz_host, true,
+                                    "null vertex adjoint pointer"});
+    if (rc) return rc;
+    Staged b[] = {{grad_out_host, nullptr, image_bytes(ctx)},
+                  {nullptr, grad_xyz_host, 3 * static_cast<size_t>(ctx->n_pts) * sizeof(double)}};
+    return run_staged(ctx, "vertex adjoint", b, [&] { return enqueue_vertex_adjoint(ctx, b[0].as<const float2>(), b[1].as<double>()); });
 }
 
 // Host only.  The view is p -> R_n(... R_1(p)), R_k(p) = M_k (p - o_k) + o_k (axis 0: about the x axis, o = 0; axis 1: about

@@ -23,9 +23,13 @@ namespace {
 // and never sees ids, so files with per-cell point copies or duplicated seam points must walk like any
 // other grid (without this every face of such a file would be a boundary face).
 // cell_vert: pointed at `welded`, the cells over the points' representatives, where any point was merged.
-void weld_cells(const double* xyz, int64_t n_pts, int64_t n_cells, const int32_t*& cell_vert, std::vector<int32_t>& welded) {
-    std::vector<int32_t> rep;
-    if (c5::weld_points(xyz, n_pts, rep) <= 0) return;
+// rep: every point's representative where any was merged, else left empty.
+void weld_cells(const double* xyz, int64_t n_pts, int64_t n_cells, const int32_t*& cell_vert, std::vector<int32_t>& welded,
+                std::vector<int32_t>& rep) {
+    if (c5::weld_points(xyz, n_pts, rep) <= 0) {
+        rep.clear();
+        return;
+    }
     welded.resize(static_cast<size_t>(4 * n_cells));
     for (int64_t i = 0; i < 4 * n_cells; ++i) welded[static_cast<size_t>(i)] = rep[static_cast<size_t>(cell_vert[i])];
     cell_vert = welded.data();
@@ -240,7 +244,8 @@ int c5_upload_grid(c5_context* ctx, const double* xyz, int64_t n_pts, const int3
     // the cells as the device gets them: over welded points, in Morton order
     std::vector<int32_t> welded, ordered;
     std::vector<int32_t> perm;  // new index -> the caller's
-    weld_cells(xyz, n_pts, n_cells, cell_vert, welded);
+    std::vector<int32_t> rep;   // (empty: no point was merged)
+    weld_cells(xyz, n_pts, n_cells, cell_vert, welded, rep);
     const int32_t* caller_cell_vert = cell_vert;
     if (ctx->cell_order && n_cells >= 4096) morton_order_cells(xyz, n_cells, cell_vert, perm, ordered);
     std::vector<int32_t> adj;
@@ -260,6 +265,8 @@ int c5_upload_grid(c5_context* ctx, const double* xyz, int64_t n_pts, const int3
     rc = upload_grid_arrays(ctx, xyz, n_pts, cell_vert, n_cells, adj, bfaces, alpha, q, perm);
     if (rc) return rc;
     ctx->cell_perm = std::move(perm);
+    ctx->host_cell_vert.assign(cell_vert, cell_vert + 4 * n_cells);  // (c5_update_points measures the grid again)
+    ctx->point_rep = std::move(rep);
     ++ctx->grid_serial;
     measure_grid(ctx, xyz, n_pts, cell_vert, n_cells);
     scan_alpha(ctx, alpha, n_cells);
@@ -290,6 +297,44 @@ int c5_update_scalars(c5_context* ctx, const double* alpha, const double* q, int
     }
     scan_alpha(ctx, alpha, n_cells);
     return C5_OK;
+}
+
+int c5_update_points(c5_context* ctx, const double* xyz, int64_t n_pts) {
+    if (!ctx) return fail(nullptr, C5_ERR_INVALID, "null context");
+    if (n_pts != ctx->n_pts) return fail(ctx, C5_ERR_INVALID, "point count differs from the uploaded grid");
+    if (n_pts > 0 && !xyz) return fail(ctx, C5_ERR_INVALID, "null point array");
+    for (int64_t i = 0; i < 3 * n_pts; ++i)
+        if (!std::isfinite(xyz[i])) return fail(ctx, C5_ERR_INVALID, "point %lld has a non-finite coordinate", static_cast<long long>(i / 3));
+    ++ctx->setup_epoch;  // whatever was built per view is stale ("view_cache")
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    rc = drain(ctx);  // (frames set up on the other streams read the points too)
+    if (rc) return rc;
+    // a point welded at upload keeps following its representative
+    std::vector<double> moved;
+    if (!ctx->point_rep.empty()) {
+        moved.resize(static_cast<size_t>(3 * n_pts));
+        for (int64_t i = 0; i < n_pts; ++i)
+            for (int k = 0; k < 3; ++k) moved[static_cast<size_t>(3 * i + k)] = xyz[3 * static_cast<int64_t>(ctx->point_rep[static_cast<size_t>(i)]) + k];
+        xyz = moved.data();
+    }
+    std::vector<double> soa(static_cast<size_t>(3 * n_pts));
+    for (int64_t i = 0; i < n_pts; ++i)
+        for (int k = 0; k < 3; ++k) soa[static_cast<size_t>(k * n_pts + i)] = xyz[3 * i + k];
+    const size_t pb = static_cast<size_t>(n_pts) * sizeof(double);
+    if (n_pts > 0) {
+        C5_HIP(ctx, hipMemcpy(ctx->px.ptr, soa.data(), pb, hipMemcpyHostToDevice));
+        C5_HIP(ctx, hipMemcpy(ctx->py.ptr, soa.data() + n_pts, pb, hipMemcpyHostToDevice));
+        C5_HIP(ctx, hipMemcpy(ctx->pz.ptr, soa.data() + 2 * n_pts, pb, hipMemcpyHostToDevice));
+    }
+    // what c5_upload_grid derives from the coordinates, again
+    const int32_t* cell_vert = ctx->host_cell_vert.data();
+    measure_grid(ctx, xyz, n_pts, cell_vert, ctx->n_cells);
+    ctx->split_auto_k = 1;
+    ctx->ray_depth_known = false;
+    ctx->fit_known = false;
+    ctx->overlap_seen = false;  // (the first frame finds out again whether the components interpenetrate)
+    return upload_block_spheres(ctx, xyz, cell_vert, ctx->n_cells);
 }
 
 int c5_update_scalars_device(c5_context* ctx, const void* alpha_dev, const void* q_dev, int64_t n_cells) {

@@ -1,4 +1,5 @@
-"""One Gauss-Newton step of a fit of the cell field (alpha, Q) to observed images.
+"""One Gauss-Newton step of a fit of the cell field (alpha, Q) to observed images (and the gradient of a shape fit:
+shape_gradient, at the end).
 
     delta, models = course5_amd.fit.gn_step(ctx, alpha, q, residual, fit=("q",))
 
@@ -130,3 +131,21 @@ def view_step(ctx, alpha, q, angles, residual, weight=None, damping: float = 0.0
     g = JW @ r
     d = torch.linalg.solve(H + damping * torch.diag(torch.diagonal(H)), -g)
     return d, float(0.5 * d @ H @ d + d @ g)
+
+
+def shape_gradient(ctx, alpha, q, residual, weight=None):
+    """The loss 1/2 sum w r^2 of a fit of the grid's SHAPE and its gradient with respect to the points the context holds
+    (capi.Context.update_points, autograd.render_mesh): r = frame - target the residual image, w the per-pixel weights
+    ([local_rows, res_x, 2]; None: ones).  Returns (loss, grad_xyz): a float and float64 [n_pts, 3] on the context's GPU,
+    from ONE vertex adjoint render on g = w r.  The building block of a descent loop, no more: step size, line search and
+    the loop are the caller's."""
+    from . import autograd
+    device = autograd._gn_enter(ctx, alpha, q, "shape_gradient")
+    with torch.cuda.device(device):
+        r = residual.detach().to(device=device, dtype=torch.float32)
+        if tuple(r.shape) != (ctx.local_rows, ctx.res_x, 2):
+            raise ValueError(f"residual must be [{ctx.local_rows}, {ctx.res_x}, 2], not {list(r.shape)}")
+        w = autograd._gn_weight(ctx, weight, device)
+        g = (r if w is None else r * w).contiguous()
+        loss = 0.5 * float((g.to(torch.float64) * r.to(torch.float64)).sum())
+        return loss, autograd._vertex_adjoint(ctx, g, device)

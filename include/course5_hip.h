@@ -125,6 +125,16 @@ int c5_update_scalars(c5_context* ctx, const double* alpha, const double* q, int
  * (c5_set_stream).  The host needs the largest and the smallest alpha (the walk's choices, "depth_split"): the call reads
  * them back and WAITS for the stream.  A render after it returns the same bits as after c5_update_scalars. */
 int c5_update_scalars_device(c5_context* ctx, const void* alpha_dev, const void* q_dev, int64_t n_cells);
+/* Replace only the point coordinates of the uploaded grid (xyz[n_pts][3], the order of c5_upload_grid): what a fit of the
+ * grid's SHAPE calls between its iterations.  Connectivity, weld groups, face adjacency, the cells' order and scalars stay;
+ * what c5_upload_grid derives from the coordinates (bounding box, longest edge, the spheres of "block_cull") is made again,
+ * and the per-view data are stale ("view_cache"), as after c5_update_scalars.  Waits for the stream.  n_pts must be the
+ * uploaded grid's, every coordinate finite: else C5_ERR_INVALID and the grid is untouched.
+ * Points welded at upload STAY welded: such a point takes its representative's new coordinates, its own are ignored.
+ * Contract: a render after it returns, bit for bit, what a fresh context returns that was uploaded with the new
+ * coordinates - whenever the new coordinates create no NEW coincident points (those a fresh upload would weld and this
+ * call does not), and points welded before still coincide. */
+int c5_update_points(c5_context* ctx, const double* xyz, int64_t n_pts);
 /* Solid object `slot` (0..C5_MAX_SOLIDS-1): tets[n][4][3] raw vertex copies, one colour.
  * Replaces the solid part of the tetra vector (main.cpp:110-116,127; plane.cpp:130-131).
  * n == 0 removes the object.  Higher slots / higher tet index win ties, like serial -j1. */
@@ -222,11 +232,14 @@ int c5_set_alpha_limit(c5_context* ctx, double alpha_limit);
  *                  turns).  The second frame of such a run builds everything once more and tells its walk to leave the
  *                  per-pixel entry heads in place (the walk normally hands them back cleared); the third and later ones
  *                  skip the three setup launches (c5_stats: their ms_transform / ms_records / ms_entries are exactly 0).
- *                  Anything the data depend on makes them stale: c5_upload_grid, c5_update_scalars, c5_set_image, the row
+ *                  Anything the data depend on makes them stale: c5_upload_grid, c5_update_scalars, c5_update_points, c5_set_image, the row
  *                  setters, c5_set_stream, any option but "row_costs" / "stage_timing" / "walk_timing", a grown entry pool.
  *                  A sweep whose view changes every frame never pays for it.  0: every frame builds its own.  Same results.
  *   "batch_width"  tuning: directions or upstream images one walk of c5_render_tangent_batch* / c5_render_adjoint_batch*
  *                  carries: 4 or 8; 0 (default): 4 for batches of up to 4, else 8.  Same results (the adjoint's to rounding).
+ *   "vertex_merge" tuning: 1 (default): c5_render_vertex_adjoint* sums the lanes of a wavefront that share a cell (in LDS)
+ *                  before its atomics; 0: every lane adds its own six values (measured 10 x slower on the C3 frame).  Same
+ *                  results, to the atomics' rounding.
  *   "overlap_setup" 1: entry lists and solid mask are built on a side stream while build_records
  *                  runs (only when "stage_timing" is 0).  Default 0: measured no faster.
  *   "pipeline"     1: two frame slots; the per-view setup of frame k + 1 runs on a second stream while
@@ -390,6 +403,41 @@ int c5_render_gn_diagonal_device(c5_context* ctx, const void* weight_dev, void* 
 int c5_render_motion_tangent(c5_context* ctx, int n_dirs, const double* fields_host, float* out_host);
 int c5_render_motion_tangent_device(c5_context* ctx, int n_dirs, const double* fields_host, void* out_dev);
 int c5_rotation_motion(const c5_rotation* rots, int n_rots, int index, int what, double field[12]);
+
+/* --- vertex adjoint render ---------------------------------------------------------------------------
+ * The reverse mode of the motion tangent: the gradient of the frame c5_render would produce NOW with respect to the
+ * coordinates of every grid point, the cells' scalars held, weighted by an upstream image grad_out[local_rows][res_x][2]
+ * fp32 (channel 0: the weight of tau, 1: of I) as for c5_render_adjoint.  One adjoint-style pass for all points, where
+ * finite differences take 3 n_pts renders.
+ * With the adjoint's numbering, segment k of pixel p has d loss / d dz_k =
+ *     G_k = g_tau alpha_k + g_I T_k E_k (Q_k - a_k I_{k-1})           (raw alpha; the second term for active segments)
+ * (the clamp is on alpha, not on the chord).  The chord is dz_k = w_exit - w_entry, and a face with view-space vertices
+ * P_0, P_1, P_2 has the depth w = sum_i lambda_i z_i at the pixel, lambda the barycentric coordinates of (x, y) in the
+ * projected triangle: dw / d(x_i, y_i, z_i) = lambda_i (-gx, -gy, 1) with the face's slopes (gx, gy) - the motion
+ * tangent's dw = u_z - gx u_x - gy u_y for u(P) = sum lambda_i u_i.  So in view space
+ *     grad_view[v] = sum over pixels, segments and the segment's two faces holding v of
+ *                    (+G_k lambda_v at the exit face, -G_k lambda_v at the entry face) (-gx, -gy, 1)
+ * and the result is given in the coordinates c5_upload_grid took: grad_xyz[v] = M^T grad_view[v], M the linear part of
+ * the view (the rotations are rigid; their centres drop out).  For any affine field, sum_v grad_view[v] . (A p_v + b) =
+ * <grad_out, c5_render_motion_tangent's image> up to that image's fp32 rounding.
+ * Conventions: the other derivative renders'.  Solid-marked and uncovered pixels contribute nothing; a cell with clamped
+ * alpha < DBL_EPSILON contributes through tau only; faces edge-on to the rays contribute nothing; whole rays in the
+ * reference's order whatever "integration", "depth_split", "lds_stage" or "tile" say; pixels that gain or lose coverage
+ * when a point moves are not differentiated (the derivative of the smooth piece the pixel is on).
+ * WELDED POINTS: a point c5_upload_grid welded to another (c5_weld_points: rep[i] != i) receives 0; its representative
+ * receives the sum of the group.
+ * grad_xyz: [n_pts][3] fp64 in the caller's point order, overwritten.  Row ranges and row tiles as for a frame (the
+ * gradients of the parts sum to the whole frame's).  fp64 atomics added in arrival order: NOT bit-reproducible from run
+ * to run, as the adjoint.
+ * Status, retries, side effects: as c5_render_adjoint's (the adjoint's counters and status words, never a frame's; a
+ * c5_render afterwards returns the bits it would have returned without it).  The first call allocates the adjoint's 8
+ * bytes per local pixel, 96 bytes per cell and 24 per point; a context that never calls it uses no more memory than
+ * before.  c5_render_vertex_adjoint is synchronous with host arrays and retries by itself on C5_RETRY; the _device form
+ * is asynchronous on the context's stream with device arrays, its status (C5_RETRY included: run it again) reported by the
+ * next call that waits for the stream.  A null pointer: C5_ERR_INVALID.  Both refuse while c5_render_host_async frames
+ * are outstanding (C5_ERR_STATE). */
+int c5_render_vertex_adjoint(c5_context* ctx, const float* grad_out_host, double* grad_xyz_host);
+int c5_render_vertex_adjoint_device(c5_context* ctx, const void* grad_out_dev, void* grad_xyz_dev);
 
 /* --- frames delivered to host memory, pipelined ----------------------------------------------------
  * plane::trace_rays hands back HOST pixels (plane.cpp:144-172); over PCIe Gen5 a 2400x1800 image is
