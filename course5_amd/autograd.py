@@ -45,9 +45,16 @@ and the coordinates of upload_grid go to the context through c5_update_points wh
 (connectivity, weld groups and cell order stay; through host memory, the call waits for the stream).  Backward is ONE
 vertex adjoint render (c5_render_vertex_adjoint_device) for xyz and the adjoint render for alpha and q, whichever
 needs_input_grad asks for; a point welded to another at upload gets a zero gradient, its representative the group's sum.
-There is no per-vertex forward mode: a tangent on xyz (jvp, jacfwd) raises, as second derivatives do; tangents on alpha and
-q go through the tangent render as in render.  Under vmap a batch of cotangents (jacrev) loops the single vertex adjoint
-call: there is no batched form.
+By default a tangent on xyz (jvp, jacfwd) raises, as second derivatives do; tangents on alpha and q go through the
+tangent render as in render.  Under vmap a batch of cotangents (jacrev) loops the single vertex adjoint call: there is
+no batched form.
+
+render_mesh(ctx, xyz, alpha, q, forward_xyz=True) has forward mode in the points too: a tangent on xyz (torch.func.jvp,
+forward_ad dual tensors, jacfwd) goes to ONE vertex tangent render (c5_render_vertex_tangent_device), added in float32 to
+the scalar tangent's image when alpha or q carry tangents as well; under vmap a batch of xyz tangents goes to one batched
+call.  The rows of points welded to another at upload are not read.  Cotangents and second derivatives are as without
+the switch.  It is a switch, not the default, because the refusal of forward mode in xyz is behaviour callers (and a test)
+rely on: nothing changes for a caller that does not ask.
 
 Beside render, two operators for Gauss-Newton fits (course5_amd.fit): gn_product(ctx, alpha, q, v_alpha, v_q, weight) =
 J^T W J v and gn_diagonal(ctx, alpha, q, weight) = diag(J^T W J), one library call each (c5_render_gn_product_device,
@@ -499,6 +506,52 @@ class _VertexAdjoint(torch.autograd.Function):
             return torch.stack([_vertex_adjoint(ctx, gk, device) for gk in g]), 0
 
 
+def _vertex_tangent(ctx: capi.Context, d: torch.Tensor, device: torch.device) -> torch.Tensor:
+    """[K, local_rows, res_x, 2] float32 on the context's GPU: the vertex tangent render for the displacement fields d
+    ([K, n_pts, 3] float64, contiguous, there)."""
+    k = d.shape[0]
+    out = torch.empty((k, ctx.local_rows, ctx.res_x, 2), dtype=torch.float32, device=device)
+    _use_torch_stream(ctx, device)
+    _run(ctx, lambda: ctx.render_vertex_tangent_device(d, out, n=k))
+    return out
+
+
+class _VertexTangent(torch.autograd.Function):
+    """d img / d xyz . t: one vertex tangent render of the frame of `fr`.  Batched under vmap."""
+
+    @staticmethod
+    def forward(fr, xyz, xyz_t):
+        ctx = _current(fr, "jvp")
+        device = torch.device("cuda", ctx.device)
+        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
+            d = _tangent_arg(xyz_t, device).reshape(1, ctx.n_pts, 3)
+            return _vertex_tangent(ctx, d, device)[0]
+
+    @staticmethod
+    def setup_context(fctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(fctx, *grads):
+        _no_second("vertex tangent")
+
+    @staticmethod
+    def jvp(fctx, *tangents):
+        _no_second("vertex tangent")
+
+    @staticmethod
+    def vmap(info, in_dims, fr, xyz, xyz_t):
+        _unbatched_primals(in_dims[1:2])
+        ctx = _current(fr, "jvp")
+        device = torch.device("cuda", ctx.device)
+        k = info.batch_size
+        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
+            t = _plain(xyz_t).detach()
+            t = t.movedim(in_dims[2], 0) if in_dims[2] is not None else t.expand(k, *t.shape)
+            d = t.to(device=device, dtype=torch.float64).reshape(k, ctx.n_pts, 3).contiguous()
+            return _vertex_tangent(ctx, d, device), 0
+
+
 class _RenderMesh(torch.autograd.Function):
     @staticmethod
     def forward(ctx: capi.Context, xyz: torch.Tensor, alpha: torch.Tensor, q: torch.Tensor):
@@ -546,12 +599,38 @@ class _RenderMesh(torch.autograd.Function):
         return _RenderMesh.apply(ctx, xyz, alpha, q), None
 
 
-def render_mesh(ctx: capi.Context, xyz: torch.Tensor, alpha: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
+class _RenderMeshForward(_RenderMesh):
+    """_RenderMesh with forward mode in the points: a tangent on xyz goes to one vertex tangent render."""
+
+    @staticmethod
+    def jvp(fctx, _ctx_tangent, xyz_t, alpha_t, q_t):
+        _current(fctx, "jvp")
+        _first_order(fctx, "jvp")
+        xyz, alpha, q = getattr(fctx, "primals", (None, None, None))
+        out = None
+        if alpha_t is not None or q_t is not None:
+            out = _Tangent.apply(fctx, alpha, q, alpha_t, q_t)
+        # (torch.func hands every input a tangent, zeros for the ones it does not differentiate: J 0 = 0 needs no render)
+        if xyz_t is not None and bool((_plain(xyz_t) != 0).any()):
+            t = _VertexTangent.apply(fctx, xyz, xyz_t)
+            out = t if out is None else out + t
+        return out
+
+    @staticmethod
+    def vmap(info, in_dims, ctx, xyz, alpha, q):
+        _unbatched_primals(in_dims[1:])
+        return _RenderMeshForward.apply(ctx, xyz, alpha, q), None
+
+
+def render_mesh(ctx: capi.Context, xyz: torch.Tensor, alpha: torch.Tensor, q: torch.Tensor, forward_xyz: bool = False) -> torch.Tensor:
     """The frame of `ctx` with the grid's points xyz ([n_pts, 3], the order and coordinates of upload_grid; sent to the
-    context when they differ from the ones it holds) and the scalars alpha and q, differentiable in all three.  xyz has
-    reverse mode only (one vertex adjoint render per backward; under vmap, one per cotangent): forward mode in xyz and
-    second derivatives raise."""
-    return _RenderMesh.apply(ctx, xyz, alpha, q)
+    context when they differ from the ones it holds) and the scalars alpha and q, differentiable in all three.  Reverse
+    mode in xyz is one vertex adjoint render per backward (under vmap, one per cotangent); second derivatives raise.
+    forward_xyz False (the default): forward mode in xyz raises, as it always has - callers and a test rely on that
+    refusal, which is why forward mode is a switch and not the new default.  forward_xyz True: a tangent on xyz
+    (torch.func.jvp, forward_ad, jacfwd) goes to ONE vertex tangent render, batched under vmap, and is added to the scalar
+    tangent's image when alpha or q carry tangents too."""
+    return (_RenderMeshForward if forward_xyz else _RenderMesh).apply(ctx, xyz, alpha, q)
 
 
 # ---- Gauss-Newton operators ------------------------------------------------------------------------------------------

@@ -34,6 +34,7 @@ EXPORTS = [
     "c5_render_gn_product", "c5_render_gn_product_device", "c5_render_gn_diagonal", "c5_render_gn_diagonal_device",
     "c5_render_motion_tangent", "c5_render_motion_tangent_device", "c5_rotation_motion",
     "c5_render_vertex_adjoint", "c5_render_vertex_adjoint_device", "c5_update_points",
+    "c5_render_vertex_tangent", "c5_render_vertex_tangent_device",
 ]
 
 
@@ -124,6 +125,8 @@ def load_library() -> C.CDLL:
     lib.c5_render_vertex_adjoint.argtypes = [vp, C.POINTER(C.c_float), dp]
     lib.c5_render_vertex_adjoint_device.argtypes = [vp, vp, vp]
     lib.c5_update_points.argtypes = [vp, dp, C.c_int64]
+    lib.c5_render_vertex_tangent.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_float)]
+    lib.c5_render_vertex_tangent_device.argtypes = [vp, C.c_int, vp, vp]
     for name in EXPORTS:
         if name not in ("c5_destroy", "c5_last_error"):
             getattr(lib, name).restype = C.c_int
@@ -364,6 +367,33 @@ class Context:
         self._check(self.lib.c5_render_vertex_adjoint_device(
             self.handle, C.c_void_p(_device_ptr(grad_out, torch.float32, (self.local_rows, self.res_x, 2)) or None),
             C.c_void_p(_device_ptr(grad_xyz, torch.float64, (self.n_pts, 3)) or None)))
+
+    # -- vertex tangent render ---------------------------------------------------------------------
+    def render_vertex_tangent(self, d_xyz) -> np.ndarray:
+        """The change of the frame render() would produce now when every grid point moves with the velocity d_xyz (float64
+        [n_pts, 3] in the order and the coordinates of upload_grid): float32 [local_rows, res_x, 2] (tau_dot, I_dot); K
+        fields [K, n_pts, 3] give [K, local_rows, res_x, 2], every slice bit for bit the call for that field alone.  The
+        rows of points welded to another at upload are not read (the group moves with its representative).  The operator
+        render_vertex_adjoint is the transpose of.  Synchronous; retries by itself.  Bit-reproducible."""
+        d = np.ascontiguousarray(d_xyz, dtype=np.float64)
+        if d.ndim not in (2, 3) or d.shape[-2:] != (self.n_pts, 3) or d.shape[0] == 0:
+            raise ValueError(f"d_xyz must be [{self.n_pts}, 3] or [K, {self.n_pts}, 3], not {list(d.shape)}")
+        k = 1 if d.ndim == 2 else d.shape[0]
+        out = np.zeros((k, self.local_rows, self.res_x, 2), dtype=np.float32)
+        self._check(self.lib.c5_render_vertex_tangent(self.handle, k, _dp(d), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out[0] if d.ndim == 2 else out
+
+    def render_vertex_tangent_device(self, d_xyz, out, n: int | None = None):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (d_xyz float64 [K, n_pts, 3], out
+        float32 [K, local_rows, res_x, 2], contiguous) or raw device pointers (then give n = K).  The status comes with the
+        next synchronize() (C5_RETRY: run it again)."""
+        import torch
+        k = n if n is not None else (out.shape[0] if hasattr(out, "shape") and len(out.shape) == 4 else -1)
+        if k < 0:
+            raise ValueError("out must be [K, local_rows, res_x, 2] (or give n = K with raw device pointers)")
+        d_ptr = _device_ptr(d_xyz, torch.float64, (k, self.n_pts, 3))
+        out_ptr = _device_ptr(out, torch.float32, (k, self.local_rows, self.res_x, 2))
+        self._check(self.lib.c5_render_vertex_tangent_device(self.handle, k, C.c_void_p(d_ptr or None), C.c_void_p(out_ptr or None)))
 
     # -- tangent render ----------------------------------------------------------------------------
     def render_tangent(self, d_alpha=None, d_q=None) -> np.ndarray:

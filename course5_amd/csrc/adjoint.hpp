@@ -179,6 +179,34 @@ void launch_vertex_resolve(hipStream_t s, const GridView& g, const ImageParams& 
 void launch_vertex_finish(hipStream_t s, const MotionGeometry& geo, int64_t n_cells, const double* face_w, double* grad_view,
                           int64_t n_pts, const RotationList& R, double* grad_xyz);
 
+// ---- vertex tangent (c5_render_vertex_tangent*): the frame differentiated along a displacement per grid point, the
+// operator launch_vertex_walk + launch_vertex_finish are the transpose of.  A face's depth at the pixel moves by
+// dw = sum_i lambda_i (u_z - gx u_x - gy u_y)[vertex i], u = M d_xyz the points' view-space velocities.
+
+// u_view[pt][j][3] = M d_xyz[k0 + j][pt] for j < n_used, zero for n_used <= j < kc: the caller's [K][n_pts][3]
+// displacements -> kc view-space velocities per point (24 kc bytes, contiguous); M the linear part of the view R
+void launch_vertex_velocity(hipStream_t s, int kc, const double* d_xyz, int64_t n_pts, int k0, int n_used, const RotationList& R,
+                            double* u_view);
+
+struct VertexTangentParams {
+    WalkParams w;          // as TangentParams
+    MotionGeometry geo;
+    const double* u_view;  // [n_pts][kc][3] (launch_vertex_velocity)
+    float2* out;           // [n_used][n_local_rows][res_x] (tau_dot, I_dot): the chunk's first image
+    int64_t image_px;      // pixels per image
+    int32_t n_used;        // fields of the chunk (<= kc)
+    int32_t keep_entries;  // as TangentBatchParams
+};
+
+// motion_walk's walk for kc (4 or 8) per-point fields, both faces of every segment from the cell's vertices; every image
+// bit for bit that of its field alone at either width; counts as tangent_walk does
+void launch_vertex_tangent_walk(hipStream_t s, int kc, const VertexTangentParams& v);
+
+// the same over bin_sort_resolve's lists for field j of u_view [n_pts][kc][3] (sorts them in place, as launch_tangent_resolve)
+void launch_vertex_tangent_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const double* Xtab, const double* Ytab,
+                                   const int64_t* offs, void* segs, const uint32_t* mask, double alpha_limit, const double* u_view,
+                                   int kc, int j, float2* out);
+
 // c5_update_scalars_device: alpha[i] = alpha_src[perm[i]], q[i] = q_src[perm[i]] (perm nullptr: the identity), and into
 // stats[3] (zeroed by the caller): the bits of the largest alpha > 0, the complemented bits of the smallest alpha >=
 // DBL_EPSILON, and 1 if some alpha is NaN (the host loop of c5_update_scalars, as an order-free max / min / or)

@@ -51,6 +51,10 @@
 // The vertex adjoint (c5_render_vertex_adjoint*): the motion tangent's reverse mode, per grid point instead of per affine
 // field - adjoint_walk<1>, then vertex_walk / vertex_resolve and vertex_finish (their block further down).
 //
+// The vertex tangent (c5_render_vertex_tangent*): the operator the vertex adjoint is the transpose of - the image's change
+// for a displacement per grid point: vertex_velocity, then vertex_tangent_walk / vertex_tangent_resolve (their block
+// further down).
+//
 // Every walk kernel here (the batched and Gauss-Newton ones further down included) takes its rays through adj::Ray: ONE
 // definition of the walk's step, of how a ray begins and of what it leaves behind.  The kernels differ in what they
 // accumulate along the ray, and those that differ in nothing else share a body with a compile-time parameter
@@ -1380,6 +1384,238 @@ __global__ __launch_bounds__(256) void vertex_finish_points(const double* __rest
     grad_xyz[3 * i + 2] = gz;
 }
 
+// ---- vertex tangent (c5_render_vertex_tangent*) ---------------------------------------------------------------------------
+// The forward mode of the vertex adjoint: the motion tangent with the velocity u(P) = sum_i lambda_i u_i interpolated from
+// the face's three vertices instead of an affine field.  With u_v = M d_xyz[v] (M the linear part of the view) a face's
+// depth at the pixel moves by dw = sum_i lambda_i (u_z - gx u_x - gy u_y)[vertex i], the chord by ddz = dw_exit - dw_entry,
+// and the sums are the motion tangent's.
+//   vertex_velocity<KC>        per point and field: u_view[pt][j] = M d_xyz[k0 + j][pt] (vertex_finish_points run forward).
+//   vertex_tangent_walk<KC>    motion_walk's frame; per segment both faces from the cell's own vertices
+//                              (cell_faces_sloped: cell_faces_bary's rule, with the slopes) - nothing is carried from the
+//                              previous cell, as in vertex_walk, so the two are transposes of each other term by term.
+//   vertex_tangent_resolve     the same over bin_sort_resolve's lists, one field per launch.
+// No atomics, no LDS, no pre-pass: bit-reproducible, and a field's image does not depend on the width or on its place in
+// the chunk (its arithmetic is vertex_ddz, the same for every field).
+
+namespace adj {
+
+// cell_faces_bary's sibling: the same two faces by the same rule, with the slopes face_plane has for them.
+struct CellFacesSloped {
+    CellFacesBary b;
+    double gx_in, gy_in, gx_out, gy_out;
+};
+__device__ __forceinline__ CellFacesSloped cell_faces_sloped(const double (&p)[4][3], double x, double y) {
+    constexpr int FV[4][3] = {{0, 1, 2}, {0, 1, 3}, {0, 2, 3}, {1, 2, 3}};
+    double w_in = -INFINITY, w_out = INFINITY;
+    double in_n1 = 0.0, in_n2 = 0.0, in_m = 1.0, out_n1 = 0.0, out_n2 = 0.0, out_m = 1.0;
+    CellFacesSloped r;
+    r.gx_in = r.gy_in = r.gx_out = r.gy_out = 0.0;
+    int f_in = 0, f_out = 0;
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+        const FacePlane fp = face_plane(p, f);
+        const double w = fma(fp.gx, x - p[0][0], fma(fp.gy, y - p[0][1], fp.c));
+        const double* a = p[FV[f][0]];
+        const double* b = p[FV[f][1]];
+        const double* c = p[FV[f][2]];
+        const double m = (b[0] - a[0]) * (c[1] - a[1]) - (c[0] - a[0]) * (b[1] - a[1]);
+        const double n1 = (x - a[0]) * (c[1] - a[1]) - (c[0] - a[0]) * (y - a[1]);
+        const double n2 = (b[0] - a[0]) * (y - a[1]) - (x - a[0]) * (b[1] - a[1]);
+        if (fp.kind < 0 && w > w_in) {
+            w_in = w;
+            f_in = f;
+            in_n1 = n1, in_n2 = n2, in_m = m;
+            r.gx_in = fp.gx, r.gy_in = fp.gy;
+        }
+        if (fp.kind > 0 && w < w_out) {
+            w_out = w;
+            f_out = f;
+            out_n1 = n1, out_n2 = n2, out_m = m;
+            r.gx_out = fp.gx, r.gy_out = fp.gy;
+        }
+    }
+    r.b.found = w_in > -INFINITY && w_out < INFINITY;
+    r.b.in.f = f_in;
+    r.b.in.l1 = in_n1 / in_m;
+    r.b.in.l2 = in_n2 / in_m;
+    r.b.in.l0 = 1.0 - r.b.in.l1 - r.b.in.l2;
+    r.b.out.f = f_out;
+    r.b.out.l1 = out_n1 / out_m;
+    r.b.out.l2 = out_n2 / out_m;
+    r.b.out.l0 = 1.0 - r.b.out.l1 - r.b.out.l2;
+    return r;
+}
+
+// the three points of face f of the cell cv, in face_plane's order
+__device__ __forceinline__ void face_points(int4 cv, int f, int (&v)[3]) {
+    v[0] = f == 3 ? cv.y : cv.x;
+    v[1] = f <= 1 ? cv.y : cv.z;
+    v[2] = f == 0 ? cv.z : cv.w;
+}
+
+// lambda (u_z - gx u_x - gy u_y) of one vertex: u = its three doubles of one field
+__device__ __forceinline__ double vertex_dw(const double* __restrict__ u, double l, double gx, double gy) {
+    return l * fma(-gy, u[1], fma(-gx, u[0], u[2]));
+}
+
+// ddz = dw_exit - dw_entry of one field: six gathers of three doubles.  u: the field's first double of point 0, pitch
+// doubles from point to point.  This is ALL of a field's arithmetic that touches the velocities: the same at every width.
+__device__ __forceinline__ double vertex_ddz(const double* __restrict__ u, size_t pitch, const int (&vo)[3], const int (&vi)[3],
+                                             const CellFacesSloped& cf) {
+    const double dw_out = vertex_dw(u + vo[0] * pitch, cf.b.out.l0, cf.gx_out, cf.gy_out) +
+                          vertex_dw(u + vo[1] * pitch, cf.b.out.l1, cf.gx_out, cf.gy_out) +
+                          vertex_dw(u + vo[2] * pitch, cf.b.out.l2, cf.gx_out, cf.gy_out);
+    const double dw_in = vertex_dw(u + vi[0] * pitch, cf.b.in.l0, cf.gx_in, cf.gy_in) +
+                         vertex_dw(u + vi[1] * pitch, cf.b.in.l1, cf.gx_in, cf.gy_in) +
+                         vertex_dw(u + vi[2] * pitch, cf.b.in.l2, cf.gx_in, cf.gy_in);
+    return dw_out - dw_in;
+}
+
+}  // namespace adj
+
+// u_view[pt][j] = M d_xyz[k0 + j][pt] for j < n_used, zero beyond: the view's rotations in forward order, linear part only
+// (vertex_finish_points the other way).  One thread per point and field; a point's KC fields are contiguous.
+template <int KC>
+__global__ __launch_bounds__(256) void vertex_velocity(const double* __restrict__ d_xyz, int64_t n_pts, int k0, int n_used,
+                                                       RotationList R, double* __restrict__ u_view) {
+    const int64_t t = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (t >= n_pts * KC) return;
+    const int64_t i = t / KC;
+    const int j = static_cast<int>(t - i * KC);
+    double ux = 0.0, uy = 0.0, uz = 0.0;
+    if (j < n_used) {
+        const double* const d = d_xyz + 3 * (static_cast<int64_t>(k0 + j) * n_pts + i);
+        ux = d[0], uy = d[1], uz = d[2];
+        for (int r = 0; r < R.n; ++r) {
+            const double c = R.cosv[r], s = R.sinv[r];
+            if (R.axis[r] == 0) {  // y' = c y - s z, z' = s y + c z
+                const double y = uy;
+                uy = c * y - s * uz;
+                uz = s * y + c * uz;
+            } else {  // x' = c x - s z, z' = s x + c z (the centre drops out of the linear part)
+                const double x = ux;
+                ux = c * x - s * uz;
+                uz = s * x + c * uz;
+            }
+        }
+    }
+    u_view[3 * t] = ux;
+    u_view[3 * t + 1] = uy;
+    u_view[3 * t + 2] = uz;
+}
+
+// motion_walk's frame over the per-point velocities.  The next record and the next cell's vertex ids are loaded before the
+// arithmetic, the vertices at the top of the step (vertex_walk's order).  Nothing is shared between the lanes.
+template <int KC>
+__global__ __launch_bounds__(64) void vertex_tangent_walk(VertexTangentParams A) {
+    using namespace adj;
+    const WalkParams& P = A.w;
+    Ray r;
+    double I = 0.0, I_dot[KC], tau_dot[KC];
+#pragma unroll
+    for (int j = 0; j < KC; ++j) I_dot[j] = tau_dot[j] = 0.0;
+
+    const EntryHead ent = ray_begin(r, P);
+
+    CellRegs cur;
+    int4 cv = make_int4(0, 0, 0, 0);
+    if (r.cell >= 0) {
+        load_cell(cur, P.xrec, r.cell);
+        cv = A.geo.cell_vert[r.cell];
+    }
+
+    while (r.cell >= 0) {
+        double p[4][3];
+        load_vertices(A.geo, cv, p);
+        double dz, carry_next;
+        const int nb = ray_step(r, P, ent, cur, dz, carry_next);
+        CellRegs nxt;
+        int4 cv_nxt = cv;
+        if (nb >= 0) {
+            load_cell(nxt, P.xrec, nb);
+            cv_nxt = A.geo.cell_vert[nb];
+        }
+
+        if (is_segment(dz)) {
+            const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+            const CellFacesSloped cf = cell_faces_sloped(p, r.x, r.y);
+            int vo[3], vi[3];
+            face_points(cv, cf.b.out.f, vo);
+            face_points(cv, cf.b.in.f, vi);
+            double ddz[KC];
+#pragma unroll
+            for (int j = 0; j < KC; ++j) {
+                ddz[j] = cf.b.found ? vertex_ddz(A.u_view + 3 * j, 3 * KC, vo, vi, cf) : 0.0;  // (faces not found: 0)
+                tau_dot[j] = fma(a_raw, ddz[j], tau_dot[j]);                                   // d tau / d dz (raw alpha)
+            }
+            if (a != 0.0) {
+                const double E = exp_nonpositive(-a * dz);
+                const double dI_ddz = E * fma(-a, I, q);  // d I_k / d dz_k (the clamp is on alpha, not on the chord)
+#pragma unroll
+                for (int j = 0; j < KC; ++j) I_dot[j] = fma(E, I_dot[j], dI_ddz * ddz[j]);
+                I = segment_terms(a, q, dz, E, 1.0, I).I_next;
+            }
+        }
+        ray_advance(r, nb, carry_next);
+        cur = nxt;
+        cv = cv_nxt;
+    }
+
+    if (r.in_image) {
+#pragma unroll
+        for (int j = 0; j < KC; ++j)
+            if (j < A.n_used)
+                A.out[static_cast<size_t>(j) * A.image_px + r.lp] = make_float2(static_cast<float>(tau_dot[j]), static_cast<float>(I_dot[j]));
+    }
+    if (!A.keep_entries) ray_clear_head(r, P);
+    ray_count(r, P);
+}
+
+// motion_resolve's twin: the same sort, the same back-to-front order; both faces of a segment from its cell's vertices.
+// u: field `j`'s first double of point 0 in a velocity buffer of `pitch` doubles per point.
+__global__ __launch_bounds__(256) void vertex_tangent_resolve(GridView g, ImageParams im, const double* __restrict__ Xtab,
+                                                              const double* __restrict__ Ytab, const int64_t* __restrict__ offs,
+                                                              AdjSegment* __restrict__ segs, const uint32_t* __restrict__ mask,
+                                                              double alpha_limit, const double* __restrict__ u, int pitch,
+                                                              float2* __restrict__ out) {
+    using namespace adj;
+    const int64_t lp = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    const int64_t n_px = static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    if (lp >= n_px) return;
+    double I = 0.0, I_dot = 0.0, tau_dot = 0.0;
+    if (!(mask && mask[lp])) {
+        const int lrow = static_cast<int>(lp / im.res_x);
+        const double x = Xtab[lp - static_cast<int64_t>(lrow) * im.res_x], y = Ytab[global_row_of(im, lrow)];
+        const MotionGeometry geo{g.cell_vert, g.vx, g.vy, g.vz};
+        AdjSegment* const list = segs + offs[lp];
+        const int n = static_cast<int>(offs[lp + 1] - offs[lp]);
+        sort_segments(list, n);
+        for (int i = n - 1; i >= 0; --i) {
+            const int c = static_cast<int>(list[i].cell);
+            const double dz = list[i].dz, q = g.q[c], a_raw = g.alpha[c];
+            const ClampedAlpha ca = clamp_alpha(a_raw, alpha_limit);
+            const int4 cv = g.cell_vert[c];
+            double p[4][3];
+            load_vertices(geo, cv, p);
+            const CellFacesSloped cf = cell_faces_sloped(p, x, y);
+            double ddz = 0.0;
+            if (cf.b.found) {
+                int vo[3], vi[3];
+                face_points(cv, cf.b.out.f, vo);
+                face_points(cv, cf.b.in.f, vi);
+                ddz = vertex_ddz(u, static_cast<size_t>(pitch), vo, vi, cf);
+            }
+            tau_dot = fma(a_raw, ddz, tau_dot);
+            if (ca.active) {
+                const double E = exp(-ca.a * dz);
+                I_dot = fma(E, I_dot, E * fma(-ca.a, I, q) * ddz);
+                I = segment_terms(ca.a, q, dz, E, 1.0, I).I_next;
+            }
+        }
+    }
+    out[lp] = make_float2(static_cast<float>(tau_dot), static_cast<float>(I_dot));
+}
+
 namespace {
 // workgroups of a walk kernel: one wavefront per 8x8 pixel tile (0: no pixel)
 unsigned tile_blocks(const ImageParams& im) {
@@ -1519,6 +1755,26 @@ void launch_vertex_finish(hipStream_t s, const MotionGeometry& geo, int64_t n_ce
                           int64_t n_pts, const RotationList& R, double* grad_xyz) {
     if (n_cells > 0) hipLaunchKernelGGL(vertex_finish_cells, dim3(item_blocks(n_cells)), dim3(256), 0, s, geo, n_cells, face_w, grad_view);
     if (n_pts > 0) hipLaunchKernelGGL(vertex_finish_points, dim3(item_blocks(n_pts)), dim3(256), 0, s, grad_view, n_pts, R, grad_xyz);
+}
+
+void launch_vertex_velocity(hipStream_t s, int kc, const double* d_xyz, int64_t n_pts, int k0, int n_used, const RotationList& R,
+                            double* u_view) {
+    if (n_pts <= 0) return;
+    C5_LAUNCH_KC(vertex_velocity, kc, item_blocks(n_pts * kc), 256, s, d_xyz, n_pts, k0, n_used, R, u_view);
+}
+
+void launch_vertex_tangent_walk(hipStream_t s, int kc, const VertexTangentParams& v) {
+    const unsigned blocks = tile_blocks(v.w.im);
+    if (blocks) C5_LAUNCH_KC(vertex_tangent_walk, kc, blocks, 64, s, v);
+}
+
+void launch_vertex_tangent_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const double* Xtab, const double* Ytab,
+                                   const int64_t* offs, void* segs, const uint32_t* mask, double alpha_limit, const double* u_view,
+                                   int kc, int j, float2* out) {
+    const unsigned blocks = pixel_blocks(im);
+    if (!blocks) return;
+    hipLaunchKernelGGL(vertex_tangent_resolve, dim3(blocks), dim3(256), 0, s, g, im, Xtab, Ytab, offs, static_cast<AdjSegment*>(segs),
+                       mask, alpha_limit, u_view + 3 * j, 3 * kc, out);
 }
 
 void launch_scalars_gather(hipStream_t s, const double* alpha_src, const double* q_src, const int32_t* perm, int64_t n, double* alpha,

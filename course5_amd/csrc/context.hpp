@@ -290,6 +290,8 @@ struct c5_context {
     c5api::DeviceBuffer vtx_grad;  // [n_pts][3] fp64: the gradient in view space
     int vertex_merge = 1;          // "vertex_merge": vertex_walk sums the lanes of a wavefront in one cell before its atomics
                                    // (measured on the C3 frame: 5.7 ms against 58 ms for the walk; profiles/vertex_adjoint_probe.md)
+    // vertex tangent (c5_render_vertex_tangent*): allocated at the first call only
+    c5api::DeviceBuffer vtx_vel;   // [n_pts][width][3] fp64: the points' view-space velocities (vertex_velocity)
     // c5_update_points: the cells as the device has them (welded, in its order) and, where c5_upload_grid welded points,
     // every point's representative (empty: none welded) - what measure_grid and upload_block_spheres are run again with
     std::vector<int32_t> host_cell_vert, point_rep;

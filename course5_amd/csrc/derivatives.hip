@@ -430,6 +430,42 @@ int enqueue_vertex_adjoint(c5_context* ctx, const float2* grad_out, double* grad
     return commit_derivative(ctx, "vertex adjoint");
 }
 
+// The vertex tangent: n displacement fields ([n][n_pts][3] fp64 on the device, the caller's point order, the coordinates of
+// the upload) -> out[n][local_rows][res_x]: one per-view setup, then per chunk of up to `width` fields vertex_velocity (the
+// fields into view space, `width` per point) and one walk; the heads stay in place between the chunks and the last walk
+// hands them back cleared.  On bin_sort_resolve's lists: vertex_tangent_resolve per field (the first sorts the lists, the
+// others find them sorted).  The velocity buffer is allocated here, at the first call.
+int enqueue_vertex_tangent(c5_context* ctx, int n, const double* d_xyz, float2* out) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    if (v.no_cells) return zero_tangents(ctx, v, n, out);
+    const int width = batch_width(ctx, n);
+    C5_HIP(ctx, ctx->vtx_vel.ensure(3 * static_cast<size_t>(width) * static_cast<size_t>(ctx->n_pts) * sizeof(double)));
+    double* const u_view = ctx->vtx_vel.as<double>();
+    c5::VertexTangentParams vt{};
+    vt.w = v.w;
+    vt.geo = c5::MotionGeometry{v.g.cell_vert, v.g.vx, v.g.vy, v.g.vz};
+    vt.u_view = u_view;
+    vt.image_px = v.n_px;
+    for (int k0 = 0; k0 < n; k0 += width) {
+        vt.n_used = std::min(width, n - k0);
+        c5::launch_vertex_velocity(v.s, width, d_xyz, ctx->n_pts, k0, vt.n_used, ctx->view, u_view);
+        if (v.bin_sort) {
+            for (int j = 0; j < vt.n_used; ++j)
+                c5::launch_vertex_tangent_resolve(v.s, v.g, ctx->im, ctx->xtab.as<double>(), ctx->ytab.as<double>(),
+                                                  ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, u_view, width, j,
+                                                  out + (k0 + j) * v.n_px);
+            continue;
+        }
+        vt.out = out + k0 * v.n_px;
+        vt.keep_entries = k0 + width < n;
+        c5::launch_vertex_tangent_walk(v.s, width, vt);
+    }
+    if (!v.bin_sort) ctx->slots[0].head_clean = true;  // (the last chunk's walk hands every head back cleared)
+    return commit_derivative(ctx, "vertex tangent");
+}
+
 // diag(J^T W J): adjoint_one with the squared kernels.  weight null: ones.
 int enqueue_gn_diagonal(c5_context* ctx, const float2* weight, double* da_out, double* dq_out) {
     DerivativeView v;
@@ -469,7 +505,7 @@ int finish_adjoint(c5_context* ctx) {
 
 namespace {
 
-// What the sixteen derivative entry points check before anything else, in this order: the context; a batch's size; the
+// What the eighteen derivative entry points check before anything else, in this order: the context; a batch's size; the
 // call's own pointers (`required_ok`, and `per_cell_ok` where the grid has cells); no c5_render_host_async frame
 // outstanding; and for the host-pointer forms the image, after which the device is bound.
 struct DerivativeCall {
@@ -695,6 +731,23 @@ int c5_render_vertex_adjoint(c5_context* ctx, const float* grad_out_host, double
     Staged b[] = {{grad_out_host, nullptr, image_bytes(ctx)},
                   {nullptr, grad_xyz_host, 3 * static_cast<size_t>(ctx->n_pts) * sizeof(double)}};
     return run_staged(ctx, "vertex adjoint", b, [&] { return enqueue_vertex_adjoint(ctx, b[0].as<const float2>(), b[1].as<double>()); });
+}
+
+int c5_render_vertex_tangent_device(c5_context* ctx, int n_dirs, const void* d_xyz_dev, void* out_dev) {
+    int rc = check_derivative(ctx, {"c5_render_vertex_tangent", false, n_dirs, "displacement field", d_xyz_dev && out_dev, true,
+                                    "null displacement or output pointer"});
+    if (rc) return rc;
+    return enqueue_vertex_tangent(ctx, n_dirs, static_cast<const double*>(d_xyz_dev), static_cast<float2*>(out_dev));
+}
+
+int c5_render_vertex_tangent(c5_context* ctx, int n_dirs, const double* d_xyz_host, float* out_host) {
+    int rc = check_derivative(ctx, {"c5_render_vertex_tangent", true, n_dirs, "displacement field", d_xyz_host && out_host, true,
+                                    "null displacement or output pointer"});
+    if (rc) return rc;
+    Staged b[] = {{d_xyz_host, nullptr, 3 * static_cast<size_t>(n_dirs) * static_cast<size_t>(ctx->n_pts) * sizeof(double)},
+                  {nullptr, out_host, n_dirs * image_bytes(ctx)}};
+    return run_staged(ctx, "vertex tangent", b,
+                      [&] { return enqueue_vertex_tangent(ctx, n_dirs, b[0].as<const double>(), b[1].as<float2>()); });
 }
 
 // Host only.  The view is p -> R_n(... R_1(p)), R_k(p) = M_k (p - o_k) + o_k (axis 0: about the x axis, o = 0; axis 1: about

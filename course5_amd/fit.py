@@ -1,5 +1,5 @@
-"""One Gauss-Newton step of a fit of the cell field (alpha, Q) to observed images (and the gradient of a shape fit:
-shape_gradient, at the end).
+"""One Gauss-Newton step of a fit of the cell field (alpha, Q) to observed images (and, at the end, of a shape fit: its
+gradient, shape_gradient, and its Gauss-Newton step over the grid's points, shape_step).
 
     delta, models = course5_amd.fit.gn_step(ctx, alpha, q, residual, fit=("q",))
 
@@ -149,3 +149,66 @@ def shape_gradient(ctx, alpha, q, residual, weight=None):
         g = (r if w is None else r * w).contiguous()
         loss = 0.5 * float((g.to(torch.float64) * r.to(torch.float64)).sum())
         return loss, autograd._vertex_adjoint(ctx, g, device)
+
+
+def shape_step(ctx, alpha, q, residual, weight=None, damping: float = 1e-3, iters: int = 10, free=None):
+    """One Gauss-Newton step of a fit of the grid's SHAPE: up to `iters` iterations of CG from d = 0 on
+        (J^T W J + damping I) d = -J^T W r
+    over the points the context holds, J = d frame / d xyz at them (alpha, q the scalars), r = frame - target the residual
+    image, W the per-pixel weights ([local_rows, res_x, 2]; None: ones).  Every iteration is one vertex tangent render
+    (J p) and one vertex adjoint render (J^T W J p) on the device, float64, on torch's current stream.  free: bool [n_pts]
+    or None (all); the points outside it stay fixed - their rows of every vector are zeroed.  Returns (d_xyz, models):
+    float64 [n_pts, 3] on the context's GPU and, after every iteration done, the model 1/2 d^T (H + damping I) d +
+    d^T J^T W r as a float.  It stops early when the residual of the linear system vanishes or a direction has no
+    curvature.  No line search and no outer loop: the caller owns both (update_points(xyz + d), render, again)."""
+    from . import autograd
+    if damping < 0.0 or iters < 1:
+        raise ValueError("damping must be >= 0 and iters >= 1")
+    device = autograd._gn_enter(ctx, alpha, q, "shape_step")
+    with torch.cuda.device(device):
+        r_img = residual.detach().to(device=device, dtype=torch.float32)
+        if tuple(r_img.shape) != (ctx.local_rows, ctx.res_x, 2):
+            raise ValueError(f"residual must be [{ctx.local_rows}, {ctx.res_x}, 2], not {list(r_img.shape)}")
+        w = autograd._gn_weight(ctx, weight, device)
+        keep = None
+        if free is not None:
+            keep = torch.as_tensor(free, device=device)
+            if keep.dtype != torch.bool or tuple(keep.shape) != (ctx.n_pts,):
+                raise ValueError(f"free must be bool [{ctx.n_pts}]")
+            keep = keep.to(torch.float64).reshape(-1, 1)
+
+        def fixed(v):
+            return v if keep is None else v * keep
+
+        def JtW(img):  # J^T W img: one vertex adjoint render
+            return fixed(autograd._vertex_adjoint(ctx, (img if w is None else img * w).contiguous(), device))
+
+        def H(p):  # J^T W J p: one vertex tangent render, one vertex adjoint render
+            return JtW(autograd._vertex_tangent(ctx, p.reshape(1, ctx.n_pts, 3).contiguous(), device)[0])
+
+        def dot(a, b):
+            return float((a * b).sum())
+
+        g = JtW(r_img)
+        x = torch.zeros_like(g)
+        hx = torch.zeros_like(g)  # (H + damping I) x
+        res = -g
+        p = res.clone()
+        rr = dot(res, res)
+        models = []
+        for _ in range(iters):
+            if not rr > 0.0:
+                break
+            ap = H(p) + damping * p
+            curvature = dot(p, ap)
+            if not curvature > 0.0:
+                break
+            step = rr / curvature
+            x += step * p
+            hx += step * ap
+            res -= step * ap
+            models.append(0.5 * dot(x, hx) + dot(x, g))
+            rr_next = dot(res, res)
+            p = res + (rr_next / rr) * p
+            rr = rr_next
+    return x, models

@@ -439,6 +439,40 @@ int c5_rotation_motion(const c5_rotation* rots, int n_rots, int index, int what,
 int c5_render_vertex_adjoint(c5_context* ctx, const float* grad_out_host, double* grad_xyz_host);
 int c5_render_vertex_adjoint_device(c5_context* ctx, const void* grad_out_dev, void* grad_xyz_dev);
 
+/* --- vertex tangent render ---------------------------------------------------------------------------
+ * The forward mode of the shape: how the frame c5_render would produce NOW changes when every grid point v moves with
+ * the velocity d_xyz[v], the cells' scalars held - the motion tangent with a velocity per point instead of an affine
+ * field.  d_xyz is given in the coordinates c5_upload_grid took; in view space u_v = M d_xyz[v], M the linear part of the
+ * view.  A face with slopes (gx, gy) and the pixel's barycentric coordinates lambda in its projected triangle moves at
+ * the pixel by
+ *     dw = sum_{i<3} lambda_i (u_z - gx u_x - gy u_y)[vertex i of the face],
+ * a segment's chord by ddz_k = dw_exit,k - dw_entry,k, and
+ *     tau_dot = sum_k alpha_k ddz_k                                   (raw alpha, every segment)
+ *     I_dot_k = E_k I_dot_{k-1} + E_k (Q_k - a_k I_{k-1}) ddz_k       (active segments)
+ * as for the motion tangent.  Both faces of a segment are found from its cell's own vertices, as the vertex adjoint finds
+ * them.  For d_xyz[v] = M^T (A p_v + b), p_v the point in view space, the result is c5_render_motion_tangent's for (A, b).
+ * Conventions: the motion tangent's and the vertex adjoint's.  The clamp is on alpha, not on the chord; a cell with
+ * clamped alpha < DBL_EPSILON moves tau only; solid-marked and uncovered pixels are 0; faces edge-on to the rays move
+ * nothing; whole rays in the reference's order whatever "integration", "depth_split", "lds_stage" or "tile" say; pixels
+ * that gain or lose coverage when the points move are not differentiated.
+ * WELDED POINTS: the cells name the representative of a group of welded points (c5_weld_points: rep[i] != i), so the row
+ * of a welded non-representative is never read: the group moves with its representative's row.  (The vertex adjoint
+ * writes exact zeros to those rows.)
+ * DUALITY: this is the operator c5_render_vertex_adjoint is the transpose of.  For any upstream image g and any d_xyz,
+ * <g, out> = <grad_xyz, d_xyz> up to the fp32 rounding of out and the adjoint's order of summation.
+ * d_xyz: [n_dirs][n_pts][3] fp64 in the caller's point order.  out: [n_dirs][local_rows][res_x][2] fp32, the motion
+ * tangent's layout (row range and row tiles as for a frame).  More than "batch_width" fields run as chunks over one
+ * per-view setup; every slice is bit for bit what the call returns for that field alone.  One walk per ray, no atomics:
+ * bit-reproducible.
+ * Status, retries, side effects and the refusal while c5_render_host_async frames are outstanding: as
+ * c5_render_tangent_batch's (C5_ERR_INVALID for a null pointer or n_dirs < 1; the adjoint's counters and status words,
+ * never a frame's; a c5_render afterwards returns the bits it would have returned without it).  The first call allocates
+ * 24 bytes per point and field of a chunk; a context that never calls it uses no more memory than before.
+ * c5_render_vertex_tangent is synchronous with host arrays and retries by itself on C5_RETRY; the _device form is
+ * asynchronous on the context's stream with device arrays. */
+int c5_render_vertex_tangent(c5_context* ctx, int n_dirs, const double* d_xyz_host, float* out_host);
+int c5_render_vertex_tangent_device(c5_context* ctx, int n_dirs, const void* d_xyz_dev, void* out_dev);
+
 /* --- frames delivered to host memory, pipelined ----------------------------------------------------
  * plane::trace_rays hands back HOST pixels (plane.cpp:144-172); over PCIe Gen5 a 2400x1800 image is
  * 0.65 ms of transfer beside 0.7 ms of rendering, so the two are overlapped: c5_render_host_async renders
