@@ -60,6 +60,9 @@ Beside render, two operators for Gauss-Newton fits (course5_amd.fit): gn_product
 J^T W J v and gn_diagonal(ctx, alpha, q, weight) = diag(J^T W J), one library call each (c5_render_gn_product_device,
 c5_render_gn_diagonal_device).  They upload the scalars as the forward does, return float64 tensors on the context's GPU
 without a graph, and raise under a differentiating torch.func transform.
+
+ray_matrix(ctx) hands out the operator itself: the frame's per-pixel (cell, chord) lists as a torch.sparse_csr_tensor on the
+context's GPU (c5_ray_matrix_rows_device, c5_ray_matrix_fill_device), for solvers that want A and not only A v and A^T g.
 """
 from __future__ import annotations
 
@@ -696,4 +699,32 @@ def gn_diagonal(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, weight=
     return da, dq
 
 
-__all__ = ["render", "render_view", "render_mesh", "gn_product", "gn_diagonal"]
+def ray_matrix(ctx: capi.Context, with_depth: bool = False):
+    """The ray matrix A of the frame `ctx` would render now: a torch.sparse_csr_tensor [local_rows * res_x, n_cells],
+    float64, on the context's GPU, A[pixel, cell] = the chord of the pixel's ray through the cell (rows: local pixels lrow *
+    res_x + col; columns: cells in the order of upload_grid; within a row the deepest segment first).  A @ alpha is channel
+    0 of render() (tau) in fp64, and A.T @ g is render_adjoint's grad_alpha for the upstream image (g, 0).  Channel 1 is
+    not linear in alpha: no matrix gives it.  Indices are int32 while nnz < 2^31, else int64.  with_depth: (A, z_exit),
+    z_exit float64 [nnz]: every segment's far end in view space, in the order of A.values().  Built on torch's current
+    stream (c5_ray_matrix_rows_device, c5_ray_matrix_fill_device) and waited for; no graph: A does not depend on the
+    scalars.  Bit-reproducible."""
+    device = torch.device("cuda", ctx.device)
+    n_px = ctx.local_rows * ctx.res_x
+    with torch.cuda.device(device):
+        crow = torch.empty(n_px + 1, dtype=torch.int64, device=device)
+        _use_torch_stream(ctx, device)
+        nnz = ctx.ray_matrix_rows_device(crow)  # (waits and retries by itself)
+        # (an empty torch tensor has no data pointer to hand over)
+        col = torch.empty(max(nnz, 1), dtype=torch.int32, device=device)
+        dz = torch.empty(max(nnz, 1), dtype=torch.float64, device=device)
+        z_exit = torch.empty(max(nnz, 1), dtype=torch.float64, device=device) if with_depth else None
+        _run(ctx, lambda: ctx.ray_matrix_fill_device(crow, col, dz, z_exit))
+        if nnz < 2 ** 31:
+            crow = crow.to(torch.int32)
+        else:
+            col = col.to(torch.int64)
+        A = torch.sparse_csr_tensor(crow, col[:nnz], dz[:nnz], size=(n_px, ctx.n_cells))
+    return (A, z_exit[:nnz]) if with_depth else A
+
+
+__all__ = ["render", "render_view", "render_mesh", "gn_product", "gn_diagonal", "ray_matrix"]

@@ -35,6 +35,7 @@ EXPORTS = [
     "c5_render_motion_tangent", "c5_render_motion_tangent_device", "c5_rotation_motion",
     "c5_render_vertex_adjoint", "c5_render_vertex_adjoint_device", "c5_update_points",
     "c5_render_vertex_tangent", "c5_render_vertex_tangent_device",
+    "c5_ray_matrix_rows", "c5_ray_matrix_rows_device", "c5_ray_matrix_fill", "c5_ray_matrix_fill_device",
 ]
 
 
@@ -127,6 +128,11 @@ def load_library() -> C.CDLL:
     lib.c5_update_points.argtypes = [vp, dp, C.c_int64]
     lib.c5_render_vertex_tangent.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_float)]
     lib.c5_render_vertex_tangent_device.argtypes = [vp, C.c_int, vp, vp]
+    lp = C.POINTER(C.c_int64)
+    lib.c5_ray_matrix_rows.argtypes = [vp, lp, lp]
+    lib.c5_ray_matrix_rows_device.argtypes = [vp, vp, lp]
+    lib.c5_ray_matrix_fill.argtypes = [vp, lp, C.c_int64, ip, dp, dp]
+    lib.c5_ray_matrix_fill_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("c5_destroy", "c5_last_error"):
             getattr(lib, name).restype = C.c_int
@@ -394,6 +400,73 @@ class Context:
         d_ptr = _device_ptr(d_xyz, torch.float64, (k, self.n_pts, 3))
         out_ptr = _device_ptr(out, torch.float32, (k, self.local_rows, self.res_x, 2))
         self._check(self.lib.c5_render_vertex_tangent_device(self.handle, k, C.c_void_p(d_ptr or None), C.c_void_p(out_ptr or None)))
+
+    # -- ray matrix --------------------------------------------------------------------------------
+    def ray_matrix_rows(self) -> np.ndarray:
+        """row_ptr of the ray matrix of the frame render() would produce now: int64 [local_rows * res_x + 1], the exclusive
+        prefix sums of the pixels' segment counts (row_ptr[-1]: all of them).  Synchronous; retries by itself."""
+        row_ptr = np.zeros(self.local_rows * self.res_x + 1, dtype=np.int64)
+        nnz = C.c_int64()  # (row_ptr[-1] says the same)
+        self._check(self.lib.c5_ray_matrix_rows(self.handle, row_ptr.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(nnz)))
+        return row_ptr
+
+    def ray_matrix_rows_device(self, row_ptr) -> int:
+        """The same into device memory: a contiguous int64 [local_rows * res_x + 1] torch tensor on this context's GPU or a
+        raw device pointer.  Waits for the stream and returns the number of segments; runs the call again on C5_RETRY."""
+        import torch
+        nnz = C.c_int64()
+        ptr = _device_ptr(row_ptr, torch.int64, (self.local_rows * self.res_x + 1,))
+        for _ in range(3):
+            if self._check(self.lib.c5_ray_matrix_rows_device(self.handle, C.c_void_p(ptr or None), C.byref(nnz)), allow=(C5_RETRY,)) == C5_OK:
+                return nnz.value
+        raise C5Error(C5_RETRY, "ray_matrix_rows_device: the entry buffer kept overflowing")
+
+    def _row_ptr(self, row_ptr) -> np.ndarray:
+        if not isinstance(row_ptr, np.ndarray) or row_ptr.dtype != np.int64:
+            raise ValueError("row_ptr must be the int64 array ray_matrix_rows returned")
+        if row_ptr.shape != (self.local_rows * self.res_x + 1,):
+            raise ValueError(f"row_ptr must be [{self.local_rows * self.res_x + 1}], not {list(row_ptr.shape)}")
+        return np.ascontiguousarray(row_ptr)
+
+    def ray_matrix_fill(self, row_ptr, with_depth: bool = False, capacity: int | None = None) -> tuple:
+        """The ray matrix's arrays for ray_matrix_rows' row_ptr of this frame: (col int32, dz float64[, z_exit float64]),
+        [capacity] each (default: row_ptr[-1]).  col: cells in the order of upload_grid; within a row deepest segment first;
+        z_exit: the segment's far end in view space.  Raises C5_ERR_STATE if the frame changed since ray_matrix_rows.
+        Synchronous; retries by itself.  Bit-reproducible."""
+        row_ptr = self._row_ptr(row_ptr)
+        n = int(row_ptr[-1]) if capacity is None else int(capacity)
+        if n < 0:
+            raise ValueError(f"capacity must not be negative ({n})")
+        col = np.zeros(max(n, 1), dtype=np.int32)
+        dz = np.zeros(max(n, 1), dtype=np.float64)
+        z_exit = np.zeros(max(n, 1), dtype=np.float64) if with_depth else None
+        self._check(self.lib.c5_ray_matrix_fill(self.handle, row_ptr.ctypes.data_as(C.POINTER(C.c_int64)), n,
+                                                col.ctypes.data_as(C.POINTER(C.c_int32)), _dp(dz),
+                                                None if z_exit is None else _dp(z_exit)))
+        return (col[:n], dz[:n], z_exit[:n]) if with_depth else (col[:n], dz[:n])
+
+    def ray_matrix_fill_device(self, row_ptr, col, dz, z_exit=None, capacity: int | None = None):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (row_ptr int64 [local_rows * res_x
+        + 1], col int32 / dz float64 / z_exit float64 or None, [capacity] each, contiguous) or raw device pointers (then
+        give capacity).  Nothing beyond capacity is written; a frame that changed since ray_matrix_rows, or a capacity
+        below row_ptr's total, makes the next synchronize() raise C5_ERR_STATE."""
+        import torch
+        if capacity is None:
+            if col is None or isinstance(col, int):
+                raise ValueError("give capacity with raw device pointers")
+            capacity = col.shape[0]
+        shape = (capacity,)
+        ptrs = (_device_ptr(row_ptr, torch.int64, (self.local_rows * self.res_x + 1,)), _device_ptr(col, torch.int32, shape),
+                _device_ptr(dz, torch.float64, shape), _device_ptr(z_exit, torch.float64, shape))
+        self._check(self.lib.c5_ray_matrix_fill_device(self.handle, C.c_void_p(ptrs[0] or None), capacity, C.c_void_p(ptrs[1] or None),
+                                                       C.c_void_p(ptrs[2] or None), C.c_void_p(ptrs[3] or None)))
+
+    def ray_matrix(self, with_depth: bool = False) -> tuple:
+        """The ray matrix A of the frame render() would produce now as CSR arrays (row_ptr, col, dz[, z_exit]): rows are the
+        local pixels lrow * res_x + col, columns the cells in the order of upload_grid, A[pixel, cell] = the chord of the
+        pixel's ray through the cell.  A @ alpha is channel 0 of render() in fp64."""
+        row_ptr = self.ray_matrix_rows()
+        return (row_ptr,) + self.ray_matrix_fill(row_ptr, with_depth)
 
     # -- tangent render ----------------------------------------------------------------------------
     def render_tangent(self, d_alpha=None, d_q=None) -> np.ndarray:

@@ -207,6 +207,32 @@ void launch_vertex_tangent_resolve(hipStream_t s, const GridView& g, const Image
                                    const int64_t* offs, void* segs, const uint32_t* mask, double alpha_limit, const double* u_view,
                                    int kc, int j, float2* out);
 
+// ---- ray matrix (c5_ray_matrix_*): per pixel the cells its ray crosses and the chord of each crossing, as CSR arrays
+
+struct RayMatrixParams {
+    WalkParams w;             // as TangentParams (unused by the *_resolve twins)
+    int32_t* count;           // pass 1 out: [n_local_px] segments per pixel
+    // pass 2: row p's element k goes to row_ptr[p] + k where that lies in [0, capacity) and k < row_ptr[p + 1] - row_ptr[p]
+    const int64_t* row_ptr;   // [n_local_px + 1]
+    int64_t capacity;
+    const int32_t* perm;      // device order -> the caller's (nullptr: the identity)
+    int32_t* col;             // [capacity] the cell, the caller's order
+    double* dz;               // [capacity] the chord
+    double* z_exit;           // [capacity] the segment's far end in view space, or nullptr
+    unsigned* changed_rows;   // += rows whose length is not row_ptr's or that found no room below capacity
+};
+
+// pass 1: the count; leaves the entry heads in place and counts rays over the step bound and rays that skipped an entry as
+// launch_adjoint_walk(.., 1) does.  pass 2 (after a per-view setup of its own): the fill, in the order the walk runs -
+// deepest first; counts as pass 1 and hands the heads back cleared.  The step is adj::ray_step: the other derivatives' chords.
+void launch_segment_walk(hipStream_t s, const RayMatrixParams& m, int pass);
+
+// the same over bin_sort_resolve's lists: the count, and the fill (sorts them in place, as launch_adjoint_resolve)
+void launch_segment_count_resolve(hipStream_t s, const ImageParams& im, const int64_t* offs, const void* segs, const uint32_t* mask,
+                                  int32_t* count);
+void launch_segment_fill_resolve(hipStream_t s, const ImageParams& im, const int64_t* offs, void* segs, const uint32_t* mask,
+                                 const RayMatrixParams& m);
+
 // c5_update_scalars_device: alpha[i] = alpha_src[perm[i]], q[i] = q_src[perm[i]] (perm nullptr: the identity), and into
 // stats[3] (zeroed by the caller): the bits of the largest alpha > 0, the complemented bits of the smallest alpha >=
 // DBL_EPSILON, and 1 if some alpha is NaN (the host loop of c5_update_scalars, as an order-free max / min / or)

@@ -55,6 +55,10 @@
 // for a displacement per grid point: vertex_velocity, then vertex_tangent_walk / vertex_tangent_resolve (their block
 // further down).
 //
+// The ray matrix (c5_ray_matrix_*): the segments every render above sums over, themselves: segment_walk<1> counts them per
+// pixel, segment_walk<2> stores (cell, dz, z_exit) per segment into CSR arrays; segment_count_resolve / segment_fill_resolve
+// over bin_sort_resolve's lists (their block further down).
+//
 // Every walk kernel here (the batched and Gauss-Newton ones further down included) takes its rays through adj::Ray: ONE
 // definition of the walk's step, of how a ray begins and of what it leaves behind.  The kernels differ in what they
 // accumulate along the ray, and those that differ in nothing else share a body with a compile-time parameter
@@ -1616,6 +1620,128 @@ __global__ __launch_bounds__(256) void vertex_tangent_resolve(GridView g, ImageP
     out[lp] = make_float2(static_cast<float>(tau_dot), static_cast<float>(I_dot));
 }
 
+// ---- ray matrix (c5_ray_matrix_*): the segments themselves - per pixel the cells its ray crosses, the chord of each
+// crossing and where it ends - as CSR arrays.  Two calls with a per-view setup each: the count (pass 1, then launch_scan64
+// over the counts) and the fill (pass 2).  Each lane owns its row and appends to it with plain stores: no atomics,
+// bit-reproducible.
+
+namespace adj {
+
+// Where a lane's row goes: element k at base + k for k < n_ok, the part of row_ptr's row that lies in [0, capacity).
+// fits: all of row_ptr's row does.  Whatever row_ptr holds, base + k stays inside [0, capacity) for k < n_ok.
+struct RowSlot {
+    long long base = 0;
+    unsigned n_ok = 0;
+    bool fits = true;
+};
+__device__ __forceinline__ RowSlot row_slot(const int64_t* __restrict__ row_ptr, size_t lp, long long capacity) {
+    RowSlot s;
+    s.base = row_ptr[lp];
+    const long long end = row_ptr[lp + 1];
+    const long long len = (s.base >= 0 && end >= s.base) ? end - s.base : -1;
+    const long long room = (s.base >= 0 && s.base < capacity) ? capacity - s.base : 0;  // (0 < room <= capacity: no overflow)
+    const long long ok = len < room ? len : room;
+    s.n_ok = ok > 0 ? static_cast<unsigned>(ok < 0x7fffffffll ? ok : 0x7fffffffll) : 0u;
+    s.fits = len >= 0 && static_cast<long long>(s.n_ok) == len;
+    return s;
+}
+
+// rows whose length is not row_ptr's or that found no room below capacity, counted once per wavefront
+__device__ __forceinline__ void count_changed_rows(bool changed, unsigned* __restrict__ changed_rows) {
+    const unsigned n = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(changed)));
+    if (n && (threadIdx.x & 63) == 0) atomicAdd(changed_rows, n);
+}
+
+__device__ __forceinline__ void store_segment(const RayMatrixParams& A, long long at, int cell, double dz, double z_exit) {
+    // (plain stores: a lane's next element lands in the line its last one did, and L2 merges them.  Nontemporal stores
+    // took 16.1 ms against 4.96 for the benchmark frame's fill: profiles/ray_matrix.md)
+    A.col[at] = A.perm ? A.perm[cell] : cell;
+    A.dz[at] = dz;
+    if (A.z_exit) A.z_exit[at] = z_exit;
+}
+
+}  // namespace adj
+
+// PASS 1: the segments per pixel (int32); leaves the entry heads in place and counts as adjoint_walk<1> does.  PASS 2
+// (its own per-view setup before it): the same walk, every segment stored; counts, and hands the heads back cleared.
+// Nothing is shared between the lanes: a lane leaves the loop when its ray ends, as in tangent_walk.
+template <int PASS>
+__global__ __launch_bounds__(64) void segment_walk(RayMatrixParams A) {
+    using namespace adj;
+    const WalkParams& P = A.w;
+    Ray r;
+    unsigned k = 0;  // segments of the ray so far
+    RowSlot slot;
+
+    const EntryHead ent = ray_begin(r, P);
+    if (PASS == 2 && r.in_image) slot = row_slot(A.row_ptr, r.lp, A.capacity);
+
+    CellRegs cur;
+    if (r.cell >= 0) load_cell(cur, P.xrec, r.cell);
+
+    while (r.cell >= 0) {
+        double dz, carry_next;
+        const int nb = ray_step(r, P, ent, cur, dz, carry_next);
+        CellRegs nxt;
+        if (nb >= 0) load_cell(nxt, P.xrec, nb);
+
+        if (is_segment(dz)) {
+            // (the exit ray_step took, found again from the same registers: carry_next is already the next entry's depth
+            // where the ray re-enters the grid.  The walk coordinate of "integration" 0 is view z.)
+            if (PASS == 2 && k < slot.n_ok) store_segment(A, slot.base + k, r.cell, dz, step_geometry(cur, r.x, r.y).w_exit);
+            ++k;
+        }
+        ray_advance(r, nb, carry_next);
+        cur = nxt;
+    }
+
+    if (PASS == 1) {
+        if (r.in_image) A.count[r.lp] = static_cast<int32_t>(k);
+    } else {
+        count_changed_rows(r.in_image && !(slot.fits && k == slot.n_ok), A.changed_rows);
+        ray_clear_head(r, P);
+    }
+    ray_count(r, P);
+}
+
+// segment_walk's twins over bin_sort_resolve's lists ("algorithm" 1): the segments resolve_pixels integrates (those of
+// dz > 0: the others add nothing), in the order its recurrence runs (i = n - 1 ... 0 of the sorted list).
+__global__ __launch_bounds__(256) void segment_count_resolve(ImageParams im, const int64_t* __restrict__ offs,
+                                                             const AdjSegment* __restrict__ segs, const uint32_t* __restrict__ mask,
+                                                             int32_t* __restrict__ count) {
+    const int64_t lp = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (lp >= static_cast<int64_t>(im.n_local_rows) * im.res_x) return;
+    int32_t k = 0;
+    if (!(mask && mask[lp]))
+        for (int64_t i = offs[lp]; i < offs[lp + 1]; ++i) k += adj::is_segment(segs[i].dz) ? 1 : 0;
+    count[lp] = k;
+}
+
+__global__ __launch_bounds__(256) void segment_fill_resolve(ImageParams im, const int64_t* __restrict__ offs,
+                                                            AdjSegment* __restrict__ segs, const uint32_t* __restrict__ mask,
+                                                            RayMatrixParams A) {
+    using namespace adj;
+    const int64_t lp = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    const bool in_image = lp < static_cast<int64_t>(im.n_local_rows) * im.res_x;
+    bool changed = false;
+    if (in_image) {
+        const RowSlot slot = row_slot(A.row_ptr, static_cast<size_t>(lp), A.capacity);
+        unsigned k = 0;
+        if (!(mask && mask[lp])) {
+            AdjSegment* const list = segs + offs[lp];
+            const int n = static_cast<int>(offs[lp + 1] - offs[lp]);
+            sort_segments(list, n);
+            for (int i = n - 1; i >= 0; --i) {
+                if (!is_segment(list[i].dz)) continue;
+                if (k < slot.n_ok) store_segment(A, slot.base + k, static_cast<int>(list[i].cell), list[i].dz, list[i].z_hi);
+                ++k;
+            }
+        }
+        changed = !(slot.fits && k == slot.n_ok);
+    }
+    count_changed_rows(changed, A.changed_rows);
+}
+
 namespace {
 // workgroups of a walk kernel: one wavefront per 8x8 pixel tile (0: no pixel)
 unsigned tile_blocks(const ImageParams& im) {
@@ -1775,6 +1901,27 @@ void launch_vertex_tangent_resolve(hipStream_t s, const GridView& g, const Image
     if (!blocks) return;
     hipLaunchKernelGGL(vertex_tangent_resolve, dim3(blocks), dim3(256), 0, s, g, im, Xtab, Ytab, offs, static_cast<AdjSegment*>(segs),
                        mask, alpha_limit, u_view + 3 * j, 3 * kc, out);
+}
+
+void launch_segment_walk(hipStream_t s, const RayMatrixParams& m, int pass) {
+    const unsigned blocks = tile_blocks(m.w.im);
+    if (!blocks) return;
+    if (pass == 1)
+        hipLaunchKernelGGL(segment_walk<1>, dim3(blocks), dim3(64), 0, s, m);
+    else
+        hipLaunchKernelGGL(segment_walk<2>, dim3(blocks), dim3(64), 0, s, m);
+}
+
+void launch_segment_count_resolve(hipStream_t s, const ImageParams& im, const int64_t* offs, const void* segs, const uint32_t* mask,
+                                  int32_t* count) {
+    const unsigned blocks = pixel_blocks(im);
+    if (blocks) hipLaunchKernelGGL(segment_count_resolve, dim3(blocks), dim3(256), 0, s, im, offs, static_cast<const AdjSegment*>(segs), mask, count);
+}
+
+void launch_segment_fill_resolve(hipStream_t s, const ImageParams& im, const int64_t* offs, void* segs, const uint32_t* mask,
+                                 const RayMatrixParams& m) {
+    const unsigned blocks = pixel_blocks(im);
+    if (blocks) hipLaunchKernelGGL(segment_fill_resolve, dim3(blocks), dim3(256), 0, s, im, offs, static_cast<AdjSegment*>(segs), mask, m);
 }
 
 void launch_scalars_gather(hipStream_t s, const double* alpha_src, const double* q_src, const int32_t* perm, int64_t n, double* alpha,

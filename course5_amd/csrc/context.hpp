@@ -292,6 +292,8 @@ struct c5_context {
                                    // (measured on the C3 frame: 5.7 ms against 58 ms for the walk; profiles/vertex_adjoint_probe.md)
     // vertex tangent (c5_render_vertex_tangent*): allocated at the first call only
     c5api::DeviceBuffer vtx_vel;   // [n_pts][width][3] fp64: the points' view-space velocities (vertex_velocity)
+    // ray matrix (c5_ray_matrix_*): allocated at the first call only (the scan's scratch is bin_sort_resolve's scratch64)
+    c5api::DeviceBuffer rm_count;  // [padded local px] int32 segments per pixel, then one word: rows the fill found changed
     // c5_update_points: the cells as the device has them (welded, in its order) and, where c5_upload_grid welded points,
     // every point's representative (empty: none welded) - what measure_grid and upload_block_spheres are run again with
     std::vector<int32_t> host_cell_vert, point_rep;

@@ -473,6 +473,47 @@ int c5_render_vertex_adjoint_device(c5_context* ctx, const void* grad_out_dev, v
 int c5_render_vertex_tangent(c5_context* ctx, int n_dirs, const double* d_xyz_host, float* out_host);
 int c5_render_vertex_tangent_device(c5_context* ctx, int n_dirs, const void* d_xyz_dev, void* out_dev);
 
+/* --- ray matrix --------------------------------------------------------------------------------------
+ * The operator every derivative render applies, handed out: for each pixel the cells its ray crosses and the chord dz of
+ * each crossing, as a CSR matrix A with A[pixel][cell] = dz.  Channel 0 of the image is linear in the cells' alpha:
+ * tau = A alpha (raw alpha, line.cpp:189), and A^T g is c5_render_adjoint's grad_alpha for the upstream image (g, 0).
+ * Channel 1 (I) is not linear in alpha and is not covered.
+ * The matrix belongs to the frame c5_render would produce NOW: grid, solids, image, row range and row tiles, view.  No
+ * render needs to come first; the cells' scalars and the alpha limit do not enter.
+ * Rows: the context's local pixels, lrow * res_x + col, the output image's order.  Columns: cells in the CALLER's order
+ * (c5_upload_grid's), whatever "cell_order" does inside.  Within a row the segments come in the order of the reference's
+ * recurrence (line.cpp:206): deepest first, z ascending.  The entries are exactly the segments the frame sums: dz > 0 and
+ * finite.  Solid-marked and uncovered pixels have empty rows; a solids-only scene gives all-empty rows (its fill writes
+ * nothing, waits for the stream and returns C5_ERR_STATE itself for a row_ptr whose total is not 0).  A ray crosses a
+ * cell at most once: (row, column) pairs are unique.
+ * Two calls, count and fill:
+ * c5_ray_matrix_rows: row_ptr[local_px + 1] int64, the exclusive prefix sums of the rows' lengths; row_ptr[local_px] ==
+ * *nnz.  Waits for the stream: *nnz (host memory in both forms) is valid on return.  The host form retries by itself on
+ * C5_RETRY; the _device form returns C5_RETRY (run it again).
+ * c5_ray_matrix_fill: row_ptr is what c5_ray_matrix_rows returned for this frame (input).  col[capacity] int32,
+ * dz[capacity] fp64, z_exit[capacity] fp64 or NULL: the segment's far end in view space (the reference's z_hi; its near
+ * end is z_exit - dz).  The host form is synchronous and retries by itself; the _device form is asynchronous on the
+ * context's stream and reports at the next call that waits for it.
+ * The fill is stateless and guarded: element k of row p goes to i = row_ptr[p] + k only where 0 <= i < capacity and
+ * k < row_ptr[p + 1] - row_ptr[p]; nothing outside [0, capacity) is ever written, whatever row_ptr holds.  A row whose
+ * length differs from row_ptr's, or that found no room below capacity, is counted, and the next wait returns C5_ERR_STATE
+ * ("the frame changed between c5_ray_matrix_rows and c5_ray_matrix_fill").  row_ptr[local_px] > capacity in the host
+ * form: C5_ERR_INVALID with the size needed, nothing written.
+ * No atomics, every lane owns its row: bit-reproducible from run to run, and the rows of a row range or of row tiles
+ * are bit for bit those rows of the whole frame's matrix.
+ * Status, retries, side effects: the other derivative renders' (each call makes a per-view setup of its own; the adjoint's
+ * counters and status words, never a frame's; a c5_render afterwards returns the bits it would have returned without
+ * them; C5_ERR_WALK; C5_RETRY for a grown entry pool or interpenetrating components).  A null pointer (z_exit excepted):
+ * C5_ERR_INVALID.  All four refuse while c5_render_host_async frames are outstanding (C5_ERR_STATE).  The first call
+ * allocates 4 bytes per local pixel and the scan's scratch; a context that never calls them uses no more memory than
+ * before.  The arrays take nnz x 12 bytes, 20 with z_exit. */
+int c5_ray_matrix_rows(c5_context* ctx, int64_t* row_ptr_host, int64_t* nnz);
+int c5_ray_matrix_rows_device(c5_context* ctx, void* row_ptr_dev, int64_t* nnz);
+int c5_ray_matrix_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t capacity, int32_t* col_host, double* dz_host,
+                       double* z_exit_host);
+int c5_ray_matrix_fill_device(c5_context* ctx, const void* row_ptr_dev, int64_t capacity, void* col_dev, void* dz_dev,
+                              void* z_exit_dev);
+
 /* --- frames delivered to host memory, pipelined ----------------------------------------------------
  * plane::trace_rays hands back HOST pixels (plane.cpp:144-172); over PCIe Gen5 a 2400x1800 image is
  * 0.65 ms of transfer beside 0.7 ms of rendering, so the two are overlapped: c5_render_host_async renders

@@ -1,0 +1,409 @@
+"""Ray matrix on the GPU (c5_ray_matrix_rows*, c5_ray_matrix_fill*; capi.Context.ray_matrix, autograd.ray_matrix): the
+per-pixel (cell, chord) lists as CSR, against the reference's own lists (tests/golden/g3_segments_g2_view1.npz), against
+tests/adjoint_reference.segment_lists on whole frames, and against the library's own renders.
+
+Bars (tests/derivative_fuzz.py's, none fitted to what the GPU returns).  Chords and depths: |error| <= 16 x 2^-52 x
+max(1, max |view-space coordinate|) x max(1, F), F = |gx| + |gy| of the steeper of the segment's two faces
+(segment_lists(with_slope=True)).  fp32 outputs: 2^-23.  fp64 sums: 1e-9 on the element's own absolute-sum scale.
+Structure - the sorted (pixel, cell) pairs - must match exactly; the order inside a row is checked apart: z_exit never
+decreases.  Every reference is computed once per module and shared."""
+import ctypes as C
+import functools
+import os
+import types
+
+import numpy as np
+import pytest
+
+from course5_amd import capi
+from course5_amd import meshgen as mg
+from course5_amd import sharding
+from tests import adjoint_reference as ar, derivative_fuzz as fz
+
+pytestmark = pytest.mark.gpu
+B = mg.REFERENCE_BOUNDS
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+VIEW = mg.view_rotations(0.1, 0.07)
+
+
+def _ctx(xyz, cells, alpha, q, rots, rx, ry, bounds=B, options=()):
+    ctx = capi.Context(0)
+    for k, v in options:
+        ctx.set_option(k, v)
+    ctx.upload_grid(xyz, cells, alpha, q)
+    ctx.set_image(rx, ry, bounds)
+    ctx.set_view(rots)
+    return ctx
+
+
+@functools.lru_cache(maxsize=None)
+def _golden(name):
+    g = np.load(os.path.join(GOLDEN, name + ".npz"))
+    return {k: g[k] for k in g.files}
+
+
+@functools.lru_cache(maxsize=None)
+def _scene(kind):
+    """(xyz, cells, alpha, q, rots, rx, ry, bounds, reference segment count or None)"""
+    if ":" in kind:  # a golden fixture and one of its views
+        name, view = kind.split(":")
+        g = _golden(name)
+        rx, ry = (int(v) for v in g["res"])
+        return g["xyz"], g["cells"], g["alpha"], g["q"], g[f"rots{view}"], rx, ry, tuple(g["bounds"]), int(g[f"segments{view}"])
+    if kind == "morton":
+        xyz, cells = mg.kuhn_box(9, jitter=0.1)  # 4 374 cells: kept in Morton order on the device ("cell_order" 1)
+        return (xyz, cells) + mg.scalars(len(cells)) + (VIEW, 61, 43, B, 16194)
+    assert kind == "soup"
+    xyz, cells = mg.per_cell_point_copies(*mg.kuhn_box(4, jitter=0.1))
+    return (xyz, cells) + mg.scalars(len(cells)) + (VIEW, 61, 43, B, 7187)
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(kind):
+    """segment_lists of the scene: (pixel, cell, z_hi, dz, slope), by pixel and ascending z_hi; and the chord bar's unit."""
+    xyz, cells, _a, _q, rots, rx, ry, bounds, _n = _scene(kind)
+    ref = ar.segment_lists(xyz, cells, rots, rx, ry, bounds, with_slope=True)
+    for a in ref:
+        a.setflags(write=False)
+    return ref, fz.dz_err(types.SimpleNamespace(xyz=xyz, rots=rots))
+
+
+@functools.lru_cache(maxsize=None)
+def _matrix(kind, options=()):
+    """The GPU's matrix of the scene, with depths: (row_ptr, col, dz, z_exit)."""
+    xyz, cells, alpha, q, rots, rx, ry, bounds, _n = _scene(kind)
+    with _ctx(xyz, cells, alpha, q, rots, rx, ry, bounds, options) as ctx:
+        m = ctx.ray_matrix(with_depth=True)
+    for a in m:
+        a.setflags(write=False)
+    return m
+
+
+def _rows_of(row_ptr):
+    return np.repeat(np.arange(len(row_ptr) - 1), np.diff(row_ptr))
+
+
+def _check_csr(m, n_px, n_cells):
+    row_ptr, col, dz, z_exit = m
+    assert row_ptr.dtype == np.int64 and col.dtype == np.int32 and dz.dtype == np.float64 and z_exit.dtype == np.float64
+    assert row_ptr.shape == (n_px + 1,) and row_ptr[0] == 0 and (np.diff(row_ptr) >= 0).all()
+    assert len(col) == len(dz) == len(z_exit) == row_ptr[-1]
+    assert ((col >= 0) & (col < n_cells)).all() and (dz > 0).all() and np.isfinite(dz).all() and np.isfinite(z_exit).all()
+    pix = _rows_of(row_ptr)
+    assert len(np.unique(pix * np.int64(n_cells) + col)) == len(col)  # a ray crosses a cell at most once
+    inside = pix[1:] == pix[:-1]
+    assert (np.diff(z_exit)[inside] >= 0).all()  # deepest first, z ascending
+    return pix
+
+
+def _check_against_reference(kind, m, what):
+    """Structure exactly, nnz, dz and z_exit within the chord bar; prints the worst error / bar of both."""
+    xyz, cells, _a, _q, _rots, rx, ry, _b, want = _scene(kind)
+    (rpix, rcell, rzh, rdz, rslope), unit = _reference(kind)
+    row_ptr, col, dz, z_exit = m
+    pix = _check_csr(m, rx * ry, len(cells))
+    assert len(rpix) == want  # (the reference's own count: the fixture is what the issue says it is)
+    assert row_ptr[-1] == want
+    og, orf = np.lexsort((col, pix)), np.lexsort((rcell, rpix))
+    assert np.array_equal(pix[og], rpix[orf]) and np.array_equal(col[og], rcell[orf])
+    bar = unit * np.maximum(1.0, rslope[orf])
+    e_dz, e_z = np.abs(dz[og] - rdz[orf]) / bar, np.abs(z_exit[og] - rzh[orf]) / bar
+    print(f"{what}: nnz {want}, smallest chord {rdz.min():.3g}, bar {bar.min():.3g} .. {bar.max():.3g}, worst error / bar: "
+          f"dz {e_dz.max():.3g}, z_exit {e_z.max():.3g}")
+    assert (e_dz <= 1.0).all(), f"{what}: {int((e_dz > 1).sum())} chords over their bar, worst {e_dz.max():.3g}"
+    assert (e_z <= 1.0).all(), f"{what}: {int((e_z > 1).sum())} depths over their bar, worst {e_z.max():.3g}"
+
+
+def test_g3_the_references_own_lists():
+    """The 24 probed pixels of G3 (line::calculate_intersections in the reference's object code, nearest segment first):
+    the row's columns are tet{k} reversed exactly, its chords dz{k} reversed within the chord bar."""
+    g3, kind = _golden("g3_segments_g2_view1"), "g2_kuhn4_120x90:1"
+    xyz, cells, _a, _q, rots, rx, ry, bounds, want = _scene(kind)
+    assert np.array_equal(rots, g3["rots"]) and (rx, ry) == tuple(g3["res"]) and np.array_equal(bounds, g3["bounds"])
+    gx, gc = mg.workload("g2")[:2]
+    assert np.array_equal(gx, xyz) and np.array_equal(gc, cells)
+    (rpix, rcell, _zh, rdz, rslope), unit = _reference(kind)
+    row_ptr, col, dz, _z = _matrix(kind)
+    assert row_ptr[-1] == want == 30322
+    worst = 0.0
+    for k, (pc, pr) in enumerate(g3["probes"]):
+        p = int(pr) * rx + int(pc)
+        lo, hi = row_ptr[p], row_ptr[p + 1]
+        tet, gdz = g3[f"tet{k}"][::-1], g3[f"dz{k}"][::-1]
+        assert np.array_equal(col[lo:hi], tet), k
+        sel = rpix == p
+        assert np.array_equal(rcell[sel], tet), k  # (reversed G3 is segment_lists' order: its slopes are these segments')
+        bar = unit * np.maximum(1.0, rslope[sel])
+        worst = max(worst, float((np.abs(dz[lo:hi] - gdz) / bar).max()))
+        assert (np.abs(dz[lo:hi] - gdz) <= bar).all(), k
+    print(f"G3: 24 pixels, {int(g3['counts'].sum())} segments, worst |dz - reference's| / bar {worst:.3g}")
+
+
+@pytest.mark.parametrize("kind", ["g2_kuhn4_120x90:0", "g2_kuhn4_120x90:1", "g2_kuhn4_120x90:2", "ball12_150x112:1",
+                                  "g8_hanging_nodes_120x90:3", "g1_cube8_60x45:0"])
+def test_whole_matrices_against_segment_lists(kind):
+    _check_against_reference(kind, _matrix(kind), kind)
+
+
+def test_callers_cell_order_under_the_morton_permutation(oracle_port):
+    xyz, cells, alpha, q, rots, rx, ry, bounds, want = _scene("morton")
+    assert len(cells) >= 4096
+    r = oracle_port.render(xyz, cells, alpha, q, rots, rx, ry, bounds, threads=4)
+    assert r["segments"] == len(_reference("morton")[0][0]) == want
+    _check_against_reference("morton", _matrix("morton", (("cell_order", 1),)), "cell_order 1")
+
+
+def test_algorithm_1_lists():
+    _check_against_reference("soup", _matrix("soup", (("algorithm", 1),)), "algorithm 1")
+
+
+def test_linearity_tau_and_the_adjoint():
+    """A alpha is channel 0 of the frame, A^T g the adjoint's grad_alpha for (g, 0); grad_q is exactly 0 then."""
+    xyz, cells, alpha, q, rots, rx, ry, bounds, _n = _scene("morton")
+    row_ptr, col, dz, _z = _matrix("morton", (("cell_order", 1),))
+    pix = _rows_of(row_ptr)
+    rng = np.random.default_rng(91)
+    g = rng.normal(size=(ry, rx)).astype(np.float32)
+    g[10:20, 15:40] = 0.0
+    with _ctx(xyz, cells, alpha, q, rots, rx, ry, bounds) as ctx:
+        tau = ctx.render()[..., 0].astype(np.float64).reshape(-1)
+        ga, gq = ctx.render_adjoint(np.stack([g, np.zeros_like(g)], axis=-1))
+    mine = np.bincount(pix, weights=dz * alpha[col], minlength=rx * ry)
+    scale = np.bincount(pix, weights=dz * np.abs(alpha[col]), minlength=rx * ry)
+    tol = 2.0 ** -23 * np.abs(tau) + 1e-9 * scale
+    print(f"A alpha against tau: worst error / bar {(np.abs(mine - tau) / np.maximum(tol, 1e-300)).max():.3g}")
+    assert tau.max() > 0 and (np.abs(mine - tau) <= tol).all()
+    g64 = g.astype(np.float64).reshape(-1)
+    mine = np.bincount(col, weights=g64[pix] * dz, minlength=len(cells))
+    scale = np.bincount(col, weights=np.abs(g64[pix]) * dz, minlength=len(cells))
+    print(f"A^T g against grad_alpha: worst error / bar {(np.abs(mine - ga) / np.maximum(1e-9 * scale, 1e-300)).max():.3g}")
+    assert np.abs(ga).max() > 0 and (np.abs(mine - ga) <= 1e-9 * scale).all()
+    assert (gq == 0).all()
+
+
+def _bit_equal_rows(part, whole, global_px):
+    """The rows of `part` (local pixels = global_px of the whole frame) are bit for bit those rows of `whole`."""
+    (rp, col, dz, z), (wrp, wcol, wdz, wz) = part, whole
+    lengths = (wrp[1:] - wrp[:-1])[global_px]
+    if not np.array_equal(np.diff(rp), lengths):
+        return False
+    at = np.repeat(wrp[global_px] - rp[:-1], lengths) + np.arange(rp[-1])
+    return (np.array_equal(col, wcol[at]) and np.array_equal(dz.view(np.uint64), wdz[at].view(np.uint64))
+            and np.array_equal(z.view(np.uint64), wz[at].view(np.uint64)))
+
+
+def test_shards_are_rows_of_the_whole_frame_and_calls_repeat():
+    xyz, cells, alpha, q, rots, rx, ry, bounds, _n = _scene("morton")
+    whole = _matrix("morton", (("cell_order", 1),))
+    with _ctx(xyz, cells, alpha, q, rots, rx, ry, bounds) as ctx:
+        ctx.set_row_range(7, 20)
+        part = ctx.ray_matrix(with_depth=True)
+        again = ctx.ray_matrix(with_depth=True)
+    rows = np.arange(7, 27)
+    assert part[0][-1] > 0 and _bit_equal_rows(part, whole, (rows[:, None] * rx + np.arange(rx)).reshape(-1))
+    assert all(np.array_equal(a.view(np.uint8), b.view(np.uint8)) for a, b in zip(part, again))  # two calls: equal bits
+    seen = 0
+    for rank in range(3):
+        with _ctx(xyz, cells, alpha, q, rots, rx, ry, bounds) as ctx:
+            ctx.set_row_tiles(5, rank, 3)
+            part = ctx.ray_matrix(with_depth=True)
+        rows = sharding.local_rows(ry, 5, rank, 3)
+        assert _bit_equal_rows(part, whole, (rows[:, None] * rx + np.arange(rx)).reshape(-1)), rank
+        seen += part[0][-1]
+    assert seen == whole[0][-1]
+
+
+def test_solid_pixels_have_empty_rows():
+    kind = "g1_cube8_60x45:0"
+    xyz, cells, alpha, q, rots, rx, ry, bounds, _n = _scene(kind)
+    whole = _matrix(kind)
+    lo, hi = xyz.min(0), xyz.max(0)
+    c = 0.5 * (lo + hi)
+    e = 0.2 * (hi - lo).max()
+    tet = np.array([[c + (e, 0, 0), c + (-e, e, 0), c + (-e, -e, e), c + (0, 0, -e)]]).reshape(1, 12)
+    with _ctx(xyz, cells, alpha, q, rots, rx, ry, bounds) as ctx:
+        ctx.set_solid(0, tet)  # colour NaN: solid pixels are NaN in the image
+        ctx.set_solid_view(0, rots)
+        img = ctx.render()
+        part = ctx.ray_matrix(with_depth=True)
+    solid = np.isnan(img[..., 0]).reshape(-1)
+    covered = np.diff(whole[0]) > 0
+    assert 10 < (solid & covered).sum() < covered.sum()
+    assert (np.diff(part[0])[solid] == 0).all()
+    keep = np.flatnonzero(~solid)
+    rp = np.concatenate([[0], np.cumsum(np.diff(part[0])[keep])])
+    at = np.repeat(part[0][:-1][keep] - rp[:-1], np.diff(rp)) + np.arange(rp[-1])
+    assert rp[-1] == part[0][-1]
+    assert _bit_equal_rows((rp, part[1][at], part[2][at], part[3][at]), whole, keep)
+
+
+def test_renders_around_the_calls_are_untouched():
+    kind = "g2_kuhn4_120x90:1"
+    xyz, cells, alpha, q, rots, rx, ry, bounds, _n = _scene(kind)
+    with _ctx(xyz, cells, alpha, q, rots, rx, ry, bounds) as a, _ctx(xyz, cells, alpha, q, rots, rx, ry, bounds) as b:
+        for _ in range(3):  # (three frames: the view cache is in use by the third)
+            ia, ib = a.render(), b.render()
+        before = a.stats()
+        m = a.ray_matrix(with_depth=True)
+        assert a.stats() == before
+        for _ in range(3):
+            ja, jb = a.render(), b.render()
+            assert np.array_equal(ja.view(np.uint32), ia.view(np.uint32)) and np.array_equal(jb.view(np.uint32), ib.view(np.uint32))
+        assert a.stats()["segments"] == b.stats()["segments"] == m[0][-1]
+    assert all(np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(m, _matrix(kind)))
+
+
+def test_capacity_is_a_guard_in_both_forms():
+    import torch
+    kind = "g2_kuhn4_120x90:1"
+    xyz, cells, alpha, q, rots, rx, ry, bounds, nnz = _scene(kind)
+    row_ptr, col, dz, z = _matrix(kind)
+    lp, ip, dp = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    with _ctx(xyz, cells, alpha, q, rots, rx, ry, bounds) as ctx:
+        # host form: refused with the size needed, nothing written
+        hc, hd, hz = np.full(nnz, -7, np.int32), np.full(nnz, -7.0), np.full(nnz, -7.0)
+        rp = np.ascontiguousarray(row_ptr)
+        assert ctx.lib.c5_ray_matrix_fill(ctx.handle, rp.ctypes.data_as(lp), nnz - 1, hc.ctypes.data_as(ip), hd.ctypes.data_as(dp),
+                                          hz.ctypes.data_as(dp)) == capi.C5_ERR_INVALID
+        assert str(nnz) in ctx.lib.c5_last_error(ctx.handle).decode()
+        assert (hc == -7).all() and (hd == -7.0).all() and (hz == -7.0).all()
+        # device form: the guard, and the status word at the next wait
+        cap = nnz - 1
+        d_rp = torch.tensor(rp, device="cuda")
+        d_col = torch.full((nnz + 64,), -7, dtype=torch.int32, device="cuda")
+        d_dz = torch.full((nnz + 64,), -7.0, dtype=torch.float64, device="cuda")
+        d_z = torch.full((nnz + 64,), -7.0, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        ctx.ray_matrix_fill_device(d_rp, d_col.data_ptr(), d_dz.data_ptr(), d_z.data_ptr(), capacity=cap)
+        with pytest.raises(capi.C5Error) as e:
+            ctx.synchronize()
+        assert e.value.code == capi.C5_ERR_STATE and "c5_ray_matrix_fill" in e.value.message
+        gc, gd, gz = d_col.cpu().numpy(), d_dz.cpu().numpy(), d_z.cpu().numpy()
+        assert (gc[cap:] == -7).all() and (gd[cap:] == -7.0).all() and (gz[cap:] == -7.0).all()
+        assert np.array_equal(gc[:cap], col[:cap]) and np.array_equal(gd[:cap], dz[:cap]) and np.array_equal(gz[:cap], z[:cap])
+        assert ctx.synchronize() == capi.C5_OK  # (reported once)
+        # ... and with room for all of it, the same arrays as the host form
+        ctx.ray_matrix_fill_device(d_rp, d_col.data_ptr(), d_dz.data_ptr(), 0, capacity=nnz + 64)
+        assert ctx.synchronize() == capi.C5_OK
+        assert np.array_equal(d_col.cpu().numpy()[:nnz], col) and np.array_equal(d_dz.cpu().numpy()[:nnz], dz)
+        assert (d_col.cpu().numpy()[nnz:] == -7).all()
+
+
+def test_a_changed_view_between_the_calls_is_reported():
+    import torch
+    xyz, cells, alpha, q, rots, rx, ry, bounds, nnz = _scene("g2_kuhn4_120x90:1")
+    other = _scene("g2_kuhn4_120x90:2")[4]
+    with _ctx(xyz, cells, alpha, q, rots, rx, ry, bounds) as ctx:
+        row_ptr = ctx.ray_matrix_rows()
+        assert row_ptr[-1] == nnz
+        ctx.set_view(other)
+        with pytest.raises(capi.C5Error) as e:
+            ctx.ray_matrix_fill(row_ptr)
+        assert e.value.code == capi.C5_ERR_STATE and "the frame changed between c5_ray_matrix_rows and c5_ray_matrix_fill" in e.value.message
+        d_rp = torch.tensor(row_ptr, device="cuda")
+        d_col = torch.full((nnz + 64,), -7, dtype=torch.int32, device="cuda")
+        d_dz = torch.full((nnz + 64,), -7.0, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        ctx.ray_matrix_fill_device(d_rp, d_col.data_ptr(), d_dz.data_ptr(), 0, capacity=nnz)
+        with pytest.raises(capi.C5Error) as e:
+            ctx.synchronize()
+        assert e.value.code == capi.C5_ERR_STATE
+        assert (d_col.cpu().numpy()[nnz:] == -7).all() and (d_dz.cpu().numpy()[nnz:] == -7.0).all()
+        # the frame as it is now: a matrix of its own
+        m = ctx.ray_matrix(with_depth=True)
+    assert all(np.array_equal(a, b) for a, b in zip(m, _matrix("g2_kuhn4_120x90:2")))
+
+
+def test_bad_arguments_and_outstanding_async_frames_are_refused():
+    xyz, cells, alpha, q, rots, rx, ry, bounds, nnz = _scene("g1_cube8_60x45:0")
+    lp, ip, dp = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    rp, n = np.zeros(rx * ry + 1, np.int64), C.c_int64()
+    col, dz = np.zeros(nnz, np.int32), np.zeros(nnz)
+    with _ctx(xyz, cells, alpha, q, rots, rx, ry, bounds) as ctx:
+        lib, h = ctx.lib, ctx.handle
+        p_rp, p_col, p_dz = rp.ctypes.data_as(lp), col.ctypes.data_as(ip), dz.ctypes.data_as(dp)
+        assert lib.c5_ray_matrix_rows(h, None, C.byref(n)) == capi.C5_ERR_INVALID
+        assert lib.c5_ray_matrix_rows(h, p_rp, None) == capi.C5_ERR_INVALID
+        assert lib.c5_ray_matrix_rows(None, p_rp, C.byref(n)) == capi.C5_ERR_INVALID
+        assert lib.c5_ray_matrix_rows_device(h, None, C.byref(n)) == capi.C5_ERR_INVALID
+        assert lib.c5_ray_matrix_fill(h, None, nnz, p_col, p_dz, None) == capi.C5_ERR_INVALID
+        assert lib.c5_ray_matrix_fill(h, p_rp, nnz, None, p_dz, None) == capi.C5_ERR_INVALID
+        assert lib.c5_ray_matrix_fill(h, p_rp, nnz, p_col, None, None) == capi.C5_ERR_INVALID
+        assert lib.c5_ray_matrix_fill(h, p_rp, -1, p_col, p_dz, None) == capi.C5_ERR_INVALID
+        assert lib.c5_ray_matrix_fill_device(h, None, nnz, None, None, None) == capi.C5_ERR_INVALID
+        # (non-null stand-ins: the checks come before anything is read or written)
+        vp, some = C.c_void_p, rp.ctypes.data
+        assert lib.c5_ray_matrix_rows_device(h, vp(some), None) == capi.C5_ERR_INVALID
+        assert lib.c5_ray_matrix_fill_device(h, None, nnz, vp(some), vp(some), None) == capi.C5_ERR_INVALID
+        assert lib.c5_ray_matrix_fill_device(h, vp(some), nnz, None, vp(some), None) == capi.C5_ERR_INVALID
+        assert lib.c5_ray_matrix_fill_device(h, vp(some), nnz, vp(some), None, None) == capi.C5_ERR_INVALID
+        assert lib.c5_ray_matrix_fill_device(h, vp(some), -1, vp(some), vp(some), None) == capi.C5_ERR_INVALID
+        buf = ctx.host_image()
+        ctx.render_host_async(buf)
+        with pytest.raises(capi.C5Error) as e:
+            ctx.ray_matrix_rows()
+        assert e.value.code == capi.C5_ERR_STATE
+        with pytest.raises(capi.C5Error) as e:
+            ctx.ray_matrix_fill(rp)
+        assert e.value.code == capi.C5_ERR_STATE
+        assert ctx.render_host_wait() == capi.C5_OK
+        ctx.free_host_image(buf)
+        m = ctx.ray_matrix()
+    assert m[0][-1] == nnz
+
+
+def test_a_scene_of_solids_only_has_empty_rows():
+    sx, sc = mg.kuhn_box(2, lo=(0.9, -0.15, 0.3), size=0.3)
+    with capi.Context(0) as ctx:
+        ctx.set_solid(0, sx[sc].reshape(-1, 12), 0.5)
+        ctx.set_image(61, 43, B)
+        ctx.set_view(VIEW)
+        ctx.set_solid_view(0, VIEW)
+        assert (ctx.render()[..., 0] == 0.5).any()
+        row_ptr, col, dz, z = ctx.ray_matrix(with_depth=True)
+        # a row_ptr of a frame that had cells is another frame's
+        stale = np.zeros(61 * 43 + 1, np.int64)
+        stale[-1] = 3
+        with pytest.raises(capi.C5Error) as e:
+            ctx.ray_matrix_fill(stale)
+        assert e.value.code == capi.C5_ERR_STATE
+    assert row_ptr.shape == (61 * 43 + 1,) and not row_ptr.any() and len(col) == len(dz) == len(z) == 0
+
+
+def test_the_host_forms_retry_by_themselves_when_the_entry_pool_grows():
+    import torch
+    kind = "ball12_150x112:1"
+    xyz, cells, alpha, q, rots, rx, ry, bounds, nnz = _scene(kind)
+    with _ctx(xyz, cells, alpha, q, rots, rx, ry, bounds) as ctx:
+        # the pool of 16 does overflow on this frame: the raw _device call says C5_RETRY (and the pool has grown by then)
+        ctx.set_option("entry_pool", 16)
+        d_rp, n = torch.zeros(rx * ry + 1, dtype=torch.int64, device="cuda"), C.c_int64()
+        torch.cuda.synchronize()
+        assert ctx.lib.c5_ray_matrix_rows_device(ctx.handle, C.c_void_p(d_rp.data_ptr()), C.byref(n)) == capi.C5_RETRY
+        ctx.set_option("entry_pool", 16)
+        row_ptr = ctx.ray_matrix_rows()
+        assert row_ptr[-1] == nnz
+        ctx.set_option("entry_pool", 16)
+        m = (row_ptr,) + ctx.ray_matrix_fill(row_ptr, with_depth=True)
+    assert all(np.array_equal(a.view(np.uint8), b.view(np.uint8)) for a, b in zip(m, _matrix(kind)))
+
+
+def test_torch_sparse_csr():
+    import torch
+    from course5_amd import autograd
+    kind = "g1_cube8_60x45:0"
+    xyz, cells, alpha, q, rots, rx, ry, bounds, nnz = _scene(kind)
+    row_ptr, col, dz, z = _matrix(kind)
+    with _ctx(xyz, cells, alpha, q, rots, rx, ry, bounds) as ctx:
+        A, z_dev = autograd.ray_matrix(ctx, with_depth=True)
+        assert A.layout == torch.sparse_csr and A.is_cuda and A.dtype == torch.float64 and tuple(A.shape) == (rx * ry, len(cells))
+        assert A.crow_indices().dtype == torch.int32 and A.col_indices().dtype == torch.int32 and A._nnz() == nnz
+        dense = np.zeros((rx * ry, len(cells)))
+        dense[_rows_of(row_ptr), col] = dz
+        assert np.array_equal(A.to_dense().cpu().numpy().view(np.uint64), dense.view(np.uint64))
+        assert np.array_equal(z_dev.cpu().numpy().view(np.uint64), z.view(np.uint64))
+        assert autograd.ray_matrix(ctx).layout == torch.sparse_csr
+        mine = (A @ torch.tensor(alpha, device="cuda")).cpu().numpy()
+        tau = ctx.render()[..., 0].astype(np.float64).reshape(-1)
+    scale = np.bincount(_rows_of(row_ptr), weights=dz * np.abs(alpha[col]), minlength=rx * ry)
+    assert tau.max() > 0 and (np.abs(mine - tau) <= 2.0 ** -23 * np.abs(tau) + 1e-9 * scale).all()
