@@ -105,17 +105,32 @@ def rotate(xyz, rots):
 _FACES = ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3))  # plane.cpp:30-37
 
 
-def segment_lists(xyz, cells, rots, res_x, res_y, bounds, with_slope: bool = False):
+def pixel_coordinates(bounds, res_x, res_y, running: bool = True):
+    """(X [res_x], Y [res_y], step_x, step_y): the pixel centres as the reference and the library form them, RUNNING SUMS
+    x_{i+1} = x_i + step (plane.cpp:301-314; csrc/context.hip: c5_set_image), not x_min + i step: after a few hundred
+    additions the two differ by tens of ulps, which a face of slope F turns into F times that in its depth.  The geometry
+    sweep (tests/derivative_fuzz.py) found the restatements on x_min + i step: images of 300 - 500 pixels a side had up to
+    1.5 x the chord bar between the library's chords and segment_lists', every one of them the pixel's coordinate.
+    running=False gives those older coordinates (derivative_fuzz.derivative_scene draws its alpha from them still, so
+    that the scenes of a seed stay what they were)."""
+    b = np.asarray(bounds, dtype=np.float64)
+    sx, sy = (b[0] - b[1]) / (res_x - 1.0), (b[2] - b[3]) / (res_y - 1.0)
+    if not running:
+        return b[1] + sx * np.arange(res_x), b[3] + sy * np.arange(res_y), sx, sy
+    X = np.add.accumulate(np.concatenate([[b[1]], np.full(res_x - 1, sx)]))  # (accumulate adds in order)
+    Y = np.add.accumulate(np.concatenate([[b[3]], np.full(res_y - 1, sy)]))
+    return X, Y, sx, sy
+
+
+def segment_lists(xyz, cells, rots, res_x, res_y, bounds, with_slope: bool = False, running: bool = True):
     """Every pixel's segments, as the reference bins and pairs them (plane.cpp:184-192, line.cpp:99-138): a cell whose
     projection holds the pixel centre (two covering faces; four: two pairs in face order) gives {cell, z_hi, dz}.
     Returns (pixel, cell, z_hi, dz) arrays sorted by pixel and then by ASCENDING z_hi - the order the recurrence runs
     in (line.cpp:206); pixel = row * res_x + col over the full image.  with_slope: a fifth array, the larger |dz/dx| + |dz/dy|
-    of the segment's two faces."""
+    of the segment's two faces.  running: pixel_coordinates'."""
     P = rotate(xyz, rots)[np.asarray(cells).reshape(-1, 4)]  # [C, 4, 3]
     b = np.asarray(bounds, dtype=np.float64)
-    sx, sy = (b[0] - b[1]) / (res_x - 1.0), (b[2] - b[3]) / (res_y - 1.0)
-    X = b[1] + sx * np.arange(res_x)
-    Y = b[3] + sy * np.arange(res_y)
+    X, Y, sx, sy = pixel_coordinates(b, res_x, res_y, running)
     lo, hi = P[:, :, :2].min(1), P[:, :, :2].max(1)
     c0 = np.clip(np.floor((lo[:, 0] - b[1]) / sx) - 1, 0, res_x - 1).astype(np.int64)
     c1 = np.clip(np.ceil((hi[:, 0] - b[1]) / sx) + 1, 0, res_x - 1).astype(np.int64)

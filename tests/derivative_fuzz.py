@@ -2,6 +2,7 @@
 against the numpy restatements, element by element.
 
     python tests/derivative_fuzz.py [n_scenes] [seed0]
+    python tests/derivative_fuzz.py geometry [n_scenes] [seed0]      (the geometry sweep, below)
     python tests/derivative_fuzz.py chords SEED PIXEL      (the GPU's chords along one ray against the reference's)
 
 reports every mismatch and the worst error / tolerance per call kind; exit status 1 on any mismatch or when more than
@@ -51,6 +52,44 @@ The bar, per element (a pixel's channel, a cell's gradient), with scale and sens
   2^-970 DBL_MIN / DBL_EPSILON: below it (underflow scenes) a double keeps no relative accuracy.  For an fp32 output the
          same with fp32's numbers, FLT_MIN / 2^-23 = 2^-103: seed 3033's I_dot = 3.6e-86 is 0 in the image.
 None of these is fitted to what the GPU returns.
+
+THE GEOMETRY SWEEP (geometry_scene, check_geometry; tests/test_gpu_geometry_fuzz.py runs 40 seeds of it): the renders that
+differentiate in the grid's points - render_motion_tangent, render_vertex_tangent, render_vertex_adjoint with
+update_points - and ray_matrix, on the same scenes.  geometry_scene(seed) is derivative_scene(seed), unchanged (qualify
+too: the used and skipped seeds are the scalar sweep's), plus, from a stream of its own (default_rng([seed, 0x6E0])):
+  * affine fields: rotation_motion of every angle of the view, two normal ones, Z_SCALE, Z_TRANSLATION, a pure x / y
+    translation, and the first normal one times 2^20 and times 2^-20;
+  * per-point fields: K in 1..11 normal ones, one that is non-zero at a single point, one that is M^T (A p_v + b) of the
+    first affine field; all of them constant over a weld group (capi.weld_points: a group moves as one), and where points
+    are welded - soups, hanging-node interfaces whose ids are not shared - a second copy with 1e6 x normal garbage in the
+    rows of the non-representatives;
+  * upstream images of the vertex adjoint: g[0], and in a third of the scenes each an image with only the tau channel and
+    one with only the I channel (the patch of exact zeros exercises the walk's `wanted`);
+  * options: "vertex_merge" 0 / 1, "cell_order" 0 / 1 (before the upload), in a quarter of the scenes one of
+    ("depth_split", 2) and ("integration", 1) - the header promises whole rays in the reference's order whatever these say;
+    such a scene is held to the same bars, and whether its tangents are bit-equal to a default context's is printed;
+  * in a quarter of the scenes the context is uploaded with the points displaced by a normal field of 1e-3 x the shortest
+    cell edge (constant over a weld group), one call of each kind and three plain renders (the third reuses the per-view
+    data) run on that grid, then update_points(xyz): the next plain render must be a fresh upload's bit for bit, and
+    everything after it is held to the reference of xyz.
+Layout, soup, solid, device forms and the late limit are derivative_scene's.  Per used scene, every element compared:
+  motion_tangent, vertex_tangent   2^-23 |ref| + 1e-9 scale + dz_err sens + 2^-103 against motion_reference.motion_of (every
+      affine field; its sens with the kappa terms) and vertex_tangent_reference.tangent_of (the first per-point field, the
+      single-point one and one drawn; the others are held to the single calls by the batches); every slice of a batch at
+      both widths bit-equal to the single call; row parts put back in their rows;
+  vertex_adjoint   1e-9 scale_raw + dz_err sens_raw + 2^-970 per component against vertex_adjoint_reference.gradients_of
+      (sens_raw: its docstring; calibrated in tests/test_vertex_adjoint_cpu.py), row parts and ranks summed, the
+      reference's per-copy gradients, scales and sensitivities summed onto the representatives and the other rows
+      exactly 0; a second call on tests/test_gpu_vertex_adjoint.py's run-to-run bar (rtol 1e-12, atol 1e-15 x max, per part);
+  ray_matrix   structure exact against s.segments (without the solid-marked pixels), dz and z_exit within dz_err x
+      max(1, slope) (tests/ray_matrix_checks.py); a part's matrix is bit for bit rows of the whole frame's;
+  identities on the GPU's own results: <g, J v> = <J^T g, v> between the vertex tangent and the vertex adjoint for two
+      fields at 2^-22 sum |g| |out|; Z_TRANSLATION exactly 0; the 2^+-20 multiples are the field's image with every
+      finite, normal fp32 value scaled exactly (bits after ldexp; only values subnormal on either side are left out); the
+      single-point field is exactly 0 at every pixel whose ray crosses no cell holding the point; garbage rows change no
+      bit; stats() before and after the calls; a plain render after the calls bit-equal to the one before them.
+What the first run of it found is in profiles/geometry_fuzz.md: the restatements' pixel coordinates
+(adjoint_reference.pixel_coordinates).
 """
 import os
 import sys
@@ -64,6 +103,7 @@ import numpy as np
 
 from course5_amd import meshgen as mg, sharding
 from tests import adjoint_reference as ar, gn_reference as gr, tangent_reference as tr
+from tests import motion_reference as mr, ray_matrix_checks as rmc, vertex_adjoint_reference as vr, vertex_tangent_reference as vt
 from tests.fuzz_scenes import scene
 
 B = mg.REFERENCE_BOUNDS
@@ -76,6 +116,8 @@ ABS_FLOOR_32 = 2.0 ** -103
 ALPHA_CLASSES = ("zero", "below_eps", "eps_to_1e-6", "at_limit", "ulp_above_limit", "ulp_below_limit", "above_limit", "rest")
 _CLASS_P = (0.05, 0.04, 0.08, 0.05, 0.03, 0.03, 0.10, 0.62)
 KINDS = ("tangent", "tangent_batch", "adjoint", "adjoint_batch", "gn_product", "gn_diagonal")
+GEOMETRY_KINDS = ("motion_tangent", "vertex_tangent", "vertex_adjoint", "vertex_adjoint_rerun", "ray_matrix", "duality")
+WALK_OPTIONS = (("depth_split", 2), ("integration", 1))
 
 
 def alpha_class(alpha, limit):
@@ -102,7 +144,10 @@ def derivative_scene(seed):
     s.xyz, s.cells = xyz, cells
     n = len(cells)
     rx, ry = res
-    s.segments = pix, cell, _zh, dz, _slope = ar.segment_lists(xyz, cells, rots, rx, ry, B, with_slope=True)
+    # (alpha is drawn from the chords at the pixel coordinates x_min + i step, as it was before adjoint_reference.
+    # pixel_coordinates went over to the reference's running sums: the scenes of a seed do not change)
+    pix, cell, _zh, dz, _slope = ar.segment_lists(xyz, cells, rots, rx, ry, B, with_slope=True, running=False)
+    s.segments = ar.segment_lists(xyz, cells, rots, rx, ry, B, with_slope=True)
     s.mode = ("threshold", "threshold", "underflow", "plain", "plain", "plain", "plain", "plain")[int(rng.integers(8))]
     # -- alpha
     u = rng.uniform(0.0, 1.0, n)
@@ -210,8 +255,8 @@ def ratio(got, ref, scale, sens, dz_e, r_out=0.0, r_scale=R64):
 class Worst:
     """The worst error / tolerance per call kind, with the seed and element that showed it, and the elements compared."""
 
-    def __init__(self):
-        self.by_kind = {k: (0.0, None) for k in KINDS}
+    def __init__(self, kinds=KINDS):
+        self.by_kind = {k: (0.0, None) for k in kinds}
         self.elements = 0
 
     def add(self, kind, r, seed, what=""):
@@ -436,6 +481,329 @@ def check_scene(s, worst):
     return bad
 
 
+# ---- the geometry sweep: motion tangent, vertex tangent, vertex adjoint, ray matrix -----------------------------------
+
+def geometry_scene(seed):
+    """derivative_scene(seed), unchanged, with what the geometry calls need drawn from a stream of its own (module
+    docstring: the geometry sweep)."""
+    from course5_amd import capi
+    s = derivative_scene(seed)
+    rng = np.random.default_rng([seed, 0x6E0])
+    n_pts = len(s.xyz)
+    cells = np.asarray(s.cells).reshape(-1, 4)
+    s.rep, s.merged = capi.weld_points(s.xyz)
+    s.rep = s.rep.astype(np.int64)
+    others = s.rep != np.arange(n_pts)
+    # -- affine fields
+    rot = [capi.rotation_motion(s.rots, i) for i in range(len(s.rots))]
+    a1, a2 = rng.normal(size=(2, 12))
+    shift = np.zeros(12)
+    shift[9:11] = rng.normal(size=2)
+    s.motion = np.array(rot + [a1, a2, mr.Z_SCALE, mr.Z_TRANSLATION, shift, a1 * 2.0 ** 20, a1 * 2.0 ** -20])
+    base = len(rot)
+    s.motion_at = {"base": base, "z_translation": base + 3, "up": base + 5, "down": base + 6}
+    # -- per-point fields: normal ones, one that moves a single point, one that is an affine field at the points
+    kv = int(rng.integers(1, 12))
+    normal = rng.normal(size=(kv, n_pts, 3))
+    single = np.zeros((n_pts, 3))
+    s.single_point = int(s.rep[cells.reshape(-1)[int(rng.integers(cells.size))]])
+    single[s.single_point] = rng.normal(size=3)
+    pv = ar.rotate(s.xyz, s.rots)
+    affine = (pv @ a1[:9].reshape(3, 3).T + a1[9:]) @ vr.view_matrix(s.rots)  # d_xyz[v] = M^T (A p_v + b)
+    s.v_fields = np.concatenate([normal, single[None], affine[None]])[:, s.rep]  # (a weld group moves as one)
+    s.v_garbage = None
+    if others.any():  # the rows of welded non-representatives are never read
+        s.v_garbage = s.v_fields.copy()
+        s.v_garbage[:, others] = 1e6 * rng.normal(size=(len(s.v_fields), int(others.sum()), 3))
+    drawn = [j for j in range(len(s.v_fields)) if j not in (0, kv)]
+    s.v_single = kv
+    s.v_compare = [0, kv, int(rng.choice(drawn))]  # held to the restatement; the rest by the batches' bit equality
+    # -- upstream images of the vertex adjoint
+    s.vg = [s.g[0]]
+    which = int(rng.integers(3))
+    if which < 2:  # only the tau channel, only the I channel
+        img = s.g[1].copy()
+        img[..., 1 - which] = 0.0
+        s.vg.append(img)
+    # -- options, and a grid that is moved into place
+    s.vertex_merge, s.cell_order = int(rng.integers(2)), int(rng.integers(2))
+    s.walk_option = WALK_OPTIONS[int(rng.integers(2))] if rng.integers(4) == 0 else None
+    s.moved = bool(rng.integers(4) == 0)
+    e = s.xyz[cells[:, [0, 0, 0, 1, 1, 2]]] - s.xyz[cells[:, [1, 2, 3, 2, 3, 3]]]
+    s.displaced = s.xyz + (1e-3 * np.sqrt((e ** 2).sum(-1)).min() * rng.normal(size=(n_pts, 3)))[s.rep]
+    return s
+
+
+class _GeoCalls:
+    """The geometry calls of one context in their host forms; fields [K, 12], d [K, n_pts, 3], g [rows, res_x, 2]."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def motion(self, fields):
+        return self.ctx.render_motion_tangent(fields)
+
+    def vertex_tangent(self, d):
+        return self.ctx.render_vertex_tangent(d)
+
+    def vertex_adjoint(self, g):
+        return self.ctx.render_vertex_adjoint(g)
+
+
+class _GeoDeviceCalls(_DeviceCalls):
+    def motion(self, fields):
+        import torch
+        out = self._empty((len(fields),) + self._image_shape(), torch.float32)
+        self._run(lambda: self.ctx.render_motion_tangent_device(fields, out))
+        return out.cpu().numpy()
+
+    def vertex_tangent(self, d):
+        import torch
+        out = self._empty((len(d),) + self._image_shape(), torch.float32)
+        dt = self._t(d, torch.float64)
+        self._run(lambda: self.ctx.render_vertex_tangent_device(dt, out))
+        return out.cpu().numpy()
+
+    def vertex_adjoint(self, g):
+        import torch
+        out, gt = self._empty((self.ctx.n_pts, 3), torch.float64), self._t(g, torch.float32)
+        self._run(lambda: self.ctx.render_vertex_adjoint_device(gt, out))
+        return out.cpu().numpy()
+
+
+def _open(s, xyz, walk_option=None):
+    """A context of the scene's own, as check_scene opens it, with the geometry sweep's options."""
+    from course5_amd import capi
+    ctx = capi.Context(0)
+    if s.soup:
+        ctx.set_option("algorithm", 1)
+    ctx.set_option("cell_order", s.cell_order)  # (read by the upload)
+    ctx.set_option("vertex_merge", s.vertex_merge)
+    if walk_option:
+        ctx.set_option(*walk_option)
+    ctx.upload_grid(xyz, s.cells, s.alpha, s.q)
+    ctx.set_image(s.res[0], s.res[1], B)
+    ctx.set_view(s.rots)
+    return ctx
+
+
+def _solid_of(s):
+    v = ar.rotate(s.xyz, s.rots)
+    frac, size = s.solid_at
+    ext = v.max(0) - v.min(0)
+    sx, sc = mg.kuhn_box(2, lo=tuple(v.min(0) + frac * ext - 0.5 * size * ext.max()), size=size * float(ext.max()))
+    return sx[sc].reshape(-1, 12)
+
+
+def _scaled_bits_differ(base, scaled, power):
+    """How many fp32 values of `scaled` are not ldexp(base, power) bit for bit, leaving out only values that are subnormal
+    (or beyond the finite range) on either side."""
+    want = np.ldexp(base.astype(np.float64), power)
+    tiny, huge = float(np.finfo(np.float32).tiny), float(np.finfo(np.float32).max)
+    use = np.ones(base.shape, bool)
+    for v in (np.abs(base.astype(np.float64)), np.abs(want), np.abs(scaled.astype(np.float64))):
+        use &= ((v == 0) | (v >= tiny)) & (v <= huge)
+    return int((_bits(want.astype(np.float32))[use] != _bits(scaled)[use]).sum()), int(use.sum())
+
+
+def covered_only(m, geo):
+    """ray_matrices' and segment_faces' dicts cut down to the pixels that have a segment (most of a frame has none and
+    the restatements' time goes with the pixels): (covered [n_px] bool, m, geo), the results then [n_covered]."""
+    cov = m["valid"].any(1)
+
+    def cut(d):
+        return {k: v[cov] if isinstance(v, np.ndarray) and v.shape[:1] == (m["n_px"],) else v for k, v in d.items()}
+
+    mc = cut(m)
+    mc["n_px"] = int(cov.sum())
+    mc["shape"] = (mc["n_px"],)
+    return cov, mc, cut(geo)
+
+
+def check_geometry(s, worst, log=print):
+    """Every geometry call on one used scene (geometry_scene, qualify first).  Returns the mismatches, strings."""
+    from contextlib import ExitStack
+    bad = []
+    rx, ry = s.res
+    n_pts = len(s.xyz)
+    cells = np.asarray(s.cells).reshape(-1, 4)
+    with ExitStack() as stack:
+        ctx = stack.enter_context(_open(s, s.displaced if s.moved else s.xyz, s.walk_option))
+        # a fresh upload of the points the moved grid ends at; a context without the walk option
+        fresh = stack.enter_context(_open(s, s.xyz, s.walk_option)) if s.moved else None
+        plain = stack.enter_context(_open(s, s.xyz)) if s.walk_option else None
+        others_ctx = [c for c in (fresh, plain) if c is not None]
+        if not s.late_limit:
+            ctx.set_alpha_limit(s.limit)
+        ctx.render()
+        if not s.moved:
+            st = ctx.stats()
+            if (st["segments"], st["covered_pixels"]) != (s.n_segments, s.n_covered):
+                bad.append(f"stats: {st['segments']} segments on {st['covered_pixels']} pixels, the reference has "
+                           f"{s.n_segments} on {s.n_covered}")
+        if s.late_limit:
+            ctx.set_alpha_limit(s.limit)
+        for c in others_ctx:
+            c.set_alpha_limit(s.limit)
+        calls = _GeoDeviceCalls(ctx) if s.device else _GeoCalls(ctx)
+        if s.moved:  # one call of each kind on the displaced grid: their per-point and per-cell data are built for it
+            calls.motion(s.motion[:1]), calls.vertex_tangent(s.v_fields[:1]), calls.vertex_adjoint(s.vg[0])
+            for _ in range(3):  # (three frames of one view: the third reuses the per-view data of the displaced grid)
+                ctx.render()
+            ctx.update_points(s.xyz)
+            if not np.array_equal(_bits(ctx.render()), _bits(fresh.render())):
+                bad.append("the first plain render after update_points differs from a fresh upload's")
+            st = ctx.stats()
+            if (st["segments"], st["covered_pixels"]) != (s.n_segments, s.n_covered):
+                bad.append(f"stats after update_points: {st['segments']} segments on {st['covered_pixels']} pixels, the "
+                           f"reference has {s.n_segments} on {s.n_covered}")
+        skip = None
+        if s.solid:
+            for c in [ctx] + others_ctx:
+                c.set_solid(0, _solid_of(s))
+            skip = np.isnan(ctx.render()[..., 0])
+        whole = ctx.ray_matrix(with_depth=True)
+        if s.layout == "range":
+            b, c = s.row_range
+            rows_ref = np.arange(b, b + c)
+            parts = [(lambda x: x.set_row_range(b, c), np.arange(c))]
+        elif s.layout == "cyclic":
+            rows_ref = np.arange(ry)
+            parts = [((lambda x, r=r: x.set_row_tiles(s.tile_rows, r, s.world)), sharding.local_rows(ry, s.tile_rows, r, s.world))
+                     for r in range(s.world)]
+        else:
+            rows_ref = np.arange(ry)
+            parts = [(lambda x: None, np.arange(ry))]
+        nr = len(rows_ref)
+        km, kv = len(s.motion), len(s.v_fields)
+        mot = np.full((km, nr, rx, 2), np.nan, np.float32)
+        vtan = np.full((kv, nr, rx, 2), np.nan, np.float32)
+        grads = [np.zeros((n_pts, 3)) for _ in s.vg]
+        rerun = [np.zeros((n_pts, 3)) for _ in s.vg]
+        n_parts = 0
+        for place, where in parts:
+            if len(where) == 0:
+                continue
+            n_parts += 1
+            place(ctx)
+            before = ctx.render()
+            st = ctx.stats()
+            if fresh is not None:
+                place(fresh)
+                if not np.array_equal(_bits(before), _bits(fresh.render())):
+                    bad.append("a plain render after update_points differs from a fresh upload's")
+            # -- motion tangent and vertex tangent: singles, and the batches at both widths
+            m1 = np.concatenate([calls.motion(s.motion[j:j + 1]) for j in range(km)])
+            v1 = np.concatenate([calls.vertex_tangent(s.v_fields[j:j + 1]) for j in range(kv)])
+            for width in (4, 8):
+                ctx.set_option("batch_width", width)
+                for name, single, batch in (("motion", m1, calls.motion(s.motion)), ("vertex", v1, calls.vertex_tangent(s.v_fields))):
+                    if not np.array_equal(_bits(batch), _bits(single)):
+                        bad.append(f"{name} tangent batch (width {width}) differs from the single calls in "
+                                   f"{int((_bits(batch) != _bits(single)).sum())} values")
+            if s.v_garbage is not None and not np.array_equal(_bits(calls.vertex_tangent(s.v_garbage)), _bits(v1)):
+                bad.append("garbage in the rows of welded non-representatives changes the vertex tangent")
+            mot[:, where], vtan[:, where] = m1, v1
+            # -- vertex adjoint, twice
+            for i, g in enumerate(s.vg):
+                g_part = np.ascontiguousarray(g[rows_ref][where])
+                grads[i] += calls.vertex_adjoint(g_part)
+                rerun[i] += calls.vertex_adjoint(g_part)
+            # -- ray matrix: a part is bit for bit rows of the whole frame's
+            part = ctx.ray_matrix(with_depth=True)
+            px = (rows_ref[where][:, None] * rx + np.arange(rx)).reshape(-1)
+            if not rmc.bit_equal_rows(part, whole, px):
+                bad.append("the ray matrix of a part is not the whole frame's rows bit for bit")
+            if plain is not None and n_parts == 1:
+                place(plain)
+                pm, pv = plain.render_motion_tangent(s.motion), plain.render_vertex_tangent(s.v_fields)
+                log(f"seed {s.seed} {s.walk_option}: against a context with default walk options the motion tangent differs "
+                    f"in {int((_bits(pm) != _bits(m1)).sum())} values, the vertex tangent in {int((_bits(pv) != _bits(v1)).sum())}")
+            after = ctx.stats()
+            if (after["segments"], after["covered_pixels"]) != (st["segments"], st["covered_pixels"]):
+                bad.append("stats() changed over the geometry calls")
+            if not np.array_equal(_bits(ctx.render()), _bits(before)):
+                bad.append("a plain render after the geometry calls differs from the one before them")
+    # -- identities on the GPU's own results
+    at = s.motion_at
+    if mot[at["z_translation"]].any():
+        bad.append(f"a z-translation gives {int((mot[at['z_translation']] != 0).sum())} non-zero values")
+    for key, power in (("up", 20), ("down", -20)):
+        n_bad, n_used = _scaled_bits_differ(mot[at["base"]], mot[at[key]], power)
+        if n_bad:
+            bad.append(f"the field times 2^{power}: {n_bad} of {n_used} values are not the field's scaled exactly")
+    pix, cell = s.segments[:2]
+    hit = np.zeros(rx * ry, bool)
+    hit[pix[(s.rep[cells] == s.single_point).any(1)[cell]]] = True
+    off = ~hit.reshape(ry, rx)[rows_ref]
+    if vtan[s.v_single][off].any():
+        bad.append(f"the single-point field moves {int(vtan[s.v_single][off].any(-1).sum())} pixels whose rays miss the point's cells")
+    welded = s.rep != np.arange(n_pts)
+    for i, g in enumerate(grads):
+        if g[welded].any():
+            bad.append(f"vertex adjoint {i}: welded non-representatives hold non-zero gradients")
+    g64 = s.vg[0][rows_ref].astype(np.float64)
+    for j in (s.v_compare[0], s.v_compare[-1]):
+        out = vtan[j].astype(np.float64)
+        lhs, rhs = float((g64 * out).sum()), float((grads[0] * s.v_fields[j]).sum())
+        bar = 2.0 ** -22 * float((np.abs(g64) * np.abs(out)).sum()) + ABS_FLOOR_32
+        r = worst.add("duality", np.array([abs(lhs - rhs) / bar]), s.seed, f"field {j}")
+        if not r <= 1.0:
+            bad.append(f"duality, field {j}: <g, J v> = {lhs:.9g}, <J^T g, v> = {rhs:.9g}, difference / bar {r:.3g}")
+    # -- ray matrix against the reference's lists
+    e = dz_err(s)
+    keep = np.ones(len(pix), bool) if skip is None else ~skip.reshape(-1)[pix]
+    try:
+        r = rmc.check_against_reference(whole, tuple(a[keep] for a in s.segments), e, rx * ry, len(cells), int(keep.sum()),
+                                        f"seed {s.seed} ray matrix", log=lambda t: None)
+        worst.add("ray_matrix", np.array(r), s.seed, "(dz, z_exit)")
+    except AssertionError as err:
+        worst.add("ray_matrix", np.array([np.inf]), s.seed)
+        bad.append(f"ray matrix: {err or 'structure differs from the reference'}")
+    # -- against the restatements, element by element
+    m = ar.ray_matrices(s.xyz, s.cells, s.alpha, s.q, s.rots, rx, ry, B, s.limit, rows_ref)
+    geo = vr.segment_faces(s.xyz, s.cells, s.rots, rx, ry, B, rows_ref)
+    skip_ref = None if skip is None else skip[rows_ref]
+    cov, mc, gc = covered_only(m, geo)
+    skip_cov = None if skip_ref is None else skip_ref.reshape(-1)[cov]
+    found = []
+
+    def images(got, ref, what, kind):
+        def full(v):  # (a pixel without a segment: 0, bounds included)
+            out = np.zeros(len(cov))
+            out[cov] = v
+            return out.reshape(nr, rx)
+        td, Id, x = ref
+        found.append((kind, what, np.stack([ratio(got[..., 0], full(td), full(x["scale_tau"]), full(x["sens_tau"]), e, R_OUT),
+                                            ratio(got[..., 1], full(Id), full(x["scale_I"]), full(x["sens_I"]), e, R_OUT)], axis=-1)))
+
+    for j in range(km):
+        images(mot[j], mr.motion_of(mc, gc, s.motion[j], skip_cov, with_scale=True), f"field {j}", "motion_tangent")
+    for j in s.v_compare:
+        images(vtan[j], vt.tangent_of(mc, gc, s.cells, s.rots, s.v_fields[j], skip_cov, with_scale=True), f"field {j}", "vertex_tangent")
+    for i, g in enumerate(s.vg):
+        ref = vr.gradients_of(m, geo, s.cells, n_pts, s.rots, g[rows_ref], skip_ref)
+        on_rep = {k: np.zeros((n_pts, 3)) for k in ("raw", "scale_raw", "sens_raw")}
+        for k, v in on_rep.items():
+            np.add.at(v, s.rep, ref[k])  # the group's sum on its representative
+        found.append(("vertex_adjoint", f"image {i}", ratio(grads[i], on_rep["raw"], on_rep["scale_raw"], on_rep["sens_raw"], e)))
+        # two runs: tests/test_gpu_vertex_adjoint.py::_assert_same_run's bar, per part
+        tol = n_parts * (1e-12 * np.abs(grads[i]) + 1e-15 * np.abs(grads[i]).max()) + ABS_FLOOR
+        found.append(("vertex_adjoint_rerun", f"image {i}", np.abs(rerun[i] - grads[i]) / tol))
+    for kind, what, r in found:
+        top = worst.add(kind, r, s.seed, what)
+        if not top <= 1.0:
+            i = np.unravel_index(int(np.argmax(r)), r.shape)
+            bad.append(f"{kind} {what}: {int((~(r <= 1.0)).sum())} elements beyond the bar, worst error / tol {top:.3g} at {tuple(int(v) for v in i)}")
+    return bad
+
+
+def describe_geometry(s):
+    return (describe(s) + f"; {len(s.motion)} affine and {len(s.v_fields)} per-point fields, {len(s.vg)} upstream images, "
+            f"vertex_merge {s.vertex_merge}, cell_order {s.cell_order}" + (f", {s.walk_option[0]} {s.walk_option[1]}" if s.walk_option else "")
+            + (", moved" if s.moved else "") + (f", {s.merged} welded points" if s.merged else ""))
+
+
 def gpu_chords(s, pixel):
     """The GPU's own chords along the ray of one pixel (row * res_x + col) of the whole frame: grad_alpha for an upstream
     image that is (g_tau, g_I) = (1, 0) there is dz per cell.  Returns (cells, the reference's dz, the GPU's, F) in
@@ -464,21 +832,23 @@ def describe(s):
             + (", no d_q" if s.d_q is None else "") + (", no weight" if s.w is None else ""))
 
 
-def run(seeds, oracle, worst, log=print):
-    """check_scene over seeds.  Returns (used, skipped, mismatches [(seed, text)])."""
+def run(seeds, oracle, worst, log=print, draw=None, check=None):
+    """check_scene over seeds (draw / check: geometry_scene and check_geometry for the geometry sweep).  Returns (used,
+    skipped, mismatches [(seed, text)])."""
+    draw, check = draw or derivative_scene, check or check_scene
     used = skipped = 0
     mismatches = []
     for seed in seeds:
-        s = derivative_scene(seed)
+        s = draw(seed)
         why = qualify(s, oracle)
         if why is not None:
             skipped += 1
             log(f"seed {seed}: {why} - skipped")
             continue
         used += 1
-        for text in check_scene(s, worst):
+        for text in check(s, worst):
             mismatches.append((seed, text))
-            log(f"seed {seed} ({describe(s)}): {text}")
+            log(f"seed {seed} ({describe_geometry(s) if hasattr(s, 'motion') else describe(s)}): {text}")
     return used, skipped, mismatches
 
 
@@ -490,15 +860,20 @@ def main():
         for c, d, got, f in zip(*gpu_chords(s, int(sys.argv[3]))):
             print(f"cell {c}: dz {d:.6g}, GPU - reference {got - d:+.3g} = {(got - d) / dz_err(s):+.2f} dz_err, F {f:.1f}")
         return 0
+    geometry = len(sys.argv) > 1 and sys.argv[1] == "geometry"
+    if geometry:
+        del sys.argv[1]
     n_scenes = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-    worst = Worst()
+    worst = Worst(GEOMETRY_KINDS if geometry else KINDS)
+    draw, check = (geometry_scene, check_geometry) if geometry else (None, None)
     t0 = time.time()
     used = skipped = 0
     mismatches = []
     oracle = Oracle("port")
     for k in range(0, n_scenes, 25):
-        u, sk, mm = run(range(seed0 + k, seed0 + min(k + 25, n_scenes)), oracle, worst, log=lambda t: print(t, flush=True))
+        u, sk, mm = run(range(seed0 + k, seed0 + min(k + 25, n_scenes)), oracle, worst, log=lambda t: print(t, flush=True),
+                        draw=draw, check=check)
         used, skipped, mismatches = used + u, skipped + sk, mismatches + mm
         print(f"... {min(k + 25, n_scenes)} of {n_scenes} seeds, {len(mismatches)} mismatches so far", flush=True)
     print(f"{n_scenes} seeds from {seed0}: {used} used, {skipped} skipped, {len(mismatches)} mismatches, "

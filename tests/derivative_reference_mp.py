@@ -15,6 +15,18 @@ Every result comes with its SCALE, the same sum with every contribution replaced
 its CHORD SENSITIVITY sum_k F_k |contribution_k| / dz_k (F: tests/adjoint_reference.py): what a rounding error and an
 error of the chords can do to it.
 Results are returned rounded to fp64 (one rounding of the exact sum).
+
+THE GEOMETRY (GeometryRays and what follows it): the renders that differentiate in the grid's points (c5_render_motion_tangent,
+c5_render_vertex_tangent, c5_render_vertex_adjoint), from the view-space vertices and the pixel's coordinates - the doubles
+the restatements see, taken exactly - with nothing of the restatements' arithmetic: per face the slopes gy = A / m,
+gx = -B / m (line.cpp:158-171), the depth at the pixel and the barycentrics e1 / m, e2 / m, e0 / m at 80 digits; the chord
+is the difference of the two depths AT 80 DIGITS (not the double the segment lists carry: a restatement is held to this
+within its bar with the dz_err term, which is what that term is for); ddz for an affine field (motion_reference's dw at
+P = (x, y, z_face)) and for per-point velocities (dw = sum_i lambda_i (u_z - gx u_x - gy u_y)[vertex i]); the recurrence
+tau_dot = sum alpha_k ddz_k, I_dot_k = E_k I_dot_{k-1} + E_k (Q_k - a_k I_{k-1}) ddz_k; and G_k = g_tau alpha_k + g_I T_k E_k
+(Q_k - a_k I_{k-1}) scattered to the points as +-G_k lambda_v (-gx, -gy, 1), then M^T.  Which two faces of its cell a segment
+runs between is taken from the restatement (their indices) and CHECKED here: both cover the pixel and the exit is the
+deeper of the two.
 """
 from __future__ import annotations
 
@@ -138,3 +150,139 @@ def gn_product(seg: Segments, n_cells: int, d_alpha, d_q, weights=None):
     jv32 = np.stack([t[0], t[1]], axis=1).astype(np.float32)
     g32 = jv32 if weights is None else (np.asarray(weights, np.float32) * jv32).astype(np.float32)
     return adjoint(seg, n_cells, g32.astype(np.float64)), jv32
+
+
+# ---- the geometry ------------------------------------------------------------------------------------------------------
+
+_FACES = ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3))  # plane.cpp:30-37
+
+
+def _face(P, x, y):
+    """(gx, gy, z at the pixel, the three barycentrics, covers) of the face with view-space vertices P [3][3] (mpf)."""
+    A, B, C = P
+    Aa = (B[0] - A[0]) * (C[2] - A[2]) - (C[0] - A[0]) * (B[2] - A[2])
+    Bb = (B[1] - A[1]) * (C[2] - A[2]) - (C[1] - A[1]) * (B[2] - A[2])
+    m = (B[0] - A[0]) * (C[1] - A[1]) - (C[0] - A[0]) * (B[1] - A[1])
+    e0 = (B[0] - A[0]) * (y - A[1]) - (B[1] - A[1]) * (x - A[0])
+    e1 = (C[0] - B[0]) * (y - B[1]) - (C[1] - B[1]) * (x - B[0])
+    e2 = (A[0] - C[0]) * (y - C[1]) - (A[1] - C[1]) * (x - C[0])
+    covers = (e0 >= 0 and e1 >= 0 and e2 >= 0) or (e0 <= 0 and e1 <= 0 and e2 <= 0)
+    gy, gx = Aa / m, -Bb / m
+    return dict(gx=gx, gy=gy, z=A[2] + gx * (x - A[0]) + gy * (y - A[1]), lam=(e1 / m, e2 / m, e0 / m), covers=covers)
+
+
+class GeometryRays:
+    """The segments of the chosen pixels with their two faces and their optics at 80 digits (module docstring: the
+    geometry).  view [n_pts, 3]: the view-space points; C, X, Y, F_out, F_in: vertex_adjoint_reference.segment_faces'
+    [pixel, k] matrices; pixels: the rows of those matrices wanted."""
+
+    def __init__(self, view, cells, geo, alpha, q, limit: float, pixels):
+        mp.dps = DPS
+        cells = np.asarray(cells).reshape(-1, 4)
+        self.pixels = np.asarray(pixels)
+        self.rays, self.n_segments, self.steepest = [], 0, 0.0
+        zero, one = mpf(0), mpf(1)
+        pts = {}
+
+        def point(v):
+            if v not in pts:
+                pts[v] = tuple(mpf(float(c)) for c in view[v])
+            return pts[v]
+
+        for p in self.pixels:
+            ray, I = [], zero
+            for k in range(geo["C"].shape[1]):
+                c = int(geo["C"][p, k])
+                if c < 0:
+                    break
+                x, y = mpf(float(geo["X"][p, k])), mpf(float(geo["Y"][p, k]))
+                t = dict(c=c, x=x, y=y)
+                for side in ("out", "in"):
+                    vid = [int(cells[c][i]) for i in _FACES[int(geo["F_" + side][p, k])]]
+                    f = _face([point(v) for v in vid], x, y)
+                    assert f["covers"], (int(p), k, side)
+                    f["vid"] = vid
+                    t[side] = f
+                    self.steepest = max(self.steepest, float(abs(f["gx"]) + abs(f["gy"])))
+                d = t["out"]["z"] - t["in"]["z"]
+                assert d > 0, (int(p), k)
+                a_raw = float(alpha[c])
+                a = min(a_raw, limit)
+                t.update(d=d, a_raw=mpf(a_raw), Q=mpf(float(q[c])), active=not a < EPS, a=zero, E=one, I_prev=I)
+                if t["active"]:
+                    am = mpf(a)
+                    E = mp.exp(-am * d)
+                    t.update(a=am, E=E)
+                    I = E * I + t["Q"] * (one - E) / am
+                ray.append(t)
+            T = one
+            for t in reversed(ray):
+                t["T"] = T
+                T = T * t["E"]
+            self.rays.append(ray)
+            self.n_segments += len(ray)
+
+
+def _recurrence(ray, ddz):
+    """(tau_dot, I_dot) of one ray for the chord rates ddz (one per segment, processing order)."""
+    tau_dot = I_dot = mpf(0)
+    for t, r in zip(ray, ddz):
+        tau_dot += t["a_raw"] * r
+        if t["active"]:
+            I_dot = t["E"] * I_dot + t["E"] * (t["Q"] - t["a"] * t["I_prev"]) * r
+    return tau_dot, I_dot
+
+
+def motion_tangent(rays: GeometryRays, field):
+    """(tau_dot, I_dot) fp64 [len(pixels)] each for the affine field [12] (A row-major, then b)."""
+    f = [mpf(float(v)) for v in np.asarray(field, np.float64).reshape(12)]
+
+    def dw(t, face):
+        x, y, z = t["x"], t["y"], face["z"]
+        ux, uy, uz = (f[3 * r] * x + f[3 * r + 1] * y + f[3 * r + 2] * z + f[9 + r] for r in range(3))
+        return uz - face["gx"] * ux - face["gy"] * uy
+
+    out = [_recurrence(ray, [dw(t, t["out"]) - dw(t, t["in"]) for t in ray]) for ray in rays.rays]
+    return np.array([[float(a), float(b)] for a, b in out]).reshape(-1, 2).T
+
+
+def vertex_tangent(rays: GeometryRays, d_xyz, M):
+    """(tau_dot, I_dot) fp64 [len(pixels)] each for the displacement field d_xyz [n_pts, 3]; M: the view's linear part."""
+    d_xyz = np.asarray(d_xyz, np.float64)
+    Mm = [[mpf(float(v)) for v in row] for row in np.asarray(M, np.float64)]
+    vel = {}
+
+    def u(v):
+        if v not in vel:
+            d = [mpf(float(c)) for c in d_xyz[v]]
+            vel[v] = tuple(Mm[r][0] * d[0] + Mm[r][1] * d[1] + Mm[r][2] * d[2] for r in range(3))
+        return vel[v]
+
+    def dw(face):
+        return sum((lam * (u(v)[2] - face["gx"] * u(v)[0] - face["gy"] * u(v)[1]) for lam, v in zip(face["lam"], face["vid"])), mpf(0))
+
+    out = [_recurrence(ray, [dw(t["out"]) - dw(t["in"]) for t in ray]) for ray in rays.rays]
+    return np.array([[float(a), float(b)] for a, b in out]).reshape(-1, 2).T
+
+
+def vertex_adjoint(rays: GeometryRays, weights, n_pts: int, M):
+    """grad_xyz fp64 [n_pts, 3] in the coordinates of the upload for the upstream weights (g_tau, g_I) of rays.pixels."""
+    acc = {}
+    for ray, (g_tau, g_I) in zip(rays.rays, weights):
+        g_tau, g_I = mpf(float(g_tau)), mpf(float(g_I))
+        for t in ray:
+            G = g_tau * t["a_raw"]
+            if t["active"]:
+                G += g_I * t["T"] * t["E"] * (t["Q"] - t["a"] * t["I_prev"])
+            for side, sign in (("out", 1), ("in", -1)):
+                face = t[side]
+                vec = (-face["gx"], -face["gy"], mpf(1))
+                for lam, v in zip(face["lam"], face["vid"]):
+                    a = acc.setdefault(v, [mpf(0), mpf(0), mpf(0)])
+                    for k in range(3):
+                        a[k] += sign * G * lam * vec[k]
+    Mm = [[mpf(float(v)) for v in row] for row in np.asarray(M, np.float64)]
+    out = np.zeros((n_pts, 3))
+    for v, a in acc.items():  # grad_xyz = M^T grad_view
+        out[v] = [float(sum(Mm[r][k] * a[r] for r in range(3))) for k in range(3)]
+    return out

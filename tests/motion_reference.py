@@ -59,10 +59,8 @@ def face_matrices(xyz, cells, rots, res_x, res_y, bounds, rows=None):
     rows = np.arange(res_y) if rows is None else np.asarray(rows)
     cells = np.asarray(cells).reshape(-1, 4)
     pix, cell, zh, dz = ar.segment_lists(xyz, cells, rots, res_x, res_y, bounds)
-    b = np.asarray(bounds, dtype=np.float64)
-    sx, sy = (b[0] - b[1]) / (res_x - 1.0), (b[2] - b[3]) / (res_y - 1.0)
-    x = (b[1] + sx * np.arange(res_x))[pix % res_x]
-    y = (b[3] + sy * np.arange(res_y))[pix // res_x]
+    X, Y, _sx, _sy = ar.pixel_coordinates(bounds, res_x, res_y)
+    x, y = X[pix % res_x], Y[pix // res_x]
     P = ar.rotate(xyz, rots)[cells[cell]]  # [S, 4, 3]
     n = len(pix)
     cover = np.zeros((n, 4), dtype=bool)

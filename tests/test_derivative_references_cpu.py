@@ -16,7 +16,10 @@ from tests import derivative_fuzz as df
 from tests import derivative_reference_mp as dm
 from tests import fuzz_scenes
 from tests import gn_reference as gr
+from tests import motion_reference as mr
 from tests import tangent_reference as tr
+from tests import vertex_adjoint_reference as vr
+from tests import vertex_tangent_reference as vt
 
 B = mg.REFERENCE_BOUNDS
 RTOL = {"scal": 1e-9, "sens": 1e-6}
@@ -171,3 +174,66 @@ def test_the_scenes_cover_every_class_and_both_branches(scenes):
     assert seen["series"] > 1000 and seen["closed"] > 1000
     assert seen["modes"] == {"plain", "threshold", "underflow"}
     assert worst[0] <= 64
+
+
+# ---- the geometry restatements (motion tangent, vertex tangent, vertex adjoint) ----------------------------------------
+
+# a "threshold" and an "underflow" scene (the latter a soup); 3003 and 3007 for their steep faces, a few rows each
+GEOMETRY_SEEDS = (3001, 3006, 3003, 3007)
+N_PIXELS = 90
+
+
+@pytest.mark.parametrize("seed", GEOMETRY_SEEDS)
+def test_geometry_restatements_against_80_digits(seed, oracle_port):
+    """motion_reference, vertex_tangent_reference and vertex_adjoint_reference against derivative_reference_mp's geometry
+    on N_PIXELS pixels of a scene of the geometry sweep, element by element within their own bars
+    1e-9 scale + dz_err sens + 2^-970 - the sens term because the 80-digit chord is the difference of the two depths, not
+    the double the restatements carry.  In 3003 and 3007 the pixels are those of the rows about the steepest face."""
+    s = df.geometry_scene(seed)
+    assert df.qualify(s, oracle_port) is None
+    rx, ry = s.res
+    n_pts = len(s.xyz)
+    pix, _cell, _zh, _dz, slope = s.segments
+    rows = None
+    if seed in (3003, 3007):
+        r = int(pix[slope.argmax()] // rx)
+        rows = np.arange(max(r - 2, 0), min(r + 3, ry))
+    m = ar.ray_matrices(s.xyz, s.cells, s.alpha, s.q, s.rots, rx, ry, B, s.limit, rows)
+    geo = vr.segment_faces(s.xyz, s.cells, s.rots, rx, ry, B, rows)
+    covered = np.flatnonzero(m["valid"].any(1))
+    steep = np.flatnonzero((m["F"] * m["valid"]).max(1) > 100.0)
+    rng = np.random.default_rng([seed, 80])
+    pixels = np.unique(np.concatenate([steep[:N_PIXELS // 3], rng.choice(covered, min(N_PIXELS, len(covered)), replace=False)]))[:N_PIXELS]
+    rays = dm.GeometryRays(ar.rotate(s.xyz, s.rots), s.cells, geo, s.alpha, s.q, s.limit, pixels)
+    if seed in (3003, 3007):
+        assert rays.steepest > 100.0
+    M = vr.view_matrix(s.rots)
+    e = df.dz_err(s)
+    worst = {}
+
+    def hold(kind, got, want, scale, sens):
+        r = df.ratio(got, want, scale, sens, e)
+        worst[kind] = max(worst.get(kind, 0.0), float(r.max()))
+        assert (r <= 1.0).all(), (kind, float(r.max()))
+
+    at = s.motion_at
+    for j in (0, at["base"], at["base"] + 2, at["up"]):  # a rotation, a drawn field, the z-scale, the drawn field x 2^20
+        td, Id, x = mr.motion_of(m, geo, s.motion[j], with_scale=True)
+        want = dm.motion_tangent(rays, s.motion[j])
+        flat = lambda a: a.reshape(-1)[pixels]  # noqa: E731
+        hold("motion tau_dot", flat(td), want[0], flat(x["scale_tau"]), flat(x["sens_tau"]))
+        hold("motion I_dot", flat(Id), want[1], flat(x["scale_I"]), flat(x["sens_I"]))
+    for j in s.v_compare:
+        td, Id, x = vt.tangent_of(m, geo, s.cells, s.rots, s.v_fields[j], with_scale=True)
+        want = dm.vertex_tangent(rays, s.v_fields[j], M)
+        hold("vertex tau_dot", flat(td), want[0], flat(x["scale_tau"]), flat(x["sens_tau"]))
+        hold("vertex I_dot", flat(Id), want[1], flat(x["scale_I"]), flat(x["sens_I"]))
+    chosen = np.zeros(m["n_px"], bool)
+    chosen[pixels] = True
+    for g in s.vg:  # the upstream image on the chosen pixels, zero elsewhere
+        g = g if rows is None else g[rows]
+        w = np.where(chosen[:, None], g.reshape(-1, 2).astype(np.float64), 0.0)
+        ref = vr.gradients_of(m, geo, s.cells, n_pts, s.rots, w)
+        hold("vertex adjoint", ref["raw"], dm.vertex_adjoint(rays, w[pixels], n_pts, M), ref["scale_raw"], ref["sens_raw"])
+    print(f"seed {seed} ({df.describe(s)}; {rays.n_segments} segments on {len(pixels)} pixels at 80 digits, steepest face "
+          f"{rays.steepest:.3g}): worst error / bar " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))

@@ -18,7 +18,7 @@ import pytest
 from course5_amd import capi
 from course5_amd import meshgen as mg
 from course5_amd import sharding
-from tests import adjoint_reference as ar, derivative_fuzz as fz
+from tests import adjoint_reference as ar, derivative_fuzz as fz, ray_matrix_checks as rmc
 
 pytestmark = pytest.mark.gpu
 B = mg.REFERENCE_BOUNDS
@@ -79,39 +79,14 @@ def _matrix(kind, options=()):
     return m
 
 
-def _rows_of(row_ptr):
-    return np.repeat(np.arange(len(row_ptr) - 1), np.diff(row_ptr))
-
-
-def _check_csr(m, n_px, n_cells):
-    row_ptr, col, dz, z_exit = m
-    assert row_ptr.dtype == np.int64 and col.dtype == np.int32 and dz.dtype == np.float64 and z_exit.dtype == np.float64
-    assert row_ptr.shape == (n_px + 1,) and row_ptr[0] == 0 and (np.diff(row_ptr) >= 0).all()
-    assert len(col) == len(dz) == len(z_exit) == row_ptr[-1]
-    assert ((col >= 0) & (col < n_cells)).all() and (dz > 0).all() and np.isfinite(dz).all() and np.isfinite(z_exit).all()
-    pix = _rows_of(row_ptr)
-    assert len(np.unique(pix * np.int64(n_cells) + col)) == len(col)  # a ray crosses a cell at most once
-    inside = pix[1:] == pix[:-1]
-    assert (np.diff(z_exit)[inside] >= 0).all()  # deepest first, z ascending
-    return pix
+_rows_of, _check_csr = rmc.rows_of, rmc.check_csr
 
 
 def _check_against_reference(kind, m, what):
     """Structure exactly, nnz, dz and z_exit within the chord bar; prints the worst error / bar of both."""
-    xyz, cells, _a, _q, _rots, rx, ry, _b, want = _scene(kind)
-    (rpix, rcell, rzh, rdz, rslope), unit = _reference(kind)
-    row_ptr, col, dz, z_exit = m
-    pix = _check_csr(m, rx * ry, len(cells))
-    assert len(rpix) == want  # (the reference's own count: the fixture is what the issue says it is)
-    assert row_ptr[-1] == want
-    og, orf = np.lexsort((col, pix)), np.lexsort((rcell, rpix))
-    assert np.array_equal(pix[og], rpix[orf]) and np.array_equal(col[og], rcell[orf])
-    bar = unit * np.maximum(1.0, rslope[orf])
-    e_dz, e_z = np.abs(dz[og] - rdz[orf]) / bar, np.abs(z_exit[og] - rzh[orf]) / bar
-    print(f"{what}: nnz {want}, smallest chord {rdz.min():.3g}, bar {bar.min():.3g} .. {bar.max():.3g}, worst error / bar: "
-          f"dz {e_dz.max():.3g}, z_exit {e_z.max():.3g}")
-    assert (e_dz <= 1.0).all(), f"{what}: {int((e_dz > 1).sum())} chords over their bar, worst {e_dz.max():.3g}"
-    assert (e_z <= 1.0).all(), f"{what}: {int((e_z > 1).sum())} depths over their bar, worst {e_z.max():.3g}"
+    _xyz, cells, _a, _q, _rots, rx, ry, _b, want = _scene(kind)
+    ref, unit = _reference(kind)
+    rmc.check_against_reference(m, ref, unit, rx * ry, len(cells), want, what)
 
 
 def test_g3_the_references_own_lists():
@@ -181,15 +156,7 @@ def test_linearity_tau_and_the_adjoint():
     assert (gq == 0).all()
 
 
-def _bit_equal_rows(part, whole, global_px):
-    """The rows of `part` (local pixels = global_px of the whole frame) are bit for bit those rows of `whole`."""
-    (rp, col, dz, z), (wrp, wcol, wdz, wz) = part, whole
-    lengths = (wrp[1:] - wrp[:-1])[global_px]
-    if not np.array_equal(np.diff(rp), lengths):
-        return False
-    at = np.repeat(wrp[global_px] - rp[:-1], lengths) + np.arange(rp[-1])
-    return (np.array_equal(col, wcol[at]) and np.array_equal(dz.view(np.uint64), wdz[at].view(np.uint64))
-            and np.array_equal(z.view(np.uint64), wz[at].view(np.uint64)))
+_bit_equal_rows = rmc.bit_equal_rows
 
 
 def test_shards_are_rows_of_the_whole_frame_and_calls_repeat():

@@ -2,18 +2,21 @@
 (tests/vertex_adjoint_reference.py), the library's own motion tangent (the two are transposes of each other) and exact
 identities.  Every test opens its own contexts.
 
-Bars.  Against the restatement: per component column 1e-6 x max |ref| (tests/test_gpu_adjoint.py's bar).  Run to run:
+Bars.  Against the restatement: per component column 1e-6 x max |ref| (tests/test_gpu_adjoint.py's bar), and per component
+1e-9 scale_raw + dz_err sens_raw + 2^-970 (tests/derivative_fuzz.py's bar with the vertex adjoint's own scale and chord
+sensitivity, calibrated in tests/test_vertex_adjoint_cpu.py).  Run to run:
 rtol 1e-12, atol 1e-15 x max (the adjoint's: fp64 atomics in arrival order).  Duality with the motion tangent:
 2^-22 x sum_p |g_p| |out_p| - the motion image is fp32, every value rounded to 2^-24 relative, and a factor 4 covers the
 fp64 sides."""
 import ctypes as C
+import types
 
 import numpy as np
 import pytest
 
 from course5_amd import capi
 from course5_amd import meshgen as mg
-from tests import motion_reference as mr, vertex_adjoint_reference as vr
+from tests import derivative_fuzz as fz, motion_reference as mr, vertex_adjoint_reference as vr
 from tests.test_gpu_motion import B, ROTS, _ctx, _scene
 
 pytestmark = pytest.mark.gpu
@@ -23,12 +26,27 @@ def _weights(ry, rx, seed):
     return np.random.default_rng(seed).normal(size=(ry, rx, 2)).astype(np.float32)
 
 
-def _assert_close(got, ref, what):
+def _dz_err(xyz, rots):
+    return fz.dz_err(types.SimpleNamespace(xyz=xyz, rots=rots))
+
+
+def _assert_close(got, full, dz_err, what, onto=None):
+    """full: vertex_gradients' dict; onto: the representatives its rows are summed on (a soup), bounds included."""
+    ref, scale, sens = full["raw"], full["scale_raw"], full["sens_raw"]
+    if onto is not None:
+        ref, scale, sens = (np.zeros_like(v) for v in (ref, scale, sens))
+        for acc, v in ((ref, full["raw"]), (scale, full["scale_raw"]), (sens, full["sens_raw"])):
+            np.add.at(acc, onto, v)  # the group's sum on its representative
     assert got.shape == ref.shape and np.isfinite(got).all()
     for k, name in enumerate("xyz"):
         err, top = np.abs(got[:, k] - ref[:, k]).max(), np.abs(ref[:, k]).max()
         print(f"{what} grad_{name}: max error {err:.3g} of max {top:.3g} ({err / top:.3g})")
         assert top > 0 and err <= 1e-6 * top, f"{what} grad_{name}: max abs error {err:.3g} vs max {top:.3g}"
+    # ... and every component on its own scale: a point whose gradient is small is held as tightly as the largest
+    tol = 1e-9 * scale + dz_err * sens + 2.0 ** -970
+    r = np.abs(got - ref) / tol
+    print(f"{what}: worst error / element bar {r.max():.3g}")
+    assert (r <= 1.0).all(), f"{what}: {int((r > 1).sum())} components over their bar, worst {r.max():.3g} at {np.unravel_index(r.argmax(), r.shape)}"
 
 
 def _assert_same_run(a, b, parts=1):
@@ -50,7 +68,7 @@ def test_walk_against_the_restatement(kind):
         got = ctx.render_vertex_adjoint(g)
         again = ctx.render_vertex_adjoint(g)
     _assert_same_run(again, got)
-    _assert_close(got, vr.vertex_gradients(xyz, cells, alpha, q, rots, rx, ry, bounds, g)["raw"], kind)
+    _assert_close(got, vr.vertex_gradients(xyz, cells, alpha, q, rots, rx, ry, bounds, g), _dz_err(xyz, rots), kind)
 
 
 def test_soup_on_the_fallback_lands_on_the_representatives():
@@ -65,10 +83,8 @@ def test_soup_on_the_fallback_lands_on_the_representatives():
     assert merged == len(soup_xyz) - len(xyz)  # (every point of the soup is welded to some other)
     others = rep != np.arange(len(rep))
     assert others.sum() == merged and not got[others].any()  # exactly 0
-    per_copy = vr.vertex_gradients(soup_xyz, soup_cells, alpha, q, ROTS, 80, 60, B, g)["raw"]
-    ref = np.zeros_like(per_copy)
-    np.add.at(ref, rep, per_copy)  # the group's sum on its representative
-    _assert_close(got, ref, "soup, algorithm 1")
+    per_copy = vr.vertex_gradients(soup_xyz, soup_cells, alpha, q, ROTS, 80, 60, B, g)
+    _assert_close(got, per_copy, _dz_err(soup_xyz, ROTS), "soup, algorithm 1", onto=rep)
 
 
 def test_interpenetrating_boxes_across_the_retry():
@@ -78,7 +94,7 @@ def test_interpenetrating_boxes_across_the_retry():
     with _ctx(xyz, cells, alpha, q, ROTS, 80, 60) as ctx:
         got = ctx.render_vertex_adjoint(g)  # the first walk finds the overlap (C5_RETRY, settled inside the call)
         _assert_same_run(ctx.render_vertex_adjoint(g), got)
-    _assert_close(got, vr.vertex_gradients(xyz, cells, alpha, q, ROTS, 80, 60, B, g)["raw"], "overlapping boxes")
+    _assert_close(got, vr.vertex_gradients(xyz, cells, alpha, q, ROTS, 80, 60, B, g), _dz_err(xyz, ROTS), "overlapping boxes")
 
 
 def test_solid_pixels_contribute_nothing():
@@ -93,7 +109,7 @@ def test_solid_pixels_contribute_nothing():
         got = ctx.render_vertex_adjoint(g)
     skip = np.isnan(img[..., 0])
     assert 20 < skip.sum() < skip.size // 2
-    _assert_close(got, vr.vertex_gradients(xyz, cells, alpha, q, ROTS, rx, ry, B, g, skip=skip)["raw"], "solid")
+    _assert_close(got, vr.vertex_gradients(xyz, cells, alpha, q, ROTS, rx, ry, B, g, skip=skip), _dz_err(xyz, ROTS), "solid")
 
 
 def test_morton_ordered_cells():
@@ -104,7 +120,7 @@ def test_morton_ordered_cells():
     g = _weights(ry, rx, 35)
     with _ctx(xyz, cells, alpha, q, ROTS, rx, ry, options=(("cell_order", 1),)) as ctx:
         got = ctx.render_vertex_adjoint(g)
-    _assert_close(got, vr.vertex_gradients(xyz, cells, alpha, q, ROTS, rx, ry, B, g)["raw"], "cell_order 1")
+    _assert_close(got, vr.vertex_gradients(xyz, cells, alpha, q, ROTS, rx, ry, B, g), _dz_err(xyz, ROTS), "cell_order 1")
 
 
 def _duality(ctx, n_pts, g, fields, grad):

@@ -108,27 +108,50 @@ def test_the_convexity_rule_finds_the_paired_faces(scene):
             assert np.array_equal(g, geo[name][valid]), name
 
 
-def test_chord_sensitivity_covers_moved_chords(scene):
-    """1e-9 scale + dz_err sens covers the restatement re-evaluated with every chord moved by +-F dz_err: the per-element
-    bar of tests/test_gpu_motion.py, calibrated without the code under test."""
-    s = scene
+def _calibration_scene(scene, which):
+    """The fixed box, or a scene of the geometry sweep (tests/derivative_fuzz.py) with its own fields: (s, m, geo, fields)."""
+    if which == "box":
+        rng = np.random.default_rng(3)
+        return scene, scene.m, scene.geo, [capi.rotation_motion(ROTS, 0), capi.rotation_motion(ROTS, 1), mr.Z_SCALE, rng.normal(size=12)]
+    s = fz.geometry_scene(which)
+    assert s.mode == {3001: "threshold", 3006: "underflow"}[which]
+    m = ar.ray_matrices(s.xyz, s.cells, s.alpha, s.q, s.rots, s.res[0], s.res[1], fz.B, s.limit)
+    return s, m, mr.face_matrices(s.xyz, s.cells, s.rots, s.res[0], s.res[1], fz.B), list(s.motion)
+
+
+@pytest.mark.parametrize("which", ["box", 3001, 3006])
+def test_chord_sensitivity_covers_moved_chords(scene, which):
+    """1e-9 scale + dz_err sens covers the restatement re-evaluated with every chord moved by +-F dz_err, and with the two
+    depths a field reads (the kappa terms) moved by as much: the per-element bar of tests/test_gpu_motion.py and of the
+    geometry sweep, calibrated without the code under test - on the fixed box and on a "threshold" (3001) and an
+    "underflow" (3006) scene of the sweep with their own fields (every rotation, the 2^+-20 multiples, the shifts)."""
+    s, m, geo, fields = _calibration_scene(scene, which)
+    shape = m["shape"]
     dz_err = fz.dz_err(s)
     rng = np.random.default_rng(3)
-    fields = [capi.rotation_motion(ROTS, 0), capi.rotation_motion(ROTS, 1), mr.Z_SCALE, rng.normal(size=12)]
-    moves = [np.ones_like(s.m["D"]), -np.ones_like(s.m["D"]), rng.choice([-1.0, 1.0], s.m["D"].shape)]
+    moves = [np.ones_like(m["D"]), -np.ones_like(m["D"]), rng.choice([-1.0, 1.0], m["D"].shape)]
     worst = 0.0
     for f in fields:
-        tau_dot, I_dot, extra = mr.motion_of(s.m, s.geo, f, with_scale=True)
-        ddz = mr.chord_rates(s.geo, f)[0]
-        tol = 1e-9 * extra["scale_I"] + dz_err * extra["sens_I"]
-        assert (extra["sens_I"][s.m["active"].any(1).reshape(RY, RX)] > 0).all()
+        tau_dot, I_dot, extra = mr.motion_of(m, geo, f, with_scale=True)
+        ddz = mr.chord_rates(geo, f)[0]
+        tol_I = 1e-9 * extra["scale_I"] + dz_err * extra["sens_I"]
+        tol_tau = 1e-9 * extra["scale_tau"] + dz_err * extra["sens_tau"]
+        if np.any(f) and which == "box":
+            assert (extra["sens_I"][m["active"].any(1).reshape(shape)] > 0).all()
         for sign in moves:
-            D = np.where(s.m["valid"], s.m["D"] + sign * s.m["F"] * dz_err, 0.0)
-            moved = mr.recurrence(s.m, D, ddz)[1].reshape(RY, RX)
+            D = np.where(m["valid"], m["D"] + sign * m["F"] * dz_err, 0.0)
+            moved = mr.recurrence(m, D, ddz)[1].reshape(shape)
             diff = np.abs(moved - I_dot)
-            assert (diff <= tol).all()
-            worst = max(worst, float((diff / np.where(tol > 0, tol, 1.0)).max()))
-    print(f"moved chords: worst change / bar {worst:.3g}")
+            assert (diff <= tol_I).all()
+            worst = max(worst, float((diff / np.where(tol_I > 0, tol_I, 1.0)).max()))
+            # ... and the depths the field is evaluated at, the far end one way and the near end the other
+            there = dict(geo, Z_out=geo["Z_out"] + sign * m["F"] * dz_err, Z_in=geo["Z_in"] - sign * m["F"] * dz_err)
+            tau2, I2 = mr.recurrence(m, D, mr.chord_rates(there, f)[0])[:2]
+            for got, ref, tol in ((tau2.reshape(shape), tau_dot, tol_tau), (I2.reshape(shape), I_dot, tol_I)):
+                diff = np.abs(got - ref)
+                worst = max(worst, float((diff / np.where(tol > 0, tol, 1.0)).max()))
+                assert (diff <= tol).all(), (which, float((diff / np.where(tol > 0, tol, 1.0)).max()))
+    print(f"{which}: moved chords and depths, worst change / bar {worst:.3g}")
 
 
 def test_course_refuses_view_tangent_for_sweeps_at_parse_time(tmp_path):

@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 from course5_amd import meshgen as mg
-from tests import adjoint_reference as ar, motion_reference as mr, tangent_reference as tr, vertex_adjoint_reference as vr
+from tests import adjoint_reference as ar, derivative_fuzz as fz, motion_reference as mr, tangent_reference as tr
+from tests import vertex_adjoint_reference as vr
 
 BOUNDS = (1.9, 0.1, 0.9, -0.9)  # tests/test_gpu_motion.py: SMALL_BOUNDS, SMALL_ROTS
 RX, RY = 48, 36
@@ -114,3 +115,42 @@ def test_z_scale_is_the_tangent_along_the_scalars_themselves():
     terms = float(np.abs(z) @ ref["scale_view"][:, 2])
     print(f"z-scale: {lhs:.6g} against {rhs:.6g}, difference / sum |terms| = {abs(lhs - rhs) / terms:.3g}")
     assert abs(lhs) > 0 and abs(lhs - rhs) <= 1e-12 * terms
+
+
+@pytest.mark.parametrize("which", ["box", 3001, 3006])
+def test_chord_sensitivity_covers_moved_chords(scene, which):
+    """1e-9 scale_raw + dz_err sens_raw covers the restatement re-evaluated with every chord moved by +-F dz_err: the
+    per-element bar of the geometry sweep (tests/derivative_fuzz.py) and of tests/test_gpu_vertex_adjoint.py, calibrated
+    without the code under test (tests/test_motion_cpu.py's way) - on the fixed box and on a "threshold" (3001) and an
+    "underflow" (3006, a soup) scene of the sweep with their own upstream images."""
+    if which == "box":
+        s = scene
+        rots, images = ROTS, [s.g]
+        m = ar.ray_matrices(s.xyz, s.cells, s.alpha, s.q, ROTS, RX, RY, BOUNDS)
+        geo = vr.segment_faces(s.xyz, s.cells, ROTS, RX, RY, BOUNDS)
+    else:
+        s = fz.geometry_scene(which)
+        assert s.mode == {3001: "threshold", 3006: "underflow"}[which]
+        rots, images = s.rots, s.vg
+        m = ar.ray_matrices(s.xyz, s.cells, s.alpha, s.q, rots, s.res[0], s.res[1], fz.B, s.limit)
+        geo = vr.segment_faces(s.xyz, s.cells, rots, s.res[0], s.res[1], fz.B)
+    dz_err = fz.dz_err(types.SimpleNamespace(xyz=s.xyz, rots=rots))
+    rng = np.random.default_rng(3)
+    moves = [np.ones_like(m["D"]), -np.ones_like(m["D"]), rng.choice([-1.0, 1.0], m["D"].shape)]
+    worst = 0.0
+    for g in images:
+        ref = vr.gradients_of(m, geo, s.cells, len(s.xyz), rots, g)
+        same = vr.gradients_of(vr.with_chords(m, m["D"]), geo, s.cells, len(s.xyz), rots, g)
+        assert np.array_equal(same["raw"], ref["raw"])  # (with_chords evaluates what ray_matrices does)
+        assert (np.abs(ref["raw"]) <= ref["scale_raw"] * (1 + 1e-12)).all()
+        tol = 1e-9 * ref["scale_raw"] + dz_err * ref["sens_raw"]
+        if np.abs(np.asarray(g)[..., 1]).max() > 0:
+            assert ref["sens_raw"].max() > 0
+        else:
+            assert not ref["sens_raw"].any()  # (g_tau alpha_k holds no chord)
+        for sign in moves:
+            D = np.where(m["valid"], m["D"] + sign * m["F"] * dz_err, 0.0)
+            diff = np.abs(vr.gradients_of(vr.with_chords(m, D), geo, s.cells, len(s.xyz), rots, g)["raw"] - ref["raw"])
+            worst = max(worst, float((diff / np.where(tol > 0, tol, 1.0)).max()))
+            assert (diff <= tol).all(), (which, float((diff / np.where(tol > 0, tol, 1.0)).max()))
+    print(f"{which}: moved chords, worst change / bar {worst:.3g}")

@@ -79,31 +79,42 @@ def test_affine_fields_give_the_motion_tangent_restatement(scene):
             assert np.abs(w).max() > 0 and (err <= 1e-12 * scale).all()
 
 
-def test_chord_sensitivity_covers_moved_chords(scene):
+@pytest.mark.parametrize("which", ["box", 3001, 3006])
+def test_chord_sensitivity_covers_moved_chords(scene, which):
     """1e-9 scale + dz_err sens covers the restatement re-evaluated with every chord moved by +-F dz_err: the per-element
-    bar of tests/test_gpu_vertex_tangent.py, calibrated without the code under test (tests/test_motion_cpu.py's way).  The
-    scale bounds the result term by term."""
-    s = scene
+    bar of tests/test_gpu_vertex_tangent.py and of the geometry sweep, calibrated without the code under test (tests/
+    test_motion_cpu.py's way) - on the fixed box and on a "threshold" (3001) and an "underflow" (3006, a soup) scene of the
+    sweep with the fields the sweep compares.  The scale bounds the result term by term."""
+    if which == "box":
+        s, m, geo, rots, fields = scene, scene.m, scene.geo, ROTS, scene.fields
+    else:
+        s = fz.geometry_scene(which)
+        assert s.mode == {3001: "threshold", 3006: "underflow"}[which]
+        rots, fields = s.rots, s.v_fields[s.v_compare]
+        m = ar.ray_matrices(s.xyz, s.cells, s.alpha, s.q, rots, s.res[0], s.res[1], fz.B, s.limit)
+        geo = vr.segment_faces(s.xyz, s.cells, rots, s.res[0], s.res[1], fz.B)
+    shape = m["shape"]
     dz_err = fz.dz_err(s)
     rng = np.random.default_rng(3)
-    M = vr.view_matrix(ROTS)
-    moves = [np.ones_like(s.m["D"]), -np.ones_like(s.m["D"]), rng.choice([-1.0, 1.0], s.m["D"].shape)]
+    M = vr.view_matrix(rots)
+    moves = [np.ones_like(m["D"]), -np.ones_like(m["D"]), rng.choice([-1.0, 1.0], m["D"].shape)]
     worst = 0.0
-    for d in s.fields:
-        tau_dot, I_dot, extra = vt.tangent_of(s.m, s.geo, s.cells, ROTS, d, with_scale=True)
+    for d in fields:
+        tau_dot, I_dot, extra = vt.tangent_of(m, geo, s.cells, rots, d, with_scale=True)
         assert (np.abs(tau_dot) <= extra["scale_tau"] * (1 + 1e-12)).all() and (np.abs(I_dot) <= extra["scale_I"] * (1 + 1e-12)).all()
         assert not extra["sens_tau"].any()  # (tau_dot does not hold the chords, and a per-vertex dw not the depth)
-        ddz = vt.chord_rates(s.geo, s.cells, d @ M.T)[0]
+        ddz = vt.chord_rates(geo, s.cells, d @ M.T)[0]
         tol = 1e-9 * extra["scale_I"] + dz_err * extra["sens_I"]
-        assert (extra["sens_I"][s.m["active"].any(1).reshape(RY, RX)] > 0).all()
+        if which == "box":
+            assert (extra["sens_I"][m["active"].any(1).reshape(shape)] > 0).all()
         for sign in moves:
-            D = np.where(s.m["valid"], s.m["D"] + sign * s.m["F"] * dz_err, 0.0)
-            moved_tau, moved_I = mr.recurrence(s.m, D, ddz)[:2]
-            assert np.array_equal(moved_tau.reshape(RY, RX), tau_dot)
-            diff = np.abs(moved_I.reshape(RY, RX) - I_dot)
-            assert (diff <= tol).all()
+            D = np.where(m["valid"], m["D"] + sign * m["F"] * dz_err, 0.0)
+            moved_tau, moved_I = mr.recurrence(m, D, ddz)[:2]
+            assert np.array_equal(moved_tau.reshape(shape), tau_dot)
+            diff = np.abs(moved_I.reshape(shape) - I_dot)
+            assert (diff <= tol).all(), (which, float((diff / np.where(tol > 0, tol, 1.0)).max()))
             worst = max(worst, float((diff / np.where(tol > 0, tol, 1.0)).max()))
-    print(f"moved chords: worst change / bar {worst:.3g}")
+    print(f"{which}: moved chords, worst change / bar {worst:.3g}")
 
 
 def test_skip_and_rows(scene):
