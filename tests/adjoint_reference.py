@@ -293,3 +293,46 @@ def gradients_of(m, n_cells: int, weights, skip=None, with_scale: bool = False):
              "sens_alpha": np.abs(g_tau) * m["F"] + np.abs(g_I) * m["sens_a"], "sens_q": np.abs(g_I) * m["sens_q"]}
     extra = {name: np.bincount(C[valid], weights=np.broadcast_to(t, D.shape)[valid], minlength=n_cells) for name, t in terms.items()}
     return out + (extra,)
+
+
+def forward_of(m, skip=None, with_scale: bool = False):
+    """The forward render (include/course5_hip.h: c5_render) from ray_matrices' dict: (tau, I), the fp64 images of the
+    dict's rows; skip: optional bool [rows, res_x], True = a solid-marked pixel, NaN in both channels.
+
+    with_scale: also a dict of the per-pixel terms of the bar a render is held to (tests/derivative_fuzz.py: the forward
+    sweep), every one [rows, res_x] and 0 on a pixel without a segment:
+      scale_tau  sum dz_k |alpha_k|, sens_tau  sum F_k |alpha_k|                     (the raw alpha: tau is not clamped)
+      scale_I    sum T_k |Q_k| S_k, the emission with every contribution by its absolute value
+      sens_I     sum F_k T_k E_k |Q_k - a_k I_{k-1}| over the active segments: dI / d dz_k = T_k E_k (Q_k - a_k I_{k-1}), the
+                 chord derivative the motion tangent's header states (c5_render_motion_tangent)
+      cancel     8 x 2^-53 x sum T_k (|Q_k| + a_k |I_{k-1}|) / a_k over the active segments: the rounding of the REFERENCE'S
+                 OWN step C = Q - a I; I = (Q - C e) / a (line.cpp:220-224).  With u = 2^-53, M = |Q| + a |I| >= |C| and
+                 N = Q - C e = Q (1 - e) + a I e, |N| <= M, the step's roundings reach the numerator as: a I and C, u M e
+                 each; e = exp(-x) within one ulp of an argument that is itself rounded, (2 + x) u M e; the product C e,
+                 u M e; the difference, u |N|; and the division adds u |N| / a.  Together u M (e (5 + x) + 2) / a, and
+                 e^-x (5 + x) <= 5: 7 u M / a to first order, 8 with the second.  The step's error reaches the pixel through
+                 T_k.  This is what makes the reference "its own cancellation noise" for a in [DBL_EPSILON, ~1e-8) (DESIGN
+                 section 5): 2^-50 / a is 4e-8 at a = 2e-8 and 4 at DBL_EPSILON, against the 2^-23 = 1.2e-7 of the output's
+                 rounding; for a >= 1e-6 it is below 1e-9.  A render on "integration" 0 repeats the reference's roundings;
+                 the restatement (E and S from exp and expm1) has none of them: the term is the distance between the two.
+      emission   sum |Q_k| S_k over the active segments: what an early-out at transmittance c can drop is at most
+                 c x this ("integration" 1 with a non-zero "transmittance_cutoff": the segments behind the cut have T < c)."""
+    valid, active, D, F, T, E, S, Q = m["valid"], m["active"], m["D"], m["F"], m["T"], m["E"], m["S"], m["Q"]
+    # I as sum T_k Q_k S_k, not the recurrence's last value (m["I"]): T carries its exponent in double-double
+    # (_transmittance), while the recurrence multiplies by exp(-a dz) of a ROUNDED a dz - a ray that ends behind an optical
+    # depth of 370 with nothing emitted in front has all of its I at 370 x 2^-53 of relative error that way
+    # (tests/test_forward_reference_cpu.py, seed 2000: 127 x 2^-52 x scale against the 80-digit reference)
+    tau, I = m["tau"].reshape(m["shape"]).copy(), np.where(active, T * Q * S, 0.0).sum(1).reshape(m["shape"])
+    if skip is not None:
+        tau[np.asarray(skip)] = np.nan
+        I[np.asarray(skip)] = np.nan
+    if not with_scale:
+        return tau, I
+    a, a_raw, I_prev = m["a"], np.abs(m["a_raw"]), m["I_prev"]
+    inv_a = np.where(active, 1.0 / np.where(active, a, 1.0), 0.0)
+    terms = {"scale_tau": np.where(valid, D * a_raw, 0.0), "sens_tau": np.where(valid, F * a_raw, 0.0),
+             "scale_I": np.where(active, T * np.abs(Q) * S, 0.0),
+             "sens_I": np.where(active, F * T * E * np.abs(Q - a * I_prev), 0.0),
+             "cancel": 8.0 * 2.0 ** -53 * np.where(active, T * (np.abs(Q) + a * np.abs(I_prev)) * inv_a, 0.0),
+             "emission": np.where(active, np.abs(Q) * S, 0.0)}
+    return tau, I, {name: t.sum(1).reshape(m["shape"]) for name, t in terms.items()}

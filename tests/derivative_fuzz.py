@@ -3,6 +3,7 @@ against the numpy restatements, element by element.
 
     python tests/derivative_fuzz.py [n_scenes] [seed0]
     python tests/derivative_fuzz.py geometry [n_scenes] [seed0]      (the geometry sweep, below)
+    python tests/derivative_fuzz.py forward [n_scenes] [seed0]       (the forward sweep, at the end of this text)
     python tests/derivative_fuzz.py chords SEED PIXEL      (the GPU's chords along one ray against the reference's)
 
 reports every mismatch and the worst error / tolerance per call kind; exit status 1 on any mismatch or when more than
@@ -90,6 +91,48 @@ Layout, soup, solid, device forms and the late limit are derivative_scene's.  Pe
       bit; stats() before and after the calls; a plain render after the calls bit-equal to the one before them.
 What the first run of it found is in profiles/geometry_fuzz.md: the restatements' pixel coordinates
 (adjoint_reference.pixel_coordinates).
+
+THE FORWARD SWEEP (forward_scene, check_forward; tests/test_gpu_forward_fuzz.py runs 40 seeds of it): the render itself,
+frame by frame, against adjoint_reference.forward_of - the kernel every performance change rewrites.  forward_scene(seed) is
+derivative_scene(seed), unchanged (qualify too), plus, from a stream of its own (default_rng([seed, 0xF0])):
+  * class eps_to_1e-6 as drawn in one scene of four, redrawn as U[0, limit) elsewhere: where it stands, the bar of I is the
+    reference's own cancellation noise (`cancel`, below) at 5 - 74 % of the covered pixels and a render is held to no more
+    than that; redrawn, most scenes have no such pixel (tests/test_forward_reference_cpu.py asserts: at least half);
+  * the exp regime, a third each: as drawn; "short", alpha and limit times f so that exp_rule = min(largest alpha, limit) x
+    longest cell edge = 0.124; "just_over", 0.126 (to_rule).  Below 0.125 the library takes every exp of a frame by a
+    10-term series without range reduction (csrc/frame.hip: small_exp_only; csrc/walk_common.hpp: exp_small_nonpositive)
+    if the frame also runs on "lds_stage" 2, "tile" 3 and at most 14 staged cells.  predicted_kernel says which walk that
+    rule selects; it is printed per state and counted - there is no read-out of the kernel that ran;
+  * the kernel variant: the product default (2, 0, 3) in half of the scenes with "stage_slots" 14 or 0 (by the frame
+    before) and "depth_split" 0, 1 or forced 2..7 with tilted planes, a third each; else one of fuzz_scenes.VARIANTS (21
+    slots where the variant says so); "transmittance_cutoff" 0 in half of the "integration" 1 scenes;
+  * the call form: render(); render_device + synchronize; three outstanding render_host_async frames into pinned images,
+    each waited for; render_frame_rows_async into full pinned frames where the layout is sharded;
+  * one transition of the state exp_rule reads, with the reference made again for every state; two frames after it and
+    two after going back:
+      scalars  from the short regime (the scene is brought there first if it is not) by update_scalars or
+               update_scalars_device (by the seed's parity, the way back by the other) to alpha x g with the largest a dz
+               of a segment at 1.75 (every other such scene: the median at 4), the limit raised first; and back;
+      limit    alpha scaled to a limit of 0.124 / L with class above_limit stretched to 14 x the limit (the top on the
+               cell with the longest chord of the view); set_alpha_limit to the top alpha (the rule at 1.74), and back;
+      points   the context is uploaded with the grid shrunk by 1/16 about its centroid and alpha for 0.124 there; the shrunk
+               grid must qualify itself (else the scene makes the limit transition and says so); update_points to the
+               drawn size (1.98: the longest edge is made again), and shrunk again.
+Layout, soup, solid and the late limit are derivative_scene's.  Three frames in a row of every part of the layout (the
+second may change the staged cells and the slab count from the first's statistics, the third reuses the per-view data),
+EVERY frame compared, every pixel of it:
+    tol_tau = 2^-23 |tau| + 1e-9 scale_tau + dz_err sens_tau + 2^-103
+    tol_I   = 2^-23 |I|   + 1e-9 scale_I   + dz_err sens_I + cancel (+ cutoff) + 2^-103                       (forward_ratio)
+  with forward_of's terms: scale_tau = sum dz |alpha| and sens_tau = sum F |alpha| (the raw alpha), scale_I = sum T |Q| S,
+  sens_I = sum F T E |Q - a I_prev| (dI / d dz, the motion tangent's chord derivative), cancel = 8 x 2^-53 sum T (|Q| + a |I_prev|)
+  / a, the rounding of the reference's own step C = Q - a I; I = (Q - C e) / a (derived in forward_of's docstring: the
+  oracle's fp32 image is at 0.49 of the bar with it and at 2e7 without), and cutoff = c sum |Q| S on "integration" 1 with a
+  "transmittance_cutoff" c (what the early-out may drop).  2^-23, 1e-9, dz_err and F are the ones above.  A pixel without a
+  segment is exactly 0 in both channels, the NaN pixels are exactly the port oracle's solid-marked ones, stats() report
+  the reference's segments and covered pixels of the part's rows (with a solid: the oracle's marked pixels; the reference's
+  own counts then depend on the order its threads bin in, line.cpp:29-67) and walk_overflow 0.  None of it is fitted to
+  what the GPU returns.  Reported, not asserted: how many fp32 values of the frames on "integration" 0 with whole rays
+  are not the port oracle's bit for bit.  What the first runs found is in profiles/forward_fuzz.md.
 """
 import os
 import sys
@@ -118,6 +161,9 @@ _CLASS_P = (0.05, 0.04, 0.08, 0.05, 0.03, 0.03, 0.10, 0.62)
 KINDS = ("tangent", "tangent_batch", "adjoint", "adjoint_batch", "gn_product", "gn_diagonal")
 GEOMETRY_KINDS = ("motion_tangent", "vertex_tangent", "vertex_adjoint", "vertex_adjoint_rerun", "ray_matrix", "duality")
 WALK_OPTIONS = (("depth_split", 2), ("integration", 1))
+FORWARD_KINDS = ("render", "render_device", "host_async", "frame_rows", "split", "front_to_back", "after_update_scalars",
+                 "after_set_limit", "after_update_points")
+DEFAULT_VARIANT = (2, 0, 3)
 
 
 def alpha_class(alpha, limit):
@@ -244,10 +290,11 @@ def dz_err(s):
     return 16.0 * 2.0 ** -52 * max(1.0, float(np.abs(ar.rotate(s.xyz, s.rots)).max()))
 
 
-def ratio(got, ref, scale, sens, dz_e, r_out=0.0, r_scale=R64):
-    """error / tolerance per element (docstring: the bar); a value that is not finite counts as infinitely wrong."""
+def ratio(got, ref, scale, sens, dz_e, r_out=0.0, r_scale=R64, extra=0.0):
+    """error / tolerance per element (docstring: the bar); a value that is not finite counts as infinitely wrong.  extra:
+    further absolute terms of the bar (the forward sweep's cancel and cutoff)."""
     got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    tol = r_out * np.abs(ref) + r_scale * scale + dz_e * sens + (ABS_FLOOR_32 if r_out else ABS_FLOOR)
+    tol = r_out * np.abs(ref) + r_scale * scale + dz_e * sens + extra + (ABS_FLOOR_32 if r_out else ABS_FLOOR)
     r = np.abs(got - ref) / tol
     return np.where(np.isfinite(got), r, np.inf)
 
@@ -825,6 +872,407 @@ def gpu_chords(s, pixel):
     return cell[sel], dz[sel], ga[cell[sel]], np.maximum(1.0, slope[sel])
 
 
+# ---- the forward sweep: the render itself, frame by frame --------------------------------------------------------------
+
+def longest_edge(xyz, cells):
+    """The longest edge of any cell (what the library multiplies the largest effective alpha with: csrc/grid.hip)."""
+    c = np.asarray(cells).reshape(-1, 4)
+    e = xyz[c[:, [0, 0, 0, 1, 1, 2]]] - xyz[c[:, [1, 2, 3, 2, 3, 3]]]
+    return float(np.sqrt((e ** 2).sum(-1)).max())
+
+
+def exp_rule(alpha, limit, L):
+    """min(largest alpha, limit) x longest edge: below 0.125 the library takes every exp of the frame by the short series
+    (csrc/frame.hip: small_exp_only; its own edge carries a margin of 1e-9, so 0.124 and 0.126 decide it)."""
+    return min(float(np.max(alpha)), float(limit)) * L
+
+
+def to_rule(alpha, limit, cls, L, target):
+    """alpha and limit times f so that exp_rule gives `target`; the classes that are defined by the limit (at it, the two
+    doubles next to it) made again from the new one.  Returns (alpha, limit)."""
+    f = target / exp_rule(alpha, limit, L)
+    alpha, limit = alpha * f, float(limit * f)
+    alpha[cls == 3] = limit
+    alpha[cls == 4] = np.nextafter(limit, np.inf)
+    alpha[cls == 5] = np.nextafter(limit, -np.inf)
+    return alpha, limit
+
+
+def forward_scene(seed):
+    """derivative_scene(seed), unchanged, with what the forward sweep adds drawn from a stream of its own (module
+    docstring: the forward sweep)."""
+    from tests.fuzz_scenes import VARIANTS
+    s = derivative_scene(seed)
+    rng = np.random.default_rng([seed, 0xF0])
+    n = len(s.cells)
+    s.L = longest_edge(s.xyz, s.cells)
+    s.cls = alpha_class(s.alpha, s.limit)
+    # -- class eps_to_1e-6: as drawn in one scene of four (there the bar of I is the reference's own cancellation noise)
+    s.keep_eps = bool(rng.integers(4) == 0)
+    redrawn = rng.uniform(0.0, 1.0, n) * s.limit
+    if not s.keep_eps:
+        s.alpha = np.where(s.cls == 2, redrawn, s.alpha)
+    # -- the exp regime
+    s.regime = ("as_drawn", "short", "just_over")[int(rng.integers(3))]
+    if s.regime != "as_drawn":
+        s.alpha, s.limit = to_rule(s.alpha.copy(), s.limit, s.cls, s.L, 0.124 if s.regime == "short" else 0.126)
+    # -- the kernel variant
+    s.depth_split, s.tilt, s.stage_slots = 0, (0.0, 0.0), 14
+    if rng.integers(2) == 0:
+        s.variant = DEFAULT_VARIANT
+        s.stage_slots = (14, 0)[int(rng.integers(2))]
+        k = int(rng.integers(3))
+        if k == 1:
+            s.depth_split = 1
+        elif k == 2:
+            s.depth_split = int(rng.integers(2, 8))
+            s.tilt = tuple(float(v) for v in rng.uniform(-1.5, 1.5, 2))
+    else:
+        s.variant = VARIANTS[int(rng.integers(len(VARIANTS)))]
+        if s.variant[0] == 3:
+            s.stage_slots = 21
+    s.cutoff = 0.0 if s.variant[1] == 1 and rng.integers(2) == 0 else None  # (None: the default, 1e-12)
+    # -- the call form and the transition
+    s.form = ("render", "render_device", "host_async")[int(rng.integers(3))]
+    if s.form == "host_async" and s.layout != "whole":
+        s.form = "frame_rows"
+    s.transition = ("scalars", "limit", "points")[int(rng.integers(3))]
+    s.subtle = bool(rng.integers(2) == 0)  # (scalars: the largest a dz to 1.75; else the median to 4)
+    s.device_update = bool(seed % 2)
+    s.stretch = rng.uniform(0.0, 1.0, n)
+    c = s.xyz.mean(0)
+    s.small = c + (s.xyz - c) / 16.0
+    return s
+
+
+def predicted_kernel(s, alpha, limit, L):
+    """The walk the documented rule selects for this state (csrc/walk_kernels.hip: launch_walk_t).  Predicted, not read
+    back: the library has no read-out of the kernel that ran."""
+    if s.soup:
+        return "bin_sort_resolve"
+    lds, order, tile = s.variant
+    short = exp_rule(alpha, limit, L) * (1.0 + 1e-9) < 0.125
+    if lds < 2:
+        return f"walk_composite{'_lds' if lds else ''}<{tile}, {order}>"
+    if tile != 3:
+        return f"walk_composite_lds<{tile}, {order}, dma, {21 if s.stage_slots == 21 else 14}>"
+    slots = {0: "14 or 21 by the frame before", 14: "14", 21: "21"}[s.stage_slots]
+    series = "SMALLEXP unless 21 slots" if short and s.stage_slots == 0 else "SMALLEXP" if short and s.stage_slots == 14 else "general exp"
+    split = "" if order else {0: ", SPLIT by the frame before", 1: ""}.get(s.depth_split, f", SPLIT {s.depth_split}")
+    return f"walk_composite_lds<3, {order}, dma, {slots}, {series}{split}>"
+
+
+def describe_forward(s):
+    return (describe(s) + f"; {s.regime}, variant {s.variant}, stage_slots {s.stage_slots}, depth_split {s.depth_split}"
+            + (", cutoff 0" if s.cutoff == 0.0 else "") + f", {s.form}, transition {s.transition}"
+            + (", eps class as drawn" if s.keep_eps else ""))
+
+
+class ForwardTally:
+    """What the forward sweep reports beside Worst: the fp32 values compared bit for bit with the port oracle's image
+    ("integration" 0, whole rays) and how many differ; per scene the share of covered pixels whose bar of I is dominated
+    by `cancel`; the kernels the rule predicted."""
+
+    def __init__(self):
+        self.bit_values = self.bit_differ = self.frames = 0
+        self.cancel_share = {}
+        self.kernels = {}
+
+    def lines(self):
+        none = sum(1 for v in self.cancel_share.values() if v == 0.0)
+        out = [f"{self.frames} frames compared; {self.bit_differ} of {self.bit_values} fp32 values (\"integration\" 0, whole rays) "
+               f"are not the port oracle's bit for bit",
+               f"covered pixels whose bar of I is dominated by cancel: none in {none} of {len(self.cancel_share)} scenes"]
+        out += [f"predicted {k}: {v} states" for k, v in sorted(self.kernels.items())]
+        return out
+
+
+def cancel_share(I, x, cov):
+    """The share of the covered pixels at which cancel exceeds 2^-23 |I| (forward_of's arrays of one frame; cov: the
+    pixels with a segment)."""
+    n = int(np.isfinite(I[cov]).sum())
+    return float((x["cancel"][cov] > R_OUT * np.abs(I[cov])).sum()) / max(n, 1)
+
+
+def forward_reference(s, xyz, alpha, limit, rows_ref, oracle, solid=None):
+    """One state's reference: forward_of's images and bounds of the rows rows_ref, the port oracle's fp32 image of those
+    rows, and the set of solid-marked pixels - the ORACLE'S, not the GPU's."""
+    rx, ry = s.res
+    kw = {} if solid is None else dict(solid_tets=solid, solid_colour=np.full(len(solid), np.nan))
+    o = oracle.render(xyz, s.cells, alpha, s.q, s.rots, rx, ry, B, alpha_limit=limit, threads=8, **kw)
+    img = o["image"][rows_ref]
+    skip = np.isnan(img[..., 0]) if solid is not None else None
+    m = ar.ray_matrices(xyz, s.cells, alpha, s.q, s.rots, rx, ry, B, limit, rows_ref)
+    tau, I, x = ar.forward_of(m, skip, with_scale=True)
+    seg_rows = m["valid"].sum(1).reshape(m["shape"]).sum(1)
+    cov = m["valid"].any(1).reshape(m["shape"])
+    return types.SimpleNamespace(tau=tau, I=I, x=x, skip=skip, covered=cov, oracle=img, seg_rows=seg_rows,
+                                 cov_rows=cov.sum(1), alpha=alpha, limit=limit, xyz=xyz)
+
+
+def forward_ratio(img, ref, dz_e, cutoff):
+    """error / tolerance of one frame [rows, res_x, 2] against forward_reference's state (module docstring: the forward
+    sweep's bar), and the mismatches that are not a matter of tolerance (strings)."""
+    bad = []
+    img = np.asarray(img)
+    nan = np.isnan(img)
+    skip = np.zeros(img.shape[:2], bool) if ref.skip is None else ref.skip
+    for ch, name in ((0, "tau"), (1, "I")):
+        if not np.array_equal(nan[..., ch], skip):
+            bad.append(f"{name}: the NaN pixels are not the oracle's solid-marked ones ({int((nan[..., ch] != skip).sum())} differ)")
+    empty = ~ref.covered & ~skip
+    if (img[empty] != 0).any():
+        bad.append(f"{int((img[empty] != 0).any(-1).sum())} pixels without a segment are not exactly 0")
+    x = ref.x
+    use = ~skip
+    got = np.where(use[..., None], img, 0.0)
+    extra_I = x["cancel"] + cutoff * x["emission"]
+    r = np.stack([ratio(got[..., 0], np.where(use, ref.tau, 0.0), x["scale_tau"], x["sens_tau"], dz_e, R_OUT),
+                  ratio(got[..., 1], np.where(use, ref.I, 0.0), x["scale_I"], x["sens_I"], dz_e, R_OUT, extra=extra_I)], axis=-1)
+    r[~use] = 0.0
+    return r, bad
+
+
+def _apply_variant(ctx, s):
+    lds, order, tile = s.variant
+    if s.soup:
+        ctx.set_option("algorithm", 1)
+    ctx.set_option("lds_stage", min(lds, 2))
+    ctx.set_option("stage_slots", s.stage_slots)
+    ctx.set_option("integration", order)
+    ctx.set_option("tile", tile)
+    ctx.set_option("depth_split", s.depth_split)
+    ctx.set_option("split_tilt_x", s.tilt[0])
+    ctx.set_option("split_tilt_y", s.tilt[1])
+    if s.cutoff is not None:
+        ctx.set_option("transmittance_cutoff", s.cutoff)
+
+
+def forward_frames(ctx, s, form, n_frames, parts, rows_ref, check_stats):
+    """n_frames frames in a row of every part of the layout through one call form.  Returns n_frames images of the rows
+    rows_ref, float32 [len(rows_ref), res_x, 2], the rows of the parts put back in place.  check_stats(part rows, frame):
+    called after every frame whose statistics can be read (the last of a burst of outstanding ones)."""
+    from course5_amd import capi
+    rx, ry = s.res
+    out = [np.full((len(rows_ref), rx, 2), np.float32(7e7), np.float32) for _ in range(n_frames)]
+    for place, where in parts:
+        if len(where) == 0:  # (a rank without rows: small images in tall tiles)
+            continue
+        place(ctx)
+        if form == "render":
+            for k in range(n_frames):
+                out[k][where] = ctx.render()
+                check_stats(where, k)
+        elif form == "render_device":
+            import torch
+            for k in range(n_frames):
+                t = torch.full((len(where), rx, 2), float("nan"), dtype=torch.float32, device="cuda")
+                for _ in range(3):
+                    ctx.render_device(t.data_ptr())
+                    if ctx.synchronize() == capi.C5_OK:
+                        break
+                else:
+                    raise RuntimeError("C5_RETRY three times in a row")
+                out[k][where] = t.cpu().numpy()
+                check_stats(where, k)
+        else:  # outstanding frames into pinned host memory, each waited for
+            full = form == "frame_rows"
+            bufs = [ctx.host_image(full=full) for _ in range(n_frames)]
+            try:
+                for _ in range(3):
+                    for b in bufs:
+                        b[...] = np.float32(7e7)
+                        (ctx.render_frame_rows_async if full else ctx.render_host_async)(b)
+                    if all([ctx.render_host_wait() == capi.C5_OK for _b in bufs]):
+                        break
+                else:
+                    raise RuntimeError("C5_RETRY three times in a row")
+                check_stats(where, n_frames - 1)
+                for k, b in enumerate(bufs):
+                    out[k][where] = b[rows_ref[where]] if full else b
+            finally:
+                for b in bufs:
+                    ctx.free_host_image(b)
+    return out
+
+
+def check_forward(s, worst, oracle, tally=None, log=print):
+    """The forward render of one used scene (forward_scene, qualify first) in a context of its own, frame by frame: three
+    frames of the scene's configuration, one transition, two frames after it and two after going back.  Returns the
+    mismatches, strings."""
+    from course5_amd import capi
+    tally = tally if tally is not None else ForwardTally()
+    bad = []
+    rx, ry = s.res
+    lds, order, tile = s.variant
+    e = dz_err(s)  # (the drawn grid's: the shrunk one's coordinates are no larger)
+    cutoff = (1e-12 if s.cutoff is None else s.cutoff) if order == 1 and not s.soup else 0.0
+    whole_rays = s.soup or order == 1 or s.depth_split == 1 or not (lds >= 2 and tile == 3)
+    base_kind = "front_to_back" if order == 1 and not s.soup else "split" if not whole_rays and s.depth_split >= 2 else s.form
+    # -- the states: (xyz, alpha, limit) the context starts in, goes to, and comes back to
+    transition = s.transition
+    counts = (s.n_segments, s.n_covered)
+    if transition == "points":
+        small = types.SimpleNamespace(**vars(s))
+        small.xyz = s.small
+        small.alpha, small.limit = to_rule(s.alpha.copy(), s.limit, s.cls, s.L / 16.0, 0.124)
+        small.segments = ar.segment_lists(small.xyz, s.cells, s.rots, rx, ry, B, with_slope=True)
+        why = qualify(small, oracle)
+        if why is None:
+            start = (small.xyz, small.alpha, small.limit)
+            there = (s.xyz, small.alpha, small.limit)
+            counts = (small.n_segments, small.n_covered)
+        else:
+            log(f"seed {s.seed}: the shrunk grid does not qualify ({why}): the limit transition instead")
+            transition = "limit"
+    if transition == "scalars":
+        start = (s.xyz, s.alpha, s.limit)
+        a_short, l_short = (s.alpha, s.limit) if s.regime == "short" else to_rule(s.alpha.copy(), s.limit, s.cls, s.L, 0.124)
+        cell, dz = s.segments[1], s.segments[3]
+        x = a_short[cell] * dz  # (the limit is raised to the largest alpha: nothing is clamped)
+        g = 1.75 / float(x.max()) if s.subtle else 4.0 / max(float(np.median(x[x > 0])) if (x > 0).any() else 1.0, 1e-300)
+        a_big = a_short * g
+        there, back = (s.xyz, a_big, max(l_short, float(a_big.max()))), (start if s.regime == "short" else (s.xyz, a_short, l_short))
+    elif transition == "limit":
+        start = (s.xyz, s.alpha, s.limit)
+        l_small = 0.124 / s.L
+        a = s.alpha * (l_small / s.limit)
+        a[s.cls == 3], a[s.cls == 4], a[s.cls == 5] = l_small, np.nextafter(l_small, np.inf), np.nextafter(l_small, -np.inf)
+        a[s.cls == 6] = l_small * (1.0 + 13.0 * s.stretch[s.cls == 6])
+        chord = np.zeros(len(a))  # (the top alpha to the cell with the longest chord of this view, of its class if it has one)
+        np.maximum.at(chord, s.segments[1], s.segments[3])
+        a[int(np.argmax(np.where(s.cls == 6, chord, -1.0) if (s.cls == 6).any() else chord))] = 14.0 * l_small
+        there, back = (s.xyz, a, float(a.max())), (s.xyz, a, l_small)
+    elif transition == "points":
+        back = start
+
+    solid = _solid_of(s) if s.solid else None
+    if s.layout == "range":
+        b, c = s.row_range
+        rows_ref = np.arange(b, b + c)
+        parts = [(lambda x: x.set_row_range(b, c), np.arange(c))]
+    elif s.layout == "cyclic":
+        rows_ref = np.arange(ry)
+        parts = [((lambda x, r=r: x.set_row_tiles(s.tile_rows, r, s.world)), sharding.local_rows(ry, s.tile_rows, r, s.world))
+                 for r in range(s.world)]
+    else:
+        rows_ref = np.arange(ry)
+        parts = [(lambda x: None, np.arange(ry))]
+
+    def hold(images, ref, kind, what):
+        name = predicted_kernel(s, ref.alpha, ref.limit, longest_edge(ref.xyz, s.cells))
+        tally.kernels[name] = tally.kernels.get(name, 0) + 1
+        log(f"seed {s.seed} {what}: rule {exp_rule(ref.alpha, ref.limit, longest_edge(ref.xyz, s.cells)):.4g}, predicted {name}")
+        for k, img in enumerate(images):
+            r, wrong = forward_ratio(img, ref, e, cutoff)
+            bad.extend(f"{kind} {what} frame {k}: {t}" for t in wrong)
+            top = worst.add(kind, r, s.seed, f"{what} frame {k}")
+            tally.frames += 1
+            if not top <= 1.0:
+                i = np.unravel_index(int(np.argmax(r)), r.shape)
+                bad.append(f"{kind} {what} frame {k}: {int((~(r <= 1.0)).sum())} values beyond the bar, worst error / tol {top:.3g} "
+                           f"at (row, col, channel) {tuple(int(v) for v in i)}")
+            if whole_rays and (order == 0 or s.soup):
+                use = ~np.isnan(ref.oracle)
+                tally.bit_values += int(use.sum())
+                tally.bit_differ += int((_bits(img)[use] != _bits(ref.oracle)[use]).sum())
+
+    with capi.Context(0) as ctx:
+        _apply_variant(ctx, s)
+        ctx.upload_grid(start[0], s.cells, start[1], s.q)
+        ctx.set_image(rx, ry, B)
+        ctx.set_view(s.rots)
+        if not s.late_limit:
+            ctx.set_alpha_limit(start[2])
+        ctx.render()
+        st = ctx.stats()
+        if (st["segments"], st["covered_pixels"]) != counts:
+            bad.append(f"stats: {st['segments']} segments on {st['covered_pixels']} pixels, the reference has {counts[0]} on {counts[1]}")
+        if s.late_limit:
+            ctx.set_alpha_limit(start[2])
+        if solid is not None:
+            ctx.set_solid(0, solid)
+
+        def frames(ref, n_frames, kind, what):
+            def check_stats(where, k):
+                st = ctx.stats()
+                want = (int(ref.seg_rows[where].sum()), int(ref.cov_rows[where].sum()))
+                # (with a solid the reference's own counts depend on the order its threads bin in: line.cpp:29-67 drops the
+                # hits of a pixel that is marked already; the marked pixels themselves are exact)
+                if solid is None and (st["segments"], st["covered_pixels"]) != want:
+                    bad.append(f"{kind} {what} frame {k}: stats report {st['segments']} segments on {st['covered_pixels']} pixels, "
+                               f"the reference has {want[0]} on {want[1]}")
+                if solid is not None and st["solid_pixels"] != int(ref.skip[where].sum()):
+                    bad.append(f"{kind} {what} frame {k}: stats report {st['solid_pixels']} solid pixels, the oracle marks {int(ref.skip[where].sum())}")
+                if st["walk_overflow"] != 0:
+                    bad.append(f"{kind} {what} frame {k}: walk_overflow {st['walk_overflow']}")
+            hold(forward_frames(ctx, s, s.form, n_frames, parts, rows_ref, check_stats), ref, kind, what)
+
+        ref0 = forward_reference(s, *start, rows_ref, oracle, solid)
+        tally.cancel_share[s.seed] = cancel_share(ref0.I, ref0.x, ref0.covered)
+        log(f"seed {s.seed}: cancel dominates the bar of I at {100 * tally.cancel_share[s.seed]:.1f} % of the covered pixels")
+        frames(ref0, 3, base_kind, "as uploaded")
+
+        def scalars(alpha, device):
+            if device:
+                import torch
+                ctx.update_scalars_device(torch.tensor(alpha, dtype=torch.float64, device="cuda"),
+                                          torch.tensor(s.q, dtype=torch.float64, device="cuda"))
+            else:
+                ctx.update_scalars(alpha, s.q)
+
+        ref_there = forward_reference(s, *there, rows_ref, oracle, solid)
+        ref_back = ref0 if back is start else forward_reference(s, *back, rows_ref, oracle, solid)
+        if transition == "scalars":
+            kind = "after_update_scalars"
+            if back is not start:
+                scalars(back[1], not s.device_update)
+                ctx.set_alpha_limit(back[2])
+                frames(ref_back, 2, kind, "brought to the short regime")
+            ctx.set_alpha_limit(there[2])  # (raised first where it would clamp)
+            scalars(there[1], s.device_update)
+            frames(ref_there, 2, kind, "after update_scalars" + ("_device" if s.device_update else ""))
+            scalars(back[1], not s.device_update)
+            ctx.set_alpha_limit(back[2])
+            frames(ref_back, 2, kind, "back in the short regime by update_scalars" + ("" if s.device_update else "_device"))
+        elif transition == "limit":
+            kind = "after_set_limit"
+            scalars(back[1], s.device_update)
+            ctx.set_alpha_limit(back[2])
+            frames(ref_back, 2, kind, "at the small limit")
+            ctx.set_alpha_limit(there[2])
+            frames(ref_there, 2, kind, "after set_alpha_limit to the top alpha")
+            ctx.set_alpha_limit(back[2])
+            frames(ref_back, 2, kind, "back at the small limit")
+        else:
+            kind = "after_update_points"
+            ctx.update_points(there[0])
+            frames(ref_there, 2, kind, "after update_points to the drawn size")
+            ctx.update_points(back[0])
+            frames(ref_back, 2, kind, "shrunk again")
+    return bad
+
+
+def forward_main():
+    import torch  # noqa: F401  (HIP runtime load order)
+    from oracle.pyoracle import Oracle
+    n_scenes = int(sys.argv[1]) if len(sys.argv) > 1 else 40
+    seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 3000
+    worst, tally, oracle = Worst(FORWARD_KINDS), ForwardTally(), Oracle("port")
+    t0 = time.time()
+    log = lambda t: print(t, flush=True)  # noqa: E731
+    used, skipped, mismatches = run(range(seed0, seed0 + n_scenes), oracle, worst, log=log, draw=forward_scene,
+                                    check=lambda s, w: check_forward(s, w, oracle, tally, log))
+    print(f"{n_scenes} seeds from {seed0}: {used} used, {skipped} skipped, {len(mismatches)} mismatches, "
+          f"{worst.elements} elements compared, {time.time() - t0:.0f} s")
+    for line in worst.lines() + tally.lines():
+        print(line)
+    too_many = skipped > 0.1 * n_scenes
+    if too_many:
+        print("more than 10 % of the seeds were skipped")
+    return 1 if mismatches or too_many else 0
+
+
 def describe(s):
     return (f"{len(s.cells)} cells, {s.res[0]}x{s.res[1]}, limit {s.limit:.4g}, {s.mode}, {s.layout}, K {s.k}"
             + (", soup" if s.soup else "") + (", solid" if s.solid else "") + (", device" if s.device else "")
@@ -848,7 +1296,8 @@ def run(seeds, oracle, worst, log=print, draw=None, check=None):
         used += 1
         for text in check(s, worst):
             mismatches.append((seed, text))
-            log(f"seed {seed} ({describe_geometry(s) if hasattr(s, 'motion') else describe(s)}): {text}")
+            about = describe_geometry(s) if hasattr(s, "motion") else describe_forward(s) if hasattr(s, "regime") else describe(s)
+            log(f"seed {seed} ({about}): {text}")
     return used, skipped, mismatches
 
 
@@ -860,6 +1309,9 @@ def main():
         for c, d, got, f in zip(*gpu_chords(s, int(sys.argv[3]))):
             print(f"cell {c}: dz {d:.6g}, GPU - reference {got - d:+.3g} = {(got - d) / dz_err(s):+.2f} dz_err, F {f:.1f}")
         return 0
+    if len(sys.argv) > 1 and sys.argv[1] == "forward":
+        del sys.argv[1]
+        return forward_main()
     geometry = len(sys.argv) > 1 and sys.argv[1] == "geometry"
     if geometry:
         del sys.argv[1]

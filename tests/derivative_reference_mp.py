@@ -1,5 +1,5 @@
-"""80-digit reference of the derivative renders (include/course5_hip.h: c5_render_tangent, c5_render_adjoint,
-c5_render_gn_product, c5_render_gn_diagonal) from per-pixel segment lists, in mpmath.
+"""80-digit reference of the forward render (c5_render: forward) and of the derivative renders (include/course5_hip.h:
+c5_render_tangent, c5_render_adjoint, c5_render_gn_product, c5_render_gn_diagonal) from per-pixel segment lists, in mpmath.
 
 The per-segment terms are evaluated AS THE HEADER AND line.cpp:176-227 STATE THEM - no series, no threshold at
 a dz = 1/8, no expm1: at 80 digits the cancellation of (1 - E) / a and of the bracket does not matter down to
@@ -60,7 +60,7 @@ class Segments:
                 c = int(cell[k])
                 a_raw = float(alpha[c])
                 a = min(a_raw, limit)
-                t = dict(c=c, d=mpf(float(dz[k])), Q=mpf(float(q[c])), active=not a < EPS, moves=False, a=zero, E=one, s=zero,
+                t = dict(c=c, d=mpf(float(dz[k])), a_raw=mpf(a_raw), Q=mpf(float(q[c])), active=not a < EPS, moves=False, a=zero, E=one, s=zero,
                          B=zero, I_prev=I, F=mpf(1.0 if slope is None else max(1.0, float(slope[k]))))
                 if t["active"]:
                     d, Q, am = t["d"], t["Q"], mpf(a)
@@ -78,6 +78,30 @@ class Segments:
                     t["abs_da"] = T * (abs(t["B"]) + d * E * abs(I_prev))
                 T = T * E
             self.rays.append(ray)
+
+
+def forward(seg: Segments):
+    """The forward render per pixel of seg.pixels: (tau, I, scale_tau, scale_I, sens_tau, sens_I, cancel), fp64 arrays -
+    tau = sum dz_k alpha_k (raw alpha), I the recurrence's last value, and the bounds adjoint_reference.forward_of states:
+    the absolute sums, the chord sensitivities sum F_k |alpha_k| and sum F_k T_k E_k |Q_k - a_k I_{k-1}|, and the rounding of
+    the reference's own step, 8 x 2^-53 sum T_k (|Q_k| + a_k |I_{k-1}|) / a_k."""
+    out = np.zeros((7, len(seg.pixels)))
+    c8 = mpf(8) * mpf(2) ** -53
+    for i, ray in enumerate(seg.rays):
+        tau = scale_tau = sens_tau = scale_I = sens_I = cancel = I = mpf(0)
+        for t in ray:
+            tau += t["d"] * t["a_raw"]
+            scale_tau += t["d"] * abs(t["a_raw"])
+            sens_tau += t["F"] * abs(t["a_raw"])
+            if not t["active"]:
+                continue
+            a, Q, E, I_prev, T = t["a"], t["Q"], t["E"], t["I_prev"], t["T"]
+            I = E * I_prev + Q * t["s"]
+            scale_I += T * abs(Q) * t["s"]
+            sens_I += t["F"] * T * E * abs(Q - a * I_prev)
+            cancel += c8 * T * (abs(Q) + a * abs(I_prev)) / a
+        out[:, i] = [float(v) for v in (tau, I, scale_tau, scale_I, sens_tau, sens_I, cancel)]
+    return out
 
 
 def tangent(seg: Segments, d_alpha, d_q):

@@ -46,6 +46,24 @@ def hanging_node_grid():
     return xyz, cells
 
 
+# g9: g2's three views and the oblique one from behind
+THIN_VIEWS = VIEWS + ((0.37, -0.61),)
+
+
+def thin_alpha(xyz, cells, alpha):
+    """(alpha, limit) of g9: min(largest alpha, limit) x longest cell edge = 0.1, below the 1/8 at which the walk takes
+    every exp of a frame by its short series (csrc/frame.hip: small_exp_only) - no other fixture is.  The limit is
+    0.1 / longest edge (0.1 with a limit of 2.5 would leave no cell above the limit); every 17th cell at 0, every 23rd
+    between 1.5 and 3.5 x the limit, the others g2's alpha scaled to end just below the limit."""
+    c = np.asarray(cells).reshape(-1, 4)
+    e = xyz[c[:, [0, 0, 0, 1, 1, 2]]] - xyz[c[:, [1, 2, 3, 2, 3, 3]]]
+    limit = 0.1 / float(np.sqrt((e ** 2).sum(-1)).max())
+    a = alpha / alpha.max() * (0.999 * limit)
+    a[::17] = 0.0
+    a[5::23] = limit * (1.5 + 2.0 * (np.arange(len(a[5::23])) % 5) / 4.0)
+    return a, limit
+
+
 def main():
     only = tuple(sys.argv[1:])
     ref = Oracle("reference")
@@ -73,6 +91,11 @@ def main():
     xyz, cells = hanging_node_grid()
     a, q = mg.scalars(len(cells), seed=4)
     fixtures.append(("g8_hanging_nodes_120x90", xyz, cells, a, q, 120, 90, 2.5, 1, HANGING_VIEWS))
+
+    # G9: the G2 grid in the regime of the short exp series (thin_alpha)
+    xyz, cells, a, q = mg.workload("g2")
+    a9, limit9 = thin_alpha(xyz, cells, a)
+    fixtures.append(("g9_kuhn4_thin_120x90", xyz, cells, a9, q, 120, 90, limit9, 1, THIN_VIEWS))
 
     for fx in fixtures:
         name, xyz, cells, a, q, rx, ry, limit, stride = fx[:9]
