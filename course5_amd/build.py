@@ -26,7 +26,11 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wex
 LIB_SOURCES = [
     ("exact_kernels.hip", ["-ffp-contract=off"]),   # must round like the reference's host build
     ("walk_kernels.hip", []),
-    ("adjoint_kernels.hip", ["-munsafe-fp-atomics"]),  # fp64 atomicAdd as global_atomic_add_f64, no compare-and-swap loop
+    # the derivative renders; fp64 atomicAdd as global_atomic_add_f64, no compare-and-swap loop: the same flag for all
+    # three, so that no kernel's code depends on which file it is in
+    ("scalar_derivative_kernels.hip", ["-munsafe-fp-atomics"]),
+    ("geometry_derivative_kernels.hip", ["-munsafe-fp-atomics"]),
+    ("ray_matrix_kernels.hip", ["-munsafe-fp-atomics"]),
     # the C ABI, host code only (context.hpp)
     ("context.hip", []),
     ("grid.hip", []),

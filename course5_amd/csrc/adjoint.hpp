@@ -1,6 +1,7 @@
-// Host-callable launchers of the adjoint render (adjoint_kernels.hip): gradients of the image with respect to the cells'
-// alpha and Q; and of the tangent render: the image's change for a change of them.  All launches are asynchronous on the
-// given stream.
+// Host-callable launchers of the derivative renders.  scalar_derivative_kernels.hip: the adjoint (gradients of the image
+// with respect to the cells' alpha and Q), the tangent (the image's change for a change of them), their batches and the
+// Gauss-Newton renders; geometry_derivative_kernels.hip: the motion tangent, the vertex adjoint and the vertex tangent;
+// ray_matrix_kernels.hip: the ray matrix.  All launches are asynchronous on the given stream.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -11,6 +12,18 @@
 #include "kernels.hpp"
 
 namespace c5 {
+
+// What every *_resolve kernel reads ("algorithm" 1): bin_sort_resolve's per-pixel segment lists of launch_bin_fill, which
+// the kernel sorts in place, over the view's grid and image.
+struct ResolveParams {
+    GridView g;
+    ImageParams im;
+    const double *Xtab, *Ytab;  // the pixels' view-space coordinates (the kernels that look faces up)
+    const int64_t* offs;        // [n_local_px + 1] a pixel's list: segs[offs[p] .. offs[p + 1])
+    void* segs;
+    const uint32_t* mask;       // solid-marked pixels, or nullptr
+    double alpha_limit;
+};
 
 struct AdjointParams {
     // the walk's inputs, as walk_composite reads them (records built with "integration" 0: the reference's order)
@@ -26,8 +39,7 @@ struct AdjointParams {
 void launch_adjoint_walk(hipStream_t s, const AdjointParams& a, int pass);
 
 // bin_sort_resolve's twin: the per-pixel segment lists of launch_bin_fill -> grad_a / grad_q (device order)
-void launch_adjoint_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const int64_t* offs, void* segs,
-                            const uint32_t* mask, double alpha_limit, const float2* grad_out, double* grad_a, double* grad_q);
+void launch_adjoint_resolve(hipStream_t s, const ResolveParams& r, const float2* grad_out, double* grad_a, double* grad_q);
 
 // out[perm[i]] = dev[i] for both arrays (perm nullptr: the identity)
 void launch_adjoint_permute(hipStream_t s, const double* ga_dev, const double* gq_dev, const int32_t* perm, int64_t n,
@@ -50,10 +62,10 @@ void launch_tangent_gather(hipStream_t s, const double* d_alpha, const double* d
 void launch_tangent_walk(hipStream_t s, const TangentParams& t);
 
 // the tangent over bin_sort_resolve's lists (sorts them in place, as launch_adjoint_resolve)
-void launch_tangent_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const int64_t* offs, void* segs,
-                            const uint32_t* mask, double alpha_limit, const double2* dir, float2* out);
+void launch_tangent_resolve(hipStream_t s, const ResolveParams& r, const double2* dir, float2* out);
 
-// bytes of one segment of the bin-sort lists as this file reads them (c_api.hip checks it against segment_bytes())
+// bytes of one segment of the bin-sort lists as the *_resolve kernels read them (deriv_lists.hpp: AdjSegment;
+// derivatives.hip checks it against segment_bytes())
 size_t adjoint_segment_bytes();
 
 // ---- batches (c5_render_tangent_batch*, c5_render_adjoint_batch*): one walk per ray for up to kc directions or upstream
@@ -118,8 +130,7 @@ void launch_gn_diag_walk(hipStream_t s, const AdjointParams& a);
 void launch_gn_weight(hipStream_t s, const float2* t, const float2* w, int64_t n_px, int n_imgs, float2* g);
 
 // launch_adjoint_resolve's twin for the diagonal
-void launch_gn_diag_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const int64_t* offs, void* segs,
-                            const uint32_t* mask, double alpha_limit, const float2* weight, double* diag_a, double* diag_q);
+void launch_gn_diag_resolve(hipStream_t s, const ResolveParams& r, const float2* weight, double* diag_a, double* diag_q);
 
 // ---- motion tangent (c5_render_motion_tangent*): the frame differentiated with respect to an affine motion of the grid in
 // view space, u(p) = A p + b
@@ -148,9 +159,7 @@ struct MotionParams {
 void launch_motion_walk(hipStream_t s, int kc, const MotionParams& m);
 
 // the same over bin_sort_resolve's lists, one field (sorts them in place, as launch_tangent_resolve)
-void launch_motion_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const double* Xtab, const double* Ytab,
-                           const int64_t* offs, void* segs, const uint32_t* mask, double alpha_limit, const MotionField& field,
-                           float2* out);
+void launch_motion_resolve(hipStream_t s, const ResolveParams& r, const MotionField& field, float2* out);
 
 // ---- vertex adjoint (c5_render_vertex_adjoint*): the gradient of the frame with respect to the grid's points.  With
 // G_k = d loss / d dz_k of a segment and lambda the barycentric coordinates of the pixel in the two faces the chord runs
@@ -170,9 +179,7 @@ struct VertexParams {
 void launch_vertex_walk(hipStream_t s, const VertexParams& v, bool merge);
 
 // the same over bin_sort_resolve's lists (sorts them in place, as launch_adjoint_resolve)
-void launch_vertex_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const double* Xtab, const double* Ytab,
-                           const int64_t* offs, void* segs, const uint32_t* mask, double alpha_limit, const float2* grad_out,
-                           double* face_w);
+void launch_vertex_resolve(hipStream_t s, const ResolveParams& r, const float2* grad_out, double* face_w);
 
 // face_w -> grad_view[n_pts][3] (zeroed by the caller; accumulated per cell and face, edge-on faces skipped), then
 // grad_xyz[v] = M^T grad_view[v] for every point, M the linear part of the view R
@@ -203,9 +210,7 @@ struct VertexTangentParams {
 void launch_vertex_tangent_walk(hipStream_t s, int kc, const VertexTangentParams& v);
 
 // the same over bin_sort_resolve's lists for field j of u_view [n_pts][kc][3] (sorts them in place, as launch_tangent_resolve)
-void launch_vertex_tangent_resolve(hipStream_t s, const GridView& g, const ImageParams& im, const double* Xtab, const double* Ytab,
-                                   const int64_t* offs, void* segs, const uint32_t* mask, double alpha_limit, const double* u_view,
-                                   int kc, int j, float2* out);
+void launch_vertex_tangent_resolve(hipStream_t s, const ResolveParams& r, const double* u_view, int kc, int j, float2* out);
 
 // ---- ray matrix (c5_ray_matrix_*): per pixel the cells its ray crosses and the chord of each crossing, as CSR arrays
 
@@ -228,10 +233,8 @@ struct RayMatrixParams {
 void launch_segment_walk(hipStream_t s, const RayMatrixParams& m, int pass);
 
 // the same over bin_sort_resolve's lists: the count, and the fill (sorts them in place, as launch_adjoint_resolve)
-void launch_segment_count_resolve(hipStream_t s, const ImageParams& im, const int64_t* offs, const void* segs, const uint32_t* mask,
-                                  int32_t* count);
-void launch_segment_fill_resolve(hipStream_t s, const ImageParams& im, const int64_t* offs, void* segs, const uint32_t* mask,
-                                 const RayMatrixParams& m);
+void launch_segment_count_resolve(hipStream_t s, const ResolveParams& r, int32_t* count);
+void launch_segment_fill_resolve(hipStream_t s, const ResolveParams& r, const RayMatrixParams& m);
 
 // c5_update_scalars_device: alpha[i] = alpha_src[perm[i]], q[i] = q_src[perm[i]] (perm nullptr: the identity), and into
 // stats[3] (zeroed by the caller): the bits of the largest alpha > 0, the complemented bits of the smallest alpha >=

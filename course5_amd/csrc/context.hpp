@@ -264,7 +264,7 @@ struct c5_context {
     c5_stats last{};
 
     // adjoint render (c5_render_adjoint*): nothing of it is allocated before the first adjoint call
-    c5api::DeviceBuffer adj_lambda;    // [n_local_px] fp64: pass 1 -> pass 2 (adjoint_kernels.hip)
+    c5api::DeviceBuffer adj_lambda;    // [n_local_px] fp64: pass 1 -> pass 2 (scalar_derivative_kernels.hip)
     c5api::DeviceBuffer adj_counters;  // the adjoint's own FrameCounters: a frame's statistics and failure words stay the frame's
     c5api::DeviceBuffer adj_sticky;    // the entry raster's failure words for the adjoint (never the frames' sticky words)
     c5api::DeviceBuffer adj_grad;      // [2][n_cells] fp64, device order
@@ -276,11 +276,11 @@ struct c5_context {
 
     // tangent render (c5_render_tangent*): shares the adjoint's counters, sticky and status words and adj_perm; nothing of
     // it is allocated before the first tangent call
-    c5api::DeviceBuffer tan_dir;  // [n_cells] {dalpha, dQ} fp64, device order (adjoint_kernels.hip: tangent_gather)
+    c5api::DeviceBuffer tan_dir;  // [n_cells] {dalpha, dQ} fp64, device order (scalar_derivative_kernels.hip: tangent_gather)
 
     // batches (c5_render_tangent_batch*, c5_render_adjoint_batch*): nothing of it is allocated before the first batch call
     int batch_width = 0;    // "batch_width": directions or upstream images per walk (0: 4 for batches of up to 4, else 8)
-    c5api::DeviceBuffer bat_dirs;  // [n_cells][width] {dalpha, dQ} fp64, device order (adjoint_kernels.hip: tangent_gather_batch)
+    c5api::DeviceBuffer bat_dirs;  // [n_cells][width] {dalpha, dQ} fp64, device order (scalar_derivative_kernels.hip: tangent_gather_batch)
     c5api::DeviceBuffer bat_grad;  // [n_cells][2 width] fp64, device order (adjoint_walk_batch)
     // Gauss-Newton renders (c5_render_gn_product*, c5_render_gn_diagonal*): nothing of it is allocated before the first call
     c5api::DeviceBuffer gn_g;      // [width][n_local_px] float2: pass A's w * J v, pass B's upstream images (a chunk's)

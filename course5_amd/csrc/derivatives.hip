@@ -1,10 +1,10 @@
 // ------------------------------------------------------------------------------------------
-// Derivative renders (c5_render_adjoint*, c5_render_tangent*; adjoint_kernels.hip): the frame c5_render would produce now,
-// differentiated with respect to the cells' alpha and Q.  Both share one per-view setup on the context's stream into slot
-// 0's buffers - records of "integration" 0 (the reference's order, whatever the option says), whole rays (no
-// "depth_split"), the entry lists, the solid mask; or bin_sort_resolve's lists - then run their own kernels.  They leave
-// the options alone and the frames' statistics and failure words too (counters and sticky words of their own); the slot's
-// per-view data are marked stale, so the next frame builds its own ("view_cache").
+// Derivative renders (scalar_derivative_kernels.hip, geometry_derivative_kernels.hip, ray_matrix_kernels.hip): the frame
+// c5_render would produce now, differentiated.  All share one per-view setup on the context's stream into slot 0's buffers -
+// records of "integration" 0 (the reference's order, whatever the option says), whole rays (no "depth_split"), the entry
+// lists, the solid mask; or bin_sort_resolve's lists - then run their own kernels.  They leave the options alone and the
+// frames' statistics and failure words too (counters and sticky words of their own); the slot's per-view data are marked
+// stale, so the next frame builds its own ("view_cache").
 // ------------------------------------------------------------------------------------------
 #include "context.hpp"
 
@@ -18,9 +18,10 @@ struct DerivativeView {
     hipStream_t s = nullptr;        // the context's stream: everything of a derivative runs on it
     int64_t n_px = 0, padded = 0;   // pixels of the context's rows; rounded up to the scan's 1024
     const int32_t* perm = nullptr;  // cell_perm on the device (device order -> the caller's), or nullptr: the identity
-    c5::GridView g{};
     const uint32_t* mask = nullptr;  // solid-marked pixels, or nullptr
     c5::WalkParams w{};
+    c5::ResolveParams r{};     // (bin_sort) what every *_resolve kernel reads
+    c5::MotionGeometry geo{};  // the cells' vertices in view space
 };
 
 int setup_derivative(c5_context* ctx, DerivativeView& v) {
@@ -57,7 +58,8 @@ int setup_derivative(c5_context* ctx, DerivativeView& v) {
     c5::FrameCounters* const counters = ctx->adj_counters.as<c5::FrameCounters>();
     C5_HIP(ctx, hipMemsetAsync(ctx->adj_sticky.ptr, 0, kStickyWords * sizeof(unsigned), s));
 
-    c5::GridView& g = v.g = grid_view(ctx, fs);
+    const c5::GridView g = grid_view(ctx, fs);
+    v.geo = c5::MotionGeometry{g.cell_vert, g.vx, g.vy, g.vz};
     // the slot's per-view data are about to hold the derivative's: no frame may take them for its own
     fs.setup_epoch = 0;
     fs.setup_kept = false;
@@ -74,6 +76,8 @@ int setup_derivative(c5_context* ctx, DerivativeView& v) {
         rc = enqueue_solids(ctx, fs, 0, s, table, any_solid);
         if (rc) return rc;
         v.mask = any_solid ? fs.mask.as<uint32_t>() : nullptr;
+        v.r = c5::ResolveParams{g, im, ctx->xtab.as<double>(), ctx->ytab.as<double>(), ctx->offs64.as<int64_t>(), ctx->segs.ptr,
+                                v.mask, ctx->alpha_limit};
     } else {
         const double key_slack = entry_key_slack(ctx);
         c5::launch_build_records(s, g, ctx->alpha_limit, 0);
@@ -141,7 +145,7 @@ int adjoint_one(c5_context* ctx, const DerivativeView& v, bool squared, const fl
     C5_HIP(ctx, hipMemsetAsync(ga_dev, 0, 2 * n_cells * sizeof(double), v.s));
     if (v.bin_sort) {
         const auto resolve = squared ? c5::launch_gn_diag_resolve : c5::launch_adjoint_resolve;
-        resolve(v.s, v.g, ctx->im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, weights, ga_dev, gq_dev);
+        resolve(v.s, v.r, weights, ga_dev, gq_dev);
     } else {
         c5::AdjointParams ap;
         int rc = adjoint_params(ctx, v, ap);
@@ -174,7 +178,7 @@ int tangent_one(c5_context* ctx, const DerivativeView& v, const double* d_alpha,
     double2* const dir = ctx->tan_dir.as<double2>();
     c5::launch_tangent_gather(v.s, d_alpha, d_q, v.perm, ctx->n_cells, dir);
     if (v.bin_sort) {
-        c5::launch_tangent_resolve(v.s, v.g, ctx->im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, dir, out);
+        c5::launch_tangent_resolve(v.s, v.r, dir, out);
     } else {
         c5::TangentParams tp{};
         tp.w = v.w;
@@ -371,15 +375,14 @@ int enqueue_motion(c5_context* ctx, int n, const double* fields, float2* out) {
         for (int j = 0; j < n; ++j) {
             c5::MotionField f;
             std::copy(fields + 12 * j, fields + 12 * j + 12, f.f);
-            c5::launch_motion_resolve(v.s, v.g, ctx->im, ctx->xtab.as<double>(), ctx->ytab.as<double>(), ctx->offs64.as<int64_t>(),
-                                      ctx->segs.ptr, v.mask, ctx->alpha_limit, f, out + j * v.n_px);
+            c5::launch_motion_resolve(v.s, v.r, f, out + j * v.n_px);
         }
         return commit_derivative(ctx, "motion tangent");
     }
     const int width = batch_width(ctx, n);
     c5::MotionParams mp{};
     mp.w = v.w;
-    mp.geo = c5::MotionGeometry{v.g.cell_vert, v.g.vx, v.g.vy, v.g.vz};
+    mp.geo = v.geo;
     mp.image_px = v.n_px;
     for (int k0 = 0; k0 < n; k0 += width) {
         mp.n_used = std::min(width, n - k0);
@@ -411,10 +414,8 @@ int enqueue_vertex_adjoint(c5_context* ctx, const float2* grad_out, double* grad
     double* const grad_view = ctx->vtx_grad.as<double>();
     C5_HIP(ctx, hipMemsetAsync(face_w, 0, 12 * n_cells * sizeof(double), v.s));
     C5_HIP(ctx, hipMemsetAsync(grad_view, 0, 3 * n_pts * sizeof(double), v.s));
-    const c5::MotionGeometry geo{v.g.cell_vert, v.g.vx, v.g.vy, v.g.vz};
     if (v.bin_sort) {
-        c5::launch_vertex_resolve(v.s, v.g, ctx->im, ctx->xtab.as<double>(), ctx->ytab.as<double>(), ctx->offs64.as<int64_t>(),
-                                  ctx->segs.ptr, v.mask, ctx->alpha_limit, grad_out, face_w);
+        c5::launch_vertex_resolve(v.s, v.r, grad_out, face_w);
     } else {
         c5::AdjointParams ap;
         rc = adjoint_params(ctx, v, ap);
@@ -422,14 +423,14 @@ int enqueue_vertex_adjoint(c5_context* ctx, const float2* grad_out, double* grad
         c5::launch_adjoint_walk(v.s, ap, 1);
         c5::VertexParams vp{};
         vp.w = v.w;
-        vp.geo = geo;
+        vp.geo = v.geo;
         vp.grad_out = grad_out;
         vp.lambda = ap.lambda;
         vp.face_w = face_w;
         c5::launch_vertex_walk(v.s, vp, ctx->vertex_merge != 0);
         ctx->slots[0].head_clean = true;  // (vertex_walk hands every head back cleared)
     }
-    c5::launch_vertex_finish(v.s, geo, ctx->n_cells, face_w, grad_view, ctx->n_pts, ctx->view, grad_xyz);
+    c5::launch_vertex_finish(v.s, v.geo, ctx->n_cells, face_w, grad_view, ctx->n_pts, ctx->view, grad_xyz);
     return commit_derivative(ctx, "vertex adjoint");
 }
 
@@ -448,7 +449,7 @@ int enqueue_vertex_tangent(c5_context* ctx, int n, const double* d_xyz, float2* 
     double* const u_view = ctx->vtx_vel.as<double>();
     c5::VertexTangentParams vt{};
     vt.w = v.w;
-    vt.geo = c5::MotionGeometry{v.g.cell_vert, v.g.vx, v.g.vy, v.g.vz};
+    vt.geo = v.geo;
     vt.u_view = u_view;
     vt.image_px = v.n_px;
     for (int k0 = 0; k0 < n; k0 += width) {
@@ -456,9 +457,7 @@ int enqueue_vertex_tangent(c5_context* ctx, int n, const double* d_xyz, float2* 
         c5::launch_vertex_velocity(v.s, width, d_xyz, ctx->n_pts, k0, vt.n_used, ctx->view, u_view);
         if (v.bin_sort) {
             for (int j = 0; j < vt.n_used; ++j)
-                c5::launch_vertex_tangent_resolve(v.s, v.g, ctx->im, ctx->xtab.as<double>(), ctx->ytab.as<double>(),
-                                                  ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, ctx->alpha_limit, u_view, width, j,
-                                                  out + (k0 + j) * v.n_px);
+                c5::launch_vertex_tangent_resolve(v.s, v.r, u_view, width, j, out + (k0 + j) * v.n_px);
             continue;
         }
         vt.out = out + k0 * v.n_px;
@@ -491,7 +490,7 @@ int enqueue_ray_matrix_rows(c5_context* ctx, int64_t* row_ptr) {
     if (rc) return rc;
     C5_HIP(ctx, ctx->scratch64.ensure(static_cast<size_t>(v.padded / 1024 + 1024) * sizeof(int64_t)));
     if (v.bin_sort) {
-        c5::launch_segment_count_resolve(v.s, ctx->im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, count);
+        c5::launch_segment_count_resolve(v.s, v.r, count);
     } else {
         c5::RayMatrixParams m{};
         m.w = v.w;
@@ -532,7 +531,7 @@ int enqueue_ray_matrix_fill(c5_context* ctx, const int64_t* row_ptr, int64_t cap
     m.z_exit = z_exit;
     m.changed_rows = changed_rows;
     if (v.bin_sort) {
-        c5::launch_segment_fill_resolve(v.s, ctx->im, ctx->offs64.as<int64_t>(), ctx->segs.ptr, v.mask, m);
+        c5::launch_segment_fill_resolve(v.s, v.r, m);
     } else {
         c5::launch_segment_walk(v.s, m, 2);
         ctx->slots[0].head_clean = true;  // (the fill hands every head back cleared)

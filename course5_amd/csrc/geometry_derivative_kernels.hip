@@ -1,0 +1,509 @@
+// gfx950 kernels of the geometry derivatives: the frame differentiated with respect to where the grid is.  They walk as the
+// scalar derivatives do (deriv_ray.hpp) and look a chord's two faces up by one rule (deriv_faces.hpp).
+//
+// The motion tangent (c5_render_motion_tangent*): the change of every pixel when the grid moves rigidly or affinely in
+// view space with the velocity field u(p) = A p + b (a change of a view angle is one such field, c5_rotation_motion),
+// the cells' scalars held.  The rays are parallel to z, and a face is a plane w = c + gx x + gy y: its depth at the
+// pixel (x, y) changes by dw = u_z(P) - gx u_x(P) - gy u_y(P), P = (x, y, w) the point hit.  With ddz_k = dw_exit,k -
+// dw_entry,k the change of the k-th chord,
+//     tau_dot = sum_k alpha_k ddz_k                                              (raw alpha, every segment)
+//     I_dot_k = E_k I_dot_{k-1} + E_k (Q_k - a_k I_{k-1}) ddz_k                  (active segments; dI_k / ddz_k)
+// (a clamped alpha still moves with its chord: the clamp is on alpha).  Pixels that gain or lose coverage - silhouettes,
+// a ray that crosses an edge into another list of cells - are not differentiated: the result is the derivative of the
+// smooth piece the pixel is on.
+//   motion_walk<KC>   tangent_walk's frame for KC fields: I, and per field I_dot, tau_dot and the dw of the face the ray
+//                     entered its cell through.  An interior step hands the exit face's dw on; a boundary entry (the
+//                     ray's start, a re-entry, a pick-up across a hanging-node interface) has no plane in the record of
+//                     the cell entered and finds the face from the cell's four vertices (cell_slopes).  The fields are
+//                     kernel arguments: uniform loads.
+//   motion_resolve    the same over bin_sort_resolve's lists: both faces of every segment from the cell's vertices.
+// No atomics, no pre-pass: bit-reproducible, like the tangent.
+//
+// The vertex adjoint (c5_render_vertex_adjoint*), the motion tangent's reverse mode per grid point, and the vertex tangent
+// (c5_render_vertex_tangent*), the operator it is the transpose of: their blocks further down.  The vertex adjoint's sums
+// are fp64 atomics (global_atomic_add_f64: -munsafe-fp-atomics, build.py), added in arrival order: NOT bit-reproducible.
+#include "deriv_faces.hpp"
+#include "deriv_lists.hpp"
+
+namespace c5 {
+
+// ---- motion tangent (c5_render_motion_tangent*) ---------------------------------------------------------------------------
+
+// tangent_walk's frame for KC velocity fields.  Nothing is shared between the lanes: a lane leaves when its ray ends.
+template <int KC>
+__global__ __launch_bounds__(64) void motion_walk(MotionParams A) {
+    using namespace adj;
+    const WalkParams& P = A.w;
+    Ray r;
+    double I = 0.0, I_dot[KC], tau_dot[KC], dw_carry[KC];  // dw_carry: of the face the ray entered its cell through
+#pragma unroll
+    for (int j = 0; j < KC; ++j) I_dot[j] = tau_dot[j] = dw_carry[j] = 0.0;
+
+    const EntryHead ent = ray_begin(r, P);
+
+    // a boundary entry into `cell`: the entry face from the cell's vertices (rare: a few times per ray)
+    auto enter = [&](int cell) {
+        const CellSlopes cf = cell_slopes(A.geo, cell, r.x, r.y);
+#pragma unroll
+        for (int j = 0; j < KC; ++j) dw_carry[j] = cf.found ? face_dw(A.field[j], cf.in.gx, cf.in.gy, r.x, r.y, cf.in.w) : 0.0;
+    };
+
+    CellRegs cur;
+    if (r.cell >= 0) {
+        load_cell(cur, P.xrec, r.cell);
+        enter(r.cell);
+    }
+
+    while (r.cell >= 0) {
+        const SlopedExit se = step_geometry_sloped(cur, r.x, r.y);  // (ray_step's own geometry: the same operations, once)
+        double dz, carry_next;
+        const int nb = ray_step(r, P, ent, cur, dz, carry_next);
+        CellRegs nxt;
+        if (nb >= 0) load_cell(nxt, P.xrec, nb);
+
+        const bool has_exit = se.w_exit < INFINITY;
+        // nb, if any, lies behind the exit face (else it is a boundary entry)
+        const bool through_face = has_exit && (se.w_out & kIdMask) != kNoCell;
+        double dw_exit[KC];
+#pragma unroll
+        for (int j = 0; j < KC; ++j) dw_exit[j] = has_exit ? face_dw(A.field[j], se.gx, se.gy, r.x, r.y, se.w_exit) : 0.0;
+
+        if (is_segment(dz)) {
+            const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+            double ddz[KC];
+#pragma unroll
+            for (int j = 0; j < KC; ++j) {
+                ddz[j] = dw_exit[j] - dw_carry[j];
+                tau_dot[j] = fma(a_raw, ddz[j], tau_dot[j]);  // d tau / d dz (raw alpha)
+            }
+            if (a != 0.0) {
+                const double E = exp_nonpositive(-a * dz);
+                const double dI_ddz = chord_dI(a, q, E, I);
+#pragma unroll
+                for (int j = 0; j < KC; ++j) I_dot[j] = fma(E, I_dot[j], dI_ddz * ddz[j]);
+                I = segment_terms(a, q, dz, E, 1.0, I).I_next;
+            }
+        }
+        if (nb >= 0) {
+            if (through_face) {
+#pragma unroll
+                for (int j = 0; j < KC; ++j) dw_carry[j] = dw_exit[j];
+            } else {
+                enter(nb);
+            }
+        }
+        ray_advance(r, nb, carry_next);
+        cur = nxt;
+    }
+
+    if (r.in_image) {
+#pragma unroll
+        for (int j = 0; j < KC; ++j)
+            if (j < A.n_used)
+                A.out[static_cast<size_t>(j) * A.image_px + r.lp] = make_float2(static_cast<float>(tau_dot[j]), static_cast<float>(I_dot[j]));
+    }
+    if (!A.keep_entries) ray_clear_head(r, P);
+    ray_count(r, P);
+}
+
+// tangent_resolve's frame: the same sort, the same back-to-front order; both faces of a segment from its cell's vertices.
+__global__ __launch_bounds__(256) void motion_resolve(ResolveParams R, MotionField field, float2* __restrict__ out) {
+    using namespace adj;
+    const ListFrame f = list_frame<true>(R);
+    if (!f.in_image) return;
+    const GridView& g = R.g;
+    const MotionGeometry geo{g.cell_vert, g.vx, g.vy, g.vz};
+    double I = 0.0, I_dot = 0.0, tau_dot = 0.0;
+    for (int i = f.n - 1; i >= 0; --i) {
+        const int c = static_cast<int>(f.list[i].cell);
+        const double dz = f.list[i].dz, q = g.q[c], a_raw = g.alpha[c];
+        const ClampedAlpha ca = clamp_alpha(a_raw, R.alpha_limit);
+        const CellSlopes cf = cell_slopes(geo, c, f.x, f.y);
+        const double ddz = cf.found ? face_dw(field.f, cf.out.gx, cf.out.gy, f.x, f.y, cf.out.w) -
+                                          face_dw(field.f, cf.in.gx, cf.in.gy, f.x, f.y, cf.in.w)
+                                    : 0.0;
+        tau_dot = fma(a_raw, ddz, tau_dot);
+        if (ca.active) {
+            const double E = exp(-ca.a * dz);
+            I_dot = fma(E, I_dot, chord_dI(ca.a, q, E, I) * ddz);
+            I = segment_terms(ca.a, q, dz, E, 1.0, I).I_next;
+        }
+    }
+    out[f.lp] = make_float2(static_cast<float>(tau_dot), static_cast<float>(I_dot));
+}
+
+// ---- vertex adjoint (c5_render_vertex_adjoint*) ---------------------------------------------------------------------------
+// The gradient of the frame with respect to the grid's points, the reverse mode of the motion tangent.  A segment's chord is
+// dz_k = w_exit - w_entry and d loss / d dz_k = G_k = g_tau alpha_k + g_I T_k E_k (Q_k - a_k I_{k-1}) (the second term for
+// active segments; T_k as the adjoint's pass 2 forms it).  A face's depth at the pixel is w = sum_i lambda_i z_i, lambda the
+// barycentric coordinates of (x, y) in the projected triangle, and dw / d(x_i, y_i, z_i) = lambda_i (-gx, -gy, 1).
+//   adjoint_walk<1>   Lambda per pixel, as for the adjoint.
+//   vertex_walk       adjoint_walk<2>'s walk; per segment the two faces from the cell's vertices (cell_faces_bary) and
+//                     +-G_k lambda added to face_w[cell][face][vertex of the face]: six atomics per segment, no slopes.
+//   vertex_resolve    the same over bin_sort_resolve's lists.
+//   vertex_finish     per cell: the four faces' slopes again, face_w times (-gx, -gy, 1) added to grad_view[point]; per
+//                     point: M^T grad_view, M the linear part of the view, into the caller's array.
+// Cells name the representatives of welded points, so a group's sum lands on its representative and the others stay 0.
+
+namespace adj {
+
+// +G lambda to the exit face's three vertices, -G lambda to the entry face's: six atomics
+__device__ __forceinline__ void scatter_faces(double* __restrict__ face_w, int cell, double G, const CellFacesBary& cf) {
+    double* const fw = face_w + static_cast<size_t>(cell) * 12;
+    double* const o = fw + 3 * cf.out.f;
+    double* const i = fw + 3 * cf.in.f;
+    atomicAdd(o, G * cf.out.l0);
+    atomicAdd(o + 1, G * cf.out.l1);
+    atomicAdd(o + 2, G * cf.out.l2);
+    atomicAdd(i, -G * cf.in.l0);
+    atomicAdd(i + 1, -G * cf.in.l1);
+    atomicAdd(i + 2, -G * cf.in.l2);
+}
+
+}  // namespace adj
+
+// adjoint_walk<2>'s frame.  The cell's vertex ids are loaded beside its record, the vertices at the top of its step.
+// MERGE false ("vertex_merge" 0): nothing is shared between the lanes, a lane leaves when its ray ends and adds its six
+// values by itself - ten times slower on the C3 frame (neighbouring rays are in the same cells: the atomics of a step
+// queue up on a few addresses).  MERGE true (the default): adjoint_walk_batch's reduction (deriv_ray.hpp: reduce_rows) - the
+// loop is wave-uniform and every lane stages its cell's twelve values (six of them zero) in a row of LDS.
+template <bool MERGE>
+__global__ __launch_bounds__(64) void vertex_walk(VertexParams A) {
+    using namespace adj;
+    constexpr int kV = 12;
+    __shared__ double stage[MERGE ? RowStage<kV>::kDoubles : 1];
+    const WalkParams& P = A.w;
+    Ray r;
+    const int lane = r.lane;
+    if (MERGE) stage_begin<kV>(stage, lane);
+    double lam = 0.0, lam_total = 0.0, I = 0.0, g_tau = 0.0, g_I = 0.0;
+
+    const EntryHead ent = ray_begin(r, P, [&] {
+        const float2 g = A.grad_out[r.lp];
+        g_tau = g.x;
+        g_I = g.y;
+        lam_total = A.lambda[r.lp];
+        return g_tau != 0.0 || g_I != 0.0;
+    });
+
+    CellRegs cur;
+    int4 cv = make_int4(0, 0, 0, 0);
+    if (r.cell >= 0) {
+        load_cell(cur, P.xrec, r.cell);
+        cv = A.geo.cell_vert[r.cell];
+    }
+
+    for (;;) {
+        const bool live = r.cell >= 0;
+        if (MERGE ? __builtin_amdgcn_ballot_w64(live) == 0ull : !live) break;
+        const int here = r.cell;
+        bool emit = false;
+        if (live) {
+            double p[4][3];
+            load_vertices(A.geo, cv, p);
+            double dz, carry_next;
+            const int nb = ray_step(r, P, ent, cur, dz, carry_next);
+            CellRegs nxt;
+            int4 cv_nxt = cv;
+            if (nb >= 0) {
+                load_cell(nxt, P.xrec, nb);
+                cv_nxt = A.geo.cell_vert[nb];
+            }
+
+            if (is_segment(dz)) {
+                const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+                double G = g_tau * a_raw;                                  // d tau / d dz (raw alpha, every segment)
+                if (a != 0.0) {
+                    lam = lambda_add(lam, a, dz);  // (as in pass 1: Lambda_n == Lambda bit for bit, Lambda - Lambda_k >= 0)
+                    const double T = exp_nonpositive(fmin(lam - lam_total, 0.0));
+                    const double E = exp_nonpositive(-a * dz);
+                    G = fma(g_I * T, chord_dI(a, q, E, I), G);  // G_k
+                    I = segment_terms(a, q, dz, E, 1.0, I).I_next;
+                }
+                if (G != 0.0) {
+                    const CellFacesBary cf = cell_faces_bary(p, r.x, r.y);
+                    if (cf.found) {
+                        if (!MERGE) {
+                            scatter_faces(A.face_w, here, G, cf);
+                        } else {
+                            emit = true;
+                            double* const row = stage_row<kV>(stage, lane);
+#pragma unroll
+                            for (int v = 0; v < kV; ++v) row[v] = 0.0;
+                            row[3 * cf.out.f] = G * cf.out.l0;
+                            row[3 * cf.out.f + 1] = G * cf.out.l1;
+                            row[3 * cf.out.f + 2] = G * cf.out.l2;
+                            row[3 * cf.in.f] = -G * cf.in.l0;
+                            row[3 * cf.in.f + 1] = -G * cf.in.l1;
+                            row[3 * cf.in.f + 2] = -G * cf.in.l2;
+                        }
+                    }
+                }
+            }
+            ray_advance(r, nb, carry_next);
+            cur = nxt;
+            cv = cv_nxt;
+        }
+        if (MERGE) reduce_rows<kV>(stage, emit, here, lane, A.face_w);
+    }
+
+    ray_clear_head(r, P);
+}
+
+// adjoint_resolve's frame: the same sort, the same back-to-front order; both faces of a segment from its cell's vertices.
+__global__ __launch_bounds__(256) void vertex_resolve(ResolveParams R, const float2* __restrict__ grad_out, double* __restrict__ face_w) {
+    using namespace adj;
+    double g_tau = 0.0, g_I = 0.0;
+    const ListFrame f = list_frame<true>(R, [&](int64_t lp) {
+        const float2 gw = grad_out[lp];
+        g_tau = gw.x;
+        g_I = gw.y;
+        return !(g_tau == 0.0 && g_I == 0.0);
+    });
+    const GridView& g = R.g;
+    const MotionGeometry geo{g.cell_vert, g.vx, g.vy, g.vz};
+    const double lam_total = lambda_total(f.list, f.n, g, R.alpha_limit);
+    double lam = 0.0, I = 0.0;
+    for (int i = f.n - 1; i >= 0; --i) {
+        const int c = static_cast<int>(f.list[i].cell);
+        const double dz = f.list[i].dz, q = g.q[c], a_raw = g.alpha[c];
+        const ClampedAlpha ca = clamp_alpha(a_raw, R.alpha_limit);
+        double G = g_tau * a_raw;
+        if (ca.active) {
+            lam = lambda_add(lam, ca.a, dz);
+            const double T = exp(fmin(lam - lam_total, 0.0));
+            const double E = exp(-ca.a * dz);
+            G = fma(g_I * T, chord_dI(ca.a, q, E, I), G);
+            I = segment_terms(ca.a, q, dz, E, 1.0, I).I_next;
+        }
+        if (G != 0.0) {
+            double p[4][3];
+            load_vertices(geo, g.cell_vert[c], p);
+            const CellFacesBary cf = cell_faces_bary(p, f.x, f.y);
+            if (cf.found) scatter_faces(face_w, c, G, cf);
+        }
+    }
+}
+
+// vertex_finish, per cell: the weights of its faces' vertices times (-gx, -gy, 1) to the points
+__global__ __launch_bounds__(256) void vertex_finish_cells(MotionGeometry G, int64_t n_cells, const double* __restrict__ face_w,
+                                                           double* __restrict__ grad_view) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n_cells) return;
+    double w[12];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        w[k] = face_w[i * 12 + k];
+        any = any || w[k] != 0.0;
+    }
+    if (!any) return;
+    const int4 cv = G.cell_vert[i];
+    const int vid[4] = {cv.x, cv.y, cv.z, cv.w};
+    double p[4][3];
+    adj::load_vertices(G, cv, p);
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+        const FacePlane fp = face_plane(p, f);
+        if (fp.kind == 0) continue;  // (edge-on: no ray crosses it, and it has no slopes)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double wk = w[3 * f + k];
+            if (wk != 0.0) {
+                double* const gv = grad_view + 3 * static_cast<int64_t>(vid[adj::face_vertex(f, k)]);
+                atomicAdd(gv, -fp.gx * wk);
+                atomicAdd(gv + 1, -fp.gy * wk);
+                atomicAdd(gv + 2, wk);
+            }
+        }
+    }
+}
+
+// vertex_finish, per point: grad_xyz = M^T grad_view, the view's rotations transposed in reverse order (their centres
+// drop out of the linear part)
+__global__ __launch_bounds__(256) void vertex_finish_points(const double* __restrict__ grad_view, int64_t n_pts, RotationList R,
+                                                            double* __restrict__ grad_xyz) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n_pts) return;
+    double gx = grad_view[3 * i], gy = grad_view[3 * i + 1], gz = grad_view[3 * i + 2];
+    adj::rotate_linear<true>(R, gx, gy, gz);
+    grad_xyz[3 * i] = gx;
+    grad_xyz[3 * i + 1] = gy;
+    grad_xyz[3 * i + 2] = gz;
+}
+
+// ---- vertex tangent (c5_render_vertex_tangent*) ---------------------------------------------------------------------------
+// The forward mode of the vertex adjoint: the motion tangent with the velocity u(P) = sum_i lambda_i u_i interpolated from
+// the face's three vertices instead of an affine field.  With u_v = M d_xyz[v] (M the linear part of the view) a face's
+// depth at the pixel moves by dw = sum_i lambda_i (u_z - gx u_x - gy u_y)[vertex i], the chord by ddz = dw_exit - dw_entry,
+// and the sums are the motion tangent's.
+//   vertex_velocity<KC>        per point and field: u_view[pt][j] = M d_xyz[k0 + j][pt] (vertex_finish_points run forward).
+//   vertex_tangent_walk<KC>    motion_walk's frame; per segment both faces from the cell's own vertices
+//                              (cell_faces: cell_faces_bary's rule, with the slopes) - nothing is carried from the previous cell, as
+//                              in vertex_walk, so the two are transposes of each other term by term.
+//   vertex_tangent_resolve     the same over bin_sort_resolve's lists, one field per launch.
+// No atomics, no LDS, no pre-pass: bit-reproducible, and a field's image does not depend on the width or on its place in
+// the chunk (its arithmetic is vertex_ddz, the same for every field).
+
+// u_view[pt][j] = M d_xyz[k0 + j][pt] for j < n_used, zero beyond: the view's rotations in forward order, linear part only
+// (vertex_finish_points the other way).  One thread per point and field; a point's KC fields are contiguous.
+template <int KC>
+__global__ __launch_bounds__(256) void vertex_velocity(const double* __restrict__ d_xyz, int64_t n_pts, int k0, int n_used,
+                                                       RotationList R, double* __restrict__ u_view) {
+    const int64_t t = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (t >= n_pts * KC) return;
+    const int64_t i = t / KC;
+    const int j = static_cast<int>(t - i * KC);
+    double ux = 0.0, uy = 0.0, uz = 0.0;
+    if (j < n_used) {
+        const double* const d = d_xyz + 3 * (static_cast<int64_t>(k0 + j) * n_pts + i);
+        ux = d[0], uy = d[1], uz = d[2];
+        adj::rotate_linear<false>(R, ux, uy, uz);
+    }
+    u_view[3 * t] = ux;
+    u_view[3 * t + 1] = uy;
+    u_view[3 * t + 2] = uz;
+}
+
+// motion_walk's frame over the per-point velocities.  The next record and the next cell's vertex ids are loaded before the
+// arithmetic, the vertices at the top of the step (vertex_walk's order).  Nothing is shared between the lanes.
+template <int KC>
+__global__ __launch_bounds__(64) void vertex_tangent_walk(VertexTangentParams A) {
+    using namespace adj;
+    const WalkParams& P = A.w;
+    Ray r;
+    double I = 0.0, I_dot[KC], tau_dot[KC];
+#pragma unroll
+    for (int j = 0; j < KC; ++j) I_dot[j] = tau_dot[j] = 0.0;
+
+    const EntryHead ent = ray_begin(r, P);
+
+    CellRegs cur;
+    int4 cv = make_int4(0, 0, 0, 0);
+    if (r.cell >= 0) {
+        load_cell(cur, P.xrec, r.cell);
+        cv = A.geo.cell_vert[r.cell];
+    }
+
+    while (r.cell >= 0) {
+        double p[4][3];
+        load_vertices(A.geo, cv, p);
+        double dz, carry_next;
+        const int nb = ray_step(r, P, ent, cur, dz, carry_next);
+        CellRegs nxt;
+        int4 cv_nxt = cv;
+        if (nb >= 0) {
+            load_cell(nxt, P.xrec, nb);
+            cv_nxt = A.geo.cell_vert[nb];
+        }
+
+        if (is_segment(dz)) {
+            const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+            const CellFaces cf = cell_faces(p, r.x, r.y);
+            int vo[3], vi[3];
+            face_points(cv, cf.b.out.f, vo);
+            face_points(cv, cf.b.in.f, vi);
+            double ddz[KC];
+#pragma unroll
+            for (int j = 0; j < KC; ++j) {
+                ddz[j] = cf.b.found ? vertex_ddz(A.u_view + 3 * j, 3 * KC, vo, vi, cf) : 0.0;  // (faces not found: 0)
+                tau_dot[j] = fma(a_raw, ddz[j], tau_dot[j]);                                         // d tau / d dz (raw alpha)
+            }
+            if (a != 0.0) {
+                const double E = exp_nonpositive(-a * dz);
+                const double dI_ddz = chord_dI(a, q, E, I);
+#pragma unroll
+                for (int j = 0; j < KC; ++j) I_dot[j] = fma(E, I_dot[j], dI_ddz * ddz[j]);
+                I = segment_terms(a, q, dz, E, 1.0, I).I_next;
+            }
+        }
+        ray_advance(r, nb, carry_next);
+        cur = nxt;
+        cv = cv_nxt;
+    }
+
+    if (r.in_image) {
+#pragma unroll
+        for (int j = 0; j < KC; ++j)
+            if (j < A.n_used)
+                A.out[static_cast<size_t>(j) * A.image_px + r.lp] = make_float2(static_cast<float>(tau_dot[j]), static_cast<float>(I_dot[j]));
+    }
+    if (!A.keep_entries) ray_clear_head(r, P);
+    ray_count(r, P);
+}
+
+// motion_resolve's frame over a velocity per point.  u: field `j`'s first double of point 0 in a velocity buffer of `pitch`
+// doubles per point.
+__global__ __launch_bounds__(256) void vertex_tangent_resolve(ResolveParams R, const double* __restrict__ u, int pitch,
+                                                              float2* __restrict__ out) {
+    using namespace adj;
+    const ListFrame f = list_frame<true>(R);
+    if (!f.in_image) return;
+    const GridView& g = R.g;
+    const MotionGeometry geo{g.cell_vert, g.vx, g.vy, g.vz};
+    double I = 0.0, I_dot = 0.0, tau_dot = 0.0;
+    for (int i = f.n - 1; i >= 0; --i) {
+        const int c = static_cast<int>(f.list[i].cell);
+        const double dz = f.list[i].dz, q = g.q[c], a_raw = g.alpha[c];
+        const ClampedAlpha ca = clamp_alpha(a_raw, R.alpha_limit);
+        const int4 cv = g.cell_vert[c];
+        double p[4][3];
+        load_vertices(geo, cv, p);
+        const CellFaces cf = cell_faces(p, f.x, f.y);
+        double ddz = 0.0;
+        if (cf.b.found) {
+            int vo[3], vi[3];
+            face_points(cv, cf.b.out.f, vo);
+            face_points(cv, cf.b.in.f, vi);
+            ddz = vertex_ddz(u, static_cast<size_t>(pitch), vo, vi, cf);
+        }
+        tau_dot = fma(a_raw, ddz, tau_dot);
+        if (ca.active) {
+            const double E = exp(-ca.a * dz);
+            I_dot = fma(E, I_dot, chord_dI(ca.a, q, E, I) * ddz);
+            I = segment_terms(ca.a, q, dz, E, 1.0, I).I_next;
+        }
+    }
+    out[f.lp] = make_float2(static_cast<float>(tau_dot), static_cast<float>(I_dot));
+}
+
+void launch_motion_walk(hipStream_t s, int kc, const MotionParams& m) {
+    if (const unsigned blocks = tile_blocks(m.w.im)) C5_LAUNCH_KC(motion_walk, kc, blocks, 64, s, m);
+}
+
+void launch_motion_resolve(hipStream_t s, const ResolveParams& r, const MotionField& field, float2* out) {
+    if (const unsigned blocks = pixel_blocks(r.im)) hipLaunchKernelGGL(motion_resolve, dim3(blocks), dim3(256), 0, s, r, field, out);
+}
+
+void launch_vertex_walk(hipStream_t s, const VertexParams& v, bool merge) {
+    const unsigned blocks = tile_blocks(v.w.im);
+    if (!blocks) return;
+    if (merge) hipLaunchKernelGGL(vertex_walk<true>, dim3(blocks), dim3(64), 0, s, v);
+    else hipLaunchKernelGGL(vertex_walk<false>, dim3(blocks), dim3(64), 0, s, v);
+}
+
+void launch_vertex_resolve(hipStream_t s, const ResolveParams& r, const float2* grad_out, double* face_w) {
+    if (const unsigned blocks = pixel_blocks(r.im)) hipLaunchKernelGGL(vertex_resolve, dim3(blocks), dim3(256), 0, s, r, grad_out, face_w);
+}
+
+void launch_vertex_finish(hipStream_t s, const MotionGeometry& geo, int64_t n_cells, const double* face_w, double* grad_view,
+                          int64_t n_pts, const RotationList& R, double* grad_xyz) {
+    if (n_cells > 0) hipLaunchKernelGGL(vertex_finish_cells, dim3(item_blocks(n_cells)), dim3(256), 0, s, geo, n_cells, face_w, grad_view);
+    if (n_pts > 0) hipLaunchKernelGGL(vertex_finish_points, dim3(item_blocks(n_pts)), dim3(256), 0, s, grad_view, n_pts, R, grad_xyz);
+}
+
+void launch_vertex_velocity(hipStream_t s, int kc, const double* d_xyz, int64_t n_pts, int k0, int n_used, const RotationList& R,
+                            double* u_view) {
+    if (n_pts <= 0) return;
+    C5_LAUNCH_KC(vertex_velocity, kc, item_blocks(n_pts * kc), 256, s, d_xyz, n_pts, k0, n_used, R, u_view);
+}
+
+void launch_vertex_tangent_walk(hipStream_t s, int kc, const VertexTangentParams& v) {
+    if (const unsigned blocks = tile_blocks(v.w.im)) C5_LAUNCH_KC(vertex_tangent_walk, kc, blocks, 64, s, v);
+}
+
+void launch_vertex_tangent_resolve(hipStream_t s, const ResolveParams& r, const double* u_view, int kc, int j, float2* out) {
+    if (const unsigned blocks = pixel_blocks(r.im)) hipLaunchKernelGGL(vertex_tangent_resolve, dim3(blocks), dim3(256), 0, s, r, u_view + 3 * j, 3 * kc, out);
+}
+
+}  // namespace c5

@@ -99,6 +99,18 @@ def test_device_sources_hash_and_abi_version_stay():
     assert ctypes.CDLL(capi.LIB_PATH).c5_abi_version() == 2
 
 
+def test_the_derivative_kernels_are_three_translation_units():
+    from course5_amd import build
+    listed = [name for name, _ in build.LIB_SOURCES]
+    for name in sorted(os.listdir(build.CSRC)):
+        if name.endswith((".hip", ".cpp")):
+            assert listed.count(name) == 1, name
+    assert not os.path.exists(os.path.join(build.CSRC, "adjoint_kernels.hip"))
+    flags = dict(build.LIB_SOURCES)
+    for name in ("scalar_derivative_kernels.hip", "geometry_derivative_kernels.hip", "ray_matrix_kernels.hip"):
+        assert "-munsafe-fp-atomics" in flags[name], name
+
+
 # ---- the restatement ------------------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")

@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 REGRESSIONS = {
     # grad_q of cell 18845 off by 42.8 x the bar (4e-8 of its scale), and every other "underflow" scene likewise: with
     # alpha = 1e9 one chord is worth 1e7 of Lambda, and T = exp(-(Lambda - Lambda_k)) carried Lambda's rounding into the
-    # cells in front of it.  Fixed in adjoint_kernels.hip: lambda_add caps a segment's share of Lambda at 1024.
+    # cells in front of it.  Fixed in deriv_ray.hpp: lambda_add caps a segment's share of Lambda at 1024.
     3009: "Lambda - Lambda_k cancels behind a cell of optical depth 1e7",
     # I_dot = 3.6e-86 in fp64 is 0 in the fp32 image: the absolute floor of an fp32 output is fp32's own,
     # FLT_MIN / 2^-23 = 2^-103, not the 2^-970 of a double (a mistake of the bar, not of the kernel)
