@@ -61,6 +61,11 @@ J^T W J v and gn_diagonal(ctx, alpha, q, weight) = diag(J^T W J), one library ca
 c5_render_gn_diagonal_device).  They upload the scalars as the forward does, return float64 tensors on the context's GPU
 without a graph, and raise under a differentiating torch.func transform.
 
+Second derivatives through render itself raise, but the exact second-order operator in the scalars is there as a call of
+its own: hvp(ctx, alpha, q, v_alpha, v_q, grad_img) = Hess(sum_p grad_img_p . img_p) v, one library call
+(c5_render_hvp_device), with gn_product's conventions.  course5_amd.fit.newton_product / newton_step build the exact
+Hessian of a least-squares fit from it.
+
 ray_matrix(ctx) hands out the operator itself: the frame's per-pixel (cell, chord) lists as a torch.sparse_csr_tensor on the
 context's GPU (c5_ray_matrix_rows_device, c5_ray_matrix_fill_device), for solvers that want A and not only A v and A^T g.
 """
@@ -309,7 +314,8 @@ class _Render(torch.autograd.Function):
 
 
 def render(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
-    """The frame of `ctx` with the cells' scalars alpha (AbsorpCoef) and q (radEnLooseRate), differentiable in both."""
+    """The frame of `ctx` with the cells' scalars alpha (AbsorpCoef) and q (radEnLooseRate), differentiable in both.
+    Second derivatives of it raise; the Hessian-vector product in (alpha, q) is hvp(), an operator of its own."""
     return _Render.apply(ctx, alpha, q)
 
 
@@ -699,6 +705,28 @@ def gn_diagonal(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, weight=
     return da, dq
 
 
+def hvp(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, v_alpha, v_q, grad_img) -> tuple:
+    """(h_alpha, h_q) = Hess(phi) (v_alpha, v_q), phi = sum_p grad_img_p . img_p, for the frame of `ctx` with the scalars
+    alpha and q: the exact second derivative of the frame in the cells' scalars, weighted by the upstream image grad_img
+    [local_rows, res_x, 2] and applied to the direction v_alpha / v_q [n_cells] (either may be None: zero).  Channel 0 of
+    grad_img has no effect (tau is linear in alpha).  float64 [n_cells] each on the context's GPU, no graph.  One library
+    call (c5_render_hvp_device) on torch's current stream."""
+    device = _gn_enter(ctx, alpha, q, "hvp")
+    given = [v for v in (v_alpha, v_q) if v is not None]
+    if not given or any(tuple(v.shape) != (ctx.n_cells,) for v in given):
+        raise ValueError(f"v_alpha and / or v_q must be [{ctx.n_cells}]")
+    with torch.cuda.device(device):
+        va, vq = (None if v is None else _plain(v).detach().to(device=device, dtype=torch.float64).contiguous() for v in (v_alpha, v_q))
+        g = _plain(grad_img).detach().to(device=device, dtype=torch.float32).contiguous()
+        if tuple(g.shape) != (ctx.local_rows, ctx.res_x, 2):
+            raise ValueError(f"grad_img must be [{ctx.local_rows}, {ctx.res_x}, 2], not {list(g.shape)}")
+        ha = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
+        hq = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
+        _use_torch_stream(ctx, device)
+        _run(ctx, lambda: ctx.render_hvp_device(va, vq, g, ha, hq))
+    return ha, hq
+
+
 def ray_matrix(ctx: capi.Context, with_depth: bool = False):
     """The ray matrix A of the frame `ctx` would render now: a torch.sparse_csr_tensor [local_rows * res_x, n_cells],
     float64, on the context's GPU, A[pixel, cell] = the chord of the pixel's ray through the cell (rows: local pixels lrow *
@@ -727,4 +755,4 @@ def ray_matrix(ctx: capi.Context, with_depth: bool = False):
     return (A, z_exit[:nnz]) if with_depth else A
 
 
-__all__ = ["render", "render_view", "render_mesh", "gn_product", "gn_diagonal", "ray_matrix"]
+__all__ = ["render", "render_view", "render_mesh", "gn_product", "gn_diagonal", "hvp", "ray_matrix"]

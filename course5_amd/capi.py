@@ -32,6 +32,7 @@ EXPORTS = [
     "c5_render_tangent_batch", "c5_render_tangent_batch_device", "c5_render_adjoint_batch", "c5_render_adjoint_batch_device",
     "c5_update_scalars_device",
     "c5_render_gn_product", "c5_render_gn_product_device", "c5_render_gn_diagonal", "c5_render_gn_diagonal_device",
+    "c5_render_hvp", "c5_render_hvp_device",
     "c5_render_motion_tangent", "c5_render_motion_tangent_device", "c5_rotation_motion",
     "c5_render_vertex_adjoint", "c5_render_vertex_adjoint_device", "c5_update_points",
     "c5_render_vertex_tangent", "c5_render_vertex_tangent_device",
@@ -120,6 +121,8 @@ def load_library() -> C.CDLL:
     lib.c5_render_gn_product_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.c5_render_gn_diagonal.argtypes = [vp, C.POINTER(C.c_float), dp, dp]
     lib.c5_render_gn_diagonal_device.argtypes = [vp, vp, vp, vp]
+    lib.c5_render_hvp.argtypes = [vp, dp, dp, C.POINTER(C.c_float), dp, dp]
+    lib.c5_render_hvp_device.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.c5_render_motion_tangent.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_float)]
     lib.c5_render_motion_tangent_device.argtypes = [vp, C.c_int, dp, vp]
     lib.c5_rotation_motion.argtypes = [C.POINTER(Rotation), C.c_int, C.c_int, C.c_int, dp]
@@ -675,6 +678,57 @@ class Context:
             self.handle, C.c_void_p(_device_ptr(weight, torch.float32, (self.local_rows, self.res_x, 2)) or None),
             C.c_void_p(_device_ptr(diag_alpha, torch.float64, (self.n_cells,))),
             C.c_void_p(_device_ptr(diag_q, torch.float64, (self.n_cells,)))))
+
+    # -- Hessian-vector render ------------------------------------------------------------------------
+    def render_hvp(self, d_alpha=None, d_q=None, grad_out=None, fit=("alpha", "q")) -> tuple:
+        """(h_alpha, h_q) = Hess(sum_p g_I I_p) (d_alpha, d_q) of the frame render() would produce now: the exact second
+        derivative in the cells' scalars applied to one direction (d_alpha / d_q: [n_cells], either may be None: zero),
+        grad_out [local_rows, res_x, 2] the upstream image (channel 0 has no effect: tau is linear in alpha).  float64
+        [n_cells] each in the order of upload_grid; fit names the blocks wanted (the other comes back as None).
+        Synchronous; retries by itself.  Not bit-reproducible (fp64 atomics), as render_adjoint."""
+        def direction(d):
+            if d is None:
+                return None
+            d = np.ascontiguousarray(d, dtype=np.float64)
+            if d.shape != (self.n_cells,):
+                raise ValueError(f"a direction must hold one value per cell ({self.n_cells}), not {list(d.shape)}")
+            return d
+
+        da, dq = direction(d_alpha), direction(d_q)
+        if da is None and dq is None:
+            raise ValueError("give d_alpha and / or d_q")
+        if grad_out is None:
+            raise ValueError("grad_out is required")
+        g = np.ascontiguousarray(grad_out, dtype=np.float32)
+        if g.shape != (self.local_rows, self.res_x, 2):
+            raise ValueError(f"grad_out must be [{self.local_rows}, {self.res_x}, 2], not {list(g.shape)}")
+        fit = tuple(fit)
+        if not fit or any(f not in ("alpha", "q") for f in fit):
+            raise ValueError(f"fit must name 'alpha', 'q' or both, not {fit!r}")
+        ha = np.zeros(self.n_cells, dtype=np.float64) if "alpha" in fit else None
+        hq = np.zeros(self.n_cells, dtype=np.float64) if "q" in fit else None
+        self._check(self.lib.c5_render_hvp(
+            self.handle, None if da is None else _dp(da), None if dq is None else _dp(dq), g.ctypes.data_as(C.POINTER(C.c_float)),
+            None if ha is None else _dp(ha), None if hq is None else _dp(hq)))
+        return ha, hq
+
+    def render_hvp_device(self, d_alpha, d_q, grad_out, h_alpha, h_q):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (d_alpha / d_q float64 [n_cells],
+        one of them may be None; grad_out float32 [local_rows, res_x, 2]; h_alpha / h_q float64 [n_cells], one of them may
+        be None; contiguous) or raw device pointers.  The status comes with the next synchronize() (C5_RETRY: run it
+        again)."""
+        import torch
+        if d_alpha is None and d_q is None:
+            raise ValueError("give d_alpha and / or d_q")
+        if h_alpha is None and h_q is None:
+            raise ValueError("give h_alpha and / or h_q")
+        if grad_out is None:
+            raise ValueError("grad_out is required")
+        cells = (self.n_cells,)
+        args = [C.c_void_p(_device_ptr(d_alpha, torch.float64, cells) or None), C.c_void_p(_device_ptr(d_q, torch.float64, cells) or None),
+                C.c_void_p(_device_ptr(grad_out, torch.float32, (self.local_rows, self.res_x, 2))),
+                C.c_void_p(_device_ptr(h_alpha, torch.float64, cells) or None), C.c_void_p(_device_ptr(h_q, torch.float64, cells) or None)]
+        self._check(self.lib.c5_render_hvp_device(self.handle, *args))
 
     # -- frames delivered to host memory, pipelined -------------------------------------------------
     def host_image(self, full: bool = False) -> np.ndarray:

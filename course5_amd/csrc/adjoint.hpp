@@ -132,6 +132,30 @@ void launch_gn_weight(hipStream_t s, const float2* t, const float2* w, int64_t n
 // launch_adjoint_resolve's twin for the diagonal
 void launch_gn_diag_resolve(hipStream_t s, const ResolveParams& r, const float2* weight, double* diag_a, double* diag_q);
 
+// ---- Hessian-vector render (c5_render_hvp*): the second derivative of sum_p g_I I_p in the cells' (alpha, Q), applied to
+// one direction
+
+struct HvpParams {
+    WalkParams w;            // as AdjointParams
+    const double2* dir;      // [n_cells] device order: {dalpha, dQ} (launch_tangent_gather)
+    const float2* grad_out;  // [n_local_rows][res_x] upstream weights; channel 0 has no effect (pass 2)
+    double* lambda;          // [n_local_px] pass 1 -> pass 2: Lambda, as AdjointParams
+    double* lambda_dot;      // [n_local_px] pass 1 -> pass 2: sum of dalpha dz over the active, unclamped segments
+    double* h_a;             // [n_cells] device order, accumulated by pass 2
+    double* h_q;
+};
+
+// pass 1: Lambda and Lambda_dot per pixel; leaves the entry heads in place and counts as launch_adjoint_walk(.., 1) does.
+// pass 2: the scatter of (h_alpha, h_q); hands the heads back cleared.
+void launch_hvp_walk(hipStream_t s, const HvpParams& h, int pass);
+
+// the same over bin_sort_resolve's lists (sorts them in place, as launch_adjoint_resolve)
+void launch_hvp_resolve(hipStream_t s, const ResolveParams& r, const double2* dir, const float2* grad_out, double* h_a, double* h_q);
+
+// launch_adjoint_permute with either output null (that block is not written)
+void launch_hvp_permute(hipStream_t s, const double* ha_dev, const double* hq_dev, const int32_t* perm, int64_t n, double* ha_out,
+                        double* hq_out);
+
 // ---- motion tangent (c5_render_motion_tangent*): the frame differentiated with respect to an affine motion of the grid in
 // view space, u(p) = A p + b
 

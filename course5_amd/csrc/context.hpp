@@ -285,6 +285,8 @@ struct c5_context {
     // Gauss-Newton renders (c5_render_gn_product*, c5_render_gn_diagonal*): nothing of it is allocated before the first call
     c5api::DeviceBuffer gn_g;      // [width][n_local_px] float2: pass A's w * J v, pass B's upstream images (a chunk's)
     c5api::DeviceBuffer gn_spare;  // [width][n_cells] fp64: where the block of H v goes that the caller did not ask for
+    // Hessian-vector render (c5_render_hvp*): shares adj_lambda, adj_grad and tan_dir; allocated at the first call only
+    c5api::DeviceBuffer hvp_lambda_dot;  // [n_local_px] fp64: pass 1 -> pass 2 (scalar_derivative_kernels.hip: hvp_walk)
     // vertex adjoint (c5_render_vertex_adjoint*): nothing of it is allocated before the first call (it shares adj_lambda)
     c5api::DeviceBuffer vtx_face;  // [n_cells][4][3] fp64, device order: the chords' weights per face and vertex of the face
     c5api::DeviceBuffer vtx_grad;  // [n_pts][3] fp64: the gradient in view space

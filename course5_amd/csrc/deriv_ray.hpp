@@ -272,6 +272,70 @@ __device__ __forceinline__ void tangent_step(double a, bool clamped, double q, d
     I = t.I_next;
 }
 
+// d^2 S / d a^2 / dz^3 of S = (1 - e^(-a dz)) / a, x = a dz:  (2 (1 - e^-x) - 2 x e^-x - x^2 e^-x) / x^3
+//   = sum_m (-1)^m (m + 2)(m + 1) / (m + 3)! x^m = 1/3 - x/4 + x^2/10 - x^3/36 + ...  for 0 <= x < 1/8, cut where
+// dalpha_bracket_series is (x^10): the closed form cancels to nothing for short chords, two orders worse than the bracket
+__device__ __forceinline__ double d2alpha_series(double x) {
+    double p = 1.0 / 47174400.0;
+    p = fma(p, x, -1.0 / 4354560.0);
+    p = fma(p, x, 1.0 / 443520.0);
+    p = fma(p, x, -1.0 / 50400.0);
+    p = fma(p, x, 1.0 / 6480.0);
+    p = fma(p, x, -1.0 / 960.0);
+    p = fma(p, x, 1.0 / 168.0);
+    p = fma(p, x, -1.0 / 36.0);
+    p = fma(p, x, 0.1);
+    p = fma(p, x, -0.25);
+    return fma(p, x, 1.0 / 3.0);
+}
+
+// The Hessian-vector render's terms of one active segment, free of Q: S = (1 - E) / a and its first and second
+// derivatives in a (segment_terms' s_over_q and bracket / Q, and one order more), by their series below a dz = 1/8.
+struct SegmentTerms2 {
+    double S, S_a, S_aa;
+};
+__device__ __forceinline__ SegmentTerms2 segment_terms2(double a, double dz, double E) {
+    const double x = a * dz;
+    SegmentTerms2 t;
+    if (x < -kSmallExpArg) {
+        const double dz2 = dz * dz;
+        t.S = dz * one_minus_exp_over_x(x);
+        t.S_a = dz2 * dalpha_bracket_series(x);
+        t.S_aa = dz2 * dz * d2alpha_series(x);
+    } else {
+        t.S = (1.0 - E) / a;
+        t.S_a = (dz * E - t.S) / a;
+        t.S_aa = -fma(dz * dz, E, 2.0 * t.S_a) / a;
+    }
+    return t;
+}
+
+// Lambda_dot's running sum, sum_{j <= k} a_dot_j dz_j over the active segments whose alpha is not clamped: the same in
+// both passes of the Hessian-vector render, so that Lambda_dot_n == Lambda_dot to the bit.  Not capped: behind a segment
+// that lambda_add caps, lambda is exactly 0 and so is lambda times anything finite.
+__device__ __forceinline__ double lambda_dot_add(double lam_dot, double a_dot, double dz) { return fma(a_dot, dz, lam_dot); }
+
+// One active segment of the Hessian-vector render's second pass.  In: the segment (a clamped, q, dz, E), the direction
+// there (a_dot: 0 where alpha is clamped; q_dot), lam = g_I T_k and lam_dot = -lam (Lambda_dot - Lambda_dot_k), and the
+// carried I_{k-1}, I_dot_{k-1}.  Out: the segment's (h_alpha, h_q); I and I_dot advance to k (I_dot as tangent_step's).
+__device__ __forceinline__ void hvp_step(double a, bool clamped, double q, double dz, double E, double a_dot, double q_dot,
+                                         double lam, double lam_dot, double& I, double& I_dot, double& h_a, double& h_q) {
+    const SegmentTerms2 t = segment_terms2(a, dz, E);
+    const double dzE = dz * E;
+    h_q = fma(lam_dot, t.S, lam * (t.S_a * a_dot));
+    h_a = 0.0;
+    if (!clamped) {  // (a clamped alpha does not move: no row and no column)
+        const double G = fma(q, t.S_a, -dzE * I);
+        double second = fma(q_dot, t.S_a, q * (t.S_aa * a_dot));
+        second = fma(dz * dzE, a_dot * I, second);
+        second = fma(-dzE, I_dot, second);
+        h_a = fma(lam_dot, G, lam * second);
+    }
+    double src = fma(q_dot, t.S, a_dot * fma(q, t.S_a, -dzE * I));
+    I_dot = fma(E, I_dot, src);
+    I = fma(E, I, q * t.S);
+}
+
 // The staged per-cell reduction (one wavefront per workgroup).  Every lane stages its kV values of a step in a row of LDS;
 // then, per distinct cell of the step, lanes v < kV each sum column v over the cell's member rows (four rows per round, an
 // all-zero row 64 filling up) and add it with one atomic: kV atomics in one instruction, to one 8 kV-byte stretch.  A 64-lane

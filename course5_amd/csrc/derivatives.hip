@@ -542,6 +542,42 @@ int enqueue_ray_matrix_fill(c5_context* ctx, const int64_t* row_ptr, int64_t cap
     return C5_OK;
 }
 
+// The Hessian-vector render: the direction into device order (the tangent's buffer), the per-cell sums zeroed (the
+// adjoint's buffer), two passes of the walk - Lambda and Lambda_dot per pixel, then the scatter - or hvp_resolve over
+// bin_sort_resolve's lists, and the permutation into the caller's order.  ha_out / hq_out: either may be null.
+int enqueue_hvp(c5_context* ctx, const double* d_alpha, const double* d_q, const float2* grad_out, double* ha_out, double* hq_out) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc || v.no_cells) return rc;
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
+    C5_HIP(ctx, ctx->tan_dir.ensure(n_cells * sizeof(double2)));
+    C5_HIP(ctx, ctx->adj_grad.ensure(2 * n_cells * sizeof(double)));
+    double2* const dir = ctx->tan_dir.as<double2>();
+    double* const ha_dev = ctx->adj_grad.as<double>();
+    double* const hq_dev = ha_dev + n_cells;
+    c5::launch_tangent_gather(v.s, d_alpha, d_q, v.perm, ctx->n_cells, dir);
+    C5_HIP(ctx, hipMemsetAsync(ha_dev, 0, 2 * n_cells * sizeof(double), v.s));
+    if (v.bin_sort) {
+        c5::launch_hvp_resolve(v.s, v.r, dir, grad_out, ha_dev, hq_dev);
+    } else {
+        C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
+        C5_HIP(ctx, ctx->hvp_lambda_dot.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
+        c5::HvpParams hp{};
+        hp.w = v.w;
+        hp.dir = dir;
+        hp.grad_out = grad_out;
+        hp.lambda = ctx->adj_lambda.as<double>();
+        hp.lambda_dot = ctx->hvp_lambda_dot.as<double>();
+        hp.h_a = ha_dev;
+        hp.h_q = hq_dev;
+        c5::launch_hvp_walk(v.s, hp, 1);
+        c5::launch_hvp_walk(v.s, hp, 2);
+        ctx->slots[0].head_clean = true;  // (the second pass hands every head back cleared)
+    }
+    c5::launch_hvp_permute(v.s, ha_dev, hq_dev, v.perm, ctx->n_cells, ha_out, hq_out);
+    return commit_derivative(ctx, "hvp");
+}
+
 // diag(J^T W J): adjoint_one with the squared kernels.  weight null: ones.
 int enqueue_gn_diagonal(c5_context* ctx, const float2* weight, double* da_out, double* dq_out) {
     DerivativeView v;
@@ -587,7 +623,7 @@ int finish_adjoint(c5_context* ctx) {
 
 namespace {
 
-// What the twenty-two derivative entry points check before anything else, in this order: the context; a batch's size; the
+// What the twenty-four derivative entry points check before anything else, in this order: the context; a batch's size; the
 // call's own pointers (`required_ok`, and `per_cell_ok` where the grid has cells); no c5_render_host_async frame
 // outstanding; and for the host-pointer forms the image, after which the device is bound.
 struct DerivativeCall {
@@ -780,6 +816,33 @@ int c5_render_gn_diagonal(c5_context* ctx, const float* weight_host, double* dia
                   {nullptr, diag_q_host, cells_bytes(ctx)}};
     return run_staged(ctx, "gn diagonal", b, [&] {
         return enqueue_gn_diagonal(ctx, b[0].as<const float2>(), b[1].as<double>(), b[2].as<double>());
+    });
+}
+
+int c5_render_hvp_device(c5_context* ctx, const void* d_alpha_dev, const void* d_q_dev, const void* grad_out_dev, void* h_alpha_dev,
+                         void* h_q_dev) {
+    int rc = check_derivative(ctx, {"c5_render_hvp", false, 1, nullptr,
+                                    grad_out_dev && (d_alpha_dev || d_q_dev) && (h_alpha_dev || h_q_dev), true,
+                                    "null hvp pointer: give grad_out, d_alpha or d_q (or both), and h_alpha or h_q (or both)"});
+    if (rc) return rc;
+    return enqueue_hvp(ctx, static_cast<const double*>(d_alpha_dev), static_cast<const double*>(d_q_dev),
+                       static_cast<const float2*>(grad_out_dev), static_cast<double*>(h_alpha_dev), static_cast<double*>(h_q_dev));
+}
+
+int c5_render_hvp(c5_context* ctx, const double* d_alpha_host, const double* d_q_host, const float* grad_out_host, double* h_alpha_host,
+                  double* h_q_host) {
+    int rc = check_derivative(ctx, {"c5_render_hvp", true, 1, nullptr,
+                                    grad_out_host && (d_alpha_host || d_q_host) && (h_alpha_host || h_q_host), true,
+                                    "null hvp pointer: give grad_out, d_alpha or d_q (or both), and h_alpha or h_q (or both)"});
+    if (rc) return rc;
+    Staged b[] = {{grad_out_host, nullptr, image_bytes(ctx)},
+                  {d_alpha_host, nullptr, cells_bytes(ctx)},
+                  {d_q_host, nullptr, cells_bytes(ctx)},
+                  {nullptr, h_alpha_host, cells_bytes(ctx)},
+                  {nullptr, h_q_host, cells_bytes(ctx)}};
+    return run_staged(ctx, "hvp", b, [&] {
+        return enqueue_hvp(ctx, b[1].as<const double>(), b[2].as<const double>(), b[0].as<const float2>(), b[3].as<double>(),
+                           b[4].as<double>());
     });
 }
 

@@ -493,6 +493,165 @@ __global__ __launch_bounds__(256) void gn_diag_resolve(ResolveParams R, const fl
     adj::adjoint_resolve_body<true>(R, weight, diag_a, diag_q);
 }
 
+// ---- Hessian-vector render (c5_render_hvp*) ---------------------------------------------------------------------------
+// h = Hess(phi) v for phi = sum_p (g_tau tau + g_I I) and a direction v = (a_dot, Q_dot) of the cells' scalars.  tau is
+// linear in alpha: only g_I counts.  With lambda_k = g_I T_k, S_k = (1 - E_k) / a_k and its derivatives S_a, S_aa in a,
+// G_k = Q_k S_a,k - dz_k E_k I_{k-1}, Lambda_dot_k = sum_{j <= k} a_dot_j dz_j and lambda_dot_k = -lambda_k (Lambda_dot -
+// Lambda_dot_k) (a_dot_k = 0 where the cell is inactive or its alpha clamped; I_dot as the tangent carries it):
+//     h_q[c]     += lambda_dot_k S_k + lambda_k S_a,k a_dot_k
+//     h_alpha[c] += lambda_dot_k G_k + lambda_k (Q_dot_k S_a,k + Q_k S_aa,k a_dot_k + dz_k^2 E_k a_dot_k I_{k-1} - dz_k E_k I_dot_{k-1})
+// (h_alpha only where alpha is not clamped).
+//   hvp_walk<1>   adjoint_walk<1>'s walk with the direction loaded beside the next record (tangent_walk): Lambda and
+//                 Lambda_dot per pixel.  Leaves the entry lists in place for ...
+//   hvp_walk<2>   ... adjoint_walk<2>'s frame: I, I_dot, Lambda_k, Lambda_dot_k run along, and the segment's (h_alpha, h_q)
+//                 go through scatter_wave.  A pixel with g_I == 0 is not walked.
+//   hvp_resolve   the same over bin_sort_resolve's lists ("algorithm" 1).
+//   hvp_permute   device order -> the caller's; either output may be null.
+
+namespace adj {
+
+template <int PASS>
+__device__ __forceinline__ void hvp_walk_body(const HvpParams& A) {
+    const WalkParams& P = A.w;
+    const D2* __restrict__ dir = reinterpret_cast<const D2*>(A.dir);
+    Ray r;
+    double lam = 0.0, lam_dot = 0.0;                                              // Lambda_k, Lambda_dot_k so far
+    double lam_total = 0.0, lam_dot_total = 0.0, I = 0.0, I_dot = 0.0, g_I = 0.0;  // pass 2
+
+    const EntryHead ent = ray_begin(r, P, [&] {
+        if (PASS == 1) return true;
+        g_I = A.grad_out[r.lp].y;
+        lam_total = A.lambda[r.lp];
+        lam_dot_total = A.lambda_dot[r.lp];
+        return g_I != 0.0;
+    });
+
+    CellRegs cur;
+    D2 d_cur{0.0, 0.0};
+    if (r.cell >= 0) {
+        load_cell(cur, P.xrec, r.cell);
+        d_cur = dir[r.cell];
+    }
+
+    // wave-uniform loop in pass 2 (the scatter wants every lane): a lane whose ray has ended takes part with nothing to add
+    for (;;) {
+        const bool live = r.cell >= 0;
+        if (PASS == 1 ? !live : __builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        bool emit = false;
+        double ha = 0.0, hq = 0.0;
+        const int here = r.cell;
+        if (live) {
+            double dz, carry_next;
+            const int nb = ray_step(r, P, ent, cur, dz, carry_next);
+            CellRegs nxt;
+            D2 d_nxt{0.0, 0.0};
+            if (nb >= 0) {
+                load_cell(nxt, P.xrec, nb);
+                d_nxt = dir[nb];
+            }
+
+            if (is_segment(dz)) {
+                const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+                if (a != 0.0) {
+                    const bool clamped = a != a_raw;
+                    const double a_dot = clamped ? 0.0 : d_cur.a;
+                    // (the same sums in both passes: Lambda_n == Lambda and Lambda_dot_n == Lambda_dot bit for bit)
+                    lam = lambda_add(lam, a, dz);
+                    if (!clamped) lam_dot = lambda_dot_add(lam_dot, a_dot, dz);
+                    if (PASS == 2) {
+                        emit = true;
+                        const double T = exp_nonpositive(fmin(lam - lam_total, 0.0));
+                        const double E = exp_nonpositive(-a * dz);
+                        const double lambda = g_I * T;
+                        const double lambda_dot = -lambda * (lam_dot_total - lam_dot);
+                        hvp_step(a, clamped, q, dz, E, a_dot, d_cur.b, lambda, lambda_dot, I, I_dot, ha, hq);
+                    }
+                }
+            }
+            ray_advance(r, nb, carry_next);
+            cur = nxt;
+            d_cur = d_nxt;
+        }
+        if (PASS == 2) scatter_wave(emit, here, ha, hq, A.h_a, A.h_q);
+    }
+
+    if (PASS == 1) {
+        if (r.in_image) {
+            A.lambda[r.lp] = lam;
+            A.lambda_dot[r.lp] = lam_dot;
+        }
+        ray_count(r, P);
+    } else {
+        ray_clear_head(r, P);
+    }
+}
+
+}  // namespace adj
+
+template <int PASS>
+__global__ __launch_bounds__(64) void hvp_walk(HvpParams A) {
+    adj::hvp_walk_body<PASS>(A);
+}
+
+// adjoint_resolve's frame with the tangent carried along; Lambda and Lambda_dot from a pre-pass over the sorted list, in
+// the order the loop re-sums them.
+__global__ __launch_bounds__(256) void hvp_resolve(ResolveParams R, const double2* __restrict__ dir_v, const float2* __restrict__ grad_out,
+                                                   double* __restrict__ h_a, double* __restrict__ h_q) {
+    using namespace adj;
+    const GridView& g = R.g;
+    const D2* __restrict__ dir = reinterpret_cast<const D2*>(dir_v);
+    double g_I = 0.0;
+    const ListFrame f = list_frame<false>(R, [&](int64_t lp) {
+        g_I = grad_out[lp].y;
+        return g_I != 0.0;
+    });
+    const double lam_total = lambda_total(f.list, f.n, g, R.alpha_limit);
+    double lam_dot_total = 0.0;
+    for (int i = f.n - 1; i >= 0; --i) {
+        const int c = static_cast<int>(f.list[i].cell);
+        const ClampedAlpha ca = clamp_alpha(g.alpha[c], R.alpha_limit);
+        if (ca.active && !ca.clamped) lam_dot_total = lambda_dot_add(lam_dot_total, dir[c].a, f.list[i].dz);
+    }
+    double lam = 0.0, lam_dot = 0.0, I = 0.0, I_dot = 0.0;
+    // wave-uniform loop over the steps (the scatter wants every lane)
+    for (int i = f.n - 1;; --i) {
+        const bool live = i >= 0;
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        int c = -1;
+        bool emit = false;
+        double ha = 0.0, hq = 0.0;
+        if (live) {
+            c = static_cast<int>(f.list[i].cell);
+            const double dz = f.list[i].dz, q = g.q[c];
+            const ClampedAlpha ca = clamp_alpha(g.alpha[c], R.alpha_limit);
+            if (ca.active) {
+                const D2 d = dir[c];
+                const double a = ca.a, a_dot = ca.clamped ? 0.0 : d.a;
+                lam = lambda_add(lam, a, dz);
+                if (!ca.clamped) lam_dot = lambda_dot_add(lam_dot, a_dot, dz);
+                emit = true;
+                const double T = exp(fmin(lam - lam_total, 0.0));
+                const double E = exp(-a * dz);
+                const double lambda = g_I * T;
+                const double lambda_dot = -lambda * (lam_dot_total - lam_dot);
+                hvp_step(a, ca.clamped, q, dz, E, a_dot, d.b, lambda, lambda_dot, I, I_dot, ha, hq);
+            }
+        }
+        scatter_wave(emit, c, ha, hq, h_a, h_q);
+    }
+}
+
+// adjoint_permute with either output null
+__global__ __launch_bounds__(256) void hvp_permute(const double* __restrict__ ha_dev, const double* __restrict__ hq_dev,
+                                                   const int32_t* __restrict__ perm, int64_t n, double* __restrict__ ha_out,
+                                                   double* __restrict__ hq_out) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n) return;
+    const int64_t d = perm ? static_cast<int64_t>(perm[i]) : i;
+    if (ha_out) ha_out[d] = ha_dev[i];
+    if (hq_out) hq_out[d] = hq_dev[i];
+}
+
 // c5_update_scalars_device: the gather into device order, and c5_update_scalars' three statistics as bit-pattern maxima
 // (non-negative doubles order as their bits do; the smallest one is the largest complement).  A grid-stride loop over a
 // few hundred workgroups, reduced per workgroup: one atomic per statistic and workgroup (atomics on one address are
@@ -601,7 +760,24 @@ void launch_gn_diag_resolve(hipStream_t s, const ResolveParams& r, const float2*
     if (const unsigned blocks = pixel_blocks(r.im)) hipLaunchKernelGGL(gn_diag_resolve, dim3(blocks), dim3(256), 0, s, r, weight, diag_a, diag_q);
 }
 
-void launch_scalars_gather(hipStream_t s, const double* alpha_src, const double* q_src, const int32_t* perm, int64_t n, double* alpha,
+void launch_hvp_walk(hipStream_t s, const HvpParams& h, int pass) {
+    const unsigned blocks = tile_blocks(h.w.im);
+    if (!blocks) return;
+    if (pass == 1) hipLaunchKernelGGL(hvp_walk<1>, dim3(blocks), dim3(64), 0, s, h);
+    else hipLaunchKernelGGL(hvp_walk<2>, dim3(blocks), dim3(64), 0, s, h);
+}
+
+void launch_hvp_resolve(hipStream_t s, const ResolveParams& r, const double2* dir, const float2* grad_out, double* h_a, double* h_q) {
+    if (const unsigned blocks = pixel_blocks(r.im)) hipLaunchKernelGGL(hvp_resolve, dim3(blocks), dim3(256), 0, s, r, dir, grad_out, h_a, h_q);
+}
+
+void launch_hvp_permute(hipStream_t s, const double* ha_dev, const double* hq_dev, const int32_t* perm, int64_t n, double* ha_out,
+                        double* hq_out) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(hvp_permute, dim3(item_blocks(n)), dim3(256), 0, s, ha_dev, hq_dev, perm, n, ha_out, hq_out);
+}
+
+void launch_scalars_gather(hipStream_t s,const double* alpha_src, const double* q_src, const int32_t* perm, int64_t n, double* alpha,
                            double* q, unsigned long long* stats) {
     if (n <= 0) return;
     const unsigned blocks = static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, kScalarBlocks));

@@ -17,6 +17,11 @@ A context may bring its own operators: if it has a method gn_operators(alpha, q,
 rhs(residual) -> (J^T W r)_alpha, (..)_q, diagonal() -> (diag_alpha, diag_q) and product(v_alpha, v_q) -> (h_alpha, h_q)
 (torch float64 tensors; v_alpha / v_q None: zero), gn_step uses those - a set of row shards that sums its parts, a dense
 model.
+
+newton_product and newton_step are the same with the EXACT Hessian of 1/2 sum w r^2: H + sum_p w_p r_p Hess(img_p), the
+second term from autograd.hvp (c5_render_hvp) on grad_img = W r.  The frame is exponential in alpha, so a fit of alpha is
+not a linear least-squares problem and the two differ by the residual-weighted curvature; in q alone they coincide.  A
+context's own operators then also need hvp(v_alpha, v_q, grad_img) -> (h_alpha, h_q).
 """
 from __future__ import annotations
 
@@ -52,19 +57,33 @@ class _LibraryOperators:
         from . import autograd
         return autograd.gn_product(self.ctx, self.alpha, self.q, v_alpha, v_q, self.weight)
 
+    def hvp(self, v_alpha, v_q, grad_img):
+        from . import autograd
+        return autograd.hvp(self.ctx, self.alpha, self.q, v_alpha, v_q, grad_img)
 
-def gn_step(ctx, alpha, q, residual, weight=None, fit=("q",), damping: float = 0.0, iters: int = 10, precondition: bool = True):
-    """Up to `iters` iterations of (Jacobi-preconditioned) CG from d = 0 on (H + damping diag(H)) d = -J^T W r over the
-    fields named in `fit` ("alpha", "q" or both; the other is held fixed).  Returns ((d_alpha, d_q), models): the step
-    (None for a field not fitted) and the model value m(d_i) after every iteration done, as floats.  It stops early when
-    the residual of the linear system vanishes or a direction has no curvature."""
+
+def _weighted(residual, weight):
+    """W r as the upstream image of the curvature term (float32, as the right-hand side forms it)."""
+    g = residual.detach().to(torch.float32)
+    if weight is not None:
+        g = g * weight.detach().to(device=g.device, dtype=torch.float32)
+    return g.contiguous()
+
+
+def _operators(ctx, alpha, q, weight):
+    return ctx.gn_operators(alpha, q, weight) if hasattr(ctx, "gn_operators") else _LibraryOperators(ctx, alpha, q, weight)
+
+
+def _cg_step(ctx, alpha, q, residual, weight, fit, damping, iters, precondition, exact):
+    """gn_step (exact False: H = J^T W J) and newton_step (exact True: H the exact Hessian of 1/2 sum w r^2)."""
     fit = tuple(fit)
     if not fit or any(f not in ("alpha", "q") for f in fit) or len(set(fit)) != len(fit):
         raise ValueError(f"fit must name 'alpha', 'q' or both, not {fit!r}")
     if damping < 0.0 or iters < 1:
         raise ValueError("damping must be >= 0 and iters >= 1")
-    ops = ctx.gn_operators(alpha, q, weight) if hasattr(ctx, "gn_operators") else _LibraryOperators(ctx, alpha, q, weight)
+    ops = _operators(ctx, alpha, q, weight)
     n = alpha.shape[0]
+    wr = _weighted(residual, weight) if exact else None
 
     def pick(a, b):
         return torch.cat([t for name, t in (("alpha", a), ("q", b)) if name in fit])
@@ -75,7 +94,9 @@ def gn_step(ctx, alpha, q, residual, weight=None, fit=("q",), damping: float = 0
         return (x, None) if fit[0] == "alpha" else (None, x)
 
     def H(x):
-        return pick(*ops.product(*split(x)))
+        va, vq = split(x)
+        h = pick(*ops.product(va, vq))
+        return h + pick(*ops.hvp(va, vq, wr)) if exact else h
 
     g = pick(*ops.rhs(residual)).to(torch.float64)  # J^T W r
     d = pick(*ops.diagonal()).to(torch.float64)
@@ -96,6 +117,8 @@ def gn_step(ctx, alpha, q, residual, weight=None, fit=("q",), damping: float = 0
         ap = hp + damping * d * p
         curvature = float(p @ ap)
         if not curvature > 0.0:
+            if exact and not models:
+                x = p.clone()  # (nothing else to return: steepest descent in the preconditioner's metric)
             break
         step = rz / curvature
         x += step * p
@@ -107,6 +130,36 @@ def gn_step(ctx, alpha, q, residual, weight=None, fit=("q",), damping: float = 0
         p = z + (rz_next / rz) * p
         rz = rz_next
     return split(x), models
+
+
+def gn_step(ctx, alpha, q, residual, weight=None, fit=("q",), damping: float = 0.0, iters: int = 10, precondition: bool = True):
+    """Up to `iters` iterations of (Jacobi-preconditioned) CG from d = 0 on (H + damping diag(H)) d = -J^T W r over the
+    fields named in `fit` ("alpha", "q" or both; the other is held fixed).  Returns ((d_alpha, d_q), models): the step
+    (None for a field not fitted) and the model value m(d_i) after every iteration done, as floats.  It stops early when
+    the residual of the linear system vanishes or a direction has no curvature."""
+    return _cg_step(ctx, alpha, q, residual, weight, fit, damping, iters, precondition, exact=False)
+
+
+def newton_product(ctx, alpha, q, residual, v_alpha, v_q, weight=None) -> tuple:
+    """(h_alpha, h_q) = Hess(1/2 sum w r^2) (v_alpha, v_q) at (alpha, q), r = render(alpha, q) - target the residual image
+    ([local_rows, res_x, 2]) and w the per-pixel weights (None: ones): gn_product(v) + hvp(v, grad_img = W r), the
+    Gauss-Newton product plus the residual-weighted curvature it leaves out.  v_alpha / v_q [n_cells], either may be None
+    (zero).  Two library calls; float64 on the context's GPU."""
+    ops = _operators(ctx, alpha, q, weight)
+    ga, gq = ops.product(v_alpha, v_q)
+    ha, hq = ops.hvp(v_alpha, v_q, _weighted(residual, weight))
+    return ga + ha, gq + hq
+
+
+def newton_step(ctx, alpha, q, residual, weight=None, fit=("q",), damping: float = 0.0, iters: int = 10):
+    """gn_step with the exact Hessian: up to `iters` iterations of Jacobi-preconditioned CG from d = 0 on
+        (Hess(1/2 sum w r^2) + damping diag(J^T W J)) d = -J^T W r
+    over the fields named in `fit`, one gn_product and one hvp per iteration (newton_product); the preconditioner is the
+    Gauss-Newton diagonal.  The exact Hessian can be indefinite: the iteration stops at the first direction without
+    positive curvature and returns what it has - if that is the very first direction, the preconditioned steepest-descent
+    direction itself (its model value is then not appended: the model has no minimum along it).  Returns ((d_alpha, d_q),
+    models) as gn_step does.  No line search and no outer loop: the caller owns both."""
+    return _cg_step(ctx, alpha, q, residual, weight, fit, damping, iters, True, exact=True)
 
 
 def view_step(ctx, alpha, q, angles, residual, weight=None, damping: float = 0.0):

@@ -375,6 +375,40 @@ int c5_render_gn_product_device(c5_context* ctx, int n_dirs, const void* d_alpha
 int c5_render_gn_diagonal(c5_context* ctx, const float* weight_host, double* diag_alpha_host, double* diag_q_host);
 int c5_render_gn_diagonal_device(c5_context* ctx, const void* weight_dev, void* diag_alpha_dev, void* diag_q_dev);
 
+/* --- Hessian-vector render ---------------------------------------------------------------------------
+ * The exact second derivative of the frame c5_render would produce now in the cells' (alpha, Q), applied to one
+ * direction: with phi = sum over the pixels of g_tau tau + g_I I for an upstream image grad_out = (g_tau, g_I),
+ *     (h_alpha, h_q) = Hess(phi) (d_alpha, d_q),
+ * the residual-weighted curvature sum_p g_p Hess(I_p) v that the Gauss-Newton product leaves out: c5_render_gn_product
+ * (weight W) plus this call on grad_out = W r is the exact Hessian product of 1/2 sum w r^2, r the residual image.
+ * tau is linear in alpha: channel 0 of grad_out is read and has no effect, and a pixel with g_I == 0 is not walked.
+ * With the adjoint's numbering and conventions (segments k = 1..n, deepest first; a_k = min(alpha_k, limit); E_k =
+ * exp(-a_k dz_k); T_k the transmittance to the viewer; Lambda_k = sum_{j <= k} a_j dz_j), lambda_k = g_I T_k,
+ *     S_k    = (1 - E_k) / a_k,   S_a = dz E / a - (1 - E) / a^2,   S_aa = 2 (1 - E) / a^3 - 2 dz E / a^2 - dz^2 E / a
+ * (S_a and S_aa by their series below a dz = 1/8), G_k = Q_k S_a,k - dz_k E_k I_{k-1}, and for the direction
+ *     a_dot_k = d_alpha[cell_k] where the cell is active and its alpha not clamped, else 0 (a clamped alpha does not
+ *               move: no row and no column, as in c5_render_adjoint);   Q_dot_k = d_q[cell_k];
+ *     I_dot_k = E_k I_dot_{k-1} - dz_k E_k a_dot_k I_{k-1} + Q_dot_k S_k + Q_k S_a,k a_dot_k     (c5_render_tangent's I_dot)
+ *     Lambda_dot_k = sum_{j <= k} a_dot_j dz_j,   lambda_dot_k = -lambda_k (Lambda_dot_n - Lambda_dot_k)
+ * every segment adds to its cell
+ *     h_q     += lambda_dot_k S_k + lambda_k S_a,k a_dot_k
+ *     h_alpha += lambda_dot_k G_k + lambda_k (Q_dot_k S_a,k + Q_k S_aa,k a_dot_k + dz_k^2 E_k a_dot_k I_{k-1} - dz_k E_k I_dot_{k-1})
+ * (h_alpha only where alpha is not clamped).  Inactive cells and solid-marked pixels add nothing.  The operator is
+ * symmetric, in general indefinite, and its Q-Q block is zero (I is linear in Q).
+ * d_alpha / d_q [n_cells] fp64 in the caller's cell order; either may be NULL (zero), both NULL is C5_ERR_INVALID.
+ * grad_out [local_rows][res_x][2] fp32, required.  h_alpha / h_q [n_cells] fp64 in the caller's order, overwritten;
+ * either may be NULL, not both.  The sums are fp64 atomics in arrival order: NOT bit-reproducible from run to run (the
+ * last bits move), as the adjoint's.  Row ranges and row tiles, side effects, status and retries as the adjoint's (its
+ * counters and status words, never a frame's; a c5_render afterwards returns the bits it would have returned without
+ * the call): c5_render_hvp is synchronous and retries by itself on C5_RETRY; the _device form is asynchronous on the
+ * context's stream with device arrays and reports through the next call that waits for it.  Memory is allocated at the
+ * first call only: the adjoint's and the tangent's buffers and 8 bytes more per local pixel.  Both refuse while
+ * c5_render_host_async frames are outstanding. */
+int c5_render_hvp(c5_context* ctx, const double* d_alpha_host, const double* d_q_host, const float* grad_out_host,
+                  double* h_alpha_host, double* h_q_host);
+int c5_render_hvp_device(c5_context* ctx, const void* d_alpha_dev, const void* d_q_dev, const void* grad_out_dev,
+                         void* h_alpha_dev, void* h_q_dev);
+
 /* --- motion tangent render ---------------------------------------------------------------------------
  * The frame c5_render would produce NOW differentiated with respect to the GEOMETRY, the cells' scalars held: the grid
  * moves in view space with an affine velocity field u(p) = A p + b, and out is the change of every pixel per unit of that
