@@ -71,6 +71,8 @@ context's GPU (c5_ray_matrix_rows_device, c5_ray_matrix_fill_device), for solver
 """
 from __future__ import annotations
 
+from contextlib import contextmanager, nullcontext
+
 import numpy as np
 import torch
 
@@ -95,11 +97,43 @@ def _run(ctx: capi.Context, enqueue) -> None:
     raise capi.C5Error(capi.C5_RETRY, "the frame kept needing to be rendered again")
 
 
+@contextmanager
+def _on_gpu(ctx: capi.Context, unwrapped: bool = False):
+    """The context's GPU as torch's current device, and as what the block gets.  unwrapped: torch.func's dispatch is off
+    inside (under torch.func.jvp / vmap the arguments arrive wrapped, with no storage of their own: the library reads
+    plain tensors, _plain's)."""
+    device = torch.device("cuda", ctx.device)
+    with torch._C._DisableFuncTorch() if unwrapped else nullcontext(), torch.cuda.device(device):
+        yield device
+
+
+def _launch(ctx: capi.Context, device: torch.device, enqueue) -> None:
+    """enqueue() on torch's current stream, after what torch has queued there (the call's inputs), and waited for."""
+    _use_torch_stream(ctx, device)
+    _run(ctx, enqueue)
+
+
 def _plain(t: torch.Tensor) -> torch.Tensor:
     """t without torch.func's wrappers."""
     while torch._C._functorch.is_functorch_wrapped_tensor(t):
         t = torch._C._functorch.get_unwrapped(t)
     return t
+
+
+def _lift(t: torch.Tensor, dim, k: int) -> torch.Tensor:
+    """_plain(t) with its batch dimension first; an unbatched one (dim None) is the same for every one of the k."""
+    t = _plain(t).detach()
+    return t.movedim(dim, 0) if dim is not None else t.expand(k, *t.shape)
+
+
+def _cell_pair(ctx: capi.Context, device: torch.device, *k) -> tuple:
+    """Two float64 [*k, n_cells] results on the context's GPU."""
+    return tuple(torch.empty((*k, ctx.n_cells), dtype=torch.float64, device=device) for _ in range(2))
+
+
+def _frames(ctx: capi.Context, device: torch.device, *k) -> torch.Tensor:
+    """A float32 [*k, local_rows, res_x, 2] result on the context's GPU."""
+    return torch.empty((*k, ctx.local_rows, ctx.res_x, 2), dtype=torch.float32, device=device)
 
 
 class _Scalars:
@@ -111,10 +145,19 @@ class _Scalars:
         self.alpha, self.q = alpha, q
 
 
+def _scalars_of(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor) -> _Scalars:
+    """alpha and q as the context takes them: float64 on its GPU when they are there, else numpy arrays on the host.  A copy
+    of their own either way: the caller may change alpha and q in place before a backward."""
+    if alpha.shape != (ctx.n_cells,) or q.shape != (ctx.n_cells,):
+        raise ValueError(f"alpha and q must hold one value per cell ({ctx.n_cells})")
+    if all(t.is_cuda and t.device.index == ctx.device for t in (alpha, q)):
+        return _Scalars(*(t.detach().to(dtype=torch.float64, copy=True).contiguous() for t in (alpha, q)))
+    return _Scalars(*(t.detach().to("cpu", torch.float64).contiguous().numpy().copy() for t in (alpha, q)))
+
+
 def _upload(ctx: capi.Context, owner: _Scalars) -> None:
     if isinstance(owner.alpha, torch.Tensor):
-        device = torch.device("cuda", ctx.device)
-        with torch.cuda.device(device):
+        with _on_gpu(ctx) as device:
             _use_torch_stream(ctx, device)
             ctx.update_scalars_device(owner.alpha, owner.q)
     else:
@@ -163,120 +206,108 @@ def _tangent_arg(t, device: torch.device):
     return None if t is None else _plain(t).detach().to(device=device, dtype=torch.float64).contiguous()
 
 
-class _Tangent(torch.autograd.Function):
-    """J v: the tangent render of the frame of `fr` (the forward's autograd context); alpha and q only mark what the
-    result depends on.  Batched under vmap."""
-
-    @staticmethod
-    def forward(fr, alpha, q, alpha_t, q_t):
-        ctx = _current(fr, "jvp")
-        device = torch.device("cuda", ctx.device)
-        # under torch.func.jvp the tangents arrive wrapped (no storage of their own): the library reads plain tensors
-        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
-            da, dq = _tangent_arg(alpha_t, device), _tangent_arg(q_t, device)
-            out = torch.empty((ctx.local_rows, ctx.res_x, 2), dtype=torch.float32, device=device)
-            _use_torch_stream(ctx, device)
-            _run(ctx, lambda: ctx.render_tangent_device(da, dq, out))
-        return out
+class _Operator(torch.autograd.Function):
+    """A derivative render of the frame of `fr` (the forward's autograd context, the first argument) as a Function of its
+    own, so that torch.func can batch it (vmap); the primals after `fr` only mark what the result depends on.  It has no
+    derivative: backward and jvp refuse, naming the render (`what`).  A subclass gives what, forward and vmap."""
+    what = ""
 
     @staticmethod
     def setup_context(fctx, inputs, output):
         pass
 
-    @staticmethod
-    def backward(fctx, *grads):
-        _no_second("tangent")
+    @classmethod
+    def backward(cls, fctx, *grads):
+        _no_second(cls.what)
+
+    @classmethod
+    def jvp(cls, fctx, *tangents):
+        _no_second(cls.what)
+
+
+class _Tangent(_Operator):
+    """J v: the tangent render of the frame of `fr` (the forward's autograd context); alpha and q only mark what the
+    result depends on.  Batched under vmap."""
+    what = "tangent"
 
     @staticmethod
-    def jvp(fctx, *tangents):
-        _no_second("tangent")
+    def forward(fr, alpha, q, alpha_t, q_t):
+        ctx = _current(fr, "jvp")
+        with _on_gpu(ctx, unwrapped=True) as device:
+            da, dq = _tangent_arg(alpha_t, device), _tangent_arg(q_t, device)
+            out = _frames(ctx, device)
+            _launch(ctx, device, lambda: ctx.render_tangent_device(da, dq, out))
+        return out
 
     @staticmethod
     def vmap(info, in_dims, fr, alpha, q, alpha_t, q_t):
         _unbatched_primals(in_dims[1:3])
         ctx = _current(fr, "jvp")
-        device = torch.device("cuda", ctx.device)
         k = info.batch_size
-
-        def lift(t, d):  # the batch dimension first; an unbatched tangent is the same for every direction
-            if t is None:
-                return None
-            t = _plain(t).detach()
-            t = t.movedim(d, 0) if d is not None else t.expand(k, *t.shape)
-            return t.to(device=device, dtype=torch.float64).contiguous()
-
-        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
-            da, dq = lift(alpha_t, in_dims[3]), lift(q_t, in_dims[4])
-            out = torch.empty((k, ctx.local_rows, ctx.res_x, 2), dtype=torch.float32, device=device)
-            _use_torch_stream(ctx, device)
-            _run(ctx, lambda: ctx.render_tangent_batch_device(da, dq, out, n=k))
+        with _on_gpu(ctx, unwrapped=True) as device:
+            da, dq = (None if t is None else _lift(t, d, k).to(device=device, dtype=torch.float64).contiguous()
+                      for t, d in ((alpha_t, in_dims[3]), (q_t, in_dims[4])))
+            out = _frames(ctx, device, k)
+            _launch(ctx, device, lambda: ctx.render_tangent_batch_device(da, dq, out, n=k))
         return out, 0
 
 
-class _Adjoint(torch.autograd.Function):
+def _adjoint(ctx: capi.Context, g: torch.Tensor, device: torch.device) -> tuple:
+    """(grad_alpha, grad_q), float64 [n_cells] each on the context's GPU: the adjoint render for the upstream image g
+    (float32, contiguous, there), on torch's current stream."""
+    ga, gq = _cell_pair(ctx, device)
+    _launch(ctx, device, lambda: ctx.render_adjoint_device(g, ga, gq))
+    return ga, gq
+
+
+class _Adjoint(_Operator):
     """J^T g: the adjoint render of the frame of `fr`; (grad_alpha, grad_q) float64 on the context's GPU.  Batched under
     vmap."""
+    what = "adjoint"
 
     @staticmethod
     def forward(fr, alpha, q, grad_img):
         ctx = _current(fr, "backward")
-        device = torch.device("cuda", ctx.device)
-        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
-            g = _plain(grad_img).detach().to(device=device, dtype=torch.float32).contiguous()
-            ga = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
-            gq = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
-            _use_torch_stream(ctx, device)
-            _run(ctx, lambda: ctx.render_adjoint_device(g, ga, gq))
-        return ga, gq
-
-    @staticmethod
-    def setup_context(fctx, inputs, output):
-        pass
-
-    @staticmethod
-    def backward(fctx, *grads):
-        _no_second("adjoint")
-
-    @staticmethod
-    def jvp(fctx, *tangents):
-        _no_second("adjoint")
+        with _on_gpu(ctx, unwrapped=True) as device:
+            return _adjoint(ctx, _plain(grad_img).detach().to(device=device, dtype=torch.float32).contiguous(), device)
 
     @staticmethod
     def vmap(info, in_dims, fr, alpha, q, grad_img):
         _unbatched_primals(in_dims[1:3])
         ctx = _current(fr, "backward")
-        device = torch.device("cuda", ctx.device)
-        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
-            g = _plain(grad_img).detach()
-            g = g.movedim(in_dims[3], 0) if in_dims[3] is not None else g.expand(info.batch_size, *g.shape)
-            g = g.to(device=device, dtype=torch.float32).contiguous()
+        with _on_gpu(ctx, unwrapped=True) as device:
+            g = _lift(grad_img, in_dims[3], info.batch_size).to(device=device, dtype=torch.float32).contiguous()
             k = g.shape[0]
-            ga = torch.empty((k, ctx.n_cells), dtype=torch.float64, device=device)
-            gq = torch.empty((k, ctx.n_cells), dtype=torch.float64, device=device)
-            _use_torch_stream(ctx, device)
-            _run(ctx, lambda: ctx.render_adjoint_batch_device(g, ga, gq, n=k))
+            ga, gq = _cell_pair(ctx, device, k)
+            _launch(ctx, device, lambda: ctx.render_adjoint_batch_device(g, ga, gq, n=k))
         return (ga, gq), (0, 0)
+
+
+def _scalar_grads(fctx, ga: torch.Tensor, gq: torch.Tensor, i_alpha: int, i_q: int) -> tuple:
+    """The adjoint's (ga, gq) in the dtype and on the device of alpha and q; None for the one needs_input_grad (at i_alpha,
+    i_q) does not ask for."""
+    return tuple(g.to(device=dev, dtype=dtype) if fctx.needs_input_grad[i] else None
+                 for g, (dtype, dev), i in zip((ga, gq), fctx.meta, (i_alpha, i_q)))
+
+
+def _tangent_sum(fctx, alpha, q, alpha_t, q_t, other):
+    """The scalar tangent's image when alpha or q carry a tangent, plus other() (the image of another input's tangent) when
+    there is one, added in float32; None when there is neither."""
+    out = _Tangent.apply(fctx, alpha, q, alpha_t, q_t) if alpha_t is not None or q_t is not None else None
+    if other is not None:
+        t = other()
+        out = t if out is None else out + t
+    return out
 
 
 class _Render(torch.autograd.Function):
     @staticmethod
     def forward(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor):
-        if alpha.shape != (ctx.n_cells,) or q.shape != (ctx.n_cells,):
-            raise ValueError(f"alpha and q must hold one value per cell ({ctx.n_cells})")
-        device = torch.device("cuda", ctx.device)
-        on_gpu = all(t.is_cuda and t.device.index == ctx.device for t in (alpha, q))
-        if not on_gpu:
-            a_host = alpha.detach().to("cpu", torch.float64).contiguous().numpy().copy()
-            q_host = q.detach().to("cpu", torch.float64).contiguous().numpy().copy()
-            ctx.update_scalars(a_host, q_host)
-            ctx.scalars_owner = _Scalars(a_host, q_host)  # (setup_context takes it from here)
-        out = torch.empty((ctx.local_rows, ctx.res_x, 2), dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            _use_torch_stream(ctx, device)
-            if on_gpu:  # (a copy of their own: the caller may change alpha and q in place before a backward)
-                _upload(ctx, _Scalars(alpha.detach().to(dtype=torch.float64, copy=True).contiguous(),
-                                      q.detach().to(dtype=torch.float64, copy=True).contiguous()))
-            _run(ctx, lambda: ctx.render_device(out.data_ptr()))
+        owner = _scalars_of(ctx, alpha, q)
+        with _on_gpu(ctx) as device:
+            _upload(ctx, owner)  # (setup_context takes it from the context's scalars_owner)
+            out = _frames(ctx, device)
+            _launch(ctx, device, lambda: ctx.render_device(out.data_ptr()))
         return out
 
     @staticmethod
@@ -293,11 +324,7 @@ class _Render(torch.autograd.Function):
     def backward(fctx, grad_img: torch.Tensor):
         _first_order(fctx, "backward")
         alpha, q = fctx.primals
-        ga, gq = _Adjoint.apply(fctx, alpha, q, grad_img)
-        (a_dtype, a_dev), (q_dtype, q_dev) = fctx.meta
-        ga_out = ga.to(device=a_dev, dtype=a_dtype) if fctx.needs_input_grad[1] else None
-        gq_out = gq.to(device=q_dev, dtype=q_dtype) if fctx.needs_input_grad[2] else None
-        return None, ga_out, gq_out
+        return (None, *_scalar_grads(fctx, *_Adjoint.apply(fctx, alpha, q, grad_img), 1, 2))
 
     @staticmethod
     def jvp(fctx, _ctx_tangent, alpha_t, q_t):
@@ -332,15 +359,15 @@ def _set_angles(ctx: capi.Context, angles: torch.Tensor) -> None:
 
 def _motion(ctx: capi.Context, fields, device: torch.device) -> torch.Tensor:
     """[K, local_rows, res_x, 2] float32 on the context's GPU: the motion tangent render for fields [K, 12] (numpy)."""
-    with torch._C._DisableFuncTorch(), torch.cuda.device(device):
-        out = torch.empty((len(fields), ctx.local_rows, ctx.res_x, 2), dtype=torch.float32, device=device)
-        _use_torch_stream(ctx, device)
-        _run(ctx, lambda: ctx.render_motion_tangent_device(fields, out))
+    with _on_gpu(ctx, unwrapped=True):
+        out = _frames(ctx, device, len(fields))
+        _launch(ctx, device, lambda: ctx.render_motion_tangent_device(fields, out))
     return out
 
 
-class _ViewTangent(torch.autograd.Function):
+class _ViewTangent(_Operator):
     """d img / d angles . t: one motion tangent render for the field sum_i t_i field_i.  Batched under vmap."""
+    what = "motion tangent"
 
     @staticmethod
     def forward(fr, alpha, q, angles, angles_t):
@@ -349,30 +376,17 @@ class _ViewTangent(torch.autograd.Function):
         return _motion(ctx, t @ ctx.view_fields(), torch.device("cuda", ctx.device))[0]
 
     @staticmethod
-    def setup_context(fctx, inputs, output):
-        pass
-
-    @staticmethod
-    def backward(fctx, *grads):
-        _no_second("motion tangent")
-
-    @staticmethod
-    def jvp(fctx, *tangents):
-        _no_second("motion tangent")
-
-    @staticmethod
     def vmap(info, in_dims, fr, alpha, q, angles, angles_t):
         _unbatched_primals(in_dims[1:4])
         ctx = _current(fr, "jvp")
-        t = _plain(angles_t).detach()
-        t = t.movedim(in_dims[4], 0) if in_dims[4] is not None else t.expand(info.batch_size, *t.shape)
-        t = t.to("cpu", torch.float64).reshape(info.batch_size, -1).numpy()
+        t = _lift(angles_t, in_dims[4], info.batch_size).to("cpu", torch.float64).reshape(info.batch_size, -1).numpy()
         return _motion(ctx, t @ ctx.view_fields(), torch.device("cuda", ctx.device)), 0
 
 
-class _ViewAdjoint(torch.autograd.Function):
+class _ViewAdjoint(_Operator):
     """grad_angles[i] = sum g * d img / d angle_i, summed in fp64: one motion tangent render for all the angles.  A batch
     of upstream images (vmap) shares it."""
+    what = "motion tangent"
 
     @staticmethod
     def forward(fr, alpha, q, angles, grad_img):
@@ -384,27 +398,13 @@ class _ViewAdjoint(torch.autograd.Function):
             return (imgs.to(torch.float64) * g).sum(dim=(1, 2, 3))
 
     @staticmethod
-    def setup_context(fctx, inputs, output):
-        pass
-
-    @staticmethod
-    def backward(fctx, *grads):
-        _no_second("motion tangent")
-
-    @staticmethod
-    def jvp(fctx, *tangents):
-        _no_second("motion tangent")
-
-    @staticmethod
     def vmap(info, in_dims, fr, alpha, q, angles, grad_img):
         _unbatched_primals(in_dims[1:4])
         ctx = _current(fr, "backward")
         device = torch.device("cuda", ctx.device)
         imgs = _motion(ctx, ctx.view_fields(), device)
         with torch._C._DisableFuncTorch():
-            g = _plain(grad_img).detach()
-            g = g.movedim(in_dims[4], 0) if in_dims[4] is not None else g.expand(info.batch_size, *g.shape)
-            g = g.to(device=device, dtype=torch.float64)
+            g = _lift(grad_img, in_dims[4], info.batch_size).to(device=device, dtype=torch.float64)
             return torch.einsum("kyxc,nyxc->kn", g, imgs.to(torch.float64)), 0
 
 
@@ -427,10 +427,7 @@ class _RenderView(torch.autograd.Function):
         alpha, q, angles = fctx.primals
         ga_out = gq_out = gv_out = None
         if fctx.needs_input_grad[1] or fctx.needs_input_grad[2]:
-            ga, gq = _Adjoint.apply(fctx, alpha, q, grad_img)
-            (a_dtype, a_dev), (q_dtype, q_dev) = fctx.meta
-            ga_out = ga.to(device=a_dev, dtype=a_dtype) if fctx.needs_input_grad[1] else None
-            gq_out = gq.to(device=q_dev, dtype=q_dtype) if fctx.needs_input_grad[2] else None
+            ga_out, gq_out = _scalar_grads(fctx, *_Adjoint.apply(fctx, alpha, q, grad_img), 1, 2)
         if fctx.needs_input_grad[3]:
             dtype, dev = fctx.angles_meta
             gv_out = _ViewAdjoint.apply(fctx, alpha, q, angles, grad_img).to(device=dev, dtype=dtype)
@@ -441,13 +438,8 @@ class _RenderView(torch.autograd.Function):
         _current(fctx, "jvp")
         _first_order(fctx, "jvp")
         alpha, q, angles = getattr(fctx, "primals", (None, None, None))
-        out = None
-        if alpha_t is not None or q_t is not None:
-            out = _Tangent.apply(fctx, alpha, q, alpha_t, q_t)
-        if angles_t is not None:
-            t = _ViewTangent.apply(fctx, alpha, q, angles, angles_t)
-            out = t if out is None else out + t
-        return out
+        return _tangent_sum(fctx, alpha, q, alpha_t, q_t,
+                            None if angles_t is None else lambda: _ViewTangent.apply(fctx, alpha, q, angles, angles_t))
 
     @staticmethod
     def vmap(info, in_dims, ctx, alpha, q, angles):
@@ -474,44 +466,28 @@ def _set_points(ctx: capi.Context, xyz: torch.Tensor) -> None:
 def _vertex_adjoint(ctx: capi.Context, g: torch.Tensor, device: torch.device) -> torch.Tensor:
     """[n_pts, 3] float64 on the context's GPU: the vertex adjoint render for the upstream image g (float32, there)."""
     out = torch.empty((ctx.n_pts, 3), dtype=torch.float64, device=device)
-    _use_torch_stream(ctx, device)
-    _run(ctx, lambda: ctx.render_vertex_adjoint_device(g, out))
+    _launch(ctx, device, lambda: ctx.render_vertex_adjoint_device(g, out))
     return out
 
 
-class _VertexAdjoint(torch.autograd.Function):
+class _VertexAdjoint(_Operator):
     """d loss / d xyz: the vertex adjoint render of the frame of `fr`, float64 [n_pts, 3] on the context's GPU.  A batch of
     upstream images (vmap) loops the single call."""
+    what = "vertex adjoint"
 
     @staticmethod
     def forward(fr, xyz, grad_img):
         ctx = _current(fr, "backward")
-        device = torch.device("cuda", ctx.device)
-        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
+        with _on_gpu(ctx, unwrapped=True) as device:
             g = _plain(grad_img).detach().to(device=device, dtype=torch.float32).contiguous()
             return _vertex_adjoint(ctx, g, device)
-
-    @staticmethod
-    def setup_context(fctx, inputs, output):
-        pass
-
-    @staticmethod
-    def backward(fctx, *grads):
-        _no_second("vertex adjoint")
-
-    @staticmethod
-    def jvp(fctx, *tangents):
-        _no_second("vertex adjoint")
 
     @staticmethod
     def vmap(info, in_dims, fr, xyz, grad_img):
         _unbatched_primals(in_dims[1:2])
         ctx = _current(fr, "backward")
-        device = torch.device("cuda", ctx.device)
-        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
-            g = _plain(grad_img).detach()
-            g = g.movedim(in_dims[2], 0) if in_dims[2] is not None else g.expand(info.batch_size, *g.shape)
-            g = g.to(device=device, dtype=torch.float32).contiguous()
+        with _on_gpu(ctx, unwrapped=True) as device:
+            g = _lift(grad_img, in_dims[2], info.batch_size).to(device=device, dtype=torch.float32).contiguous()
             return torch.stack([_vertex_adjoint(ctx, gk, device) for gk in g]), 0
 
 
@@ -519,45 +495,29 @@ def _vertex_tangent(ctx: capi.Context, d: torch.Tensor, device: torch.device) ->
     """[K, local_rows, res_x, 2] float32 on the context's GPU: the vertex tangent render for the displacement fields d
     ([K, n_pts, 3] float64, contiguous, there)."""
     k = d.shape[0]
-    out = torch.empty((k, ctx.local_rows, ctx.res_x, 2), dtype=torch.float32, device=device)
-    _use_torch_stream(ctx, device)
-    _run(ctx, lambda: ctx.render_vertex_tangent_device(d, out, n=k))
+    out = _frames(ctx, device, k)
+    _launch(ctx, device, lambda: ctx.render_vertex_tangent_device(d, out, n=k))
     return out
 
 
-class _VertexTangent(torch.autograd.Function):
+class _VertexTangent(_Operator):
     """d img / d xyz . t: one vertex tangent render of the frame of `fr`.  Batched under vmap."""
+    what = "vertex tangent"
 
     @staticmethod
     def forward(fr, xyz, xyz_t):
         ctx = _current(fr, "jvp")
-        device = torch.device("cuda", ctx.device)
-        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
+        with _on_gpu(ctx, unwrapped=True) as device:
             d = _tangent_arg(xyz_t, device).reshape(1, ctx.n_pts, 3)
             return _vertex_tangent(ctx, d, device)[0]
-
-    @staticmethod
-    def setup_context(fctx, inputs, output):
-        pass
-
-    @staticmethod
-    def backward(fctx, *grads):
-        _no_second("vertex tangent")
-
-    @staticmethod
-    def jvp(fctx, *tangents):
-        _no_second("vertex tangent")
 
     @staticmethod
     def vmap(info, in_dims, fr, xyz, xyz_t):
         _unbatched_primals(in_dims[1:2])
         ctx = _current(fr, "jvp")
-        device = torch.device("cuda", ctx.device)
         k = info.batch_size
-        with torch._C._DisableFuncTorch(), torch.cuda.device(device):
-            t = _plain(xyz_t).detach()
-            t = t.movedim(in_dims[2], 0) if in_dims[2] is not None else t.expand(k, *t.shape)
-            d = t.to(device=device, dtype=torch.float64).reshape(k, ctx.n_pts, 3).contiguous()
+        with _on_gpu(ctx, unwrapped=True) as device:
+            d = _lift(xyz_t, in_dims[2], k).to(device=device, dtype=torch.float64).reshape(k, ctx.n_pts, 3).contiguous()
             return _vertex_tangent(ctx, d, device), 0
 
 
@@ -583,10 +543,7 @@ class _RenderMesh(torch.autograd.Function):
             dtype, dev = fctx.xyz_meta
             gx_out = _VertexAdjoint.apply(fctx, xyz, grad_img).to(device=dev, dtype=dtype)
         if fctx.needs_input_grad[2] or fctx.needs_input_grad[3]:
-            ga, gq = _Adjoint.apply(fctx, alpha, q, grad_img)
-            (a_dtype, a_dev), (q_dtype, q_dev) = fctx.meta
-            ga_out = ga.to(device=a_dev, dtype=a_dtype) if fctx.needs_input_grad[2] else None
-            gq_out = gq.to(device=q_dev, dtype=q_dtype) if fctx.needs_input_grad[3] else None
+            ga_out, gq_out = _scalar_grads(fctx, *_Adjoint.apply(fctx, alpha, q, grad_img), 2, 3)
         return None, gx_out, ga_out, gq_out
 
     @staticmethod
@@ -598,9 +555,7 @@ class _RenderMesh(torch.autograd.Function):
             raise RuntimeError("course5_amd.autograd.render_mesh: forward mode in the points is not supported (there is no "
                                "per-vertex tangent render); use backward / vjp for xyz, or render_view for a rigid motion")
         xyz, alpha, q = getattr(fctx, "primals", (None, None, None))
-        if alpha_t is None and q_t is None:
-            return None
-        return _Tangent.apply(fctx, alpha, q, alpha_t, q_t)
+        return _tangent_sum(fctx, alpha, q, alpha_t, q_t, None)
 
     @staticmethod
     def vmap(info, in_dims, ctx, xyz, alpha, q):
@@ -616,14 +571,9 @@ class _RenderMeshForward(_RenderMesh):
         _current(fctx, "jvp")
         _first_order(fctx, "jvp")
         xyz, alpha, q = getattr(fctx, "primals", (None, None, None))
-        out = None
-        if alpha_t is not None or q_t is not None:
-            out = _Tangent.apply(fctx, alpha, q, alpha_t, q_t)
         # (torch.func hands every input a tangent, zeros for the ones it does not differentiate: J 0 = 0 needs no render)
-        if xyz_t is not None and bool((_plain(xyz_t) != 0).any()):
-            t = _VertexTangent.apply(fctx, xyz, xyz_t)
-            out = t if out is None else out + t
-        return out
+        moved = xyz_t is not None and bool((_plain(xyz_t) != 0).any())
+        return _tangent_sum(fctx, alpha, q, alpha_t, q_t, (lambda: _VertexTangent.apply(fctx, xyz, xyz_t)) if moved else None)
 
     @staticmethod
     def vmap(info, in_dims, ctx, xyz, alpha, q):
@@ -650,16 +600,8 @@ def _gn_enter(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, what: str
     if _differentiating_levels():
         raise RuntimeError(f"course5_amd.autograd.{what}: it is an operator with no derivative of its own (second derivatives "
                            "are not supported); call it outside torch.func.grad / vjp / jvp")
-    alpha, q = _plain(alpha).detach(), _plain(q).detach()
-    if alpha.shape != (ctx.n_cells,) or q.shape != (ctx.n_cells,):
-        raise ValueError(f"alpha and q must hold one value per cell ({ctx.n_cells})")
-    device = torch.device("cuda", ctx.device)
-    if all(t.is_cuda and t.device.index == ctx.device for t in (alpha, q)):
-        _upload(ctx, _Scalars(alpha.to(dtype=torch.float64, copy=True).contiguous(), q.to(dtype=torch.float64, copy=True).contiguous()))
-    else:
-        _upload(ctx, _Scalars(alpha.to("cpu", torch.float64).contiguous().numpy().copy(),
-                              q.to("cpu", torch.float64).contiguous().numpy().copy()))
-    return device
+    _upload(ctx, _scalars_of(ctx, _plain(alpha), _plain(q)))
+    return torch.device("cuda", ctx.device)
 
 
 def _gn_weight(ctx: capi.Context, weight, device: torch.device):
@@ -680,15 +622,13 @@ def gn_product(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, v_alpha,
     if not given or any(v.shape != given[0].shape for v in given) or given[0].ndim not in (1, 2) or given[0].shape[-1] != ctx.n_cells:
         raise ValueError(f"v_alpha and / or v_q must be [{ctx.n_cells}] or [K, {ctx.n_cells}], of one shape")
     single = given[0].ndim == 1
-    with torch.cuda.device(device):
+    with _on_gpu(ctx):
         va, vq = (None if v is None else _plain(v).detach().to(device=device, dtype=torch.float64).reshape(-1, ctx.n_cells).contiguous()
                   for v in (v_alpha, v_q))
         w = _gn_weight(ctx, weight, device)
         k = (va if va is not None else vq).shape[0]
-        ha = torch.empty((k, ctx.n_cells), dtype=torch.float64, device=device)
-        hq = torch.empty((k, ctx.n_cells), dtype=torch.float64, device=device)
-        _use_torch_stream(ctx, device)
-        _run(ctx, lambda: ctx.render_gn_product_device(va, vq, w, ha, hq, None, n=k))
+        ha, hq = _cell_pair(ctx, device, k)
+        _launch(ctx, device, lambda: ctx.render_gn_product_device(va, vq, w, ha, hq, None, n=k))
     return (ha[0], hq[0]) if single else (ha, hq)
 
 
@@ -696,12 +636,10 @@ def gn_diagonal(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, weight=
     """(d_alpha, d_q) = diag(J^T W J), float64 [n_cells] each on the context's GPU (c5_render_gn_diagonal_device on
     torch's current stream)."""
     device = _gn_enter(ctx, alpha, q, "gn_diagonal")
-    with torch.cuda.device(device):
+    with _on_gpu(ctx):
         w = _gn_weight(ctx, weight, device)
-        da = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
-        dq = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
-        _use_torch_stream(ctx, device)
-        _run(ctx, lambda: ctx.render_gn_diagonal_device(w, da, dq))
+        da, dq = _cell_pair(ctx, device)
+        _launch(ctx, device, lambda: ctx.render_gn_diagonal_device(w, da, dq))
     return da, dq
 
 
@@ -715,15 +653,13 @@ def hvp(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, v_alpha, v_q, g
     given = [v for v in (v_alpha, v_q) if v is not None]
     if not given or any(tuple(v.shape) != (ctx.n_cells,) for v in given):
         raise ValueError(f"v_alpha and / or v_q must be [{ctx.n_cells}]")
-    with torch.cuda.device(device):
+    with _on_gpu(ctx):
         va, vq = (None if v is None else _plain(v).detach().to(device=device, dtype=torch.float64).contiguous() for v in (v_alpha, v_q))
         g = _plain(grad_img).detach().to(device=device, dtype=torch.float32).contiguous()
         if tuple(g.shape) != (ctx.local_rows, ctx.res_x, 2):
             raise ValueError(f"grad_img must be [{ctx.local_rows}, {ctx.res_x}, 2], not {list(g.shape)}")
-        ha = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
-        hq = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
-        _use_torch_stream(ctx, device)
-        _run(ctx, lambda: ctx.render_hvp_device(va, vq, g, ha, hq))
+        ha, hq = _cell_pair(ctx, device)
+        _launch(ctx, device, lambda: ctx.render_hvp_device(va, vq, g, ha, hq))
     return ha, hq
 
 
@@ -736,9 +672,8 @@ def ray_matrix(ctx: capi.Context, with_depth: bool = False):
     z_exit float64 [nnz]: every segment's far end in view space, in the order of A.values().  Built on torch's current
     stream (c5_ray_matrix_rows_device, c5_ray_matrix_fill_device) and waited for; no graph: A does not depend on the
     scalars.  Bit-reproducible."""
-    device = torch.device("cuda", ctx.device)
     n_px = ctx.local_rows * ctx.res_x
-    with torch.cuda.device(device):
+    with _on_gpu(ctx) as device:
         crow = torch.empty(n_px + 1, dtype=torch.int64, device=device)
         _use_torch_stream(ctx, device)
         nnz = ctx.ray_matrix_rows_device(crow)  # (waits and retries by itself)

@@ -19,27 +19,6 @@ LIB_PATH = os.environ.get("C5_LIB", os.path.join(PKG, "libcourse5_hip.so"))  # C
 
 C5_OK, C5_ERR_INVALID, C5_ERR_STATE, C5_ERR_HIP, C5_ERR_MESH, C5_ERR_NO_DEVICE, C5_ERR_WALK, C5_RETRY = range(8)
 
-# every symbol include/course5_hip.h declares
-EXPORTS = [
-    "c5_abi_version", "c5_device_count", "c5_create", "c5_destroy", "c5_last_error",
-    "c5_upload_grid", "c5_update_scalars", "c5_set_solid", "c5_set_image", "c5_set_row_tiles",
-    "c5_local_rows", "c5_set_view", "c5_set_solid_view", "c5_set_alpha_limit", "c5_set_option",
-    "c5_render", "c5_render_device", "c5_synchronize", "c5_get_stats", "c5_walk_kernel_ms",
-    "c5_download_view_points", "c5_face_adjacency", "c5_set_stream",
-    "c5_set_row_range", "c5_get_row_costs", "c5_weld_points",
-    "c5_render_host_async", "c5_render_host_wait", "c5_host_alloc", "c5_host_free", "c5_render_frame_rows_async",
-    "c5_render_adjoint", "c5_render_adjoint_device", "c5_render_tangent", "c5_render_tangent_device",
-    "c5_render_tangent_batch", "c5_render_tangent_batch_device", "c5_render_adjoint_batch", "c5_render_adjoint_batch_device",
-    "c5_update_scalars_device",
-    "c5_render_gn_product", "c5_render_gn_product_device", "c5_render_gn_diagonal", "c5_render_gn_diagonal_device",
-    "c5_render_hvp", "c5_render_hvp_device",
-    "c5_render_motion_tangent", "c5_render_motion_tangent_device", "c5_rotation_motion",
-    "c5_render_vertex_adjoint", "c5_render_vertex_adjoint_device", "c5_update_points",
-    "c5_render_vertex_tangent", "c5_render_vertex_tangent_device",
-    "c5_ray_matrix_rows", "c5_ray_matrix_rows_device", "c5_ray_matrix_fill", "c5_ray_matrix_fill_device",
-]
-
-
 class Rotation(C.Structure):
     _fields_ = [("axis", C.c_int32), ("reserved", C.c_int32), ("angle", C.c_double), ("x0", C.c_double)]
 
@@ -63,6 +42,72 @@ class C5Error(RuntimeError):
         self.message = message
 
 
+_vp, _dp_t, _fp_t, _ip_t, _lp_t = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+_rp_t = C.POINTER(Rotation)
+
+# every symbol include/course5_hip.h declares: its argument types, or (argument types, result type) where that is not int
+SIGNATURES = {
+    "c5_abi_version": None,
+    "c5_device_count": [C.POINTER(C.c_int)],
+    "c5_create": [C.c_int, C.POINTER(_vp)],
+    "c5_destroy": ([_vp], None),
+    "c5_last_error": ([_vp], C.c_char_p),
+    "c5_upload_grid": [_vp, _dp_t, C.c_int64, _ip_t, C.c_int64, _dp_t, _dp_t],
+    "c5_update_scalars": [_vp, _dp_t, _dp_t, C.c_int64],
+    "c5_set_solid": [_vp, C.c_int, _dp_t, C.c_int64, C.c_double],
+    "c5_set_image": [_vp, C.c_int, C.c_int, _dp_t],
+    "c5_set_row_tiles": [_vp, C.c_int, C.c_int, C.c_int],
+    "c5_local_rows": [_vp, C.POINTER(C.c_int)],
+    "c5_set_view": [_vp, _rp_t, C.c_int],
+    "c5_set_solid_view": [_vp, C.c_int, _rp_t, C.c_int],
+    "c5_set_alpha_limit": [_vp, C.c_double],
+    "c5_set_option": [_vp, C.c_char_p, C.c_double],
+    "c5_render": [_vp, _fp_t],
+    "c5_render_device": [_vp, _vp],
+    "c5_synchronize": [_vp],
+    "c5_get_stats": [_vp, C.POINTER(Stats)],
+    "c5_walk_kernel_ms": [_vp, C.c_int, _dp_t, _lp_t],
+    "c5_download_view_points": [_vp, _dp_t],
+    "c5_face_adjacency": [_ip_t, C.c_int64, C.c_int64, _ip_t, _lp_t],
+    "c5_set_stream": [_vp, _vp],
+    "c5_set_row_range": [_vp, C.c_int, C.c_int],
+    "c5_get_row_costs": [_vp, C.POINTER(C.c_uint32), C.c_int],
+    "c5_weld_points": [_dp_t, C.c_int64, _ip_t, _lp_t],
+    "c5_render_host_async": [_vp, _fp_t],
+    "c5_render_host_wait": [_vp],
+    "c5_host_alloc": [_vp, C.c_size_t, C.POINTER(_vp)],
+    "c5_host_free": [_vp, _vp],
+    "c5_render_frame_rows_async": [_vp, _fp_t],
+    "c5_render_adjoint": [_vp, _fp_t, _dp_t, _dp_t],
+    "c5_render_adjoint_device": [_vp, _vp, _vp, _vp],
+    "c5_render_tangent": [_vp, _dp_t, _dp_t, _fp_t],
+    "c5_render_tangent_device": [_vp, _vp, _vp, _vp],
+    "c5_render_tangent_batch": [_vp, C.c_int, _dp_t, _dp_t, _fp_t],
+    "c5_render_tangent_batch_device": [_vp, C.c_int, _vp, _vp, _vp],
+    "c5_render_adjoint_batch": [_vp, C.c_int, _fp_t, _dp_t, _dp_t],
+    "c5_render_adjoint_batch_device": [_vp, C.c_int, _vp, _vp, _vp],
+    "c5_update_scalars_device": [_vp, _vp, _vp, C.c_int64],
+    "c5_render_gn_product": [_vp, C.c_int, _dp_t, _dp_t, _fp_t, _dp_t, _dp_t, _fp_t],
+    "c5_render_gn_product_device": [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "c5_render_gn_diagonal": [_vp, _fp_t, _dp_t, _dp_t],
+    "c5_render_gn_diagonal_device": [_vp, _vp, _vp, _vp],
+    "c5_render_hvp": [_vp, _dp_t, _dp_t, _fp_t, _dp_t, _dp_t],
+    "c5_render_hvp_device": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "c5_render_motion_tangent": [_vp, C.c_int, _dp_t, _fp_t],
+    "c5_render_motion_tangent_device": [_vp, C.c_int, _dp_t, _vp],
+    "c5_rotation_motion": [_rp_t, C.c_int, C.c_int, C.c_int, _dp_t],
+    "c5_render_vertex_adjoint": [_vp, _fp_t, _dp_t],
+    "c5_render_vertex_adjoint_device": [_vp, _vp, _vp],
+    "c5_update_points": [_vp, _dp_t, C.c_int64],
+    "c5_render_vertex_tangent": [_vp, C.c_int, _dp_t, _fp_t],
+    "c5_render_vertex_tangent_device": [_vp, C.c_int, _vp, _vp],
+    "c5_ray_matrix_rows": [_vp, _lp_t, _lp_t],
+    "c5_ray_matrix_rows_device": [_vp, _vp, _lp_t],
+    "c5_ray_matrix_fill": [_vp, _lp_t, C.c_int64, _ip_t, _dp_t, _dp_t],
+    "c5_ray_matrix_fill_device": [_vp, _vp, C.c_int64, _vp, _vp, _vp],
+}
+EXPORTS = list(SIGNATURES)
+
 _lib = None
 
 
@@ -74,71 +119,9 @@ def load_library() -> C.CDLL:
     if not os.path.exists(LIB_PATH):
         raise FileNotFoundError(f"{LIB_PATH} is missing: run `python -m course5_amd.build` (or __graft_entry__.build())")
     lib = C.CDLL(LIB_PATH)
-    dp, ip, vp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p
-    lib.c5_abi_version.restype = C.c_int
-    lib.c5_device_count.argtypes = [C.POINTER(C.c_int)]
-    lib.c5_create.argtypes = [C.c_int, C.POINTER(vp)]
-    lib.c5_destroy.argtypes = [vp]
-    lib.c5_destroy.restype = None
-    lib.c5_last_error.argtypes = [vp]
-    lib.c5_last_error.restype = C.c_char_p
-    lib.c5_upload_grid.argtypes = [vp, dp, C.c_int64, ip, C.c_int64, dp, dp]
-    lib.c5_update_scalars.argtypes = [vp, dp, dp, C.c_int64]
-    lib.c5_set_solid.argtypes = [vp, C.c_int, dp, C.c_int64, C.c_double]
-    lib.c5_set_image.argtypes = [vp, C.c_int, C.c_int, dp]
-    lib.c5_set_row_tiles.argtypes = [vp, C.c_int, C.c_int, C.c_int]
-    lib.c5_local_rows.argtypes = [vp, C.POINTER(C.c_int)]
-    lib.c5_set_view.argtypes = [vp, C.POINTER(Rotation), C.c_int]
-    lib.c5_set_solid_view.argtypes = [vp, C.c_int, C.POINTER(Rotation), C.c_int]
-    lib.c5_set_alpha_limit.argtypes = [vp, C.c_double]
-    lib.c5_set_option.argtypes = [vp, C.c_char_p, C.c_double]
-    lib.c5_render.argtypes = [vp, C.POINTER(C.c_float)]
-    lib.c5_render_device.argtypes = [vp, vp]
-    lib.c5_synchronize.argtypes = [vp]
-    lib.c5_get_stats.argtypes = [vp, C.POINTER(Stats)]
-    lib.c5_walk_kernel_ms.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    lib.c5_download_view_points.argtypes = [vp, dp]
-    lib.c5_set_stream.argtypes = [vp, vp]
-    lib.c5_set_row_range.argtypes = [vp, C.c_int, C.c_int]
-    lib.c5_get_row_costs.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int]
-    lib.c5_face_adjacency.argtypes = [ip, C.c_int64, C.c_int64, ip, C.POINTER(C.c_int64)]
-    lib.c5_weld_points.argtypes = [dp, C.c_int64, ip, C.POINTER(C.c_int64)]
-    lib.c5_render_host_async.argtypes = [vp, C.POINTER(C.c_float)]
-    lib.c5_render_host_wait.argtypes = [vp]
-    lib.c5_render_frame_rows_async.argtypes = [vp, C.POINTER(C.c_float)]
-    lib.c5_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
-    lib.c5_host_free.argtypes = [vp, vp]
-    lib.c5_render_adjoint.argtypes = [vp, C.POINTER(C.c_float), dp, dp]
-    lib.c5_render_adjoint_device.argtypes = [vp, vp, vp, vp]
-    lib.c5_render_tangent.argtypes = [vp, dp, dp, C.POINTER(C.c_float)]
-    lib.c5_render_tangent_device.argtypes = [vp, vp, vp, vp]
-    lib.c5_render_tangent_batch.argtypes = [vp, C.c_int, dp, dp, C.POINTER(C.c_float)]
-    lib.c5_render_tangent_batch_device.argtypes = [vp, C.c_int, vp, vp, vp]
-    lib.c5_render_adjoint_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_float), dp, dp]
-    lib.c5_render_adjoint_batch_device.argtypes = [vp, C.c_int, vp, vp, vp]
-    lib.c5_update_scalars_device.argtypes = [vp, vp, vp, C.c_int64]
-    lib.c5_render_gn_product.argtypes = [vp, C.c_int, dp, dp, C.POINTER(C.c_float), dp, dp, C.POINTER(C.c_float)]
-    lib.c5_render_gn_product_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
-    lib.c5_render_gn_diagonal.argtypes = [vp, C.POINTER(C.c_float), dp, dp]
-    lib.c5_render_gn_diagonal_device.argtypes = [vp, vp, vp, vp]
-    lib.c5_render_hvp.argtypes = [vp, dp, dp, C.POINTER(C.c_float), dp, dp]
-    lib.c5_render_hvp_device.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.c5_render_motion_tangent.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_float)]
-    lib.c5_render_motion_tangent_device.argtypes = [vp, C.c_int, dp, vp]
-    lib.c5_rotation_motion.argtypes = [C.POINTER(Rotation), C.c_int, C.c_int, C.c_int, dp]
-    lib.c5_render_vertex_adjoint.argtypes = [vp, C.POINTER(C.c_float), dp]
-    lib.c5_render_vertex_adjoint_device.argtypes = [vp, vp, vp]
-    lib.c5_update_points.argtypes = [vp, dp, C.c_int64]
-    lib.c5_render_vertex_tangent.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_float)]
-    lib.c5_render_vertex_tangent_device.argtypes = [vp, C.c_int, vp, vp]
-    lp = C.POINTER(C.c_int64)
-    lib.c5_ray_matrix_rows.argtypes = [vp, lp, lp]
-    lib.c5_ray_matrix_rows_device.argtypes = [vp, vp, lp]
-    lib.c5_ray_matrix_fill.argtypes = [vp, lp, C.c_int64, ip, dp, dp]
-    lib.c5_ray_matrix_fill_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
-    for name in EXPORTS:
-        if name not in ("c5_destroy", "c5_last_error"):
-            getattr(lib, name).restype = C.c_int
+    for name, signature in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = signature if isinstance(signature, tuple) else (signature, C.c_int)
     _lib = lib
     return lib
 
@@ -154,7 +137,13 @@ def _rot_array(rots) -> tuple:
 
 
 def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
+    """The pointer of a float64 array, or NULL for None."""
+    return None if a is None else a.ctypes.data_as(_dp_t)
+
+
+def _fp(a):
+    """The pointer of a float32 array, or NULL for None."""
+    return None if a is None else a.ctypes.data_as(_fp_t)
 
 
 def _device_ptr(t, dtype, shape) -> int:
@@ -326,34 +315,58 @@ class Context:
         """Asynchronous render into device memory (e.g. a torch tensor's data_ptr())."""
         self._check(self.lib.c5_render_device(self.handle, C.c_void_p(device_ptr)))
 
+    # -- the derivative renders' arguments -------------------------------------------------------------
+    # host forms: numpy arrays, checked here (the messages name the argument); device forms: _device_ptr
+    def _image(self, a, name: str, batch: bool = False) -> np.ndarray:
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        shape = (self.local_rows, self.res_x, 2)
+        if (a.shape[1:] if batch else a.shape) != shape:
+            raise ValueError(f"{name} must be [{'K, ' if batch else ''}{shape[0]}, {shape[1]}, 2], not {list(a.shape)}")
+        return a
+
+    def _direction(self, d):
+        if d is None:
+            return None
+        d = np.ascontiguousarray(d, dtype=np.float64)
+        if d.shape != (self.n_cells,):
+            raise ValueError(f"a direction must hold one value per cell ({self.n_cells}), not {list(d.shape)}")
+        return d
+
+    @staticmethod
+    def _fit(fit, once: bool = False) -> tuple:
+        fit = tuple(fit)
+        if not fit or any(f not in ("alpha", "q") for f in fit) or (once and len(set(fit)) != len(fit)):
+            raise ValueError(f"fit must name 'alpha', 'q' or both, not {fit!r}")
+        return fit
+
+    def _images(self, k: int) -> np.ndarray:
+        return np.zeros((k, self.local_rows, self.res_x, 2), dtype=np.float32)
+
+    def _cells_dev(self, t, k: int | None = None) -> int:
+        import torch
+        return _device_ptr(t, torch.float64, (self.n_cells,) if k is None else (k, self.n_cells))
+
+    def _image_dev(self, t, k: int | None = None) -> int:
+        import torch
+        shape = (self.local_rows, self.res_x, 2)
+        return _device_ptr(t, torch.float32, shape if k is None else (k,) + shape)
+
     # -- adjoint render ----------------------------------------------------------------------------
     def render_adjoint(self, grad_out) -> tuple:
         """Gradients of the frame render() would produce now, weighted by grad_out ([local_rows, res_x, 2]: the weights
         of tau and of I per pixel): (grad_alpha, grad_q), float64 [n_cells] each in the order of upload_grid.
         Synchronous; retries by itself."""
-        g = np.ascontiguousarray(grad_out, dtype=np.float32)
-        if g.shape != (self.local_rows, self.res_x, 2):
-            raise ValueError(f"grad_out must be [{self.local_rows}, {self.res_x}, 2], not {list(g.shape)}")
-        ga = np.zeros(self.n_cells, dtype=np.float64)
-        gq = np.zeros(self.n_cells, dtype=np.float64)
-        self._check(self.lib.c5_render_adjoint(self.handle, g.ctypes.data_as(C.POINTER(C.c_float)), _dp(ga), _dp(gq)))
+        g = self._image(grad_out, "grad_out")
+        ga, gq = np.zeros(self.n_cells), np.zeros(self.n_cells)
+        self._check(self.lib.c5_render_adjoint(self.handle, _fp(g), _dp(ga), _dp(gq)))
         return ga, gq
 
     def render_adjoint_device(self, grad_out, grad_alpha, grad_q):
         """Asynchronous form on the context's stream, into device memory: torch tensors on this context's GPU (grad_out
         float32 [local_rows, res_x, 2] contiguous, grad_alpha / grad_q float64 [n_cells] contiguous) or raw device
         pointers.  The status comes with the next synchronize() (C5_RETRY: run it again)."""
-        def ptr(t, dtype, shape):
-            if isinstance(t, int):
-                return t
-            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
-                raise ValueError(f"expected a contiguous {dtype} tensor of shape {shape} on the GPU")
-            return t.data_ptr()
-
-        import torch
-        self._check(self.lib.c5_render_adjoint_device(
-            self.handle, C.c_void_p(ptr(grad_out, torch.float32, (self.local_rows, self.res_x, 2))),
-            C.c_void_p(ptr(grad_alpha, torch.float64, (self.n_cells,))), C.c_void_p(ptr(grad_q, torch.float64, (self.n_cells,)))))
+        self._check(self.lib.c5_render_adjoint_device(self.handle, self._image_dev(grad_out), self._cells_dev(grad_alpha),
+                                                      self._cells_dev(grad_q)))
 
     # -- vertex adjoint render ---------------------------------------------------------------------
     def render_vertex_adjoint(self, grad_out) -> np.ndarray:
@@ -361,11 +374,9 @@ class Context:
         ([local_rows, res_x, 2]: the weights of tau and of I per pixel): float64 [n_pts, 3] in the order and the coordinates
         of upload_grid.  A point welded to another at upload gets 0, its representative the group's sum.  Synchronous;
         retries by itself.  Not bit-reproducible from run to run (fp64 atomics), like render_adjoint."""
-        g = np.ascontiguousarray(grad_out, dtype=np.float32)
-        if g.shape != (self.local_rows, self.res_x, 2):
-            raise ValueError(f"grad_out must be [{self.local_rows}, {self.res_x}, 2], not {list(g.shape)}")
-        out = np.zeros((self.n_pts, 3), dtype=np.float64)
-        self._check(self.lib.c5_render_vertex_adjoint(self.handle, g.ctypes.data_as(C.POINTER(C.c_float)), _dp(out)))
+        g = self._image(grad_out, "grad_out")
+        out = np.zeros((self.n_pts, 3))
+        self._check(self.lib.c5_render_vertex_adjoint(self.handle, _fp(g), _dp(out)))
         return out
 
     def render_vertex_adjoint_device(self, grad_out, grad_xyz):
@@ -373,9 +384,8 @@ class Context:
         float32 [local_rows, res_x, 2], grad_xyz float64 [n_pts, 3]; contiguous) or raw device pointers.  The status comes
         with the next synchronize() (C5_RETRY: run it again)."""
         import torch
-        self._check(self.lib.c5_render_vertex_adjoint_device(
-            self.handle, C.c_void_p(_device_ptr(grad_out, torch.float32, (self.local_rows, self.res_x, 2)) or None),
-            C.c_void_p(_device_ptr(grad_xyz, torch.float64, (self.n_pts, 3)) or None)))
+        self._check(self.lib.c5_render_vertex_adjoint_device(self.handle, self._image_dev(grad_out),
+                                                             _device_ptr(grad_xyz, torch.float64, (self.n_pts, 3))))
 
     # -- vertex tangent render ---------------------------------------------------------------------
     def render_vertex_tangent(self, d_xyz) -> np.ndarray:
@@ -388,8 +398,8 @@ class Context:
         if d.ndim not in (2, 3) or d.shape[-2:] != (self.n_pts, 3) or d.shape[0] == 0:
             raise ValueError(f"d_xyz must be [{self.n_pts}, 3] or [K, {self.n_pts}, 3], not {list(d.shape)}")
         k = 1 if d.ndim == 2 else d.shape[0]
-        out = np.zeros((k, self.local_rows, self.res_x, 2), dtype=np.float32)
-        self._check(self.lib.c5_render_vertex_tangent(self.handle, k, _dp(d), out.ctypes.data_as(C.POINTER(C.c_float))))
+        out = self._images(k)
+        self._check(self.lib.c5_render_vertex_tangent(self.handle, k, _dp(d), _fp(out)))
         return out[0] if d.ndim == 2 else out
 
     def render_vertex_tangent_device(self, d_xyz, out, n: int | None = None):
@@ -400,9 +410,8 @@ class Context:
         k = n if n is not None else (out.shape[0] if hasattr(out, "shape") and len(out.shape) == 4 else -1)
         if k < 0:
             raise ValueError("out must be [K, local_rows, res_x, 2] (or give n = K with raw device pointers)")
-        d_ptr = _device_ptr(d_xyz, torch.float64, (k, self.n_pts, 3))
-        out_ptr = _device_ptr(out, torch.float32, (k, self.local_rows, self.res_x, 2))
-        self._check(self.lib.c5_render_vertex_tangent_device(self.handle, k, C.c_void_p(d_ptr or None), C.c_void_p(out_ptr or None)))
+        ptrs = _device_ptr(d_xyz, torch.float64, (k, self.n_pts, 3)), self._image_dev(out, k)
+        self._check(self.lib.c5_render_vertex_tangent_device(self.handle, k, *ptrs))
 
     # -- ray matrix --------------------------------------------------------------------------------
     def ray_matrix_rows(self) -> np.ndarray:
@@ -410,7 +419,7 @@ class Context:
         prefix sums of the pixels' segment counts (row_ptr[-1]: all of them).  Synchronous; retries by itself."""
         row_ptr = np.zeros(self.local_rows * self.res_x + 1, dtype=np.int64)
         nnz = C.c_int64()  # (row_ptr[-1] says the same)
-        self._check(self.lib.c5_ray_matrix_rows(self.handle, row_ptr.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(nnz)))
+        self._check(self.lib.c5_ray_matrix_rows(self.handle, row_ptr.ctypes.data_as(_lp_t), C.byref(nnz)))
         return row_ptr
 
     def ray_matrix_rows_device(self, row_ptr) -> int:
@@ -420,7 +429,7 @@ class Context:
         nnz = C.c_int64()
         ptr = _device_ptr(row_ptr, torch.int64, (self.local_rows * self.res_x + 1,))
         for _ in range(3):
-            if self._check(self.lib.c5_ray_matrix_rows_device(self.handle, C.c_void_p(ptr or None), C.byref(nnz)), allow=(C5_RETRY,)) == C5_OK:
+            if self._check(self.lib.c5_ray_matrix_rows_device(self.handle, ptr, C.byref(nnz)), allow=(C5_RETRY,)) == C5_OK:
                 return nnz.value
         raise C5Error(C5_RETRY, "ray_matrix_rows_device: the entry buffer kept overflowing")
 
@@ -441,11 +450,10 @@ class Context:
         if n < 0:
             raise ValueError(f"capacity must not be negative ({n})")
         col = np.zeros(max(n, 1), dtype=np.int32)
-        dz = np.zeros(max(n, 1), dtype=np.float64)
-        z_exit = np.zeros(max(n, 1), dtype=np.float64) if with_depth else None
-        self._check(self.lib.c5_ray_matrix_fill(self.handle, row_ptr.ctypes.data_as(C.POINTER(C.c_int64)), n,
-                                                col.ctypes.data_as(C.POINTER(C.c_int32)), _dp(dz),
-                                                None if z_exit is None else _dp(z_exit)))
+        dz = np.zeros(max(n, 1))
+        z_exit = np.zeros(max(n, 1)) if with_depth else None
+        self._check(self.lib.c5_ray_matrix_fill(self.handle, row_ptr.ctypes.data_as(_lp_t), n, col.ctypes.data_as(_ip_t), _dp(dz),
+                                                _dp(z_exit)))
         return (col[:n], dz[:n], z_exit[:n]) if with_depth else (col[:n], dz[:n])
 
     def ray_matrix_fill_device(self, row_ptr, col, dz, z_exit=None, capacity: int | None = None):
@@ -461,8 +469,7 @@ class Context:
         shape = (capacity,)
         ptrs = (_device_ptr(row_ptr, torch.int64, (self.local_rows * self.res_x + 1,)), _device_ptr(col, torch.int32, shape),
                 _device_ptr(dz, torch.float64, shape), _device_ptr(z_exit, torch.float64, shape))
-        self._check(self.lib.c5_ray_matrix_fill_device(self.handle, C.c_void_p(ptrs[0] or None), capacity, C.c_void_p(ptrs[1] or None),
-                                                       C.c_void_p(ptrs[2] or None), C.c_void_p(ptrs[3] or None)))
+        self._check(self.lib.c5_ray_matrix_fill_device(self.handle, ptrs[0], capacity, *ptrs[1:]))
 
     def ray_matrix(self, with_depth: bool = False) -> tuple:
         """The ray matrix A of the frame render() would produce now as CSR arrays (row_ptr, col, dz[, z_exit]): rows are the
@@ -476,36 +483,16 @@ class Context:
         """The change of the frame render() would produce now for a change (d_alpha, d_q) of the cells' scalars ([n_cells]
         each in the order of upload_grid; None: zero): float32 [local_rows, res_x, 2] (tau_dot, I_dot).  Synchronous;
         retries by itself.  Bit-reproducible."""
-        def direction(d):
-            if d is None:
-                return None
-            d = np.ascontiguousarray(d, dtype=np.float64)
-            if d.shape != (self.n_cells,):
-                raise ValueError(f"a direction must hold one value per cell ({self.n_cells}), not {list(d.shape)}")
-            return d
-
-        da, dq = direction(d_alpha), direction(d_q)
+        da, dq = self._direction(d_alpha), self._direction(d_q)
         out = np.zeros((self.local_rows, self.res_x, 2), dtype=np.float32)
-        self._check(self.lib.c5_render_tangent(self.handle, None if da is None else _dp(da), None if dq is None else _dp(dq),
-                                               out.ctypes.data_as(C.POINTER(C.c_float))))
+        self._check(self.lib.c5_render_tangent(self.handle, _dp(da), _dp(dq), _fp(out)))
         return out
 
     def render_tangent_device(self, d_alpha, d_q, out):
         """Asynchronous form on the context's stream, in device memory: torch tensors on this context's GPU (d_alpha / d_q
         float64 [n_cells] contiguous or None for zero, out float32 [local_rows, res_x, 2] contiguous) or raw device
         pointers (0: zero).  The status comes with the next synchronize() (C5_RETRY: run it again)."""
-        def ptr(t, dtype, shape):
-            if t is None or isinstance(t, int):
-                return t or 0
-            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
-                raise ValueError(f"expected a contiguous {dtype} tensor of shape {shape} on the GPU")
-            return t.data_ptr()
-
-        import torch
-        self._check(self.lib.c5_render_tangent_device(
-            self.handle, C.c_void_p(ptr(d_alpha, torch.float64, (self.n_cells,)) or None),
-            C.c_void_p(ptr(d_q, torch.float64, (self.n_cells,)) or None),
-            C.c_void_p(ptr(out, torch.float32, (self.local_rows, self.res_x, 2)))))
+        self._check(self.lib.c5_render_tangent_device(self.handle, self._cells_dev(d_alpha), self._cells_dev(d_q), self._image_dev(out)))
 
     # -- batched derivative renders ---------------------------------------------------------------
     def _batch_directions(self, d_alpha, d_q) -> tuple:
@@ -527,44 +514,34 @@ class Context:
         """render_tangent for K directions at once (d_alpha / d_q: [K, n_cells], either may be None: zero): float32
         [K, local_rows, res_x, 2], every slice bit for bit render_tangent's for that direction alone."""
         da, dq, k = self._batch_directions(d_alpha, d_q)
-        out = np.zeros((k, self.local_rows, self.res_x, 2), dtype=np.float32)
-        self._check(self.lib.c5_render_tangent_batch(self.handle, k, None if da is None else _dp(da), None if dq is None else _dp(dq),
-                                                     out.ctypes.data_as(C.POINTER(C.c_float))))
+        out = self._images(k)
+        self._check(self.lib.c5_render_tangent_batch(self.handle, k, _dp(da), _dp(dq), _fp(out)))
         return out
 
     def render_tangent_batch_device(self, d_alpha, d_q, out, n: int | None = None):
         """Asynchronous form on the context's stream: torch tensors on this context's GPU (d_alpha / d_q float64 [K,
         n_cells] contiguous or None, out float32 [K, local_rows, res_x, 2] contiguous) or raw device pointers (then give
         n = K).  The status comes with the next synchronize() (C5_RETRY: run it again)."""
-        import torch
         k = n if n is not None else out.shape[0]
-        self._check(self.lib.c5_render_tangent_batch_device(
-            self.handle, k, C.c_void_p(_device_ptr(d_alpha, torch.float64, (k, self.n_cells)) or None),
-            C.c_void_p(_device_ptr(d_q, torch.float64, (k, self.n_cells)) or None),
-            C.c_void_p(_device_ptr(out, torch.float32, (k, self.local_rows, self.res_x, 2)))))
+        self._check(self.lib.c5_render_tangent_batch_device(self.handle, k, self._cells_dev(d_alpha, k), self._cells_dev(d_q, k),
+                                                            self._image_dev(out, k)))
 
     def render_adjoint_batch(self, grad_out) -> tuple:
         """render_adjoint for K upstream images at once (grad_out [K, local_rows, res_x, 2]): (grad_alpha, grad_q), float64
         [K, n_cells] each; every slice render_adjoint's for that image to rounding.  Synchronous; retries by itself."""
-        g = np.ascontiguousarray(grad_out, dtype=np.float32)
-        if g.ndim != 4 or g.shape[1:] != (self.local_rows, self.res_x, 2):
-            raise ValueError(f"grad_out must be [K, {self.local_rows}, {self.res_x}, 2], not {list(g.shape)}")
+        g = self._image(grad_out, "grad_out", batch=True)
         k = g.shape[0]
-        ga = np.zeros((k, self.n_cells), dtype=np.float64)
-        gq = np.zeros((k, self.n_cells), dtype=np.float64)
-        self._check(self.lib.c5_render_adjoint_batch(self.handle, k, g.ctypes.data_as(C.POINTER(C.c_float)), _dp(ga), _dp(gq)))
+        ga, gq = np.zeros((k, self.n_cells)), np.zeros((k, self.n_cells))
+        self._check(self.lib.c5_render_adjoint_batch(self.handle, k, _fp(g), _dp(ga), _dp(gq)))
         return ga, gq
 
     def render_adjoint_batch_device(self, grad_out, grad_alpha, grad_q, n: int | None = None):
         """Asynchronous form on the context's stream: torch tensors on this context's GPU (grad_out float32 [K, local_rows,
         res_x, 2], grad_alpha / grad_q float64 [K, n_cells], contiguous) or raw device pointers (then give n = K).  The
         status comes with the next synchronize() (C5_RETRY: run it again)."""
-        import torch
         k = n if n is not None else grad_out.shape[0]
-        self._check(self.lib.c5_render_adjoint_batch_device(
-            self.handle, k, C.c_void_p(_device_ptr(grad_out, torch.float32, (k, self.local_rows, self.res_x, 2))),
-            C.c_void_p(_device_ptr(grad_alpha, torch.float64, (k, self.n_cells))),
-            C.c_void_p(_device_ptr(grad_q, torch.float64, (k, self.n_cells)))))
+        self._check(self.lib.c5_render_adjoint_batch_device(self.handle, k, self._image_dev(grad_out, k), self._cells_dev(grad_alpha, k),
+                                                            self._cells_dev(grad_q, k)))
 
     # -- motion tangent render -----------------------------------------------------------------------
     @staticmethod
@@ -581,19 +558,17 @@ class Context:
         Bit-reproducible, and every slice is bit for bit the call for that field alone."""
         f = self._motion_fields(fields)
         k = f.size // 12
-        out = np.zeros((k, self.local_rows, self.res_x, 2), dtype=np.float32)
-        self._check(self.lib.c5_render_motion_tangent(self.handle, k, _dp(f), out.ctypes.data_as(C.POINTER(C.c_float))))
+        out = self._images(k)
+        self._check(self.lib.c5_render_motion_tangent(self.handle, k, _dp(f), _fp(out)))
         return out[0] if f.ndim == 1 else out
 
     def render_motion_tangent_device(self, fields, out):
         """Asynchronous form on the context's stream: fields as above (host memory: they travel as kernel arguments), out a
         float32 [K, local_rows, res_x, 2] contiguous torch tensor on this context's GPU or a raw device pointer.  The
         status comes with the next synchronize() (C5_RETRY: run it again)."""
-        import torch
         f = self._motion_fields(fields)
         k = f.size // 12
-        self._check(self.lib.c5_render_motion_tangent_device(
-            self.handle, k, _dp(f), C.c_void_p(_device_ptr(out, torch.float32, (k, self.local_rows, self.res_x, 2)))))
+        self._check(self.lib.c5_render_motion_tangent_device(self.handle, k, _dp(f), self._image_dev(out, k)))
 
     def view_fields(self) -> np.ndarray:
         """[n_rots, 12]: the velocity field of every angle of the current view (rotation_motion)."""
@@ -603,18 +578,10 @@ class Context:
         """d image / d angle for every rotation of the current view (set_view): float32 [n_rots, local_rows, res_x, 2], per
         radian."""
         if len(self.rots) == 0:
-            return np.zeros((0, self.local_rows, self.res_x, 2), dtype=np.float32)
+            return self._images(0)
         return self.render_motion_tangent(self.view_fields())
 
     # -- Gauss-Newton renders -----------------------------------------------------------------------
-    def _weight_image(self, weight):
-        if weight is None:
-            return None
-        w = np.ascontiguousarray(weight, dtype=np.float32)
-        if w.shape != (self.local_rows, self.res_x, 2):
-            raise ValueError(f"weight must be [{self.local_rows}, {self.res_x}, 2], not {list(w.shape)}")
-        return w
-
     def render_gn_product(self, d_alpha=None, d_q=None, weight=None, want_jv: bool = False, fit=("alpha", "q")):
         """H v = J^T W J v for K directions (d_alpha / d_q: [K, n_cells], either may be None: zero), J the Jacobian of the
         frame render() would produce now, W = diag(weight) ([local_rows, res_x, 2] float32 >= 0; None: ones):
@@ -622,18 +589,12 @@ class Context:
         render_tangent_batch's.  fit names the blocks wanted (the other comes back as None).  One call for
         render_adjoint_batch(weight * render_tangent_batch(v)); synchronous, retries by itself."""
         da, dq, k = self._batch_directions(d_alpha, d_q)
-        w = self._weight_image(weight)
-        fit = tuple(fit)
-        if not fit or any(f not in ("alpha", "q") for f in fit):
-            raise ValueError(f"fit must name 'alpha', 'q' or both, not {fit!r}")
-        ha = np.zeros((k, self.n_cells), dtype=np.float64) if "alpha" in fit else None
-        hq = np.zeros((k, self.n_cells), dtype=np.float64) if "q" in fit else None
-        jv = np.zeros((k, self.local_rows, self.res_x, 2), dtype=np.float32) if want_jv else None
-        fp = C.POINTER(C.c_float)
-        self._check(self.lib.c5_render_gn_product(
-            self.handle, k, None if da is None else _dp(da), None if dq is None else _dp(dq),
-            None if w is None else w.ctypes.data_as(fp), None if ha is None else _dp(ha), None if hq is None else _dp(hq),
-            None if jv is None else jv.ctypes.data_as(fp)))
+        w = None if weight is None else self._image(weight, "weight")
+        fit = self._fit(fit)
+        ha = np.zeros((k, self.n_cells)) if "alpha" in fit else None
+        hq = np.zeros((k, self.n_cells)) if "q" in fit else None
+        jv = self._images(k) if want_jv else None
+        self._check(self.lib.c5_render_gn_product(self.handle, k, _dp(da), _dp(dq), _fp(w), _dp(ha), _dp(hq), _fp(jv)))
         return (ha, hq, jv) if want_jv else (ha, hq)
 
     def render_gn_product_device(self, d_alpha, d_q, weight, h_alpha, h_q, jv_out=None, n: int | None = None):
@@ -641,7 +602,6 @@ class Context:
         n_cells] or None, weight float32 [local_rows, res_x, 2] or None, h_alpha / h_q float64 [K, n_cells], one of them
         may be None, jv_out float32 [K, local_rows, res_x, 2] or None; contiguous) or raw device pointers (then give
         n = K).  The status comes with the next synchronize() (C5_RETRY: run it again)."""
-        import torch
         if n is None:
             shaped = [t for t in (h_alpha, h_q, d_alpha, d_q) if t is not None and not isinstance(t, int)]
             if not shaped:
@@ -652,32 +612,23 @@ class Context:
         if h_alpha is None and h_q is None:
             raise ValueError("give h_alpha and / or h_q")
         self._check(self.lib.c5_render_gn_product_device(
-            self.handle, n, C.c_void_p(_device_ptr(d_alpha, torch.float64, (n, self.n_cells)) or None),
-            C.c_void_p(_device_ptr(d_q, torch.float64, (n, self.n_cells)) or None),
-            C.c_void_p(_device_ptr(weight, torch.float32, (self.local_rows, self.res_x, 2)) or None),
-            C.c_void_p(_device_ptr(h_alpha, torch.float64, (n, self.n_cells)) or None),
-            C.c_void_p(_device_ptr(h_q, torch.float64, (n, self.n_cells)) or None),
-            C.c_void_p(_device_ptr(jv_out, torch.float32, (n, self.local_rows, self.res_x, 2)) or None)))
+            self.handle, n, self._cells_dev(d_alpha, n), self._cells_dev(d_q, n), self._image_dev(weight),
+            self._cells_dev(h_alpha, n), self._cells_dev(h_q, n), self._image_dev(jv_out, n)))
 
     def render_gn_diagonal(self, weight=None) -> tuple:
         """diag(J^T W J) as (diag_alpha, diag_q), float64 [n_cells] each in the order of upload_grid (weight: as
         render_gn_product).  Synchronous; retries by itself."""
-        w = self._weight_image(weight)
-        da = np.zeros(self.n_cells, dtype=np.float64)
-        dq = np.zeros(self.n_cells, dtype=np.float64)
-        self._check(self.lib.c5_render_gn_diagonal(self.handle, None if w is None else w.ctypes.data_as(C.POINTER(C.c_float)),
-                                                   _dp(da), _dp(dq)))
+        w = None if weight is None else self._image(weight, "weight")
+        da, dq = np.zeros(self.n_cells), np.zeros(self.n_cells)
+        self._check(self.lib.c5_render_gn_diagonal(self.handle, _fp(w), _dp(da), _dp(dq)))
         return da, dq
 
     def render_gn_diagonal_device(self, weight, diag_alpha, diag_q):
         """Asynchronous form on the context's stream: torch tensors on this context's GPU (weight float32 [local_rows,
         res_x, 2] or None, diag_alpha / diag_q float64 [n_cells]; contiguous) or raw device pointers.  The status comes
         with the next synchronize() (C5_RETRY: run it again)."""
-        import torch
-        self._check(self.lib.c5_render_gn_diagonal_device(
-            self.handle, C.c_void_p(_device_ptr(weight, torch.float32, (self.local_rows, self.res_x, 2)) or None),
-            C.c_void_p(_device_ptr(diag_alpha, torch.float64, (self.n_cells,))),
-            C.c_void_p(_device_ptr(diag_q, torch.float64, (self.n_cells,)))))
+        self._check(self.lib.c5_render_gn_diagonal_device(self.handle, self._image_dev(weight), self._cells_dev(diag_alpha),
+                                                          self._cells_dev(diag_q)))
 
     # -- Hessian-vector render ------------------------------------------------------------------------
     def render_hvp(self, d_alpha=None, d_q=None, grad_out=None, fit=("alpha", "q")) -> tuple:
@@ -686,30 +637,16 @@ class Context:
         grad_out [local_rows, res_x, 2] the upstream image (channel 0 has no effect: tau is linear in alpha).  float64
         [n_cells] each in the order of upload_grid; fit names the blocks wanted (the other comes back as None).
         Synchronous; retries by itself.  Not bit-reproducible (fp64 atomics), as render_adjoint."""
-        def direction(d):
-            if d is None:
-                return None
-            d = np.ascontiguousarray(d, dtype=np.float64)
-            if d.shape != (self.n_cells,):
-                raise ValueError(f"a direction must hold one value per cell ({self.n_cells}), not {list(d.shape)}")
-            return d
-
-        da, dq = direction(d_alpha), direction(d_q)
+        da, dq = self._direction(d_alpha), self._direction(d_q)
         if da is None and dq is None:
             raise ValueError("give d_alpha and / or d_q")
         if grad_out is None:
             raise ValueError("grad_out is required")
-        g = np.ascontiguousarray(grad_out, dtype=np.float32)
-        if g.shape != (self.local_rows, self.res_x, 2):
-            raise ValueError(f"grad_out must be [{self.local_rows}, {self.res_x}, 2], not {list(g.shape)}")
-        fit = tuple(fit)
-        if not fit or any(f not in ("alpha", "q") for f in fit):
-            raise ValueError(f"fit must name 'alpha', 'q' or both, not {fit!r}")
-        ha = np.zeros(self.n_cells, dtype=np.float64) if "alpha" in fit else None
-        hq = np.zeros(self.n_cells, dtype=np.float64) if "q" in fit else None
-        self._check(self.lib.c5_render_hvp(
-            self.handle, None if da is None else _dp(da), None if dq is None else _dp(dq), g.ctypes.data_as(C.POINTER(C.c_float)),
-            None if ha is None else _dp(ha), None if hq is None else _dp(hq)))
+        g = self._image(grad_out, "grad_out")
+        fit = self._fit(fit)
+        ha = np.zeros(self.n_cells) if "alpha" in fit else None
+        hq = np.zeros(self.n_cells) if "q" in fit else None
+        self._check(self.lib.c5_render_hvp(self.handle, _dp(da), _dp(dq), _fp(g), _dp(ha), _dp(hq)))
         return ha, hq
 
     def render_hvp_device(self, d_alpha, d_q, grad_out, h_alpha, h_q):
@@ -717,19 +654,15 @@ class Context:
         one of them may be None; grad_out float32 [local_rows, res_x, 2]; h_alpha / h_q float64 [n_cells], one of them may
         be None; contiguous) or raw device pointers.  The status comes with the next synchronize() (C5_RETRY: run it
         again)."""
-        import torch
         if d_alpha is None and d_q is None:
             raise ValueError("give d_alpha and / or d_q")
         if h_alpha is None and h_q is None:
             raise ValueError("give h_alpha and / or h_q")
         if grad_out is None:
             raise ValueError("grad_out is required")
-        cells = (self.n_cells,)
-        args = [C.c_void_p(_device_ptr(d_alpha, torch.float64, cells) or None), C.c_void_p(_device_ptr(d_q, torch.float64, cells) or None),
-                C.c_void_p(_device_ptr(grad_out, torch.float32, (self.local_rows, self.res_x, 2))),
-                C.c_void_p(_device_ptr(h_alpha, torch.float64, cells) or None), C.c_void_p(_device_ptr(h_q, torch.float64, cells) or None)]
-        self._check(self.lib.c5_render_hvp_device(self.handle, *args))
-
+        ptrs = (self._cells_dev(d_alpha), self._cells_dev(d_q), self._image_dev(grad_out), self._cells_dev(h_alpha),
+                self._cells_dev(h_q))
+        self._check(self.lib.c5_render_hvp_device(self.handle, *ptrs))
     # -- frames delivered to host memory, pipelined -------------------------------------------------
     def host_image(self, full: bool = False) -> np.ndarray:
         """A pinned float32 [local_rows (or res_y), res_x, 2] image (c5_host_alloc); release with free_host_image."""
@@ -827,16 +760,19 @@ class Context:
         return out
 
 
+def _host_check(lib, rc: int) -> None:
+    """The status of a call that takes no context."""
+    if rc != C5_OK:
+        raise C5Error(rc, lib.c5_last_error(None).decode())
+
+
 def face_adjacency(cells, n_pts: int):
     """Host-only: (adj[n,4], n_boundary_faces) via c5_face_adjacency."""
     lib = load_library()
     cells = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 4)
     adj = np.empty_like(cells)
     nb = C.c_int64()
-    rc = lib.c5_face_adjacency(cells.ctypes.data_as(C.POINTER(C.c_int32)), cells.shape[0], n_pts,
-                               adj.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nb))
-    if rc != C5_OK:
-        raise C5Error(rc, lib.c5_last_error(None).decode())
+    _host_check(lib, lib.c5_face_adjacency(cells.ctypes.data_as(_ip_t), cells.shape[0], n_pts, adj.ctypes.data_as(_ip_t), C.byref(nb)))
     return adj, nb.value
 
 
@@ -846,9 +782,7 @@ def rotation_motion(rots, index: int, what: int = 0) -> np.ndarray:
     lib = load_library()
     arr, n = _rot_array(rots)
     field = np.zeros(12, dtype=np.float64)
-    rc = lib.c5_rotation_motion(arr, n, index, what, _dp(field))
-    if rc != C5_OK:
-        raise C5Error(rc, lib.c5_last_error(None).decode())
+    _host_check(lib, lib.c5_rotation_motion(arr, n, index, what, _dp(field)))
     return field
 
 
@@ -858,9 +792,7 @@ def weld_points(xyz):
     xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
     rep = np.empty(xyz.shape[0], dtype=np.int32)
     m = C.c_int64()
-    rc = lib.c5_weld_points(_dp(xyz), xyz.shape[0], rep.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(m))
-    if rc != C5_OK:
-        raise C5Error(rc, lib.c5_last_error(None).decode())
+    _host_check(lib, lib.c5_weld_points(_dp(xyz), xyz.shape[0], rep.ctypes.data_as(_ip_t), C.byref(m)))
     return rep, m.value
 
 

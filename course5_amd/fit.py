@@ -27,6 +27,8 @@ from __future__ import annotations
 
 import torch
 
+from . import capi
+
 
 class _LibraryOperators:
     """The three operators of a capi.Context."""
@@ -42,12 +44,7 @@ class _LibraryOperators:
             g = residual.detach().to(device=device, dtype=torch.float32)
             if self.weight is not None:
                 g = g * autograd._gn_weight(ctx, self.weight, device)
-            g = g.contiguous()
-            ga = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
-            gq = torch.empty(ctx.n_cells, dtype=torch.float64, device=device)
-            autograd._use_torch_stream(ctx, device)
-            autograd._run(ctx, lambda: ctx.render_adjoint_device(g, ga, gq))
-        return ga, gq
+            return autograd._adjoint(ctx, g.contiguous(), device)
 
     def diagonal(self):
         from . import autograd
@@ -76,9 +73,7 @@ def _operators(ctx, alpha, q, weight):
 
 def _cg_step(ctx, alpha, q, residual, weight, fit, damping, iters, precondition, exact):
     """gn_step (exact False: H = J^T W J) and newton_step (exact True: H the exact Hessian of 1/2 sum w r^2)."""
-    fit = tuple(fit)
-    if not fit or any(f not in ("alpha", "q") for f in fit) or len(set(fit)) != len(fit):
-        raise ValueError(f"fit must name 'alpha', 'q' or both, not {fit!r}")
+    fit = capi.Context._fit(fit, once=True)
     if damping < 0.0 or iters < 1:
         raise ValueError("damping must be >= 0 and iters >= 1")
     ops = _operators(ctx, alpha, q, weight)

@@ -59,7 +59,7 @@ def test_functions_have_vmap_rules_and_refuse_second_derivatives():
     from course5_amd import autograd
     for fn in (autograd._Render, autograd._Tangent, autograd._Adjoint):
         for name in ("forward", "setup_context", "backward", "jvp", "vmap"):
-            assert name in vars(fn), (fn.__name__, name)
+            assert getattr(fn, name) is not getattr(torch.autograd.Function, name), (fn.__name__, name)  # (overridden below torch's)
     a, q = torch.zeros(4), torch.zeros(4)
     info = types.SimpleNamespace(batch_size=2, randomness="error")
     with pytest.raises(RuntimeError, match="a batch of scalar fields"):
@@ -70,6 +70,12 @@ def test_functions_have_vmap_rules_and_refuse_second_derivatives():
         autograd._Tangent.backward(None, torch.zeros(3))
     with pytest.raises(RuntimeError, match="second derivatives are not supported"):
         autograd._Adjoint.jvp(None, None, None, None)
+    for fn, what in ((autograd._Tangent, "tangent"), (autograd._Adjoint, "adjoint"), (autograd._ViewTangent, "motion tangent"),
+                     (autograd._ViewAdjoint, "motion tangent"), (autograd._VertexAdjoint, "vertex adjoint"),
+                     (autograd._VertexTangent, "vertex tangent")):
+        for refuse in (fn.backward, fn.jvp):
+            with pytest.raises(RuntimeError, match=rf"second derivatives are not supported \(the {what} render has no"):
+                refuse(None, torch.zeros(3))
     fctx = types.SimpleNamespace(levels=2, primals=(a, q))
     with pytest.raises(RuntimeError, match="second derivatives are not supported"):
         autograd._Render.backward(fctx, torch.zeros(3, 4, 2))

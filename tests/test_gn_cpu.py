@@ -12,6 +12,7 @@ import pytest
 from course5_amd import capi
 from course5_amd import meshgen as mg
 from tests import adjoint_reference as ar
+from tests.fake_library import bare_context
 from tests import gn_reference as gr
 from tests import tangent_reference as tr
 
@@ -55,22 +56,8 @@ def test_library_and_bindings_have_them():
     assert params["fit"].default == ("q",) and params["damping"].default == 0.0 and params["precondition"].default is True
 
 
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError(f"the library was entered ({name})")
-
-
-def _bare_context(n_cells=7, rows=5, cols=6):
-    ctx = capi.Context.__new__(capi.Context)  # (no GPU here: the argument checks come before the library)
-    ctx.lib, ctx.handle = _NoLibrary(), None
-    ctx.n_cells, ctx.res_x, ctx.res_y, ctx.device = n_cells, cols, rows, 0
-    ctx.__dict__["_local_rows"] = rows
-    return ctx
-
-
-def test_argument_checks_raise_before_the_library(monkeypatch):
-    monkeypatch.setattr(capi.Context, "local_rows", property(lambda self: self.__dict__["_local_rows"]), raising=False)
-    ctx = _bare_context()
+def test_argument_checks_raise_before_the_library():
+    ctx = bare_context()
     good = np.zeros((2, 7))
     with pytest.raises(ValueError, match=r"directions must be \[K, 7\]"):
         ctx.render_gn_product(np.zeros(7), None)

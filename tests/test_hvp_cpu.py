@@ -25,6 +25,7 @@ import pytest
 from course5_amd import capi
 from course5_amd import meshgen as mg
 from tests import adjoint_reference as ar
+from tests.fake_library import bare_context
 from tests import hvp_reference as hr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -344,17 +345,8 @@ def test_the_forward_kernels_are_untouched():
     assert build.kernel_source_hash() == "85a78f3eaf095461"
 
 
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError(f"the library was entered ({name})")
-
-
-def test_argument_checks_raise_before_the_library(monkeypatch):
-    monkeypatch.setattr(capi.Context, "local_rows", property(lambda self: self.__dict__["_local_rows"]), raising=False)
-    ctx = capi.Context.__new__(capi.Context)  # (no GPU here: the argument checks come before the library)
-    ctx.lib, ctx.handle = _NoLibrary(), None
-    ctx.n_cells, ctx.res_x, ctx.res_y, ctx.device = 7, 6, 5, 0
-    ctx.__dict__["_local_rows"] = 5
+def test_argument_checks_raise_before_the_library():
+    ctx = bare_context()
     g = np.zeros((5, 6, 2), np.float32)
     with pytest.raises(ValueError, match=r"one value per cell \(7\)"):
         ctx.render_hvp(np.zeros(8), None, g)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from course5_amd import capi
+from tests.fake_library import bare_context
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DECLARATIONS = (
@@ -36,25 +37,8 @@ def test_header_declares_and_the_library_exports_the_four_symbols():
     assert "ray_matrix" in autograd.__all__
 
 
-class _NoLibrary:
-    """Any call into the library fails the test: the wrappers must have raised before."""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"{name} reached the library")
-
-
-class _Ctx(capi.Context):
-    local_rows = 5
-
-    def __init__(self):  # no library, no GPU
-        self.lib, self.handle, self.res_x, self.n_cells = _NoLibrary(), None, 7, 11
-
-    def __del__(self):
-        pass
-
-
 def test_fill_rejects_wrong_row_ptr_shapes_and_dtypes_before_touching_a_gpu():
-    ctx = _Ctx()
+    ctx = bare_context(n_cells=11, rows=5, cols=7)
     n = 5 * 7 + 1
     for bad in (np.zeros(n, np.int32), np.zeros(n, np.float64), np.zeros(n - 1, np.int64), np.zeros((n, 1), np.int64),
                 [0] * n, None):
@@ -66,7 +50,7 @@ def test_fill_rejects_wrong_row_ptr_shapes_and_dtypes_before_touching_a_gpu():
 
 def test_device_forms_reject_wrong_tensors_before_touching_a_gpu():
     import torch
-    ctx = _Ctx()
+    ctx = bare_context(n_cells=11, rows=5, cols=7)
     n = 5 * 7 + 1
     # (CPU tensors, wrong dtypes, wrong lengths: _device_ptr raises before the call)
     for bad in (torch.zeros(n, dtype=torch.int64), torch.zeros(n, dtype=torch.int32), torch.zeros(n - 1, dtype=torch.int64)):

@@ -16,6 +16,7 @@ import pytest
 from course5_amd import build, capi, meshgen as mg
 from tests import adjoint_reference as ar, derivative_fuzz as fz, motion_reference as mr
 from tests import vertex_adjoint_reference as vr, vertex_tangent_reference as vt
+from tests.fake_library import bare_context
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOUNDS = (1.9, 0.1, 0.9, -0.9)
@@ -159,18 +160,9 @@ def test_pins_still_hold():
     assert "#define C5_ABI_VERSION 2" in open(os.path.join(ROOT, "include", "course5_hip.h")).read()
 
 
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError(f"the library was entered ({name})")
-
-
-def test_argument_checks_before_the_library(monkeypatch):
+def test_argument_checks_before_the_library():
     import torch
-    monkeypatch.setattr(capi.Context, "local_rows", property(lambda self: self.__dict__["_local_rows"]), raising=False)
-    ctx = capi.Context.__new__(capi.Context)  # (no GPU here: the argument checks come before the library)
-    ctx.lib, ctx.handle = _NoLibrary(), None
-    ctx.n_cells, ctx.n_pts, ctx.res_x, ctx.res_y, ctx.device = 7, 9, 6, 5, 0
-    ctx.__dict__["_local_rows"] = 5
+    ctx = bare_context()
     for bad in (np.zeros(27), np.zeros((8, 3)), np.zeros((9, 2)), np.zeros((2, 8, 3)), np.zeros((0, 9, 3)), np.zeros((1, 2, 9, 3))):
         with pytest.raises(ValueError, match=r"d_xyz must be \[9, 3\] or \[K, 9, 3\]"):
             ctx.render_vertex_tangent(bad)
