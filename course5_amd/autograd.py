@@ -30,7 +30,8 @@ The context holds ONE set of scalars: a backward or jvp whose forward's scalars 
 an update_scalars) uploads its own again, from the copy the forward kept (on the GPU when they came from there).  A
 backward or jvp after the view, image, rows, solids, alpha limit or grid changed raises instead of differentiating a frame
 other than the one rendered.  The gradients are fp64 sums added by atomics in arrival order: not bit-reproducible from run
-to run; the tangent is, batched or not.
+to run, unless the context's option "adjoint_exact" is 1 (ctx.set_option("adjoint_exact", 1): the backward calls
+render_adjoint_device, which then returns the exact integer sums - the same bits every run); the tangent is, batched or not.
 
 render_view(ctx, alpha, q, angles) is render with the view's angles as a third differentiable input: angles [n_rots]
 (radians) are written into the context's current rotation list (axes and x0 kept) before the frame is rendered.  Its

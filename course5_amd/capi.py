@@ -105,6 +105,12 @@ SIGNATURES = {
     "c5_ray_matrix_rows_device": [_vp, _vp, _lp_t],
     "c5_ray_matrix_fill": [_vp, _lp_t, C.c_int64, _ip_t, _dp_t, _dp_t],
     "c5_ray_matrix_fill_device": [_vp, _vp, C.c_int64, _vp, _vp, _vp],
+    "c5_render_adjoint_exact_bounds": [_vp, _fp_t, _ip_t, _ip_t],
+    "c5_render_adjoint_exact_bounds_device": [_vp, _vp, _vp, _vp],
+    "c5_render_adjoint_exact_sums": [_vp, _fp_t, _ip_t, _ip_t, _lp_t, _lp_t],
+    "c5_render_adjoint_exact_sums_device": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "c5_exact_sums_finish": [_ip_t, _lp_t, C.c_int64, C.c_int, C.c_int, _dp_t],
+    "c5_exact_quantise": [_dp_t, C.c_int64, C.c_int32, C.c_int, C.c_int, _lp_t],
 }
 EXPORTS = list(SIGNATURES)
 
@@ -355,7 +361,8 @@ class Context:
     def render_adjoint(self, grad_out) -> tuple:
         """Gradients of the frame render() would produce now, weighted by grad_out ([local_rows, res_x, 2]: the weights
         of tau and of I per pixel): (grad_alpha, grad_q), float64 [n_cells] each in the order of upload_grid.
-        Synchronous; retries by itself."""
+        Synchronous; retries by itself.  fp64 atomics, not bit-reproducible - unless set_option("adjoint_exact", 1): then
+        the exact sums, the same bits every run and for any split of the rows (as for the _device and batch forms)."""
         g = self._image(grad_out, "grad_out")
         ga, gq = np.zeros(self.n_cells), np.zeros(self.n_cells)
         self._check(self.lib.c5_render_adjoint(self.handle, _fp(g), _dp(ga), _dp(gq)))
@@ -367,6 +374,56 @@ class Context:
         pointers.  The status comes with the next synchronize() (C5_RETRY: run it again)."""
         self._check(self.lib.c5_render_adjoint_device(self.handle, self._image_dev(grad_out), self._cells_dev(grad_alpha),
                                                       self._cells_dev(grad_q)))
+
+    # -- exact adjoint sums ------------------------------------------------------------------------
+    # (set_option("adjoint_exact", 1) makes render_adjoint* return them finished; these are the two intermediate results,
+    # for callers who split an image: sharding.combine_exact, then exact_sums_finish)
+    def _exponents(self, e, name: str) -> np.ndarray:
+        e = np.asarray(e)
+        if e.dtype != np.int32 or e.shape != (self.n_cells,) or not e.flags.c_contiguous:
+            raise ValueError(f"{name} must be a contiguous int32 array of one exponent per cell ({self.n_cells}), "
+                             f"not {e.dtype} {list(e.shape)}")
+        return e
+
+    def render_adjoint_exact_bounds(self, grad_out) -> tuple:
+        """The exponents of the exact adjoint sums over the context's rows for the upstream image grad_out ([local_rows,
+        res_x, 2]): (exp_alpha, exp_q), int32 [n_cells] each in the order of upload_grid (INT32_MIN: no contribution,
+        INT32_MAX: one that is not finite).  Parts of an image combine by elementwise max.  Synchronous; retries by itself."""
+        g = self._image(grad_out, "grad_out")
+        ea, eq = np.zeros(self.n_cells, np.int32), np.zeros(self.n_cells, np.int32)
+        self._check(self.lib.c5_render_adjoint_exact_bounds(self.handle, _fp(g), ea.ctypes.data_as(_ip_t), eq.ctypes.data_as(_ip_t)))
+        return ea, eq
+
+    def render_adjoint_exact_sums(self, grad_out, exp_alpha, exp_q) -> tuple:
+        """The words of the exact adjoint sums over the context's rows against the given exponents (int32 [n_cells] each:
+        those of render_adjoint_exact_bounds, combined over every part of the image): (sums_alpha, sums_q), int64
+        [n_cells, 2] each.  Parts of an image combine by elementwise integer add.  C5_ERR_INVALID if a contribution lies
+        beyond its cell's exponent.  Synchronous; retries by itself."""
+        g = self._image(grad_out, "grad_out")
+        ea, eq = self._exponents(exp_alpha, "exp_alpha"), self._exponents(exp_q, "exp_q")
+        sa, sq = np.zeros((self.n_cells, 2), np.int64), np.zeros((self.n_cells, 2), np.int64)
+        self._check(self.lib.c5_render_adjoint_exact_sums(self.handle, _fp(g), ea.ctypes.data_as(_ip_t), eq.ctypes.data_as(_ip_t),
+                                                          sa.ctypes.data_as(_lp_t), sq.ctypes.data_as(_lp_t)))
+        return sa, sq
+
+    def render_adjoint_exact_bounds_device(self, grad_out, exp_alpha, exp_q):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (grad_out float32 [local_rows,
+        res_x, 2], exp_alpha / exp_q int32 [n_cells], contiguous) or raw device pointers.  The status comes with the next
+        synchronize()."""
+        import torch
+        n = (self.n_cells,)
+        self._check(self.lib.c5_render_adjoint_exact_bounds_device(self.handle, self._image_dev(grad_out), _device_ptr(exp_alpha, torch.int32, n),
+                                                                   _device_ptr(exp_q, torch.int32, n)))
+
+    def render_adjoint_exact_sums_device(self, grad_out, exp_alpha, exp_q, sums_alpha, sums_q):
+        """Asynchronous form on the context's stream: as render_adjoint_exact_bounds_device, and sums_alpha / sums_q int64
+        [n_cells, 2].  The status (C5_ERR_INVALID for exponents that are too small included) comes with the next
+        synchronize()."""
+        import torch
+        n, n2 = (self.n_cells,), (self.n_cells, 2)
+        self._check(self.lib.c5_render_adjoint_exact_sums_device(
+            self.handle, self._image_dev(grad_out), _device_ptr(exp_alpha, torch.int32, n), _device_ptr(exp_q, torch.int32, n),
+            _device_ptr(sums_alpha, torch.int64, n2), _device_ptr(sums_q, torch.int64, n2)))
 
     # -- vertex adjoint render ---------------------------------------------------------------------
     def render_vertex_adjoint(self, grad_out) -> np.ndarray:
@@ -764,6 +821,23 @@ def _host_check(lib, rc: int) -> None:
     """The status of a call that takes no context."""
     if rc != C5_OK:
         raise C5Error(rc, lib.c5_last_error(None).decode())
+
+
+def exact_sums_finish(exp, sums, res_x: int, res_y: int) -> np.ndarray:
+    """Host-only: the fp64 values of exact adjoint sums - exp int32 [n], sums int64 [n, 2], contiguous, for an image of
+    res_x x res_y pixels (the whole image, not a rank's rows) - rounded once, via c5_exact_sums_finish."""
+    exp, sums = np.asarray(exp), np.asarray(sums)
+    if exp.dtype != np.int32 or exp.ndim != 1 or not exp.flags.c_contiguous:
+        raise ValueError(f"exp must be a contiguous int32 array [n], not {exp.dtype} {list(exp.shape)}")
+    if sums.dtype != np.int64 or sums.shape != (exp.shape[0], 2) or not sums.flags.c_contiguous:
+        raise ValueError(f"sums must be a contiguous int64 array [{exp.shape[0]}, 2], not {sums.dtype} {list(sums.shape)}")
+    if int(res_x) < 1 or int(res_y) < 1:
+        raise ValueError(f"an image of {res_x} x {res_y} pixels")
+    lib = load_library()
+    out = np.zeros(exp.shape[0], dtype=np.float64)
+    _host_check(lib, lib.c5_exact_sums_finish(exp.ctypes.data_as(_ip_t), sums.ctypes.data_as(_lp_t), exp.shape[0], int(res_x), int(res_y),
+                                              _dp(out)))
+    return out
 
 
 def face_adjacency(cells, n_pts: int):

@@ -45,6 +45,29 @@ void launch_adjoint_resolve(hipStream_t s, const ResolveParams& r, const float2*
 void launch_adjoint_permute(hipStream_t s, const double* ga_dev, const double* gq_dev, const int32_t* perm, int64_t n,
                             double* ga_out, double* gq_out);
 
+// ---- exact adjoint sums ("adjoint_exact", c5_render_adjoint_exact_*): the fixed-point format of exact_sum.hpp.  40
+// bytes per cell and one word, in device order.
+struct ExactSums {
+    int2* exps;            // [n_cells] {exponent of grad_alpha's contributions, of grad_q's}: pass E's atomicMax
+    long long* words;      // [n_cells][4] {alpha s1, alpha s0, q s1, q s0}: pass S's integer atomicAdd
+    unsigned* misfits;     // += contributions pass S found beyond their cell's exponent (added nowhere)
+    int32_t word_bits;     // m of the WHOLE image (c5_set_image), not of the context's rows
+    int32_t keep_entries;  // pass S, the walk: 1 leaves the entry heads in place (another image follows); 0 hands them back cleared
+};
+
+// exps to "no contribution", words to zero and / or *misfits to zero
+void launch_exact_clear(hipStream_t s, const ExactSums& x, int64_t n, bool exps, bool words, bool misfits);
+// pass E (sums false: leaves the entry heads in place) or pass S of the walk; both need launch_adjoint_walk(.., 1) first
+// and read a.w, a.grad_out and a.lambda only
+void launch_adjoint_exact_walk(hipStream_t s, const AdjointParams& a, const ExactSums& x, bool sums);
+// the same over bin_sort_resolve's lists (sorts them in place, as launch_adjoint_resolve)
+void launch_adjoint_exact_resolve(hipStream_t s, const ResolveParams& r, const float2* grad_out, const ExactSums& x, bool sums);
+// x.exps[i] = {exp_a[perm[i]], exp_q[perm[i]]} (perm nullptr: the identity), and back; the words back; the words as fp64
+void launch_exact_gather_exps(hipStream_t s, const int32_t* exp_a, const int32_t* exp_q, const int32_t* perm, int64_t n, const ExactSums& x);
+void launch_exact_emit_exps(hipStream_t s, const ExactSums& x, const int32_t* perm, int64_t n, int32_t* exp_a, int32_t* exp_q);
+void launch_exact_emit_words(hipStream_t s, const ExactSums& x, const int32_t* perm, int64_t n, int64_t* sums_a, int64_t* sums_q);
+void launch_exact_finish(hipStream_t s, const ExactSums& x, const int32_t* perm, int64_t n, double* ga_out, double* gq_out);
+
 struct TangentParams {
     // the walk's inputs, as for the adjoint (records of "integration" 0)
     WalkParams w;

@@ -241,7 +241,8 @@ void c5_destroy(c5_context* ctx) {
                             &ctx->offs64, &ctx->scratch64, &ctx->segs, &ctx->adj_lambda, &ctx->adj_counters,
                             &ctx->adj_sticky, &ctx->adj_grad, &ctx->adj_perm, &ctx->tan_dir,
                             &ctx->bat_dirs, &ctx->bat_grad, &ctx->gn_g, &ctx->gn_spare, &ctx->deriv_io,
-                            &ctx->scal_stats, &ctx->vtx_face, &ctx->vtx_grad, &ctx->vtx_vel, &ctx->rm_count, &ctx->hvp_lambda_dot};
+                            &ctx->scal_stats, &ctx->vtx_face, &ctx->vtx_grad, &ctx->vtx_vel, &ctx->rm_count, &ctx->hvp_lambda_dot,
+                            &ctx->adj_exact};
     if (ctx->host_sticky) (void)hipHostFree(ctx->host_sticky);
     if (ctx->adj_status) (void)hipHostFree(ctx->adj_status);
     if (ctx->scal_host) (void)hipHostFree(ctx->scal_host);
@@ -562,6 +563,8 @@ int c5_set_option(c5_context* ctx, const char* name, double value) {
         ctx->batch_width = static_cast<int>(value);
     } else if (n == "vertex_merge") {
         ctx->vertex_merge = static_cast<int>(value) != 0;
+    } else if (n == "adjoint_exact") {
+        ctx->adjoint_exact = static_cast<int>(value) != 0;
     } else if (n == "split_tilt_x" || n == "split_tilt_y") {  // testing: tilt of a forced split's planes
         if (!(std::fabs(value) < 64.0)) return fail(ctx, C5_ERR_INVALID, "split tilt out of range");
         (n == "split_tilt_x" ? ctx->split_tilt_x : ctx->split_tilt_y) = value;

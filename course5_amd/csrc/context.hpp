@@ -270,9 +270,14 @@ struct c5_context {
     c5api::DeviceBuffer adj_grad;      // [2][n_cells] fp64, device order
     c5api::DeviceBuffer adj_perm;      // cell_perm on the device, for the grid of upload adj_perm_serial
     uint64_t grid_serial = 0, adj_perm_serial = ~uint64_t{0};
-    unsigned* adj_status = nullptr;  // pinned: walk_overflow, entry_overflow, overlap_rays of the last adjoint or tangent
+    unsigned* adj_status = nullptr;  // pinned: walk_overflow, entry_overflow, overlap_rays of the last adjoint or tangent,
+                                     // rows a ray matrix fill found changed, contributions an exact sum found beyond their exponent
     bool adjoint_pending = false;    // its status has not been looked at yet
     const char* adj_what = "adjoint";  // which of the two it was (finish_adjoint's messages)
+
+    // exact adjoint sums ("adjoint_exact", c5_render_adjoint_exact_*): allocated at the first exact call only
+    int adjoint_exact = 0;           // "adjoint_exact": c5_render_adjoint* and its batch return the exact sums (exact_sum.hpp)
+    c5api::DeviceBuffer adj_exact;   // [n_cells][4] int64 words, [n_cells] int2 exponents (device order), then the misfit word
 
     // tangent render (c5_render_tangent*): shares the adjoint's counters, sticky and status words and adj_perm; nothing of
     // it is allocated before the first tangent call

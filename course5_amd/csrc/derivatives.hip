@@ -7,6 +7,7 @@
 // stale, so the next frame builds its own ("view_cache").
 // ------------------------------------------------------------------------------------------
 #include "context.hpp"
+#include "exact_sum.hpp"
 
 using namespace c5api;
 
@@ -49,8 +50,9 @@ int setup_derivative(c5_context* ctx, DerivativeView& v) {
     C5_HIP(ctx, ctx->adj_counters.ensure(kCountersBytes));
     C5_HIP(ctx, ctx->adj_sticky.ensure(kStickyWords * sizeof(unsigned)));
     if (!ctx->adj_status) {
-        C5_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->adj_status), 4 * sizeof(unsigned), hipHostMallocDefault));
+        C5_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->adj_status), 5 * sizeof(unsigned), hipHostMallocDefault));
         ctx->adj_status[3] = 0;  // (rows a ray matrix fill found changed: written by that call alone, cleared by finish_adjoint)
+        ctx->adj_status[4] = 0;  // (contributions an exact sum found beyond their cell's exponent: the same)
     }
     rc = ensure_device_perm(ctx);
     if (rc) return rc;
@@ -162,11 +164,106 @@ int adjoint_one(c5_context* ctx, const DerivativeView& v, bool squared, const fl
     return C5_OK;
 }
 
-// The adjoint: adjoint_one on the upstream image.
+// The exact sums' buffer over the context's cells - 40 bytes per cell and the misfit word, allocated here at the first
+// exact call - with the word width of the WHOLE image (c5_set_image): the same for every rank of a split.
+int exact_sums(c5_context* ctx, c5::ExactSums& x) {
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
+    const int m = c5::exact::word_bits(static_cast<int64_t>(ctx->im.res_x) * ctx->im.res_y);
+    if (m < c5::exact::kMinWordBits)
+        return fail(ctx, C5_ERR_INVALID, "exact sums: an image of %d x %d pixels leaves %d bits per word", ctx->im.res_x, ctx->im.res_y, m);
+    C5_HIP(ctx, ctx->adj_exact.ensure(n_cells * 40 + 8));
+    x = c5::ExactSums{};
+    x.words = ctx->adj_exact.as<long long>();
+    x.exps = reinterpret_cast<int2*>(x.words + 4 * n_cells);
+    x.misfits = reinterpret_cast<unsigned*>(x.exps + n_cells);
+    x.word_bits = m;
+    return C5_OK;
+}
+
+// The exact passes over the view for one upstream image: pass 1 (unless Lambda is there: `have_lambda`, a batch's later
+// images), pass E into x.exps (`bounds`: cleared here first) and pass S against x.exps into x.words (`sums`: cleared here
+// first, the misfit word with them where `first`) - the walk's, or the resolve's over bin_sort_resolve's lists.  keep: the
+// walk's pass S leaves the entry heads in place (another image follows); without pass S they stay in place anyway, and the
+// next per-view setup clears them.
+int exact_passes(c5_context* ctx, const DerivativeView& v, c5::ExactSums x, const float2* weights, bool bounds, bool sums,
+                 bool have_lambda, bool keep, bool first) {
+    c5::launch_exact_clear(v.s, x, ctx->n_cells, bounds, sums, sums && first);
+    if (v.bin_sort) {
+        if (bounds) c5::launch_adjoint_exact_resolve(v.s, v.r, weights, x, false);
+        if (sums) c5::launch_adjoint_exact_resolve(v.s, v.r, weights, x, true);
+        return C5_OK;
+    }
+    c5::AdjointParams ap;
+    int rc = adjoint_params(ctx, v, ap);
+    if (rc) return rc;
+    ap.grad_out = weights;
+    if (!have_lambda) c5::launch_adjoint_walk(v.s, ap, 1);
+    if (bounds) c5::launch_adjoint_exact_walk(v.s, ap, x, false);
+    x.keep_entries = keep ? 1 : 0;
+    if (sums) {
+        c5::launch_adjoint_exact_walk(v.s, ap, x, true);
+        if (!keep) ctx->slots[0].head_clean = true;  // (pass S hands every head back cleared)
+    }
+    return C5_OK;
+}
+
+// commit_derivative for a call that ran pass S: the misfit word travels to the host behind the status words
+int commit_exact(c5_context* ctx, const c5::ExactSums& x, const char* what) {
+    int rc = commit_derivative(ctx, what);
+    if (rc) return rc;
+    C5_HIP(ctx, hipMemcpyAsync(ctx->adj_status + 4, x.misfits, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    return C5_OK;
+}
+
+// "adjoint_exact" 1: n upstream images -> ga_out / gq_out [n][n_cells], every image through passes E and S and the
+// finish, one after the other (the host loop "algorithm" 1 uses for its batches); pass 1 runs once for all of them.
+int exact_images(c5_context* ctx, const DerivativeView& v, int n, const float2* grad_out, double* ga_out, double* gq_out, const char* what) {
+    c5::ExactSums x;
+    int rc = exact_sums(ctx, x);
+    const int64_t n_cells = ctx->n_cells;
+    for (int j = 0; j < n && !rc; ++j) {
+        rc = exact_passes(ctx, v, x, grad_out + j * v.n_px, true, true, j > 0, j + 1 < n, j == 0);
+        if (!rc) c5::launch_exact_finish(v.s, x, v.perm, n_cells, ga_out + j * n_cells, gq_out + j * n_cells);
+    }
+    return rc ? rc : commit_exact(ctx, x, what);
+}
+
+// c5_render_adjoint_exact_bounds: pass 1 and pass E over the context's rows; the exponents in the caller's order
+int enqueue_exact_bounds(c5_context* ctx, const float2* grad_out, int32_t* exp_a, int32_t* exp_q) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc || v.no_cells) return rc;
+    c5::ExactSums x;
+    rc = exact_sums(ctx, x);
+    if (!rc) rc = exact_passes(ctx, v, x, grad_out, true, false, false, false, false);
+    if (rc) return rc;
+    c5::launch_exact_emit_exps(v.s, x, v.perm, ctx->n_cells, exp_a, exp_q);
+    return commit_derivative(ctx, "adjoint exact bounds");
+}
+
+// c5_render_adjoint_exact_sums: the caller's exponents into device order, pass 1 and pass S against them; the words in
+// the caller's order
+int enqueue_exact_sums(c5_context* ctx, const float2* grad_out, const int32_t* exp_a, const int32_t* exp_q, int64_t* sums_a,
+                       int64_t* sums_q) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc || v.no_cells) return rc;
+    c5::ExactSums x;
+    rc = exact_sums(ctx, x);
+    if (rc) return rc;
+    c5::launch_exact_gather_exps(v.s, exp_a, exp_q, v.perm, ctx->n_cells, x);
+    rc = exact_passes(ctx, v, x, grad_out, false, true, false, false, true);
+    if (rc) return rc;
+    c5::launch_exact_emit_words(v.s, x, v.perm, ctx->n_cells, sums_a, sums_q);
+    return commit_exact(ctx, x, "adjoint exact sums");
+}
+
+// The adjoint: adjoint_one on the upstream image; with "adjoint_exact", the exact sums.
 int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, double* gq_out) {
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc || v.no_cells) return rc;
+    if (ctx->adjoint_exact) return exact_images(ctx, v, 1, grad_out, ga_out, gq_out, "adjoint");
     rc = adjoint_one(ctx, v, false, grad_out, ga_out, gq_out);
     return rc ? rc : commit_derivative(ctx, "adjoint");
 }
@@ -277,12 +374,13 @@ int enqueue_tangent_batch(c5_context* ctx, int n, const double* d_alpha, const d
 // n upstream images ([n][local_rows][res_x] float2) -> ga_out / gq_out [n][n_cells] in the caller's order: one per-view
 // setup and ONE pass 1 (Lambda does not depend on the weights), then per chunk of up to `width` images the batched pass 2
 // into [n_cells][2 width] and its permutation.  On bin_sort_resolve's lists: adjoint_one per image.  A batch of one is the
-// single adjoint.
+// single adjoint.  With "adjoint_exact": the single exact path per image (exact_images).
 int enqueue_adjoint_batch(c5_context* ctx, int n, const float2* grad_out, double* ga_out, double* gq_out) {
     if (n == 1) return enqueue_adjoint(ctx, grad_out, ga_out, gq_out);
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc || v.no_cells) return rc;
+    if (ctx->adjoint_exact) return exact_images(ctx, v, n, grad_out, ga_out, gq_out, "adjoint batch");
     const int64_t n_cells = ctx->n_cells;
     if (v.bin_sort) {
         for (int j = 0; j < n && !rc; ++j)
@@ -597,6 +695,8 @@ int finish_adjoint(c5_context* ctx) {
     const unsigned lost_rays = ctx->adj_status[0], refused = ctx->adj_status[1], overlap_rays = ctx->adj_status[2];
     const unsigned changed_rows = ctx->adj_status[3];  // (a ray matrix fill's; short rows of a call that has to be run again anyway come last)
     ctx->adj_status[3] = 0;
+    const unsigned misfits = ctx->adj_status[4];  // (an exact sum's pass S; the same)
+    ctx->adj_status[4] = 0;
     if (refused) {
         int rc = drain(ctx);
         if (rc) return rc;
@@ -617,13 +717,17 @@ int finish_adjoint(c5_context* ctx) {
         return fail(ctx, C5_ERR_STATE,
                     "%s: the frame changed between c5_ray_matrix_rows and c5_ray_matrix_fill: %u rows differ from row_ptr's or found no "
                     "room below capacity", ctx->adj_what, changed_rows);
+    if (misfits)
+        return fail(ctx, C5_ERR_INVALID,
+                    "%s: %u contributions lie beyond their cell's exponent and were added nowhere: the exponents given are too small "
+                    "(take the elementwise max of c5_render_adjoint_exact_bounds over every part of the image)", ctx->adj_what, misfits);
     return C5_OK;
 }
 }  // namespace c5api
 
 namespace {
 
-// What the twenty-four derivative entry points check before anything else, in this order: the context; a batch's size; the
+// What the twenty-eight derivative entry points check before anything else, in this order: the context; a batch's size; the
 // call's own pointers (`required_ok`, and `per_cell_ok` where the grid has cells); no c5_render_host_async frame
 // outstanding; and for the host-pointer forms the image, after which the device is bound.
 struct DerivativeCall {
@@ -709,6 +813,77 @@ int c5_render_adjoint(c5_context* ctx, const float* grad_out_host, double* grad_
     return run_staged(ctx, "adjoint", b, [&] {
         return enqueue_adjoint(ctx, b[0].as<const float2>(), b[1].as<double>(), b[2].as<double>());
     });
+}
+
+int c5_render_adjoint_exact_bounds_device(c5_context* ctx, const void* grad_out_device, void* exp_alpha_device, void* exp_q_device) {
+    int rc = check_derivative(ctx, {"c5_render_adjoint_exact_bounds", false, 1, nullptr, grad_out_device != nullptr,
+                                    exp_alpha_device && exp_q_device, "null exact bounds pointer"});
+    if (rc) return rc;
+    return enqueue_exact_bounds(ctx, static_cast<const float2*>(grad_out_device), static_cast<int32_t*>(exp_alpha_device),
+                                static_cast<int32_t*>(exp_q_device));
+}
+
+int c5_render_adjoint_exact_bounds(c5_context* ctx, const float* grad_out_host, int32_t* exp_alpha_host, int32_t* exp_q_host) {
+    int rc = check_derivative(ctx, {"c5_render_adjoint_exact_bounds", true, 1, nullptr, grad_out_host != nullptr,
+                                    exp_alpha_host && exp_q_host, "null exact bounds pointer"});
+    if (rc) return rc;
+    const size_t exp_bytes = static_cast<size_t>(ctx->n_cells) * sizeof(int32_t);
+    Staged b[] = {{grad_out_host, nullptr, image_bytes(ctx)}, {nullptr, exp_alpha_host, exp_bytes}, {nullptr, exp_q_host, exp_bytes}};
+    return run_staged(ctx, "adjoint exact bounds", b, [&] {
+        return enqueue_exact_bounds(ctx, b[0].as<const float2>(), b[1].as<int32_t>(), b[2].as<int32_t>());
+    });
+}
+
+int c5_render_adjoint_exact_sums_device(c5_context* ctx, const void* grad_out_device, const void* exp_alpha_device,
+                                        const void* exp_q_device, void* sums_alpha_device, void* sums_q_device) {
+    int rc = check_derivative(ctx, {"c5_render_adjoint_exact_sums", false, 1, nullptr, grad_out_device != nullptr,
+                                    exp_alpha_device && exp_q_device && sums_alpha_device && sums_q_device, "null exact sums pointer"});
+    if (rc) return rc;
+    return enqueue_exact_sums(ctx, static_cast<const float2*>(grad_out_device), static_cast<const int32_t*>(exp_alpha_device),
+                              static_cast<const int32_t*>(exp_q_device), static_cast<int64_t*>(sums_alpha_device),
+                              static_cast<int64_t*>(sums_q_device));
+}
+
+int c5_render_adjoint_exact_sums(c5_context* ctx, const float* grad_out_host, const int32_t* exp_alpha_host, const int32_t* exp_q_host,
+                                 int64_t* sums_alpha_host, int64_t* sums_q_host) {
+    int rc = check_derivative(ctx, {"c5_render_adjoint_exact_sums", true, 1, nullptr, grad_out_host != nullptr,
+                                    exp_alpha_host && exp_q_host && sums_alpha_host && sums_q_host, "null exact sums pointer"});
+    if (rc) return rc;
+    const size_t exp_bytes = static_cast<size_t>(ctx->n_cells) * sizeof(int32_t), word_bytes = static_cast<size_t>(ctx->n_cells) * 2 * sizeof(int64_t);
+    Staged b[] = {{grad_out_host, nullptr, image_bytes(ctx)},
+                  {exp_alpha_host, nullptr, exp_bytes},
+                  {exp_q_host, nullptr, exp_bytes},
+                  {nullptr, sums_alpha_host, word_bytes},
+                  {nullptr, sums_q_host, word_bytes}};
+    return run_staged(ctx, "adjoint exact sums", b, [&] {
+        return enqueue_exact_sums(ctx, b[0].as<const float2>(), b[1].as<const int32_t>(), b[2].as<const int32_t>(), b[3].as<int64_t>(),
+                                  b[4].as<int64_t>());
+    });
+}
+
+// A pure host function: no context, no GPU.
+int c5_exact_sums_finish(const int32_t* exp, const int64_t* sums, int64_t n, int res_x, int res_y, double* out_fp64) {
+    if (n < 0 || (n > 0 && (!exp || !sums || !out_fp64))) return fail(nullptr, C5_ERR_INVALID, "c5_exact_sums_finish: null pointer");
+    if (res_x < 1 || res_y < 1) return fail(nullptr, C5_ERR_INVALID, "c5_exact_sums_finish: an image of %d x %d pixels", res_x, res_y);
+    const int m = c5::exact::word_bits(static_cast<int64_t>(res_x) * res_y);
+    if (m < c5::exact::kMinWordBits)
+        return fail(nullptr, C5_ERR_INVALID, "exact sums: an image of %d x %d pixels leaves %d bits per word", res_x, res_y, m);
+    for (int64_t i = 0; i < n; ++i) out_fp64[i] = c5::exact::finish(exp[i], sums[2 * i], sums[2 * i + 1], m);
+    return C5_OK;
+}
+
+// Testing: the host side of exact_sum.hpp's quantise.
+int c5_exact_quantise(const double* x, int64_t n, int32_t exp, int res_x, int res_y, int64_t* words) {
+    if (n < 0 || (n > 0 && (!x || !words)) || res_x < 1 || res_y < 1) return fail(nullptr, C5_ERR_INVALID, "c5_exact_quantise: bad arguments");
+    const int m = c5::exact::word_bits(static_cast<int64_t>(res_x) * res_y);
+    if (m < c5::exact::kMinWordBits)
+        return fail(nullptr, C5_ERR_INVALID, "exact sums: an image of %d x %d pixels leaves %d bits per word", res_x, res_y, m);
+    int64_t misfits = 0;
+    for (int64_t i = 0; i < n; ++i) misfits += !c5::exact::quantise(x[i], exp, m, words[2 * i], words[2 * i + 1]);
+    if (misfits)
+        return fail(nullptr, C5_ERR_INVALID, "c5_exact_quantise: %lld values lie beyond the exponent %d", static_cast<long long>(misfits),
+                    static_cast<int>(exp));
+    return C5_OK;
 }
 
 int c5_render_tangent_device(c5_context* ctx, const void* d_alpha_dev, const void* d_q_dev, void* out_device) {

@@ -17,6 +17,7 @@
 //                     same cell at the same step are summed first: one pair of atomics per distinct cell and step.
 //   adjoint_resolve   the same for the per-pixel sorted segment lists of bin_sort_resolve ("algorithm" 1).
 //   adjoint_permute   device order -> the caller's (c5_upload_grid, "cell_order").
+//   adjoint_exact_*   adjoint_walk<2> / adjoint_resolve with the exact sums' scatter policies (further down).
 //
 // The tangent (forward mode, c5_render_tangent*): the change (tau_dot, I_dot) of every pixel for a change (dalpha, dQ) of
 // the cells' scalars, the same terms carried forward along the ray instead of scattered back:
@@ -37,16 +38,134 @@
 // reference's sort, its clamp of alpha and one frame around their lists (deriv_lists.hpp).
 //
 // The sums are fp64 atomics, added in arrival order: the gradients are NOT bit-reproducible from run to run (the last bits
-// move).  Every derivative file is compiled with -munsafe-fp-atomics (build.py): global_atomic_add_f64, no compare-and-swap.
+// move) - unless "adjoint_exact" is on: then the same bodies run with another scatter policy, every contribution is rounded
+// once onto a per-cell fixed-point grid and summed in int64 (exact_sum.hpp; adjoint_exact_walk below).
+// Every derivative file is compiled with -munsafe-fp-atomics (build.py): global_atomic_add_f64, no compare-and-swap.
 #include "deriv_lists.hpp"
+#include "exact_sum.hpp"
 
 namespace c5 {
 namespace adj {
 
+// ---- scatter policies: where a step's (ga, gq) per lane go.  adjoint_walk_body and adjoint_resolve_body take one as a
+// template parameter.  first / next / advance: the cell the lane is in, the cell it steps to (called beside the record's
+// load), and the step's end - for a policy that reads something of its own per cell.  keep_heads: pass 2 leaves the
+// entry heads in place (another walk over the same lists follows).
+
+// fp64 atomics in arrival order (scatter_wave): the adjoint as it always was, and the Gauss-Newton diagonal
+struct WaveScatter {
+    double* __restrict__ grad_a;
+    double* __restrict__ grad_q;
+    __device__ __forceinline__ void first(int) {}
+    __device__ __forceinline__ void next(int) {}
+    __device__ __forceinline__ void advance() {}
+    __device__ __forceinline__ bool keep_heads() const { return false; }
+    __device__ __forceinline__ void operator()(bool pending, int cell, double ga, double gq) const {
+        scatter_wave(pending, cell, ga, gq, grad_a, grad_q);
+    }
+};
+
+// Pass E of the exact sums (exact_sum.hpp): per cell the largest exponent of its contributions, by an int32 atomicMax -
+// order-free.  The lanes of a wavefront in one cell are reduced first by a max butterfly, in scatter_wave's ballot loop.
+struct ExponentScatter {
+    int2* __restrict__ exps;
+    __device__ __forceinline__ void first(int) {}
+    __device__ __forceinline__ void next(int) {}
+    __device__ __forceinline__ void advance() {}
+    __device__ __forceinline__ bool keep_heads() const { return true; }
+    __device__ __forceinline__ void operator()(bool pending, int cell, double ga, double gq) const {
+        const int lane = static_cast<int>(threadIdx.x & 63);
+        const int ea = pending ? exact::exponent_of(ga) : exact::kNone, eq = pending ? exact::exponent_of(gq) : exact::kNone;
+        unsigned long long m = __builtin_amdgcn_ballot_w64(pending);
+        while (m != 0ull) {
+            const int leader = __builtin_ctzll(m);
+            const int lc = __builtin_amdgcn_readlane(cell, leader);
+            const bool mine = pending && cell == lc;
+            int xa = mine ? ea : exact::kNone, xq = mine ? eq : exact::kNone;
+            const unsigned long long mine_mask = __builtin_amdgcn_ballot_w64(mine);
+            if (mine_mask != (1ull << leader)) {  // (wave-uniform) more than one lane in this cell
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) {
+                    xa = max(xa, __shfl_xor(xa, d));
+                    xq = max(xq, __shfl_xor(xq, d));
+                }
+            }
+            // the leader's pair to lanes 0 and 1: both atomics in one instruction, to one 8-byte stretch
+            const int ua = __builtin_amdgcn_readlane(xa, leader), uq = __builtin_amdgcn_readlane(xq, leader);
+            if (lane < 2) {
+                const int v = lane == 0 ? ua : uq;
+                if (v != exact::kNone) atomicMax(reinterpret_cast<int*>(exps + lc) + lane, v);
+            }
+            pending = pending && !mine;
+            m &= ~mine_mask;
+        }
+    }
+};
+
+// lane `from`'s 64-bit value, in every lane (from: wave-uniform)
+__device__ __forceinline__ unsigned long long uniform_of(long long v, int from) {
+    const unsigned lo = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(v), from));
+    const unsigned hi = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(v >> 32), from));
+    return (static_cast<unsigned long long>(hi) << 32) | lo;
+}
+
+// Pass S of the exact sums: every lane rounds its own (ga, gq) onto the cell's grid - the only rounding there is - before
+// any cross-lane work; the words of the lanes of a wavefront in one cell are summed as int64 on the scalar unit and added
+// with no-return 64-bit integer atomics - by four lanes in one instruction, as reduce_rows issues its atomics.  Integer
+// adds commute: the words do not depend on the order of arrival or on which rays share a wavefront.  A contribution
+// beyond the cell's exponent is added nowhere and counted in *misfits.
+struct ExactScatter {
+    const int2* __restrict__ exps;
+    long long* __restrict__ words;  // [n_cells][4]: {alpha s1, alpha s0, q s1, q s0}
+    unsigned* __restrict__ misfits;
+    int word_bits;
+    bool keep;
+    int2 e_cur = {exact::kNone, exact::kNone}, e_nxt = {exact::kNone, exact::kNone};
+    __device__ __forceinline__ void first(int cell) { e_cur = exps[cell]; }
+    __device__ __forceinline__ void next(int cell) { e_nxt = exps[cell]; }
+    __device__ __forceinline__ void advance() { e_cur = e_nxt; }
+    __device__ __forceinline__ bool keep_heads() const { return keep; }
+    __device__ __forceinline__ void operator()(bool pending, int cell, double ga, double gq) const {
+        const int lane = static_cast<int>(threadIdx.x & 63);
+        int64_t a1 = 0, a0 = 0, q1 = 0, q0 = 0;
+        bool misfit = false;
+        if (pending) {  // (a cell marked not finite stays NaN whatever is added: its words are not looked at)
+            if (e_cur.x != exact::kNotFinite) misfit = !exact::quantise(ga, e_cur.x, word_bits, a1, a0);
+            if (e_cur.y != exact::kNotFinite) misfit = !exact::quantise(gq, e_cur.y, word_bits, q1, q0) || misfit;
+        }
+        const unsigned long long bad = __builtin_amdgcn_ballot_w64(misfit);
+        if (bad != 0ull && lane == 0) atomicAdd(misfits, static_cast<unsigned>(__popcll(bad)));
+        unsigned long long m = __builtin_amdgcn_ballot_w64(pending);
+        while (m != 0ull) {
+            const int leader = __builtin_ctzll(m);
+            const int lc = __builtin_amdgcn_readlane(cell, leader);
+            const bool mine = pending && cell == lc;
+            const unsigned long long mine_mask = __builtin_amdgcn_ballot_w64(mine);
+            // the members' words summed on the scalar unit, one member at a time: every lane's words are read once per step
+            // (an int64 butterfly over four values is 48 cross-lane moves per shared cell, whoever shares it)
+            unsigned long long u0 = 0ull, u1 = 0ull, u2 = 0ull, u3 = 0ull;
+            for (unsigned long long rows = mine_mask; rows != 0ull; rows &= rows - 1ull) {
+                const int member = __builtin_ctzll(rows);
+                u0 += uniform_of(a1, member);
+                u1 += uniform_of(a0, member);
+                u2 += uniform_of(q1, member);
+                u3 += uniform_of(q0, member);
+            }
+            // lanes 0 .. 3 add them: four atomics in one instruction, to one 32-byte stretch
+            if (lane < 4) {
+                const unsigned long long v = lane == 0 ? u0 : lane == 1 ? u1 : lane == 2 ? u2 : u3;
+                if (v) atomicAdd(reinterpret_cast<unsigned long long*>(words) + 4 * static_cast<size_t>(lc) + lane, v);
+            }
+            pending = pending && !mine;
+            m &= ~mine_mask;
+        }
+    }
+};
+
 // Pass 1 (Lambda per pixel) and pass 2 (the scatter) of the adjoint; SQUARED: pass 2 with the segment's terms squared
-// and A.grad_out the weights or nullptr for ones (gn_diag_walk).
-template <int PASS, bool SQUARED>
-__device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A) {
+// and A.grad_out the weights or nullptr for ones (gn_diag_walk).  Scatter: where pass 2's terms go (above).
+template <int PASS, bool SQUARED, class Scatter>
+__device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A, Scatter sc) {
     const WalkParams& P = A.w;
     Ray r;
     double lam = 0.0;                                         // Lambda_k so far
@@ -62,7 +181,10 @@ __device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A) {
     });
 
     CellRegs cur;
-    if (r.cell >= 0) load_cell(cur, P.xrec, r.cell);
+    if (r.cell >= 0) {
+        load_cell(cur, P.xrec, r.cell);
+        if (PASS == 2) sc.first(r.cell);
+    }
 
     // wave-uniform loop (the scatter wants every lane): a lane whose ray has ended takes part with nothing to add
     for (;;) {
@@ -75,7 +197,10 @@ __device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A) {
             double dz, carry_next;
             const int nb = ray_step(r, P, ent, cur, dz, carry_next);
             CellRegs nxt;
-            if (nb >= 0) load_cell(nxt, P.xrec, nb);
+            if (nb >= 0) {
+                load_cell(nxt, P.xrec, nb);
+                if (PASS == 2) sc.next(nb);
+            }
 
             if (is_segment(dz)) {
                 const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
@@ -99,13 +224,16 @@ __device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A) {
             ray_advance(r, nb, carry_next);
             cur = nxt;
         }
-        if (PASS == 2) scatter_wave(emit, here, ga, gq, A.grad_a, A.grad_q);
+        if (PASS == 2) {
+            sc(emit, here, ga, gq);
+            if (live) sc.advance();
+        }
     }
 
     if (PASS == 1) {
         if (r.in_image) A.lambda[r.lp] = lam;
         ray_count(r, P);
-    } else {
+    } else if (!sc.keep_heads()) {
         ray_clear_head(r, P);
     }
 }
@@ -113,9 +241,8 @@ __device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A) {
 
 // resolve_pixels (exact_kernels.hip) differentiated: its list sorted, the recurrence run from the back (i = n - 1 ... 0:
 // k = n - i).  SQUARED: the segment's terms squared, `weights` nullptr for ones (gn_diag_resolve).
-template <bool SQUARED>
-__device__ __forceinline__ void adjoint_resolve_body(const ResolveParams& R, const float2* __restrict__ weights,
-                                                     double* __restrict__ grad_a, double* __restrict__ grad_q) {
+template <bool SQUARED, class Scatter>
+__device__ __forceinline__ void adjoint_resolve_body(const ResolveParams& R, const float2* __restrict__ weights, Scatter sc) {
     const GridView& g = R.g;
     double g_tau = 0.0, g_I = 0.0;
     const ListFrame f = list_frame<false>(R, [&](int64_t lp) {
@@ -134,6 +261,7 @@ __device__ __forceinline__ void adjoint_resolve_body(const ResolveParams& R, con
         double ga = 0.0, gq = 0.0;
         if (live) {
             c = static_cast<int>(f.list[i].cell);
+            sc.first(c);
             const double dz = f.list[i].dz, q = g.q[c];
             const ClampedAlpha ca = clamp_alpha(g.alpha[c], R.alpha_limit);
             const double a = ca.a;
@@ -148,7 +276,7 @@ __device__ __forceinline__ void adjoint_resolve_body(const ResolveParams& R, con
                 I = t.I_next;
             }
         }
-        scatter_wave(live, c, ga, gq, grad_a, grad_q);
+        sc(live, c, ga, gq);
     }
 }
 
@@ -158,12 +286,12 @@ size_t adjoint_segment_bytes() { return sizeof(AdjSegment); }
 
 template <int PASS>
 __global__ __launch_bounds__(64) void adjoint_walk(AdjointParams A) {
-    adj::adjoint_walk_body<PASS, false>(A);
+    adj::adjoint_walk_body<PASS, false>(A, adj::WaveScatter{A.grad_a, A.grad_q});
 }
 
 __global__ __launch_bounds__(256) void adjoint_resolve(ResolveParams R, const float2* __restrict__ grad_out,
                                                        double* __restrict__ grad_a, double* __restrict__ grad_q) {
-    adj::adjoint_resolve_body<false>(R, grad_out, grad_a, grad_q);
+    adj::adjoint_resolve_body<false>(R, grad_out, adj::WaveScatter{grad_a, grad_q});
 }
 
 __global__ __launch_bounds__(256) void adjoint_permute(const double* __restrict__ ga_dev, const double* __restrict__ gq_dev,
@@ -174,6 +302,78 @@ __global__ __launch_bounds__(256) void adjoint_permute(const double* __restrict_
     const int64_t d = perm ? static_cast<int64_t>(perm[i]) : i;
     ga_out[d] = ga_dev[i];
     gq_out[d] = gq_dev[i];
+}
+
+// ---- exact adjoint sums ("adjoint_exact", c5_render_adjoint_exact_*; exact_sum.hpp has the format)
+//   exact_clear               the exponents to "no contribution" and / or the words to zero
+//   adjoint_exact_walk<0>     pass E: pass 2's walk, the exponent of every (ga, gq) into the cell's int32 pair (atomicMax)
+//   adjoint_exact_walk<1>     pass S: pass 2's walk again, every (ga, gq) rounded onto the cell's grid and added as int64
+//   adjoint_exact_resolve<.>  the same two over bin_sort_resolve's lists ("algorithm" 1)
+//   exact_gather_exps         the caller's exponents -> device order;  exact_emit_exps / exact_emit_words: back
+//   exact_finish              the words to fp64, rounded once, in the caller's order
+// Both walks follow adjoint_walk<1> (Lambda, and the entry heads left in place); pass E leaves the heads in place too.
+__global__ __launch_bounds__(256) void exact_clear(ExactSums X, int64_t n, int exps, int words, int misfits) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i == 0 && misfits) *X.misfits = 0u;
+    if (i >= n) return;
+    if (exps) X.exps[i] = make_int2(exact::kNone, exact::kNone);
+    if (words) {
+        longlong2* const w = reinterpret_cast<longlong2*>(X.words + 4 * i);
+        w[0] = make_longlong2(0, 0);
+        w[1] = make_longlong2(0, 0);
+    }
+}
+
+template <int SUMS>
+__global__ __launch_bounds__(64) void adjoint_exact_walk(AdjointParams A, ExactSums X) {
+    if (SUMS) adj::adjoint_walk_body<2, false>(A, adj::ExactScatter{X.exps, X.words, X.misfits, X.word_bits, X.keep_entries != 0});
+    else adj::adjoint_walk_body<2, false>(A, adj::ExponentScatter{X.exps});
+}
+
+template <int SUMS>
+__global__ __launch_bounds__(256) void adjoint_exact_resolve(ResolveParams R, const float2* __restrict__ grad_out, ExactSums X) {
+    if (SUMS) adj::adjoint_resolve_body<false>(R, grad_out, adj::ExactScatter{X.exps, X.words, X.misfits, X.word_bits, true});
+    else adj::adjoint_resolve_body<false>(R, grad_out, adj::ExponentScatter{X.exps});
+}
+
+__global__ __launch_bounds__(256) void exact_gather_exps(const int32_t* __restrict__ exp_a, const int32_t* __restrict__ exp_q,
+                                                         const int32_t* __restrict__ perm, int64_t n, int2* __restrict__ exps) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n) return;
+    const int64_t d = perm ? static_cast<int64_t>(perm[i]) : i;
+    exps[i] = make_int2(exp_a[d], exp_q[d]);
+}
+
+__global__ __launch_bounds__(256) void exact_emit_exps(const int2* __restrict__ exps, const int32_t* __restrict__ perm, int64_t n,
+                                                       int32_t* __restrict__ exp_a, int32_t* __restrict__ exp_q) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n) return;
+    const int64_t d = perm ? static_cast<int64_t>(perm[i]) : i;
+    const int2 e = exps[i];
+    exp_a[d] = e.x;
+    exp_q[d] = e.y;
+}
+
+__global__ __launch_bounds__(256) void exact_emit_words(const long long* __restrict__ words, const int32_t* __restrict__ perm, int64_t n,
+                                                        long long* __restrict__ sums_a, long long* __restrict__ sums_q) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n) return;
+    const int64_t d = perm ? static_cast<int64_t>(perm[i]) : i;
+    const longlong2* const w = reinterpret_cast<const longlong2*>(words + 4 * i);
+    reinterpret_cast<longlong2*>(sums_a)[d] = w[0];
+    reinterpret_cast<longlong2*>(sums_q)[d] = w[1];
+}
+
+__global__ __launch_bounds__(256) void exact_finish(ExactSums X, const int32_t* __restrict__ perm, int64_t n, double* __restrict__ ga_out,
+                                                    double* __restrict__ gq_out) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n) return;
+    const int64_t d = perm ? static_cast<int64_t>(perm[i]) : i;
+    const int2 e = X.exps[i];
+    const longlong2* const w = reinterpret_cast<const longlong2*>(X.words + 4 * i);
+    const longlong2 wa = w[0], wq = w[1];
+    ga_out[d] = exact::finish(e.x, wa.x, wa.y, X.word_bits);
+    gq_out[d] = exact::finish(e.y, wq.x, wq.y, X.word_bits);
 }
 
 // Nothing is shared between the lanes, so a lane leaves the loop when its ray ends.  The cell's direction is loaded
@@ -474,7 +674,7 @@ __global__ __launch_bounds__(64) void gn_walk_a(GnWalkParams A) {
 
 // adjoint_walk<2> with squares (after adjoint_walk<1>: A.lambda).  A.grad_out holds the weights, or nullptr for ones.
 __global__ __launch_bounds__(64) void gn_diag_walk(AdjointParams A) {
-    adj::adjoint_walk_body<2, true>(A);
+    adj::adjoint_walk_body<2, true>(A, adj::WaveScatter{A.grad_a, A.grad_q});
 }
 
 // g = w * t per channel, one fp32 multiply (gn_walk_a's store, for tangent_resolve's images); w nullptr: ones
@@ -490,7 +690,7 @@ __global__ __launch_bounds__(256) void gn_weight(const float2* __restrict__ t, c
 // adjoint_resolve with squares (weights nullptr: ones)
 __global__ __launch_bounds__(256) void gn_diag_resolve(ResolveParams R, const float2* __restrict__ weight,
                                                        double* __restrict__ diag_a, double* __restrict__ diag_q) {
-    adj::adjoint_resolve_body<true>(R, weight, diag_a, diag_q);
+    adj::adjoint_resolve_body<true>(R, weight, adj::WaveScatter{diag_a, diag_q});
 }
 
 // ---- Hessian-vector render (c5_render_hvp*) ---------------------------------------------------------------------------
@@ -707,6 +907,42 @@ void launch_adjoint_permute(hipStream_t s, const double* ga_dev, const double* g
                             double* ga_out, double* gq_out) {
     if (n <= 0) return;
     hipLaunchKernelGGL(adjoint_permute, dim3(item_blocks(n)), dim3(256), 0, s, ga_dev, gq_dev, perm, n, ga_out, gq_out);
+}
+
+void launch_exact_clear(hipStream_t s, const ExactSums& x, int64_t n, bool exps, bool words, bool misfits) {
+    hipLaunchKernelGGL(exact_clear, dim3(std::max(1u, item_blocks(n))), dim3(256), 0, s, x, n, exps ? 1 : 0, words ? 1 : 0, misfits ? 1 : 0);
+}
+
+void launch_adjoint_exact_walk(hipStream_t s, const AdjointParams& a, const ExactSums& x, bool sums) {
+    const unsigned blocks = tile_blocks(a.w.im);
+    if (!blocks) return;
+    if (sums) hipLaunchKernelGGL(adjoint_exact_walk<1>, dim3(blocks), dim3(64), 0, s, a, x);
+    else hipLaunchKernelGGL(adjoint_exact_walk<0>, dim3(blocks), dim3(64), 0, s, a, x);
+}
+
+void launch_adjoint_exact_resolve(hipStream_t s, const ResolveParams& r, const float2* grad_out, const ExactSums& x, bool sums) {
+    const unsigned blocks = pixel_blocks(r.im);
+    if (!blocks) return;
+    if (sums) hipLaunchKernelGGL(adjoint_exact_resolve<1>, dim3(blocks), dim3(256), 0, s, r, grad_out, x);
+    else hipLaunchKernelGGL(adjoint_exact_resolve<0>, dim3(blocks), dim3(256), 0, s, r, grad_out, x);
+}
+
+void launch_exact_gather_exps(hipStream_t s, const int32_t* exp_a, const int32_t* exp_q, const int32_t* perm, int64_t n, const ExactSums& x) {
+    if (n > 0) hipLaunchKernelGGL(exact_gather_exps, dim3(item_blocks(n)), dim3(256), 0, s, exp_a, exp_q, perm, n, x.exps);
+}
+
+void launch_exact_emit_exps(hipStream_t s, const ExactSums& x, const int32_t* perm, int64_t n, int32_t* exp_a, int32_t* exp_q) {
+    if (n > 0) hipLaunchKernelGGL(exact_emit_exps, dim3(item_blocks(n)), dim3(256), 0, s, x.exps, perm, n, exp_a, exp_q);
+}
+
+void launch_exact_emit_words(hipStream_t s, const ExactSums& x, const int32_t* perm, int64_t n, int64_t* sums_a, int64_t* sums_q) {
+    if (n > 0)
+        hipLaunchKernelGGL(exact_emit_words, dim3(item_blocks(n)), dim3(256), 0, s, x.words, perm, n, reinterpret_cast<long long*>(sums_a),
+                           reinterpret_cast<long long*>(sums_q));
+}
+
+void launch_exact_finish(hipStream_t s, const ExactSums& x, const int32_t* perm, int64_t n, double* ga_out, double* gq_out) {
+    if (n > 0) hipLaunchKernelGGL(exact_finish, dim3(item_blocks(n)), dim3(256), 0, s, x, perm, n, ga_out, gq_out);
 }
 
 void launch_tangent_gather(hipStream_t s, const double* d_alpha, const double* d_q, const int32_t* perm, int64_t n,

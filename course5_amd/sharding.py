@@ -98,3 +98,31 @@ def assemble_blocks(strips, blocks, res_y: int) -> np.ndarray:
     for s, (b, n) in zip(strips, blocks):
         out[b:b + n] = np.asarray(s)[:n]
     return out
+
+
+def combine_exact(parts):
+    """The exact adjoint sums of several parts of one image (row ranges, row tiles, ranks) combined: `parts` is a list of
+    (exp_alpha, exp_q, sums_alpha, sums_q) - int32 [n_cells] exponents as capi.Context.render_adjoint_exact_bounds returns
+    them, int64 [n_cells, 2] words as render_adjoint_exact_sums does; the exponents combine by elementwise max, the words
+    by elementwise integer add (the words must have been computed against the COMBINED exponents).  An entry of a tuple
+    may be None (a part that has only its exponents yet): the result's is None if every part's is.
+    capi.exact_sums_finish turns the result into fp64."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("no parts to combine")
+    out = []
+    for k, (dtype, fold) in enumerate(((np.int32, np.maximum), (np.int32, np.maximum), (np.int64, np.add), (np.int64, np.add))):
+        acc = None
+        for p in parts:
+            if len(p) != 4:
+                raise ValueError("a part is (exp_alpha, exp_q, sums_alpha, sums_q)")
+            if p[k] is None:
+                continue
+            a = np.asarray(p[k])
+            if a.dtype != dtype:
+                raise ValueError(f"entry {k} of a part must be {np.dtype(dtype).name}, not {a.dtype}")
+            if acc is not None and a.shape != acc.shape:
+                raise ValueError(f"entry {k} of the parts differs in shape: {list(a.shape)} and {list(acc.shape)}")
+            acc = a.copy() if acc is None else fold(acc, a)
+        out.append(acc)
+    return tuple(out)

@@ -240,6 +240,10 @@ int c5_set_alpha_limit(c5_context* ctx, double alpha_limit);
  *   "vertex_merge" tuning: 1 (default): c5_render_vertex_adjoint* sums the lanes of a wavefront that share a cell (in LDS)
  *                  before its atomics; 0: every lane adds its own six values (measured 10 x slower on the C3 frame).  Same
  *                  results, to the atomics' rounding.
+ *   "adjoint_exact" 1: c5_render_adjoint, c5_render_adjoint_device and their batch forms return the exact adjoint sums
+ *                  (the section below c5_render_adjoint_batch): bit-reproducible from run to run and additive over rows.
+ *                  Default 0: fp64 atomics, every kernel, code path and bit as before.  The Gauss-Newton, Hessian-vector
+ *                  and vertex adjoint calls ignore it.  40 more bytes per cell, allocated at the first exact call.
  *   "overlap_setup" 1: entry lists and solid mask are built on a side stream while build_records
  *                  runs (only when "stage_timing" is 0).  Default 0: measured no faster.
  *   "pipeline"     1: two frame slots; the per-view setup of frame k + 1 runs on a second stream while
@@ -286,7 +290,8 @@ int c5_synchronize(c5_context* ctx);
  * solid-marked pixels contribute nothing, whatever "integration", "depth_split", "lds_stage" or "tile" say.
  * grad_alpha / grad_q: n_cells fp64 each, in the caller's cell order (c5_upload_grid's), overwritten.
  * The sums are fp64 atomics added in arrival order: the results are NOT bit-reproducible from run to run (relative
- * differences of ~1e-15).
+ * differences of ~1e-15).  Option "adjoint_exact" 1 makes these two calls and the batch forms return the exact adjoint
+ * sums instead (below: "exact adjoint sums"): the same bits every run, for any split of the rows.
  * Side effects: none on the options, the statistics or the images — a c5_render after an adjoint returns bit for bit
  * what it would have returned without it (the per-view data it reused are rebuilt: "view_cache").  The first call
  * allocates what the adjoint needs (8 bytes per local pixel, 16 per cell, the status words); a context that never
@@ -341,6 +346,57 @@ int c5_render_tangent_batch(c5_context* ctx, int n_dirs, const double* d_alpha_h
 int c5_render_tangent_batch_device(c5_context* ctx, int n_dirs, const void* d_alpha_dev, const void* d_q_dev, void* out_dev);
 int c5_render_adjoint_batch(c5_context* ctx, int n_imgs, const float* grad_out_host, double* grad_alpha_host, double* grad_q_host);
 int c5_render_adjoint_batch_device(c5_context* ctx, int n_imgs, const void* grad_out_dev, void* grad_alpha_dev, void* grad_q_dev);
+
+/* --- exact adjoint sums --------------------------------------------------------------------------
+ * The adjoint's per-cell sums in integers.  Float adds do not commute, integer adds do: every contribution (one per
+ * segment of a cell on a ray: the terms of c5_render_adjoint, computed as there) is rounded ONCE onto a fixed-point grid
+ * of its cell, and everything after that - the sum inside a wavefront, the atomic in memory, the combination of ranks -
+ * is a 64-bit integer add.  The grid of a cell follows from the largest exponent among its contributions, itself an
+ * order-free reduction (an integer max).  The format, for an image of res_x x res_y pixels - the WHOLE image of
+ * c5_set_image, not a rank's rows - and per cell for each of the two sums (grad_alpha, grad_q):
+ *     h = ceil(log2(res_x res_y)) + 1     headroom: a ray crosses a cell at most once, so a cell has at most res_x res_y contributions
+ *     m = 62 - h                          bits per word (images beyond 2^39 pixels are refused)
+ *     e (int32)   the largest ilogb(|x|) over the cell's non-zero finite contributions x; INT32_MIN: no contribution;
+ *                 INT32_MAX: some contribution was not finite, and the result is NaN
+ *     for |x| < 2^(e+1):  y = x 2^(m-e-1),  k1 = rint(y),  k0 = rint((y - k1) 2^m)   (ties to even; nothing else rounds)
+ *     words  s1 = sum k1,  s0 = sum k0   (int64; |s1| <= 2^61, |s0| <= 2^60: they cannot overflow)
+ *     value  (s1 2^m + s0) 2^(e+1-2m), rounded once to fp64 with ties to even, subnormals included; INT32_MIN gives +0.0
+ * Each contribution is off by at most 2^(e-2m); for 2400 x 1800 pixels (h = 24, m = 38) the whole sum of a cell is within
+ * 2^(e-53) of the exact sum of its fp64 contributions, before the one final rounding.
+ *
+ * With option "adjoint_exact" 1, c5_render_adjoint, c5_render_adjoint_device, c5_render_adjoint_batch and
+ * c5_render_adjoint_batch_device return these sums, finished to fp64, through four passes inside the one call: the
+ * adjoint's pass 1, pass E (the exponents), pass S (the words) and the finish.  The batch forms then run that single
+ * path image after image (the host loop that "algorithm" 1 uses for its batches; pass 1 runs once).  Results are
+ * bit-reproducible from run to run, whatever "cell_order", the walk's options or the rows' split.  On "algorithm" 1 that
+ * is promised only as far as the tangent's is: a pixel whose list holds segments of equal depth takes them in an order that
+ * may change from call to call.  c5_render_gn_*, c5_render_hvp* and c5_render_vertex_adjoint* ignore the option.
+ * Memory: 40 more bytes per cell, allocated at the first exact call.
+ *
+ * For callers who split an image (row ranges, row tiles, several GPUs), the two intermediate results:
+ * c5_render_adjoint_exact_bounds: pass 1 and pass E over the context's rows; exp_alpha / exp_q: int32 [n_cells] in the
+ * caller's cell order, overwritten.
+ * c5_render_adjoint_exact_sums: pass 1 and pass S against the GIVEN exponents (int32 [n_cells] each); sums_alpha / sums_q:
+ * int64 [n_cells][2] = (s1, s0) in the caller's order, overwritten.  A contribution with |x| >= 2^(e+1) - the exponent
+ * given is too small - is never wrapped: it is added nowhere and counted, and the call (its _device form: the next call
+ * that waits for the stream) reports C5_ERR_INVALID with a c5_last_error text.  Cells marked INT32_MAX take nothing.
+ * c5_exact_sums_finish: a pure host function (no context, no GPU): out_fp64[i] = the value of (exp[i], sums[i][0],
+ * sums[i][1]) for i < n with the m of a res_x x res_y image.
+ * The contract: take the exponents of any set of row ranges (or row tiles) combined by elementwise max, and the words -
+ * every part's computed against those combined exponents - combined by elementwise integer add; finished, they are bit
+ * for bit what one call over the union of the rows gives.  The "adjoint_exact" single call is exactly that composition.
+ * Status, retries, side effects: as c5_render_adjoint's; the _device forms are asynchronous on the context's stream with
+ * device arrays, and all four refuse while c5_render_host_async frames are outstanding. */
+int c5_render_adjoint_exact_bounds(c5_context* ctx, const float* grad_out_host, int32_t* exp_alpha_host, int32_t* exp_q_host);
+int c5_render_adjoint_exact_bounds_device(c5_context* ctx, const void* grad_out_device, void* exp_alpha_device, void* exp_q_device);
+int c5_render_adjoint_exact_sums(c5_context* ctx, const float* grad_out_host, const int32_t* exp_alpha_host, const int32_t* exp_q_host,
+                                 int64_t* sums_alpha_host, int64_t* sums_q_host);
+int c5_render_adjoint_exact_sums_device(c5_context* ctx, const void* grad_out_device, const void* exp_alpha_device,
+                                        const void* exp_q_device, void* sums_alpha_device, void* sums_q_device);
+int c5_exact_sums_finish(const int32_t* exp, const int64_t* sums, int64_t n, int res_x, int res_y, double* out_fp64);
+/* Testing: (k1, k0) of every x[i], i < n, against the exponent `exp` with the m of a res_x x res_y image, into
+ * words[n][2]; C5_ERR_INVALID if some x does not fit (|x| >= 2^(exp+1) or not finite).  No context, no GPU. */
+int c5_exact_quantise(const double* x, int64_t n, int32_t exp, int res_x, int res_y, int64_t* words);
 
 /* --- Gauss-Newton renders ---------------------------------------------------------------------------
  * With J the Jacobian of the frame c5_render would produce now with respect to the cells' (alpha, Q) - the map of
