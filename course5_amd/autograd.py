@@ -617,7 +617,9 @@ def _gn_weight(ctx: capi.Context, weight, device: torch.device):
 def gn_product(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, v_alpha, v_q, weight=None) -> tuple:
     """(h_alpha, h_q) = J^T W J (v_alpha, v_q) for the frame of `ctx` with the scalars alpha and q: v_alpha / v_q [n_cells]
     or [K, n_cells] (either may be None: zero), weight [local_rows, res_x, 2] (None: ones).  float64 on the context's GPU,
-    shaped like the directions.  One library call (c5_render_gn_product_device) on torch's current stream."""
+    shaped like the directions.  One library call (c5_render_gn_product_device) on torch's current stream.  With
+    ctx.set_option("exact_sums", 1) the sums are exact: the same bits every call, those of the exact adjoint of
+    weight * fp32(J v)."""
     device = _gn_enter(ctx, alpha, q, "gn_product")
     given = [v for v in (v_alpha, v_q) if v is not None]
     if not given or any(v.shape != given[0].shape for v in given) or given[0].ndim not in (1, 2) or given[0].shape[-1] != ctx.n_cells:
@@ -635,7 +637,7 @@ def gn_product(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, v_alpha,
 
 def gn_diagonal(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, weight=None) -> tuple:
     """(d_alpha, d_q) = diag(J^T W J), float64 [n_cells] each on the context's GPU (c5_render_gn_diagonal_device on
-    torch's current stream)."""
+    torch's current stream).  With ctx.set_option("exact_sums", 1) the sums are exact: the same bits every call."""
     device = _gn_enter(ctx, alpha, q, "gn_diagonal")
     with _on_gpu(ctx):
         w = _gn_weight(ctx, weight, device)
@@ -649,7 +651,8 @@ def hvp(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, v_alpha, v_q, g
     alpha and q: the exact second derivative of the frame in the cells' scalars, weighted by the upstream image grad_img
     [local_rows, res_x, 2] and applied to the direction v_alpha / v_q [n_cells] (either may be None: zero).  Channel 0 of
     grad_img has no effect (tau is linear in alpha).  float64 [n_cells] each on the context's GPU, no graph.  One library
-    call (c5_render_hvp_device) on torch's current stream."""
+    call (c5_render_hvp_device) on torch's current stream.  With ctx.set_option("exact_sums", 1) the sums are exact: the
+    same bits every call."""
     device = _gn_enter(ctx, alpha, q, "hvp")
     given = [v for v in (v_alpha, v_q) if v is not None]
     if not given or any(tuple(v.shape) != (ctx.n_cells,) for v in given):

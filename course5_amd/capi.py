@@ -18,6 +18,9 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("C5_LIB", os.path.join(PKG, "libcourse5_hip.so"))  # C5_LIB: A/B another build
 
 C5_OK, C5_ERR_INVALID, C5_ERR_STATE, C5_ERR_HIP, C5_ERR_MESH, C5_ERR_NO_DEVICE, C5_ERR_WALK, C5_RETRY = range(8)
+# the kinds of exact sums of c5_render_exact_bounds / c5_render_exact_sums
+C5_EXACT_ADJOINT, C5_EXACT_GN_DIAGONAL, C5_EXACT_HVP = range(3)
+
 
 class Rotation(C.Structure):
     _fields_ = [("axis", C.c_int32), ("reserved", C.c_int32), ("angle", C.c_double), ("x0", C.c_double)]
@@ -109,6 +112,10 @@ SIGNATURES = {
     "c5_render_adjoint_exact_bounds_device": [_vp, _vp, _vp, _vp],
     "c5_render_adjoint_exact_sums": [_vp, _fp_t, _ip_t, _ip_t, _lp_t, _lp_t],
     "c5_render_adjoint_exact_sums_device": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "c5_render_exact_bounds": [_vp, C.c_int, _dp_t, _dp_t, _fp_t, _ip_t, _ip_t],
+    "c5_render_exact_bounds_device": [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp],
+    "c5_render_exact_sums": [_vp, C.c_int, _dp_t, _dp_t, _fp_t, _ip_t, _ip_t, _lp_t, _lp_t],
+    "c5_render_exact_sums_device": [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "c5_exact_sums_finish": [_ip_t, _lp_t, C.c_int64, C.c_int, C.c_int, _dp_t],
     "c5_exact_quantise": [_dp_t, C.c_int64, C.c_int32, C.c_int, C.c_int, _lp_t],
 }
@@ -425,6 +432,59 @@ class Context:
             self.handle, self._image_dev(grad_out), _device_ptr(exp_alpha, torch.int32, n), _device_ptr(exp_q, torch.int32, n),
             _device_ptr(sums_alpha, torch.int64, n2), _device_ptr(sums_q, torch.int64, n2)))
 
+    # -- exact sums of every operator of a fit (set_option("exact_sums", 1) makes render_adjoint*, render_gn_diagonal*,
+    # render_gn_product* and render_hvp* return them finished; these are the two intermediate results of one kind of sum -
+    # C5_EXACT_ADJOINT, C5_EXACT_GN_DIAGONAL or C5_EXACT_HVP - for callers who split an image: fit.RowShards)
+    def _exact_inputs(self, what, image, d_alpha, d_q) -> tuple:
+        g = None if image is None else self._image(image, "image")
+        return g, self._direction(d_alpha), self._direction(d_q)
+
+    def render_exact_bounds(self, what: int, image=None, d_alpha=None, d_q=None) -> tuple:
+        """The exponents of one kind of exact sum over the context's rows: (exp_alpha, exp_q), int32 [n_cells] each in the
+        order of upload_grid (INT32_MIN: no contribution, INT32_MAX: one that is not finite).  image [local_rows, res_x, 2]:
+        the upstream image (C5_EXACT_ADJOINT, C5_EXACT_HVP: required) or the weights (C5_EXACT_GN_DIAGONAL; None: ones);
+        d_alpha / d_q [n_cells]: the direction, for C5_EXACT_HVP alone (either may be None, not both).  Parts of an image
+        combine by elementwise max.  Synchronous; retries by itself."""
+        g, da, dq = self._exact_inputs(what, image, d_alpha, d_q)
+        ea, eq = np.zeros(self.n_cells, np.int32), np.zeros(self.n_cells, np.int32)
+        self._check(self.lib.c5_render_exact_bounds(self.handle, what, _dp(da), _dp(dq), _fp(g), ea.ctypes.data_as(_ip_t),
+                                                    eq.ctypes.data_as(_ip_t)))
+        return ea, eq
+
+    def render_exact_sums(self, what: int, exp_alpha, exp_q, image=None, d_alpha=None, d_q=None) -> tuple:
+        """The words of one kind of exact sum over the context's rows against the given exponents (int32 [n_cells] each:
+        those of render_exact_bounds, combined over every part of the image): (sums_alpha, sums_q), int64 [n_cells, 2]
+        each.  Parts of an image combine by elementwise integer add (sharding.combine_exact), and exact_sums_finish then
+        gives the bits of the single call under set_option("exact_sums", 1) over the whole image.  C5_ERR_INVALID if a
+        contribution lies beyond its cell's exponent.  Synchronous; retries by itself."""
+        g, da, dq = self._exact_inputs(what, image, d_alpha, d_q)
+        ea, eq = self._exponents(exp_alpha, "exp_alpha"), self._exponents(exp_q, "exp_q")
+        sa, sq = np.zeros((self.n_cells, 2), np.int64), np.zeros((self.n_cells, 2), np.int64)
+        self._check(self.lib.c5_render_exact_sums(self.handle, what, _dp(da), _dp(dq), _fp(g), ea.ctypes.data_as(_ip_t),
+                                                  eq.ctypes.data_as(_ip_t), sa.ctypes.data_as(_lp_t), sq.ctypes.data_as(_lp_t)))
+        return sa, sq
+
+    def render_exact_bounds_device(self, what: int, exp_alpha, exp_q, image=None, d_alpha=None, d_q=None):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (image float32 [local_rows, res_x,
+        2], d_alpha / d_q float64 [n_cells], exp_alpha / exp_q int32 [n_cells], contiguous; None where render_exact_bounds
+        allows it) or raw device pointers.  The status comes with the next synchronize()."""
+        import torch
+        n = (self.n_cells,)
+        self._check(self.lib.c5_render_exact_bounds_device(self.handle, what, self._cells_dev(d_alpha), self._cells_dev(d_q),
+                                                           self._image_dev(image), _device_ptr(exp_alpha, torch.int32, n),
+                                                           _device_ptr(exp_q, torch.int32, n)))
+
+    def render_exact_sums_device(self, what: int, exp_alpha, exp_q, sums_alpha, sums_q, image=None, d_alpha=None, d_q=None):
+        """Asynchronous form on the context's stream: as render_exact_bounds_device, and sums_alpha / sums_q int64
+        [n_cells, 2].  The status (C5_ERR_INVALID for exponents that are too small included) comes with the next
+        synchronize()."""
+        import torch
+        n, n2 = (self.n_cells,), (self.n_cells, 2)
+        self._check(self.lib.c5_render_exact_sums_device(
+            self.handle, what, self._cells_dev(d_alpha), self._cells_dev(d_q), self._image_dev(image),
+            _device_ptr(exp_alpha, torch.int32, n), _device_ptr(exp_q, torch.int32, n), _device_ptr(sums_alpha, torch.int64, n2),
+            _device_ptr(sums_q, torch.int64, n2)))
+
     # -- vertex adjoint render ---------------------------------------------------------------------
     def render_vertex_adjoint(self, grad_out) -> np.ndarray:
         """The gradient of the frame render() would produce now with respect to the grid's points, weighted by grad_out
@@ -693,7 +753,8 @@ class Context:
         derivative in the cells' scalars applied to one direction (d_alpha / d_q: [n_cells], either may be None: zero),
         grad_out [local_rows, res_x, 2] the upstream image (channel 0 has no effect: tau is linear in alpha).  float64
         [n_cells] each in the order of upload_grid; fit names the blocks wanted (the other comes back as None).
-        Synchronous; retries by itself.  Not bit-reproducible (fp64 atomics), as render_adjoint."""
+        Synchronous; retries by itself.  Not bit-reproducible (fp64 atomics), as render_adjoint - unless
+        set_option("exact_sums", 1): then exact sums, as render_gn_product's and render_gn_diagonal's."""
         da, dq = self._direction(d_alpha), self._direction(d_q)
         if da is None and dq is None:
             raise ValueError("give d_alpha and / or d_q")

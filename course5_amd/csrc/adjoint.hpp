@@ -66,6 +66,7 @@ void launch_adjoint_exact_resolve(hipStream_t s, const ResolveParams& r, const f
 void launch_exact_gather_exps(hipStream_t s, const int32_t* exp_a, const int32_t* exp_q, const int32_t* perm, int64_t n, const ExactSums& x);
 void launch_exact_emit_exps(hipStream_t s, const ExactSums& x, const int32_t* perm, int64_t n, int32_t* exp_a, int32_t* exp_q);
 void launch_exact_emit_words(hipStream_t s, const ExactSums& x, const int32_t* perm, int64_t n, int64_t* sums_a, int64_t* sums_q);
+// (ga_out or gq_out null: that block is not written)
 void launch_exact_finish(hipStream_t s, const ExactSums& x, const int32_t* perm, int64_t n, double* ga_out, double* gq_out);
 
 struct TangentParams {
@@ -155,6 +156,11 @@ void launch_gn_weight(hipStream_t s, const float2* t, const float2* w, int64_t n
 // launch_adjoint_resolve's twin for the diagonal
 void launch_gn_diag_resolve(hipStream_t s, const ResolveParams& r, const float2* weight, double* diag_a, double* diag_q);
 
+// "exact_sums": pass E (sums false) or pass S of the diagonal - launch_adjoint_exact_walk / _resolve with the segment
+// terms squared, pass E on the squares themselves; a.grad_out / weight: the weights (nullptr: ones)
+void launch_gn_diag_exact_walk(hipStream_t s, const AdjointParams& a, const ExactSums& x, bool sums);
+void launch_gn_diag_exact_resolve(hipStream_t s, const ResolveParams& r, const float2* weight, const ExactSums& x, bool sums);
+
 // ---- Hessian-vector render (c5_render_hvp*): the second derivative of sum_p g_I I_p in the cells' (alpha, Q), applied to
 // one direction
 
@@ -174,6 +180,13 @@ void launch_hvp_walk(hipStream_t s, const HvpParams& h, int pass);
 
 // the same over bin_sort_resolve's lists (sorts them in place, as launch_adjoint_resolve)
 void launch_hvp_resolve(hipStream_t s, const ResolveParams& r, const double2* dir, const float2* grad_out, double* h_a, double* h_q);
+
+// "exact_sums": pass E (sums false: leaves the entry heads in place) or pass S of launch_hvp_walk(.., 2)'s walk, after
+// launch_hvp_walk(.., 1); reads h.w, h.dir, h.grad_out, h.lambda and h.lambda_dot only.  And the same over
+// bin_sort_resolve's lists.
+void launch_hvp_exact_walk(hipStream_t s, const HvpParams& h, const ExactSums& x, bool sums);
+void launch_hvp_exact_resolve(hipStream_t s, const ResolveParams& r, const double2* dir, const float2* grad_out, const ExactSums& x,
+                              bool sums);
 
 // launch_adjoint_permute with either output null (that block is not written)
 void launch_hvp_permute(hipStream_t s, const double* ha_dev, const double* hq_dev, const int32_t* perm, int64_t n, double* ha_out,

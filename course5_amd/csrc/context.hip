@@ -565,6 +565,9 @@ int c5_set_option(c5_context* ctx, const char* name, double value) {
         ctx->vertex_merge = static_cast<int>(value) != 0;
     } else if (n == "adjoint_exact") {
         ctx->adjoint_exact = static_cast<int>(value) != 0;
+    } else if (n == "exact_sums") {
+        if (value != 0 && value != 1) return fail(ctx, C5_ERR_INVALID, "exact_sums must be 0 (fp64 atomics) or 1");
+        ctx->exact_sums = static_cast<int>(value);
     } else if (n == "split_tilt_x" || n == "split_tilt_y") {  // testing: tilt of a forced split's planes
         if (!(std::fabs(value) < 64.0)) return fail(ctx, C5_ERR_INVALID, "split tilt out of range");
         (n == "split_tilt_x" ? ctx->split_tilt_x : ctx->split_tilt_y) = value;

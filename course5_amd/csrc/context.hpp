@@ -277,6 +277,7 @@ struct c5_context {
 
     // exact adjoint sums ("adjoint_exact", c5_render_adjoint_exact_*): allocated at the first exact call only
     int adjoint_exact = 0;           // "adjoint_exact": c5_render_adjoint* and its batch return the exact sums (exact_sum.hpp)
+    int exact_sums = 0;              // "exact_sums": the adjoint, c5_render_gn_* and c5_render_hvp* return the exact sums
     c5api::DeviceBuffer adj_exact;   // [n_cells][4] int64 words, [n_cells] int2 exponents (device order), then the misfit word
 
     // tangent render (c5_render_tangent*): shares the adjoint's counters, sticky and status words and adj_perm; nothing of

@@ -184,13 +184,15 @@ int exact_sums(c5_context* ctx, c5::ExactSums& x) {
 // images), pass E into x.exps (`bounds`: cleared here first) and pass S against x.exps into x.words (`sums`: cleared here
 // first, the misfit word with them where `first`) - the walk's, or the resolve's over bin_sort_resolve's lists.  keep: the
 // walk's pass S leaves the entry heads in place (another image follows); without pass S they stay in place anyway, and the
-// next per-view setup clears them.
+// next per-view setup clears them.  squared: the Gauss-Newton diagonal's kernels, `weights` may then be null (ones).
 int exact_passes(c5_context* ctx, const DerivativeView& v, c5::ExactSums x, const float2* weights, bool bounds, bool sums,
-                 bool have_lambda, bool keep, bool first) {
+                 bool have_lambda, bool keep, bool first, bool squared = false) {
     c5::launch_exact_clear(v.s, x, ctx->n_cells, bounds, sums, sums && first);
+    const auto walk = squared ? c5::launch_gn_diag_exact_walk : c5::launch_adjoint_exact_walk;
     if (v.bin_sort) {
-        if (bounds) c5::launch_adjoint_exact_resolve(v.s, v.r, weights, x, false);
-        if (sums) c5::launch_adjoint_exact_resolve(v.s, v.r, weights, x, true);
+        const auto resolve = squared ? c5::launch_gn_diag_exact_resolve : c5::launch_adjoint_exact_resolve;
+        if (bounds) resolve(v.s, v.r, weights, x, false);
+        if (sums) resolve(v.s, v.r, weights, x, true);
         return C5_OK;
     }
     c5::AdjointParams ap;
@@ -198,10 +200,10 @@ int exact_passes(c5_context* ctx, const DerivativeView& v, c5::ExactSums x, cons
     if (rc) return rc;
     ap.grad_out = weights;
     if (!have_lambda) c5::launch_adjoint_walk(v.s, ap, 1);
-    if (bounds) c5::launch_adjoint_exact_walk(v.s, ap, x, false);
+    if (bounds) walk(v.s, ap, x, false);
     x.keep_entries = keep ? 1 : 0;
     if (sums) {
-        c5::launch_adjoint_exact_walk(v.s, ap, x, true);
+        walk(v.s, ap, x, true);
         if (!keep) ctx->slots[0].head_clean = true;  // (pass S hands every head back cleared)
     }
     return C5_OK;
@@ -228,23 +230,67 @@ int exact_images(c5_context* ctx, const DerivativeView& v, int n, const float2* 
     return rc ? rc : commit_exact(ctx, x, what);
 }
 
-// c5_render_adjoint_exact_bounds: pass 1 and pass E over the context's rows; the exponents in the caller's order
-int enqueue_exact_bounds(c5_context* ctx, const float2* grad_out, int32_t* exp_a, int32_t* exp_q) {
+// The exact passes of the Hessian-vector render: the direction into device order (the tangent's buffer), pass 1 (Lambda
+// and Lambda_dot per pixel), pass E into x.exps (`bounds`: cleared here first) and pass S against x.exps into x.words
+// (`sums`: cleared here first, with the misfit word) - the walk's, or hvp_resolve's over bin_sort_resolve's lists.
+int hvp_exact_passes(c5_context* ctx, const DerivativeView& v, c5::ExactSums x, const double* d_alpha, const double* d_q,
+                     const float2* grad_out, bool bounds, bool sums) {
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
+    C5_HIP(ctx, ctx->tan_dir.ensure(n_cells * sizeof(double2)));
+    double2* const dir = ctx->tan_dir.as<double2>();
+    c5::launch_tangent_gather(v.s, d_alpha, d_q, v.perm, ctx->n_cells, dir);
+    c5::launch_exact_clear(v.s, x, ctx->n_cells, bounds, sums, sums);
+    if (v.bin_sort) {
+        if (bounds) c5::launch_hvp_exact_resolve(v.s, v.r, dir, grad_out, x, false);
+        if (sums) c5::launch_hvp_exact_resolve(v.s, v.r, dir, grad_out, x, true);
+        return C5_OK;
+    }
+    C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
+    C5_HIP(ctx, ctx->hvp_lambda_dot.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
+    c5::HvpParams hp{};
+    hp.w = v.w;
+    hp.dir = dir;
+    hp.grad_out = grad_out;
+    hp.lambda = ctx->adj_lambda.as<double>();
+    hp.lambda_dot = ctx->hvp_lambda_dot.as<double>();
+    c5::launch_hvp_walk(v.s, hp, 1);
+    if (bounds) c5::launch_hvp_exact_walk(v.s, hp, x, false);
+    x.keep_entries = 0;
+    if (sums) {
+        c5::launch_hvp_exact_walk(v.s, hp, x, true);
+        ctx->slots[0].head_clean = true;  // (pass S hands every head back cleared)
+    }
+    return C5_OK;
+}
+
+// The passes of one kind of exact sum (C5_EXACT_*) over the view; `image`: the upstream image, or the diagonal's weights
+int exact_passes_of(c5_context* ctx, const DerivativeView& v, const c5::ExactSums& x, int what, const double* d_alpha,
+                    const double* d_q, const float2* image, bool bounds, bool sums) {
+    if (what == C5_EXACT_HVP) return hvp_exact_passes(ctx, v, x, d_alpha, d_q, image, bounds, sums);
+    return exact_passes(ctx, v, x, image, bounds, sums, false, false, sums, what == C5_EXACT_GN_DIAGONAL);
+}
+
+const char* const kExactBoundsName[] = {"adjoint exact bounds", "gn diagonal exact bounds", "hvp exact bounds"};
+const char* const kExactSumsName[] = {"adjoint exact sums", "gn diagonal exact sums", "hvp exact sums"};
+
+// c5_render_exact_bounds: pass 1 and pass E over the context's rows; the exponents in the caller's order
+int enqueue_exact_bounds(c5_context* ctx, int what, const double* d_alpha, const double* d_q, const float2* image, int32_t* exp_a,
+                         int32_t* exp_q) {
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc || v.no_cells) return rc;
     c5::ExactSums x;
     rc = exact_sums(ctx, x);
-    if (!rc) rc = exact_passes(ctx, v, x, grad_out, true, false, false, false, false);
+    if (!rc) rc = exact_passes_of(ctx, v, x, what, d_alpha, d_q, image, true, false);
     if (rc) return rc;
     c5::launch_exact_emit_exps(v.s, x, v.perm, ctx->n_cells, exp_a, exp_q);
-    return commit_derivative(ctx, "adjoint exact bounds");
+    return commit_derivative(ctx, kExactBoundsName[what]);
 }
 
-// c5_render_adjoint_exact_sums: the caller's exponents into device order, pass 1 and pass S against them; the words in
-// the caller's order
-int enqueue_exact_sums(c5_context* ctx, const float2* grad_out, const int32_t* exp_a, const int32_t* exp_q, int64_t* sums_a,
-                       int64_t* sums_q) {
+// c5_render_exact_sums: the caller's exponents into device order, pass 1 and pass S against them; the words in the
+// caller's order
+int enqueue_exact_sums(c5_context* ctx, int what, const double* d_alpha, const double* d_q, const float2* image, const int32_t* exp_a,
+                       const int32_t* exp_q, int64_t* sums_a, int64_t* sums_q) {
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc || v.no_cells) return rc;
@@ -252,18 +298,18 @@ int enqueue_exact_sums(c5_context* ctx, const float2* grad_out, const int32_t* e
     rc = exact_sums(ctx, x);
     if (rc) return rc;
     c5::launch_exact_gather_exps(v.s, exp_a, exp_q, v.perm, ctx->n_cells, x);
-    rc = exact_passes(ctx, v, x, grad_out, false, true, false, false, true);
+    rc = exact_passes_of(ctx, v, x, what, d_alpha, d_q, image, false, true);
     if (rc) return rc;
     c5::launch_exact_emit_words(v.s, x, v.perm, ctx->n_cells, sums_a, sums_q);
-    return commit_exact(ctx, x, "adjoint exact sums");
+    return commit_exact(ctx, x, kExactSumsName[what]);
 }
 
-// The adjoint: adjoint_one on the upstream image; with "adjoint_exact", the exact sums.
+// The adjoint: adjoint_one on the upstream image; with "adjoint_exact" or "exact_sums", the exact sums.
 int enqueue_adjoint(c5_context* ctx, const float2* grad_out, double* ga_out, double* gq_out) {
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc || v.no_cells) return rc;
-    if (ctx->adjoint_exact) return exact_images(ctx, v, 1, grad_out, ga_out, gq_out, "adjoint");
+    if (ctx->adjoint_exact || ctx->exact_sums) return exact_images(ctx, v, 1, grad_out, ga_out, gq_out, "adjoint");
     rc = adjoint_one(ctx, v, false, grad_out, ga_out, gq_out);
     return rc ? rc : commit_derivative(ctx, "adjoint");
 }
@@ -374,13 +420,13 @@ int enqueue_tangent_batch(c5_context* ctx, int n, const double* d_alpha, const d
 // n upstream images ([n][local_rows][res_x] float2) -> ga_out / gq_out [n][n_cells] in the caller's order: one per-view
 // setup and ONE pass 1 (Lambda does not depend on the weights), then per chunk of up to `width` images the batched pass 2
 // into [n_cells][2 width] and its permutation.  On bin_sort_resolve's lists: adjoint_one per image.  A batch of one is the
-// single adjoint.  With "adjoint_exact": the single exact path per image (exact_images).
+// single adjoint.  With "adjoint_exact" or "exact_sums": the single exact path per image (exact_images).
 int enqueue_adjoint_batch(c5_context* ctx, int n, const float2* grad_out, double* ga_out, double* gq_out) {
     if (n == 1) return enqueue_adjoint(ctx, grad_out, ga_out, gq_out);
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc || v.no_cells) return rc;
-    if (ctx->adjoint_exact) return exact_images(ctx, v, n, grad_out, ga_out, gq_out, "adjoint batch");
+    if (ctx->adjoint_exact || ctx->exact_sums) return exact_images(ctx, v, n, grad_out, ga_out, gq_out, "adjoint batch");
     const int64_t n_cells = ctx->n_cells;
     if (v.bin_sort) {
         for (int j = 0; j < n && !rc; ++j)
@@ -410,6 +456,9 @@ int enqueue_adjoint_batch(c5_context* ctx, int n, const float2* grad_out, double
 // batched pass 2 on g, and its permutation.  The heads stay in place from pass A to pass B and between the chunks; the
 // last pass B hands them back cleared.  On bin_sort_resolve's lists: tangent_one -> gn_weight -> adjoint_one per
 // direction.  ha_out / hq_out: either may be null (then that block goes to a spare buffer); jv_out may be null.
+// With "exact_sums": pass A per chunk as it is, then every direction's g through the single exact path - passes E and S
+// on Lambda as pass A left it, and the finish - one after the other (exact_images' loop): bit for bit the exact adjoint
+// of g.  Pass S leaves the heads in place for all but the last direction of the call.
 int enqueue_gn_product(c5_context* ctx, int n, const double* d_alpha, const double* d_q, const float2* weight, double* ha_out,
                        double* hq_out, float2* jv_out) {
     DerivativeView v;
@@ -418,7 +467,20 @@ int enqueue_gn_product(c5_context* ctx, int n, const double* d_alpha, const doub
     if (v.no_cells) return zero_tangents(ctx, v, n, jv_out);
     const int64_t n_cells = ctx->n_cells, n_px = v.n_px;
     const int width = v.bin_sort ? 1 : batch_width(ctx, n);
-    if (!ha_out || !hq_out) C5_HIP(ctx, ctx->gn_spare.ensure(static_cast<size_t>(n_cells) * width * sizeof(double)));
+    const bool exact = ctx->exact_sums != 0;
+    c5::ExactSums x{};
+    if (exact) {
+        rc = exact_sums(ctx, x);
+        if (rc) return rc;
+    }
+    // direction j's g through passes E and S and the finish (a null output is not written)
+    auto exact_one = [&](int j, const float2* g) -> int {
+        const int rc1 = exact_passes(ctx, v, x, g, true, true, true, j + 1 < n, j == 0);
+        if (rc1) return rc1;
+        c5::launch_exact_finish(v.s, x, v.perm, n_cells, ha_out ? ha_out + j * n_cells : nullptr, hq_out ? hq_out + j * n_cells : nullptr);
+        return C5_OK;
+    };
+    if (!exact && (!ha_out || !hq_out)) C5_HIP(ctx, ctx->gn_spare.ensure(static_cast<size_t>(n_cells) * width * sizeof(double)));
     double* const spare = ctx->gn_spare.as<double>();
     if (v.bin_sort) {
         C5_HIP(ctx, ctx->gn_g.ensure(2 * static_cast<size_t>(n_px) * sizeof(float2) + 16));
@@ -428,13 +490,15 @@ int enqueue_gn_product(c5_context* ctx, int n, const double* d_alpha, const doub
             rc = tangent_one(ctx, v, d_alpha ? d_alpha + j * n_cells : nullptr, d_q ? d_q + j * n_cells : nullptr, t);
             if (rc) return rc;
             c5::launch_gn_weight(v.s, t, weight, n_px, 1, g);
-            rc = adjoint_one(ctx, v, false, g, ha_out ? ha_out + j * n_cells : spare, hq_out ? hq_out + j * n_cells : spare);
+            rc = exact ? exact_one(j, g)
+                       : adjoint_one(ctx, v, false, g, ha_out ? ha_out + j * n_cells : spare, hq_out ? hq_out + j * n_cells : spare);
             if (rc) return rc;
         }
-        return commit_derivative(ctx, "gn product");
+        return exact ? commit_exact(ctx, x, "gn product") : commit_derivative(ctx, "gn product");
     }
-    c5::AdjointBatchParams ab;
-    rc = adjoint_batch_params(ctx, v, width, ab);
+    c5::AdjointBatchParams ab{};
+    if (exact) C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
+    else rc = adjoint_batch_params(ctx, v, width, ab);
     if (rc) return rc;
     C5_HIP(ctx, ctx->bat_dirs.ensure(static_cast<size_t>(n_cells) * width * sizeof(double2)));
     C5_HIP(ctx, ctx->gn_g.ensure(static_cast<size_t>(width) * n_px * sizeof(float2) + 16));
@@ -452,11 +516,15 @@ int enqueue_gn_product(c5_context* ctx, int n, const double* d_alpha, const doub
         ab.keep_entries = k0 + width < n;
         gather_chunk(ctx, v, width, d_alpha, d_q, k0, ga.n_used);
         c5::launch_gn_walk_a(v.s, width, ga);
-        rc = adjoint_chunk(ctx, v, width, ab, 0, ha_out ? ha_out + k0 * n_cells : spare, hq_out ? hq_out + k0 * n_cells : spare);
+        if (exact) {
+            for (int j = 0; j < ga.n_used && !rc; ++j) rc = exact_one(k0 + j, ga.g + j * n_px);
+        } else {
+            rc = adjoint_chunk(ctx, v, width, ab, 0, ha_out ? ha_out + k0 * n_cells : spare, hq_out ? hq_out + k0 * n_cells : spare);
+        }
         if (rc) return rc;
     }
-    ctx->slots[0].head_clean = true;  // (the last chunk's pass B hands every head back cleared)
-    return commit_derivative(ctx, "gn product");
+    ctx->slots[0].head_clean = true;  // (the last chunk's pass B - or the last direction's pass S - hands every head back cleared)
+    return exact ? commit_exact(ctx, x, "gn product") : commit_derivative(ctx, "gn product");
 }
 
 // The motion tangent: n velocity fields (host memory, [n][12]: A row-major then b, view space) -> out[n][local_rows][res_x]:
@@ -647,6 +715,14 @@ int enqueue_hvp(c5_context* ctx, const double* d_alpha, const double* d_q, const
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc || v.no_cells) return rc;
+    if (ctx->exact_sums) {  // pass 1, pass E, pass S and the finish
+        c5::ExactSums x;
+        rc = exact_sums(ctx, x);
+        if (!rc) rc = hvp_exact_passes(ctx, v, x, d_alpha, d_q, grad_out, true, true);
+        if (rc) return rc;
+        c5::launch_exact_finish(v.s, x, v.perm, ctx->n_cells, ha_out, hq_out);
+        return commit_exact(ctx, x, "hvp");
+    }
     const size_t n_cells = static_cast<size_t>(ctx->n_cells);
     C5_HIP(ctx, ctx->tan_dir.ensure(n_cells * sizeof(double2)));
     C5_HIP(ctx, ctx->adj_grad.ensure(2 * n_cells * sizeof(double)));
@@ -681,6 +757,14 @@ int enqueue_gn_diagonal(c5_context* ctx, const float2* weight, double* da_out, d
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc || v.no_cells) return rc;
+    if (ctx->exact_sums) {  // pass 1, pass E on the squares, pass S and the finish
+        c5::ExactSums x;
+        rc = exact_sums(ctx, x);
+        if (!rc) rc = exact_passes(ctx, v, x, weight, true, true, false, false, true, true);
+        if (rc) return rc;
+        c5::launch_exact_finish(v.s, x, v.perm, ctx->n_cells, da_out, dq_out);
+        return commit_exact(ctx, x, "gn diagonal");
+    }
     rc = adjoint_one(ctx, v, true, weight, da_out, dq_out);
     return rc ? rc : commit_derivative(ctx, "gn diagonal");
 }
@@ -720,14 +804,14 @@ int finish_adjoint(c5_context* ctx) {
     if (misfits)
         return fail(ctx, C5_ERR_INVALID,
                     "%s: %u contributions lie beyond their cell's exponent and were added nowhere: the exponents given are too small "
-                    "(take the elementwise max of c5_render_adjoint_exact_bounds over every part of the image)", ctx->adj_what, misfits);
+                    "(take the elementwise max of c5_render_exact_bounds over every part of the image)", ctx->adj_what, misfits);
     return C5_OK;
 }
 }  // namespace c5api
 
 namespace {
 
-// What the twenty-eight derivative entry points check before anything else, in this order: the context; a batch's size; the
+// What the thirty-two derivative entry points check before anything else, in this order: the context; a batch's size; the
 // call's own pointers (`required_ok`, and `per_cell_ok` where the grid has cells); no c5_render_host_async frame
 // outstanding; and for the host-pointer forms the image, after which the device is bound.
 struct DerivativeCall {
@@ -790,6 +874,19 @@ int run_staged(c5_context* ctx, const char* what, Staged (&blocks)[N], Enqueue e
 }
 
 size_t cells_bytes(const c5_context* ctx) { return static_cast<size_t>(ctx->n_cells) * sizeof(double); }
+
+// What c5_render_exact_bounds / _sums check of their kind and its inputs (`arrays_ok`: the call's own exponent and word
+// arrays), in check_derivative's terms.
+DerivativeCall exact_call(const char* name, bool host, int what, const void* d_alpha, const void* d_q, const void* image, bool arrays_ok) {
+    const bool known = what == C5_EXACT_ADJOINT || what == C5_EXACT_GN_DIAGONAL || what == C5_EXACT_HVP;
+    const bool dirs_ok = what == C5_EXACT_HVP ? (d_alpha || d_q) : (!d_alpha && !d_q);
+    const bool image_ok = what == C5_EXACT_GN_DIAGONAL || image != nullptr;
+    const char* const msg = !known      ? "unknown kind of exact sum: C5_EXACT_ADJOINT, C5_EXACT_GN_DIAGONAL or C5_EXACT_HVP"
+                            : !dirs_ok  ? "directions belong to C5_EXACT_HVP alone (d_alpha, d_q or both); the other kinds take NULL"
+                            : !image_ok ? "null upstream image"
+                                        : "null exact bounds or sums pointer";
+    return {name, host, 1, nullptr, known && dirs_ok && image_ok, arrays_ok, msg};
+}
 }  // namespace
 
 extern "C" {
@@ -815,50 +912,78 @@ int c5_render_adjoint(c5_context* ctx, const float* grad_out_host, double* grad_
     });
 }
 
-int c5_render_adjoint_exact_bounds_device(c5_context* ctx, const void* grad_out_device, void* exp_alpha_device, void* exp_q_device) {
-    int rc = check_derivative(ctx, {"c5_render_adjoint_exact_bounds", false, 1, nullptr, grad_out_device != nullptr,
-                                    exp_alpha_device && exp_q_device, "null exact bounds pointer"});
+int c5_render_exact_bounds_device(c5_context* ctx, int what, const void* d_alpha_dev, const void* d_q_dev, const void* image_dev,
+                                  void* exp_alpha_dev, void* exp_q_dev) {
+    int rc = check_derivative(ctx, exact_call("c5_render_exact_bounds", false, what, d_alpha_dev, d_q_dev, image_dev, exp_alpha_dev && exp_q_dev));
     if (rc) return rc;
-    return enqueue_exact_bounds(ctx, static_cast<const float2*>(grad_out_device), static_cast<int32_t*>(exp_alpha_device),
-                                static_cast<int32_t*>(exp_q_device));
+    return enqueue_exact_bounds(ctx, what, static_cast<const double*>(d_alpha_dev), static_cast<const double*>(d_q_dev),
+                                static_cast<const float2*>(image_dev), static_cast<int32_t*>(exp_alpha_dev), static_cast<int32_t*>(exp_q_dev));
 }
 
-int c5_render_adjoint_exact_bounds(c5_context* ctx, const float* grad_out_host, int32_t* exp_alpha_host, int32_t* exp_q_host) {
-    int rc = check_derivative(ctx, {"c5_render_adjoint_exact_bounds", true, 1, nullptr, grad_out_host != nullptr,
-                                    exp_alpha_host && exp_q_host, "null exact bounds pointer"});
+int c5_render_exact_bounds(c5_context* ctx, int what, const double* d_alpha_host, const double* d_q_host, const float* image_host,
+                           int32_t* exp_alpha_host, int32_t* exp_q_host) {
+    int rc = check_derivative(ctx, exact_call("c5_render_exact_bounds", true, what, d_alpha_host, d_q_host, image_host, exp_alpha_host && exp_q_host));
     if (rc) return rc;
     const size_t exp_bytes = static_cast<size_t>(ctx->n_cells) * sizeof(int32_t);
-    Staged b[] = {{grad_out_host, nullptr, image_bytes(ctx)}, {nullptr, exp_alpha_host, exp_bytes}, {nullptr, exp_q_host, exp_bytes}};
-    return run_staged(ctx, "adjoint exact bounds", b, [&] {
-        return enqueue_exact_bounds(ctx, b[0].as<const float2>(), b[1].as<int32_t>(), b[2].as<int32_t>());
+    Staged b[] = {{image_host, nullptr, image_bytes(ctx)},
+                  {d_alpha_host, nullptr, cells_bytes(ctx)},
+                  {d_q_host, nullptr, cells_bytes(ctx)},
+                  {nullptr, exp_alpha_host, exp_bytes},
+                  {nullptr, exp_q_host, exp_bytes}};
+    return run_staged(ctx, kExactBoundsName[what], b, [&] {
+        return enqueue_exact_bounds(ctx, what, b[1].as<const double>(), b[2].as<const double>(), b[0].as<const float2>(), b[3].as<int32_t>(),
+                                    b[4].as<int32_t>());
     });
 }
 
-int c5_render_adjoint_exact_sums_device(c5_context* ctx, const void* grad_out_device, const void* exp_alpha_device,
-                                        const void* exp_q_device, void* sums_alpha_device, void* sums_q_device) {
-    int rc = check_derivative(ctx, {"c5_render_adjoint_exact_sums", false, 1, nullptr, grad_out_device != nullptr,
-                                    exp_alpha_device && exp_q_device && sums_alpha_device && sums_q_device, "null exact sums pointer"});
+int c5_render_exact_sums_device(c5_context* ctx, int what, const void* d_alpha_dev, const void* d_q_dev, const void* image_dev,
+                                const void* exp_alpha_dev, const void* exp_q_dev, void* sums_alpha_dev, void* sums_q_dev) {
+    int rc = check_derivative(ctx, exact_call("c5_render_exact_sums", false, what, d_alpha_dev, d_q_dev, image_dev,
+                                              exp_alpha_dev && exp_q_dev && sums_alpha_dev && sums_q_dev));
     if (rc) return rc;
-    return enqueue_exact_sums(ctx, static_cast<const float2*>(grad_out_device), static_cast<const int32_t*>(exp_alpha_device),
-                              static_cast<const int32_t*>(exp_q_device), static_cast<int64_t*>(sums_alpha_device),
-                              static_cast<int64_t*>(sums_q_device));
+    return enqueue_exact_sums(ctx, what, static_cast<const double*>(d_alpha_dev), static_cast<const double*>(d_q_dev),
+                              static_cast<const float2*>(image_dev), static_cast<const int32_t*>(exp_alpha_dev),
+                              static_cast<const int32_t*>(exp_q_dev), static_cast<int64_t*>(sums_alpha_dev), static_cast<int64_t*>(sums_q_dev));
 }
 
-int c5_render_adjoint_exact_sums(c5_context* ctx, const float* grad_out_host, const int32_t* exp_alpha_host, const int32_t* exp_q_host,
-                                 int64_t* sums_alpha_host, int64_t* sums_q_host) {
-    int rc = check_derivative(ctx, {"c5_render_adjoint_exact_sums", true, 1, nullptr, grad_out_host != nullptr,
-                                    exp_alpha_host && exp_q_host && sums_alpha_host && sums_q_host, "null exact sums pointer"});
+int c5_render_exact_sums(c5_context* ctx, int what, const double* d_alpha_host, const double* d_q_host, const float* image_host,
+                         const int32_t* exp_alpha_host, const int32_t* exp_q_host, int64_t* sums_alpha_host, int64_t* sums_q_host) {
+    int rc = check_derivative(ctx, exact_call("c5_render_exact_sums", true, what, d_alpha_host, d_q_host, image_host,
+                                              exp_alpha_host && exp_q_host && sums_alpha_host && sums_q_host));
     if (rc) return rc;
     const size_t exp_bytes = static_cast<size_t>(ctx->n_cells) * sizeof(int32_t), word_bytes = static_cast<size_t>(ctx->n_cells) * 2 * sizeof(int64_t);
-    Staged b[] = {{grad_out_host, nullptr, image_bytes(ctx)},
+    Staged b[] = {{image_host, nullptr, image_bytes(ctx)},
+                  {d_alpha_host, nullptr, cells_bytes(ctx)},
+                  {d_q_host, nullptr, cells_bytes(ctx)},
                   {exp_alpha_host, nullptr, exp_bytes},
                   {exp_q_host, nullptr, exp_bytes},
                   {nullptr, sums_alpha_host, word_bytes},
                   {nullptr, sums_q_host, word_bytes}};
-    return run_staged(ctx, "adjoint exact sums", b, [&] {
-        return enqueue_exact_sums(ctx, b[0].as<const float2>(), b[1].as<const int32_t>(), b[2].as<const int32_t>(), b[3].as<int64_t>(),
-                                  b[4].as<int64_t>());
+    return run_staged(ctx, kExactSumsName[what], b, [&] {
+        return enqueue_exact_sums(ctx, what, b[1].as<const double>(), b[2].as<const double>(), b[0].as<const float2>(),
+                                  b[3].as<const int32_t>(), b[4].as<const int32_t>(), b[5].as<int64_t>(), b[6].as<int64_t>());
     });
+}
+
+// The adjoint's own pair: C5_EXACT_ADJOINT of the generic one.
+int c5_render_adjoint_exact_bounds_device(c5_context* ctx, const void* grad_out_device, void* exp_alpha_device, void* exp_q_device) {
+    return c5_render_exact_bounds_device(ctx, C5_EXACT_ADJOINT, nullptr, nullptr, grad_out_device, exp_alpha_device, exp_q_device);
+}
+
+int c5_render_adjoint_exact_bounds(c5_context* ctx, const float* grad_out_host, int32_t* exp_alpha_host, int32_t* exp_q_host) {
+    return c5_render_exact_bounds(ctx, C5_EXACT_ADJOINT, nullptr, nullptr, grad_out_host, exp_alpha_host, exp_q_host);
+}
+
+int c5_render_adjoint_exact_sums_device(c5_context* ctx, const void* grad_out_device, const void* exp_alpha_device,
+                                        const void* exp_q_device, void* sums_alpha_device, void* sums_q_device) {
+    return c5_render_exact_sums_device(ctx, C5_EXACT_ADJOINT, nullptr, nullptr, grad_out_device, exp_alpha_device, exp_q_device,
+                                       sums_alpha_device, sums_q_device);
+}
+
+int c5_render_adjoint_exact_sums(c5_context* ctx, const float* grad_out_host, const int32_t* exp_alpha_host, const int32_t* exp_q_host,
+                                 int64_t* sums_alpha_host, int64_t* sums_q_host) {
+    return c5_render_exact_sums(ctx, C5_EXACT_ADJOINT, nullptr, nullptr, grad_out_host, exp_alpha_host, exp_q_host, sums_alpha_host,
+                                sums_q_host);
 }
 
 // A pure host function: no context, no GPU.

@@ -17,7 +17,9 @@
 //                     same cell at the same step are summed first: one pair of atomics per distinct cell and step.
 //   adjoint_resolve   the same for the per-pixel sorted segment lists of bin_sort_resolve ("algorithm" 1).
 //   adjoint_permute   device order -> the caller's (c5_upload_grid, "cell_order").
-//   adjoint_exact_*   adjoint_walk<2> / adjoint_resolve with the exact sums' scatter policies (further down).
+//   adjoint_exact_*   adjoint_walk<2> / adjoint_resolve with the exact sums' scatter policies (further down); with
+//                     "exact_sums" the diagonal's and the Hessian-vector render's bodies take them too (gn_diag_exact_*,
+//                     hvp_exact_*), and the product runs adjoint_exact_* on each direction's g.
 //
 // The tangent (forward mode, c5_render_tangent*): the change (tau_dot, I_dot) of every pixel for a change (dalpha, dQ) of
 // the cells' scalars, the same terms carried forward along the ray instead of scattered back:
@@ -38,7 +40,7 @@
 // reference's sort, its clamp of alpha and one frame around their lists (deriv_lists.hpp).
 //
 // The sums are fp64 atomics, added in arrival order: the gradients are NOT bit-reproducible from run to run (the last bits
-// move) - unless "adjoint_exact" is on: then the same bodies run with another scatter policy, every contribution is rounded
+// move) - unless "adjoint_exact" or "exact_sums" is on: then the same bodies run with another scatter policy, every contribution is rounded
 // once onto a per-cell fixed-point grid and summed in int64 (exact_sum.hpp; adjoint_exact_walk below).
 // Every derivative file is compiled with -munsafe-fp-atomics (build.py): global_atomic_add_f64, no compare-and-swap.
 #include "deriv_lists.hpp"
@@ -52,7 +54,8 @@ namespace adj {
 // load), and the step's end - for a policy that reads something of its own per cell.  keep_heads: pass 2 leaves the
 // entry heads in place (another walk over the same lists follows).
 
-// fp64 atomics in arrival order (scatter_wave): the adjoint as it always was, and the Gauss-Newton diagonal
+// fp64 atomics in arrival order (scatter_wave): the adjoint, the Gauss-Newton diagonal and the Hessian-vector render as
+// they always were
 struct WaveScatter {
     double* __restrict__ grad_a;
     double* __restrict__ grad_q;
@@ -372,8 +375,8 @@ __global__ __launch_bounds__(256) void exact_finish(ExactSums X, const int32_t* 
     const int2 e = X.exps[i];
     const longlong2* const w = reinterpret_cast<const longlong2*>(X.words + 4 * i);
     const longlong2 wa = w[0], wq = w[1];
-    ga_out[d] = exact::finish(e.x, wa.x, wa.y, X.word_bits);
-    gq_out[d] = exact::finish(e.y, wq.x, wq.y, X.word_bits);
+    if (ga_out) ga_out[d] = exact::finish(e.x, wa.x, wa.y, X.word_bits);  // (either may be null: the product's and the hvp's)
+    if (gq_out) gq_out[d] = exact::finish(e.y, wq.x, wq.y, X.word_bits);
 }
 
 // Nothing is shared between the lanes, so a lane leaves the loop when its ray ends.  The cell's direction is loaded
@@ -666,6 +669,8 @@ __global__ __launch_bounds__(256) void adjoint_permute_batch(const double* __res
 //                     d_q += w_I (dI/dQ_k)^2 (a ray crosses a convex cell in at most one segment, so the Jacobian's entry
 //                     of (pixel, cell) is that segment's term).
 //   gn_weight / gn_diag_resolve   the same over bin_sort_resolve's lists ("algorithm" 1).
+//   gn_diag_exact_walk<0 / 1>, gn_diag_exact_resolve<0 / 1>   pass E and pass S of "exact_sums" on the squared terms.
+// The exact product needs no kernel of its own: gn_walk_a leaves g and Lambda, and adjoint_exact_walk / _resolve run on g.
 
 template <int KC>
 __global__ __launch_bounds__(64) void gn_walk_a(GnWalkParams A) {
@@ -693,6 +698,20 @@ __global__ __launch_bounds__(256) void gn_diag_resolve(ResolveParams R, const fl
     adj::adjoint_resolve_body<true>(R, weight, adj::WaveScatter{diag_a, diag_q});
 }
 
+// pass E (SUMS 0) and pass S (SUMS 1) of the exact diagonal: gn_diag_walk / gn_diag_resolve with the exact sums' scatter
+// policies.  Pass E runs on the SQUARED terms: the exponents of the unsquared adjoint say nothing about them.
+template <int SUMS>
+__global__ __launch_bounds__(64) void gn_diag_exact_walk(AdjointParams A, ExactSums X) {
+    if (SUMS) adj::adjoint_walk_body<2, true>(A, adj::ExactScatter{X.exps, X.words, X.misfits, X.word_bits, X.keep_entries != 0});
+    else adj::adjoint_walk_body<2, true>(A, adj::ExponentScatter{X.exps});
+}
+
+template <int SUMS>
+__global__ __launch_bounds__(256) void gn_diag_exact_resolve(ResolveParams R, const float2* __restrict__ weight, ExactSums X) {
+    if (SUMS) adj::adjoint_resolve_body<true>(R, weight, adj::ExactScatter{X.exps, X.words, X.misfits, X.word_bits, true});
+    else adj::adjoint_resolve_body<true>(R, weight, adj::ExponentScatter{X.exps});
+}
+
 // ---- Hessian-vector render (c5_render_hvp*) ---------------------------------------------------------------------------
 // h = Hess(phi) v for phi = sum_p (g_tau tau + g_I I) and a direction v = (a_dot, Q_dot) of the cells' scalars.  tau is
 // linear in alpha: only g_I counts.  With lambda_k = g_I T_k, S_k = (1 - E_k) / a_k and its derivatives S_a, S_aa in a,
@@ -704,14 +723,17 @@ __global__ __launch_bounds__(256) void gn_diag_resolve(ResolveParams R, const fl
 //   hvp_walk<1>   adjoint_walk<1>'s walk with the direction loaded beside the next record (tangent_walk): Lambda and
 //                 Lambda_dot per pixel.  Leaves the entry lists in place for ...
 //   hvp_walk<2>   ... adjoint_walk<2>'s frame: I, I_dot, Lambda_k, Lambda_dot_k run along, and the segment's (h_alpha, h_q)
-//                 go through scatter_wave.  A pixel with g_I == 0 is not walked.
+//                 go to the scatter policy (WaveScatter: scatter_wave).  A pixel with g_I == 0 is not walked.
 //   hvp_resolve   the same over bin_sort_resolve's lists ("algorithm" 1).
+//   hvp_exact_walk<0 / 1>, hvp_exact_resolve<0 / 1>   pass E and pass S of "exact_sums": the same two bodies with
+//                 ExponentScatter / ExactScatter, after hvp_walk<1>.
 //   hvp_permute   device order -> the caller's; either output may be null.
 
 namespace adj {
 
-template <int PASS>
-__device__ __forceinline__ void hvp_walk_body(const HvpParams& A) {
+// Scatter: where pass 2's (h_alpha, h_q) go, as adjoint_walk_body's (pass 1 takes one and does not use it).
+template <int PASS, class Scatter>
+__device__ __forceinline__ void hvp_walk_body(const HvpParams& A, Scatter sc) {
     const WalkParams& P = A.w;
     const D2* __restrict__ dir = reinterpret_cast<const D2*>(A.dir);
     Ray r;
@@ -731,6 +753,7 @@ __device__ __forceinline__ void hvp_walk_body(const HvpParams& A) {
     if (r.cell >= 0) {
         load_cell(cur, P.xrec, r.cell);
         d_cur = dir[r.cell];
+        if (PASS == 2) sc.first(r.cell);
     }
 
     // wave-uniform loop in pass 2 (the scatter wants every lane): a lane whose ray has ended takes part with nothing to add
@@ -748,6 +771,7 @@ __device__ __forceinline__ void hvp_walk_body(const HvpParams& A) {
             if (nb >= 0) {
                 load_cell(nxt, P.xrec, nb);
                 d_nxt = dir[nb];
+                if (PASS == 2) sc.next(nb);
             }
 
             if (is_segment(dz)) {
@@ -772,7 +796,10 @@ __device__ __forceinline__ void hvp_walk_body(const HvpParams& A) {
             cur = nxt;
             d_cur = d_nxt;
         }
-        if (PASS == 2) scatter_wave(emit, here, ha, hq, A.h_a, A.h_q);
+        if (PASS == 2) {
+            sc(emit, here, ha, hq);
+            if (live) sc.advance();
+        }
     }
 
     if (PASS == 1) {
@@ -781,7 +808,7 @@ __device__ __forceinline__ void hvp_walk_body(const HvpParams& A) {
             A.lambda_dot[r.lp] = lam_dot;
         }
         ray_count(r, P);
-    } else {
+    } else if (!sc.keep_heads()) {
         ray_clear_head(r, P);
     }
 }
@@ -790,14 +817,23 @@ __device__ __forceinline__ void hvp_walk_body(const HvpParams& A) {
 
 template <int PASS>
 __global__ __launch_bounds__(64) void hvp_walk(HvpParams A) {
-    adj::hvp_walk_body<PASS>(A);
+    adj::hvp_walk_body<PASS>(A, adj::WaveScatter{A.h_a, A.h_q});
+}
+
+// pass E (SUMS 0) and pass S (SUMS 1) of the exact Hessian-vector sums: hvp_walk<2>'s walk with the exact sums' scatter
+// policies; both follow hvp_walk<1> (Lambda, Lambda_dot, and the entry heads left in place)
+template <int SUMS>
+__global__ __launch_bounds__(64) void hvp_exact_walk(HvpParams A, ExactSums X) {
+    if (SUMS) adj::hvp_walk_body<2>(A, adj::ExactScatter{X.exps, X.words, X.misfits, X.word_bits, X.keep_entries != 0});
+    else adj::hvp_walk_body<2>(A, adj::ExponentScatter{X.exps});
 }
 
 // adjoint_resolve's frame with the tangent carried along; Lambda and Lambda_dot from a pre-pass over the sorted list, in
 // the order the loop re-sums them.
-__global__ __launch_bounds__(256) void hvp_resolve(ResolveParams R, const double2* __restrict__ dir_v, const float2* __restrict__ grad_out,
-                                                   double* __restrict__ h_a, double* __restrict__ h_q) {
-    using namespace adj;
+namespace adj {
+template <class Scatter>
+__device__ __forceinline__ void hvp_resolve_body(const ResolveParams& R, const double2* __restrict__ dir_v,
+                                                 const float2* __restrict__ grad_out, Scatter sc) {
     const GridView& g = R.g;
     const D2* __restrict__ dir = reinterpret_cast<const D2*>(dir_v);
     double g_I = 0.0;
@@ -822,6 +858,7 @@ __global__ __launch_bounds__(256) void hvp_resolve(ResolveParams R, const double
         double ha = 0.0, hq = 0.0;
         if (live) {
             c = static_cast<int>(f.list[i].cell);
+            sc.first(c);
             const double dz = f.list[i].dz, q = g.q[c];
             const ClampedAlpha ca = clamp_alpha(g.alpha[c], R.alpha_limit);
             if (ca.active) {
@@ -837,8 +874,21 @@ __global__ __launch_bounds__(256) void hvp_resolve(ResolveParams R, const double
                 hvp_step(a, ca.clamped, q, dz, E, a_dot, d.b, lambda, lambda_dot, I, I_dot, ha, hq);
             }
         }
-        scatter_wave(emit, c, ha, hq, h_a, h_q);
+        sc(emit, c, ha, hq);
     }
+}
+}  // namespace adj
+
+__global__ __launch_bounds__(256) void hvp_resolve(ResolveParams R, const double2* __restrict__ dir_v, const float2* __restrict__ grad_out,
+                                                   double* __restrict__ h_a, double* __restrict__ h_q) {
+    adj::hvp_resolve_body(R, dir_v, grad_out, adj::WaveScatter{h_a, h_q});
+}
+
+template <int SUMS>
+__global__ __launch_bounds__(256) void hvp_exact_resolve(ResolveParams R, const double2* __restrict__ dir_v,
+                                                         const float2* __restrict__ grad_out, ExactSums X) {
+    if (SUMS) adj::hvp_resolve_body(R, dir_v, grad_out, adj::ExactScatter{X.exps, X.words, X.misfits, X.word_bits, true});
+    else adj::hvp_resolve_body(R, dir_v, grad_out, adj::ExponentScatter{X.exps});
 }
 
 // adjoint_permute with either output null
@@ -1005,6 +1055,35 @@ void launch_hvp_walk(hipStream_t s, const HvpParams& h, int pass) {
 
 void launch_hvp_resolve(hipStream_t s, const ResolveParams& r, const double2* dir, const float2* grad_out, double* h_a, double* h_q) {
     if (const unsigned blocks = pixel_blocks(r.im)) hipLaunchKernelGGL(hvp_resolve, dim3(blocks), dim3(256), 0, s, r, dir, grad_out, h_a, h_q);
+}
+
+void launch_gn_diag_exact_walk(hipStream_t s, const AdjointParams& a, const ExactSums& x, bool sums) {
+    const unsigned blocks = tile_blocks(a.w.im);
+    if (!blocks) return;
+    if (sums) hipLaunchKernelGGL(gn_diag_exact_walk<1>, dim3(blocks), dim3(64), 0, s, a, x);
+    else hipLaunchKernelGGL(gn_diag_exact_walk<0>, dim3(blocks), dim3(64), 0, s, a, x);
+}
+
+void launch_gn_diag_exact_resolve(hipStream_t s, const ResolveParams& r, const float2* weight, const ExactSums& x, bool sums) {
+    const unsigned blocks = pixel_blocks(r.im);
+    if (!blocks) return;
+    if (sums) hipLaunchKernelGGL(gn_diag_exact_resolve<1>, dim3(blocks), dim3(256), 0, s, r, weight, x);
+    else hipLaunchKernelGGL(gn_diag_exact_resolve<0>, dim3(blocks), dim3(256), 0, s, r, weight, x);
+}
+
+void launch_hvp_exact_walk(hipStream_t s, const HvpParams& h, const ExactSums& x, bool sums) {
+    const unsigned blocks = tile_blocks(h.w.im);
+    if (!blocks) return;
+    if (sums) hipLaunchKernelGGL(hvp_exact_walk<1>, dim3(blocks), dim3(64), 0, s, h, x);
+    else hipLaunchKernelGGL(hvp_exact_walk<0>, dim3(blocks), dim3(64), 0, s, h, x);
+}
+
+void launch_hvp_exact_resolve(hipStream_t s, const ResolveParams& r, const double2* dir, const float2* grad_out, const ExactSums& x,
+                              bool sums) {
+    const unsigned blocks = pixel_blocks(r.im);
+    if (!blocks) return;
+    if (sums) hipLaunchKernelGGL(hvp_exact_resolve<1>, dim3(blocks), dim3(256), 0, s, r, dir, grad_out, x);
+    else hipLaunchKernelGGL(hvp_exact_resolve<0>, dim3(blocks), dim3(256), 0, s, r, dir, grad_out, x);
 }
 
 void launch_hvp_permute(hipStream_t s, const double* ha_dev, const double* hq_dev, const int32_t* perm, int64_t n, double* ha_out,

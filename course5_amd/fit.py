@@ -15,8 +15,8 @@ both.  Everything is float64 on the context's GPU.
 
 A context may bring its own operators: if it has a method gn_operators(alpha, q, weight) returning an object with
 rhs(residual) -> (J^T W r)_alpha, (..)_q, diagonal() -> (diag_alpha, diag_q) and product(v_alpha, v_q) -> (h_alpha, h_q)
-(torch float64 tensors; v_alpha / v_q None: zero), gn_step uses those - a set of row shards that sums its parts, a dense
-model.
+(torch float64 tensors; v_alpha / v_q None: zero), gn_step uses those - a set of row shards that sums its parts
+(RowShards below), a dense model.
 
 newton_product and newton_step are the same with the EXACT Hessian of 1/2 sum w r^2: H + sum_p w_p r_p Hess(img_p), the
 second term from autograd.hvp (c5_render_hvp) on grad_img = W r.  The frame is exponential in alpha, so a fit of alpha is
@@ -25,9 +25,10 @@ context's own operators then also need hvp(v_alpha, v_q, grad_img) -> (h_alpha, 
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
-from . import capi
+from . import capi, sharding
 
 
 class _LibraryOperators:
@@ -57,6 +58,111 @@ class _LibraryOperators:
     def hvp(self, v_alpha, v_q, grad_img):
         from . import autograd
         return autograd.hvp(self.ctx, self.alpha, self.q, v_alpha, v_q, grad_img)
+
+
+def _host(t, dtype):
+    """A tensor or array as a contiguous numpy array of `dtype` on the host (None stays None)."""
+    if t is None:
+        return None
+    if isinstance(t, torch.Tensor):
+        t = t.detach().to("cpu").numpy()
+    return np.ascontiguousarray(t, dtype=dtype)
+
+
+class _ShardOperators:
+    """The four operators of a RowShards: every per-cell sum is the exact sum over the whole image, put together from the
+    parts' integers."""
+
+    def __init__(self, shards, alpha, q, weight):
+        self.shards = shards
+        a, qq = _host(alpha, np.float64), _host(q, np.float64)
+        for ctx, _rows in shards.parts:
+            ctx.update_scalars(a, qq)
+        self.weight = shards.whole_image(weight, "weight")
+
+    def _cut(self, image):
+        """The whole image's rows of every part (None: None for every part)."""
+        return [None if image is None else np.ascontiguousarray(image[rows]) for _ctx, rows in self.shards.parts]
+
+    def _exact(self, what, images, d_alpha=None, d_q=None):
+        """One kind of exact sum over all parts: bounds on every part, the exponents combined, sums on every part against
+        the combined exponents, the words combined, the finish."""
+        sh = self.shards
+        bounds = [ctx.render_exact_bounds(what, image=img, d_alpha=d_alpha, d_q=d_q) for (ctx, _rows), img in zip(sh.parts, images)]
+        ea, eq, _, _ = sharding.combine_exact([tuple(b) + (None, None) for b in bounds])
+        words = [ctx.render_exact_sums(what, ea, eq, image=img, d_alpha=d_alpha, d_q=d_q) for (ctx, _rows), img in zip(sh.parts, images)]
+        _, _, sa, sq = sharding.combine_exact([(ea, eq) + tuple(w) for w in words])
+        return tuple(torch.as_tensor(capi.exact_sums_finish(e, s, sh.res_x, sh.res_y), device=sh.device) for e, s in ((ea, sa), (eq, sq)))
+
+    def _times_weight(self, images):
+        """Per part: image * weight in float32, one multiply per channel (a None weight: ones)."""
+        return [img if w is None else img * w for img, w in zip(images, self._cut(self.weight))]
+
+    def rhs(self, residual):
+        r = self.shards.whole_image(residual, "residual")
+        return self._exact(capi.C5_EXACT_ADJOINT, self._times_weight(self._cut(r)))
+
+    def diagonal(self):
+        return self._exact(capi.C5_EXACT_GN_DIAGONAL, self._cut(self.weight))
+
+    def product(self, v_alpha, v_q):
+        va, vq = _host(v_alpha, np.float64), _host(v_q, np.float64)
+        # the split product: a tangent render on the part's rows, the fp32 multiply, then the exact adjoint of that image
+        jv = [ctx.render_tangent(va, vq) for ctx, _rows in self.shards.parts]
+        return self._exact(capi.C5_EXACT_ADJOINT, self._times_weight(jv))
+
+    def hvp(self, v_alpha, v_q, grad_img):
+        g = self.shards.whole_image(grad_img, "grad_img")
+        return self._exact(capi.C5_EXACT_HVP, self._cut(g), _host(v_alpha, np.float64), _host(v_q, np.float64))
+
+
+class RowShards:
+    """An image whose rows are spread over several contexts, as one context to gn_step and newton_step:
+
+        shards = course5_amd.fit.RowShards([(ctx0, rows0), (ctx1, rows1)])
+        delta, models = course5_amd.fit.gn_step(shards, alpha, q, residual, weight, fit=("alpha", "q"))
+
+    parts: a list of (ctx, rows).  Every context carries the same grid, image (set_image), view and alpha limit; rows is
+    the index array of the image rows that context owns - what its set_row_range or set_row_tiles was given
+    (sharding.local_rows).  The rows must partition range(res_y): a row owned twice or by nobody is refused.
+
+    gn_operators(alpha, q, weight) is the hook course5_amd.fit looks for.  The operators take whole-image residual, weight
+    and upstream arrays [res_y, res_x, 2], cut them by `rows`, send the scalars to every context, and put every per-cell
+    sum together from the parts' integers: render_exact_bounds on every part, sharding.combine_exact, render_exact_sums on
+    every part against the combined exponents, combine_exact, capi.exact_sums_finish.  So rhs, diagonal, product and hvp
+    - and with them the steps of gn_step and newton_step - are bit for bit those of ONE context over the whole image
+    with set_option("exact_sums", 1), however the rows are split.  They return float64 torch tensors on the first
+    context's device (a stand-in whose `device` is not an index names a torch device itself).
+
+    This class is about bits, not speed: it uses the host-pointer forms and numpy between them.  Contexts on one device
+    are the tested case; contexts on several devices work by construction and are unmeasured."""
+
+    def __init__(self, parts):
+        parts = [(ctx, np.asarray(rows, dtype=np.int64).reshape(-1)) for ctx, rows in parts]
+        if not parts:
+            raise ValueError("RowShards needs at least one (ctx, rows)")
+        first = parts[0][0]
+        self.res_x, self.res_y, self.n_cells = first.res_x, first.res_y, first.n_cells
+        for ctx, rows in parts:
+            if (ctx.res_x, ctx.res_y, ctx.n_cells) != (self.res_x, self.res_y, self.n_cells):
+                raise ValueError("every context of a RowShards carries the same grid and image")
+            if len(rows) != ctx.local_rows:
+                raise ValueError(f"a context renders {ctx.local_rows} rows and was given {len(rows)}")
+        owned = np.sort(np.concatenate([rows for _ctx, rows in parts]))
+        if len(owned) != self.res_y or not np.array_equal(owned, np.arange(self.res_y)):
+            raise ValueError(f"the rows of the parts must partition range({self.res_y}): every row once, none left out")
+        self.parts = parts
+        self.device = torch.device("cuda", first.device) if isinstance(first.device, int) else torch.device(first.device)
+
+    def whole_image(self, image, name: str):
+        """A whole-image array as float32 [res_y, res_x, 2] on the host (None stays None)."""
+        a = _host(image, np.float32)
+        if a is not None and a.shape != (self.res_y, self.res_x, 2):
+            raise ValueError(f"{name} must be the whole image [{self.res_y}, {self.res_x}, 2], not {list(a.shape)}")
+        return a
+
+    def gn_operators(self, alpha, q, weight):
+        return _ShardOperators(self, alpha, q, weight)
 
 
 def _weighted(residual, weight):

@@ -244,6 +244,9 @@ int c5_set_alpha_limit(c5_context* ctx, double alpha_limit);
  *                  (the section below c5_render_adjoint_batch): bit-reproducible from run to run and additive over rows.
  *                  Default 0: fp64 atomics, every kernel, code path and bit as before.  The Gauss-Newton, Hessian-vector
  *                  and vertex adjoint calls ignore it.  40 more bytes per cell, allocated at the first exact call.
+ *   "exact_sums"   1: c5_render_adjoint* as under "adjoint_exact" 1, and c5_render_gn_diagonal*, c5_render_gn_product* and
+ *                  c5_render_hvp* return exact sums too (the section below c5_render_hvp): every operator of a fit of
+ *                  (alpha, Q) bit-reproducible and additive over rows.  Default 0: as before.  The vertex adjoint ignores it.
  *   "overlap_setup" 1: entry lists and solid mask are built on a side stream while build_records
  *                  runs (only when "stage_timing" is 0).  Default 0: measured no faster.
  *   "pipeline"     1: two frame slots; the per-view setup of frame k + 1 runs on a second stream while
@@ -370,7 +373,8 @@ int c5_render_adjoint_batch_device(c5_context* ctx, int n_imgs, const void* grad
  * path image after image (the host loop that "algorithm" 1 uses for its batches; pass 1 runs once).  Results are
  * bit-reproducible from run to run, whatever "cell_order", the walk's options or the rows' split.  On "algorithm" 1 that
  * is promised only as far as the tangent's is: a pixel whose list holds segments of equal depth takes them in an order that
- * may change from call to call.  c5_render_gn_*, c5_render_hvp* and c5_render_vertex_adjoint* ignore the option.
+ * may change from call to call.  c5_render_gn_*, c5_render_hvp* and c5_render_vertex_adjoint* ignore the option
+ * (the first two have "exact_sums").
  * Memory: 40 more bytes per cell, allocated at the first exact call.
  *
  * For callers who split an image (row ranges, row tiles, several GPUs), the two intermediate results:
@@ -464,6 +468,57 @@ int c5_render_hvp(c5_context* ctx, const double* d_alpha_host, const double* d_q
                   double* h_alpha_host, double* h_q_host);
 int c5_render_hvp_device(c5_context* ctx, const void* d_alpha_dev, const void* d_q_dev, const void* grad_out_dev,
                          void* h_alpha_dev, void* h_q_dev);
+
+/* --- exact sums for the Gauss-Newton and Hessian-vector renders --------------------------------------
+ * Option "exact_sums" 1 gives every per-cell sum a fit of (alpha, Q) runs on the number format of "exact adjoint sums"
+ * above - the same h, m, exponents, words and finish; in all three operators below a ray adds to a cell at most once,
+ * each segment to its own cell, so the headroom argument carries over as it is:
+ *   c5_render_adjoint* and its batch    behave as under "adjoint_exact" 1.
+ *   c5_render_gn_diagonal*              pass 1, pass E on the SQUARED terms w (term)^2 as c5_render_gn_diagonal forms them
+ *                                       (the exponents of the unsquared adjoint say nothing about them), pass S, the finish.
+ *   c5_render_hvp*                      pass 1 (Lambda and Lambda_dot per pixel) once, then pass E, pass S and the finish
+ *                                       on the per-segment (h_alpha, h_q) terms of c5_render_hvp.
+ *   c5_render_gn_product*               per chunk of "batch_width" directions the tangent walk as it is (J v, g = weight *
+ *                                       fp32(J v) with one fp32 multiply per channel, and Lambda); then every direction's g
+ *                                       goes through pass E, pass S and the finish, one direction after the other.  The
+ *                                       result is DEFINED as, and is bit for bit, what c5_render_adjoint under
+ *                                       "adjoint_exact" 1 returns for grad_out = weight * (fp32 image of
+ *                                       c5_render_tangent_batch); jv_out keeps its bits; every slice of a batch is the
+ *                                       single call's, whatever "batch_width".
+ * All results are finished to fp64 inside the one call and are bit-reproducible from run to run, whatever "cell_order",
+ * the walk's options or the rows' split (on "algorithm" 1 as far as the tangent's is: lists with segments of equal depth).
+ * Where a NULL output or direction is legal without the option it stays legal.  "adjoint_exact" keeps its meaning: the
+ * adjoint only.  c5_render_vertex_adjoint* ignores both options (its per-point finish is another reduction).  Default 0:
+ * fp64 atomics, every kernel, code path and bit as before.  Memory: the exact adjoint's 40 bytes per cell, the same buffer.
+ *
+ * For callers who split an image, the two intermediate results of every kind of sum, one generic pair:
+ *   what = C5_EXACT_ADJOINT      image: the upstream image grad_out, required.  d_alpha / d_q: must be NULL.  Exactly
+ *                                c5_render_adjoint_exact_bounds / _sums, which are this kind by another name.
+ *   what = C5_EXACT_GN_DIAGONAL  image: the weight image, NULL = all ones.  d_alpha / d_q: must be NULL.
+ *   what = C5_EXACT_HVP          image: the upstream image grad_out, required.  d_alpha / d_q [n_cells] fp64 in the
+ *                                caller's order: either may be NULL (zero), not both.
+ * A direction given to another kind than C5_EXACT_HVP, a missing image, or an unknown `what`: C5_ERR_INVALID.
+ * c5_render_exact_bounds: pass 1 and pass E over the context's rows; exp_alpha / exp_q int32 [n_cells] in the caller's
+ * order, overwritten.  c5_render_exact_sums: pass 1 and pass S against the GIVEN exponents; sums_alpha / sums_q int64
+ * [n_cells][2] = (s1, s0), overwritten.  The contract is the exact adjoint's: exponents over any row ranges or row tiles
+ * combine by elementwise max, the words - every part's computed against the combined exponents - by elementwise integer
+ * add, and c5_exact_sums_finish then gives bit for bit what the single "exact_sums" call over the union of the rows
+ * gives.  The split Gauss-Newton product needs no kind of its own: it is a tangent render on the part's rows, the fp32
+ * multiply by the part's weights, then C5_EXACT_ADJOINT on that image.
+ * The mechanisms are the exact adjoint's too: a contribution beyond its cell's exponent is counted and reported, never
+ * wrapped (C5_ERR_INVALID with a c5_last_error text; the _device forms: by the next call that waits for the stream);
+ * INT32_MAX marks a non-finite contribution and finishes to NaN; the host forms retry by themselves on C5_RETRY; status
+ * and counters are the adjoint's own, never a frame's; the _device forms are asynchronous on the context's stream with
+ * device arrays; all four refuse while c5_render_host_async frames are outstanding. */
+enum { C5_EXACT_ADJOINT = 0, C5_EXACT_GN_DIAGONAL = 1, C5_EXACT_HVP = 2 };
+int c5_render_exact_bounds(c5_context* ctx, int what, const double* d_alpha_host, const double* d_q_host, const float* image_host,
+                           int32_t* exp_alpha_host, int32_t* exp_q_host);
+int c5_render_exact_bounds_device(c5_context* ctx, int what, const void* d_alpha_dev, const void* d_q_dev, const void* image_dev,
+                                  void* exp_alpha_dev, void* exp_q_dev);
+int c5_render_exact_sums(c5_context* ctx, int what, const double* d_alpha_host, const double* d_q_host, const float* image_host,
+                         const int32_t* exp_alpha_host, const int32_t* exp_q_host, int64_t* sums_alpha_host, int64_t* sums_q_host);
+int c5_render_exact_sums_device(c5_context* ctx, int what, const void* d_alpha_dev, const void* d_q_dev, const void* image_dev,
+                                const void* exp_alpha_dev, const void* exp_q_dev, void* sums_alpha_dev, void* sums_q_dev);
 
 /* --- motion tangent render ---------------------------------------------------------------------------
  * The frame c5_render would produce NOW differentiated with respect to the GEOMETRY, the cells' scalars held: the grid
