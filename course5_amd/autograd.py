@@ -47,8 +47,8 @@ and the coordinates of upload_grid go to the context through c5_update_points wh
 vertex adjoint render (c5_render_vertex_adjoint_device) for xyz and the adjoint render for alpha and q, whichever
 needs_input_grad asks for; a point welded to another at upload gets a zero gradient, its representative the group's sum.
 By default a tangent on xyz (jvp, jacfwd) raises, as second derivatives do; tangents on alpha and q go through the
-tangent render as in render.  Under vmap a batch of cotangents (jacrev) loops the single vertex adjoint call: there is
-no batched form.
+tangent render as in render.  Under vmap a batch of cotangents (jacrev, vmap over a vjp) goes to ONE batched vertex
+adjoint call (c5_render_vertex_adjoint_batch_device): one walk per ray for up to "batch_width" cotangents.
 
 render_mesh(ctx, xyz, alpha, q, forward_xyz=True) has forward mode in the points too: a tangent on xyz (torch.func.jvp,
 forward_ad dual tensors, jacfwd) goes to ONE vertex tangent render (c5_render_vertex_tangent_device), added in float32 to
@@ -471,9 +471,18 @@ def _vertex_adjoint(ctx: capi.Context, g: torch.Tensor, device: torch.device) ->
     return out
 
 
+def _vertex_adjoint_batch(ctx: capi.Context, g: torch.Tensor, device: torch.device) -> torch.Tensor:
+    """[K, n_pts, 3] float64 on the context's GPU: the batched vertex adjoint render for the upstream images g
+    ([K, local_rows, res_x, 2] float32, contiguous, there)."""
+    k = g.shape[0]
+    out = torch.empty((k, ctx.n_pts, 3), dtype=torch.float64, device=device)
+    _launch(ctx, device, lambda: ctx.render_vertex_adjoint_batch_device(g, out, n=k))
+    return out
+
+
 class _VertexAdjoint(_Operator):
     """d loss / d xyz: the vertex adjoint render of the frame of `fr`, float64 [n_pts, 3] on the context's GPU.  A batch of
-    upstream images (vmap) loops the single call."""
+    upstream images (vmap) is one batched call: [K, n_pts, 3]."""
     what = "vertex adjoint"
 
     @staticmethod
@@ -489,7 +498,7 @@ class _VertexAdjoint(_Operator):
         ctx = _current(fr, "backward")
         with _on_gpu(ctx, unwrapped=True) as device:
             g = _lift(grad_img, in_dims[2], info.batch_size).to(device=device, dtype=torch.float32).contiguous()
-            return torch.stack([_vertex_adjoint(ctx, gk, device) for gk in g]), 0
+            return _vertex_adjoint_batch(ctx, g, device), 0
 
 
 def _vertex_tangent(ctx: capi.Context, d: torch.Tensor, device: torch.device) -> torch.Tensor:
@@ -585,7 +594,8 @@ class _RenderMeshForward(_RenderMesh):
 def render_mesh(ctx: capi.Context, xyz: torch.Tensor, alpha: torch.Tensor, q: torch.Tensor, forward_xyz: bool = False) -> torch.Tensor:
     """The frame of `ctx` with the grid's points xyz ([n_pts, 3], the order and coordinates of upload_grid; sent to the
     context when they differ from the ones it holds) and the scalars alpha and q, differentiable in all three.  Reverse
-    mode in xyz is one vertex adjoint render per backward (under vmap, one per cotangent); second derivatives raise.
+    mode in xyz is one vertex adjoint render per backward (under vmap, one batched render for all the cotangents); second
+    derivatives raise.
     forward_xyz False (the default): forward mode in xyz raises, as it always has - callers and a test rely on that
     refusal, which is why forward mode is a switch and not the new default.  forward_xyz True: a tangent on xyz
     (torch.func.jvp, forward_ad, jacfwd) goes to ONE vertex tangent render, batched under vmap, and is added to the scalar

@@ -101,6 +101,8 @@ SIGNATURES = {
     "c5_rotation_motion": [_rp_t, C.c_int, C.c_int, C.c_int, _dp_t],
     "c5_render_vertex_adjoint": [_vp, _fp_t, _dp_t],
     "c5_render_vertex_adjoint_device": [_vp, _vp, _vp],
+    "c5_render_vertex_adjoint_batch": [_vp, C.c_int, _fp_t, _dp_t],
+    "c5_render_vertex_adjoint_batch_device": [_vp, C.c_int, _vp, _vp],
     "c5_update_points": [_vp, _dp_t, C.c_int64],
     "c5_render_vertex_tangent": [_vp, C.c_int, _dp_t, _fp_t],
     "c5_render_vertex_tangent_device": [_vp, C.c_int, _vp, _vp],
@@ -503,6 +505,30 @@ class Context:
         import torch
         self._check(self.lib.c5_render_vertex_adjoint_device(self.handle, self._image_dev(grad_out),
                                                              _device_ptr(grad_xyz, torch.float64, (self.n_pts, 3))))
+
+    def render_vertex_adjoint_batch(self, grad_out) -> np.ndarray:
+        """render_vertex_adjoint for K upstream images at once (grad_out [K, local_rows, res_x, 2], or one image
+        [local_rows, res_x, 2]): float64 [K, n_pts, 3], every slice render_vertex_adjoint's for that image alone up to the
+        order of the fp64 additions.  One walk per ray for up to "batch_width" images.  Synchronous; retries by itself."""
+        g = np.ascontiguousarray(grad_out, dtype=np.float32)
+        shape = (self.local_rows, self.res_x, 2)
+        if g.ndim not in (3, 4) or g.shape[-3:] != shape or g.shape[0] == 0:
+            raise ValueError(f"grad_out must be [{shape[0]}, {shape[1]}, 2] or [K, {shape[0]}, {shape[1]}, 2], not {list(g.shape)}")
+        k = 1 if g.ndim == 3 else g.shape[0]
+        out = np.zeros((k, self.n_pts, 3))
+        self._check(self.lib.c5_render_vertex_adjoint_batch(self.handle, k, _fp(g), _dp(out)))
+        return out
+
+    def render_vertex_adjoint_batch_device(self, grad_out, grad_xyz, n: int | None = None):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (grad_out float32 [K, local_rows,
+        res_x, 2], grad_xyz float64 [K, n_pts, 3], contiguous) or raw device pointers (then give n = K).  The status comes
+        with the next synchronize() (C5_RETRY: run it again)."""
+        import torch
+        k = n if n is not None else (grad_xyz.shape[0] if hasattr(grad_xyz, "shape") and len(grad_xyz.shape) == 3 else -1)
+        if k < 1:
+            raise ValueError("grad_xyz must be [K, n_pts, 3] with K >= 1 (or give n = K with raw device pointers)")
+        ptrs = self._image_dev(grad_out, k), _device_ptr(grad_xyz, torch.float64, (k, self.n_pts, 3))
+        self._check(self.lib.c5_render_vertex_adjoint_batch_device(self.handle, k, *ptrs))
 
     # -- vertex tangent render ---------------------------------------------------------------------
     def render_vertex_tangent(self, d_xyz) -> np.ndarray:

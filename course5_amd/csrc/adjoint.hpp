@@ -246,6 +246,30 @@ void launch_vertex_resolve(hipStream_t s, const ResolveParams& r, const float2* 
 void launch_vertex_finish(hipStream_t s, const MotionGeometry& geo, int64_t n_cells, const double* face_w, double* grad_view,
                           int64_t n_pts, const RotationList& R, double* grad_xyz);
 
+// ---- batched vertex adjoint (c5_render_vertex_adjoint_batch*): one walk per ray for up to kc upstream images (kc: the
+// chunk width, 4 or 8), after ONE pass 1
+
+struct VertexBatchParams {
+    WalkParams w;            // as VertexParams (the heads left in place by pass 1)
+    MotionGeometry geo;
+    const float2* grad_out;  // [n_used][n_local_rows][res_x] upstream weights: the chunk's first image
+    int64_t image_px;        // pixels per image
+    const double* lambda;    // pass 1's Lambda per pixel (launch_adjoint_walk(.., 1), once for every chunk)
+    double* face_w;          // [n_cells][kc][4][3] device order, accumulated: VertexParams' face_w per image
+    int32_t n_used;          // images of the chunk (<= kc)
+    int32_t keep_entries;    // as TangentBatchParams
+};
+
+// vertex_walk (merged) for kc upstream images at once (needs pass 1 first): every contribution the double the single
+// walk adds for that image alone, added in another order
+void launch_vertex_walk_batch(hipStream_t s, int kc, const VertexBatchParams& v);
+
+// launch_vertex_finish per image: face_w [n_cells][kc][12] -> grad_view[n_pts][3][kc] (zeroed by the caller; a point's
+// components apart, the images of one component side by side), then grad_xyz[k0 + j][v] = M^T grad_view[v][.][j] for
+// j < n_used
+void launch_vertex_finish_batch(hipStream_t s, int kc, const MotionGeometry& geo, int64_t n_cells, const double* face_w, double* grad_view,
+                                int64_t n_pts, const RotationList& R, int k0, int n_used, double* grad_xyz);
+
 // ---- vertex tangent (c5_render_vertex_tangent*): the frame differentiated along a displacement per grid point, the
 // operator launch_vertex_walk + launch_vertex_finish are the transpose of.  A face's depth at the pixel moves by
 // dw = sum_i lambda_i (u_z - gx u_x - gy u_y)[vertex i], u = M d_xyz the points' view-space velocities.

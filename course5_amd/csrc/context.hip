@@ -242,7 +242,7 @@ void c5_destroy(c5_context* ctx) {
                             &ctx->adj_sticky, &ctx->adj_grad, &ctx->adj_perm, &ctx->tan_dir,
                             &ctx->bat_dirs, &ctx->bat_grad, &ctx->gn_g, &ctx->gn_spare, &ctx->deriv_io,
                             &ctx->scal_stats, &ctx->vtx_face, &ctx->vtx_grad, &ctx->vtx_vel, &ctx->rm_count, &ctx->hvp_lambda_dot,
-                            &ctx->adj_exact};
+                            &ctx->adj_exact, &ctx->vtx_bat_face, &ctx->vtx_bat_grad};
     if (ctx->host_sticky) (void)hipHostFree(ctx->host_sticky);
     if (ctx->adj_status) (void)hipHostFree(ctx->adj_status);
     if (ctx->scal_host) (void)hipHostFree(ctx->scal_host);

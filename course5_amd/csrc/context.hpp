@@ -298,6 +298,9 @@ struct c5_context {
     c5api::DeviceBuffer vtx_grad;  // [n_pts][3] fp64: the gradient in view space
     int vertex_merge = 1;          // "vertex_merge": vertex_walk sums the lanes of a wavefront in one cell before its atomics
                                    // (measured on the C3 frame: 5.7 ms against 58 ms for the walk; profiles/vertex_adjoint_probe.md)
+    // batched vertex adjoint (c5_render_vertex_adjoint_batch*): allocated at the first batched call only
+    c5api::DeviceBuffer vtx_bat_face;  // [n_cells][width][4][3] fp64, device order: vtx_face per image of a chunk
+    c5api::DeviceBuffer vtx_bat_grad;  // [n_pts][3][width] fp64: vtx_grad per image of a chunk, the images of a component side by side
     // vertex tangent (c5_render_vertex_tangent*): allocated at the first call only
     c5api::DeviceBuffer vtx_vel;   // [n_pts][width][3] fp64: the points' view-space velocities (vertex_velocity)
     // ray matrix (c5_ray_matrix_*): allocated at the first call only (the scan's scratch is bin_sort_resolve's scratch64)

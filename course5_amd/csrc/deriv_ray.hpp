@@ -383,6 +383,69 @@ __device__ __forceinline__ void reduce_rows(const double* stage, bool emit, int 
     __syncthreads();  // (the rows are read before the next step writes them)
 }
 
+// The staged reduction of an outer product (the batched vertex adjoint: one wavefront per workgroup).  A lane's step is
+// twelve signed weights lambda_v times KC values G_j: it stages the 12 + KC factors, not the 12 KC products, so a row
+// stays 17 or 21 doubles where the products' would be 49 or 97 (reduce_rows takes 64 columns at most).  Per distinct cell
+// of the step, lane 12 q + v (q < 4) then sums lambda_v G_j over the cell's member rows for j = q, q + 4, ..: KC / 4
+// columns per lane with one read of lambda_v, in reduce_rows' four-rows-per-round grouping, and adds each sum with one
+// atomic to dst[cell][j][v].  Every product is rounded by itself (__dmul_rn: not contracted into the sum) - the double a
+// lane of vertex_walk stages.
+template <int KC>
+struct FaceStage {
+    static constexpr int kG = 12;                // where a row's G_j begin, behind the twelve weights
+    static constexpr int kRow = (12 + KC) | 1;   // (row pitch: an odd number of doubles)
+    static constexpr int kDoubles = 65 * kRow;
+};
+
+template <int KC>  // once per kernel, before the first step: the all-zero row 64
+__device__ __forceinline__ void face_stage_begin(double* stage, int lane) {
+    if (lane < FaceStage<KC>::kRow) stage[64 * FaceStage<KC>::kRow + lane] = 0.0;
+}
+template <int KC>
+__device__ __forceinline__ double* face_stage_row(double* stage, int lane) { return stage + lane * FaceStage<KC>::kRow; }
+
+// one step's reduction, by every lane: the rows of the lanes with `emit` set, summed per cell `here` into dst[cell][KC][12]
+template <int KC>
+__device__ __forceinline__ void reduce_faces(const double* stage, bool emit, int here, int lane, double* __restrict__ dst) {
+    constexpr int kRow = FaceStage<KC>::kRow, kG = FaceStage<KC>::kG, kPer = KC / 4;
+    static_assert(KC % 4 == 0, "four images per round of 48 lanes");
+    __syncthreads();  // (one wavefront: the rows are visible to every lane)
+    unsigned long long m = __builtin_amdgcn_ballot_w64(emit);
+    const int q = lane / 12, v = lane - 12 * q;
+    while (m != 0ull) {
+        const int leader = __builtin_ctzll(m);
+        const int lc = __builtin_amdgcn_readlane(here, leader);
+        const unsigned long long members = __builtin_amdgcn_ballot_w64(emit && here == lc);
+        if (lane < 48) {
+            double s[kPer];
+#pragma unroll
+            for (int h = 0; h < kPer; ++h) s[h] = 0.0;
+            for (unsigned long long rows = members; rows != 0ull;) {
+                const int b0 = __builtin_ctzll(rows);
+                rows &= rows - 1;
+                const int b1 = rows ? __builtin_ctzll(rows) : 64;
+                rows &= rows - 1;
+                const int b2 = rows ? __builtin_ctzll(rows) : 64;
+                rows &= rows - 1;
+                const int b3 = rows ? __builtin_ctzll(rows) : 64;
+                rows &= rows - 1;
+                const double *r0 = stage + b0 * kRow, *r1 = stage + b1 * kRow, *r2 = stage + b2 * kRow, *r3 = stage + b3 * kRow;
+                const double l0 = r0[v], l1 = r1[v], l2 = r2[v], l3 = r3[v];
+#pragma unroll
+                for (int h = 0; h < kPer; ++h) {
+                    const int j = kG + q + 4 * h;
+                    s[h] += (__dmul_rn(l0, r0[j]) + __dmul_rn(l1, r1[j])) + (__dmul_rn(l2, r2[j]) + __dmul_rn(l3, r3[j]));
+                }
+            }
+#pragma unroll
+            for (int h = 0; h < kPer; ++h)  // (image q + 4 h, vertex v: column 48 h + lane of the cell's 12 KC)
+                if (s[h] != 0.0) atomicAdd(dst + static_cast<size_t>(lc) * (12 * KC) + 48 * h + lane, s[h]);
+        }
+        m &= ~members;
+    }
+    __syncthreads();  // (the rows are read before the next step writes them)
+}
+
 }  // namespace adj
 
 // workgroups of a walk kernel: one wavefront per 8x8 pixel tile (0: no pixel)

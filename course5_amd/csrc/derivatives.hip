@@ -600,6 +600,65 @@ int enqueue_vertex_adjoint(c5_context* ctx, const float2* grad_out, double* grad
     return commit_derivative(ctx, "vertex adjoint");
 }
 
+// The batched vertex adjoint: n upstream images ([n][local_rows][res_x] float2) -> grad_xyz [n][n_pts][3] in the caller's
+// point order: one per-view setup and ONE pass 1 (Lambda does not depend on the weights), then per chunk of up to `width`
+// images the two buffers zeroed, vertex_walk_batch and the batched finish; the heads stay in place between the chunks and
+// the last walk hands them back cleared.  On bin_sort_resolve's lists: vertex_resolve and vertex_finish per image (the
+// first sorts the lists, the others find them sorted).  A batch of one is the single vertex adjoint.  Always merged
+// ("vertex_merge" is the single call's); the chunk's buffers - 96 width bytes per cell, 24 width per point - are
+// allocated here, at the first batched call.
+int enqueue_vertex_adjoint_batch(c5_context* ctx, int n, const float2* grad_out, double* grad_xyz) {
+    if (n == 1) return enqueue_vertex_adjoint(ctx, grad_out, grad_xyz);
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells), n_pts = static_cast<size_t>(ctx->n_pts);
+    if (v.no_cells) {  // (solids only: no point the frame depends on)
+        if (n_pts > 0) C5_HIP(ctx, hipMemsetAsync(grad_xyz, 0, 3 * n * n_pts * sizeof(double), v.s));
+        return C5_OK;
+    }
+    if (v.bin_sort) {
+        C5_HIP(ctx, ctx->vtx_face.ensure(12 * n_cells * sizeof(double)));
+        C5_HIP(ctx, ctx->vtx_grad.ensure(3 * n_pts * sizeof(double)));
+        double* const face_w = ctx->vtx_face.as<double>();
+        double* const grad_view = ctx->vtx_grad.as<double>();
+        for (int j = 0; j < n; ++j) {
+            C5_HIP(ctx, hipMemsetAsync(face_w, 0, 12 * n_cells * sizeof(double), v.s));
+            C5_HIP(ctx, hipMemsetAsync(grad_view, 0, 3 * n_pts * sizeof(double), v.s));
+            c5::launch_vertex_resolve(v.s, v.r, grad_out + j * v.n_px, face_w);
+            c5::launch_vertex_finish(v.s, v.geo, ctx->n_cells, face_w, grad_view, ctx->n_pts, ctx->view, grad_xyz + 3 * j * n_pts);
+        }
+        return commit_derivative(ctx, "vertex adjoint batch");
+    }
+    const int width = batch_width(ctx, n);
+    const size_t face_bytes = 12 * n_cells * width * sizeof(double), grad_bytes = 3 * n_pts * width * sizeof(double);
+    C5_HIP(ctx, ctx->vtx_bat_face.ensure(face_bytes));
+    C5_HIP(ctx, ctx->vtx_bat_grad.ensure(grad_bytes));
+    c5::AdjointParams ap;
+    rc = adjoint_params(ctx, v, ap);
+    if (rc) return rc;
+    c5::launch_adjoint_walk(v.s, ap, 1);
+    c5::VertexBatchParams vb{};
+    vb.w = v.w;
+    vb.geo = v.geo;
+    vb.image_px = v.n_px;
+    vb.lambda = ap.lambda;
+    vb.face_w = ctx->vtx_bat_face.as<double>();
+    double* const grad_view = ctx->vtx_bat_grad.as<double>();
+    for (int k0 = 0; k0 < n; k0 += width) {
+        vb.n_used = std::min(width, n - k0);
+        vb.grad_out = grad_out + k0 * v.n_px;
+        vb.keep_entries = k0 + width < n;
+        C5_HIP(ctx, hipMemsetAsync(vb.face_w, 0, face_bytes, v.s));
+        C5_HIP(ctx, hipMemsetAsync(grad_view, 0, grad_bytes, v.s));
+        c5::launch_vertex_walk_batch(v.s, width, vb);
+        c5::launch_vertex_finish_batch(v.s, width, v.geo, ctx->n_cells, vb.face_w, grad_view, ctx->n_pts, ctx->view, k0, vb.n_used,
+                                       grad_xyz);
+    }
+    ctx->slots[0].head_clean = true;  // (the last chunk's walk hands every head back cleared)
+    return commit_derivative(ctx, "vertex adjoint batch");
+}
+
 // The vertex tangent: n displacement fields ([n][n_pts][3] fp64 on the device, the caller's point order, the coordinates of
 // the upload) -> out[n][local_rows][res_x]: one per-view setup, then per chunk of up to `width` fields vertex_velocity (the
 // fields into view space, `width` per point) and one walk; the heads stay in place between the chunks and the last walk
@@ -811,7 +870,7 @@ int finish_adjoint(c5_context* ctx) {
 
 namespace {
 
-// What the thirty-two derivative entry points check before anything else, in this order: the context; a batch's size; the
+// What the thirty-four derivative entry points check before anything else, in this order: the context; a batch's size; the
 // call's own pointers (`required_ok`, and `per_cell_ok` where the grid has cells); no c5_render_host_async frame
 // outstanding; and for the host-pointer forms the image, after which the device is bound.
 struct DerivativeCall {
@@ -1176,6 +1235,23 @@ int c5_render_vertex_adjoint(c5_context* ctx, const float* grad_out_host, double
     Staged b[] = {{grad_out_host, nullptr, image_bytes(ctx)},
                   {nullptr, grad_xyz_host, 3 * static_cast<size_t>(ctx->n_pts) * sizeof(double)}};
     return run_staged(ctx, "vertex adjoint", b, [&] { return enqueue_vertex_adjoint(ctx, b[0].as<const float2>(), b[1].as<double>()); });
+}
+
+int c5_render_vertex_adjoint_batch_device(c5_context* ctx, int n_imgs, const void* grad_out_dev, void* grad_xyz_dev) {
+    int rc = check_derivative(ctx, {"c5_render_vertex_adjoint_batch", false, n_imgs, "upstream image", grad_out_dev && grad_xyz_dev, true,
+                                    "null vertex adjoint pointer"});
+    if (rc) return rc;
+    return enqueue_vertex_adjoint_batch(ctx, n_imgs, static_cast<const float2*>(grad_out_dev), static_cast<double*>(grad_xyz_dev));
+}
+
+int c5_render_vertex_adjoint_batch(c5_context* ctx, int n_imgs, const float* grad_out_host, double* grad_xyz_host) {
+    int rc = check_derivative(ctx, {"c5_render_vertex_adjoint_batch", true, n_imgs, "upstream image", grad_out_host && grad_xyz_host, true,
+                                    "null vertex adjoint pointer"});
+    if (rc) return rc;
+    Staged b[] = {{grad_out_host, nullptr, n_imgs * image_bytes(ctx)},
+                  {nullptr, grad_xyz_host, 3 * static_cast<size_t>(n_imgs) * static_cast<size_t>(ctx->n_pts) * sizeof(double)}};
+    return run_staged(ctx, "vertex adjoint batch", b,
+                      [&] { return enqueue_vertex_adjoint_batch(ctx, n_imgs, b[0].as<const float2>(), b[1].as<double>()); });
 }
 
 int c5_render_vertex_tangent_device(c5_context* ctx, int n_dirs, const void* d_xyz_dev, void* out_dev) {

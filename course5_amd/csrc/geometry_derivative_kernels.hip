@@ -19,9 +19,10 @@
 //   motion_resolve    the same over bin_sort_resolve's lists: both faces of every segment from the cell's vertices.
 // No atomics, no pre-pass: bit-reproducible, like the tangent.
 //
-// The vertex adjoint (c5_render_vertex_adjoint*), the motion tangent's reverse mode per grid point, and the vertex tangent
-// (c5_render_vertex_tangent*), the operator it is the transpose of: their blocks further down.  The vertex adjoint's sums
-// are fp64 atomics (global_atomic_add_f64: -munsafe-fp-atomics, build.py), added in arrival order: NOT bit-reproducible.
+// The vertex adjoint (c5_render_vertex_adjoint*), the motion tangent's reverse mode per grid point, its batch over K
+// upstream images (c5_render_vertex_adjoint_batch*) and the vertex tangent (c5_render_vertex_tangent*), the operator it is
+// the transpose of: their blocks further down.  The vertex adjoint's sums, single and batched, are fp64 atomics
+// (global_atomic_add_f64: -munsafe-fp-atomics, build.py), added in arrival order: NOT bit-reproducible.
 #include "deriv_faces.hpp"
 #include "deriv_lists.hpp"
 
@@ -332,6 +333,200 @@ __global__ __launch_bounds__(256) void vertex_finish_points(const double* __rest
     grad_xyz[3 * i + 2] = gz;
 }
 
+// ---- batched vertex adjoint (c5_render_vertex_adjoint_batch*) --------------------------------------------------------------
+// KC upstream images per walk.  Of a segment only g_tau and g_I differ from image to image: Lambda, T, E, chord_dI, the I
+// recurrence and the two faces' lambda are the ray's.  With G_j = fma(g_I,j T, chord_dI, g_tau,j a_raw) an image costs two
+// multiplies and one fma per segment and its share of the scatter.
+//   vertex_walk_batch<KC>          vertex_walk<true>'s frame; per step a lane stages its twelve signed lambda and its KC
+//                                  values G_j, and reduce_faces (deriv_ray.hpp) adds the cells' sums of lambda_v G_j to
+//                                  face_w[cell][j][face][vertex of the face].  Every contribution is the double
+//                                  vertex_walk stages for image j alone - the same two factors, rounded once - so a slice
+//                                  differs from the single call in the order of the additions only.
+//   vertex_finish_cells_batch<KC>  vertex_finish_cells per (cell, image), into grad_view[point][3][KC].
+//   vertex_finish_points_batch<KC> vertex_finish_points per (point, image), into the caller's [K][n_pts][3].
+// On bin_sort_resolve's lists the host runs vertex_resolve and vertex_finish per image.
+
+// The images: float2 g[KC] in registers at KC = 4 (168 VGPRs, the third wave per SIMD), in LDS ([KC][64], one 8-byte
+// column per lane) at KC = 8 - in registers the 8-wide kernel takes 186 VGPRs and loses that wave; from LDS it takes 154,
+// its 15 024 bytes of LDS per workgroup still let ten waves onto a CU, and the K = 8 batch on the C3 frame ran in 26.6 ms
+// against 27.5 (profiles/vertex_adjoint_batch_probe.md).
+template <int KC>
+__global__ __launch_bounds__(64) void vertex_walk_batch(VertexBatchParams A) {
+    using namespace adj;
+    using Stage = FaceStage<KC>;
+    constexpr bool G_LDS = KC > 4;
+    __shared__ double stage[Stage::kDoubles];
+    __shared__ float2 gs[G_LDS ? 64 * KC : 1];
+    const WalkParams& P = A.w;
+    Ray r;
+    const int lane = r.lane;
+    face_stage_begin<KC>(stage, lane);
+    double lam = 0.0, lam_total = 0.0, I = 0.0;
+    float2 g[G_LDS ? 1 : KC];
+    auto g_set = [&](int j, float2 v) {
+        if constexpr (G_LDS) gs[j * 64 + lane] = v;
+        else g[j] = v;
+    };
+    auto g_of = [&](int j) {
+        if constexpr (G_LDS) return gs[j * 64 + lane];
+        else return g[j];
+    };
+#pragma unroll
+    for (int j = 0; j < KC; ++j) g_set(j, make_float2(0.0f, 0.0f));
+
+    const EntryHead ent = ray_begin(r, P, [&] {
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < KC; ++j)
+            if (j < A.n_used) {
+                const float2 gj = A.grad_out[static_cast<size_t>(j) * A.image_px + r.lp];
+                g_set(j, gj);
+                any = any || gj.x != 0.0f || gj.y != 0.0f;
+            }
+        lam_total = A.lambda[r.lp];
+        return any;
+    });
+
+    CellRegs cur;
+    int4 cv = make_int4(0, 0, 0, 0);
+    if (r.cell >= 0) {
+        load_cell(cur, P.xrec, r.cell);
+        cv = A.geo.cell_vert[r.cell];
+    }
+
+    // wave-uniform loop (the reduction wants every lane): a lane whose ray has ended takes part with nothing to add
+    for (;;) {
+        const bool live = r.cell >= 0;
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        const int here = r.cell;
+        bool emit = false;
+        if (live) {
+            double p[4][3];
+            load_vertices(A.geo, cv, p);
+            double dz, carry_next;
+            const int nb = ray_step(r, P, ent, cur, dz, carry_next);
+            CellRegs nxt;
+            int4 cv_nxt = cv;
+            if (nb >= 0) {
+                load_cell(nxt, P.xrec, nb);
+                cv_nxt = A.geo.cell_vert[nb];
+            }
+
+            if (is_segment(dz)) {
+                const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+                double* const row = face_stage_row<KC>(stage, lane);
+                bool any = false;
+                if (a != 0.0) {
+                    lam = lambda_add(lam, a, dz);  // (as in pass 1: Lambda_n == Lambda bit for bit, Lambda - Lambda_k >= 0)
+                    const double T = exp_nonpositive(fmin(lam - lam_total, 0.0));
+                    const double E = exp_nonpositive(-a * dz);
+                    const double dI = chord_dI(a, q, E, I);
+#pragma unroll
+                    for (int j = 0; j < KC; ++j) {  // G_j, vertex_walk's operations
+                        const float2 gj = g_of(j);
+                        const double g_tau = gj.x, g_I = gj.y;
+                        const double G = fma(g_I * T, dI, g_tau * a_raw);
+                        row[Stage::kG + j] = G;
+                        any = any || G != 0.0;
+                    }
+                    I = segment_terms(a, q, dz, E, 1.0, I).I_next;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < KC; ++j) {
+                        const double g_tau = g_of(j).x;
+                        const double G = g_tau * a_raw;  // d tau / d dz (raw alpha, every segment)
+                        row[Stage::kG + j] = G;
+                        any = any || G != 0.0;
+                    }
+                }
+                if (any) {
+                    const CellFacesBary cf = cell_faces_bary(p, r.x, r.y);
+                    if (cf.found) {
+                        emit = true;
+#pragma unroll
+                        for (int v = 0; v < 12; ++v) row[v] = 0.0;
+                        row[3 * cf.out.f] = cf.out.l0;  // exit +, entry -: (-lambda) G is -(lambda G) to the bit
+                        row[3 * cf.out.f + 1] = cf.out.l1;
+                        row[3 * cf.out.f + 2] = cf.out.l2;
+                        row[3 * cf.in.f] = -cf.in.l0;
+                        row[3 * cf.in.f + 1] = -cf.in.l1;
+                        row[3 * cf.in.f + 2] = -cf.in.l2;
+                    }
+                }
+            }
+            ray_advance(r, nb, carry_next);
+            cur = nxt;
+            cv = cv_nxt;
+        }
+        reduce_faces<KC>(stage, emit, here, lane, A.face_w);
+    }
+
+    if (!A.keep_entries) ray_clear_head(r, P);
+}
+
+// vertex_finish_cells for KC images: face_w[cell][KC][12] -> grad_view[point][3][KC].  One thread per (cell, image), each
+// running vertex_finish_cells' atomics (the same products) for its image; the slopes are found per thread (the loads of a
+// cell's KC threads are one).  The KC lanes of a cell add to KC neighbouring doubles - one component of one point - which is
+// why grad_view keeps a point's components apart, [3][KC], not [KC][3].  Measured on the C3 frame at KC = 8 (profiles/
+// vertex_adjoint_batch_probe.md): 2.28 ms, 1.45 single finishes.  One thread per cell with the slopes found once - its
+// 36 KC atomics in turn, every lane of an instruction on another point - took 14.3 ms, more than eight single finishes
+// (12.5), and the K = 8 batch 26.6 ms instead of 14.5; threads per (cell, image) into [KC][3], 18.9 ms.
+template <int KC>
+__global__ __launch_bounds__(256) void vertex_finish_cells_batch(MotionGeometry G, int64_t n_cells, int n_used,
+                                                                 const double* __restrict__ face_w, double* __restrict__ grad_view) {
+    const int64_t t = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (t >= n_cells * KC) return;
+    const int64_t i = t / KC;
+    const int j = static_cast<int>(t - i * KC);
+    if (j >= n_used) return;
+    double w[12];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        w[k] = face_w[t * 12 + k];
+        any = any || w[k] != 0.0;
+    }
+    if (!any) return;
+    const int4 cv = G.cell_vert[i];
+    const int vid[4] = {cv.x, cv.y, cv.z, cv.w};
+    double p[4][3];
+    adj::load_vertices(G, cv, p);
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+        const FacePlane fp = face_plane(p, f);
+        if (fp.kind == 0) continue;  // (edge-on: no ray crosses it, and it has no slopes)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double wk = w[3 * f + k];
+            if (wk != 0.0) {
+                double* const gv = grad_view + static_cast<int64_t>(vid[adj::face_vertex(f, k)]) * (3 * KC) + j;
+                atomicAdd(gv, -fp.gx * wk);
+                atomicAdd(gv + KC, -fp.gy * wk);
+                atomicAdd(gv + 2 * KC, wk);
+            }
+        }
+    }
+}
+
+// vertex_finish_points for KC images: grad_xyz[k0 + j][point] = M^T grad_view[point][.][j] for j < n_used.  One thread per
+// (point, image).
+template <int KC>
+__global__ __launch_bounds__(256) void vertex_finish_points_batch(const double* __restrict__ grad_view, int64_t n_pts, int k0, int n_used,
+                                                                  RotationList R, double* __restrict__ grad_xyz) {
+    const int64_t t = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (t >= n_pts * KC) return;
+    const int64_t i = t / KC;
+    const int j = static_cast<int>(t - i * KC);
+    if (j >= n_used) return;
+    const double* const gv = grad_view + i * (3 * KC) + j;
+    double gx = gv[0], gy = gv[KC], gz = gv[2 * KC];
+    adj::rotate_linear<true>(R, gx, gy, gz);
+    double* const out = grad_xyz + 3 * (static_cast<int64_t>(k0 + j) * n_pts + i);
+    out[0] = gx;
+    out[1] = gy;
+    out[2] = gz;
+}
+
 // ---- vertex tangent (c5_render_vertex_tangent*) ---------------------------------------------------------------------------
 // The forward mode of the vertex adjoint: the motion tangent with the velocity u(P) = sum_i lambda_i u_i interpolated from
 // the face's three vertices instead of an affine field.  With u_v = M d_xyz[v] (M the linear part of the view) a face's
@@ -490,6 +685,16 @@ void launch_vertex_finish(hipStream_t s, const MotionGeometry& geo, int64_t n_ce
                           int64_t n_pts, const RotationList& R, double* grad_xyz) {
     if (n_cells > 0) hipLaunchKernelGGL(vertex_finish_cells, dim3(item_blocks(n_cells)), dim3(256), 0, s, geo, n_cells, face_w, grad_view);
     if (n_pts > 0) hipLaunchKernelGGL(vertex_finish_points, dim3(item_blocks(n_pts)), dim3(256), 0, s, grad_view, n_pts, R, grad_xyz);
+}
+
+void launch_vertex_walk_batch(hipStream_t s, int kc, const VertexBatchParams& v) {
+    if (const unsigned blocks = tile_blocks(v.w.im)) C5_LAUNCH_KC(vertex_walk_batch, kc, blocks, 64, s, v);
+}
+
+void launch_vertex_finish_batch(hipStream_t s, int kc, const MotionGeometry& geo, int64_t n_cells, const double* face_w, double* grad_view,
+                                int64_t n_pts, const RotationList& R, int k0, int n_used, double* grad_xyz) {
+    if (n_cells > 0) C5_LAUNCH_KC(vertex_finish_cells_batch, kc, item_blocks(n_cells * kc), 256, s, geo, n_cells, n_used, face_w, grad_view);
+    if (n_pts > 0) C5_LAUNCH_KC(vertex_finish_points_batch, kc, item_blocks(n_pts * kc), 256, s, grad_view, n_pts, k0, n_used, R, grad_xyz);
 }
 
 void launch_vertex_velocity(hipStream_t s, int kc, const double* d_xyz, int64_t n_pts, int k0, int n_used, const RotationList& R,

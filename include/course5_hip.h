@@ -237,9 +237,12 @@ int c5_set_alpha_limit(c5_context* ctx, double alpha_limit);
  *                  A sweep whose view changes every frame never pays for it.  0: every frame builds its own.  Same results.
  *   "batch_width"  tuning: directions or upstream images one walk of c5_render_tangent_batch* / c5_render_adjoint_batch*
  *                  carries: 4 or 8; 0 (default): 4 for batches of up to 4, else 8.  Same results (the adjoint's to rounding).
+ *                  c5_render_vertex_adjoint_batch* chunks its upstream images by it in the same way (96 x "batch_width" bytes
+ *                  per cell and 24 x "batch_width" per point), its results the same to the atomics' rounding.
  *   "vertex_merge" tuning: 1 (default): c5_render_vertex_adjoint* sums the lanes of a wavefront that share a cell (in LDS)
  *                  before its atomics; 0: every lane adds its own six values (measured 10 x slower on the C3 frame).  Same
- *                  results, to the atomics' rounding.
+ *                  results, to the atomics' rounding.  c5_render_vertex_adjoint_batch* ignores it for more than one image:
+ *                  it always merges.
  *   "adjoint_exact" 1: c5_render_adjoint, c5_render_adjoint_device and their batch forms return the exact adjoint sums
  *                  (the section below c5_render_adjoint_batch): bit-reproducible from run to run and additive over rows.
  *                  Default 0: fp64 atomics, every kernel, code path and bit as before.  The Gauss-Newton, Hessian-vector
@@ -583,6 +586,23 @@ int c5_rotation_motion(const c5_rotation* rots, int n_rots, int index, int what,
  * are outstanding (C5_ERR_STATE). */
 int c5_render_vertex_adjoint(c5_context* ctx, const float* grad_out_host, double* grad_xyz_host);
 int c5_render_vertex_adjoint_device(c5_context* ctx, const void* grad_out_dev, void* grad_xyz_dev);
+
+/* The batch: n_imgs upstream images grad_out[n_imgs][local_rows][res_x][2] fp32 -> grad_xyz[n_imgs][n_pts][3] fp64 in the
+ * caller's point order, overwritten.  Every ray is walked once for up to "batch_width" images at a time, and the adjoint's
+ * first pass (Lambda: it does not depend on the weights) runs once for all of them: of a segment only g_tau and g_I
+ * differ from image to image.  Every slice is c5_render_vertex_adjoint's for that image alone up to the order of the fp64
+ * additions - each contribution is the same product of the same two doubles - and like it NOT bit-reproducible from run
+ * to run.  An image of zeros gives a slice of exact zeros, and welded non-representatives receive exact zeros in every
+ * slice.  n_imgs == 1 is the single call.  On "algorithm" 1, and after a C5_RETRY onto its lists, the images run one
+ * after the other over one per-view setup.  "vertex_merge" is ignored for n_imgs > 1 (the batch always merges), as are
+ * "adjoint_exact" and "exact_sums".
+ * Status, counters, retries and side effects: the single call's.  The first batched call allocates 96 x "batch_width"
+ * bytes per cell and 24 x "batch_width" per point beside the single call's buffers; a context that never calls it uses
+ * no more memory than before.  c5_render_vertex_adjoint_batch is synchronous with host arrays and retries by itself on
+ * C5_RETRY; the _device form is asynchronous on the context's stream with device arrays.  n_imgs < 1 or a null pointer:
+ * C5_ERR_INVALID.  Both refuse while c5_render_host_async frames are outstanding (C5_ERR_STATE). */
+int c5_render_vertex_adjoint_batch(c5_context* ctx, int n_imgs, const float* grad_out_host, double* grad_xyz_host);
+int c5_render_vertex_adjoint_batch_device(c5_context* ctx, int n_imgs, const void* grad_out_dev, void* grad_xyz_dev);
 
 /* --- vertex tangent render ---------------------------------------------------------------------------
  * The forward mode of the shape: how the frame c5_render would produce NOW changes when every grid point v moves with
