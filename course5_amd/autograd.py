@@ -595,7 +595,9 @@ def render_mesh(ctx: capi.Context, xyz: torch.Tensor, alpha: torch.Tensor, q: to
     """The frame of `ctx` with the grid's points xyz ([n_pts, 3], the order and coordinates of upload_grid; sent to the
     context when they differ from the ones it holds) and the scalars alpha and q, differentiable in all three.  Reverse
     mode in xyz is one vertex adjoint render per backward (under vmap, one batched render for all the cotangents); second
-    derivatives raise.
+    derivatives raise.  With ctx.set_option("vertex_exact", 1) the calls the backward and its vmap rule make return the exact
+    vertex adjoint sums: the gradient in xyz is the same bits every run, under either cell order, and a batch's slices are
+    the single calls' (no function of its own: the option is the library's).
     forward_xyz False (the default): forward mode in xyz raises, as it always has - callers and a test rely on that
     refusal, which is why forward mode is a switch and not the new default.  forward_xyz True: a tangent on xyz
     (torch.func.jvp, forward_ad, jacfwd) goes to ONE vertex tangent render, batched under vmap, and is added to the scalar

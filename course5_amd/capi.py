@@ -103,6 +103,12 @@ SIGNATURES = {
     "c5_render_vertex_adjoint_device": [_vp, _vp, _vp],
     "c5_render_vertex_adjoint_batch": [_vp, C.c_int, _fp_t, _dp_t],
     "c5_render_vertex_adjoint_batch_device": [_vp, C.c_int, _vp, _vp],
+    "c5_render_vertex_exact_bounds": [_vp, _fp_t, _ip_t],
+    "c5_render_vertex_exact_bounds_device": [_vp, _vp, _vp],
+    "c5_render_vertex_exact_sums": [_vp, _fp_t, _ip_t, _lp_t],
+    "c5_render_vertex_exact_sums_device": [_vp, _vp, _vp, _vp],
+    "c5_vertex_exact_finish": [_vp, _ip_t, _lp_t, _dp_t],
+    "c5_vertex_exact_finish_device": [_vp, _vp, _vp, _vp],
     "c5_update_points": [_vp, _dp_t, C.c_int64],
     "c5_render_vertex_tangent": [_vp, C.c_int, _dp_t, _fp_t],
     "c5_render_vertex_tangent_device": [_vp, C.c_int, _vp, _vp],
@@ -492,7 +498,9 @@ class Context:
         """The gradient of the frame render() would produce now with respect to the grid's points, weighted by grad_out
         ([local_rows, res_x, 2]: the weights of tau and of I per pixel): float64 [n_pts, 3] in the order and the coordinates
         of upload_grid.  A point welded to another at upload gets 0, its representative the group's sum.  Synchronous;
-        retries by itself.  Not bit-reproducible from run to run (fp64 atomics), like render_adjoint."""
+        retries by itself.  Not bit-reproducible from run to run (fp64 atomics), like render_adjoint - unless
+        set_option("vertex_exact", 1): then the exact vertex adjoint sums, the same bits every run, under either cell order
+        and for any split of the rows (as for the _device and batch forms)."""
         g = self._image(grad_out, "grad_out")
         out = np.zeros((self.n_pts, 3))
         self._check(self.lib.c5_render_vertex_adjoint(self.handle, _fp(g), _dp(out)))
@@ -529,6 +537,79 @@ class Context:
             raise ValueError("grad_xyz must be [K, n_pts, 3] with K >= 1 (or give n = K with raw device pointers)")
         ptrs = self._image_dev(grad_out, k), _device_ptr(grad_xyz, torch.float64, (k, self.n_pts, 3))
         self._check(self.lib.c5_render_vertex_adjoint_batch_device(self.handle, k, *ptrs))
+
+    # -- exact vertex adjoint sums -----------------------------------------------------------------
+    # (set_option("vertex_exact", 1) makes render_vertex_adjoint* return them finished; these are the intermediate results,
+    # for callers who split an image: elementwise max of the exponents, elementwise add of the words - sharding.
+    # combine_vertex_exact - then vertex_exact_finish on any one of the contexts: fit.RowShards.shape_operators)
+    def _slot_exponents(self, e) -> np.ndarray:
+        e = np.asarray(e)
+        if e.dtype != np.int32 or e.shape != (self.n_cells, 12) or not e.flags.c_contiguous:
+            raise ValueError(f"exps must be a contiguous int32 array [{self.n_cells}, 12] (one exponent per cell and slot), "
+                             f"not {e.dtype} {list(e.shape)}")
+        return e
+
+    def _slot_words(self, s) -> np.ndarray:
+        s = np.asarray(s)
+        if s.dtype != np.int64 or s.shape != (self.n_cells, 12, 2) or not s.flags.c_contiguous:
+            raise ValueError(f"sums must be a contiguous int64 array [{self.n_cells}, 12, 2] (two words per cell and slot), "
+                             f"not {s.dtype} {list(s.shape)}")
+        return s
+
+    def render_vertex_exact_bounds(self, grad_out) -> np.ndarray:
+        """The exponents of the exact vertex adjoint sums over the context's rows for the upstream image grad_out
+        ([local_rows, res_x, 2]): int32 [n_cells, 12] in the cell order of upload_grid, a cell's slots [4 faces][3 vertices
+        of the face] (INT32_MIN: no contribution, INT32_MAX: one that is not finite).  Parts of an image combine by
+        elementwise max.  Synchronous; retries by itself."""
+        g = self._image(grad_out, "grad_out")
+        exps = np.zeros((self.n_cells, 12), np.int32)
+        self._check(self.lib.c5_render_vertex_exact_bounds(self.handle, _fp(g), exps.ctypes.data_as(_ip_t)))
+        return exps
+
+    def render_vertex_exact_sums(self, grad_out, exps) -> np.ndarray:
+        """The words of the exact vertex adjoint sums over the context's rows against the given exponents (int32 [n_cells,
+        12]: those of render_vertex_exact_bounds, combined over every part of the image): int64 [n_cells, 12, 2].  Parts
+        of an image combine by elementwise integer add.  C5_ERR_INVALID if a contribution lies beyond its slot's
+        exponent.  Synchronous; retries by itself."""
+        g = self._image(grad_out, "grad_out")
+        e = self._slot_exponents(exps)
+        sums = np.zeros((self.n_cells, 12, 2), np.int64)
+        self._check(self.lib.c5_render_vertex_exact_sums(self.handle, _fp(g), e.ctypes.data_as(_ip_t), sums.ctypes.data_as(_lp_t)))
+        return sums
+
+    def vertex_exact_finish(self, exps, sums) -> np.ndarray:
+        """The gradient the exponents and words stand for (int32 [n_cells, 12], int64 [n_cells, 12, 2]: combined over every
+        part of the image): float64 [n_pts, 3], bit for bit render_vertex_adjoint's under set_option("vertex_exact", 1)
+        over the whole image.  Uses the context's grid, points and view, none of its rows.  Synchronous; retries by itself."""
+        e, s = self._slot_exponents(exps), self._slot_words(sums)
+        out = np.zeros((self.n_pts, 3))
+        self._check(self.lib.c5_vertex_exact_finish(self.handle, e.ctypes.data_as(_ip_t), s.ctypes.data_as(_lp_t), _dp(out)))
+        return out
+
+    def render_vertex_exact_bounds_device(self, grad_out, exps):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (grad_out float32 [local_rows,
+        res_x, 2], exps int32 [n_cells, 12], contiguous) or raw device pointers.  The status comes with the next
+        synchronize()."""
+        import torch
+        ptrs = self._image_dev(grad_out), _device_ptr(exps, torch.int32, (self.n_cells, 12))
+        self._check(self.lib.c5_render_vertex_exact_bounds_device(self.handle, *ptrs))
+
+    def render_vertex_exact_sums_device(self, grad_out, exps, sums):
+        """Asynchronous form on the context's stream: as render_vertex_exact_bounds_device, and sums int64 [n_cells, 12, 2].
+        The status (C5_ERR_INVALID for exponents that are too small included) comes with the next synchronize()."""
+        import torch
+        ptrs = (self._image_dev(grad_out), _device_ptr(exps, torch.int32, (self.n_cells, 12)),
+                _device_ptr(sums, torch.int64, (self.n_cells, 12, 2)))
+        self._check(self.lib.c5_render_vertex_exact_sums_device(self.handle, *ptrs))
+
+    def vertex_exact_finish_device(self, exps, sums, grad_xyz):
+        """Asynchronous form on the context's stream: exps int32 [n_cells, 12], sums int64 [n_cells, 12, 2], grad_xyz float64
+        [n_pts, 3]; torch tensors on this context's GPU, contiguous, or raw device pointers.  The status comes with the next
+        synchronize()."""
+        import torch
+        ptrs = (_device_ptr(exps, torch.int32, (self.n_cells, 12)), _device_ptr(sums, torch.int64, (self.n_cells, 12, 2)),
+                _device_ptr(grad_xyz, torch.float64, (self.n_pts, 3)))
+        self._check(self.lib.c5_vertex_exact_finish_device(self.handle, *ptrs))
 
     # -- vertex tangent render ---------------------------------------------------------------------
     def render_vertex_tangent(self, d_xyz) -> np.ndarray:

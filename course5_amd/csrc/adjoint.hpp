@@ -246,6 +246,41 @@ void launch_vertex_resolve(hipStream_t s, const ResolveParams& r, const float2* 
 void launch_vertex_finish(hipStream_t s, const MotionGeometry& geo, int64_t n_cells, const double* face_w, double* grad_view,
                           int64_t n_pts, const RotationList& R, double* grad_xyz);
 
+// ---- exact vertex adjoint sums ("vertex_exact", c5_render_vertex_exact_*): face_w's twelve slots per cell in the
+// fixed-point format of exact_sum.hpp, then fixed arithmetic per cell and a gather per point in a fixed order.  240 bytes
+// per cell for exponents and words, 96 for the per-cell triples, in device order.
+struct VertexExactSums {
+    int32_t* exps;         // [n_cells][12] the exponent of every slot's contributions: pass E's atomicMax
+    long long* words;      // [n_cells][12][2] {s1, s0} per slot: pass S's integer atomicAdd
+    unsigned* misfits;     // += contributions pass S found beyond their slot's exponent (added nowhere)
+    int32_t word_bits;     // m of the WHOLE image (c5_set_image), not of the context's rows
+    int32_t keep_entries;  // pass S, the walk: 1 leaves the entry heads in place (another image follows); 0 hands them back cleared
+};
+
+// exps to "no contribution", words to zero and / or *misfits to zero
+void launch_vertex_exact_clear(hipStream_t s, const VertexExactSums& x, int64_t n_cells, bool exps, bool words, bool misfits);
+// pass E (sums false: leaves the entry heads in place) or pass S of vertex_walk's walk; both need launch_adjoint_walk(.., 1)
+// first and read v.w, v.geo, v.grad_out and v.lambda only
+void launch_vertex_exact_walk(hipStream_t s, const VertexParams& v, const VertexExactSums& x, bool sums);
+// the same over bin_sort_resolve's lists (sorts them in place, as launch_vertex_resolve)
+void launch_vertex_exact_resolve(hipStream_t s, const ResolveParams& r, const float2* grad_out, const VertexExactSums& x, bool sums);
+// the caller's cell order -> the device's: x.exps[i][.] = exps[perm[i]][.] and x.words[i][.] = sums[perm[i]][.] (perm
+// nullptr: the identity; exps or sums null: that block stays), and back
+void launch_vertex_exact_gather(hipStream_t s, const int32_t* exps, const int64_t* sums, const int32_t* perm, int64_t n_cells,
+                                const VertexExactSums& x);
+void launch_vertex_exact_emit(hipStream_t s, const VertexExactSums& x, const int32_t* perm, int64_t n_cells, int32_t* exps, int64_t* sums);
+// the point -> (cell, local vertex) incidence as CSR: inc_idx[inc_ptr[v] .. inc_ptr[v + 1]) = 4 * (device cell) + (vertex),
+// ascending in the CALLER's cell index
+struct VertexIncidence {
+    const int32_t* ptr;  // [n_pts + 1]
+    const int32_t* idx;  // [4 n_cells]
+};
+// words -> face_w (device order, one rounding per slot), face_w -> cell_triples [n_cells][4][3] (plain stores; separately
+// rounded products and sums, a vertex's faces in ascending order), then per point the triples of its incidence list added
+// in the list's order and grad_xyz[v] = M^T of that sum (a point of no cell, and a sum of zeros: exact +0.0)
+void launch_vertex_exact_finish(hipStream_t s, const VertexExactSums& x, const MotionGeometry& geo, int64_t n_cells, double* face_w,
+                                double* cell_triples, const VertexIncidence& inc, int64_t n_pts, const RotationList& R, double* grad_xyz);
+
 // ---- batched vertex adjoint (c5_render_vertex_adjoint_batch*): one walk per ray for up to kc upstream images (kc: the
 // chunk width, 4 or 8), after ONE pass 1
 

@@ -242,7 +242,8 @@ void c5_destroy(c5_context* ctx) {
                             &ctx->adj_sticky, &ctx->adj_grad, &ctx->adj_perm, &ctx->tan_dir,
                             &ctx->bat_dirs, &ctx->bat_grad, &ctx->gn_g, &ctx->gn_spare, &ctx->deriv_io,
                             &ctx->scal_stats, &ctx->vtx_face, &ctx->vtx_grad, &ctx->vtx_vel, &ctx->rm_count, &ctx->hvp_lambda_dot,
-                            &ctx->adj_exact, &ctx->vtx_bat_face, &ctx->vtx_bat_grad};
+                            &ctx->adj_exact, &ctx->vtx_bat_face, &ctx->vtx_bat_grad, &ctx->vtx_exact, &ctx->vtx_triples,
+                            &ctx->vtx_inc};
     if (ctx->host_sticky) (void)hipHostFree(ctx->host_sticky);
     if (ctx->adj_status) (void)hipHostFree(ctx->adj_status);
     if (ctx->scal_host) (void)hipHostFree(ctx->scal_host);
@@ -568,6 +569,9 @@ int c5_set_option(c5_context* ctx, const char* name, double value) {
     } else if (n == "exact_sums") {
         if (value != 0 && value != 1) return fail(ctx, C5_ERR_INVALID, "exact_sums must be 0 (fp64 atomics) or 1");
         ctx->exact_sums = static_cast<int>(value);
+    } else if (n == "vertex_exact") {
+        if (value != 0 && value != 1) return fail(ctx, C5_ERR_INVALID, "vertex_exact must be 0 (fp64 atomics) or 1");
+        ctx->vertex_exact = static_cast<int>(value);
     } else if (n == "split_tilt_x" || n == "split_tilt_y") {  // testing: tilt of a forced split's planes
         if (!(std::fabs(value) < 64.0)) return fail(ctx, C5_ERR_INVALID, "split tilt out of range");
         (n == "split_tilt_x" ? ctx->split_tilt_x : ctx->split_tilt_y) = value;

@@ -301,6 +301,12 @@ struct c5_context {
     // batched vertex adjoint (c5_render_vertex_adjoint_batch*): allocated at the first batched call only
     c5api::DeviceBuffer vtx_bat_face;  // [n_cells][width][4][3] fp64, device order: vtx_face per image of a chunk
     c5api::DeviceBuffer vtx_bat_grad;  // [n_pts][3][width] fp64: vtx_grad per image of a chunk, the images of a component side by side
+    // exact vertex adjoint sums ("vertex_exact", c5_render_vertex_exact_*): allocated at the first exact vertex call only
+    int vertex_exact = 0;              // "vertex_exact": c5_render_vertex_adjoint* and its batch return the exact sums
+    c5api::DeviceBuffer vtx_exact;     // [n_cells][12][2] int64 words, [n_cells][12] int32 exponents (device order), the misfit word
+    c5api::DeviceBuffer vtx_triples;   // [n_cells][4][3] fp64, device order: a cell's share of its four vertices' view-space gradient
+    c5api::DeviceBuffer vtx_inc;       // point -> (cell, vertex) incidence, CSR: int32 [n_pts + 1] offsets, int32 [4 n_cells] entries
+    uint64_t vtx_inc_serial = ~uint64_t{0};  // ... for the grid of this upload (kept across c5_update_points)
     // vertex tangent (c5_render_vertex_tangent*): allocated at the first call only
     c5api::DeviceBuffer vtx_vel;   // [n_pts][width][3] fp64: the points' view-space velocities (vertex_velocity)
     // ray matrix (c5_ray_matrix_*): allocated at the first call only (the scan's scratch is bin_sort_resolve's scratch64)

@@ -446,6 +446,84 @@ __device__ __forceinline__ void reduce_faces(const double* stage, bool emit, int
     __syncthreads();  // (the rows are read before the next step writes them)
 }
 
+// The staged reductions of the exact vertex adjoint ("vertex_exact"; one wavefront per workgroup): reduce_rows' ballot
+// loop over other element types.  Pass E stages twelve int32 exponents per lane and takes their max per cell; pass S
+// stages 24 int64 words per lane - its six values already rounded onto their grids - and adds them per cell as integers.
+// Max and integer add commute: what a cell receives does not depend on which rays share a wavefront, or on the order.
+template <class T, int kV>
+struct WordStage {
+    static constexpr int kRow = kV + 1;  // (row pitch: an odd number of elements)
+    static constexpr int kWords = 65 * kRow;
+};
+
+template <class T, int kV>  // once per kernel, before the first step: row 64 holds the reduction's neutral element
+__device__ __forceinline__ void word_stage_begin(T* stage, int lane, T neutral) {
+    if (lane < WordStage<T, kV>::kRow) stage[64 * WordStage<T, kV>::kRow + lane] = neutral;
+}
+template <class T, int kV>
+__device__ __forceinline__ T* word_stage_row(T* stage, int lane) { return stage + lane * WordStage<T, kV>::kRow; }
+
+// pass E's step, by every lane: per distinct cell the max of the member rows' twelve exponents, one atomicMax per slot
+// (twelve in one instruction, to one 48-byte stretch); a slot nobody touched (kNone, INT32_MIN: the neutral) is left alone
+__device__ __forceinline__ void reduce_rows_max(const int* stage, bool emit, int here, int lane, int neutral, int* __restrict__ dst) {
+    constexpr int kV = 12, kRow = WordStage<int, kV>::kRow;
+    __syncthreads();  // (one wavefront: the rows are visible to every lane)
+    unsigned long long m = __builtin_amdgcn_ballot_w64(emit);
+    while (m != 0ull) {
+        const int leader = __builtin_ctzll(m);
+        const int lc = __builtin_amdgcn_readlane(here, leader);
+        const unsigned long long members = __builtin_amdgcn_ballot_w64(emit && here == lc);
+        if (lane < kV) {
+            int s = neutral;
+            for (unsigned long long rows = members; rows != 0ull;) {
+                const int b0 = __builtin_ctzll(rows);
+                rows &= rows - 1;
+                const int b1 = rows ? __builtin_ctzll(rows) : 64;
+                rows &= rows - 1;
+                const int b2 = rows ? __builtin_ctzll(rows) : 64;
+                rows &= rows - 1;
+                const int b3 = rows ? __builtin_ctzll(rows) : 64;
+                rows &= rows - 1;
+                s = max(s, max(max(stage[b0 * kRow + lane], stage[b1 * kRow + lane]), max(stage[b2 * kRow + lane], stage[b3 * kRow + lane])));
+            }
+            if (s != neutral) atomicMax(dst + static_cast<size_t>(lc) * kV + lane, s);
+        }
+        m &= ~members;
+    }
+    __syncthreads();  // (the rows are read before the next step writes them)
+}
+
+// pass S's step, by every lane: per distinct cell the int64 sums of the member rows' 24 words, one no-return 64-bit
+// integer atomicAdd per word (24 in one instruction, to one 192-byte stretch)
+__device__ __forceinline__ void reduce_rows_words(const long long* stage, bool emit, int here, int lane, long long* __restrict__ dst) {
+    constexpr int kV = 24, kRow = WordStage<long long, kV>::kRow;
+    __syncthreads();  // (one wavefront: the rows are visible to every lane)
+    unsigned long long m = __builtin_amdgcn_ballot_w64(emit);
+    while (m != 0ull) {
+        const int leader = __builtin_ctzll(m);
+        const int lc = __builtin_amdgcn_readlane(here, leader);
+        const unsigned long long members = __builtin_amdgcn_ballot_w64(emit && here == lc);
+        if (lane < kV) {
+            unsigned long long s = 0ull;  // (unsigned: the sum of two's-complement words, wrap-free by the format's headroom)
+            for (unsigned long long rows = members; rows != 0ull;) {
+                const int b0 = __builtin_ctzll(rows);
+                rows &= rows - 1;
+                const int b1 = rows ? __builtin_ctzll(rows) : 64;
+                rows &= rows - 1;
+                const int b2 = rows ? __builtin_ctzll(rows) : 64;
+                rows &= rows - 1;
+                const int b3 = rows ? __builtin_ctzll(rows) : 64;
+                rows &= rows - 1;
+                s += (static_cast<unsigned long long>(stage[b0 * kRow + lane]) + static_cast<unsigned long long>(stage[b1 * kRow + lane])) +
+                     (static_cast<unsigned long long>(stage[b2 * kRow + lane]) + static_cast<unsigned long long>(stage[b3 * kRow + lane]));
+            }
+            if (s != 0ull) atomicAdd(reinterpret_cast<unsigned long long*>(dst) + static_cast<size_t>(lc) * kV + lane, s);
+        }
+        m &= ~members;
+    }
+    __syncthreads();  // (the rows are read before the next step writes them)
+}
+
 }  // namespace adj
 
 // workgroups of a walk kernel: one wavefront per 8x8 pixel tile (0: no pixel)

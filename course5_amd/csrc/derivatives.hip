@@ -562,9 +562,169 @@ int enqueue_motion(c5_context* ctx, int n, const double* fields, float2* out) {
     return commit_derivative(ctx, "motion tangent");
 }
 
+// ---- exact vertex adjoint sums ("vertex_exact", c5_render_vertex_exact_*)
+
+// The exact vertex sums' buffer over the context's cells - 240 bytes per cell (192 of words, 48 of exponents) and the
+// misfit word, allocated here at the first exact vertex call - with the word width of the WHOLE image (c5_set_image).
+int vertex_exact_sums(c5_context* ctx, c5::VertexExactSums& x) {
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
+    const int m = c5::exact::word_bits(static_cast<int64_t>(ctx->im.res_x) * ctx->im.res_y);
+    if (m < c5::exact::kMinWordBits)
+        return fail(ctx, C5_ERR_INVALID, "exact sums: an image of %d x %d pixels leaves %d bits per word", ctx->im.res_x, ctx->im.res_y, m);
+    C5_HIP(ctx, ctx->vtx_exact.ensure(n_cells * 240 + 8));
+    x = c5::VertexExactSums{};
+    x.words = ctx->vtx_exact.as<long long>();
+    x.exps = reinterpret_cast<int32_t*>(x.words + 24 * n_cells);  // (192 n_cells bytes on: 16-byte aligned)
+    x.misfits = reinterpret_cast<unsigned*>(x.exps + 12 * n_cells);
+    x.word_bits = m;
+    return C5_OK;
+}
+
+// The point -> (cell, local vertex) incidence table of the grid on the device, built by the host at the first exact vertex
+// call after an upload: per point its entries 4 * (device cell) + (vertex) in ascending order of the CALLER's cell index,
+// so that the per-point sums do not depend on "cell_order".  Connectivity only: c5_update_points keeps it.  Cells name
+// the representatives of welded points: the others' lists are empty.
+int vertex_incidence(c5_context* ctx, c5::VertexIncidence& inc) {
+    const int64_t n_pts = ctx->n_pts, n_cells = ctx->n_cells;
+    if (ctx->vtx_inc_serial != ctx->grid_serial || !ctx->vtx_inc.ptr) {
+        const std::vector<int32_t>& cv = ctx->host_cell_vert;  // (device order)
+        std::vector<int32_t> tab(static_cast<size_t>(n_pts + 1 + 4 * n_cells), 0);
+        int32_t* const ptr = tab.data();
+        int32_t* const idx = ptr + n_pts + 1;
+        for (int64_t i = 0; i < 4 * n_cells; ++i) ++ptr[cv[static_cast<size_t>(i)] + 1];
+        for (int64_t p = 0; p < n_pts; ++p) ptr[p + 1] += ptr[p];
+        std::vector<int32_t> at(ptr, ptr + n_pts), of_caller;  // where a point's next entry goes; caller's index -> the device's
+        if (!ctx->cell_perm.empty()) {
+            of_caller.resize(static_cast<size_t>(n_cells));
+            for (int64_t d = 0; d < n_cells; ++d) of_caller[static_cast<size_t>(ctx->cell_perm[static_cast<size_t>(d)])] = static_cast<int32_t>(d);
+        }
+        for (int64_t c = 0; c < n_cells; ++c) {
+            const int64_t d = of_caller.empty() ? c : of_caller[static_cast<size_t>(c)];
+            for (int k = 0; k < 4; ++k) idx[at[static_cast<size_t>(cv[static_cast<size_t>(4 * d + k)])]++] = static_cast<int32_t>(4 * d + k);
+        }
+        C5_HIP(ctx, ctx->vtx_inc.ensure(tab.size() * sizeof(int32_t)));
+        C5_HIP(ctx, hipMemcpy(ctx->vtx_inc.ptr, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        ctx->vtx_inc_serial = ctx->grid_serial;
+    }
+    inc.ptr = ctx->vtx_inc.as<int32_t>();
+    inc.idx = inc.ptr + n_pts + 1;
+    return C5_OK;
+}
+
+// The exact passes of the vertex adjoint over the view for one upstream image - exact_passes with the vertex kernels:
+// pass 1 (unless Lambda is there: `have_lambda`), pass E into x.exps (`bounds`: cleared here first) and pass S against
+// x.exps into x.words (`sums`: cleared here first, the misfit word with them where `first`); keep: the walk's pass S
+// leaves the entry heads in place (another image follows).
+int vertex_exact_passes(c5_context* ctx, const DerivativeView& v, c5::VertexExactSums x, const float2* grad_out, bool bounds, bool sums,
+                        bool have_lambda, bool keep, bool first) {
+    c5::launch_vertex_exact_clear(v.s, x, ctx->n_cells, bounds, sums, sums && first);
+    if (v.bin_sort) {
+        if (bounds) c5::launch_vertex_exact_resolve(v.s, v.r, grad_out, x, false);
+        if (sums) c5::launch_vertex_exact_resolve(v.s, v.r, grad_out, x, true);
+        return C5_OK;
+    }
+    c5::AdjointParams ap;
+    int rc = adjoint_params(ctx, v, ap);
+    if (rc) return rc;
+    if (!have_lambda) c5::launch_adjoint_walk(v.s, ap, 1);
+    c5::VertexParams vp{};
+    vp.w = v.w;
+    vp.geo = v.geo;
+    vp.grad_out = grad_out;
+    vp.lambda = ap.lambda;
+    if (bounds) c5::launch_vertex_exact_walk(v.s, vp, x, false);
+    x.keep_entries = keep ? 1 : 0;
+    if (sums) {
+        c5::launch_vertex_exact_walk(v.s, vp, x, true);
+        if (!keep) ctx->slots[0].head_clean = true;  // (pass S hands every head back cleared)
+    }
+    return C5_OK;
+}
+
+// Steps 1 (the finish of the words) to 4 of the exact vertex adjoint on x's exponents and words (device order): face_w,
+// the per-cell triples, the per-point gather over the incidence table and the view's M^T, into grad_xyz [n_pts][3].
+int vertex_exact_finish(c5_context* ctx, const DerivativeView& v, const c5::VertexExactSums& x, double* grad_xyz) {
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
+    C5_HIP(ctx, ctx->vtx_face.ensure(12 * n_cells * sizeof(double)));
+    C5_HIP(ctx, ctx->vtx_triples.ensure(12 * n_cells * sizeof(double)));
+    c5::VertexIncidence inc;
+    int rc = vertex_incidence(ctx, inc);
+    if (rc) return rc;
+    c5::launch_vertex_exact_finish(v.s, x, v.geo, ctx->n_cells, ctx->vtx_face.as<double>(), ctx->vtx_triples.as<double>(), inc, ctx->n_pts,
+                                   ctx->view, grad_xyz);
+    return C5_OK;
+}
+
+// commit_exact for the vertex sums' misfit word
+int commit_vertex_exact(c5_context* ctx, const c5::VertexExactSums& x, const char* what) {
+    c5::ExactSums words{};
+    words.misfits = x.misfits;
+    return commit_exact(ctx, words, what);
+}
+
+// "vertex_exact" 1: n upstream images -> grad_xyz [n][n_pts][3], every image through passes E and S and the finish, one
+// after the other; pass 1 runs once for all of them.  "vertex_merge" has no say here.
+int vertex_exact_images(c5_context* ctx, const DerivativeView& v, int n, const float2* grad_out, double* grad_xyz, const char* what) {
+    c5::VertexExactSums x;
+    int rc = vertex_exact_sums(ctx, x);
+    const int64_t n_pts = ctx->n_pts;
+    for (int j = 0; j < n && !rc; ++j) {
+        rc = vertex_exact_passes(ctx, v, x, grad_out + j * v.n_px, true, true, j > 0, j + 1 < n, j == 0);
+        if (!rc) rc = vertex_exact_finish(ctx, v, x, grad_xyz + 3 * j * n_pts);
+    }
+    return rc ? rc : commit_vertex_exact(ctx, x, what);
+}
+
+// c5_render_vertex_exact_bounds: pass 1 and pass E over the context's rows; the exponents in the caller's cell order
+int enqueue_vertex_exact_bounds(c5_context* ctx, const float2* grad_out, int32_t* exps) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc || v.no_cells) return rc;
+    c5::VertexExactSums x;
+    rc = vertex_exact_sums(ctx, x);
+    if (!rc) rc = vertex_exact_passes(ctx, v, x, grad_out, true, false, false, false, false);
+    if (rc) return rc;
+    c5::launch_vertex_exact_emit(v.s, x, v.perm, ctx->n_cells, exps, nullptr);
+    return commit_derivative(ctx, "vertex exact bounds");
+}
+
+// c5_render_vertex_exact_sums: the caller's exponents into device order, pass 1 and pass S against them; the words in the
+// caller's cell order
+int enqueue_vertex_exact_sums(c5_context* ctx, const float2* grad_out, const int32_t* exps, int64_t* sums) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc || v.no_cells) return rc;
+    c5::VertexExactSums x;
+    rc = vertex_exact_sums(ctx, x);
+    if (rc) return rc;
+    c5::launch_vertex_exact_gather(v.s, exps, nullptr, v.perm, ctx->n_cells, x);
+    rc = vertex_exact_passes(ctx, v, x, grad_out, false, true, false, false, true);
+    if (rc) return rc;
+    c5::launch_vertex_exact_emit(v.s, x, v.perm, ctx->n_cells, nullptr, sums);
+    return commit_vertex_exact(ctx, x, "vertex exact sums");
+}
+
+// c5_vertex_exact_finish: the per-view setup (the finish wants the points in view space), the caller's exponents and words
+// into device order, and the finish.  No walk: the entry lists the setup built stay unused.
+int enqueue_vertex_exact_finish(c5_context* ctx, const int32_t* exps, const int64_t* sums, double* grad_xyz) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    if (v.no_cells) {  // (solids only: no point the frame depends on)
+        if (ctx->n_pts > 0) C5_HIP(ctx, hipMemsetAsync(grad_xyz, 0, 3 * static_cast<size_t>(ctx->n_pts) * sizeof(double), v.s));
+        return C5_OK;
+    }
+    c5::VertexExactSums x;
+    rc = vertex_exact_sums(ctx, x);
+    if (rc) return rc;
+    c5::launch_vertex_exact_gather(v.s, exps, sums, v.perm, ctx->n_cells, x);
+    rc = vertex_exact_finish(ctx, v, x, grad_xyz);
+    return rc ? rc : commit_derivative(ctx, "vertex exact finish");
+}
+
 // The vertex adjoint: the per-face weights and the view-space gradient zeroed, the adjoint's pass 1 and vertex_walk (or
 // vertex_resolve over bin_sort_resolve's lists), then vertex_finish into the caller's [n_pts][3] (the caller's point
-// order is the device's: only the cells are reordered).
+// order is the device's: only the cells are reordered).  With "vertex_exact": the exact sums (vertex_exact_images).
 int enqueue_vertex_adjoint(c5_context* ctx, const float2* grad_out, double* grad_xyz) {
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
@@ -574,6 +734,7 @@ int enqueue_vertex_adjoint(c5_context* ctx, const float2* grad_out, double* grad
         if (n_pts > 0) C5_HIP(ctx, hipMemsetAsync(grad_xyz, 0, 3 * n_pts * sizeof(double), v.s));
         return C5_OK;
     }
+    if (ctx->vertex_exact) return vertex_exact_images(ctx, v, 1, grad_out, grad_xyz, "vertex adjoint");
     C5_HIP(ctx, ctx->vtx_face.ensure(12 * n_cells * sizeof(double)));
     C5_HIP(ctx, ctx->vtx_grad.ensure(3 * n_pts * sizeof(double)));
     double* const face_w = ctx->vtx_face.as<double>();
@@ -617,6 +778,8 @@ int enqueue_vertex_adjoint_batch(c5_context* ctx, int n, const float2* grad_out,
         if (n_pts > 0) C5_HIP(ctx, hipMemsetAsync(grad_xyz, 0, 3 * n * n_pts * sizeof(double), v.s));
         return C5_OK;
     }
+    // "vertex_exact": ONE pass 1, then the single exact path image by image - every slice bit for bit the single call's
+    if (ctx->vertex_exact) return vertex_exact_images(ctx, v, n, grad_out, grad_xyz, "vertex adjoint batch");
     if (v.bin_sort) {
         C5_HIP(ctx, ctx->vtx_face.ensure(12 * n_cells * sizeof(double)));
         C5_HIP(ctx, ctx->vtx_grad.ensure(3 * n_pts * sizeof(double)));
@@ -863,14 +1026,15 @@ int finish_adjoint(c5_context* ctx) {
     if (misfits)
         return fail(ctx, C5_ERR_INVALID,
                     "%s: %u contributions lie beyond their cell's exponent and were added nowhere: the exponents given are too small "
-                    "(take the elementwise max of c5_render_exact_bounds over every part of the image)", ctx->adj_what, misfits);
+                    "(take the elementwise max of c5_render_exact_bounds - the vertex sums: c5_render_vertex_exact_bounds - over "
+                    "every part of the image)", ctx->adj_what, misfits);
     return C5_OK;
 }
 }  // namespace c5api
 
 namespace {
 
-// What the thirty-four derivative entry points check before anything else, in this order: the context; a batch's size; the
+// What the forty derivative entry points check before anything else, in this order: the context; a batch's size; the
 // call's own pointers (`required_ok`, and `per_cell_ok` where the grid has cells); no c5_render_host_async frame
 // outstanding; and for the host-pointer forms the image, after which the device is bound.
 struct DerivativeCall {
@@ -1252,6 +1416,66 @@ int c5_render_vertex_adjoint_batch(c5_context* ctx, int n_imgs, const float* gra
                   {nullptr, grad_xyz_host, 3 * static_cast<size_t>(n_imgs) * static_cast<size_t>(ctx->n_pts) * sizeof(double)}};
     return run_staged(ctx, "vertex adjoint batch", b,
                       [&] { return enqueue_vertex_adjoint_batch(ctx, n_imgs, b[0].as<const float2>(), b[1].as<double>()); });
+}
+
+// The exact vertex adjoint's staged calls ("vertex_exact" makes c5_render_vertex_adjoint* return them finished).
+int c5_render_vertex_exact_bounds_device(c5_context* ctx, const void* grad_out_dev, void* exps_dev) {
+    int rc = check_derivative(ctx, {"c5_render_vertex_exact_bounds", false, 1, nullptr, grad_out_dev != nullptr, exps_dev != nullptr,
+                                    "null upstream image or exponent pointer"});
+    if (rc) return rc;
+    return enqueue_vertex_exact_bounds(ctx, static_cast<const float2*>(grad_out_dev), static_cast<int32_t*>(exps_dev));
+}
+
+int c5_render_vertex_exact_bounds(c5_context* ctx, const float* grad_out_host, int32_t* exps_host) {
+    int rc = check_derivative(ctx, {"c5_render_vertex_exact_bounds", true, 1, nullptr, grad_out_host != nullptr, exps_host != nullptr,
+                                    "null upstream image or exponent pointer"});
+    if (rc) return rc;
+    Staged b[] = {{grad_out_host, nullptr, image_bytes(ctx)},
+                  {nullptr, exps_host, 12 * static_cast<size_t>(ctx->n_cells) * sizeof(int32_t)}};
+    return run_staged(ctx, "vertex exact bounds", b,
+                      [&] { return enqueue_vertex_exact_bounds(ctx, b[0].as<const float2>(), b[1].as<int32_t>()); });
+}
+
+int c5_render_vertex_exact_sums_device(c5_context* ctx, const void* grad_out_dev, const void* exps_dev, void* sums_dev) {
+    int rc = check_derivative(ctx, {"c5_render_vertex_exact_sums", false, 1, nullptr, grad_out_dev != nullptr, exps_dev && sums_dev,
+                                    "null upstream image, exponent or sums pointer"});
+    if (rc) return rc;
+    return enqueue_vertex_exact_sums(ctx, static_cast<const float2*>(grad_out_dev), static_cast<const int32_t*>(exps_dev),
+                                     static_cast<int64_t*>(sums_dev));
+}
+
+int c5_render_vertex_exact_sums(c5_context* ctx, const float* grad_out_host, const int32_t* exps_host, int64_t* sums_host) {
+    int rc = check_derivative(ctx, {"c5_render_vertex_exact_sums", true, 1, nullptr, grad_out_host != nullptr, exps_host && sums_host,
+                                    "null upstream image, exponent or sums pointer"});
+    if (rc) return rc;
+    const size_t slots = 12 * static_cast<size_t>(ctx->n_cells);
+    Staged b[] = {{grad_out_host, nullptr, image_bytes(ctx)},
+                  {exps_host, nullptr, slots * sizeof(int32_t)},
+                  {nullptr, sums_host, slots * 2 * sizeof(int64_t)}};
+    return run_staged(ctx, "vertex exact sums", b, [&] {
+        return enqueue_vertex_exact_sums(ctx, b[0].as<const float2>(), b[1].as<const int32_t>(), b[2].as<int64_t>());
+    });
+}
+
+int c5_vertex_exact_finish_device(c5_context* ctx, const void* exps_dev, const void* sums_dev, void* grad_xyz_dev) {
+    int rc = check_derivative(ctx, {"c5_vertex_exact_finish", false, 1, nullptr, grad_xyz_dev != nullptr, exps_dev && sums_dev,
+                                    "null exponent, sums or gradient pointer"});
+    if (rc) return rc;
+    return enqueue_vertex_exact_finish(ctx, static_cast<const int32_t*>(exps_dev), static_cast<const int64_t*>(sums_dev),
+                                       static_cast<double*>(grad_xyz_dev));
+}
+
+int c5_vertex_exact_finish(c5_context* ctx, const int32_t* exps_host, const int64_t* sums_host, double* grad_xyz_host) {
+    int rc = check_derivative(ctx, {"c5_vertex_exact_finish", true, 1, nullptr, grad_xyz_host != nullptr, exps_host && sums_host,
+                                    "null exponent, sums or gradient pointer"});
+    if (rc) return rc;
+    const size_t slots = 12 * static_cast<size_t>(ctx->n_cells);
+    Staged b[] = {{exps_host, nullptr, slots * sizeof(int32_t)},
+                  {sums_host, nullptr, slots * 2 * sizeof(int64_t)},
+                  {nullptr, grad_xyz_host, 3 * static_cast<size_t>(ctx->n_pts) * sizeof(double)}};
+    return run_staged(ctx, "vertex exact finish", b, [&] {
+        return enqueue_vertex_exact_finish(ctx, b[0].as<const int32_t>(), b[1].as<const int64_t>(), b[2].as<double>());
+    });
 }
 
 int c5_render_vertex_tangent_device(c5_context* ctx, int n_dirs, const void* d_xyz_dev, void* out_dev) {

@@ -22,9 +22,13 @@
 // The vertex adjoint (c5_render_vertex_adjoint*), the motion tangent's reverse mode per grid point, its batch over K
 // upstream images (c5_render_vertex_adjoint_batch*) and the vertex tangent (c5_render_vertex_tangent*), the operator it is
 // the transpose of: their blocks further down.  The vertex adjoint's sums, single and batched, are fp64 atomics
-// (global_atomic_add_f64: -munsafe-fp-atomics, build.py), added in arrival order: NOT bit-reproducible.
+// (global_atomic_add_f64: -munsafe-fp-atomics, build.py), added in arrival order: NOT bit-reproducible - unless
+// "vertex_exact" is on: then the exact vertex adjoint sums' kernels run instead (their block below the vertex adjoint's).
+#include <type_traits>
+
 #include "deriv_faces.hpp"
 #include "deriv_lists.hpp"
+#include "exact_sum.hpp"
 
 namespace c5 {
 
@@ -328,6 +332,312 @@ __global__ __launch_bounds__(256) void vertex_finish_points(const double* __rest
     if (i >= n_pts) return;
     double gx = grad_view[3 * i], gy = grad_view[3 * i + 1], gz = grad_view[3 * i + 2];
     adj::rotate_linear<true>(R, gx, gy, gz);
+    grad_xyz[3 * i] = gx;
+    grad_xyz[3 * i + 1] = gy;
+    grad_xyz[3 * i + 2] = gz;
+}
+
+// ---- exact vertex adjoint sums ("vertex_exact", c5_render_vertex_exact_*) --------------------------------------------------
+// The vertex adjoint with no step that depends on an order of arrival.  A segment's six contributions are the doubles
+// vertex_walk stages (+G lambda to the exit face's slots, -G lambda to the entry face's: the same G, the same
+// cell_faces_bary, one rounding each); they are summed per (cell, slot) in the fixed-point format of exact_sum.hpp - a ray
+// crosses a cell at most once and its two faces differ, so a slot receives at most one contribution per ray and the
+// format's headroom holds as it does for the scalar sums.
+//   adjoint_walk<1>             Lambda per pixel, as for the adjoint.
+//   vertex_exact_walk<false>    pass E: vertex_walk<true>'s frame; per step a lane stages the exponents of its twelve values
+//                               (kNone for the six slots it does not touch), reduce_rows_max takes the max per cell and
+//                               slot into exps[cell][12].  Leaves the entry heads in place.
+//   vertex_exact_walk<true>     pass S: the same walk again.  A lane loads the exponents of its six slots, rounds its six
+//                               values onto their grids (exact::quantise: the only rounding) before any cross-lane work
+//                               and stages 24 int64 words;
+//                               reduce_rows_words adds them per cell into words[cell][12][2].  A value beyond its slot's
+//                               exponent is added nowhere and counted in *misfits.
+//   vertex_exact_resolve<.>     the same two over bin_sort_resolve's lists: six atomicMax or twelve integer adds per segment.
+//   vertex_exact_face_w         face_w[cell][slot] = exact::finish of the slot's words: one rounding.
+//   vertex_exact_cells          per cell and local vertex the triple (sum -gx w, sum -gy w, sum w) over the faces holding
+//                               the vertex, in ascending order of the face; products and sums rounded separately; plain
+//                               stores into [n_cells][4][3].  Edge-on faces and zero weights are skipped, as in
+//                               vertex_finish_cells.
+//   vertex_exact_points         per point the triples of its (cell, vertex) incidences added in the list's order -
+//                               ascending in the caller's cell index (derivatives.hip builds the list) - then M^T.
+//   vertex_exact_clear / _gather / _emit   the staged calls' traffic between the caller's cell order and the device's.
+
+namespace adj {
+
+// the exponents of the three slots of face f among a cell's twelve (selects: no register is indexed)
+// a product and a sum that round by themselves, whatever stands around them (__dmul_rn / __dadd_rn are plain operators in
+// a header compiled with contraction on: the pragma takes the permission away from these two)
+__device__ __forceinline__ double mul_alone(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ double add_alone(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+// one face's three values against the exact sums, by the lane itself (the resolve twins): pass E's atomicMax or pass S's
+// integer adds
+template <bool SUMS>
+__device__ __forceinline__ void exact_scatter_face(const VertexExactSums& X, int cell, double g, const FaceBary& fb, unsigned& bad) {
+    const double l[3] = {fb.l0, fb.l1, fb.l2};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double v = mul_alone(g, l[k]);
+        const size_t slot = 12 * static_cast<size_t>(cell) + 3 * fb.f + k;
+        if (!SUMS) {
+            const int32_t e = exact::exponent_of(v);
+            if (e != exact::kNone) atomicMax(X.exps + slot, e);
+        } else {
+            const int32_t e = X.exps[slot];
+            if (e == exact::kNotFinite) continue;  // (the slot stays NaN whatever is added: its words are not looked at)
+            int64_t k1, k0;
+            if (!exact::quantise(v, e, X.word_bits, k1, k0)) {
+                ++bad;
+                continue;
+            }
+            unsigned long long* const w = reinterpret_cast<unsigned long long*>(X.words) + 2 * slot;
+            if (k1) atomicAdd(w, static_cast<unsigned long long>(k1));
+            if (k0) atomicAdd(w + 1, static_cast<unsigned long long>(k0));
+        }
+    }
+}
+
+}  // namespace adj
+
+// vertex_walk<true>'s frame.  SUMS false: pass E; true: pass S.
+template <bool SUMS>
+__global__ __launch_bounds__(64) void vertex_exact_walk(VertexParams A, VertexExactSums X) {
+    using namespace adj;
+    using Word = typename std::conditional<SUMS, long long, int>::type;
+    constexpr int kV = SUMS ? 24 : 12;
+    __shared__ Word stage[WordStage<Word, kV>::kWords];
+    const WalkParams& P = A.w;
+    Ray r;
+    const int lane = r.lane;
+    word_stage_begin<Word, kV>(stage, lane, SUMS ? Word(0) : Word(exact::kNone));
+    double lam = 0.0, lam_total = 0.0, I = 0.0, g_tau = 0.0, g_I = 0.0;
+    unsigned bad = 0;
+
+    const EntryHead ent = ray_begin(r, P, [&] {
+        const float2 g = A.grad_out[r.lp];
+        g_tau = g.x;
+        g_I = g.y;
+        lam_total = A.lambda[r.lp];
+        return g_tau != 0.0 || g_I != 0.0;
+    });
+
+    CellRegs cur;
+    int4 cv = make_int4(0, 0, 0, 0);
+    if (r.cell >= 0) {
+        load_cell(cur, P.xrec, r.cell);
+        cv = A.geo.cell_vert[r.cell];
+    }
+
+    // wave-uniform loop (the reduction wants every lane): a lane whose ray has ended takes part with nothing to add
+    for (;;) {
+        const bool live = r.cell >= 0;
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        const int here = r.cell;
+        bool emit = false;
+        if (live) {
+            double p[4][3];
+            load_vertices(A.geo, cv, p);
+            double dz, carry_next;
+            const int nb = ray_step(r, P, ent, cur, dz, carry_next);
+            CellRegs nxt;
+            int4 cv_nxt = cv;
+            if (nb >= 0) {
+                load_cell(nxt, P.xrec, nb);
+                cv_nxt = A.geo.cell_vert[nb];
+            }
+
+            if (is_segment(dz)) {
+                const double a_raw = cur.r6.a, a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+                double G = g_tau * a_raw;                                  // d tau / d dz (raw alpha, every segment)
+                if (a != 0.0) {
+                    lam = lambda_add(lam, a, dz);  // (as in pass 1: Lambda_n == Lambda bit for bit, Lambda - Lambda_k >= 0)
+                    const double T = exp_nonpositive(fmin(lam - lam_total, 0.0));
+                    const double E = exp_nonpositive(-a * dz);
+                    G = fma(g_I * T, chord_dI(a, q, E, I), G);  // G_k
+                    I = segment_terms(a, q, dz, E, 1.0, I).I_next;
+                }
+                if (G != 0.0) {
+                    const CellFacesBary cf = cell_faces_bary(p, r.x, r.y);
+                    if (cf.found) {
+                        emit = true;
+                        // vertex_walk's six doubles: exit +, entry -, each rounded once
+                        Word* const row = word_stage_row<Word, kV>(stage, lane);
+#pragma unroll
+                        for (int v = 0; v < kV; ++v) row[v] = SUMS ? Word(0) : Word(exact::kNone);
+                        const int so = 3 * cf.out.f, si = 3 * cf.in.f;
+                        if constexpr (!SUMS) {
+                            row[so] = exact::exponent_of(mul_alone(G, cf.out.l0));
+                            row[so + 1] = exact::exponent_of(mul_alone(G, cf.out.l1));
+                            row[so + 2] = exact::exponent_of(mul_alone(G, cf.out.l2));
+                            row[si] = exact::exponent_of(mul_alone(-G, cf.in.l0));
+                            row[si + 1] = exact::exponent_of(mul_alone(-G, cf.in.l1));
+                            row[si + 2] = exact::exponent_of(mul_alone(-G, cf.in.l2));
+                        } else {
+                            // (a slot marked not finite stays NaN whatever is added: its words are not looked at)
+                            auto put = [&](int slot, double v, int e) {
+                                if (e == exact::kNotFinite) return;
+                                int64_t k1, k0;
+                                if (!exact::quantise(v, e, X.word_bits, k1, k0)) ++bad;
+                                row[2 * slot] = k1;
+                                row[2 * slot + 1] = k0;
+                            };
+                            // the two faces' exponents, loaded here: held in registers from the step before (twelve per
+                            // cell, beside the next cell's record) the choice of a face's three compiled to a table in
+                            // scratch, 52 to 112 bytes per lane (profiles/experiments.md)
+                            const int32_t* const ex = X.exps + 12 * static_cast<size_t>(here);
+                            const int eo0 = ex[so], eo1 = ex[so + 1], eo2 = ex[so + 2], ei0 = ex[si], ei1 = ex[si + 1], ei2 = ex[si + 2];
+                            put(so, mul_alone(G, cf.out.l0), eo0);
+                            put(so + 1, mul_alone(G, cf.out.l1), eo1);
+                            put(so + 2, mul_alone(G, cf.out.l2), eo2);
+                            put(si, mul_alone(-G, cf.in.l0), ei0);
+                            put(si + 1, mul_alone(-G, cf.in.l1), ei1);
+                            put(si + 2, mul_alone(-G, cf.in.l2), ei2);
+                        }
+                    }
+                }
+            }
+            ray_advance(r, nb, carry_next);
+            cur = nxt;
+            cv = cv_nxt;
+        }
+        if constexpr (SUMS) reduce_rows_words(stage, emit, here, lane, X.words);
+        else reduce_rows_max(stage, emit, here, lane, exact::kNone, X.exps);
+    }
+
+    if (SUMS) {
+        if (bad) atomicAdd(X.misfits, bad);
+        if (!X.keep_entries) ray_clear_head(r, P);
+    }
+}
+
+// vertex_resolve's frame: the same sort, the same back-to-front order; six atomicMax (pass E) or twelve integer adds
+// (pass S) per segment.  Reproducible as far as the list order is (segments of equal depth).
+template <bool SUMS>
+__global__ __launch_bounds__(256) void vertex_exact_resolve(ResolveParams R, const float2* __restrict__ grad_out, VertexExactSums X) {
+    using namespace adj;
+    double g_tau = 0.0, g_I = 0.0;
+    const ListFrame f = list_frame<true>(R, [&](int64_t lp) {
+        const float2 gw = grad_out[lp];
+        g_tau = gw.x;
+        g_I = gw.y;
+        return !(g_tau == 0.0 && g_I == 0.0);
+    });
+    const GridView& g = R.g;
+    const MotionGeometry geo{g.cell_vert, g.vx, g.vy, g.vz};
+    const double lam_total = lambda_total(f.list, f.n, g, R.alpha_limit);
+    double lam = 0.0, I = 0.0;
+    unsigned bad = 0;
+    for (int i = f.n - 1; i >= 0; --i) {
+        const int c = static_cast<int>(f.list[i].cell);
+        const double dz = f.list[i].dz, q = g.q[c], a_raw = g.alpha[c];
+        const ClampedAlpha ca = clamp_alpha(a_raw, R.alpha_limit);
+        double G = g_tau * a_raw;
+        if (ca.active) {
+            lam = lambda_add(lam, ca.a, dz);
+            const double T = exp(fmin(lam - lam_total, 0.0));
+            const double E = exp(-ca.a * dz);
+            G = fma(g_I * T, chord_dI(ca.a, q, E, I), G);
+            I = segment_terms(ca.a, q, dz, E, 1.0, I).I_next;
+        }
+        if (G != 0.0) {
+            double p[4][3];
+            load_vertices(geo, g.cell_vert[c], p);
+            const CellFacesBary cf = cell_faces_bary(p, f.x, f.y);
+            if (cf.found) {
+                exact_scatter_face<SUMS>(X, c, G, cf.out, bad);
+                exact_scatter_face<SUMS>(X, c, -G, cf.in, bad);
+            }
+        }
+    }
+    if (SUMS && bad) atomicAdd(X.misfits, bad);
+}
+
+// one thread per (cell, slot)
+__global__ __launch_bounds__(256) void vertex_exact_clear(VertexExactSums X, int64_t n_slots, int exps, int words, int misfits) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (misfits && i == 0) *X.misfits = 0u;
+    if (i >= n_slots) return;
+    if (exps) X.exps[i] = exact::kNone;
+    if (words) X.words[2 * i] = X.words[2 * i + 1] = 0ll;
+}
+
+// the caller's cell order -> the device's (TO_DEVICE) or back; one thread per (cell, slot); a null array stays out of it
+template <bool TO_DEVICE>
+__global__ __launch_bounds__(256) void vertex_exact_permute(VertexExactSums X, const int32_t* __restrict__ perm, int64_t n_cells,
+                                                            int32_t* __restrict__ exps, long long* __restrict__ sums) {
+    const int64_t t = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (t >= 12 * n_cells) return;
+    const int64_t i = t / 12, k = t - 12 * i;
+    const int64_t c = 12 * (perm ? static_cast<int64_t>(perm[i]) : i) + k;  // the caller's slot
+    if (exps) {
+        if (TO_DEVICE) X.exps[t] = exps[c];
+        else exps[c] = X.exps[t];
+    }
+    if (sums) {
+        if (TO_DEVICE) X.words[2 * t] = sums[2 * c], X.words[2 * t + 1] = sums[2 * c + 1];
+        else sums[2 * c] = X.words[2 * t], sums[2 * c + 1] = X.words[2 * t + 1];
+    }
+}
+
+__global__ __launch_bounds__(256) void vertex_exact_face_w(VertexExactSums X, int64_t n_slots, double* __restrict__ face_w) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n_slots) return;
+    face_w[i] = exact::finish(X.exps[i], X.words[2 * i], X.words[2 * i + 1], X.word_bits);
+}
+
+// per cell: the four vertices' triples.  Nothing here may be contracted: every product and every sum rounds by itself.
+__global__ __launch_bounds__(256) void vertex_exact_cells(MotionGeometry G, int64_t n_cells, const double* __restrict__ face_w,
+                                                          double* __restrict__ triples) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n_cells) return;
+    double w[12], t[4][3];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        w[k] = face_w[i * 12 + k];
+        t[k / 3][k % 3] = 0.0;
+    }
+    double p[4][3];
+    adj::load_vertices(G, G.cell_vert[i], p);
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {  // (ascending: a vertex's faces are added in this order)
+        const FacePlane fp = face_plane(p, f);
+        if (fp.kind == 0) continue;  // (edge-on: no ray crosses it, and it has no slopes)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double wk = w[3 * f + k];
+            if (wk != 0.0) {
+                double* const tv = t[adj::face_vertex(f, k)];
+                tv[0] = adj::add_alone(tv[0], adj::mul_alone(-fp.gx, wk));
+                tv[1] = adj::add_alone(tv[1], adj::mul_alone(-fp.gy, wk));
+                tv[2] = adj::add_alone(tv[2], wk);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) triples[i * 12 + k] = t[k / 3][k % 3];
+}
+
+// per point: its incidences' triples in the list's order, then grad_xyz = M^T grad_view (vertex_finish_points' rotation).
+// A point of no cell (a welded non-representative) and a sum of zeros give exact +0.0.
+__global__ __launch_bounds__(256) void vertex_exact_points(VertexIncidence inc, const double* __restrict__ triples, int64_t n_pts,
+                                                           RotationList R, double* __restrict__ grad_xyz) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n_pts) return;
+    double gx = 0.0, gy = 0.0, gz = 0.0;
+    for (int32_t j = inc.ptr[i]; j < inc.ptr[i + 1]; ++j) {
+        const double* const t = triples + 3 * static_cast<int64_t>(inc.idx[j]);
+        gx = adj::add_alone(gx, t[0]);
+        gy = adj::add_alone(gy, t[1]);
+        gz = adj::add_alone(gz, t[2]);
+    }
+    if (gx == 0.0 && gy == 0.0 && gz == 0.0) gx = gy = gz = 0.0;  // (+0.0, whatever the signs of the zeros and of the view's cosines)
+    else adj::rotate_linear<true>(R, gx, gy, gz);
     grad_xyz[3 * i] = gx;
     grad_xyz[3 * i + 1] = gy;
     grad_xyz[3 * i + 2] = gz;
@@ -685,6 +995,47 @@ void launch_vertex_finish(hipStream_t s, const MotionGeometry& geo, int64_t n_ce
                           int64_t n_pts, const RotationList& R, double* grad_xyz) {
     if (n_cells > 0) hipLaunchKernelGGL(vertex_finish_cells, dim3(item_blocks(n_cells)), dim3(256), 0, s, geo, n_cells, face_w, grad_view);
     if (n_pts > 0) hipLaunchKernelGGL(vertex_finish_points, dim3(item_blocks(n_pts)), dim3(256), 0, s, grad_view, n_pts, R, grad_xyz);
+}
+
+void launch_vertex_exact_clear(hipStream_t s, const VertexExactSums& x, int64_t n_cells, bool exps, bool words, bool misfits) {
+    hipLaunchKernelGGL(vertex_exact_clear, dim3(std::max(1u, item_blocks(12 * n_cells))), dim3(256), 0, s, x, 12 * n_cells, exps ? 1 : 0,
+                       words ? 1 : 0, misfits ? 1 : 0);
+}
+
+void launch_vertex_exact_walk(hipStream_t s, const VertexParams& v, const VertexExactSums& x, bool sums) {
+    const unsigned blocks = tile_blocks(v.w.im);
+    if (!blocks) return;
+    if (sums) hipLaunchKernelGGL(vertex_exact_walk<true>, dim3(blocks), dim3(64), 0, s, v, x);
+    else hipLaunchKernelGGL(vertex_exact_walk<false>, dim3(blocks), dim3(64), 0, s, v, x);
+}
+
+void launch_vertex_exact_resolve(hipStream_t s, const ResolveParams& r, const float2* grad_out, const VertexExactSums& x, bool sums) {
+    const unsigned blocks = pixel_blocks(r.im);
+    if (!blocks) return;
+    if (sums) hipLaunchKernelGGL(vertex_exact_resolve<true>, dim3(blocks), dim3(256), 0, s, r, grad_out, x);
+    else hipLaunchKernelGGL(vertex_exact_resolve<false>, dim3(blocks), dim3(256), 0, s, r, grad_out, x);
+}
+
+void launch_vertex_exact_gather(hipStream_t s, const int32_t* exps, const int64_t* sums, const int32_t* perm, int64_t n_cells,
+                                const VertexExactSums& x) {
+    if (n_cells > 0)
+        hipLaunchKernelGGL(vertex_exact_permute<true>, dim3(item_blocks(12 * n_cells)), dim3(256), 0, s, x, perm, n_cells,
+                           const_cast<int32_t*>(exps), reinterpret_cast<long long*>(const_cast<int64_t*>(sums)));
+}
+
+void launch_vertex_exact_emit(hipStream_t s, const VertexExactSums& x, const int32_t* perm, int64_t n_cells, int32_t* exps, int64_t* sums) {
+    if (n_cells > 0)
+        hipLaunchKernelGGL(vertex_exact_permute<false>, dim3(item_blocks(12 * n_cells)), dim3(256), 0, s, x, perm, n_cells, exps,
+                           reinterpret_cast<long long*>(sums));
+}
+
+void launch_vertex_exact_finish(hipStream_t s, const VertexExactSums& x, const MotionGeometry& geo, int64_t n_cells, double* face_w,
+                                double* cell_triples, const VertexIncidence& inc, int64_t n_pts, const RotationList& R, double* grad_xyz) {
+    if (n_cells > 0) {
+        hipLaunchKernelGGL(vertex_exact_face_w, dim3(item_blocks(12 * n_cells)), dim3(256), 0, s, x, 12 * n_cells, face_w);
+        hipLaunchKernelGGL(vertex_exact_cells, dim3(item_blocks(n_cells)), dim3(256), 0, s, geo, n_cells, face_w, cell_triples);
+    }
+    if (n_pts > 0) hipLaunchKernelGGL(vertex_exact_points, dim3(item_blocks(n_pts)), dim3(256), 0, s, inc, cell_triples, n_pts, R, grad_xyz);
 }
 
 void launch_vertex_walk_batch(hipStream_t s, int kc, const VertexBatchParams& v) {

@@ -69,9 +69,8 @@ def _host(t, dtype):
     return np.ascontiguousarray(t, dtype=dtype)
 
 
-class _ShardOperators:
-    """The four operators of a RowShards: every per-cell sum is the exact sum over the whole image, put together from the
-    parts' integers."""
+class _ShardImages:
+    """What the operators of a RowShards share: the scalars sent to every part, the whole-image weight, and the cuts."""
 
     def __init__(self, shards, alpha, q, weight):
         self.shards = shards
@@ -84,6 +83,15 @@ class _ShardOperators:
         """The whole image's rows of every part (None: None for every part)."""
         return [None if image is None else np.ascontiguousarray(image[rows]) for _ctx, rows in self.shards.parts]
 
+    def _times_weight(self, images):
+        """Per part: image * weight in float32, one multiply per channel (a None weight: ones)."""
+        return [img if w is None else img * w for img, w in zip(images, self._cut(self.weight))]
+
+
+class _ShardOperators(_ShardImages):
+    """The four operators of a RowShards: every per-cell sum is the exact sum over the whole image, put together from the
+    parts' integers."""
+
     def _exact(self, what, images, d_alpha=None, d_q=None):
         """One kind of exact sum over all parts: bounds on every part, the exponents combined, sums on every part against
         the combined exponents, the words combined, the finish."""
@@ -93,10 +101,6 @@ class _ShardOperators:
         words = [ctx.render_exact_sums(what, ea, eq, image=img, d_alpha=d_alpha, d_q=d_q) for (ctx, _rows), img in zip(sh.parts, images)]
         _, _, sa, sq = sharding.combine_exact([(ea, eq) + tuple(w) for w in words])
         return tuple(torch.as_tensor(capi.exact_sums_finish(e, s, sh.res_x, sh.res_y), device=sh.device) for e, s in ((ea, sa), (eq, sq)))
-
-    def _times_weight(self, images):
-        """Per part: image * weight in float32, one multiply per channel (a None weight: ones)."""
-        return [img if w is None else img * w for img, w in zip(images, self._cut(self.weight))]
 
     def rhs(self, residual):
         r = self.shards.whole_image(residual, "residual")
@@ -114,6 +118,32 @@ class _ShardOperators:
     def hvp(self, v_alpha, v_q, grad_img):
         g = self.shards.whole_image(grad_img, "grad_img")
         return self._exact(capi.C5_EXACT_HVP, self._cut(g), _host(v_alpha, np.float64), _host(v_q, np.float64))
+
+
+class _ShardShapeOperators(_ShardImages):
+    """The two operators of a shape fit over a RowShards: the vertex adjoint's sums are the exact sums over the whole image,
+    put together from the parts' integers and finished on the first part's context."""
+
+    def _exact(self, images):
+        """bounds on every part, the exponents combined (max), sums on every part against the combined exponents, the
+        words combined (add), the finish on the first part."""
+        sh = self.shards
+        bounds = [ctx.render_vertex_exact_bounds(img) for (ctx, _rows), img in zip(sh.parts, images)]
+        exps, _ = sharding.combine_vertex_exact([(b, None) for b in bounds])
+        words = [ctx.render_vertex_exact_sums(img, exps) for (ctx, _rows), img in zip(sh.parts, images)]
+        _, sums = sharding.combine_vertex_exact([(exps, w) for w in words])
+        return torch.as_tensor(sh.parts[0][0].vertex_exact_finish(exps, sums), device=sh.device)
+
+    def rhs(self, residual):
+        """J^T W r, float64 [n_pts, 3]."""
+        r = self.shards.whole_image(residual, "residual")
+        return self._exact(self._times_weight(self._cut(r)))
+
+    def product(self, p):
+        """J^T W J p, float64 [n_pts, 3]: a vertex tangent render on every part's rows, the fp32 multiply by the part's
+        weights, then the exact vertex adjoint of those images."""
+        d = _host(p, np.float64)
+        return self._exact(self._times_weight([ctx.render_vertex_tangent(d) for ctx, _rows in self.shards.parts]))
 
 
 class RowShards:
@@ -134,6 +164,12 @@ class RowShards:
     with set_option("exact_sums", 1), however the rows are split.  They return float64 torch tensors on the first
     context's device (a stand-in whose `device` is not an index names a torch device itself).
 
+    shape_operators(alpha, q, weight) is the hook shape_gradient and shape_step look for: rhs(residual) -> J^T W r and
+    product(p) -> J^T W J p over the grid's points, float64 [n_pts, 3], the vertex adjoint's sums put together in the same
+    way (render_vertex_exact_bounds, sharding.combine_vertex_exact, render_vertex_exact_sums, combine, vertex_exact_finish
+    on the first context) - bit for bit those of ONE context over the whole image with set_option("vertex_exact", 1).
+    update_points(xyz) sends new points to every context (the outer loop of a shape fit).
+
     This class is about bits, not speed: it uses the host-pointer forms and numpy between them.  Contexts on one device
     are the tested case; contexts on several devices work by construction and are unmeasured."""
 
@@ -143,6 +179,7 @@ class RowShards:
             raise ValueError("RowShards needs at least one (ctx, rows)")
         first = parts[0][0]
         self.res_x, self.res_y, self.n_cells = first.res_x, first.res_y, first.n_cells
+        self.n_pts = getattr(first, "n_pts", None)  # (a stand-in for the cell field's fit need not have points)
         for ctx, rows in parts:
             if (ctx.res_x, ctx.res_y, ctx.n_cells) != (self.res_x, self.res_y, self.n_cells):
                 raise ValueError("every context of a RowShards carries the same grid and image")
@@ -163,6 +200,15 @@ class RowShards:
 
     def gn_operators(self, alpha, q, weight):
         return _ShardOperators(self, alpha, q, weight)
+
+    def shape_operators(self, alpha, q, weight):
+        return _ShardShapeOperators(self, alpha, q, weight)
+
+    def update_points(self, xyz):
+        """New coordinates of the grid's points (float64 [n_pts, 3]) to every part."""
+        xyz = _host(xyz, np.float64)
+        for ctx, _rows in self.parts:
+            ctx.update_points(xyz)
 
 
 def _weighted(residual, weight):
@@ -287,22 +333,75 @@ def view_step(ctx, alpha, q, angles, residual, weight=None, damping: float = 0.0
     return d, float(0.5 * d @ H @ d + d @ g)
 
 
+def _shape_loss(r, w):
+    """(g, loss): g = w r in float32 and 1/2 sum w r^2 summed in float64, where r lives (w None: ones)."""
+    g = (r if w is None else r * w).contiguous()
+    return g, 0.5 * float((g.to(torch.float64) * r.to(torch.float64)).sum())
+
+
 def shape_gradient(ctx, alpha, q, residual, weight=None):
     """The loss 1/2 sum w r^2 of a fit of the grid's SHAPE and its gradient with respect to the points the context holds
     (capi.Context.update_points, autograd.render_mesh): r = frame - target the residual image, w the per-pixel weights
     ([local_rows, res_x, 2]; None: ones).  Returns (loss, grad_xyz): a float and float64 [n_pts, 3] on the context's GPU,
     from ONE vertex adjoint render on g = w r.  The building block of a descent loop, no more: step size, line search and
-    the loop are the caller's."""
+    the loop are the caller's.
+    A context may bring its own operators, as for gn_step: if it has a method shape_operators(alpha, q, weight) returning
+    an object with rhs(residual) -> J^T W r and product(p) -> J^T W J p (float64 [n_pts, 3] tensors), the gradient is its
+    rhs - RowShards, whose residual and weight are whole images [res_y, res_x, 2]."""
     from . import autograd
+    if hasattr(ctx, "shape_operators"):
+        grad = ctx.shape_operators(alpha, q, weight).rhs(residual)
+        r = torch.as_tensor(residual).detach().to(device=grad.device, dtype=torch.float32)
+        w = None if weight is None else torch.as_tensor(weight).detach().to(device=grad.device, dtype=torch.float32)
+        return _shape_loss(r, w)[1], grad
     device = autograd._gn_enter(ctx, alpha, q, "shape_gradient")
     with torch.cuda.device(device):
         r = residual.detach().to(device=device, dtype=torch.float32)
         if tuple(r.shape) != (ctx.local_rows, ctx.res_x, 2):
             raise ValueError(f"residual must be [{ctx.local_rows}, {ctx.res_x}, 2], not {list(r.shape)}")
-        w = autograd._gn_weight(ctx, weight, device)
-        g = (r if w is None else r * w).contiguous()
-        loss = 0.5 * float((g.to(torch.float64) * r.to(torch.float64)).sum())
+        g, loss = _shape_loss(r, autograd._gn_weight(ctx, weight, device))
         return loss, autograd._vertex_adjoint(ctx, g, device)
+
+
+def _shape_cg(JtWr, H, damping, iters, free, n_pts):
+    """shape_step's iteration on the two operators: JtWr() -> J^T W r, H(p) -> J^T W J p, float64 [n_pts, 3]."""
+    g = JtWr()
+    keep = None
+    if free is not None:
+        keep = torch.as_tensor(free, device=g.device)
+        if keep.dtype != torch.bool or tuple(keep.shape) != (n_pts,):
+            raise ValueError(f"free must be bool [{n_pts}]")
+        keep = keep.to(torch.float64).reshape(-1, 1)
+
+    def fixed(v):
+        return v if keep is None else v * keep
+
+    def dot(a, b):
+        return float((a * b).sum())
+
+    g = fixed(g)
+    x = torch.zeros_like(g)
+    hx = torch.zeros_like(g)  # (H + damping I) x
+    res = -g
+    p = res.clone()
+    rr = dot(res, res)
+    models = []
+    for _ in range(iters):
+        if not rr > 0.0:
+            break
+        ap = fixed(H(p)) + damping * p
+        curvature = dot(p, ap)
+        if not curvature > 0.0:
+            break
+        step = rr / curvature
+        x += step * p
+        hx += step * ap
+        res -= step * ap
+        models.append(0.5 * dot(x, hx) + dot(x, g))
+        rr_next = dot(res, res)
+        p = res + (rr_next / rr) * p
+        rr = rr_next
+    return x, models
 
 
 def shape_step(ctx, alpha, q, residual, weight=None, damping: float = 1e-3, iters: int = 10, free=None):
@@ -314,55 +413,27 @@ def shape_step(ctx, alpha, q, residual, weight=None, damping: float = 1e-3, iter
     or None (all); the points outside it stay fixed - their rows of every vector are zeroed.  Returns (d_xyz, models):
     float64 [n_pts, 3] on the context's GPU and, after every iteration done, the model 1/2 d^T (H + damping I) d +
     d^T J^T W r as a float.  It stops early when the residual of the linear system vanishes or a direction has no
-    curvature.  No line search and no outer loop: the caller owns both (update_points(xyz + d), render, again)."""
+    curvature.  No line search and no outer loop: the caller owns both (update_points(xyz + d), render, again).
+    CG amplifies last-bit differences of J^T W (J p) from iteration to iteration: with set_option("vertex_exact", 1) on the
+    context the steps are the same bits every run.  A context's own operators (shape_operators: shape_gradient) are used
+    where it has them - over RowShards the step is bit for bit the one context's, however the rows are split."""
     from . import autograd
     if damping < 0.0 or iters < 1:
         raise ValueError("damping must be >= 0 and iters >= 1")
+    if hasattr(ctx, "shape_operators"):
+        ops = ctx.shape_operators(alpha, q, weight)
+        return _shape_cg(lambda: ops.rhs(residual), ops.product, damping, iters, free, ctx.n_pts)
     device = autograd._gn_enter(ctx, alpha, q, "shape_step")
     with torch.cuda.device(device):
         r_img = residual.detach().to(device=device, dtype=torch.float32)
         if tuple(r_img.shape) != (ctx.local_rows, ctx.res_x, 2):
             raise ValueError(f"residual must be [{ctx.local_rows}, {ctx.res_x}, 2], not {list(r_img.shape)}")
         w = autograd._gn_weight(ctx, weight, device)
-        keep = None
-        if free is not None:
-            keep = torch.as_tensor(free, device=device)
-            if keep.dtype != torch.bool or tuple(keep.shape) != (ctx.n_pts,):
-                raise ValueError(f"free must be bool [{ctx.n_pts}]")
-            keep = keep.to(torch.float64).reshape(-1, 1)
-
-        def fixed(v):
-            return v if keep is None else v * keep
 
         def JtW(img):  # J^T W img: one vertex adjoint render
-            return fixed(autograd._vertex_adjoint(ctx, (img if w is None else img * w).contiguous(), device))
+            return autograd._vertex_adjoint(ctx, (img if w is None else img * w).contiguous(), device)
 
         def H(p):  # J^T W J p: one vertex tangent render, one vertex adjoint render
             return JtW(autograd._vertex_tangent(ctx, p.reshape(1, ctx.n_pts, 3).contiguous(), device)[0])
 
-        def dot(a, b):
-            return float((a * b).sum())
-
-        g = JtW(r_img)
-        x = torch.zeros_like(g)
-        hx = torch.zeros_like(g)  # (H + damping I) x
-        res = -g
-        p = res.clone()
-        rr = dot(res, res)
-        models = []
-        for _ in range(iters):
-            if not rr > 0.0:
-                break
-            ap = H(p) + damping * p
-            curvature = dot(p, ap)
-            if not curvature > 0.0:
-                break
-            step = rr / curvature
-            x += step * p
-            hx += step * ap
-            res -= step * ap
-            models.append(0.5 * dot(x, hx) + dot(x, g))
-            rr_next = dot(res, res)
-            p = res + (rr_next / rr) * p
-            rr = rr_next
-    return x, models
+        return _shape_cg(lambda: JtW(r_img), H, damping, iters, free, ctx.n_pts)

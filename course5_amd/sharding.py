@@ -107,15 +107,28 @@ def combine_exact(parts):
     by elementwise integer add (the words must have been computed against the COMBINED exponents).  An entry of a tuple
     may be None (a part that has only its exponents yet): the result's is None if every part's is.
     capi.exact_sums_finish turns the result into fp64."""
+    return _combine(parts, ((np.int32, np.maximum), (np.int32, np.maximum), (np.int64, np.add), (np.int64, np.add)),
+                    "(exp_alpha, exp_q, sums_alpha, sums_q)")
+
+
+def combine_vertex_exact(parts):
+    """combine_exact for the exact vertex adjoint sums: `parts` is a list of (exps, sums) - int32 [n_cells, 12] exponents as
+    capi.Context.render_vertex_exact_bounds returns them, int64 [n_cells, 12, 2] words as render_vertex_exact_sums does
+    (computed against the COMBINED exponents); either entry may be None.  Elementwise max and elementwise integer add;
+    capi.Context.vertex_exact_finish on any one of the parts' contexts turns the result into the gradient."""
+    return _combine(parts, ((np.int32, np.maximum), (np.int64, np.add)), "(exps, sums)")
+
+
+def _combine(parts, folds, layout: str):
     parts = list(parts)
     if not parts:
         raise ValueError("no parts to combine")
     out = []
-    for k, (dtype, fold) in enumerate(((np.int32, np.maximum), (np.int32, np.maximum), (np.int64, np.add), (np.int64, np.add))):
+    for k, (dtype, fold) in enumerate(folds):
         acc = None
         for p in parts:
-            if len(p) != 4:
-                raise ValueError("a part is (exp_alpha, exp_q, sums_alpha, sums_q)")
+            if len(p) != len(folds):
+                raise ValueError(f"a part is {layout}")
             if p[k] is None:
                 continue
             a = np.asarray(p[k])

@@ -246,10 +246,18 @@ int c5_set_alpha_limit(c5_context* ctx, double alpha_limit);
  *   "adjoint_exact" 1: c5_render_adjoint, c5_render_adjoint_device and their batch forms return the exact adjoint sums
  *                  (the section below c5_render_adjoint_batch): bit-reproducible from run to run and additive over rows.
  *                  Default 0: fp64 atomics, every kernel, code path and bit as before.  The Gauss-Newton, Hessian-vector
- *                  and vertex adjoint calls ignore it.  40 more bytes per cell, allocated at the first exact call.
+ *                  and vertex adjoint calls ignore it (the vertex adjoint has "vertex_exact").  40 more bytes per cell,
+ *                  allocated at the first exact call.
  *   "exact_sums"   1: c5_render_adjoint* as under "adjoint_exact" 1, and c5_render_gn_diagonal*, c5_render_gn_product* and
  *                  c5_render_hvp* return exact sums too (the section below c5_render_hvp): every operator of a fit of
- *                  (alpha, Q) bit-reproducible and additive over rows.  Default 0: as before.  The vertex adjoint ignores it.
+ *                  (alpha, Q) bit-reproducible and additive over rows.  Default 0: as before.  The vertex adjoint ignores it
+ *                  (its own option: "vertex_exact").
+ *   "vertex_exact" 1: c5_render_vertex_adjoint, c5_render_vertex_adjoint_device and their batch forms return the exact
+ *                  vertex adjoint sums (the section below c5_render_vertex_adjoint_batch): bit-reproducible from run to run,
+ *                  whatever "cell_order" and the walk's options, and additive over rows.  0 (default): fp64 atomics, every
+ *                  kernel, code path and bit as before.  Anything else: C5_ERR_INVALID.  "vertex_merge" is ignored under it.
+ *                  336 more bytes per cell and 4 (n_pts + 1) + 16 n_cells bytes of incidence table, allocated at the first
+ *                  exact vertex call.
  *   "overlap_setup" 1: entry lists and solid mask are built on a side stream while build_records
  *                  runs (only when "stage_timing" is 0).  Default 0: measured no faster.
  *   "pipeline"     1: two frame slots; the per-view setup of frame k + 1 runs on a second stream while
@@ -491,7 +499,8 @@ int c5_render_hvp_device(c5_context* ctx, const void* d_alpha_dev, const void* d
  * All results are finished to fp64 inside the one call and are bit-reproducible from run to run, whatever "cell_order",
  * the walk's options or the rows' split (on "algorithm" 1 as far as the tangent's is: lists with segments of equal depth).
  * Where a NULL output or direction is legal without the option it stays legal.  "adjoint_exact" keeps its meaning: the
- * adjoint only.  c5_render_vertex_adjoint* ignores both options (its per-point finish is another reduction).  Default 0:
+ * adjoint only.  c5_render_vertex_adjoint* ignores both options (its per-point finish is another reduction; its own
+ * option is "vertex_exact", the section below c5_render_vertex_adjoint_batch).  Default 0:
  * fp64 atomics, every kernel, code path and bit as before.  Memory: the exact adjoint's 40 bytes per cell, the same buffer.
  *
  * For callers who split an image, the two intermediate results of every kind of sum, one generic pair:
@@ -576,7 +585,7 @@ int c5_rotation_motion(const c5_rotation* rots, int n_rots, int index, int what,
  * receives the sum of the group.
  * grad_xyz: [n_pts][3] fp64 in the caller's point order, overwritten.  Row ranges and row tiles as for a frame (the
  * gradients of the parts sum to the whole frame's).  fp64 atomics added in arrival order: NOT bit-reproducible from run
- * to run, as the adjoint.
+ * to run, as the adjoint - unless option "vertex_exact" is 1 (exact vertex adjoint sums, below).
  * Status, retries, side effects: as c5_render_adjoint's (the adjoint's counters and status words, never a frame's; a
  * c5_render afterwards returns the bits it would have returned without it).  The first call allocates the adjoint's 8
  * bytes per local pixel, 96 bytes per cell and 24 per point; a context that never calls it uses no more memory than
@@ -595,7 +604,8 @@ int c5_render_vertex_adjoint_device(c5_context* ctx, const void* grad_out_dev, v
  * to run.  An image of zeros gives a slice of exact zeros, and welded non-representatives receive exact zeros in every
  * slice.  n_imgs == 1 is the single call.  On "algorithm" 1, and after a C5_RETRY onto its lists, the images run one
  * after the other over one per-view setup.  "vertex_merge" is ignored for n_imgs > 1 (the batch always merges), as are
- * "adjoint_exact" and "exact_sums".
+ * "adjoint_exact" and "exact_sums".  Under "vertex_exact" 1 the first pass runs once and every image then goes through the
+ * single exact path, one after the other: every slice is bit for bit the single exact call's, whatever "batch_width".
  * Status, counters, retries and side effects: the single call's.  The first batched call allocates 96 x "batch_width"
  * bytes per cell and 24 x "batch_width" per point beside the single call's buffers; a context that never calls it uses
  * no more memory than before.  c5_render_vertex_adjoint_batch is synchronous with host arrays and retries by itself on
@@ -603,6 +613,53 @@ int c5_render_vertex_adjoint_device(c5_context* ctx, const void* grad_out_dev, v
  * C5_ERR_INVALID.  Both refuse while c5_render_host_async frames are outstanding (C5_ERR_STATE). */
 int c5_render_vertex_adjoint_batch(c5_context* ctx, int n_imgs, const float* grad_out_host, double* grad_xyz_host);
 int c5_render_vertex_adjoint_batch_device(c5_context* ctx, int n_imgs, const void* grad_out_dev, void* grad_xyz_dev);
+
+/* --- exact vertex adjoint sums -------------------------------------------------------------------------
+ * Option "vertex_exact" 1 makes c5_render_vertex_adjoint* and its batch return grad_xyz DEFINED by four steps, none of
+ * which depends on an order of arrival:
+ *   1. Per cell and slot, an exact sum.  A segment adds six doubles, the ones the atomic mode adds: +G_k lambda to the
+ *      three slots of its exit face, -G_k lambda to those of its entry face, one rounding each.  The slots are a cell's
+ *      [4 faces][3 vertices of the face] (faces 0:(0,1,2) 1:(0,1,3) 2:(0,2,3) 3:(1,2,3) of the cell's four points).  They
+ *      are summed per (cell, slot) in the number format of "exact adjoint sums" above: exponent e = the largest ilogb over
+ *      the slot's contributions (INT32_MIN: none, INT32_MAX: one that is not finite), two int64 words (s1, s0), h and m of
+ *      the WHOLE image.  A ray crosses a cell at most once and its two faces differ, so a slot receives at most one
+ *      contribution per ray and the headroom argument carries over.  face_w[cell][slot] = the words finished: one rounding.
+ *   2. Per cell, fixed arithmetic.  For each of the cell's four vertices the triple (sum -gx_f w, sum -gy_f w, sum w) over
+ *      the faces f holding the vertex, in ascending f, (gx, gy) the face's slopes; edge-on faces and zero weights are
+ *      skipped; every product and every sum is rounded by itself (no contraction).
+ *   3. Per point, a gather in a fixed order: grad_view[point] = the sum of the triples of its (cell, vertex) incidences in
+ *      ascending order of the CALLER's cell index (not the device's: the result does not depend on "cell_order"), from
+ *      +0.0.  Points welded to another have no incidences and receive exact +0.0, as does every point of an all-zero sum.
+ *   4. grad_xyz[point] = M^T grad_view[point], as in the atomic mode.
+ * Bit-reproducible from run to run, whatever "cell_order", "vertex_merge", "batch_width" and the walk's options (on
+ * "algorithm" 1, and after a C5_RETRY onto its lists, as far as the list order is: segments of equal depth).  Against
+ * the atomic mode it is one more valid order of the same terms.  "adjoint_exact" and "exact_sums" have no say here.
+ *
+ * For callers who split an image, the intermediate results:
+ *   c5_render_vertex_exact_bounds  the adjoint's first pass and pass E over the context's rows.  exps: int32 [n_cells][12]
+ *                                  in the caller's cell order, overwritten.
+ *   c5_render_vertex_exact_sums    the first pass and pass S against the GIVEN exponents.  sums: int64 [n_cells][12][2] =
+ *                                  (s1, s0) per slot, the word order of c5_render_exact_sums, overwritten.
+ *   c5_vertex_exact_finish         steps 1 (the finish of the words) to 4 for the given exponents and words into grad_xyz
+ *                                  [n_pts][3] fp64.  It needs the context - the faces' slopes in the current view, the
+ *                                  grid's incidences, the view - and runs a per-view setup of its own; no ray is walked.
+ * SPLIT CONTRACT.  Exponents over any row ranges or row tiles combine by elementwise max; the words - every part's taken
+ * against the combined exponents - by elementwise integer add; c5_vertex_exact_finish on ANY ONE of the contexts (same
+ * grid, points and view) then gives bit for bit what the single "vertex_exact" call over the union of the rows gives.
+ * The mechanisms are the exact adjoint's: a contribution beyond its slot's exponent is added nowhere, counted and reported
+ * (C5_ERR_INVALID with a c5_last_error text; the _device forms: by the next call that waits for the stream); the host forms
+ * are synchronous and retry by themselves on C5_RETRY; the _device forms are asynchronous on the context's stream with
+ * device arrays; status and counters are the adjoint's own, never a frame's, and a c5_render afterwards returns the bits
+ * it would have returned without them; a null pointer: C5_ERR_INVALID; all six refuse while c5_render_host_async frames
+ * are outstanding (C5_ERR_STATE).  A scene without cells: nothing is written to exps / sums (they are empty), grad_xyz is
+ * zeros.  The incidence table is built by the host at the first exact vertex call after c5_upload_grid and kept across
+ * c5_update_points. */
+int c5_render_vertex_exact_bounds(c5_context* ctx, const float* grad_out_host, int32_t* exps_host);
+int c5_render_vertex_exact_bounds_device(c5_context* ctx, const void* grad_out_dev, void* exps_dev);
+int c5_render_vertex_exact_sums(c5_context* ctx, const float* grad_out_host, const int32_t* exps_host, int64_t* sums_host);
+int c5_render_vertex_exact_sums_device(c5_context* ctx, const void* grad_out_dev, const void* exps_dev, void* sums_dev);
+int c5_vertex_exact_finish(c5_context* ctx, const int32_t* exps_host, const int64_t* sums_host, double* grad_xyz_host);
+int c5_vertex_exact_finish_device(c5_context* ctx, const void* exps_dev, const void* sums_dev, void* grad_xyz_dev);
 
 /* --- vertex tangent render ---------------------------------------------------------------------------
  * The forward mode of the shape: how the frame c5_render would produce NOW changes when every grid point v moves with
