@@ -4,6 +4,8 @@ against the numpy restatements, element by element.
     python tests/derivative_fuzz.py [n_scenes] [seed0]
     python tests/derivative_fuzz.py geometry [n_scenes] [seed0]      (the geometry sweep, below)
     python tests/derivative_fuzz.py forward [n_scenes] [seed0]       (the forward sweep, at the end of this text)
+    python tests/derivative_fuzz.py second [n_scenes] [seed0]        (the second-order and exact-sum sweep, below)
+    python tests/derivative_fuzz.py vertex_exact [n_scenes] [seed0]  (the vertex sweep, below)
     python tests/derivative_fuzz.py chords SEED PIXEL      (the GPU's chords along one ray against the reference's)
 
 reports every mismatch and the worst error / tolerance per call kind; exit status 1 on any mismatch or when more than
@@ -133,6 +135,56 @@ EVERY frame compared, every pixel of it:
   own counts then depend on the order its threads bin in, line.cpp:29-67) and walk_overflow 0.  None of it is fitted to
   what the GPU returns.  Reported, not asserted: how many fp32 values of the frames on "integration" 0 with whole rays
   are not the port oracle's bit for bit.  What the first runs found is in profiles/forward_fuzz.md.
+
+THE SECOND-ORDER AND EXACT-SUM SWEEP (second_order_scene, check_second_order; tests/test_gpu_second_order_fuzz.py runs 40
+seeds of it): render_hvp and the exact modes ("adjoint_exact" 1, "exact_sums" 1, the C5_EXACT_* bounds / sums pair).
+second_order_scene(seed) is derivative_scene(seed), unchanged (qualify too), plus, from a stream of its own
+(default_rng([seed, 0x2E0])):
+  * the walk option of a comparison context (COMPARE_OPTIONS): none, ("depth_split", 2), ("integration", 1), ("cell_order", 0),
+    or ("lds_stage", 0) with ("tile", 0);
+  * a second split of the rows of the WHOLE image, whatever the scene's layout: cyclic tiles with the scene's tile_rows and
+    world, or two row ranges [0, cut), [cut, ry) with cut no multiple of the 8-row tile (off_tile_cut).
+Layout, soup, solid, device forms and the late limit are derivative_scene's, applied as check_scene applies them (the first
+render and the stats check included).  Per part of the layout, sums over the parts compared:
+  hvp   render_hvp for direction 0 (with the scene's NULL d_alpha / d_q) and g[0], and with fit=("alpha",) / ("q",) (the other
+      block None), every element of h_alpha and h_q at 1e-9 scale + dz_err sens + 2^-970 against hvp_reference.hvp_of; clamped
+      and inactive cells exactly 0 in h_alpha; stats() and a plain render after the calls as before them;
+  hvp_symmetry   with direction 1: |<u, H v> - <v, H u>| <= 1e-9 (sum |u (H v)| + sum |v (H u)|), tests/test_gpu_hvp.py's bar;
+  exact_adjoint, exact_gn_diagonal, exact_gn_product, exact_hvp   the adjoint of g[0], the diagonal, the product and the
+      Hessian-vector product of direction 0 on the same context with both options on, each on the bar of its atomic form
+      above (the product's r64 + 2^-22 on scale_h), NOT on a relation to the atomic result;
+  bit identities of the exact mode (BitTally): a second call; the comparison context; the product against the exact adjoint
+      of weight x fp32(J v) and its J v against the tangent; the second split - the bounds per part combined
+      (sharding.combine_exact) are the whole image's exponents, the words per part against them add up to the whole image's
+      integers, and finished (capi.exact_sums_finish) they are the single whole-image call's doubles, for C5_EXACT_ADJOINT,
+      _GN_DIAGONAL and _HVP.  A part's words must not all be zero where it owns a cell's largest contribution (its own exponent
+      is the combined one, so that contribution is >= 2^(e-1) on the cell's grid) or, for the two kinds with a tau term
+      (g_tau dz, w_tau dz^2), where it holds a covered, not solid-marked pixel whose image is not zero - a pixel with a zero
+      image, and a part 300 decades below another in every cell it shares, may rightly add nothing;
+  afterwards   the four atomic results within rtol 1e-12, atol 1e-15 x max of the ones before the exact calls
+      (tests/test_gpu_exact_fit.py's run-to-run bar), stats() and a plain render as before.
+On soups ("algorithm" 1: lists with equal depths may change their order from call to call) the identities that compare
+two calls - second call, comparison context, second split - are counted and printed, not asserted
+(tests/test_gpu_exact_adjoint.py's rule); the bars, the product identity and `afterwards` hold everywhere.
+
+THE VERTEX SWEEP (check_vertex_exact; tests/test_gpu_vertex_exact_fuzz.py runs 40 seeds of it): render_vertex_adjoint_batch and
+"vertex_exact" on geometry_scene(seed), unchanged - welded soups, "vertex_merge" 0 / 1, either cell order, the walk option,
+update_points (a moved scene is uploaded displaced, one call and a frame run there, then update_points), cyclic tiles, solids
+and device forms together.  The batch is s.vg followed by g[1:K]: up to 13 images, more than one pass at either width.
+  vertex_adjoint_batch   at "batch_width" 4 and 8 over the parts of the layout, summed: the slices of s.vg at 1e-9 scale_raw +
+      dz_err sens_raw + 2^-970 against vertex_adjoint_reference.gradients_of on the representatives, welded non-representatives
+      exactly 0, every slice against the single call at check_geometry's rerun bar;
+  vertex_exact   the single call of vg[0] on the same reference bar; on the whole image a second call, a context with the OTHER
+      cell_order and the OTHER vertex_merge, and every slice of the batch at both widths against the exact single call of
+      that image: equal bits; the staged path (render_vertex_exact_bounds per part, sharding.combine_vertex_exact, _sums,
+      combine, vertex_exact_finish) over the layout's cyclic tiles, else over two ranges cut off the 8-row tile
+      (default_rng([seed, 0x7E0])): the single whole-image call's bits; welded non-representatives +0.0 to the bit;
+  vertex_exact_duality   <g, J v> = <J^T g, v> with render_vertex_tangent of field v_compare[0] at 2^-22 sum |g| |out|.
+The soup rule is the one above.
+
+Both sweeps take their restatements over the rows of the layout that hold a covered pixel and over the covered pixels alone
+(covered_rows, covered_only; second_order_restatements and vertex_restatements run without a GPU): a pixel without a segment
+adds nothing to any cell or point.  The GPU calls run over every row and pixel.  profiles/second_order_fuzz.md has the runs.
 """
 import os
 import sys
@@ -147,6 +199,7 @@ import numpy as np
 from course5_amd import meshgen as mg, sharding
 from tests import adjoint_reference as ar, gn_reference as gr, tangent_reference as tr
 from tests import motion_reference as mr, ray_matrix_checks as rmc, vertex_adjoint_reference as vr, vertex_tangent_reference as vt
+from tests import exact_sum_reference as er, hvp_reference as hr
 from tests.fuzz_scenes import scene
 
 B = mg.REFERENCE_BOUNDS
@@ -164,6 +217,9 @@ WALK_OPTIONS = (("depth_split", 2), ("integration", 1))
 FORWARD_KINDS = ("render", "render_device", "host_async", "frame_rows", "split", "front_to_back", "after_update_scalars",
                  "after_set_limit", "after_update_points")
 DEFAULT_VARIANT = (2, 0, 3)
+SECOND_KINDS = ("hvp", "hvp_symmetry", "exact_adjoint", "exact_gn_diagonal", "exact_gn_product", "exact_hvp")
+VERTEX_EXACT_KINDS = ("vertex_adjoint_batch", "vertex_exact", "vertex_exact_duality")
+COMPARE_OPTIONS = ((), (("depth_split", 2),), (("integration", 1),), (("cell_order", 0),), (("lds_stage", 0), ("tile", 0)))
 
 
 def alpha_class(alpha, limit):
@@ -346,6 +402,9 @@ class _Calls:
     def gn_diagonal(self, w):
         return self.ctx.render_gn_diagonal(w)
 
+    def hvp(self, da, dq, g, fit=("alpha", "q")):
+        return self.ctx.render_hvp(da, dq, g, fit=fit)
+
 
 class _DeviceCalls(_Calls):
     """The same through the _device forms: torch tensors on the GPU, the status from synchronize() (C5_RETRY: again)."""
@@ -413,6 +472,15 @@ class _DeviceCalls(_Calls):
         da, dq, wt = self._empty((n,), torch.float64), self._empty((n,), torch.float64), self._t(w, torch.float32)
         self._run(lambda: self.ctx.render_gn_diagonal_device(wt, da, dq))
         return da.cpu().numpy(), dq.cpu().numpy()
+
+    def hvp(self, da, dq, g, fit=("alpha", "q")):
+        import torch
+        n = self.ctx.n_cells
+        ha = self._empty((n,), torch.float64) if "alpha" in fit else None
+        hq = self._empty((n,), torch.float64) if "q" in fit else None
+        a, q, gt = self._t(da), self._t(dq), self._t(g, torch.float32)
+        self._run(lambda: self.ctx.render_hvp_device(a, q, gt, ha, hq))
+        return None if ha is None else ha.cpu().numpy(), None if hq is None else hq.cpu().numpy()
 
 
 def check_scene(s, worst):
@@ -596,6 +664,9 @@ class _GeoCalls:
     def vertex_adjoint(self, g):
         return self.ctx.render_vertex_adjoint(g)
 
+    def vertex_adjoint_batch(self, g):
+        return self.ctx.render_vertex_adjoint_batch(g)
+
 
 class _GeoDeviceCalls(_DeviceCalls):
     def motion(self, fields):
@@ -617,15 +688,22 @@ class _GeoDeviceCalls(_DeviceCalls):
         self._run(lambda: self.ctx.render_vertex_adjoint_device(gt, out))
         return out.cpu().numpy()
 
+    def vertex_adjoint_batch(self, g):
+        import torch
+        out, gt = self._empty((len(g), self.ctx.n_pts, 3), torch.float64), self._t(g, torch.float32)
+        self._run(lambda: self.ctx.render_vertex_adjoint_batch_device(gt, out))
+        return out.cpu().numpy()
 
-def _open(s, xyz, walk_option=None):
-    """A context of the scene's own, as check_scene opens it, with the geometry sweep's options."""
+
+def _open(s, xyz, walk_option=None, cell_order=None, vertex_merge=None):
+    """A context of the scene's own, as check_scene opens it, with the geometry sweep's options (cell_order, vertex_merge:
+    in place of the scene's)."""
     from course5_amd import capi
     ctx = capi.Context(0)
     if s.soup:
         ctx.set_option("algorithm", 1)
-    ctx.set_option("cell_order", s.cell_order)  # (read by the upload)
-    ctx.set_option("vertex_merge", s.vertex_merge)
+    ctx.set_option("cell_order", s.cell_order if cell_order is None else cell_order)  # (read by the upload)
+    ctx.set_option("vertex_merge", s.vertex_merge if vertex_merge is None else vertex_merge)
     if walk_option:
         ctx.set_option(*walk_option)
     ctx.upload_grid(xyz, s.cells, s.alpha, s.q)
@@ -1273,6 +1351,512 @@ def forward_main():
     return 1 if mismatches or too_many else 0
 
 
+# ---- the second-order and exact-sum sweep, and the vertex sweep ----------------------------------------------------------
+
+def off_tile_cut(rng, ry):
+    """A row in 1..ry-1 that is no multiple of the walk's 8-row tile: rows [0, cut) and [cut, ry) cut a tile in two."""
+    cut = int(rng.integers(1, ry))
+    return cut - 1 if cut % 8 == 0 else cut
+
+
+def second_order_scene(seed):
+    """derivative_scene(seed), unchanged, with the walk option of the comparison context and the second split of the rows
+    drawn from a stream of its own (module docstring: the second-order sweep)."""
+    s = derivative_scene(seed)
+    rng = np.random.default_rng([seed, 0x2E0])
+    s.compare_options = COMPARE_OPTIONS[int(rng.integers(len(COMPARE_OPTIONS)))]
+    s.second_split = ("cyclic", "ranges")[int(rng.integers(2))]
+    s.second_cut = off_tile_cut(rng, s.res[1])
+    return s
+
+
+def second_split(s):
+    """[(place(ctx), the global rows the context then owns)] of the second split: together rows 0..ry-1, each once."""
+    ry = s.res[1]
+    if s.second_split == "cyclic":
+        return [((lambda c, r=r: c.set_row_tiles(s.tile_rows, r, s.world)), sharding.local_rows(ry, s.tile_rows, r, s.world))
+                for r in range(s.world)]
+    return [((lambda c, b=b, n=n: c.set_row_range(b, n)), np.arange(b, b + n)) for b, n in ((0, s.second_cut), (s.second_cut, ry - s.second_cut))]
+
+
+def layout_of(s):
+    """(the global rows the scene's layout renders, [(place(ctx), the local rows of that part among them)])."""
+    ry = s.res[1]
+    if s.layout == "range":
+        b, c = s.row_range
+        return np.arange(b, b + c), [(lambda x: x.set_row_range(b, c), np.arange(c))]
+    if s.layout == "cyclic":
+        return np.arange(ry), [((lambda x, r=r: x.set_row_tiles(s.tile_rows, r, s.world)), sharding.local_rows(ry, s.tile_rows, r, s.world))
+                               for r in range(s.world)]
+    return np.arange(ry), [(lambda x: None, np.arange(ry))]
+
+
+def covered_rows(s):
+    """The rows of the scene's layout that hold a covered pixel (s.segments): the restatements are taken over these alone -
+    a row without a segment adds nothing to any cell or point, and their time goes with the pixels."""
+    rows = layout_of(s)[0]
+    return rows[np.isin(rows, np.unique(s.segments[0] // s.res[0]))]
+
+
+class BitTally:
+    """The bit identities: asserted, except on soups ("algorithm" 1: lists with equal depths may change their order from
+    call to call - tests/test_gpu_exact_adjoint.py), where they are counted and printed."""
+
+    def __init__(self):
+        self.counts = {}
+
+    def hold(self, bad, s, name, same, text=None):
+        if s.soup:
+            c = self.counts.setdefault(name, [0, 0])
+            c[0] += 1
+            c[1] += 0 if same else 1
+        elif not same:
+            bad.append(text or f"{name}: the bits differ")
+
+    def lines(self):
+        return [f"on soups, {name}: {c[1]} of {c[0]} comparisons differ in bits (counted, not asserted)" for name, c in sorted(self.counts.items())]
+
+
+def _bits64(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def _same64(a, b):
+    return len(a) == len(b) and all(np.array_equal(_bits64(x), _bits64(y)) for x, y in zip(a, b))
+
+
+def _directions(s, j):
+    return None if s.d_alpha is None else s.d_alpha[j], None if s.d_q is None else s.d_q[j]
+
+
+def second_order_restatements(s, skip=None):
+    """The reference half of check_second_order, no GPU: {name: ((alpha block, q block), hvp_of's / gradients_of's / ... dict
+    of scales and sensitivities)} for the Hessian-vector product of direction 0 with g[0], the adjoint of g[0], the
+    Gauss-Newton diagonal and the product of direction 0, over the rows of the scene's layout and their covered pixels
+    only (covered_only: a pixel without a segment adds nothing to any cell).  skip: the solid-marked pixels, bool [ry, rx]."""
+    rx, ry = s.res
+    n = len(s.cells)
+    rows_ref = covered_rows(s)
+    m = ar.ray_matrices(s.xyz, s.cells, s.alpha, s.q, s.rots, rx, ry, B, s.limit, rows_ref)
+    cov, mc, _ = covered_only(m, {})
+    cut = lambda img: None if img is None else np.asarray(img)[rows_ref].reshape((len(cov),) + np.shape(img)[2:])[cov]  # noqa: E731
+    skip_cov = cut(skip)
+    da, dq = _directions(s, 0)
+    g, w = cut(s.g[0]), cut(s.w)
+    out = {}
+    ha, hq, x = hr.hvp_of(mc, n, da, dq, g, skip_cov, with_scale=True)
+    out["hvp"] = ((ha, hq), x)
+    ga, gq, _tau, _I, x = ar.gradients_of(mc, n, g, skip_cov, with_scale=True)
+    out["adjoint"] = ((ga, gq), x)
+    terms = gr.terms_of(mc, skip_cov, with_scale=True)
+    out["diagonal"] = (gr.diagonal(terms, mc["n_px"], n, w), gr.diagonal_scale(terms, mc["n_px"], n, w))
+    ha, hq, _jv, x = gr.product_header(terms, mc["n_px"], n, da, dq, w)
+    out["product"] = ((ha, hq), x)
+    return out
+
+
+def _open_scalar(s, options=(), exact=False):
+    """A context of the scene's own as check_scene opens it, `options` set before the upload; the alpha limit is left to
+    the caller.  exact: on "adjoint_exact" 1 and "exact_sums" 1."""
+    from course5_amd import capi
+    ctx = capi.Context(0)
+    if s.soup:
+        ctx.set_option("algorithm", 1)
+    for k, v in options:
+        ctx.set_option(k, v)
+    ctx.upload_grid(s.xyz, s.cells, s.alpha, s.q)
+    ctx.set_image(s.res[0], s.res[1], B)
+    ctx.set_view(s.rots)
+    if exact:
+        _set_exact(ctx, 1)
+    return ctx
+
+
+def _set_exact(ctx, on):
+    ctx.set_option("adjoint_exact", on)
+    ctx.set_option("exact_sums", on)
+
+
+def _four(calls, s, g, w):
+    """The adjoint of g, the Gauss-Newton diagonal, the product and the Hessian-vector product of direction 0 (atomic or
+    exact by the context's options): ({name: (alpha block, q block)}, the product's J v)."""
+    da, dq = _directions(s, 0)
+    ha, hq, jv = calls.gn_product(None if da is None else da[None], None if dq is None else dq[None], w)
+    return {"adjoint": calls.adjoint(g), "diagonal": calls.gn_diagonal(w), "product": (ha[0], hq[0]), "hvp": calls.hvp(da, dq, g)}, jv[0]
+
+
+def _counts(ctx):
+    return {k: v for k, v in ctx.stats().items() if not k.startswith("ms_")}
+
+
+def _exact_kinds(s, image_rows=None):
+    """(name, kind, the image of the rows, the directions) of the three kinds of the bounds / sums pair."""
+    from course5_amd import capi
+    rows = slice(None) if image_rows is None else image_rows
+    da, dq = _directions(s, 0)
+    dirs = {k: v for k, v in (("d_alpha", da), ("d_q", dq)) if v is not None}
+    w = None if s.w is None else np.ascontiguousarray(s.w[rows])
+    g = np.ascontiguousarray(s.g[0][rows])
+    return (("adjoint", capi.C5_EXACT_ADJOINT, g, {}), ("diagonal", capi.C5_EXACT_GN_DIAGONAL, w, {}), ("hvp", capi.C5_EXACT_HVP, g, dirs))
+
+
+def _second_split_identity(s, skip, tally, bad):
+    """(e) of the module docstring: bounds per part, combined; sums per part against the combined exponents, combined;
+    finished - the exponents, the integer words and the finished doubles are the whole image's."""
+    from course5_amd import capi
+    rx, ry = s.res
+    pix = s.segments[0]
+    covered = np.zeros(rx * ry, bool)
+    covered[pix] = True
+    covered = covered.reshape(ry, rx) & (True if skip is None else ~skip)
+    live = {"adjoint": covered & (s.g[0][..., 0] != 0), "diagonal": covered & (True if s.w is None else s.w[..., 0] != 0)}
+    finish = lambda e, w: (capi.exact_sums_finish(e[0], w[0], rx, ry), capi.exact_sums_finish(e[1], w[1], rx, ry))  # noqa: E731
+    with _open_scalar(s, exact=True) as ctx:
+        ctx.set_alpha_limit(s.limit)
+        if s.solid:
+            ctx.set_solid(0, _solid_of(s))
+        calls = _Calls(ctx)
+        single = _four(calls, s, s.g[0], s.w)[0]
+        whole = {}
+        for name, what, image, dirs in _exact_kinds(s):
+            exps = ctx.render_exact_bounds(what, image=image, **dirs)
+            words = ctx.render_exact_sums(what, *exps, image=image, **dirs)
+            whole[name] = (exps, words)
+            tally.hold(bad, s, "bounds, sums, finish against the single call",
+                       _same64(finish(exps, words), single[name]), f"exact {name}: bounds, sums and finish do not give the single call's bits")
+        parts = [(place, rows) for place, rows in second_split(s) if len(rows)]
+        bounds = []
+        for place, rows in parts:
+            place(ctx)
+            bounds.append({name: ctx.render_exact_bounds(what, image=image, **dirs) for name, what, image, dirs in _exact_kinds(s, rows)})
+        combined = {name: sharding.combine_exact([b[name] + (None, None) for b in bounds])[:2] for name in whole}
+        for name in whole:
+            tally.hold(bad, s, "second split, exponents", all(np.array_equal(a, b) for a, b in zip(combined[name], whole[name][0])),
+                       f"exact {name}: the combined exponents of the second split ({s.second_split}) are not the whole image's")
+        words = []
+        for place, rows in parts:
+            place(ctx)
+            words.append({name: ctx.render_exact_sums(what, *combined[name], image=image, **dirs) for name, what, image, dirs in _exact_kinds(s, rows)})
+        for name in whole:
+            total = sharding.combine_exact([combined[name] + w[name] for w in words])
+            tally.hold(bad, s, "second split, words", np.array_equal(total[2], whole[name][1][0]) and np.array_equal(total[3], whole[name][1][1]),
+                       f"exact {name}: the integer words of the second split ({s.second_split}) do not add up to the whole image's")
+            tally.hold(bad, s, "second split, finished", _same64(finish(total[:2], total[2:]), single[name]),
+                       f"exact {name}: the second split ({s.second_split}) finished is not the single whole-image call's bits")
+            for (place, rows), b, w in zip(parts, bounds, words):
+                # a part must hold non-zero words where it owns a cell's largest contribution (its own exponent is the
+                # combined one: that contribution is at least 2^(e-1) on the cell's grid), and, for the two kinds with a
+                # tau term g_tau dz / w_tau dz^2, where it holds a covered pixel whose image is not zero
+                owns = any(((e == c) & (e != er.NONE)).any() for e, c in zip(b[name], combined[name]))
+                if (owns or (name in live and live[name][rows].any())) and not (w[name][0].any() or w[name][1].any()):
+                    bad.append(f"exact {name}: a part of the second split ({s.second_split}) with covered rows has all-zero words")
+
+
+def check_second_order(s, worst, tally=None):
+    """The Hessian-vector render and the exact-sum modes on one used scene (second_order_scene, qualify first; module
+    docstring: the second-order sweep).  Returns the mismatches, strings."""
+    from contextlib import ExitStack
+    bad = []
+    tally = tally or BitTally()
+    n = len(s.cells)
+    with ExitStack() as stack:
+        ctx = stack.enter_context(_open_scalar(s))
+        if not s.late_limit:
+            ctx.set_alpha_limit(s.limit)
+        ctx.render()
+        st = ctx.stats()
+        if (st["segments"], st["covered_pixels"]) != (s.n_segments, s.n_covered):
+            bad.append(f"stats: {st['segments']} segments on {st['covered_pixels']} pixels, the reference has "
+                       f"{s.n_segments} on {s.n_covered}")
+        if s.late_limit:
+            ctx.set_alpha_limit(s.limit)  # (after a frame: the cell records carry the clamp and must be rebuilt)
+        cmp_ctx = stack.enter_context(_open_scalar(s, s.compare_options, exact=True))
+        cmp_ctx.set_alpha_limit(s.limit)
+        skip = None
+        if s.solid:
+            ctx.set_solid(0, _solid_of(s))
+            cmp_ctx.set_solid(0, _solid_of(s))
+            skip = np.isnan(ctx.render()[..., 0])
+        rows_ref, parts = layout_of(s)
+        g_ref = s.g[:, rows_ref]
+        w_ref = None if s.w is None else s.w[rows_ref]
+        calls = _DeviceCalls(ctx) if s.device else _Calls(ctx)
+        da, dq = _directions(s, 0)
+        ua, uq = _directions(s, 1)
+        names = ("adjoint", "diagonal", "product", "hvp")
+        sums = {k: [np.zeros(n), np.zeros(n)] for k in ("hvp", "hvp_u", "only_alpha", "only_q") + tuple("exact_" + k for k in names)}
+
+        def add(name, pair):
+            for acc, v in zip(sums[name], pair):
+                if v is not None:
+                    acc += v
+
+        for place, where in parts:
+            if len(where) == 0:  # (a rank without rows: small images in tall tiles)
+                continue
+            place(ctx), place(cmp_ctx)
+            before, counts = ctx.render(), _counts(ctx)
+            g = np.ascontiguousarray(g_ref[0, where])
+            w = None if w_ref is None else np.ascontiguousarray(w_ref[where])
+            # -- atomic mode: the Hessian-vector render
+            add("hvp", calls.hvp(da, dq, g))
+            add("hvp_u", calls.hvp(ua, uq, g))
+            only_a, none_q = calls.hvp(da, dq, g, fit=("alpha",))
+            none_a, only_q = calls.hvp(da, dq, g, fit=("q",))
+            if none_q is not None or none_a is not None:
+                bad.append("render_hvp returns a block that fit does not name")
+            add("only_alpha", (only_a, None)), add("only_q", (None, only_q))
+            atomic = _four(calls, s, g, w)[0]
+            if _counts(ctx) != counts:
+                bad.append("stats() changed over the Hessian-vector calls")
+            if not np.array_equal(_bits(ctx.render()), _bits(before)):
+                bad.append("a plain render after the Hessian-vector calls differs from the one before them")
+            # -- exact modes, on the same context and inputs
+            _set_exact(ctx, 1)
+            exact, jv = _four(calls, s, g, w)
+            again = _four(calls, s, g, w)[0]
+            tangent = calls.tangent(da, dq)
+            weighted = tangent if w is None else (w * tangent).astype(np.float32)
+            as_adjoint = calls.adjoint(np.ascontiguousarray(weighted))
+            other = _four(_Calls(cmp_ctx), s, g, w)[0]
+            _set_exact(ctx, 0)
+            for name in names:
+                add("exact_" + name, exact[name])
+                tally.hold(bad, s, "call to call", _same64(again[name], exact[name]), f"exact {name}: a second call gives other bits")
+                tally.hold(bad, s, "comparison context", _same64(other[name], exact[name]),
+                           f"exact {name}: a context on {s.compare_options or 'the default options'} gives other bits")
+            if not _same64(as_adjoint, exact["product"]):
+                bad.append("the exact product is not the exact adjoint of weight x fp32(J v) bit for bit")
+            if not np.array_equal(_bits(jv), _bits(tangent)):
+                bad.append(f"the exact product's J v differs from the tangent in {int((_bits(jv) != _bits(tangent)).sum())} values")
+            # -- afterwards: the atomic mode on its run-to-run bar (tests/test_gpu_exact_fit.py), the frame as it was
+            after = _four(calls, s, g, w)[0]
+            for name in names:
+                for a, b in zip(after[name], atomic[name]):
+                    if not (np.abs(a - b) <= 1e-12 * np.abs(b) + 1e-15 * np.abs(b).max() + ABS_FLOOR).all():
+                        bad.append(f"atomic {name} after the exact calls: beyond rtol 1e-12, atol 1e-15 x max of the call before them")
+            if _counts(ctx) != counts:
+                bad.append("stats() changed over the exact calls")
+            if not np.array_equal(_bits(ctx.render()), _bits(before)):
+                bad.append("a plain render after the exact calls differs from the one before them")
+    _second_split_identity(s, skip, tally, bad)
+    # -- identities on the library's own results
+    frozen = (s.alpha > s.limit) | (np.minimum(s.alpha, s.limit) < EPS)
+    for name in ("hvp", "hvp_u", "only_alpha", "exact_hvp"):
+        if sums[name][0][frozen].any():
+            bad.append(f"{name}: {int((sums[name][0][frozen] != 0).sum())} clamped or inactive cells have a non-zero h_alpha")
+    zero = np.zeros(n)
+    u, v = [zero if t is None else t for t in (ua, uq)], [zero if t is None else t for t in (da, dq)]
+    hv, hu = sums["hvp"], sums["hvp_u"]
+    lhs, rhs = float(u[0] @ hv[0] + u[1] @ hv[1]), float(v[0] @ hu[0] + v[1] @ hu[1])
+    bar = 1e-9 * float(sum(np.abs(a * b).sum() for a, b in ((u[0], hv[0]), (u[1], hv[1]), (v[0], hu[0]), (v[1], hu[1]))))
+    r = worst.add("hvp_symmetry", np.array([0.0 if lhs == rhs else abs(lhs - rhs) / bar if bar else np.inf]), s.seed, "directions 0, 1")
+    if not r <= 1.0:
+        bad.append(f"symmetry: <u, H v> = {lhs:.15g}, <v, H u> = {rhs:.15g}, difference / bar {r:.3g}")
+    # -- against the restatements, element by element
+    e = dz_err(s)
+    ref = second_order_restatements(s, skip)
+
+    def pair(got, name, r_scale=R64):
+        want, x = ref[name]
+        return np.stack([ratio(got[0], want[0], x["scale_alpha"], x["sens_alpha"], e, r_scale=r_scale),
+                         ratio(got[1], want[1], x["scale_q"], x["sens_q"], e, r_scale=r_scale)])
+
+    found = [("hvp", "(alpha, q)", pair(sums["hvp"], "hvp")),
+             ("hvp", "one output at a time (alpha, q)", pair((sums["only_alpha"][0], sums["only_q"][1]), "hvp")),
+             ("exact_adjoint", "(alpha, q)", pair(sums["exact_adjoint"], "adjoint")),
+             ("exact_gn_diagonal", "(alpha, q)", pair(sums["exact_diagonal"], "diagonal")),
+             ("exact_gn_product", "(alpha, q)", pair(sums["exact_product"], "product", R64 + R_H)),
+             ("exact_hvp", "(alpha, q)", pair(sums["exact_hvp"], "hvp"))]
+    for kind, what, r in found:
+        top = worst.add(kind, r, s.seed, what)
+        if not top <= 1.0:
+            i = np.unravel_index(int(np.argmax(r)), r.shape)
+            bad.append(f"{kind} {what}: {int((~(r <= 1.0)).sum())} elements beyond the bar, worst error / tol {top:.3g} at {tuple(int(v) for v in i)}")
+    return bad
+
+
+def describe_second_order(s):
+    return (describe(s) + f"; comparison context on {dict(s.compare_options) or 'the default options'}, second split {s.second_split}"
+            + (f" at row {s.second_cut}" if s.second_split == "ranges" else f" ({s.tile_rows} rows, world {s.world})"))
+
+
+def vertex_batch(s):
+    """The upstream images of the vertex sweep's batch: s.vg, then g[1:K] - up to 13, more than one pass at either width."""
+    return np.stack(list(s.vg) + list(s.g[1:s.k]))
+
+
+def vertex_restatements(s, skip=None):
+    """The reference half of check_vertex_exact, no GPU: per image of s.vg the dict {raw, scale_raw, sens_raw} [n_pts, 3] of
+    vertex_adjoint_reference.gradients_of over the rows of the scene's layout (covered pixels only), a weld group's sums
+    on its representative."""
+    rx, ry = s.res
+    n_pts = len(s.xyz)
+    rows_ref = covered_rows(s)
+    m = ar.ray_matrices(s.xyz, s.cells, s.alpha, s.q, s.rots, rx, ry, B, s.limit, rows_ref)
+    geo = vr.segment_faces(s.xyz, s.cells, s.rots, rx, ry, B, rows_ref)
+    cov, mc, gc = covered_only(m, geo)
+    skip_cov = None if skip is None else skip[rows_ref].reshape(-1)[cov]
+    out = []
+    for g in s.vg:
+        ref = vr.gradients_of(mc, gc, s.cells, n_pts, s.rots, g[rows_ref].reshape(-1, 2)[cov], skip_cov)
+        on_rep = {k: np.zeros((n_pts, 3)) for k in ("raw", "scale_raw", "sens_raw")}
+        for k, v in on_rep.items():
+            np.add.at(v, s.rep, ref[k])  # the group's sum on its representative
+        out.append(on_rep)
+    return out
+
+
+def check_vertex_exact(s, worst, tally=None):
+    """The batched vertex adjoint and the exact vertex adjoint sums on one used scene (geometry_scene, qualify first; module
+    docstring: the vertex sweep).  Returns the mismatches, strings."""
+    from contextlib import ExitStack
+    bad = []
+    tally = tally or BitTally()
+    ry = s.res[1]
+    n_pts = len(s.xyz)
+    batch = vertex_batch(s)
+    nb = len(batch)
+    welded = s.rep != np.arange(n_pts)
+    with ExitStack() as stack:
+        ctx = stack.enter_context(_open(s, s.displaced if s.moved else s.xyz, s.walk_option))
+        flipped = stack.enter_context(_open(s, s.xyz, s.walk_option, cell_order=1 - s.cell_order, vertex_merge=1 - s.vertex_merge))
+        if not s.late_limit:
+            ctx.set_alpha_limit(s.limit)
+        ctx.render()
+        if s.late_limit:
+            ctx.set_alpha_limit(s.limit)
+        flipped.set_alpha_limit(s.limit)
+        calls = _GeoDeviceCalls(ctx) if s.device else _GeoCalls(ctx)
+        if s.moved:  # one call on the displaced grid (its per-point and per-cell data are built for it), then into place
+            calls.vertex_adjoint(s.vg[0])
+            ctx.render()
+            ctx.update_points(s.xyz)
+            ctx.render()
+        st = ctx.stats()
+        if (st["segments"], st["covered_pixels"]) != (s.n_segments, s.n_covered):
+            bad.append(f"stats: {st['segments']} segments on {st['covered_pixels']} pixels, the reference has {s.n_segments} on {s.n_covered}")
+        skip = None
+        if s.solid:
+            for c in (ctx, flipped):
+                c.set_solid(0, _solid_of(s))
+            skip = np.isnan(ctx.render()[..., 0])
+        rows_ref, parts = layout_of(s)
+        # -- "vertex_exact" 1 on the whole image: the single calls, the other cell order and merge, the batches, duality
+        ctx.set_option("vertex_exact", 1)
+        flipped.set_option("vertex_exact", 1)
+        singles = np.stack([calls.vertex_adjoint(g) for g in batch])
+        tally.hold(bad, s, "call to call", np.array_equal(_bits64(calls.vertex_adjoint(batch[0])), _bits64(singles[0])),
+                   "vertex_exact: a second call gives other bits")
+        tally.hold(bad, s, "other cell_order and vertex_merge", np.array_equal(_bits64(flipped.render_vertex_adjoint(batch[0])), _bits64(singles[0])),
+                   f"vertex_exact: cell_order {1 - s.cell_order}, vertex_merge {1 - s.vertex_merge} give other bits than {s.cell_order}, {s.vertex_merge}")
+        for width in (4, 8):
+            ctx.set_option("batch_width", width)
+            got = calls.vertex_adjoint_batch(batch)
+            tally.hold(bad, s, "batch against single calls", np.array_equal(_bits64(got), _bits64(singles)),
+                       f"vertex_exact: the batch of {nb} (width {width}) differs from the single calls in {int((_bits64(got) != _bits64(singles)).sum())} values")
+        if _bits64(singles[:, welded]).any():
+            bad.append("vertex_exact: welded non-representatives are not +0.0 to the bit")
+        j = s.v_compare[0]
+        out = ctx.render_vertex_tangent(s.v_fields[j:j + 1])[0].astype(np.float64)
+        g64 = batch[0].astype(np.float64)
+        lhs, rhs = float((g64 * out).sum()), float((singles[0] * s.v_fields[j]).sum())
+        bar = 2.0 ** -22 * float((np.abs(g64) * np.abs(out)).sum()) + ABS_FLOOR_32
+        r = worst.add("vertex_exact_duality", np.array([abs(lhs - rhs) / bar]), s.seed, f"field {j}")
+        if not r <= 1.0:
+            bad.append(f"vertex_exact duality, field {j}: <g, J v> = {lhs:.9g}, <J^T g, v> = {rhs:.9g}, difference / bar {r:.3g}")
+        # -- the staged path: over the layout's parts where it has any, else over two ranges cut off the 8-row tile
+        if s.layout == "cyclic":
+            staged = [(place, rows_ref[where]) for place, where in parts if len(where)]
+        else:
+            cut = off_tile_cut(np.random.default_rng([s.seed, 0x7E0]), ry)
+            staged = [((lambda x, b=b, c=c: x.set_row_range(b, c)), np.arange(b, b + c)) for b, c in ((0, cut), (cut, ry - cut))]
+        bounds = []
+        for place, rows in staged:
+            place(ctx)
+            bounds.append(ctx.render_vertex_exact_bounds(np.ascontiguousarray(batch[0][rows])))
+        exps, _ = sharding.combine_vertex_exact([(b, None) for b in bounds])
+        words = []
+        for place, rows in staged:
+            place(ctx)
+            words.append(ctx.render_vertex_exact_sums(np.ascontiguousarray(batch[0][rows]), exps))
+        _, total = sharding.combine_vertex_exact([(exps, w) for w in words])
+        tally.hold(bad, s, "staged path", np.array_equal(_bits64(ctx.vertex_exact_finish(exps, total)), _bits64(singles[0])),
+                   f"vertex_exact: bounds, sums and finish over {len(staged)} parts do not give the single whole-image call's bits")
+        if s.layout != "cyclic":
+            ctx.set_row_range(0, ry)
+        ctx.set_option("vertex_exact", 0)
+        # -- over the parts of the layout: the exact single call, and the atomic mode's batches and single calls
+        exact = np.zeros((n_pts, 3))
+        atomic = {width: np.zeros((nb, n_pts, 3)) for width in (4, 8)}
+        alone = np.zeros((nb, n_pts, 3))
+        n_parts = 0
+        for place, where in parts:
+            if len(where) == 0:
+                continue
+            n_parts += 1
+            place(ctx)
+            before, counts = ctx.render(), _counts(ctx)
+            part = np.ascontiguousarray(batch[:, rows_ref[where]])
+            ctx.set_option("vertex_exact", 1)
+            exact += calls.vertex_adjoint(part[0])
+            ctx.set_option("vertex_exact", 0)
+            for width in (4, 8):
+                ctx.set_option("batch_width", width)
+                atomic[width] += calls.vertex_adjoint_batch(part)
+            for i in range(nb):
+                alone[i] += calls.vertex_adjoint(part[i])
+            if _counts(ctx) != counts:
+                bad.append("stats() changed over the vertex adjoint calls")
+            if not np.array_equal(_bits(ctx.render()), _bits(before)):
+                bad.append("a plain render after the vertex adjoint calls differs from the one before them")
+    for name, a in (("the batches", atomic[4]), ("the batches", atomic[8]), ("the single calls", alone), ("vertex_exact", exact)):
+        if a[..., welded, :].any():
+            bad.append(f"{name}: welded non-representatives hold non-zero gradients")
+    # -- against the restatement, element by element, and the batches against the single calls
+    e = dz_err(s)
+    found = []
+    for i, ref in enumerate(vertex_restatements(s, skip)):
+        for width in (4, 8):
+            found.append(("vertex_adjoint_batch", f"width {width}, image {i}", ratio(atomic[width][i], ref["raw"], ref["scale_raw"], ref["sens_raw"], e)))
+        if i == 0:
+            found.append(("vertex_exact", "image 0", ratio(exact, ref["raw"], ref["scale_raw"], ref["sens_raw"], e)))
+    for width in (4, 8):  # check_geometry's rerun bar (tests/test_gpu_vertex_adjoint.py::_assert_same_run), per part
+        tol = n_parts * (1e-12 * np.abs(alone) + 1e-15 * np.abs(alone).max(axis=(1, 2), keepdims=True)) + ABS_FLOOR
+        found.append(("vertex_adjoint_batch", f"width {width} against the single calls", np.abs(atomic[width] - alone) / tol))
+    for kind, what, r in found:
+        top = worst.add(kind, r, s.seed, what)
+        if not top <= 1.0:
+            i = np.unravel_index(int(np.argmax(r)), r.shape)
+            bad.append(f"{kind} {what}: {int((~(r <= 1.0)).sum())} elements beyond the bar, worst error / tol {top:.3g} at {tuple(int(v) for v in i)}")
+    return bad
+
+
+def sweep_main(kinds, draw, check):
+    """`second` and `vertex_exact`: n seeds from seed0 in blocks of 25, the worst ratios and the soups' counts at the end."""
+    import torch  # noqa: F401  (HIP runtime load order)
+    from oracle.pyoracle import Oracle
+    n_scenes = int(sys.argv[1]) if len(sys.argv) > 1 else 40
+    seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 3000
+    worst, tally, oracle = Worst(kinds), BitTally(), Oracle("port")
+    t0 = time.time()
+    used = skipped = 0
+    mismatches = []
+    for k in range(0, n_scenes, 25):
+        u, sk, mm = run(range(seed0 + k, seed0 + min(k + 25, n_scenes)), oracle, worst, log=lambda t: print(t, flush=True),
+                        draw=draw, check=lambda s, w: check(s, w, tally))
+        used, skipped, mismatches = used + u, skipped + sk, mismatches + mm
+        print(f"... {min(k + 25, n_scenes)} of {n_scenes} seeds, {len(mismatches)} mismatches so far", flush=True)
+    print(f"{n_scenes} seeds from {seed0}: {used} used, {skipped} skipped, {len(mismatches)} mismatches, "
+          f"{worst.elements} elements compared, {time.time() - t0:.0f} s")
+    for line in worst.lines() + tally.lines():
+        print(line)
+    too_many = skipped > 0.1 * n_scenes
+    if too_many:
+        print("more than 10 % of the seeds were skipped")
+    return 1 if mismatches or too_many else 0
+
+
 def describe(s):
     return (f"{len(s.cells)} cells, {s.res[0]}x{s.res[1]}, limit {s.limit:.4g}, {s.mode}, {s.layout}, K {s.k}"
             + (", soup" if s.soup else "") + (", solid" if s.solid else "") + (", device" if s.device else "")
@@ -1296,7 +1880,8 @@ def run(seeds, oracle, worst, log=print, draw=None, check=None):
         used += 1
         for text in check(s, worst):
             mismatches.append((seed, text))
-            about = describe_geometry(s) if hasattr(s, "motion") else describe_forward(s) if hasattr(s, "regime") else describe(s)
+            about = (describe_geometry(s) if hasattr(s, "motion") else describe_forward(s) if hasattr(s, "regime")
+                     else describe_second_order(s) if hasattr(s, "compare_options") else describe(s))
             log(f"seed {seed} ({about}): {text}")
     return used, skipped, mismatches
 
@@ -1312,6 +1897,11 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "forward":
         del sys.argv[1]
         return forward_main()
+    if len(sys.argv) > 1 and sys.argv[1] in ("second", "vertex_exact"):
+        second = sys.argv[1] == "second"
+        del sys.argv[1]
+        return sweep_main(*((SECOND_KINDS, second_order_scene, check_second_order) if second
+                            else (VERTEX_EXACT_KINDS, geometry_scene, check_vertex_exact)))
     geometry = len(sys.argv) > 1 and sys.argv[1] == "geometry"
     if geometry:
         del sys.argv[1]

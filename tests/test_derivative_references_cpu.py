@@ -176,6 +176,61 @@ def test_the_scenes_cover_every_class_and_both_branches(scenes):
     assert worst[0] <= 64
 
 
+# ---- the second-order sweep's draws leave the scenes alone ---------------------------------------------------------------
+
+def _same(a, b):
+    if isinstance(a, (tuple, list)):
+        return type(a) is type(b) and len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    if isinstance(a, np.ndarray):
+        return isinstance(b, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    return type(a) is type(b) and a == b
+
+
+@pytest.mark.parametrize("seed", range(3000, 3040, 4))
+def test_second_order_scene_is_derivative_scene_with_a_full_second_split(seed):
+    """second_order_scene(seed) draws from a stream of its own: every field of derivative_scene(seed) is there bit for bit,
+    and the second split of the rows covers rows 0..ry-1 exactly once, whichever kind was drawn."""
+    base, s = df.derivative_scene(seed), df.second_order_scene(seed)
+    for name, value in vars(base).items():
+        assert _same(value, getattr(s, name)), (seed, name)
+    assert set(vars(s)) - set(vars(base)) == {"compare_options", "second_split", "second_cut"}
+    assert s.compare_options in df.COMPARE_OPTIONS and s.second_split in ("cyclic", "ranges")
+    assert 0 < s.second_cut < s.res[1] and s.second_cut % 8
+    for kind in ("cyclic", "ranges"):  # (both kinds, the drawn one included)
+        s.second_split = kind
+        rows = np.concatenate([r for _place, r in df.second_split(s)])
+        assert np.array_equal(np.sort(rows), np.arange(s.res[1])), (seed, kind)
+
+
+def test_the_second_split_covers_every_row_once_at_every_size():
+    """Every image height of the fuzz scenes (20..500) with every tile height and world derivative_scene draws, and every
+    cut off_tile_cut can return (no scene is built)."""
+    import types
+    for ry in (20, 21, 23, 24, 25, 31, 32, 33, 64, 65, 127, 263, 499, 500):
+        for cut in range(1, ry):
+            rng = types.SimpleNamespace(integers=lambda lo, hi, cut=cut: cut)
+            got = df.off_tile_cut(rng, ry)
+            assert 0 < got < ry and got % 8 and got in (cut, cut - 1)
+        for tile_rows in (1, 3, 8, 16):
+            for world in range(2, 6):
+                for kind in ("cyclic", "ranges"):
+                    s = types.SimpleNamespace(res=(40, ry), tile_rows=tile_rows, world=world, second_split=kind,
+                                              second_cut=df.off_tile_cut(np.random.default_rng([ry, tile_rows, world]), ry))
+                    rows = np.concatenate([r for _place, r in df.second_split(s)])
+                    assert np.array_equal(np.sort(rows), np.arange(ry)), (ry, tile_rows, world, kind)
+
+
+def test_the_second_order_draws_take_every_value():
+    """Over the 40 pytest seeds every walk option of the comparison context and both kinds of second split are drawn (the
+    stream alone: no scene is built)."""
+    options, kinds = set(), set()
+    for seed in range(3000, 3040):
+        rng = np.random.default_rng([seed, 0x2E0])
+        options.add(df.COMPARE_OPTIONS[int(rng.integers(len(df.COMPARE_OPTIONS)))])
+        kinds.add(("cyclic", "ranges")[int(rng.integers(2))])
+    assert options == set(df.COMPARE_OPTIONS) and kinds == {"cyclic", "ranges"}
+
+
 # ---- the geometry restatements (motion tangent, vertex tangent, vertex adjoint) ----------------------------------------
 
 # a "threshold" and an "underflow" scene (the latter a soup); 3003 and 3007 for their steep faces, a few rows each

@@ -51,6 +51,9 @@ def test_restatement_against_80_digits(seed, oracle_port):
     from tests import derivative_fuzz as df
     from tests import derivative_reference_mp as dm
     from tests import hvp_reference_mp as hm
+    """The pin covers the three modes of the fuzz scenes: among SEEDS 2027, 2014 and 2016 are "threshold" scenes (S_aa in
+    closed form just above a dz = 1/8, cells at 0.125 / dz and its neighbouring doubles), 2009 and 2000 "underflow" scenes
+    (T and E through the subnormals), the rest plain - the scenes tests/test_gpu_second_order_fuzz.py holds the kernel to."""
     s = df.derivative_scene(seed)
     assert df.qualify(s, oracle_port) is None
     rx, ry = s.res
@@ -82,6 +85,28 @@ def test_restatement_against_80_digits(seed, oracle_port):
           + ", ".join(f"{k[0]} {k[1]} {v:.3g}" for k, v in worst.items()) + "  [x 2^-52 x scale]")
     for k, v in worst.items():
         assert v <= 64, (k, v)
+
+
+@pytest.mark.parametrize("block", range(8))
+def test_restatement_is_finite_on_the_fuzz_seeds_of_the_gpu_sweep(block, oracle_port):
+    """hvp_of with direction 0 and g[0] on the 40 seeds of tests/test_gpu_second_order_fuzz.py (8 blocks of 5; the covered
+    pixels of the whole image): every result, scale and sensitivity is finite - the "underflow" scenes run T and E through
+    the subnormals - and h_alpha is not identically zero (the fewest non-zero elements: 1 in seed 3029, 21 in seed 3006)."""
+    from tests import derivative_fuzz as df
+    for seed in range(3000 + 5 * block, 3005 + 5 * block):
+        s = df.derivative_scene(seed)
+        assert df.qualify(s, oracle_port) is None
+        rx, ry = s.res
+        rows = np.unique(s.segments[0] // rx)  # (a row without a segment adds nothing)
+        m = ar.ray_matrices(s.xyz, s.cells, s.alpha, s.q, s.rots, rx, ry, B, s.limit, rows)
+        cov, mc, _ = df.covered_only(m, {})
+        da = None if s.d_alpha is None else s.d_alpha[0]
+        dq = None if s.d_q is None else s.d_q[0]
+        ha, hq, x = hr.hvp_of(mc, len(s.cells), da, dq, s.g[0][rows].reshape(-1, 2)[cov], with_scale=True)
+        assert np.isfinite(ha).all() and np.isfinite(hq).all(), seed
+        assert set(x) == {"scale_alpha", "scale_q", "sens_alpha", "sens_q"} and all(np.isfinite(v).all() for v in x.values()), seed
+        print(f"seed {seed} ({s.mode}): {int((ha != 0).sum())} non-zero elements of h_alpha, {int((hq != 0).sum())} of h_q")
+        assert (ha != 0).any(), seed
 
 
 # ---- identities on the restatement ----------------------------------------------------------------------------------
