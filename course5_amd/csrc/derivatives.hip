@@ -164,13 +164,21 @@ int adjoint_one(c5_context* ctx, const DerivativeView& v, bool squared, const fl
     return C5_OK;
 }
 
+// The exact sums' word width m for an image of res_x x res_y pixels (exact_sum.hpp), refused where it leaves too few bits.
+// ctx may be null (the pure host functions).
+int exact_word_bits(c5_context* ctx, int res_x, int res_y, int& m) {
+    m = c5::exact::word_bits(static_cast<int64_t>(res_x) * res_y);
+    if (m < c5::exact::kMinWordBits)
+        return fail(ctx, C5_ERR_INVALID, "exact sums: an image of %d x %d pixels leaves %d bits per word", res_x, res_y, m);
+    return C5_OK;
+}
+
 // The exact sums' buffer over the context's cells - 40 bytes per cell and the misfit word, allocated here at the first
 // exact call - with the word width of the WHOLE image (c5_set_image): the same for every rank of a split.
 int exact_sums(c5_context* ctx, c5::ExactSums& x) {
     const size_t n_cells = static_cast<size_t>(ctx->n_cells);
-    const int m = c5::exact::word_bits(static_cast<int64_t>(ctx->im.res_x) * ctx->im.res_y);
-    if (m < c5::exact::kMinWordBits)
-        return fail(ctx, C5_ERR_INVALID, "exact sums: an image of %d x %d pixels leaves %d bits per word", ctx->im.res_x, ctx->im.res_y, m);
+    int m;
+    if (const int rc = exact_word_bits(ctx, ctx->im.res_x, ctx->im.res_y, m)) return rc;
     C5_HIP(ctx, ctx->adj_exact.ensure(n_cells * 40 + 8));
     x = c5::ExactSums{};
     x.words = ctx->adj_exact.as<long long>();
@@ -209,11 +217,12 @@ int exact_passes(c5_context* ctx, const DerivativeView& v, c5::ExactSums x, cons
     return C5_OK;
 }
 
-// commit_derivative for a call that ran pass S: the misfit word travels to the host behind the status words
-int commit_exact(c5_context* ctx, const c5::ExactSums& x, const char* what) {
+// commit_derivative for a call that ran pass S: the misfit word (on the device: the scalar sums' or the vertex sums')
+// travels to the host behind the status words
+int commit_exact(c5_context* ctx, const unsigned* misfits, const char* what) {
     int rc = commit_derivative(ctx, what);
     if (rc) return rc;
-    C5_HIP(ctx, hipMemcpyAsync(ctx->adj_status + 4, x.misfits, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    C5_HIP(ctx, hipMemcpyAsync(ctx->adj_status + 4, misfits, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     return C5_OK;
 }
 
@@ -227,7 +236,26 @@ int exact_images(c5_context* ctx, const DerivativeView& v, int n, const float2* 
         rc = exact_passes(ctx, v, x, grad_out + j * v.n_px, true, true, j > 0, j + 1 < n, j == 0);
         if (!rc) c5::launch_exact_finish(v.s, x, v.perm, n_cells, ga_out + j * n_cells, gq_out + j * n_cells);
     }
-    return rc ? rc : commit_exact(ctx, x, what);
+    return rc ? rc : commit_exact(ctx, x.misfits, what);
+}
+
+// The Hessian-vector render's parameters: the direction into device order (the tangent's buffer: the gather is launched
+// here) and, over the view's walk, Lambda's and Lambda_dot's buffers (pass 1 -> pass 2); where the sums go is the caller's
+// to fill in.  On bin_sort_resolve's lists hvp_resolve takes hp.dir and hp.grad_out alone.
+int hvp_params(c5_context* ctx, const DerivativeView& v, const double* d_alpha, const double* d_q, const float2* grad_out,
+               c5::HvpParams& hp) {
+    C5_HIP(ctx, ctx->tan_dir.ensure(static_cast<size_t>(ctx->n_cells) * sizeof(double2)));
+    hp = c5::HvpParams{};
+    hp.dir = ctx->tan_dir.as<double2>();
+    c5::launch_tangent_gather(v.s, d_alpha, d_q, v.perm, ctx->n_cells, ctx->tan_dir.as<double2>());
+    hp.grad_out = grad_out;
+    if (v.bin_sort) return C5_OK;
+    C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
+    C5_HIP(ctx, ctx->hvp_lambda_dot.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
+    hp.w = v.w;
+    hp.lambda = ctx->adj_lambda.as<double>();
+    hp.lambda_dot = ctx->hvp_lambda_dot.as<double>();
+    return C5_OK;
 }
 
 // The exact passes of the Hessian-vector render: the direction into device order (the tangent's buffer), pass 1 (Lambda
@@ -235,24 +263,14 @@ int exact_images(c5_context* ctx, const DerivativeView& v, int n, const float2* 
 // (`sums`: cleared here first, with the misfit word) - the walk's, or hvp_resolve's over bin_sort_resolve's lists.
 int hvp_exact_passes(c5_context* ctx, const DerivativeView& v, c5::ExactSums x, const double* d_alpha, const double* d_q,
                      const float2* grad_out, bool bounds, bool sums) {
-    const size_t n_cells = static_cast<size_t>(ctx->n_cells);
-    C5_HIP(ctx, ctx->tan_dir.ensure(n_cells * sizeof(double2)));
-    double2* const dir = ctx->tan_dir.as<double2>();
-    c5::launch_tangent_gather(v.s, d_alpha, d_q, v.perm, ctx->n_cells, dir);
+    c5::HvpParams hp;
+    if (const int rc = hvp_params(ctx, v, d_alpha, d_q, grad_out, hp)) return rc;
     c5::launch_exact_clear(v.s, x, ctx->n_cells, bounds, sums, sums);
     if (v.bin_sort) {
-        if (bounds) c5::launch_hvp_exact_resolve(v.s, v.r, dir, grad_out, x, false);
-        if (sums) c5::launch_hvp_exact_resolve(v.s, v.r, dir, grad_out, x, true);
+        if (bounds) c5::launch_hvp_exact_resolve(v.s, v.r, hp.dir, grad_out, x, false);
+        if (sums) c5::launch_hvp_exact_resolve(v.s, v.r, hp.dir, grad_out, x, true);
         return C5_OK;
     }
-    C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
-    C5_HIP(ctx, ctx->hvp_lambda_dot.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
-    c5::HvpParams hp{};
-    hp.w = v.w;
-    hp.dir = dir;
-    hp.grad_out = grad_out;
-    hp.lambda = ctx->adj_lambda.as<double>();
-    hp.lambda_dot = ctx->hvp_lambda_dot.as<double>();
     c5::launch_hvp_walk(v.s, hp, 1);
     if (bounds) c5::launch_hvp_exact_walk(v.s, hp, x, false);
     x.keep_entries = 0;
@@ -301,7 +319,7 @@ int enqueue_exact_sums(c5_context* ctx, int what, const double* d_alpha, const d
     rc = exact_passes_of(ctx, v, x, what, d_alpha, d_q, image, false, true);
     if (rc) return rc;
     c5::launch_exact_emit_words(v.s, x, v.perm, ctx->n_cells, sums_a, sums_q);
-    return commit_exact(ctx, x, kExactSumsName[what]);
+    return commit_exact(ctx, x.misfits, kExactSumsName[what]);
 }
 
 // The adjoint: adjoint_one on the upstream image; with "adjoint_exact" or "exact_sums", the exact sums.
@@ -494,7 +512,7 @@ int enqueue_gn_product(c5_context* ctx, int n, const double* d_alpha, const doub
                        : adjoint_one(ctx, v, false, g, ha_out ? ha_out + j * n_cells : spare, hq_out ? hq_out + j * n_cells : spare);
             if (rc) return rc;
         }
-        return exact ? commit_exact(ctx, x, "gn product") : commit_derivative(ctx, "gn product");
+        return exact ? commit_exact(ctx, x.misfits, "gn product") : commit_derivative(ctx, "gn product");
     }
     c5::AdjointBatchParams ab{};
     if (exact) C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
@@ -524,7 +542,7 @@ int enqueue_gn_product(c5_context* ctx, int n, const double* d_alpha, const doub
         if (rc) return rc;
     }
     ctx->slots[0].head_clean = true;  // (the last chunk's pass B - or the last direction's pass S - hands every head back cleared)
-    return exact ? commit_exact(ctx, x, "gn product") : commit_derivative(ctx, "gn product");
+    return exact ? commit_exact(ctx, x.misfits, "gn product") : commit_derivative(ctx, "gn product");
 }
 
 // The motion tangent: n velocity fields (host memory, [n][12]: A row-major then b, view space) -> out[n][local_rows][res_x]:
@@ -568,9 +586,8 @@ int enqueue_motion(c5_context* ctx, int n, const double* fields, float2* out) {
 // misfit word, allocated here at the first exact vertex call - with the word width of the WHOLE image (c5_set_image).
 int vertex_exact_sums(c5_context* ctx, c5::VertexExactSums& x) {
     const size_t n_cells = static_cast<size_t>(ctx->n_cells);
-    const int m = c5::exact::word_bits(static_cast<int64_t>(ctx->im.res_x) * ctx->im.res_y);
-    if (m < c5::exact::kMinWordBits)
-        return fail(ctx, C5_ERR_INVALID, "exact sums: an image of %d x %d pixels leaves %d bits per word", ctx->im.res_x, ctx->im.res_y, m);
+    int m;
+    if (const int rc = exact_word_bits(ctx, ctx->im.res_x, ctx->im.res_y, m)) return rc;
     C5_HIP(ctx, ctx->vtx_exact.ensure(n_cells * 240 + 8));
     x = c5::VertexExactSums{};
     x.words = ctx->vtx_exact.as<long long>();
@@ -611,6 +628,25 @@ int vertex_incidence(c5_context* ctx, c5::VertexIncidence& inc) {
     return C5_OK;
 }
 
+// The vertex adjoint's parameters over the view's walk for one upstream image, and pass 1's on the same Lambda (its buffer
+// is ensured here, by adjoint_params); where the sums go (vp.face_w, or the exact sums) is the caller's to fill in.
+int vertex_params(c5_context* ctx, const DerivativeView& v, const float2* grad_out, c5::AdjointParams& ap, c5::VertexParams& vp) {
+    if (const int rc = adjoint_params(ctx, v, ap)) return rc;
+    vp = c5::VertexParams{};
+    vp.w = v.w;
+    vp.geo = v.geo;
+    vp.grad_out = grad_out;
+    vp.lambda = ap.lambda;
+    return C5_OK;
+}
+
+// nothing but solids: n gradients [n_pts][3] do not depend on any point
+int zero_vertex_grads(c5_context* ctx, const DerivativeView& v, int n, double* grad_xyz) {
+    const size_t n_pts = static_cast<size_t>(ctx->n_pts);
+    if (n_pts > 0) C5_HIP(ctx, hipMemsetAsync(grad_xyz, 0, 3 * n * n_pts * sizeof(double), v.s));
+    return C5_OK;
+}
+
 // The exact passes of the vertex adjoint over the view for one upstream image - exact_passes with the vertex kernels:
 // pass 1 (unless Lambda is there: `have_lambda`), pass E into x.exps (`bounds`: cleared here first) and pass S against
 // x.exps into x.words (`sums`: cleared here first, the misfit word with them where `first`); keep: the walk's pass S
@@ -624,14 +660,9 @@ int vertex_exact_passes(c5_context* ctx, const DerivativeView& v, c5::VertexExac
         return C5_OK;
     }
     c5::AdjointParams ap;
-    int rc = adjoint_params(ctx, v, ap);
-    if (rc) return rc;
+    c5::VertexParams vp;
+    if (const int rc = vertex_params(ctx, v, grad_out, ap, vp)) return rc;
     if (!have_lambda) c5::launch_adjoint_walk(v.s, ap, 1);
-    c5::VertexParams vp{};
-    vp.w = v.w;
-    vp.geo = v.geo;
-    vp.grad_out = grad_out;
-    vp.lambda = ap.lambda;
     if (bounds) c5::launch_vertex_exact_walk(v.s, vp, x, false);
     x.keep_entries = keep ? 1 : 0;
     if (sums) {
@@ -655,13 +686,6 @@ int vertex_exact_finish(c5_context* ctx, const DerivativeView& v, const c5::Vert
     return C5_OK;
 }
 
-// commit_exact for the vertex sums' misfit word
-int commit_vertex_exact(c5_context* ctx, const c5::VertexExactSums& x, const char* what) {
-    c5::ExactSums words{};
-    words.misfits = x.misfits;
-    return commit_exact(ctx, words, what);
-}
-
 // "vertex_exact" 1: n upstream images -> grad_xyz [n][n_pts][3], every image through passes E and S and the finish, one
 // after the other; pass 1 runs once for all of them.  "vertex_merge" has no say here.
 int vertex_exact_images(c5_context* ctx, const DerivativeView& v, int n, const float2* grad_out, double* grad_xyz, const char* what) {
@@ -672,7 +696,7 @@ int vertex_exact_images(c5_context* ctx, const DerivativeView& v, int n, const f
         rc = vertex_exact_passes(ctx, v, x, grad_out + j * v.n_px, true, true, j > 0, j + 1 < n, j == 0);
         if (!rc) rc = vertex_exact_finish(ctx, v, x, grad_xyz + 3 * j * n_pts);
     }
-    return rc ? rc : commit_vertex_exact(ctx, x, what);
+    return rc ? rc : commit_exact(ctx, x.misfits, what);
 }
 
 // c5_render_vertex_exact_bounds: pass 1 and pass E over the context's rows; the exponents in the caller's cell order
@@ -701,7 +725,7 @@ int enqueue_vertex_exact_sums(c5_context* ctx, const float2* grad_out, const int
     rc = vertex_exact_passes(ctx, v, x, grad_out, false, true, false, false, true);
     if (rc) return rc;
     c5::launch_vertex_exact_emit(v.s, x, v.perm, ctx->n_cells, nullptr, sums);
-    return commit_vertex_exact(ctx, x, "vertex exact sums");
+    return commit_exact(ctx, x.misfits, "vertex exact sums");
 }
 
 // c5_vertex_exact_finish: the per-view setup (the finish wants the points in view space), the caller's exponents and words
@@ -710,10 +734,7 @@ int enqueue_vertex_exact_finish(c5_context* ctx, const int32_t* exps, const int6
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc) return rc;
-    if (v.no_cells) {  // (solids only: no point the frame depends on)
-        if (ctx->n_pts > 0) C5_HIP(ctx, hipMemsetAsync(grad_xyz, 0, 3 * static_cast<size_t>(ctx->n_pts) * sizeof(double), v.s));
-        return C5_OK;
-    }
+    if (v.no_cells) return zero_vertex_grads(ctx, v, 1, grad_xyz);
     c5::VertexExactSums x;
     rc = vertex_exact_sums(ctx, x);
     if (rc) return rc;
@@ -722,19 +743,11 @@ int enqueue_vertex_exact_finish(c5_context* ctx, const int32_t* exps, const int6
     return rc ? rc : commit_derivative(ctx, "vertex exact finish");
 }
 
-// The vertex adjoint: the per-face weights and the view-space gradient zeroed, the adjoint's pass 1 and vertex_walk (or
-// vertex_resolve over bin_sort_resolve's lists), then vertex_finish into the caller's [n_pts][3] (the caller's point
-// order is the device's: only the cells are reordered).  With "vertex_exact": the exact sums (vertex_exact_images).
-int enqueue_vertex_adjoint(c5_context* ctx, const float2* grad_out, double* grad_xyz) {
-    DerivativeView v;
-    int rc = setup_derivative(ctx, v);
-    if (rc) return rc;
+// One vertex adjoint over the view: the per-face weights and the view-space gradient zeroed, the adjoint's pass 1 and
+// vertex_walk (or vertex_resolve over bin_sort_resolve's lists), then vertex_finish into the caller's [n_pts][3] (the
+// caller's point order is the device's: only the cells are reordered).
+int vertex_one(c5_context* ctx, const DerivativeView& v, const float2* grad_out, double* grad_xyz) {
     const size_t n_cells = static_cast<size_t>(ctx->n_cells), n_pts = static_cast<size_t>(ctx->n_pts);
-    if (v.no_cells) {  // (solids only: no point the frame depends on)
-        if (n_pts > 0) C5_HIP(ctx, hipMemsetAsync(grad_xyz, 0, 3 * n_pts * sizeof(double), v.s));
-        return C5_OK;
-    }
-    if (ctx->vertex_exact) return vertex_exact_images(ctx, v, 1, grad_out, grad_xyz, "vertex adjoint");
     C5_HIP(ctx, ctx->vtx_face.ensure(12 * n_cells * sizeof(double)));
     C5_HIP(ctx, ctx->vtx_grad.ensure(3 * n_pts * sizeof(double)));
     double* const face_w = ctx->vtx_face.as<double>();
@@ -745,27 +758,33 @@ int enqueue_vertex_adjoint(c5_context* ctx, const float2* grad_out, double* grad
         c5::launch_vertex_resolve(v.s, v.r, grad_out, face_w);
     } else {
         c5::AdjointParams ap;
-        rc = adjoint_params(ctx, v, ap);
-        if (rc) return rc;
+        c5::VertexParams vp;
+        if (const int rc = vertex_params(ctx, v, grad_out, ap, vp)) return rc;
         c5::launch_adjoint_walk(v.s, ap, 1);
-        c5::VertexParams vp{};
-        vp.w = v.w;
-        vp.geo = v.geo;
-        vp.grad_out = grad_out;
-        vp.lambda = ap.lambda;
         vp.face_w = face_w;
         c5::launch_vertex_walk(v.s, vp, ctx->vertex_merge != 0);
         ctx->slots[0].head_clean = true;  // (vertex_walk hands every head back cleared)
     }
     c5::launch_vertex_finish(v.s, v.geo, ctx->n_cells, face_w, grad_view, ctx->n_pts, ctx->view, grad_xyz);
-    return commit_derivative(ctx, "vertex adjoint");
+    return C5_OK;
+}
+
+// The vertex adjoint: vertex_one on the upstream image; with "vertex_exact", the exact sums (vertex_exact_images).
+int enqueue_vertex_adjoint(c5_context* ctx, const float2* grad_out, double* grad_xyz) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    if (v.no_cells) return zero_vertex_grads(ctx, v, 1, grad_xyz);
+    if (ctx->vertex_exact) return vertex_exact_images(ctx, v, 1, grad_out, grad_xyz, "vertex adjoint");
+    rc = vertex_one(ctx, v, grad_out, grad_xyz);
+    return rc ? rc : commit_derivative(ctx, "vertex adjoint");
 }
 
 // The batched vertex adjoint: n upstream images ([n][local_rows][res_x] float2) -> grad_xyz [n][n_pts][3] in the caller's
 // point order: one per-view setup and ONE pass 1 (Lambda does not depend on the weights), then per chunk of up to `width`
 // images the two buffers zeroed, vertex_walk_batch and the batched finish; the heads stay in place between the chunks and
-// the last walk hands them back cleared.  On bin_sort_resolve's lists: vertex_resolve and vertex_finish per image (the
-// first sorts the lists, the others find them sorted).  A batch of one is the single vertex adjoint.  Always merged
+// the last walk hands them back cleared.  On bin_sort_resolve's lists: vertex_one per image (the first sorts the lists,
+// the others find them sorted).  A batch of one is the single vertex adjoint.  Always merged
 // ("vertex_merge" is the single call's); the chunk's buffers - 96 width bytes per cell, 24 width per point - are
 // allocated here, at the first batched call.
 int enqueue_vertex_adjoint_batch(c5_context* ctx, int n, const float2* grad_out, double* grad_xyz) {
@@ -773,25 +792,13 @@ int enqueue_vertex_adjoint_batch(c5_context* ctx, int n, const float2* grad_out,
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc) return rc;
-    const size_t n_cells = static_cast<size_t>(ctx->n_cells), n_pts = static_cast<size_t>(ctx->n_pts);
-    if (v.no_cells) {  // (solids only: no point the frame depends on)
-        if (n_pts > 0) C5_HIP(ctx, hipMemsetAsync(grad_xyz, 0, 3 * n * n_pts * sizeof(double), v.s));
-        return C5_OK;
-    }
+    if (v.no_cells) return zero_vertex_grads(ctx, v, n, grad_xyz);
     // "vertex_exact": ONE pass 1, then the single exact path image by image - every slice bit for bit the single call's
     if (ctx->vertex_exact) return vertex_exact_images(ctx, v, n, grad_out, grad_xyz, "vertex adjoint batch");
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells), n_pts = static_cast<size_t>(ctx->n_pts);
     if (v.bin_sort) {
-        C5_HIP(ctx, ctx->vtx_face.ensure(12 * n_cells * sizeof(double)));
-        C5_HIP(ctx, ctx->vtx_grad.ensure(3 * n_pts * sizeof(double)));
-        double* const face_w = ctx->vtx_face.as<double>();
-        double* const grad_view = ctx->vtx_grad.as<double>();
-        for (int j = 0; j < n; ++j) {
-            C5_HIP(ctx, hipMemsetAsync(face_w, 0, 12 * n_cells * sizeof(double), v.s));
-            C5_HIP(ctx, hipMemsetAsync(grad_view, 0, 3 * n_pts * sizeof(double), v.s));
-            c5::launch_vertex_resolve(v.s, v.r, grad_out + j * v.n_px, face_w);
-            c5::launch_vertex_finish(v.s, v.geo, ctx->n_cells, face_w, grad_view, ctx->n_pts, ctx->view, grad_xyz + 3 * j * n_pts);
-        }
-        return commit_derivative(ctx, "vertex adjoint batch");
+        for (int j = 0; j < n && !rc; ++j) rc = vertex_one(ctx, v, grad_out + j * v.n_px, grad_xyz + 3 * j * n_pts);
+        return rc ? rc : commit_derivative(ctx, "vertex adjoint batch");
     }
     const int width = batch_width(ctx, n);
     const size_t face_bytes = 12 * n_cells * width * sizeof(double), grad_bytes = 3 * n_pts * width * sizeof(double);
@@ -943,27 +950,19 @@ int enqueue_hvp(c5_context* ctx, const double* d_alpha, const double* d_q, const
         if (!rc) rc = hvp_exact_passes(ctx, v, x, d_alpha, d_q, grad_out, true, true);
         if (rc) return rc;
         c5::launch_exact_finish(v.s, x, v.perm, ctx->n_cells, ha_out, hq_out);
-        return commit_exact(ctx, x, "hvp");
+        return commit_exact(ctx, x.misfits, "hvp");
     }
     const size_t n_cells = static_cast<size_t>(ctx->n_cells);
-    C5_HIP(ctx, ctx->tan_dir.ensure(n_cells * sizeof(double2)));
     C5_HIP(ctx, ctx->adj_grad.ensure(2 * n_cells * sizeof(double)));
-    double2* const dir = ctx->tan_dir.as<double2>();
     double* const ha_dev = ctx->adj_grad.as<double>();
     double* const hq_dev = ha_dev + n_cells;
-    c5::launch_tangent_gather(v.s, d_alpha, d_q, v.perm, ctx->n_cells, dir);
+    c5::HvpParams hp;
+    rc = hvp_params(ctx, v, d_alpha, d_q, grad_out, hp);
+    if (rc) return rc;
     C5_HIP(ctx, hipMemsetAsync(ha_dev, 0, 2 * n_cells * sizeof(double), v.s));
     if (v.bin_sort) {
-        c5::launch_hvp_resolve(v.s, v.r, dir, grad_out, ha_dev, hq_dev);
+        c5::launch_hvp_resolve(v.s, v.r, hp.dir, grad_out, ha_dev, hq_dev);
     } else {
-        C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
-        C5_HIP(ctx, ctx->hvp_lambda_dot.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
-        c5::HvpParams hp{};
-        hp.w = v.w;
-        hp.dir = dir;
-        hp.grad_out = grad_out;
-        hp.lambda = ctx->adj_lambda.as<double>();
-        hp.lambda_dot = ctx->hvp_lambda_dot.as<double>();
         hp.h_a = ha_dev;
         hp.h_q = hq_dev;
         c5::launch_hvp_walk(v.s, hp, 1);
@@ -985,7 +984,7 @@ int enqueue_gn_diagonal(c5_context* ctx, const float2* weight, double* da_out, d
         if (!rc) rc = exact_passes(ctx, v, x, weight, true, true, false, false, true, true);
         if (rc) return rc;
         c5::launch_exact_finish(v.s, x, v.perm, ctx->n_cells, da_out, dq_out);
-        return commit_exact(ctx, x, "gn diagonal");
+        return commit_exact(ctx, x.misfits, "gn diagonal");
     }
     rc = adjoint_one(ctx, v, true, weight, da_out, dq_out);
     return rc ? rc : commit_derivative(ctx, "gn diagonal");
@@ -1213,9 +1212,8 @@ int c5_render_adjoint_exact_sums(c5_context* ctx, const float* grad_out_host, co
 int c5_exact_sums_finish(const int32_t* exp, const int64_t* sums, int64_t n, int res_x, int res_y, double* out_fp64) {
     if (n < 0 || (n > 0 && (!exp || !sums || !out_fp64))) return fail(nullptr, C5_ERR_INVALID, "c5_exact_sums_finish: null pointer");
     if (res_x < 1 || res_y < 1) return fail(nullptr, C5_ERR_INVALID, "c5_exact_sums_finish: an image of %d x %d pixels", res_x, res_y);
-    const int m = c5::exact::word_bits(static_cast<int64_t>(res_x) * res_y);
-    if (m < c5::exact::kMinWordBits)
-        return fail(nullptr, C5_ERR_INVALID, "exact sums: an image of %d x %d pixels leaves %d bits per word", res_x, res_y, m);
+    int m;
+    if (const int rc = exact_word_bits(nullptr, res_x, res_y, m)) return rc;
     for (int64_t i = 0; i < n; ++i) out_fp64[i] = c5::exact::finish(exp[i], sums[2 * i], sums[2 * i + 1], m);
     return C5_OK;
 }
@@ -1223,9 +1221,8 @@ int c5_exact_sums_finish(const int32_t* exp, const int64_t* sums, int64_t n, int
 // Testing: the host side of exact_sum.hpp's quantise.
 int c5_exact_quantise(const double* x, int64_t n, int32_t exp, int res_x, int res_y, int64_t* words) {
     if (n < 0 || (n > 0 && (!x || !words)) || res_x < 1 || res_y < 1) return fail(nullptr, C5_ERR_INVALID, "c5_exact_quantise: bad arguments");
-    const int m = c5::exact::word_bits(static_cast<int64_t>(res_x) * res_y);
-    if (m < c5::exact::kMinWordBits)
-        return fail(nullptr, C5_ERR_INVALID, "exact sums: an image of %d x %d pixels leaves %d bits per word", res_x, res_y, m);
+    int m;
+    if (const int rc = exact_word_bits(nullptr, res_x, res_y, m)) return rc;
     int64_t misfits = 0;
     for (int64_t i = 0; i < n; ++i) misfits += !c5::exact::quantise(x[i], exp, m, words[2 * i], words[2 * i + 1]);
     if (misfits)

@@ -145,7 +145,9 @@ __global__ __launch_bounds__(256) void motion_resolve(ResolveParams R, MotionFie
 //   adjoint_walk<1>   Lambda per pixel, as for the adjoint.
 //   vertex_walk       adjoint_walk<2>'s walk; per segment the two faces from the cell's vertices (cell_faces_bary) and
 //                     +-G_k lambda added to face_w[cell][face][vertex of the face]: six atomics per segment, no slopes.
-//   vertex_resolve    the same over bin_sort_resolve's lists.
+//   vertex_resolve    the same over bin_sort_resolve's lists: adj::vertex_resolve_body, the ONE list body of the vertex
+//                     adjoint, with the sink LaneAtomics (the exact sums run it with LaneExact<SUMS>: their block below).
+//                     The body finds a segment's (cell, G, two faces); the sink, per lane, says what they become.
 //   vertex_finish     per cell: the four faces' slopes again, face_w times (-gx, -gy, 1) added to grad_view[point]; per
 //                     point: M^T grad_view, M the linear part of the view, into the caller's array.
 // Cells name the representatives of welded points, so a group's sum lands on its representative and the others stay 0.
@@ -255,9 +257,13 @@ __global__ __launch_bounds__(64) void vertex_walk(VertexParams A) {
     ray_clear_head(r, P);
 }
 
-// adjoint_resolve's frame: the same sort, the same back-to-front order; both faces of a segment from its cell's vertices.
-__global__ __launch_bounds__(256) void vertex_resolve(ResolveParams R, const float2* __restrict__ grad_out, double* __restrict__ face_w) {
-    using namespace adj;
+namespace adj {
+
+// The list body of the vertex adjoint: adjoint_resolve's frame - the same sort, the same back-to-front order - with both
+// faces of a segment from its cell's vertices.  The sink, per lane, says what a segment's (cell, G, two faces) becomes
+// (segment) and what is left to do behind the list (finish): LaneAtomics here, LaneExact<SUMS> for the exact sums below.
+template <class Sink>
+__device__ __forceinline__ void vertex_resolve_body(const ResolveParams& R, const float2* __restrict__ grad_out, Sink sk) {
     double g_tau = 0.0, g_I = 0.0;
     const ListFrame f = list_frame<true>(R, [&](int64_t lp) {
         const float2 gw = grad_out[lp];
@@ -285,9 +291,23 @@ __global__ __launch_bounds__(256) void vertex_resolve(ResolveParams R, const flo
             double p[4][3];
             load_vertices(geo, g.cell_vert[c], p);
             const CellFacesBary cf = cell_faces_bary(p, f.x, f.y);
-            if (cf.found) scatter_faces(face_w, c, G, cf);
+            if (cf.found) sk.segment(c, G, cf);
         }
     }
+    sk.finish();
+}
+
+// the lane adds its six values by itself, fp64 atomics in arrival order
+struct LaneAtomics {
+    double* __restrict__ face_w;
+    __device__ __forceinline__ void segment(int cell, double G, const CellFacesBary& cf) const { scatter_faces(face_w, cell, G, cf); }
+    __device__ __forceinline__ void finish() const {}
+};
+
+}  // namespace adj
+
+__global__ __launch_bounds__(256) void vertex_resolve(ResolveParams R, const float2* __restrict__ grad_out, double* __restrict__ face_w) {
+    adj::vertex_resolve_body(R, grad_out, adj::LaneAtomics{face_w});
 }
 
 // vertex_finish, per cell: the weights of its faces' vertices times (-gx, -gy, 1) to the points
@@ -352,7 +372,8 @@ __global__ __launch_bounds__(256) void vertex_finish_points(const double* __rest
 //                               and stages 24 int64 words;
 //                               reduce_rows_words adds them per cell into words[cell][12][2].  A value beyond its slot's
 //                               exponent is added nowhere and counted in *misfits.
-//   vertex_exact_resolve<.>     the same two over bin_sort_resolve's lists: six atomicMax or twelve integer adds per segment.
+//   vertex_exact_resolve<.>     the same two over bin_sort_resolve's lists: vertex_resolve_body with the sink LaneExact<SUMS>,
+//                               six atomicMax or twelve integer adds per segment.
 //   vertex_exact_face_w         face_w[cell][slot] = exact::finish of the slot's words: one rounding.
 //   vertex_exact_cells          per cell and local vertex the triple (sum -gx w, sum -gy w, sum w) over the faces holding
 //                               the vertex, in ascending order of the face; products and sums rounded separately; plain
@@ -364,7 +385,6 @@ __global__ __launch_bounds__(256) void vertex_finish_points(const double* __rest
 
 namespace adj {
 
-// the exponents of the three slots of face f among a cell's twelve (selects: no register is indexed)
 // a product and a sum that round by themselves, whatever stands around them (__dmul_rn / __dadd_rn are plain operators in
 // a header compiled with contraction on: the pragma takes the permission away from these two)
 __device__ __forceinline__ double mul_alone(double a, double b) {
@@ -402,6 +422,20 @@ __device__ __forceinline__ void exact_scatter_face(const VertexExactSums& X, int
         }
     }
 }
+
+// vertex_resolve_body's sink for the exact sums: pass E (SUMS false) or pass S; misfits counted per lane, added once
+template <bool SUMS>
+struct LaneExact {
+    const VertexExactSums& X;
+    unsigned bad = 0;
+    __device__ __forceinline__ void segment(int cell, double G, const CellFacesBary& cf) {
+        exact_scatter_face<SUMS>(X, cell, G, cf.out, bad);
+        exact_scatter_face<SUMS>(X, cell, -G, cf.in, bad);
+    }
+    __device__ __forceinline__ void finish() const {
+        if (SUMS && bad) atomicAdd(X.misfits, bad);
+    }
+};
 
 }  // namespace adj
 
@@ -516,46 +550,11 @@ __global__ __launch_bounds__(64) void vertex_exact_walk(VertexParams A, VertexEx
     }
 }
 
-// vertex_resolve's frame: the same sort, the same back-to-front order; six atomicMax (pass E) or twelve integer adds
-// (pass S) per segment.  Reproducible as far as the list order is (segments of equal depth).
+// vertex_resolve_body with the exact sink: pass E (SUMS false) or pass S.  Reproducible as far as the list order is
+// (segments of equal depth).
 template <bool SUMS>
 __global__ __launch_bounds__(256) void vertex_exact_resolve(ResolveParams R, const float2* __restrict__ grad_out, VertexExactSums X) {
-    using namespace adj;
-    double g_tau = 0.0, g_I = 0.0;
-    const ListFrame f = list_frame<true>(R, [&](int64_t lp) {
-        const float2 gw = grad_out[lp];
-        g_tau = gw.x;
-        g_I = gw.y;
-        return !(g_tau == 0.0 && g_I == 0.0);
-    });
-    const GridView& g = R.g;
-    const MotionGeometry geo{g.cell_vert, g.vx, g.vy, g.vz};
-    const double lam_total = lambda_total(f.list, f.n, g, R.alpha_limit);
-    double lam = 0.0, I = 0.0;
-    unsigned bad = 0;
-    for (int i = f.n - 1; i >= 0; --i) {
-        const int c = static_cast<int>(f.list[i].cell);
-        const double dz = f.list[i].dz, q = g.q[c], a_raw = g.alpha[c];
-        const ClampedAlpha ca = clamp_alpha(a_raw, R.alpha_limit);
-        double G = g_tau * a_raw;
-        if (ca.active) {
-            lam = lambda_add(lam, ca.a, dz);
-            const double T = exp(fmin(lam - lam_total, 0.0));
-            const double E = exp(-ca.a * dz);
-            G = fma(g_I * T, chord_dI(ca.a, q, E, I), G);
-            I = segment_terms(ca.a, q, dz, E, 1.0, I).I_next;
-        }
-        if (G != 0.0) {
-            double p[4][3];
-            load_vertices(geo, g.cell_vert[c], p);
-            const CellFacesBary cf = cell_faces_bary(p, f.x, f.y);
-            if (cf.found) {
-                exact_scatter_face<SUMS>(X, c, G, cf.out, bad);
-                exact_scatter_face<SUMS>(X, c, -G, cf.in, bad);
-            }
-        }
-    }
-    if (SUMS && bad) atomicAdd(X.misfits, bad);
+    adj::vertex_resolve_body(R, grad_out, adj::LaneExact<SUMS>{X});
 }
 
 // one thread per (cell, slot)
