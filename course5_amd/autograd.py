@@ -62,6 +62,10 @@ J^T W J v and gn_diagonal(ctx, alpha, q, weight) = diag(J^T W J), one library ca
 c5_render_gn_diagonal_device).  They upload the scalars as the forward does, return float64 tensors on the context's GPU
 without a graph, and raise under a differentiating torch.func transform.
 
+The shape has the same operator: vertex_gn_product(ctx, alpha, q, v_xyz, weight) = J^T W J v with J the frame's Jacobian
+in the points the context holds (render_mesh's derivative in xyz), one library call (c5_render_vertex_gn_product_device)
+with gn_product's conventions; course5_amd.fit.shape_step's CG calls it once per iteration.
+
 Second derivatives through render itself raise, but the exact second-order operator in the scalars is there as a call of
 its own: hvp(ctx, alpha, q, v_alpha, v_q, grad_img) = Hess(sum_p grad_img_p . img_p) v, one library call
 (c5_render_hvp_device), with gn_product's conventions.  course5_amd.fit.newton_product / newton_step build the exact
@@ -647,6 +651,33 @@ def gn_product(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, v_alpha,
     return (ha[0], hq[0]) if single else (ha, hq)
 
 
+def _vertex_gn_product(ctx: capi.Context, v: torch.Tensor, w, device: torch.device) -> torch.Tensor:
+    """vertex_gn_product's library call for the scalars the context holds: v float64 [K, n_pts, 3] contiguous, w float32
+    [local_rows, res_x, 2] or None, both on `device` -> float64 [K, n_pts, 3]."""
+    k = v.shape[0]
+    h = torch.empty((k, ctx.n_pts, 3), dtype=torch.float64, device=device)
+    _launch(ctx, device, lambda: ctx.render_vertex_gn_product_device(v, w, h, None, n=k))
+    return h
+
+
+def vertex_gn_product(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, v_xyz: torch.Tensor, weight=None) -> torch.Tensor:
+    """h_xyz = J^T W J v_xyz for the frame of `ctx` with the scalars alpha and q and the points the context holds, J the
+    Jacobian of the frame with respect to those points (render_mesh's derivative in xyz): v_xyz [n_pts, 3] or [K, n_pts, 3]
+    (the rows of points welded to another are not read), weight [local_rows, res_x, 2] (None: ones).  float64 on the
+    context's GPU, shaped like v_xyz, zero on points welded to another.  One library call
+    (c5_render_vertex_gn_product_device) on torch's current stream for what render_mesh's jvp, a multiply and its vjp take
+    two renders for.  With ctx.set_option("vertex_exact", 1) the sums are exact: the same bits every call, those of the
+    exact vertex adjoint of weight * fp32(J v)."""
+    device = _gn_enter(ctx, alpha, q, "vertex_gn_product")
+    if v_xyz is None or v_xyz.ndim not in (2, 3) or tuple(v_xyz.shape[-2:]) != (ctx.n_pts, 3) or v_xyz.shape[0] == 0:
+        raise ValueError(f"v_xyz must be [{ctx.n_pts}, 3] or [K, {ctx.n_pts}, 3]")
+    single = v_xyz.ndim == 2
+    with _on_gpu(ctx):
+        v = _plain(v_xyz).detach().to(device=device, dtype=torch.float64).reshape(-1, ctx.n_pts, 3).contiguous()
+        h = _vertex_gn_product(ctx, v, _gn_weight(ctx, weight, device), device)
+    return h[0] if single else h
+
+
 def gn_diagonal(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, weight=None) -> tuple:
     """(d_alpha, d_q) = diag(J^T W J), float64 [n_cells] each on the context's GPU (c5_render_gn_diagonal_device on
     torch's current stream).  With ctx.set_option("exact_sums", 1) the sums are exact: the same bits every call."""
@@ -706,4 +737,4 @@ def ray_matrix(ctx: capi.Context, with_depth: bool = False):
     return (A, z_exit[:nnz]) if with_depth else A
 
 
-__all__ = ["render", "render_view", "render_mesh", "gn_product", "gn_diagonal", "hvp", "ray_matrix"]
+__all__ = ["render", "render_view", "render_mesh", "gn_product", "gn_diagonal", "vertex_gn_product", "hvp", "ray_matrix"]

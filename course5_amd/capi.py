@@ -112,6 +112,8 @@ SIGNATURES = {
     "c5_update_points": [_vp, _dp_t, C.c_int64],
     "c5_render_vertex_tangent": [_vp, C.c_int, _dp_t, _fp_t],
     "c5_render_vertex_tangent_device": [_vp, C.c_int, _vp, _vp],
+    "c5_render_vertex_gn_product": [_vp, C.c_int, _dp_t, _fp_t, _dp_t, _fp_t],
+    "c5_render_vertex_gn_product_device": [_vp, C.c_int, _vp, _vp, _vp, _vp],
     "c5_ray_matrix_rows": [_vp, _lp_t, _lp_t],
     "c5_ray_matrix_rows_device": [_vp, _vp, _lp_t],
     "c5_ray_matrix_fill": [_vp, _lp_t, C.c_int64, _ip_t, _dp_t, _dp_t],
@@ -636,6 +638,42 @@ class Context:
             raise ValueError("out must be [K, local_rows, res_x, 2] (or give n = K with raw device pointers)")
         ptrs = _device_ptr(d_xyz, torch.float64, (k, self.n_pts, 3)), self._image_dev(out, k)
         self._check(self.lib.c5_render_vertex_tangent_device(self.handle, k, *ptrs))
+
+    # -- vertex Gauss-Newton product -----------------------------------------------------------------
+    def render_vertex_gn_product(self, d_xyz, weight=None, want_jv: bool = False):
+        """H v = J^T W J v for per-point fields v (d_xyz float64 [n_pts, 3] or [K, n_pts, 3], render_vertex_tangent's
+        conventions), J the Jacobian of the frame render() would produce now with respect to the grid's points, W =
+        diag(weight) ([local_rows, res_x, 2] float32 >= 0; None: ones): float64 [n_pts, 3] or [K, n_pts, 3] with
+        render_vertex_adjoint's conventions (0 on points welded to another); with want_jv the pair (h, J v), J v float32
+        [local_rows, res_x, 2] or [K, ...], bit for bit render_vertex_tangent's.  One call for
+        render_vertex_adjoint_batch(weight * render_vertex_tangent(v)): the same up to the order of the fp64 additions,
+        bit for bit under set_option("vertex_exact", 1).  Synchronous; retries by itself."""
+        d = np.ascontiguousarray(d_xyz, dtype=np.float64)
+        if d.ndim not in (2, 3) or d.shape[-2:] != (self.n_pts, 3) or d.shape[0] == 0:
+            raise ValueError(f"d_xyz must be [{self.n_pts}, 3] or [K, {self.n_pts}, 3], not {list(d.shape)}")
+        w = None if weight is None else self._image(weight, "weight")
+        k = 1 if d.ndim == 2 else d.shape[0]
+        h = np.zeros((k, self.n_pts, 3))
+        jv = self._images(k) if want_jv else None
+        self._check(self.lib.c5_render_vertex_gn_product(self.handle, k, _dp(d), _fp(w), _dp(h), _fp(jv)))
+        if d.ndim == 2:
+            h, jv = h[0], (jv[0] if want_jv else None)
+        return (h, jv) if want_jv else h
+
+    def render_vertex_gn_product_device(self, d_xyz, weight, h_xyz, jv_out=None, n: int | None = None):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (d_xyz and h_xyz float64 [K, n_pts,
+        3], weight float32 [local_rows, res_x, 2] or None, jv_out float32 [K, local_rows, res_x, 2] or None; contiguous) or
+        raw device pointers (then give n = K).  The status comes with the next synchronize() (C5_RETRY: run it again)."""
+        import torch
+        k = n if n is not None else (h_xyz.shape[0] if hasattr(h_xyz, "shape") and len(h_xyz.shape) == 3 else -1)
+        if k < 1:
+            raise ValueError("h_xyz must be [K, n_pts, 3] with K >= 1 (or give n = K with raw device pointers)")
+        if d_xyz is None or h_xyz is None:
+            raise ValueError("give d_xyz and h_xyz")
+        shape = (k, self.n_pts, 3)
+        ptrs = (_device_ptr(d_xyz, torch.float64, shape), self._image_dev(weight), _device_ptr(h_xyz, torch.float64, shape),
+                self._image_dev(jv_out, k))
+        self._check(self.lib.c5_render_vertex_gn_product_device(self.handle, k, *ptrs))
 
     # -- ray matrix --------------------------------------------------------------------------------
     def ray_matrix_rows(self) -> np.ndarray:

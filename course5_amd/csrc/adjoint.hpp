@@ -331,6 +331,23 @@ void launch_vertex_tangent_walk(hipStream_t s, int kc, const VertexTangentParams
 // the same over bin_sort_resolve's lists for field j of u_view [n_pts][kc][3] (sorts them in place, as launch_tangent_resolve)
 void launch_vertex_tangent_resolve(hipStream_t s, const ResolveParams& r, const double* u_view, int kc, int j, float2* out);
 
+// ---- vertex Gauss-Newton product (c5_render_vertex_gn_product*): J^T W J v for per-point fields, J the vertex tangent's map
+
+struct VertexGnWalkParams {
+    WalkParams w;          // as VertexTangentParams
+    MotionGeometry geo;
+    const double* u_view;  // [n_pts][kc][3] (launch_vertex_velocity)
+    const float2* weight;  // [n_local_rows][res_x] (w_tau, w_I), or nullptr: ones
+    double* lambda;        // [n_local_px] out: pass 1's Lambda
+    float2* g;             // [n_used][n_local_rows][res_x] out: w * (float)(tau_dot, I_dot), one fp32 multiply per channel
+    float2* jv_out;        // the same shape, out: (tau_dot, I_dot) as launch_vertex_tangent_walk stores them; or nullptr
+    int64_t image_px;      // pixels per image
+    int32_t n_used;        // fields of the chunk (<= kc)
+};
+
+// vertex_tangent_walk's walk that is also pass 1 of the adjoint: leaves the entry heads in place and counts as pass 1 does
+void launch_vertex_gn_walk_a(hipStream_t s, int kc, const VertexGnWalkParams& a);
+
 // ---- ray matrix (c5_ray_matrix_*): per pixel the cells its ray crosses and the chord of each crossing, as CSR arrays
 
 struct RayMatrixParams {

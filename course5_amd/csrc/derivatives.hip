@@ -686,17 +686,24 @@ int vertex_exact_finish(c5_context* ctx, const DerivativeView& v, const c5::Vert
     return C5_OK;
 }
 
-// "vertex_exact" 1: n upstream images -> grad_xyz [n][n_pts][3], every image through passes E and S and the finish, one
-// after the other; pass 1 runs once for all of them.  "vertex_merge" has no say here.
-int vertex_exact_images(c5_context* ctx, const DerivativeView& v, int n, const float2* grad_out, double* grad_xyz, const char* what) {
+// "vertex_exact" 1: images k0 .. k0 + n - 1 of a call of n_total upstream images (grad_out: image k0) -> rows k0 .. of
+// grad_xyz [n_total][n_pts][3], every image through passes E and S and the finish, one after the other; pass 1 runs once,
+// before the call's first image - or not at all where Lambda is there (`have_lambda`: the vertex Gauss-Newton product's
+// pass A left it).  The call's last image hands the heads back cleared, and behind it the call is committed under the name
+// `what` (commit_exact: the misfit word travels).  "vertex_merge" has no say here.
+int vertex_exact_images(c5_context* ctx, const DerivativeView& v, int n, const float2* grad_out, double* grad_xyz, const char* what,
+                        bool have_lambda = false, int k0 = 0, int n_total = -1) {
+    if (n_total < 0) n_total = n;
     c5::VertexExactSums x;
     int rc = vertex_exact_sums(ctx, x);
     const int64_t n_pts = ctx->n_pts;
     for (int j = 0; j < n && !rc; ++j) {
-        rc = vertex_exact_passes(ctx, v, x, grad_out + j * v.n_px, true, true, j > 0, j + 1 < n, j == 0);
-        if (!rc) rc = vertex_exact_finish(ctx, v, x, grad_xyz + 3 * j * n_pts);
+        const int k = k0 + j;
+        rc = vertex_exact_passes(ctx, v, x, grad_out + j * v.n_px, true, true, have_lambda || k > 0, k + 1 < n_total, k == 0);
+        if (!rc) rc = vertex_exact_finish(ctx, v, x, grad_xyz + 3 * k * n_pts);
     }
-    return rc ? rc : commit_exact(ctx, x.misfits, what);
+    if (rc || k0 + n < n_total) return rc;
+    return commit_exact(ctx, x.misfits, what);
 }
 
 // c5_render_vertex_exact_bounds: pass 1 and pass E over the context's rows; the exponents in the caller's cell order
@@ -745,8 +752,9 @@ int enqueue_vertex_exact_finish(c5_context* ctx, const int32_t* exps, const int6
 
 // One vertex adjoint over the view: the per-face weights and the view-space gradient zeroed, the adjoint's pass 1 and
 // vertex_walk (or vertex_resolve over bin_sort_resolve's lists), then vertex_finish into the caller's [n_pts][3] (the
-// caller's point order is the device's: only the cells are reordered).
-int vertex_one(c5_context* ctx, const DerivativeView& v, const float2* grad_out, double* grad_xyz) {
+// caller's point order is the device's: only the cells are reordered).  have_lambda: Lambda is there (the vertex
+// Gauss-Newton product's pass A left it, with the heads in place): pass 1 is not launched.
+int vertex_one(c5_context* ctx, const DerivativeView& v, const float2* grad_out, double* grad_xyz, bool have_lambda = false) {
     const size_t n_cells = static_cast<size_t>(ctx->n_cells), n_pts = static_cast<size_t>(ctx->n_pts);
     C5_HIP(ctx, ctx->vtx_face.ensure(12 * n_cells * sizeof(double)));
     C5_HIP(ctx, ctx->vtx_grad.ensure(3 * n_pts * sizeof(double)));
@@ -760,7 +768,7 @@ int vertex_one(c5_context* ctx, const DerivativeView& v, const float2* grad_out,
         c5::AdjointParams ap;
         c5::VertexParams vp;
         if (const int rc = vertex_params(ctx, v, grad_out, ap, vp)) return rc;
-        c5::launch_adjoint_walk(v.s, ap, 1);
+        if (!have_lambda) c5::launch_adjoint_walk(v.s, ap, 1);
         vp.face_w = face_w;
         c5::launch_vertex_walk(v.s, vp, ctx->vertex_merge != 0);
         ctx->slots[0].head_clean = true;  // (vertex_walk hands every head back cleared)
@@ -780,6 +788,33 @@ int enqueue_vertex_adjoint(c5_context* ctx, const float2* grad_out, double* grad
     return rc ? rc : commit_derivative(ctx, "vertex adjoint");
 }
 
+// The batched vertex walk over the view: its buffers (Lambda's, [n_cells][width][12] weights and [n_pts][3][width] view-space
+// sums) and its parameters but for the chunk's (grad_out, n_used, keep_entries).
+int vertex_batch_params(c5_context* ctx, const DerivativeView& v, int width, c5::VertexBatchParams& vb) {
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells), n_pts = static_cast<size_t>(ctx->n_pts);
+    C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
+    C5_HIP(ctx, ctx->vtx_bat_face.ensure(12 * n_cells * width * sizeof(double)));
+    C5_HIP(ctx, ctx->vtx_bat_grad.ensure(3 * n_pts * width * sizeof(double)));
+    vb = c5::VertexBatchParams{};
+    vb.w = v.w;
+    vb.geo = v.geo;
+    vb.image_px = v.n_px;
+    vb.lambda = ctx->adj_lambda.as<double>();
+    vb.face_w = ctx->vtx_bat_face.as<double>();
+    return C5_OK;
+}
+
+// ... and one chunk of it: the two buffers zeroed, the walk, the batched finish into rows k0 .. of the caller's array
+int vertex_chunk(c5_context* ctx, const DerivativeView& v, int width, const c5::VertexBatchParams& vb, int k0, double* grad_xyz) {
+    const size_t n_cells = static_cast<size_t>(ctx->n_cells), n_pts = static_cast<size_t>(ctx->n_pts);
+    double* const grad_view = ctx->vtx_bat_grad.as<double>();
+    C5_HIP(ctx, hipMemsetAsync(vb.face_w, 0, 12 * n_cells * width * sizeof(double), v.s));
+    C5_HIP(ctx, hipMemsetAsync(grad_view, 0, 3 * n_pts * width * sizeof(double), v.s));
+    c5::launch_vertex_walk_batch(v.s, width, vb);
+    c5::launch_vertex_finish_batch(v.s, width, v.geo, ctx->n_cells, vb.face_w, grad_view, ctx->n_pts, ctx->view, k0, vb.n_used, grad_xyz);
+    return C5_OK;
+}
+
 // The batched vertex adjoint: n upstream images ([n][local_rows][res_x] float2) -> grad_xyz [n][n_pts][3] in the caller's
 // point order: one per-view setup and ONE pass 1 (Lambda does not depend on the weights), then per chunk of up to `width`
 // images the two buffers zeroed, vertex_walk_batch and the batched finish; the heads stay in place between the chunks and
@@ -795,35 +830,24 @@ int enqueue_vertex_adjoint_batch(c5_context* ctx, int n, const float2* grad_out,
     if (v.no_cells) return zero_vertex_grads(ctx, v, n, grad_xyz);
     // "vertex_exact": ONE pass 1, then the single exact path image by image - every slice bit for bit the single call's
     if (ctx->vertex_exact) return vertex_exact_images(ctx, v, n, grad_out, grad_xyz, "vertex adjoint batch");
-    const size_t n_cells = static_cast<size_t>(ctx->n_cells), n_pts = static_cast<size_t>(ctx->n_pts);
+    const size_t n_pts = static_cast<size_t>(ctx->n_pts);
     if (v.bin_sort) {
         for (int j = 0; j < n && !rc; ++j) rc = vertex_one(ctx, v, grad_out + j * v.n_px, grad_xyz + 3 * j * n_pts);
         return rc ? rc : commit_derivative(ctx, "vertex adjoint batch");
     }
     const int width = batch_width(ctx, n);
-    const size_t face_bytes = 12 * n_cells * width * sizeof(double), grad_bytes = 3 * n_pts * width * sizeof(double);
-    C5_HIP(ctx, ctx->vtx_bat_face.ensure(face_bytes));
-    C5_HIP(ctx, ctx->vtx_bat_grad.ensure(grad_bytes));
     c5::AdjointParams ap;
+    c5::VertexBatchParams vb;
     rc = adjoint_params(ctx, v, ap);
+    if (!rc) rc = vertex_batch_params(ctx, v, width, vb);
     if (rc) return rc;
     c5::launch_adjoint_walk(v.s, ap, 1);
-    c5::VertexBatchParams vb{};
-    vb.w = v.w;
-    vb.geo = v.geo;
-    vb.image_px = v.n_px;
-    vb.lambda = ap.lambda;
-    vb.face_w = ctx->vtx_bat_face.as<double>();
-    double* const grad_view = ctx->vtx_bat_grad.as<double>();
     for (int k0 = 0; k0 < n; k0 += width) {
         vb.n_used = std::min(width, n - k0);
         vb.grad_out = grad_out + k0 * v.n_px;
         vb.keep_entries = k0 + width < n;
-        C5_HIP(ctx, hipMemsetAsync(vb.face_w, 0, face_bytes, v.s));
-        C5_HIP(ctx, hipMemsetAsync(grad_view, 0, grad_bytes, v.s));
-        c5::launch_vertex_walk_batch(v.s, width, vb);
-        c5::launch_vertex_finish_batch(v.s, width, v.geo, ctx->n_cells, vb.face_w, grad_view, ctx->n_pts, ctx->view, k0, vb.n_used,
-                                       grad_xyz);
+        rc = vertex_chunk(ctx, v, width, vb, k0, grad_xyz);
+        if (rc) return rc;
     }
     ctx->slots[0].head_clean = true;  // (the last chunk's walk hands every head back cleared)
     return commit_derivative(ctx, "vertex adjoint batch");
@@ -861,6 +885,75 @@ int enqueue_vertex_tangent(c5_context* ctx, int n, const double* d_xyz, float2* 
     }
     if (!v.bin_sort) ctx->slots[0].head_clean = true;  // (the last chunk's walk hands every head back cleared)
     return commit_derivative(ctx, "vertex tangent");
+}
+
+// The vertex Gauss-Newton product H v = J^T W J v for n per-point fields, J the vertex tangent's map: one per-view setup,
+// then per chunk of up to `width` fields vertex_velocity, pass A (vertex_gn_walk_a: the vertex tangent's walk that is also
+// the adjoint's pass 1; g = w * J v in fp32 and Lambda) and pass B on g with pass A's Lambda - pass 1 is never launched.
+// Pass B: one field goes through vertex_one ("vertex_merge" has its say), several through the batched walk and finish, and
+// under "vertex_exact" every field's g through the single exact path (vertex_exact_images) - bit for bit the exact vertex
+// adjoint of g.  The heads stay in place from pass A to pass B and between the chunks; the last pass B hands them back
+// cleared.  On bin_sort_resolve's lists: vertex_tangent_resolve -> gn_weight -> vertex_one (or the exact passes) per field.
+// jv_out may be null.
+int enqueue_vertex_gn_product(c5_context* ctx, int n, const double* d_xyz, const float2* weight, double* h_xyz, float2* jv_out) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    if (v.no_cells) {
+        rc = zero_vertex_grads(ctx, v, n, h_xyz);
+        return rc ? rc : zero_tangents(ctx, v, n, jv_out);
+    }
+    const int64_t n_px = v.n_px, n_pts = ctx->n_pts;
+    const int width = batch_width(ctx, n);
+    const bool exact = ctx->vertex_exact != 0;
+    const char* const what = "vertex gn product";
+    C5_HIP(ctx, ctx->vtx_vel.ensure(3 * static_cast<size_t>(width) * static_cast<size_t>(n_pts) * sizeof(double)));
+    double* const u_view = ctx->vtx_vel.as<double>();
+    if (v.bin_sort) {
+        C5_HIP(ctx, ctx->gn_g.ensure(2 * static_cast<size_t>(n_px) * sizeof(float2) + 16));
+        float2* const g = ctx->gn_g.as<float2>();
+        for (int k0 = 0; k0 < n; k0 += width) {
+            const int n_used = std::min(width, n - k0);
+            c5::launch_vertex_velocity(v.s, width, d_xyz, n_pts, k0, n_used, ctx->view, u_view);
+            for (int j = k0; j < k0 + n_used; ++j) {
+                float2* const t = jv_out ? jv_out + j * n_px : g + n_px;
+                c5::launch_vertex_tangent_resolve(v.s, v.r, u_view, width, j - k0, t);
+                c5::launch_gn_weight(v.s, t, weight, n_px, 1, g);
+                rc = exact ? vertex_exact_images(ctx, v, 1, g, h_xyz, what, true, j, n) : vertex_one(ctx, v, g, h_xyz + 3 * j * n_pts);
+                if (rc) return rc;
+            }
+        }
+        return exact ? C5_OK : commit_derivative(ctx, what);  // (exact: the last field's vertex_exact_images committed)
+    }
+    const bool batched = !exact && n > 1;
+    c5::VertexBatchParams vb{};
+    if (batched) rc = vertex_batch_params(ctx, v, width, vb);
+    else C5_HIP(ctx, ctx->adj_lambda.ensure(static_cast<size_t>(v.padded) * sizeof(double)));
+    if (rc) return rc;
+    C5_HIP(ctx, ctx->gn_g.ensure(static_cast<size_t>(width) * n_px * sizeof(float2) + 16));
+    c5::VertexGnWalkParams ga{};
+    ga.w = v.w;
+    ga.geo = v.geo;
+    ga.u_view = u_view;
+    ga.weight = weight;
+    ga.lambda = ctx->adj_lambda.as<double>();
+    ga.g = ctx->gn_g.as<float2>();
+    ga.image_px = n_px;
+    vb.grad_out = ga.g;
+    for (int k0 = 0; k0 < n; k0 += width) {
+        ga.n_used = vb.n_used = std::min(width, n - k0);
+        ga.jv_out = jv_out ? jv_out + k0 * n_px : nullptr;
+        vb.keep_entries = k0 + width < n;
+        c5::launch_vertex_velocity(v.s, width, d_xyz, n_pts, k0, ga.n_used, ctx->view, u_view);
+        c5::launch_vertex_gn_walk_a(v.s, width, ga);
+        if (exact) rc = vertex_exact_images(ctx, v, ga.n_used, ga.g, h_xyz, what, true, k0, n);
+        else if (batched) rc = vertex_chunk(ctx, v, width, vb, k0, h_xyz);
+        else rc = vertex_one(ctx, v, ga.g, h_xyz, true);
+        if (rc) return rc;
+    }
+    if (exact) return C5_OK;          // (the last field's pass S handed the heads back; vertex_exact_images committed)
+    ctx->slots[0].head_clean = true;  // (the last chunk's pass B hands every head back cleared)
+    return commit_derivative(ctx, what);
 }
 
 // The ray matrix's own buffer: the count per pixel ([padded] int32) and, behind them, the fill's word of changed rows.
@@ -1490,6 +1583,30 @@ int c5_render_vertex_tangent(c5_context* ctx, int n_dirs, const double* d_xyz_ho
                   {nullptr, out_host, n_dirs * image_bytes(ctx)}};
     return run_staged(ctx, "vertex tangent", b,
                       [&] { return enqueue_vertex_tangent(ctx, n_dirs, b[0].as<const double>(), b[1].as<float2>()); });
+}
+
+int c5_render_vertex_gn_product_device(c5_context* ctx, int n_dirs, const void* d_xyz_dev, const void* weight_dev, void* h_xyz_dev,
+                                       void* jv_out_dev) {
+    int rc = check_derivative(ctx, {"c5_render_vertex_gn_product", false, n_dirs, "displacement field", d_xyz_dev && h_xyz_dev, true,
+                                    "null displacement or output pointer"});
+    if (rc) return rc;
+    return enqueue_vertex_gn_product(ctx, n_dirs, static_cast<const double*>(d_xyz_dev), static_cast<const float2*>(weight_dev),
+                                     static_cast<double*>(h_xyz_dev), static_cast<float2*>(jv_out_dev));
+}
+
+int c5_render_vertex_gn_product(c5_context* ctx, int n_dirs, const double* d_xyz_host, const float* weight_host, double* h_xyz_host,
+                                float* jv_out_host) {
+    int rc = check_derivative(ctx, {"c5_render_vertex_gn_product", true, n_dirs, "displacement field", d_xyz_host && h_xyz_host, true,
+                                    "null displacement or output pointer"});
+    if (rc) return rc;
+    const size_t field_bytes = 3 * static_cast<size_t>(n_dirs) * static_cast<size_t>(ctx->n_pts) * sizeof(double);
+    Staged b[] = {{weight_host, nullptr, image_bytes(ctx)},
+                  {d_xyz_host, nullptr, field_bytes},
+                  {nullptr, h_xyz_host, field_bytes},
+                  {nullptr, jv_out_host, n_dirs * image_bytes(ctx)}};
+    return run_staged(ctx, "vertex gn product", b, [&] {
+        return enqueue_vertex_gn_product(ctx, n_dirs, b[1].as<const double>(), b[0].as<const float2>(), b[2].as<double>(), b[3].as<float2>());
+    });
 }
 
 // Waits for the stream: *nnz is valid on return.

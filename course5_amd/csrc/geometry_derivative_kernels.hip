@@ -21,7 +21,8 @@
 //
 // The vertex adjoint (c5_render_vertex_adjoint*), the motion tangent's reverse mode per grid point, its batch over K
 // upstream images (c5_render_vertex_adjoint_batch*) and the vertex tangent (c5_render_vertex_tangent*), the operator it is
-// the transpose of: their blocks further down.  The vertex adjoint's sums, single and batched, are fp64 atomics
+// the transpose of, and the vertex Gauss-Newton product (c5_render_vertex_gn_product*: the vertex tangent's walk that is
+// also the adjoint's first pass): their blocks further down.  The vertex adjoint's sums, single and batched, are fp64 atomics
 // (global_atomic_add_f64: -munsafe-fp-atomics, build.py), added in arrival order: NOT bit-reproducible - unless
 // "vertex_exact" is on: then the exact vertex adjoint sums' kernels run instead (their block below the vertex adjoint's).
 #include <type_traits>
@@ -870,12 +871,15 @@ __global__ __launch_bounds__(256) void vertex_velocity(const double* __restrict_
 }
 
 // motion_walk's frame over the per-point velocities.  The next record and the next cell's vertex ids are loaded before the
-// arithmetic, the vertices at the top of the step (vertex_walk's order).  Nothing is shared between the lanes.
-template <int KC>
-__global__ __launch_bounds__(64) void vertex_tangent_walk(VertexTangentParams A) {
+// arithmetic, the vertices at the top of the step (vertex_walk's order).  Nothing is shared between the lanes.  Params:
+// VertexTangentParams, or VertexGnWalkParams for the walk that is also adjoint_walk<1> (vertex_gn_walk_a below).
+template <int KC, class Params>
+__device__ __forceinline__ void vertex_tangent_body(const Params& A) {
     using namespace adj;
+    constexpr bool kGn = std::is_same<Params, VertexGnWalkParams>::value;
     const WalkParams& P = A.w;
     Ray r;
+    double lam = 0.0;  // (kGn) Lambda, summed as adjoint_walk<1> sums it
     double I = 0.0, I_dot[KC], tau_dot[KC];
 #pragma unroll
     for (int j = 0; j < KC; ++j) I_dot[j] = tau_dot[j] = 0.0;
@@ -914,6 +918,7 @@ __global__ __launch_bounds__(64) void vertex_tangent_walk(VertexTangentParams A)
                 tau_dot[j] = fma(a_raw, ddz[j], tau_dot[j]);                                         // d tau / d dz (raw alpha)
             }
             if (a != 0.0) {
+                if (kGn) lam = lambda_add(lam, a, dz);  // (adjoint_walk<1>: pass B's running Lambda_k ends on this to the bit)
                 const double E = exp_nonpositive(-a * dz);
                 const double dI_ddz = chord_dI(a, q, E, I);
 #pragma unroll
@@ -926,14 +931,50 @@ __global__ __launch_bounds__(64) void vertex_tangent_walk(VertexTangentParams A)
         cv = cv_nxt;
     }
 
-    if (r.in_image) {
+    if constexpr (kGn) {
+        if (r.in_image) {
+            A.lambda[r.lp] = lam;
+            const float2 w = A.weight ? A.weight[r.lp] : make_float2(1.0f, 1.0f);  // (loaded here, not held across the loop)
 #pragma unroll
-        for (int j = 0; j < KC; ++j)
-            if (j < A.n_used)
-                A.out[static_cast<size_t>(j) * A.image_px + r.lp] = make_float2(static_cast<float>(tau_dot[j]), static_cast<float>(I_dot[j]));
+            for (int j = 0; j < KC; ++j)
+                if (j < A.n_used) {
+                    const float2 t = make_float2(static_cast<float>(tau_dot[j]), static_cast<float>(I_dot[j]));
+                    if (A.jv_out) A.jv_out[static_cast<size_t>(j) * A.image_px + r.lp] = t;
+                    A.g[static_cast<size_t>(j) * A.image_px + r.lp] = make_float2(__fmul_rn(w.x, t.x), __fmul_rn(w.y, t.y));
+                }
+            // (the entry heads stay in place for pass B)
+        }
+    } else {
+        if (r.in_image) {
+#pragma unroll
+            for (int j = 0; j < KC; ++j)
+                if (j < A.n_used)
+                    A.out[static_cast<size_t>(j) * A.image_px + r.lp] = make_float2(static_cast<float>(tau_dot[j]), static_cast<float>(I_dot[j]));
+        }
+        if (!A.keep_entries) ray_clear_head(r, P);
     }
-    if (!A.keep_entries) ray_clear_head(r, P);
     ray_count(r, P);
+}
+
+template <int KC>
+__global__ __launch_bounds__(64) void vertex_tangent_walk(VertexTangentParams A) {
+    vertex_tangent_body<KC>(A);
+}
+
+// ---- vertex Gauss-Newton product (c5_render_vertex_gn_product*) -------------------------------------------------------------
+// H v = J^T W J v, J the Jacobian of the image with respect to the grid's points (the vertex tangent's map, its transpose
+// the vertex adjoint's), W a per-pixel, per-channel weight image.
+//   vertex_gn_walk_a<KC>   vertex_tangent_walk<KC>'s walk that is also adjoint_walk<1>: per pixel Lambda, and per field
+//                          g = w * (float)(tau_dot, I_dot), ONE fp32 multiply per channel - the bits a caller would get who
+//                          multiplied render_vertex_tangent's image by the weights in fp32 and handed it to
+//                          render_vertex_adjoint_batch.  A field's arithmetic is vertex_tangent_walk's: jv_out is its image
+//                          to the bit.  Leaves the entry heads in place.
+//   pass B                 vertex_walk / vertex_walk_batch<KC> / vertex_exact_walk as they are, on g and Lambda.
+// On bin_sort_resolve's lists: vertex_tangent_resolve -> gn_weight (scalar_derivative_kernels.hip) -> the vertex adjoint's
+// resolve per field.
+template <int KC>
+__global__ __launch_bounds__(64) void vertex_gn_walk_a(VertexGnWalkParams A) {
+    vertex_tangent_body<KC>(A);
 }
 
 // motion_resolve's frame over a velocity per point.  u: field `j`'s first double of point 0 in a velocity buffer of `pitch`
@@ -1055,6 +1096,10 @@ void launch_vertex_velocity(hipStream_t s, int kc, const double* d_xyz, int64_t 
 
 void launch_vertex_tangent_walk(hipStream_t s, int kc, const VertexTangentParams& v) {
     if (const unsigned blocks = tile_blocks(v.w.im)) C5_LAUNCH_KC(vertex_tangent_walk, kc, blocks, 64, s, v);
+}
+
+void launch_vertex_gn_walk_a(hipStream_t s, int kc, const VertexGnWalkParams& a) {
+    if (const unsigned blocks = tile_blocks(a.w.im)) C5_LAUNCH_KC(vertex_gn_walk_a, kc, blocks, 64, s, a);
 }
 
 void launch_vertex_tangent_resolve(hipStream_t s, const ResolveParams& r, const double* u_view, int kc, int j, float2* out) {

@@ -1,5 +1,6 @@
 """One Gauss-Newton step of a fit of the cell field (alpha, Q) to observed images (and, at the end, of a shape fit: its
-gradient, shape_gradient, and its Gauss-Newton step over the grid's points, shape_step).
+gradient, shape_gradient, and its Gauss-Newton step over the grid's points, shape_step, whose CG takes one
+autograd.vertex_gn_product per iteration).
 
     delta, models = course5_amd.fit.gn_step(ctx, alpha, q, residual, fit=("q",))
 
@@ -408,8 +409,9 @@ def shape_step(ctx, alpha, q, residual, weight=None, damping: float = 1e-3, iter
     """One Gauss-Newton step of a fit of the grid's SHAPE: up to `iters` iterations of CG from d = 0 on
         (J^T W J + damping I) d = -J^T W r
     over the points the context holds, J = d frame / d xyz at them (alpha, q the scalars), r = frame - target the residual
-    image, W the per-pixel weights ([local_rows, res_x, 2]; None: ones).  Every iteration is one vertex tangent render
-    (J p) and one vertex adjoint render (J^T W J p) on the device, float64, on torch's current stream.  free: bool [n_pts]
+    image, W the per-pixel weights ([local_rows, res_x, 2]; None: ones).  Every iteration is one vertex Gauss-Newton
+    product (autograd.vertex_gn_product: J^T W J p in one library call, the vertex adjoint of W * fp32(J p)) on the device,
+    float64, on torch's current stream.  free: bool [n_pts]
     or None (all); the points outside it stay fixed - their rows of every vector are zeroed.  Returns (d_xyz, models):
     float64 [n_pts, 3] on the context's GPU and, after every iteration done, the model 1/2 d^T (H + damping I) d +
     d^T J^T W r as a float.  It stops early when the residual of the linear system vanishes or a direction has no
@@ -433,7 +435,7 @@ def shape_step(ctx, alpha, q, residual, weight=None, damping: float = 1e-3, iter
         def JtW(img):  # J^T W img: one vertex adjoint render
             return autograd._vertex_adjoint(ctx, (img if w is None else img * w).contiguous(), device)
 
-        def H(p):  # J^T W J p: one vertex tangent render, one vertex adjoint render
-            return JtW(autograd._vertex_tangent(ctx, p.reshape(1, ctx.n_pts, 3).contiguous(), device)[0])
+        def H(p):  # J^T W J p: autograd.vertex_gn_product's one library call (the scalars are the context's already)
+            return autograd._vertex_gn_product(ctx, p.reshape(1, ctx.n_pts, 3).contiguous(), w, device)[0]
 
         return _shape_cg(lambda: JtW(r_img), H, damping, iters, free, ctx.n_pts)

@@ -695,6 +695,40 @@ int c5_vertex_exact_finish_device(c5_context* ctx, const void* exps_dev, const v
 int c5_render_vertex_tangent(c5_context* ctx, int n_dirs, const double* d_xyz_host, float* out_host);
 int c5_render_vertex_tangent_device(c5_context* ctx, int n_dirs, const void* d_xyz_dev, void* out_dev);
 
+/* --- vertex Gauss-Newton product -----------------------------------------------------------------------
+ * With J the Jacobian of the frame c5_render would produce now with respect to the coordinates of the grid's points - the
+ * map of c5_render_vertex_tangent, its transpose the map of c5_render_vertex_adjoint - and W a diagonal matrix of
+ * per-pixel, per-channel weights:
+ * c5_render_vertex_gn_product: H v = J^T W J v for n_dirs per-point fields v, the normal-equation product of a
+ * Gauss-Newton / CG fit of the SHAPE to observed images.  d_xyz [n_dirs][n_pts][3] fp64 with c5_render_vertex_tangent's
+ * conventions (the caller's point order, the coordinates of the upload; rows of welded non-representatives are never
+ * read).  weight [local_rows][res_x][2] fp32 (channel 0 weighs tau, 1 weighs I), NULL = all ones; one weight image for all
+ * fields.  h_xyz [n_dirs][n_pts][3] fp64, overwritten, with c5_render_vertex_adjoint's conventions (welded
+ * non-representatives receive exact zeros).  jv_out [n_dirs][local_rows][res_x][2] fp32 or NULL: J v, bit for bit
+ * c5_render_vertex_tangent's image.
+ * It is ONE call for what otherwise takes c5_render_vertex_tangent, a multiply and c5_render_vertex_adjoint_batch: one
+ * per-view setup, and the tangent walk leaves the adjoint's first pass (Lambda) behind - that pass is never launched.  The
+ * intermediate image is fp32 on purpose: the result is that of c5_render_vertex_adjoint_batch on grad_out = weight * (fp32
+ * image of c5_render_vertex_tangent), one fp32 multiply per channel (rounded by itself, no fma) -
+ *   "vertex_exact" 0: up to the order of the fp64 additions, and like the vertex adjoint NOT bit-reproducible from run to
+ *                     run.  One field takes the single vertex adjoint's second pass ("vertex_merge" has its say), several
+ *                     take the batch's.
+ *   "vertex_exact" 1: bit for bit; every field's weighted image goes through the single exact path, one after the other.
+ * So H is symmetric positive semidefinite for weights >= 0 up to that fp32 rounding.  On "algorithm" 1, and after a
+ * C5_RETRY onto its lists, the fields run one after the other over one per-view setup.
+ * n_dirs < 1, a NULL d_xyz or a NULL h_xyz: C5_ERR_INVALID.  A scene without cells: zeros in h_xyz and jv_out.  Row ranges
+ * and row tiles (the products of the parts sum to the whole frame's), status words, counters, retries and side effects:
+ * the batch calls' (the adjoint's counters and status words, never a frame's; a c5_render afterwards returns the bits it
+ * would have returned without it).  Memory is allocated at the first call only: the buffers of the vertex tangent, of the
+ * vertex adjoint (its batch's for n_dirs > 1, the exact sums' under "vertex_exact") and "batch_width" images.
+ * c5_render_vertex_gn_product is synchronous with host arrays and retries by itself on C5_RETRY; the _device form is
+ * asynchronous on the context's stream with device arrays, its status reported by the next call that waits for the
+ * stream.  Both refuse while c5_render_host_async frames are outstanding (C5_ERR_STATE). */
+int c5_render_vertex_gn_product(c5_context* ctx, int n_dirs, const double* d_xyz_host, const float* weight_host,
+                                double* h_xyz_host, float* jv_out_host);
+int c5_render_vertex_gn_product_device(c5_context* ctx, int n_dirs, const void* d_xyz_dev, const void* weight_dev,
+                                       void* h_xyz_dev, void* jv_out_dev);
+
 /* --- ray matrix --------------------------------------------------------------------------------------
  * The operator every derivative render applies, handed out: for each pixel the cells its ray crosses and the chord dz of
  * each crossing, as a CSR matrix A with A[pixel][cell] = dz.  Channel 0 of the image is linear in the cells' alpha:
