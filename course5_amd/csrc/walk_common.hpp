@@ -14,6 +14,8 @@ namespace c5 {
 // ------------------------------------------------------------------------------------------
 // build_records
 // ------------------------------------------------------------------------------------------
+constexpr double kEdgeOnSlope = 0x1p40;  // a face this steep against the rays is stored as edge-on (face_plane)
+
 struct FacePlane {
     double c, gx, gy;  // z = c + gx (x - x0) + gy (y - y0)
     int kind;          // +1 upper (cell body below the plane), -1 lower, 0 edge-on / flat
@@ -39,8 +41,12 @@ __device__ __forceinline__ FacePlane face_plane(const double (&p)[4][3], int f) 
     r.gx = -B / m;
     r.c = a[2] + r.gx * (x0 - a[0]) + r.gy * (y0 - a[1]);
     const double z_under_opp = r.c + r.gx * (o[0] - x0) + r.gy * (o[1] - y0);
-    const bool finite = (fabs(r.gx) <= DBL_MAX) && (fabs(r.gy) <= DBL_MAX) && (fabs(r.c) <= DBL_MAX);
-    r.kind = (!finite || !(o[2] != z_under_opp)) ? 0 : (o[2] < z_under_opp ? 1 : -1);
+    // Edge-on is |gx| + |gy| >= 2^40, not only a vanishing m: such a plane's depth at a pixel is known to eps * 2^40 * |x|,
+    // more than any cell is deep, so it says nothing about where a ray leaves (a lattice viewed along an axis through
+    // rotations by +pi/2 and -pi/2 has its vertical faces at m ~ 1e-17, slopes of 1e16: DESIGN section 5).  The
+    // comparison is false for a slope that is not finite.
+    const bool crossed = (fabs(r.gx) + fabs(r.gy) < kEdgeOnSlope) && (fabs(r.c) <= DBL_MAX);
+    r.kind = (!crossed || !(o[2] != z_under_opp)) ? 0 : (o[2] < z_under_opp ? 1 : -1);
     return r;
 }
 
@@ -357,9 +363,13 @@ __device__ __forceinline__ int next_entry(const WalkParams& P, size_t lp, EntryH
         const double we = kUp ? z : -z;
         const double slack = ldexp(P.key_slack, static_cast<int>(word >> kEntrySlackShift));
         const double key = we + slack;
-        if (key > w_cur && key < key_best && we < own_hi && key >= own_lo) {
+        // (twin entries - a pixel centre exactly on the common edge of two boundary faces of one plane - can have EQUAL
+        // keys: the lower cell id wins, not the one the raster's atomics happened to list first, so that a frame, a ray
+        // matrix's two passes and an exact sum walk the same cells call after call)
+        const int id = static_cast<int>(word & kIdMask);
+        if (key > w_cur && (key < key_best || (key == key_best && id < cell)) && we < own_hi && key >= own_lo) {
             key_best = key;
-            cell = static_cast<int>(word & kIdMask);
+            cell = id;
             w_entry = we;
         }
         if (key > key_taken + 2.0 * slack && we + 2.0 * slack < stretch_hi && we > own_lo) skipped = true;

@@ -854,8 +854,11 @@ __global__ __launch_bounds__(256, DMA ? ((SLOTS > 16 || SPLIT) ? 7 : C5_DMA_WAVE
             bool skipped = false;
             const double w_lo = slab_lo(x, y);
             if (SPLIT) w_hi = P.split.w[slab + 1] + fma(P.split.gx, x, P.split.gy * y);
-            if (SPLIT && slab > 0) {
+            if (SPLIT && slab > 0 && ent.count > 0) {
                 // where is the ray at the cutting plane?  (plane_raster; a word of another frame: nowhere inside the grid)
+                // Only a ray with a boundary entry can be inside the grid anywhere: plane_raster claims a pixel within
+                // rounding of a cell's faces, entry_raster takes closed triangles exactly, and a pixel on an edge-on
+                // silhouette that the first claims and the second does not would get the slabs above the first plane only.
                 const uint32_t pc = P.split.plane_cell[static_cast<size_t>(slab - 1) * P.split.plane_stride + lp];
                 if ((pc >> 28) == P.split.stamp) {
                     nb = static_cast<int>(pc & kIdMask);

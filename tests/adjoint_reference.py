@@ -227,6 +227,16 @@ def ray_matrices(xyz, cells, alpha, q, rots, res_x, res_y, bounds, limit: float 
     D = np.zeros((n_px, M))
     F = np.ones((n_px, M))
     C[lp, k], D[lp, k], F[lp, k] = cell, dz, np.maximum(1.0, slope)
+    return matrices_of(C, D, F, alpha, q, limit, (len(rows), res_x))
+
+
+def matrices_of(C, D, F, alpha, q, limit, shape):
+    """ray_matrices' dict from C, D, F [pixel, k] (a row's segments deepest first, C = -1 where it has none) and the scalars
+    alpha, q that C indexes: everything after the geometry.  ray_matrices indexes cells; tests/slab_reference.py the layers
+    of a layered medium."""
+    alpha, q = np.asarray(alpha, np.float64), np.asarray(q, np.float64)
+    n_px = len(C)
+    M = C.shape[1]
     valid = C >= 0
     a_raw = np.where(valid, alpha[np.maximum(C, 0)], 0.0)
     Q = np.where(valid, q[np.maximum(C, 0)], 0.0)
@@ -255,7 +265,7 @@ def ray_matrices(xyz, cells, alpha, q, rots, res_x, res_y, bounds, limit: float 
     sens_a = np.where(moves, np.abs(T * (B - D * E * I_prev)), 0.0) * F_dz
     return dict(C=C, D=D, F=F, F_dz=F_dz, valid=valid, a_raw=a_raw, a=a_eff, Q=Q, active=active, clamped=a_raw > limit, E=E, S=S,
                 B=B, T=T, I_prev=I_prev, I=I, tau=tau, abs_da=abs_da, sens_a=sens_a, sens_q=sens_q, n_px=n_px,
-                shape=(len(rows), res_x))
+                shape=tuple(shape))
 
 
 def image_gradients(xyz, cells, alpha, q, rots, res_x, res_y, bounds, weights, limit: float = 2.5, rows=None, skip=None,

@@ -1,0 +1,275 @@
+"""An analytic reference that never looks at a cell: a box lo + [0, extent] cut into n_layers equal layers along one grid
+axis, alpha and Q constant in every layer.  What a render of ANY tetrahedral cut of that box must give, whichever cells a
+ray lying in a common face, edge or vertex of the cut is said to cross - the rays on which the per-cell references
+(tests/adjoint_reference.py: segment_lists; the port oracle) mis-pair or give up.
+
+The view is the affine map p_view = R p + t that adjoint_reference.rotate applies (view_map rotates the origin and the unit
+vectors), the pixel centres are adjoint_reference.pixel_coordinates', and a ray's chord in every layer comes from the slab
+method: the ray (X, Y, z), z free, is o + z d in grid coordinates, o = R^T ((X, Y, 0) - t), d = R^T e_z; every pair of
+parallel planes lo_i <= p_i <= hi_i bounds z to an interval, and a chord is the length of the intersection of three of them.
+A ray parallel to an axis is inside iff it lies in the closed interval.
+
+slab_matrices returns adjoint_reference.ray_matrices' dict (through the shared adjoint_reference.matrices_of) with the
+LAYERS in place of the cells, so that forward_of, tangent_of, gradients_of, gn_reference.terms_of / product and
+hvp_reference.hvp_of work on it unchanged with n_cells = n_layers, scales and sensitivities included.  F_k = max(1, |gx| + |gy|)
+of the steeper of the two planes that bound segment k, a layer plane or a side of the box, from the plane's view-space
+normal R n: z = c + gx x + gy y has gx = -(R n)_x / (R n)_z.
+
+THE EDGE-ON CONTRACT.  A family of planes with F >= EDGE_ON = 2^40 says nothing about where a ray leaves a cell: dz_err x F
+exceeds any cell's extent.  It is taken as exactly edge-on - parallel to the rays: it bounds no chord, and a ray is inside
+it iff its (constant) coordinate is within SILHOUETTE = 2^-40 of the closed interval.  The pixels whose coordinate is within
+2^-40 of either end are the dict's "silhouette": they have no single answer (outside: nothing; inside: the full column, which
+is what the dict holds for them).
+
+Two more entries.  "lat" [pixel, k]: per segment, sum over the five LATERAL families of the Kuhn cut with lattice step
+`lattice` (the two lateral axes u, v and the diagonals u - v, u - w, v - w = m h; w the layer axis) of the interior lattice
+planes the ray crosses inside the segment, |floor(g_end / h) - floor(g_start / h)|, times the family's own F; an edge-on
+family adds nothing (with graze_err: a plane within that depth error x F of the segment counts as crossed).  A walk takes a chord as w_exit(cell) - w_exit(cell before); across a lateral face with the same
+scalars on both sides the face's depth error cancels between the two chords, except where it makes a sliver's chord
+negative and the walk drops that chord instead of subtracting it: an excess of at most dz_err x F_face per face crossed.
+"lateral": the same dict with lat in place of F, so that every with_scale restatement run on it returns that excess as its
+`sens`.  "graze" [pixel, layer]: F of a layer the ray misses by no more than graze_err x F in depth (its two bounds meet,
+or pass each other by that little), 0 elsewhere: a chord that is 0 here may be up to dz_err x F to whoever evaluates the
+planes, which no sensitivity of a segment covers - the segment does not exist.
+"""
+import types
+
+import numpy as np
+
+from course5_amd import meshgen as mg
+from tests import adjoint_reference as ar
+
+EDGE_ON = 2.0 ** 40
+SILHOUETTE = 2.0 ** -40
+
+
+def view_map(rots):
+    """(R, t) with rotate(p, rots) = R p + t."""
+    t = ar.rotate(np.zeros((1, 3)), rots)[0]
+    return (ar.rotate(np.eye(3), rots) - t).T, t
+
+
+def slope(nv):
+    """|gx| + |gy| of the planes with view-space normal nv: inf where they are parallel to the rays."""
+    with np.errstate(divide="ignore"):
+        return float(np.divide(abs(nv[0]) + abs(nv[1]), abs(nv[2])))
+
+
+def rays(rots, res_x, res_y, bounds, rows=None):
+    """(o [n_px, 3], d [3], R, number of rows): the rays of the global rows `rows` in grid coordinates, pixel = local row * res_x + col."""
+    R, t = view_map(rots)
+    X, Y, _sx, _sy = ar.pixel_coordinates(bounds, res_x, res_y)
+    rows = np.arange(res_y) if rows is None else np.asarray(rows)
+    xy0 = np.stack(np.broadcast_arrays(X[None, :], Y[rows][:, None], 0.0), axis=-1).reshape(-1, 3)
+    return (xy0 - t) @ R, R[2].copy(), R, len(rows)
+
+
+def slab_matrices(lo, extent, n_layers, axis, alpha, q, rots, res_x, res_y, bounds, limit=2.5, rows=None, lattice=None,
+                  graze_err=0.0):
+    """ray_matrices' dict of the box lo + [0, extent] (extent: a number or one per axis) in n_layers layers along grid axis
+    `axis` with the per-layer scalars alpha, q; C is the layer id, deepest first.  lattice: the step of the lateral
+    families counted in "lat" (default: a layer's thickness); graze_err: the chord error per unit F below which a layer
+    that a ray just misses counts as grazed.  Module docstring: "silhouette", "lat", "lateral", "graze"."""
+    lo = np.asarray(lo, np.float64)
+    hi = lo + np.broadcast_to(np.asarray(extent, np.float64), (3,))
+    o, d, R, n_rows = rays(rots, res_x, res_y, bounds, rows)
+    n_px = len(o)
+    h = (hi[axis] - lo[axis]) / n_layers
+    F_axis = [slope(R[:, i]) for i in range(3)]
+    if F_axis[axis] >= EDGE_ON:
+        raise ValueError("the layers are edge-on: a ray lying in a layer plane has no single answer")
+    inside = np.ones(n_px, bool)
+    silhouette = np.zeros(n_px, bool)
+    z_in, z_out = np.full(n_px, -np.inf), np.full(n_px, np.inf)
+    F_in, F_out = np.ones(n_px), np.ones(n_px)
+
+    def steeper(z_old, F_old, z_new, F_new, later):
+        """The bound and F of the plane that binds; the steeper of two that bind together."""
+        wins = z_new > z_old if later else z_new < z_old
+        return np.where(wins, z_new, z_old), np.where(wins, F_new, np.where(z_new == z_old, np.maximum(F_old, F_new), F_old))
+
+    for i in range(3):
+        if i == axis:
+            continue
+        if F_axis[i] >= EDGE_ON:
+            inside &= (o[:, i] >= lo[i] - SILHOUETTE) & (o[:, i] <= hi[i] + SILHOUETTE)
+            silhouette |= (np.abs(o[:, i] - lo[i]) <= SILHOUETTE) | (np.abs(o[:, i] - hi[i]) <= SILHOUETTE)
+            continue
+        za, zb = (lo[i] - o[:, i]) / d[i], (hi[i] - o[:, i]) / d[i]
+        Fi = max(1.0, F_axis[i])
+        z_in, F_in = steeper(z_in, F_in, np.minimum(za, zb), Fi, True)
+        z_out, F_out = steeper(z_out, F_out, np.maximum(za, zb), Fi, False)
+    # the layer planes in ascending depth; segment j lies between planes j and j + 1
+    layers = np.arange(n_layers)
+    planes = (lo[axis] + h * np.arange(n_layers + 1) - o[:, axis:axis + 1]) / d[axis]
+    planes[:, -1] = (hi[axis] - o[:, axis]) / d[axis]
+    if d[axis] < 0:
+        planes, layers = planes[:, ::-1], layers[::-1]
+    Fl = max(1.0, F_axis[axis])
+    start, F_start = steeper(z_in[:, None], F_in[:, None], planes[:, :-1], Fl, True)
+    end, F_end = steeper(z_out[:, None], F_out[:, None], planes[:, 1:], Fl, False)
+    D = np.where(inside[:, None], np.maximum(end - start, 0.0), 0.0)
+    valid = D > 0
+    F_seg = np.maximum(F_start, F_end)
+    graze = np.zeros((n_px, n_layers))
+    graze[:, layers] = np.where(inside[:, None] & ~valid & (end - start >= -graze_err * F_seg), F_seg, 0.0)
+    # interior lattice planes of the lateral families crossed inside each segment
+    hl = h if lattice is None else float(lattice)
+    u, v = (i for i in range(3) if i != axis)
+    lat = np.zeros_like(D)
+    ps = (o[:, None, :] + np.where(valid, start, 0.0)[..., None] * d) - lo
+    pe = (o[:, None, :] + np.where(valid, end, 0.0)[..., None] * d) - lo
+    for plus, minus in ((u, None), (v, None), (u, v), (u, axis), (v, axis)):
+        nv = R[:, plus] - (0.0 if minus is None else R[:, minus])
+        Ff = slope(nv)
+        if Ff >= EDGE_ON:
+            continue
+        gs, ge = (p[..., plus] - (0.0 if minus is None else p[..., minus]) for p in (ps, pe))
+        # (a plane the ray passes within its depth error counts as crossed: graze_err F in depth is graze_err (|n_x| + |n_y|)
+        # <= 2 graze_err in g, whose gradient along the ray is n_z)
+        reach = 2.0 * graze_err
+        lat += (np.floor((np.maximum(gs, ge) + reach) / hl) - np.floor((np.minimum(gs, ge) - reach) / hl)) * max(1.0, Ff)
+    # the segments of a row first, deepest first
+    order = np.argsort(~valid, axis=1, kind="stable")
+    take = lambda a: np.take_along_axis(np.broadcast_to(a, D.shape), order, axis=1)  # noqa: E731
+    valid = take(valid)
+    C = np.where(valid, take(layers[None, :]), -1)
+    D = np.where(valid, take(D), 0.0)
+    F = np.where(valid, take(F_seg), 1.0)
+    lat = np.where(valid, take(lat), 0.0)
+    M = max(1, int(valid.sum(1).max()) if n_px else 1)
+    C, D, F, lat = C[:, :M], D[:, :M], F[:, :M], lat[:, :M]
+    m = ar.matrices_of(C, D, F, alpha, q, limit, (n_rows, res_x))
+    m["lat"] = lat
+    m["lateral"] = ar.matrices_of(C, D, lat, alpha, q, limit, (n_rows, res_x))
+    m["silhouette"] = silhouette & m["valid"].any(1)
+    m["graze"] = graze
+    return m
+
+
+def layers_of_cells(mc, layer_of_cell, alpha, q, limit=2.5):
+    """ray_matrices' dict mc of a layered grid restated per LAYER with the cell restatement's own chords: the consecutive
+    segments of a ray that lie in one layer become one, their chords added, F the largest among them.  What the slab dict
+    is when both take the same chords: the two differ by the rounding of the recurrences alone."""
+    C, D, F, valid = mc["C"], mc["D"], mc["F"], mc["valid"]
+    L = np.where(valid, np.asarray(layer_of_cell)[np.maximum(C, 0)], -1)
+    first = valid.copy()
+    first[:, 1:] &= L[:, 1:] != L[:, :-1]
+    k = np.cumsum(first, axis=1) - 1
+    M = max(1, int(k.max()) + 1)
+    P = np.broadcast_to(np.arange(len(C))[:, None], C.shape)
+    at = P[valid], k[valid]
+    Cl, Dl, Fl = np.full((len(C), M), -1), np.zeros((len(C), M)), np.ones((len(C), M))
+    Cl[at] = L[valid]
+    np.add.at(Dl, at, D[valid])
+    np.maximum.at(Fl, at, F[valid])
+    return ar.matrices_of(Cl, Dl, Fl, alpha, q, limit, mc["shape"])
+
+
+def layer_sums(per_cell, layer_of_cell, n_layers):
+    """P^T g: a per-cell result summed over each layer's cells (the layer is a linear map P from layer to cell values)."""
+    return np.bincount(layer_of_cell, weights=np.asarray(per_cell, np.float64), minlength=n_layers)
+
+
+# ---- the scenes of tests/test_slab_reference_cpu.py and tests/test_gpu_degenerate_rays.py ----------------------------------
+# Dyadic coordinates: at the exact alignment every edge function of a pixel centre is exact in fp64.
+LO, SIZE, LIMIT = (0.5, -0.5, -0.5), 1.0, 2.5
+BOUNDS, RES = (2.0, 0.0, 1.0, -1.0), (65, 65)  # pixel step 1/32
+IDENTITY = np.zeros((0, 3))
+TILTS = (2.0 ** -10, 2.0 ** -20, 2.0 ** -30)
+
+
+def layer_scalars(n):
+    """Per-layer (alpha, Q): a layer with alpha 0, one above the limit, one equal to it, one with Q = 0, the rest in
+    [0.1, limit); nothing in [DBL_EPSILON, 1e-6), where the reference's recurrence is its own noise.  With fewer than four
+    layers the classes that fit, in this order: rest, 0, above, equal."""
+    rng = np.random.default_rng([n, 0x51AB])
+    alpha, q = rng.uniform(0.1, LIMIT, n), rng.uniform(0.2, 2.0, n)
+    for at, value in ((1, 0.0), (2, 1.4 * LIMIT), (3, LIMIT)):
+        if at < n:
+            alpha[at] = value
+    q[0] = 0.0 if n > 1 else q[0]
+    return alpha, q
+
+
+def _scene(name, xyz, cells, rots, axis=2, n=4, res=RES, lattice=None, lo=LO, alpha_q=None, absent=(), derivatives=False):
+    """A scene: the grid, the view, the layer of every cell (by its centroid), per-layer and per-cell scalars.  absent:
+    layers without cells, alpha = Q = 0 in the reference."""
+    s = types.SimpleNamespace(name=name, xyz=xyz, cells=np.asarray(cells), rots=np.asarray(rots, np.float64).reshape(-1, 3),
+                              axis=axis, n_layers=n, res=res, bounds=BOUNDS, limit=LIMIT, lo=lo, extent=SIZE,
+                              lattice=SIZE / n if lattice is None else lattice, derivatives=derivatives)
+    h = SIZE / n
+    s.layer_of_cell = np.floor((xyz[s.cells].mean(1)[:, axis] - lo[axis]) / h).astype(np.int64)
+    assert s.layer_of_cell.min() >= 0 and s.layer_of_cell.max() < n
+    s.alpha_l, s.q_l = layer_scalars(n) if alpha_q is None else alpha_q
+    s.alpha, s.q = s.alpha_l[s.layer_of_cell], s.q_l[s.layer_of_cell]  # (what the cells carry)
+    s.present = np.ones(n, bool)
+    s.present[list(absent)] = False
+    s.alpha_ref, s.q_ref = np.where(s.present, s.alpha_l, 0.0), np.where(s.present, s.q_l, 0.0)
+    assert set(np.unique(s.layer_of_cell)) == set(np.flatnonzero(s.present))
+    return s
+
+
+def matrices(s, rows=None, graze_err=0.0):
+    """slab_matrices of a scene."""
+    return slab_matrices(s.lo, s.extent, s.n_layers, s.axis, s.alpha_ref, s.q_ref, s.rots, s.res[0], s.res[1], s.bounds, s.limit,
+                         rows, s.lattice, graze_err)
+
+
+def _permuted(xyz, cells):
+    """(x, y, z) -> (y + 1, z, x - 1): the box stays where it is, what was an x = const plane is a z = const plane."""
+    p = np.stack([xyz[:, 1] + 1.0, xyz[:, 2], xyz[:, 0] - 1.0], axis=1)
+    return p, mg.orient_positive(p, cells)
+
+
+def _tilt(about, angle):
+    return {"x": [[0.0, angle, 0.0]], "y": [[1.0, angle, 1.0]], "xy": [[0.0, angle, 0.0], [1.0, angle, 1.0]]}[about]
+
+
+def degenerate_scenes():
+    """name -> a function that builds the scene (tests/test_gpu_degenerate_rays.py's docstring has the table)."""
+    a = lambda: mg.kuhn_box(4, lo=LO, size=SIZE)  # noqa: E731
+    generic = mg.view_rotations(0.37, -0.61)
+    out = {
+        "A": lambda: _scene("A", *a(), IDENTITY, derivatives=True),
+        "B": lambda: _scene("B", *mg.kuhn_box(32, lo=LO, size=SIZE), IDENTITY, n=32),
+        "C": lambda: _scene("C", *mg.cube8(LO, SIZE), IDENTITY, n=1),
+        "D": lambda: _scene("D", *mg.kuhn_box(4, lo=LO, size=SIZE, keep=lambda cen: np.floor((cen[:, 2] - LO[2]) * 4) != 2),
+                            IDENTITY, absent=(2,), derivatives=True),
+        "F": lambda: _scene("F", *mg.per_cell_point_copies(*a()), IDENTITY),
+        "G": lambda: _scene("G", *a(), mg.view_rotations(0.0, 0.0), derivatives=True),
+        "G-B": lambda: _scene("G-B", *mg.kuhn_box(32, lo=LO, size=SIZE), mg.view_rotations(0.0, 0.0), n=32),
+        "H": lambda: _scene("H", *a(), generic),
+    }
+    for weld in (True, False):
+        def e(weld=weld, permute=False):
+            xyz, cells, _ = mg.refined_interface(4, 2, 4, lo=LO, size=SIZE, jitter=0.0, warp=0.0, weld=weld)
+            if permute:
+                xyz, cells = _permuted(xyz, cells)
+            return _scene(f"E-{'z' if permute else 'x'}-{'welded' if weld else 'unwelded'}", xyz, cells, IDENTITY, lattice=SIZE / 8,
+                          derivatives=weld)
+        out[f"E-x-{'welded' if weld else 'unwelded'}"] = e
+        out[f"E-z-{'welded' if weld else 'unwelded'}"] = lambda e=e: e(permute=True)
+    for axis in range(3):
+        for about in ("x", "y", "xy"):
+            if (axis, about) in ((0, "x"), (1, "y")):  # (the layer planes would stay edge-on)
+                continue
+            for p, angle in zip((10, 20, 30), TILTS):
+                name = f"I-{'xyz'[axis]}-{about}-{p}"
+                out[name] = lambda axis=axis, about=about, angle=angle, name=name: _scene(
+                    name, *a(), _tilt(about, angle), axis=axis, derivatives=name == "I-z-xy-10")
+    return out
+
+
+def edge_pixels(s):
+    """bool [res_y, res_x]: the pixel centres on a projected edge of the Kuhn cut at the exact alignment - on a line
+    x = m h, y = m h or x - y = m h of the lattice with step s.lattice - inside the closed footprint.  Integer
+    arithmetic on the pixel indices: the step divides the lattice."""
+    rx, ry = s.res
+    X, Y, sx, sy = ar.pixel_coordinates(s.bounds, rx, ry)
+    i = np.rint((X - s.lo[0]) / sx).astype(np.int64)[None, :]
+    j = np.rint((Y - s.lo[1]) / sy).astype(np.int64)[:, None]
+    k = int(round(s.lattice / sx))
+    assert k * sx == s.lattice and sx == sy
+    inside = (i >= 0) & (i <= round(s.extent / sx)) & (j >= 0) & (j <= round(s.extent / sx))
+    return inside & ((i % k == 0) | (j % k == 0) | ((i - j) % k == 0))

@@ -82,7 +82,7 @@ def test_argument_checks_raise_before_the_library():
 def test_device_sources_hash_and_abi_version_stay():
     from course5_amd import build
     assert build.DEVICE_SOURCES == ("device_types.hpp", "kernels.hpp", "walk_common.hpp", "exact_kernels.hip", "walk_kernels.hip")
-    assert build.kernel_source_hash() == "85a78f3eaf095461"
+    assert build.kernel_source_hash() == "688bc525360ea908"
     assert ctypes.CDLL(capi.LIB_PATH).c5_abi_version() == 2
 
 
