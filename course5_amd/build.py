@@ -35,7 +35,10 @@ LIB_SOURCES = [
     ("context.hip", []),
     ("grid.hip", []),
     ("frame.hip", []),
-    ("derivatives.hip", []),
+    ("derivative_setup.hip", []),
+    ("scalar_derivatives.hip", []),
+    ("geometry_derivatives.hip", []),
+    ("ray_matrix.hip", []),
     ("host_ring.hip", []),
     ("adjacency.cpp", ["-x", "c++", "-fopenmp"]),
 ]

@@ -238,14 +238,9 @@ void c5_destroy(c5_context* ctx) {
     if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
     DeviceBuffer* bufs[] = {&ctx->px, &ctx->py, &ctx->pz, &ctx->cell_vert, &ctx->cell_adj, &ctx->alpha,
                             &ctx->q, &ctx->bface, &ctx->xtab, &ctx->ytab, &ctx->out, &ctx->sticky,
-                            &ctx->offs64, &ctx->scratch64, &ctx->segs, &ctx->adj_lambda, &ctx->adj_counters,
-                            &ctx->adj_sticky, &ctx->adj_grad, &ctx->adj_perm, &ctx->tan_dir,
-                            &ctx->bat_dirs, &ctx->bat_grad, &ctx->gn_g, &ctx->gn_spare, &ctx->deriv_io,
-                            &ctx->scal_stats, &ctx->vtx_face, &ctx->vtx_grad, &ctx->vtx_vel, &ctx->rm_count, &ctx->hvp_lambda_dot,
-                            &ctx->adj_exact, &ctx->vtx_bat_face, &ctx->vtx_bat_grad, &ctx->vtx_exact, &ctx->vtx_triples,
-                            &ctx->vtx_inc};
+                            &ctx->offs64, &ctx->scratch64, &ctx->segs, &ctx->adj_perm, &ctx->scal_stats};
+    ctx->deriv.release();
     if (ctx->host_sticky) (void)hipHostFree(ctx->host_sticky);
-    if (ctx->adj_status) (void)hipHostFree(ctx->adj_status);
     if (ctx->scal_host) (void)hipHostFree(ctx->scal_host);
     if (ctx->host_sb) (void)hipHostFree(ctx->host_sb);
     for (DeviceBuffer* b : bufs) b->release();
@@ -561,17 +556,17 @@ int c5_set_option(c5_context* ctx, const char* name, double value) {
         ctx->view_cache = static_cast<int>(value) != 0;
     } else if (n == "batch_width") {
         if (value != 0 && value != 4 && value != 8) return fail(ctx, C5_ERR_INVALID, "batch_width must be 0 (by the batch), 4 or 8");
-        ctx->batch_width = static_cast<int>(value);
+        ctx->deriv.batch_width = static_cast<int>(value);
     } else if (n == "vertex_merge") {
-        ctx->vertex_merge = static_cast<int>(value) != 0;
+        ctx->deriv.vertex_merge = static_cast<int>(value) != 0;
     } else if (n == "adjoint_exact") {
-        ctx->adjoint_exact = static_cast<int>(value) != 0;
+        ctx->deriv.adjoint_exact = static_cast<int>(value) != 0;
     } else if (n == "exact_sums") {
         if (value != 0 && value != 1) return fail(ctx, C5_ERR_INVALID, "exact_sums must be 0 (fp64 atomics) or 1");
-        ctx->exact_sums = static_cast<int>(value);
+        ctx->deriv.exact_sums = static_cast<int>(value);
     } else if (n == "vertex_exact") {
         if (value != 0 && value != 1) return fail(ctx, C5_ERR_INVALID, "vertex_exact must be 0 (fp64 atomics) or 1");
-        ctx->vertex_exact = static_cast<int>(value);
+        ctx->deriv.vertex_exact = static_cast<int>(value);
     } else if (n == "split_tilt_x" || n == "split_tilt_y") {  // testing: tilt of a forced split's planes
         if (!(std::fabs(value) < 64.0)) return fail(ctx, C5_ERR_INVALID, "split tilt out of range");
         (n == "split_tilt_x" ? ctx->split_tilt_x : ctx->split_tilt_y) = value;

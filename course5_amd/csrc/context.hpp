@@ -145,6 +145,69 @@ struct FrameSlot {
     hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
+// Everything the derivative renders keep on the context (derivative_host.hpp and the files over it): buffers, options,
+// and the status of the last call.
+struct DerivativeState {
+    // adjoint render (c5_render_adjoint*): nothing of it is allocated before the first adjoint call
+    DeviceBuffer adj_lambda;    // [n_local_px] fp64: pass 1 -> pass 2 (scalar_derivative_kernels.hip)
+    DeviceBuffer adj_counters;  // the adjoint's own FrameCounters: a frame's statistics and failure words stay the frame's
+    DeviceBuffer adj_sticky;    // the entry raster's failure words for the adjoint (never the frames' sticky words)
+    DeviceBuffer adj_grad;      // [2][n_cells] fp64, device order
+    unsigned* adj_status = nullptr;  // pinned: walk_overflow, entry_overflow, overlap_rays of the last adjoint or tangent,
+                                     // rows a ray matrix fill found changed, contributions an exact sum found beyond their exponent
+    bool adjoint_pending = false;    // its status has not been looked at yet
+    const char* adj_what = "adjoint";  // which of the two it was (finish_adjoint's messages)
+
+    // exact adjoint sums ("adjoint_exact", c5_render_adjoint_exact_*): allocated at the first exact call only
+    int adjoint_exact = 0;           // "adjoint_exact": c5_render_adjoint* and its batch return the exact sums (exact_sum.hpp)
+    int exact_sums = 0;              // "exact_sums": the adjoint, c5_render_gn_* and c5_render_hvp* return the exact sums
+    DeviceBuffer adj_exact;   // [n_cells][4] int64 words, [n_cells] int2 exponents (device order), then the misfit word
+
+    // tangent render (c5_render_tangent*): shares the adjoint's counters, sticky and status words; nothing of
+    // it is allocated before the first tangent call
+    DeviceBuffer tan_dir;  // [n_cells] {dalpha, dQ} fp64, device order (scalar_derivative_kernels.hip: tangent_gather)
+
+    // batches (c5_render_tangent_batch*, c5_render_adjoint_batch*): nothing of it is allocated before the first batch call
+    int batch_width = 0;    // "batch_width": directions or upstream images per walk (0: 4 for batches of up to 4, else 8)
+    DeviceBuffer bat_dirs;  // [n_cells][width] {dalpha, dQ} fp64, device order (scalar_derivative_kernels.hip: tangent_gather_batch)
+    DeviceBuffer bat_grad;  // [n_cells][2 width] fp64, device order (adjoint_walk_batch)
+    // Gauss-Newton renders (c5_render_gn_product*, c5_render_gn_diagonal*): nothing of it is allocated before the first call
+    DeviceBuffer gn_g;      // [width][n_local_px] float2: pass A's w * J v, pass B's upstream images (a chunk's)
+    DeviceBuffer gn_spare;  // [width][n_cells] fp64: where the block of H v goes that the caller did not ask for
+    // Hessian-vector render (c5_render_hvp*): shares adj_lambda, adj_grad and tan_dir; allocated at the first call only
+    DeviceBuffer hvp_lambda_dot;  // [n_local_px] fp64: pass 1 -> pass 2 (scalar_derivative_kernels.hip: hvp_walk)
+    // vertex adjoint (c5_render_vertex_adjoint*): nothing of it is allocated before the first call (it shares adj_lambda)
+    DeviceBuffer vtx_face;  // [n_cells][4][3] fp64, device order: the chords' weights per face and vertex of the face
+    DeviceBuffer vtx_grad;  // [n_pts][3] fp64: the gradient in view space
+    int vertex_merge = 1;          // "vertex_merge": vertex_walk sums the lanes of a wavefront in one cell before its atomics
+                                   // (measured on the C3 frame: 5.7 ms against 58 ms for the walk; profiles/vertex_adjoint_probe.md)
+    // batched vertex adjoint (c5_render_vertex_adjoint_batch*): allocated at the first batched call only
+    DeviceBuffer vtx_bat_face;  // [n_cells][width][4][3] fp64, device order: vtx_face per image of a chunk
+    DeviceBuffer vtx_bat_grad;  // [n_pts][3][width] fp64: vtx_grad per image of a chunk, the images of a component side by side
+    // exact vertex adjoint sums ("vertex_exact", c5_render_vertex_exact_*): allocated at the first exact vertex call only
+    int vertex_exact = 0;              // "vertex_exact": c5_render_vertex_adjoint* and its batch return the exact sums
+    DeviceBuffer vtx_exact;     // [n_cells][12][2] int64 words, [n_cells][12] int32 exponents (device order), the misfit word
+    DeviceBuffer vtx_triples;   // [n_cells][4][3] fp64, device order: a cell's share of its four vertices' view-space gradient
+    DeviceBuffer vtx_inc;       // point -> (cell, vertex) incidence, CSR: int32 [n_pts + 1] offsets, int32 [4 n_cells] entries
+    uint64_t vtx_inc_serial = ~uint64_t{0};  // ... for the grid of this upload (c5_context::grid_serial; kept across c5_update_points)
+    // vertex tangent (c5_render_vertex_tangent*): allocated at the first call only
+    DeviceBuffer vtx_vel;   // [n_pts][width][3] fp64: the points' view-space velocities (vertex_velocity)
+    // ray matrix (c5_ray_matrix_*): allocated at the first call only (the scan's scratch is bin_sort_resolve's scratch64)
+    DeviceBuffer rm_count;  // [padded local px] int32 segments per pixel, then one word: rows the fill found changed
+    // the host-pointer forms of all derivative renders: what the caller hands in and what goes back (run_staged)
+    DeviceBuffer io;
+
+    // Frees everything above that is owned: every buffer, and the pinned status words.
+    void release() {
+        DeviceBuffer* const owned[] = {&adj_lambda, &adj_counters, &adj_sticky, &adj_grad, &adj_exact, &tan_dir, &bat_dirs, &bat_grad,
+                                       &gn_g, &gn_spare, &hvp_lambda_dot, &vtx_face, &vtx_grad, &vtx_bat_face, &vtx_bat_grad,
+                                       &vtx_exact, &vtx_triples, &vtx_inc, &vtx_vel, &rm_count, &io};
+        for (DeviceBuffer* b : owned) b->release();
+        if (adj_status) (void)hipHostFree(adj_status);
+        adj_status = nullptr;
+    }
+};
+
 }  // namespace c5api
 
 struct c5_context {
@@ -263,59 +326,12 @@ struct c5_context {
     bool frame_timed = false;
     c5_stats last{};
 
-    // adjoint render (c5_render_adjoint*): nothing of it is allocated before the first adjoint call
-    c5api::DeviceBuffer adj_lambda;    // [n_local_px] fp64: pass 1 -> pass 2 (scalar_derivative_kernels.hip)
-    c5api::DeviceBuffer adj_counters;  // the adjoint's own FrameCounters: a frame's statistics and failure words stay the frame's
-    c5api::DeviceBuffer adj_sticky;    // the entry raster's failure words for the adjoint (never the frames' sticky words)
-    c5api::DeviceBuffer adj_grad;      // [2][n_cells] fp64, device order
-    c5api::DeviceBuffer adj_perm;      // cell_perm on the device, for the grid of upload adj_perm_serial
+    c5api::DerivativeState deriv;      // the derivative renders' buffers, options and status (derivative_host.hpp)
+    c5api::DeviceBuffer adj_perm;      // cell_perm on the device, for the grid of upload adj_perm_serial (grid.hip: ensure_device_perm)
     uint64_t grid_serial = 0, adj_perm_serial = ~uint64_t{0};
-    unsigned* adj_status = nullptr;  // pinned: walk_overflow, entry_overflow, overlap_rays of the last adjoint or tangent,
-                                     // rows a ray matrix fill found changed, contributions an exact sum found beyond their exponent
-    bool adjoint_pending = false;    // its status has not been looked at yet
-    const char* adj_what = "adjoint";  // which of the two it was (finish_adjoint's messages)
-
-    // exact adjoint sums ("adjoint_exact", c5_render_adjoint_exact_*): allocated at the first exact call only
-    int adjoint_exact = 0;           // "adjoint_exact": c5_render_adjoint* and its batch return the exact sums (exact_sum.hpp)
-    int exact_sums = 0;              // "exact_sums": the adjoint, c5_render_gn_* and c5_render_hvp* return the exact sums
-    c5api::DeviceBuffer adj_exact;   // [n_cells][4] int64 words, [n_cells] int2 exponents (device order), then the misfit word
-
-    // tangent render (c5_render_tangent*): shares the adjoint's counters, sticky and status words and adj_perm; nothing of
-    // it is allocated before the first tangent call
-    c5api::DeviceBuffer tan_dir;  // [n_cells] {dalpha, dQ} fp64, device order (scalar_derivative_kernels.hip: tangent_gather)
-
-    // batches (c5_render_tangent_batch*, c5_render_adjoint_batch*): nothing of it is allocated before the first batch call
-    int batch_width = 0;    // "batch_width": directions or upstream images per walk (0: 4 for batches of up to 4, else 8)
-    c5api::DeviceBuffer bat_dirs;  // [n_cells][width] {dalpha, dQ} fp64, device order (scalar_derivative_kernels.hip: tangent_gather_batch)
-    c5api::DeviceBuffer bat_grad;  // [n_cells][2 width] fp64, device order (adjoint_walk_batch)
-    // Gauss-Newton renders (c5_render_gn_product*, c5_render_gn_diagonal*): nothing of it is allocated before the first call
-    c5api::DeviceBuffer gn_g;      // [width][n_local_px] float2: pass A's w * J v, pass B's upstream images (a chunk's)
-    c5api::DeviceBuffer gn_spare;  // [width][n_cells] fp64: where the block of H v goes that the caller did not ask for
-    // Hessian-vector render (c5_render_hvp*): shares adj_lambda, adj_grad and tan_dir; allocated at the first call only
-    c5api::DeviceBuffer hvp_lambda_dot;  // [n_local_px] fp64: pass 1 -> pass 2 (scalar_derivative_kernels.hip: hvp_walk)
-    // vertex adjoint (c5_render_vertex_adjoint*): nothing of it is allocated before the first call (it shares adj_lambda)
-    c5api::DeviceBuffer vtx_face;  // [n_cells][4][3] fp64, device order: the chords' weights per face and vertex of the face
-    c5api::DeviceBuffer vtx_grad;  // [n_pts][3] fp64: the gradient in view space
-    int vertex_merge = 1;          // "vertex_merge": vertex_walk sums the lanes of a wavefront in one cell before its atomics
-                                   // (measured on the C3 frame: 5.7 ms against 58 ms for the walk; profiles/vertex_adjoint_probe.md)
-    // batched vertex adjoint (c5_render_vertex_adjoint_batch*): allocated at the first batched call only
-    c5api::DeviceBuffer vtx_bat_face;  // [n_cells][width][4][3] fp64, device order: vtx_face per image of a chunk
-    c5api::DeviceBuffer vtx_bat_grad;  // [n_pts][3][width] fp64: vtx_grad per image of a chunk, the images of a component side by side
-    // exact vertex adjoint sums ("vertex_exact", c5_render_vertex_exact_*): allocated at the first exact vertex call only
-    int vertex_exact = 0;              // "vertex_exact": c5_render_vertex_adjoint* and its batch return the exact sums
-    c5api::DeviceBuffer vtx_exact;     // [n_cells][12][2] int64 words, [n_cells][12] int32 exponents (device order), the misfit word
-    c5api::DeviceBuffer vtx_triples;   // [n_cells][4][3] fp64, device order: a cell's share of its four vertices' view-space gradient
-    c5api::DeviceBuffer vtx_inc;       // point -> (cell, vertex) incidence, CSR: int32 [n_pts + 1] offsets, int32 [4 n_cells] entries
-    uint64_t vtx_inc_serial = ~uint64_t{0};  // ... for the grid of this upload (kept across c5_update_points)
-    // vertex tangent (c5_render_vertex_tangent*): allocated at the first call only
-    c5api::DeviceBuffer vtx_vel;   // [n_pts][width][3] fp64: the points' view-space velocities (vertex_velocity)
-    // ray matrix (c5_ray_matrix_*): allocated at the first call only (the scan's scratch is bin_sort_resolve's scratch64)
-    c5api::DeviceBuffer rm_count;  // [padded local px] int32 segments per pixel, then one word: rows the fill found changed
     // c5_update_points: the cells as the device has them (welded, in its order) and, where c5_upload_grid welded points,
     // every point's representative (empty: none welded) - what measure_grid and upload_block_spheres are run again with
     std::vector<int32_t> host_cell_vert, point_rep;
-    // the host-pointer forms of all derivative renders: what the caller hands in and what goes back (run_staged)
-    c5api::DeviceBuffer deriv_io;
     // c5_update_scalars_device: the three statistics of the scalars on the device, and their pinned copy
     c5api::DeviceBuffer scal_stats;
     unsigned long long* scal_host = nullptr;
@@ -362,7 +378,7 @@ int enqueue_solids(c5_context* ctx, FrameSlot& fs, int slot_id, hipStream_t s, c
 int enqueue_frame(c5_context* ctx, float2* out_dev, c5::FrameCounters* own_counters = nullptr);
 int wait_and_collect(c5_context* ctx);
 
-// ---- derivatives.hip
+// ---- derivative_setup.hip (derivative_host.hpp: what the derivative renders' files share)
 int finish_adjoint(c5_context* ctx);
 
 }  // namespace c5api

@@ -268,8 +268,8 @@ int c5_upload_grid(c5_context* ctx, const double* xyz, int64_t n_pts, const int3
     ctx->host_cell_vert.assign(cell_vert, cell_vert + 4 * n_cells);  // (c5_update_points measures the grid again)
     ctx->point_rep = std::move(rep);
     ++ctx->grid_serial;
-    ctx->vtx_inc.release();  // ("vertex_exact": the incidence table is the old connectivity's; the next exact call builds its own)
-    ctx->vtx_inc_serial = ~uint64_t{0};
+    ctx->deriv.vtx_inc.release();  // ("vertex_exact": the incidence table is the old connectivity's; the next exact call builds its own)
+    ctx->deriv.vtx_inc_serial = ~uint64_t{0};
     measure_grid(ctx, xyz, n_pts, cell_vert, n_cells);
     scan_alpha(ctx, alpha, n_cells);
     ctx->split_auto_k = 1;

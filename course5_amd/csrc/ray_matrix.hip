@@ -1,0 +1,145 @@
+// ------------------------------------------------------------------------------------------
+// The ray matrix (ray_matrix_kernels.hip): per pixel the cells its ray crosses and the chord of each crossing, as CSR
+// arrays - rows and fill over derivative_host.hpp and, next to them, their entry points.
+// ------------------------------------------------------------------------------------------
+#include "derivative_host.hpp"
+
+using namespace c5api;
+
+namespace {
+
+// The ray matrix's own buffer: the count per pixel ([padded] int32) and, behind them, the fill's word of changed rows.
+int ray_matrix_buffer(c5_context* ctx, const DerivativeView& v, int32_t*& count, unsigned*& changed_rows) {
+    C5_HIP(ctx, ctx->deriv.rm_count.ensure(static_cast<size_t>(v.padded + 1) * sizeof(int32_t)));
+    count = ctx->deriv.rm_count.as<int32_t>();
+    changed_rows = reinterpret_cast<unsigned*>(count + v.padded);
+    return C5_OK;
+}
+
+// The ray matrix's rows: one per-view setup, the count per pixel (segment_walk<1>, which leaves the entry heads in place:
+// the next per-view setup clears them; or segment_count_resolve over bin_sort_resolve's lists) and the scan into row_ptr
+// [n_px + 1] on the device.
+int enqueue_ray_matrix_rows(c5_context* ctx, int64_t* row_ptr) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    if (v.no_cells || v.n_px <= 0) C5_HIP(ctx, hipMemsetAsync(row_ptr, 0, static_cast<size_t>(v.n_px + 1) * sizeof(int64_t), v.s));
+    if (v.no_cells) return C5_OK;  // (solids only: every row is empty)
+    int32_t* count;
+    unsigned* changed_rows;
+    rc = ray_matrix_buffer(ctx, v, count, changed_rows);
+    if (rc) return rc;
+    C5_HIP(ctx, ctx->scratch64.ensure(static_cast<size_t>(v.padded / 1024 + 1024) * sizeof(int64_t)));
+    if (v.bin_sort) {
+        c5::launch_segment_count_resolve(v.s, v.r, count);
+    } else {
+        c5::RayMatrixParams m{};
+        m.w = v.w;
+        m.count = count;
+        c5::launch_segment_walk(v.s, m, 1);
+    }
+    c5::launch_scan64(v.s, count, row_ptr, v.n_px, ctx->scratch64.as<int64_t>());
+    return commit_derivative(ctx, v, "ray matrix rows");
+}
+
+// The ray matrix's arrays: a per-view setup of its own, then segment_walk<2> (or segment_fill_resolve), which writes only
+// inside [0, capacity) and counts the rows that differ from row_ptr; that count travels to the host behind the status words.
+int enqueue_ray_matrix_fill(c5_context* ctx, const int64_t* row_ptr, int64_t capacity, int32_t* col, double* dz, double* z_exit) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    if (v.no_cells) {  // (solids only: every row is empty, and a row_ptr that says otherwise is another frame's; this waits)
+        int64_t total = 0;
+        C5_HIP(ctx, hipMemcpyAsync(&total, row_ptr + v.n_px, sizeof total, hipMemcpyDeviceToHost, v.s));
+        C5_HIP(ctx, hipStreamSynchronize(v.s));
+        if (total != 0)
+            return fail(ctx, C5_ERR_STATE, "ray matrix fill: the frame changed between c5_ray_matrix_rows and c5_ray_matrix_fill: "
+                        "row_ptr holds %lld segments, the scene has no cells", static_cast<long long>(total));
+        return C5_OK;
+    }
+    int32_t* count;
+    unsigned* changed_rows;
+    rc = ray_matrix_buffer(ctx, v, count, changed_rows);
+    if (rc) return rc;
+    C5_HIP(ctx, hipMemsetAsync(changed_rows, 0, sizeof(unsigned), v.s));
+    c5::RayMatrixParams m{};
+    m.w = v.w;
+    m.row_ptr = row_ptr;
+    m.capacity = capacity;
+    m.perm = v.perm;
+    m.col = col;
+    m.dz = dz;
+    m.z_exit = z_exit;
+    m.changed_rows = changed_rows;
+    if (v.bin_sort) {
+        c5::launch_segment_fill_resolve(v.s, v.r, m);
+    } else {
+        v.keep(false);  // (the fill hands every head back cleared)
+        c5::launch_segment_walk(v.s, m, 2);
+    }
+    rc = commit_derivative(ctx, v, "ray matrix fill");
+    if (rc) return rc;
+    C5_HIP(ctx, hipMemcpyAsync(ctx->deriv.adj_status + 3, changed_rows, sizeof(unsigned), hipMemcpyDeviceToHost, v.s));
+    return C5_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Waits for the stream: *nnz is valid on return.
+int c5_ray_matrix_rows_device(c5_context* ctx, void* row_ptr_dev, int64_t* nnz) {
+    int rc = check_derivative(ctx, {"c5_ray_matrix_rows", false, 1, nullptr, row_ptr_dev && nnz, true, "null row_ptr or nnz pointer"});
+    if (rc) return rc;
+    *nnz = 0;
+    int64_t* const row_ptr = static_cast<int64_t*>(row_ptr_dev);
+    rc = enqueue_ray_matrix_rows(ctx, row_ptr);
+    if (rc) return rc;
+    C5_HIP(ctx, hipMemcpyAsync(nnz, row_ptr + local_pixels(ctx->im), sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    return c5_synchronize(ctx);
+}
+
+int c5_ray_matrix_rows(c5_context* ctx, int64_t* row_ptr_host, int64_t* nnz) {
+    int rc = check_derivative(ctx, {"c5_ray_matrix_rows", true, 1, nullptr, row_ptr_host && nnz, true, "null row_ptr or nnz pointer"});
+    if (rc) return rc;
+    *nnz = 0;
+    const int64_t n_px = local_pixels(ctx->im);
+    Staged b[] = {{nullptr, row_ptr_host, static_cast<size_t>(n_px + 1) * sizeof(int64_t)}};
+    rc = run_staged(ctx, "ray matrix rows", b, [&] { return enqueue_ray_matrix_rows(ctx, b[0].as<int64_t>()); });
+    if (rc) return rc;
+    *nnz = row_ptr_host[n_px];
+    return C5_OK;
+}
+
+int c5_ray_matrix_fill_device(c5_context* ctx, const void* row_ptr_dev, int64_t capacity, void* col_dev, void* dz_dev, void* z_exit_dev) {
+    int rc = check_derivative(ctx, {"c5_ray_matrix_fill", false, 1, nullptr, row_ptr_dev && col_dev && dz_dev, true,
+                                    "null row_ptr, col or dz pointer"});
+    if (rc) return rc;
+    if (capacity < 0) return fail(ctx, C5_ERR_INVALID, "c5_ray_matrix_fill: negative capacity (%lld)", static_cast<long long>(capacity));
+    return enqueue_ray_matrix_fill(ctx, static_cast<const int64_t*>(row_ptr_dev), capacity, static_cast<int32_t*>(col_dev),
+                                   static_cast<double*>(dz_dev), static_cast<double*>(z_exit_dev));
+}
+
+// The arrays are staged for row_ptr's total, which is also the capacity the kernel is given: nothing beyond it is written
+// on the device or copied back.
+int c5_ray_matrix_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t capacity, int32_t* col_host, double* dz_host,
+                       double* z_exit_host) {
+    int rc = check_derivative(ctx, {"c5_ray_matrix_fill", true, 1, nullptr, row_ptr_host && col_host && dz_host, true,
+                                    "null row_ptr, col or dz pointer"});
+    if (rc) return rc;
+    if (capacity < 0) return fail(ctx, C5_ERR_INVALID, "c5_ray_matrix_fill: negative capacity (%lld)", static_cast<long long>(capacity));
+    const int64_t n_px = local_pixels(ctx->im), need = row_ptr_host[n_px];
+    if (need < 0 || need > capacity)
+        return fail(ctx, C5_ERR_INVALID, "c5_ray_matrix_fill: row_ptr asks for %lld elements, capacity is %lld", static_cast<long long>(need),
+                    static_cast<long long>(capacity));
+    const size_t n = static_cast<size_t>(need);
+    Staged b[] = {{row_ptr_host, nullptr, static_cast<size_t>(n_px + 1) * sizeof(int64_t)},
+                  {nullptr, col_host, n * sizeof(int32_t)},
+                  {nullptr, dz_host, n * sizeof(double)},
+                  {nullptr, z_exit_host, z_exit_host ? n * sizeof(double) : 0}};
+    return run_staged(ctx, "ray matrix fill", b, [&] {
+        return enqueue_ray_matrix_fill(ctx, b[0].as<const int64_t>(), need, b[1].as<int32_t>(), b[2].as<double>(), b[3].as<double>());
+    });
+}
+
+}  // extern "C"
