@@ -26,6 +26,7 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wex
 LIB_SOURCES = [
     ("exact_kernels.hip", ["-ffp-contract=off"]),   # must round like the reference's host build
     ("walk_kernels.hip", []),
+    ("setup_kernels.hip", []),
     # the derivative renders; fp64 atomicAdd as global_atomic_add_f64, no compare-and-swap loop: the same flag for all
     # three, so that no kernel's code depends on which file it is in
     ("scalar_derivative_kernels.hip", ["-munsafe-fp-atomics"]),
@@ -44,7 +45,8 @@ LIB_SOURCES = [
 ]
 
 
-DEVICE_SOURCES = ("device_types.hpp", "kernels.hpp", "walk_common.hpp", "exact_kernels.hip", "walk_kernels.hip")
+DEVICE_SOURCES = ("device_types.hpp", "kernels.hpp", "walk_common.hpp", "walk_plan.hpp", "tile_of_block_body.hpp", "walk_steps.hpp", "walk_stamps.hpp",
+                  "exact_kernels.hip", "walk_kernels.hip", "setup_kernels.hip")
 
 
 def kernel_source_hash() -> str:

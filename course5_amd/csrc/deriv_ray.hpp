@@ -16,41 +16,9 @@
 namespace c5 {
 namespace adj {
 
-// The walk's per-step helpers, as walk_kernels.hip has them (CellRegs, load_cell, step_geometry): a copy, so that file and
-// the hash of the forward kernels stay as they are.
-struct CellRegs {
-    D2 r0, r1, r2, r3, r4, r5, r6, r7;  // ExitRecord: r0-r4 planes (+ nbr[0..1] in r4.b), r5.a = nbr[2] | flags, r6 / r7 optics
-};
-
-__device__ __forceinline__ void load_cell(CellRegs& c, const ExitRecord* rec, int cell) {
-    const D2* rp = reinterpret_cast<const D2*>(rec + cell);
-    c.r0 = rp[0];
-    c.r1 = rp[1];
-    c.r2 = rp[2];
-    c.r3 = rp[3];
-    c.r4 = rp[4];
-    c.r5 = rp[5];
-    c.r6 = rp[6];
-    c.r7 = rp[7];
-}
-
-struct StepGeometry {
-    double w_exit;   // +inf: the ray cannot leave (flat cell, edge-on faces): it ends here
-    uint32_t w_out;  // neighbour word of the exit face
-};
-
-__device__ __forceinline__ StepGeometry step_geometry(const CellRegs& cur, double x, double y) {
-    const double w0 = fma(cur.r0.b, x, fma(cur.r1.a, y, cur.r0.a));
-    const double w1 = fma(cur.r2.a, x, fma(cur.r2.b, y, cur.r1.b));
-    const double w2 = fma(cur.r3.b, x, fma(cur.r4.a, y, cur.r3.a));
-    const unsigned long long n01 = __double_as_longlong(cur.r4.b);
-    const uint32_t n0 = static_cast<uint32_t>(n01), n1 = static_cast<uint32_t>(n01 >> 32);
-    const uint32_t n2 = static_cast<uint32_t>(__double_as_longlong(cur.r5.a));
-    StepGeometry g;
-    g.w_exit = fmin(w0, fmin(w1, w2));  // (never NaN: a candidate is a finite depth or +inf)
-    g.w_out = (w0 == g.w_exit) ? n0 : (w1 == g.w_exit) ? n1 : n2;
-    return g;
-}
+// The walk's per-step helpers (walk_common.hpp: CellRegs, load_cell, step_geometry), the step with the library's fmin: these
+// kernels' registers are sensitive to it (see MinFmin there).
+__device__ __forceinline__ StepGeometry step_geometry(const CellRegs& cur, double x, double y) { return c5::step_geometry<MinFmin>(cur, x, y); }
 
 // step_geometry, and the exit face's slopes beside it (the motion tangent: how the face's depth moves)
 struct SlopedExit {
@@ -166,7 +134,7 @@ __device__ __forceinline__ void scatter_wave(bool pending, int cell, double ga, 
 
 // One ray of a walk kernel: one wavefront per 8x8 pixel tile, one lane per pixel (the walk's default tiling: neighbouring
 // rays share cells, which is what the per-wave sums before the atomics live on).  Every walk kernel of the derivative renders
-// takes its steps through this struct, and the step is that of walk_composite<*, 0> (walk_kernels.hip) operation for operation: the
+// takes its steps through this struct, and the step is that of walk_composite<*, 0> (walk_kernels.hip; one step_geometry for both: walk_common.hpp) operation for operation: the
 // same segments, to the bit.  What a kernel accumulates along the ray stays in its own body.
 //
 // Three things a step needs are deliberately NOT members but locals of the kernel: the cell's record `cur`, the next

@@ -924,7 +924,7 @@ int finish_frame(c5_context* ctx) {
     const FrameTotals hc = sum_counters(fs.host_counters);
     update_sb_order(ctx, fs, hc.covered);
     // How coarse the pixels are against the cells decides how many distinct cells an 8x8 tile meets per step, and
-    // with it how many staging slots the next frame's walk gets (walk_kernels.hip: 14 or 21): rays per cell of the
+    // with it how many staging slots the next frame's walk gets (walk_plan.hpp: walk_plan, 14 or 21): rays per cell of the
     // WHOLE frame, this context's share scaled up by the number of row shards.
     if (ctx->n_cells > 0 && hc.segments > 0)
         ctx->rays_per_cell = static_cast<double>(hc.segments) * static_cast<double>(ctx->im.world > 0 ? ctx->im.world : 1) *

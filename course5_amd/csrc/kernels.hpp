@@ -1,4 +1,4 @@
-// Host-callable launchers of the gfx950 kernels (definitions in exact_kernels.hip and
+// Host-callable launchers of the gfx950 kernels (definitions in exact_kernels.hip, setup_kernels.hip and
 // walk_kernels.hip).  All launches are asynchronous on the given stream.
 #pragma once
 
@@ -50,7 +50,7 @@ struct WalkParams {
     double t_cutoff;            // front-to-back early-out on transmittance
     uint32_t max_steps;
     int32_t xcd_mode;
-    int32_t band_tiles;         // xcd_mode 1: workgroup-tile rows per band (set by launch_walk)
+    int32_t band_tiles;         // xcd_mode 1: workgroup-tile rows per band; 2: tiles along a super-block (set by launch_walk: walk_plan.hpp)
     int32_t lds_stage;          // 2: walk_composite_lds with LDS-DMA staging, 1: staged through registers, 0: direct loads
     int32_t stage_slots;        // lds_stage 1 / 2: 14 or 21 distinct cells staged per wavefront and step (2 / 3 DMA passes of 7)
     int32_t band_rows;          // xcd_mode 1: image rows per band (0: 32)
@@ -114,7 +114,7 @@ size_t segment_bytes();
 // dst[p] = src[p] wherever src[p] != 0 (a cached solid mask laid over the frame's mask, in slot order)
 void launch_mask_overlay(hipStream_t s, const uint32_t* src, uint32_t* dst, int64_t n_padded);
 
-// walk_kernels.hip
+// setup_kernels.hip (the per-view set-up) and walk_kernels.hip (launch_walk, walk_sb_rows, walk_tiles)
 // key_slack of the two launchers below: how far an entry's depth key lies behind its face (walk_common.hpp:
 // entry_key_slack) = this fraction of the diagonal of the grid's bounding box (+ a term for the rounding of an
 // absolute depth, c_api.hip), the same for every face of a frame

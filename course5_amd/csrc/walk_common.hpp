@@ -1,5 +1,5 @@
-// Device helpers of the walk kernels (walk_kernels.hip, fp64): face planes and per-cell records, tile shapes, exp,
-// entry lists.
+// Device helpers of the set-up and walk kernels (setup_kernels.hip, walk_kernels.hip, fp64): face planes and per-cell
+// records, the step geometry, exp, entry lists.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +8,7 @@
 
 #include "device_types.hpp"
 #include "kernels.hpp"
+#include "walk_plan.hpp"
 
 namespace c5 {
 
@@ -218,26 +219,7 @@ __device__ __forceinline__ void to_exit_record(const CellRecord& r, const CellOp
     x.q = o.q;
 }
 
-template <int TILE>
-struct TileShape;
-template <>
-struct TileShape<0> {  // each wavefront owns a 64x1 row tile; workgroup 64 x 4
-    static constexpr int WW = 64, WH = 1, GX = 1, GY = 4;
-};
-template <>
-struct TileShape<1> {  // 16x4 per wavefront; workgroup 32 x 8
-    static constexpr int WW = 16, WH = 4, GX = 2, GY = 2;
-};
-template <>
-struct TileShape<2> {  // 8x8 per wavefront; workgroup 16 x 16
-    static constexpr int WW = 8, WH = 8, GX = 2, GY = 2;
-};
-template <>
-struct TileShape<3> {  // 8x8 per wavefront, ONE wavefront per workgroup: a wavefront's slot (and its LDS) is free for
-                       // the next tile the moment its own rays are done, not when the slowest of four is
-    static constexpr int WW = 8, WH = 8, GX = 1, GY = 1;
-};
-
+// (TileShape: walk_plan.hpp)
 __device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
@@ -247,6 +229,67 @@ __device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
 struct alignas(16) D2 {
     double a, b;
 };
+
+// ------------------------------------------------------------------------------------------
+// One step of a walk: the cell's record in registers, and where the ray leaves the cell.  The forward kernels
+// (walk_kernels.hip) and every walk kernel of the derivative renders (deriv_ray.hpp) take their steps through these.
+// ------------------------------------------------------------------------------------------
+struct CellRegs {
+    D2 r0, r1, r2, r3, r4, r5, r6, r7;  // ExitRecord: r0-r4 planes (+ nbr[0..1] in r4.b), r5.a = nbr[2] | flags, r6 / r7 optics
+};
+
+__device__ __forceinline__ void load_cell(CellRegs& c, const ExitRecord* rec, int cell) {
+    const D2* rp = reinterpret_cast<const D2*>(rec + cell);
+    c.r0 = rp[0];
+    c.r1 = rp[1];
+    c.r2 = rp[2];
+    c.r3 = rp[3];
+    c.r4 = rp[4];
+    c.r5 = rp[5];
+    c.r6 = rp[6];
+    c.r7 = rp[7];
+}
+
+// Geometry of one step: how far along the walk the ray (x, y) leaves the current cell, and through which face.
+// The record holds the (up to three) faces a ray can leave through as planes of the walk coordinate w about the
+// absolute pixel coordinates (device_types.hpp: ExitRecord); the chord is w_exit minus the depth at which the ray
+// entered — the exit depth of the cell before, or the boundary entry's own depth (the caller's `carry`).
+struct StepGeometry {
+    double w_exit;     // min over the candidates; +inf: the ray cannot leave (flat cell, edge-on faces): it ends here
+    uint32_t w_out;    // neighbour word of the exit face
+};
+
+// The minimum of two candidates, as a policy of step_geometry.  The operands are never NaN (a candidate is a finite
+// depth or +inf), so the two give the same number; what differs is the code around them.
+//   MinInstruction  v_min_f64 and nothing else: fmin() on a value the compiler cannot prove canonical is preceded by a
+//                   canonicalising v_max_f64 x, x.  The forward kernels' choice.
+//   MinFmin         the library's fmin.  The derivative kernels' choice: given the one instruction, motion_walk<8>
+//                   gained 36 bytes of scratch and segment_walk<2> went from 70 to 76 VGPRs.
+struct MinInstruction {
+    static __device__ __forceinline__ double of(double a, double b) {
+        double r;
+        asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+        return r;
+    }
+};
+struct MinFmin {
+    static __device__ __forceinline__ double of(double a, double b) { return fmin(a, b); }
+};
+
+template <class Min = MinInstruction>
+__device__ __forceinline__ StepGeometry step_geometry(const CellRegs& cur, double x, double y) {
+    // plane k = (c, gx, gy): r0.a r0.b r1.a | r1.b r2.a r2.b | r3.a r3.b r4.a
+    const double w0 = fma(cur.r0.b, x, fma(cur.r1.a, y, cur.r0.a));
+    const double w1 = fma(cur.r2.a, x, fma(cur.r2.b, y, cur.r1.b));
+    const double w2 = fma(cur.r3.b, x, fma(cur.r4.a, y, cur.r3.a));
+    const unsigned long long n01 = __double_as_longlong(cur.r4.b);
+    const uint32_t n0 = static_cast<uint32_t>(n01), n1 = static_cast<uint32_t>(n01 >> 32);
+    const uint32_t n2 = static_cast<uint32_t>(__double_as_longlong(cur.r5.a));
+    StepGeometry g;
+    g.w_exit = Min::of(w0, Min::of(w1, w2));
+    g.w_out = (w0 == g.w_exit) ? n0 : (w1 == g.w_exit) ? n1 : n2;
+    return g;
+}
 
 // exp(x) for x <= 0 (x = -alpha * dz).  Same scheme as the device library's exp — k = rint(x log2 e),
 // r = x - k ln 2 in two pieces, polynomial in r, scale by 2^k — but written as one fused

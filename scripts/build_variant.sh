@@ -1,6 +1,7 @@
 #!/bin/bash
 # Scratch: build a variant of the library with extra -D flags for walk_kernels.hip.
-#   scripts/build_variant.sh NAME -DC5_ELECT_LEADERS=0 ...   -> course5_amd/libcourse5_hip_NAME.so
+#   scripts/build_variant.sh NAME -DC5_WALK_STAMPS=1 ...   -> course5_amd/libcourse5_hip_NAME.so
+# (the flags walk_kernels.hip still reads: C5_WALK_STAMPS 1 / 2 and C5_ISA_MARKERS, csrc/walk_stamps.hpp)
 # (A/B against the in-tree build with scripts/ab_probe.py)
 set -e
 cd "$(dirname "$0")/.."

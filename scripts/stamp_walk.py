@@ -36,7 +36,7 @@ out = torch.zeros((ctx.local_rows if rows else 1800, 2400, 2), dtype=torch.float
 buf = (C.c_ulonglong * 16)()
 names = ["election: ticket -> leader -> slot (2 LDS round trips)",
          "slot ids read back + staging loads (LDS-DMA) issued",
-         "(emission of the previous step in the loads' shadow: only in builds with C5_EMIT_NOW=0)",
+         "(emission of the previous step in the loads' shadow: only in the register-staged kernel, \"lds_stage\" 1)",
          "staging loads land: s_waitcnt vmcnt(0)",
          "8 x ds_read_b128 + three exit planes + exit face (+ re-entry) + this step's emission / absorption (exp)"]
 short = ["election", "issue", "deferred emission", "load wait", "read + geometry + emission"]

@@ -1024,8 +1024,9 @@ def forward_scene(seed):
 
 
 def predicted_kernel(s, alpha, limit, L):
-    """The walk the documented rule selects for this state (csrc/walk_kernels.hip: launch_walk_t).  Predicted, not read
-    back: the library has no read-out of the kernel that ran."""
+    """The walk the launch plan selects for this state (csrc/walk_plan.hpp: walk_plan, checked against the rules written
+    out again in tests/cpp/walk_plan_check.cpp; csrc/walk_kernels.hip: launch_walk_t switches on it).  Predicted, not
+    read back: the library has no read-out of the kernel that ran."""
     if s.soup:
         return "bin_sort_resolve"
     lds, order, tile = s.variant

@@ -81,8 +81,9 @@ def test_argument_checks_raise_before_the_library():
 
 def test_device_sources_hash_and_abi_version_stay():
     from course5_amd import build
-    assert build.DEVICE_SOURCES == ("device_types.hpp", "kernels.hpp", "walk_common.hpp", "exact_kernels.hip", "walk_kernels.hip")
-    assert build.kernel_source_hash() == "688bc525360ea908"
+    assert build.DEVICE_SOURCES == ("device_types.hpp", "kernels.hpp", "walk_common.hpp", "walk_plan.hpp", "tile_of_block_body.hpp", "walk_steps.hpp", "walk_stamps.hpp",
+                                    "exact_kernels.hip", "walk_kernels.hip", "setup_kernels.hip")
+    assert build.kernel_source_hash() == "8d8cb316b206ad86"
     assert ctypes.CDLL(capi.LIB_PATH).c5_abi_version() == 2
 
 

@@ -136,3 +136,36 @@ def test_local_row_span_matches_brute_force(tmp_path):
                     os.path.join(root, "tests", "cpp", "row_span_check.cpp"), "-o", str(exe)], check=True)
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
     assert out.startswith("ok "), out
+
+
+@pytest.fixture(scope="module")
+def walk_plan_check(tmp_path_factory):
+    """tests/cpp/walk_plan_check.cpp built with g++ against csrc/walk_plan.hpp (plain C++: no GPU, no HIP runtime)"""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path_factory.mktemp("walk_plan") / "walk_plan_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(root, "course5_amd", "csrc"),
+                    os.path.join(root, "tests", "cpp", "walk_plan_check.cpp"), "-o", str(exe)], check=True)
+    return str(exe)
+
+
+def test_walk_plan_matches_restated_rules(walk_plan_check):
+    """walk_plan (kernel family, slots, SMALLEXP, SPLIT, grid, band_tiles) against the launch rules written out again in
+    the check, for every combination of tile 0-3, order, xcd_mode 0-2, lds_stage 0-2, stage_slots {0, 14, 21},
+    small_exp_only, n_slabs 1-3, band_rows {0, 8, 16, 32, 64} and five images (+ one without a pixel: no launch)."""
+    import subprocess
+    out = subprocess.run([walk_plan_check, "plan"], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("ok 38880 plans"), out.stdout + out.stderr
+
+
+def test_tile_of_block_covers_every_tile_once(walk_plan_check):
+    """The kernels' block-to-tile mapping (csrc/tile_of_block_body.hpp: one text, compiled into tile_of_block here and for
+    walk_composite, and in place into walk_composite_lds) over 0 .. grid-1 of the plan's own grid yields every
+    (tile, slab) exactly once and "no tile" for the rest: row-major, bands and super-blocks, every tile shape, image and
+    band_rows, the rows of super-blocks in image order (no table, and an identity table) and reversed, n_slabs 1-3
+    where SPLIT applies."""
+    import subprocess
+    out = subprocess.run([walk_plan_check, "layout"], capture_output=True, text=True)
+    # 6 layouts x 4 tile shapes x 5 images x 5 band_rows; + 2 x 25 for n_slabs 2 and 3; + 2 x 150 for the super-block
+    # launches (25 x (tile shapes 0-2 + tile shape 3 with n_slabs 1-3)) with an identity and a reversed sb_order
+    assert out.returncode == 0 and out.stdout.startswith("ok 950 layouts"), out.stdout + out.stderr

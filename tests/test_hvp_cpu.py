@@ -366,8 +366,9 @@ def test_library_and_bindings_have_them():
 
 def test_the_forward_kernels_are_untouched():
     from course5_amd import build
-    assert build.DEVICE_SOURCES == ("device_types.hpp", "kernels.hpp", "walk_common.hpp", "exact_kernels.hip", "walk_kernels.hip")
-    assert build.kernel_source_hash() == "688bc525360ea908"
+    assert build.DEVICE_SOURCES == ("device_types.hpp", "kernels.hpp", "walk_common.hpp", "walk_plan.hpp", "tile_of_block_body.hpp", "walk_steps.hpp", "walk_stamps.hpp",
+                                    "exact_kernels.hip", "walk_kernels.hip", "setup_kernels.hip")
+    assert build.kernel_source_hash() == "8d8cb316b206ad86"
 
 
 def test_argument_checks_raise_before_the_library():
