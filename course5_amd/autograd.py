@@ -715,7 +715,7 @@ def ray_matrix(ctx: capi.Context, with_depth: bool = False):
     float64, on the context's GPU, A[pixel, cell] = the chord of the pixel's ray through the cell (rows: local pixels lrow *
     res_x + col; columns: cells in the order of upload_grid; within a row the deepest segment first).  A @ alpha is channel
     0 of render() (tau) in fp64, and A.T @ g is render_adjoint's grad_alpha for the upstream image (g, 0).  Channel 1 is
-    not linear in alpha: no matrix gives it.  Indices are int32 while nnz < 2^31, else int64.  with_depth: (A, z_exit),
+    not linear in alpha: ray_jacobian gives its derivatives.  Indices are int32 while nnz < 2^31, else int64.  with_depth: (A, z_exit),
     z_exit float64 [nnz]: every segment's far end in view space, in the order of A.values().  Built on torch's current
     stream (c5_ray_matrix_rows_device, c5_ray_matrix_fill_device) and waited for; no graph: A does not depend on the
     scalars.  Bit-reproducible."""
@@ -737,4 +737,42 @@ def ray_matrix(ctx: capi.Context, with_depth: bool = False):
     return (A, z_exit[:nnz]) if with_depth else A
 
 
-__all__ = ["render", "render_view", "render_mesh", "gn_product", "gn_diagonal", "vertex_gn_product", "hvp", "ray_matrix"]
+def _ray_jacobian_arrays(ctx: capi.Context, device: torch.device) -> tuple:
+    """(crow int64 [local_px + 1], col int32 [nnz], dz, dI_dalpha, dI_dq float64 [nnz]) on `device`, for the scalars the
+    context holds: c5_ray_matrix_rows_device and c5_ray_jacobian_fill_device on torch's current stream, waited for."""
+    n_px = ctx.local_rows * ctx.res_x
+    crow = torch.empty(n_px + 1, dtype=torch.int64, device=device)
+    _use_torch_stream(ctx, device)
+    nnz = ctx.ray_matrix_rows_device(crow)  # (waits and retries by itself)
+    # (an empty torch tensor has no data pointer to hand over)
+    col = torch.empty(max(nnz, 1), dtype=torch.int32, device=device)
+    dz, da, dq = (torch.empty(max(nnz, 1), dtype=torch.float64, device=device) for _ in range(3))
+    _run(ctx, lambda: ctx.ray_jacobian_fill_device(crow, col, dz, da, dq))
+    return crow, col[:nnz], dz[:nnz], da[:nnz], dq[:nnz]
+
+
+def ray_jacobian(ctx: capi.Context, alpha=None, q=None) -> tuple:
+    """(A, J_alpha, J_q): the Jacobian of the frame `ctx` would render now with respect to the cells' scalars, as three
+    torch.sparse_csr_tensor [local_rows * res_x, n_cells], float64, on the context's GPU: A[pixel, cell] = d tau / d alpha
+    (ray_matrix's A, bit for bit), J_alpha[pixel, cell] = d I / d alpha, J_q[pixel, cell] = d I / d Q (rows: local pixels
+    lrow * res_x + col; columns: cells in the order of upload_grid; within a row the deepest segment first; explicit zeros
+    where a cell is inactive, and in J_alpha where its alpha is clamped).  The three share one crow_indices / col_indices
+    storage; indices are int32 while nnz < 2^31, else int64.  alpha and q: the scalars to differentiate at (both or
+    neither; None: those the context holds).  Built on torch's current stream (c5_ray_matrix_rows_device,
+    c5_ray_jacobian_fill_device) and waited for; the results carry no graph.  Bit-reproducible."""
+    if (alpha is None) != (q is None):
+        raise ValueError("give both alpha and q, or neither")
+    if alpha is not None:
+        _gn_enter(ctx, alpha, q, "ray_jacobian")
+    with _on_gpu(ctx) as device:
+        crow, col, dz, da, dq = _ray_jacobian_arrays(ctx, device)
+        if dz.shape[0] < 2 ** 31:
+            crow = crow.to(torch.int32)
+        else:
+            col = col.to(torch.int64)
+        size = (ctx.local_rows * ctx.res_x, ctx.n_cells)
+        # (check_invariants off: one storage, not three validated copies)
+        return tuple(torch.sparse_csr_tensor(crow, col, v, size=size, check_invariants=False) for v in (dz, da, dq))
+
+
+__all__ = ["render", "render_view", "render_mesh", "gn_product", "gn_diagonal", "vertex_gn_product", "hvp", "ray_matrix", "ray_jacobian"]

@@ -118,6 +118,8 @@ SIGNATURES = {
     "c5_ray_matrix_rows_device": [_vp, _vp, _lp_t],
     "c5_ray_matrix_fill": [_vp, _lp_t, C.c_int64, _ip_t, _dp_t, _dp_t],
     "c5_ray_matrix_fill_device": [_vp, _vp, C.c_int64, _vp, _vp, _vp],
+    "c5_ray_jacobian_fill": [_vp, _lp_t, C.c_int64, _ip_t, _dp_t, _dp_t, _dp_t],
+    "c5_ray_jacobian_fill_device": [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp],
     "c5_render_adjoint_exact_bounds": [_vp, _fp_t, _ip_t, _ip_t],
     "c5_render_adjoint_exact_bounds_device": [_vp, _vp, _vp, _vp],
     "c5_render_adjoint_exact_sums": [_vp, _fp_t, _ip_t, _ip_t, _lp_t, _lp_t],
@@ -739,6 +741,56 @@ class Context:
         pixel's ray through the cell.  A @ alpha is channel 0 of render() in fp64."""
         row_ptr = self.ray_matrix_rows()
         return (row_ptr,) + self.ray_matrix_fill(row_ptr, with_depth)
+
+    # -- ray Jacobian ------------------------------------------------------------------------------
+    def ray_jacobian_fill(self, row_ptr, capacity: int | None = None, with_structure: bool = True) -> tuple:
+        """The ray Jacobian's arrays for ray_matrix_rows' row_ptr of this frame: (col int32, dz, dI_dalpha, dI_dq), float64,
+        [capacity] each (default: row_ptr[-1]), or (dI_dalpha, dI_dq) alone without the structure.  col and dz are
+        ray_matrix_fill's, bit for bit; dI_dalpha / dI_dq: the derivative of the pixel's I with respect to the crossed
+        cell's alpha / Q at the scalars and the alpha limit the context holds now (0 where the cell is inactive; dI_dalpha
+        0 where its alpha is clamped).  Raises C5_ERR_STATE if the frame changed since ray_matrix_rows.  Synchronous;
+        retries by itself.  Bit-reproducible."""
+        row_ptr = self._row_ptr(row_ptr)
+        n = int(row_ptr[-1]) if capacity is None else int(capacity)
+        if n < 0:
+            raise ValueError(f"capacity must not be negative ({n})")
+        col = np.zeros(max(n, 1), dtype=np.int32) if with_structure else None
+        dz = np.zeros(max(n, 1)) if with_structure else None
+        da, dq = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        self._check(self.lib.c5_ray_jacobian_fill(self.handle, row_ptr.ctypes.data_as(_lp_t), n,
+                                                  None if col is None else col.ctypes.data_as(_ip_t), _dp(dz), _dp(da), _dp(dq)))
+        return (col[:n], dz[:n], da[:n], dq[:n]) if with_structure else (da[:n], dq[:n])
+
+    def ray_jacobian_fill_device(self, row_ptr, col, dz, dI_dalpha, dI_dq, capacity: int | None = None):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (row_ptr int64 [local_rows * res_x
+        + 1]; col int32, dz / dI_dalpha / dI_dq float64, [capacity] each, contiguous) or raw device pointers (then give
+        capacity).  col and dz may be None, and one of dI_dalpha and dI_dq.  Nothing beyond capacity is written; a frame
+        that changed since ray_matrix_rows, or a capacity below row_ptr's total, makes the next synchronize() raise
+        C5_ERR_STATE."""
+        import torch
+        if dI_dalpha is None and dI_dq is None:
+            raise ValueError("give dI_dalpha or dI_dq")
+        if row_ptr is None:
+            raise ValueError("give row_ptr")
+        if capacity is None:
+            first = next((t for t in (dI_dalpha, dI_dq) if t is not None), None)
+            if isinstance(first, int):
+                raise ValueError("give capacity with raw device pointers")
+            capacity = first.shape[0]
+        if capacity < 0:
+            raise ValueError(f"capacity must not be negative ({capacity})")
+        shape = (capacity,)
+        ptrs = (_device_ptr(row_ptr, torch.int64, (self.local_rows * self.res_x + 1,)), _device_ptr(col, torch.int32, shape),
+                _device_ptr(dz, torch.float64, shape), _device_ptr(dI_dalpha, torch.float64, shape),
+                _device_ptr(dI_dq, torch.float64, shape))
+        self._check(self.lib.c5_ray_jacobian_fill_device(self.handle, ptrs[0], capacity, *ptrs[1:]))
+
+    def ray_jacobian(self) -> tuple:
+        """The Jacobian of the frame render() would produce now with respect to the cells' scalars, per segment, as CSR
+        arrays (row_ptr, col, dz, dI_dalpha, dI_dq) over the ray matrix's structure: d tau[pixel] / d alpha[cell] = dz,
+        d I[pixel] / d alpha[cell] = dI_dalpha, d I[pixel] / d Q[cell] = dI_dq."""
+        row_ptr = self.ray_matrix_rows()
+        return (row_ptr,) + self.ray_jacobian_fill(row_ptr)
 
     # -- tangent render ----------------------------------------------------------------------------
     def render_tangent(self, d_alpha=None, d_q=None) -> np.ndarray:

@@ -1,7 +1,8 @@
 // Host-callable launchers of the derivative renders.  scalar_derivative_kernels.hip: the adjoint (gradients of the image
 // with respect to the cells' alpha and Q), the tangent (the image's change for a change of them), their batches and the
 // Gauss-Newton renders; geometry_derivative_kernels.hip: the motion tangent, the vertex adjoint and the vertex tangent;
-// ray_matrix_kernels.hip: the ray matrix.  All launches are asynchronous on the given stream.
+// ray_matrix_kernels.hip: the ray matrix (the ray Jacobian's kernels run the adjoint's bodies: scalar_derivative_kernels.hip).
+// All launches are asynchronous on the given stream.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -371,6 +372,27 @@ void launch_segment_walk(hipStream_t s, const RayMatrixParams& m, int pass);
 // the same over bin_sort_resolve's lists: the count, and the fill (sorts them in place, as launch_adjoint_resolve)
 void launch_segment_count_resolve(hipStream_t s, const ResolveParams& r, int32_t* count);
 void launch_segment_fill_resolve(hipStream_t s, const ResolveParams& r, const RayMatrixParams& m);
+
+// ---- ray Jacobian (c5_ray_jacobian_fill*): the ray matrix's structure with the adjoint's per-segment terms as values -
+// per pixel and crossed cell d tau / d alpha = dz, d I / d alpha and d I / d Q, what adjoint_walk<2> adds to the cells' sums
+
+struct JacobianRows {
+    // row p's element k goes where RayMatrixParams says; any array may be null (not written)
+    const int64_t* row_ptr;   // [n_local_px + 1]
+    int64_t capacity;
+    const int32_t* perm;      // device order -> the caller's (nullptr: the identity)
+    int32_t* col;             // [capacity] the cell, the caller's order
+    double* dz;               // [capacity] the chord: d tau / d alpha
+    double* dI_da;            // [capacity] 0 for an inactive segment and for a clamped alpha
+    double* dI_dq;            // [capacity] 0 for an inactive segment
+    unsigned* changed_rows;   // += rows whose length is not row_ptr's or that found no room below capacity
+};
+
+// adjoint_walk<2>'s walk (after launch_adjoint_walk(.., 1): a.w and a.lambda are read) for the upstream image (0, 1) of
+// every pixel, each lane's terms stored to its own row in the order the walk runs, deepest first; hands the heads back cleared
+void launch_jacobian_walk(hipStream_t s, const AdjointParams& a, const JacobianRows& j);
+// the same over bin_sort_resolve's lists: adjoint_resolve's arithmetic, segment_fill_resolve's rows
+void launch_jacobian_fill_resolve(hipStream_t s, const ResolveParams& r, const JacobianRows& j);
 
 // c5_update_scalars_device: alpha[i] = alpha_src[perm[i]], q[i] = q_src[perm[i]] (perm nullptr: the identity), and into
 // stats[3] (zeroed by the caller): the bits of the largest alpha > 0, the complemented bits of the smallest alpha >=

@@ -1,5 +1,5 @@
 // What every walk kernel of the derivative renders shares: the ray and its step, the segment arithmetic, the per-wave and
-// per-cell reductions in front of the atomics, the K-image store and the launch helpers.
+// per-cell reductions in front of the atomics, the rows a lane owns in a CSR array, the K-image store and the launch helpers.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -490,6 +490,34 @@ __device__ __forceinline__ void reduce_rows_words(const long long* stage, bool e
         m &= ~members;
     }
     __syncthreads();  // (the rows are read before the next step writes them)
+}
+
+// ---- rows a lane owns (the ray matrix and the ray Jacobian: CSR arrays, every lane appends to its pixel's row with plain
+// stores - no atomics, bit-reproducible)
+
+// Where a lane's row goes: element k at base + k for k < n_ok, the part of row_ptr's row that lies in [0, capacity).
+// fits: all of row_ptr's row does.  Whatever row_ptr holds, base + k stays inside [0, capacity) for k < n_ok.
+struct RowSlot {
+    long long base = 0;
+    unsigned n_ok = 0;
+    bool fits = true;
+};
+__device__ __forceinline__ RowSlot row_slot(const int64_t* __restrict__ row_ptr, size_t lp, long long capacity) {
+    RowSlot s;
+    s.base = row_ptr[lp];
+    const long long end = row_ptr[lp + 1];
+    const long long len = (s.base >= 0 && end >= s.base) ? end - s.base : -1;
+    const long long room = (s.base >= 0 && s.base < capacity) ? capacity - s.base : 0;  // (0 < room <= capacity: no overflow)
+    const long long ok = len < room ? len : room;
+    s.n_ok = ok > 0 ? static_cast<unsigned>(ok < 0x7fffffffll ? ok : 0x7fffffffll) : 0u;
+    s.fits = len >= 0 && static_cast<long long>(s.n_ok) == len;
+    return s;
+}
+
+// rows whose length is not row_ptr's or that found no room below capacity, counted once per wavefront
+__device__ __forceinline__ void count_changed_rows(bool changed, unsigned* __restrict__ changed_rows) {
+    const unsigned n = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(changed)));
+    if (n && (threadIdx.x & 63) == 0) atomicAdd(changed_rows, n);
 }
 
 }  // namespace adj

@@ -1,6 +1,7 @@
 // ------------------------------------------------------------------------------------------
 // The ray matrix (ray_matrix_kernels.hip): per pixel the cells its ray crosses and the chord of each crossing, as CSR
-// arrays - rows and fill over derivative_host.hpp and, next to them, their entry points.
+// arrays - rows and fill over derivative_host.hpp and, next to them, their entry points.  And the ray Jacobian: the same
+// rows with the adjoint's per-segment terms as values (jacobian_walk / jacobian_fill_resolve, scalar_derivative_kernels.hip).
 // ------------------------------------------------------------------------------------------
 #include "derivative_host.hpp"
 
@@ -42,21 +43,24 @@ int enqueue_ray_matrix_rows(c5_context* ctx, int64_t* row_ptr) {
     return commit_derivative(ctx, v, "ray matrix rows");
 }
 
+// A fill on a scene of solids only: every row is empty, and a row_ptr that says otherwise is another frame's; this waits
+int fill_without_cells(c5_context* ctx, const DerivativeView& v, const int64_t* row_ptr, const char* what, const char* fill) {
+    int64_t total = 0;
+    C5_HIP(ctx, hipMemcpyAsync(&total, row_ptr + v.n_px, sizeof total, hipMemcpyDeviceToHost, v.s));
+    C5_HIP(ctx, hipStreamSynchronize(v.s));
+    if (total != 0)
+        return fail(ctx, C5_ERR_STATE, "%s: the frame changed between c5_ray_matrix_rows and %s: "
+                    "row_ptr holds %lld segments, the scene has no cells", what, fill, static_cast<long long>(total));
+    return C5_OK;
+}
+
 // The ray matrix's arrays: a per-view setup of its own, then segment_walk<2> (or segment_fill_resolve), which writes only
 // inside [0, capacity) and counts the rows that differ from row_ptr; that count travels to the host behind the status words.
 int enqueue_ray_matrix_fill(c5_context* ctx, const int64_t* row_ptr, int64_t capacity, int32_t* col, double* dz, double* z_exit) {
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc) return rc;
-    if (v.no_cells) {  // (solids only: every row is empty, and a row_ptr that says otherwise is another frame's; this waits)
-        int64_t total = 0;
-        C5_HIP(ctx, hipMemcpyAsync(&total, row_ptr + v.n_px, sizeof total, hipMemcpyDeviceToHost, v.s));
-        C5_HIP(ctx, hipStreamSynchronize(v.s));
-        if (total != 0)
-            return fail(ctx, C5_ERR_STATE, "ray matrix fill: the frame changed between c5_ray_matrix_rows and c5_ray_matrix_fill: "
-                        "row_ptr holds %lld segments, the scene has no cells", static_cast<long long>(total));
-        return C5_OK;
-    }
+    if (v.no_cells) return fill_without_cells(ctx, v, row_ptr, "ray matrix fill", "c5_ray_matrix_fill");
     int32_t* count;
     unsigned* changed_rows;
     rc = ray_matrix_buffer(ctx, v, count, changed_rows);
@@ -80,6 +84,46 @@ int enqueue_ray_matrix_fill(c5_context* ctx, const int64_t* row_ptr, int64_t cap
     rc = commit_derivative(ctx, v, "ray matrix fill");
     if (rc) return rc;
     C5_HIP(ctx, hipMemcpyAsync(ctx->deriv.adj_status + 3, changed_rows, sizeof(unsigned), hipMemcpyDeviceToHost, v.s));
+    return C5_OK;
+}
+
+// The ray Jacobian's arrays: the ray matrix fill's frame around the adjoint's two passes - the Lambda pre-pass as adjoint_one
+// runs it (adjoint_walk<1>, the heads left in place), then jacobian_walk, which stores where segment_walk<2> would; or
+// jacobian_fill_resolve over bin_sort_resolve's lists.  Any array may be null.
+int enqueue_ray_jacobian_fill(c5_context* ctx, const int64_t* row_ptr, int64_t capacity, int32_t* col, double* dz, double* dI_da,
+                              double* dI_dq) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    if (v.no_cells) return fill_without_cells(ctx, v, row_ptr, "ray jacobian fill", "c5_ray_jacobian_fill");
+    int32_t* count;
+    unsigned* changed_rows;
+    rc = ray_matrix_buffer(ctx, v, count, changed_rows);
+    if (rc) return rc;
+    C5_HIP(ctx, hipMemsetAsync(changed_rows, 0, sizeof(unsigned), v.s));
+    const c5::JacobianRows j{row_ptr, capacity, v.perm, col, dz, dI_da, dI_dq, changed_rows};
+    if (v.bin_sort) {
+        c5::launch_jacobian_fill_resolve(v.s, v.r, j);
+    } else {
+        c5::AdjointParams ap;
+        rc = adjoint_params(ctx, v, ap);
+        if (rc) return rc;
+        c5::launch_adjoint_walk(v.s, ap, 1);
+        v.keep(false);  // (the fill hands every head back cleared)
+        c5::launch_jacobian_walk(v.s, ap, j);
+    }
+    rc = commit_derivative(ctx, v, "ray jacobian fill");
+    if (rc) return rc;
+    C5_HIP(ctx, hipMemcpyAsync(ctx->deriv.adj_status + 3, changed_rows, sizeof(unsigned), hipMemcpyDeviceToHost, v.s));
+    return C5_OK;
+}
+
+// what both forms of c5_ray_jacobian_fill check of their arguments
+int check_ray_jacobian(c5_context* ctx, bool host, const void* row_ptr, int64_t capacity, const void* dI_da, const void* dI_dq) {
+    int rc = check_derivative(ctx, {"c5_ray_jacobian_fill", host, 1, nullptr, row_ptr && (dI_da || dI_dq), true,
+                                    "null row_ptr, or neither dI_dalpha nor dI_dq"});
+    if (rc) return rc;
+    if (capacity < 0) return fail(ctx, C5_ERR_INVALID, "c5_ray_jacobian_fill: negative capacity (%lld)", static_cast<long long>(capacity));
     return C5_OK;
 }
 
@@ -139,6 +183,35 @@ int c5_ray_matrix_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t cap
                   {nullptr, z_exit_host, z_exit_host ? n * sizeof(double) : 0}};
     return run_staged(ctx, "ray matrix fill", b, [&] {
         return enqueue_ray_matrix_fill(ctx, b[0].as<const int64_t>(), need, b[1].as<int32_t>(), b[2].as<double>(), b[3].as<double>());
+    });
+}
+
+int c5_ray_jacobian_fill_device(c5_context* ctx, const void* row_ptr_dev, int64_t capacity, void* col_dev, void* dz_dev,
+                                void* dI_dalpha_dev, void* dI_dq_dev) {
+    int rc = check_ray_jacobian(ctx, false, row_ptr_dev, capacity, dI_dalpha_dev, dI_dq_dev);
+    if (rc) return rc;
+    return enqueue_ray_jacobian_fill(ctx, static_cast<const int64_t*>(row_ptr_dev), capacity, static_cast<int32_t*>(col_dev),
+                                     static_cast<double*>(dz_dev), static_cast<double*>(dI_dalpha_dev), static_cast<double*>(dI_dq_dev));
+}
+
+// Staged for row_ptr's total, as c5_ray_matrix_fill: nothing beyond it is written on the device or copied back.
+int c5_ray_jacobian_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t capacity, int32_t* col_host, double* dz_host,
+                         double* dI_dalpha_host, double* dI_dq_host) {
+    int rc = check_ray_jacobian(ctx, true, row_ptr_host, capacity, dI_dalpha_host, dI_dq_host);
+    if (rc) return rc;
+    const int64_t n_px = local_pixels(ctx->im), need = row_ptr_host[n_px];
+    if (need < 0 || need > capacity)
+        return fail(ctx, C5_ERR_INVALID, "c5_ray_jacobian_fill: row_ptr asks for %lld elements, capacity is %lld",
+                    static_cast<long long>(need), static_cast<long long>(capacity));
+    const size_t n = static_cast<size_t>(need);
+    Staged b[] = {{row_ptr_host, nullptr, static_cast<size_t>(n_px + 1) * sizeof(int64_t)},
+                  {nullptr, col_host, col_host ? n * sizeof(int32_t) : 0},
+                  {nullptr, dz_host, dz_host ? n * sizeof(double) : 0},
+                  {nullptr, dI_dalpha_host, dI_dalpha_host ? n * sizeof(double) : 0},
+                  {nullptr, dI_dq_host, dI_dq_host ? n * sizeof(double) : 0}};
+    return run_staged(ctx, "ray jacobian fill", b, [&] {
+        return enqueue_ray_jacobian_fill(ctx, b[0].as<const int64_t>(), need, b[1].as<int32_t>(), b[2].as<double>(), b[3].as<double>(),
+                                         b[4].as<double>());
     });
 }
 

@@ -3,36 +3,11 @@
 // each: the count (pass 1: segment_walk<1>, then launch_scan64 over the counts) and the fill (pass 2: segment_walk<2> stores
 // (cell, dz, z_exit) per segment); segment_count_resolve / segment_fill_resolve over bin_sort_resolve's lists.  The walk is
 // adj::Ray's (deriv_ray.hpp), the other derivatives' chords to the bit.  Each lane owns its row and appends to it with plain
-// stores: no atomics, bit-reproducible.
+// stores: no atomics, bit-reproducible (adj::row_slot, count_changed_rows: deriv_ray.hpp, shared with the ray Jacobian).
 #include "deriv_lists.hpp"
 
 namespace c5 {
 namespace adj {
-
-// Where a lane's row goes: element k at base + k for k < n_ok, the part of row_ptr's row that lies in [0, capacity).
-// fits: all of row_ptr's row does.  Whatever row_ptr holds, base + k stays inside [0, capacity) for k < n_ok.
-struct RowSlot {
-    long long base = 0;
-    unsigned n_ok = 0;
-    bool fits = true;
-};
-__device__ __forceinline__ RowSlot row_slot(const int64_t* __restrict__ row_ptr, size_t lp, long long capacity) {
-    RowSlot s;
-    s.base = row_ptr[lp];
-    const long long end = row_ptr[lp + 1];
-    const long long len = (s.base >= 0 && end >= s.base) ? end - s.base : -1;
-    const long long room = (s.base >= 0 && s.base < capacity) ? capacity - s.base : 0;  // (0 < room <= capacity: no overflow)
-    const long long ok = len < room ? len : room;
-    s.n_ok = ok > 0 ? static_cast<unsigned>(ok < 0x7fffffffll ? ok : 0x7fffffffll) : 0u;
-    s.fits = len >= 0 && static_cast<long long>(s.n_ok) == len;
-    return s;
-}
-
-// rows whose length is not row_ptr's or that found no room below capacity, counted once per wavefront
-__device__ __forceinline__ void count_changed_rows(bool changed, unsigned* __restrict__ changed_rows) {
-    const unsigned n = static_cast<unsigned>(__popcll(__builtin_amdgcn_ballot_w64(changed)));
-    if (n && (threadIdx.x & 63) == 0) atomicAdd(changed_rows, n);
-}
 
 __device__ __forceinline__ void store_segment(const RayMatrixParams& A, long long at, int cell, double dz, double z_exit) {
     // (plain stores: a lane's next element lands in the line its last one did, and L2 merges them.  Nontemporal stores

@@ -21,6 +21,10 @@
 //                     "exact_sums" the diagonal's and the Hessian-vector render's bodies take them too (gn_diag_exact_*,
 //                     hvp_exact_*), and the product runs adjoint_exact_* on each direction's g.
 //
+//   jacobian_walk / jacobian_fill_resolve   (c5_ray_jacobian_fill*) adjoint_walk<2> / adjoint_resolve for the upstream image
+//                     (0, 1) at every pixel with the scatter policy RowStore: nothing is summed, every lane appends its
+//                     segments' (cell, dz, d I / d alpha, d I / d Q) to its own pixel's row of the ray matrix's CSR structure.
+//
 // The tangent (forward mode, c5_render_tangent*): the change (tau_dot, I_dot) of every pixel for a change (dalpha, dQ) of
 // the cells' scalars, the same terms carried forward along the ray instead of scattered back:
 //     tau_dot = sum_k dz_k dalpha_k                                              (raw alpha, every segment)
@@ -165,10 +169,47 @@ struct ExactScatter {
     }
 };
 
+// The ray Jacobian's sink: nothing is summed.  The bodies run with the upstream image (0, 1) at every pixel, so a step's
+// (ga, gq) ARE the segment's (d I / d alpha, d I / d Q) - the doubles the adjoint adds for a one-hot upstream image - and
+// each lane appends them, with the chord, to its own pixel's row (row_slot: inside [0, capacity) whatever row_ptr holds).
+// No lane needs another: with this sink the bodies' loops are per lane, and a lane leaves when its ray ends.
+struct RowStore {
+    JacobianRows J;
+    RowSlot slot;
+    unsigned k = 0;  // segments of the row so far
+    double chord_dz = 0.0;
+    __device__ explicit RowStore(const JacobianRows& j) : J(j) {}
+    __device__ __forceinline__ void begin(bool in_image, size_t lp) {
+        if (in_image) slot = row_slot(J.row_ptr, lp, J.capacity);
+    }
+    __device__ __forceinline__ void first(int) {}
+    __device__ __forceinline__ void next(int) {}
+    __device__ __forceinline__ void advance() {}
+    __device__ __forceinline__ bool keep_heads() const { return false; }
+    __device__ __forceinline__ void chord(double dz) { chord_dz = dz; }
+    __device__ __forceinline__ void operator()(bool emit, int cell, double ga, double gq) {
+        if (!emit) return;
+        if (k < slot.n_ok) {  // (plain stores, as store_segment's: ray_matrix_kernels.hip)
+            const long long at = slot.base + k;
+            if (J.col) J.col[at] = J.perm ? J.perm[cell] : cell;
+            if (J.dz) J.dz[at] = chord_dz;
+            if (J.dI_da) J.dI_da[at] = ga;
+            if (J.dI_dq) J.dI_dq[at] = gq;
+        }
+        ++k;
+    }
+    // by every lane of the wavefront, after its loop
+    __device__ __forceinline__ void end(bool in_image) const {
+        count_changed_rows(in_image && !(slot.fits && k == slot.n_ok), J.changed_rows);
+    }
+};
+
 // Pass 1 (Lambda per pixel) and pass 2 (the scatter) of the adjoint; SQUARED: pass 2 with the segment's terms squared
-// and A.grad_out the weights or nullptr for ones (gn_diag_walk).  Scatter: where pass 2's terms go (above).
+// and A.grad_out the weights or nullptr for ones (gn_diag_walk).  Scatter: where pass 2's terms go (above); RowStore:
+// the upstream image is (0, 1) everywhere, A.grad_out is not read.
 template <int PASS, bool SQUARED, class Scatter>
 __device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A, Scatter sc) {
+    constexpr bool kRows = std::is_same<Scatter, RowStore>::value;
     const WalkParams& P = A.w;
     Ray r;
     double lam = 0.0;                                         // Lambda_k so far
@@ -176,12 +217,13 @@ __device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A, Scatte
 
     const EntryHead ent = ray_begin(r, P, [&] {
         if (PASS == 1) return true;
-        const float2 g = (SQUARED && !A.grad_out) ? make_float2(1.0f, 1.0f) : A.grad_out[r.lp];
+        const float2 g = kRows ? make_float2(0.0f, 1.0f) : (SQUARED && !A.grad_out) ? make_float2(1.0f, 1.0f) : A.grad_out[r.lp];
         g_tau = g.x;
         g_I = g.y;
         lam_total = A.lambda[r.lp];
         return g_tau != 0.0 || g_I != 0.0;
     });
+    if constexpr (kRows) sc.begin(r.in_image, r.lp);
 
     CellRegs cur;
     if (r.cell >= 0) {
@@ -189,10 +231,11 @@ __device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A, Scatte
         if (PASS == 2) sc.first(r.cell);
     }
 
-    // wave-uniform loop (the scatter wants every lane): a lane whose ray has ended takes part with nothing to add
+    // wave-uniform loop (the scatter wants every lane): a lane whose ray has ended takes part with nothing to add.  kRows:
+    // per lane, as tangent_walk's
     for (;;) {
         const bool live = r.cell >= 0;
-        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        if (kRows ? !live : __builtin_amdgcn_ballot_w64(live) == 0ull) break;
         bool emit = false;
         double ga = 0.0, gq = 0.0;
         const int here = r.cell;
@@ -211,6 +254,7 @@ __device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A, Scatte
                     if (a != 0.0) lam = lambda_add(lam, a, dz);
                 } else {
                     emit = true;
+                    if constexpr (kRows) sc.chord(dz);
                     ga = g_tau * (SQUARED ? dz * dz : dz);  // d tau / d alpha (line.cpp:189: raw alpha, every segment)
                     if (a != 0.0) {
                         lam = lambda_add(lam, a, dz);  // (as in pass 1: Lambda_n == Lambda bit for bit, Lambda - Lambda_k >= 0)
@@ -236,8 +280,9 @@ __device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A, Scatte
     if (PASS == 1) {
         if (r.in_image) A.lambda[r.lp] = lam;
         ray_count(r, P);
-    } else if (!sc.keep_heads()) {
-        ray_clear_head(r, P);
+    } else {
+        if constexpr (kRows) sc.end(r.in_image);
+        if (!sc.keep_heads()) ray_clear_head(r, P);
     }
 }
 
@@ -246,26 +291,33 @@ __device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A, Scatte
 // k = n - i).  SQUARED: the segment's terms squared, `weights` nullptr for ones (gn_diag_resolve).
 template <bool SQUARED, class Scatter>
 __device__ __forceinline__ void adjoint_resolve_body(const ResolveParams& R, const float2* __restrict__ weights, Scatter sc) {
+    constexpr bool kRows = std::is_same<Scatter, RowStore>::value;  // (as adjoint_walk_body's: `weights` is not read)
     const GridView& g = R.g;
     double g_tau = 0.0, g_I = 0.0;
     const ListFrame f = list_frame<false>(R, [&](int64_t lp) {
-        const float2 gw = (SQUARED && !weights) ? make_float2(1.0f, 1.0f) : weights[lp];
+        const float2 gw = kRows ? make_float2(0.0f, 1.0f) : (SQUARED && !weights) ? make_float2(1.0f, 1.0f) : weights[lp];
         g_tau = gw.x;
         g_I = gw.y;
         return !(g_tau == 0.0 && g_I == 0.0);
     });
+    if constexpr (kRows) sc.begin(f.in_image, static_cast<size_t>(f.lp));
     const double lam_total = lambda_total(f.list, f.n, g, R.alpha_limit);
     double lam = 0.0, I = 0.0;
-    // wave-uniform loop over the steps (the scatter wants every lane)
+    // wave-uniform loop over the steps (the scatter wants every lane; kRows: per lane)
     for (int i = f.n - 1;; --i) {
         const bool live = i >= 0;
-        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        if (kRows ? !live : __builtin_amdgcn_ballot_w64(live) == 0ull) break;
         int c = -1;
+        bool emit = live;
         double ga = 0.0, gq = 0.0;
         if (live) {
             c = static_cast<int>(f.list[i].cell);
             sc.first(c);
             const double dz = f.list[i].dz, q = g.q[c];
+            if constexpr (kRows) {  // (the rows hold the segments the frame sums, as segment_fill_resolve's: a chord of 0 adds nothing)
+                emit = is_segment(dz);
+                sc.chord(dz);
+            }
             const ClampedAlpha ca = clamp_alpha(g.alpha[c], R.alpha_limit);
             const double a = ca.a;
             ga = g_tau * (SQUARED ? dz * dz : dz);
@@ -279,8 +331,9 @@ __device__ __forceinline__ void adjoint_resolve_body(const ResolveParams& R, con
                 I = t.I_next;
             }
         }
-        sc(live, c, ga, gq);
+        sc(emit, c, ga, gq);
     }
+    if constexpr (kRows) sc.end(f.in_image);
 }
 
 }  // namespace adj
@@ -295,6 +348,16 @@ __global__ __launch_bounds__(64) void adjoint_walk(AdjointParams A) {
 __global__ __launch_bounds__(256) void adjoint_resolve(ResolveParams R, const float2* __restrict__ grad_out,
                                                        double* __restrict__ grad_a, double* __restrict__ grad_q) {
     adj::adjoint_resolve_body<false>(R, grad_out, adj::WaveScatter{grad_a, grad_q});
+}
+
+// The ray Jacobian's fill (after adjoint_walk<1>): adjoint_walk<2> with every lane's terms stored to its own row.  Pass 1
+// has counted the view's rays (ray_count: once per view).
+__global__ __launch_bounds__(64) void jacobian_walk(AdjointParams A, JacobianRows J) {
+    adj::adjoint_walk_body<2, false>(A, adj::RowStore(J));
+}
+
+__global__ __launch_bounds__(256) void jacobian_fill_resolve(ResolveParams R, JacobianRows J) {
+    adj::adjoint_resolve_body<false>(R, nullptr, adj::RowStore(J));
 }
 
 __global__ __launch_bounds__(256) void adjoint_permute(const double* __restrict__ ga_dev, const double* __restrict__ gq_dev,
@@ -951,6 +1014,14 @@ void launch_adjoint_walk(hipStream_t s, const AdjointParams& a, int pass) {
 
 void launch_adjoint_resolve(hipStream_t s, const ResolveParams& r, const float2* grad_out, double* grad_a, double* grad_q) {
     if (const unsigned blocks = pixel_blocks(r.im)) hipLaunchKernelGGL(adjoint_resolve, dim3(blocks), dim3(256), 0, s, r, grad_out, grad_a, grad_q);
+}
+
+void launch_jacobian_walk(hipStream_t s, const AdjointParams& a, const JacobianRows& j) {
+    if (const unsigned blocks = tile_blocks(a.w.im)) hipLaunchKernelGGL(jacobian_walk, dim3(blocks), dim3(64), 0, s, a, j);
+}
+
+void launch_jacobian_fill_resolve(hipStream_t s, const ResolveParams& r, const JacobianRows& j) {
+    if (const unsigned blocks = pixel_blocks(r.im)) hipLaunchKernelGGL(jacobian_fill_resolve, dim3(blocks), dim3(256), 0, s, r, j);
 }
 
 void launch_adjoint_permute(hipStream_t s, const double* ga_dev, const double* gq_dev, const int32_t* perm, int64_t n,

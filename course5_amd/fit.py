@@ -17,7 +17,8 @@ both.  Everything is float64 on the context's GPU.
 A context may bring its own operators: if it has a method gn_operators(alpha, q, weight) returning an object with
 rhs(residual) -> (J^T W r)_alpha, (..)_q, diagonal() -> (diag_alpha, diag_q) and product(v_alpha, v_q) -> (h_alpha, h_q)
 (torch float64 tensors; v_alpha / v_q None: zero), gn_step uses those - a set of row shards that sums its parts
-(RowShards below), a dense model.
+(RowShards below), a dense model, or the Jacobian itself: ExplicitJacobian(ctx) exports it once per linearisation
+(autograd.ray_jacobian's arrays), and every CG iteration is then sparse products in float64 with no walk.
 
 newton_product and newton_step are the same with the EXACT Hessian of 1/2 sum w r^2: H + sum_p w_p r_p Hess(img_p), the
 second term from autograd.hvp (c5_render_hvp) on grad_img = W r.  The frame is exponential in alpha, so a fit of alpha is
@@ -59,6 +60,129 @@ class _LibraryOperators:
     def hvp(self, v_alpha, v_q, grad_img):
         from . import autograd
         return autograd.hvp(self.ctx, self.alpha, self.q, v_alpha, v_q, grad_img)
+
+
+class JacobianOperators:
+    """rhs, diagonal and product of gn_step from the Jacobian's CSR arrays (capi.Context.ray_jacobian,
+    autograd.ray_jacobian): row_ptr [n_px + 1], col, dz = d tau / d alpha, dI_dalpha, dI_dq [nnz] - torch tensors on any
+    one device, the CPU included - n_cells, and weight [n_px, 2] or [rows, res_x, 2] (None: ones).  Everything in float64:
+
+        H v = A^T (w_tau * (A v_a)) + J_I^T (w_I * (J_alpha v_a + J_q v_q)),   J_I^T = (J_alpha^T, J_q^T).
+
+    Neither a CSR product nor its transpose is asked of torch.  A product is one gather, one multiply and one segmented sum
+    (torch.segment_reduce): over the CSR rows for J v, and for J^T g over a copy of the values sorted by column, made once
+    here (a stable argsort of col, the row of every nonzero from repeat_interleave of the rows' lengths).  No atomics: the
+    same bits every call, on the CPU and on a GPU.  (index_add_ by col is correct too and needs no copy, but on the
+    benchmark frame its fp64 atomics take a second per product where the segmented sums take milliseconds: DESIGN 4.19.)
+    Unlike the library's product, J v is not rounded to float32 on the way.
+    hvp: what newton_step also needs, (v_alpha, v_q, grad_img) -> (h_alpha, h_q), or None."""
+
+    def __init__(self, row_ptr, col, dz, dI_dalpha, dI_dq, n_cells: int, weight=None, hvp=None):
+        row_ptr = torch.as_tensor(row_ptr).to(torch.int64)
+        self.n_px, self.n_cells = row_ptr.shape[0] - 1, int(n_cells)
+        self.row_ptr = row_ptr.contiguous()
+        self.col = torch.as_tensor(col).to(device=row_ptr.device, dtype=torch.int64)
+        row = torch.repeat_interleave(torch.arange(self.n_px, device=row_ptr.device), row_ptr[1:] - row_ptr[:-1])
+        self.dz, self.da, self.dq = (torch.as_tensor(t).to(device=row_ptr.device, dtype=torch.float64) for t in (dz, dI_dalpha, dI_dq))
+        if not (row.shape == self.col.shape == self.dz.shape == self.da.shape == self.dq.shape):
+            raise ValueError(f"col, dz, dI_dalpha and dI_dq must hold row_ptr's {row.shape[0]} elements each")
+        if self.col.numel() and not (0 <= int(self.col.min()) and int(self.col.max()) < self.n_cells):
+            raise ValueError(f"col must name cells 0 .. {self.n_cells - 1}")
+        # the same matrix by column: where every cell's nonzeros are, their rows and their values
+        order = torch.argsort(self.col, stable=True)
+        self.col_ptr = torch.zeros(self.n_cells + 1, dtype=torch.int64, device=row_ptr.device)
+        self.col_ptr[1:] = torch.cumsum(torch.bincount(self.col, minlength=self.n_cells), 0)
+        self.row_by_col = row[order]
+        self.dz_c, self.da_c, self.dq_c = self.dz[order], self.da[order], self.dq[order]
+        self.weight = None
+        if weight is not None:
+            self.weight = torch.as_tensor(weight).detach().to(device=row_ptr.device, dtype=torch.float32).reshape(-1, 2)
+            if self.weight.shape[0] != self.n_px:
+                raise ValueError(f"weight must hold two values for each of the {self.n_px} pixels")
+        self._hvp = hvp
+
+    def _to_pixels(self, values, v):
+        """sum over a pixel's nonzeros of values * v[col]: one column of J v (values in row order)."""
+        return torch.segment_reduce(values * v[self.col], "sum", offsets=self.row_ptr)
+
+    def _to_cells(self, values_c, g):
+        """sum over a cell's nonzeros of values * g[row]: one block of J^T g (values in column order)."""
+        return torch.segment_reduce(values_c * g[self.row_by_col], "sum", offsets=self.col_ptr)
+
+    def _direction(self, v):
+        return None if v is None else torch.as_tensor(v).detach().to(device=self.dz.device, dtype=torch.float64).reshape(self.n_cells)
+
+    def jv(self, v_alpha, v_q):
+        """J v per pixel: (tau_dot, I_dot), float64 [n_px] each (a None direction: zero)."""
+        va, vq = self._direction(v_alpha), self._direction(v_q)
+        zero = torch.zeros(self.n_px, dtype=torch.float64, device=self.dz.device)
+        tau = zero if va is None else self._to_pixels(self.dz, va)
+        I = zero.clone()
+        if va is not None:
+            I = I + self._to_pixels(self.da, va)
+        if vq is not None:
+            I = I + self._to_pixels(self.dq, vq)
+        return tau, I
+
+    def jt(self, g_tau, g_I):
+        """J^T g per cell: (grad_alpha, grad_q) for the upstream image (g_tau, g_I), float64 [n_px] each."""
+        return self._to_cells(self.dz_c, g_tau) + self._to_cells(self.da_c, g_I), self._to_cells(self.dq_c, g_I)
+
+    def rhs(self, residual):
+        """J^T W r; W r is formed in float32, as the library's right-hand side forms it."""
+        g = torch.as_tensor(residual).detach().to(device=self.dz.device, dtype=torch.float32).reshape(-1, 2)
+        if g.shape[0] != self.n_px:
+            raise ValueError(f"residual must hold two values for each of the {self.n_px} pixels")
+        if self.weight is not None:
+            g = g * self.weight
+        g = g.to(torch.float64)
+        return self.jt(g[:, 0], g[:, 1])
+
+    def _w(self):
+        w = self.weight
+        return (None, None) if w is None else (w[:, 0].to(torch.float64), w[:, 1].to(torch.float64))
+
+    def diagonal(self):
+        w_tau, w_I = self._w()
+        one = torch.ones(self.n_px, dtype=torch.float64, device=self.dz.device)
+        w_tau, w_I = (one if w is None else w for w in (w_tau, w_I))
+        return (self._to_cells(self.dz_c * self.dz_c, w_tau) + self._to_cells(self.da_c * self.da_c, w_I),
+                self._to_cells(self.dq_c * self.dq_c, w_I))
+
+    def product(self, v_alpha, v_q):
+        tau, I = self.jv(v_alpha, v_q)
+        w_tau, w_I = self._w()
+        return self.jt(tau if w_tau is None else w_tau * tau, I if w_I is None else w_I * I)
+
+    def hvp(self, v_alpha, v_q, grad_img):
+        if self._hvp is None:
+            raise RuntimeError("these operators were built from arrays alone: the Jacobian does not hold second derivatives")
+        return self._hvp(v_alpha, v_q, grad_img)
+
+
+class ExplicitJacobian:
+    """A context whose Gauss-Newton operators work on the exported Jacobian:
+
+        delta, models = course5_amd.fit.gn_step(course5_amd.fit.ExplicitJacobian(ctx), alpha, q, residual, fit=("q",))
+
+    gn_operators(alpha, q, weight) exports the Jacobian of the frame of `ctx` at (alpha, q) once (autograd.ray_jacobian's
+    arrays: one c5_ray_matrix_rows and one c5_ray_jacobian_fill, nnz x 28 bytes on the context's GPU) and returns
+    JacobianOperators over it: the right-hand side, the diagonal and every CG iteration's product are then sparse sums
+    in float64 with no walk.  It pays where one linearisation serves many products: small and medium frames, many CG
+    iterations, LSQR or column norms of the caller's own.  hvp goes to the library (c5_render_hvp), so newton_step works."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def gn_operators(self, alpha, q, weight):
+        from . import autograd
+        ctx = self.ctx
+        device = autograd._gn_enter(ctx, alpha, q, "ExplicitJacobian")
+        with torch.cuda.device(device):
+            crow, col, dz, da, dq = autograd._ray_jacobian_arrays(ctx, device)
+            w = autograd._gn_weight(ctx, weight, device)
+        library = _LibraryOperators(ctx, alpha, q, weight)
+        return JacobianOperators(crow, col, dz, da, dq, ctx.n_cells, w, hvp=library.hvp)
 
 
 def _host(t, dtype):

@@ -733,7 +733,7 @@ int c5_render_vertex_gn_product_device(c5_context* ctx, int n_dirs, const void* 
  * The operator every derivative render applies, handed out: for each pixel the cells its ray crosses and the chord dz of
  * each crossing, as a CSR matrix A with A[pixel][cell] = dz.  Channel 0 of the image is linear in the cells' alpha:
  * tau = A alpha (raw alpha, line.cpp:189), and A^T g is c5_render_adjoint's grad_alpha for the upstream image (g, 0).
- * Channel 1 (I) is not linear in alpha and is not covered.
+ * Channel 1 (I) is not linear in alpha: its derivatives per segment are c5_ray_jacobian_fill's, below.
  * The matrix belongs to the frame c5_render would produce NOW: grid, solids, image, row range and row tiles, view.  No
  * render needs to come first; the cells' scalars and the alpha limit do not enter.
  * Rows: the context's local pixels, lrow * res_x + col, the output image's order.  Columns: cells in the CALLER's order
@@ -769,6 +769,43 @@ int c5_ray_matrix_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t cap
                        double* z_exit_host);
 int c5_ray_matrix_fill_device(c5_context* ctx, const void* row_ptr_dev, int64_t capacity, void* col_dev, void* dz_dev,
                               void* z_exit_dev);
+
+/* --- ray Jacobian ------------------------------------------------------------------------------------
+ * The Jacobian J = d(tau, I) / d(alpha, Q) the derivative renders apply, handed out per segment: three CSR matrices over
+ * the ray matrix's structure.  For pixel p and the k-th cell c its ray crosses (the notation of c5_render_adjoint: a_k =
+ * min(alpha_k, limit), E_k = exp(-a_k dz_k), T_k the transmittance from segment k to the viewer, I_{k-1} the intensity
+ * behind it):
+ *   dz[k]        = d tau_p / d alpha_c                                                    (raw alpha, every segment)
+ *   dI_dalpha[k] = d I_p / d alpha_c = T_k [Q_k (dz_k E_k / a_k - (1 - E_k) / a_k^2) - dz_k E_k I_{k-1}]
+ *   dI_dq[k]     = d I_p / d Q_c     = T_k (1 - E_k) / a_k
+ * An inactive segment (a_k < DBL_EPSILON) stores explicit zeros in dI_dalpha and dI_dq; a clamped alpha (alpha_k > limit)
+ * stores 0 in dI_dalpha and the value in dI_dq.  The values are the doubles c5_render_adjoint adds to its sums:
+ * c5_render_adjoint for an upstream image that is (0, 1) at pixel p and zero elsewhere returns row p of dI_dalpha /
+ * dI_dq scattered by col, bit for bit, and for (1, 0) row p of dz (an element of -0 reads +0 there).
+ * Inputs: row_ptr is c5_ray_matrix_rows' output for the same frame.  The Jacobian belongs to the frame c5_render would
+ * produce NOW; unlike the ray matrix it includes the cells' scalars (c5_update_scalars(_device)) and c5_set_alpha_limit.
+ * The STRUCTURE never depends on them: rows, the column convention (the caller's cell order), the entries (dz > 0 and
+ * finite) and the order within a row (deepest first) are exactly c5_ray_matrix_fill's, col and dz its arrays bit for bit;
+ * solid-marked and uncovered pixels give empty rows.
+ * col and dz may be NULL (a caller who has them from c5_ray_matrix_fill); one of dI_dalpha and dI_dq may be NULL, both:
+ * C5_ERR_INVALID.  A NULL row_ptr, a negative capacity: C5_ERR_INVALID.
+ * Guard and status are the ray matrix fill's: nothing outside [0, capacity) is ever written, whatever row_ptr holds; rows
+ * whose length differs from row_ptr's, or that found no room below capacity, are counted, and the next wait returns
+ * C5_ERR_STATE; row_ptr[local_px] > capacity in the host form: C5_ERR_INVALID with the size needed, nothing written; a
+ * solids-only scene writes nothing and returns C5_ERR_STATE itself for a row_ptr whose total is not 0.  C5_RETRY and
+ * C5_ERR_WALK as for every derivative; the host form is synchronous and retries by itself, the _device form is asynchronous
+ * on the context's stream and reports at the next call that waits for it.  Both refuse while c5_render_host_async frames
+ * are outstanding (C5_ERR_STATE), and a context without a grid or an image as c5_render_adjoint does.
+ * The options "integration", "depth_split", "lds_stage", "tile", "adjoint_exact", "exact_sums" and "vertex_exact" change
+ * nothing: whole rays, the reference's order.  No atomics, every lane owns its row: bit-reproducible, and the rows of a
+ * row range or of row tiles are bit for bit those rows of the whole frame's.  A c5_render afterwards returns the bits it
+ * would have returned without the call (the slot's per-view data are marked stale, as by the adjoint).
+ * Memory: the arrays are the caller's, nnz x 28 bytes for all four.  The library allocates the adjoint's 8 bytes per local
+ * pixel (Lambda) and the ray matrix's 4; a context that never calls it allocates nothing. */
+int c5_ray_jacobian_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t capacity, int32_t* col_host, double* dz_host,
+                         double* dI_dalpha_host, double* dI_dq_host);
+int c5_ray_jacobian_fill_device(c5_context* ctx, const void* row_ptr_dev, int64_t capacity, void* col_dev, void* dz_dev,
+                                void* dI_dalpha_dev, void* dI_dq_dev);
 
 /* --- frames delivered to host memory, pipelined ----------------------------------------------------
  * plane::trace_rays hands back HOST pixels (plane.cpp:144-172); over PCIe Gen5 a 2400x1800 image is
