@@ -6,14 +6,18 @@ against the numpy restatements, element by element.
     python tests/derivative_fuzz.py forward [n_scenes] [seed0]       (the forward sweep, at the end of this text)
     python tests/derivative_fuzz.py second [n_scenes] [seed0]        (the second-order and exact-sum sweep, below)
     python tests/derivative_fuzz.py vertex_exact [n_scenes] [seed0]  (the vertex sweep, below)
-    python tests/derivative_fuzz.py chords SEED PIXEL      (the GPU's chords along one ray against the reference's)
+    python tests/derivative_fuzz.py chords [unstructured] SEED PIXEL   (the GPU's chords along one ray against the
+                                                            reference's; unstructured: tests/unstructured_scenes.py's scene)
 
 reports every mismatch and the worst error / tolerance per call kind; exit status 1 on any mismatch or when more than
 10 % of the seeds had to be skipped.  tests/test_gpu_derivative_fuzz.py runs 40 seeds of it under pytest;
 tests/test_derivative_references_cpu.py holds the restatements to an 80-digit reference on the same scenes.
 
 derivative_scene(seed) takes grid, view, image size and alpha limit from fuzz_scenes.scene(seed) (images of 20-500
-pixels a side, almost never a multiple of the 8x8 tile; limits U[0.5, 6); views about three axes) and adds
+pixels a side, almost never a multiple of the 8x8 tile; limits U[0.5, 6); views about three axes) - or, with
+mesh=unstructured_scenes.scene, from the graded, high-valence, relabelled meshes of tests/unstructured_scenes.py, which
+tests/test_gpu_unstructured_fuzz.py sends through all five sweeps; geometry_scene, forward_scene and second_order_scene pass
+the argument on - and adds
   * alpha by class, every class in every scene with >= 10 cells (ALPHA_CLASSES): 0; (0, DBL_EPSILON); [DBL_EPSILON, 1e-6)
     log-uniform; == limit; the two doubles next to the limit; (limit, 2 limit]; the rest U[0, limit).  "threshold" scenes
     (one in four) scale the rest so that the median a dz of the segments sits at 1/8, the switch between series and closed
@@ -236,8 +240,9 @@ def alpha_class(alpha, limit):
     return c
 
 
-def derivative_scene(seed):
-    xyz, cells, _alpha, _q, rots, res, limit = scene(seed)
+def derivative_scene(seed, mesh=scene):
+    """mesh: the draw of grid, view, image size and limit - fuzz_scenes.scene, or tests/unstructured_scenes.py's."""
+    xyz, cells, _alpha, _q, rots, res, limit = mesh(seed)
     rng = np.random.default_rng([seed, 0xD5])
     s = types.SimpleNamespace(seed=seed, rots=rots, res=res)
     s.soup = bool(rng.integers(5) == 0)
@@ -598,11 +603,11 @@ def check_scene(s, worst):
 
 # ---- the geometry sweep: motion tangent, vertex tangent, vertex adjoint, ray matrix -----------------------------------
 
-def geometry_scene(seed):
+def geometry_scene(seed, mesh=scene):
     """derivative_scene(seed), unchanged, with what the geometry calls need drawn from a stream of its own (module
     docstring: the geometry sweep)."""
     from course5_amd import capi
-    s = derivative_scene(seed)
+    s = derivative_scene(seed, mesh)
     rng = np.random.default_rng([seed, 0x6E0])
     n_pts = len(s.xyz)
     cells = np.asarray(s.cells).reshape(-1, 4)
@@ -976,11 +981,11 @@ def to_rule(alpha, limit, cls, L, target):
     return alpha, limit
 
 
-def forward_scene(seed):
+def forward_scene(seed, mesh=scene):
     """derivative_scene(seed), unchanged, with what the forward sweep adds drawn from a stream of its own (module
     docstring: the forward sweep)."""
     from tests.fuzz_scenes import VARIANTS
-    s = derivative_scene(seed)
+    s = derivative_scene(seed, mesh)
     rng = np.random.default_rng([seed, 0xF0])
     n = len(s.cells)
     s.L = longest_edge(s.xyz, s.cells)
@@ -1360,10 +1365,10 @@ def off_tile_cut(rng, ry):
     return cut - 1 if cut % 8 == 0 else cut
 
 
-def second_order_scene(seed):
+def second_order_scene(seed, mesh=scene):
     """derivative_scene(seed), unchanged, with the walk option of the comparison context and the second split of the rows
     drawn from a stream of its own (module docstring: the second-order sweep)."""
-    s = derivative_scene(seed)
+    s = derivative_scene(seed, mesh)
     rng = np.random.default_rng([seed, 0x2E0])
     s.compare_options = COMPARE_OPTIONS[int(rng.integers(len(COMPARE_OPTIONS)))]
     s.second_split = ("cyclic", "ranges")[int(rng.integers(2))]
@@ -1891,7 +1896,12 @@ def main():
     import torch  # noqa: F401  (HIP runtime load order)
     from oracle.pyoracle import Oracle
     if len(sys.argv) > 3 and sys.argv[1] == "chords":
-        s = derivative_scene(int(sys.argv[2]))
+        mesh = scene
+        if sys.argv[2] == "unstructured":  # (the family of tests/unstructured_scenes.py)
+            from tests import unstructured_scenes
+            mesh = unstructured_scenes.scene
+            del sys.argv[2]
+        s = derivative_scene(int(sys.argv[2]), mesh)
         for c, d, got, f in zip(*gpu_chords(s, int(sys.argv[3]))):
             print(f"cell {c}: dz {d:.6g}, GPU - reference {got - d:+.3g} = {(got - d) / dz_err(s):+.2f} dz_err, F {f:.1f}")
         return 0

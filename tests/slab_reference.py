@@ -1,7 +1,8 @@
-"""An analytic reference that never looks at a cell: a box lo + [0, extent] cut into n_layers equal layers along one grid
-axis, alpha and Q constant in every layer.  What a render of ANY tetrahedral cut of that box must give, whichever cells a
-ray lying in a common face, edge or vertex of the cut is said to cross - the rays on which the per-cell references
-(tests/adjoint_reference.py: segment_lists; the port oracle) mis-pair or give up.
+"""An analytic reference that never looks at a cell: a box lo + [0, extent] cut into n_layers layers along one grid axis -
+equal ones, or with their planes at given positions (planes=) - alpha and Q constant in every layer.  What a render of
+ANY tetrahedral cut of that box must give, whichever cells a ray lying in a common face, edge or vertex of the cut is said
+to cross - the rays on which the per-cell references (tests/adjoint_reference.py: segment_lists; the port oracle) mis-pair
+or give up.
 
 The view is the affine map p_view = R p + t that adjoint_reference.rotate applies (view_map rotates the origin and the unit
 vectors), the pixel centres are adjoint_reference.pixel_coordinates', and a ray's chord in every layer comes from the slab
@@ -24,8 +25,8 @@ is what the dict holds for them).
 Two more entries.  "lat" [pixel, k]: per segment, sum over the five LATERAL families of the Kuhn cut with lattice step
 `lattice` (the two lateral axes u, v and the diagonals u - v, u - w, v - w = m h; w the layer axis) of the interior lattice
 planes the ray crosses inside the segment, |floor(g_end / h) - floor(g_start / h)|, times the family's own F; an edge-on
-family adds nothing (with graze_err: a plane within that depth error x F of the segment counts as crossed).  A walk takes a chord as w_exit(cell) - w_exit(cell before); across a lateral face with the same
-scalars on both sides the face's depth error cancels between the two chords, except where it makes a sliver's chord
+family adds nothing (with graze_err: a plane within that depth error x F of the segment counts as crossed).  A walk takes
+a chord as w_exit(cell) - w_exit(cell before); across a lateral face with the same scalars on both sides the face's depth error cancels between the two chords, except where it makes a sliver's chord
 negative and the walk drops that chord instead of subtracting it: an excess of at most dz_err x F_face per face crossed.
 "lateral": the same dict with lat in place of F, so that every with_scale restatement run on it returns that excess as its
 `sens`.  "graze" [pixel, layer]: F of a layer the ray misses by no more than graze_err x F in depth (its two bounds meet,
@@ -65,11 +66,14 @@ def rays(rots, res_x, res_y, bounds, rows=None):
 
 
 def slab_matrices(lo, extent, n_layers, axis, alpha, q, rots, res_x, res_y, bounds, limit=2.5, rows=None, lattice=None,
-                  graze_err=0.0):
+                  graze_err=0.0, planes=None):
     """ray_matrices' dict of the box lo + [0, extent] (extent: a number or one per axis) in n_layers layers along grid axis
     `axis` with the per-layer scalars alpha, q; C is the layer id, deepest first.  lattice: the step of the lateral
     families counted in "lat" (default: a layer's thickness); graze_err: the chord error per unit F below which a layer
-    that a ray just misses counts as grazed.  Module docstring: "silhouette", "lat", "lateral", "graze"."""
+    that a ray just misses counts as grazed.  Module docstring: "silhouette", "lat", "lateral", "graze".
+    planes: the positions of the n_layers + 1 layer planes along `axis`, ascending from lo to lo + extent (default: equal
+    layers).  The two lateral families that hold the layer axis are then those of a Kuhn cut stretched layer by layer:
+    in a layer [w_j, w_j + t_j] the planes u / lattice - (w - w_j) / t_j = m, with the slope of that normal."""
     lo = np.asarray(lo, np.float64)
     hi = lo + np.broadcast_to(np.asarray(extent, np.float64), (3,))
     o, d, R, n_rows = rays(rots, res_x, res_y, bounds, rows)
@@ -101,7 +105,13 @@ def slab_matrices(lo, extent, n_layers, axis, alpha, q, rots, res_x, res_y, boun
         z_out, F_out = steeper(z_out, F_out, np.maximum(za, zb), Fi, False)
     # the layer planes in ascending depth; segment j lies between planes j and j + 1
     layers = np.arange(n_layers)
-    planes = (lo[axis] + h * np.arange(n_layers + 1) - o[:, axis:axis + 1]) / d[axis]
+    at = lo[axis] + h * np.arange(n_layers + 1)
+    if planes is not None:
+        at = np.asarray(planes, np.float64)
+        assert at.shape == (n_layers + 1,) and (np.diff(at) > 0).all() and at[0] == lo[axis] and at[-1] == hi[axis]
+    w_lo, thick = at[:-1], np.diff(at)  # (per layer, for the stretched lateral families)
+    graded = planes is not None
+    planes = (at - o[:, axis:axis + 1]) / d[axis]
     planes[:, -1] = (hi[axis] - o[:, axis]) / d[axis]
     if d[axis] < 0:
         planes, layers = planes[:, ::-1], layers[::-1]
@@ -120,6 +130,15 @@ def slab_matrices(lo, extent, n_layers, axis, alpha, q, rots, res_x, res_y, boun
     ps = (o[:, None, :] + np.where(valid, start, 0.0)[..., None] * d) - lo
     pe = (o[:, None, :] + np.where(valid, end, 0.0)[..., None] * d) - lo
     for plus, minus in ((u, None), (v, None), (u, v), (u, axis), (v, axis)):
+        if graded and minus == axis:  # column k of the segment arrays is layer layers[k]
+            for k, j in enumerate(layers):
+                Ff = slope(R[:, plus] / hl - R[:, axis] / thick[j])
+                if Ff >= EDGE_ON:
+                    continue
+                gs, ge = (p[:, k, plus] / hl - (p[:, k, axis] + lo[axis] - w_lo[j]) / thick[j] for p in (ps, pe))
+                reach = graze_err * (1.0 / hl + 1.0 / thick[j])  # (graze_err F in depth is graze_err (|n_x| + |n_y|) in g)
+                lat[:, k] += (np.floor(np.maximum(gs, ge) + reach) - np.floor(np.minimum(gs, ge) - reach)) * max(1.0, Ff)
+            continue
         nv = R[:, plus] - (0.0 if minus is None else R[:, minus])
         Ff = slope(nv)
         if Ff >= EDGE_ON:
@@ -192,14 +211,17 @@ def layer_scalars(n):
     return alpha, q
 
 
-def _scene(name, xyz, cells, rots, axis=2, n=4, res=RES, lattice=None, lo=LO, alpha_q=None, absent=(), derivatives=False):
+def _scene(name, xyz, cells, rots, axis=2, n=4, res=RES, lattice=None, lo=LO, alpha_q=None, absent=(), derivatives=False,
+           planes=None, bounds=BOUNDS):
     """A scene: the grid, the view, the layer of every cell (by its centroid), per-layer and per-cell scalars.  absent:
-    layers without cells, alpha = Q = 0 in the reference."""
+    layers without cells, alpha = Q = 0 in the reference.  planes: slab_matrices' (unequal layers)."""
     s = types.SimpleNamespace(name=name, xyz=xyz, cells=np.asarray(cells), rots=np.asarray(rots, np.float64).reshape(-1, 3),
-                              axis=axis, n_layers=n, res=res, bounds=BOUNDS, limit=LIMIT, lo=lo, extent=SIZE,
-                              lattice=SIZE / n if lattice is None else lattice, derivatives=derivatives)
+                              axis=axis, n_layers=n, res=res, bounds=bounds, limit=LIMIT, lo=lo, extent=SIZE,
+                              lattice=SIZE / n if lattice is None else lattice, derivatives=derivatives, planes=planes)
     h = SIZE / n
     s.layer_of_cell = np.floor((xyz[s.cells].mean(1)[:, axis] - lo[axis]) / h).astype(np.int64)
+    if planes is not None:
+        s.layer_of_cell = np.searchsorted(planes, xyz[s.cells].mean(1)[:, axis], side="right") - 1
     assert s.layer_of_cell.min() >= 0 and s.layer_of_cell.max() < n
     s.alpha_l, s.q_l = layer_scalars(n) if alpha_q is None else alpha_q
     s.alpha, s.q = s.alpha_l[s.layer_of_cell], s.q_l[s.layer_of_cell]  # (what the cells carry)
@@ -213,7 +235,7 @@ def _scene(name, xyz, cells, rots, axis=2, n=4, res=RES, lattice=None, lo=LO, al
 def matrices(s, rows=None, graze_err=0.0):
     """slab_matrices of a scene."""
     return slab_matrices(s.lo, s.extent, s.n_layers, s.axis, s.alpha_ref, s.q_ref, s.rots, s.res[0], s.res[1], s.bounds, s.limit,
-                         rows, s.lattice, graze_err)
+                         rows, s.lattice, graze_err, getattr(s, "planes", None))
 
 
 def _permuted(xyz, cells):
@@ -259,6 +281,95 @@ def degenerate_scenes():
                 out[name] = lambda axis=axis, about=about, angle=angle, name=name: _scene(
                     name, *a(), _tilt(about, angle), axis=axis, derivatives=name == "I-z-xy-10")
     return out
+
+
+# ---- graded layer stacks (tests/test_gpu_graded_layers.py; pinned on the CPU by tests/test_slab_reference_cpu.py) -----------
+# A 4 x 4 lateral lattice in 12 layers along z whose thicknesses span 2^-1 .. 2^-26 of the box: what a boundary layer of a
+# real grid looks like to the walk's set-up, whose entry-key slack is 2^-24 of the bounding box's diagonal (times up to
+# 2^15 on steep faces).  Dyadic thicknesses: every plane position is exact.
+GRADED_RES, GRADED_LATERAL, GRADED_LAYERS = (65, 49), 4, 12
+# BOUNDS moved by 2^-10 in x and y: no pixel centre on the image of a lattice vertex or edge.  (On BOUNDS itself column 32 is
+# X = 1, the pivot of view_rotations' y-rotation, which the lattice plane x = 1 passes through - scene H's ground, and
+# row 24 of 49 is Y = 0: pixel (24, 32) is the image of the lattice vertex (1, 0, 0).)  No more than 2^-10: under the steep
+# view the layers are seen nearly edge-on and the thin core of a stack is a band 6e-3 wide about Y = 0, which row 24 must
+# stay in (33 of its pixels then cross all twelve layers; moved by 2^-7 none does).
+GRADED_BOUNDS = (2.0 + 2.0 ** -10, 2.0 ** -10, 1.0 + 2.0 ** -10, -1.0 + 2.0 ** -10)
+_INNER = tuple(2.0 ** -p for p in (12, 14, 16, 18, 20))  # a ratio of 1/4 toward the middle, the thinnest 2^-20 of the box
+STACKS = {
+    # name -> (thicknesses in units of the box, the layers without cells)
+    "geometric": (_INNER, False, ()),
+    "thin": (_INNER[:4] + (2.0 ** -26,), False, ()),  # the middle pair below the uniform key slack
+    "gap": (_INNER, False, (5,)),  # a 2^-20 layer without cells: every ray leaves and re-enters
+    "gap-thin": (_INNER[:4] + (2.0 ** -26,), False, (5,)),  # ... across a gap below the uniform key slack
+    "layered-outer": (_INNER[::-1], True, ()),  # the thin layers outside: 2^-20 at the boundary faces
+    "layered-outer-thin": ((2.0 ** -26,) + _INNER[3::-1], True, ()),  # ... 2^-26: a neighbour inside the uniform slack
+}
+# What no stack reaches: a face whose key gets MORE than the uniform slack (walk_common.hpp: entry_key_exponent) needs
+# 256 eps kappa^2 x extent above 2^-24 of the diagonal, a slope of about 1 300 on these faces; the steep view's 159 (the
+# range asked of it is 50 .. 500) leaves every exponent at 0, so the documented swap of steep keys stays untested.
+GRADED_VIEWS = {"generic": (0.37, -0.61), "steep": (0.498, 0.13)}  # steep: the layer planes at |gx| + |gy| = 159
+
+
+def stack_planes(name):
+    """The 13 plane positions of a stack: five drawn thicknesses per side, mirrored, the remaining two layers (the outermost
+    - or, with the thin layers outside, the middle - ones) share the rest of the box."""
+    side, outside, _absent = STACKS[name]
+    rest = (1.0 - 2.0 * sum(side)) / 2.0
+    half = side + (rest,) if outside else (rest,) + side
+    return LO[2] + SIZE * np.concatenate([[0.0], np.cumsum(half + half[::-1])])
+
+
+def layered_box(planes, absent=()):
+    """The Kuhn cut of the 4 x 4 x (len(planes) - 1) lattice with its z-planes at `planes`, less the cells of the layers `absent`."""
+    pts, cells = mg._kuhn_lattice(GRADED_LATERAL, GRADED_LATERAL, len(planes) - 1)
+    step = SIZE / GRADED_LATERAL
+    xyz = np.stack([LO[0] + step * pts[:, 0], LO[1] + step * pts[:, 1], np.asarray(planes)[pts[:, 2]]], axis=1)
+    if len(absent):
+        layer = pts[cells][:, :, 2].min(1)
+        cells = cells[~np.isin(layer, absent)]
+        used = np.unique(cells)
+        new_id = np.full(len(xyz), -1, np.int64)
+        new_id[used] = np.arange(len(used))
+        xyz, cells = xyz[used], new_id[cells].astype(np.int32)
+    return xyz, mg.orient_positive(xyz, cells)
+
+
+def graded_scenes(aligned=False):
+    """name -> a function that builds the scene: every stack under both views of GRADED_VIEWS.  aligned: on BOUNDS itself
+    (names end in "/aligned"): pixel ALIGNED_PIXEL is the image of the lattice vertex (1, 0, 0) and column 32 the pivot
+    column - degenerate rays, tests/test_gpu_degenerate_rays.py's ground, through layers 2^-20 and 2^-26 thick."""
+    out = {}
+    for stack, (_side, _outside, absent) in STACKS.items():
+        for view, angles in GRADED_VIEWS.items():
+            name = f"{stack}/{view}" + ("/aligned" if aligned else "")
+            out[name] = lambda stack=stack, angles=angles, absent=absent, name=name: _scene(
+                name, *layered_box(stack_planes(stack), absent), mg.view_rotations(*angles), n=GRADED_LAYERS, res=GRADED_RES,
+                lattice=SIZE / GRADED_LATERAL, absent=absent, derivatives=True, planes=stack_planes(stack),
+                bounds=BOUNDS if aligned else GRADED_BOUNDS)
+    return out
+
+
+ALIGNED_PIXEL = (24, 32)  # (row, col) of 49 x 65 over BOUNDS: X = 1, Y = 0
+
+
+def distance_to_lattice(s):
+    """[res_y, res_x] x 2: the distance in the image of every pixel centre to the nearest projected vertex and to the nearest
+    projected edge of the scene's cells (view space, x and y)."""
+    P = ar.rotate(s.xyz, s.rots)[:, :2]
+    X, Y, _sx, _sy = ar.pixel_coordinates(s.bounds, *s.res)
+    px = np.stack(np.meshgrid(X, Y), axis=-1).reshape(-1, 2)
+    c = np.asarray(s.cells, np.int64)
+    e = np.unique(np.sort(np.concatenate([c[:, [i, j]] for i in range(4) for j in range(i + 1, 4)]), axis=1), axis=0)
+    to_vertex = np.full(len(px), np.inf)
+    for v in P[np.unique(c)]:
+        to_vertex = np.minimum(to_vertex, np.hypot(px[:, 0] - v[0], px[:, 1] - v[1]))
+    to_edge = np.full(len(px), np.inf)
+    for a, b in zip(P[e[:, 0]], P[e[:, 1]]):
+        d = b - a
+        L2 = float(d @ d)
+        t = np.clip(((px - a) @ d) / L2, 0.0, 1.0) if L2 > 0 else np.zeros(len(px))
+        to_edge = np.minimum(to_edge, np.hypot(px[:, 0] - a[0] - t * d[0], px[:, 1] - a[1] - t * d[1]))
+    return to_vertex.reshape(s.res[::-1]), to_edge.reshape(s.res[::-1])
 
 
 def edge_pixels(s):

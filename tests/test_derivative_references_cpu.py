@@ -80,10 +80,11 @@ def scenes(oracle_port):
     return _Scenes(oracle_port)
 
 
-def _against_80_digits(seed, oracle_port):
-    """One scene: the worst ratios per output, and what the scene covered."""
+def _against_80_digits(seed, oracle_port, mesh=fuzz_scenes.scene):
+    """One scene: the worst ratios per output, and what the scene covered.  mesh: derivative_scene's (tests/
+    test_unstructured_scenes_cpu.py sends three scenes of its family through here)."""
     seen = {"classes": np.zeros(8, np.int64), "series": 0, "closed": 0, "modes": set(), "worst": [], "elements": 0}
-    s = df.derivative_scene(seed)
+    s = df.derivative_scene(seed, mesh)
     assert df.qualify(s, oracle_port) is None
     rx, ry = s.res
     n = len(s.cells)
@@ -244,13 +245,19 @@ def test_geometry_restatements_against_80_digits(seed, oracle_port):
     on N_PIXELS pixels of a scene of the geometry sweep, element by element within their own bars
     1e-9 scale + dz_err sens + 2^-970 - the sens term because the 80-digit chord is the difference of the two depths, not
     the double the restatements carry.  In 3003 and 3007 the pixels are those of the rows about the steepest face."""
-    s = df.geometry_scene(seed)
+    _geometry_against_80_digits(seed, oracle_port, fuzz_scenes.scene, seed in (3003, 3007))
+
+
+def _geometry_against_80_digits(seed, oracle_port, mesh, steep_rows):
+    """The body of the test above for one scene of `mesh` (tests/test_unstructured_scenes_cpu.py sends one of its family
+    through here).  Returns the steepest face among the chosen pixels' segments."""
+    s = df.geometry_scene(seed, mesh)
     assert df.qualify(s, oracle_port) is None
     rx, ry = s.res
     n_pts = len(s.xyz)
     pix, _cell, _zh, _dz, slope = s.segments
     rows = None
-    if seed in (3003, 3007):
+    if steep_rows:
         r = int(pix[slope.argmax()] // rx)
         rows = np.arange(max(r - 2, 0), min(r + 3, ry))
     m = ar.ray_matrices(s.xyz, s.cells, s.alpha, s.q, s.rots, rx, ry, B, s.limit, rows)
@@ -260,7 +267,7 @@ def test_geometry_restatements_against_80_digits(seed, oracle_port):
     rng = np.random.default_rng([seed, 80])
     pixels = np.unique(np.concatenate([steep[:N_PIXELS // 3], rng.choice(covered, min(N_PIXELS, len(covered)), replace=False)]))[:N_PIXELS]
     rays = dm.GeometryRays(ar.rotate(s.xyz, s.rots), s.cells, geo, s.alpha, s.q, s.limit, pixels)
-    if seed in (3003, 3007):
+    if steep_rows:
         assert rays.steepest > 100.0
     M = vr.view_matrix(s.rots)
     e = df.dz_err(s)
@@ -292,3 +299,4 @@ def test_geometry_restatements_against_80_digits(seed, oracle_port):
         hold("vertex adjoint", ref["raw"], dm.vertex_adjoint(rays, w[pixels], n_pts, M), ref["scale_raw"], ref["sens_raw"])
     print(f"seed {seed} ({df.describe(s)}; {rays.n_segments} segments on {len(pixels)} pixels at 80 digits, steepest face "
           f"{rays.steepest:.3g}): worst error / bar " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    return rays.steepest

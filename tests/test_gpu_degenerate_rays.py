@@ -77,7 +77,11 @@ DEFAULT_CUTOFF = 1e-12  # ("transmittance_cutoff" as a context starts)
 @functools.lru_cache(maxsize=None)
 def reference(name):
     """The scene and its slab dict with everything the bars need, made once."""
-    s = SCENES[name]()
+    return reference_of(SCENES[name]())
+
+
+def reference_of(s):
+    """The same of any scene of slab_reference's (tests/test_gpu_graded_layers.py holds its stacks to it)."""
     e = df.dz_err(s)
     m = sr.matrices(s, graze_err=e)
     tau, I, x = ar.forward_of(m, with_scale=True)
@@ -258,8 +262,12 @@ def _per_layer(ref, got, want, x, lateral, kind, tally, bad, r_scale=df.R64):
 
 @pytest.mark.parametrize("name", DERIVATIVE_SCENES)
 def test_derivative_renders_summed_over_the_layers(name):
-    ref = reference(name)
+    derivative_renders_against_the_slab(reference(name))
+
+
+def derivative_renders_against_the_slab(ref):
     s, m = ref.s, ref.m
+    name = s.name
     assert s.derivatives and not ref.grazed.any()  # (no term of these bars stands for a layer that is only grazed)
     n, n_px = s.n_layers, m["n_px"]
     d_alpha, d_q, g, w = _layer_fields(s, 1)
@@ -331,14 +339,14 @@ G_DEPTH_ORDER = ("scene G, pixel (24, 48): the row lists cells 288, 294, 300, 30
 @pytest.mark.parametrize("name", [pytest.param(n, marks=pytest.mark.xfail(strict=True, reason=G_DEPTH_ORDER)) if n == "G" else n
                                   for n in DERIVATIVE_SCENES])
 def test_ray_matrix_holds_the_slab_chords(name):
-    ray_matrix_against_the_slab(name, depth_order=True)
+    ray_matrix_against_the_slab(reference(name), depth_order=True)
 
 
 def test_ray_matrix_of_scene_g_but_for_the_order_of_depths():
     """Everything test_ray_matrix_holds_the_slab_chords asks, of the scene it is an expected failure for, except that z_exit
     never decreases inside a row: there it may, by no more than a rounding of the depths (2^-52 x the largest |z|), and
     only next to a chord that is itself no longer than that."""
-    row_ptr, _col, dz, z = ray_matrix_against_the_slab("G", depth_order=False)
+    row_ptr, _col, dz, z = ray_matrix_against_the_slab(reference("G"), depth_order=False)
     inside = np.diff(rmc.rows_of(row_ptr)) == 0
     down = inside & (np.diff(z) < 0)
     print(f"scene G: z_exit decreases at {int(down.sum())} places, by up to {float(-np.diff(z)[down].min()) if down.any() else 0.0:.3g}")
@@ -346,9 +354,13 @@ def test_ray_matrix_of_scene_g_but_for_the_order_of_depths():
     assert (-np.diff(z)[down] <= bound).all() and (dz[1:][down] <= bound).all()
 
 
-def ray_matrix_against_the_slab(name, depth_order):
-    ref = reference(name)
+def ray_matrix_against_the_slab(ref, depth_order, less_overlap=False, leave_out=()):
+    """leave_out: pixels (row * res_x + col) whose chords are not held to the slab's (everything else of their rows is).
+    less_overlap: where a listed chord starts below the exit listed before it (z_exit - dz < the z_exit before: the walk
+    dropped a negative chord between them and took its exit as this chord's start), that overlap is taken
+    off the chord before it is held to the slab's; returns the overlaps per listed chord as a fifth array."""
     s, m = ref.s, ref.m
+    name = s.name
     n, n_px = s.n_layers, m["n_px"]
     with open_context(s) as ctx:
         img = ctx.render()
@@ -368,8 +380,12 @@ def ray_matrix_against_the_slab(name, depth_order):
     L = m["C"][m["valid"]]
     want = _dense(n_px, n, P, L, m["D"][m["valid"]])
     bar = ref.e * (_dense(n_px, n, P, L, m["F"][m["valid"]]) + _dense(n_px, n, P, L, m["lat"][m["valid"]]))
-    got = _dense(n_px, n, pix, s.layer_of_cell[col], dz)
+    overlap = np.zeros(len(dz))
+    if less_overlap:
+        overlap[1:] = np.where(pix[1:] == pix[:-1], np.maximum(_z[:-1] - (_z[1:] - dz[1:]), 0.0), 0.0)
+    got = _dense(n_px, n, pix, s.layer_of_cell[col], dz - overlap)
     use = np.broadcast_to(s.present, want.shape) & ~(sil & empty)[:, None]
+    use[list(leave_out)] = False
     assert not got[:, ~s.present].any()
     r = np.abs(got - want)[use] / np.maximum(bar[use], 2.0 ** -970)
     print(f"scene {name}: nnz {segments}, {int(use.sum())} (pixel, layer) chords, worst error / (dz_err (F + lat)) {r.max():.3g}; "
@@ -388,6 +404,8 @@ def ray_matrix_against_the_slab(name, depth_order):
             e2 = (a[:, 0] - c[:, 0]) * (y - c[:, 1]) - (a[:, 1] - c[:, 1]) * (x - c[:, 0])
             hit |= ((e0 >= 0) & (e1 >= 0) & (e2 >= 0)) | ((e0 <= 0) & (e1 <= 0) & (e2 <= 0))
         assert hit.all(), f"{int((~hit).sum())} listed cells do not hold their pixel's centre"
+    if less_overlap:
+        return row_ptr, col, dz, _z, overlap
     return row_ptr, col, dz, _z
 
 

@@ -11,6 +11,8 @@
     64 x 2^-52 x scale + dz_err x sens.  Without the chord term it cannot hold: on the sliver chords at the silhouette (a
     chord of 1.4e-3 between faces of F = 3.8) the two differ by 717 and 1262 x 2^-52 x the pixel's own scale at the two views,
     0.05 and 0.04 of dz_err x sens - the chords' rounding, not the recurrences' (measured here; printed by the test).
+    The same with unequal layers (planes=; slab_reference.graded_scenes: thicknesses from half the box down to 2^-26 of it),
+    under both views and in the frame tests/test_gpu_graded_layers.py renders; equal planes given explicitly are the default.
   * At the exact alignment every chord is exactly h.
   * What motivates the reference: the cell restatement differs from the slab value on exactly the pixels whose centre is
     on a projected edge (scene A: 417 of 1089) and on the 21 pixels of the pivot column of scene H.
@@ -171,3 +173,148 @@ def test_conditions_on_the_scenes(name):
         a = s.alpha_l
         assert (a == 0).any() and (a > s.limit).any() and (a == s.limit).any() and (s.q_l == 0).any()
         assert not ((a >= df.EPS) & (a < 1e-6)).any()
+
+
+# ---- unequal layers (slab_matrices' planes=; slab_reference.graded_scenes) ------------------------------------------------
+
+GRADED = sr.graded_scenes()
+
+
+def _per_layer(m, key, n_layers, how=np.add):
+    """[pixel, layer] of a ray_matrices dict whose C holds layer ids: the chords added (or the largest F)."""
+    out = np.zeros((m["n_px"], n_layers))
+    v = m["valid"]
+    how.at(out, (np.broadcast_to(np.arange(m["n_px"])[:, None], v.shape)[v], m["C"][v]), m[key][v])
+    return out
+
+
+def test_equal_planes_are_the_default(scene_a):
+    """planes at lo + h k: the same dict as without them - C, D, F, tau and I to the bit, lat (whose two families with the
+    layer axis are then counted layer by layer, with the slope of a scaled normal) to rounding."""
+    s = scene_a
+    rots = mg.view_rotations(0.37, -0.61)
+    args = (s.lo, s.extent, s.n_layers, s.axis, s.alpha_l, s.q_l, rots, 61, 47, mg.REFERENCE_BOUNDS, s.limit)
+    default = sr.slab_matrices(*args)
+    given = sr.slab_matrices(*args, planes=s.lo[s.axis] + (s.extent / s.n_layers) * np.arange(s.n_layers + 1))
+    for key in ("C", "D", "F", "T", "I", "tau", "valid", "silhouette", "graze"):
+        np.testing.assert_array_equal(given[key], default[key], err_msg=key)
+    np.testing.assert_allclose(given["lat"], default["lat"], rtol=1e-12, atol=0)
+    assert default["lat"].max() > 0
+
+
+@pytest.mark.parametrize("name", sorted(GRADED))
+def test_unequal_layers_agree_with_the_cell_restatement_at_generic_views(name):
+    """The graded stacks under both of their views, each in the frame the GPU test renders (65 x 49, no pixel centre on the
+    image of a lattice edge), slab dict against cell restatement: per pixel and layer the slab chord against the sum of the
+    cell restatement's chords in that layer within dz_err x F, and the forward image per pixel within 64 x 2^-52 x scale +
+    dz_err x sens - the bars of test_generic_views_agree_with_the_cell_restatement.  A layer without cells is alpha = Q = 0
+    in the slab dict and absent from the cells'."""
+    s = GRADED[name]()
+    stack = name
+    n, (rx, ry), B = s.n_layers, s.res, s.bounds
+    assert n == 12 and len(s.planes) == 13 and np.bincount(s.layer_of_cell, minlength=n)[s.present].min() == 96
+    cells = ar.ray_matrices(s.xyz, s.cells, s.alpha, s.q, s.rots, rx, ry, B, s.limit)
+    slab = sr.slab_matrices(s.lo, s.extent, n, s.axis, s.alpha_ref, s.q_ref, s.rots, rx, ry, B, s.limit, lattice=s.lattice,
+                            planes=s.planes)
+    e = 16.0 * ULP * max(1.0, float(np.abs(ar.rotate(s.xyz, s.rots)).max()))
+    assert not slab["silhouette"].any()
+    by_layer = dict(cells, C=np.where(cells["valid"], s.layer_of_cell[np.maximum(cells["C"], 0)], -1))
+    got, want = _per_layer(by_layer, "D", n), _per_layer(slab, "D", n)
+    F = np.maximum(_per_layer(slab, "F", n, np.maximum), 1.0)
+    assert not got[:, ~s.present].any()
+    chord = float((np.abs(got - want) / (e * F))[:, s.present].max())
+    thinnest = float(np.diff(s.planes).min())
+    crossed = int((want[:, np.diff(s.planes) == thinnest] > 0).sum())
+    tau, I, x = ar.forward_of(slab, with_scale=True)
+    tau_c, I_c = ar.forward_of(cells)
+    r = {"tau": _ratio(tau, tau_c, x["scale_tau"], e * x["sens_tau"]), "I": _ratio(I, I_c, x["scale_I"], e * x["sens_I"])}
+    print(f"{stack}: {int(slab['valid'].any(1).sum())} covered pixels, {int(slab['valid'].sum())} (pixel, layer) chords, {crossed} of them "
+          f"in the layers of {thinnest:.3g}; worst error / (dz_err F) {chord:.3g}; worst error / bar tau {r['tau']:.3g}, I {r['I']:.3g}")
+    assert crossed >= (500 if name.endswith("/generic") else 50) and chord <= 1.0 and max(r.values()) <= 1.0
+
+
+@pytest.mark.parametrize("name", sorted(GRADED))
+def test_conditions_on_the_graded_scenes(name):
+    s = GRADED[name]()
+    m = sr.matrices(s, graze_err=df.dz_err(s))
+    cov = m["valid"].any(1)
+    R, _t = sr.view_map(s.rots)
+    F = [sr.slope(R[:, i]) for i in range(3)]
+    thick = np.diff(s.planes)
+    diagonal = float(np.linalg.norm(s.xyz.max(0) - s.xyz.min(0)))
+    print(f"scene {name}: {len(s.cells)} cells, {int(cov.sum())} covered pixels, layers of {thick.min():.3g} .. {thick.max():.3g}, "
+          f"slopes of the axes' planes {F[0]:.3g}, {F[1]:.3g}, {F[2]:.3g}, largest lat {m['lat'].max():.4g}")
+    assert s.res == (65, 49) and cov.sum() >= 1000 and not m["silhouette"].any() and not (m["graze"] > 0).any()
+    assert abs(thick.sum() - s.extent) <= ULP and all(f < sr.EDGE_ON for f in F)
+    assert (50 < F[2] < 500) == name.endswith("/steep")
+    assert thick.min() == (2.0 ** -26 if "thin" in name else 2.0 ** -20) * s.extent
+    assert ("thin" in name) == (thick.min() < 2.0 ** -24 * diagonal) and thick.min() < 2.0 ** -9 * diagonal
+    if name.startswith("layered-outer"):
+        assert thick[0] == thick[-1] == thick.min()
+    if name.startswith("gap"):
+        assert list(np.flatnonzero(~s.present)) == [5] and thick[5] == thick.min()
+    a = s.alpha_l
+    assert (a == 0).any() and (a > s.limit).any() and (a == s.limit).any() and (s.q_l == 0).any()
+
+
+@pytest.mark.parametrize("name", sorted(GRADED))
+def test_no_pixel_centre_of_a_graded_scene_is_on_the_lattice(name):
+    """What GRADED_BOUNDS is moved for: every pixel centre is at least 2^-30 (1e6 roundings of a view-space coordinate) from the
+    image of every vertex and every edge of the scene's cells.  On BOUNDS itself (graded_scenes(aligned=True), the scenes of
+    tests/test_gpu_graded_layers.py's last section) pixel ALIGNED_PIXEL is the image of a lattice vertex to rounding, the only
+    one, and the pixels on a projected edge are in the pivot column."""
+    s = GRADED[name]()
+    to_vertex, to_edge = sr.distance_to_lattice(s)
+    print(f"scene {name}: nearest projected vertex {to_vertex.min():.3g}, nearest projected edge {to_edge.min():.3g}")
+    assert to_vertex.min() > 2.0 ** -30 and to_edge.min() > 2.0 ** -30
+    a = sr.graded_scenes(aligned=True)[name + "/aligned"]()
+    assert np.array_equal(a.xyz, s.xyz) and np.array_equal(a.cells, s.cells) and a.bounds == sr.BOUNDS
+    to_vertex, to_edge = sr.distance_to_lattice(a)
+    assert [tuple(int(v) for v in i) for i in np.argwhere(to_vertex < 2.0 ** -40)] == [sr.ALIGNED_PIXEL]
+    assert set(np.nonzero(to_edge < 2.0 ** -40)[1].tolist()) == {sr.ALIGNED_PIXEL[1]}
+
+
+def test_at_the_vertex_of_the_gap_stack_the_entry_is_right_and_a_sliver_face_is_not():
+    """What tests/test_gpu_graded_layers.py says of gap-thin / steep / aligned, pixel (24, 32), restated: csrc/walk_common.hpp's
+    face_plane (the reference's formula, line.cpp:158-171, about the cell's first point) evaluated in doubles at that pixel for
+    the faces of the cells of layer 6 (2^-26 thick, behind the gap) that hold the lattice vertex, against the exact plane
+    through the same rounded points (rational arithmetic).  Every face of projected area above 1e-6 - the faces in the
+    layer's two planes, slope 159, the boundary faces an entry's depth comes from among them - is within 2^-50 of it: the entry
+    is right.  Among the sliver faces through an edge 2^-26 long (projected area about 1e-9: the determinant m cancels to
+    1e-8 of its terms, the slope keeps 1e-8 of its digits) one is off by more than 1e-12, far beyond dz_err x its slope,
+    and lies BELOW the plane the ray entered through: a cell left through it has a negative chord."""
+    from fractions import Fraction
+    s = sr.graded_scenes(aligned=True)["gap-thin/steep/aligned"]()
+    P = ar.rotate(s.xyz, s.rots)
+    X, Y, _sx, _sy = ar.pixel_coordinates(s.bounds, *s.res)
+    x, y = X[sr.ALIGNED_PIXEL[1]], Y[sr.ALIGNED_PIXEL[0]]
+    e = 16.0 * ULP * max(1.0, float(np.abs(P).max()))
+    vertex = int(np.flatnonzero((s.xyz == [1.0, 0.0, 0.0]).all(1))[0])
+    entered, flat, slivers = [], [], []
+    for cell in np.flatnonzero((s.cells == vertex).any(1) & (s.layer_of_cell == 6)):
+        p = P[s.cells[cell]]
+        for f, (ia, ib, ic) in enumerate(ar._FACES):
+            a, b, c = p[ia], p[ib], p[ic]
+            A = (b[0] - a[0]) * (c[2] - a[2]) - (c[0] - a[0]) * (b[2] - a[2])
+            B = (b[1] - a[1]) * (c[2] - a[2]) - (c[1] - a[1]) * (b[2] - a[2])
+            m = (b[0] - a[0]) * (c[1] - a[1]) - (c[0] - a[0]) * (b[1] - a[1])
+            gy, gx = A / m, -B / m
+            z = (a[2] + gx * (p[0][0] - a[0]) + gy * (p[0][1] - a[1])) + gx * (x - p[0][0]) + gy * (y - p[0][1])
+            fa, fb, fc = ([Fraction(float(v)) for v in q] for q in (a, b, c))
+            Ae = (fb[0] - fa[0]) * (fc[2] - fa[2]) - (fc[0] - fa[0]) * (fb[2] - fa[2])
+            Be = (fb[1] - fa[1]) * (fc[2] - fa[2]) - (fc[1] - fa[1]) * (fb[2] - fa[2])
+            me = (fb[0] - fa[0]) * (fc[1] - fa[1]) - (fc[0] - fa[0]) * (fb[1] - fa[1])
+            exact = float(((Fraction(float(y)) - fa[1]) * Ae - (Fraction(float(x)) - fa[0]) * Be) / me + fa[2])
+            grid_z = s.xyz[s.cells[cell][[ia, ib, ic]], 2]
+            if abs(m) > 1e-6:
+                flat.append(abs(z - exact))
+                if (grid_z == s.planes[6]).all():
+                    entered.append(z)
+            elif vertex in s.cells[cell][[ia, ib, ic]]:
+                slivers.append((z - exact, abs(gx) + abs(gy), abs(m), int(cell), z))
+    worst = min(slivers)
+    print(f"{len(flat)} faces in the layer's planes: within {max(flat):.3g} of the exact plane, the entry at {min(entered):.6g} .. {max(entered):.6g}; "
+          f"{len(slivers)} sliver faces at the vertex, the worst {worst[0]:.3g} off (cell {worst[3]}, slope {worst[1]:.3g}, projected area {worst[2]:.3g})")
+    assert len(entered) >= 4 and max(flat) <= 2.0 ** -50 and max(entered) - min(entered) <= 2.0 ** -50
+    assert worst[0] < -1e-12 and abs(worst[0]) > 100 * e * worst[1] and worst[2] < 1e-8
+    assert worst[4] < min(entered) - 1e-12
