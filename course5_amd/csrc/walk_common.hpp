@@ -380,9 +380,11 @@ __device__ __forceinline__ EntryHead load_entry_head(const EntryHead* p) {
 // once.  Connectivity does not show it, but the entry lists do: such a ray meets a boundary entry INSIDE a stretch it
 // has just walked through cells — beyond the entry it took last (key_taken: that entry's key; -DBL_MAX for a ray that
 // started from a cutting plane), before the depth at which it left the grid (stretch_hi) — an entry it can never take.
-// `skipped` is set for it, with a margin of twice the entry's own key slack either side (keeps out the twin entries of
-// a pixel centre exactly on the common edge of two boundary faces, and the abutting entry of a hanging-node interface,
-// whose depth is that of the exit to rounding); the walk counts such rays, and the host answers with C5_RETRY and
+// `skipped` is set for it: every entry whose key lies beyond the taken entry's by more than the twin margin (in the loop
+// below: keeps out the twin entries of a pixel centre exactly on the common edge of two boundary faces) and more than
+// two of its own slacks before stretch_hi - the abutting entry of a hanging-node interface, whose depth is that of the
+// exit to rounding, and any entry up to two slacks inside the stretch are taken, not flagged: an entry is one or the
+// other; the walk counts such rays, and the host answers with C5_RETRY and
 // renders the grid with bin_sort_resolve from then on (c_api.hip: finish_frame).  Only on the (re-)entry path: nothing
 // is added to a step.
 //
@@ -396,6 +398,9 @@ template <bool kUp>
 __device__ __forceinline__ int next_entry(const WalkParams& P, size_t lp, EntryHead h, double& w_cur, double& w_entry,
                                           double key_taken, double stretch_hi, bool& skipped, double own_lo = -DBL_MAX,
                                           double own_hi = DBL_MAX, bool has_pre = false, double pre_z = 0.0, uint32_t pre_cell = 0u) {
+    // (a ray that has walked a stretch has used an entry - the one it took, or the one before the cutting plane it started
+    // from: with a single entry in the pixel, the rays of a convex grid, there is none to take and none to judge)
+    if (stretch_hi > -DBL_MAX && h.count <= 1) return -1;
     double key_best = DBL_MAX;
     int cell = -1;
     const Entry* e = P.entry_first + lp;
@@ -410,12 +415,34 @@ __device__ __forceinline__ int next_entry(const WalkParams& P, size_t lp, EntryH
         // keys: the lower cell id wins, not the one the raster's atomics happened to list first, so that a frame, a ray
         // matrix's two passes and an exact sum walk the same cells call after call)
         const int id = static_cast<int>(word & kIdMask);
-        if (key > w_cur && (key < key_best || (key == key_best && id < cell)) && we < own_hi && key >= own_lo) {
+        // Beyond the entry taken last (by more than the twin margin) every entry is either taken once or makes the ray
+        // `skipped`, with no depth in between: `reach`, the key pushed one more slack along the walk, is compared with
+        // the end of the stretch either way.  reach > w_cur: an entry no more than two slacks inside the stretch just
+        // walked is still the abutting one (two mated parts overlapping by 1e-7 of their size; its chord starts at its
+        // own depth, as the reference's does) - the nearest KEY wins as before.  reach <= stretch_hi: deeper inside, the
+        // ray is in two cells at once.  (Until the component sweep an entry was taken only with key > w_cur but flagged
+        // only with we + 2 slack < stretch_hi: one lying between one and two slacks inside the stretch was neither, and
+        // everything behind it was lost without a word - tests/test_gpu_component_fuzz.py, profiles/component_fuzz.md.)
+        // A twin is told by its key: on a face that is not steep (k = 0) two evaluations of one plane differ by 2^-6 of
+        // the slack at the most (entry_key_exponent: 64 eps kappa coord <= base), so a quarter of the slack keeps twins
+        // out; faces of one plane with different exponents have keys up to the larger slack apart, so a steep entry
+        // keeps a margin of twice its own.  A part flush with another to within that margin enters like a twin and is not
+        // seen on this ray.
+        // (judged: a stretch has been walked.  A first entry - stretch_hi = -DBL_MAX, a constant at those call sites - is
+        // the nearest key beyond w_cur and nothing else: every ray's way in stays as lean as it was)
+        bool take = key > w_cur;
+        if (stretch_hi > -DBL_MAX && key > key_taken) {
+            const double twin = (word >> kEntrySlackShift) == 0u ? 0.25 * slack : 2.0 * slack;
+            const double reach = key + slack;
+            const bool beyond = key > key_taken + twin;
+            take = take || (beyond && reach > w_cur);
+            if (beyond && reach <= stretch_hi && we > own_lo) skipped = true;
+        }
+        if (take && (key < key_best || (key == key_best && id < cell)) && we < own_hi && key >= own_lo) {
             key_best = key;
             cell = id;
             w_entry = we;
         }
-        if (key > key_taken + 2.0 * slack && we + 2.0 * slack < stretch_hi && we > own_lo) skipped = true;
         if (hop <= 0 || hop > P.pool_capacity) break;
         e = P.entry_pool + (hop - 1);
         hop = e->next;

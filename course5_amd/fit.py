@@ -295,6 +295,13 @@ class RowShards:
     on the first context) - bit for bit those of ONE context over the whole image with set_option("vertex_exact", 1).
     update_points(xyz) sends new points to every context (the outer loop of a shape fit).
 
+    A grid of several components that may interpenetrate (parts that share no face: nothing in the connectivity shows an
+    overlap) must have set_option("algorithm", 1) on EVERY context, before the upload.  Left to itself a context finds
+    the overlap only from its own rays: one whose rows miss it stays on the walk, the whole-image context falls back to
+    sorted lists, and the two take their chords differently - the bars hold either way, the bits do not
+    (tests/test_gpu_component_fuzz.py counts it: the exact scalar sums of 3 row splits in 8 differed, profiles/
+    component_fuzz.md).  With "algorithm" 1 on every part the identity above holds on such grids too (asserted there).
+
     This class is about bits, not speed: it uses the host-pointer forms and numpy between them.  Contexts on one device
     are the tested case; contexts on several devices work by construction and are unmeasured."""
 

@@ -186,6 +186,12 @@ and device forms together.  The batch is s.vg followed by g[1:K]: up to 13 image
   vertex_exact_duality   <g, J v> = <J^T g, v> with render_vertex_tangent of field v_compare[0] at 2^-22 sum |g| |out|.
 The soup rule is the one above.
 
+On the scenes of several components of tests/component_scenes.py (tests/test_gpu_component_fuzz.py) both sweeps read one
+optional attribute, s.shards (shard_identities): the row split of the exact sums once more over CONTEXTS OF THEIR OWN, one
+per part - asserted with "algorithm" 1 on each, counted with the parts left to find an overlap from their own rays; and the
+second-order sweep's comparison context, which renders nothing but the layout's parts, is then opened on "algorithm" 1.  No
+other scene carries the attribute.
+
 Both sweeps take their restatements over the rows of the layout that hold a covered pixel and over the covered pixels alone
 (covered_rows, covered_only; second_order_restatements and vertex_restatements run without a GPU): a pixel without a segment
 adds nothing to any cell or point.  The GPU calls run over every row and pixel.  profiles/second_order_fuzz.md has the runs.
@@ -700,13 +706,15 @@ class _GeoDeviceCalls(_DeviceCalls):
         return out.cpu().numpy()
 
 
-def _open(s, xyz, walk_option=None, cell_order=None, vertex_merge=None):
+def _open(s, xyz, walk_option=None, cell_order=None, vertex_merge=None, algorithm=None):
     """A context of the scene's own, as check_scene opens it, with the geometry sweep's options (cell_order, vertex_merge:
-    in place of the scene's)."""
+    in place of the scene's).  algorithm: set where the scene is no soup (a shard's context: shard_identities)."""
     from course5_amd import capi
     ctx = capi.Context(0)
     if s.soup:
         ctx.set_option("algorithm", 1)
+    elif algorithm is not None:
+        ctx.set_option("algorithm", algorithm)
     ctx.set_option("cell_order", s.cell_order if cell_order is None else cell_order)  # (read by the upload)
     ctx.set_option("vertex_merge", s.vertex_merge if vertex_merge is None else vertex_merge)
     if walk_option:
@@ -1461,13 +1469,16 @@ def second_order_restatements(s, skip=None):
     return out
 
 
-def _open_scalar(s, options=(), exact=False):
+def _open_scalar(s, options=(), exact=False, algorithm=None):
     """A context of the scene's own as check_scene opens it, `options` set before the upload; the alpha limit is left to
-    the caller.  exact: on "adjoint_exact" 1 and "exact_sums" 1."""
+    the caller.  exact: on "adjoint_exact" 1 and "exact_sums" 1.  algorithm: set where the scene is no soup (a shard's
+    context: shard_identities)."""
     from course5_amd import capi
     ctx = capi.Context(0)
     if s.soup:
         ctx.set_option("algorithm", 1)
+    elif algorithm is not None:
+        ctx.set_option("algorithm", algorithm)
     for k, v in options:
         ctx.set_option(k, v)
     ctx.upload_grid(s.xyz, s.cells, s.alpha, s.q)
@@ -1504,6 +1515,26 @@ def _exact_kinds(s, image_rows=None):
     w = None if s.w is None else np.ascontiguousarray(s.w[rows])
     g = np.ascontiguousarray(s.g[0][rows])
     return (("adjoint", capi.C5_EXACT_ADJOINT, g, {}), ("diagonal", capi.C5_EXACT_GN_DIAGONAL, w, {}), ("hvp", capi.C5_EXACT_HVP, g, dirs))
+
+
+def shard_identities(s, bad, what, run):
+    """The optional scene attribute s.shards (absent on every scene but those of tests/test_gpu_component_fuzz.py: grids of
+    several components, where a context that renders a part of the rows cannot see an overlap that only other rows' rays
+    cross, stays on the walk and takes its chords otherwise than the whole-image context, which fell back to sorted
+    lists): a dict {"counts": {}}.  run(algorithm) -> {name: whether a row split over CONTEXTS OF THEIR OWN, one per part,
+    opened with that "algorithm", gives the whole-image context's bits}.  With "algorithm" 1 that is asserted - what a
+    caller who shards such a grid must set (fit.RowShards' docstring); with the parts left on their own judgement (None)
+    it is counted into s.shards["counts"][what + name] = [comparisons, differing] and printed by the caller."""
+    shards = getattr(s, "shards", None)
+    if shards is None or s.soup:
+        return
+    for name, same in run(1).items():
+        if not same:
+            bad.append(f"{what}{name}: a row split over contexts of their own on \"algorithm\" 1 does not give the whole-image context's bits")
+    for name, same in run(None).items():
+        c = shards["counts"].setdefault(what + name, [0, 0])
+        c[0] += 1
+        c[1] += 0 if same else 1
 
 
 def _second_split_identity(s, skip, tally, bad):
@@ -1557,6 +1588,29 @@ def _second_split_identity(s, skip, tally, bad):
                 if (owns or (name in live and live[name][rows].any())) and not (w[name][0].any() or w[name][1].any()):
                     bad.append(f"exact {name}: a part of the second split ({s.second_split}) with covered rows has all-zero words")
 
+        def own_contexts(algorithm):
+            from contextlib import ExitStack
+            with ExitStack() as stack:
+                each = []
+                for place, rows in parts:
+                    c = stack.enter_context(_open_scalar(s, exact=True, algorithm=algorithm))
+                    c.set_alpha_limit(s.limit)
+                    if s.solid:
+                        c.set_solid(0, _solid_of(s))
+                    place(c)
+                    each.append((c, rows))
+                same = {}
+                for i, (name, what, _image, _dirs) in enumerate(_exact_kinds(s)):
+                    kinds = [_exact_kinds(s, rows)[i] for _c, rows in each]
+                    exps = sharding.combine_exact([c.render_exact_bounds(what, image=k[2], **k[3]) + (None, None)
+                                                   for (c, _rows), k in zip(each, kinds)])[:2]
+                    total = sharding.combine_exact([exps + c.render_exact_sums(what, *exps, image=k[2], **k[3])
+                                                    for (c, _rows), k in zip(each, kinds)])
+                    same[name] = _same64(finish(total[:2], total[2:]), single[name])
+                return same
+
+        shard_identities(s, bad, "exact ", own_contexts)
+
 
 def check_second_order(s, worst, tally=None):
     """The Hessian-vector render and the exact-sum modes on one used scene (second_order_scene, qualify first; module
@@ -1576,7 +1630,9 @@ def check_second_order(s, worst, tally=None):
                        f"{s.n_segments} on {s.n_covered}")
         if s.late_limit:
             ctx.set_alpha_limit(s.limit)  # (after a frame: the cell records carry the clamp and must be rebuilt)
-        cmp_ctx = stack.enter_context(_open_scalar(s, s.compare_options, exact=True))
+        # (the comparison context renders nothing but the layout's parts: on a scene with s.shards it is a shard's context)
+        sharded = getattr(s, "shards", None) is not None and s.layout != "whole"
+        cmp_ctx = stack.enter_context(_open_scalar(s, s.compare_options, exact=True, algorithm=1 if sharded else None))
         cmp_ctx.set_alpha_limit(s.limit)
         skip = None
         if s.solid:
@@ -1789,6 +1845,22 @@ def check_vertex_exact(s, worst, tally=None):
         _, total = sharding.combine_vertex_exact([(exps, w) for w in words])
         tally.hold(bad, s, "staged path", np.array_equal(_bits64(ctx.vertex_exact_finish(exps, total)), _bits64(singles[0])),
                    f"vertex_exact: bounds, sums and finish over {len(staged)} parts do not give the single whole-image call's bits")
+
+        def own_contexts(algorithm):
+            with ExitStack() as shard_stack:
+                each = []
+                for place, rows in staged:
+                    c = shard_stack.enter_context(_open(s, s.xyz, s.walk_option, algorithm=algorithm))
+                    c.set_alpha_limit(s.limit)
+                    if s.solid:
+                        c.set_solid(0, _solid_of(s))
+                    place(c)
+                    each.append((c, np.ascontiguousarray(batch[0][rows])))
+                exps, _ = sharding.combine_vertex_exact([(c.render_vertex_exact_bounds(g), None) for c, g in each])
+                _, total = sharding.combine_vertex_exact([(exps, c.render_vertex_exact_sums(g, exps)) for c, g in each])
+                return {"staged path": np.array_equal(_bits64(each[0][0].vertex_exact_finish(exps, total)), _bits64(singles[0]))}
+
+        shard_identities(s, bad, "vertex_exact ", own_contexts)
         if s.layout != "cyclic":
             ctx.set_row_range(0, ry)
         ctx.set_option("vertex_exact", 0)
