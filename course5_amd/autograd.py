@@ -73,6 +73,11 @@ Hessian of a least-squares fit from it.
 
 ray_matrix(ctx) hands out the operator itself: the frame's per-pixel (cell, chord) lists as a torch.sparse_csr_tensor on the
 context's GPU (c5_ray_matrix_rows_device, c5_ray_matrix_fill_device), for solvers that want A and not only A v and A^T g.
+
+prior(ctx, alpha, q, prior) is the regulariser such a fit needs: the smoothness prior R(alpha) + R(q) over the grid's
+interior faces (capi.Prior; include/course5_hip.h: c5_prior_*), a float64 scalar differentiable TWICE in alpha and q - the
+forward is one c5_prior_gradient_device, which leaves the gradient too, and the second derivative is one
+c5_prior_product_device.  It needs the grid alone: no image, no view, and not the context's own scalars.
 """
 from __future__ import annotations
 
@@ -775,4 +780,155 @@ def ray_jacobian(ctx: capi.Context, alpha=None, q=None) -> tuple:
         return tuple(torch.sparse_csr_tensor(crow, col, v, size=size, check_invariants=False) for v in (dz, da, dq))
 
 
-__all__ = ["render", "render_view", "render_mesh", "gn_product", "gn_diagonal", "vertex_gn_product", "hvp", "ray_matrix", "ray_jacobian"]
+# ---- the smoothness prior ----------------------------------------------------------------------------------------------
+# R(alpha) + R(q) of capi.Prior as a differentiable function of the two fields: the value and the gradient come from ONE
+# c5_prior_gradient_device, the second derivative (reverse over reverse, jvp of grad) from ONE c5_prior_product_device.
+# The calls are enqueued on torch's current stream.  On a stream of torch's own that orders them with what torch does
+# there, before and after, and nothing is waited for.  Torch's DEFAULT stream is the null stream, which the library takes
+# for "its own stream" - one the null stream does not synchronise with: there the call is waited for before torch reads
+# its outputs (or hands its inputs back to the allocator), as every other operator of this module does (_launch).
+
+def _enqueue(ctx: capi.Context, device: torch.device, enqueue) -> None:
+    """enqueue() - library calls that take no per-view setup - on torch's current stream, after what torch has queued
+    there; waited for where that is the null stream, left to the stream's order elsewhere."""
+    _use_torch_stream(ctx, device)
+    if ctx.stream_ptr == 0:
+        _run(ctx, enqueue)
+    else:
+        enqueue()
+
+
+def _no_prior_vmap():
+    raise RuntimeError("course5_amd.autograd.prior: vmap (a batch of fields, tangents or cotangents) is not supported; "
+                       "call it once per field")
+
+
+def _prior_fields(ctx: capi.Context, device: torch.device, *ts) -> tuple:
+    out = tuple(None if t is None else _plain(t).detach().to(device=device, dtype=torch.float64).contiguous() for t in ts)
+    if any(t is not None and tuple(t.shape) != (ctx.n_cells,) for t in out):
+        raise ValueError(f"alpha and q must hold one value per cell ({ctx.n_cells})")
+    return out
+
+
+def _no_prior_third(*_args):
+    raise RuntimeError("course5_amd.autograd.prior: derivatives beyond the second are not supported (the prior's Hessian "
+                       "product has no derivative of its own)")
+
+
+class _PriorProduct(_Operator):
+    """Hess R(x) v: one c5_prior_product_device at the point `fr` kept.  It has no derivative of its own."""
+    what = "smoothness prior's Hessian product"
+    backward = staticmethod(_no_prior_third)
+    jvp = staticmethod(_no_prior_third)
+
+    @staticmethod
+    def forward(fr, alpha, q, v_alpha, v_q):
+        ctx: capi.Context = fr.c5
+        with _on_gpu(ctx, unwrapped=True) as device:
+            va, vq = (torch.zeros(ctx.n_cells, dtype=torch.float64, device=device) if v is None else v
+                      for v in _prior_fields(ctx, device, v_alpha, v_q))
+            ha, hq = _cell_pair(ctx, device)
+            _enqueue(ctx, device, lambda: ctx.prior_product_device(fr.prior, fr.point[0], fr.point[1], va, vq, ha, hq))
+        return ha, hq
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        _no_prior_vmap()
+
+
+class _PriorGradient(torch.autograd.Function):
+    """grad R at the point of `fr`, as the forward's call left it (no call of its own); its derivative is _PriorProduct."""
+
+    @staticmethod
+    def forward(fr, alpha, q):
+        return tuple(g.clone() for g in fr.grads)
+
+    @staticmethod
+    def setup_context(fctx, inputs, output):
+        fctx.fr, fctx.primals = inputs[0], inputs[1:]
+        fctx.meta = inputs[0].meta
+
+    @staticmethod
+    def backward(fctx, g_alpha, g_q):
+        alpha, q = fctx.primals
+        ha, hq = _PriorProduct.apply(fctx.fr, alpha, q, g_alpha, g_q)
+        return (None, *_scalar_grads(fctx, ha, hq, 1, 2))
+
+    @staticmethod
+    def jvp(fctx, _fr_tangent, alpha_t, q_t):
+        alpha, q = fctx.primals
+        return _PriorProduct.apply(fctx.fr, alpha, q, alpha_t, q_t)
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        _no_prior_vmap()
+
+
+class _PriorValue(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, prior: capi.Prior):
+        with _on_gpu(ctx, unwrapped=True) as device:
+            a, b = _prior_fields(ctx, device, alpha, q)
+            value = torch.empty(2, dtype=torch.float64, device=device)
+            ga, gq = _cell_pair(ctx, device)
+            _enqueue(ctx, device, lambda: ctx.prior_gradient_device(prior, a, b, value, ga, gq))
+            ctx.prior_last = ((a, b), (ga, gq))  # (setup_context takes them from here)
+            return value[0] + value[1]
+
+    @staticmethod
+    def setup_context(fctx, inputs, output):
+        ctx, alpha, q, prior = inputs
+        fctx.c5, fctx.prior = ctx, prior
+        fctx.point, fctx.grads = ctx.prior_last  # (forward has just set it)
+        fctx.meta = ((alpha.dtype, alpha.device), (q.dtype, q.device))
+        fctx.primals = (alpha, q)
+
+    @staticmethod
+    def backward(fctx, g_value: torch.Tensor):
+        alpha, q = fctx.primals
+        ga, gq = _PriorGradient.apply(fctx, alpha, q)
+        ga, gq = _scalar_grads(fctx, ga, gq, 1, 2)
+        return (None, None if ga is None else g_value.to(ga.device) * ga, None if gq is None else g_value.to(gq.device) * gq, None)
+
+    @staticmethod
+    def jvp(fctx, _ctx_tangent, alpha_t, q_t, _prior_tangent):
+        # The value's tangent is grad R . t, with grad R through _PriorGradient: no call of its own, and a derivative of
+        # the tangent (torch.func.grad of a jvp, forward_ad under create_graph) finds the Hessian product there.  Forward
+        # over forward does not: torch.func drops the outer tangent of what a jvp rule computes from its saved inputs.
+        from torch._C._functorch import TransformType
+        from torch._functorch.pyfunctorch import retrieve_all_functorch_interpreters
+        levels = [i.key() for i in retrieve_all_functorch_interpreters()]
+        if sum(k == TransformType.Jvp for k in levels) > 1:
+            raise RuntimeError("course5_amd.autograd.prior: torch.func.jvp of a jvp (forward over forward) is not supported; "
+                               "take the second derivative as jvp of grad, grad of jvp, or by double backward")
+        alpha, q = fctx.primals
+        if _differentiating_levels() > 1 or alpha.requires_grad or q.requires_grad:
+            ga, gq = _PriorGradient.apply(fctx, alpha, q)
+        else:  # (nothing can differentiate the tangent: the gradient as the forward left it)
+            ga, gq = fctx.grads
+        out = None
+        for g, t in ((ga, alpha_t), (gq, q_t)):
+            if t is not None:
+                term = (g * t.to(device=g.device, dtype=g.dtype)).sum()
+                out = term if out is None else out + term
+        return out
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        _no_prior_vmap()
+
+
+def prior(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, prior: capi.Prior) -> torch.Tensor:
+    """R(alpha) + R(q): the smoothness prior `prior` (capi.Prior) of the grid of `ctx` at the fields alpha and q ([n_cells],
+    the order of upload_grid), a float64 scalar on the context's GPU.  Needs a grid and nothing else; the context's own
+    scalars play no part.  Differentiable in alpha and q: the forward is one c5_prior_gradient_device on torch's current
+    stream, which leaves the gradient too (torch.autograd.grad and torch.func.grad make no further call); the second
+    derivative - reverse over reverse (create_graph=True), torch.func.jvp(torch.func.grad(f), ...), torch.func.grad of a
+    jvp - is one c5_prior_product_device.  Derivatives beyond the second, jvp of a jvp and vmap raise.  Bit-reproducible.
+    Under a torch.cuda.Stream of torch's own the calls are only enqueued, in that stream's order; on torch's default (null)
+    stream, which the library's stream is not ordered against, each call is waited for."""
+    return _PriorValue.apply(ctx, alpha, q, prior)
+
+
+__all__ = ["render", "render_view", "render_mesh", "gn_product", "gn_diagonal", "vertex_gn_product", "hvp", "ray_matrix", "ray_jacobian",
+           "prior"]

@@ -32,6 +32,7 @@ LIB_SOURCES = [
     ("scalar_derivative_kernels.hip", ["-munsafe-fp-atomics"]),
     ("geometry_derivative_kernels.hip", ["-munsafe-fp-atomics"]),
     ("ray_matrix_kernels.hip", ["-munsafe-fp-atomics"]),
+    ("prior_kernels.hip", ["-ffp-contract=off"]),   # every product rounds: a numpy restatement gives the same bits
     # the C ABI, host code only (context.hpp)
     ("context.hip", []),
     ("grid.hip", []),
@@ -40,6 +41,7 @@ LIB_SOURCES = [
     ("scalar_derivatives.hip", []),
     ("geometry_derivatives.hip", []),
     ("ray_matrix.hip", []),
+    ("prior.hip", []),
     ("host_ring.hip", []),
     ("adjacency.cpp", ["-x", "c++", "-fopenmp"]),
 ]

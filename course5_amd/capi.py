@@ -20,6 +20,9 @@ LIB_PATH = os.environ.get("C5_LIB", os.path.join(PKG, "libcourse5_hip.so"))  # C
 C5_OK, C5_ERR_INVALID, C5_ERR_STATE, C5_ERR_HIP, C5_ERR_MESH, C5_ERR_NO_DEVICE, C5_ERR_WALK, C5_RETRY = range(8)
 # the kinds of exact sums of c5_render_exact_bounds / c5_render_exact_sums
 C5_EXACT_ADJOINT, C5_EXACT_GN_DIAGONAL, C5_EXACT_HVP = range(3)
+# the smoothness prior's penalties and weightings (c5_prior)
+C5_PRIOR_QUADRATIC, C5_PRIOR_PSEUDO_HUBER = range(2)
+C5_PRIOR_UNIT, C5_PRIOR_TPFA = range(2)
 
 
 class Rotation(C.Structure):
@@ -38,6 +41,16 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class Prior(C.Structure):
+    """c5_prior: the smoothness prior's penalty, weighting, and per field its lambda (0: the field is left out) and the
+    pseudo-Huber delta."""
+    _fields_ = [("penalty", C.c_int32), ("weighting", C.c_int32), ("lambda_alpha", C.c_double), ("lambda_q", C.c_double),
+                ("delta_alpha", C.c_double), ("delta_q", C.c_double)]
+
+    def __init__(self, penalty=C5_PRIOR_QUADRATIC, weighting=C5_PRIOR_TPFA, lambda_alpha=0.0, lambda_q=0.0, delta_alpha=1.0, delta_q=1.0):
+        super().__init__(int(penalty), int(weighting), float(lambda_alpha), float(lambda_q), float(delta_alpha), float(delta_q))
+
+
 class C5Error(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"[c5 status {code}] {message}")
@@ -47,6 +60,7 @@ class C5Error(RuntimeError):
 
 _vp, _dp_t, _fp_t, _ip_t, _lp_t = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
 _rp_t = C.POINTER(Rotation)
+_pp_t = C.POINTER(Prior)
 
 # every symbol include/course5_hip.h declares: its argument types, or (argument types, result type) where that is not int
 SIGNATURES = {
@@ -130,6 +144,14 @@ SIGNATURES = {
     "c5_render_exact_sums_device": [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "c5_exact_sums_finish": [_ip_t, _lp_t, C.c_int64, C.c_int, C.c_int, _dp_t],
     "c5_exact_quantise": [_dp_t, C.c_int64, C.c_int32, C.c_int, C.c_int, _lp_t],
+    "c5_prior_weights": [_vp, C.c_int, _dp_t, _lp_t, _lp_t],
+    "c5_prior_weights_device": [_vp, C.c_int, _vp, _lp_t, _lp_t],
+    "c5_prior_gradient": [_vp, _pp_t, _dp_t, _dp_t, _dp_t, _dp_t, _dp_t],
+    "c5_prior_gradient_device": [_vp, _pp_t, _vp, _vp, _vp, _vp, _vp],
+    "c5_prior_product": [_vp, _pp_t, _dp_t, _dp_t, _dp_t, _dp_t, _dp_t, _dp_t],
+    "c5_prior_product_device": [_vp, _pp_t, _vp, _vp, _vp, _vp, _vp, _vp],
+    "c5_prior_diagonal": [_vp, _pp_t, _dp_t, _dp_t, _dp_t, _dp_t],
+    "c5_prior_diagonal_device": [_vp, _pp_t, _vp, _vp, _vp, _vp],
 }
 EXPORTS = list(SIGNATURES)
 
@@ -943,6 +965,82 @@ class Context:
         with the next synchronize() (C5_RETRY: run it again)."""
         self._check(self.lib.c5_render_gn_diagonal_device(self.handle, self._image_dev(weight), self._cells_dev(diag_alpha),
                                                           self._cells_dev(diag_q)))
+
+    # -- smoothness prior -----------------------------------------------------------------------------
+    def _cells_host(self, a, name: str):
+        """A per-cell float64 array of the caller's, or None."""
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != (self.n_cells,):
+            raise ValueError(f"{name} must be [n_cells] = [{self.n_cells}], not {list(a.shape)}")
+        return a
+
+    def _prior_out(self, prior):
+        """The two output arrays of an operator of `prior` (None for a field whose lambda is 0)."""
+        return (np.zeros(self.n_cells) if prior.lambda_alpha != 0.0 else None, np.zeros(self.n_cells) if prior.lambda_q != 0.0 else None)
+
+    def prior_weights(self, weighting: int = C5_PRIOR_TPFA) -> tuple:
+        """(w, n_interior_faces, n_degenerate): the prior's face weights, float64 [n_cells, 4] in the order of upload_grid
+        and its face numbering (0 on a face without a neighbour), the number of interior faces, and of those whose TPFA
+        weight was not finite and positive and is stored as 0.  Needs a grid and nothing else."""
+        w = np.zeros((self.n_cells, 4))
+        n_int, n_deg = C.c_int64(), C.c_int64()
+        self._check(self.lib.c5_prior_weights(self.handle, int(weighting), _dp(w), C.byref(n_int), C.byref(n_deg)))
+        return w, n_int.value, n_deg.value
+
+    def prior_weights_device(self, weighting: int, w) -> tuple:
+        """The weights into device memory (a torch tensor float64 [n_cells, 4] on this context's GPU, or a raw device
+        pointer, or None) on the context's stream: (n_interior_faces, n_degenerate)."""
+        import torch
+        n_int, n_deg = C.c_int64(), C.c_int64()
+        self._check(self.lib.c5_prior_weights_device(self.handle, int(weighting), _device_ptr(w, torch.float64, (self.n_cells, 4)),
+                                                     C.byref(n_int), C.byref(n_deg)))
+        return n_int.value, n_deg.value
+
+    def prior_gradient(self, prior: Prior, alpha=None, q=None) -> tuple:
+        """(value, grad_alpha, grad_q) of the smoothness prior at the fields alpha / q (float64 [n_cells] in the order of
+        upload_grid; the context's own scalars play no part): value = float64 [2], (R(alpha), R(q)); a field whose lambda
+        is 0 may be None and comes back as None.  Synchronous; bit-reproducible."""
+        a, qq = self._cells_host(alpha, "alpha"), self._cells_host(q, "q")
+        value = np.zeros(2)
+        ga, gq = self._prior_out(prior)
+        self._check(self.lib.c5_prior_gradient(self.handle, C.byref(prior), _dp(a), _dp(qq), _dp(value), _dp(ga), _dp(gq)))
+        return value, ga, gq
+
+    def prior_gradient_device(self, prior: Prior, alpha, q, value, grad_alpha, grad_q):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (float64 [n_cells]; value
+        float64 [2] or None) or raw device pointers."""
+        import torch
+        self._check(self.lib.c5_prior_gradient_device(self.handle, C.byref(prior), self._cells_dev(alpha), self._cells_dev(q),
+                                                      _device_ptr(value, torch.float64, (2,)), self._cells_dev(grad_alpha),
+                                                      self._cells_dev(grad_q)))
+
+    def prior_product(self, prior: Prior, alpha=None, q=None, v_alpha=None, v_q=None) -> tuple:
+        """(h_alpha, h_q) = Hess R(alpha, q) (v_alpha, v_q); the point may be None where the penalty is quadratic."""
+        a, qq = self._cells_host(alpha, "alpha"), self._cells_host(q, "q")
+        va, vq = self._cells_host(v_alpha, "v_alpha"), self._cells_host(v_q, "v_q")
+        ha, hq = self._prior_out(prior)
+        self._check(self.lib.c5_prior_product(self.handle, C.byref(prior), _dp(a), _dp(qq), _dp(va), _dp(vq), _dp(ha), _dp(hq)))
+        return ha, hq
+
+    def prior_product_device(self, prior: Prior, alpha, q, v_alpha, v_q, h_alpha, h_q):
+        """Asynchronous form on the context's stream (tensors or raw device pointers as prior_gradient_device)."""
+        self._check(self.lib.c5_prior_product_device(self.handle, C.byref(prior), self._cells_dev(alpha), self._cells_dev(q),
+                                                     self._cells_dev(v_alpha), self._cells_dev(v_q), self._cells_dev(h_alpha),
+                                                     self._cells_dev(h_q)))
+
+    def prior_diagonal(self, prior: Prior, alpha=None, q=None) -> tuple:
+        """(diag_alpha, diag_q): the diagonal of Hess R(alpha, q); the point may be None where the penalty is quadratic."""
+        a, qq = self._cells_host(alpha, "alpha"), self._cells_host(q, "q")
+        da, dq = self._prior_out(prior)
+        self._check(self.lib.c5_prior_diagonal(self.handle, C.byref(prior), _dp(a), _dp(qq), _dp(da), _dp(dq)))
+        return da, dq
+
+    def prior_diagonal_device(self, prior: Prior, alpha, q, diag_alpha, diag_q):
+        """Asynchronous form on the context's stream (tensors or raw device pointers as prior_gradient_device)."""
+        self._check(self.lib.c5_prior_diagonal_device(self.handle, C.byref(prior), self._cells_dev(alpha), self._cells_dev(q),
+                                                      self._cells_dev(diag_alpha), self._cells_dev(diag_q)))
 
     # -- Hessian-vector render ------------------------------------------------------------------------
     def render_hvp(self, d_alpha=None, d_q=None, grad_out=None, fit=("alpha", "q")) -> tuple:

@@ -208,6 +208,21 @@ struct DerivativeState {
     }
 };
 
+// The smoothness prior (c5_prior_*, prior.hip): nothing of it is allocated before the first call.
+struct PriorState {
+    DeviceBuffer w[2];  // [n_cells][4] fp64 face weights, device order, per weighting (C5_PRIOR_UNIT, C5_PRIOR_TPFA)
+    uint64_t w_grid[2] = {~uint64_t{0}, ~uint64_t{0}};    // ... for the grid of this upload (c5_context::grid_serial)
+    uint64_t w_points[2] = {~uint64_t{0}, ~uint64_t{0}};  // ... and these points (c5_context::points_serial; TPFA alone looks)
+    int64_t n_interior[2] = {0, 0}, n_degenerate[2] = {0, 0};
+    DeviceBuffer counts;    // two words the weights' build counts into
+    DeviceBuffer partials;  // [2][blocks] fp64: the value's per-block sums
+    DeviceBuffer io;        // the host-pointer forms' staging
+    void release() {
+        DeviceBuffer* const owned[] = {&w[0], &w[1], &counts, &partials, &io};
+        for (DeviceBuffer* b : owned) b->release();
+    }
+};
+
 }  // namespace c5api
 
 struct c5_context {
@@ -329,6 +344,8 @@ struct c5_context {
     c5api::DerivativeState deriv;      // the derivative renders' buffers, options and status (derivative_host.hpp)
     c5api::DeviceBuffer adj_perm;      // cell_perm on the device, for the grid of upload adj_perm_serial (grid.hip: ensure_device_perm)
     uint64_t grid_serial = 0, adj_perm_serial = ~uint64_t{0};
+    uint64_t points_serial = 0;        // bumped by c5_update_points: what is derived from the coordinates on demand is stale
+    c5api::PriorState prior;           // the smoothness prior's weights and scratch (prior.hip)
     // c5_update_points: the cells as the device has them (welded, in its order) and, where c5_upload_grid welded points,
     // every point's representative (empty: none welded) - what measure_grid and upload_block_spheres are run again with
     std::vector<int32_t> host_cell_vert, point_rep;

@@ -308,6 +308,7 @@ int c5_update_points(c5_context* ctx, const double* xyz, int64_t n_pts) {
     for (int64_t i = 0; i < 3 * n_pts; ++i)
         if (!std::isfinite(xyz[i])) return fail(ctx, C5_ERR_INVALID, "point %lld has a non-finite coordinate", static_cast<long long>(i / 3));
     ++ctx->setup_epoch;  // whatever was built per view is stale ("view_cache")
+    ++ctx->points_serial;  // (c5_prior_*: the TPFA weights are the old points')
     int rc = bind_device(ctx);
     if (rc) return rc;
     rc = drain(ctx);  // (frames set up on the other streams read the points too)

@@ -24,6 +24,10 @@ newton_product and newton_step are the same with the EXACT Hessian of 1/2 sum w 
 second term from autograd.hvp (c5_render_hvp) on grad_img = W r.  The frame is exponential in alpha, so a fit of alpha is
 not a linear least-squares problem and the two differ by the residual-weighted curvature; in q alone they coincide.  A
 context's own operators then also need hvp(v_alpha, v_q, grad_img) -> (h_alpha, h_q).
+
+Where rays say nothing - a cell no ray crosses, the null space along every ray of one view - the system above is singular:
+SmoothnessPrior(ctx, lambda_q=...) is the library's face-neighbour penalty (include/course5_hip.h: c5_prior_*), and
+gn_step(..., prior=P) / newton_step(WithPrior(ctx, P), ...) add its gradient, Hessian and diagonal to the system.
 """
 from __future__ import annotations
 
@@ -355,11 +359,100 @@ def _operators(ctx, alpha, q, weight):
     return ctx.gn_operators(alpha, q, weight) if hasattr(ctx, "gn_operators") else _LibraryOperators(ctx, alpha, q, weight)
 
 
-def _cg_step(ctx, alpha, q, residual, weight, fit, damping, iters, precondition, exact):
-    """gn_step (exact False: H = J^T W J) and newton_step (exact True: H the exact Hessian of 1/2 sum w r^2)."""
+class SmoothnessPrior:
+    """The smoothness prior of the grid of `ctx` (a capi.Context; of a RowShards any one part's: they carry the same grid) as
+    gn_step and newton_step take it (prior=):
+
+        P = course5_amd.fit.SmoothnessPrior(ctx, lambda_q=1e-3)
+        delta, models = course5_amd.fit.gn_step(ctx, alpha, q, residual, fit=("q",), prior=P)
+
+    lambda_alpha / lambda_q >= 0 weigh the two fields (0: the field has no prior); penalty "quadratic" or "pseudo_huber"
+    (then with delta_alpha / delta_q > 0 for the fields that have a lambda); weighting "tpfa" (face area over the
+    centroids' distance) or "unit".  The definitions are include/course5_hip.h's (c5_prior).  The three operators take
+    torch tensors [n_cells] in the order of upload_grid, any dtype and device, and return float64 tensors on the context's
+    GPU (zeros for a field whose lambda is 0), one library call each on torch's current stream: enqueued in that stream's
+    order with no wait under a torch.cuda.Stream of torch's own, waited for on torch's default (null) stream, which the
+    library's stream is not ordered against (autograd._enqueue)."""
+
+    PENALTIES = {"quadratic": capi.C5_PRIOR_QUADRATIC, "pseudo_huber": capi.C5_PRIOR_PSEUDO_HUBER}
+    WEIGHTINGS = {"unit": capi.C5_PRIOR_UNIT, "tpfa": capi.C5_PRIOR_TPFA}
+
+    def __init__(self, ctx, lambda_alpha: float = 0.0, lambda_q: float = 0.0, penalty: str = "quadratic", weighting: str = "tpfa",
+                 delta_alpha=None, delta_q=None):
+        if penalty not in self.PENALTIES:
+            raise ValueError(f"penalty must be one of {sorted(self.PENALTIES)}, not {penalty!r}")
+        if weighting not in self.WEIGHTINGS:
+            raise ValueError(f"weighting must be one of {sorted(self.WEIGHTINGS)}, not {weighting!r}")
+        for name, lam, delta in (("alpha", lambda_alpha, delta_alpha), ("q", lambda_q, delta_q)):
+            if not (lam >= 0.0 and np.isfinite(lam)):
+                raise ValueError(f"lambda_{name} must be finite and >= 0, not {lam!r}")
+            if penalty == "pseudo_huber" and lam > 0.0 and (delta is None or not (delta > 0.0 and np.isfinite(delta))):
+                raise ValueError(f"the pseudo-Huber penalty needs delta_{name} > 0, not {delta!r}")
+        self.ctx = ctx
+        # (a delta nobody reads is 1: the struct holds a number either way)
+        self.prior = capi.Prior(self.PENALTIES[penalty], self.WEIGHTINGS[weighting], lambda_alpha, lambda_q,
+                                1.0 if delta_alpha is None else delta_alpha, 1.0 if delta_q is None else delta_q)
+
+    def _call(self, fields, enqueue, with_value: bool = False):
+        from . import autograd
+        ctx = self.ctx
+        with autograd._on_gpu(ctx) as device:
+            args = [torch.zeros(ctx.n_cells, dtype=torch.float64, device=device) if t is None else
+                    torch.as_tensor(t).detach().to(device=device, dtype=torch.float64).contiguous() for t in fields]
+            if any(tuple(t.shape) != (ctx.n_cells,) for t in args):
+                raise ValueError(f"every field must hold one value per cell ({ctx.n_cells})")
+            out = autograd._cell_pair(ctx, device)
+            value = torch.empty(2, dtype=torch.float64, device=device) if with_value else None
+            autograd._enqueue(ctx, device, lambda: enqueue(args, value, out))
+        return (value, *out) if with_value else out
+
+    def only(self, fields):
+        """This prior with the lambda of every field not named in `fields` set to 0: the kernels skip a field left out."""
+        p = self.prior
+        kept = SmoothnessPrior.__new__(SmoothnessPrior)
+        kept.ctx = self.ctx
+        kept.prior = capi.Prior(p.penalty, p.weighting, p.lambda_alpha if "alpha" in fields else 0.0,
+                                p.lambda_q if "q" in fields else 0.0, p.delta_alpha, p.delta_q)
+        return kept
+
+    def value_gradient(self, alpha, q) -> tuple:
+        """(value, grad_alpha, grad_q): value float64 [2] = (R(alpha), R(q))."""
+        return self._call((alpha, q), lambda a, value, out: self.ctx.prior_gradient_device(self.prior, a[0], a[1], value, *out), True)
+
+    def product(self, alpha, q, v_alpha, v_q) -> tuple:
+        """(h_alpha, h_q) = Hess R(alpha, q) (v_alpha, v_q); a None direction is zero."""
+        return self._call((alpha, q, v_alpha, v_q), lambda a, _value, out: self.ctx.prior_product_device(self.prior, *a, *out))
+
+    def diagonal(self, alpha, q) -> tuple:
+        """(diag_alpha, diag_q) of Hess R(alpha, q)."""
+        return self._call((alpha, q), lambda a, _value, out: self.ctx.prior_diagonal_device(self.prior, a[0], a[1], *out))
+
+
+class WithPrior:
+    """A context together with a SmoothnessPrior, as one context to gn_step and newton_step:
+
+        delta, models = course5_amd.fit.newton_step(course5_amd.fit.WithPrior(ctx, P), alpha, q, residual)
+
+    the same as prior=P where the step has that argument (gn_step).  ctx: a capi.Context, or anything gn_step takes in its
+    place (RowShards, ExplicitJacobian)."""
+
+    def __init__(self, ctx, prior):
+        self.ctx, self.prior = ctx, prior
+
+
+def _cg_step(ctx, alpha, q, residual, weight, fit, damping, iters, precondition, exact, prior=None):
+    """gn_step (exact False: H = J^T W J) and newton_step (exact True: H the exact Hessian of 1/2 sum w r^2); with a
+    prior P its gradient joins the right-hand side, its Hessian the operator and its diagonal the preconditioner - once,
+    behind whatever sum the context's own operators form."""
     fit = capi.Context._fit(fit, once=True)
     if damping < 0.0 or iters < 1:
         raise ValueError("damping must be >= 0 and iters >= 1")
+    if isinstance(ctx, WithPrior):
+        if prior is not None:
+            raise ValueError("give the prior once: with the context (WithPrior) or as prior=")
+        ctx, prior = ctx.ctx, ctx.prior
+    if hasattr(prior, "only"):
+        prior = prior.only(fit)  # (a field that is not fitted is not computed either)
     ops = _operators(ctx, alpha, q, weight)
     n = alpha.shape[0]
     wr = _weighted(residual, weight) if exact else None
@@ -375,12 +468,19 @@ def _cg_step(ctx, alpha, q, residual, weight, fit, damping, iters, precondition,
     def H(x):
         va, vq = split(x)
         h = pick(*ops.product(va, vq))
-        return h + pick(*ops.hvp(va, vq, wr)) if exact else h
+        if exact:
+            h = h + pick(*ops.hvp(va, vq, wr))
+        return h if prior is None else h + pick(*prior.product(alpha, q, va, vq)).to(h.device)
 
     g = pick(*ops.rhs(residual)).to(torch.float64)  # J^T W r
     d = pick(*ops.diagonal()).to(torch.float64)
-    # (a cell no ray crosses: a zero row and column of H and a zero of the right-hand side; its unknown stays 0)
-    m_inv = torch.where(d > 0, 1.0 / torch.where(d > 0, d, torch.ones_like(d)), torch.zeros_like(d)) if precondition else None
+    # (a cell no ray crosses: a zero row and column of H and a zero of the right-hand side; its unknown stays 0 - unless
+    # a prior couples it to its neighbours)
+    dm = d  # the preconditioner's diagonal; damping scales diag(H) = d alone
+    if prior is not None:
+        g = g + pick(*prior.value_gradient(alpha, q)[1:]).to(g.device)  # J^T W r + grad P
+        dm = d + pick(*prior.diagonal(alpha, q)).to(d.device)
+    m_inv = torch.where(dm > 0, 1.0 / torch.where(dm > 0, dm, torch.ones_like(dm)), torch.zeros_like(dm)) if precondition else None
 
     x = torch.zeros_like(g)
     hx = torch.zeros_like(g)
@@ -411,12 +511,19 @@ def _cg_step(ctx, alpha, q, residual, weight, fit, damping, iters, precondition,
     return split(x), models
 
 
-def gn_step(ctx, alpha, q, residual, weight=None, fit=("q",), damping: float = 0.0, iters: int = 10, precondition: bool = True):
+def gn_step(ctx, alpha, q, residual, weight=None, fit=("q",), damping: float = 0.0, iters: int = 10, precondition: bool = True,
+            prior=None):
     """Up to `iters` iterations of (Jacobi-preconditioned) CG from d = 0 on (H + damping diag(H)) d = -J^T W r over the
     fields named in `fit` ("alpha", "q" or both; the other is held fixed).  Returns ((d_alpha, d_q), models): the step
     (None for a field not fitted) and the model value m(d_i) after every iteration done, as floats.  It stops early when
-    the residual of the linear system vanishes or a direction has no curvature."""
-    return _cg_step(ctx, alpha, q, residual, weight, fit, damping, iters, precondition, exact=False)
+    the residual of the linear system vanishes or a direction has no curvature.
+    prior: a SmoothnessPrior P (None: none, today's path and bits).  CG then runs on
+        (H + damping diag(H) + Hess P) d = -(J^T W r + grad P)
+    with P taken at (alpha, q): the Jacobi preconditioner is the inverse of diag(H) + diag(Hess P), damping keeps scaling
+    diag(H) alone, and models[i] = 1/2 d^T (H + Hess P) d + d^T (J^T W r + grad P).  Only the fields named in `fit` enter,
+    and a fitted field whose lambda is 0 gets no term.  A context with operators of its own (RowShards, ExplicitJacobian)
+    gets the prior added once, after its own sum."""
+    return _cg_step(ctx, alpha, q, residual, weight, fit, damping, iters, precondition, exact=False, prior=prior)
 
 
 def newton_product(ctx, alpha, q, residual, v_alpha, v_q, weight=None) -> tuple:
@@ -437,7 +544,8 @@ def newton_step(ctx, alpha, q, residual, weight=None, fit=("q",), damping: float
     Gauss-Newton diagonal.  The exact Hessian can be indefinite: the iteration stops at the first direction without
     positive curvature and returns what it has - if that is the very first direction, the preconditioned steepest-descent
     direction itself (its model value is then not appended: the model has no minimum along it).  Returns ((d_alpha, d_q),
-    models) as gn_step does.  No line search and no outer loop: the caller owns both."""
+    models) as gn_step does.  No line search and no outer loop: the caller owns both.  A smoothness prior comes with the
+    context: newton_step(WithPrior(ctx, P), ...) adds it as gn_step(..., prior=P) does."""
     return _cg_step(ctx, alpha, q, residual, weight, fit, damping, iters, True, exact=True)
 
 

@@ -807,6 +807,84 @@ int c5_ray_jacobian_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t c
 int c5_ray_jacobian_fill_device(c5_context* ctx, const void* row_ptr_dev, int64_t capacity, void* col_dev, void* dz_dev,
                                 void* dI_dalpha_dev, void* dI_dq_dev);
 
+/* --- cell-field smoothness prior ---------------------------------------------------------------------
+ * What makes a fit of (alpha, Q) well-posed where the rays say nothing: a penalty on the difference of a field across
+ * every interior face of the grid, with its gradient, its Hessian product and the Hessian's diagonal.  The calls need a
+ * grid and nothing else (no image, view, rows or options); the fields are ARGUMENTS, in the caller's cell order - the
+ * prior may be taken at any field, not only at the context's scalars.
+ *
+ * Interior face: a pair of cells (c, n) joined by face f of c (c5_face_adjacency's numbering) in the adjacency
+ * c5_upload_grid built - over welded points, so cells joined only through coincident point copies are neighbours.  Faces
+ * without a partner couple nothing: boundary faces, faces at hanging nodes, the two sides of a non-conforming interface.
+ *
+ * Weight w of a face.  0 on a face that is not interior.  On an interior face
+ *   C5_PRIOR_UNIT   w = 1
+ *   C5_PRIOR_TPFA   w = A / |x_n - x_c|: A the face's area, x a cell's centroid (the mean of its four points), both from
+ *                   the object-space coordinates as the device holds them now (after welding, after the last
+ *                   c5_update_points; no view enters).  In fp64, no contraction: with the face's three welded point ids
+ *                   ascending, t0 < t1 < t2, e1 = P[t1] - P[t0], e2 = P[t2] - P[t0], c = e1 x e2 (cx = e1y e2z - e1z e2y,
+ *                   ...), A = 0.5 sqrt((cx^2 + cy^2) + cz^2); the two cells share the face's points, so x_n - x_c is
+ *                   (a_n - a_c) / 4 for their remaining points a: g = a_n - a_c, |x_n - x_c| = 0.25 sqrt((gx^2 + gy^2) +
+ *                   gz^2); w = A / |x_n - x_c|.  A weight that is not finite and positive (zero area, coincident
+ *                   centroids) is stored as 0 and counted.
+ * w is a function of the UNORDERED pair: every operand above is the same whichever cell asks (g only changes sign, and is
+ * squared), so w[c][f] and its partner's w[n][f'] are the same bits, under "cell_order" 0 and 1 alike.
+ *
+ * Penalty psi of a difference d = x_c - x_n, per field with its own delta:
+ *   C5_PRIOR_QUADRATIC     psi = d^2 / 2, psi' = d, psi'' = 1
+ *   C5_PRIOR_PSEUDO_HUBER  with u = d / delta, t = u u, s = sqrt(1 + t):
+ *                          psi = delta^2 t / (1 + s), formed as (d d) / (1 + s)   (never s - 1, which is 0 below |u| = 1e-8;
+ *                          d d is delta^2 t without delta^2 leaving the format), psi' = d / s, psi'' = 1 / ((1 + t) s)
+ * Operators, per field x (alpha or Q) with its own lambda >= 0, the sums over the faces f of cell c that have a neighbour n:
+ *   R(x)            = lambda sum over interior faces, each once, of w psi(d)
+ *   (grad R)_c      = lambda sum_f w_f psi'(x_c - x_n)
+ *   (hess R(x) p)_c = lambda sum_f (w_f psi''(x_c - x_n)) (p_c - p_n)
+ *   diag_c          = lambda sum_f w_f psi''(x_c - x_n)
+ * Order of operations: a cell's sum runs over f = 0, 1, 2, 3 as (((0 + t0) + t1) + t2) + t3, a face without a neighbour
+ * adding nothing; each term by plain multiplies as bracketed above, no fused multiply-add; lambda multiplies the finished
+ * sum.  So a numpy restatement reproduces the quadratic operators bit for bit from c5_prior_weights' output, no vector
+ * depends on the cells' device order ("cell_order"), and the quadratic gradient at x IS the product applied to x.
+ * The value: cell c's half h_c = 0.5 (((0 + w_0 psi_0) + w_1 psi_1) + ...), summed over the cells of the device's order in
+ * a fixed tree (wavefront, block, then one block over the blocks' partials) and multiplied by lambda: no atomics, the same
+ * bits from call to call, on a fresh context and between the host and _device forms.
+ *
+ * c5_prior_weights: w[n_cells][4] in the caller's cell and face order (may be NULL), the number of interior faces and of
+ * those stored as 0 (either may be NULL; always host pointers).  The weights are kept on the device per weighting, built
+ * at first use and again after c5_upload_grid and (TPFA) c5_update_points; that build waits for the context's stream once.
+ * c5_prior_gradient: value[2] = (R(alpha), R(q)) where value is not NULL, and the two gradients.
+ * c5_prior_product: the point (alpha, q) is ignored and may be NULL for C5_PRIOR_QUADRATIC, as in c5_prior_diagonal.
+ * A field whose lambda is 0 is left out: its value is 0, its output array, where given, is zeros, all its pointers may be
+ * NULL.  A field with lambda > 0 needs its arrays: C5_ERR_INVALID.  An unknown penalty or weighting, a negative or
+ * non-finite lambda, a delta that is not finite and positive where the penalty is C5_PRIOR_PSEUDO_HUBER and the field's
+ * lambda > 0: C5_ERR_INVALID, nothing written.  A grid uploaded as non-conforming (a face in more than two cells) holds no
+ * adjacency: C5_ERR_MESH.  A context without cells answers as the derivative renders do: C5_ERR_STATE where there is
+ * nothing at all, C5_OK with nothing written but value = (0, 0) where there are only solids.
+ * The host forms are synchronous.  The _device forms take device pointers (value: a device double[2]), are enqueued on
+ * the context's stream and do not wait (but for a pending build of the weights).  One lane per cell, no atomics:
+ * bit-reproducible.  Memory: 32 bytes per cell and weighting used, 16 bytes per 256 cells for the value. */
+enum { C5_PRIOR_QUADRATIC = 0, C5_PRIOR_PSEUDO_HUBER = 1 };
+enum { C5_PRIOR_UNIT = 0, C5_PRIOR_TPFA = 1 };
+typedef struct c5_prior {
+    int32_t penalty;                /* C5_PRIOR_QUADRATIC | C5_PRIOR_PSEUDO_HUBER */
+    int32_t weighting;              /* C5_PRIOR_UNIT | C5_PRIOR_TPFA */
+    double lambda_alpha, lambda_q;  /* >= 0, finite; 0 leaves the field out */
+    double delta_alpha, delta_q;    /* > 0, finite where the penalty uses them */
+} c5_prior;
+int c5_prior_weights(c5_context* ctx, int weighting, double* w_host, int64_t* n_interior_faces, int64_t* n_degenerate);
+int c5_prior_weights_device(c5_context* ctx, int weighting, void* w_dev, int64_t* n_interior_faces, int64_t* n_degenerate);
+int c5_prior_gradient(c5_context* ctx, const c5_prior* prior, const double* alpha_host, const double* q_host, double value_host[2],
+                      double* grad_alpha_host, double* grad_q_host);
+int c5_prior_gradient_device(c5_context* ctx, const c5_prior* prior, const void* alpha_dev, const void* q_dev, void* value_dev,
+                             void* grad_alpha_dev, void* grad_q_dev);
+int c5_prior_product(c5_context* ctx, const c5_prior* prior, const double* alpha_host, const double* q_host, const double* v_alpha_host,
+                     const double* v_q_host, double* h_alpha_host, double* h_q_host);
+int c5_prior_product_device(c5_context* ctx, const c5_prior* prior, const void* alpha_dev, const void* q_dev, const void* v_alpha_dev,
+                            const void* v_q_dev, void* h_alpha_dev, void* h_q_dev);
+int c5_prior_diagonal(c5_context* ctx, const c5_prior* prior, const double* alpha_host, const double* q_host, double* diag_alpha_host,
+                      double* diag_q_host);
+int c5_prior_diagonal_device(c5_context* ctx, const c5_prior* prior, const void* alpha_dev, const void* q_dev, void* diag_alpha_dev,
+                             void* diag_q_dev);
+
 /* --- frames delivered to host memory, pipelined ----------------------------------------------------
  * plane::trace_rays hands back HOST pixels (plane.cpp:144-172); over PCIe Gen5 a 2400x1800 image is
  * 0.65 ms of transfer beside 0.7 ms of rendering, so the two are overlapped: c5_render_host_async renders
