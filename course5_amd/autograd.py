@@ -78,6 +78,11 @@ prior(ctx, alpha, q, prior) is the regulariser such a fit needs: the smoothness 
 interior faces (capi.Prior; include/course5_hip.h: c5_prior_*), a float64 scalar differentiable TWICE in alpha and q - the
 forward is one c5_prior_gradient_device, which leaves the gradient too, and the second derivative is one
 c5_prior_product_device.  It needs the grid alone: no image, no view, and not the context's own scalars.
+
+shape_prior(ctx, xyz, prior) is the regulariser of a SHAPE fit: the elastic energy of the coordinates xyz [n_pts, 3] against
+the rest shape the context holds (ctx.shape_prior_rest; capi.ShapePrior; include/course5_hip.h: c5_shape_prior_*), a
+float64 scalar differentiable twice in xyz exactly as prior is in its fields - one c5_shape_prior_gradient_device for value
+and gradient, one c5_shape_prior_product_device for the second derivative.  The context's own points play no part.
 """
 from __future__ import annotations
 
@@ -930,5 +935,132 @@ def prior(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, prior: capi.P
     return _PriorValue.apply(ctx, alpha, q, prior)
 
 
+# ---- the shape prior ---------------------------------------------------------------------------------------------------
+# R(xyz) of capi.ShapePrior as a differentiable function of the points, built as prior is: the value and the gradient come
+# from ONE c5_shape_prior_gradient_device, the second derivative from ONE c5_shape_prior_product_device, on the same stream
+# rules (_enqueue).
+
+def _no_shape_vmap():
+    raise RuntimeError("course5_amd.autograd.shape_prior: vmap (a batch of point sets, tangents or cotangents) is not supported; "
+                       "call it once per point set")
+
+
+def _shape_points(ctx: capi.Context, device: torch.device, t):
+    if t is None:
+        return None
+    t = _plain(t).detach().to(device=device, dtype=torch.float64).contiguous()
+    if tuple(t.shape) != (ctx.n_pts, 3):
+        raise ValueError(f"xyz must be [n_pts, 3] = [{ctx.n_pts}, 3], not {list(t.shape)}")
+    return t
+
+
+def _no_shape_third(*_args):
+    raise RuntimeError("course5_amd.autograd.shape_prior: derivatives beyond the second are not supported (the shape prior's "
+                       "Hessian product has no derivative of its own)")
+
+
+class _ShapeProduct(_Operator):
+    """Hess R(xyz) v: one c5_shape_prior_product_device at the point `fr` kept.  It has no derivative of its own."""
+    what = "shape prior's Hessian product"
+    backward = staticmethod(_no_shape_third)
+    jvp = staticmethod(_no_shape_third)
+
+    @staticmethod
+    def forward(fr, xyz, v):
+        ctx: capi.Context = fr.c5
+        with _on_gpu(ctx, unwrapped=True) as device:
+            vv = _shape_points(ctx, device, v)
+            h = torch.empty((ctx.n_pts, 3), dtype=torch.float64, device=device)
+            _enqueue(ctx, device, lambda: ctx.shape_prior_product_device(fr.prior, fr.point, vv, h))
+        return h
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        _no_shape_vmap()
+
+
+class _ShapeGradient(torch.autograd.Function):
+    """grad R at the point of `fr`, as the forward's call left it (no call of its own); its derivative is _ShapeProduct."""
+
+    @staticmethod
+    def forward(fr, xyz):
+        return fr.grad.clone()
+
+    @staticmethod
+    def setup_context(fctx, inputs, output):
+        fctx.fr, fctx.xyz = inputs
+
+    @staticmethod
+    def backward(fctx, g):
+        dtype, dev = fctx.fr.meta
+        return None, _ShapeProduct.apply(fctx.fr, fctx.xyz, g).to(device=dev, dtype=dtype)
+
+    @staticmethod
+    def jvp(fctx, _fr_tangent, xyz_t):
+        return _ShapeProduct.apply(fctx.fr, fctx.xyz, xyz_t)
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        _no_shape_vmap()
+
+
+class _ShapeValue(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx: capi.Context, xyz: torch.Tensor, prior: capi.ShapePrior):
+        with _on_gpu(ctx, unwrapped=True) as device:
+            x = _shape_points(ctx, device, xyz)
+            value = torch.empty(1, dtype=torch.float64, device=device)
+            grad = torch.empty((ctx.n_pts, 3), dtype=torch.float64, device=device)
+            _enqueue(ctx, device, lambda: ctx.shape_prior_gradient_device(prior, x, value, None, grad))
+            ctx.shape_prior_last = (x, grad)  # (setup_context takes them from here)
+            return value[0].clone()
+
+    @staticmethod
+    def setup_context(fctx, inputs, output):
+        ctx, xyz, prior = inputs
+        fctx.c5, fctx.prior = ctx, prior
+        fctx.point, fctx.grad = ctx.shape_prior_last  # (forward has just set it)
+        fctx.meta = (xyz.dtype, xyz.device)
+        fctx.xyz = xyz
+
+    @staticmethod
+    def backward(fctx, g_value: torch.Tensor):
+        dtype, dev = fctx.meta
+        g = _ShapeGradient.apply(fctx, fctx.xyz).to(device=dev, dtype=dtype)
+        return None, g_value.to(g.device) * g, None
+
+    @staticmethod
+    def jvp(fctx, _ctx_tangent, xyz_t, _prior_tangent):
+        # as _PriorValue.jvp: the value's tangent is grad R . t with grad R through _ShapeGradient where something can
+        # differentiate the tangent, and forward over forward is refused
+        from torch._C._functorch import TransformType
+        from torch._functorch.pyfunctorch import retrieve_all_functorch_interpreters
+        levels = [i.key() for i in retrieve_all_functorch_interpreters()]
+        if sum(k == TransformType.Jvp for k in levels) > 1:
+            raise RuntimeError("course5_amd.autograd.shape_prior: torch.func.jvp of a jvp (forward over forward) is not supported; "
+                               "take the second derivative as jvp of grad, grad of jvp, or by double backward")
+        if xyz_t is None:
+            return None
+        xyz = fctx.xyz
+        g = _ShapeGradient.apply(fctx, xyz) if _differentiating_levels() > 1 or xyz.requires_grad else fctx.grad
+        return (g * xyz_t.to(device=g.device, dtype=g.dtype)).sum()
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        _no_shape_vmap()
+
+
+def shape_prior(ctx: capi.Context, xyz: torch.Tensor, prior: capi.ShapePrior) -> torch.Tensor:
+    """R(xyz): the shape prior `prior` (capi.ShapePrior) of the grid of `ctx` against the rest shape it holds
+    (ctx.shape_prior_rest) at the coordinates xyz ([n_pts, 3], the order of upload_grid), a float64 scalar on the context's
+    GPU; +inf under the Neo-Hookean energy where a cell is inverted (the gradient stays finite).  The context's own points
+    play no part.  Differentiable in xyz exactly as prior is in its fields: the forward is one
+    c5_shape_prior_gradient_device on torch's current stream, which leaves the gradient too (torch.autograd.grad and
+    torch.func.grad make no further call); the second derivative - reverse over reverse (create_graph=True),
+    torch.func.jvp(torch.func.grad(f), ...), torch.func.grad of a jvp - is one c5_shape_prior_product_device.  Derivatives
+    beyond the second, jvp of a jvp and vmap raise.  Bit-reproducible.  The stream rules are prior's."""
+    return _ShapeValue.apply(ctx, xyz, prior)
+
+
 __all__ = ["render", "render_view", "render_mesh", "gn_product", "gn_diagonal", "vertex_gn_product", "hvp", "ray_matrix", "ray_jacobian",
-           "prior"]
+           "prior", "shape_prior"]

@@ -33,6 +33,7 @@ LIB_SOURCES = [
     ("geometry_derivative_kernels.hip", ["-munsafe-fp-atomics"]),
     ("ray_matrix_kernels.hip", ["-munsafe-fp-atomics"]),
     ("prior_kernels.hip", ["-ffp-contract=off"]),   # every product rounds: a numpy restatement gives the same bits
+    ("shape_prior_kernels.hip", ["-ffp-contract=off"]),   # the same
     # the C ABI, host code only (context.hpp)
     ("context.hip", []),
     ("grid.hip", []),
@@ -42,6 +43,7 @@ LIB_SOURCES = [
     ("geometry_derivatives.hip", []),
     ("ray_matrix.hip", []),
     ("prior.hip", []),
+    ("shape_prior.hip", []),
     ("host_ring.hip", []),
     ("adjacency.cpp", ["-x", "c++", "-fopenmp"]),
 ]

@@ -23,6 +23,8 @@ C5_EXACT_ADJOINT, C5_EXACT_GN_DIAGONAL, C5_EXACT_HVP = range(3)
 # the smoothness prior's penalties and weightings (c5_prior)
 C5_PRIOR_QUADRATIC, C5_PRIOR_PSEUDO_HUBER = range(2)
 C5_PRIOR_UNIT, C5_PRIOR_TPFA = range(2)
+# the shape prior's energies (c5_shape_prior)
+C5_SHAPE_DIRICHLET, C5_SHAPE_NEO_HOOKEAN = range(2)
 
 
 class Rotation(C.Structure):
@@ -51,6 +53,14 @@ class Prior(C.Structure):
         super().__init__(int(penalty), int(weighting), float(lambda_alpha), float(lambda_q), float(delta_alpha), float(delta_q))
 
 
+class ShapePrior(C.Structure):
+    """c5_shape_prior: the shape prior's energy, its weight lambda and the Neo-Hookean volume term's kappa."""
+    _fields_ = [("energy", C.c_int32), ("reserved", C.c_int32), ("lambda_", C.c_double), ("kappa", C.c_double)]
+
+    def __init__(self, energy=C5_SHAPE_NEO_HOOKEAN, lambda_=0.0, kappa=1.0, reserved=0):
+        super().__init__(int(energy), int(reserved), float(lambda_), float(kappa))
+
+
 class C5Error(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"[c5 status {code}] {message}")
@@ -61,6 +71,7 @@ class C5Error(RuntimeError):
 _vp, _dp_t, _fp_t, _ip_t, _lp_t = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
 _rp_t = C.POINTER(Rotation)
 _pp_t = C.POINTER(Prior)
+_sp_t = C.POINTER(ShapePrior)
 
 # every symbol include/course5_hip.h declares: its argument types, or (argument types, result type) where that is not int
 SIGNATURES = {
@@ -152,6 +163,18 @@ SIGNATURES = {
     "c5_prior_product_device": [_vp, _pp_t, _vp, _vp, _vp, _vp, _vp, _vp],
     "c5_prior_diagonal": [_vp, _pp_t, _dp_t, _dp_t, _dp_t, _dp_t],
     "c5_prior_diagonal_device": [_vp, _pp_t, _vp, _vp, _vp, _vp],
+    "c5_shape_prior_rest": [_vp, _dp_t, C.c_int64, _lp_t],
+    "c5_shape_prior_rest_device": [_vp, _vp, C.c_int64, _lp_t],
+    "c5_shape_prior_rest_data": [_vp, _dp_t, _dp_t, _ip_t],
+    "c5_shape_prior_rest_data_device": [_vp, _vp, _vp, _vp],
+    "c5_shape_prior_gradient": [_vp, _sp_t, _dp_t, _dp_t, _lp_t, _dp_t],
+    "c5_shape_prior_gradient_device": [_vp, _sp_t, _vp, _vp, _vp, _vp],
+    "c5_shape_prior_product": [_vp, _sp_t, _dp_t, _dp_t, _dp_t],
+    "c5_shape_prior_product_device": [_vp, _sp_t, _vp, _vp, _vp],
+    "c5_shape_prior_diagonal": [_vp, _sp_t, _dp_t, _dp_t],
+    "c5_shape_prior_diagonal_device": [_vp, _sp_t, _vp, _vp],
+    "c5_shape_prior_quality": [_vp, _dp_t, _dp_t, _lp_t],
+    "c5_shape_prior_quality_device": [_vp, _vp, _vp, _vp],
 }
 EXPORTS = list(SIGNATURES)
 
@@ -1041,6 +1064,108 @@ class Context:
         """Asynchronous form on the context's stream (tensors or raw device pointers as prior_gradient_device)."""
         self._check(self.lib.c5_prior_diagonal_device(self.handle, C.byref(prior), self._cells_dev(alpha), self._cells_dev(q),
                                                       self._cells_dev(diag_alpha), self._cells_dev(diag_q)))
+
+    # -- shape prior ------------------------------------------------------------------------------------
+    def _points_host(self, a, name: str):
+        """A per-point float64 [n_pts, 3] array of the caller's, or None."""
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != (self.n_pts, 3):
+            raise ValueError(f"{name} must be [n_pts, 3] = [{self.n_pts}, 3], not {list(a.shape)}")
+        return a
+
+    def _points_dev(self, t) -> int:
+        import torch
+        return _device_ptr(t, torch.float64, (self.n_pts, 3))
+
+    def shape_prior_rest(self, xyz=None) -> int:
+        """Take the shape prior's rest shape: xyz float64 [n_pts, 3] in the order of upload_grid, or None for the points
+        the context holds now.  Returns the number of degenerate rest cells (stored with volume 0: they contribute nothing).
+        The rest data stay until the next upload_grid; update_points does not touch them.  Waits for the stream."""
+        x = self._points_host(xyz, "xyz")
+        n_deg = C.c_int64()
+        self._check(self.lib.c5_shape_prior_rest(self.handle, _dp(x), self.n_pts, C.byref(n_deg)))
+        return n_deg.value
+
+    def shape_prior_rest_device(self, xyz) -> int:
+        """shape_prior_rest from device memory (a torch tensor float64 [n_pts, 3] on this context's GPU, a raw device
+        pointer, or None: the context's points), read on the context's stream and waited for."""
+        n_deg = C.c_int64()
+        self._check(self.lib.c5_shape_prior_rest_device(self.handle, self._points_dev(xyz), self.n_pts, C.byref(n_deg)))
+        return n_deg.value
+
+    def shape_prior_rest_data(self) -> tuple:
+        """(binv, vol, vert): the rest data in the order of upload_grid's cells - B = Dm^-1 float64 [n_cells, 3, 3], V0
+        float64 [n_cells] (0: a degenerate cell) and int32 [n_cells, 4], the four points (weld representatives) in the
+        order the arithmetic uses."""
+        n = self.n_cells
+        binv, vol, vert = np.zeros((n, 3, 3)), np.zeros(n), np.zeros((n, 4), dtype=np.int32)
+        self._check(self.lib.c5_shape_prior_rest_data(self.handle, _dp(binv), _dp(vol), vert.ctypes.data_as(_ip_t)))
+        return binv, vol, vert
+
+    def shape_prior_rest_data_device(self, binv, vol, vert):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (float64 [n_cells, 3, 3], float64
+        [n_cells], int32 [n_cells, 4]; any may be None) or raw device pointers."""
+        import torch
+        n = self.n_cells
+        self._check(self.lib.c5_shape_prior_rest_data_device(self.handle, _device_ptr(binv, torch.float64, (n, 3, 3)),
+                                                             _device_ptr(vol, torch.float64, (n,)), _device_ptr(vert, torch.int32, (n, 4))))
+
+    def shape_prior_gradient(self, prior: ShapePrior, xyz) -> tuple:
+        """(value, n_inverted, grad_xyz) of the shape prior at the coordinates xyz (float64 [n_pts, 3] in the order of
+        upload_grid; the context's own points play no part): a float (+inf under the Neo-Hookean energy where a cell is
+        inverted), the number of inverted cells and float64 [n_pts, 3].  Synchronous; bit-reproducible."""
+        x = self._points_host(xyz, "xyz")
+        value, n_inv, grad = np.zeros(1), C.c_int64(), np.zeros((self.n_pts, 3))
+        self._check(self.lib.c5_shape_prior_gradient(self.handle, C.byref(prior), _dp(x), _dp(value), C.byref(n_inv), _dp(grad)))
+        return float(value[0]), n_inv.value, grad
+
+    def shape_prior_gradient_device(self, prior: ShapePrior, xyz, value, n_inverted, grad_xyz):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (xyz, grad_xyz float64 [n_pts, 3];
+        value float64 [1] or None; n_inverted int64 [1] or None) or raw device pointers."""
+        import torch
+        self._check(self.lib.c5_shape_prior_gradient_device(self.handle, C.byref(prior), self._points_dev(xyz),
+                                                            _device_ptr(value, torch.float64, (1,)), _device_ptr(n_inverted, torch.int64, (1,)),
+                                                            self._points_dev(grad_xyz)))
+
+    def shape_prior_product(self, prior: ShapePrior, xyz, v_xyz) -> np.ndarray:
+        """Hess R(xyz) v_xyz, float64 [n_pts, 3]; xyz may be None under the Dirichlet energy (it is ignored there)."""
+        x, v = self._points_host(xyz, "xyz"), self._points_host(v_xyz, "v_xyz")
+        h = np.zeros((self.n_pts, 3))
+        self._check(self.lib.c5_shape_prior_product(self.handle, C.byref(prior), _dp(x), _dp(v), _dp(h)))
+        return h
+
+    def shape_prior_product_device(self, prior: ShapePrior, xyz, v_xyz, h_xyz):
+        """Asynchronous form on the context's stream (tensors or raw device pointers as shape_prior_gradient_device)."""
+        self._check(self.lib.c5_shape_prior_product_device(self.handle, C.byref(prior), self._points_dev(xyz), self._points_dev(v_xyz),
+                                                           self._points_dev(h_xyz)))
+
+    def shape_prior_diagonal(self, prior: ShapePrior, xyz=None) -> np.ndarray:
+        """The diagonal of Hess R(xyz), float64 [n_pts, 3]: the product applied to unit vectors."""
+        x = self._points_host(xyz, "xyz")
+        d = np.zeros((self.n_pts, 3))
+        self._check(self.lib.c5_shape_prior_diagonal(self.handle, C.byref(prior), _dp(x), _dp(d)))
+        return d
+
+    def shape_prior_diagonal_device(self, prior: ShapePrior, xyz, diag_xyz):
+        """Asynchronous form on the context's stream (tensors or raw device pointers as shape_prior_gradient_device)."""
+        self._check(self.lib.c5_shape_prior_diagonal_device(self.handle, C.byref(prior), self._points_dev(xyz), self._points_dev(diag_xyz)))
+
+    def shape_prior_quality(self, xyz) -> tuple:
+        """(ratio, n_inverted): J = det F of every cell at xyz against the rest shape, float64 [n_cells] in the order of
+        upload_grid (0 for a degenerate rest cell), and the number of cells with J <= 0 or not finite."""
+        x = self._points_host(xyz, "xyz")
+        ratio, n_inv = np.zeros(self.n_cells), C.c_int64()
+        self._check(self.lib.c5_shape_prior_quality(self.handle, _dp(x), _dp(ratio), C.byref(n_inv)))
+        return ratio, n_inv.value
+
+    def shape_prior_quality_device(self, xyz, ratio, n_inverted):
+        """Asynchronous form on the context's stream: xyz float64 [n_pts, 3], ratio float64 [n_cells] or None, n_inverted
+        int64 [1] or None (torch tensors on this context's GPU, or raw device pointers)."""
+        import torch
+        self._check(self.lib.c5_shape_prior_quality_device(self.handle, self._points_dev(xyz), _device_ptr(ratio, torch.float64, (self.n_cells,)),
+                                                           _device_ptr(n_inverted, torch.int64, (1,))))
 
     # -- Hessian-vector render ------------------------------------------------------------------------
     def render_hvp(self, d_alpha=None, d_q=None, grad_out=None, fit=("alpha", "q")) -> tuple:

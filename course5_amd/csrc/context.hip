@@ -241,6 +241,7 @@ void c5_destroy(c5_context* ctx) {
                             &ctx->offs64, &ctx->scratch64, &ctx->segs, &ctx->adj_perm, &ctx->scal_stats};
     ctx->deriv.release();
     ctx->prior.release();
+    ctx->shape.release();
     if (ctx->host_sticky) (void)hipHostFree(ctx->host_sticky);
     if (ctx->scal_host) (void)hipHostFree(ctx->scal_host);
     if (ctx->host_sb) (void)hipHostFree(ctx->host_sb);

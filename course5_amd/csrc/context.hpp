@@ -223,6 +223,22 @@ struct PriorState {
     }
 };
 
+// The shape prior (c5_shape_prior_*, shape_prior.hip): nothing of it is allocated before the first call.
+struct ShapeState {
+    DeviceBuffer binv, vol;  // the rest data, device order: B = Dm^-1 [n_cells][3][3] and V0 [n_cells] (zeros: a degenerate cell)
+    bool have_rest = false;  // ... set by c5_shape_prior_rest, dropped by c5_upload_grid, kept across c5_update_points
+    int64_t n_degenerate = 0;
+    DeviceBuffer shares;     // [n_cells][4][3] fp64, device order: the cell launch -> the point launch
+    DeviceBuffer partials;   // [blocks] fp64 then [blocks] int64: the value's and the inverted count's per-block sums
+    DeviceBuffer counts;     // two words the rest's build counts into (non-finite coordinates, degenerate cells)
+    DeviceBuffer io;         // the host-pointer forms' staging
+    void release() {
+        DeviceBuffer* const owned[] = {&binv, &vol, &shares, &partials, &counts, &io};
+        for (DeviceBuffer* b : owned) b->release();
+        have_rest = false;
+    }
+};
+
 }  // namespace c5api
 
 struct c5_context {
@@ -346,6 +362,7 @@ struct c5_context {
     uint64_t grid_serial = 0, adj_perm_serial = ~uint64_t{0};
     uint64_t points_serial = 0;        // bumped by c5_update_points: what is derived from the coordinates on demand is stale
     c5api::PriorState prior;           // the smoothness prior's weights and scratch (prior.hip)
+    c5api::ShapeState shape;           // the shape prior's rest data and scratch (shape_prior.hip)
     // c5_update_points: the cells as the device has them (welded, in its order) and, where c5_upload_grid welded points,
     // every point's representative (empty: none welded) - what measure_grid and upload_block_spheres are run again with
     std::vector<int32_t> host_cell_vert, point_rep;
@@ -397,5 +414,10 @@ int wait_and_collect(c5_context* ctx);
 
 // ---- derivative_setup.hip (derivative_host.hpp: what the derivative renders' files share)
 int finish_adjoint(c5_context* ctx);
+
+// ---- geometry_derivatives.hip
+// the point -> (cell, local vertex) incidence table of the uploaded grid on the device (adjoint.hpp: VertexIncidence), built
+// at first use after an upload: shared by the exact vertex sums and the shape prior
+int vertex_incidence(c5_context* ctx, c5::VertexIncidence& inc);
 
 }  // namespace c5api

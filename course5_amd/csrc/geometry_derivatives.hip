@@ -7,6 +7,37 @@
 
 using namespace c5api;
 
+// The point -> (cell, local vertex) incidence table of the grid on the device, built by the host at the first exact vertex or shape prior
+// call after an upload: per point its entries 4 * (device cell) + (vertex) in ascending order of the CALLER's cell index,
+// so that the per-point sums do not depend on "cell_order".  Connectivity only: c5_update_points keeps it.  Cells name
+// the representatives of welded points: the others' lists are empty.
+int c5api::vertex_incidence(c5_context* ctx, c5::VertexIncidence& inc) {
+    const int64_t n_pts = ctx->n_pts, n_cells = ctx->n_cells;
+    if (ctx->deriv.vtx_inc_serial != ctx->grid_serial || !ctx->deriv.vtx_inc.ptr) {
+        const std::vector<int32_t>& cv = ctx->host_cell_vert;  // (device order)
+        std::vector<int32_t> tab(static_cast<size_t>(n_pts + 1 + 4 * n_cells), 0);
+        int32_t* const ptr = tab.data();
+        int32_t* const idx = ptr + n_pts + 1;
+        for (int64_t i = 0; i < 4 * n_cells; ++i) ++ptr[cv[static_cast<size_t>(i)] + 1];
+        for (int64_t p = 0; p < n_pts; ++p) ptr[p + 1] += ptr[p];
+        std::vector<int32_t> at(ptr, ptr + n_pts), of_caller;  // where a point's next entry goes; caller's index -> the device's
+        if (!ctx->cell_perm.empty()) {
+            of_caller.resize(static_cast<size_t>(n_cells));
+            for (int64_t d = 0; d < n_cells; ++d) of_caller[static_cast<size_t>(ctx->cell_perm[static_cast<size_t>(d)])] = static_cast<int32_t>(d);
+        }
+        for (int64_t c = 0; c < n_cells; ++c) {
+            const int64_t d = of_caller.empty() ? c : of_caller[static_cast<size_t>(c)];
+            for (int k = 0; k < 4; ++k) idx[at[static_cast<size_t>(cv[static_cast<size_t>(4 * d + k)])]++] = static_cast<int32_t>(4 * d + k);
+        }
+        C5_HIP(ctx, ctx->deriv.vtx_inc.ensure(tab.size() * sizeof(int32_t)));
+        C5_HIP(ctx, hipMemcpy(ctx->deriv.vtx_inc.ptr, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        ctx->deriv.vtx_inc_serial = ctx->grid_serial;
+    }
+    inc.ptr = ctx->deriv.vtx_inc.as<int32_t>();
+    inc.idx = inc.ptr + n_pts + 1;
+    return C5_OK;
+}
+
 namespace {
 
 // The motion tangent: n velocity fields (host memory, [n][12]: A row-major then b, view space) -> out[n][local_rows][res_x]:
@@ -57,37 +88,6 @@ int vertex_exact_sums(c5_context* ctx, c5::VertexExactSums& x) {
     x.exps = reinterpret_cast<int32_t*>(x.words + 24 * n_cells);  // (192 n_cells bytes on: 16-byte aligned)
     x.misfits = reinterpret_cast<unsigned*>(x.exps + 12 * n_cells);
     x.word_bits = m;
-    return C5_OK;
-}
-
-// The point -> (cell, local vertex) incidence table of the grid on the device, built by the host at the first exact vertex
-// call after an upload: per point its entries 4 * (device cell) + (vertex) in ascending order of the CALLER's cell index,
-// so that the per-point sums do not depend on "cell_order".  Connectivity only: c5_update_points keeps it.  Cells name
-// the representatives of welded points: the others' lists are empty.
-int vertex_incidence(c5_context* ctx, c5::VertexIncidence& inc) {
-    const int64_t n_pts = ctx->n_pts, n_cells = ctx->n_cells;
-    if (ctx->deriv.vtx_inc_serial != ctx->grid_serial || !ctx->deriv.vtx_inc.ptr) {
-        const std::vector<int32_t>& cv = ctx->host_cell_vert;  // (device order)
-        std::vector<int32_t> tab(static_cast<size_t>(n_pts + 1 + 4 * n_cells), 0);
-        int32_t* const ptr = tab.data();
-        int32_t* const idx = ptr + n_pts + 1;
-        for (int64_t i = 0; i < 4 * n_cells; ++i) ++ptr[cv[static_cast<size_t>(i)] + 1];
-        for (int64_t p = 0; p < n_pts; ++p) ptr[p + 1] += ptr[p];
-        std::vector<int32_t> at(ptr, ptr + n_pts), of_caller;  // where a point's next entry goes; caller's index -> the device's
-        if (!ctx->cell_perm.empty()) {
-            of_caller.resize(static_cast<size_t>(n_cells));
-            for (int64_t d = 0; d < n_cells; ++d) of_caller[static_cast<size_t>(ctx->cell_perm[static_cast<size_t>(d)])] = static_cast<int32_t>(d);
-        }
-        for (int64_t c = 0; c < n_cells; ++c) {
-            const int64_t d = of_caller.empty() ? c : of_caller[static_cast<size_t>(c)];
-            for (int k = 0; k < 4; ++k) idx[at[static_cast<size_t>(cv[static_cast<size_t>(4 * d + k)])]++] = static_cast<int32_t>(4 * d + k);
-        }
-        C5_HIP(ctx, ctx->deriv.vtx_inc.ensure(tab.size() * sizeof(int32_t)));
-        C5_HIP(ctx, hipMemcpy(ctx->deriv.vtx_inc.ptr, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        ctx->deriv.vtx_inc_serial = ctx->grid_serial;
-    }
-    inc.ptr = ctx->deriv.vtx_inc.as<int32_t>();
-    inc.idx = inc.ptr + n_pts + 1;
     return C5_OK;
 }
 

@@ -270,6 +270,7 @@ int c5_upload_grid(c5_context* ctx, const double* xyz, int64_t n_pts, const int3
     ++ctx->grid_serial;
     ctx->deriv.vtx_inc.release();  // ("vertex_exact": the incidence table is the old connectivity's; the next exact call builds its own)
     ctx->deriv.vtx_inc_serial = ~uint64_t{0};
+    ctx->shape.have_rest = false;  // (c5_shape_prior_*: the rest shape was the old grid's)
     measure_grid(ctx, xyz, n_pts, cell_vert, n_cells);
     scan_alpha(ctx, alpha, n_cells);
     ctx->split_auto_k = 1;

@@ -28,6 +28,11 @@ context's own operators then also need hvp(v_alpha, v_q, grad_img) -> (h_alpha, 
 Where rays say nothing - a cell no ray crosses, the null space along every ray of one view - the system above is singular:
 SmoothnessPrior(ctx, lambda_q=...) is the library's face-neighbour penalty (include/course5_hip.h: c5_prior_*), and
 gn_step(..., prior=P) / newton_step(WithPrior(ctx, P), ...) add its gradient, Hessian and diagonal to the system.
+
+The shape fit has the same gap - a point none of whose cells a ray crosses - and one more: nothing keeps a step from turning
+a cell inside out.  ShapePrior(ctx, lam) is the library's elastic energy of the points against a rest shape
+(include/course5_hip.h: c5_shape_prior_*); shape_gradient / shape_step(WithShapePrior(ctx, P), ...) add it, and
+shape_line_search(ctx, P, xyz, d) halves a step until no cell is inverted.
 """
 from __future__ import annotations
 
@@ -573,6 +578,127 @@ def view_step(ctx, alpha, q, angles, residual, weight=None, damping: float = 0.0
     return d, float(0.5 * d @ H @ d + d @ g)
 
 
+class ShapePrior:
+    """The shape prior of the grid of `ctx` (a capi.Context; of a RowShards any one part's: they carry the same grid): the
+    elastic energy lam * sum V0 psi(F) of the points against a rest shape (include/course5_hip.h: c5_shape_prior).
+
+        P = course5_amd.fit.ShapePrior(ctx, 1e-2)                      # rest: the points the context holds now
+        d, models = course5_amd.fit.shape_step(course5_amd.fit.WithShapePrior(ctx, P), alpha, q, residual)
+        t = course5_amd.fit.shape_line_search(ctx, P, ctx.points, d)   # no cell of xyz + t d is inverted
+
+    energy "neo_hookean" (rotation-invariant, a barrier against inversion, kappa >= 0 its volume term) or "dirichlet"
+    (quadratic).  rest: float64 [n_pts, 3] in the order of upload_grid, None for the points the context holds, or False
+    to keep the rest shape the context already has.  The rest shape lives on the context until the next upload_grid;
+    update_points does not touch it.  The operators take coordinates [n_pts, 3] (torch tensors or arrays, any dtype and
+    device) and return float64 tensors on the context's GPU, one library call each on torch's current stream, under
+    SmoothnessPrior's stream rules (autograd._enqueue)."""
+
+    ENERGIES = {"dirichlet": capi.C5_SHAPE_DIRICHLET, "neo_hookean": capi.C5_SHAPE_NEO_HOOKEAN}
+
+    def __init__(self, ctx, lam: float, energy: str = "neo_hookean", kappa: float = 1.0, rest=None):
+        if energy not in self.ENERGIES:
+            raise ValueError(f"energy must be one of {sorted(self.ENERGIES)}, not {energy!r}")
+        for name, v in (("lam", lam), ("kappa", kappa)):
+            if not (v >= 0.0 and np.isfinite(v)):
+                raise ValueError(f"{name} must be finite and >= 0, not {v!r}")
+        self.ctx = ctx
+        self.prior = capi.ShapePrior(self.ENERGIES[energy], lam, kappa)
+        self.n_degenerate = None
+        if ctx is not None and rest is not False:
+            self.n_degenerate = ctx.shape_prior_rest(None if rest is None else _host(rest, np.float64))
+
+    def _points(self, t, device):
+        t = torch.as_tensor(t).detach().to(device=device, dtype=torch.float64).contiguous()
+        if tuple(t.shape) != (self.ctx.n_pts, 3):
+            raise ValueError(f"coordinates must be [n_pts, 3] = [{self.ctx.n_pts}, 3], not {list(t.shape)}")
+        return t
+
+    def _call(self, arrays, enqueue, outputs):
+        """enqueue(args, outs) with `arrays` as float64 [n_pts, 3] tensors on the context's GPU and outs made by outputs(device)."""
+        from . import autograd
+        ctx = self.ctx
+        with autograd._on_gpu(ctx) as device:
+            args = [None if t is None else self._points(t, device) for t in arrays]
+            outs = outputs(device)
+            autograd._enqueue(ctx, device, lambda: enqueue(args, outs))
+        return outs
+
+    def _vector(self, device):
+        return torch.empty((self.ctx.n_pts, 3), dtype=torch.float64, device=device)
+
+    def value_gradient(self, xyz) -> tuple:
+        """(value, grad): a float64 [1] tensor (+inf where the Neo-Hookean energy meets an inverted cell) and float64 [n_pts, 3]."""
+        value, grad = self._call((xyz,), lambda a, o: self.ctx.shape_prior_gradient_device(self.prior, a[0], o[0], None, o[1]),
+                                 lambda device: (torch.empty(1, dtype=torch.float64, device=device), self._vector(device)))
+        return value, grad
+
+    def product(self, xyz, v) -> torch.Tensor:
+        """Hess R(xyz) v, float64 [n_pts, 3]."""
+        return self._call((xyz, v), lambda a, o: self.ctx.shape_prior_product_device(self.prior, a[0], a[1], o[0]),
+                          lambda device: (self._vector(device),))[0]
+
+    def diagonal(self, xyz) -> torch.Tensor:
+        """The diagonal of Hess R(xyz), float64 [n_pts, 3]."""
+        return self._call((xyz,), lambda a, o: self.ctx.shape_prior_diagonal_device(self.prior, a[0], o[0]),
+                          lambda device: (self._vector(device),))[0]
+
+    def quality(self, xyz) -> tuple:
+        """(ratio, n_inverted): J = det F per cell at xyz, float64 [n_cells] on the context's GPU in the order of
+        upload_grid, and the number of inverted cells as an int (read back: this call waits)."""
+        ratio, n_inv = self._call((xyz,), lambda a, o: self.ctx.shape_prior_quality_device(a[0], o[0], o[1]),
+                                  lambda device: (torch.empty(self.ctx.n_cells, dtype=torch.float64, device=device),
+                                                  torch.zeros(1, dtype=torch.int64, device=device)))
+        return ratio, int(n_inv.item())
+
+    def feasible(self, xyz) -> bool:
+        """No cell is inverted at xyz."""
+        return self.quality(xyz)[1] == 0
+
+
+class WithShapePrior:
+    """A context together with a ShapePrior, as one context to shape_gradient and shape_step:
+
+        d, models = course5_amd.fit.shape_step(course5_amd.fit.WithShapePrior(ctx, P), alpha, q, residual)
+
+    ctx: a capi.Context, or anything shape_step takes in its place (RowShards).  The prior is taken at the points the
+    context holds (ctx.points; of a RowShards its first part's) and enters once, after whatever sum the context's own
+    operators form."""
+
+    def __init__(self, ctx, prior):
+        self.ctx, self.prior = ctx, prior
+
+    def points(self):
+        ctx = self.ctx
+        return (ctx.parts[0][0] if hasattr(ctx, "parts") else ctx).points
+
+
+def shape_line_search(ctx, P, xyz, d, shrink: float = 0.5, max_halvings: int = 30) -> float:
+    """The largest t in 1, shrink, shrink^2, ... for which no cell is inverted at xyz + t d (P.quality: one cell launch per
+    trial, no render): the feasibility half of a line search, the smallest useful piece of the loop around shape_step.
+    xyz, d: [n_pts, 3].  Returns t as a float; 0.0 if max_halvings trials did not find one (xyz itself is then the only
+    point known feasible - or is not feasible either).  ctx is the context whose grid P belongs to."""
+    from . import autograd
+    if P.ctx is not ctx:
+        raise ValueError("the prior belongs to another context")
+    if not 0.0 < shrink < 1.0:
+        raise ValueError("shrink must lie in (0, 1)")
+    with autograd._on_gpu(ctx) as device:
+        x, step = P._points(xyz, device), P._points(d, device)
+    t = 1.0
+    for _ in range(max_halvings + 1):
+        if P.feasible(x + t * step):
+            return t
+        t *= shrink
+    return 0.0
+
+
+def _split_shape_prior(ctx):
+    """(ctx, prior, points): a WithShapePrior taken apart (prior None: a plain context)."""
+    if isinstance(ctx, WithShapePrior):
+        return ctx.ctx, ctx.prior, ctx.points()
+    return ctx, None, None
+
+
 def _shape_loss(r, w):
     """(g, loss): g = w r in float32 and 1/2 sum w r^2 summed in float64, where r lives (w None: ones)."""
     g = (r if w is None else r * w).contiguous()
@@ -587,8 +713,14 @@ def shape_gradient(ctx, alpha, q, residual, weight=None):
     the loop are the caller's.
     A context may bring its own operators, as for gn_step: if it has a method shape_operators(alpha, q, weight) returning
     an object with rhs(residual) -> J^T W r and product(p) -> J^T W J p (float64 [n_pts, 3] tensors), the gradient is its
-    rhs - RowShards, whose residual and weight are whole images [res_y, res_x, 2]."""
+    rhs - RowShards, whose residual and weight are whole images [res_y, res_x, 2].
+    WithShapePrior(ctx, P) in place of ctx: the loss gains R and the gradient grad R, at the points the context holds."""
     from . import autograd
+    ctx, prior, points = _split_shape_prior(ctx)
+    if prior is not None:  # the loss and the gradient gain R and grad R at the points the context holds
+        loss, grad = shape_gradient(ctx, alpha, q, residual, weight)
+        value, g = prior.value_gradient(points)
+        return loss + float(value[0]), grad + g.to(grad.device)
     if hasattr(ctx, "shape_operators"):
         grad = ctx.shape_operators(alpha, q, weight).rhs(residual)
         r = torch.as_tensor(residual).detach().to(device=grad.device, dtype=torch.float32)
@@ -657,13 +789,33 @@ def shape_step(ctx, alpha, q, residual, weight=None, damping: float = 1e-3, iter
     curvature.  No line search and no outer loop: the caller owns both (update_points(xyz + d), render, again).
     CG amplifies last-bit differences of J^T W (J p) from iteration to iteration: with set_option("vertex_exact", 1) on the
     context the steps are the same bits every run.  A context's own operators (shape_operators: shape_gradient) are used
-    where it has them - over RowShards the step is bit for bit the one context's, however the rows are split."""
+    where it has them - over RowShards the step is bit for bit the one context's, however the rows are split.
+    A shape prior comes with the context: shape_step(WithShapePrior(ctx, P), ...) runs CG on
+        (J^T W J + damping I + Hess R) d = -(J^T W r + grad R)
+    with R taken at the points the context holds, one c5_shape_prior_product more per iteration; models[i] then holds the
+    prior's terms too.  The Neo-Hookean Hessian can be indefinite: the iteration stops at a direction without curvature."""
     from . import autograd
     if damping < 0.0 or iters < 1:
         raise ValueError("damping must be >= 0 and iters >= 1")
+    ctx, prior, points = _split_shape_prior(ctx)
+
+    def with_prior(JtWr, H):  # the two operators with the prior's gradient and Hessian product added, once
+        if prior is None:
+            return JtWr, H
+
+        def rhs():
+            g = JtWr()
+            return g + prior.value_gradient(points)[1].to(g.device)
+
+        def product(p):
+            h = H(p)
+            return h + prior.product(points, p).to(h.device)
+
+        return rhs, product
+
     if hasattr(ctx, "shape_operators"):
         ops = ctx.shape_operators(alpha, q, weight)
-        return _shape_cg(lambda: ops.rhs(residual), ops.product, damping, iters, free, ctx.n_pts)
+        return _shape_cg(*with_prior(lambda: ops.rhs(residual), ops.product), damping, iters, free, ctx.n_pts)
     device = autograd._gn_enter(ctx, alpha, q, "shape_step")
     with torch.cuda.device(device):
         r_img = residual.detach().to(device=device, dtype=torch.float32)
@@ -677,4 +829,4 @@ def shape_step(ctx, alpha, q, residual, weight=None, damping: float = 1e-3, iter
         def H(p):  # J^T W J p: autograd.vertex_gn_product's one library call (the scalars are the context's already)
             return autograd._vertex_gn_product(ctx, p.reshape(1, ctx.n_pts, 3).contiguous(), w, device)[0]
 
-        return _shape_cg(lambda: JtW(r_img), H, damping, iters, free, ctx.n_pts)
+        return _shape_cg(*with_prior(lambda: JtW(r_img), H), damping, iters, free, ctx.n_pts)

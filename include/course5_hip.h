@@ -885,6 +885,93 @@ int c5_prior_diagonal(c5_context* ctx, const c5_prior* prior, const double* alph
 int c5_prior_diagonal_device(c5_context* ctx, const c5_prior* prior, const void* alpha_dev, const void* q_dev, void* diag_alpha_dev,
                              void* diag_q_dev);
 
+/* --- shape prior ---------------------------------------------------------------------------------------
+ * What makes a fit of the grid's SHAPE (c5_update_points, c5_render_vertex_adjoint, c5_render_vertex_gn_product)
+ * well-posed where the rays say nothing, and what tells a caller that a trial step turns a cell inside out: an elastic
+ * energy of the points relative to a rest shape, with its gradient, its Hessian product, the Hessian's diagonal and the
+ * cells' volume ratios.  The calls need a grid and nothing else (no image, view, rows or options, and no face adjacency:
+ * a grid uploaded as non-conforming is served like any other); the coordinates are ARGUMENTS, [n_pts][3] fp64 in the order
+ * of c5_upload_grid - a line search evaluates trial points without moving the grid.
+ *
+ * Rest shape.  Coordinates X[n_pts][3], taken once by c5_shape_prior_rest, give per cell with points (X0..X3) - in the
+ * order the device holds the cell's four ids, a point welded at upload replaced by its representative -
+ *   Dm = [X1 - X0, X2 - X0, X3 - X0] (columns), B = Dm^-1, V0 = |det Dm| / 6,
+ * in fp64 without contraction: with the cofactors C00 = D11 D22 - D12 D21, C01 = D12 D20 - D10 D22, C02 = D10 D21 - D11 D20,
+ * C10 = D02 D21 - D01 D22, C11 = D00 D22 - D02 D20, C12 = D01 D20 - D00 D21, C20 = D01 D12 - D02 D11, C21 = D02 D10 - D00 D12,
+ * C22 = D00 D11 - D01 D10: det = (D00 C00 + D01 C01) + D02 C02 and B[r][c] = C[c][r] / det (the adjugate over the
+ * determinant).  A cell whose V0 or B is not finite, or whose V0 is not positive, is DEGENERATE: it is stored with V0 = 0
+ * and B = 0, contributes nothing anywhere (its ratio below is 0 and it is never counted as inverted), and is counted in
+ * n_degenerate.
+ *
+ * Deformation at coordinates x: Ds = [x1 - x0, x2 - x0, x3 - x0], F = Ds B with F[r][c] = (Ds[r][0] B[0][c] + Ds[r][1]
+ * B[1][c]) + Ds[r][2] B[2][c], J = det F by the cofactor formula above.
+ *
+ * Energy R(x) = lambda sum over the cells of V0 psi(F):
+ *   C5_SHAPE_DIRICHLET    psi = 1/2 |F - I|^2, P = F - I, dP = dF.  Quadratic: the Hessian is constant, the point x is
+ *                         ignored by product and diagonal.  Invariant under translation, not under rotation.
+ *   C5_SHAPE_NEO_HOOKEAN  psi = 1/2 (|F|^2 - 3) - ln J + (kappa / 2) (ln J)^2, kappa >= 0: invariant under rotation, zero with
+ *                         zero gradient at rest, +inf as J -> 0+.  With F^-T = cofactors(F) / J:
+ *                         P  = F + (kappa ln J - 1) F^-T
+ *                         dP = (dF + (1 - kappa ln J) (F^-T dF^T F^-T)) + (kappa tr(F^-1 dF)) F^-T
+ *                         the exact Hessian, which can be indefinite.
+ * |A|^2 is the sum of the squares of A's entries, row by row from the first; tr(F^-1 dF) the sum of F^-T[r][c] dF[r][c] in
+ * the same order; every 3-term inner product is (a0 b0 + a1 b1) + a2 b2.
+ *
+ * A cell's shares.  G = V0 (P B^T): G[r][i] = V0 ((P[r][0] B[i][0] + P[r][1] B[i][1]) + P[r][2] B[i][2]); the gradient at
+ * x_i (i = 1..3) is column i - 1 of G, at x_0 it is -((G[r][0] + G[r][1]) + G[r][2]).  The product: the same with dP of
+ * dF = [v1 - v0, v2 - v0, v3 - v0] B.  The diagonal: entry (point k, coordinate r) of the product applied to the unit
+ * vector of (k, r), by the same operations - it IS the product on unit vectors.
+ *
+ * Inverted cells.  A non-degenerate cell with J <= 0 or J not finite at x is INVERTED: counted in n_inverted under both
+ * energies; under C5_SHAPE_NEO_HOOKEAN it makes the value +inf and contributes nothing to gradient, product and
+ * diagonal, whose outputs stay finite - a caller can back off.
+ *
+ * Per-point sums.  A point's result is the sum of its incident cells' shares in ascending order of the CALLER's cell
+ * index, left to right from 0, then multiplied by lambda: bit-reproducible and independent of "cell_order".  A point
+ * welded to another receives 0, its representative the group's sum, and the welded point's own input coordinates are
+ * ignored (c5_update_points' and c5_render_vertex_adjoint's conventions).  So a numpy restatement reproduces the Dirichlet
+ * operators bit for bit from c5_shape_prior_rest_data's output.  The value: the cells' V0 psi summed over the device's cell
+ * order in a fixed tree (wavefront, block, one block over the blocks' partials), multiplied by lambda: no atomics, the
+ * same bits from call to call and between the host and _device forms.
+ *
+ * c5_shape_prior_rest: xyz[n_pts][3], or NULL for the points the context holds now (after the last c5_update_points);
+ *   n_degenerate may be NULL (always a host pointer; both forms wait for the stream).  The rest data live on the context:
+ *   c5_upload_grid drops them, c5_update_points does not touch them.  A wrong n_pts or a non-finite coordinate:
+ *   C5_ERR_INVALID, and the rest shape set before stays.  Every other call returns C5_ERR_STATE before a rest shape is set.
+ * c5_shape_prior_rest_data: B [n_cells][3][3] (row-major), V0 [n_cells] and the four representatives int32 [n_cells][4] in
+ *   the order the arithmetic uses, all in the CALLER's cell order; every output may be NULL.
+ * c5_shape_prior_gradient: value[1] and n_inverted[1] (either may be NULL) and the gradient.
+ * c5_shape_prior_product / _diagonal: xyz may be NULL under C5_SHAPE_DIRICHLET.
+ * c5_shape_prior_quality: ratio[n_cells] = J in the caller's cell order (may be NULL) and n_inverted (may be NULL); it is
+ *   the operators' cell launch with a store of J.
+ * Any other NULL array, an unknown energy, a lambda or kappa that is negative or not finite, reserved != 0:
+ * C5_ERR_INVALID, nothing written.  A context without cells answers as the c5_prior_* calls do; all calls refuse while
+ * c5_render_host_async frames are outstanding (C5_ERR_STATE).  The host forms are synchronous.  The _device forms take
+ * device pointers (value: a device double, n_inverted: a device int64, read them after the next wait), are enqueued on the
+ * context's stream and do not wait - but for c5_shape_prior_rest and, once per upload, the build of the point-to-cell
+ * incidence table that "vertex_exact" shares.  Memory: 80 bytes per cell of rest data, 96 of shares. */
+enum { C5_SHAPE_DIRICHLET = 0, C5_SHAPE_NEO_HOOKEAN = 1 };
+typedef struct c5_shape_prior {
+    int32_t energy;    /* C5_SHAPE_DIRICHLET | C5_SHAPE_NEO_HOOKEAN */
+    int32_t reserved;  /* 0 */
+    double lambda;     /* >= 0, finite */
+    double kappa;      /* >= 0, finite (C5_SHAPE_NEO_HOOKEAN's volume term) */
+} c5_shape_prior;
+int c5_shape_prior_rest(c5_context* ctx, const double* xyz_host, int64_t n_pts, int64_t* n_degenerate);
+int c5_shape_prior_rest_device(c5_context* ctx, const void* xyz_dev, int64_t n_pts, int64_t* n_degenerate);
+int c5_shape_prior_rest_data(c5_context* ctx, double* binv_host, double* vol_host, int32_t* vert_host);
+int c5_shape_prior_rest_data_device(c5_context* ctx, void* binv_dev, void* vol_dev, void* vert_dev);
+int c5_shape_prior_gradient(c5_context* ctx, const c5_shape_prior* prior, const double* xyz_host, double* value_host, int64_t* n_inverted,
+                            double* grad_xyz_host);
+int c5_shape_prior_gradient_device(c5_context* ctx, const c5_shape_prior* prior, const void* xyz_dev, void* value_dev, void* n_inverted_dev,
+                                   void* grad_xyz_dev);
+int c5_shape_prior_product(c5_context* ctx, const c5_shape_prior* prior, const double* xyz_host, const double* v_xyz_host, double* h_xyz_host);
+int c5_shape_prior_product_device(c5_context* ctx, const c5_shape_prior* prior, const void* xyz_dev, const void* v_xyz_dev, void* h_xyz_dev);
+int c5_shape_prior_diagonal(c5_context* ctx, const c5_shape_prior* prior, const double* xyz_host, double* diag_xyz_host);
+int c5_shape_prior_diagonal_device(c5_context* ctx, const c5_shape_prior* prior, const void* xyz_dev, void* diag_xyz_dev);
+int c5_shape_prior_quality(c5_context* ctx, const double* xyz_host, double* ratio_host, int64_t* n_inverted);
+int c5_shape_prior_quality_device(c5_context* ctx, const void* xyz_dev, void* ratio_dev, void* n_inverted_dev);
+
 /* --- frames delivered to host memory, pipelined ----------------------------------------------------
  * plane::trace_rays hands back HOST pixels (plane.cpp:144-172); over PCIe Gen5 a 2400x1800 image is
  * 0.65 ms of transfer beside 0.7 ms of rendering, so the two are overlapped: c5_render_host_async renders
