@@ -129,17 +129,26 @@ struct Psi<C5_PRIOR_QUADRATIC> {
 template <>
 struct Psi<C5_PRIOR_PSEUDO_HUBER> {
     static constexpr bool kCurvatureNeedsPoint = true;
+    // From |u| = 2^256 on the penalty's linear tail is taken in closed form: there s = |u| to the last bit (1 + t rounds to t
+    // from 2^27 on, and the square root of a rounded square is the number), and past 2^512 t leaves the format - without
+    // the branch the slope would come back as 0 and the value as inf / inf.  A u that is inf takes the branch, a NaN does not.
+    static constexpr double kTail = 0x1p256;
     // delta^2 t = d^2: formed as d * d, so that a large delta (delta^2 beyond the format, t below it) gives the quadratic's bits
     __device__ static double value(double d, double delta) {
         const double u = d / delta;
-        return (d * d) / (1.0 + sqrt(1.0 + u * u));
+        if (fabs(u) >= kTail) return delta * (fabs(d) - delta);
+        const double dd = d * d, s1 = 1.0 + sqrt(1.0 + u * u);
+        if (dd < INFINITY) return dd / s1;
+        return fabs(d) * (fabs(d) / s1);  // (d d beyond the format while d d / (1 + s) may be inside it)
     }
     __device__ static double slope(double d, double delta) {
         const double u = d / delta;
+        if (fabs(u) >= kTail) return copysign(delta, d);
         return d / sqrt(1.0 + u * u);
     }
     __device__ static double curvature(double d, double delta) {
         const double u = d / delta;
+        if (fabs(u) >= kTail) return ((1.0 / fabs(u)) / fabs(u)) / fabs(u);  // (|u|^-3, underflowing gradually to 0)
         const double q = 1.0 + u * u;
         return 1.0 / (q * sqrt(q));
     }

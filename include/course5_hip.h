@@ -835,6 +835,12 @@ int c5_ray_jacobian_fill_device(c5_context* ctx, const void* row_ptr_dev, int64_
  *   C5_PRIOR_PSEUDO_HUBER  with u = d / delta, t = u u, s = sqrt(1 + t):
  *                          psi = delta^2 t / (1 + s), formed as (d d) / (1 + s)   (never s - 1, which is 0 below |u| = 1e-8;
  *                          d d is delta^2 t without delta^2 leaving the format), psi' = d / s, psi'' = 1 / ((1 + t) s)
+ *                          Range: every finite d and delta > 0.  t leaves the format at |u| = 2^512 (and u itself may be inf),
+ *                          where the forms above would give psi' = 0 and psi = inf / inf; so from |u| >= 2^256 on - where
+ *                          s = |u| to the last bit - the linear tail is taken in closed form: psi = delta (|d| - delta),
+ *                          psi' = copysign(delta, d), psi'' = ((1 / |u|) / |u|) / |u|, which underflows gradually to 0.
+ *                          Below that, where d d is inf, psi = |d| (|d| / (1 + s)).  Below |u| = 2^256 a finite result of the plain
+ *                          forms is returned as it is.  A psi beyond the format is +inf; a NaN comes from a NaN only.
  * Operators, per field x (alpha or Q) with its own lambda >= 0, the sums over the faces f of cell c that have a neighbour n:
  *   R(x)            = lambda sum over interior faces, each once, of w psi(d)
  *   (grad R)_c      = lambda sum_f w_f psi'(x_c - x_n)

@@ -82,11 +82,27 @@ def weights(xyz, cells, adj, weighting):
 
 # ---- the penalties, in the header's order of operations (float64 arrays in, float64 out)
 
+TAIL = 2.0 ** 256  # |u| from which the header takes the pseudo-Huber penalty's linear tail in closed form
+
+
+def _quiet(f):
+    """The header's forms pass through inf on their way to a finite result (u u, d d): numpy need not warn of it."""
+    def wrapped(*args):
+        with np.errstate(over="ignore", under="ignore", invalid="ignore", divide="ignore"):
+            return f(*args)
+    wrapped.__name__, wrapped.__doc__ = f.__name__, f.__doc__
+    return wrapped
+
+
+@_quiet
 def psi(penalty, d, delta):
     if penalty == QUADRATIC:
         return 0.5 * (d * d)
+    d = np.asarray(d, dtype=np.float64)
     u = d / delta
-    return (d * d) / (1.0 + np.sqrt(1.0 + u * u))
+    dd, s1 = d * d, 1.0 + np.sqrt(1.0 + u * u)
+    below = np.where(dd < np.inf, dd / s1, np.abs(d) * (np.abs(d) / s1))
+    return np.where(np.abs(u) >= TAIL, delta * (np.abs(d) - delta), below)[()]
 
 
 def psi_naive(d, delta):
@@ -95,19 +111,60 @@ def psi_naive(d, delta):
     return (delta * delta) * (np.sqrt(1.0 + u * u) - 1.0)
 
 
+@_quiet
 def slope(penalty, d, delta):
     if penalty == QUADRATIC:
         return d
+    d = np.asarray(d, dtype=np.float64)
     u = d / delta
-    return d / np.sqrt(1.0 + u * u)
+    return np.where(np.abs(u) >= TAIL, np.copysign(delta, d), d / np.sqrt(1.0 + u * u))[()]
 
 
+@_quiet
 def curvature(penalty, d, delta):
     if penalty == QUADRATIC:
         return np.ones_like(d)
+    d = np.asarray(d, dtype=np.float64)
     u = d / delta
     q = 1.0 + u * u
-    return 1.0 / (q * np.sqrt(q))
+    au = np.abs(u)
+    return np.where(au >= TAIL, ((1.0 / au) / au) / au, 1.0 / (q * np.sqrt(q)))[()]
+
+
+# ---- the pseudo-Huber penalty over the format's range (tests/test_prior_fuzz_cpu.py, tests/test_gpu_prior_fuzz.py)
+
+HUBER_BAR = 24 * EPS  # tests/test_gpu_prior.py derives it
+TINY = 2.0 ** -1022   # the smallest normal number: below it a result is held to HUBER_BAR x TINY absolutely
+
+
+def huber_at_80_digits(d, delta):
+    """(psi, psi', psi'') of the float64 d and delta from the definitions; psi = delta^2 (sqrt(1 + t) - 1) as d^2 / (1 +
+    sqrt(1 + t)), the same number, since 80 digits do not hold 1 + 1e-600 either."""
+    import mpmath as mp
+    mp.mp.dps = 80
+    md, mdelta = mp.mpf(float(d)), mp.mpf(float(delta))
+    t = (md / mdelta) ** 2
+    return md ** 2 / (1 + mp.sqrt(1 + t)), md / mp.sqrt(1 + t), (1 + t) ** mp.mpf(-1.5)
+
+
+def huber_sweep():
+    """[(delta, d)]: |d| / delta by decades from 1e-300 to 1e300 for delta in 1e-150, 1, 1e150, both signs in turn, where d
+    is a finite non-zero float64."""
+    out = []
+    for delta in (1e-150, 1.0, 1e150):
+        for k in range(-300, 301):
+            d = (10.0 ** k) * delta  # (Python floats: inf beyond the format, 0 or a subnormal below it)
+            if math.isfinite(d) and d != 0:
+                out.append((delta, float(d) if k % 2 else -float(d)))
+    return out
+
+
+def huber_within_the_bar(got, want):
+    """|got - want| <= HUBER_BAR max(|want|, TINY) where want is inside the format; beyond it nothing is asked but no NaN."""
+    import mpmath as mp
+    if abs(want) >= mp.mpf(2) ** 1024:
+        return not math.isnan(got)
+    return math.isfinite(got) and abs(mp.mpf(float(got)) - want) <= mp.mpf(HUBER_BAR) * max(abs(want), mp.mpf(TINY))
 
 
 # ---- the operators
@@ -159,6 +216,58 @@ def value(w, adj, x, lam, penalty=QUADRATIC, delta=1.0) -> float:
     x = np.asarray(x, dtype=np.float64)
     total, _ = _sum(adj, x, lambda f, nb, d: w[:, f] * psi(penalty, d, delta))
     return lam * math.fsum(0.5 * total)
+
+
+# ---- the value's tree
+
+def block_sums(v):
+    """[m, 256] lane values -> [m]: per wavefront of 64 lanes v[l] += v[l + off] for off = 32, 16, ..., 1, then the block's
+    four wavefronts added in order from 0 - the header's fixed tree, in float64."""
+    w = np.array(v, dtype=np.float64).reshape(-1, 4, 64)
+    off = 32
+    while off:
+        w[:, :, :off] = w[:, :, :off] + w[:, :, off:2 * off]
+        off //= 2
+    t = np.zeros(len(w))
+    for k in range(4):
+        t = t + w[:, k, 0]
+    return t
+
+
+def tree_sum(lane_values):
+    """The device's sum of one value per cell, cells in the device's order (the caller's under "cell_order" 0): 256 cells
+    per block (the last padded with zeros) through block_sums, 256 strided sums over the blocks' partials, each from 0
+    (lane j takes partials j, j + 256, ...), and block_sums once more.  TREE_DEPTH(n) additions on the longest path."""
+    v = np.asarray(lane_values, dtype=np.float64)
+    n_blocks = max(1, -(-len(v) // 256))
+    padded = np.zeros(n_blocks * 256)
+    padded[:len(v)] = v
+    partials = block_sums(padded.reshape(n_blocks, 256))
+    s = np.zeros(256)
+    for j0 in range(0, n_blocks, 256):
+        chunk = partials[j0:j0 + 256]
+        s[:len(chunk)] = s[:len(chunk)] + chunk
+    return float(block_sums(s[None])[0])
+
+
+def tree_depth(n_cells):
+    """Additions on the longest path from a cell's term to the total: 6 in the wavefront and 4 over the block's wavefronts
+    (from 0), ceil(n_blocks / 256) strided over the partials (from 0), and 6 + 4 again."""
+    n_blocks = max(1, -(-n_cells // 256))
+    return 10 + -(-n_blocks // 256) + 10
+
+
+def value_terms(w, adj, x, penalty=QUADRATIC, delta=1.0):
+    """The cells' halves h_c = 0.5 (((0 + w_0 psi_0) + w_1 psi_1) + ...) as the header forms them, before lambda."""
+    w = np.asarray(w, dtype=np.float64)
+    x = np.asarray(x, dtype=np.float64)
+    total, _ = _sum(adj, x, lambda f, nb, d: w[:, f] * psi(penalty, d, delta))
+    return 0.5 * total
+
+
+def value_tree(w, adj, x, lam, penalty=QUADRATIC, delta=1.0) -> float:
+    """R(x) as the device sums it under "cell_order" 0: tree_sum of the cells' halves in the caller's order, lambda last."""
+    return lam * tree_sum(value_terms(w, adj, x, penalty, delta))
 
 
 def dense_laplacian(w, adj, coefficient=None):
