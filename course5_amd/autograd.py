@@ -785,6 +785,98 @@ def ray_jacobian(ctx: capi.Context, alpha=None, q=None) -> tuple:
         return tuple(torch.sparse_csr_tensor(crow, col, v, size=size, check_invariants=False) for v in (dz, da, dq))
 
 
+def _ray_shape_jacobian_arrays(ctx: capi.Context, device: torch.device) -> tuple:
+    """(crow int64 [local_px + 1], col int32 [nnz], dI_ddz float64 [nnz], faces uint8 [nnz], bary float64 [nnz, 2, 3],
+    face_points int32 [n_cells, 4, 3], dw_dxyz float64 [n_cells, 4, 3]) on `device`, for the scalars, points and view the
+    context holds: c5_ray_matrix_rows_device, c5_ray_matrix_fill_device, c5_ray_shape_jacobian_fill_device and
+    c5_face_gradients_device on torch's current stream, waited for."""
+    n_px = ctx.local_rows * ctx.res_x
+    crow = torch.empty(n_px + 1, dtype=torch.int64, device=device)
+    _use_torch_stream(ctx, device)
+    nnz = ctx.ray_matrix_rows_device(crow)  # (waits and retries by itself)
+    # (an empty torch tensor has no data pointer to hand over)
+    n = max(nnz, 1)
+    col = torch.zeros(n, dtype=torch.int32, device=device)
+    dz, dI = (torch.empty(n, dtype=torch.float64, device=device) for _ in range(2))
+    faces = torch.zeros(n, dtype=torch.uint8, device=device)
+    bary = torch.zeros((n, 2, 3), dtype=torch.float64, device=device)
+    fp = torch.zeros((max(ctx.n_cells, 1), 4, 3), dtype=torch.int32, device=device)
+    dw = torch.zeros((max(ctx.n_cells, 1), 4, 3), dtype=torch.float64, device=device)
+    _run(ctx, lambda: ctx.ray_matrix_fill_device(crow, col, dz))
+    _run(ctx, lambda: ctx.ray_shape_jacobian_device(crow, dI, faces, bary))
+    if ctx.n_cells > 0:
+        _run(ctx, lambda: ctx.face_gradients_device(fp, dw))
+    return crow, col[:nnz], dI[:nnz], faces[:nnz], bary[:nnz], fp[:ctx.n_cells], dw[:ctx.n_cells]
+
+
+def assemble_shape_jacobian(row_ptr, col, alpha, dI_ddz, faces, bary, face_points, dw_dxyz, n_pts: int) -> tuple:
+    """The shape Jacobian's per-segment arrays (capi.Context.ray_shape_jacobian) as ONE coalesced CSR structure with two
+    value arrays: (crow int64 [n_px + 1], cols int64 [nnz_J], v_tau, v_I float64 [nnz_J]) with
+        d tau[p] / d xyz[v][j] = v_tau at (row p, column 3 v + j),     d I[p] / d xyz[v][j] = v_I there.
+    Torch ops on the arrays' device (the CPU included).  A segment expands to up to 18 entries - two faces, three vertices,
+    three coordinates, + at the exit face and - at the entry face, a face whose bit is clear none; entries of the same
+    (pixel, column) are added in the order of the segments (a stable sort by the key): the same bits every call.  alpha:
+    the cells' raw alpha [n_cells] (d tau / d dz), in the order of upload_grid."""
+    row_ptr = torch.as_tensor(row_ptr).to(torch.int64)
+    dev = row_ptr.device
+    n_px, n_col = row_ptr.shape[0] - 1, 3 * int(n_pts)
+    col = torch.as_tensor(col).to(device=dev, dtype=torch.int64)
+    faces = torch.as_tensor(faces).to(device=dev, dtype=torch.int64)
+    f64 = lambda t: torch.as_tensor(t).detach().to(device=dev, dtype=torch.float64)  # noqa: E731
+    alpha, dI, bary, dw = f64(alpha), f64(dI_ddz), f64(bary).reshape(-1, 2, 3), f64(dw_dxyz).reshape(-1, 4, 3)
+    fpts = torch.as_tensor(face_points).to(device=dev, dtype=torch.int64).reshape(-1, 4, 3)
+    nnz = col.shape[0]
+    if not (dI.shape[0] == faces.shape[0] == bary.shape[0] == nnz == int(row_ptr[-1])):
+        raise ValueError(f"col, dI_ddz, faces and bary must hold row_ptr's {int(row_ptr[-1])} elements each")
+    row = torch.repeat_interleave(torch.arange(n_px, device=dev), row_ptr[1:] - row_ptr[:-1])
+    f = torch.stack([faces & 3, (faces >> 2) & 3], 1)                      # [nnz, 2]: exit, entry
+    on = torch.stack([(faces >> 4) & 1, (faces >> 5) & 1], 1).to(torch.bool)
+    c2 = col[:, None].expand(-1, 2)
+    pts = fpts[c2, f]                                                       # [nnz, 2, 3 (vertex)]
+    g = dw[c2, f]                                                           # [nnz, 2, 3 (coordinate)]
+    sign = torch.tensor([1.0, -1.0], dtype=torch.float64, device=dev)
+    coef = bary * sign[None, :, None]
+    vals = coef[:, :, :, None] * g[:, :, None, :]                           # [nnz, 2, 3, 3]
+    cols = 3 * pts[:, :, :, None] + torch.arange(3, device=dev)
+    keep = on[:, :, None, None].expand(-1, -1, 3, 3).reshape(-1)
+    key = (row[:, None, None, None] * n_col + cols).reshape(-1)[keep]
+    seg = torch.arange(nnz, device=dev)[:, None, None, None].expand(-1, 2, 3, 3).reshape(-1)[keep]
+    vals = vals.reshape(-1)[keep]
+    order = torch.argsort(key, stable=True)
+    key, seg, vals = key[order], seg[order], vals[order]
+    ukey, counts = torch.unique_consecutive(key, return_counts=True)
+    offsets = torch.zeros(ukey.shape[0] + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(counts, 0)
+    if ukey.shape[0]:
+        v_tau = torch.segment_reduce(vals * alpha[col[seg]], "sum", offsets=offsets)
+        v_I = torch.segment_reduce(vals * dI[seg], "sum", offsets=offsets)
+    else:
+        v_tau = v_I = torch.zeros(0, dtype=torch.float64, device=dev)
+    crow = torch.zeros(n_px + 1, dtype=torch.int64, device=dev)
+    crow[1:] = torch.cumsum(torch.bincount(torch.div(ukey, n_col, rounding_mode="floor"), minlength=n_px), 0)
+    return crow, ukey % n_col, v_tau, v_I
+
+
+def ray_shape_jacobian(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor) -> tuple:
+    """(J_tau, J_I): the Jacobian of the frame `ctx` would render now, with the scalars alpha and q, with respect to the
+    points the context holds, as two torch.sparse_csr_tensor [local_rows * res_x, 3 * n_pts], float64, on the context's GPU:
+    J_tau[pixel, 3 v + j] = d tau / d xyz[v][j], J_I[pixel, 3 v + j] = d I / d xyz[v][j] (rows: local pixels lrow * res_x +
+    col; points in the order of upload_grid; the columns of points welded to another are empty).  Row p is
+    render_vertex_adjoint's gradient for the upstream image (1, 0) / (0, 1) at p, and J @ d_xyz.reshape(-1) is
+    render_vertex_tangent's image in fp64.  The two share one crow_indices / col_indices storage.  Built from the
+    library's per-segment arrays (c5_ray_matrix_*, c5_ray_shape_jacobian_fill_device, c5_face_gradients_device) on
+    torch's current stream, waited for, and assembled with torch ops (assemble_shape_jacobian: 18 entries per segment
+    before they are coalesced - small and medium frames); no graph.  Bit-reproducible."""
+    device = _gn_enter(ctx, alpha, q, "ray_shape_jacobian")
+    with _on_gpu(ctx):
+        arrays = _ray_shape_jacobian_arrays(ctx, device)
+        a = _plain(alpha).detach().to(device=device, dtype=torch.float64)
+        crow, cols, v_tau, v_I = assemble_shape_jacobian(arrays[0], arrays[1], a, *arrays[2:], ctx.n_pts)
+        size = (ctx.local_rows * ctx.res_x, 3 * ctx.n_pts)
+        # (check_invariants off: one storage, not two validated copies)
+        return tuple(torch.sparse_csr_tensor(crow, cols, v, size=size, check_invariants=False) for v in (v_tau, v_I))
+
+
 # ---- the smoothness prior ----------------------------------------------------------------------------------------------
 # R(alpha) + R(q) of capi.Prior as a differentiable function of the two fields: the value and the gradient come from ONE
 # c5_prior_gradient_device, the second derivative (reverse over reverse, jvp of grad) from ONE c5_prior_product_device.
@@ -1063,4 +1155,4 @@ def shape_prior(ctx: capi.Context, xyz: torch.Tensor, prior: capi.ShapePrior) ->
 
 
 __all__ = ["render", "render_view", "render_mesh", "gn_product", "gn_diagonal", "vertex_gn_product", "hvp", "ray_matrix", "ray_jacobian",
-           "prior", "shape_prior"]
+           "ray_shape_jacobian", "assemble_shape_jacobian", "prior", "shape_prior"]

@@ -145,6 +145,10 @@ SIGNATURES = {
     "c5_ray_matrix_fill_device": [_vp, _vp, C.c_int64, _vp, _vp, _vp],
     "c5_ray_jacobian_fill": [_vp, _lp_t, C.c_int64, _ip_t, _dp_t, _dp_t, _dp_t],
     "c5_ray_jacobian_fill_device": [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp],
+    "c5_ray_shape_jacobian_fill": [_vp, _lp_t, C.c_int64, _dp_t, C.POINTER(C.c_uint8), _dp_t],
+    "c5_ray_shape_jacobian_fill_device": [_vp, _vp, C.c_int64, _vp, _vp, _vp],
+    "c5_face_gradients": [_vp, _ip_t, _dp_t],
+    "c5_face_gradients_device": [_vp, _vp, _vp],
     "c5_render_adjoint_exact_bounds": [_vp, _fp_t, _ip_t, _ip_t],
     "c5_render_adjoint_exact_bounds_device": [_vp, _vp, _vp, _vp],
     "c5_render_adjoint_exact_sums": [_vp, _fp_t, _ip_t, _ip_t, _lp_t, _lp_t],
@@ -836,6 +840,74 @@ class Context:
         d I[pixel] / d alpha[cell] = dI_dalpha, d I[pixel] / d Q[cell] = dI_dq."""
         row_ptr = self.ray_matrix_rows()
         return (row_ptr,) + self.ray_jacobian_fill(row_ptr)
+
+    # -- ray shape Jacobian ------------------------------------------------------------------------
+    def ray_shape_jacobian_fill(self, row_ptr, capacity: int | None = None) -> tuple:
+        """The shape Jacobian's per-segment arrays for ray_matrix_rows' row_ptr of this frame: (dI_ddz float64 [capacity],
+        faces uint8 [capacity], bary float64 [capacity, 2, 3]) (default capacity: row_ptr[-1]), over ray_matrix_fill's
+        structure.  dI_ddz: d I[pixel] / d (the chord of the crossed cell), 0 where the cell is inactive; faces: exit face |
+        entry face << 2 | 16 (the exit face contributes) | 32 (the entry face does); bary: the pixel's barycentric
+        coordinates in the exit and the entry face, zeros where the face does not contribute.  Raises C5_ERR_STATE if the
+        frame changed since ray_matrix_rows.  Synchronous; retries by itself.  Bit-reproducible."""
+        row_ptr = self._row_ptr(row_ptr)
+        n = int(row_ptr[-1]) if capacity is None else int(capacity)
+        if n < 0:
+            raise ValueError(f"capacity must not be negative ({n})")
+        dI = np.zeros(max(n, 1))
+        faces = np.zeros(max(n, 1), dtype=np.uint8)
+        bary = np.zeros((max(n, 1), 2, 3))
+        self._check(self.lib.c5_ray_shape_jacobian_fill(self.handle, row_ptr.ctypes.data_as(_lp_t), n, _dp(dI),
+                                                        faces.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(bary)))
+        return dI[:n], faces[:n], bary[:n]
+
+    def ray_shape_jacobian_device(self, row_ptr, dI_ddz, faces, bary, capacity: int | None = None):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (row_ptr int64 [local_rows * res_x
+        + 1]; dI_ddz float64 [capacity], faces uint8 [capacity], bary float64 [capacity, 2, 3], contiguous) or raw device
+        pointers (then give capacity).  Any one of the three may be None, not all.  Nothing beyond capacity is written; a
+        frame that changed since ray_matrix_rows, or a capacity below row_ptr's total, makes the next synchronize() raise
+        C5_ERR_STATE."""
+        import torch
+        if dI_ddz is None and faces is None and bary is None:
+            raise ValueError("give dI_ddz, faces or bary")
+        if row_ptr is None:
+            raise ValueError("give row_ptr")
+        if capacity is None:
+            first = next(t for t in (dI_ddz, faces, bary) if t is not None)
+            if isinstance(first, int):
+                raise ValueError("give capacity with raw device pointers")
+            capacity = first.shape[0]
+        if capacity < 0:
+            raise ValueError(f"capacity must not be negative ({capacity})")
+        ptrs = (_device_ptr(row_ptr, torch.int64, (self.local_rows * self.res_x + 1,)), _device_ptr(dI_ddz, torch.float64, (capacity,)),
+                _device_ptr(faces, torch.uint8, (capacity,)), _device_ptr(bary, torch.float64, (capacity, 2, 3)))
+        self._check(self.lib.c5_ray_shape_jacobian_fill_device(self.handle, ptrs[0], capacity, *ptrs[1:]))
+
+    def face_gradients(self) -> tuple:
+        """Per cell (the order of upload_grid) and face, for the grid, points and view the context holds: (face_points int32
+        [n_cells, 4, 3]: the points of the face's three vertices, representatives where points were welded; dw_dxyz float64
+        [n_cells, 4, 3]: the change of the face's depth per unit of barycentric weight and unit motion of a vertex, zeros
+        for a face edge-on to the rays).  Synchronous; retries by itself."""
+        fp = np.zeros((max(self.n_cells, 1), 4, 3), dtype=np.int32)
+        dw = np.zeros((max(self.n_cells, 1), 4, 3))
+        self._check(self.lib.c5_face_gradients(self.handle, fp.ctypes.data_as(_ip_t), _dp(dw)))
+        return fp[:self.n_cells], dw[:self.n_cells]
+
+    def face_gradients_device(self, face_points, dw_dxyz):
+        """Asynchronous form on the context's stream: torch tensors on this context's GPU (face_points int32, dw_dxyz float64,
+        [n_cells, 4, 3] each, contiguous) or raw device pointers."""
+        import torch
+        if face_points is None or dw_dxyz is None:
+            raise ValueError("give face_points and dw_dxyz")
+        shape = (self.n_cells, 4, 3)
+        self._check(self.lib.c5_face_gradients_device(self.handle, _device_ptr(face_points, torch.int32, shape),
+                                                      _device_ptr(dw_dxyz, torch.float64, shape)))
+
+    def ray_shape_jacobian(self) -> tuple:
+        """The Jacobian of the frame render() would produce now with respect to the grid's points, per segment:
+        (row_ptr, col, dz, dI_ddz, faces, bary, face_points, dw_dxyz) - ray_matrix's structure, ray_shape_jacobian_fill's
+        arrays and face_gradients' (the formula: include/course5_hip.h, "ray shape Jacobian")."""
+        row_ptr = self.ray_matrix_rows()
+        return (row_ptr,) + self.ray_matrix_fill(row_ptr) + self.ray_shape_jacobian_fill(row_ptr) + self.face_gradients()
 
     # -- tangent render ----------------------------------------------------------------------------
     def render_tangent(self, d_alpha=None, d_q=None) -> np.ndarray:

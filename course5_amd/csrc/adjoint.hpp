@@ -394,6 +394,30 @@ void launch_jacobian_walk(hipStream_t s, const AdjointParams& a, const JacobianR
 // the same over bin_sort_resolve's lists: adjoint_resolve's arithmetic, segment_fill_resolve's rows
 void launch_jacobian_fill_resolve(hipStream_t s, const ResolveParams& r, const JacobianRows& j);
 
+// ---- shape Jacobian (c5_ray_shape_jacobian_fill*, c5_face_gradients*): the ray matrix's structure with the vertex adjoint's
+// per-segment terms as values - d I / d dz, the chord's two faces and the pixel's barycentric coordinates in them - and, per
+// cell and face, what turns a face's depth into its three points' coordinates
+
+struct ShapeRows {
+    // row p's element k goes where RayMatrixParams says; any array may be null (not written)
+    const int64_t* row_ptr;   // [n_local_px + 1]
+    int64_t capacity;
+    double* dI_ddz;           // [capacity] T E (Q - a I_prev): the g_I factor of vertex_walk's G_k; 0 for an inactive segment
+    uint8_t* faces;           // [capacity] exit face | entry face << 2 | 0x10 (exit contributes) | 0x20 (entry contributes)
+    double* bary;             // [capacity][2][3] cell_faces_bary's (l0, l1, l2) of the exit face, then of the entry face
+    unsigned* changed_rows;   // += rows whose length is not row_ptr's or that found no room below capacity
+};
+
+// vertex_walk's walk (after launch_adjoint_walk(.., 1): v.w, v.geo and v.lambda are read) for the upstream image (0, 1) of
+// every pixel, each lane's terms stored to its own row in the order the walk runs, deepest first; hands the heads back cleared
+void launch_shape_jacobian_walk(hipStream_t s, const VertexParams& v, const ShapeRows& j);
+// the same over bin_sort_resolve's lists: vertex_resolve's arithmetic, segment_fill_resolve's rows
+void launch_shape_jacobian_resolve(hipStream_t s, const ResolveParams& r, const ShapeRows& j);
+// per cell (the caller's order through perm; nullptr: the identity) and face: the three points in face_plane's order and
+// M^T (-gx, -gy, 1), zeros for an edge-on face; either array may be null
+void launch_face_gradients(hipStream_t s, const MotionGeometry& geo, int64_t n_cells, const int32_t* perm, const RotationList& R,
+                           int32_t* face_points, double* dw_dxyz);
+
 // c5_update_scalars_device: alpha[i] = alpha_src[perm[i]], q[i] = q_src[perm[i]] (perm nullptr: the identity), and into
 // stats[3] (zeroed by the caller): the bits of the largest alpha > 0, the complemented bits of the smallest alpha >=
 // DBL_EPSILON, and 1 if some alpha is NaN (the host loop of c5_update_scalars, as an order-free max / min / or)

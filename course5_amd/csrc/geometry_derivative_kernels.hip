@@ -25,6 +25,8 @@
 // also the adjoint's first pass): their blocks further down.  The vertex adjoint's sums, single and batched, are fp64 atomics
 // (global_atomic_add_f64: -munsafe-fp-atomics, build.py), added in arrival order: NOT bit-reproducible - unless
 // "vertex_exact" is on: then the exact vertex adjoint sums' kernels run instead (their block below the vertex adjoint's).
+// The shape Jacobian (c5_ray_shape_jacobian_fill*, c5_face_gradients*): the vertex adjoint's per-segment terms stored to
+// the ray matrix's rows instead of summed, no atomics at all: its block at the end.
 #include <type_traits>
 
 #include "deriv_faces.hpp"
@@ -265,13 +267,16 @@ namespace adj {
 // (segment) and what is left to do behind the list (finish): LaneAtomics here, LaneExact<SUMS> for the exact sums below.
 template <class Sink>
 __device__ __forceinline__ void vertex_resolve_body(const ResolveParams& R, const float2* __restrict__ grad_out, Sink sk) {
+    constexpr bool kRows = Sink::kRows;  // (the shape Jacobian's rows: the upstream image is (0, 1) everywhere, grad_out is not read)
     double g_tau = 0.0, g_I = 0.0;
     const ListFrame f = list_frame<true>(R, [&](int64_t lp) {
+        if constexpr (kRows) return true;
         const float2 gw = grad_out[lp];
         g_tau = gw.x;
         g_I = gw.y;
         return !(g_tau == 0.0 && g_I == 0.0);
     });
+    if constexpr (kRows) sk.begin(f.in_image, static_cast<size_t>(f.lp));
     const GridView& g = R.g;
     const MotionGeometry geo{g.cell_vert, g.vx, g.vy, g.vz};
     const double lam_total = lambda_total(f.list, f.n, g, R.alpha_limit);
@@ -280,15 +285,22 @@ __device__ __forceinline__ void vertex_resolve_body(const ResolveParams& R, cons
         const int c = static_cast<int>(f.list[i].cell);
         const double dz = f.list[i].dz, q = g.q[c], a_raw = g.alpha[c];
         const ClampedAlpha ca = clamp_alpha(a_raw, R.alpha_limit);
-        double G = g_tau * a_raw;
+        double G = kRows ? 0.0 : g_tau * a_raw;  // (kRows: an inactive segment stores +0.0, whatever its raw alpha)
         if (ca.active) {
             lam = lambda_add(lam, ca.a, dz);
             const double T = exp(fmin(lam - lam_total, 0.0));
             const double E = exp(-ca.a * dz);
-            G = fma(g_I * T, chord_dI(ca.a, q, E, I), G);
+            if constexpr (kRows) G = T * chord_dI(ca.a, q, E, I);  // (G_k's g_I factor: d I / d dz_k)
+            else G = fma(g_I * T, chord_dI(ca.a, q, E, I), G);
             I = segment_terms(ca.a, q, dz, E, 1.0, I).I_next;
         }
-        if (G != 0.0) {
+        if constexpr (kRows) {  // (the rows hold the segments the frame sums, as segment_fill_resolve's)
+            if (is_segment(dz)) {
+                double p[4][3];
+                load_vertices(geo, g.cell_vert[c], p);
+                sk.segment(c, G, cell_faces_bary(p, f.x, f.y));
+            }
+        } else if (G != 0.0) {
             double p[4][3];
             load_vertices(geo, g.cell_vert[c], p);
             const CellFacesBary cf = cell_faces_bary(p, f.x, f.y);
@@ -300,6 +312,7 @@ __device__ __forceinline__ void vertex_resolve_body(const ResolveParams& R, cons
 
 // the lane adds its six values by itself, fp64 atomics in arrival order
 struct LaneAtomics {
+    static constexpr bool kRows = false;
     double* __restrict__ face_w;
     __device__ __forceinline__ void segment(int cell, double G, const CellFacesBary& cf) const { scatter_faces(face_w, cell, G, cf); }
     __device__ __forceinline__ void finish() const {}
@@ -310,6 +323,18 @@ struct LaneAtomics {
 __global__ __launch_bounds__(256) void vertex_resolve(ResolveParams R, const float2* __restrict__ grad_out, double* __restrict__ face_w) {
     adj::vertex_resolve_body(R, grad_out, adj::LaneAtomics{face_w});
 }
+
+namespace adj {
+
+// d w / d (x, y, z) of a vertex of the face fp that holds the weight wk of the face's depth: wk (-gx, -gy, 1), view space
+// (vertex_finish_cells adds it; face_gradients_kernel hands it out for wk = 1)
+__device__ __forceinline__ void face_weight_gradient(const FacePlane& fp, double wk, double (&g)[3]) {
+    g[0] = -fp.gx * wk;
+    g[1] = -fp.gy * wk;
+    g[2] = wk;
+}
+
+}  // namespace adj
 
 // vertex_finish, per cell: the weights of its faces' vertices times (-gx, -gy, 1) to the points
 __global__ __launch_bounds__(256) void vertex_finish_cells(MotionGeometry G, int64_t n_cells, const double* __restrict__ face_w,
@@ -337,9 +362,11 @@ __global__ __launch_bounds__(256) void vertex_finish_cells(MotionGeometry G, int
             const double wk = w[3 * f + k];
             if (wk != 0.0) {
                 double* const gv = grad_view + 3 * static_cast<int64_t>(vid[adj::face_vertex(f, k)]);
-                atomicAdd(gv, -fp.gx * wk);
-                atomicAdd(gv + 1, -fp.gy * wk);
-                atomicAdd(gv + 2, wk);
+                double g[3];
+                adj::face_weight_gradient(fp, wk, g);
+                atomicAdd(gv, g[0]);
+                atomicAdd(gv + 1, g[1]);
+                atomicAdd(gv + 2, g[2]);
             }
         }
     }
@@ -427,6 +454,7 @@ __device__ __forceinline__ void exact_scatter_face(const VertexExactSums& X, int
 // vertex_resolve_body's sink for the exact sums: pass E (SUMS false) or pass S; misfits counted per lane, added once
 template <bool SUMS>
 struct LaneExact {
+    static constexpr bool kRows = false;
     const VertexExactSums& X;
     unsigned bad = 0;
     __device__ __forceinline__ void segment(int cell, double G, const CellFacesBary& cf) {
@@ -1010,6 +1038,164 @@ __global__ __launch_bounds__(256) void vertex_tangent_resolve(ResolveParams R, c
         }
     }
     out[f.lp] = make_float2(static_cast<float>(tau_dot), static_cast<float>(I_dot));
+}
+
+// ---- shape Jacobian (c5_ray_shape_jacobian_fill*, c5_face_gradients*) --------------------------------------------------------
+// The vertex adjoint's per-segment terms handed out instead of summed, over the ray matrix's rows: per segment
+// d I / d dz_k (the g_I factor of vertex_walk's G_k; d tau / d dz_k is the cell's raw alpha, which the caller holds), the two
+// faces the chord runs between and the pixel's barycentric coordinates in them (cell_faces_bary, to the bit).  What turns
+// a face's depth into its vertices' coordinates depends on grid and view alone: face_gradients_kernel, per cell and face.
+//   adjoint_walk<1>          Lambda per pixel, as for the adjoint.
+//   shape_jacobian_walk      vertex_walk<false>'s frame for the upstream image (0, 1) at every pixel: nothing is shared between
+//                            the lanes, a lane leaves when its ray ends.  EVERY segment is a row's element (the rows are
+//                            segment_walk<2>'s), whatever its G_k: each lane appends to its own row with plain stores.
+//   shape_jacobian_resolve   vertex_resolve_body with the sink ShapeRowStore, over bin_sort_resolve's lists.
+//   face_gradients_kernel    one lane per cell of the device's order, stored through perm into the caller's.
+// No atomics, no LDS, every lane owns its row: bit-reproducible.
+
+namespace adj {
+
+// The shape Jacobian's sink: a lane's row (row_slot: inside [0, capacity) whatever row_ptr holds) and its next element.
+struct ShapeRowStore {
+    static constexpr bool kRows = true;
+    ShapeRows J;
+    RowSlot slot;
+    unsigned k = 0;  // segments of the row so far
+    bool in_image = false;
+    __device__ explicit ShapeRowStore(const ShapeRows& j) : J(j) {}
+    __device__ __forceinline__ void begin(bool in_img, size_t lp) {
+        in_image = in_img;
+        if (in_img) slot = row_slot(J.row_ptr, lp, J.capacity);
+    }
+    // faces: bits 0-1 the exit face, 2-3 the entry face, 4 / 5: the exit / entry face contributes (found: both or neither)
+    __device__ __forceinline__ void segment(int, double dI_ddz, const CellFacesBary& cf) {
+        if (k < slot.n_ok) {  // (plain stores, as store_segment's: ray_matrix_kernels.hip)
+            const long long at = slot.base + k;
+            if (J.dI_ddz) J.dI_ddz[at] = dI_ddz;
+            if (J.faces) J.faces[at] = cf.found ? static_cast<uint8_t>(cf.out.f | (cf.in.f << 2) | 0x30) : static_cast<uint8_t>(0);
+            if (J.bary) {
+                double* const b = J.bary + 6 * at;
+                b[0] = cf.found ? cf.out.l0 : 0.0;
+                b[1] = cf.found ? cf.out.l1 : 0.0;
+                b[2] = cf.found ? cf.out.l2 : 0.0;
+                b[3] = cf.found ? cf.in.l0 : 0.0;
+                b[4] = cf.found ? cf.in.l1 : 0.0;
+                b[5] = cf.found ? cf.in.l2 : 0.0;
+            }
+        }
+        ++k;
+    }
+    // by every lane of the wavefront, after its loop
+    __device__ __forceinline__ void finish() const { count_changed_rows(in_image && !(slot.fits && k == slot.n_ok), J.changed_rows); }
+};
+
+}  // namespace adj
+
+// vertex_walk<false>'s frame (A.grad_out and A.face_w are not read).  The next record and the next cell's vertex ids are
+// loaded before the arithmetic, the vertices at the top of the step.
+__global__ __launch_bounds__(64) void shape_jacobian_walk(VertexParams A, ShapeRows J) {
+    using namespace adj;
+    const WalkParams& P = A.w;
+    Ray r;
+    ShapeRowStore sk(J);
+    double lam = 0.0, lam_total = 0.0, I = 0.0;
+
+    const EntryHead ent = ray_begin(r, P, [&] {
+        lam_total = A.lambda[r.lp];
+        return true;
+    });
+    sk.begin(r.in_image, r.lp);
+
+    CellRegs cur;
+    int4 cv = make_int4(0, 0, 0, 0);
+    if (r.cell >= 0) {
+        load_cell(cur, P.xrec, r.cell);
+        cv = A.geo.cell_vert[r.cell];
+    }
+
+    while (r.cell >= 0) {
+        double p[4][3];
+        load_vertices(A.geo, cv, p);
+        double dz, carry_next;
+        const int nb = ray_step(r, P, ent, cur, dz, carry_next);
+        CellRegs nxt;
+        int4 cv_nxt = cv;
+        if (nb >= 0) {
+            load_cell(nxt, P.xrec, nb);
+            cv_nxt = A.geo.cell_vert[nb];
+        }
+
+        if (is_segment(dz)) {
+            const double a = cur.r6.b, q = cur.r7.b;  // a: clamped, 0 = inactive (cell_optics)
+            double dI_ddz = 0.0;
+            if (a != 0.0) {
+                lam = lambda_add(lam, a, dz);  // (as in pass 1: Lambda_n == Lambda bit for bit, Lambda - Lambda_k >= 0)
+                const double T = exp_nonpositive(fmin(lam - lam_total, 0.0));
+                const double E = exp_nonpositive(-a * dz);
+                dI_ddz = T * chord_dI(a, q, E, I);  // (G_k's g_I factor)
+                I = segment_terms(a, q, dz, E, 1.0, I).I_next;
+            }
+            sk.segment(r.cell, dI_ddz, cell_faces_bary(p, r.x, r.y));
+        }
+        ray_advance(r, nb, carry_next);
+        cur = nxt;
+        cv = cv_nxt;
+    }
+
+    sk.finish();
+    ray_clear_head(r, P);
+}
+
+__global__ __launch_bounds__(256) void shape_jacobian_resolve(ResolveParams R, ShapeRows J) {
+    adj::vertex_resolve_body(R, nullptr, adj::ShapeRowStore(J));
+}
+
+// Per cell i of the device's order, into cell c = perm[i] of the caller's: face_points[c][f][k] the point of vertex k of face
+// f (face_plane's order; cells name the representatives of welded points) and dw_dxyz[c][f] = M^T (-gx, -gy, 1), the face's
+// slopes as vertex_finish_cells forms them (face_weight_gradient at weight 1), M the linear part of the view; an edge-on
+// face (kind 0: no ray crosses it, and it has no slopes): exact zeros.  Either array may be null.
+__global__ __launch_bounds__(256) void face_gradients_kernel(MotionGeometry G, int64_t n_cells, const int32_t* __restrict__ perm,
+                                                             RotationList R, int32_t* __restrict__ face_points,
+                                                             double* __restrict__ dw_dxyz) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= n_cells) return;
+    const int64_t c = perm ? static_cast<int64_t>(perm[i]) : i;
+    const int4 cv = G.cell_vert[i];
+    double p[4][3];
+    adj::load_vertices(G, cv, p);
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+        if (face_points) {
+            int v[3];
+            adj::face_points(cv, f, v);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) face_points[12 * c + 3 * f + k] = v[k];
+        }
+        if (dw_dxyz) {
+            const FacePlane fp = face_plane(p, f);
+            double g[3] = {0.0, 0.0, 0.0};
+            if (fp.kind != 0) {
+                adj::face_weight_gradient(fp, 1.0, g);
+                adj::rotate_linear<true>(R, g[0], g[1], g[2]);
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) dw_dxyz[12 * c + 3 * f + k] = g[k];
+        }
+    }
+}
+
+void launch_shape_jacobian_walk(hipStream_t s, const VertexParams& v, const ShapeRows& j) {
+    if (const unsigned blocks = tile_blocks(v.w.im)) hipLaunchKernelGGL(shape_jacobian_walk, dim3(blocks), dim3(64), 0, s, v, j);
+}
+
+void launch_shape_jacobian_resolve(hipStream_t s, const ResolveParams& r, const ShapeRows& j) {
+    if (const unsigned blocks = pixel_blocks(r.im)) hipLaunchKernelGGL(shape_jacobian_resolve, dim3(blocks), dim3(256), 0, s, r, j);
+}
+
+void launch_face_gradients(hipStream_t s, const MotionGeometry& geo, int64_t n_cells, const int32_t* perm, const RotationList& R,
+                           int32_t* face_points, double* dw_dxyz) {
+    if (n_cells > 0)
+        hipLaunchKernelGGL(face_gradients_kernel, dim3(item_blocks(n_cells)), dim3(256), 0, s, geo, n_cells, perm, R, face_points, dw_dxyz);
 }
 
 void launch_motion_walk(hipStream_t s, int kc, const MotionParams& m) {

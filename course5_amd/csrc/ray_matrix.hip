@@ -2,6 +2,8 @@
 // The ray matrix (ray_matrix_kernels.hip): per pixel the cells its ray crosses and the chord of each crossing, as CSR
 // arrays - rows and fill over derivative_host.hpp and, next to them, their entry points.  And the ray Jacobian: the same
 // rows with the adjoint's per-segment terms as values (jacobian_walk / jacobian_fill_resolve, scalar_derivative_kernels.hip).
+// And the shape Jacobian: the same rows with the vertex adjoint's per-segment terms (shape_jacobian_walk / _resolve) and the
+// faces' points and gradients (face_gradients_kernel; geometry_derivative_kernels.hip).
 // ------------------------------------------------------------------------------------------
 #include "derivative_host.hpp"
 
@@ -127,6 +129,61 @@ int check_ray_jacobian(c5_context* ctx, bool host, const void* row_ptr, int64_t 
     return C5_OK;
 }
 
+// The shape Jacobian's arrays: the ray Jacobian fill's frame around the vertex adjoint's two passes - the Lambda pre-pass
+// (adjoint_walk<1>, the heads left in place), then shape_jacobian_walk, which stores where segment_walk<2> would; or
+// shape_jacobian_resolve over bin_sort_resolve's lists.  Any array may be null.
+int enqueue_shape_jacobian_fill(c5_context* ctx, const int64_t* row_ptr, int64_t capacity, double* dI_ddz, uint8_t* faces, double* bary) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc) return rc;
+    if (v.no_cells) return fill_without_cells(ctx, v, row_ptr, "ray shape jacobian fill", "c5_ray_shape_jacobian_fill");
+    int32_t* count;
+    unsigned* changed_rows;
+    rc = ray_matrix_buffer(ctx, v, count, changed_rows);
+    if (rc) return rc;
+    C5_HIP(ctx, hipMemsetAsync(changed_rows, 0, sizeof(unsigned), v.s));
+    const c5::ShapeRows j{row_ptr, capacity, dI_ddz, faces, bary, changed_rows};
+    if (v.bin_sort) {
+        c5::launch_shape_jacobian_resolve(v.s, v.r, j);
+    } else {
+        c5::AdjointParams ap;
+        rc = adjoint_params(ctx, v, ap);
+        if (rc) return rc;
+        c5::VertexParams vp{};
+        vp.w = v.w;
+        vp.geo = v.geo;
+        vp.lambda = ap.lambda;
+        c5::launch_adjoint_walk(v.s, ap, 1);
+        v.keep(false);  // (the fill hands every head back cleared)
+        c5::launch_shape_jacobian_walk(v.s, vp, j);
+    }
+    rc = commit_derivative(ctx, v, "ray shape jacobian fill");
+    if (rc) return rc;
+    C5_HIP(ctx, hipMemcpyAsync(ctx->deriv.adj_status + 3, changed_rows, sizeof(unsigned), hipMemcpyDeviceToHost, v.s));
+    return C5_OK;
+}
+
+// what both forms of c5_ray_shape_jacobian_fill check of their arguments
+int check_shape_jacobian(c5_context* ctx, bool host, const void* row_ptr, int64_t capacity, const void* dI_ddz, const void* faces,
+                         const void* bary) {
+    int rc = check_derivative(ctx, {"c5_ray_shape_jacobian_fill", host, 1, nullptr, row_ptr && (dI_ddz || faces || bary), true,
+                                    "null row_ptr, or none of dI_ddz, faces and bary"});
+    if (rc) return rc;
+    if (capacity < 0)
+        return fail(ctx, C5_ERR_INVALID, "c5_ray_shape_jacobian_fill: negative capacity (%lld)", static_cast<long long>(capacity));
+    return C5_OK;
+}
+
+// The faces' points and gradients: one per-view setup (the cells' vertices in view space), one kernel over the cells.  No walk:
+// the entry lists the setup built stay unused, and the next setup clears them (as c5_vertex_exact_finish's).
+int enqueue_face_gradients(c5_context* ctx, int32_t* face_points, double* dw_dxyz) {
+    DerivativeView v;
+    int rc = setup_derivative(ctx, v);
+    if (rc || v.no_cells) return rc;
+    c5::launch_face_gradients(v.s, v.geo, ctx->n_cells, v.perm, ctx->view, face_points, dw_dxyz);
+    return commit_derivative(ctx, v, "face gradients");
+}
+
 }  // namespace
 
 extern "C" {
@@ -213,6 +270,49 @@ int c5_ray_jacobian_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t c
         return enqueue_ray_jacobian_fill(ctx, b[0].as<const int64_t>(), need, b[1].as<int32_t>(), b[2].as<double>(), b[3].as<double>(),
                                          b[4].as<double>());
     });
+}
+
+int c5_ray_shape_jacobian_fill_device(c5_context* ctx, const void* row_ptr_dev, int64_t capacity, void* dI_ddz_dev, void* faces_dev,
+                                      void* bary_dev) {
+    int rc = check_shape_jacobian(ctx, false, row_ptr_dev, capacity, dI_ddz_dev, faces_dev, bary_dev);
+    if (rc) return rc;
+    return enqueue_shape_jacobian_fill(ctx, static_cast<const int64_t*>(row_ptr_dev), capacity, static_cast<double*>(dI_ddz_dev),
+                                       static_cast<uint8_t*>(faces_dev), static_cast<double*>(bary_dev));
+}
+
+// Staged for row_ptr's total, as c5_ray_matrix_fill: nothing beyond it is written on the device or copied back.
+int c5_ray_shape_jacobian_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t capacity, double* dI_ddz_host, uint8_t* faces_host,
+                               double* bary_host) {
+    int rc = check_shape_jacobian(ctx, true, row_ptr_host, capacity, dI_ddz_host, faces_host, bary_host);
+    if (rc) return rc;
+    const int64_t n_px = local_pixels(ctx->im), need = row_ptr_host[n_px];
+    if (need < 0 || need > capacity)
+        return fail(ctx, C5_ERR_INVALID, "c5_ray_shape_jacobian_fill: row_ptr asks for %lld elements, capacity is %lld",
+                    static_cast<long long>(need), static_cast<long long>(capacity));
+    const size_t n = static_cast<size_t>(need);
+    Staged b[] = {{row_ptr_host, nullptr, static_cast<size_t>(n_px + 1) * sizeof(int64_t)},
+                  {nullptr, dI_ddz_host, dI_ddz_host ? n * sizeof(double) : 0},
+                  {nullptr, faces_host, faces_host ? n * sizeof(uint8_t) : 0},
+                  {nullptr, bary_host, bary_host ? 6 * n * sizeof(double) : 0}};
+    return run_staged(ctx, "ray shape jacobian fill", b, [&] {
+        return enqueue_shape_jacobian_fill(ctx, b[0].as<const int64_t>(), need, b[1].as<double>(), b[2].as<uint8_t>(), b[3].as<double>());
+    });
+}
+
+int c5_face_gradients_device(c5_context* ctx, void* face_points_dev, void* dw_dxyz_dev) {
+    int rc = check_derivative(ctx, {"c5_face_gradients", false, 1, nullptr, true, face_points_dev && dw_dxyz_dev,
+                                    "null face_points or dw_dxyz pointer"});
+    if (rc) return rc;
+    return enqueue_face_gradients(ctx, static_cast<int32_t*>(face_points_dev), static_cast<double*>(dw_dxyz_dev));
+}
+
+int c5_face_gradients(c5_context* ctx, int32_t* face_points_host, double* dw_dxyz_host) {
+    int rc = check_derivative(ctx, {"c5_face_gradients", true, 1, nullptr, true, face_points_host && dw_dxyz_host,
+                                    "null face_points or dw_dxyz pointer"});
+    if (rc) return rc;
+    const size_t n = 12 * static_cast<size_t>(ctx->n_cells);
+    Staged b[] = {{nullptr, face_points_host, n * sizeof(int32_t)}, {nullptr, dw_dxyz_host, n * sizeof(double)}};
+    return run_staged(ctx, "face gradients", b, [&] { return enqueue_face_gradients(ctx, b[0].as<int32_t>(), b[1].as<double>()); });
 }
 
 }  // extern "C"

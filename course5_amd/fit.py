@@ -32,7 +32,9 @@ gn_step(..., prior=P) / newton_step(WithPrior(ctx, P), ...) add its gradient, He
 The shape fit has the same gap - a point none of whose cells a ray crosses - and one more: nothing keeps a step from turning
 a cell inside out.  ShapePrior(ctx, lam) is the library's elastic energy of the points against a rest shape
 (include/course5_hip.h: c5_shape_prior_*); shape_gradient / shape_step(WithShapePrior(ctx, P), ...) add it, and
-shape_line_search(ctx, P, xyz, d) halves a step until no cell is inverted.
+shape_line_search(ctx, P, xyz, d) halves a step until no cell is inverted.  ExplicitShapeJacobian(ctx) is ExplicitJacobian's
+twin for the shape (autograd.ray_shape_jacobian's arrays), the one set of shape operators with diag(J^T W J), and
+shape_step_preconditioned the step whose CG is Jacobi-preconditioned with it.
 """
 from __future__ import annotations
 
@@ -192,6 +194,110 @@ class ExplicitJacobian:
             w = autograd._gn_weight(ctx, weight, device)
         library = _LibraryOperators(ctx, alpha, q, weight)
         return JacobianOperators(crow, col, dz, da, dq, ctx.n_cells, w, hvp=library.hvp)
+
+
+class ShapeJacobianOperators:
+    """rhs, product and diagonal of shape_step from the coalesced shape Jacobian (autograd.assemble_shape_jacobian: crow
+    [n_px + 1], cols [nnz] = 3 * point + coordinate, v_tau = d tau / d xyz, v_I = d I / d xyz) - torch tensors on any one
+    device, the CPU included - n_pts, and weight [n_px, 2] or [rows, res_x, 2] (None: ones).  Everything in float64:
+
+        H p = J_tau^T (w_tau * (J_tau p)) + J_I^T (w_I * (J_I p)),     diag(H) = sum_p w_tau J_tau^2 + w_I J_I^2.
+
+    Products are JacobianOperators': one gather, one multiply and one segmented sum (torch.segment_reduce) over the CSR rows
+    for J p, and for J^T g over a copy of the values sorted by column, made once here.  No atomics: the same bits every
+    call.  Unlike the library's product, J p is not rounded to float32 on the way.  The vectors are [n_pts, 3]."""
+
+    def __init__(self, crow, cols, v_tau, v_I, n_pts: int, weight=None):
+        crow = torch.as_tensor(crow).to(torch.int64).contiguous()
+        dev = crow.device
+        self.n_px, self.n_pts = crow.shape[0] - 1, int(n_pts)
+        self.crow = crow
+        self.cols = torch.as_tensor(cols).to(device=dev, dtype=torch.int64)
+        self.v_tau, self.v_I = (torch.as_tensor(t).to(device=dev, dtype=torch.float64) for t in (v_tau, v_I))
+        row = torch.repeat_interleave(torch.arange(self.n_px, device=dev), crow[1:] - crow[:-1])
+        if not (row.shape == self.cols.shape == self.v_tau.shape == self.v_I.shape):
+            raise ValueError(f"cols, v_tau and v_I must hold crow's {row.shape[0]} elements each")
+        if self.cols.numel() and not (0 <= int(self.cols.min()) and int(self.cols.max()) < 3 * self.n_pts):
+            raise ValueError(f"cols must name coordinates 0 .. {3 * self.n_pts - 1}")
+        order = torch.argsort(self.cols, stable=True)
+        self.col_ptr = torch.zeros(3 * self.n_pts + 1, dtype=torch.int64, device=dev)
+        self.col_ptr[1:] = torch.cumsum(torch.bincount(self.cols, minlength=3 * self.n_pts), 0)
+        self.row_by_col = row[order]
+        self.v_tau_c, self.v_I_c = self.v_tau[order], self.v_I[order]
+        self.weight = None
+        if weight is not None:
+            self.weight = torch.as_tensor(weight).detach().to(device=dev, dtype=torch.float32).reshape(-1, 2)
+            if self.weight.shape[0] != self.n_px:
+                raise ValueError(f"weight must hold two values for each of the {self.n_px} pixels")
+
+    def _to_pixels(self, values, v):
+        return torch.segment_reduce(values * v[self.cols], "sum", offsets=self.crow)
+
+    def _to_points(self, values_c, g):
+        return torch.segment_reduce(values_c * g[self.row_by_col], "sum", offsets=self.col_ptr)
+
+    def _w(self):
+        w = self.weight
+        return (None, None) if w is None else (w[:, 0].to(torch.float64), w[:, 1].to(torch.float64))
+
+    def jv(self, p):
+        """J p per pixel: (tau_dot, I_dot), float64 [n_px] each."""
+        v = torch.as_tensor(p).detach().to(device=self.crow.device, dtype=torch.float64).reshape(3 * self.n_pts)
+        return self._to_pixels(self.v_tau, v), self._to_pixels(self.v_I, v)
+
+    def jt(self, g_tau, g_I):
+        """J^T g, float64 [n_pts, 3], for the upstream image (g_tau, g_I), float64 [n_px] each."""
+        return (self._to_points(self.v_tau_c, g_tau) + self._to_points(self.v_I_c, g_I)).reshape(self.n_pts, 3)
+
+    def rhs(self, residual):
+        """J^T W r; W r is formed in float32, as the library's right-hand side forms it."""
+        g = torch.as_tensor(residual).detach().to(device=self.crow.device, dtype=torch.float32).reshape(-1, 2)
+        if g.shape[0] != self.n_px:
+            raise ValueError(f"residual must hold two values for each of the {self.n_px} pixels")
+        if self.weight is not None:
+            g = g * self.weight
+        g = g.to(torch.float64)
+        return self.jt(g[:, 0], g[:, 1])
+
+    def product(self, p):
+        tau, I = self.jv(p)
+        w_tau, w_I = self._w()
+        return self.jt(tau if w_tau is None else w_tau * tau, I if w_I is None else w_I * I)
+
+    def diagonal(self):
+        """diag(J^T W J) = sum over the pixels of w J^2 on the coalesced matrix, float64 [n_pts, 3]."""
+        one = torch.ones(self.n_px, dtype=torch.float64, device=self.crow.device)
+        w_tau, w_I = (one if w is None else w for w in self._w())
+        return (self._to_points(self.v_tau_c * self.v_tau_c, w_tau) + self._to_points(self.v_I_c * self.v_I_c, w_I)).reshape(self.n_pts, 3)
+
+
+class ExplicitShapeJacobian:
+    """A context whose shape operators work on the exported shape Jacobian:
+
+        d, models = course5_amd.fit.shape_step_preconditioned(course5_amd.fit.ExplicitShapeJacobian(ctx), alpha, q, residual)
+
+    shape_operators(alpha, q, weight) exports the Jacobian of the frame of `ctx` at (alpha, q) and the points the context
+    holds once (autograd.ray_shape_jacobian's arrays: c5_ray_matrix_rows / _fill, c5_ray_shape_jacobian_fill and
+    c5_face_gradients, coalesced by autograd.assemble_shape_jacobian) and returns ShapeJacobianOperators over it: the
+    right-hand side and every CG iteration's product are then sparse sums in float64 with no walk, and diagonal() is the
+    exact diag(J^T W J) shape_step_preconditioned wants.  The Jacobian belongs to the points it was exported at:
+    after update_points take a fresh object (or call shape_operators again)."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.n_pts = ctx.n_pts
+        self.points = ctx.points
+
+    def shape_operators(self, alpha, q, weight):
+        from . import autograd
+        ctx = self.ctx
+        device = autograd._gn_enter(ctx, alpha, q, "ExplicitShapeJacobian")
+        with torch.cuda.device(device):
+            arrays = autograd._ray_shape_jacobian_arrays(ctx, device)
+            a = autograd._plain(alpha).detach().to(device=device, dtype=torch.float64)  # (as autograd.ray_shape_jacobian)
+            csr = autograd.assemble_shape_jacobian(arrays[0], arrays[1], a, *arrays[2:], ctx.n_pts)
+            w = autograd._gn_weight(ctx, weight, device)
+        return ShapeJacobianOperators(*csr, ctx.n_pts, w)
 
 
 def _host(t, dtype):
@@ -735,8 +841,10 @@ def shape_gradient(ctx, alpha, q, residual, weight=None):
         return loss, autograd._vertex_adjoint(ctx, g, device)
 
 
-def _shape_cg(JtWr, H, damping, iters, free, n_pts):
-    """shape_step's iteration on the two operators: JtWr() -> J^T W r, H(p) -> J^T W J p, float64 [n_pts, 3]."""
+def _shape_cg(JtWr, H, damping, iters, free, n_pts, diagonal=None):
+    """shape_step's iteration on the two operators: JtWr() -> J^T W r, H(p) -> J^T W J p, float64 [n_pts, 3].  diagonal:
+    None (plain CG), or a function returning the diagonal of H's operator, float64 [n_pts, 3]: CG is then preconditioned by
+    the inverse of diagonal() + damping (0 where that is not positive, and in the rows `free` fixes)."""
     g = JtWr()
     keep = None
     if free is not None:
@@ -755,9 +863,32 @@ def _shape_cg(JtWr, H, damping, iters, free, n_pts):
     x = torch.zeros_like(g)
     hx = torch.zeros_like(g)  # (H + damping I) x
     res = -g
+    models = []
+    if diagonal is not None:
+        m = diagonal().to(device=g.device, dtype=torch.float64).reshape(n_pts, 3) + damping
+        m_inv = fixed(torch.where(m > 0, 1.0 / torch.where(m > 0, m, torch.ones_like(m)), torch.zeros_like(m)))
+        z = res * m_inv
+        p = z.clone()
+        rz = dot(res, z)
+        for _ in range(iters):
+            if not rz > 0.0:
+                break
+            ap = fixed(H(p)) + damping * p
+            curvature = dot(p, ap)
+            if not curvature > 0.0:
+                break
+            step = rz / curvature
+            x += step * p
+            hx += step * ap
+            res -= step * ap
+            models.append(0.5 * dot(x, hx) + dot(x, g))
+            z = res * m_inv
+            rz_next = dot(res, z)
+            p = z + (rz_next / rz) * p
+            rz = rz_next
+        return x, models
     p = res.clone()
     rr = dot(res, res)
-    models = []
     for _ in range(iters):
         if not rr > 0.0:
             break
@@ -793,11 +924,44 @@ def shape_step(ctx, alpha, q, residual, weight=None, damping: float = 1e-3, iter
     A shape prior comes with the context: shape_step(WithShapePrior(ctx, P), ...) runs CG on
         (J^T W J + damping I + Hess R) d = -(J^T W r + grad R)
     with R taken at the points the context holds, one c5_shape_prior_product more per iteration; models[i] then holds the
-    prior's terms too.  The Neo-Hookean Hessian can be indefinite: the iteration stops at a direction without curvature."""
+    prior's terms too.  The Neo-Hookean Hessian can be indefinite: the iteration stops at a direction without curvature.
+    shape_step_preconditioned is the same step with a Jacobi preconditioner from the exported Jacobian."""
+    return _shape_step(ctx, alpha, q, residual, weight, damping, iters, free, False)
+
+
+def shape_step_preconditioned(ctx, alpha, q, residual, weight=None, damping: float = 1e-3, iters: int = 10, free=None):
+    """shape_step with Jacobi-preconditioned CG: the same system, the same arguments and the same returns (models[i] is the same
+    model), preconditioned by the inverse of diag(J^T W J) + damping (+ the prior's diagonal at the points the context holds,
+    under WithShapePrior); the rows `free` fixes get 0.  On graded grids diag(J^T W J) spans orders of magnitude from point to
+    point, which damping I does not scale with, and plain CG converges slowly.  The diagonal of the data term cannot be summed
+    per segment (a ray meets a point through several faces, and their terms add before they are squared): it comes from the
+    exported Jacobian, so the context's operators must offer diagonal() - ExplicitShapeJacobian(ctx) does; a plain context or a
+    RowShards raises ValueError.  A function of its own, not an argument of shape_step: shape_step keeps its parameters and runs
+    the code and returns the bits it did."""
+    return _shape_step(ctx, alpha, q, residual, weight, damping, iters, free, True)
+
+
+def _shape_step(ctx, alpha, q, residual, weight, damping, iters, free, precondition):
+    """shape_step (precondition False) and shape_step_preconditioned (True)."""
     from . import autograd
     if damping < 0.0 or iters < 1:
         raise ValueError("damping must be >= 0 and iters >= 1")
     ctx, prior, points = _split_shape_prior(ctx)
+
+    def preconditioner(ops):  # the diagonal _shape_cg inverts, or None
+        if not precondition:
+            return None
+        if ops is None or not hasattr(ops, "diagonal"):
+            raise ValueError("shape_step_preconditioned needs diag(J^T W J), which only the exported Jacobian has: give "
+                             "course5_amd.fit.ExplicitShapeJacobian(ctx) in place of the context")
+        if prior is None:
+            return ops.diagonal
+
+        def diagonal():
+            d = ops.diagonal()
+            return d + prior.diagonal(points).to(d.device)
+
+        return diagonal
 
     def with_prior(JtWr, H):  # the two operators with the prior's gradient and Hessian product added, once
         if prior is None:
@@ -815,7 +979,8 @@ def shape_step(ctx, alpha, q, residual, weight=None, damping: float = 1e-3, iter
 
     if hasattr(ctx, "shape_operators"):
         ops = ctx.shape_operators(alpha, q, weight)
-        return _shape_cg(*with_prior(lambda: ops.rhs(residual), ops.product), damping, iters, free, ctx.n_pts)
+        return _shape_cg(*with_prior(lambda: ops.rhs(residual), ops.product), damping, iters, free, ctx.n_pts, preconditioner(ops))
+    preconditioner(None)  # (a plain context has no diagonal: raises if one is asked for)
     device = autograd._gn_enter(ctx, alpha, q, "shape_step")
     with torch.cuda.device(device):
         r_img = residual.detach().to(device=device, dtype=torch.float32)

@@ -807,6 +807,59 @@ int c5_ray_jacobian_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t c
 int c5_ray_jacobian_fill_device(c5_context* ctx, const void* row_ptr_dev, int64_t capacity, void* col_dev, void* dz_dev,
                                 void* dI_dalpha_dev, void* dI_dq_dev);
 
+/* --- ray shape Jacobian ------------------------------------------------------------------------------
+ * The Jacobian J = d(tau, I) / d xyz the vertex renders apply (c5_render_vertex_tangent forwards, c5_render_vertex_adjoint
+ * transposed), handed out per segment over the ray matrix's structure, in two parts.
+ * c5_ray_shape_jacobian_fill: for pixel p and the k-th cell c its ray crosses (the notation of c5_render_vertex_adjoint:
+ * the chord is dz_k = w_exit - w_entry, a face's depth at the pixel w = sum_i lambda_i z_i)
+ *   dI_ddz[k]  = d I_p / d dz_k = T_k E_k (Q_k - a_k I_{k-1})              (an inactive segment, a_k < DBL_EPSILON: explicit 0;
+ *                the clamp is on alpha, not on the chord: a clamped alpha stores the value.)  d tau_p / d dz_k is the cell's
+ *                raw alpha, which the caller holds: there is no array for it.  The double is the g_I factor of the G_k
+ *                c5_render_vertex_adjoint forms.
+ *   faces[k]   = bits 0-1: the exit face's index in the cell (c5_face_adjacency's numbering: face f lacks vertex 3 - f),
+ *                bits 2-3: the entry face's; bit 4: the exit face contributes, bit 5: the entry face does.  Where the cell's
+ *                two faces are not found at the pixel (a face edge-on to the rays is never a candidate) neither contributes, as
+ *                in the vertex adjoint: the byte is 0.
+ *   bary[k][0][.], bary[k][1][.] = the pixel's barycentric coordinates in the projected exit and entry face, for the
+ *                face's three vertices in the order of face_points below; exact zeros where the face's bit is clear.
+ * c5_face_gradients: per cell c (the CALLER's order) and face f, from grid, points and view alone:
+ *   face_points[c][f][i] int32 = the point (the caller's order; the representative where points were welded) of vertex i of
+ *                face f: {0,1,2}, {0,1,3}, {0,2,3}, {1,2,3} of the cell's four;
+ *   dw_dxyz[c][f][.] = M^T (-gx, -gy, 1): the change of the face's depth at a pixel per unit of barycentric weight and unit
+ *                motion of a vertex, (gx, gy) the face's slopes in view space, M the linear part of the view; exact zeros
+ *                for a face edge-on to the rays.
+ * From these, with col and dz of c5_ray_matrix_fill (c = col[k]),
+ *   d I_p / d xyz[v]   = sum_k dI_ddz[k] sum_{side, i: face_points[c][f_side][i] == v} (+-bary[k][side][i]) dw_dxyz[c][f_side]
+ * with + at the exit face (side 0) and - at the entry face (side 1), and d tau_p / d xyz[v] the same sum with alpha[c] in
+ * place of dI_ddz[k].  Row p of it is c5_render_vertex_adjoint's gradient for the upstream image that is (0, 1) / (1, 0) at
+ * p and zero elsewhere, up to the order of its sums; J d is c5_render_vertex_tangent's image.  Pixels that gain or lose
+ * coverage are not differentiated, as there.
+ * Structure: rows, entries (dz > 0 and finite) and the order within a row (deepest first) are c5_ray_matrix_fill's for
+ * c5_ray_matrix_rows' row_ptr of the same frame; the values include the cells' scalars and c5_set_alpha_limit, the
+ * structure never does.  Any one of dI_ddz, faces and bary may be NULL; all three: C5_ERR_INVALID.  A NULL row_ptr, a
+ * negative capacity, a NULL face_points or dw_dxyz: C5_ERR_INVALID.
+ * Guard and status are c5_ray_jacobian_fill's: nothing outside [0, capacity) (elements; 6 doubles each in bary) is ever
+ * written, whatever row_ptr holds; rows whose length differs from row_ptr's, or that found no room below capacity, are
+ * counted, and the next wait returns C5_ERR_STATE; row_ptr[local_px] > capacity in the host form: C5_ERR_INVALID with the
+ * size needed, nothing written; a solids-only scene writes nothing and returns C5_ERR_STATE itself for a row_ptr whose
+ * total is not 0 (c5_face_gradients: writes nothing, C5_OK).  C5_RETRY and C5_ERR_WALK as for every derivative; the host
+ * forms are synchronous and retry by themselves, the _device forms are asynchronous on the context's stream and report at
+ * the next call that waits for it.  All four refuse while c5_render_host_async frames are outstanding (C5_ERR_STATE), and a
+ * context without a grid or an image as c5_render_adjoint does.
+ * The options "integration", "depth_split", "lds_stage", "tile", "adjoint_exact", "exact_sums", "vertex_exact" and
+ * "vertex_merge" change nothing.  No atomics, every lane owns its row: bit-reproducible, and the rows of a row range or of
+ * row tiles are bit for bit those rows of the whole frame's.  A c5_render afterwards returns the bits it would have
+ * returned without the calls (the slot's per-view data are marked stale, as by the adjoint).
+ * Memory: the arrays are the caller's, nnz x 57 bytes for all three and n_cells x 144 for the faces.  The library
+ * allocates the adjoint's 8 bytes per local pixel (Lambda) and the ray matrix's 4; a context that never calls them
+ * allocates nothing. */
+int c5_ray_shape_jacobian_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t capacity, double* dI_ddz_host,
+                               uint8_t* faces_host, double* bary_host);
+int c5_ray_shape_jacobian_fill_device(c5_context* ctx, const void* row_ptr_dev, int64_t capacity, void* dI_ddz_dev,
+                                      void* faces_dev, void* bary_dev);
+int c5_face_gradients(c5_context* ctx, int32_t* face_points_host, double* dw_dxyz_host);
+int c5_face_gradients_device(c5_context* ctx, void* face_points_dev, void* dw_dxyz_dev);
+
 /* --- cell-field smoothness prior ---------------------------------------------------------------------
  * What makes a fit of (alpha, Q) well-posed where the rays say nothing: a penalty on the difference of a field across
  * every interior face of the grid, with its gradient, its Hessian product and the Hessian's diagonal.  The calls need a
