@@ -720,6 +720,15 @@ def hvp(ctx: capi.Context, alpha: torch.Tensor, q: torch.Tensor, v_alpha, v_q, g
     return ha, hq
 
 
+def _ray_rows(ctx: capi.Context, device: torch.device) -> tuple:
+    """What every export starts with: (crow int64 [local_px + 1] on `device`, nnz, the length to allocate for the arrays of
+    its fill: an empty torch tensor has no data pointer to hand over) - c5_ray_matrix_rows_device on torch's current stream."""
+    crow = torch.empty(ctx.local_rows * ctx.res_x + 1, dtype=torch.int64, device=device)
+    _use_torch_stream(ctx, device)
+    nnz = ctx.ray_matrix_rows_device(crow)  # (waits and retries by itself)
+    return crow, nnz, max(nnz, 1)
+
+
 def ray_matrix(ctx: capi.Context, with_depth: bool = False):
     """The ray matrix A of the frame `ctx` would render now: a torch.sparse_csr_tensor [local_rows * res_x, n_cells],
     float64, on the context's GPU, A[pixel, cell] = the chord of the pixel's ray through the cell (rows: local pixels lrow *
@@ -731,13 +740,10 @@ def ray_matrix(ctx: capi.Context, with_depth: bool = False):
     scalars.  Bit-reproducible."""
     n_px = ctx.local_rows * ctx.res_x
     with _on_gpu(ctx) as device:
-        crow = torch.empty(n_px + 1, dtype=torch.int64, device=device)
-        _use_torch_stream(ctx, device)
-        nnz = ctx.ray_matrix_rows_device(crow)  # (waits and retries by itself)
-        # (an empty torch tensor has no data pointer to hand over)
-        col = torch.empty(max(nnz, 1), dtype=torch.int32, device=device)
-        dz = torch.empty(max(nnz, 1), dtype=torch.float64, device=device)
-        z_exit = torch.empty(max(nnz, 1), dtype=torch.float64, device=device) if with_depth else None
+        crow, nnz, n = _ray_rows(ctx, device)
+        col = torch.empty(n, dtype=torch.int32, device=device)
+        dz = torch.empty(n, dtype=torch.float64, device=device)
+        z_exit = torch.empty(n, dtype=torch.float64, device=device) if with_depth else None
         _run(ctx, lambda: ctx.ray_matrix_fill_device(crow, col, dz, z_exit))
         if nnz < 2 ** 31:
             crow = crow.to(torch.int32)
@@ -750,13 +756,9 @@ def ray_matrix(ctx: capi.Context, with_depth: bool = False):
 def _ray_jacobian_arrays(ctx: capi.Context, device: torch.device) -> tuple:
     """(crow int64 [local_px + 1], col int32 [nnz], dz, dI_dalpha, dI_dq float64 [nnz]) on `device`, for the scalars the
     context holds: c5_ray_matrix_rows_device and c5_ray_jacobian_fill_device on torch's current stream, waited for."""
-    n_px = ctx.local_rows * ctx.res_x
-    crow = torch.empty(n_px + 1, dtype=torch.int64, device=device)
-    _use_torch_stream(ctx, device)
-    nnz = ctx.ray_matrix_rows_device(crow)  # (waits and retries by itself)
-    # (an empty torch tensor has no data pointer to hand over)
-    col = torch.empty(max(nnz, 1), dtype=torch.int32, device=device)
-    dz, da, dq = (torch.empty(max(nnz, 1), dtype=torch.float64, device=device) for _ in range(3))
+    crow, nnz, n = _ray_rows(ctx, device)
+    col = torch.empty(n, dtype=torch.int32, device=device)
+    dz, da, dq = (torch.empty(n, dtype=torch.float64, device=device) for _ in range(3))
     _run(ctx, lambda: ctx.ray_jacobian_fill_device(crow, col, dz, da, dq))
     return crow, col[:nnz], dz[:nnz], da[:nnz], dq[:nnz]
 
@@ -790,12 +792,7 @@ def _ray_shape_jacobian_arrays(ctx: capi.Context, device: torch.device) -> tuple
     face_points int32 [n_cells, 4, 3], dw_dxyz float64 [n_cells, 4, 3]) on `device`, for the scalars, points and view the
     context holds: c5_ray_matrix_rows_device, c5_ray_matrix_fill_device, c5_ray_shape_jacobian_fill_device and
     c5_face_gradients_device on torch's current stream, waited for."""
-    n_px = ctx.local_rows * ctx.res_x
-    crow = torch.empty(n_px + 1, dtype=torch.int64, device=device)
-    _use_torch_stream(ctx, device)
-    nnz = ctx.ray_matrix_rows_device(crow)  # (waits and retries by itself)
-    # (an empty torch tensor has no data pointer to hand over)
-    n = max(nnz, 1)
+    crow, nnz, n = _ray_rows(ctx, device)
     col = torch.zeros(n, dtype=torch.int32, device=device)
     dz, dI = (torch.empty(n, dtype=torch.float64, device=device) for _ in range(2))
     faces = torch.zeros(n, dtype=torch.uint8, device=device)

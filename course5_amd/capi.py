@@ -746,25 +746,38 @@ class Context:
                 return nnz.value
         raise C5Error(C5_RETRY, "ray_matrix_rows_device: the entry buffer kept overflowing")
 
-    def _row_ptr(self, row_ptr) -> np.ndarray:
+    def _fill_rows(self, row_ptr, capacity) -> tuple:
+        """What the host forms of the three fills take first: (row_ptr checked and contiguous, n = the capacity asked for or
+        row_ptr's total, the length to allocate: an empty array has no pointer to hand over)."""
         if not isinstance(row_ptr, np.ndarray) or row_ptr.dtype != np.int64:
             raise ValueError("row_ptr must be the int64 array ray_matrix_rows returned")
         if row_ptr.shape != (self.local_rows * self.res_x + 1,):
             raise ValueError(f"row_ptr must be [{self.local_rows * self.res_x + 1}], not {list(row_ptr.shape)}")
-        return np.ascontiguousarray(row_ptr)
+        n = int(row_ptr[-1]) if capacity is None else int(capacity)
+        if n < 0:
+            raise ValueError(f"capacity must not be negative ({n})")
+        return np.ascontiguousarray(row_ptr), n, max(n, 1)
+
+    @staticmethod
+    def _fill_capacity(capacity, *arrays):
+        """What the device forms of the three fills take for the capacity: the one given, else the length of the first array
+        that is there - which a raw device pointer does not say."""
+        if capacity is None:
+            first = next((t for t in arrays if t is not None), None)
+            if first is None or isinstance(first, int):
+                raise ValueError("give capacity with raw device pointers")
+            capacity = first.shape[0]
+        return capacity
 
     def ray_matrix_fill(self, row_ptr, with_depth: bool = False, capacity: int | None = None) -> tuple:
         """The ray matrix's arrays for ray_matrix_rows' row_ptr of this frame: (col int32, dz float64[, z_exit float64]),
         [capacity] each (default: row_ptr[-1]).  col: cells in the order of upload_grid; within a row deepest segment first;
         z_exit: the segment's far end in view space.  Raises C5_ERR_STATE if the frame changed since ray_matrix_rows.
         Synchronous; retries by itself.  Bit-reproducible."""
-        row_ptr = self._row_ptr(row_ptr)
-        n = int(row_ptr[-1]) if capacity is None else int(capacity)
-        if n < 0:
-            raise ValueError(f"capacity must not be negative ({n})")
-        col = np.zeros(max(n, 1), dtype=np.int32)
-        dz = np.zeros(max(n, 1))
-        z_exit = np.zeros(max(n, 1)) if with_depth else None
+        row_ptr, n, room = self._fill_rows(row_ptr, capacity)
+        col = np.zeros(room, dtype=np.int32)
+        dz = np.zeros(room)
+        z_exit = np.zeros(room) if with_depth else None
         self._check(self.lib.c5_ray_matrix_fill(self.handle, row_ptr.ctypes.data_as(_lp_t), n, col.ctypes.data_as(_ip_t), _dp(dz),
                                                 _dp(z_exit)))
         return (col[:n], dz[:n], z_exit[:n]) if with_depth else (col[:n], dz[:n])
@@ -775,10 +788,7 @@ class Context:
         give capacity).  Nothing beyond capacity is written; a frame that changed since ray_matrix_rows, or a capacity
         below row_ptr's total, makes the next synchronize() raise C5_ERR_STATE."""
         import torch
-        if capacity is None:
-            if col is None or isinstance(col, int):
-                raise ValueError("give capacity with raw device pointers")
-            capacity = col.shape[0]
+        capacity = self._fill_capacity(capacity, col)
         shape = (capacity,)
         ptrs = (_device_ptr(row_ptr, torch.int64, (self.local_rows * self.res_x + 1,)), _device_ptr(col, torch.int32, shape),
                 _device_ptr(dz, torch.float64, shape), _device_ptr(z_exit, torch.float64, shape))
@@ -799,13 +809,10 @@ class Context:
         cell's alpha / Q at the scalars and the alpha limit the context holds now (0 where the cell is inactive; dI_dalpha
         0 where its alpha is clamped).  Raises C5_ERR_STATE if the frame changed since ray_matrix_rows.  Synchronous;
         retries by itself.  Bit-reproducible."""
-        row_ptr = self._row_ptr(row_ptr)
-        n = int(row_ptr[-1]) if capacity is None else int(capacity)
-        if n < 0:
-            raise ValueError(f"capacity must not be negative ({n})")
-        col = np.zeros(max(n, 1), dtype=np.int32) if with_structure else None
-        dz = np.zeros(max(n, 1)) if with_structure else None
-        da, dq = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        row_ptr, n, room = self._fill_rows(row_ptr, capacity)
+        col = np.zeros(room, dtype=np.int32) if with_structure else None
+        dz = np.zeros(room) if with_structure else None
+        da, dq = np.zeros(room), np.zeros(room)
         self._check(self.lib.c5_ray_jacobian_fill(self.handle, row_ptr.ctypes.data_as(_lp_t), n,
                                                   None if col is None else col.ctypes.data_as(_ip_t), _dp(dz), _dp(da), _dp(dq)))
         return (col[:n], dz[:n], da[:n], dq[:n]) if with_structure else (da[:n], dq[:n])
@@ -821,11 +828,7 @@ class Context:
             raise ValueError("give dI_dalpha or dI_dq")
         if row_ptr is None:
             raise ValueError("give row_ptr")
-        if capacity is None:
-            first = next((t for t in (dI_dalpha, dI_dq) if t is not None), None)
-            if isinstance(first, int):
-                raise ValueError("give capacity with raw device pointers")
-            capacity = first.shape[0]
+        capacity = self._fill_capacity(capacity, dI_dalpha, dI_dq)
         if capacity < 0:
             raise ValueError(f"capacity must not be negative ({capacity})")
         shape = (capacity,)
@@ -849,13 +852,10 @@ class Context:
         entry face << 2 | 16 (the exit face contributes) | 32 (the entry face does); bary: the pixel's barycentric
         coordinates in the exit and the entry face, zeros where the face does not contribute.  Raises C5_ERR_STATE if the
         frame changed since ray_matrix_rows.  Synchronous; retries by itself.  Bit-reproducible."""
-        row_ptr = self._row_ptr(row_ptr)
-        n = int(row_ptr[-1]) if capacity is None else int(capacity)
-        if n < 0:
-            raise ValueError(f"capacity must not be negative ({n})")
-        dI = np.zeros(max(n, 1))
-        faces = np.zeros(max(n, 1), dtype=np.uint8)
-        bary = np.zeros((max(n, 1), 2, 3))
+        row_ptr, n, room = self._fill_rows(row_ptr, capacity)
+        dI = np.zeros(room)
+        faces = np.zeros(room, dtype=np.uint8)
+        bary = np.zeros((room, 2, 3))
         self._check(self.lib.c5_ray_shape_jacobian_fill(self.handle, row_ptr.ctypes.data_as(_lp_t), n, _dp(dI),
                                                         faces.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(bary)))
         return dI[:n], faces[:n], bary[:n]
@@ -871,11 +871,7 @@ class Context:
             raise ValueError("give dI_ddz, faces or bary")
         if row_ptr is None:
             raise ValueError("give row_ptr")
-        if capacity is None:
-            first = next(t for t in (dI_ddz, faces, bary) if t is not None)
-            if isinstance(first, int):
-                raise ValueError("give capacity with raw device pointers")
-            capacity = first.shape[0]
+        capacity = self._fill_capacity(capacity, dI_ddz, faces, bary)
         if capacity < 0:
             raise ValueError(f"capacity must not be negative ({capacity})")
         ptrs = (_device_ptr(row_ptr, torch.int64, (self.local_rows * self.res_x + 1,)), _device_ptr(dI_ddz, torch.float64, (capacity,)),

@@ -520,6 +520,26 @@ __device__ __forceinline__ void count_changed_rows(bool changed, unsigned* __res
     if (n && (threadIdx.x & 63) == 0) atomicAdd(changed_rows, n);
 }
 
+// A lane's way along its row: begin once; put(store) per element - store(at) where row_ptr's row and the capacity have room
+// for it, and it counts either way; finish by every lane of the wavefront, after its loop.
+struct RowCursor {
+    RowSlot slot;
+    unsigned k = 0;  // elements of the row so far
+    bool in_image = false;
+    __device__ __forceinline__ void begin(bool in_img, const int64_t* __restrict__ row_ptr, size_t lp, long long capacity) {
+        in_image = in_img;
+        if (in_img) slot = row_slot(row_ptr, lp, capacity);
+    }
+    template <class Store>
+    __device__ __forceinline__ void put(Store store) {
+        if (k < slot.n_ok) store(slot.base + k);
+        ++k;
+    }
+    __device__ __forceinline__ void finish(unsigned* __restrict__ changed_rows) const {
+        count_changed_rows(in_image && !(slot.fits && k == slot.n_ok), changed_rows);
+    }
+};
+
 }  // namespace adj
 
 // workgroups of a walk kernel: one wavefront per 8x8 pixel tile (0: no pixel)

@@ -1055,22 +1055,16 @@ __global__ __launch_bounds__(256) void vertex_tangent_resolve(ResolveParams R, c
 
 namespace adj {
 
-// The shape Jacobian's sink: a lane's row (row_slot: inside [0, capacity) whatever row_ptr holds) and its next element.
+// The shape Jacobian's sink: a lane's row (RowCursor: inside [0, capacity) whatever row_ptr holds) and what it stores there.
 struct ShapeRowStore {
     static constexpr bool kRows = true;
     ShapeRows J;
-    RowSlot slot;
-    unsigned k = 0;  // segments of the row so far
-    bool in_image = false;
+    RowCursor row;
     __device__ explicit ShapeRowStore(const ShapeRows& j) : J(j) {}
-    __device__ __forceinline__ void begin(bool in_img, size_t lp) {
-        in_image = in_img;
-        if (in_img) slot = row_slot(J.row_ptr, lp, J.capacity);
-    }
+    __device__ __forceinline__ void begin(bool in_image, size_t lp) { row.begin(in_image, J.row_ptr, lp, J.capacity); }
     // faces: bits 0-1 the exit face, 2-3 the entry face, 4 / 5: the exit / entry face contributes (found: both or neither)
     __device__ __forceinline__ void segment(int, double dI_ddz, const CellFacesBary& cf) {
-        if (k < slot.n_ok) {  // (plain stores, as store_segment's: ray_matrix_kernels.hip)
-            const long long at = slot.base + k;
+        row.put([&](long long at) {  // (plain stores, as store_segment's: ray_matrix_kernels.hip)
             if (J.dI_ddz) J.dI_ddz[at] = dI_ddz;
             if (J.faces) J.faces[at] = cf.found ? static_cast<uint8_t>(cf.out.f | (cf.in.f << 2) | 0x30) : static_cast<uint8_t>(0);
             if (J.bary) {
@@ -1082,11 +1076,10 @@ struct ShapeRowStore {
                 b[4] = cf.found ? cf.in.l1 : 0.0;
                 b[5] = cf.found ? cf.in.l2 : 0.0;
             }
-        }
-        ++k;
+        });
     }
     // by every lane of the wavefront, after its loop
-    __device__ __forceinline__ void finish() const { count_changed_rows(in_image && !(slot.fits && k == slot.n_ok), J.changed_rows); }
+    __device__ __forceinline__ void finish() const { row.finish(J.changed_rows); }
 };
 
 }  // namespace adj

@@ -56,121 +56,113 @@ int fill_without_cells(c5_context* ctx, const DerivativeView& v, const int64_t* 
     return C5_OK;
 }
 
-// The ray matrix's arrays: a per-view setup of its own, then segment_walk<2> (or segment_fill_resolve), which writes only
-// inside [0, capacity) and counts the rows that differ from row_ptr; that count travels to the host behind the status words.
-int enqueue_ray_matrix_fill(c5_context* ctx, const int64_t* row_ptr, int64_t capacity, int32_t* col, double* dz, double* z_exit) {
+// The frame of the three fills: a per-view setup of its own, the word of changed rows cleared, launch(v, changed_rows) - the
+// fill's kernels, which write only inside [0, capacity) and count the rows that differ from row_ptr; before its last walk
+// launch calls v.keep(false): the fill hands every head back cleared - and that count sent to the host behind the status
+// words.  what: the fill's name in messages ("ray matrix fill"); fill: its entry point's.
+template <class Launch>
+int enqueue_fill(c5_context* ctx, const int64_t* row_ptr, const char* what, const char* fill, Launch launch) {
     DerivativeView v;
     int rc = setup_derivative(ctx, v);
     if (rc) return rc;
-    if (v.no_cells) return fill_without_cells(ctx, v, row_ptr, "ray matrix fill", "c5_ray_matrix_fill");
+    if (v.no_cells) return fill_without_cells(ctx, v, row_ptr, what, fill);
     int32_t* count;
     unsigned* changed_rows;
     rc = ray_matrix_buffer(ctx, v, count, changed_rows);
     if (rc) return rc;
     C5_HIP(ctx, hipMemsetAsync(changed_rows, 0, sizeof(unsigned), v.s));
-    c5::RayMatrixParams m{};
-    m.w = v.w;
-    m.row_ptr = row_ptr;
-    m.capacity = capacity;
-    m.perm = v.perm;
-    m.col = col;
-    m.dz = dz;
-    m.z_exit = z_exit;
-    m.changed_rows = changed_rows;
-    if (v.bin_sort) {
-        c5::launch_segment_fill_resolve(v.s, v.r, m);
-    } else {
-        v.keep(false);  // (the fill hands every head back cleared)
-        c5::launch_segment_walk(v.s, m, 2);
-    }
-    rc = commit_derivative(ctx, v, "ray matrix fill");
+    rc = launch(v, changed_rows);
+    if (rc) return rc;
+    rc = commit_derivative(ctx, v, what);
     if (rc) return rc;
     C5_HIP(ctx, hipMemcpyAsync(ctx->deriv.adj_status + 3, changed_rows, sizeof(unsigned), hipMemcpyDeviceToHost, v.s));
     return C5_OK;
 }
 
-// The ray Jacobian's arrays: the ray matrix fill's frame around the adjoint's two passes - the Lambda pre-pass as adjoint_one
-// runs it (adjoint_walk<1>, the heads left in place), then jacobian_walk, which stores where segment_walk<2> would; or
-// jacobian_fill_resolve over bin_sort_resolve's lists.  Any array may be null.
+// The ray matrix's arrays: segment_walk<2>, or segment_fill_resolve over bin_sort_resolve's lists.
+int enqueue_ray_matrix_fill(c5_context* ctx, const int64_t* row_ptr, int64_t capacity, int32_t* col, double* dz, double* z_exit) {
+    return enqueue_fill(ctx, row_ptr, "ray matrix fill", "c5_ray_matrix_fill", [&](DerivativeView& v, unsigned* changed_rows) -> int {
+        c5::RayMatrixParams m{};
+        m.w = v.w;
+        m.row_ptr = row_ptr;
+        m.capacity = capacity;
+        m.perm = v.perm;
+        m.col = col;
+        m.dz = dz;
+        m.z_exit = z_exit;
+        m.changed_rows = changed_rows;
+        if (v.bin_sort) {
+            c5::launch_segment_fill_resolve(v.s, v.r, m);
+        } else {
+            v.keep(false);
+            c5::launch_segment_walk(v.s, m, 2);
+        }
+        return C5_OK;
+    });
+}
+
+// The ray Jacobian's arrays: the adjoint's two passes - the Lambda pre-pass as adjoint_one runs it (adjoint_walk<1>, the
+// heads left in place), then jacobian_walk, which stores where segment_walk<2> would; or jacobian_fill_resolve over
+// bin_sort_resolve's lists.  Any array may be null.
 int enqueue_ray_jacobian_fill(c5_context* ctx, const int64_t* row_ptr, int64_t capacity, int32_t* col, double* dz, double* dI_da,
                               double* dI_dq) {
-    DerivativeView v;
-    int rc = setup_derivative(ctx, v);
-    if (rc) return rc;
-    if (v.no_cells) return fill_without_cells(ctx, v, row_ptr, "ray jacobian fill", "c5_ray_jacobian_fill");
-    int32_t* count;
-    unsigned* changed_rows;
-    rc = ray_matrix_buffer(ctx, v, count, changed_rows);
-    if (rc) return rc;
-    C5_HIP(ctx, hipMemsetAsync(changed_rows, 0, sizeof(unsigned), v.s));
-    const c5::JacobianRows j{row_ptr, capacity, v.perm, col, dz, dI_da, dI_dq, changed_rows};
-    if (v.bin_sort) {
-        c5::launch_jacobian_fill_resolve(v.s, v.r, j);
-    } else {
+    return enqueue_fill(ctx, row_ptr, "ray jacobian fill", "c5_ray_jacobian_fill", [&](DerivativeView& v, unsigned* changed_rows) -> int {
+        const c5::JacobianRows j{row_ptr, capacity, v.perm, col, dz, dI_da, dI_dq, changed_rows};
+        if (v.bin_sort) {
+            c5::launch_jacobian_fill_resolve(v.s, v.r, j);
+            return C5_OK;
+        }
         c5::AdjointParams ap;
-        rc = adjoint_params(ctx, v, ap);
+        const int rc = adjoint_params(ctx, v, ap);
         if (rc) return rc;
         c5::launch_adjoint_walk(v.s, ap, 1);
-        v.keep(false);  // (the fill hands every head back cleared)
+        v.keep(false);
         c5::launch_jacobian_walk(v.s, ap, j);
-    }
-    rc = commit_derivative(ctx, v, "ray jacobian fill");
-    if (rc) return rc;
-    C5_HIP(ctx, hipMemcpyAsync(ctx->deriv.adj_status + 3, changed_rows, sizeof(unsigned), hipMemcpyDeviceToHost, v.s));
-    return C5_OK;
+        return C5_OK;
+    });
 }
 
-// what both forms of c5_ray_jacobian_fill check of their arguments
-int check_ray_jacobian(c5_context* ctx, bool host, const void* row_ptr, int64_t capacity, const void* dI_da, const void* dI_dq) {
-    int rc = check_derivative(ctx, {"c5_ray_jacobian_fill", host, 1, nullptr, row_ptr && (dI_da || dI_dq), true,
-                                    "null row_ptr, or neither dI_dalpha nor dI_dq"});
-    if (rc) return rc;
-    if (capacity < 0) return fail(ctx, C5_ERR_INVALID, "c5_ray_jacobian_fill: negative capacity (%lld)", static_cast<long long>(capacity));
-    return C5_OK;
-}
-
-// The shape Jacobian's arrays: the ray Jacobian fill's frame around the vertex adjoint's two passes - the Lambda pre-pass
-// (adjoint_walk<1>, the heads left in place), then shape_jacobian_walk, which stores where segment_walk<2> would; or
-// shape_jacobian_resolve over bin_sort_resolve's lists.  Any array may be null.
+// The shape Jacobian's arrays: the vertex adjoint's two passes - the Lambda pre-pass (adjoint_walk<1>, the heads left in
+// place), then shape_jacobian_walk, which stores where segment_walk<2> would; or shape_jacobian_resolve over
+// bin_sort_resolve's lists.  Any array may be null.
 int enqueue_shape_jacobian_fill(c5_context* ctx, const int64_t* row_ptr, int64_t capacity, double* dI_ddz, uint8_t* faces, double* bary) {
-    DerivativeView v;
-    int rc = setup_derivative(ctx, v);
-    if (rc) return rc;
-    if (v.no_cells) return fill_without_cells(ctx, v, row_ptr, "ray shape jacobian fill", "c5_ray_shape_jacobian_fill");
-    int32_t* count;
-    unsigned* changed_rows;
-    rc = ray_matrix_buffer(ctx, v, count, changed_rows);
-    if (rc) return rc;
-    C5_HIP(ctx, hipMemsetAsync(changed_rows, 0, sizeof(unsigned), v.s));
-    const c5::ShapeRows j{row_ptr, capacity, dI_ddz, faces, bary, changed_rows};
-    if (v.bin_sort) {
-        c5::launch_shape_jacobian_resolve(v.s, v.r, j);
-    } else {
+    return enqueue_fill(ctx, row_ptr, "ray shape jacobian fill", "c5_ray_shape_jacobian_fill", [&](DerivativeView& v, unsigned* changed_rows) -> int {
+        const c5::ShapeRows j{row_ptr, capacity, dI_ddz, faces, bary, changed_rows};
+        if (v.bin_sort) {
+            c5::launch_shape_jacobian_resolve(v.s, v.r, j);
+            return C5_OK;
+        }
         c5::AdjointParams ap;
-        rc = adjoint_params(ctx, v, ap);
+        const int rc = adjoint_params(ctx, v, ap);
         if (rc) return rc;
         c5::VertexParams vp{};
         vp.w = v.w;
         vp.geo = v.geo;
         vp.lambda = ap.lambda;
         c5::launch_adjoint_walk(v.s, ap, 1);
-        v.keep(false);  // (the fill hands every head back cleared)
+        v.keep(false);
         c5::launch_shape_jacobian_walk(v.s, vp, j);
-    }
-    rc = commit_derivative(ctx, v, "ray shape jacobian fill");
+        return C5_OK;
+    });
+}
+
+// What both forms of a fill check of their arguments: check_derivative's (ok: the pointers it needs are there, else
+// `missing`) and the capacity's sign.
+int check_fill(c5_context* ctx, const char* fill, bool host, bool ok, const char* missing, int64_t capacity) {
+    int rc = check_derivative(ctx, {fill, host, 1, nullptr, ok, true, missing});
     if (rc) return rc;
-    C5_HIP(ctx, hipMemcpyAsync(ctx->deriv.adj_status + 3, changed_rows, sizeof(unsigned), hipMemcpyDeviceToHost, v.s));
+    if (capacity < 0) return fail(ctx, C5_ERR_INVALID, "%s: negative capacity (%lld)", fill, static_cast<long long>(capacity));
     return C5_OK;
 }
 
-// what both forms of c5_ray_shape_jacobian_fill check of their arguments
-int check_shape_jacobian(c5_context* ctx, bool host, const void* row_ptr, int64_t capacity, const void* dI_ddz, const void* faces,
-                         const void* bary) {
-    int rc = check_derivative(ctx, {"c5_ray_shape_jacobian_fill", host, 1, nullptr, row_ptr && (dI_ddz || faces || bary), true,
-                                    "null row_ptr, or none of dI_ddz, faces and bary"});
-    if (rc) return rc;
-    if (capacity < 0)
-        return fail(ctx, C5_ERR_INVALID, "c5_ray_shape_jacobian_fill: negative capacity (%lld)", static_cast<long long>(capacity));
+// The host forms stage their arrays for row_ptr's total, which is also the capacity the kernels are given: nothing beyond
+// it is written on the device or copied back.  A total the caller's capacity does not cover is refused.
+int staged_elements(c5_context* ctx, const char* fill, const int64_t* row_ptr_host, int64_t capacity, int64_t& n_px, int64_t& need) {
+    n_px = local_pixels(ctx->im);
+    need = row_ptr_host[n_px];
+    if (need < 0 || need > capacity)
+        return fail(ctx, C5_ERR_INVALID, "%s: row_ptr asks for %lld elements, capacity is %lld", fill, static_cast<long long>(need),
+                    static_cast<long long>(capacity));
     return C5_OK;
 }
 
@@ -213,26 +205,18 @@ int c5_ray_matrix_rows(c5_context* ctx, int64_t* row_ptr_host, int64_t* nnz) {
 }
 
 int c5_ray_matrix_fill_device(c5_context* ctx, const void* row_ptr_dev, int64_t capacity, void* col_dev, void* dz_dev, void* z_exit_dev) {
-    int rc = check_derivative(ctx, {"c5_ray_matrix_fill", false, 1, nullptr, row_ptr_dev && col_dev && dz_dev, true,
-                                    "null row_ptr, col or dz pointer"});
+    int rc = check_fill(ctx, "c5_ray_matrix_fill", false, row_ptr_dev && col_dev && dz_dev, "null row_ptr, col or dz pointer", capacity);
     if (rc) return rc;
-    if (capacity < 0) return fail(ctx, C5_ERR_INVALID, "c5_ray_matrix_fill: negative capacity (%lld)", static_cast<long long>(capacity));
     return enqueue_ray_matrix_fill(ctx, static_cast<const int64_t*>(row_ptr_dev), capacity, static_cast<int32_t*>(col_dev),
                                    static_cast<double*>(dz_dev), static_cast<double*>(z_exit_dev));
 }
 
-// The arrays are staged for row_ptr's total, which is also the capacity the kernel is given: nothing beyond it is written
-// on the device or copied back.
 int c5_ray_matrix_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t capacity, int32_t* col_host, double* dz_host,
                        double* z_exit_host) {
-    int rc = check_derivative(ctx, {"c5_ray_matrix_fill", true, 1, nullptr, row_ptr_host && col_host && dz_host, true,
-                                    "null row_ptr, col or dz pointer"});
+    int64_t n_px, need;
+    int rc = check_fill(ctx, "c5_ray_matrix_fill", true, row_ptr_host && col_host && dz_host, "null row_ptr, col or dz pointer", capacity);
+    if (!rc) rc = staged_elements(ctx, "c5_ray_matrix_fill", row_ptr_host, capacity, n_px, need);
     if (rc) return rc;
-    if (capacity < 0) return fail(ctx, C5_ERR_INVALID, "c5_ray_matrix_fill: negative capacity (%lld)", static_cast<long long>(capacity));
-    const int64_t n_px = local_pixels(ctx->im), need = row_ptr_host[n_px];
-    if (need < 0 || need > capacity)
-        return fail(ctx, C5_ERR_INVALID, "c5_ray_matrix_fill: row_ptr asks for %lld elements, capacity is %lld", static_cast<long long>(need),
-                    static_cast<long long>(capacity));
     const size_t n = static_cast<size_t>(need);
     Staged b[] = {{row_ptr_host, nullptr, static_cast<size_t>(n_px + 1) * sizeof(int64_t)},
                   {nullptr, col_host, n * sizeof(int32_t)},
@@ -245,21 +229,20 @@ int c5_ray_matrix_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t cap
 
 int c5_ray_jacobian_fill_device(c5_context* ctx, const void* row_ptr_dev, int64_t capacity, void* col_dev, void* dz_dev,
                                 void* dI_dalpha_dev, void* dI_dq_dev) {
-    int rc = check_ray_jacobian(ctx, false, row_ptr_dev, capacity, dI_dalpha_dev, dI_dq_dev);
+    int rc = check_fill(ctx, "c5_ray_jacobian_fill", false, row_ptr_dev && (dI_dalpha_dev || dI_dq_dev),
+                        "null row_ptr, or neither dI_dalpha nor dI_dq", capacity);
     if (rc) return rc;
     return enqueue_ray_jacobian_fill(ctx, static_cast<const int64_t*>(row_ptr_dev), capacity, static_cast<int32_t*>(col_dev),
                                      static_cast<double*>(dz_dev), static_cast<double*>(dI_dalpha_dev), static_cast<double*>(dI_dq_dev));
 }
 
-// Staged for row_ptr's total, as c5_ray_matrix_fill: nothing beyond it is written on the device or copied back.
 int c5_ray_jacobian_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t capacity, int32_t* col_host, double* dz_host,
                          double* dI_dalpha_host, double* dI_dq_host) {
-    int rc = check_ray_jacobian(ctx, true, row_ptr_host, capacity, dI_dalpha_host, dI_dq_host);
+    int64_t n_px, need;
+    int rc = check_fill(ctx, "c5_ray_jacobian_fill", true, row_ptr_host && (dI_dalpha_host || dI_dq_host),
+                        "null row_ptr, or neither dI_dalpha nor dI_dq", capacity);
+    if (!rc) rc = staged_elements(ctx, "c5_ray_jacobian_fill", row_ptr_host, capacity, n_px, need);
     if (rc) return rc;
-    const int64_t n_px = local_pixels(ctx->im), need = row_ptr_host[n_px];
-    if (need < 0 || need > capacity)
-        return fail(ctx, C5_ERR_INVALID, "c5_ray_jacobian_fill: row_ptr asks for %lld elements, capacity is %lld",
-                    static_cast<long long>(need), static_cast<long long>(capacity));
     const size_t n = static_cast<size_t>(need);
     Staged b[] = {{row_ptr_host, nullptr, static_cast<size_t>(n_px + 1) * sizeof(int64_t)},
                   {nullptr, col_host, col_host ? n * sizeof(int32_t) : 0},
@@ -274,21 +257,20 @@ int c5_ray_jacobian_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t c
 
 int c5_ray_shape_jacobian_fill_device(c5_context* ctx, const void* row_ptr_dev, int64_t capacity, void* dI_ddz_dev, void* faces_dev,
                                       void* bary_dev) {
-    int rc = check_shape_jacobian(ctx, false, row_ptr_dev, capacity, dI_ddz_dev, faces_dev, bary_dev);
+    int rc = check_fill(ctx, "c5_ray_shape_jacobian_fill", false, row_ptr_dev && (dI_ddz_dev || faces_dev || bary_dev),
+                        "null row_ptr, or none of dI_ddz, faces and bary", capacity);
     if (rc) return rc;
     return enqueue_shape_jacobian_fill(ctx, static_cast<const int64_t*>(row_ptr_dev), capacity, static_cast<double*>(dI_ddz_dev),
                                        static_cast<uint8_t*>(faces_dev), static_cast<double*>(bary_dev));
 }
 
-// Staged for row_ptr's total, as c5_ray_matrix_fill: nothing beyond it is written on the device or copied back.
 int c5_ray_shape_jacobian_fill(c5_context* ctx, const int64_t* row_ptr_host, int64_t capacity, double* dI_ddz_host, uint8_t* faces_host,
                                double* bary_host) {
-    int rc = check_shape_jacobian(ctx, true, row_ptr_host, capacity, dI_ddz_host, faces_host, bary_host);
+    int64_t n_px, need;
+    int rc = check_fill(ctx, "c5_ray_shape_jacobian_fill", true, row_ptr_host && (dI_ddz_host || faces_host || bary_host),
+                        "null row_ptr, or none of dI_ddz, faces and bary", capacity);
+    if (!rc) rc = staged_elements(ctx, "c5_ray_shape_jacobian_fill", row_ptr_host, capacity, n_px, need);
     if (rc) return rc;
-    const int64_t n_px = local_pixels(ctx->im), need = row_ptr_host[n_px];
-    if (need < 0 || need > capacity)
-        return fail(ctx, C5_ERR_INVALID, "c5_ray_shape_jacobian_fill: row_ptr asks for %lld elements, capacity is %lld",
-                    static_cast<long long>(need), static_cast<long long>(capacity));
     const size_t n = static_cast<size_t>(need);
     Staged b[] = {{row_ptr_host, nullptr, static_cast<size_t>(n_px + 1) * sizeof(int64_t)},
                   {nullptr, dI_ddz_host, dI_ddz_host ? n * sizeof(double) : 0},

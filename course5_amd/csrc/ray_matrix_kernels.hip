@@ -4,6 +4,8 @@
 // (cell, dz, z_exit) per segment); segment_count_resolve / segment_fill_resolve over bin_sort_resolve's lists.  The walk is
 // adj::Ray's (deriv_ray.hpp), the other derivatives' chords to the bit.  Each lane owns its row and appends to it with plain
 // stores: no atomics, bit-reproducible (adj::row_slot, count_changed_rows: deriv_ray.hpp, shared with the ray Jacobian).
+// The two fills here spell out what adj::RowCursor does for the Jacobians' sinks: written with it they compile to other
+// machine code (profiles/export_refactor.md), and what they do is to stay what was measured.
 #include "deriv_lists.hpp"
 
 namespace c5 {

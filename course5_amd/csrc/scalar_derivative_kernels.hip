@@ -171,17 +171,14 @@ struct ExactScatter {
 
 // The ray Jacobian's sink: nothing is summed.  The bodies run with the upstream image (0, 1) at every pixel, so a step's
 // (ga, gq) ARE the segment's (d I / d alpha, d I / d Q) - the doubles the adjoint adds for a one-hot upstream image - and
-// each lane appends them, with the chord, to its own pixel's row (row_slot: inside [0, capacity) whatever row_ptr holds).
+// each lane appends them, with the chord, to its own pixel's row (RowCursor: inside [0, capacity) whatever row_ptr holds).
 // No lane needs another: with this sink the bodies' loops are per lane, and a lane leaves when its ray ends.
 struct RowStore {
     JacobianRows J;
-    RowSlot slot;
-    unsigned k = 0;  // segments of the row so far
+    RowCursor row;
     double chord_dz = 0.0;
     __device__ explicit RowStore(const JacobianRows& j) : J(j) {}
-    __device__ __forceinline__ void begin(bool in_image, size_t lp) {
-        if (in_image) slot = row_slot(J.row_ptr, lp, J.capacity);
-    }
+    __device__ __forceinline__ void begin(bool in_image, size_t lp) { row.begin(in_image, J.row_ptr, lp, J.capacity); }
     __device__ __forceinline__ void first(int) {}
     __device__ __forceinline__ void next(int) {}
     __device__ __forceinline__ void advance() {}
@@ -189,19 +186,15 @@ struct RowStore {
     __device__ __forceinline__ void chord(double dz) { chord_dz = dz; }
     __device__ __forceinline__ void operator()(bool emit, int cell, double ga, double gq) {
         if (!emit) return;
-        if (k < slot.n_ok) {  // (plain stores, as store_segment's: ray_matrix_kernels.hip)
-            const long long at = slot.base + k;
+        row.put([&](long long at) {  // (plain stores, as store_segment's: ray_matrix_kernels.hip)
             if (J.col) J.col[at] = J.perm ? J.perm[cell] : cell;
             if (J.dz) J.dz[at] = chord_dz;
             if (J.dI_da) J.dI_da[at] = ga;
             if (J.dI_dq) J.dI_dq[at] = gq;
-        }
-        ++k;
+        });
     }
     // by every lane of the wavefront, after its loop
-    __device__ __forceinline__ void end(bool in_image) const {
-        count_changed_rows(in_image && !(slot.fits && k == slot.n_ok), J.changed_rows);
-    }
+    __device__ __forceinline__ void end() const { row.finish(J.changed_rows); }
 };
 
 // Pass 1 (Lambda per pixel) and pass 2 (the scatter) of the adjoint; SQUARED: pass 2 with the segment's terms squared
@@ -281,7 +274,7 @@ __device__ __forceinline__ void adjoint_walk_body(const AdjointParams& A, Scatte
         if (r.in_image) A.lambda[r.lp] = lam;
         ray_count(r, P);
     } else {
-        if constexpr (kRows) sc.end(r.in_image);
+        if constexpr (kRows) sc.end();
         if (!sc.keep_heads()) ray_clear_head(r, P);
     }
 }
@@ -333,7 +326,7 @@ __device__ __forceinline__ void adjoint_resolve_body(const ResolveParams& R, con
         }
         sc(emit, c, ga, gq);
     }
-    if constexpr (kRows) sc.end(f.in_image);
+    if constexpr (kRows) sc.end();
 }
 
 }  // namespace adj

@@ -337,6 +337,45 @@ def test_a_scene_of_solids_only_has_empty_rows():
     assert row_ptr.shape == (61 * 43 + 1,) and not row_ptr.any() and len(col) == len(dz) == len(z) == 0
 
 
+def test_the_three_fills_on_a_grid_without_cells():
+    """upload_grid with no cell, one solid tetrahedron, 8 x 8: every row is empty, the three fills (c5_ray_matrix_fill,
+    c5_ray_jacobian_fill, c5_ray_shape_jacobian_fill) return empty arrays and their device forms write nothing; a row_ptr
+    with segments - a five-tetrahedron cube's at the same image - is another frame's, and the context renders on."""
+    import torch
+    corners = np.array([[x, y, z] for x in (0.0, 1.0) for y in (0.0, 1.0) for z in (0.0, 1.0)]) + (0.5, -0.5, -0.5)  # id = 4x+2y+z
+    cube = mg.orient_positive(corners, np.array([[4, 0, 6, 5], [2, 0, 6, 3], [1, 0, 5, 3], [7, 6, 5, 3], [0, 6, 5, 3]], np.int32))
+    with _ctx(corners, cube, *mg.scalars(5), VIEW, 8, 8) as ctx:
+        stale = ctx.ray_matrix_rows()
+    assert stale[-1] > 0
+    solid = np.array([[0.7, -0.3, -0.3, 1.3, -0.3, -0.3, 0.7, 0.3, -0.3, 0.7, -0.3, 0.3]])
+    with _ctx(corners[:4], np.zeros((0, 4), np.int32), np.zeros(0), np.zeros(0), VIEW, 8, 8) as ctx:
+        ctx.set_solid(0, solid, 0.5)
+        before = ctx.render()
+        row_ptr = ctx.ray_matrix_rows()
+        assert row_ptr.shape == (65,) and not row_ptr.any()
+        host = (ctx.ray_matrix_fill(row_ptr, with_depth=True), ctx.ray_jacobian_fill(row_ptr), ctx.ray_shape_jacobian_fill(row_ptr))
+        assert [len(out) for out in host] == [3, 4, 3] and all(len(a) == 0 for out in host for a in out)
+        # the device forms: buffers of 16 full of a sentinel stay as they are
+        d_rp = torch.zeros(65, dtype=torch.int64, device="cuda")
+        i32, f64, u8, f64x6 = (torch.full(shape, 7, dtype=dtype, device="cuda") for shape, dtype in
+                               (((16,), torch.int32), ((4, 16), torch.float64), ((16,), torch.uint8), ((16, 2, 3), torch.float64)))
+        torch.cuda.synchronize()
+        assert ctx.ray_matrix_rows_device(d_rp) == 0 and not d_rp.any()
+        ctx.ray_matrix_fill_device(d_rp, i32, f64[0], f64[1])
+        ctx.ray_jacobian_fill_device(d_rp, i32, f64[0], f64[2], f64[3])
+        ctx.ray_shape_jacobian_device(d_rp, f64[1], u8, f64x6)
+        assert ctx.synchronize() == capi.C5_OK
+        assert all(bool((t == 7).all()) for t in (i32, f64, u8, f64x6))
+        # a row_ptr that holds segments is another frame's
+        for fill in (ctx.ray_matrix_fill, ctx.ray_jacobian_fill, ctx.ray_shape_jacobian_fill):
+            with pytest.raises(capi.C5Error) as e:
+                fill(stale)
+            assert e.value.code == capi.C5_ERR_STATE and "the scene has no cells" in e.value.message, fill.__name__
+        after = ctx.render()
+        assert not ctx.ray_matrix_rows().any()
+    assert np.array_equal(before.view(np.uint32), after.view(np.uint32)) and (before[..., 0] == 0.5).any()
+
+
 def test_the_host_forms_retry_by_themselves_when_the_entry_pool_grows():
     import torch
     kind = "ball12_150x112:1"

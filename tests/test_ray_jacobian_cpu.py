@@ -251,3 +251,86 @@ def test_array_built_operators_have_no_second_derivatives_and_check_their_shapes
         fit.JacobianOperators(t(scene["row_ptr"]), t(C.astype(np.int32)), t(dz[:-1]), t(da), t(dq), scene["n"])
     with pytest.raises(ValueError, match="weight"):
         fit.JacobianOperators(t(scene["row_ptr"]), t(C.astype(np.int32)), t(dz), t(da), t(dq), scene["n"], torch.zeros(3, 2))
+
+
+# ---- the operators bit for bit: every product is the gather, the multiply and the segmented sum written out ---------------
+
+def _small(kind):
+    """(row_ptr, col, n_cells, n_px) of a matrix whose offsets are the awkward ones: `empty` has no nonzero at all; `gaps` an
+    empty first row, an empty last row, an empty row between, and columns (0, 3 and the last) no row names."""
+    if kind == "empty":
+        return np.zeros(5, np.int64), np.zeros(0, np.int32), 3, 4
+    return np.array([0, 0, 2, 2, 5, 6, 6], np.int64), np.array([4, 1, 2, 5, 1, 4], np.int32), 7, 6
+
+
+def _written_out_cases(scene):
+    P, C, dz, da, dq = scene["terms"]
+    yield "scene", scene["row_ptr"], C.astype(np.int32), scene["n"], (dz, da, dq), scene["w"]
+    rng = np.random.default_rng(5)
+    for kind in ("empty", "gaps"):
+        row_ptr, col, n, n_px = _small(kind)
+        yield kind, row_ptr, col, n, tuple(rng.normal(size=len(col)) for _ in range(3)), rng.uniform(0.0, 2.0, (n_px, 2)).astype(np.float32)
+
+
+def test_every_product_is_the_segmented_sum_written_out_bit_for_bit(scene):
+    from tests import operators_written_out as wo
+    t = torch.from_numpy
+    for kind, row_ptr, col, n, values, w in _written_out_cases(scene):
+        n_px = len(row_ptr) - 1
+        dz, da, dq = (t(v) for v in values)
+        m = wo.ByRowAndColumn(row_ptr, col, n)
+        rng = np.random.default_rng(6)
+        va, vq = t(rng.normal(size=n)), t(rng.normal(size=n))
+        r = rng.normal(size=(n_px, 2)).astype(np.float32)
+        zero = torch.zeros(n_px, dtype=torch.float64)
+        for weight in (None, w):
+            ops = fit.JacobianOperators(t(row_ptr), t(col), dz, da, dq, n, None if weight is None else t(weight))
+            jt = lambda g_tau, g_I: (m.to_columns(dz, g_tau) + m.to_columns(da, g_I), m.to_columns(dq, g_I))  # noqa: E731
+            for a, b in ((va, vq), (va, None), (None, vq)):
+                tau = zero if a is None else m.to_rows(dz, a)
+                I = zero.clone()
+                if a is not None:
+                    I = I + m.to_rows(da, a)
+                if b is not None:
+                    I = I + m.to_rows(dq, b)
+                got = ops.jv(a, b)
+                assert torch.equal(got[0], tau) and torch.equal(got[1], I), (kind, "jv")
+                w_tau, w_I = wo.weights(weight, n_px)
+                want = jt(tau if weight is None else w_tau * tau, I if weight is None else w_I * I)
+                got = ops.product(a, b)
+                assert got[0].shape == (n,) and torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), (kind, "product")
+            g_tau, g_I = t(rng.normal(size=n_px)), t(rng.normal(size=n_px))
+            got, want = ops.jt(g_tau, g_I), jt(g_tau, g_I)
+            assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), (kind, "jt")
+            got, want = ops.rhs(t(r)), jt(*wo.weighted_image(r, weight))
+            assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), (kind, "rhs")
+            w_tau, w_I = wo.weights(weight, n_px)
+            got = ops.diagonal()
+            assert torch.equal(got[0], m.to_columns(dz * dz, w_tau) + m.to_columns(da * da, w_I)), (kind, "diag_alpha")
+            assert torch.equal(got[1], m.to_columns(dq * dq, w_I)), (kind, "diag_q")
+            if kind == "gaps":  # the rows and columns nothing names are exact zeros, the others are not
+                named = torch.zeros(n, dtype=torch.bool)
+                named[t(col).long()] = True
+                assert not got[1][~named].any() and (got[1][named] > 0).all()
+                assert not ops.jv(va, vq)[1][[0, 2, 5]].any()
+
+
+def test_the_messages_of_the_four_checks(scene):
+    P, C, dz, da, dq = scene["terms"]
+    t = torch.from_numpy
+    row_ptr, col, n, n_px = t(scene["row_ptr"]), t(C.astype(np.int32)), scene["n"], scene["n_px"]
+    nnz = len(C)
+    with pytest.raises(ValueError, match=re.escape(f"col, dz, dI_dalpha and dI_dq must hold row_ptr's {nnz} elements each")):
+        fit.JacobianOperators(row_ptr, col, t(dz), t(da[:-1]), t(dq), n)
+    with pytest.raises(ValueError, match=re.escape(f"col, dz, dI_dalpha and dI_dq must hold row_ptr's {nnz} elements each")):
+        fit.JacobianOperators(row_ptr, col[:-1], t(dz), t(da), t(dq), n)
+    with pytest.raises(ValueError, match=re.escape(f"col must name cells 0 .. {int(C.max()) - 1}")):
+        fit.JacobianOperators(row_ptr, col, t(dz), t(da), t(dq), int(C.max()))
+    bad = col.clone()
+    bad[0] = -1
+    with pytest.raises(ValueError, match=re.escape(f"col must name cells 0 .. {n - 1}")):
+        fit.JacobianOperators(row_ptr, bad, t(dz), t(da), t(dq), n)
+    with pytest.raises(ValueError, match=re.escape(f"weight must hold two values for each of the {n_px} pixels")):
+        fit.JacobianOperators(row_ptr, col, t(dz), t(da), t(dq), n, torch.zeros(n_px + 1, 2))
+    with pytest.raises(ValueError, match=re.escape(f"residual must hold two values for each of the {n_px} pixels")):
+        _operators(scene, None).rhs(torch.zeros(n_px - 1, 2))
